@@ -17,7 +17,7 @@ which); "parts" is reported, never the headline.  Per-GPU work is fixed => weak 
 the BASELINE configs[3] shape -- 16384x16384 as 256 tiles of 1024x1024 split over the ranks, strong
 scaling.  `python bench.py --gpus N` starts its N ranks itself (launch_ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|cfg2|cfg1|cfg3|cfg4tile]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|cfg2|cfg1|cfg3|cfg4tile] [--dump-outputs DIR]
 """
 import argparse
 import ctypes as C
@@ -431,28 +431,6 @@ def cfg5_sequence(ctx, dev, p5, table, d_c, ref5, S, flights):
     return res
 
 
-def cfg5_sequence_child(fcs, fref, S, device):
-    """`bench.py --cfg5-sequence <codestream> <reference pixels .npy> <S> <device>`: the child process of the cfg5 leg (started with
-    GPU_MAX_HW_QUEUES=8 in its environment); prints one JSON object."""
-    import j2kparse as J
-    with open(fcs, "rb") as fh:
-        cs5 = fh.read()
-    ref5 = np.load(fref)
-    dev = torch.device("cuda", device)
-    torch.cuda.set_device(dev)
-    info = J.parse(cs5)
-    p5 = G.TileParams.make(S, S, 3, 12, info["levels"], irreversible=True, mct=True, part1=True)
-    blocks, _ = G.tile_layout(p5)
-    rows, data = J.decode_table(info, blocks, True)
-    table = np.array(rows, dtype=G.capi.CODED_DTYPE)
-    ctx = G.Context(device)
-    ctx.set_decode_qcd([(e << 11) | m for e, m in info["qcd"]])
-    d_c = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
-    res = cfg5_sequence(ctx, dev, p5, table, d_c, ref5, S, (2, 4, 8))
-    res["hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES")
-    print(json.dumps(res))
-
-
 def extra_workloads(ctx, dev, stream, steps, cfg5, cpu_md5s=None):
     """The other BASELINE configurations on the same GPU, a few steps each: cfg2, cfg3 with its
     9/7 DWT family against the HBM roofline (north_star's >= 40 % target), the cfg4 tiling and the whole cfg4 image (256
@@ -552,29 +530,10 @@ def extra_workloads(ctx, dev, stream, steps, cfg5, cpu_md5s=None):
             ctx.enable_timing(False)
             # a SEQUENCE of such frames through the one context, several in flight (grk_amd_set_decode_pipelining): the later frames'
             # lane waves and long chains run beside the first's -- chain-bound kernels leave most of the machine's issue slots free.
-            # Two, four and eight in flight here (r06: a frame's block decoding is ONE launch on one stream), on the HIP runtime's default 4 hardware queues and beside every other stream this process
-            # has made (streams that share a queue run in turn); the same in a child process of this one started with
-            # GPU_MAX_HW_QUEUES=8 -- process-wide, read at the runtime's start, and a setting the encode-over-RCCL path does not
-            # like, so it is the host's to make (profiles/r04_hw_queues.txt)
+            # Two, four and eight in flight here (r06: a frame's block decoding is ONE launch on one stream), on the HIP runtime's default
+            # hardware queues and beside every other stream this process has made (streams that share a queue run in turn)
             seq5 = cfg5_sequence(ctx, dev, p5, table, d_c, ref5, S, (2, 4, 8))
-            seq5["hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "4 (runtime default)")
-            try:
-                import subprocess
-                import tempfile
-                with tempfile.TemporaryDirectory() as td:
-                    fcs, fref = os.path.join(td, "cfg5.j2k"), os.path.join(td, "cfg5_ref.npy")
-                    with open(fcs, "wb") as fh:
-                        fh.write(cs5)
-                    np.save(fref, ref5)
-                    env = dict(os.environ, GPU_MAX_HW_QUEUES="8")
-                    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "GROK_AMD_FORCE_DIST"):
-                        env.pop(k, None)
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cfg5-sequence", fcs, fref, str(S), str(dev.index or 0)],
-                                       env=env, capture_output=True, text=True, timeout=300)
-                    seq5["child_process_GPU_MAX_HW_QUEUES_8"] = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 else \
-                        {"error": (r.stderr or r.stdout)[-300:]}
-            except Exception as e:      # noqa: BLE001
-                seq5["child_process_GPU_MAX_HW_QUEUES_8"] = {"error": str(e)}
+            seq5["hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "runtime default")
             samples = 3.0 * S * S
             out["cfg5"] = {"workload": "8192x8192x3 12-bit decode, Part-1 EBCOT + ICT + 9/7 stream written by grk_compress (BASELINE configs[4])",
                            "ms_per_step": round(ms, 3), "value": round(S * S / ms / 1e3, 1), "unit": "Mpixels/s", "dtype": "f32",
@@ -838,6 +797,10 @@ def launch_ranks(n, dry_run):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % n,
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
+    if dry_run:
+        # no process of a dry run opens the GPU: the launcher's torch.cuda.is_available() counts devices without the HIP runtime
+        # (none visible), and the ranks' barriers are gloo's own (dry_run)
+        env.update(PYTORCH_NVML_BASED_CUDA_CHECK="1", HIP_VISIBLE_DEVICES="")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC: RCCL across processes needs it on this driver
     env.setdefault("OMP_NUM_THREADS", "1")
     sys.stdout.flush()
@@ -890,17 +853,18 @@ def _emit(o):
 
 
 def dry_run(world, rank, args):
-    """The launch path without kernels: the ranks form a gloo group, meet at the barrier and count each other."""
+    """The launch path without kernels: the ranks form a gloo group, meet at the barrier and count each other.  (gloo's
+    monitored_barrier: dist.barrier() asks for the machine's accelerator first, which initialises the HIP runtime.)"""
     arrived = 1
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo", rank=rank, world_size=world)
-        dist.barrier()
+        dist.monitored_barrier()
         t = torch.ones(1, dtype=torch.int64)
         dist.all_reduce(t)
         arrived = int(t.item())
         n_group = dist.get_world_size()
-        dist.barrier()
+        dist.monitored_barrier()
     else:
         n_group = 1
     line = {"metric": "encode Mpixels/s (whole node), 8K RGB HTJ2K lossless", "value": None, "unit": "Mpixels/s",
@@ -920,6 +884,36 @@ def dry_run(world, rank, args):
     if rank == 0:
         print(json.dumps(line), flush=True)
     return 0
+
+
+DUMP_SEED = 20240601
+DUMP_MAX_SAMPLES = 8 << 20              # float32 coded-byte samples: 32 MB, well inside the 64 MB the dump may take
+
+
+def dump_outputs(ctx, nblocks, out_dir):
+    """--dump-outputs DIR: what the caller of the timed path receives for its last step -- the block table and the coded bytes --
+    as .npy files, so that two builds can be compared output for output.  Everything is in BLOCK order: where a block's bytes
+    land in the arena depends on which workgroup allocated first, so the offsets are left out and the bytes are read as the blocks'
+    bytes one after the other.  At 8K those are ~100 MB: a fixed, seeded sample of DUMP_MAX_SAMPLES positions (sorted) stands for
+    them when they are more.  Returns {name: number of elements}."""
+    table, total = ctx.fetch_table(nblocks)
+    coded = ctx.fetch_coded(total)
+    lens = table["length"].astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    n = int(starts[-1])
+    if n <= DUMP_MAX_SAMPLES:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_SAMPLES))
+    blk = np.searchsorted(starts, pos, side="right") - 1
+    src = table["offset"][blk].astype(np.int64) + (pos - starts[blk])
+    arrays = {"block_length": lens.astype(np.float64),
+              "block_missing_msbs": table["missing_msbs"].astype(np.float64),
+              "coded_bytes_block_order": coded[src].astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.size) for name, a in arrays.items()}
 
 
 def main():
@@ -957,15 +951,15 @@ def main():
                     help="exit code of every rank when the gather watchdog fires (the line is printed first, with the counts figures)")
     ap.add_argument("--dry-run-stall", type=int, default=-1,
                     help="with --dry-run: after the barrier this rank never joins the next collective -- the gather watchdog's path")
-    ap.add_argument("--cfg5-sequence", nargs=4, metavar=("CODESTREAM", "REF_NPY", "S", "DEVICE"), default=None,
-                    help="(internal) child process of the cfg5 leg: the Part-1 stream as a sequence with 2, 3 and 6 frames in flight")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: the ranks meet over gloo, count each other at the barrier and rank 0 prints "
                          "a line with n_gpus = the ranks that really arrived; no kernels run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last one computed (block table and coded bytes, block order) "
+                         "to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
-    if args.cfg5_sequence:
-        fcs, fref, S5, dv = args.cfg5_sequence
-        return cfg5_sequence_child(fcs, fref, int(S5), int(dv))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` starts its N ranks ITSELF (the reference's analogue is its in-process tile pool,
     # codestream/CodeStreamCompress.cpp:535-603: one command, all workers); under a launcher (WORLD_SIZE set) it is one rank
@@ -1163,6 +1157,8 @@ def main():
         dt_r, last_parts, last_root = run_frames(params, ntiles, rot, nblocks, exchange, args.steps, args.warmup)
         regions.append(dt_r)
     dt = sorted(regions)[len(regions) // 2]
+    # (the context's current buffer set is the last timed step's until the next encode: read it before anything else runs)
+    dumped = dump_outputs(ctx, nblocks, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     dt_single, _, _ = run_frames(params, ntiles, d_px, nblocks, exchange, args.steps, args.warmup)
     multi_gpu = None
     cs_len = 0
@@ -1491,6 +1487,8 @@ def main():
         }
         if use_dist:
             out["multi_gpu"] = multi_gpu
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
         cfg5 = None
         if not args.no_cpu_baseline and world == 1:
             # rank 0 at N = 1 only (at N > 1 the other ranks would wait in the final barrier for it, and the N = 1 line of the same

@@ -235,8 +235,8 @@ int grk_amd_decode_status(grk_amd_ctx* ctx);
  * Streams and hardware queues: the HIP runtime puts a process's streams on (by default) 4 hardware queues per priority level
  * and kernels that share a queue run in turn; the internal sets therefore use two streams each, and for Part-1 frames (two
  * long kernels per frame) streams of both priority levels in turn (8192x8192x3 12-bit: 15.0 ms one frame at a time, 9.1 with
- * two in flight, 7.2 with six).  A host that decodes such sequences gains a little more from GPU_MAX_HW_QUEUES=8 in its
- * environment before its first HIP call (6.2-6.8 with six); the library leaves the variable alone: it is process-wide, and the
+ * two in flight, 7.2 with six).  A host that decodes such sequences gains a little more from eight hardware queues
+ * (GPU_MAX_HW_QUEUES in its environment before its first HIP call) (6.2-6.8 with six); the library leaves the variable alone: it is process-wide, and the
  * encode pipeline beside an RCCL exchange measured 25 % slower on anything but the default. */
 int grk_amd_set_decode_pipelining(grk_amd_ctx* ctx, int frames_in_flight);
 /* Buffer lifetime in a decode sequence.  With n frames in flight a call's device buffers -- the coded bytes it reads, the pixels

@@ -101,3 +101,49 @@ def test_gather_watchdog_at_world_8_with_a_stalled_rank():
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["exchange"]["counts"] == {"ranks": 8}
     assert "did not complete within 6 s" in line["exchange"]["gather"]["error"]
+
+
+class _FakeCtx:
+    """fetch_table / fetch_coded of a context whose last encode left 4 blocks in the arena in another order than the table's"""
+
+    def __init__(self):
+        import numpy as np
+        self.lens = np.array([3, 0, 5, 2], np.uint32)
+        self.offs = np.array([7, 0, 0, 5], np.uint64)       # block 2 first in the arena, then 3, then 0 (block 1 is empty)
+        self.arena = np.arange(100, 110, dtype=np.uint8)
+
+    def fetch_table(self, nblocks):
+        import numpy as np
+        import grok_amd.capi as capi
+        assert nblocks == 4
+        t = np.zeros(4, capi.CODED_DTYPE)
+        t["offset"], t["length"], t["missing_msbs"] = self.offs, self.lens, [1, 2, 3, 4]
+        return t, self.arena.size
+
+    def fetch_coded(self, n):
+        return self.arena[:n].copy()
+
+
+def test_dump_outputs_block_order_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs: block table and coded bytes in BLOCK order (arena placement left out), float .npy files; a byte stream
+    longer than the cap is a sorted sample of positions drawn from the fixed seed, the same in every run."""
+    import numpy as np
+    B = _bench()
+    got = B.dump_outputs(_FakeCtx(), 4, str(tmp_path / "d"))
+    assert got == {"block_length": 4, "block_missing_msbs": 4, "coded_bytes_block_order": 10}
+    ln = np.load(tmp_path / "d" / "block_length.npy")
+    cb = np.load(tmp_path / "d" / "coded_bytes_block_order.npy")
+    assert ln.dtype == np.float64 and cb.dtype == np.float32
+    assert ln.tolist() == [3, 0, 5, 2] and np.load(tmp_path / "d" / "block_missing_msbs.npy").tolist() == [1, 2, 3, 4]
+    assert cb.tolist() == [107, 108, 109, 100, 101, 102, 103, 104, 105, 106]
+    monkeypatch.setattr(B, "DUMP_MAX_SAMPLES", 6)
+    for d in ("s1", "s2"):
+        assert B.dump_outputs(_FakeCtx(), 4, str(tmp_path / d))["coded_bytes_block_order"] == 6
+    s1, s2 = (np.load(tmp_path / d / "coded_bytes_block_order.npy") for d in ("s1", "s2"))
+    assert np.array_equal(s1, s2)
+    assert np.array_equal(s1, cb[np.sort(np.random.default_rng(B.DUMP_SEED).integers(0, 10, 6))])
+
+
+def test_steps_below_one_is_refused():
+    r = _run_bench("--dry-run", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -98,9 +98,10 @@ def _worker(rank, world, port, q, W, H, TW, TH, L, frames, tmpfile, depth=1, lag
     for k, t in enumerate(mine):
         os.pwrite(fd, G.write_tile_part(p, t, table[k * bpt:(k + 1) * bpt], cbytes, flags=flags), int(starts[t]))
     os.close(fd)
-    dist.barrier()
+    # (gloo's own barrier: dist.barrier() asks for the machine's accelerator first, and on a GPU box that opens the GPU in every rank)
+    dist.monitored_barrier()
     q.put((rank, files))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

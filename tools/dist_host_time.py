@@ -1,5 +1,5 @@
 """The per-frame exchange step at world size 1 over RCCL (dev tool, GPU box): host time to submit a frame vs the period, by the
-pieces of the step -- which piece costs what under GPU_MAX_HW_QUEUES=4 / 8.  python tools/dist_host_time.py"""
+pieces of the step -- which piece costs what.  python tools/dist_host_time.py"""
 import os, sys, time, socket
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,0 +1,241 @@
+// grok_amd/csrc/context.h -- the context behind include/grok_amd.h and the helpers its sources share (private to the library).
+// One grk_amd_ctx per process per GPU.  All device memory is owned by the context and grows monotonically (288 GB of HBM3E:
+// an 8K x 8K x 3 tile needs ~3.6 GB of working planes, a batch of 256 1024^2 tiles ~12 GB), so steady-state encode calls
+// perform no allocation and enqueue nothing but kernels on one HIP stream.
+#pragma once
+#include "../../include/grok_amd.h"
+#include "geometry.h"
+#include "kernels.h"
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include <algorithm>
+#include <cmath>
+#include <atomic>
+#include <thread>
+
+using namespace grk_amd;
+
+#pragma GCC visibility push(hidden)       // nothing declared below is part of the library's interface
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t n)
+    {
+        if (n <= cap) return hipSuccess;
+        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
+        size_t want = n + (n >> 3) + 4096;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = want;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+struct Timer {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    double total_ms = 0; uint32_t launches = 0;
+};
+
+// Pinned staging for the host-pointer entry points (pixels in, coded bytes / pixels out).  A buffer that IS pinned
+// (grk_amd_host_alloc, hipHostMalloc, a pinned torch tensor) goes over the link as it lies -- one DMA at the link's rate.
+// Pageable memory is moved through context-owned pinned chunks by kLanes copy threads, each double-buffered on its own
+// stream (a memcpy into / out of one chunk while the other chunk's DMA runs): the threads' memcpy rate adds up, where one
+// thread -- what a plain hipMemcpy of pageable memory amounts to -- is the limit otherwise.
+struct HostStage {
+    static constexpr size_t kChunk = 8u << 20;
+    static constexpr int kLanes = 4;
+    void* buf[kLanes][2] = {};
+    hipEvent_t ev[kLanes][2] = {};
+    hipEvent_t ev_in = nullptr, ev_out[kLanes] = {};
+    hipStream_t st[kLanes] = {};
+    bool ready = false;
+    hipError_t ensure()
+    {
+        if (ready) return hipSuccess;
+        hipError_t e = hipEventCreateWithFlags(&ev_in, hipEventDisableTiming);
+        for (int t = 0; t < kLanes && e == hipSuccess; ++t) {
+            e = hipStreamCreateWithFlags(&st[t], hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_out[t], hipEventDisableTiming);
+            for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+                e = hipHostMalloc(&buf[t][k], kChunk, hipHostMallocDefault);
+                if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[t][k], hipEventDisableTiming);
+            }
+        }
+        ready = e == hipSuccess;
+        return e;
+    }
+    void release()
+    {
+        for (int t = 0; t < kLanes; ++t) {
+            if (st[t]) { (void)hipStreamSynchronize(st[t]); (void)hipStreamDestroy(st[t]); st[t] = nullptr; }
+            if (ev_out[t]) { (void)hipEventDestroy(ev_out[t]); ev_out[t] = nullptr; }
+            for (int k = 0; k < 2; ++k) {
+                if (buf[t][k]) { (void)hipHostFree(buf[t][k]); buf[t][k] = nullptr; }
+                if (ev[t][k]) { (void)hipEventDestroy(ev[t][k]); ev[t][k] = nullptr; }
+            }
+        }
+        if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
+        ready = false;
+    }
+};
+
+struct grk_amd_ctx {
+    int device = 0;
+    int verbose = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::string err;
+    // working set
+    DevBuf pixels, p0, p1, llA, llB, blockdesc, lengths, offsets, arena, flag;
+    DevBuf dec_desc, dec_table, dec_quads, dec_mslen, dec_coded, dec_pixels, dec_work;
+    // geometry cache
+    grk_amd_tile_params gp{};
+    bool have_geom = false;
+    TileGeom geom;
+    std::vector<HtBlockDesc> h_desc, h_desc_dec;
+    std::vector<uint16_t> dec_qcd;                          // decode: QCD words of a foreign stream (optional)
+    std::vector<float> dec_steps;                           // decode: band step sizes as the host holds them (optional), [comp][band]
+    std::vector<uint32_t> dec_seg_first;                    // Part-1 decode: codeword segments (optional), [nblocks + 1]
+    std::vector<grk_amd_segment> dec_segs;
+    DevBuf dec_seg_dev;
+    HtClass ht_classes[kHtMaxClasses]; uint32_t ht_num_classes = 0;   // block classes of K3: {top resolution, rest} x {LDS small, large}
+    uint8_t ht_class_top[kHtMaxClasses] = {}, ht_class_big[kHtMaxClasses] = {};
+    int seq_index = -1;               // >= 0: one of a decode sequence's internal contexts (grk_amd_set_decode_pipelining)
+    int seq_flavour = 0;              // ... whose two streams are made for 0: HT frames, 1: Part-1 frames (sequence_streams)
+    hipStream_t side2 = nullptr; hipEvent_t ev_side2 = nullptr;      // the large-LDS classes run beside the small-LDS ones
+    hipStream_t side = nullptr;                             // K3 of the top resolution runs here beside DWT levels >= 1
+    hipEvent_t ev_level0 = nullptr, ev_side = nullptr;
+    bool overlap = false;
+    // Pipelining of consecutive encodes (grk_amd_set_pipelining): a second set of per-encode buffers, so that the next
+    // encode's DWT can start while the side streams still code the blocks of this one
+    static constexpr int kMaxAltSets = 7;
+    struct AltSet { DevBuf p1, arena, lengths, offsets, flag, ovf, llA, llB; hipEvent_t ev_side = nullptr, ev_side2 = nullptr; } alts[kMaxAltSets];
+    int alt_head = 0;                // the OLDEST of the sets not in use (a ring: the set a call retires becomes the newest)
+    int pipe_depth = 2;              // buffer sets in rotation when pipelining: grk_amd_set_pipelining(ctx, n) -> n + 1 of them (2 ..
+                                     // 8): the results of a call then stay valid until the (n + 1)-th next call
+    DevBuf ovf;                      // K3: blocks handed to the fallback launch (kernels.h: HtArgs::ovf_list)
+    bool lds_cap = true;             // K3 with capped LDS buffers + fallback launch (GRK_AMD_LDS_CAP=0: worst-case buffers)
+    bool pipelining = false;
+    hipEvent_t ev_main = nullptr;
+    bool side_pending = false;       // side-stream work of the latest encode has not been joined on the main stream yet
+    bool dec_planes16 = true;                               // 16-bit planes between K5b and K6 for 8-bit reversible HT tiles
+                                                            // (GRK_AMD_DEC_PLANES16=0 / grk_amd_set_decode_planes16: int32)
+    int dwt_pk = 1;                                         // packed int16 pairs in K2 / K6 where the range allows (GRK_AMD_DWT_PK=0: 32-bit)
+    int dwt_xcd = 1;                                        // XCD-aware workgroup order in K2 / K6 (GRK_AMD_DWT_XCD=0: plain)
+    bool fuse_egress = true;                                // K7 inside the last inverse DWT level (GRK_AMD_FUSE_EGRESS=0: separate)
+    bool planes16 = true;                                   // int16 planes between K2 and K3 where the range allows (GRK_AMD_PLANES16=0: never)
+    DevBuf ht_sel;
+    DevBuf energy;                   // grk_amd_block_distortion: sum of q^2 per block
+    // Tier-2 on the device (grk_amd_assemble_device): the packets of the geometry in the order last asked for, scratch, and the
+    // finished tile-parts
+    struct T2State {
+        bool valid = false; grk_amd_tile_params p{}; uint32_t order = 0;
+        T2Plan plan; uint32_t max_blocks = 0;
+        DevBuf packets, pob;
+    } t2;
+    DevBuf t2_u, t2_h, t2_rel, t2_pkhdr, t2_pkbody, t2_pkdst, t2_lit, t2_litlen, t2_index;      // scratch: ONE stream at a time uses it
+    // the finished tile-parts, their places and lengths ([tile]: uint64 / uint32) and {bytes assembled by the call, end of the output};
+    // the asynchronous form rotates as many of these as the encoder rotates buffer sets, so that a frame's tile-parts stay where they
+    // are while an exchange sends them
+    struct T2Out { DevBuf out, tile_dst, part_len, total; };
+    T2Out t2_outs[kMaxAltSets + 1];
+    int t2_cur = 0;
+    uint64_t t2_out_used = 0;        // (the synchronous form) bytes of t2_outs[t2_cur].out that hold tile-parts
+    std::vector<uint64_t> h_off;
+    std::vector<uint32_t> h_len;
+    uint32_t last_ntiles = 0;
+    uint64_t last_nblocks = 0;
+    bool last_h16 = false;           // the latest encode left int16 coefficients in the Mallat planes
+    HostStage stage;                 // pinned chunks for pageable host buffers (copy_h2d)
+    void* d2h_pin = nullptr; size_t d2h_cap = 0; std::vector<hipEvent_t> d2h_ev;   // copy_d2h: a staging area of the transfer's size, an event per piece
+    // A decode call's tables -- the code-block rows (a window's skipped blocks marked), behind them K5's scratch index and the list
+    // of blocks with data -- are put together in pinned memory the context owns and fetched by a kernel of the call's stream
+    // (launch_dec_upload); two sets in turn: the kernel of one call may still be queued when the next call fills its tables
+    // Full decode with overlap on: K5b of the top resolution's blocks (3/4 of them) runs on the side stream beside K5b of the
+    // other blocks and the inverse levels that need only those; the last inverse level waits for it
+    hipEvent_t ev_dec_front = nullptr, ev_dec_top = nullptr;
+    bool dec_top_pending = false;
+    // Pipelined encodes of SMALL frames (up to kFrameStreamSamples samples per call): a frame's whole chain on ONE of the two side streams,
+    // taken in turn -- no event inside a frame (12 instead of 18 runtime calls), consecutive frames overlap through the streams.  A call
+    // is bound by the host's launches below ~2048^2 x 3: 512^2 x 3 0.058 -> 0.045 ms, 2048^2 x 3 0.073 -> 0.058; at 4096^2 it makes no
+    // difference, at 8192^2 it loses 19 % (no top-resolution K3 beside the remaining levels, no stream priorities).
+    // GRK_AMD_FRAME_STREAMS = 0: never, 1 (default): by size, 2: always
+    static constexpr uint64_t kFrameStreamSamples = 16ull << 20;
+    int frame_streams = 1; int fs_parity = 0;
+    // ... the caller's pixels are then read on the frame's stream, not on the context's: level 0 -- their only reader -- is followed by
+    // this event, and the context's stream waits for it, so that whatever the caller queues behind the call in stream order (the
+    // next frame's pixels into the same buffer, a stream-ordered free) still comes after the read, as it does on the other paths
+    // (grk_amd_set_pixel_hold(ctx, 1): the caller keeps a call's pixels untouched until grk_amd_stream_wait_pixels / a synchronisation;
+    //  the wait -- two queue hand-overs between consecutive small frames, 0.038 -> 0.057 ms per 512^2 call -- is then left out)
+    hipEvent_t ev_px = nullptr; bool want_px_event = false; bool px_hold = false; bool px_event_valid = false;
+    // The encoder's three streams have to DISPATCH side by side.  Hardware queues are served by a few dispatch pipes; two queues on one
+    // pipe take turns while one of them has a large grid in flight, and which queue a stream gets depends on how many streams the process
+    // made before (profiles/r06_hw_queues.txt: 0.37 -> 0.55 ms per 8K frame with 4, 5 or 8 earlier streams).  Before the first
+    // overlapped encode on a given main stream the three are probed pairwise (a grid that stays in dispatch for ~150 us on one, a
+    // one-workgroup kernel on the other) and a side stream that has to wait is replaced (GRK_AMD_STREAM_PROBE=0: never)
+    int stream_probe = 1; hipStream_t probed_main = nullptr; int side_priority = 0;
+    hipStream_t probed_before[4] = {};   // main streams probed earlier: a host that alternates between a few streams is not probed at every switch
+    int probe_replaced = 0;           // side streams replaced by the probe so far (grk_amd_stream_probe_result)
+    bool probe_warm = false;          // the probe's kernels have been launched once (their first launch loads their code: not to be measured)
+    bool seq_vetted = false;          // (a sequence's internal context) its streams have been vetted against its neighbours' (vet_sequence_streams)
+    unsigned long long* pend_alloc = nullptr; uint32_t pend_alloc_units = 0;   // K3's allocator reset handed to the fused level 0 (run_dwt)
+    // Part-1 decode: blocks of the default style go 64 to a wave (K8L, kernels_t1lanes.hip) unless much longer than the rest
+    // (GRK_AMD_T1_LANES=0: every block its own wave, K8 as in r01-r03; 2: lanes wherever they can be used; see run_t1_decode)
+    // Decode of a SEQUENCE of frames (grk_amd_set_decode_pipelining): consecutive grk_amd_decode_tiles calls with device buffers
+    // go in turn to this context and to `dec_kids` -- contexts of their own on the same device: own streams, tables, planes --,
+    // each behind an event on the caller's stream.  A frame's serial block-decoding chains (K5a / K8) leave most of the machine
+    // idle; the next frame's kernels take what is free.  grk_amd_synchronize / grk_amd_decode_status cover them all.
+    std::vector<grk_amd_ctx*> dec_kids;
+    uint32_t dec_seq = 0;
+    hipEvent_t ev_seq = nullptr;
+    hipEvent_t ev_frame_done = nullptr;   // (an internal context of a sequence) behind the last frame it was given: grk_amd_decode_stream_wait_slot
+    int t1_lanes = 1;                    // 0: never, 1: where the cost model below says they are faster, 2: wherever they can (tests)
+    bool t1_pass_sync = true;            // K8L's waves hold blocks of equal bit-plane / pass counts and run pass by pass (GRK_AMD_T1_SYNC=0: free-running lanes)
+    struct DecUpload { char* p = nullptr; char* dp = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } dec_up[2];
+    uint32_t dec_turn = 0;
+    // timing
+    bool timing = false;
+    Timer timers[10];
+};
+
+int fail(grk_amd_ctx* c, int code, const char* what, hipError_t e = hipSuccess);                                 // context.hip
+#define HIP_TRY(c, call, what)                                                      \
+    do { hipError_t _e = (call); if (_e != hipSuccess) return fail(c, GRK_AMD_ERR_NO_DEVICE, what, _e); } while (0)
+
+struct ScopedTimer {
+    grk_amd_ctx* c; int which; hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t st;
+    ScopedTimer(grk_amd_ctx* c_, int w, hipStream_t s = nullptr) : c(c_), which(w), st(s ? s : c_->stream)
+    {
+        if (!c->timing) return;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
+        (void)hipEventRecord(a, st);
+    }
+    void cancel() { if (a) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); a = b = nullptr; } }
+    ~ScopedTimer()
+    {
+        if (!a) return;
+        (void)hipEventRecord(b, st);
+        c->timers[which].ev.emplace_back(a, b);
+    }
+};
+
+inline uint32_t ll_stride_for(uint32_t w) { return (((w + 1) >> 1) + 31u) & ~31u; }
+int create_context(int device_id, int verbose, bool decode_only, grk_amd_ctx** out);                             // context.hip
+bool host_is_pinned(const void* p);                                                                              // context.hip
+int copy_h2d(grk_amd_ctx* c, void* dst, const void* src, size_t bytes);                                          // context.hip
+int copy_d2h(grk_amd_ctx* c, void* dst, const void* src, size_t bytes);                                          // context.hip
+bool same_params(const grk_amd_tile_params& a, const grk_amd_tile_params& b);                                    // context.hip
+int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p);                                                   // context.hip
+int probe_streams(grk_amd_ctx* c);                                                                               // streams.hip
+int vetted_stream(grk_amd_ctx* c, hipStream_t* cur, const std::vector<hipStream_t>& against, int* replaced);     // streams.hip
+int join_side(grk_amd_ctx* c);                                                                                   // streams.hip
+int sequence_streams(grk_amd_ctx* k, bool part1);                                                                // streams.hip
+bool planes16_ok(const grk_amd_tile_params& p);                                                                  // encode.hip
+bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l);                                                    // encode.hip
+#pragma GCC visibility pop

@@ -1,0 +1,531 @@
+// grok_amd/csrc/encode.hip -- encode: ingest, forward DWT, HT block coding (K1-K3), pipelined encodes and their results.
+#include "context.h"
+
+namespace {
+int run_ingest(grk_amd_ctx* c, uint32_t ntiles, const void* d_pixels, void* d_planes)
+{
+    const TileGeom& g = c->geom;
+    IngestArgs a{};
+    a.pixels = d_pixels; a.planes = (int32_t*)d_planes;
+    a.w = g.p.tile_w; a.h = g.p.tile_h; a.stride = g.stride; a.pitch = g.plane_elems;
+    a.ncomp = g.p.num_comps; a.ntiles = ntiles;
+    a.bytes_per_sample = (g.p.prec + 7) / 8;
+    a.dc = g.p.sgnd ? 0 : (1 << (g.p.prec - 1));
+    a.sext = g.p.sgnd ? (1 << (8 * a.bytes_per_sample - 1)) : 0;
+    a.mct = g.p.mct; a.irreversible = g.p.irreversible;
+    ScopedTimer t(c, 0);
+    HIP_TRY(c, launch_ingest(a, c->stream), "launch ingest");
+    return GRK_AMD_OK;
+}
+
+HtArgs make_ht_args(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, int* rc, bool h16)
+{
+    HtArgs a{};
+    *rc = GRK_AMD_OK;
+    auto try_ = [&](hipError_t e, const char* what) { if (e != hipSuccess && *rc == GRK_AMD_OK) *rc = fail(c, GRK_AMD_ERR_NO_DEVICE, what, e); };
+    const TileGeom& g = c->geom;
+    const uint32_t bpt = g.blocks_per_comp * g.p.num_comps;
+    const uint64_t nblocks = (uint64_t)bpt * ntiles;
+    try_(c->lengths.ensure(nblocks * 4), "alloc lengths");
+    try_(c->offsets.ensure((nblocks + 1) * 8), "alloc offsets");
+    try_(c->flag.ensure(kHtAllocBytes), "alloc allocator state");
+    // arena: worst case of the HT cleanup pass is ~ (kmax+1)/8 * 8/7 bytes per sample + VLC/MEL;
+    // twice the raw input size plus per-block slack covers every lossless case we accept
+    const uint64_t raw = (uint64_t)ntiles * g.p.num_comps * g.p.tile_w * g.p.tile_h * ((g.p.prec + 7) / 8);
+    // Allocation regions: every block reserves its bytes with an atomic on its region's word, and the blocks of a launch that fits
+    // the machine in one round (up to ~6 000) all arrive there within microseconds of each other -- atomics on ONE address are
+    // served one after the other, and a chunk refill makes the region's other waves wait.  At least one region per 64 blocks (r04:
+    // with one per 256, K3 of a 2048^2 frame took 0.151 ms, with this 0.048; 1024^2 0.079 -> 0.038, 3072^2 0.177 -> 0.069; from
+    // 4096^2 on all 64 regions were in use before: tools/k3_sizes.py); small jobs take smaller chunks, so that the slack of the
+    // regions' half-used chunks stays small against their coded bytes.
+    constexpr uint32_t kBlocksPerRegion = 64;
+    uint32_t regions = 1;
+    while (regions < kHtAllocRegions && nblocks / (regions * 2) >= kBlocksPerRegion) regions *= 2;
+    // (a chunk holds at least two of the largest blocks the geometry can produce: worst case (Kmax + 2) bits per sample and 15 VLC
+    //  bits per quad, stuffing 1 bit in 15, 256 MEL bytes -- ~20 KiB for a 64 x 64 block at Kmax 31)
+    size_t worst_block = 0;
+    for (uint32_t k = 0; k < c->ht_num_classes; ++k) {
+        const HtClass& hc = c->ht_classes[k];
+        worst_block = std::max(worst_block, ((size_t)hc.max_samples * (hc.max_kmax + 2u) + (size_t)hc.max_quads * 15u) * 16u / 15u / 8u + 280u);
+    }
+    const uint32_t chunk = (nblocks < 16384 && 2 * worst_block <= kHtAllocChunkSmall) ? kHtAllocChunkSmall : kHtAllocChunk;
+    try_(c->arena.ensure(raw * 2 + nblocks * 64 + (size_t)(regions + 1) * kHtAllocChunk + (1u << 20)), "alloc coded arena");
+    a.mallat = (const int32_t*)d_mallat; a.stride = g.stride; a.pitch = g.plane_elems; a.h16 = h16 ? 1 : 0;
+    a.blocks = (const HtBlockDesc*)c->blockdesc.p; a.blocks_per_tile = bpt; a.ncomp = g.p.num_comps; a.ntiles = ntiles;
+    a.arena = (uint8_t*)c->arena.p; a.arena_bytes = c->arena.cap;
+    a.alloc = (unsigned long long*)c->flag.p;        // [0] status flags, [1] bytes used (launch_ht_alloc_init resets them)
+    a.lengths = (uint32_t*)c->lengths.p; a.offsets = (unsigned long long*)c->offsets.p;
+    try_(c->ovf.ensure(2 * nblocks * 4 + 16), "alloc fallback list");      // (every block is in two classes)
+    a.ovf_list = c->lds_cap ? (uint32_t*)c->ovf.p : nullptr;
+    a.region_mask = regions - 1;
+    a.chunk_units = chunk / 16u;
+    a.irreversible = g.p.irreversible;
+    a.num_classes = c->ht_num_classes;
+    uint32_t ovf_base = 0;
+    for (uint32_t k = 0; k < c->ht_num_classes; ++k) {
+        a.classes[k] = c->ht_classes[k];
+        a.classes[k].ovf_base = ovf_base;
+        ovf_base += c->ht_classes[k].count * ntiles;
+    }
+    return a;
+}
+
+// d_pixels != nullptr: level 0 reads the caller's pixels directly (K1 fused into K2), d_in is unused
+int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const void* d_pixels = nullptr, uint32_t ntiles = 0,
+            bool overlap_ht = false, bool h16 = false)
+{
+    const TileGeom& g = c->geom;
+    const uint32_t L = g.p.num_levels;
+    const uint32_t W = g.p.tile_w, H = g.p.tile_h;
+    if (L == 0) {
+        HIP_TRY(c, hipMemcpyAsync(d_out, d_in, (size_t)nplanes * g.plane_elems * 4, hipMemcpyDeviceToDevice, c->stream), "copy planes");
+        return GRK_AMD_OK;
+    }
+    // LL ping-pong storage: A holds LL1, LL3, ...; B holds LL2, LL4, ...
+    const uint32_t sA = ll_stride_for(W), hA = (H + 1) >> 1;
+    const uint32_t sB = ll_stride_for((W + 1) >> 1), hB = (hA + 1) >> 1;
+    const uint64_t pitchA = (uint64_t)sA * hA, pitchB = (uint64_t)sB * hB;
+    HIP_TRY(c, c->llA.ensure((size_t)nplanes * pitchA * 4 + 256), "alloc LL ping");
+    HIP_TRY(c, c->llB.ensure((size_t)nplanes * pitchB * 4 + 256), "alloc LL pong");
+    ScopedTimer t(c, 1);
+    for (uint32_t l = 0; l < L; ++l) {
+        DwtLevelArgs a{};
+        a.cw = level_geom(g, l).w; a.ch = level_geom(g, l).h;
+        a.px = level_geom(g, l).x0 & 1u; a.py = level_geom(g, l).y0 & 1u;
+        if (l == 0) { a.in = (const int32_t*)d_in; a.in_stride = g.stride; a.in_pitch = g.plane_elems; }
+        else if (l & 1) { a.in = (const int32_t*)c->llA.p; a.in_stride = sA; a.in_pitch = pitchA; }
+        else { a.in = (const int32_t*)c->llB.p; a.in_stride = sB; a.in_pitch = pitchB; }
+        a.mallat = (int32_t*)d_out; a.m_stride = g.stride; a.m_pitch = g.plane_elems;
+        if (l + 1 == L) { a.ll = (int32_t*)d_out; a.ll_stride = g.stride; a.ll_pitch = g.plane_elems; }
+        else if ((l + 1) & 1) { a.ll = (int32_t*)c->llA.p; a.ll_stride = sA; a.ll_pitch = pitchA; }
+        else { a.ll = (int32_t*)c->llB.p; a.ll_stride = sB; a.ll_pitch = pitchB; }
+        a.nplanes = nplanes;
+        a.irreversible = g.p.irreversible;
+        a.h16 = h16 ? 1 : 0;
+        a.pk = h16 && c->dwt_pk && pk16_level_ok(g.p, l);
+        a.xcd = c->dwt_xcd;
+        // enough workgroups to cover the chip several times, few enough to amortise warm-up rows (profiles/r06_dwt_reads.txt: at 4096
+        // the 8K level 0 ran 16-row segments and read 1.55 x its pixels; 2048 -> 32-row segments, 1.35 x, the DWT 1 % faster)
+        const uint32_t sh = (a.ch + a.py + 1) >> 1;           // row pairs on the coordinate grid
+        uint32_t seg = 64;
+        const uint64_t strips = (a.cw + a.px + dwt_level_strip_cols(a) - 1) / dwt_level_strip_cols(a);
+        // workgroups along z: planes, or for the fused level 0 tiles (x components when there is no MCT triple)
+        const uint32_t zslots = (l == 0 && d_pixels) ? ntiles * ((g.p.mct && g.p.num_comps >= 3) ? 1u : g.p.num_comps) : nplanes;
+        // (... for the packed 5/3 kernel; the 32-bit kernels -- 448-column strips, twice the workgroups per row -- are better off with
+        //  the finer cut: cfg3's 9/7 family 0.361 ms at 4096, 0.394 at 2048)
+        const uint32_t kMinWgs = a.pk ? 2048u : 4096u;
+        while (seg > 8 && strips * ((sh + seg - 1) / seg) * zslots < kMinWgs) seg >>= 1;
+        a.seg_pairs = seg;
+        if (a.cw == 0 || a.ch == 0) {
+            // a level without samples (a narrow tile off the origin: [ceil(x0 / 2^l), ceil((x0 + w) / 2^l)) can be empty):
+            // nothing to transform, and nothing deeper either
+        } else if (l == 0 && d_pixels) {
+            a.pixels = d_pixels; a.px_bytes = (g.p.prec + 7) / 8;
+            a.alloc_reset = c->pend_alloc; a.alloc_chunk_units = c->pend_alloc_units; c->pend_alloc = nullptr;
+            a.dc = g.p.sgnd ? 0 : (1 << (g.p.prec - 1));
+            a.sext = g.p.sgnd ? (1 << (8 * a.px_bytes - 1)) : 0;
+            HIP_TRY(c, launch_dwt_level0_fused(a, ntiles, g.p.num_comps, g.p.mct, c->stream), "launch fused dwt level 0");
+            if (c->want_px_event) HIP_TRY(c, hipEventRecord(c->ev_px, c->stream), "record the pixels' last read");
+        } else {
+            HIP_TRY(c, launch_dwt_level(a, c->stream), "launch dwt level");
+        }
+        if (overlap_ht && (l == 0 || l + 1 == L)) {
+            // After level 0 the top resolution's sub-bands are final: its code-blocks (3/4 of all) are coded on
+            // low-priority side streams while the remaining levels -- short, latency-bound launches that are the
+            // critical path -- run here.  After the last level the rest follows: small-LDS class on this stream (run_ht),
+            // large-LDS class on the second side stream, so that the launches' tails overlap.
+            int rc = GRK_AMD_OK;
+            const HtArgs h = make_ht_args(c, ntiles, d_out, &rc, h16);
+            if (rc) return rc;
+            HIP_TRY(c, hipEventRecord(c->ev_level0, c->stream), "record level");
+            for (uint32_t k = 0; k < h.num_classes; ++k) {
+                if (c->ht_class_top[k] == 2) continue;               // (the all-blocks class is for the non-overlapped path)
+                const bool top = c->ht_class_top[k] != 0, big = c->ht_class_big[k] != 0;
+                hipStream_t st = nullptr;
+                if (l == 0 && top) st = big ? c->side2 : c->side;
+                if (l + 1 == L && !top && big) st = c->side2;
+                // the rest: on the main stream (run_ht) beside the tail of the top resolution -- unless consecutive encodes
+                // are pipelined: then the main stream carries nothing but the DWT chain, so that the next encode's level 0
+                // starts as early as possible, and every K3 launch queues on a side stream
+                if (l + 1 == L && !top && !big && c->pipelining) st = c->side2;    // (its tail then overlaps the top class's)
+                if (!st) continue;
+                HIP_TRY(c, hipStreamWaitEvent(st, c->ev_level0, 0), "side stream waits for the level");
+                ScopedTimer tt(c, st == c->side ? 4 : 8, st);
+                // (consecutive encodes pipelined: the top class is still running when the next encode's level 0 arrives)
+                HtArgs hs = h;
+                hs.room = c->pipelining ? 1 : 0;
+                HIP_TRY(c, launch_ht_classes(hs, k, k + 1, st), "launch ht encode (side stream)");
+            }
+            if (l + 1 == L) {
+                HIP_TRY(c, hipEventRecord(c->ev_side, c->side), "record side stream");
+                HIP_TRY(c, hipEventRecord(c->ev_side2, c->side2), "record side stream 2");
+            }
+        }
+    }
+    return GRK_AMD_OK;
+}
+
+// overlapped: the top resolution and the large-LDS classes are already running on the side streams (run_dwt)
+int run_ht(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool overlapped = false, bool h16 = false, bool room = false)
+{
+    int rc = GRK_AMD_OK;
+    HtArgs a = make_ht_args(c, ntiles, d_mallat, &rc, h16);
+    if (rc) return rc;
+    a.room = room ? 1 : 0;
+    {
+        ScopedTimer t(c, 2);
+        if (!overlapped) {         // one launch of every block where there is such a class, else class by class
+            HIP_TRY(c, launch_ht_alloc_init(a, c->stream), "reset arena allocator");
+            bool all = false;
+            for (uint32_t k = 0; k < a.num_classes; ++k) all = all || c->ht_class_top[k] == 2;
+            for (uint32_t k = 0; k < a.num_classes; ++k)
+                if ((c->ht_class_top[k] == 2) == all) HIP_TRY(c, launch_ht_classes(a, k, k + 1, c->stream), "launch ht encode");
+        } else {
+            for (uint32_t k = 0; k < a.num_classes && !c->pipelining; ++k)
+                if (!c->ht_class_top[k] && !c->ht_class_big[k]) HIP_TRY(c, launch_ht_classes(a, k, k + 1, c->stream), "launch ht encode");
+        }
+    }
+    if (overlapped) {
+        c->side_pending = true;
+        if (!c->pipelining) { const int jr = join_side(c); if (jr) return jr; }    // pipelining: the next consumer joins
+    }
+    c->last_ntiles = ntiles;
+    c->last_nblocks = (uint64_t)c->geom.blocks_per_comp * c->geom.p.num_comps * ntiles;
+    return GRK_AMD_OK;
+}
+} // namespace
+
+// 16-bit planes are safe when no coefficient of any level can leave int16.  Bound (5/3, L1 norms of the analysis
+// filters: low-pass 1.5, high-pass 2 per dimension; RCT chroma is one bit wider than the pixels): the LL of level l is
+// below M * 2.25^l, a detail band of level l below 4 * M * 2.25^(l-1), with M = 2^prec the largest input magnitude.
+bool planes16_ok(const grk_amd_tile_params& p)
+{
+    if (p.irreversible || p.prec > 8 || p.num_levels == 0) return false;
+    double bound = (double)(1u << p.prec) * 4.0;
+    for (uint32_t l = 1; l < p.num_levels; ++l) bound *= 2.25;
+    return bound + 8.0 * p.num_levels < 32767.0;
+}
+
+// Level l of such a tile on PACKED int16 pairs (kernels_dwt.hip, strip_pk): every intermediate of the 2-D lifting step has to
+// stay inside 16 bits as well.  With M the largest magnitude entering the level (2^prec after DC shift and RCT, times the
+// low-pass gain 1.5 x 1.5 per level before, plus rounding), the largest is the horizontal update's sum of two high-pass
+// values of a vertically high-pass row: 2 x 2 x 2M each, 8M + 2 in all.
+bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l)
+{
+    if (p.sgnd) return false;                        // (the packed unpacking is written for unsigned pixels)
+    double m = (double)(1u << p.prec);
+    for (uint32_t i = 0; i < l; ++i) m = m * 2.25 + 4.0;
+    return 8.0 * m + 16.0 < 32767.0;
+}
+
+extern "C" {
+int grk_amd_stage_ingest_mct(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_pixels, void* d_planes)
+{
+    if (!c || !p || !d_pixels || !d_planes) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = ensure_geom(c, p); if (rc) return rc;
+    return run_ingest(c, ntiles, d_pixels, d_planes);
+}
+
+int grk_amd_stage_dwt_fwd(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nplanes, void* d_in, void* d_out)
+{
+    if (c) { const int jr = join_side(c); if (jr) return jr; }
+    if (!c || !p || !d_in || !d_out) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = ensure_geom(c, p); if (rc) return rc;
+    return run_dwt(c, nplanes, d_in, d_out);
+}
+
+int grk_amd_stage_ht_encode(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat)
+{
+    if (c) { const int jr = join_side(c); if (jr) return jr; }
+    if (!c || !p || !d_mallat) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = ensure_geom(c, p); if (rc) return rc;
+    return run_ht(c, ntiles, d_mallat);
+}
+
+int grk_amd_fetch_table(grk_amd_ctx* c, grk_amd_coded_block* table, uint64_t* total)
+{
+    if (!c || !c->last_nblocks) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    { const int jr = join_side(c); if (jr) return jr; }
+    const uint64_t n = c->last_nblocks;
+    uint64_t flagwords[2] = {0, 0};       // [0] low 32 bits: overflow flag, [1]: arena cursor
+    HIP_TRY(c, hipMemcpyAsync(flagwords, c->flag.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch flag");
+    if (table) {
+        c->h_off.resize(n); c->h_len.resize(n);
+        HIP_TRY(c, hipMemcpyAsync(c->h_off.data(), c->offsets.p, n * 8, hipMemcpyDeviceToHost, c->stream), "fetch offsets");
+        HIP_TRY(c, hipMemcpyAsync(c->h_len.data(), c->lengths.p, n * 4, hipMemcpyDeviceToHost, c->stream), "fetch lengths");
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    if (flagwords[0] & 1u) return fail(c, GRK_AMD_ERR_OVERFLOW, "coded arena overflow");
+    if (flagwords[0] & 2u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "coefficient magnitude exceeds Kmax+1 bits");
+    if (table) {
+        const uint32_t bpt = (uint32_t)c->h_desc.size();
+        for (uint64_t i = 0; i < n; ++i) {
+            table[i].offset = c->h_off[i]; table[i].length = c->h_len[i];
+            table[i].missing_msbs = c->h_desc[i % bpt].kmax - 1u;      // numbps = 1 is signalled (T1HT.cpp:123)
+        }
+    }
+    if (total) *total = flagwords[1];
+    return GRK_AMD_OK;
+}
+
+int grk_amd_fetch_coded(grk_amd_ctx* c, uint8_t* dst, uint64_t nbytes)
+{
+    if (!c || !dst) return GRK_AMD_ERR_INVALID;
+    if (nbytes > c->arena.cap) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    { const int jr = join_side(c); if (jr) return jr; }
+    { const int rc = copy_d2h(c, dst, c->arena.p, nbytes); if (rc) return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    return GRK_AMD_OK;
+}
+
+int grk_amd_fetch_coded_async(grk_amd_ctx* c, uint8_t* dst, uint64_t nbytes)
+{
+    if (!c || !dst) return GRK_AMD_ERR_INVALID;
+    if (nbytes > c->arena.cap) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    if (!host_is_pinned(dst)) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_fetch_coded_async needs pinned memory (grk_amd_host_alloc)");
+    { const int jr = join_side(c); if (jr) return jr; }
+    if (nbytes) HIP_TRY(c, hipMemcpyAsync(dst, c->arena.p, nbytes, hipMemcpyDeviceToHost, c->stream), "download");
+    return GRK_AMD_OK;
+}
+
+int grk_amd_fetch_coefficients(grk_amd_ctx* c, uint32_t comp, int32_t* dst, uint32_t dst_stride)
+{
+    if (!c || !dst || !c->have_geom || !c->last_nblocks || comp >= c->geom.p.num_comps || dst_stride < c->geom.p.tile_w)
+        return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    { const int jr = join_side(c); if (jr) return jr; }
+    const TileGeom& g = c->geom;
+    const uint32_t W = g.p.tile_w, H = g.p.tile_h;
+    if (c->last_h16) {              // 16-bit planes between K2 and K3 (8-bit reversible content): widened here
+        std::vector<int16_t> tmp((size_t)g.stride * H);
+        HIP_TRY(c, hipMemcpyAsync(tmp.data(), (const int16_t*)c->p1.p + (size_t)comp * g.plane_elems, tmp.size() * 2,
+                                  hipMemcpyDeviceToHost, c->stream), "fetch coefficients");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+        for (uint32_t y = 0; y < H; ++y)
+            for (uint32_t x = 0; x < W; ++x) dst[(size_t)y * dst_stride + x] = tmp[(size_t)y * g.stride + x];
+    } else {
+        HIP_TRY(c, hipMemcpy2DAsync(dst, (size_t)dst_stride * 4, (const int32_t*)c->p1.p + (size_t)comp * g.plane_elems,
+                                    (size_t)g.stride * 4, (size_t)W * 4, H, hipMemcpyDeviceToHost, c->stream), "fetch coefficients");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    }
+    return GRK_AMD_OK;
+}
+
+// Weights of T1::getwmsedec (t1/t1_part1/T1.cpp:394-414): L2 norms of the synthesis basis functions by orientation and decomposition
+// level (dwt_norms / dwt_norms_real, T1.cpp:224-235; T1::getnorm clamps the level, :258-267) and of the inverse colour transform's
+// columns (mct_norms_rev / _irrev, point_transform/mct.cpp:30-35)
+static double band_norm(uint32_t orient, uint32_t level, bool reversible)
+{
+    static const double n53[4][10] = {{1.000, 1.500, 2.750, 5.375, 10.68, 21.34, 42.67, 85.33, 170.7, 341.3},
+                                      {1.038, 1.592, 2.919, 5.703, 11.33, 22.64, 45.25, 90.48, 180.9, 0},
+                                      {1.038, 1.592, 2.919, 5.703, 11.33, 22.64, 45.25, 90.48, 180.9, 0},
+                                      {.7186, .9218, 1.586, 3.043, 6.019, 12.01, 24.00, 47.97, 95.93, 0}};
+    static const double n97[4][10] = {{1.000, 1.965, 4.177, 8.403, 16.90, 33.84, 67.69, 135.3, 270.6, 540.9},
+                                      {2.022, 3.989, 8.355, 17.04, 34.27, 68.63, 137.3, 274.6, 549.0, 0},
+                                      {2.022, 3.989, 8.355, 17.04, 34.27, 68.63, 137.3, 274.6, 549.0, 0},
+                                      {2.080, 3.865, 8.307, 17.18, 34.71, 69.59, 139.3, 278.6, 557.2, 0}};
+    if (orient == 0 && level > 9) level = 9;
+    else if (orient > 0 && level > 8) level = 8;
+    return reversible ? n53[orient & 3u][level] : n97[orient & 3u][level];
+}
+
+int grk_amd_block_distortion(grk_amd_ctx* c, double* out, uint64_t cap)
+{
+    if (!c || !out || !c->have_geom || !c->last_nblocks || cap < c->last_nblocks) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    { const int jr = join_side(c); if (jr) return jr; }
+    const TileGeom& g = c->geom;
+    const uint64_t n = c->last_nblocks;
+    const uint32_t bpt = (uint32_t)c->h_desc.size();
+    HIP_TRY(c, c->energy.ensure(n * 8), "alloc block energies");
+    HIP_TRY(c, launch_block_energy(c->p1.p, c->last_h16 ? 1 : 0, g.p.irreversible, g.stride, g.plane_elems, (const HtBlockDesc*)c->blockdesc.p,
+                                   bpt, g.p.num_comps, n, (unsigned long long*)c->energy.p, c->stream), "launch block energy");
+    std::vector<unsigned long long> e(n);
+    HIP_TRY(c, hipMemcpyAsync(e.data(), c->energy.p, n * 8, hipMemcpyDeviceToHost, c->stream), "fetch block energies");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    static const double mct_rev[3] = {1.732, .8292, .8292}, mct_irrev[3] = {1.732, 1.805, 1.573};
+    for (uint64_t i = 0; i < n; ++i) {
+        const grk_amd_block& b = g.blocks_comp0[(i % bpt) % g.blocks_per_comp];
+        const uint32_t comp = (uint32_t)((i % bpt) / g.blocks_per_comp);
+        const double w1 = (g.p.mct && g.p.num_comps >= 3 && comp < 3) ? (g.p.irreversible ? mct_irrev[comp] : mct_rev[comp]) : 1.0;
+        const double w2 = band_norm(b.band, g.p.num_levels - b.res, !g.p.irreversible);
+        const double w = w1 * w2 * (double)b.stepsize;
+        out[i] = w * w * (double)e[i];
+    }
+    return GRK_AMD_OK;
+}
+
+void* grk_amd_coded_device_ptr(grk_amd_ctx* c) { return c ? c->arena.p : nullptr; }
+void* grk_amd_table_device_ptr(grk_amd_ctx* c, int which)
+{
+    if (!c) return nullptr;
+    switch (which) {
+    case 0: return c->offsets.p;                                    // uint64[nblocks]
+    case 1: return c->lengths.p;                                    // uint32[nblocks]
+    case 2: return c->flag.p ? (uint8_t*)c->flag.p + 8 : nullptr;   // uint64: bytes used in the arena
+    case 3: return c->flag.p ? (uint8_t*)c->flag.p + 16 : nullptr;  // uint64[24]: blocks each K3 class handed to its fallback launch
+    default: return nullptr;
+    }
+}
+
+int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* pixels,
+                         int on_device, grk_amd_coded_block* table, uint64_t* total)
+{
+    if (!c || !p || !pixels || ntiles == 0) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = ensure_geom(c, p); if (rc) return rc;
+    const TileGeom& g = c->geom;
+    const size_t tile_bytes = (size_t)g.p.num_comps * g.p.tile_w * g.p.tile_h * ((g.p.prec + 7) / 8);
+    const void* d_px = pixels;
+    if (!on_device) {
+        HIP_TRY(c, c->pixels.ensure(tile_bytes * ntiles), "alloc pixel staging");
+        rc = copy_h2d(c, c->pixels.p, pixels, tile_bytes * ntiles); if (rc) return rc;
+        d_px = c->pixels.p;
+    }
+    const uint32_t nplanes = ntiles * g.p.num_comps;
+    // with at least one DWT level, level 0 consumes the pixels itself and the int32 ingest planes
+    // (4 bytes per sample written and read back) never exist
+    const bool fused = g.p.num_levels >= 1 && ((uintptr_t)d_px & 3u) == 0;
+    if (!fused) HIP_TRY(c, c->p0.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc planes");
+    HIP_TRY(c, c->p1.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc Mallat planes");
+    {
+        ScopedTimer t(c, 3);
+        const bool ov = c->overlap && g.p.num_levels >= 1 && c->side != nullptr;
+        if (ov && c->pipelining && c->seq_index < 0 && probe_streams(c) != GRK_AMD_OK) {
+            // (the probe is a convenience: when it cannot run, the streams stay as they are and it is not tried again)
+            c->stream_probe = 0; (void)hipGetLastError();
+        }
+        // (device-resident pixels only: the staging buffer of host pixels is filled on the main stream, which must then carry level 0)
+        // (... and the fused level 0: the stand-alone ingest writes planes that are not part of a buffer set)
+        const bool fs = ov && c->pipelining && c->side2 != nullptr && on_device && fused &&
+                        (c->frame_streams == 2 || (c->frame_streams == 1 && (uint64_t)nplanes * g.plane_elems <= grk_amd_ctx::kFrameStreamSamples));
+        hipStream_t fs_st = nullptr;
+        if (ov && c->pipelining) {
+            // take the other buffer set: the blocks of the previous encode may still be being coded from the set used
+            // last; the set taken now was last used two encodes ago, and its side-stream work is waited for here
+            // (hipStreamWaitEvent on an event never recorded is a no-op)
+            auto swap_with = [&](grk_amd_ctx::AltSet& as) {
+                std::swap(c->p1, as.p1); std::swap(c->arena, as.arena); std::swap(c->lengths, as.lengths);
+                std::swap(c->offsets, as.offsets); std::swap(c->flag, as.flag); std::swap(c->ovf, as.ovf);
+                std::swap(c->ev_side, as.ev_side); std::swap(c->ev_side2, as.ev_side2);
+            };
+            // the oldest of the pipe_depth - 1 other sets becomes current; the set retired here takes its slot as the newest
+            swap_with(c->alts[c->alt_head]);
+            // (the LL ping-pong buffers belong to the set as well: frames on different streams transform at the same time, and a call
+            //  of the other form -- the same geometry, more tiles -- must not take a running frame's)
+            std::swap(c->llA, c->alts[c->alt_head].llA); std::swap(c->llB, c->alts[c->alt_head].llB);
+            c->alt_head = (c->alt_head + 1) % (c->pipe_depth - 1);
+            c->side_pending = false;
+            if (fs) {
+                fs_st = c->fs_parity ? c->side2 : c->side; c->fs_parity ^= 1;
+                if (!c->ev_main) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming), "create event");
+                HIP_TRY(c, hipEventRecord(c->ev_main, c->stream), "record the caller's stream");
+                HIP_TRY(c, hipStreamWaitEvent(fs_st, c->ev_main, 0), "the frame's stream waits for the pixels");
+            }
+            HIP_TRY(c, hipStreamWaitEvent(fs ? fs_st : c->stream, c->ev_side, 0), "wait for the buffer set");
+            HIP_TRY(c, hipStreamWaitEvent(fs ? fs_st : c->stream, c->ev_side2, 0), "wait for the buffer set");
+            HIP_TRY(c, c->p1.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc Mallat planes");
+        } else {
+            rc = join_side(c); if (rc) return rc;
+        }
+        // 8-bit reversible content: int16 LL / Mallat planes between K2 and K3 (half the bytes written and read back);
+        // needs the fused level 0 (the stand-alone ingest kernel writes int32 planes)
+        const bool h16 = c->planes16 && fused && planes16_ok(g.p);
+        c->last_h16 = h16;
+        if (fs) {
+            t.cancel();
+            // the whole frame on its stream, as the non-overlapped path lays it out (one K3 launch of every block, the ROOM instance)
+            struct StreamSwap { grk_amd_ctx* c; hipStream_t keep; StreamSwap(grk_amd_ctx* c_, hipStream_t s) : c(c_), keep(c_->stream) { c->stream = s; }
+                                ~StreamSwap() { c->stream = keep; } } on_frame_stream(c, fs_st);
+            if (!c->ev_px) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_px, hipEventDisableTiming), "create event");
+            ScopedTimer tf(c, 3);              // (the call's timer on the stream that carries the call)
+            c->want_px_event = true;
+            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, false, h16);
+            c->want_px_event = false;
+            if (rc) return rc;
+            // the pixel-lifetime contract of every other path: work queued on the context's stream after this call comes after the read
+            c->px_event_valid = true;
+            if (!c->px_hold)
+                HIP_TRY(c, hipStreamWaitEvent(on_frame_stream.keep, c->ev_px, 0), "the context's stream waits for the pixels' last read");
+            rc = run_ht(c, ntiles, c->p1.p, false, h16, true); if (rc) return rc;
+            HIP_TRY(c, hipEventRecord(c->ev_side, fs_st), "record the frame's stream");
+            HIP_TRY(c, hipEventRecord(c->ev_side2, fs_st), "record the frame's stream");
+            c->side_pending = true;
+            if (table || total) return grk_amd_fetch_table(c, table, total);
+            return GRK_AMD_OK;
+        }
+        c->px_event_valid = false;          // (the pixels are read on the context's stream itself from here on)
+        if (ov) {       // the allocator must be reset before the first K3 launch of either stream
+            int rc2 = GRK_AMD_OK;
+            const HtArgs h = make_ht_args(c, ntiles, c->p1.p, &rc2, h16);
+            if (rc2) return rc2;
+            // (with the fused level 0 its first workgroup does it: one launch less on the main stream's chain)
+            if (fused) { c->pend_alloc = h.alloc; c->pend_alloc_units = h.chunk_units; }
+            else HIP_TRY(c, launch_ht_alloc_init(h, c->stream), "reset arena allocator");
+        }
+        if (fused) {
+            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, ov, h16); if (rc) return rc;
+        } else {
+            rc = run_ingest(c, ntiles, d_px, c->p0.p); if (rc) return rc;
+            rc = run_dwt(c, nplanes, c->p0.p, c->p1.p, nullptr, ntiles, ov); if (rc) return rc;
+        }
+        rc = run_ht(c, ntiles, c->p1.p, ov, h16); if (rc) return rc;
+    }
+    if (table || total) return grk_amd_fetch_table(c, table, total);
+    return GRK_AMD_OK;
+}
+
+int grk_amd_stream_wait_results(grk_amd_ctx* c, void* hip_stream)
+{
+    if (!c || !hip_stream) return GRK_AMD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!c->ev_main) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming), "create event");
+    HIP_TRY(c, hipEventRecord(c->ev_main, c->stream), "record main stream");
+    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_main, 0), "wait for the main stream");
+    if (c->side_pending) {
+        HIP_TRY(c, hipStreamWaitEvent(s, c->ev_side, 0), "wait for the side stream");
+        HIP_TRY(c, hipStreamWaitEvent(s, c->ev_side2, 0), "wait for the side stream 2");
+    }
+    return GRK_AMD_OK;
+}
+
+int grk_amd_set_pixel_hold(grk_amd_ctx* c, int on)
+{
+    if (!c) return GRK_AMD_ERR_INVALID;
+    c->px_hold = on != 0;
+    return GRK_AMD_OK;
+}
+
+int grk_amd_stream_wait_pixels(grk_amd_ctx* c, void* hip_stream)
+{
+    if (!c || !hip_stream) return GRK_AMD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (c->px_event_valid) { HIP_TRY(c, hipStreamWaitEvent(s, c->ev_px, 0), "wait for the pixels' last read"); return GRK_AMD_OK; }
+    if (s == c->stream) return GRK_AMD_OK;        // (stream order)
+    if (!c->ev_main) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming), "create event");
+    HIP_TRY(c, hipEventRecord(c->ev_main, c->stream), "record main stream");
+    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_main, 0), "wait for the main stream");
+    return GRK_AMD_OK;
+}
+
+int grk_amd_get_pipelining(grk_amd_ctx* c)
+{
+    return c && c->pipelining && c->overlap && c->side ? c->pipe_depth - 1 : 0;
+}
+
+int grk_amd_set_pipelining(grk_amd_ctx* c, int on)
+{
+    if (!c) return GRK_AMD_ERR_INVALID;
+    const int rc = grk_amd_synchronize(c);
+    c->pipelining = on != 0 && c->side != nullptr && c->side2 != nullptr;
+    c->pipe_depth = std::min(std::max(on, 1) + 1, grk_amd_ctx::kMaxAltSets + 1);
+    c->alt_head = 0;
+    return rc;
+}
+} // extern "C"

@@ -34,7 +34,6 @@
 // the order of WaveletFwd.cpp:143-160; scaling low*invK, high*K as in :46, :203-213.
 #include "kernels.h"
 #include "pk16.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace grk_amd {
@@ -108,7 +107,7 @@ struct V97 {
 };
 
 // ---- the same on PAIRS of int16 in one register (pk16.h); the host vouches for the range level by level
-//      (context.hip: pk16_level_ok) ------------------------------------------------------------------------------------
+//      (encode.hip: pk16_level_ok) ------------------------------------------------------------------------------------
 struct V53pk {
     pk16 xe, dp;
     __device__ __forceinline__ void init(pk16 x_even) { xe = x_even; dp = (pk16)(0); }
@@ -177,7 +176,7 @@ __device__ __forceinline__ void color_fwd_px(int32_t& c0, int32_t& c1, int32_t& 
 //   through the transform side by side, so the int32 ingest planes are never written or read
 //   (saves 8 of the 8 + b_in + 4 bytes per sample that K1 + level 0 move separately).
 // H16 (reversible only): the planes this level reads (PX = 0) and writes hold int16 coefficients -- half the bytes
-//   of the int32 working type; the caller guarantees the range (context.hip: planes16_ok).
+//   of the int32 working type; the caller guarantees the range (encode.hip: planes16_ok).
 // GEN = false: the instance for levels the launcher knows to be even (on the origin, even width >= 4, even height >= 16), whose
 //   every strip takes a FAST path -- without the general path in the kernel the three-component 9/7 level 0 needs 83 registers
 //   instead of 124 (the 5/3 one 84 instead of 99): five waves per SIMD, and room on a SIMD whose other waves are the block
@@ -748,8 +747,7 @@ hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint
         if (comp0 != 0) a.alloc_reset = nullptr;             // (the first launch resets the allocator)
         dim3 grid((a.cw + a.px + kOutCols - 1) / kOutCols, (sh + a.seg_pairs - 1) / a.seg_pairs, ntiles * zdiv);
         // (what the kernel calls `even`: every strip of the level takes a FAST path)
-        static const bool only_fast_ok = !(getenv("GRK_AMD_DWT_FAST_ONLY") && atoi(getenv("GRK_AMD_DWT_FAST_ONLY")) == 0);   // (=0: A/B runs)
-        const bool all_fast = only_fast_ok && (a.px | a.py) == 0 && (a.cw & 1u) == 0 && a.cw >= 4 && a.ch >= 16 && (a.ch & 1u) == 0;
+        const bool all_fast = (a.px | a.py) == 0 && (a.cw & 1u) == 0 && a.cw >= 4 && a.ch >= 16 && (a.ch & 1u) == 0;
 #define GRK_L0(F97, NC, PX) do { if (all_fast) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, false, false>), grid, block, 0, s, a); \
                                  else hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX>), grid, block, 0, s, a); } while (0)
         const int px = a.px_bytes == 1 ? 1 : 2;
@@ -766,7 +764,7 @@ hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint
                 if (nc == 3) hipLaunchKernelGGL((dwt53_pk_kernel<3, 1, 256>), grid, block, 0, s, a);
                 else         hipLaunchKernelGGL((dwt53_pk_kernel<1, 1, 256>), grid, block, 0, s, a);
             }
-        } else if (a.h16 && px == 1) {       // 16-bit planes exist for 8-bit pixels only (context.hip: planes16_ok)
+        } else if (a.h16 && px == 1) {       // 16-bit planes exist for 8-bit pixels only (encode.hip: planes16_ok)
             if (nc == 3) hipLaunchKernelGGL((dwt_level_kernel<false, 3, 1, true>), grid, block, 0, s, a);
             else         hipLaunchKernelGGL((dwt_level_kernel<false, 1, 1, true>), grid, block, 0, s, a);
         } else {

@@ -435,7 +435,7 @@ __device__ __forceinline__ unsigned long long arena_alloc(unsigned long long* fl
 {
     unsigned long long* word = flagbuf + 32 * (1 + region);
     const unsigned long long n = (bytes + 15u) >> 4;
-    // (a request that does not fit a chunk -- the host sizes chunks at twice the largest block, context.hip make_ht_args: only a
+    // (a request that does not fit a chunk -- the host sizes chunks at twice the largest block, encode.hip make_ht_args: only a
     //  geometry it did not foresee gets here -- takes its bytes from the shared cursor itself and leaves the region's chunk alone;
     //  handed a fresh chunk it would run past the chunk's end into the next region's)
     if (n > kChunkUnits) return __hip_atomic_fetch_add(flagbuf + 1, n << 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

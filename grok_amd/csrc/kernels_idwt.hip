@@ -368,7 +368,7 @@ __global__ __launch_bounds__(kThreads) void idwt_level_kernel(IdwtLevelArgs a)
 //   for the vertical recurrence on packed pairs, and stores finished rows four columns at a time.
 // Range: every sum stays inside 16 bits as long as the level's inputs lie within +-kPkDecodeBound (pk16.h) -- the block
 // decoder's flag vouches for the coefficients, and an intermediate level checks the LL it writes (status bit 3 otherwise;
-// the decode is then done again in 32 bits, context.hip decode_impl).
+// the decode is then done again in 32 bits, decode.hip decode_impl).
 struct IV53pk {       // yields rows 2i-1 and 2i
     pk16 dprev, xprev;
     __device__ __forceinline__ void init() { dprev = (pk16)(0); xprev = (pk16)(0); }

@@ -3,7 +3,7 @@
 cfg3  8192x8192x3 16-bit, ICT + 9/7 + dead-zone quantiser + HT: the GPU's sub-band coefficients == the oracle's
       (and the real reference's dwt97) to the bit -- north_star asks for <= 1 ULP --, and sampled code-blocks ==
       the oracle chain's bytes.  This is the only place the 9/7 kernel runs with the row-segment sizes the
-      8K launch heuristic picks (context.hip run_dwt: seg >= 16 needs >= 4K images).
+      8K launch heuristic picks (encode.hip run_dwt: seg >= 16 needs >= 4K images).
 cfg4  a 64-tile batch (8192x8192 cut into 1024x1024 tiles, every tile different content): whole codestream ==
       grk_compress's, byte for byte; the batch decode returns the source.  And the configuration itself: 16384x16384 as 256
       tiles on one GPU == grk_compress's file (the N = 1 point of its scaling curve).

@@ -263,7 +263,7 @@ def test_gpu_codestream_other_block_sizes_vs_grok(cblk):
 @pytest.mark.parametrize("C,H,W,L,sgnd,mct", [(3, 512, 640, 5, False, True), (1, 300, 517, 3, False, False), (3, 257, 129, 2, False, True),
                                               (3, 256, 256, 5, True, True), (4, 192, 320, 4, False, True), (3, 1024, 1024, 1, False, False)])
 def test_int16_planes_equal_int32_planes(C, H, W, L, sgnd, mct, monkeypatch):
-    """8-bit reversible encodes keep int16 LL / Mallat planes between K2 and K3 (half the bytes; context.hip
+    """8-bit reversible encodes keep int16 LL / Mallat planes between K2 and K3 (half the bytes; encode.hip
     planes16_ok).  The same tile through a context with GRK_AMD_PLANES16=0 (int32 planes), with and without the
     K3/DWT overlap, and through the oracle chain: identical blocks.  Extreme pixels (0 / 255 checkerboards)
     push the coefficients to the bound the 16-bit planes are sized for."""
@@ -293,7 +293,7 @@ def test_int16_planes_equal_int32_planes(C, H, W, L, sgnd, mct, monkeypatch):
 @pytest.mark.parametrize("cell", [1, 2, 4, 8, 0])
 def test_packed_int16_dwt_at_the_extremes(cell, monkeypatch):
     """Levels whose every intermediate stays inside 16 bits run on packed int16 pairs (kernels_dwt.hip strip_pk;
-    context.hip pk16_level_ok gives the levels).  Content made to drive the lifting sums as far as 8-bit pixels can --
+    encode.hip pk16_level_ok gives the levels).  Content made to drive the lifting sums as far as 8-bit pixels can --
     0 / 255 checkerboards with cells of 1, 2, 4, 8 pixels (each resonates with one level), and binary noise (cell 0) -- through
     5 levels, with different phases per component so that the RCT's chroma reaches +-255: blocks identical to the 32-bit
     arithmetic (GRK_AMD_DWT_PK=0) and to the oracle chain."""
@@ -369,18 +369,15 @@ def _dev_view(ptr, n, typestr):
     return torch.as_tensor(h, device="cuda")
 
 
-@pytest.mark.parametrize("depth,room,frame_streams", [(1, None, "0"), (2, None, "0"), (1, "0", "0"), (2, "1", "0"), (1, "2", "0"),
-                                                      (1, None, None), (2, None, None), (3, "0", "2")])
-def test_pipelined_encodes_keep_their_results_until_the_second_next_call(depth, room, frame_streams, monkeypatch):
+@pytest.mark.parametrize("depth,frame_streams", [(1, "0"), (2, "0"), (1, None), (2, None), (3, "2")])
+def test_pipelined_encodes_keep_their_results_until_the_second_next_call(depth, frame_streams, monkeypatch):
     """grk_amd_set_pipelining: consecutive encodes overlap (the next one's DWT runs while this one's blocks are still
     being coded), each working in its own buffer set.  Different images back to back without any fetch in between:
     the device-resident results of encode k are read AFTER encode k+1 (two sets) / k+2 (three sets: set_pipelining(2))
-    has been issued, and equal a plain encode's.  `room`: GRK_AMD_K3_ROOM -- which K3 launches of the sequence run the
-    instance that leaves registers for the next frame's DWT (default: both classes); `frame_streams`: GRK_AMD_FRAME_STREAMS -- "0":
+    has been issued, and equal a plain encode's (every K3 launch of the sequence runs the instance that leaves registers for the
+    next frame's DWT).  `frame_streams`: GRK_AMD_FRAME_STREAMS -- "0":
     the DWT chain on the main stream and K3 on the side streams behind events (what large frames take), default / "2": a frame's whole
     chain on one of the side streams in turn (what frames of this size take); the bytes are the same either way."""
-    if room is not None:
-        monkeypatch.setenv("GRK_AMD_K3_ROOM", room)
     if frame_streams is not None:
         monkeypatch.setenv("GRK_AMD_FRAME_STREAMS", frame_streams)
     p = G.TileParams.make(1024, 768, 3, 8, 5)

@@ -1,4 +1,4 @@
-"""-m gpu: the stream probe (context.hip probe_streams; profiles/r06_hw_queues.txt).  Which hardware queue a stream gets depends on
+"""-m gpu: the stream probe (streams.hip probe_streams; profiles/r06_hw_queues.txt).  Which hardware queue a stream gets depends on
 the streams the process made before, so what the probe FINDS differs from process to process; what has to hold everywhere: results
 do not depend on it, it can be switched off, the exported pair test answers for a host's own streams and refuses nonsense."""
 import numpy as np

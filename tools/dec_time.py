@@ -1,6 +1,6 @@
 """HT decode at 8K on the GPU (dev tool): per step, the K5 family (HIP events), the inverse DWT family, the whole
 decode_tiles call back to back, and a check that the pixels come back.  Environment switches of the build under test are
-passed through (e.g. GRK_AMD_K5A_LANES)."""
+passed through (e.g. GRK_AMD_DEC_PLANES16)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -374,6 +374,7 @@ int check_decode_status(grk_amd_ctx* c)
     HIP_TRY(c, hipMemcpyAsync(&st, c->flag.p, 4, hipMemcpyDeviceToHost, c->stream), "fetch status");
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
     if (st & 4u) return fail(c, GRK_AMD_ERR_INVALID, "corrupt HT code-block (bad Scup or U_q > missing_msbs)");
+    if (st & 16u) return fail(c, GRK_AMD_ERR_INVALID, "Part-1 code-block with more than 24 bit-planes (k_max_bit_planes)");
     if (st & 8u) return fail(c, GRK_AMD_ERR_RANGE, "a coefficient left the 16-bit planes: decode again after grk_amd_set_decode_planes16(ctx, 0)");
     return GRK_AMD_OK;
 }

@@ -159,7 +159,7 @@ struct T1DecArgs {
     uint32_t blocks_per_tile, nblocks, ncomp;
     const uint8_t* coded; uint64_t coded_bytes;
     int32_t* work;                             // [nblocks][64*64] decoded values
-    unsigned int* status;
+    unsigned int* status;                      // bit 4: a block with more than 24 bit-planes (refused, left at zero)
     int32_t* mallat; uint32_t stride; uint64_t pitch;
     int irreversible;
     uint32_t cblksty;                          // COD code-block style bits (LAZY 1, RESET 2, TERMALL 4, VSC 8, PTERM 16, SEGSYM 32)

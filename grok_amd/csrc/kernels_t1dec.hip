@@ -420,7 +420,7 @@ __device__ __forceinline__ void t1_dec_block(const T1DecArgs& a, const uint32_t 
     const uint32_t tile = blk / a.blocks_per_tile;
     int32_t* const dst = a.mallat + ((size_t)tile * a.ncomp + bd.comp) * a.pitch + (size_t)bd.py * a.stride + bd.px;
     if (in.length == 0 || numpasses == 0 || numbps == 0 || numbps >= 25u) {   // absent (or beyond k_max_bit_planes, t1_common.h:70): zeros
-        if (numbps >= 25u && in.length != 0 && numpasses != 0 && writer) atomicOr(a.status, 4u);
+        if (numbps >= 25u && in.length != 0 && numpasses != 0 && writer) atomicOr(a.status, 16u);    // (T1.cpp:1271-1275 refuses it)
         if (threadIdx.x < w)
             for (uint32_t y = 0; y < h; ++y) dst[(size_t)y * a.stride + threadIdx.x] = 0;
         return;

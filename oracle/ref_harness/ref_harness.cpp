@@ -40,6 +40,9 @@ static void msg_err(const char* m, void*) { if (g_verbose) fprintf(stderr, "[gro
 
 extern "C" {
 
+// present in harness builds that honour REF_SGND (signed components); older builds read every sample as unsigned
+int ref_harness_sgnd(void) { return 1; }
+
 int ref_init(int threads, int verbose)
 {
 	g_verbose = verbose;
@@ -236,6 +239,12 @@ static void fill_params(grk_cparameters& p, const EncCfg& c)
 	if (const char* e = getenv("REF_IMG_Y0")) p.image_offset_y0 = (uint32_t)atoi(e);
 }
 
+static bool ref_sgnd()
+{
+	const char* e = getenv("REF_SGND");
+	return e && atoi(e) != 0;
+}
+
 static grk_image* make_image(const EncCfg& c, bool alloc)
 {
 	std::vector<grk_image_cmptparm> cp((size_t)c.C);
@@ -244,11 +253,13 @@ static grk_image* make_image(const EncCfg& c, bool alloc)
 	const uint32_t iy0 = getenv("REF_IMG_Y0") ? (uint32_t)atoi(getenv("REF_IMG_Y0")) : 0;
 	// (sub-sampled components, grk_compress -s: the image area on the reference grid is what the image readers make of a w x h
 	//  component, x1 = x0 + (w - 1) dx + 1, src/bin/image_format: every component then has ceil(x1 / dx) - ceil(x0 / dx) = w columns)
+	// signed components (REF_SGND=1: grk_compress of a signed raw image, -F w,h,c,prec,s): samples read as int8 / int16
+	const bool sgnd = ref_sgnd();
 	unsigned sdx = 1, sdy = 1;
 	if (const char* e = getenv("REF_SUBSAMPLING")) { if (sscanf(e, "%u,%u", &sdx, &sdy) != 2 || !sdx || !sdy) sdx = sdy = 1; }
 	for (auto& q : cp) {
 		q.dx = sdx; q.dy = sdy; q.w = (uint32_t)c.W; q.h = (uint32_t)c.H;
-		q.x0 = ix0; q.y0 = iy0; q.prec = (uint8_t)c.prec; q.sgnd = false;
+		q.x0 = ix0; q.y0 = iy0; q.prec = (uint8_t)c.prec; q.sgnd = sgnd;
 	}
 	// components sub-sampled each in its own way (REF_COMP_SUBSAMPLING="dx0,dy0,dx1,dy1,...": a raw / yuv image, grk_compress -F
 	// w,h,c,prec,u@1x1:2x2:2x2, image_format/RAWFormat.cpp:255-290): W x H is the image area on the reference grid, component c has
@@ -284,6 +295,7 @@ int64_t ref_encode(const EncCfg* cfg, const uint8_t* pixels, uint8_t* out, uint6
 	fill_params(param, c);
 	const int bps = (c.prec + 7) / 8;
 	bool use_image_data = (c.mode == 1) || plugin_tile;
+	const bool sgnd = ref_sgnd();
 	grk_image* image = make_image(c, true);   // multi-tile paths dereference comp->data (TileProcessor.cpp:1137-1147)
 	if (!image) return -2;
 	if (use_image_data) {
@@ -296,7 +308,8 @@ int64_t ref_encode(const EncCfg* cfg, const uint8_t* pixels, uint8_t* out, uint6
 				for (int x = 0; x < cw; ++x) {
 					size_t i = (size_t)y * cw + x;
 					comp->data[(size_t)y * comp->stride + x] =
-						bps == 1 ? (int32_t)src[i] : (int32_t)((const uint16_t*)src)[i];
+						bps == 1 ? (sgnd ? (int32_t)(int8_t)src[i] : (int32_t)src[i])
+								 : (sgnd ? (int32_t)((const int16_t*)src)[i] : (int32_t)((const uint16_t*)src)[i]);
 				}
 			src += (size_t)cw * chh * bps;
 		}

@@ -59,16 +59,27 @@ def lib(threads=0):
 
 def encode(pixels, prec, TW=None, TH=None, irrev=0, numres=6, ht=1, mode=0, rate_algo=0,
            plugin_tile=None, cblk=(0, 0), cblksty=0):
-    """pixels: (C,H,W) uint8/uint16 array. Returns (bytes, seconds)."""
+    """pixels: (C,H,W) uint8/uint16 array, or int8/int16 for signed components (REF_SGND is set for the call; a harness
+    built without it refuses them rather than read them as unsigned).  Returns (bytes, seconds)."""
     L = lib()
     px = np.ascontiguousarray(pixels)
+    if px.dtype.kind == "i" and not reads_signed():
+        raise RuntimeError("this build of the harness reads unsigned samples only (no ref_harness_sgnd)")
     Cn, H, W = px.shape
     cfg = EncCfg(Cn, W, H, TW or W, TH or H, prec, irrev, numres, ht, mode, rate_algo, cblk[0], cblk[1], cblksty)
     cap = px.size * 4 + (1 << 20)
     out = np.zeros(cap, np.uint8)
     secs = C.c_double(0)
-    n = L.ref_encode(C.byref(cfg), px.ctypes.data, out.ctypes.data, cap, C.byref(secs),
-                     plugin_tile)
+    keep = os.environ.get("REF_SGND")
+    os.environ["REF_SGND"] = "1" if px.dtype.kind == "i" else "0"
+    try:
+        n = L.ref_encode(C.byref(cfg), px.ctypes.data, out.ctypes.data, cap, C.byref(secs),
+                         plugin_tile)
+    finally:
+        if keep is None:
+            os.environ.pop("REF_SGND", None)
+        else:
+            os.environ["REF_SGND"] = keep
     if n < 0:
         raise RuntimeError("ref_encode failed rc=%d" % n)
     return out[:n].tobytes(), secs.value
@@ -122,6 +133,23 @@ def decode_planes(j2k, sampling, W, H):
         res.append(flat[at:at + w * h].reshape(h, w).copy())
         at += w * h
     return res
+
+
+def reads_signed():
+    """whether this harness build honours REF_SGND (ref_harness_sgnd is exported); one built from an older recipe does not"""
+    return hasattr(lib(), "ref_harness_sgnd")
+
+
+def with_signed_siz(cs):
+    """The file of the signed image s from grk_compress's file of the unsigned image u = s + 2^(prec-1): the unsigned DC level
+    shift subtracts 2^(prec-1) before the transform, the signed path subtracts nothing, so both code the same coefficients and
+    every byte but Ssiz bit 7 of each component in SIZ (SOC, SIZ marker, Lsiz, Rsiz, 8 x 32-bit sizes, Csiz, then 3 bytes a
+    component) is the same."""
+    b = bytearray(cs)
+    assert b[0:4] == b"\xff\x4f\xff\x51"
+    for c in range((b[40] << 8) | b[41]):
+        b[42 + 3 * c] |= 0x80
+    return bytes(b)
 
 
 def decode(j2k, Cn, H, W):

@@ -66,3 +66,36 @@ def g2_mid(C, H, W, prec, seed=12345):
     is one grk_decompress accepts at every size (the coded size stays within 6 % of plain G2's)."""
     a = g2(C, H, W, prec, seed=seed)
     return np.clip(a, (1 << prec) // 8, 7 * (1 << prec) // 8).astype(a.dtype)
+
+
+KINDS = ("ramp", "noise", "checker", "impulse", "low", "high")
+
+
+def content(kind, C, H, W, prec, seed=1):
+    """Content valid at every precision 1..16 (g2 needs prec >= 5): `ramp` a ramp over the full range with a little noise,
+    `noise` full-range white noise, `checker` a 0 / max checkerboard (cells of 1, 2 and 3 pixels in turn by component),
+    `impulse` a mid-grey field with sparse 0 and max impulses, `low` / `high` the lower / upper rail alone."""
+    rng = np.random.default_rng(seed)
+    top = (1 << prec) - 1
+    dt = np.uint8 if prec <= 8 else np.uint16
+    if kind == "ramp":
+        xy = np.arange(H)[:, None] + np.arange(W)[None, :] + 37 * np.arange(C)[:, None, None]
+        v = xy * top // max(1, W + H + 37 * C - 39)
+        v = v + rng.integers(-(top >> 5) - 1, (top >> 5) + 2, size=(C, H, W))
+    elif kind == "noise":
+        v = rng.integers(0, top + 1, size=(C, H, W))
+    elif kind == "checker":
+        yy, xx = np.mgrid[0:H, 0:W]
+        v = np.stack([(((yy // (c % 3 + 1)) + (xx // (c % 3 + 1)) + c) & 1) * top for c in range(C)])
+    elif kind == "impulse":
+        v = np.full((C, H, W), (top + 1) >> 1, np.int64)
+        r = rng.random((C, H, W))
+        v[r < 0.02] = 0
+        v[r > 0.98] = top
+    elif kind == "low":
+        v = np.zeros((C, H, W), np.int64)
+    elif kind == "high":
+        v = np.full((C, H, W), top, np.int64)
+    else:
+        raise ValueError(kind)
+    return np.clip(v, 0, top).astype(dt)

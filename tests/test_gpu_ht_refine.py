@@ -14,7 +14,8 @@ from test_oracle_ht_refine import make_block, code_block
 pytestmark = pytest.mark.gpu
 
 
-def _case(W, H, L, C, prec, irrev, seed, passes_of):
+def _case(W, H, L, C, prec, irrev, seed, passes_of, cap=14):
+    """cap: the largest Kmax the cleanup magnitudes are drawn for (None: each block's own)"""
     rng = np.random.default_rng(seed)
     p = G.TileParams.make(W, H, C, prec, L, irreversible=irrev)
     blocks, qcd = G.tile_layout(p)
@@ -23,7 +24,7 @@ def _case(W, H, L, C, prec, irrev, seed, passes_of):
     npass_count = {1: 0, 2: 0, 3: 0}
     for i, b in enumerate(blocks):
         bw, bh = b.x1 - b.x0, b.y1 - b.y0
-        kb = min(b.kmax, 14)
+        kb = b.kmax if cap is None else min(b.kmax, cap)
         npasses = passes_of(i)
         mag, sign = make_block(rng, bw, bh, kb, int(rng.integers(0, 5)))
         cup, seg, _ = code_block(mag, sign, b.kmax, npasses) if npasses > 1 else (code_block(mag, sign, b.kmax, 2)[0], b"", 0)

@@ -108,3 +108,81 @@ def test_signed_samples_lossless_vs_reference_decoder(Cn, prec):
     ref = R.decode(cs, Cn, H, W)
     assert np.array_equal(ref, px.astype(np.int32))
     assert np.array_equal(chain.decode_tile_oracle(p, blocks, qcd, table, coded), ref)
+
+
+# ---- missing_msbs other than Kmax - 1 (a stream of another HT encoder: the zero-bit-plane count of each block, k_msbs = band numbps -
+#      block numbps, T1DecompressScheduler.cpp:59) -----------------------------------------------------------------------------
+def _uq_max(coef):
+    """the largest U_q of a block: bit length of 2 * mu - 1 over its samples (0 when none is significant)"""
+    mu = np.abs(coef.astype(np.int64))
+    return int(np.max(np.where(mu > 0, np.ceil(np.log2(np.maximum(2 * mu - 1, 1) + 1)), 0)))
+
+
+@needs_ref
+@pytest.mark.parametrize("kb", [2, 5, 9, 13, 17, 22, 26])
+def test_ht_decode_every_missing_msbs_vs_reference(kb):
+    """A block coded at its own Kmax kb decodes at any missing_msbs from 0 to 29: the oracle and the reference give the same words
+    (aligned at p = 30 - missing_msbs) wherever U_q <= missing_msbs, and both refuse below that (and at 0)."""
+    rng = np.random.default_rng(900 + kb)
+    for (w, h) in ((64, 64), (19, 7), (1, 1)):
+        for mode in (0, 1, 2, 4):
+            coef = _random_block(rng, w, h, kb, mode)
+            cb = O.ht_encode_sm(O.signmag(coef, kb), kb)
+            uq = max(_uq_max(coef), 1)
+            for mm in range(0, 30):
+                got = O.ht_decode_block(cb, mm, w, h)
+                if got is None:
+                    assert mm < uq, (w, h, mode, mm, uq)                # (a quad's U_q can stay below its samples' bit lengths)
+                    with pytest.raises(RuntimeError):
+                        R.ht_decode_block(cb, mm, w, h)
+                    continue
+                assert mm > 0
+                assert np.array_equal(got, R.ht_decode_block(cb, mm, w, h)), (w, h, mode, mm)
+                mu = np.abs(coef.astype(np.int64))
+                want = np.where(mu > 0, np.where(coef < 0, 0x80000000, 0) | ((2 * mu + 1) << (29 - mm)), 0).astype(np.uint32)
+                assert np.array_equal(got, want)
+                assert np.array_equal(O.ht_dequant_rev(got, mm), coef)
+
+
+def _shift_ht_filter(sm, k_msbs):
+    """PostDecompressFilters.h ShiftHTFilter: shift = 31 - (k_msbs + 1), the magnitude shifted down, the sign applied"""
+    v = np.asarray(sm, np.uint32)
+    m = ((v & np.uint32(0x7FFFFFFF)) >> np.uint32(31 - (k_msbs + 1))).astype(np.int64)
+    return np.where(v >> 31, -m, m).astype(np.int32)
+
+
+def _scale_ht_filter(sm, scale):
+    """PostDecompressFilters.h ScaleHTFilter: (float)(int32)(val & 0x7FFFFFFF) * stepsize, negated when the sign bit is set"""
+    v = np.asarray(sm, np.uint32)
+    f = (v & np.uint32(0x7FFFFFFF)).astype(np.int32).astype(np.float32) * np.float32(scale)
+    return np.where(v >> 31, -f, f).astype(np.float32)
+
+
+@pytest.mark.parametrize("prec,L", [(8, 3), (12, 5), (16, 5), (16, 1), (4, 2)])
+def test_ht_dequant_at_k_msbs_below_the_bands(prec, L):
+    """k_msbs < band numbps - 1 (blocks with fewer coded bit-planes than their band): the oracle's reversible dequantisation is the
+    reference's shift at the BLOCK's k_msbs, and its irreversible one the reference's scale at the BAND's step
+    (Quantizer.cpp:54-63: stepsize / 2^(31 - band numbps), whatever the block's k_msbs)."""
+    rng = np.random.default_rng(prec * 10 + L)
+    for irrev in (False, True):
+        p = G.TileParams.make(96, 80, 1, prec, L, irreversible=irrev)
+        blocks, qcd = G.tile_layout(p)
+        for b in blocks[::max(1, len(blocks) // 12)]:
+            for mm in sorted({1, 2, b.kmax // 2, b.kmax - 2, b.kmax - 1}):
+                if mm < 1:
+                    continue
+                kb = mm + 1
+                coef = _random_block(rng, 16, 8, kb, 0)
+                cb = O.ht_encode_sm(O.signmag(coef, kb), kb)
+                sm = O.ht_decode_block(cb, mm, 16, 8)
+                assert sm is not None
+                if R.have_ref():
+                    assert np.array_equal(sm, R.ht_decode_block(cb, mm, 16, 8))
+                if irrev:
+                    scale = chain.band_scale_dec(prec, qcd[chain.band_index(b)], b.kmax)
+                    got = O.ht_dequant_irrev(sm, scale)
+                    assert np.array_equal(got.view(np.int32), _scale_ht_filter(sm, scale).view(np.int32))
+                else:
+                    got = O.ht_dequant_rev(sm, mm)
+                    assert np.array_equal(got, _shift_ht_filter(sm, mm))
+                    assert np.array_equal(got, coef)

@@ -189,3 +189,69 @@ def test_reference_ht_stream_through_t2_reader():
     px = synth.g2(3, 96, 160, 8)
     cs, _ = R.encode(px, 8, numres=5, mode=1)
     assert np.array_equal(_oracle_decode_stream(cs, False), px.astype(np.int32))
+
+
+# ---- deep blocks: 13 .. 24 bit-planes (the GPU keeps int16 workspaces up to 14 planes, int32 beyond; k_max_bit_planes = 25) -------
+def deep_block(rng, w, h, nbps):
+    """a block of moderate coefficients whose plane count one large sample sets to nbps"""
+    coef = (rng.integers(-2000, 2001, size=(h, w)) >> rng.integers(0, 11, size=(h, w))).astype(np.int64)
+    big = int(rng.integers(1 << (nbps - 1), 1 << nbps))
+    coef[int(rng.integers(0, h)), int(rng.integers(0, w))] = big if rng.random() < 0.5 else -big
+    return coef.astype(np.int32)
+
+
+DEEP = [13, 14, 15, 16, 20, 24]
+
+
+@pytest.mark.parametrize("nbps", DEEP)
+@pytest.mark.parametrize("orient", [0, 3])
+def test_t1_decode_deep_planes_equal_reference(nbps, orient):
+    """Full and truncated pass sequences of blocks with 13 .. 24 planes: oracle == reference T1; all passes: lossless."""
+    rng = np.random.default_rng(nbps * 7 + orient)
+    for (w, h) in ((64, 64), (37, 13), (1, 1)):
+        coef = deep_block(rng, w, h, nbps)
+        cb, npass, got_nbps = R.t1_encode_block(coef, orient)
+        assert got_nbps == nbps
+        ref = R.t1_decode_block(cb, npass, nbps, orient, w, h)
+        assert np.array_equal(O.t1_decode_block(cb, npass, nbps, orient, w, h), ref)
+        assert np.array_equal(O.t1_dequant_rev(ref), coef)
+        for keep in (1, 2, npass // 2, npass - 1):
+            if keep >= 1:
+                assert np.array_equal(O.t1_decode_block(cb, keep, nbps, orient, w, h), R.t1_decode_block(cb, keep, nbps, orient, w, h))
+
+
+@pytest.mark.parametrize("nbps", DEEP)
+@pytest.mark.parametrize("sty", STYLES)
+def test_t1_decode_deep_planes_styles_equal_reference(nbps, sty):
+    """Every code-block style at 13 .. 24 planes, all segments and with trailing segments dropped: oracle == reference T1."""
+    rng = np.random.default_rng(nbps * 131 + sty)
+    for (w, h, orient) in ((64, 64, 1), (29, 45, 2)):
+        coef = deep_block(rng, w, h, nbps)
+        cb, segs, got_nbps = R.t1_encode_block_sty(coef, orient, sty)
+        assert got_nbps == nbps
+        for keep in sorted({len(segs), max(1, len(segs) - 1), max(1, len(segs) // 2)}):
+            part = segs[:keep]
+            n = sum(a for a, _ in part)
+            ref = R.t1_decode_block_sty(cb[:n], part, nbps, orient, sty, w, h)
+            got, bad = O.t1_decode_block_sty(cb[:n], part, nbps, orient, sty, w, h)
+            assert bad == 0
+            assert np.array_equal(got, ref), (w, h, keep, len(segs))
+            if keep == len(segs):
+                assert np.array_equal(O.t1_dequant_rev(got), coef)
+
+
+def test_t1_decode_refuses_25_planes_like_the_reference():
+    """numbps >= k_max_bit_planes (31 - T1_NMSEDEC_FRACBITS = 25): the reference's T1 refuses the block (T1.cpp:1271-1275), and so
+    does the oracle; 24 planes still decode."""
+    rng = np.random.default_rng(25)
+    coef = deep_block(rng, 16, 16, 24)
+    cb, npass, nbps = R.t1_encode_block(coef, 0)
+    assert nbps == 24
+    assert np.array_equal(O.t1_decode_block(cb, npass, 24, 0, 16, 16), R.t1_decode_block(cb, npass, 24, 0, 16, 16))
+    for bad_nbps in (25, 26, 31):
+        assert O.t1_decode_block(cb, npass, bad_nbps, 0, 16, 16) is None
+        with pytest.raises(RuntimeError):
+            R.t1_decode_block(cb, npass, bad_nbps, 0, 16, 16)
+        assert O.t1_decode_block_sty(cb, [(len(cb), npass)], bad_nbps, 0, 0, 16, 16)[0] is None
+        with pytest.raises(RuntimeError):
+            R.t1_decode_block_sty(cb, [(len(cb), npass)], bad_nbps, 0, 0, 16, 16)

@@ -230,3 +230,86 @@ def test_whole_codestream_vs_reference_and_roundtrip():
     ref, _ = R.encode(px, 8, numres=5)
     assert oracle_codestream(px, 8, 4) == ref
     assert np.array_equal(R.decode(ref, 3, 192, 320), px.astype(np.int32))
+
+
+def _content_mode(rng, w, h, kmax, m):
+    """the five content modes of the block tests: uniform, shifted down by random amounts, sparse, small, all at the top"""
+    mag = rng.integers(0, 1 << kmax, size=(h, w))
+    if m == 1: mag = mag >> rng.integers(0, kmax, size=(h, w))
+    if m == 2: mag = np.where(rng.random((h, w)) < 0.9, 0, mag)
+    if m == 3: mag = mag & 3
+    if m == 4: mag = np.full((h, w), (1 << kmax) - 1)
+    return mag
+
+
+@needs_ref
+@pytest.mark.ref
+@pytest.mark.parametrize("kmax", range(20, 30))
+def test_ht_encoder_vs_reference_deep_kmax(kmax):
+    """Kmax 20 .. 29 (the random test above stops at 19): the oracle's HT block encoder == ojph_encode_codeblock, every mode.
+    (At 30 the reference's encoder has no bit-plane left below the cleanup pass, p = 30 - missing_msbs = 0, and fails an
+    assertion of its own: outside its domain.)"""
+    rng = np.random.default_rng(kmax)
+    for m in range(5):
+        for (w, h) in ((64, 64), (int(rng.integers(1, 65)), int(rng.integers(1, 65)))):
+            mag = _content_mode(rng, w, h, kmax, m)
+            sm = O.signmag(mag * np.where(rng.random((h, w)) < 0.5, -1, 1), kmax)
+            assert O.ht_encode_sm(sm, kmax) == R.ht_encode_block(sm, kmax), (w, h, kmax, m)
+
+
+# ---- every bit depth: the oracle chain + the product's Tier-2 writer == grk_compress, 1 .. 16 bits (unsigned) and 2 .. 16 (signed) --
+import chain
+import grok_amd as G
+
+
+@needs_ref
+@pytest.mark.ref
+@pytest.mark.parametrize("prec", range(1, 17))
+def test_whole_file_every_bit_depth_vs_reference(prec):
+    """Reversible HT files at every precision, 1 and 3 components, 0 / 1 / 5 levels, every synth.content kind: byte-equal to the
+    reference's; the reference decoder returns the source or refuses the stream (D5: full-range content) exactly where the
+    oracle's decode chain does."""
+    for C in (1, 3):
+        for L in (0, 1, 5):
+            H, W = (37, 53) if L < 5 else (70, 90)
+            for kind in synth.KINDS:
+                px = synth.content(kind, C, H, W, prec, seed=prec * 100 + C * 10 + L)
+                want, _ = R.encode(px, prec, numres=L + 1, mode=1)
+                p, blocks, qcd, table, coded = chain.encode_tile_oracle(px, prec, L)
+                assert G.write_codestream(p, W, H, table, coded) == want, (C, L, kind)
+                try:
+                    ref = R.decode(want, C, H, W)
+                except RuntimeError:
+                    with pytest.raises(AssertionError):
+                        chain.decode_tile_oracle(p, blocks, qcd, table, coded)
+                    continue
+                assert np.array_equal(ref, px.astype(np.int32)), (C, L, kind)
+                assert np.array_equal(chain.decode_tile_oracle(p, blocks, qcd, table, coded), ref), (C, L, kind)
+
+
+@needs_ref
+@pytest.mark.ref
+@pytest.mark.parametrize("prec", range(2, 17))
+def test_whole_file_signed_every_bit_depth_vs_reference(prec):
+    """Signed components at every precision 2 .. 16: the oracle chain's file == grk_compress's file of the unsigned image
+    u = s + 2^(prec-1) with the components marked signed (R.with_signed_siz) -- and == grk_compress of the signed samples
+    themselves where the harness was built with REF_SGND --; grk_decompress returns the signed source from it (or refuses it,
+    D5, exactly where the oracle's decode chain does)."""
+    for C in (1, 3):
+        for L in (0, 2):
+            for kind in ("ramp", "noise", "checker", "low", "high"):
+                u = synth.content(kind, C, 33, 41, prec, seed=prec)
+                px = (u.astype(np.int32) - (1 << (prec - 1))).astype(np.int8 if prec <= 8 else np.int16)
+                want = R.with_signed_siz(R.encode(u, prec, numres=L + 1, mode=1)[0])
+                if R.reads_signed():
+                    assert R.encode(px, prec, numres=L + 1, mode=1)[0] == want, (C, L, kind)
+                p, blocks, qcd, table, coded = chain.encode_tile_oracle(px, prec, L, sgnd=True)
+                assert G.write_codestream(p, 41, 33, table, coded) == want, (C, L, kind)
+                try:
+                    ref = R.decode(want, C, 33, 41)
+                except RuntimeError:
+                    with pytest.raises(AssertionError):
+                        chain.decode_tile_oracle(p, blocks, qcd, table, coded)
+                    continue
+                assert np.array_equal(ref, px.astype(np.int32)), (C, L, kind)
+                assert np.array_equal(chain.decode_tile_oracle(p, blocks, qcd, table, coded), ref), (C, L, kind)

@@ -87,3 +87,22 @@ def test_truncated_and_empty_refinement_segments():
         part = seg[:cut]
         ref = R.ht_decode_block_passes(cup + part, len(cup), len(part), 3, 9, 64, 64)
         assert np.array_equal(O.ht_refine_decode(base, 9, part, 3), ref)
+
+
+@needs_ref
+@pytest.mark.parametrize("kmax", [15, 16, 18, 21, 24, 28])
+def test_refinement_passes_at_deep_kmax(kmax):
+    """Kmax above 14 (the GPU refinement test caps its magnitudes there): oracle == reference decoder, every mode, both pass
+    counts, with cleanup magnitudes up to the decodable top."""
+    rng = np.random.default_rng(7000 + kmax)
+    for (w, h) in ((64, 64), (33, 17), (5, 9), (1, 1)):
+        for mode in range(5):
+            for npasses in (2, 3):
+                mag, sign = make_block(rng, w, h, kmax, mode)
+                cup, seg, _ = code_block(mag, sign, kmax, npasses)
+                mm = kmax - 1
+                ref = R.ht_decode_block_passes(cup + seg, len(cup), len(seg), npasses, mm, w, h)
+                assert ref is not None
+                base = O.ht_decode_block(cup, mm, w, h)
+                assert np.array_equal(base, R.ht_decode_block(cup, mm, w, h))
+                assert np.array_equal(O.ht_refine_decode(base, mm, seg, npasses), ref), (w, h, mode, npasses)

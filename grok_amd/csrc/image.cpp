@@ -7,11 +7,13 @@
 // code-blocks, and where a resolution begins on an odd coordinate the lifting starts with a high-pass sample
 // (tile/TileProcessor.cpp:100-170 tile rectangle; tile/TileComponent.cpp:131-138 bands; WaveletFwd.cpp:884-905).
 // Here the tiles are grouped by geometry, each group goes through grk_amd_encode_tiles as one batch, and the
-// tile-parts are written in tile order (codestream/CodeStreamCompress.cpp:535-603).
-#include "../../include/grok_amd.h"
-#include "geometry.h"
+// tile-parts are written in tile order (codestream/CodeStreamCompress.cpp:535-603); those steps (image.h) serve node.cpp too.
+#include "image.h"
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 using namespace grk_amd;
@@ -25,29 +27,133 @@ extern "C" int grk_amd_same_tile_geometry(const grk_amd_tile_params* a, const gr
     return same_geometry(ga, gb) ? 1 : 0;
 }
 
+// ---- the steps of the whole-image encoders (image.h) -------------------------------------------------------------------------
+int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p)
+{
+    TileGeom geom;
+    const int rc = build_tile_geom(p, geom);
+    if (rc) return rc;
+    size_t k = 0;
+    for (; k < g.geoms.size(); ++k)
+        if (g.geoms[k].p.num_comps == p.num_comps && g.geoms[k].p.mct == p.mct && same_geometry(g.geoms[k], geom)) break;
+    if (k == g.geoms.size()) { g.geoms.push_back(std::move(geom)); g.members.emplace_back(); }
+    g.members[k].push_back((uint32_t)g.of.size());
+    g.of.push_back((uint32_t)k);
+    return GRK_AMD_OK;
+}
+
+int grk_amd::plain_image(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,
+                         std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g)
+{
+    const int64_t nt = grk_amd_layout_num_tiles(im);
+    if (nt < 0) return (int)nt;
+    const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps;
+    if ((flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
+    const uint64_t W = im->x1 - im->x0, H = im->y1 - im->y0;
+    src = SourcePlanes{(const uint8_t*)pixels, (base->prec + 7u) / 8u, {}};
+    for (uint32_t c = 0; c < nc; ++c) src.comp.push_back({c * W * H * src.bps, W, im->x0, im->y0});
+    units.assign(ntiles, Unit{{}, 0});
+    for (uint32_t t = 0; t < ntiles; ++t) {
+        int rc = grk_amd_layout_tile(im, base, t, &units[t].p);
+        if (!rc) rc = add_unit(g, units[t].p);
+        if (rc) return rc;
+    }
+    return GRK_AMD_OK;
+}
+
+void grk_amd::stage_units(const SourcePlanes& src, const std::vector<Unit>& units, const std::vector<uint32_t>& idx, uint8_t* dst, uint32_t threads)
+{
+    const size_t bytes = idx.empty() ? 0 : unit_bytes(units[idx[0]], src.bps), bps = src.bps;
+    (void)parallel_for(threads, threads, [&](size_t j) -> int {
+        for (size_t i = 0; i < idx.size(); ++i) {
+            const grk_amd_tile_params& q = units[idx[i]].p;
+            const size_t y0 = (size_t)q.tile_h * j / threads, y1 = (size_t)q.tile_h * (j + 1) / threads, row = (size_t)q.tile_w * bps;
+            for (uint32_t k = 0; k < q.num_comps; ++k) {
+                const SourcePlanes::Plane& c = src.comp[units[idx[i]].c0 + k];
+                const uint8_t* from = src.px + c.at + ((q.tile_y0 - c.y0) * c.w + (q.tile_x0 - c.x0)) * bps;
+                for (size_t y = y0; y < y1; ++y)
+                    std::memcpy(dst + i * bytes + ((size_t)k * q.tile_h + y) * row, from + y * c.w * bps, row);
+            }
+        }
+        return GRK_AMD_OK;
+    });
+}
+
+int grk_amd::encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const std::vector<Unit>& units, const UnitGroups& g,
+                                std::vector<grk_amd_coded_block>& rows, std::vector<uint8_t>& coded)
+{
+    // unit u's rows start at row_at[u]
+    std::vector<uint64_t> row_at(units.size() + 1, 0);
+    for (size_t u = 0; u < units.size(); ++u) row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].p.num_comps;
+    rows.resize(row_at[units.size()]);
+    coded.clear();
+    std::vector<uint8_t> staging;
+    for (size_t k = 0; k < g.members.size(); ++k) {
+        const auto& G = g.members[k];
+        const grk_amd_tile_params& p = units[G[0]].p;
+        staging.resize(unit_bytes(units[G[0]], src.bps) * G.size());
+        stage_units(src, units, G, staging.data(), 1);
+        const uint64_t bpu = (uint64_t)g.geoms[k].blocks_per_comp * p.num_comps;
+        std::vector<grk_amd_coded_block> table(bpu * G.size());
+        uint64_t total = 0;
+        int rc = grk_amd_encode_tiles(ctx, &p, (uint32_t)G.size(), staging.data(), 0, table.data(), &total);
+        if (rc) return rc;
+        const size_t at = coded.size();
+        coded.resize(at + total);
+        rc = grk_amd_fetch_coded(ctx, coded.data() + at, total);
+        if (rc) return rc;
+        for (size_t i = 0; i < G.size(); ++i)
+            for (uint64_t b = 0; b < bpu; ++b) { rows[row_at[G[i]] + b] = table[i * bpu + b]; rows[row_at[G[i]] + b].offset += at; }
+    }
+    return GRK_AMD_OK;
+}
+
+int64_t grk_amd::frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
+                            const std::vector<uint32_t>& part_len, uint8_t* out, uint64_t cap,
+                            const std::function<int(const std::vector<uint64_t>& at)>& body)
+{
+    const int64_t hdr = grk_amd_write_main_header_layout(im, base, flags, part_len.data(), out, cap);
+    if (hdr < 0) return hdr;
+    std::vector<uint64_t> at(part_len.size() + 1, (uint64_t)hdr);
+    for (size_t t = 0; t < part_len.size(); ++t) at[t + 1] = at[t] + part_len[t];
+    if (at.back() + 2 > cap) return GRK_AMD_ERR_OVERFLOW;
+    const int rc = body(at);
+    if (rc) return rc;
+    uint64_t end = at.back();
+    out[end++] = 0xFF; out[end++] = 0xD9;
+    return (int64_t)end;
+}
+
+int grk_amd::parallel_for(size_t n, uint32_t threads, const std::function<int(size_t)>& fn)
+{
+    threads = (uint32_t)std::max<size_t>(1, std::min<size_t>(threads, n));
+    std::atomic<size_t> next{0};
+    std::atomic<int> rc{GRK_AMD_OK};
+    auto work = [&]() {
+        for (;;) {
+            const size_t i = next.fetch_add(1);
+            if (i >= n || rc.load() != GRK_AMD_OK) return;
+            const int r = fn(i);
+            if (r != GRK_AMD_OK) { int ok = GRK_AMD_OK; (void)rc.compare_exchange_strong(ok, r); }
+        }
+    };
+    std::vector<std::thread> th;
+    for (uint32_t i = 1; i < threads; ++i) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    return rc.load();
+}
+
 extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                         const void* pixels, uint32_t flags, uint8_t* out, uint64_t cap)
 {
     if (!ctx || !im || !base || !pixels || !out) return GRK_AMD_ERR_INVALID;
-    const int64_t nt = grk_amd_layout_num_tiles(im);
-    if (nt < 0) return nt;
-    const uint32_t ntiles = (uint32_t)nt;
-    const uint32_t W = im->x1 - im->x0, H = im->y1 - im->y0;
-    const uint32_t bps = (base->prec + 7u) / 8u, nc = base->num_comps;
-    std::vector<grk_amd_tile_params> tp(ntiles);
-    std::vector<TileGeom> geoms;                       // one per group
-    std::vector<std::vector<uint32_t>> groups;
-    for (uint32_t t = 0; t < ntiles; ++t) {
-        int rc = grk_amd_layout_tile(im, base, t, &tp[t]);
-        if (rc) return rc;
-        TileGeom g;
-        rc = build_tile_geom(tp[t], g);
-        if (rc) return rc;
-        size_t k = 0;
-        for (; k < geoms.size(); ++k) if (same_geometry(geoms[k], g)) break;
-        if (k == geoms.size()) { geoms.push_back(std::move(g)); groups.emplace_back(); }
-        groups[k].push_back(t);
-    }
+    std::vector<Unit> tiles;
+    SourcePlanes src;
+    UnitGroups g;
+    int64_t rc = plain_image(im, base, pixels, flags, tiles, src, g);
+    if (rc) return rc;
+    const uint32_t ntiles = (uint32_t)tiles.size();
     // Tier-2 on the device (grk_amd_assemble_device; GRK_AMD_IMAGE_T2=host: the host writer below, which is also where a layout beyond
     // the device writer's tables goes): every group's finished tile-parts appended in the context's output buffer, then -- their sizes
     // known -- the main header and each tile-part fetched to its place
@@ -57,20 +163,11 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
         std::vector<uint64_t> dev_at(ntiles, 0);
         std::vector<uint8_t> staging;
         uint64_t used = 0;
-        int64_t rc = GRK_AMD_OK;
-        for (size_t k = 0; k < groups.size() && rc >= 0; ++k) {
-            const auto& G = groups[k];
-            const grk_amd_tile_params& p = tp[G[0]];
-            const size_t tile_bytes = (size_t)p.tile_w * p.tile_h * nc * bps;
-            staging.resize(tile_bytes * G.size());
-            for (size_t i = 0; i < G.size(); ++i) {
-                const grk_amd_tile_params& q = tp[G[i]];
-                const size_t ox = q.tile_x0 - im->x0, oy = q.tile_y0 - im->y0;
-                for (uint32_t c = 0; c < nc; ++c)
-                    for (uint32_t y = 0; y < q.tile_h; ++y)
-                        std::memcpy(&staging[i * tile_bytes + ((size_t)c * q.tile_h + y) * q.tile_w * bps],
-                                    (const uint8_t*)pixels + (((size_t)c * H + oy + y) * W + ox) * bps, (size_t)q.tile_w * bps);
-            }
+        for (size_t k = 0; k < g.members.size() && rc >= 0; ++k) {
+            const auto& G = g.members[k];
+            const grk_amd_tile_params& p = tiles[G[0]].p;
+            staging.resize(unit_bytes(tiles[G[0]], src.bps) * G.size());
+            stage_units(src, tiles, G, staging.data(), 1);
             rc = grk_amd_encode_tiles(ctx, &p, (uint32_t)G.size(), staging.data(), 0, nullptr, nullptr);
             if (rc < 0) return rc;
             std::vector<uint32_t> lens(G.size());
@@ -78,61 +175,26 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
             if (rc < 0) break;
             for (size_t i = 0; i < G.size(); ++i) { part_len[G[i]] = lens[i]; dev_at[G[i]] = used; used += lens[i]; }
         }
-        if (rc >= 0) {
-            if ((flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
-            const int64_t hdr = grk_amd_write_main_header_layout(im, base, flags, part_len.data(), out, cap);
-            if (hdr < 0) return hdr;
-            uint64_t at = (uint64_t)hdr;
-            for (uint32_t t = 0; t < ntiles; ++t) at += part_len[t];
-            if (at + 2 > cap) return GRK_AMD_ERR_OVERFLOW;
-            at = (uint64_t)hdr;
-            for (uint32_t t = 0; t < ntiles; ++t) {
-                // (tile-parts that lie one behind the other on the device as in the file go in one piece)
-                uint32_t t1 = t;
-                uint64_t n = part_len[t];
-                while (t1 + 1 < ntiles && dev_at[t1 + 1] == dev_at[t] + n) { n += part_len[t1 + 1]; ++t1; }
-                const int fr = grk_amd_fetch_assembled(ctx, dev_at[t], n, out + at);
-                if (fr) return fr;
-                at += n; t = t1;
-            }
-            out[at++] = 0xFF; out[at++] = 0xD9;
-            return (int64_t)at;
-        }
+        if (rc >= 0)
+            return frame_file(im, base, flags, part_len, out, cap, [&](const std::vector<uint64_t>& at) -> int {
+                for (uint32_t t = 0; t < ntiles; ++t) {
+                    // (tile-parts that lie one behind the other on the device as in the file go in one piece)
+                    uint32_t t1 = t;
+                    uint64_t n = part_len[t];
+                    while (t1 + 1 < ntiles && dev_at[t1 + 1] == dev_at[t] + n) { n += part_len[t1 + 1]; ++t1; }
+                    const int fr = grk_amd_fetch_assembled(ctx, dev_at[t], n, out + at[t]);
+                    if (fr) return fr;
+                    t = t1;
+                }
+                return GRK_AMD_OK;
+            });
         if (rc != GRK_AMD_ERR_UNSUPPORTED) return rc;
     }
-    // per tile: its rows and where its group's coded bytes start in `coded`
-    std::vector<std::vector<grk_amd_coded_block>> rows(ntiles);
-    std::vector<uint8_t> coded, staging;
-    for (size_t k = 0; k < groups.size(); ++k) {
-        const auto& G = groups[k];
-        const grk_amd_tile_params& p = tp[G[0]];
-        const size_t tile_bytes = (size_t)p.tile_w * p.tile_h * nc * bps;
-        staging.resize(tile_bytes * G.size());
-        for (size_t i = 0; i < G.size(); ++i) {
-            const grk_amd_tile_params& q = tp[G[i]];
-            const size_t ox = q.tile_x0 - im->x0, oy = q.tile_y0 - im->y0;
-            for (uint32_t c = 0; c < nc; ++c)
-                for (uint32_t y = 0; y < q.tile_h; ++y)
-                    std::memcpy(&staging[i * tile_bytes + ((size_t)c * q.tile_h + y) * q.tile_w * bps],
-                                (const uint8_t*)pixels + (((size_t)c * H + oy + y) * W + ox) * bps, (size_t)q.tile_w * bps);
-        }
-        const uint64_t bpt = (uint64_t)geoms[k].blocks_per_comp * nc;
-        std::vector<grk_amd_coded_block> table(bpt * G.size());
-        uint64_t total = 0;
-        int rc = grk_amd_encode_tiles(ctx, &p, (uint32_t)G.size(), staging.data(), 0, table.data(), &total);
-        if (rc) return rc;
-        const size_t at = coded.size();
-        coded.resize(at + total);
-        rc = grk_amd_fetch_coded(ctx, coded.data() + at, total);
-        if (rc) return rc;
-        for (size_t i = 0; i < G.size(); ++i) {
-            rows[G[i]].assign(table.begin() + i * bpt, table.begin() + (i + 1) * bpt);
-            for (auto& r : rows[G[i]]) r.offset += at;
-        }
-    }
-    std::vector<grk_amd_coded_block> all;
-    for (uint32_t t = 0; t < ntiles; ++t) all.insert(all.end(), rows[t].begin(), rows[t].end());
-    return grk_amd_write_codestream_layout(im, base, all.data(), coded.data(), flags, out, cap);
+    std::vector<grk_amd_coded_block> rows;
+    std::vector<uint8_t> coded;
+    rc = encode_groups_host(ctx, src, tiles, g, rows, coded);
+    if (rc) return rc;
+    return grk_amd_write_codestream_layout(im, base, rows.data(), coded.data(), flags, out, cap);
 }
 
 // ---- sub-sampled components (4:2:2, 4:2:0, ...) ---------------------------------------------------------------------------
@@ -160,67 +222,28 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
     const bool mct = base->mct && nc >= 3 && runs[0].n >= 3;
     // the image's components in `pixels`: component c is ceil(x1 / dx) - ceil(x0 / dx) columns wide, planes back to back
     auto cdiv = [](uint64_t a, uint64_t b) { return (a + b - 1) / b; };
-    std::vector<uint64_t> cw(nc), ch(nc), cx0(nc), cy0(nc), plane_at(nc + 1, 0);
-    for (uint32_t c = 0; c < nc; ++c) {
-        cx0[c] = cdiv(im->x0, comp_dx[c]); cy0[c] = cdiv(im->y0, comp_dy[c]);
-        cw[c] = cdiv(im->x1, comp_dx[c]) - cx0[c]; ch[c] = cdiv(im->y1, comp_dy[c]) - cy0[c];
-        plane_at[c + 1] = plane_at[c] + cw[c] * ch[c] * bps;
+    SourcePlanes src{(const uint8_t*)pixels, bps, {}};
+    for (uint64_t c = 0, at = 0; c < nc; ++c) {
+        const uint64_t x0 = cdiv(im->x0, comp_dx[c]), y0 = cdiv(im->y0, comp_dy[c]), w = cdiv(im->x1, comp_dx[c]) - x0;
+        src.comp.push_back({at, w, x0, y0});
+        at += w * (cdiv(im->y1, comp_dy[c]) - y0) * bps;
     }
-    struct Unit { uint32_t tile, run; grk_amd_tile_params p; size_t group; };
     std::vector<Unit> units;
-    std::vector<TileGeom> geoms;
-    std::vector<grk_amd_tile_params> gparams;
-    std::vector<std::vector<size_t>> groups;
+    UnitGroups g;
     for (uint32_t t = 0; t < ntiles; ++t)
         for (uint32_t k = 0; k < runs.size(); ++k) {
-            Unit u{t, k, {}, 0};
+            Unit u{{}, runs[k].c0};
             int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].c0], comp_dy[runs[k].c0], t, &u.p);
             if (rc) return rc;
             u.p.num_comps = (uint16_t)runs[k].n;
             u.p.mct = (mct && k == 0) ? 1 : 0;
-            TileGeom g;
-            rc = build_tile_geom(u.p, g);
-            if (rc) return rc;
-            size_t gi = 0;
-            for (; gi < geoms.size(); ++gi)
-                if (gparams[gi].num_comps == u.p.num_comps && gparams[gi].mct == u.p.mct && same_geometry(geoms[gi], g)) break;
-            if (gi == geoms.size()) { geoms.push_back(std::move(g)); gparams.push_back(u.p); groups.emplace_back(); }
-            u.group = gi;
-            groups[gi].push_back(units.size());
             units.push_back(u);
+            rc = add_unit(g, u.p);
+            if (rc) return rc;
         }
-    std::vector<std::vector<grk_amd_coded_block>> rows(units.size());
-    std::vector<uint8_t> coded, staging;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const auto& G = groups[gi];
-        const grk_amd_tile_params& p = units[G[0]].p;
-        const size_t unit_bytes = (size_t)p.tile_w * p.tile_h * p.num_comps * bps;
-        staging.resize(unit_bytes * G.size());
-        for (size_t i = 0; i < G.size(); ++i) {
-            const Unit& u = units[G[i]];
-            for (uint32_t k = 0; k < u.p.num_comps; ++k) {
-                const uint32_t c = runs[u.run].c0 + k;
-                const size_t ox = u.p.tile_x0 - cx0[c], oy = u.p.tile_y0 - cy0[c];
-                for (uint32_t y = 0; y < u.p.tile_h; ++y)
-                    std::memcpy(&staging[i * unit_bytes + ((size_t)k * u.p.tile_h + y) * u.p.tile_w * bps],
-                                (const uint8_t*)pixels + plane_at[c] + ((oy + y) * cw[c] + ox) * bps, (size_t)u.p.tile_w * bps);
-            }
-        }
-        const uint64_t bpu = (uint64_t)geoms[gi].blocks_per_comp * p.num_comps;
-        std::vector<grk_amd_coded_block> table(bpu * G.size());
-        uint64_t total = 0;
-        int rc = grk_amd_encode_tiles(ctx, &p, (uint32_t)G.size(), staging.data(), 0, table.data(), &total);
-        if (rc) return rc;
-        const size_t at = coded.size();
-        coded.resize(at + total);
-        rc = grk_amd_fetch_coded(ctx, coded.data() + at, total);
-        if (rc) return rc;
-        for (size_t i = 0; i < G.size(); ++i) {
-            rows[G[i]].assign(table.begin() + i * bpu, table.begin() + (i + 1) * bpu);
-            for (auto& r : rows[G[i]]) r.offset += at;
-        }
-    }
-    std::vector<grk_amd_coded_block> all;                       // tile-major, within a tile component-major (the runs in order)
-    for (size_t i = 0; i < units.size(); ++i) all.insert(all.end(), rows[i].begin(), rows[i].end());
-    return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, all.data(), coded.data(), flags, out, cap);
+    std::vector<grk_amd_coded_block> rows;                   // tile-major, within a tile component-major (the runs in order)
+    std::vector<uint8_t> coded;
+    const int rc = encode_groups_host(ctx, src, units, g, rows, coded);
+    if (rc) return rc;
+    return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, cap);
 }

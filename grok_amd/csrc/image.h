@@ -1,0 +1,64 @@
+// grok_amd/csrc/image.h -- the steps every whole-image encoder takes (grk_amd_encode_image, grk_amd_encode_image_subsampled,
+// grk_amd_node_encode_image; private to the library, defined in image.cpp): cut the image into units, group them by geometry, stage
+// each group's pixels, code each group as one grk_amd_encode_tiles batch, frame the file.
+#pragma once
+#include "../../include/grok_amd.h"
+#include "geometry.h"
+#include <functional>
+#include <vector>
+
+#pragma GCC visibility push(hidden)       // nothing declared below is part of the library's interface
+namespace grk_amd {
+
+// A unit of coding: a tile, or a run of a tile's components of one size (sub-sampled images) -- its parameters and its first
+// component in the caller's image
+struct Unit { grk_amd_tile_params p; uint32_t c0; };
+
+// The caller's planar image: component c's samples start comp[c].at bytes into `px`, in rows of comp[c].w samples, the first of
+// them at (comp[c].x0, comp[c].y0) on the component's grid
+struct SourcePlanes {
+    const uint8_t* px;
+    uint32_t bps;                                  // bytes per sample
+    struct Plane { uint64_t at, w, x0, y0; };
+    std::vector<Plane> comp;
+};
+
+struct UnitGroups {
+    std::vector<TileGeom> geoms;                   // [group]: its first unit's geometry
+    std::vector<uint32_t> of;                      // [unit]: its group
+    std::vector<std::vector<uint32_t>> members;    // [group]: its units in unit order
+};
+
+// the next unit, of parameters `p`, into its group: the first whose num_comps, mct and geometry (same_geometry) it shares -- one
+// batch of grk_amd_encode_tiles --, or a new one.  GRK_AMD_OK or build_tile_geom's error.
+int add_unit(UnitGroups& g, const grk_amd_tile_params& p);
+
+// A plain image (component-major planar, tight, W x H per component): one unit per tile with all components, grouped.
+// A file with TLM holds at most 255 tiles (one-byte Ttlm): GRK_AMD_ERR_UNSUPPORTED before any work.
+int plain_image(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,
+                std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g);
+
+inline size_t unit_bytes(const Unit& u, uint32_t bps) { return (size_t)u.p.tile_w * u.p.tile_h * u.p.num_comps * bps; }
+
+// units[idx[i]]'s rows out of the source into `dst`, tight, component-major, unit i at i x unit_bytes (a group's units are of one
+// size); each of `threads` threads copies its share of the rows of every unit component
+void stage_units(const SourcePlanes& src, const std::vector<Unit>& units, const std::vector<uint32_t>& idx, uint8_t* dst, uint32_t threads);
+
+// Every group through grk_amd_encode_tiles with its first unit's parameters, its table and coded bytes to the host: `rows` are the
+// units' rows one after the other in unit order, their offsets into `coded` (the groups' bytes back to back).  What the host
+// codestream writers take.
+int encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const std::vector<Unit>& units, const UnitGroups& g,
+                       std::vector<grk_amd_coded_block>& rows, std::vector<uint8_t>& coded);
+
+// The file around tile-parts of known sizes: main header (TLM from `part_len`), `body(at)` puts tile-part t at out + at[t]
+// (at[ntiles]: their end), EOC.  The file's length, or the header writer's error (TLM over 255 tiles: GRK_AMD_ERR_UNSUPPORTED),
+// GRK_AMD_ERR_OVERFLOW when `cap` cannot hold it, or the body's error.
+int64_t frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags, const std::vector<uint32_t>& part_len,
+                   uint8_t* out, uint64_t cap, const std::function<int(const std::vector<uint64_t>& at)>& body);
+
+// fn(i) for i in [0, n) on up to `threads` host threads, the caller's among them; items are handed out by a counter and the
+// first error wins (no item starts after it)
+int parallel_for(size_t n, uint32_t threads, const std::function<int(size_t)>& fn);
+
+} // namespace grk_amd
+#pragma GCC visibility pop

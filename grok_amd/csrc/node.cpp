@@ -12,12 +12,11 @@
 //     GPUs) into the frame's WRITER device, which rotates with the frame number so that consecutive frames spread over all
 //     GPUs' links; the writer brings everything to the host in one piece and runs Tier-2 for all tiles -- north_star's
 //     "gather of coded tile-parts over xGMI" in a single process, without RCCL.
-// A device may appear more than once in the list (two contexts on one GPU): every code path runs on a one-GPU box.
-#include "../../include/grok_amd.h"
-#include "geometry.h"
+// A device may appear more than once in the list (two contexts on one GPU): every code path runs on a one-GPU box.  Grouping
+// by geometry, staging, file framing and the host's thread pool are the steps image.h shares with grk_amd_encode_image.
+#include "image.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -61,14 +60,7 @@ bool pin_ensure(grk_amd_ctx* ctx, uint8_t*& p, size_t& cap, size_t n)
 
 constexpr int kRing = 3;       // a worker's encodes rotate kRing + 1 buffer sets (a regular tiling has at most four geometry groups)
 
-// rows of `w` bytes, `src_pitch` apart -> tight; a few threads when there is enough to copy (one core moves ~10 GB/s, a worker of
-// BASELINE configs[3] stages 100 MB per image)
-void copy_rows(uint8_t* dst, const uint8_t* src, size_t w, size_t src_pitch, size_t rows)
-{
-    for (size_t y = 0; y < rows; ++y) std::memcpy(dst + y * w, src + y * src_pitch, w);
-}
-
-// the same, keeping the first `keep` bytes when the buffer has to grow
+// pin_ensure, keeping the first `keep` bytes when the buffer has to grow
 bool pin_grow(grk_amd_ctx* ctx, uint8_t*& p, size_t& cap, size_t n, size_t keep)
 {
     if (n <= cap) return true;
@@ -89,27 +81,6 @@ struct TileJob {               // what the workers leave per tile
     std::vector<grk_amd_tp_segment> segs;      // ... and the segments it is made of
     uint64_t dev_at = 0;                       // Tier-2 on the device: where the finished tile-part lies in its worker's assembled bytes
 };
-
-// fn(t) for t in [0, n) on up to `threads` host threads; the first error wins
-template <class F> int parallel_tiles(uint32_t n, uint32_t threads, F fn)
-{
-    threads = std::max(1u, std::min(threads, n));
-    std::atomic<uint32_t> next{0};
-    std::atomic<int> rc{GRK_AMD_OK};
-    auto work = [&]() {
-        for (;;) {
-            const uint32_t t = next.fetch_add(1);
-            if (t >= n || rc.load() != GRK_AMD_OK) return;
-            const int r = fn(t);
-            if (r != GRK_AMD_OK) { int ok = GRK_AMD_OK; (void)rc.compare_exchange_strong(ok, r); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (uint32_t i = 1; i < threads; ++i) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-    return rc.load();
-}
 
 bool is_pinned(const void* p)
 {
@@ -251,29 +222,17 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
                                  const void* pixels, int pixels_device, uint32_t flags, uint8_t* out, uint64_t cap, bool host_t2)
 {
     if (nd->w.empty() || !im || !base || !pixels || !out) return GRK_AMD_ERR_INVALID;
-    const int64_t nt = grk_amd_layout_num_tiles(im);
-    if (nt < 0) return nt;
-    const uint32_t ntiles = (uint32_t)nt, R = (uint32_t)nd->w.size();
     const bool gather = (flags & GRK_AMD_NODE_GATHER) != 0;
     const uint32_t cs_flags = flags & ~GRK_AMD_NODE_GATHER;
-    if ((cs_flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
+    // the tiles, grouped by geometry (image.h): a batch of grk_amd_encode_tiles shares one
+    std::vector<Unit> tiles;
+    SourcePlanes planes;
+    UnitGroups groups;
+    if (const int rc = plain_image(im, base, pixels, cs_flags, tiles, planes, groups)) return rc;
+    const std::vector<TileGeom>& geoms = groups.geoms;
+    const uint32_t ntiles = (uint32_t)tiles.size(), R = (uint32_t)nd->w.size();
     const uint32_t W = im->x1 - im->x0, H = im->y1 - im->y0;
-    const uint32_t bps = (base->prec + 7u) / 8u, nc = base->num_comps;
-    // the tiles, grouped by geometry (image.cpp): a batch of grk_amd_encode_tiles shares one
-    std::vector<grk_amd_tile_params> tp(ntiles);
-    std::vector<TileGeom> geoms;
-    std::vector<uint32_t> group_of(ntiles);
-    for (uint32_t t = 0; t < ntiles; ++t) {
-        int rc = grk_amd_layout_tile(im, base, t, &tp[t]);
-        if (rc) return rc;
-        TileGeom g;
-        rc = build_tile_geom(tp[t], g);
-        if (rc) return rc;
-        size_t k = 0;
-        for (; k < geoms.size(); ++k) if (same_geometry(geoms[k], g)) break;
-        if (k == geoms.size()) geoms.push_back(std::move(g));
-        group_of[t] = (uint32_t)k;
-    }
+    const uint32_t bps = planes.bps, nc = base->num_comps;
     std::vector<TileJob> jobs(ntiles);
     const uint32_t writer = (uint32_t)(nd->frame++ % R);
     // gather: worker r's bytes land at gather_at[r] of the writer's device buffer; an upper bound of what a worker can produce
@@ -284,7 +243,7 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
         for (uint32_t r = 0; r < R; ++r) {
             uint64_t ub = 0;
             for (uint32_t t = r; t < ntiles; t += R)
-                ub += (uint64_t)tp[t].tile_w * tp[t].tile_h * nc * bps * 2u + (uint64_t)geoms[group_of[t]].blocks_per_comp * nc * 64u + (1u << 20);
+                ub += (uint64_t)tiles[t].p.tile_w * tiles[t].p.tile_h * nc * bps * 2u + (uint64_t)geoms[groups.of[t]].blocks_per_comp * nc * 64u + (1u << 20);
             gather_at[r + 1] = gather_at[r] + ((ub + 255u) & ~255ull);
         }
         auto& ww = nd->w[writer];
@@ -316,9 +275,9 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
             if (gather && geoms.size() > 1 && grk_amd_get_pipelining(w.ctx) < kRing) (void)grk_amd_set_pipelining(w.ctx, kRing);
             for (size_t k = 0; k < geoms.size() && rc == GRK_AMD_OK; ++k) {
                 std::vector<uint32_t> mine;
-                for (uint32_t t = r; t < ntiles; t += R) if (group_of[t] == k) mine.push_back(t);
+                for (uint32_t t = r; t < ntiles; t += R) if (groups.of[t] == k) mine.push_back(t);
                 if (mine.empty()) continue;
-                const grk_amd_tile_params& p = tp[mine[0]];
+                const grk_amd_tile_params& p = tiles[mine[0]].p;
                 const size_t tile_bytes = (size_t)p.tile_w * p.tile_h * nc * bps;
                 const void* enc_px = nullptr;
                 if (pixels_device < 0 && mine.size() == 1 && p.tile_w == W && p.tile_h == H) {
@@ -327,25 +286,9 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
                     enc_px = pixels;
                 } else if (pixels_device < 0) {
                     if (!pin_ensure(w.ctx, w.pin_px, w.pin_px_cap, tile_bytes * mine.size())) { rc = GRK_AMD_ERR_NOMEM; break; }
-                    // the tiles' rows out of the caller's image into pinned memory; several threads when it is much, each taking
-                    // its share of the rows of every tile component (one tile of 8192 x 8192 x 3 is 200 MB for one worker)
-                    const size_t nthr = tile_bytes * mine.size() >= (32u << 20) ? 4 : 1;
-                    auto stage = [&](size_t j) {
-                        for (size_t i = 0; i < mine.size(); ++i) {
-                            const grk_amd_tile_params& q = tp[mine[i]];
-                            const size_t ox = q.tile_x0 - im->x0, oy = q.tile_y0 - im->y0;
-                            const size_t y0 = (size_t)q.tile_h * j / nthr, y1 = (size_t)q.tile_h * (j + 1) / nthr;
-                            for (uint32_t c = 0; c < nc; ++c)
-                                copy_rows(w.pin_px + i * tile_bytes + ((size_t)c * q.tile_h + y0) * q.tile_w * bps,
-                                          (const uint8_t*)pixels + (((size_t)c * H + oy + y0) * W + ox) * bps, (size_t)q.tile_w * bps, (size_t)W * bps, y1 - y0);
-                        }
-                    };
-                    if (nthr > 1) {
-                        std::vector<std::thread> st;
-                        for (size_t j = 1; j < nthr; ++j) st.emplace_back(stage, j);
-                        stage(0);
-                        for (auto& t : st) t.join();
-                    } else stage(0);
+                    // the tiles' rows out of the caller's image into pinned memory; four threads when it is much (one core moves
+                    // ~10 GB/s; one tile of 8192 x 8192 x 3 is 200 MB for one worker)
+                    stage_units(planes, tiles, mine, w.pin_px, tile_bytes * mine.size() >= (32u << 20) ? 4 : 1);
                     enc_px = w.pin_px;
                 } else {
                     // device-resident image: 2-D copies (rows of the tile out of rows of the image) on this worker's copy stream
@@ -361,7 +304,7 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
                     }
                     hipError_t e = hipSuccess;
                     for (size_t i = 0; i < mine.size() && e == hipSuccess; ++i) {
-                        const grk_amd_tile_params& q = tp[mine[i]];
+                        const grk_amd_tile_params& q = tiles[mine[i]].p;
                         const size_t ox = q.tile_x0 - im->x0, oy = q.tile_y0 - im->y0;
                         for (uint32_t c = 0; c < nc && e == hipSuccess; ++c)
                             e = hipMemcpy2DAsync((uint8_t*)w.dev_px + i * tile_bytes + (size_t)c * q.tile_h * q.tile_w * bps, (size_t)q.tile_w * bps,
@@ -435,7 +378,7 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
                 // device to device to the frame's writer): a plan needs the table only
                 for (size_t i = 0; i < mine.size() && rc == GRK_AMD_OK; ++i) {
                     TileJob& j = jobs[mine[i]];
-                    const int64_t need = plan_tile_part(tp[mine[i]], mine[i], cs_flags, j.rows.data(), j.lit, j.segs);
+                    const int64_t need = plan_tile_part(tiles[mine[i]].p, mine[i], cs_flags, j.rows.data(), j.lit, j.segs);
                     if (need < 0) rc = (int)need; else { j.part_len = (uint64_t)need; j.planned = true; }
                 }
                 if (!gather) {
@@ -461,61 +404,48 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
         if (rcs[r]) { nd->err = std::string("worker ") + std::to_string(r) + ": " + grk_amd_last_error(nd->w[r].ctx); return rcs[r]; }
 
     trace.mark("workers done");
+    const uint32_t host_threads = std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency() / 4u));
+    std::vector<uint32_t> sizes(ntiles);
     if (dev_t2) {
-        std::vector<uint32_t> sizes(ntiles);
         for (uint32_t t = 0; t < ntiles; ++t) sizes[t] = (uint32_t)jobs[t].part_len;
-        const int64_t hdr = grk_amd_write_main_header_layout(im, base, cs_flags, sizes.data(), out, cap);
-        if (hdr < 0) return hdr;
-        std::vector<uint64_t> at(ntiles + 1, (uint64_t)hdr);
-        for (uint32_t t = 0; t < ntiles; ++t) at[t + 1] = at[t] + jobs[t].part_len;
-        if (at[ntiles] + 2 > cap) return GRK_AMD_ERR_OVERFLOW;
-        int rc = GRK_AMD_OK;
-        if (R == 1 && geoms.size() == 1) {
-            // one worker, one batch: its assembled bytes ARE the file behind the main header -- one DMA into pinned memory, pinned
-            // chunks on several copy threads into pageable memory
-            rc = grk_amd_fetch_assembled(nd->w[0].ctx, 0, asm_used[0], out + hdr);
-        } else if (is_pinned(out)) {
-            for (uint32_t t = 0; t < ntiles && rc == GRK_AMD_OK; ++t)
-                rc = grk_amd_fetch_assembled_async(nd->w[t % R].ctx, jobs[t].dev_at, jobs[t].part_len, out + at[t]);
-            for (uint32_t r = 0; r < R; ++r) { const int sr = grk_amd_synchronize(nd->w[r].ctx); if (rc == GRK_AMD_OK) rc = sr; }
-        } else {
-            // every worker's assembled bytes over its own link into its pinned buffer, then the tile-parts -- whole, not 49 152
-            // code-blocks each -- to their places on the host's threads
-            for (uint32_t r = 0; r < R && rc == GRK_AMD_OK; ++r) {
-                auto& w = nd->w[r];
-                if (!pin_ensure(w.ctx, w.pin_coded, w.pin_coded_cap, asm_used[r] + 16)) { rc = GRK_AMD_ERR_NOMEM; break; }
-                rc = grk_amd_fetch_assembled_async(w.ctx, 0, asm_used[r], w.pin_coded);
-            }
-            for (uint32_t r = 0; r < R; ++r) { const int sr = grk_amd_synchronize(nd->w[r].ctx); if (rc == GRK_AMD_OK) rc = sr; }
-            if (rc == GRK_AMD_OK) {
-                struct Piece { uint32_t t; uint64_t o, n; };
-                std::vector<Piece> pieces;
-                for (uint32_t t = 0; t < ntiles; ++t)
-                    for (uint64_t o = 0; o < jobs[t].part_len; o += 2u << 20) pieces.push_back(Piece{t, o, std::min<uint64_t>(2u << 20, jobs[t].part_len - o)});
-                std::atomic<size_t> next{0};
-                auto work = [&]() {
-                    for (;;) {
-                        const size_t k = next.fetch_add(1);
-                        if (k >= pieces.size()) break;
+        return frame_file(im, base, cs_flags, sizes, out, cap, [&](const std::vector<uint64_t>& at) -> int {
+            int rc = GRK_AMD_OK;
+            if (R == 1 && geoms.size() == 1) {
+                // one worker, one batch: its assembled bytes ARE the file behind the main header -- one DMA into pinned memory, pinned
+                // chunks on several copy threads into pageable memory
+                rc = grk_amd_fetch_assembled(nd->w[0].ctx, 0, asm_used[0], out + at[0]);
+            } else if (is_pinned(out)) {
+                for (uint32_t t = 0; t < ntiles && rc == GRK_AMD_OK; ++t)
+                    rc = grk_amd_fetch_assembled_async(nd->w[t % R].ctx, jobs[t].dev_at, jobs[t].part_len, out + at[t]);
+                for (uint32_t r = 0; r < R; ++r) { const int sr = grk_amd_synchronize(nd->w[r].ctx); if (rc == GRK_AMD_OK) rc = sr; }
+            } else {
+                // every worker's assembled bytes over its own link into its pinned buffer, then the tile-parts -- whole, not 49 152
+                // code-blocks each -- to their places on the host's threads, in pieces of up to 2 MB
+                for (uint32_t r = 0; r < R && rc == GRK_AMD_OK; ++r) {
+                    auto& w = nd->w[r];
+                    if (!pin_ensure(w.ctx, w.pin_coded, w.pin_coded_cap, asm_used[r] + 16)) { rc = GRK_AMD_ERR_NOMEM; break; }
+                    rc = grk_amd_fetch_assembled_async(w.ctx, 0, asm_used[r], w.pin_coded);
+                }
+                for (uint32_t r = 0; r < R; ++r) { const int sr = grk_amd_synchronize(nd->w[r].ctx); if (rc == GRK_AMD_OK) rc = sr; }
+                if (rc == GRK_AMD_OK) {
+                    struct Piece { uint32_t t; uint64_t o, n; };
+                    std::vector<Piece> pieces;
+                    for (uint32_t t = 0; t < ntiles; ++t)
+                        for (uint64_t o = 0; o < jobs[t].part_len; o += 2u << 20) pieces.push_back(Piece{t, o, std::min<uint64_t>(2u << 20, jobs[t].part_len - o)});
+                    rc = parallel_for(pieces.size(), host_threads, [&](size_t k) -> int {
                         const Piece& pc = pieces[k];
                         std::memcpy(out + at[pc.t] + pc.o, nd->w[pc.t % R].pin_coded + jobs[pc.t].dev_at + pc.o, pc.n);
-                    }
-                };
-                const uint32_t nthr = (uint32_t)std::min<size_t>(std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency() / 4u)), pieces.size());
-                std::vector<std::thread> pool;
-                for (uint32_t i = 1; i < nthr; ++i) pool.emplace_back(work);
-                work();
-                for (auto& th2 : pool) th2.join();
+                        return GRK_AMD_OK;
+                    });
+                }
             }
-        }
-        if (rc) {
-            for (uint32_t r = 0; r < R; ++r) if (*grk_amd_last_error(nd->w[r].ctx)) { nd->err = std::string("worker ") + std::to_string(r) + ": " + grk_amd_last_error(nd->w[r].ctx); break; }
-            return rc;
-        }
-        trace.mark("header + tile-parts fetched");
-        uint64_t end = at[ntiles];
-        out[end++] = 0xFF; out[end++] = 0xD9;
-        return (int64_t)end;
+            if (rc) {
+                for (uint32_t r = 0; r < R; ++r) if (*grk_amd_last_error(nd->w[r].ctx)) { nd->err = std::string("worker ") + std::to_string(r) + ": " + grk_amd_last_error(nd->w[r].ctx); break; }
+                return rc;
+            }
+            trace.mark("header + tile-parts fetched");
+            return GRK_AMD_OK;
+        });
     }
     // Where every tile's coded bytes are on the host: with parallel writers in its own worker's pinned buffer (fetched over
     // that worker's PCIe link), in the gather form in the writer's (one piece per worker, brought over by the writer's device).
@@ -543,24 +473,17 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
     // threads; the plans give the tile-parts' sizes, those the main header (TLM) and every tile-part's place; then the segments --
     // ~100 MB of coded bytes per 8K frame -- are copied to where they belong by all the threads, whatever the number of tiles (r05
     // ran Tier-2 twice, once to size and once to write, and one tile's bytes were one thread's work: 12.8 ms per 8K frame as one tile).
-    const uint32_t host_threads = std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency() / 4u));
-    int rc = parallel_tiles(ntiles, host_threads, [&](uint32_t t) -> int {
+    int rc = parallel_for(ntiles, host_threads, [&](size_t t) -> int {
         if (jobs[t].planned) return GRK_AMD_OK;
-        const int64_t need = plan_tile_part(tp[t], t, cs_flags, jobs[t].rows.data(), jobs[t].lit, jobs[t].segs);
+        const int64_t need = plan_tile_part(tiles[t].p, (uint32_t)t, cs_flags, jobs[t].rows.data(), jobs[t].lit, jobs[t].segs);
         if (need < 0) return (int)need;
         jobs[t].part_len = (uint64_t)need;
         return GRK_AMD_OK;
     });
     if (rc) return rc;
-    std::vector<uint32_t> sizes(ntiles);
     for (uint32_t t = 0; t < ntiles; ++t) sizes[t] = (uint32_t)jobs[t].part_len;
-    const int64_t hdr = grk_amd_write_main_header_layout(im, base, cs_flags, sizes.data(), out, cap);
-    if (hdr < 0) return hdr;
-    std::vector<uint64_t> at(ntiles + 1, (uint64_t)hdr);
-    for (uint32_t t = 0; t < ntiles; ++t) at[t + 1] = at[t] + jobs[t].part_len;
-    if (at[ntiles] + 2 > cap) return GRK_AMD_ERR_OVERFLOW;
-    {
-        // pieces of ~2 MB of output: (tile, first segment, segment count), handed out by a counter
+    return frame_file(im, base, cs_flags, sizes, out, cap, [&](const std::vector<uint64_t>& at) -> int {
+        // pieces of ~2 MB of output: (tile, first segment, segment count)
         struct Piece { uint32_t t; size_t s0, s1; };
         std::vector<Piece> pieces;
         for (uint32_t t = 0; t < ntiles; ++t) {
@@ -571,27 +494,15 @@ static int64_t node_encode_image(grk_amd_node* nd, const grk_amd_image_layout* i
                 if (bytes >= (2u << 20) || i + 1 == sg.size()) { pieces.push_back(Piece{t, s0, i + 1}); s0 = i + 1; bytes = 0; }
             }
         }
-        std::atomic<size_t> next{0};
-        auto work = [&]() {
-            for (;;) {
-                const size_t k = next.fetch_add(1);
-                if (k >= pieces.size()) break;
-                const Piece& pc = pieces[k];
-                const TileJob& j = jobs[pc.t];
-                uint8_t* const dst = out + at[pc.t];
-                for (size_t i = pc.s0; i < pc.s1; ++i) {
-                    const grk_amd_tp_segment& sgm = j.segs[i];
-                    std::memcpy(dst + sgm.dst, (sgm.kind ? src[pc.t] : j.lit.data()) + sgm.src, sgm.len);
-                }
+        return parallel_for(pieces.size(), host_threads, [&](size_t k) -> int {
+            const Piece& pc = pieces[k];
+            const TileJob& j = jobs[pc.t];
+            uint8_t* const dst = out + at[pc.t];
+            for (size_t i = pc.s0; i < pc.s1; ++i) {
+                const grk_amd_tp_segment& sgm = j.segs[i];
+                std::memcpy(dst + sgm.dst, (sgm.kind ? src[pc.t] : j.lit.data()) + sgm.src, sgm.len);
             }
-        };
-        std::vector<std::thread> pool;
-        const uint32_t nthr = (uint32_t)std::min<size_t>(host_threads, pieces.size());
-        for (uint32_t i = 1; i < nthr; ++i) pool.emplace_back(work);
-        work();
-        for (auto& th2 : pool) th2.join();
-    }
-    uint64_t end = at[ntiles];
-    out[end++] = 0xFF; out[end++] = 0xD9;
-    return (int64_t)end;
+            return GRK_AMD_OK;
+        });
+    });
 }

@@ -176,6 +176,28 @@ def test_encode_image_takes_the_device_route_and_the_host_writer_agrees(monkeypa
     assert c.encode_image(layout, base, px, flags) == dev
 
 
+@pytest.mark.parametrize("route", ["device", "host"])
+def test_tlm_with_more_than_255_tiles_is_unsupported(monkeypatch, route):
+    """Ttlm is one byte: a file with TLM holds at most 255 tiles.  256 tiles of 16 x 16 with TLM are GRK_AMD_ERR_UNSUPPORTED from
+    grk_amd_encode_image and from a one-worker node on either Tier-2 route; the same image without TLM is coded."""
+    monkeypatch.setenv("GRK_AMD_IMAGE_T2", route)
+    monkeypatch.setenv("GRK_AMD_NODE_T2", route)
+    px = synth.g2(1, 256, 256, 8, seed=41)
+    layout = G.ImageLayout.make(256, 256, 16, 16)
+    base = G.TileParams.make(1, 1, 1, 8, 2)
+    c = U.ctx()
+    with pytest.raises(RuntimeError, match=r"failed: -2 "):
+        c.encode_image(layout, base, px, G.CS_TLM)
+    want = c.encode_image(layout, base, px, G.CS_PLT)
+    node = G.Node([0])
+    try:
+        with pytest.raises(RuntimeError, match=r"failed: -2 \(unsupported layout"):
+            node.encode_image(layout, base, px, G.CS_TLM)
+        assert bytes(node.encode_image(layout, base, px, G.CS_PLT)) == want
+    finally:
+        node.close()
+
+
 @pytest.mark.parametrize("C,W,H,prec,L,org,cblk", [
     (1, 1, 1, 8, 1, (0, 0), (6, 6)),          # one sample: resolutions without a band, packets that are just the "not empty" bit
     (3, 5, 3, 8, 3, (0, 0), (6, 6)),          # more levels than the tile has rows to halve

@@ -115,6 +115,8 @@ def lib():
         L.grk_amd_set_decode_segments.argtypes = [vp, vp, vp, u32]
         L.grk_amd_set_decode_steps.argtypes = [vp, vp, u32]
         L.grk_amd_decode_region.argtypes = [vp, PP, vp, vp, u64, i32, u32, u32, u32, u32, vp, i32]
+        L.grk_amd_set_decode_reduce.argtypes = [vp, u32]
+        L.grk_amd_reduced_tile_rect.argtypes = [PP] + [u32] + [C.POINTER(u32)] * 4
         L.grk_amd_set_overlap.argtypes = [vp, i32]
         L.grk_amd_set_decode_planes16.argtypes = [vp, i32]
         if hasattr(L, "grk_amd_plane_sample_bytes"):      # (absent from older builds loaded through GRK_AMD_LIB for A/B timing)
@@ -185,6 +187,15 @@ def tile_layout(params):
     if rc < 0:
         raise ValueError("grk_amd_tile_layout failed: %d" % rc)
     return list(blocks), list(qcd)[:3 * params.num_levels + 1]
+
+
+def reduced_tile_rect(params, reduce):
+    """(x0, y0, w, h) of the tile at 1 / 2^reduce of its size, on the reduced grid (grk_amd_reduced_tile_rect)."""
+    v = [C.c_uint32(0) for _ in range(4)]
+    rc = lib().grk_amd_reduced_tile_rect(C.byref(params), int(reduce), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise ValueError("grk_amd_reduced_tile_rect(reduce=%d) failed: %d" % (reduce, rc))
+    return tuple(x.value for x in v)
 
 
 CS_TLM, CS_PLT, CS_SOP, CS_EPH = 1, 2, 4, 8
@@ -299,6 +310,7 @@ class Context:
         if rc != 0:
             raise RuntimeError("grk_amd_create(device=%d) failed: %d (no usable HIP device?)" % (device, rc))
         self._h = h
+        self._reduce = 0
 
     def close(self):
         if self._h:
@@ -458,13 +470,28 @@ class Context:
         t = np.ascontiguousarray(table)
         cb = np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else np.ascontiguousarray(coded)
         dt = np.uint8 if params.prec <= 8 else np.uint16
-        out = np.zeros((ntiles, params.num_comps, params.tile_h, params.tile_w), dt)
+        _, _, w, h = self.decode_size(params)
+        out = np.zeros((ntiles, params.num_comps, h, w), dt)
         self._check(self._L.grk_amd_decode_tiles(self._h, C.byref(params), ntiles, t.ctypes.data, cb.ctypes.data, cb.size, 0,
                                                  out.ctypes.data, 0), "decode_tiles")
         return out
 
+    def set_decode_reduce(self, reduce):
+        """Decode at 1 / 2^reduce of the size from now on (grk_decompress -r; 0: full resolution).  Tables, coded bytes and
+        segment lists stay the full tile's; decode_host returns, and decode_device writes, the reduced tiles."""
+        self._check(self._L.grk_amd_set_decode_reduce(self._h, int(reduce)), "set_decode_reduce")
+        self._reduce = int(reduce)
+
+    def decode_size(self, params):
+        """(x0, y0, w, h) of the tile the decode calls return under the current reduce setting (the full tile's size when the
+        setting exceeds the tile's levels: the call itself refuses that)."""
+        if self._reduce and self._reduce <= params.num_levels:
+            return reduced_tile_rect(params, self._reduce)
+        return params.tile_x0, params.tile_y0, params.tile_w, params.tile_h
+
     def decode_region_host(self, params, table, coded, x0, y0, x1, y1):
-        """Windowed decode of one tile -> pixels (C, y1 - y0, x1 - x0)."""
+        """Windowed decode of one tile -> pixels (C, y1 - y0, x1 - x0); the window is in the coordinates of the tile decode_size
+        describes (the reduced tile under set_decode_reduce)."""
         t = np.ascontiguousarray(table)
         cb = np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else np.ascontiguousarray(coded)
         dt = np.uint8 if params.prec <= 8 else np.uint16

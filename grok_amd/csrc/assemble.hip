@@ -104,7 +104,7 @@ int assemble_enqueue(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntil
 int assemble_check(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index)
 {
     if (!c || !p || !ntiles || !tile_index) return GRK_AMD_ERR_INVALID;
-    if (!c->have_geom || !same_params(c->gp, *p) || ntiles != c->last_ntiles || !c->last_nblocks)
+    if (!c->have_geom || !same_params(c->gp, *p) || c->geom.reduce || ntiles != c->last_ntiles || !c->last_nblocks)
         return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_assemble_device assembles the grk_amd_encode_tiles call before it: same tiles, same parameters");
     return GRK_AMD_OK;
 }

@@ -102,6 +102,9 @@ struct grk_amd_ctx {
     std::vector<float> dec_steps;                           // decode: band step sizes as the host holds them (optional), [comp][band]
     std::vector<uint32_t> dec_seg_first;                    // Part-1 decode: codeword segments (optional), [nblocks + 1]
     std::vector<grk_amd_segment> dec_segs;
+    uint32_t dec_reduce = 0;                                // decode at 1 / 2^dec_reduce of the size (grk_amd_set_decode_reduce)
+    std::vector<uint32_t> red_seg_first;                    // ... the segment list of the blocks that decode keeps (decode_impl)
+    std::vector<grk_amd_segment> red_segs;
     DevBuf dec_seg_dev;
     HtClass ht_classes[kHtMaxClasses]; uint32_t ht_num_classes = 0;   // block classes of K3: {top resolution, rest} x {LDS small, large}
     uint8_t ht_class_top[kHtMaxClasses] = {}, ht_class_big[kHtMaxClasses] = {};
@@ -231,7 +234,7 @@ bool host_is_pinned(const void* p);                                             
 int copy_h2d(grk_amd_ctx* c, void* dst, const void* src, size_t bytes);                                          // context.hip
 int copy_d2h(grk_amd_ctx* c, void* dst, const void* src, size_t bytes);                                          // context.hip
 bool same_params(const grk_amd_tile_params& a, const grk_amd_tile_params& b);                                    // context.hip
-int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p);                                                   // context.hip
+int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t reduce = 0);                              // context.hip
 int probe_streams(grk_amd_ctx* c);                                                                               // streams.hip
 int vetted_stream(grk_amd_ctx* c, hipStream_t* cur, const std::vector<hipStream_t>& against, int* replaced);     // streams.hip
 int join_side(grk_amd_ctx* c);                                                                                   // streams.hip

@@ -147,9 +147,10 @@ bool same_params(const grk_amd_tile_params& a, const grk_amd_tile_params& b)
            std::memcmp(a.precinct_exp, b.precinct_exp, sizeof a.precinct_exp) == 0;
 }
 
-int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p)
+int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t reduce)
 {
-    if (c->have_geom && same_params(c->gp, *p)) return GRK_AMD_OK;
+    if (c->have_geom && same_params(c->gp, *p) && c->geom.reduce == reduce) return GRK_AMD_OK;
+    if (reduce > p->num_levels) return fail(c, GRK_AMD_ERR_INVALID, "decode reduce above the tile's number of DWT levels");
     // the tables rebuilt below may still be read by K3 launches of a pipelined predecessor on the side streams
     if (c->side) HIP_TRY(c, hipStreamSynchronize(c->side), "sync side stream");
     if (c->side2) HIP_TRY(c, hipStreamSynchronize(c->side2), "sync side stream 2");
@@ -158,6 +159,11 @@ int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p)
     c->have_geom = false;                      // valid again only once every table below is on the device
     int rc = build_tile_geom(*p, c->geom);
     if (rc != GRK_AMD_OK) return fail(c, rc, "unsupported tile parameters");
+    if (reduce) {
+        TileGeom full = std::move(c->geom);
+        rc = reduce_tile_geom(full, reduce, c->geom);
+        if (rc != GRK_AMD_OK) return fail(c, rc, "reduced geometry");
+    }
     c->gp = *p;
     const TileGeom& g = c->geom;
     c->h_desc.clear();
@@ -226,10 +232,11 @@ int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p)
             for (const auto& b : g.blocks_comp0) {
                 float scale = 1.0f;
                 const uint32_t bi = b.res == 0 ? 0u : 3u * b.res - 2u + (b.band - 1u);
-                if (p->irreversible && c->dec_steps.size() == (size_t)p->num_comps * g.num_bands_total) {
-                    scale = c->dec_steps[(size_t)k * g.num_bands_total + bi];      // the host's TileBand::stepsize, fix-ups included
+                // (both lists are over the full tile's bands, also for a reduced decode: its bands are their first ones)
+                if (p->irreversible && c->dec_steps.size() == (size_t)p->num_comps * g.full_bands_total) {
+                    scale = c->dec_steps[(size_t)k * g.full_bands_total + bi];     // the host's TileBand::stepsize, fix-ups included
                 } else if (p->irreversible) {
-                    const uint16_t wq = (c->dec_qcd.size() == g.num_bands_total) ? c->dec_qcd[bi] : g.qcd_words[bi];
+                    const uint16_t wq = (c->dec_qcd.size() == g.full_bands_total) ? c->dec_qcd[bi] : g.qcd_words[bi];
                     const double step = (1.0 + (wq & 0x7FF) / 2048.0) * std::pow(2.0, (int)p->prec - (int)(wq >> 11));
                     scale = (float)step;
                     if (!p->reserved[0]) scale /= (float)(1u << (31 - b.kmax));     // HT only (Quantizer.cpp:54-63)

@@ -108,7 +108,8 @@ int run_idwt(grk_amd_ctx* c, uint32_t nplanes, const void* d_mallat, void* d_out
 }
 
 // The pinned tables of this call with the caller's rows in them (room for K5's index behind the rows); the set's last upload
-// has been waited for (two calls ago: long done)
+// has been waited for (two calls ago: long done).  nblocks counts the rows of the context's geometry (a reduced one: fewer than
+// the caller's table holds)
 int stage_table(grk_amd_ctx* c, const grk_amd_coded_block* table, uint64_t nblocks, grk_amd_ctx::DecUpload** out)
 {
     grk_amd_ctx::DecUpload* u = &c->dec_up[c->dec_turn++ & 1u];
@@ -122,7 +123,15 @@ int stage_table(grk_amd_ctx* c, const grk_amd_coded_block* table, uint64_t nbloc
         HIP_TRY(c, hipHostGetDevicePointer((void**)&u->dp, u->p, 0), "map pinned tables");
         u->cap = need;
     }
-    std::memcpy(u->p, table, (size_t)nblocks * sizeof(grk_amd_coded_block));
+    const TileGeom& g = c->geom;
+    if (g.reduce) {             // the caller's rows are the full tile's: each component keeps its first blocks_per_comp rows
+        const uint64_t groups = nblocks / g.blocks_per_comp;
+        for (uint64_t k = 0; k < groups; ++k)
+            std::memcpy(u->p + k * g.blocks_per_comp * sizeof(grk_amd_coded_block), table + k * g.full_blocks_per_comp,
+                        (size_t)g.blocks_per_comp * sizeof(grk_amd_coded_block));
+    } else {
+        std::memcpy(u->p, table, (size_t)nblocks * sizeof(grk_amd_coded_block));
+    }
     *out = u;
     return GRK_AMD_OK;
 }
@@ -171,20 +180,22 @@ int run_ht_decode(grk_amd_ctx* c, uint32_t ntiles, grk_amd_ctx::DecUpload* up, c
     a.irreversible = g.p.irreversible;
     a.h16 = h16 ? 1 : 0;
     a.h16_bias = (h16 && c->dwt_pk) ? 2048 : 32768;        // (pk16.h kPkDecodeBound + 1: the inverse transform runs on packed pairs)
-    if (!c->dec_seg_first.empty()) {
+    const std::vector<uint32_t>& seg_first = g.reduce ? c->red_seg_first : c->dec_seg_first;
+    const std::vector<grk_amd_segment>& segs = g.reduce ? c->red_segs : c->dec_segs;
+    if (!seg_first.empty()) {
         // HT blocks with refinement passes: segment 0 = the cleanup pass, segment 1 = SigProp (+ MagRef), end to end
-        if (c->dec_seg_first.size() != nblocks + 1 || c->dec_seg_first.back() != c->dec_segs.size())
+        if (seg_first.size() != nblocks + 1 || seg_first.back() != segs.size())
             return fail(c, GRK_AMD_ERR_INVALID, "segment list does not match the number of blocks");
         std::vector<uint2> ref(nblocks, make_uint2(0u, 1u));
         for (uint64_t i = 0; i < nblocks; ++i) {
-            const uint32_t s0 = c->dec_seg_first[i], ns = c->dec_seg_first[i + 1] - s0;
+            const uint32_t s0 = seg_first[i], ns = seg_first[i + 1] - s0;
             if (ns > 2) return fail(c, GRK_AMD_ERR_INVALID, "an HT code-block has at most two codeword segments");
             uint64_t sum = 0;
-            for (uint32_t k = 0; k < ns; ++k) sum += c->dec_segs[s0 + k].length;
+            for (uint32_t k = 0; k < ns; ++k) sum += segs[s0 + k].length;
             if (ns && sum != table[i].length) return fail(c, GRK_AMD_ERR_INVALID, "segment lengths do not add up to the block's length");
-            if (ns == 2 && c->dec_segs[s0 + 1].length) {
-                const uint32_t passes = 1u + std::min<uint32_t>(c->dec_segs[s0 + 1].numpasses, 2u);
-                ref[i] = make_uint2(c->dec_segs[s0 + 1].length, passes);
+            if (ns == 2 && segs[s0 + 1].length) {
+                const uint32_t passes = 1u + std::min<uint32_t>(segs[s0 + 1].numpasses, 2u);
+                ref[i] = make_uint2(segs[s0 + 1].length, passes);
                 a.max_refine_bytes = std::max(a.max_refine_bytes, ref[i].x);
             }
         }
@@ -319,15 +330,17 @@ int run_t1_decode(grk_amd_ctx* c, uint32_t ntiles, grk_amd_ctx::DecUpload* up, c
     a.mallat = (int32_t*)d_mallat; a.stride = g.stride; a.pitch = g.plane_elems;
     a.irreversible = g.p.irreversible;
     a.cblksty = g.p.reserved[1];
-    if (!c->dec_seg_first.empty()) {
-        if (c->dec_seg_first.size() != nblocks + 1 || c->dec_seg_first.back() != c->dec_segs.size())
+    const std::vector<uint32_t>& seg_first = g.reduce ? c->red_seg_first : c->dec_seg_first;
+    const std::vector<grk_amd_segment>& segs = g.reduce ? c->red_segs : c->dec_segs;
+    if (!seg_first.empty()) {
+        if (seg_first.size() != nblocks + 1 || seg_first.back() != segs.size())
             return fail(c, GRK_AMD_ERR_INVALID, "segment list does not match the number of blocks");
         static_assert(sizeof(grk_amd_segment) == sizeof(uint2), "segments are {bytes, passes}");
-        const size_t nf = c->dec_seg_first.size() * 4, ns = c->dec_segs.size() * sizeof(grk_amd_segment);
+        const size_t nf = seg_first.size() * 4, ns = segs.size() * sizeof(grk_amd_segment);
         const size_t ns_off = (nf + 15) & ~(size_t)15;
         HIP_TRY(c, c->dec_seg_dev.ensure(ns_off + ns + 16), "alloc segment list");
-        HIP_TRY(c, hipMemcpyAsync(c->dec_seg_dev.p, c->dec_seg_first.data(), nf, hipMemcpyHostToDevice, c->stream), "upload segment index");
-        if (ns) HIP_TRY(c, hipMemcpyAsync((char*)c->dec_seg_dev.p + ns_off, c->dec_segs.data(), ns, hipMemcpyHostToDevice, c->stream), "upload segments");
+        HIP_TRY(c, hipMemcpyAsync(c->dec_seg_dev.p, seg_first.data(), nf, hipMemcpyHostToDevice, c->stream), "upload segment index");
+        if (ns) HIP_TRY(c, hipMemcpyAsync((char*)c->dec_seg_dev.p + ns_off, segs.data(), ns, hipMemcpyHostToDevice, c->stream), "upload segments");
         a.seg_first = (const uint32_t*)c->dec_seg_dev.p;
         a.segs = (const uint2*)((const char*)c->dec_seg_dev.p + ns_off);
     }
@@ -434,9 +447,24 @@ static int decode_impl(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nt
     if (c->overlap && c->side && c->seq_index < 0 && c->stream_probe && c->probed_main != c->stream && probe_streams(c) != GRK_AMD_OK) {
         c->stream_probe = 0; (void)hipGetLastError();
     }
-    rc = ensure_geom(c, p); if (rc) return rc;
+    rc = ensure_geom(c, p, c->dec_reduce); if (rc) return rc;
     const TileGeom& g = c->geom;
     const uint32_t nplanes = ntiles * g.p.num_comps;
+    if (g.reduce && !c->dec_seg_first.empty()) {
+        // the segment list is over the full tile's blocks: the kept blocks' segments, in the order of the kept rows
+        const uint64_t groups = (uint64_t)ntiles * g.p.num_comps;
+        if (c->dec_seg_first.size() != groups * g.full_blocks_per_comp + 1 || c->dec_seg_first.back() != c->dec_segs.size())
+            return fail(c, GRK_AMD_ERR_INVALID, "segment list does not match the number of blocks");
+        c->red_seg_first.clear(); c->red_segs.clear();
+        for (uint64_t k = 0; k < groups; ++k)
+            for (uint64_t i = k * g.full_blocks_per_comp, e = i + g.blocks_per_comp; i < e; ++i) {
+                c->red_seg_first.push_back((uint32_t)c->red_segs.size());
+                c->red_segs.insert(c->red_segs.end(), c->dec_segs.begin() + c->dec_seg_first[i], c->dec_segs.begin() + c->dec_seg_first[i + 1]);
+            }
+        c->red_seg_first.push_back((uint32_t)c->red_segs.size());
+    } else {
+        c->red_seg_first.clear(); c->red_segs.clear();
+    }
     const uint32_t bps = (g.p.prec + 7u) / 8u;
     const bool fuse_out = g.p.num_levels >= 1 && bps <= 2 && c->fuse_egress;
     // region decode: the blocks no sample of the window depends on are not decoded, the synthesis covers what is needed
@@ -530,6 +558,7 @@ int grk_amd_decode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             // what the caller set on the context applies to the frame wherever it is decoded
             if (k->dec_qcd != c->dec_qcd || k->dec_steps != c->dec_steps) { k->dec_qcd = c->dec_qcd; k->dec_steps = c->dec_steps; k->have_geom = false; }
             if (k->dec_seg_first != c->dec_seg_first) k->dec_seg_first = c->dec_seg_first;
+            k->dec_reduce = c->dec_reduce;
             if (k->dec_segs.size() != c->dec_segs.size() ||
                 (!c->dec_segs.empty() && std::memcmp(k->dec_segs.data(), c->dec_segs.data(), c->dec_segs.size() * sizeof(c->dec_segs[0])) != 0))
                 k->dec_segs = c->dec_segs;
@@ -632,6 +661,19 @@ int grk_amd_set_decode_steps(grk_amd_ctx* c, const float* steps, uint32_t count)
     c->dec_steps.assign(steps, steps + count);
     c->have_geom = false;                  // the per-block dequantisation scales are rebuilt on the next call
     return GRK_AMD_OK;
+}
+
+int grk_amd_set_decode_reduce(grk_amd_ctx* c, uint32_t reduce)
+{
+    if (!c) return GRK_AMD_ERR_INVALID;
+    c->dec_reduce = reduce;                // checked against each call's number of levels (decode_impl -> ensure_geom)
+    return GRK_AMD_OK;
+}
+
+int grk_amd_reduced_tile_rect(const grk_amd_tile_params* p, uint32_t reduce, uint32_t* x0, uint32_t* y0, uint32_t* w, uint32_t* h)
+{
+    if (!p || !x0 || !y0 || !w || !h) return GRK_AMD_ERR_INVALID;
+    return reduced_tile_rect(*p, reduce, x0, y0, w, h);
 }
 
 int grk_amd_set_decode_segments(grk_amd_ctx* c, const uint32_t* first_segment, const grk_amd_segment* segments, uint32_t nblocks)

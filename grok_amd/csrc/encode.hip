@@ -296,7 +296,8 @@ int grk_amd_fetch_coded_async(grk_amd_ctx* c, uint8_t* dst, uint64_t nbytes)
 
 int grk_amd_fetch_coefficients(grk_amd_ctx* c, uint32_t comp, int32_t* dst, uint32_t dst_stride)
 {
-    if (!c || !dst || !c->have_geom || !c->last_nblocks || comp >= c->geom.p.num_comps || dst_stride < c->geom.p.tile_w)
+    // (after a reduced decode the context holds the reduced geometry, not the encoded tile's)
+    if (!c || !dst || !c->have_geom || c->geom.reduce || !c->last_nblocks || comp >= c->geom.p.num_comps || dst_stride < c->geom.p.tile_w)
         return GRK_AMD_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     { const int jr = join_side(c); if (jr) return jr; }
@@ -337,7 +338,7 @@ static double band_norm(uint32_t orient, uint32_t level, bool reversible)
 
 int grk_amd_block_distortion(grk_amd_ctx* c, double* out, uint64_t cap)
 {
-    if (!c || !out || !c->have_geom || !c->last_nblocks || cap < c->last_nblocks) return GRK_AMD_ERR_INVALID;
+    if (!c || !out || !c->have_geom || c->geom.reduce || !c->last_nblocks || cap < c->last_nblocks) return GRK_AMD_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     { const int jr = join_side(c); if (jr) return jr; }
     const TileGeom& g = c->geom;

@@ -198,6 +198,41 @@ static int build_tile_geom_uncached(const grk_amd_tile_params& p, TileGeom& g)
         }
     }
     g.blocks_per_comp = nblk;
+    g.reduce = 0;
+    g.full_blocks_per_comp = nblk;
+    g.full_bands_total = g.num_bands_total;
+    return GRK_AMD_OK;
+}
+
+int reduced_tile_rect(const grk_amd_tile_params& p, uint32_t reduce, uint32_t* x0, uint32_t* y0, uint32_t* w, uint32_t* h)
+{
+    if (reduce > p.num_levels || p.tile_w == 0 || p.tile_h == 0) return GRK_AMD_ERR_INVALID;
+    const uint64_t X0 = p.tile_x0, Y0 = p.tile_y0, X1 = X0 + p.tile_w, Y1 = Y0 + p.tile_h;
+    auto lo = [reduce](uint64_t v) { return (uint32_t)((v + (1ull << reduce) - 1) >> reduce); };
+    *x0 = lo(X0); *y0 = lo(Y0);
+    *w = lo(X1) - lo(X0); *h = lo(Y1) - lo(Y0);
+    return GRK_AMD_OK;
+}
+
+int reduce_tile_geom(const TileGeom& full, uint32_t reduce, TileGeom& g)
+{
+    if (full.reduce != 0) return GRK_AMD_ERR_INVALID;
+    const uint32_t L = full.p.num_levels;
+    if (reduce > L) return GRK_AMD_ERR_INVALID;
+    g = full;
+    if (reduce == 0) return GRK_AMD_OK;
+    const uint32_t Lr = L - reduce;
+    const ResGeom& top = full.res[Lr];             // resolution L - reduce is the reduced tile itself (res_lo nests: ceil of ceil)
+    g.p.num_levels = (uint8_t)Lr;
+    g.p.tile_x0 = top.x0; g.p.tile_y0 = top.y0;
+    g.p.tile_w = top.w; g.p.tile_h = top.h;
+    g.res.resize(Lr + 1);
+    g.blocks_per_comp = Lr < L ? full.res[Lr + 1].band[0].first_block : full.blocks_per_comp;
+    g.blocks_comp0.resize(g.blocks_per_comp);
+    g.num_bands_total = 3 * Lr + 1;
+    g.stride = (g.p.tile_w + 31u) & ~31u;
+    g.plane_elems = (uint64_t)g.stride * g.p.tile_h;
+    g.reduce = reduce;
     return GRK_AMD_OK;
 }
 

@@ -44,10 +44,24 @@ struct TileGeom {
     uint32_t blocks_per_comp;
     uint16_t qcd_words[3 * GRK_AMD_MAX_LEVELS + 1];
     uint32_t num_bands_total;
+    // decode at reduced resolution (reduce_tile_geom): the full tile's resolutions 0 .. L - reduce; qcd_words, the blocks' Kmax and
+    // steps stay the full tile's, the caller's tables and band lists are over the full tile (full_* of them)
+    uint32_t reduce = 0;
+    uint32_t full_blocks_per_comp = 0;
+    uint32_t full_bands_total = 0;
 };
 
 // returns GRK_AMD_OK or an error code
 int build_tile_geom(const grk_amd_tile_params& p, TileGeom& g);
+
+// The tile at 1 / 2^reduce of its size (the reference's cp_reduce: TileComponent.cpp:69-170 with numResolutionsToDecompress
+// = numresolutions - reduce): the reduced tile's p (levels L - reduce, bounds ceil(x / 2^reduce), rectceildivpow2 of
+// CodeStreamDecompress.cpp:412-420), resolutions 0 .. L - reduce of the full tile with their bands, precincts, Kmax and steps, and
+// the first blocks of each component -- resolution-major, so a prefix -- whose Mallat positions lie in the top-left corner of
+// the full layout.  Not build_tile_geom of a smaller tile: the default step sizes depend on each band's decomposition level.
+int reduce_tile_geom(const TileGeom& full, uint32_t reduce, TileGeom& out);
+// the reduced tile's bounds on the reduced grid (GRK_AMD_ERR_INVALID for reduce > num_levels)
+int reduced_tile_rect(const grk_amd_tile_params& p, uint32_t reduce, uint32_t* x0, uint32_t* y0, uint32_t* w, uint32_t* h);
 
 // the same sub-band partition, block partition and lifting variants: what one batch of grk_amd_encode_tiles needs
 bool same_geometry(const TileGeom& a, const TileGeom& b);

@@ -29,6 +29,13 @@
 #include <dirent.h>
 #include <dlfcn.h>
 
+// the tree's components [comp0, comp0 + p->num_comps), which all have p's geometry (the whole tree: comp0 = 0), and the tree of an
+// image whose components are sub-sampled each in its own way -- decoded at 1 / 2^reduce of their size (0: full size)
+static int decode_tree_comps(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const gra_plugin_tile* tile, uint32_t comp0,
+                             const uint8_t* band_numbps, uint32_t nbands, uint32_t reduce, void* pixels, int pixels_on_device);
+static int decode_tree_subsampled(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                                  const gra_plugin_tile* tile, const uint8_t* band_numbps, uint32_t nbands, uint32_t reduce, void* planes);
+
 namespace {
 
 grk_amd_ctx* g_ctx = nullptr;          // the device Grok named (grk_plugin_init_info.deviceId): the single-file entry points
@@ -649,6 +656,15 @@ int dec_init_decompressors(gra_header_info* h, gra_image* img)
     return 0;
 }
 
+// the host's component is the rectangle p covers at 1 / 2^reduce of its size (with an origin off the 2^reduce grid the host's reduced
+// header can size a component one column / row larger, SIZMarker.cpp:54: such a component is left to the host)
+bool reduced_matches(const grk_amd_tile_params& p, uint32_t reduce, const gra_image_comp& ck)
+{
+    uint32_t x0, y0, w, h;
+    if (grk_amd_reduced_tile_rect(&p, reduce, &x0, &y0, &w, &h) != GRK_AMD_OK) return false;
+    return ck.w == w && ck.h == h && (!reduce || (ck.x0 == x0 && ck.y0 == y0));
+}
+
 // The plugin side of Grok's decode protocol (grk_decompress.cpp:792-1008 is the host side):
 //   1. GRK_DECODE_HEADER: the host opens the stream, reads the main header and calls init_decompressors_func
 //   2. GRK_DECODE_T2 with our tile tree attached: the host runs Tier-2 and decompress_synch_plugin_with_host copies
@@ -682,11 +698,18 @@ int32_t decompress_file(void* params, DecodeUserCallback cb, const char* in_path
     // the stream's main header, from the file the host was pointed at (grk_decompress -i: parameters->infile,
     // grk_decompress.cpp:552).  A host that decodes from memory gives us nothing to read it from: declined.
     StreamHeader sh;
+    uint32_t reduce = 0;
     {
         const gra_decompress_parameters_head* dp = static_cast<const gra_decompress_parameters_head*>(params);
         const char* path = in_path ? in_path : !dp ? nullptr : dp->infile[0] ? dp->infile : dp->core.infile[0] ? dp->core.infile : nullptr;
         if (!path || !read_stream_header(path, sh) || sh.overrides) return clean(-1);
+        reduce = dp ? dp->core.cp_reduce : 0;
     }
+    // grk_decompress -r N (cp_reduce): the host reports its components at the reduced size, but its tile -- the tree its Tier-2
+    // synch walks, plugin_bridge.cpp:24-80 -- keeps every resolution.  The tree below is therefore the FULL tile's, from the image
+    // bounds on the reference grid, and the decode returns it reduced (grk_amd_set_decode_reduce).  N >= numresolutions is refused
+    // by the host itself (CodeStreamDecompress.cpp:1604)
+    if (reduce >= h.numresolutions) return clean(-1);
     // the scope of the hot path: one tile (anywhere on the canonical grid), equal full-resolution components, one
     // layer, one codeword segment per block (the host's bridge throws on more); irreversible only for classic
     // blocks (the reference's own HT + 9/7 encoder is broken, D1: there is no stream to be compatible with)
@@ -709,6 +732,12 @@ int32_t decompress_file(void* params, DecodeUserCallback cb, const char* in_path
     // alike: the tile IS the component rectangle; else: the tile on the reference grid, the components derived from it
     tp.tile_w = alike ? c0.w : img->x1 - img->x0; tp.tile_h = alike ? c0.h : img->y1 - img->y0; tp.num_comps = img->numcomps;
     tp.tile_x0 = alike ? c0.x0 : img->x0; tp.tile_y0 = alike ? c0.y0 : img->y0;
+    if (reduce && alike) {                                // the full component rectangle: ceil(image bounds / d)
+        const uint32_t x0 = (uint32_t)(((uint64_t)img->x0 + c0.dx - 1) / c0.dx), x1 = (uint32_t)(((uint64_t)img->x1 + c0.dx - 1) / c0.dx);
+        const uint32_t y0 = (uint32_t)(((uint64_t)img->y0 + c0.dy - 1) / c0.dy), y1 = (uint32_t)(((uint64_t)img->y1 + c0.dy - 1) / c0.dy);
+        if (x1 <= x0 || y1 <= y0) return clean(-1);
+        tp.tile_x0 = x0; tp.tile_y0 = y0; tp.tile_w = x1 - x0; tp.tile_h = y1 - y0;
+    }
     tp.prec = c0.prec; tp.sgnd = c0.sgnd; tp.irreversible = h.irreversible ? 1 : 0; tp.mct = h.mct ? 1 : 0;
     tp.num_levels = (uint8_t)(h.numresolutions - 1);
     uint32_t ew = 0, eh = 0;
@@ -731,6 +760,7 @@ int32_t decompress_file(void* params, DecodeUserCallback cb, const char* in_path
     std::vector<grk_amd_block> layout;
     int64_t nb = 0;
     if (alike) {
+        if (tp.num_levels < reduce || !reduced_matches(tp, reduce, c0)) return clean(-1);
         nb = grk_amd_tile_num_blocks(&tp);
         if (nb <= 0) return clean(-1);
         layout.resize((size_t)nb);
@@ -744,7 +774,7 @@ int32_t decompress_file(void* params, DecodeUserCallback cb, const char* in_path
             cdx[c] = (uint8_t)ck.dx; cdy[c] = (uint8_t)ck.dy;
             if (grk_amd_layout_tile_comp(&iml, &tp, ck.dx, ck.dy, 0, &cps[c]) != GRK_AMD_OK) return clean(-1);
             cps[c].num_comps = 1; cps[c].mct = 0;
-            if (cps[c].tile_w != ck.w || cps[c].tile_h != ck.h) return clean(-1);      // (the host's component is not the rectangle SIZ implies)
+            if (!reduced_matches(cps[c], reduce, ck)) return clean(-1);      // (the host's component is not the rectangle SIZ implies)
             const int64_t nbc = grk_amd_tile_num_blocks(&cps[c]);
             if (nbc <= 0) return clean(-1);
             const size_t at = layout.size();
@@ -803,18 +833,22 @@ int32_t decompress_file(void* params, DecodeUserCallback cb, const char* in_path
     }
     const size_t bps = (tp.prec + 7u) / 8u;
     std::vector<size_t> plane_at(tp.num_comps + 1u, 0);
-    for (uint32_t c = 0; c < tp.num_comps; ++c)
-        plane_at[c + 1] = plane_at[c] + (alike ? (size_t)tp.tile_w * tp.tile_h : (size_t)cps[c].tile_w * cps[c].tile_h) * bps;
+    std::vector<uint32_t> plane_w(tp.num_comps), plane_h(tp.num_comps);      // the decoded (reduced) components
+    for (uint32_t c = 0; c < tp.num_comps; ++c) {
+        uint32_t rx0, ry0;
+        if (grk_amd_reduced_tile_rect(alike ? &tp : &cps[c], reduce, &rx0, &ry0, &plane_w[c], &plane_h[c]) != GRK_AMD_OK) return done(-1);
+        plane_at[c + 1] = plane_at[c] + (size_t)plane_w[c] * plane_h[c] * bps;
+    }
     std::vector<uint8_t> px(plane_at[tp.num_comps]);
-    const int drc = alike ? grk_amd_plugin_tile_decode_qcd(g_ctx, &tp, tree, band_numbps.empty() ? nullptr : band_numbps.data(),
-                                                           (uint32_t)band_numbps.size(), px.data(), 0)
-                          : grk_amd_plugin_tile_decode_subsampled(g_ctx, &tp, cdx, cdy, tree, band_numbps.empty() ? nullptr : band_numbps.data(),
-                                                                  (uint32_t)band_numbps.size(), px.data());
+    const uint8_t* const bn = band_numbps.empty() ? nullptr : band_numbps.data();
+    const int drc = alike ? decode_tree_comps(g_ctx, &tp, tree, 0, bn, (uint32_t)band_numbps.size(), reduce, px.data(), 0)
+                          : decode_tree_subsampled(g_ctx, &tp, cdx, cdy, tree, bn, (uint32_t)band_numbps.size(), reduce, px.data());
     if (drc != GRK_AMD_OK) return done(-1);
     img = info.image ? info.image : img;
     for (uint16_t k = 0; k < img->numcomps; ++k) {
         gra_image_comp& ck = img->comps[k];
-        const uint32_t pw = alike ? tp.tile_w : cps[k].tile_w;
+        if (ck.w != plane_w[k] || ck.h != plane_h[k]) return done(-1);
+        const uint32_t pw = plane_w[k];
         if (!ck.data) {                                   // the host skipped post-T1, so nothing was allocated
             ck.stride = (ck.w + 31u) & ~31u;
             void* mem = nullptr;
@@ -962,16 +996,12 @@ GRA_EXPORT int grk_amd_plugin_tile_decode(grk_amd_ctx* ctx, const grk_amd_tile_p
     return grk_amd_plugin_tile_decode_qcd(ctx, p, tile, nullptr, 0, pixels, pixels_on_device);
 }
 
-// components [comp0, comp0 + p->num_comps) of the tree, which all have p's geometry (the whole tree: comp0 = 0)
-static int decode_tree_comps(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const gra_plugin_tile* tile, uint32_t comp0,
-                             const uint8_t* band_numbps, uint32_t nbands, void* pixels, int pixels_on_device);
-
 GRA_EXPORT int grk_amd_plugin_tile_decode_qcd(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const gra_plugin_tile* tile,
                                               const uint8_t* band_numbps, uint32_t nbands, void* pixels, int pixels_on_device)
 {
     if (!ctx || !p || !tile || !pixels) return GRK_AMD_ERR_INVALID;
     if (tile->numComponents != p->num_comps) return GRK_AMD_ERR_INVALID;
-    return decode_tree_comps(ctx, p, tile, 0, band_numbps, nbands, pixels, pixels_on_device);
+    return decode_tree_comps(ctx, p, tile, 0, band_numbps, nbands, 0, pixels, pixels_on_device);
 }
 
 // The decode counterpart of grk_amd_plugin_tile_create_subsampled: `p` = the tile on the reference grid, component c of the tree has
@@ -981,6 +1011,12 @@ GRA_EXPORT int grk_amd_plugin_tile_decode_qcd(grk_amd_ctx* ctx, const grk_amd_ti
 GRA_EXPORT int grk_amd_plugin_tile_decode_subsampled(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const uint8_t* comp_dx,
                                                      const uint8_t* comp_dy, const gra_plugin_tile* tile, const uint8_t* band_numbps,
                                                      uint32_t nbands, void* planes)
+{
+    return decode_tree_subsampled(ctx, p, comp_dx, comp_dy, tile, band_numbps, nbands, 0, planes);
+}
+
+static int decode_tree_subsampled(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                                  const gra_plugin_tile* tile, const uint8_t* band_numbps, uint32_t nbands, uint32_t reduce, void* planes)
 {
     if (!ctx || !p || !comp_dx || !comp_dy || !tile || !planes || tile->numComponents != p->num_comps) return GRK_AMD_ERR_INVALID;
     const uint32_t nc = p->num_comps, bps = (p->prec + 7u) / 8u;
@@ -995,16 +1031,19 @@ GRA_EXPORT int grk_amd_plugin_tile_decode_subsampled(grk_amd_ctx* ctx, const grk
         pr.num_comps = (uint16_t)n;
         pr.mct = (p->mct && c0 == 0 && n >= 3) ? 1 : 0;
         if (p->mct && c0 == 0 && n < 3 && nc >= 3) return GRK_AMD_ERR_UNSUPPORTED;     // (a colour transform across sizes: no encoder writes that)
-        rc = decode_tree_comps(ctx, &pr, tile, c0, band_numbps, nbands, (uint8_t*)planes + at, 0);
+        rc = decode_tree_comps(ctx, &pr, tile, c0, band_numbps, nbands, reduce, (uint8_t*)planes + at, 0);
         if (rc) return rc;
-        at += (size_t)pr.tile_w * pr.tile_h * n * bps;
+        uint32_t rx0, ry0, rw, rh;                       // (each component reduced from its own rectangle)
+        rc = grk_amd_reduced_tile_rect(&pr, reduce, &rx0, &ry0, &rw, &rh);
+        if (rc) return rc;
+        at += (size_t)rw * rh * n * bps;
         c0 += n;
     }
     return GRK_AMD_OK;
 }
 
 static int decode_tree_comps(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const gra_plugin_tile* tile, uint32_t comp0,
-                             const uint8_t* band_numbps, uint32_t nbands, void* pixels, int pixels_on_device)
+                             const uint8_t* band_numbps, uint32_t nbands, uint32_t reduce, void* pixels, int pixels_on_device)
 {
     if (band_numbps && nbands != 3u * p->num_levels + 1u) return GRK_AMD_ERR_INVALID;
     const int64_t nb = grk_amd_tile_num_blocks(p);
@@ -1051,7 +1090,10 @@ static int decode_tree_comps(grk_amd_ctx* ctx, const grk_amd_tile_params* p, con
     if (i != (size_t)nb) return GRK_AMD_ERR_INVALID;
     coded.resize(coded.size() + 16);
     if (p->irreversible && grk_amd_set_decode_steps(ctx, steps.data(), (uint32_t)steps.size()) != GRK_AMD_OK) return GRK_AMD_ERR_INVALID;
-    const int rc = grk_amd_decode_tiles(ctx, p, 1, table.data(), coded.data(), coded.size(), 0, pixels, pixels_on_device);
+    // (the tree is the full tile's; reduce > 0: the tile at 1 / 2^reduce of its size, the setting reset afterwards)
+    int rc = grk_amd_set_decode_reduce(ctx, reduce);
+    if (rc == GRK_AMD_OK) rc = grk_amd_decode_tiles(ctx, p, 1, table.data(), coded.data(), coded.size(), 0, pixels, pixels_on_device);
+    (void)grk_amd_set_decode_reduce(ctx, 0);
     if (p->irreversible) (void)grk_amd_set_decode_steps(ctx, nullptr, 0);
     return rc;
 }

@@ -303,7 +303,8 @@ uint32_t grk_amd_plugin_num_devices(void);
 /* ---- the decode counterpart: a tile tree as the HOST fills it after its Tier-2 parse in
  * decompress_synch_plugin_with_host (plugin/plugin_bridge.cpp:63-76: per block compressedData,
  * compressedDataLength, numBitPlanes = block numbps, numPasses) is decoded on the GPU into `pixels`
- * (layout of grk_amd_decode_tiles).  p->reserved[0] = 1 for Part-1 (EBCOT) blocks, 0 for HT.
+ * (layout of grk_amd_decode_tiles).  p->reserved[0] = 1 for Part-1 (EBCOT) blocks, 0 for HT.  These three calls decode at full
+ * size: they leave grk_amd_set_decode_reduce(ctx, 0) behind (plugin_decompress serves grk_decompress -r through the same tree walk).
  * Returns 0, or a negative GRK_AMD_ERR_* so that the host keeps its CPU decoder. */
 int grk_amd_plugin_tile_decode(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const gra_plugin_tile* tile,
                                void* pixels, int pixels_on_device);

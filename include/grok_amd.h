@@ -270,6 +270,35 @@ int grk_amd_plane_sample_bytes(grk_amd_ctx* ctx, const grk_amd_tile_params* p, i
 int grk_amd_decode_region(grk_amd_ctx* ctx, const grk_amd_tile_params* p,
                           const grk_amd_coded_block* table, const void* coded, uint64_t coded_bytes, int coded_on_device,
                           uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* pixels, int pixels_on_device);
+/* Decode at reduced resolution -- grk_decompress -r N, grk_dparameters::cp_reduce (grok.h:692-732; the reference skips the
+ * code-blocks of the `reduce` finest resolutions and runs `reduce` fewer inverse DWT levels, TileComponent.cpp:69-170 with
+ * numResolutionsToDecompress): the following grk_amd_decode_tiles / grk_amd_decode_region calls return the tile at 1 / 2^reduce
+ * of its size, bit-identical to the component the reference returns with cp_reduce = reduce -- for a tile whose origin is off
+ * the 2^reduce grid, to its first w x h samples (see grk_amd_reduced_tile_rect).  0 (the default) = full resolution.
+ * A call whose tile has fewer DWT levels than `reduce` returns GRK_AMD_ERR_INVALID (the reference refuses cp_reduce >=
+ * numresolutions, CodeStreamDecompress.cpp:1604); reduce = num_levels is legal: the LL band, no inverse level.
+ *   - p, table and coded are those of the FULL tile, as for a full decode: one row per block of the full tile.  Rows of the
+ *     resolutions above num_levels - reduce are ignored and never read (their offsets and lengths need not be valid).
+ *   - The segment list of grk_amd_set_decode_segments is still indexed over the full tile's blocks, the lists of
+ *     grk_amd_set_decode_qcd / grk_amd_set_decode_steps over the full tile's bands.
+ *   - pixels: the reduced tiles back to back, component-major, tight, ceil(prec / 8) bytes per sample -- each
+ *     grk_amd_reduced_tile_rect(p, reduce) in size.  grk_amd_decode_region takes its window in the reduced tile's coordinates,
+ *     [0, w) x [0, h), and needs at least one remaining DWT level (GRK_AMD_ERR_UNSUPPORTED for reduce = num_levels).
+ *   - A decode sequence (grk_amd_set_decode_pipelining) hands the value to its frames like the settings above; it may change from
+ *     one frame to the next.
+ *   - The grk_amd_stage_* calls and every encode path ignore it: they always work on the full tile.
+ *   - A context keeps the device tables of ONE geometry: a call whose reduce differs from the previous call's on the same context
+ *     (or internal context of a sequence) rebuilds them behind a host synchronisation of the context's streams.  Interleaving
+ *     settings costs that much per change; a host that alternates keeps one context per setting. */
+int grk_amd_set_decode_reduce(grk_amd_ctx* ctx, uint32_t reduce);
+/* The tile's rectangle at that reduction, on the reduced grid (host only, no context): x0 = ceil(tile_x0 / 2^reduce), x1 =
+ * ceil((tile_x0 + tile_w) / 2^reduce), w = x1 - x0, likewise in y -- the reference's rectceildivpow2 of the tile bounds
+ * (CodeStreamDecompress.cpp:412-420), i.e. the samples the reference's reduced tile-component holds.  For an origin on the
+ * 2^reduce grid that is the component size grk_decompress_read_header reports for a one-tile image with cp_reduce = reduce; for
+ * an origin off it the header sizes a component as ceil(width / 2^reduce) (SIZMarker.cpp:54), which can be one column / row
+ * more -- samples beyond the tile-component's resolution that the stream does not define.  GRK_AMD_ERR_INVALID for reduce >
+ * p->num_levels. */
+int grk_amd_reduced_tile_rect(const grk_amd_tile_params* p, uint32_t reduce, uint32_t* x0, uint32_t* y0, uint32_t* w, uint32_t* h);
 /* Irreversible streams of another encoder: the SPqcd words (expn << 11 | mant, one per sub-band in QCD
  * order) its QCD marker carries, from which the decode-side step sizes are derived
  * (codestream/Quantizer.cpp:41-63).  count = 0 returns to the exponents this library's encoder writes. */

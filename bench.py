@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: encode Mpixels/s (whole job) for 8K RGB HTJ2K
-lossless, with the dominant kernel's HBM roofline and the reference CPU encoder beside it.
+lossless; with --full, the dominant kernel's HBM roofline and the reference CPU encoder beside it.
 
 One "step" = one pass of the hot path (ingest+DC+RCT -> 5-level 5/3 DWT -> HT cleanup coding of
 64x64 code-blocks -> compaction) over one 8192x8192x3 8-bit tile whose pixels are already
@@ -17,7 +17,13 @@ which); "parts" is reported, never the headline.  Per-GPU work is fixed => weak 
 the BASELINE configs[3] shape -- 16384x16384 as 256 tiles of 1024x1024 split over the ranks, strong
 scaling.  `python bench.py --gpus N` starts its N ranks itself (launch_ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|cfg2|cfg1|cfg3|cfg4tile] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, the pre-warm frames, the timed regions, --dump-outputs, and at
+N > 1 the exchanges the headline is chosen from.  `--full` adds everything else the line can carry: the single-buffer
+region, per-kernel and roofline figures, HBM counters, the decode direction, the bit-exactness check, the CPU baseline,
+the other BASELINE configurations, the host-boundary routes and, at N > 1, the cfg4 strong-scaling shape and the "parts"
+exchange.  `--no-cpu-baseline`, `--no-workloads`, `--no-host-boundary` and `--no-live-pmc` trim a `--full` run.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|cfg2|cfg1|cfg3|cfg4tile] [--dump-outputs DIR] [--full]
 """
 import argparse
 import ctypes as C
@@ -916,19 +922,24 @@ def dump_outputs(ctx, nblocks, out_dir):
     return {name: int(a.size) for name, a in arrays.items()}
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="8k", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` object (cfg2, cfg3, cfg4tile, cfg5 decode)")
-    ap.add_argument("--no-host-boundary", action="store_true", help="skip the `host_boundary` object (PCIe-inclusive end-to-end "
-                    "rate, the route through grk_compress_with_plugin)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too (single-buffer region, per-kernel and roofline "
+                         "figures, HBM counters, decode, bit-exactness, CPU baseline, the other configurations, host-boundary "
+                         "routes; at N > 1 the cfg4 strong-scaling shape and the \"parts\" exchange); off: the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` object")
+    ap.add_argument("--no-workloads", action="store_true",
+                    help="with --full: skip the `workloads` object (cfg2, cfg3, cfg4tile, cfg5 decode)")
+    ap.add_argument("--no-host-boundary", action="store_true", help="with --full: skip the `host_boundary` object (PCIe-inclusive "
+                    "end-to-end rate, the route through grk_compress_with_plugin)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not take the HBM-traffic counters in this run (two short rocprofv3 --pmc passes of the headline "
-                         "workload, ~20 s); the committed summaries under profiles/ are quoted instead")
+                    help="with --full: do not take the HBM-traffic counters in this run (two short rocprofv3 --pmc passes of the "
+                         "headline workload, ~20 s); the committed summaries under profiles/ are quoted instead")
     ap.add_argument("--region-repeats", type=int, default=5,
                     help="the timed region (warm-up + steps) is run this many times; ms_per_step is the median region / steps")
     ap.add_argument("--no-overlap", action="store_true",
@@ -957,6 +968,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, rank 0 writes what the last one computed (block table and coded bytes, block order) "
                          "to DIR/<name>.npy (dump_outputs)")
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -1159,7 +1175,9 @@ def main():
     dt = sorted(regions)[len(regions) // 2]
     # (the context's current buffer set is the last timed step's until the next encode: read it before anything else runs)
     dumped = dump_outputs(ctx, nblocks, args.dump_outputs) if args.dump_outputs and rank == 0 else None
-    dt_single, _, _ = run_frames(params, ntiles, d_px, nblocks, exchange, args.steps, args.warmup)
+    # everything from here to the line is --full's, but for what the line's dtype says and, at N > 1, the exchanges the headline
+    # is chosen from (the gather regions below)
+    dt_single = run_frames(params, ntiles, d_px, nblocks, exchange, args.steps, args.warmup)[0] if args.full else None
     multi_gpu = None
     cs_len = 0
     if use_dist:
@@ -1177,7 +1195,7 @@ def main():
                     "behind the encoder, gather_depth frames in flight; counts = all_gather of 8 bytes per rank (parallel writers)"}
         # BASELINE configs[3]: 16384x16384 as 256 tiles of 1024x1024, the tiles split over the ranks (strong scaling)
         cfg4 = None
-        if not args.no_workloads and args.workload == "8k" and 256 % world == 0:
+        if args.full and not args.no_workloads and args.workload == "8k" and 256 % world == 0:
             p4 = G.TileParams.make(1024, 1024, 3, 8, 5)
             nt4 = 256 // world
             t4 = synth.g2(3, 1024, 1024, 8)
@@ -1196,13 +1214,13 @@ def main():
             ctx.encode_tiles(params, ntiles, d_px.data_ptr(), True, fetch=False)
             ctx.synchronize()
 
-    if rank == 0 and not use_dist and not args.no_live_pmc:
+    if args.full and rank == 0 and not use_dist and not args.no_live_pmc:
         torch.cuda.synchronize(dev)
         live_pmc_traffic(args.workload)          # this run's own HBM-traffic counters (encode and decode families of the workload)
 
     # ---- the decode direction on the blocks just produced (HBM-resident coded bytes -> pixels) ----
     decode = None
-    if not use_dist:
+    if args.full and not use_dist:
         table_d, total_d = ctx.fetch_table(nblocks)
         d_back = torch.empty_like(d_px)
         with torch.cuda.stream(stream):
@@ -1380,7 +1398,7 @@ def main():
             except Exception:         # noqa: BLE001
                 pass
 
-    # ---- per-kernel-family durations: HIP events on the stream each kernel is launched on, `steps` more encodes.
+    # ---- --full: per-kernel-family durations: HIP events on the stream each kernel is launched on, `steps` more encodes.
     # K3 runs up to three times per step -- top resolution on a side stream beside DWT levels >= 1 (timer 4), the rest
     # on the context's stream (2), large-LDS classes on a second side stream (8) -- its time per step is their sum.
     def family_pass(overlap):
@@ -1398,63 +1416,85 @@ def main():
         out["ht_cleanup_encode"] = (sum(ms * n for ms, n in parts) / n_ht if n_ht else 0.0, n_ht)
         ctx.enable_timing(False)
         return out
-    # as the timed region ran (kernels of the two directions of the pipeline share the GPU and stretch each other) ...
-    fam_overlapped = family_pass(not args.no_overlap)
-    # ... and one kernel at a time: the durations a kernel's roofline figure is about
-    fam = family_pass(False)
-    ctx.set_overlap(not args.no_overlap)
-    table, total = ctx.fetch_table(nblocks)
-    # north_star: "bit-exact lossless HTJ2K encode of an 8K x 8K image at 1 and 8 GPUs" -- every rank turns the blocks of its
-    # last encode into the tile's codestream and compares its md5 with that of the file Grok 8.0.2's own encoder writes for
-    # this image (the constant the parity tests pin against the reference built here, tests/test_gpu_stages.py)
-    bit_exact = None
-    if args.workload in GOLDEN_MD5 and ntiles == 1:
-        import hashlib
-        cs_md5 = hashlib.md5(G.write_codestream(params, W, H, table, ctx.fetch_coded(total))).hexdigest()
-        ok = torch.tensor([1 if cs_md5 == GOLDEN_MD5[args.workload] else 0], dtype=torch.int32, device=dev)
-        if use_dist:
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        bit_exact = {"codestream_md5": cs_md5, "equals_grok_cpu_file_on_all_ranks": bool(ok.item()), "ranks": world}
-    b_in = (prec + 7) // 8
-    b_pl, pk_levels = ctx.plane_sample_bytes(params)
-    coded_sum = int(table["length"].astype(np.int64).sum())      # B_out = the blocks' bytes (the arena's extent `total` carries chunk slack)
-    fused_in = fam["ingest_mct"][1] == 0                         # K1 folded into DWT level 0: that launch reads the pixels
-    algo = {"ingest_mct": samples * (b_in + 4), "dwt53_5levels": dwt_bytes(samples, b_in, b_pl, levels, fused_in),
-            "ht_cleanup_encode": ht_bytes(samples, b_pl, coded_sum)}
-    fam_kernels = {"ingest_mct": ("ingest_kernel",), "dwt53_5levels": ("dwt_level0_fused", "dwt_levels_1plus"),
-                   "ht_cleanup_encode": ("ht_encode_kernel",)}
-    dom = max(("ingest_mct", "dwt53_5levels", "ht_cleanup_encode"), key=lambda k: fam[k][0])
-    # HBM traffic per launch of each family: PMC counters cannot be read from inside this process; they come from the
-    # committed rocprofv3 --pmc passes of this same command (profiles/summarize_pmc.py: FETCH_SIZE x1024 x2 [gfx950
-    # half-count] + WRITE_SIZE x1024).
-    traffic = {k: _pmc_traffic(args.workload, v) for k, v in fam_kernels.items()}
-    ach, frac = rate(algo[dom], fam[dom][0])
-    roofline = {"kernel": dom, "bound": "hbm", "achieved": ach or 0.0, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": frac or 0.0, "traffic": traffic[dom],
-                "frac_on_traffic": rate(traffic[dom], fam[dom][0])[1] if traffic[dom] else None,
-                "traffic_source": _PMC_SOURCE.get(args.workload),
-                "algorithmic_bytes_per_launch": int(algo[dom]), "avg_launch_ms": round(fam[dom][0], 4),
-                "launches": fam[dom][1], "plane_bytes_per_coefficient": b_pl,
-                "bytes_convention": "SURVEY.md 8(d) per-unit figures at the storage width the launched instances use: %d B per "
-                                    "coefficient read (planes are int%d here) + the coded bytes written (sum of the block lengths); "
-                                    "workloads.8k_int32 is the same frame on the reference's int32 planes" % (b_pl, 8 * b_pl),
-                "measured": "HIP events around the kernel's launches, kernels one at a time (grk_amd_set_overlap(0)); "
-                            "the timed region runs K3 of the top resolution beside DWT levels >= 1, see kernels_overlapped"}
-    kernels = {k: {"avg_ms": round(v[0], 4), "launches": v[1], "algorithmic_bytes": int(algo[k]) if v[1] else 0,
-                   "algorithmic_GBps": rate(algo[k], v[0])[0], "frac": rate(algo[k], v[0])[1],
-                   "traffic": traffic[k] if v[1] else None,
-                   "frac_on_traffic": rate(traffic[k], v[0])[1] if (traffic[k] and v[1]) else None}
-               for k, v in fam.items()}
+
+    def kernel_figures():
+        """--full: the per-kernel passes, the bit-exactness check and the roofline / pipeline figures built on them.  Returns
+        (fields for the line's `config`, fields for the line)."""
+        # as the timed region ran (kernels of the two directions of the pipeline share the GPU and stretch each other) ...
+        fam_overlapped = family_pass(not args.no_overlap)
+        # ... and one kernel at a time: the durations a kernel's roofline figure is about
+        fam = family_pass(False)
+        ctx.set_overlap(not args.no_overlap)
+        table, total = ctx.fetch_table(nblocks)
+        # north_star: "bit-exact lossless HTJ2K encode of an 8K x 8K image at 1 and 8 GPUs" -- every rank turns the blocks of its
+        # last encode into the tile's codestream and compares its md5 with that of the file Grok 8.0.2's own encoder writes for
+        # this image (the constant the parity tests pin against the reference built here, tests/test_gpu_stages.py)
+        bit_exact = None
+        if args.workload in GOLDEN_MD5 and ntiles == 1:
+            import hashlib
+            cs_md5 = hashlib.md5(G.write_codestream(params, W, H, table, ctx.fetch_coded(total))).hexdigest()
+            ok = torch.tensor([1 if cs_md5 == GOLDEN_MD5[args.workload] else 0], dtype=torch.int32, device=dev)
+            if use_dist:
+                dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            bit_exact = {"codestream_md5": cs_md5, "equals_grok_cpu_file_on_all_ranks": bool(ok.item()), "ranks": world}
+        b_in = (prec + 7) // 8
+        coded_sum = int(table["length"].astype(np.int64).sum())      # B_out = the blocks' bytes (the arena's extent `total` carries chunk slack)
+        fused_in = fam["ingest_mct"][1] == 0                         # K1 folded into DWT level 0: that launch reads the pixels
+        algo = {"ingest_mct": samples * (b_in + 4), "dwt53_5levels": dwt_bytes(samples, b_in, b_pl, levels, fused_in),
+                "ht_cleanup_encode": ht_bytes(samples, b_pl, coded_sum)}
+        fam_kernels = {"ingest_mct": ("ingest_kernel",), "dwt53_5levels": ("dwt_level0_fused", "dwt_levels_1plus"),
+                       "ht_cleanup_encode": ("ht_encode_kernel",)}
+        dom = max(("ingest_mct", "dwt53_5levels", "ht_cleanup_encode"), key=lambda k: fam[k][0])
+        # HBM traffic per launch of each family: PMC counters cannot be read from inside this process; they come from the
+        # committed rocprofv3 --pmc passes of this same command (profiles/summarize_pmc.py: FETCH_SIZE x1024 x2 [gfx950
+        # half-count] + WRITE_SIZE x1024).
+        traffic = {k: _pmc_traffic(args.workload, v) for k, v in fam_kernels.items()}
+        ach, frac = rate(algo[dom], fam[dom][0])
+        roofline = {"kernel": dom, "bound": "hbm", "achieved": ach or 0.0, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": frac or 0.0, "traffic": traffic[dom],
+                    "frac_on_traffic": rate(traffic[dom], fam[dom][0])[1] if traffic[dom] else None,
+                    "traffic_source": _PMC_SOURCE.get(args.workload),
+                    "algorithmic_bytes_per_launch": int(algo[dom]), "avg_launch_ms": round(fam[dom][0], 4),
+                    "launches": fam[dom][1], "plane_bytes_per_coefficient": b_pl,
+                    "bytes_convention": "SURVEY.md 8(d) per-unit figures at the storage width the launched instances use: %d B per "
+                                        "coefficient read (planes are int%d here) + the coded bytes written (sum of the block lengths); "
+                                        "workloads.8k_int32 is the same frame on the reference's int32 planes" % (b_pl, 8 * b_pl),
+                    "measured": "HIP events around the kernel's launches, kernels one at a time (grk_amd_set_overlap(0)); "
+                                "the timed region runs K3 of the top resolution beside DWT levels >= 1, see kernels_overlapped"}
+        kernels = {k: {"avg_ms": round(v[0], 4), "launches": v[1], "algorithmic_bytes": int(algo[k]) if v[1] else 0,
+                       "algorithmic_GBps": rate(algo[k], v[0])[0], "frac": rate(algo[k], v[0])[1],
+                       "traffic": traffic[k] if v[1] else None,
+                       "frac_on_traffic": rate(traffic[k], v[0])[1] if (traffic[k] and v[1]) else None}
+                   for k, v in fam.items()}
+        kernels_overlapped = {k: {"avg_ms": round(v[0], 4), "launches": v[1]} for k, v in fam_overlapped.items()}
+        # whole-pipeline figure: the families' algorithmic bytes as launched (fused level 0, storage width)
+        pipeline_bytes = algo["dwt53_5levels"] + algo["ht_cleanup_encode"] + (algo["ingest_mct"] if not fused_in else 0.0)
+
+        pipe_traffic = _pmc_traffic(args.workload, ("ingest_kernel", "dwt_level0_fused", "dwt_levels_1plus", "ht_encode_kernel"))
+        ms_per_step = dt / args.steps * 1e3
+        return ({"coded_bytes_per_gpu": coded_sum, "arena_bytes_used_per_gpu": int(total),
+                 "single_input_buffer_ms_per_step": round(dt_single / args.steps * 1e3, 4)},
+                {"roofline": roofline,
+                 # the whole step against the HBM roofline: algorithmic bytes of its kernel families as launched, and what the PMC
+                 # counters saw per step (`dram_*`)
+                 "pipeline": {"algorithmic_bytes_per_step": int(pipeline_bytes),
+                              "algorithmic_GBps": rate(pipeline_bytes, ms_per_step)[0],
+                              "algorithmic_frac_of_hbm_peak": rate(pipeline_bytes, ms_per_step)[1],
+                              "dram_traffic_bytes_per_step": pipe_traffic,
+                              "dram_GBps": round(pipe_traffic / (ms_per_step * 1e-3) / 1e9, 1) if pipe_traffic else None,
+                              "dram_frac_of_hbm_peak": round(pipe_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if pipe_traffic else None},
+                 "bit_exact": bit_exact,
+                 "kernels": kernels,
+                 "kernels_overlapped": kernels_overlapped,
+                 "decode": decode})
+
+    b_pl, pk_levels = ctx.plane_sample_bytes(params)             # (the line's dtype: the planes' storage width, no run of its own)
     if not use_dist:
         parallelism = "1 GPU, consecutive encodes pipelined (grk_amd_set_pipelining)" if pipelined else "1 GPU"
     else:
         parallelism = ("tile-sharded x%d; per frame either the coded tile-parts (exact sizes) gathered over RCCL on the frame's "
                        "writer rank (rotating, %d gathers in flight) or only the byte counts (parallel writers): `exchange`" % (world, args.gather_depth))
-    kernels_overlapped = {k: {"avg_ms": round(v[0], 4), "launches": v[1]} for k, v in fam_overlapped.items()}
-    # whole-pipeline figure: the families' algorithmic bytes as launched (fused level 0, storage width)
-    pipeline_bytes = algo["dwt53_5levels"] + algo["ht_cleanup_encode"] + (algo["ingest_mct"] if not fused_in else 0.0)
-
-    pipe_traffic = _pmc_traffic(args.workload, ("ingest_kernel", "dwt_level0_fused", "dwt_levels_1plus", "ht_encode_kernel"))
+    full_config, full_fields = kernel_figures() if args.full else ({}, {})
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = pixels_per_step * world * args.steps / dt / 1e6
@@ -1463,45 +1503,33 @@ def main():
             "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": (dist.get_world_size() if use_dist else 1), "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": dtype_label(irrev, b_pl), "data": "synthetic",
-            "config": {"workload": desc, "tiles_per_gpu": ntiles, "code_blocks_per_gpu": int(nblocks),
-                       "coded_bytes_per_gpu": coded_sum, "arena_bytes_used_per_gpu": int(total), "packed_dwt_levels": pk_levels,
+            "config": {"workload": desc, "tiles_per_gpu": ntiles, "code_blocks_per_gpu": int(nblocks), "packed_dwt_levels": pk_levels,
                        "generator": "G2 (SURVEY.md §8d)", "parallelism": parallelism, "prewarm_steps": PREWARM,
                        "input_frames_in_rotation": len(rot),
                        "region_repeats": {"n": len(regions), "ms_per_step": [round(r / args.steps * 1e3, 4) for r in regions],
                                           "median": round(dt / args.steps * 1e3, 4), "min": round(min(regions) / args.steps * 1e3, 4),
                                           "max": round(max(regions) / args.steps * 1e3, 4)},
-                       "single_input_buffer_ms_per_step": round(dt_single / args.steps * 1e3, 4)},
-            "roofline": roofline,
-            # the whole step against the HBM roofline: algorithmic bytes of its kernel families as launched, and what the PMC
-            # counters saw per step (`dram_*`)
-            "pipeline": {"algorithmic_bytes_per_step": int(pipeline_bytes),
-                         "algorithmic_GBps": rate(pipeline_bytes, ms_per_step)[0],
-                         "algorithmic_frac_of_hbm_peak": rate(pipeline_bytes, ms_per_step)[1],
-                         "dram_traffic_bytes_per_step": pipe_traffic,
-                         "dram_GBps": round(pipe_traffic / (ms_per_step * 1e-3) / 1e9, 1) if pipe_traffic else None,
-                         "dram_frac_of_hbm_peak": round(pipe_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if pipe_traffic else None},
-            "bit_exact": bit_exact,
-            "kernels": kernels,
-            "kernels_overlapped": kernels_overlapped,
-            "decode": decode,
+                       **full_config},
+            "full": args.full,
+            **full_fields,
         }
         if use_dist:
             out["multi_gpu"] = multi_gpu
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
         cfg5 = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # rank 0 at N = 1 only (at N > 1 the other ranks would wait in the final barrier for it, and the N = 1 line of the same
             # box has it): Grok's CPU encoder on this box's host cores
             out["cpu_baseline"], cfg5 = cpu_baseline(os.cpu_count() or 1,
                                                      want_cfg5=world == 1 and not use_dist and not args.no_workloads and args.workload == "8k")
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
-        if world == 1 and not use_dist and not args.no_workloads and args.workload == "8k":
+        if args.full and world == 1 and not use_dist and not args.no_workloads and args.workload == "8k":
             cb = out.get("cpu_baseline") or {}
             out["workloads"] = extra_workloads(ctx, dev, stream, max(3, min(args.steps, 10)), cfg5,
                                                {"cfg2": (cb.get("cfg2") or {}).get("file_md5")})
-        if world == 1 and not use_dist and not args.no_host_boundary:
+        if args.full and world == 1 and not use_dist and not args.no_host_boundary:
             try:
                 hb = {"end_to_end": host_boundary(ctx, dev, stream, params, ntiles, torch.from_numpy(host.view(np.uint8)), nblocks,
                                                   max(3, min(args.steps, 10)))}
@@ -1532,9 +1560,11 @@ def main():
         for dpt in sorted(set([1, 2, 4]) - {args.gather_depth}) + [args.gather_depth]:
             gw = max(args.warmup, 2 * (dpt + 3) + 2)
             dtg, parts_g, root_g = run_frames(params, ntiles, rot, nblocks, "gather", args.steps, gw, gather_depth=dpt)
-            cs_len = assembled_bytes(params, ntiles, nblocks, W * world if ntiles == 1 else 0, H, parts_g, root_g)
             g8 = {"ms_per_step": round(dtg / args.steps * 1e3, 4), "Mpixels_s": round(pixels_per_step * world * args.steps / dtg / 1e6, 1),
-                  "assembled_codestream_bytes": cs_len, "gather_depth": dpt}
+                  "gather_depth": dpt}
+            if args.full:
+                cs_len = assembled_bytes(params, ntiles, nblocks, W * world if ntiles == 1 else 0, H, parts_g, root_g)
+                g8["assembled_codestream_bytes"] = cs_len
             by_depth[str(dpt)] = {"ms_per_step": g8["ms_per_step"], "Mpixels_s": g8["Mpixels_s"]}
             if out is not None:
                 out["exchange"]["gather_by_depth"] = dict(by_depth)     # (what the watchdog prints if a later depth never completes)
@@ -1565,31 +1595,33 @@ def main():
                 out["value"] = gbest["Mpixels_s"]
                 out["ms_per_step"] = gbest["ms_per_step"]
                 out["config"]["headline_exchange"] = "gather (depth %d)" % gbest["gather_depth"]
-                out["config"]["assembled_codestream_bytes"] = cs_len
-        # (the line already carries the gather figures and the headline: a rank that fails or stalls below costs it `exchange.parts` only --
-        #  a watchdog of its own)
+                if args.full:
+                    out["config"]["assembled_codestream_bytes"] = cs_len
         dog.cancel()
-        dog = start_gather_watchdog(args.gather_timeout, out, emit, args.gather_timeout_rc, key="parts")
-        # ---- ... and the exchange of FINISHED tile-parts: Tier-2 runs on every rank's device inside the timed region (grk_amd_assemble_device_async
-        # on the exchange's stream), the writer receives tile-parts it only has to put behind the main header.  More work per frame than
-        # the gather of loose blocks (whose Tier-2, on the writer's host, is NOT in that form's timed region): reported, never the headline
-        parts_fig = None
-        try:
-            dtp, parts_p, root_p = run_frames(params, ntiles, rot, nblocks, "parts", args.steps, gw, gather_depth=args.gather_depth)
-            plen, pmd5 = assembled_file(params, ntiles, W * world if ntiles == 1 else 0, H, parts_p, root_p)
-            parts_fig = {"ms_per_step": round(dtp / args.steps * 1e3, 4), "Mpixels_s": round(pixels_per_step * world * args.steps / dtp / 1e6, 1),
-                         "codestream_bytes": plen, "equals_gather_form_length": bool(plen == cs_len), "gather_depth": args.gather_depth,
-                         "what": "Tier-2 on each rank's device inside the timed region; finished tile-parts (one table row each) to the frame's writer"}
-            if world == 1 and pmd5 is not None and gather_md5[0] is not None:      # (one process: the same frame's two files side by side)
-                parts_fig["file_equals_gather_form_file"] = bool(pmd5 == gather_md5[0])
-                ref = (out or {}).get("cpu_baseline") or {}
-                if ref.get("file_md5"):
-                    parts_fig["file_equals_cpu_encode"] = bool(ref["file_md5"] == pmd5)
-        except Exception as e:  # noqa: BLE001
-            parts_fig = {"error": str(e)}
-        dog.cancel()
-        if out is not None:
-            out["exchange"]["parts"] = parts_fig
+        if args.full:
+            # (the line already carries the gather figures and the headline: a rank that fails or stalls below costs it `exchange.parts` only --
+            #  a watchdog of its own)
+            dog = start_gather_watchdog(args.gather_timeout, out, emit, args.gather_timeout_rc, key="parts")
+            # ---- ... and the exchange of FINISHED tile-parts: Tier-2 runs on every rank's device inside the timed region (grk_amd_assemble_device_async
+            # on the exchange's stream), the writer receives tile-parts it only has to put behind the main header.  More work per frame than
+            # the gather of loose blocks (whose Tier-2, on the writer's host, is NOT in that form's timed region): reported, never the headline
+            parts_fig = None
+            try:
+                dtp, parts_p, root_p = run_frames(params, ntiles, rot, nblocks, "parts", args.steps, gw, gather_depth=args.gather_depth)
+                plen, pmd5 = assembled_file(params, ntiles, W * world if ntiles == 1 else 0, H, parts_p, root_p)
+                parts_fig = {"ms_per_step": round(dtp / args.steps * 1e3, 4), "Mpixels_s": round(pixels_per_step * world * args.steps / dtp / 1e6, 1),
+                             "codestream_bytes": plen, "equals_gather_form_length": bool(plen == cs_len), "gather_depth": args.gather_depth,
+                             "what": "Tier-2 on each rank's device inside the timed region; finished tile-parts (one table row each) to the frame's writer"}
+                if world == 1 and pmd5 is not None and gather_md5[0] is not None:      # (one process: the same frame's two files side by side)
+                    parts_fig["file_equals_gather_form_file"] = bool(pmd5 == gather_md5[0])
+                    ref = (out or {}).get("cpu_baseline") or {}
+                    if ref.get("file_md5"):
+                        parts_fig["file_equals_cpu_encode"] = bool(ref["file_md5"] == pmd5)
+            except Exception as e:  # noqa: BLE001
+                parts_fig = {"error": str(e)}
+            dog.cancel()
+            if out is not None:
+                out["exchange"]["parts"] = parts_fig
         dist.barrier()
         dist.destroy_process_group()
     emit(out)

@@ -144,6 +144,13 @@ def test_dump_outputs_block_order_and_sample(tmp_path, monkeypatch):
     assert np.array_equal(s1, cb[np.sort(np.random.default_rng(B.DUMP_SEED).integers(0, 10, 6))])
 
 
+def test_full_is_an_option_off_by_default():
+    """A plain run measures the headline alone; every other figure of the line waits for --full."""
+    B = _bench()
+    assert B.make_parser().parse_args([]).full is False
+    assert B.make_parser().parse_args(["--full", "--no-cpu-baseline"]).full is True
+
+
 def test_steps_below_one_is_refused():
     r = _run_bench("--dry-run", "--steps", "0")
     assert r.returncode != 0 and "--steps" in r.stderr

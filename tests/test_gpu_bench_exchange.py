@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_forced_world1_exchanges_agree():
     env = dict(os.environ, GROK_AMD_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29611")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--steps", "6", "--warmup", "2", "--region-repeats", "1",
-                        "--no-cpu-baseline", "--no-workloads", "--no-host-boundary", "--no-live-pmc"],
+                        "--full", "--no-cpu-baseline", "--no-workloads", "--no-host-boundary", "--no-live-pmc"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

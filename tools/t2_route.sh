@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 for r in device host; do
-GRK_AMD_NODE_T2=$r timeout 600 python $R/bench.py --no-cpu-baseline --no-workloads --no-live-pmc --steps 20 2>/dev/null | tail -1 | python3 -c "
+GRK_AMD_NODE_T2=$r timeout 600 python $R/bench.py --full --no-cpu-baseline --no-workloads --no-live-pmc --steps 20 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('== Tier-2 on the $r'); print(json.dumps(d['host_boundary']['node_native'], indent=1))"

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for lib in [None] + sys.argv[1:]:
     env = dict(os.environ)
     if lib: env["GRK_AMD_LIB"] = lib
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-workloads", "--no-host-boundary", "--no-live-pmc"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-workloads", "--no-host-boundary", "--no-live-pmc"],
                        env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -33,6 +33,7 @@
 // fp32 9/7: (l + r) * c and the accumulate are separately rounded (__fadd_rn/__fmul_rn, no FMA),
 // the order of WaveletFwd.cpp:143-160; scaling low*invK, high*K as in :46, :203-213.
 #include "kernels.h"
+#include "dwt_common.h"
 #include "pk16.h"
 #include <type_traits>
 
@@ -48,35 +49,6 @@ constexpr int   kHalo     = 4;                 // columns each side
 constexpr int   kOutCols  = 448;
 constexpr int   kOutPairs = kOutCols / 2;
 static_assert(kOutCols <= kCols - 2 * kHalo && kOutCols % 2 == 0, "strip does not fit the staged line");
-
-__device__ __forceinline__ uint32_t mirror_idx(int32_t i, uint32_t n)
-{
-    if (n == 1) return 0;
-    const int32_t p = 2 * ((int32_t)n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return (uint32_t)(i < (int32_t)n ? i : p - i);
-}
-// same for indices that leave [0, n) by fewer than 16 samples (the row loop): one reflection, no division
-// (TALL: the caller knows n >= 16)
-template <bool TALL>
-__device__ __forceinline__ uint32_t mirror_row(int32_t i, uint32_t n)
-{
-    if (!TALL && n < 16) return mirror_idx(i, n);
-    i = i < 0 ? -i : i;
-    return (uint32_t)(i < (int32_t)n ? i : 2 * ((int32_t)n - 1) - i);
-}
-
-constexpr float kAlpha = -1.586134342f;
-constexpr float kBeta  = -0.052980118f;
-constexpr float kGamma = 0.882911075f;
-constexpr float kDelta = 0.443506852f;
-constexpr float kK     = 1.230174105f;
-
-__device__ __forceinline__ float lift(float x, float l, float r, float c)
-{
-    return __fadd_rn(x, __fmul_rn(__fadd_rn(l, r), c));
-}
 
 // ---- per-column vertical recurrences ---------------------------------------------------------
 struct V53 {
@@ -147,27 +119,6 @@ __device__ __forceinline__ void h97(const float* w, float& s, float& d, float in
     float e0  = lift(b0, cm1, cp1, kDelta);
     s = __fmul_rn(e0, inv_k);
     d = __fmul_rn(cp1, kK);
-}
-
-// forward colour transform of one pixel (same arithmetic as kernels_ingest.hip: mct.cpp:94-104, :541-553)
-__device__ __forceinline__ void color_fwd_px(int32_t& c0, int32_t& c1, int32_t& c2, bool irrev)
-{
-    if (!irrev) {
-        const int32_t r = c0, g = c1, b = c2;
-        c0 = (r + 2 * g + b) >> 2;
-        c1 = b - g;
-        c2 = r - g;
-    } else {
-        const float a_r = 0.299f, a_g = 0.587f, a_b = 0.114f;
-        const float cb = 0.5f / (1.0f - a_b), cr = 0.5f / (1.0f - a_r);
-        const float r = (float)c0, g = (float)c1, b = (float)c2;
-        float y = __fmul_rn(a_r, r);
-        y = __fadd_rn(y, __fmul_rn(a_g, g));
-        y = __fadd_rn(y, __fmul_rn(a_b, b));
-        c0 = __float_as_int(y);
-        c1 = __float_as_int(__fmul_rn(cb, __fsub_rn(b, y)));
-        c2 = __float_as_int(__fmul_rn(cr, __fsub_rn(r, y)));
-    }
 }
 
 // PX = 0: the level reads an int32/float plane (levels >= 1, and level 0 of the stage entry point).
@@ -301,8 +252,8 @@ __global__ __launch_bounds__(kThreads) void dwt_level_kernel(DwtLevelArgs a)
                     xa[k] = ((pa ^ a.sext) - a.sext) - a.dc; xb[k] = ((pb ^ a.sext) - a.sext) - a.dc;
                 }
                 if constexpr (NC == 3) {            // launched with NC = 3 only for the MCT components
-                    color_fwd_px(xa[0], xa[1], xa[2], F97);
-                    color_fwd_px(xb[0], xb[1], xb[2], F97);
+                    color_fwd(xa[0], xa[1], xa[2], F97);
+                    color_fwd(xb[0], xb[1], xb[2], F97);
     #pragma unroll
                     for (int k = 0; k < NC; ++k) {
                         if constexpr (F97) { va[k] = __int_as_float(xa[k]); vb[k] = __int_as_float(xb[k]); }

@@ -28,6 +28,7 @@
 #include <atomic>
 #include <mutex>
 #include "kernels.h"
+#include "ht_common.h"
 #include "ht_vlc_tables.h"
 // the coded bytes are written once and read by nobody on the device: non-temporal stores
 #define GRK_K3_STORE(p, v) __builtin_nontemporal_store((uint32_t)(v), (p))
@@ -40,9 +41,6 @@ namespace {
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
-
-// MEL exponents E[k], k = 0..12 = {0,0,0,1,1,1,2,2,2,3,3,4,5} (ojph_block_encoder.cpp:226), one nibble each
-constexpr uint64_t kMelE = 0x5433222111000ull;
 
 // device tables (filled by launch_ht_encode on first use per device)
 //   g_vlc_enc[0..2047]    first quad row : index (c_q<<8)|(rho<<4)|eps
@@ -397,22 +395,6 @@ __device__ __forceinline__ uint32_t pk_mul_lo_u16(uint32_t a, uint32_t b)
     return r;
 }
 
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xF, true);
-}
-// inclusive prefix sum over the 64 lanes: 4 row_shr steps inside each row of 16, then row_bcast
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    v += dpp0<0x111, 0xF>(v);      // row_shr:1
-    v += dpp0<0x112, 0xF>(v);      // row_shr:2
-    v += dpp0<0x114, 0xF>(v);      // row_shr:4
-    v += dpp0<0x118, 0xF>(v);      // row_shr:8
-    v += dpp0<0x142, 0xA>(v);      // row_bcast:15 -> rows 1,3
-    v += dpp0<0x143, 0xC>(v);      // row_bcast:31 -> rows 2,3
-    return v;
-}
 __device__ __forceinline__ uint32_t quad_swap(uint32_t v)          // value of lane ^ 1
 {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);

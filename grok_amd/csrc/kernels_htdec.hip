@@ -25,6 +25,7 @@
 #include <atomic>
 #include <mutex>
 #include "kernels.h"
+#include "ht_common.h"
 #include "ht_vlc_tables.h"
 #include <type_traits>
 
@@ -50,21 +51,6 @@ constexpr uint32_t kQuadWords  = 32 * 32;
 __device__ __forceinline__ void lds_or(uint32_t* p, uint32_t v)
 {
     (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xF, true);
-}
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    v += dpp0<0x111, 0xF>(v);
-    v += dpp0<0x112, 0xF>(v);
-    v += dpp0<0x114, 0xF>(v);
-    v += dpp0<0x118, 0xF>(v);
-    v += dpp0<0x142, 0xA>(v);
-    v += dpp0<0x143, 0xC>(v);
-    return v;
 }
 
 // lcup, scup of a block as K5a takes them from its last two bytes (:1067-1090); false: the block is rejected
@@ -219,7 +205,7 @@ struct MelBits {      // MSB first
     }
     __device__ __forceinline__ void decode_run()                 // (:196-235)
     {
-        const uint32_t e = (k < 8 ? 0x22111000u >> (4 * k) : 0x54332u >> (4 * (k - 8))) & 0xFu;   // MEL exponents (:196)
+        const uint32_t e = (k < 8 ? (uint32_t)kMelE >> (4 * k) : (uint32_t)(kMelE >> 32) >> (4 * (k - 8))) & 0xFu;   // MEL exponents (:196)
         const uint32_t top = (uint32_t)(acc >> 32);
         const bool one = (top >> 31) != 0;                       // '1': 2^e zero events; '0' + e bits: that many, then a one
         run = one ? (int)((2u << e) - 2u) : (int)((((top >> (31u - e)) & ((1u << e) - 1u)) << 1) | 1u);

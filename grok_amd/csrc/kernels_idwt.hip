@@ -26,6 +26,7 @@
 // 9/7: low*K, high*(2/K) first, then the four lifting sweeps with coefficients -delta, -gamma,
 // -beta, -alpha, each `x + ((l + r) * c)` separately rounded (:1068-1073, :1005-1008).
 #include "kernels.h"
+#include "dwt_common.h"
 #include "pk16.h"
 #include <type_traits>
 
@@ -40,33 +41,7 @@ constexpr int kHaloPairs = 2;
 constexpr int kOutPairs  = 224;
 static_assert(kOutPairs <= kThreads - 2 * kHaloPairs, "strip does not fit the staged line");
 
-__device__ __forceinline__ uint32_t mirror_idx(int32_t i, uint32_t n)
-{
-    if (n == 1) return 0;
-    const int32_t p = 2 * ((int32_t)n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return (uint32_t)(i < (int32_t)n ? i : p - i);
-}
-// same for indices that leave [0, n) by fewer than 16 samples (the row loop): one reflection, no division
-__device__ __forceinline__ uint32_t mirror_row(int32_t i, uint32_t n)
-{
-    if (n < 16) return mirror_idx(i, n);
-    i = i < 0 ? -i : i;
-    return (uint32_t)(i < (int32_t)n ? i : 2 * ((int32_t)n - 1) - i);
-}
-
-constexpr float kK        = 1.230174105f;
-constexpr float kTwoInvK  = 1.625732422f;
-constexpr float kIDelta   = -0.443506852f;
-constexpr float kIGamma   = -0.882911075f;
-constexpr float kIBeta    = 0.052980118f;
-constexpr float kIAlpha   = 1.586134342f;
-
-__device__ __forceinline__ float lift(float x, float l, float r, float c)
-{
-    return __fadd_rn(x, __fmul_rn(__fadd_rn(l, r), c));
-}
+constexpr float kIDelta = -kDelta, kIGamma = -kGamma, kIBeta = -kBeta, kIAlpha = -kAlpha;     // (dwt_common.h)
 
 // ---- horizontal synthesis of one row: s = low half (LL or LH), d = high half (HL or HH) in LDS,
 //      lane produces the samples at columns 2j and 2j+1 (j = its local pair index) -----------------
@@ -233,8 +208,8 @@ __global__ __launch_bounds__(kThreads) void idwt_level_kernel(IdwtLevelArgs a)
     struct Raw { T ls[NC], ld[NC], hs[NC], hd[NC]; };
     auto fetch = [&](int32_t i, Raw& q) {
         // vertical mirror in the interleaved domain: low row 2i, high row 2i+1
-        const uint32_t is = sh ? ((mirror_row(2 * i - (int32_t)py, ch) + py) >> 1) - py : 0;
-        const uint32_t id = ch > sh ? (mirror_row(2 * i + 1 - (int32_t)py, ch) + py - 1) >> 1 : 0;
+        const uint32_t is = sh ? ((mirror_row<false>(2 * i - (int32_t)py, ch) + py) >> 1) - py : 0;
+        const uint32_t id = ch > sh ? (mirror_row<false>(2 * i + 1 - (int32_t)py, ch) + py - 1) >> 1 : 0;
         const bool lc = FAST || sw > 0, hc = FAST || cw > sw, lr = FAST || sh > 0, hr = FAST || ch > sh;    // which halves exist (single row / column)
 #pragma unroll
         for (int k = 0; k < NC; ++k) {

@@ -7,30 +7,9 @@
 // Each lane handles 4 consecutive samples of a row: one 4/8-byte load per component and one
 // 16-byte store per component, so a wave moves 256..512 B in and 1 KiB out per instruction.
 #include "kernels.h"
+#include "dwt_common.h"
 
 namespace grk_amd {
-
-__device__ __forceinline__ void color_fwd(int32_t& c0, int32_t& c1, int32_t& c2, bool irrev)
-{
-    if (!irrev) {
-        // RCT (mct.cpp:94-104)
-        int32_t r = c0, g = c1, b = c2;
-        c0 = (r + 2 * g + b) >> 2;
-        c1 = b - g;
-        c2 = r - g;
-    } else {
-        // ICT (mct.cpp:541-553): every product/sum rounded separately, left-to-right adds.
-        const float a_r = 0.299f, a_g = 0.587f, a_b = 0.114f;
-        const float cb = 0.5f / (1.0f - a_b), cr = 0.5f / (1.0f - a_r);
-        float r = (float)c0, g = (float)c1, b = (float)c2;
-        float y = __fmul_rn(a_r, r);
-        y = __fadd_rn(y, __fmul_rn(a_g, g));
-        y = __fadd_rn(y, __fmul_rn(a_b, b));
-        float u = __fmul_rn(cb, __fsub_rn(b, y));
-        float v = __fmul_rn(cr, __fsub_rn(r, y));
-        c0 = __float_as_int(y); c1 = __float_as_int(u); c2 = __float_as_int(v);
-    }
-}
 
 template <typename PIX>
 __device__ __forceinline__ void load4(const PIX* p, bool vec, uint32_t n, int32_t v[4])

@@ -29,89 +29,19 @@
 //      with 16 lanes, 38.6 ms with 4 and 41 ms with 2 where this form takes 23 ms, on 12 288 blocks.)
 //  The wave then dequantises and stores its block's rows (r02: a second kernel, K8b, from a global workspace).
 #include "kernels.h"
+#include "t1_tables.h"
 
 namespace grk_amd {
 
 namespace {
 
-// T.800 Table C.2: Qe | NMPS << 16 | NLPS << 22 | SWITCH << 28
-#define MQROW(qe, nm, nl, sw) ((uint32_t)(qe) | ((uint32_t)(nm) << 16) | ((uint32_t)(nl) << 22) | ((uint32_t)(sw) << 28))
-__device__ const uint32_t g_mq_table[47] = {
-    MQROW(0x5601, 1, 1, 1),  MQROW(0x3401, 2, 6, 0),  MQROW(0x1801, 3, 9, 0),  MQROW(0x0AC1, 4, 12, 0), MQROW(0x0521, 5, 29, 0),
-    MQROW(0x0221, 38, 33, 0), MQROW(0x5601, 7, 6, 1),  MQROW(0x5401, 8, 14, 0), MQROW(0x4801, 9, 14, 0), MQROW(0x3801, 10, 14, 0),
-    MQROW(0x3001, 11, 17, 0), MQROW(0x2401, 12, 18, 0), MQROW(0x1C01, 13, 20, 0), MQROW(0x1601, 29, 21, 0), MQROW(0x5601, 15, 14, 1),
-    MQROW(0x5401, 16, 14, 0), MQROW(0x5101, 17, 15, 0), MQROW(0x4801, 18, 16, 0), MQROW(0x3801, 19, 17, 0), MQROW(0x3401, 20, 18, 0),
-    MQROW(0x3001, 21, 19, 0), MQROW(0x2801, 22, 19, 0), MQROW(0x2401, 23, 20, 0), MQROW(0x2201, 24, 21, 0), MQROW(0x1C01, 25, 22, 0),
-    MQROW(0x1801, 26, 23, 0), MQROW(0x1601, 27, 24, 0), MQROW(0x1401, 28, 25, 0), MQROW(0x1201, 29, 26, 0), MQROW(0x1101, 30, 27, 0),
-    MQROW(0x0AC1, 31, 28, 0), MQROW(0x09C1, 32, 29, 0), MQROW(0x08A1, 33, 30, 0), MQROW(0x0521, 34, 31, 0), MQROW(0x0441, 35, 32, 0),
-    MQROW(0x02A1, 36, 33, 0), MQROW(0x0221, 37, 34, 0), MQROW(0x0141, 38, 35, 0), MQROW(0x0111, 39, 36, 0), MQROW(0x0085, 40, 37, 0),
-    MQROW(0x0049, 41, 38, 0), MQROW(0x0025, 42, 39, 0), MQROW(0x0015, 43, 40, 0), MQROW(0x0009, 44, 41, 0), MQROW(0x0005, 45, 42, 0),
-    MQROW(0x0001, 45, 43, 0), MQROW(0x5601, 46, 46, 0)};
-#undef MQROW
+// The coding tables (t1_tables.h: Table C.2, D.1, D.2 / D.3) in the packed forms this decoder reads with v_readlane, each across the
+// lanes of one register -- the arithmetic form of the zero-coding rule was ~25 scalar instructions of every zero-coding decision's ~110
+__device__ const t1::MqWords g_mq_table{};
+__device__ const t1::ZcLut g_zc_lut{};
+__device__ const t1::SignLut g_sign_lut{};
 
 constexpr int kCtxZC = 0, kCtxAgg = 17, kCtxUni = 18, kNumCtx = 19;
-
-// Zero-coding contexts (Table D.1) as a look-up by the eight neighbour significance bits: index = row above (x-1, x, x+1) in bits
-// 0-2, left and right neighbour in bits 3-4, row below in bits 5-7; one table per sub-band orientation, 4 bits per entry, eight
-// entries per dword -> 32 dwords that live across the lanes of ONE register (lane i: entries 8 i .. 8 i + 7) and are read with
-// v_readlane like the MQ tables -- the arithmetic form was ~25 scalar instructions of every zero-coding decision's ~110.
-constexpr int zc_context(int orient, uint32_t idx)
-{
-    const uint32_t w0 = idx & 7u, l = (idx >> 3) & 1u, r = (idx >> 4) & 1u, w2 = idx >> 5;
-    int hh = (int)l + (int)r;
-    int vv = (int)((w0 >> 1) & 1u) + (int)((w2 >> 1) & 1u);
-    const int dd = (int)(w0 & 1u) + (int)((w0 >> 2) & 1u) + (int)(w2 & 1u) + (int)((w2 >> 2) & 1u);
-    if (orient == 1) { const int t = hh; hh = vv; vv = t; }
-    if (orient == 3) {
-        const int hv = hh + vv;
-        if (dd >= 3) return 8;
-        if (dd == 2) return hv >= 1 ? 7 : 6;
-        if (dd == 1) return hv >= 2 ? 5 : (hv == 1 ? 4 : 3);
-        return hv >= 2 ? 2 : hv;
-    }
-    if (hh == 2) return 8;
-    if (hh == 1) return vv >= 1 ? 7 : (dd >= 1 ? 6 : 5);
-    if (vv == 2) return 4;
-    if (vv == 1) return 3;
-    return dd >= 2 ? 2 : dd;
-}
-// ... indexed by the NINE bits of a sample's 3 x 3 neighbourhood as they lie in a column's neighbourhood word (row above in bits
-// 0-2, own row in 3-5 -- the centre bit does not matter --, row below in 6-8): 512 entries of 4 bits, 64 dwords, one per lane
-struct ZcLut {
-    uint32_t w[4][64];
-    constexpr ZcLut() : w{}
-    {
-        for (int o = 0; o < 4; ++o)
-            for (uint32_t i = 0; i < 512; ++i) {
-                const uint32_t w0 = i & 7u, w1 = (i >> 3) & 7u, w2 = i >> 6;
-                w[o][i >> 3] |= (uint32_t)zc_context(o, w0 | ((w1 & 1u) << 3) | ((w1 & 4u) << 2) | (w2 << 5)) << (4 * (i & 7u));
-            }
-    }
-};
-__device__ const ZcLut g_zc_lut{};
-// Sign-coding context and XOR bit (Table D.3) by the significance and sign of the four horizontal / vertical neighbours.  The index
-// takes the bits as they lie in the neighbourhood words: significant (up, left, right, down) in bits 0, 2, 4, 6 -- bits 1, 3, 5, 7
-// of a 3 x 3 window shifted down by one --, negative in the bit above each; entry = context | xor << 4, one byte each, 64 dwords
-// across the lanes of one register.
-constexpr uint32_t sign_context(uint32_t idx)
-{
-    auto contrib = [&](int k) { return ((idx >> (2 * k)) & 1u) ? (((idx >> (2 * k + 1)) & 1u) ? -1 : 1) : 0; };
-    int hc = contrib(1) + contrib(2), vc = contrib(0) + contrib(3);
-    hc = hc > 1 ? 1 : (hc < -1 ? -1 : hc); vc = vc > 1 ? 1 : (vc < -1 ? -1 : vc);
-    int cxn = 0, xr = 0;
-    if (hc == 1)      { cxn = vc == 1 ? 13 : (vc == 0 ? 12 : 11); xr = 0; }
-    else if (hc == 0) { cxn = vc == 0 ? 9 : 10; xr = vc == -1; }
-    else              { cxn = vc == 1 ? 11 : (vc == 0 ? 12 : 13); xr = 1; }
-    return (uint32_t)cxn | ((uint32_t)xr << 4);
-}
-struct SignLut {
-    uint32_t w[64];
-    constexpr SignLut() : w{}
-    {
-        for (uint32_t i = 0; i < 256; ++i) w[i >> 2] |= sign_context(i) << (8 * (i & 3u));
-    }
-};
-__device__ const SignLut g_sign_lut{};
 
 // One block per wave: everything the decoder touches is wave-uniform, so the compiler keeps it on the scalar unit, and
 // the two lookups on every decision's dependency chain -- context state and Table C.2 -- come out of VGPRs whose LANE i
@@ -393,13 +323,22 @@ __device__ __forceinline__ void dense_run_half(DenseRun& r, uint32_t tabv, uint3
 
 constexpr uint32_t kNarrowPlanes = 14;
 
+// a decoded value (T1's fixed point, one fraction bit) dequantised: ShiftFilter v / 2 truncating toward zero, ScaleFilter
+// v x stepsize / 2 with scale = stepsize / 2 (filters/PostDecompressFilters.h:26-35, :60-71); K8 and t1_recon_kernel (K8L)
+template <bool IRREV>
+__device__ __forceinline__ int32_t t1_dequant(int32_t v, float scale)
+{
+    if constexpr (IRREV) return __float_as_int(__fmul_rn((float)v, scale));
+    else return v / 2;
+}
+
 // (the kernel's body as a device function: kernels_t1lanes.hip includes this file -- GRK_T1_FUSED_INCLUDE -- and runs it as the first
 //  workgroups of ONE launch that also holds the lane decoder's waves: a frame's block decoding on one stream)
 template <bool IRREV>
 __device__ __forceinline__ void t1_dec_block(const T1DecArgs& a, const uint32_t bidx)
 {
     __shared__ uint64_t bm_l[4][66];
-    const uint32_t tabv0 = threadIdx.x < 47 ? g_mq_table[threadIdx.x] : 0u;       // Table C.2 across the lanes
+    const uint32_t tabv0 = threadIdx.x < 47 ? g_mq_table.w[threadIdx.x] : 0u;       // Table C.2 across the lanes
     // all 64 lanes run the same (uniform) program -- lane-resident tables need every lane's registers to stay live
     // through the compiler's copies -- and only lane 0 performs the side effects
     const bool writer = threadIdx.x == 0;
@@ -515,7 +454,7 @@ __device__ __forceinline__ void t1_dec_block(const T1DecArgs& a, const uint32_t 
                 { const uint32_t dl = tl - (x) + 1u, pat = dl < 3u ? (4u << (3 * ((j) + 1))) >> dl : 0u;           \
                   nbv |= pat; nnv |= ng ? pat : 0u; }                                                             \
             }
-            auto zc_ctx9 = [&](uint32_t nine) -> int {             // Table D.1, looked up (zc_context above)
+            auto zc_ctx9 = [&](uint32_t nine) -> int {             // Table D.1, looked up (t1::zc_context9)
                 return (int)(((uint32_t)__builtin_amdgcn_readlane((int)zcv, (int)(nine >> 3)) >> (4u * (nine & 7u))) & 0xFu);
             };
 
@@ -687,17 +626,13 @@ __device__ __forceinline__ void t1_dec_block(const T1DecArgs& a, const uint32_t 
         if (++type == 3) { type = 0; --bp; }
     }
     }
-    // ---- the block leaves dequantised (ShiftFilter: v / 2 truncating toward zero; ScaleFilter: v x stepsize / 2 --
-    //      filters/PostDecompressFilters.h:26-35, :60-71), lane <-> column, coalesced rows
+    // ---- the block leaves dequantised (t1_dequant), lane <-> column, coalesced rows
     __syncthreads();
     if (threadIdx.x < w) {
         const float scale = bd.inv_step / 2;
         for (uint32_t y = 0; y < h; ++y) {
             const int32_t v = first_pass ? 0 : (narrow ? (int32_t)ws16[y * 64u + threadIdx.x] : ws[y * 64u + threadIdx.x]);
-            int32_t o;
-            if constexpr (IRREV) o = __float_as_int(__fmul_rn((float)v, scale));
-            else o = v / 2;
-            dst[(size_t)y * a.stride + threadIdx.x] = o;
+            dst[(size_t)y * a.stride + threadIdx.x] = t1_dequant<IRREV>(v, scale);
         }
     }
 }

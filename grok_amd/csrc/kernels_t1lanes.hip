@@ -9,7 +9,7 @@
 //                       Wave-uniform loop, at most one MQ decision per lane and iteration; a block's state between stripes
 //                       and its per-plane result bitmaps live in its 16 KB of `work`.
 //   t1_recon_kernel  -- one wave per block of `list`: rows of the bitmaps loaded lane-per-row, then lanes = columns: significance / refinement bitmaps -> coefficients,
-//                       dequantised (ShiftFilter / ScaleFilter, filters/PostDecompressFilters.h:26-35, :60-71) into the Mallat plane.
+//                       dequantised (t1_dequant, kernels_t1dec.hip) into the Mallat plane.
 #include "kernels.h"
 #include "t1_lanes.h"
 #include <type_traits>
@@ -28,19 +28,6 @@ namespace {
 
 using namespace t1l;
 
-struct LaneTables {
-    uint32_t mq[96];
-    uint16_t zc[4][512];
-    uint16_t sc[256];
-    constexpr LaneTables() : mq{}, zc{}, sc{}
-    {
-        for (uint32_t e = 0; e < 94; ++e) mq[e] = t1l::mq_entry(e);
-        for (int o = 0; o < 4; ++o)
-            for (uint32_t i = 0; i < 512; ++i) zc[o][i] = (uint16_t)(t1l::zc_context9(o, i) * 256u);
-        for (uint32_t i = 0; i < 256; ++i) sc[i] = (uint16_t)t1l::sign_context(i);
-    }
-};
-static_assert(sizeof(LaneTables) == kLdsBytes - kCtxBytes, "the tables follow the context rows in LDS");
 __device__ const LaneTables g_lane_tables{};
 
 // SYNC: the wave's lanes run their passes in step, one specialised copy of the loop per pass type (t1_lanes.h) -- the host puts
@@ -182,10 +169,7 @@ __global__ __launch_bounds__(64) void t1_recon_kernel(T1LaneArgs a)
         }
         const bool ng = row_bit(neg, y);
         const int32_t v = ng ? -(int32_t)mag : (int32_t)mag;
-        int32_t o;
-        if constexpr (IRREV) o = __float_as_int(__fmul_rn((float)v, scale));
-        else o = v / 2;
-        if (x < bd.w) dst[(size_t)y * a.stride + x] = o;
+        if (x < bd.w) dst[(size_t)y * a.stride + x] = t1_dequant<IRREV>(v, scale);
     }
 }
 

@@ -25,6 +25,7 @@
 // lanes through the same phases on the CPU and compares with the oracle (test infrastructure; the product is the HIP kernel).
 #pragma once
 #include <stdint.h>
+#include "t1_tables.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define T1L_FN __device__ __forceinline__
@@ -53,69 +54,37 @@ constexpr uint32_t kOffZc = kOffMq + 96u * 4u;          // 5248
 constexpr uint32_t kOffSc = kOffZc + 4u * 512u * 2u;    // 9344
 constexpr uint32_t kLdsBytes = kOffSc + 256u * 2u;      // 9856
 
-// Table C.2: Qe, NMPS, NLPS, SWITCH
-struct MqRow { uint16_t qe; uint8_t nmps, nlps, sw; };
-constexpr MqRow kMq[47] = {
-    {0x5601, 1, 1, 1},  {0x3401, 2, 6, 0},  {0x1801, 3, 9, 0},  {0x0AC1, 4, 12, 0}, {0x0521, 5, 29, 0},
-    {0x0221, 38, 33, 0}, {0x5601, 7, 6, 1},  {0x5401, 8, 14, 0}, {0x4801, 9, 14, 0}, {0x3801, 10, 14, 0},
-    {0x3001, 11, 17, 0}, {0x2401, 12, 18, 0}, {0x1C01, 13, 20, 0}, {0x1601, 29, 21, 0}, {0x5601, 15, 14, 1},
-    {0x5401, 16, 14, 0}, {0x5101, 17, 15, 0}, {0x4801, 18, 16, 0}, {0x3801, 19, 17, 0}, {0x3401, 20, 18, 0},
-    {0x3001, 21, 19, 0}, {0x2801, 22, 19, 0}, {0x2401, 23, 20, 0}, {0x2201, 24, 21, 0}, {0x1C01, 25, 22, 0},
-    {0x1801, 26, 23, 0}, {0x1601, 27, 24, 0}, {0x1401, 28, 25, 0}, {0x1201, 29, 26, 0}, {0x1101, 30, 27, 0},
-    {0x0AC1, 31, 28, 0}, {0x09C1, 32, 29, 0}, {0x08A1, 33, 30, 0}, {0x0521, 34, 31, 0}, {0x0441, 35, 32, 0},
-    {0x02A1, 36, 33, 0}, {0x0221, 37, 34, 0}, {0x0141, 38, 35, 0}, {0x0111, 39, 36, 0}, {0x0085, 40, 37, 0},
-    {0x0049, 41, 38, 0}, {0x0025, 42, 39, 0}, {0x0015, 43, 40, 0}, {0x0009, 44, 41, 0}, {0x0005, 45, 42, 0},
-    {0x0001, 45, 43, 0}, {0x5601, 46, 46, 0}};
-// entry e = state + 47 * mps of the folded table
+// entry e = state + 47 * mps of the folded Table C.2 (t1_tables.h)
 constexpr uint32_t mq_entry(uint32_t e)
 {
+    using t1::kMq;
     const uint32_t st = e % 47u, mps = e / 47u;
     const uint32_t after_mps = kMq[st].nmps + 47u * mps;
     const uint32_t after_lps = kMq[st].nlps + 47u * (mps ^ kMq[st].sw);
     return ((uint32_t)kMq[st].qe << 16) | (mps << 14) | (after_lps << 7) | after_mps;
 }
-
-// Zero-coding context (Table D.1) by orientation and the eight neighbour bits (index: row above (x-1, x, x+1) in bits 0-2, left and
-// right in bits 3-4, row below in bits 5-7) -- the rule as in kernels_t1dec.hip
-constexpr int zc_context(int orient, uint32_t idx)
-{
-    const uint32_t w0 = idx & 7u, l = (idx >> 3) & 1u, r = (idx >> 4) & 1u, w2 = idx >> 5;
-    int hh = (int)l + (int)r;
-    int vv = (int)((w0 >> 1) & 1u) + (int)((w2 >> 1) & 1u);
-    const int dd = (int)(w0 & 1u) + (int)((w0 >> 2) & 1u) + (int)(w2 & 1u) + (int)((w2 >> 2) & 1u);
-    if (orient == 1) { const int t = hh; hh = vv; vv = t; }
-    if (orient == 3) {
-        const int hv = hh + vv;
-        if (dd >= 3) return 8;
-        if (dd == 2) return hv >= 1 ? 7 : 6;
-        if (dd == 1) return hv >= 2 ? 5 : (hv == 1 ? 4 : 3);
-        return hv >= 2 ? 2 : hv;
-    }
-    if (hh == 2) return 8;
-    if (hh == 1) return vv >= 1 ? 7 : (dd >= 1 ? 6 : 5);
-    if (vv == 2) return 4;
-    if (vv == 1) return 3;
-    return dd >= 2 ? 2 : dd;
-}
-// by the NINE bits of a 3 x 3 window (row above in bits 0-2, own row 3-5 -- centre ignored --, row below 6-8)
-constexpr uint32_t zc_context9(int orient, uint32_t nine)
-{
-    const uint32_t w0 = nine & 7u, w1 = (nine >> 3) & 7u, w2 = nine >> 6;
-    return (uint32_t)zc_context(orient, w0 | ((w1 & 1u) << 3) | ((w1 & 4u) << 2) | (w2 << 5));
-}
-// Sign context and XOR bit (Tables D.2 / D.3) by: significant (up, left, right, down) in bits 0, 2, 4, 6, negative in the bit above each
+// zero-coding context by the nine window bits (Table D.1, t1_tables.h)
+using t1::zc_context9;
+// sign-coding entry of the sclut: the context's ctxrow offset (context * 256) | XOR bit (Tables D.2 / D.3, t1_tables.h)
 constexpr uint32_t sign_context(uint32_t idx)
 {
-    int c[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4; ++k) c[k] = ((idx >> (2 * k)) & 1u) ? (((idx >> (2 * k + 1)) & 1u) ? -1 : 1) : 0;
-    int hc = c[1] + c[2], vc = c[0] + c[3];
-    hc = hc > 1 ? 1 : (hc < -1 ? -1 : hc); vc = vc > 1 ? 1 : (vc < -1 ? -1 : vc);
-    uint32_t cxn = 0, xr = 0;
-    if (hc == 1)      { cxn = vc == 1 ? 13u : (vc == 0 ? 12u : 11u); xr = 0; }
-    else if (hc == 0) { cxn = vc == 0 ? 9u : 10u; xr = vc == -1 ? 1u : 0u; }
-    else              { cxn = vc == 1 ? 11u : (vc == 0 ? 12u : 13u); xr = 1; }
-    return cxn * 256u | xr;
+    const t1::SignCx s = t1::sign_rule(idx);
+    return s.cx * 256u | s.xr;
 }
+// the tables behind the context rows, as they lie in LDS from kOffMq on
+struct LaneTables {
+    uint32_t mq[96];
+    uint16_t zc[4][512];
+    uint16_t sc[256];
+    constexpr LaneTables() : mq{}, zc{}, sc{}
+    {
+        for (uint32_t e = 0; e < 94; ++e) mq[e] = mq_entry(e);
+        for (int o = 0; o < 4; ++o)
+            for (uint32_t i = 0; i < 512; ++i) zc[o][i] = (uint16_t)(zc_context9(o, i) * 256u);
+        for (uint32_t i = 0; i < 256; ++i) sc[i] = (uint16_t)sign_context(i);
+    }
+};
+static_assert(sizeof(LaneTables) == kLdsBytes - kCtxBytes, "the tables follow the context rows in LDS");
 
 // ---- a block's work area in global memory (uint64 units) ------------------------------------------------------------------
 // [0, 256): state, stripe s at s * 16: S rows 0-3, N rows 4-7, P rows 8-11, M rows 12-15

@@ -21,10 +21,8 @@ int t1l_sim_decode(const uint8_t* coded, uint64_t coded_bytes, uint32_t nblocks,
     std::vector<uint8_t> lds(kLdsBytes);
     uint32_t* const lds32 = reinterpret_cast<uint32_t*>(lds.data());
     uint16_t* const lds16 = reinterpret_cast<uint16_t*>(lds.data());
-    for (uint32_t e = 0; e < 94; ++e) lds32[(kOffMq >> 2) + e] = mq_entry(e);
-    for (int o = 0; o < 4; ++o)
-        for (uint32_t i = 0; i < 512; ++i) lds16[(kOffZc >> 1) + o * 512 + i] = (uint16_t)(zc_context9(o, i) * 256u);
-    for (uint32_t i = 0; i < 256; ++i) lds16[(kOffSc >> 1) + i] = (uint16_t)sign_context(i);
+    const LaneTables tables;                          // behind the context rows, as the kernel copies them from g_lane_tables
+    std::memcpy(lds.data() + kCtxBytes, &tables, sizeof tables);
     std::vector<uint64_t> work((size_t)64 * kWorkU64);
     FILE* trace = std::getenv("T1L_SIM_TRACE") ? std::fopen(std::getenv("T1L_SIM_TRACE"), "w") : nullptr;
     const uint32_t kslots_max = std::getenv("T1L_KMAX") ? (uint32_t)std::atoi(std::getenv("T1L_KMAX")) : 1u;

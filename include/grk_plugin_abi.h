@@ -176,7 +176,7 @@ typedef int32_t (*gra_decode_callback)(void* info /* PluginDecodeCallbackInfo*, 
  *   gra_image_comp    grk_image_comp   grok.h:866-891
  *   gra_image         grk_image        grok.h:907-929
  * PluginDecodeCallbackInfo itself (plugin/plugin_interface.h:86-130) has std::string members: it is mirrored in
- * C++ inside plugin.cpp, and its layout is checked by oracle/ref_harness/abi_check.cpp like everything here. */
+ * C++ in grok_amd/csrc/plugin_internal.h, and its layout is checked by oracle/ref_harness/abi_check.cpp like everything here. */
 #define GRA_DECODE_HEADER        (1u << 0)      /* grok.h:1249-1254 */
 #define GRA_DECODE_T2            (1u << 1)
 #define GRA_DECODE_T1            (1u << 2)
@@ -225,7 +225,7 @@ typedef struct gra_image_cmptparm {
     bool     sgnd;
 } gra_image_cmptparm;
 /* head of grk_decompress_parameters (grok.h:692-732 grk_dparameters, :754-760): the input path is all the plugin
- * reads out of it -- plugin_decompress takes the stream's QCD and the file size from the file (see plugin.cpp) */
+ * reads out of it -- plugin_decompress takes the stream's QCD and the file size from the file (see plugin_decode.cpp, plugin_files.cpp) */
 typedef struct gra_dparameters {
     uint8_t  cp_reduce;
     uint16_t cp_layer;

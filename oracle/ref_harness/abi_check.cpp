@@ -127,7 +127,7 @@ extern "C" size_t ref_decode_info_layout(int which)
 
 extern "C" int ref_abi_mirror_checked(void) { return 1; }
 
-// decode parameters: the plugin reads the input path only (plugin.cpp: decompress_file)
+// decode parameters: the plugin reads the input path only (plugin_decode.cpp: decompress_file)
 SAME_SIZE(gra_dparameters, grk_dparameters);
 SAME_OFF(gra_dparameters, grk_dparameters, infile); SAME_OFF(gra_dparameters, grk_dparameters, outfile);
 SAME_OFF(gra_dparameters, grk_dparameters, tileCacheStrategy);

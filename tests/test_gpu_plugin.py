@@ -432,7 +432,7 @@ def test_plugin_tile_decode_round_trip(Cn, H, W, prec, L):
 
 @needs_ref
 def test_batch_compress_spreads_files_over_device_contexts(tmp_path):
-    """The batch mode runs one GPU stage per device context (plugin.cpp: the device Grok named + the node's other GPUs; here
+    """The batch mode runs one GPU stage per device context (plugin.cpp plugin_init: the device Grok named + the node's other GPUs; here
     GRK_AMD_PLUGIN_DEVICES=0,0,0 -- three contexts on the one GPU of the box -- so that the multi-device code path runs): every
     output file == the pure-CPU encode of its image.  In a process of its own: the plugin's device list is fixed at plugin_init."""
     import subprocess

@@ -64,7 +64,7 @@ def test_abi_mirror_compiled_against_grok_headers():
 @pytest.mark.ref
 def test_decode_callback_record_layout_matches_reference():
     """plugin_decompress's callback record (PluginDecodeCallbackInfo, plugin/plugin_interface.h:86-130) has std::string
-    members, so it is mirrored in C++ inside plugin.cpp: every offset and the size equal the reference's own."""
+    members, so it is mirrored in C++ in grok_amd/csrc/plugin_internal.h: every offset and the size equal the reference's own."""
     P = C.CDLL(os.path.join(R.plugin_dir(), "libgrokj2k_plugin.so"))
     P.grk_amd_plugin_decode_info_layout.restype = C.c_size_t
     P.grk_amd_plugin_decode_info_layout.argtypes = [C.c_int]

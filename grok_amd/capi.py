@@ -64,6 +64,22 @@ class CodedBlock(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("missing_msbs", C.c_uint32)]
 
 
+class StreamInfo(C.Structure):
+    """grk_amd_stream_info: what a codestream's main header says (read_header)."""
+    _fields_ = [("layout", ImageLayout), ("base", TileParams), ("flags", C.c_uint32), ("num_layers", C.c_uint16),
+                ("guard_bits", C.c_uint8), ("qstyle", C.c_uint8), ("qcd_words", C.c_uint16 * (3 * MAX_LEVELS + 1)),
+                ("num_qcd", C.c_uint32), ("comp_dx", C.c_uint8 * 4), ("comp_dy", C.c_uint8 * 4), ("num_tiles", C.c_uint32),
+                ("num_blocks", C.c_uint64)]
+
+
+class ReaderError(RuntimeError):
+    """read_header / read_packets refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ...) and the reader's reason."""
+
+    def __init__(self, what, code, reason):
+        RuntimeError.__init__(self, "%s failed: %d (%s)" % (what, code, reason))
+        self.code, self.reason = int(code), reason
+
+
 _lib = None
 
 
@@ -171,6 +187,17 @@ def lib():
         L.grk_amd_write_main_header_layout.argtypes = [PL, PP, u32, vp, vp, u64]
         L.grk_amd_encode_image.restype = C.c_int64
         L.grk_amd_encode_image.argtypes = [vp, PL, PP, vp, u32, vp, u64]
+        if hasattr(L, "grk_amd_read_header"):
+            L.grk_amd_read_header.argtypes = [vp, u64, C.POINTER(StreamInfo)]
+            L.grk_amd_read_packets.restype = C.c_int64
+            L.grk_amd_read_packets.argtypes = [vp, u64, C.POINTER(StreamInfo), u32, vp, u64, vp, vp, u64, C.POINTER(u64), vp, u64,
+                                               C.POINTER(u64), C.POINTER(u64)]
+            L.grk_amd_reader_last_error.restype = C.c_char_p
+            L.grk_amd_decode_image.argtypes = [vp, vp, u64, vp, u64, i32]
+            L.grk_amd_decode_image_launches.restype = u64
+            L.grk_amd_decode_image_launches.argtypes = [vp, i32]
+            L.grk_amd_gather_device.argtypes = [vp, vp, u64, vp, u64, vp, u64]
+            L.grk_amd_place_tiles_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, u32, u32]
         _lib = L
     return _lib
 
@@ -298,6 +325,53 @@ def locate_tile_parts(cs):
 
 
 CODED_DTYPE = np.dtype([("offset", np.uint64), ("length", np.uint32), ("missing_msbs", np.uint32)])
+SEGMENT_DTYPE = np.dtype([("length", np.uint32), ("numpasses", np.uint32)])
+MOVE_DTYPE = np.dtype([("dst", np.uint64), ("src", np.uint64), ("len", np.uint32), ("kind", np.uint32)])
+ERR_UNSUPPORTED, ERR_INVALID, ERR_OVERFLOW, ERR_RANGE = -2, -3, -5, -6
+
+
+def _cs_array(cs):
+    return cs if isinstance(cs, np.ndarray) else np.frombuffer(cs, np.uint8)
+
+
+def read_header(cs):
+    """grk_amd_read_header: the main header of a codestream (bytes-like) -> StreamInfo; ReaderError when it is refused."""
+    L = lib()
+    buf = _cs_array(cs)
+    info = StreamInfo()
+    rc = L.grk_amd_read_header(buf.ctypes.data if buf.size else None, buf.size, C.byref(info))
+    if rc:
+        raise ReaderError("read_header", rc, L.grk_amd_reader_last_error().decode())
+    return info
+
+
+def read_packets(cs, info=None, threads=1):
+    """grk_amd_read_packets: every packet header of every tile -> dict(rows CODED_DTYPE, first_segment uint32 [rows + 1],
+    segments SEGMENT_DTYPE, moves MOVE_DTYPE, appendix_bytes).  A row's offset points into `cs`, or -- at or behind len(cs) --
+    into the appendix that `moves` fill."""
+    L = lib()
+    buf = _cs_array(cs)
+    if info is None:
+        info = read_header(buf)
+    nseg, nmov, app = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    # sized for what a single-layer stream without split codeword segments needs: one parse; anything else says how much
+    # it needs (ERR_OVERFLOW with the sizes set) and is parsed again
+    nrows, seg_cap, move_cap = int(info.num_blocks), int(info.num_blocks), 0
+    while True:
+        rows = np.zeros(nrows, CODED_DTYPE)
+        first = np.zeros(nrows + 1, np.uint32)
+        segs = np.zeros(seg_cap, SEGMENT_DTYPE)
+        moves = np.zeros(move_cap, MOVE_DTYPE)
+        n = L.grk_amd_read_packets(buf.ctypes.data, buf.size, C.byref(info), threads, rows.ctypes.data, rows.size, first.ctypes.data,
+                                   segs.ctypes.data, segs.size, C.byref(nseg), moves.ctypes.data, moves.size, C.byref(nmov), C.byref(app))
+        if n == ERR_OVERFLOW and (nseg.value > seg_cap or nmov.value > move_cap):
+            seg_cap, move_cap = max(seg_cap, int(nseg.value)), max(move_cap, int(nmov.value))
+            continue
+        if n < 0:
+            raise ReaderError("read_packets", n, L.grk_amd_reader_last_error().decode())
+        break
+    segs, moves = segs[:nseg.value], moves[:nmov.value]
+    return dict(rows=rows, first_segment=first, segments=segs, moves=moves, appendix_bytes=int(app.value))
 
 
 class Context:
@@ -509,6 +583,35 @@ class Context:
         t = np.ascontiguousarray(table)
         self._check(self._L.grk_amd_decode_tiles(self._h, C.byref(params), ntiles, t.ctypes.data, d_coded, coded_bytes, 1,
                                                  d_pixels, 1), "decode_tiles")
+
+    def decode_image(self, cs):
+        """Codestream (bytes-like, host) -> pixels (C, H, W) of the image area (grk_amd_decode_image, host pixels)."""
+        buf = _cs_array(cs)
+        info = read_header(buf)
+        out = np.zeros((info.base.num_comps, info.layout.y1 - info.layout.y0, info.layout.x1 - info.layout.x0),
+                       np.uint8 if info.base.prec <= 8 else np.uint16)
+        self._check(self._L.grk_amd_decode_image(self._h, buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "decode_image")
+        return out
+
+    def decode_image_device(self, cs, d_pixels, cap):
+        """The same into device memory (asynchronous behind the reader: decode_status joins and reports)."""
+        buf = _cs_array(cs)
+        self._check(self._L.grk_amd_decode_image(self._h, buf.ctypes.data, buf.size, d_pixels, int(cap), 1), "decode_image")
+
+    def decode_image_launches(self):
+        """(gather launches, placement launches) of this context's decode_image calls so far"""
+        return int(self._L.grk_amd_decode_image_launches(self._h, 0)), int(self._L.grk_amd_decode_image_launches(self._h, 1))
+
+    def gather_device(self, moves, d_src, src_bytes, d_dst, dst_bytes):
+        m = np.ascontiguousarray(moves, MOVE_DTYPE)
+        self._check(self._L.grk_amd_gather_device(self._h, m.ctypes.data if m.size else None, m.size, d_src, int(src_bytes), d_dst,
+                                                  int(dst_bytes)), "gather_device")
+
+    def place_tiles_device(self, d_tiles, ntiles, w, h, ncomp, bps, rects, d_image, img_w, img_h):
+        """rects: [(x, y)] of every tile in the image's planes"""
+        r = np.ascontiguousarray(rects, np.uint32).reshape(-1)
+        self._check(self._L.grk_amd_place_tiles_device(self._h, d_tiles, ntiles, w, h, ncomp, bps, r.ctypes.data, d_image, img_w, img_h),
+                    "place_tiles_device")
 
     def set_decode_steps(self, steps):
         """Band step sizes as the host's decoder holds them, [comp][band] (None / empty: back to the QCD words)."""

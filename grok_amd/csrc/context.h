@@ -201,6 +201,10 @@ struct grk_amd_ctx {
     bool t1_pass_sync = true;            // K8L's waves hold blocks of equal bit-plane / pass counts and run pass by pass (GRK_AMD_T1_SYNC=0: free-running lanes)
     struct DecUpload { char* p = nullptr; char* dp = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } dec_up[2];
     uint32_t dec_turn = 0;
+    // grk_amd_decode_image: the uploaded codestream + appendix, a group's decoded tiles, the image (host pixels), the gather's
+    // moves, the tiles' places, the status of all groups; launches of the gather / placement kernels so far
+    DevBuf img_coded, img_tiles, img_pixels, img_moves, img_rects, img_status;
+    uint64_t img_launches[2] = {0, 0};
     // timing
     bool timing = false;
     Timer timers[10];

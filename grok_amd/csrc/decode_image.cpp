@@ -1,0 +1,207 @@
+// grok_amd/csrc/decode_image.cpp -- a whole codestream to pixels (grk_amd_decode_image; on top of the C ABI's own entry points, as
+// image.cpp is for encoding).  The reader (t2_reader.cpp) parses the packet headers on the host while the codestream's bytes
+// travel to the device; the uploaded codestream is then the coded buffer itself -- a block's table row points into it --, with
+// an appendix behind it for the blocks whose bytes come in several pieces (KG gathers those).  The tiles are grouped by geometry
+// as the encoder groups them (image.h: add_unit), every group is one grk_amd_decode_tiles batch into a buffer of its own, and KP
+// puts the group's tiles at their rectangles in the image.
+#include "context.h"
+#include "image.h"
+#include "t2_reader.h"
+#include <thread>
+
+namespace {
+
+// what the call sets on the context, put back when it ends
+struct SavedSettings {
+    grk_amd_ctx* c;
+    std::vector<uint16_t> qcd; std::vector<float> steps; std::vector<uint32_t> seg_first; std::vector<grk_amd_segment> segs;
+    bool planes16;
+    explicit SavedSettings(grk_amd_ctx* ctx) : c(ctx), qcd(ctx->dec_qcd), steps(ctx->dec_steps), seg_first(ctx->dec_seg_first), segs(ctx->dec_segs),
+                                               planes16(ctx->dec_planes16) {}
+    ~SavedSettings()
+    {
+        c->dec_qcd.swap(qcd); c->dec_steps.swap(steps); c->dec_seg_first.swap(seg_first); c->dec_segs.swap(segs);
+        c->dec_planes16 = planes16;
+        c->have_geom = false;              // (the dequantisation scales follow the QCD words)
+    }
+};
+
+int check_moves(grk_amd_ctx* c, const grk_amd_tp_segment* moves, uint64_t n, uint64_t src_bytes, uint64_t dst_bytes)
+{
+    for (uint64_t i = 0; i < n; ++i)
+        if (moves[i].src > src_bytes || moves[i].len > src_bytes - moves[i].src || moves[i].dst > dst_bytes || moves[i].len > dst_bytes - moves[i].dst)
+            return fail(c, GRK_AMD_ERR_INVALID, "a move outside its buffers");
+    return GRK_AMD_OK;
+}
+
+int run_gather(grk_amd_ctx* c, const grk_amd_tp_segment* moves, uint64_t n, const void* src, void* dst)
+{
+    if (!n) return GRK_AMD_OK;
+    HIP_TRY(c, c->img_moves.ensure(n * sizeof moves[0]), "alloc moves");
+    HIP_TRY(c, hipMemcpy(c->img_moves.p, moves, n * sizeof moves[0], hipMemcpyHostToDevice), "upload moves");
+    HIP_TRY(c, launch_t2dec_gather((const grk_amd_tp_segment*)c->img_moves.p, n, (const uint8_t*)src, (uint8_t*)dst, c->stream), "launch gather");
+    ++c->img_launches[0];
+    return GRK_AMD_OK;
+}
+
+} // namespace
+
+extern "C" uint64_t grk_amd_decode_image_launches(grk_amd_ctx* c, int which)
+{
+    return c && which >= 0 && which < 2 ? c->img_launches[which] : 0;
+}
+
+extern "C" int grk_amd_gather_device(grk_amd_ctx* c, const grk_amd_tp_segment* moves, uint64_t num_moves, const void* src_base, uint64_t src_bytes,
+                                     void* dst_base, uint64_t dst_bytes)
+{
+    if (!c || (num_moves && (!moves || !src_base || !dst_base))) return GRK_AMD_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = check_moves(c, moves, num_moves, src_bytes, dst_bytes); if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the moves' device copy may still be read by an earlier call)
+    return run_gather(c, moves, num_moves, src_base, dst_base);
+}
+
+extern "C" int grk_amd_place_tiles_device(grk_amd_ctx* c, const void* tiles, uint32_t ntiles, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                                          const uint32_t* rects, void* image, uint32_t img_w, uint32_t img_h)
+{
+    if (!c || !tiles || !rects || !image || !ntiles || !w || !h || !ncomp || ncomp > 65535 || ntiles > 65535 || !bps || bps > 4) return GRK_AMD_ERR_INVALID;
+    for (uint32_t t = 0; t < ntiles; ++t)
+        if (rects[2 * t] > img_w || w > img_w - rects[2 * t] || rects[2 * t + 1] > img_h || h > img_h - rects[2 * t + 1])
+            return fail(c, GRK_AMD_ERR_INVALID, "a tile outside the image");
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    HIP_TRY(c, c->img_rects.ensure((size_t)ntiles * 8), "alloc places");
+    HIP_TRY(c, hipMemcpy(c->img_rects.p, rects, (size_t)ntiles * 8, hipMemcpyHostToDevice), "upload places");
+    const PlaceArgs a{(const uint8_t*)tiles, ntiles, w, h, ncomp, bps, (const uint32_t*)c->img_rects.p, (uint8_t*)image, img_w, img_h};
+    HIP_TRY(c, launch_t2dec_place(a, c->stream), "launch placement");
+    ++c->img_launches[1];
+    return GRK_AMD_OK;
+}
+
+extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device)
+{
+    if (!c || !cs || !pixels) return GRK_AMD_ERR_INVALID;
+    if (c->dec_reduce) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_decode_image at reduced resolution");
+    if (!c->dec_kids.empty()) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_decode_image on a context with a decode sequence (grk_amd_set_decode_pipelining)");
+    grk_amd_stream_info info;
+    std::string why;
+    int rc = read_stream_header(cs, len, info, why);
+    if (rc) return fail(c, rc, why.c_str());
+    const uint32_t nc = info.base.num_comps, bps = (info.base.prec + 7u) / 8u, nt = info.num_tiles;
+    for (uint32_t k = 0; k < nc; ++k)
+        if (info.comp_dx[k] != 1 || info.comp_dy[k] != 1) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "sub-sampled components");
+    const uint64_t W = info.layout.x1 - info.layout.x0, H = info.layout.y1 - info.layout.y0, total = W * H * nc * bps;
+    if (total > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "the image does not fit `cap`");
+    // the tiles, grouped by geometry
+    std::vector<grk_amd_tile_params> tp(nt);
+    UnitGroups g;
+    for (uint32_t t = 0; t < nt; ++t) {
+        rc = grk_amd_layout_tile(&info.layout, &info.base, t, &tp[t]);
+        if (!rc) rc = add_unit(g, tp[t]);
+        if (rc) return fail(c, rc, "a tile's geometry");
+    }
+    const bool ht = !info.base.reserved[0];
+    if (ht) {
+        // HT blocks are decoded against the band's Kmax of the library's own geometry (ensure_geom), not against the stream's QCD
+        for (const TileGeom& tg : g.geoms)
+            for (uint32_t r = 0; r <= info.base.num_levels; ++r)
+                for (uint32_t bi = 0; bi < tg.res[r].num_bands; ++bi) {
+                    const uint32_t q = r ? 3 * (r - 1) + 1 + bi : 0;
+                    const uint32_t expn = info.qstyle ? info.qcd_words[q] >> 11 : info.qcd_words[q] >> 3;
+                    if (expn + info.guard_bits - 1u != tg.res[r].band[bi].kmax)
+                        return fail(c, GRK_AMD_ERR_UNSUPPORTED, "an HT stream whose QCD exponents are not the ones this library derives for the geometry");
+                }
+    }
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    rc = join_side(c); if (rc) return rc;
+    // the upload (an appendix holds bytes of the codestream: never more than it has), the packet headers meanwhile
+    const uint64_t coded_cap = len + (info.num_layers > 1 ? len : 0);
+    HIP_TRY(c, c->img_coded.ensure(coded_cap + 64), "alloc the coded buffer");
+    StreamTable tab;
+    int rrc = GRK_AMD_OK;
+    {
+        const uint32_t threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+        std::thread reader([&]() { rrc = read_stream_packets(cs, len, info, threads, tab, why); });
+        rc = copy_h2d(c, c->img_coded.p, cs, len);
+        reader.join();
+    }
+    if (rc) return rc;
+    if (rrc) return fail(c, rrc, why.c_str());
+    const uint64_t coded_bytes = len + tab.appendix_bytes;
+    if (coded_bytes > coded_cap) return fail(c, GRK_AMD_ERR_INVALID, "an appendix larger than the codestream");
+    rc = check_moves(c, tab.moves.data(), tab.moves.size(), len, tab.appendix_bytes); if (rc) return rc;
+    // (from here on the call only queues work; the small tables below are uploaded with blocking copies into buffers that an
+    //  earlier call's kernels may still read)
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    rc = run_gather(c, tab.moves.data(), tab.moves.size(), c->img_coded.p, (uint8_t*)c->img_coded.p + len); if (rc) return rc;
+
+    SavedSettings saved(c);
+    c->dec_steps.clear();
+    rc = grk_amd_set_decode_qcd(c, info.qcd_words, info.base.irreversible ? info.num_qcd : 0); if (rc) return rc;
+    // Part-1 blocks of several codeword segments need the segment list; one segment per block is what the table row says
+    const bool want_segs = !ht && (info.base.reserved[1] & 0x05);
+    auto group_tables = [&](const std::vector<uint32_t>& G, std::vector<grk_amd_coded_block>& table) -> int {
+        table.clear();
+        std::vector<uint32_t> first;
+        std::vector<grk_amd_segment> segs;
+        for (uint32_t t : G) {
+            table.insert(table.end(), tab.rows.begin() + tab.row_at[t], tab.rows.begin() + tab.row_at[t + 1]);
+            for (uint64_t i = tab.row_at[t]; want_segs && i < tab.row_at[t + 1]; ++i) {
+                first.push_back((uint32_t)segs.size());
+                segs.insert(segs.end(), tab.segments.begin() + tab.first_segment[i], tab.segments.begin() + tab.first_segment[i + 1]);
+            }
+        }
+        if (!want_segs) return grk_amd_set_decode_segments(c, nullptr, nullptr, 0);
+        first.push_back((uint32_t)segs.size());
+        return grk_amd_set_decode_segments(c, first.data(), segs.data(), (uint32_t)table.size());
+    };
+    std::vector<grk_amd_coded_block> table;
+    if (nt == 1) {
+        // one tile: decoded straight into the destination (host pixels: grk_amd_decode_tiles repeats a group that leaves the int16
+        // planes by itself)
+        rc = group_tables(g.members[0], table);
+        if (!rc) rc = grk_amd_decode_tiles(c, &tp[0], 1, table.data(), c->img_coded.p, coded_bytes, 1, pixels, pixels_on_device);
+        return rc;
+    }
+    void* d_img = pixels;
+    if (!pixels_on_device) { HIP_TRY(c, c->img_pixels.ensure(total), "alloc the image"); d_img = c->img_pixels.p; }
+    uint64_t group_bytes = 0;
+    for (const auto& G : g.members) group_bytes = std::max<uint64_t>(group_bytes, (uint64_t)tp[G[0]].tile_w * tp[G[0]].tile_h * nc * bps * G.size());
+    HIP_TRY(c, c->img_tiles.ensure(group_bytes), "alloc a group's tiles");
+    HIP_TRY(c, c->img_status.ensure(64), "alloc status");
+    HIP_TRY(c, c->img_rects.ensure((size_t)nt * 8), "alloc places");
+    {
+        std::vector<uint32_t> rects;                          // group after group
+        for (const auto& G : g.members) for (uint32_t t : G) { rects.push_back(tp[t].tile_x0 - info.layout.x0); rects.push_back(tp[t].tile_y0 - info.layout.y0); }
+        HIP_TRY(c, hipMemcpy(c->img_rects.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice), "upload places");
+    }
+    HIP_TRY(c, hipMemsetAsync(c->img_status.p, 0, 4, c->stream), "clear status");
+    size_t rect_at = 0;
+    for (const auto& G : g.members) {
+        const grk_amd_tile_params& p = tp[G[0]];
+        rc = group_tables(G, table); if (rc) return rc;
+        rc = grk_amd_decode_tiles(c, &p, (uint32_t)G.size(), table.data(), c->img_coded.p, coded_bytes, 1, c->img_tiles.p, 1); if (rc) return rc;
+        // The int16-plane rule (include/grok_amd.h, grk_amd_set_decode_planes16).  A decode into a device buffer does not repeat
+        // itself: with host pixels this call joins behind a group that may use those planes, reads its status and repeats it
+        // with int32 planes; with device pixels the status goes to grk_amd_decode_status like any other
+        if (!pixels_on_device && c->dec_planes16 && ht && !p.irreversible && p.prec <= 8) {
+            rc = grk_amd_decode_status(c);
+            if (rc == GRK_AMD_ERR_RANGE) {
+                c->dec_planes16 = false;
+                rc = grk_amd_decode_tiles(c, &p, (uint32_t)G.size(), table.data(), c->img_coded.p, coded_bytes, 1, c->img_tiles.p, 1);
+                c->dec_planes16 = true;
+            }
+            if (rc) return rc;
+        }
+        HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->img_status.p, (const unsigned int*)c->flag.p, false, c->stream), "keep status");
+        const PlaceArgs a{(const uint8_t*)c->img_tiles.p, (uint32_t)G.size(), p.tile_w, p.tile_h, nc, bps, (const uint32_t*)c->img_rects.p + 2 * rect_at,
+                          (uint8_t*)d_img, (uint32_t)W, (uint32_t)H};
+        HIP_TRY(c, launch_t2dec_place(a, c->stream), "launch placement");
+        ++c->img_launches[1];
+        rect_at += G.size();
+    }
+    HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->flag.p, (const unsigned int*)c->img_status.p, true, c->stream), "hand over status");
+    if (pixels_on_device) return GRK_AMD_OK;
+    rc = copy_d2h(c, pixels, d_img, total); if (rc) return rc;
+    return grk_amd_decode_status(c);
+}

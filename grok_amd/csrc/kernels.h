@@ -273,4 +273,17 @@ struct T2GatherArgs {
 };
 hipError_t launch_t2_gather(const T2GatherArgs& a, hipStream_t s);
 
+// ---- KG / KP: the device's share of reading a whole codestream (kernels_t2dec.hip) ----------------------------------------------
+// KG: moves[i] = len bytes from src + moves[i].src to dst + moves[i].dst (the host checked them against both buffers)
+hipError_t launch_t2dec_gather(const grk_amd_tp_segment* d_moves, uint64_t nmoves, const uint8_t* src, uint8_t* dst, hipStream_t s);
+struct PlaceArgs {
+    const uint8_t* tiles;                            // ntiles tiles of ncomp x h x w samples of bps bytes, back to back
+    uint32_t ntiles, w, h, ncomp, bps;
+    const uint32_t* rects;                           // [tile]: x, y of the tile in the image's planes (checked by the host)
+    uint8_t* image; uint32_t img_w, img_h;           // ncomp planes of img_h x img_w samples
+};
+hipError_t launch_t2dec_place(const PlaceArgs& a, hipStream_t s);
+// *into |= *from (assign: = ) on the stream: a group's decode status into the image's
+hipError_t launch_t2dec_or_status(unsigned int* into, const unsigned int* from, bool assign, hipStream_t s);
+
 } // namespace grk_amd

@@ -1,0 +1,644 @@
+// grok_amd/csrc/t2_reader.cpp -- the Tier-2 READER: a codestream's main header and every packet header of every tile, host only
+// (no HIP call).  The other side of t2_writer.cpp: what SIZ / COD / QCD say, and per code-block where its bytes lie in the file,
+// how many coding passes and zero bit-planes it has and how its bytes divide into codeword segments -- the table
+// grk_amd_decode_tiles takes (the reference: CodeStreamDecompress::readHeader, T2Decompress::decompressPacket).
+// Written from ITU-T T.800 Annex A (marker segments), Annex B (B.10 packet headers, B.10.2 tag trees, B.10.7 lengths, B.12
+// progression) and T.814 (the HT code-block style bit), as tests/j2kparse.py was.
+//
+// This is a parser of UNTRUSTED input: every read is checked against the end of its container (the codestream, the marker
+// segment, the tile-part, with PLT the packet), every count against what the bytes present could hold, sums are made in 64 bits.
+#include "t2_reader.h"
+#include "geometry.h"
+#include "image.h"
+#include "t2_order.h"
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+
+using namespace grk_amd;
+
+namespace {
+
+int refuse(std::string& err, int code, const char* fmt, ...)
+{
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    err = buf;
+    return code;
+}
+
+// the codestream: has(at, k) before any of the unchecked big-endian reads
+struct Bytes {
+    const uint8_t* d; uint64_t n;
+    bool has(uint64_t at, uint64_t k) const { return at <= n && k <= n - at; }
+    uint32_t u8(uint64_t i) const { return d[i]; }
+    uint32_t u16(uint64_t i) const { return (uint32_t)d[i] << 8 | d[i + 1]; }
+    uint32_t u32(uint64_t i) const { return (uint32_t)d[i] << 24 | (uint32_t)d[i + 1] << 16 | (uint32_t)d[i + 2] << 8 | d[i + 3]; }
+};
+
+const char* marker_name(uint32_t m)
+{
+    switch (m) {
+    case 0xFF53: return "COC"; case 0xFF5D: return "QCC"; case 0xFF5E: return "RGN"; case 0xFF5F: return "POC";
+    case 0xFF60: return "PPM"; case 0xFF61: return "PPT"; case 0xFF57: return "PLM"; case 0xFF52: return "COD"; case 0xFF5C: return "QCD";
+    case 0xFF74: return "MCT"; case 0xFF75: return "MCC"; case 0xFF77: return "MCO"; case 0xFF78: return "CBD"; case 0xFF76: return "NLT";
+    default: return nullptr;
+    }
+}
+
+// blocks and precincts an image may have before this reader declines it: a stream of a few bytes can declare any size (a block
+// that is not included costs no bit), and the tables are sized by the declaration
+constexpr uint64_t kMaxBlocksGuess = 1ull << 23;
+
+int parse_main_header(const Bytes& b, grk_amd_stream_info& info, uint64_t& sot_at, std::string& err)
+{
+    std::memset(&info, 0, sizeof info);
+    if (!b.has(0, 4) || b.u16(0) != 0xFF4F) return refuse(err, GRK_AMD_ERR_INVALID, "no SOC marker");
+    uint64_t at = 2;
+    bool siz = false, cod = false, qcd = false;
+    uint32_t xf = 0, sty = 0;
+    for (;;) {
+        if (!b.has(at, 4)) return refuse(err, GRK_AMD_ERR_INVALID, "the main header does not end in a tile-part");
+        const uint32_t m = b.u16(at);
+        if (m == 0xFF90) break;
+        const uint32_t l = b.u16(at + 2);
+        if (m < 0xFF30 || l < 2 || !b.has(at + 2, l)) return refuse(err, GRK_AMD_ERR_INVALID, "broken marker segment 0x%04X at %llu", m, (unsigned long long)at);
+        const uint64_t body = at + 4;
+        const uint32_t bl = l - 2;
+        if (!siz && m != 0xFF51) return refuse(err, GRK_AMD_ERR_INVALID, "SIZ is not the first marker segment");
+        if (m == 0xFF51) {
+            if (siz || bl < 39) return refuse(err, GRK_AMD_ERR_INVALID, "broken SIZ");
+            siz = true;
+            const uint32_t nc = b.u16(body + 34);
+            if (nc == 0 || nc > 16384 || bl != 36 + 3 * nc) return refuse(err, GRK_AMD_ERR_INVALID, "SIZ: Lsiz does not fit Csiz = %u", nc);
+            if (nc > 4) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%u components (at most 4)", nc);
+            info.layout = grk_amd_image_layout{b.u32(body + 10), b.u32(body + 14), b.u32(body + 2), b.u32(body + 6),
+                                               b.u32(body + 26), b.u32(body + 30), b.u32(body + 18), b.u32(body + 22)};
+            info.base.num_comps = (uint16_t)nc;
+            for (uint32_t c = 0; c < nc; ++c) {
+                const uint32_t ssiz = b.u8(body + 36 + 3 * c), dx = b.u8(body + 37 + 3 * c), dy = b.u8(body + 38 + 3 * c);
+                if (!dx || !dy) return refuse(err, GRK_AMD_ERR_INVALID, "SIZ: component %u with XRsiz / YRsiz 0", c);
+                if (c && ssiz != b.u8(body + 36)) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "components of differing precision or sign");
+                if ((ssiz & 0x7F) + 1 > 38) return refuse(err, GRK_AMD_ERR_INVALID, "SIZ: precision %u", (ssiz & 0x7F) + 1);
+                if ((ssiz & 0x7F) + 1 > 16) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "precision %u (at most 16)", (ssiz & 0x7F) + 1);
+                info.base.prec = (uint8_t)((ssiz & 0x7F) + 1); info.base.sgnd = (uint8_t)(ssiz >> 7);
+                info.comp_dx[c] = (uint8_t)dx; info.comp_dy[c] = (uint8_t)dy;
+            }
+        } else if (m == 0xFF52) {
+            if (cod || bl < 10) return refuse(err, GRK_AMD_ERR_INVALID, "broken COD");
+            cod = true;
+            const uint32_t scod = b.u8(body), prog = b.u8(body + 1), layers = b.u16(body + 2), mct = b.u8(body + 4), levels = b.u8(body + 5);
+            const uint32_t cbw = b.u8(body + 6) + 2, cbh = b.u8(body + 7) + 2;
+            sty = b.u8(body + 8); xf = b.u8(body + 9);
+            if (scod & ~7u) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "COD: Scod = 0x%02X", scod);
+            if (prog > 4 || layers == 0 || levels > 32 || cbw > 10 || cbh > 10 || cbw + cbh > 12)
+                return refuse(err, GRK_AMD_ERR_INVALID, "COD: progression %u, %u layers, %u levels, code-blocks 2^%u x 2^%u", prog, layers, levels, cbw, cbh);
+            if (mct > 1) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "a custom MCT (COD: multiple component transformation %u)", mct);
+            if (levels > GRK_AMD_MAX_LEVELS) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%u decomposition levels (at most %d)", levels, GRK_AMD_MAX_LEVELS);
+            if (cbw > 6 || cbh > 6) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "code-blocks of 2^%u x 2^%u (at most 2^6)", cbw, cbh);
+            if (xf > 1) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "COD: wavelet transformation %u", xf);
+            if (sty & 0x80) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "HT and Part-1 code-blocks mixed (code-block style 0x%02X)", sty);
+            if (bl != 10 + ((scod & 1) ? levels + 1 : 0)) return refuse(err, GRK_AMD_ERR_INVALID, "COD: Lcod does not fit %u levels", levels);
+            info.flags |= ((scod & 2) ? GRK_AMD_CS_SOP : 0u) | ((scod & 4) ? GRK_AMD_CS_EPH : 0u) | GRK_AMD_CS_PROG(prog);
+            info.num_layers = (uint16_t)layers;
+            info.base.mct = (uint8_t)mct; info.base.num_levels = (uint8_t)levels;
+            info.base.cblk_w_exp = (uint8_t)cbw; info.base.cblk_h_exp = (uint8_t)cbh;
+            info.base.irreversible = xf == 0;
+            if (!(sty & 0x40)) { info.base.reserved[0] = 1; info.base.reserved[1] = (uint8_t)(sty & 0x3F); }
+            for (uint32_t r = 0; (scod & 1) && r <= levels; ++r) {
+                const uint32_t pe = b.u8(body + 10 + r);
+                if (r && (!(pe & 15u) || !(pe >> 4))) return refuse(err, GRK_AMD_ERR_INVALID, "COD: precinct exponent 0 at resolution %u", r);
+                if (!pe) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "precincts of 1 x 1 at resolution 0");
+                info.base.precinct_exp[r] = pe == 0xFF ? 0 : (uint8_t)pe;
+            }
+        } else if (m == 0xFF5C) {
+            if (qcd || bl < 2) return refuse(err, GRK_AMD_ERR_INVALID, "broken QCD");
+            qcd = true;
+            const uint32_t sq = b.u8(body);
+            info.guard_bits = (uint8_t)(sq >> 5); info.qstyle = (uint8_t)(sq & 31u);
+            if (info.qstyle == 1) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "Sqcd style 1 (scalar derived quantisation)");
+            if (info.qstyle != 0 && info.qstyle != 2) return refuse(err, GRK_AMD_ERR_INVALID, "QCD: Sqcd = 0x%02X", sq);
+            const uint32_t each = info.qstyle ? 2u : 1u, n = (bl - 1) / each;
+            if ((bl - 1) % each || n > 3 * 32 + 1) return refuse(err, GRK_AMD_ERR_INVALID, "QCD: Lqcd = %u", l);
+            info.num_qcd = std::min<uint32_t>(n, 3 * GRK_AMD_MAX_LEVELS + 1);
+            for (uint32_t i = 0; i < info.num_qcd; ++i) info.qcd_words[i] = (uint16_t)(each == 2 ? b.u16(body + 1 + 2 * i) : b.u8(body + 1 + i));
+        } else if (m == 0xFF55) {
+            info.flags |= GRK_AMD_CS_TLM;
+        } else if (m == 0xFF50 || m == 0xFF64 || m == 0xFF63) {
+            // CAP, COM, CRG: nothing this reader needs
+        } else if (const char* name = marker_name(m)) {
+            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%s marker segment in the main header", name);
+        } else {
+            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "marker segment 0x%04X in the main header", m);
+        }
+        at += 2 + (uint64_t)l;
+    }
+    if (!siz || !cod || !qcd) return refuse(err, GRK_AMD_ERR_INVALID, "main header without %s", !siz ? "SIZ" : !cod ? "COD" : "QCD");
+    if (info.num_qcd < 3u * info.base.num_levels + 1u)
+        return refuse(err, GRK_AMD_ERR_INVALID, "QCD: %u sub-bands for %u levels", info.num_qcd, info.base.num_levels);
+    info.num_qcd = 3u * info.base.num_levels + 1u;
+    if (info.base.irreversible != (info.qstyle == 2))
+        return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "Sqcd style %u with the %s transformation", info.qstyle, info.base.irreversible ? "9/7" : "5/3");
+    if (info.base.mct && info.base.num_comps < 3) return refuse(err, GRK_AMD_ERR_INVALID, "COD: component transformation over %u components", info.base.num_comps);
+    sot_at = at;
+    return GRK_AMD_OK;
+}
+
+// ---- packet headers ---------------------------------------------------------------------------------------------------------
+// MSB first, a byte that follows 0xFF carries 7 bits (B.10.1).  Past `end` every bit reads as 0 and `err` stays set: the loops
+// below all end on zeros.
+struct Bits {
+    const uint8_t* d; uint64_t pos, end; uint32_t cur = 0; int n = 0; bool err = false;
+    uint32_t bit()
+    {
+        if (!n) {
+            if (pos >= end) { err = true; return 0; }
+            const bool ff = cur == 0xFF;
+            cur = d[pos++];
+            n = ff ? 7 : 8;
+        }
+        --n;
+        return (cur >> n) & 1u;
+    }
+    uint32_t bits(uint32_t k) { uint32_t v = 0; while (k--) v = (v << 1) | bit(); return v; }       // k <= 32
+    uint64_t align()                        // a header that ends on 0xFF is followed by a stuffed byte
+    {
+        if (cur == 0xFF) { if (pos >= end) err = true; else ++pos; }
+        n = 0; cur = 0;
+        return pos;
+    }
+};
+
+// Tag tree (B.10.2) in its general form: per node the lower bound so far << 1 | "value known".
+struct TreeDim { uint32_t nlev = 0; uint32_t w[17], off[17]; uint32_t nodes = 0; };
+TreeDim tree_dim(uint32_t w, uint32_t h)
+{
+    TreeDim d;
+    for (;;) {
+        d.w[d.nlev] = w; d.off[d.nlev] = d.nodes; d.nodes += w * h; ++d.nlev;
+        if ((w == 1 && h == 1) || d.nlev == 17) break;
+        w = (w + 1) >> 1; h = (h + 1) >> 1;
+    }
+    return d;
+}
+inline uint32_t tree_decode(uint32_t* nodes, const TreeDim& d, uint32_t x, uint32_t y, uint32_t threshold, Bits& br, bool& known)
+{
+    uint32_t low = 0;
+    for (int lv = (int)d.nlev - 1; lv >= 0; --lv) {
+        uint32_t& nd = nodes[d.off[lv] + (y >> lv) * d.w[lv] + (x >> lv)];
+        uint32_t v = nd >> 1;
+        bool k = (nd & 1u) != 0;
+        if (v < low) v = low;
+        while (!k && v < threshold) { if (br.bit()) k = true; else ++v; }
+        nd = v << 1 | (k ? 1u : 0u);
+        low = v;
+        known = k;
+    }
+    return low;
+}
+
+struct BlockState {
+    uint64_t src0 = 0;              // where the first piece lies
+    uint32_t total = 0;             // bytes so far
+    uint32_t pieces = 0;            // non-empty contributions (one per layer at most)
+    uint32_t last_seg = 0;          // the open codeword segment's record in its precinct's list
+    uint16_t passes = 0, seg_idx = 0;
+    uint8_t  lblock = 3, included = 0, zbp = 0, seg_fill = 0;
+};
+struct SegRec { uint32_t row, len, passes; };
+struct Piece { uint64_t src; uint32_t row, len; };
+// what one precinct's packets leave behind (a block lies in one precinct: its records are all in one of these, in order)
+struct Precinct {
+    bool ready = false;
+    TreeDim dim[3];
+    std::vector<uint32_t> nodes;            // per band: inclusion tree, zero-bit-plane tree
+    uint32_t at[3][2];
+    std::vector<SegRec> segs;
+    std::vector<Piece> pieces;
+};
+
+struct TileCtx {
+    Bytes b;
+    const grk_amd_stream_info* info;
+    TileGeom g;
+    uint32_t tile;
+    bool ht, sop, eph;
+    uint32_t sty;
+    BlockState* st;                 // the tile's rows
+    std::vector<Pk> seq;            // one layer's packets in order
+    std::vector<Precinct> prec;     // [seq index]
+};
+
+// passes a codeword segment holds (B.10.7.2; T2Decompress.cpp:169-186): TERMALL 1; LAZY 10, then 2 (raw pair) and 1 (cleanup)
+// in turn; else all of them
+inline uint32_t seg_capacity(uint32_t sty, uint32_t idx)
+{
+    if (sty & 0x04) return 1;
+    if (sty & 0x01) return idx == 0 ? 10u : (idx & 1u) ? 2u : 1u;
+    return 0xFFFFu;
+}
+inline uint32_t floor_log2(uint32_t v) { uint32_t r = 0; while (v >>= 1) ++r; return r; }
+
+// One packet: seq[i] in layer `layer`, the tile's packet number `number`, from pos (advanced) and not beyond `end`.
+int read_packet(TileCtx& T, uint32_t i, uint32_t layer, uint32_t number, uint64_t& pos, uint64_t end, std::string& err)
+{
+    const Pk& q = T.seq[i];
+    const ResGeom& R = T.g.res[q.r];
+    Precinct& P = T.prec[i];
+    if (!P.ready) {
+        uint32_t n = 0;
+        for (uint32_t bi = 0; bi < R.num_bands; ++bi) {
+            const BandGeom::Prec& G = R.band[bi].prec[q.pi];
+            if (!G.gw || !G.gh) continue;
+            P.dim[bi] = tree_dim(G.gw, G.gh);
+            P.at[bi][0] = n; n += P.dim[bi].nodes;
+            P.at[bi][1] = n; n += P.dim[bi].nodes;
+        }
+        P.nodes.assign(n, 0);
+        P.ready = true;
+    }
+    if (T.sop) {
+        if (end - pos < 6 || T.b.u16(pos) != 0xFF91 || T.b.u16(pos + 2) != 4 || T.b.u16(pos + 4) != (number & 0xFFFFu))
+            return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: no SOP marker segment with that number", T.tile, number);
+        pos += 6;
+    }
+    struct Todo { uint32_t row, len; };
+    static thread_local std::vector<Todo> todo;
+    todo.clear();
+    Bits br{T.b.d, pos, end};
+    if (br.bit()) {
+        const uint32_t row0 = q.c * T.g.blocks_per_comp;
+        for (uint32_t bi = 0; bi < R.num_bands; ++bi) {
+            const BandGeom::Prec& G = R.band[bi].prec[q.pi];
+            if (!G.gw || !G.gh) continue;
+            uint32_t* const incl = P.nodes.data() + P.at[bi][0];
+            uint32_t* const zbpt = P.nodes.data() + P.at[bi][1];
+            const TreeDim& D = P.dim[bi];
+            uint32_t row = row0 + G.first_block;
+            for (uint32_t y = 0; y < G.gh; ++y)
+                for (uint32_t x = 0; x < G.gw; ++x, ++row) {
+                    BlockState& s = T.st[row];
+                    bool known = false;
+                    if (!s.included) {
+                        const uint32_t v = tree_decode(incl, D, x, y, layer + 1, br, known);
+                        if (!known || v > layer) continue;
+                        // (B.10.5 raises the threshold one by one until the value is known; a node reads bits only once its
+                        //  parent is known, so one walk with a threshold beyond any bit-plane count reads the same bits in the same order)
+                        const uint32_t z = tree_decode(zbpt, D, x, y, 65, br, known);
+                        if (!known || br.err) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: zero bit-planes without end", T.tile, number);
+                        s.included = 1; s.zbp = (uint8_t)z;
+                    } else if (!br.bit()) continue;
+                    uint32_t np;                                       // Table B.4
+                    if (!br.bit()) np = 1;
+                    else if (!br.bit()) np = 2;
+                    else {
+                        uint32_t v = br.bits(2);
+                        if (v < 3) np = 3 + v;
+                        else { v = br.bits(5); np = v < 31 ? 6 + v : 37 + br.bits(7); }
+                    }
+                    if (T.ht && (np != 1 || s.passes))
+                        return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "tile %u packet %u: an HT code-block with more than one pass", T.tile, number);
+                    if ((uint32_t)s.passes + np > 164) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: more than 164 coding passes", T.tile, number);
+                    uint32_t lb = s.lblock;
+                    while (br.bit()) if (++lb > 32) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: Lblock beyond 32", T.tile, number);
+                    s.lblock = (uint8_t)lb;
+                    uint64_t sum = 0;
+                    for (uint32_t left = np; left;) {
+                        const uint32_t cap = T.ht ? 1u : seg_capacity(T.sty, s.seg_idx);
+                        const uint32_t k = std::min<uint32_t>(left, cap - s.seg_fill);
+                        const uint32_t nb = lb + floor_log2(k);
+                        if (nb > 32) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: a length of %u bits", T.tile, number, nb);
+                        const uint32_t len = br.bits(nb);
+                        if (s.seg_fill == 0) { s.last_seg = (uint32_t)P.segs.size(); P.segs.push_back(SegRec{row, len, k}); }
+                        else {
+                            SegRec& sr = P.segs[s.last_seg];
+                            if ((uint64_t)sr.len + len > 0xFFFFFFFFull) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: a segment length wraps", T.tile, number);
+                            sr.len += len; sr.passes += k;
+                        }
+                        s.seg_fill = (uint8_t)(s.seg_fill + k);
+                        if (s.seg_fill == cap) { ++s.seg_idx; s.seg_fill = 0; }
+                        left -= k; sum += len;
+                    }
+                    s.passes = (uint16_t)(s.passes + np);
+                    if (sum + s.total > 0xFFFFFFFFull) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: a block length wraps", T.tile, number);
+                    todo.push_back(Todo{row, (uint32_t)sum});
+                }
+        }
+    }
+    pos = br.align();
+    if (br.err) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: the header runs past its %s", T.tile, number, "container");
+    if (T.eph) {
+        if (end - pos < 2 || T.b.u16(pos) != 0xFF92) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: no EPH marker", T.tile, number);
+        pos += 2;
+    }
+    for (const Todo& t : todo) {
+        if (t.len > end - pos) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: the body runs past its container", T.tile, number);
+        if (t.len) {
+            BlockState& s = T.st[t.row];
+            if (!s.pieces++) s.src0 = pos;
+            s.total += t.len;
+            P.pieces.push_back(Piece{pos, t.row, t.len});
+            pos += t.len;
+        }
+    }
+    return GRK_AMD_OK;
+}
+
+struct TilePart { uint64_t at = 0; uint32_t len = 0; bool seen = false; };
+
+// One tile: its tile-part header (PLT), then its packets -- in file order, or, when PLT gives every packet's place, precinct by
+// precinct on `threads` threads (a precinct's packets depend on each other through its tag trees and Lblock, on nothing else).
+int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const TilePart& tp, BlockState* st, grk_amd_coded_block* rows,
+              uint32_t threads, std::vector<Precinct>& keep, std::string& err)
+{
+    TileCtx T;
+    T.b = b; T.info = &info; T.tile = t; T.st = st;
+    T.ht = !info.base.reserved[0]; T.sty = info.base.reserved[1];
+    T.sop = (info.flags & GRK_AMD_CS_SOP) != 0; T.eph = (info.flags & GRK_AMD_CS_EPH) != 0;
+    grk_amd_tile_params p;
+    int rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
+    if (!rc) rc = build_tile_geom(p, T.g);
+    if (rc) return refuse(err, rc, "tile %u: no geometry (%d)", t, rc);
+    const uint32_t order = (info.flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, L = info.num_layers;
+    {
+        std::vector<const TileGeom*> cg(p.num_comps, &T.g);
+        T.seq = packet_order(cg, nullptr, nullptr, p.tile_x0, p.tile_y0, order);
+    }
+    const uint64_t np = T.seq.size(), npk = np * L;
+    // the tile-part header
+    const uint64_t end = tp.at + tp.len;
+    uint64_t pos = tp.at + 12;
+    std::vector<uint32_t> plt;
+    bool have_plt = false;
+    uint64_t v = 0; bool open = false;
+    for (;;) {
+        if (end - pos < 2) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: no SOD marker", t);
+        const uint32_t m = b.u16(pos);
+        if (m == 0xFF93) { pos += 2; break; }
+        if (end - pos < 4) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: no SOD marker", t);
+        const uint32_t l = b.u16(pos + 2);
+        if (m < 0xFF30 || l < 2 || (uint64_t)l + 2 > end - pos) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: broken marker segment 0x%04X", t, m);
+        if (m == 0xFF58) {
+            if (l < 3) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: broken PLT", t);
+            have_plt = true;
+            for (uint64_t i = pos + 5; i < pos + 2 + l; ++i) {
+                const uint32_t x = b.u8(i);
+                v = v << 7 | (x & 0x7Fu); open = true;
+                if (v > 0xFFFFFFFFull) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: a PLT packet length wraps", t);
+                if (!(x & 0x80u)) {
+                    if (plt.size() >= npk) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: PLT lists more than the tile's %llu packets", t, (unsigned long long)npk);
+                    plt.push_back((uint32_t)v); v = 0; open = false;
+                }
+            }
+        } else if (m == 0xFF64) {
+            // COM
+        } else if (const char* name = marker_name(m)) {
+            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%s marker segment in a tile-part header", name);
+        } else {
+            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "marker segment 0x%04X in a tile-part header", m);
+        }
+        pos += 2 + (uint64_t)l;
+    }
+    if (npk > end - pos) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: %llu packets in %llu bytes", t, (unsigned long long)npk, (unsigned long long)(end - pos));
+    if (have_plt && (open || plt.size() != npk))
+        return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: PLT lists %llu packets of %llu", t, (unsigned long long)plt.size(), (unsigned long long)npk);
+    T.prec.resize(np);
+    // RLCP: the layers run inside a resolution -- run[i] = {first packet of seq[i]'s resolution, packets of it}
+    std::vector<std::pair<uint32_t, uint32_t>> run;
+    if (order == 1) {
+        run.resize(np);
+        for (uint64_t i = 0; i < np;) {
+            uint64_t j = i;
+            while (j < np && T.seq[j].r == T.seq[i].r) ++j;
+            for (uint64_t k = i; k < j; ++k) run[k] = {(uint32_t)i, (uint32_t)(j - i)};
+            i = j;
+        }
+    }
+    // the number (place in the tile-part) of precinct i's packet of layer l
+    auto number_of = [&](uint64_t i, uint64_t l) -> uint64_t {
+        if (order == 0) return l * np + i;
+        if (order == 1) return (uint64_t)run[i].first * L + l * run[i].second + (i - run[i].first);
+        return i * L + l;
+    };
+    if (have_plt && threads > 1 && np > 1) {
+        std::vector<uint64_t> start(npk + 1, pos);
+        for (uint64_t k = 0; k < npk; ++k) start[k + 1] = start[k] + plt[k];
+        if (start[npk] != end) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: the PLT lengths do not add up to the tile-part", t);
+        std::mutex mu;
+        rc = parallel_for(np, threads, [&](size_t i) -> int {
+            std::string e;
+            for (uint32_t l = 0; l < L; ++l) {
+                const uint64_t k = number_of(i, l);
+                uint64_t at = start[k];
+                int r = read_packet(T, (uint32_t)i, l, (uint32_t)k, at, start[k + 1], e);
+                if (!r && at != start[k + 1]) r = refuse(e, GRK_AMD_ERR_INVALID, "tile %u packet %llu: %llu bytes, PLT says %u", t, (unsigned long long)k,
+                                                         (unsigned long long)(at - start[k]), plt[k]);
+                if (r) { std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; return r; }
+            }
+            return GRK_AMD_OK;
+        });
+        if (rc) return rc;
+    } else {
+        uint64_t k = 0;
+        auto one = [&](uint64_t i, uint32_t l) -> int {
+            const uint64_t from = pos;
+            const int r = read_packet(T, (uint32_t)i, l, (uint32_t)k, pos, end, err);
+            if (r) return r;
+            if (have_plt && pos - from != plt[k])
+                return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %llu: %llu bytes, PLT says %u", t, (unsigned long long)k, (unsigned long long)(pos - from), plt[k]);
+            ++k;
+            return GRK_AMD_OK;
+        };
+        if (order == 0) {
+            for (uint32_t l = 0; l < L; ++l) for (uint64_t i = 0; i < np; ++i) if ((rc = one(i, l))) return rc;
+        } else if (order == 1) {
+            for (uint64_t i = 0; i < np; i += run[i].second)
+                for (uint32_t l = 0; l < L; ++l) for (uint64_t j = i; j < i + run[i].second; ++j) if ((rc = one(j, l))) return rc;
+        } else {
+            for (uint64_t i = 0; i < np; ++i) for (uint32_t l = 0; l < L; ++l) if ((rc = one(i, l))) return rc;
+        }
+        if (pos != end) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: %llu bytes behind the last packet", t, (unsigned long long)(end - pos));
+    }
+    // the tile's rows (a block of several pieces gets its place in the appendix later)
+    const uint32_t bpc = T.g.blocks_per_comp;
+    for (uint32_t c = 0; c < p.num_comps; ++c)
+        for (uint32_t i = 0; i < bpc; ++i) {
+            const BlockState& s = st[(size_t)c * bpc + i];
+            grk_amd_coded_block& row = rows[(size_t)c * bpc + i];
+            row.offset = s.pieces ? s.src0 : 0; row.length = s.total; row.missing_msbs = 0;
+            if (T.ht) row.missing_msbs = s.zbp;
+            else if (s.total) {
+                const grk_amd_block& gb = T.g.blocks_comp0[i];
+                const uint32_t bi = gb.res == 0 ? 0u : 3u * gb.res - 2u + (gb.band - 1u);
+                const int expn = info.qstyle ? info.qcd_words[bi] >> 11 : info.qcd_words[bi] >> 3;
+                const int numbps = expn + (int)info.guard_bits - 1 - (int)s.zbp;
+                if (numbps < 1 || (int)s.passes > 3 * numbps - 2)
+                    return refuse(err, GRK_AMD_ERR_INVALID, "tile %u block %u: %u passes over %d bit-planes", t, c * bpc + i, s.passes, numbps);
+                row.missing_msbs = (uint32_t)numbps | (uint32_t)s.passes << 8;
+            }
+        }
+    for (Precinct& P : T.prec) { std::vector<uint32_t>().swap(P.nodes); }
+    keep = std::move(T.prec);
+    return GRK_AMD_OK;
+}
+
+thread_local std::string g_reader_error;
+
+} // namespace
+
+int grk_amd::read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info& info, std::string& err)
+{
+    err.clear();
+    if (!cs) return refuse(err, GRK_AMD_ERR_INVALID, "no codestream");
+    const Bytes b{cs, len};
+    uint64_t sot = 0;
+    int rc = parse_main_header(b, info, sot, err);
+    if (rc) return rc;
+    const int64_t nt = grk_amd_layout_num_tiles(&info.layout);
+    if (nt < 0) return refuse(err, (int)nt, nt == GRK_AMD_ERR_UNSUPPORTED ? "SIZ: more than 65535 tiles" : "SIZ: image area and tile grid do not fit");
+    info.num_tiles = (uint32_t)nt;
+    {   // the tables are sized by what SIZ and COD declare: decline what no real image is before anything is allocated
+        uint32_t cxe = info.base.cblk_w_exp, cye = info.base.cblk_h_exp;
+        for (uint32_t r = 0; r <= info.base.num_levels; ++r)
+            if (const uint32_t pe = info.base.precinct_exp[r]) {
+                cxe = std::min<uint32_t>(cxe, (pe & 15u) - (r ? 1u : 0u)); cye = std::min<uint32_t>(cye, (pe >> 4) - (r ? 1u : 0u));
+            }
+        const uint64_t W = info.layout.x1 - info.layout.x0, H = info.layout.y1 - info.layout.y0;
+        if (((W >> cxe) + 1) * ((H >> cye) + 1) * info.base.num_comps > kMaxBlocksGuess)
+            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "an image of %llu x %llu in code-blocks of 2^%u x 2^%u: too many", (unsigned long long)W, (unsigned long long)H, cxe, cye);
+    }
+    grk_amd_tile_params p;
+    for (uint32_t t = 0; t < info.num_tiles; ++t) {
+        rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
+        const int64_t nb = rc ? rc : grk_amd_tile_num_blocks(&p);
+        if (nb < 0) return refuse(err, (int)nb, "tile %u (%u x %u at %u, %u): no geometry (%d)", t, p.tile_w, p.tile_h, p.tile_x0, p.tile_y0, (int)nb);
+        info.num_blocks += (uint64_t)nb;
+        if (info.num_blocks > 4 * kMaxBlocksGuess) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than %llu code-blocks", (unsigned long long)(4 * kMaxBlocksGuess));
+    }
+    (void)grk_amd_layout_tile(&info.layout, &info.base, 0, &p);
+    info.base = p;
+    // PLT: as the first tile-part's header has it
+    for (uint64_t at = sot + 12; b.has(at, 4) && b.u16(at) != 0xFF93; at += 2 + (uint64_t)b.u16(at + 2)) {
+        if (b.u16(at) == 0xFF58) { info.flags |= GRK_AMD_CS_PLT; break; }
+        if (b.u16(at) < 0xFF30 || b.u16(at + 2) < 2) break;
+    }
+    return GRK_AMD_OK;
+}
+
+int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err)
+{
+    grk_amd_stream_info own;
+    int rc = read_stream_header(cs, len, own, err);
+    if (rc) return rc;
+    if (std::memcmp(&own, &info, sizeof own) != 0) return refuse(err, GRK_AMD_ERR_INVALID, "info is not what grk_amd_read_header gives for this codestream");
+    threads = std::max<uint32_t>(1, std::min<uint32_t>(threads, 16));
+    const Bytes b{cs, len};
+    const uint32_t nt = info.num_tiles;
+    // the tile-parts: one per tile
+    std::vector<TilePart> parts(nt);
+    {
+        std::vector<uint64_t> off(nt); std::vector<uint32_t> ln(nt); std::vector<uint16_t> idx(nt);
+        int used = 0;
+        const int64_t n = grk_amd_locate_tile_parts(cs, len, off.data(), ln.data(), idx.data(), nt, &used);
+        if (n < 0) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts cannot be located");
+        for (int64_t i = 0; i < std::min<int64_t>(n, nt); ++i) {
+            if (ln[i] < 14 || !b.has(off[i], ln[i]) || b.u16(off[i]) != 0xFF90 || b.u16(off[i] + 2) != 10)
+                return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: no SOT marker segment where it should start", (long long)i);
+            const uint32_t isot = b.u16(off[i] + 4), psot = b.u32(off[i] + 6), tps = b.u8(off[i] + 10), tn = b.u8(off[i] + 11);
+            if (isot >= nt || (used && isot != idx[i])) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: tile index %u", (long long)i, isot);
+            if (tps != 0 || tn > 1 || parts[isot].seen) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (tile %u)", isot);
+            if (psot && psot != ln[i]) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: Psot %u, TLM %u", (long long)i, psot, ln[i]);
+            parts[isot] = TilePart{off[i], ln[i], true};
+        }
+        if (n > nt) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (%lld tile-parts, %u tiles)", (long long)n, nt);
+        for (uint32_t t = 0; t < nt; ++t) if (!parts[t].seen) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u has no tile-part", t);
+    }
+    out = StreamTable{};
+    out.row_at.assign(nt + 1, 0);
+    grk_amd_tile_params p;
+    for (uint32_t t = 0; t < nt; ++t) {
+        (void)grk_amd_layout_tile(&info.layout, &info.base, t, &p);
+        const int64_t nb = grk_amd_tile_num_blocks(&p);
+        if (nb < 0) return refuse(err, (int)nb, "tile %u: no geometry", t);
+        out.row_at[t + 1] = out.row_at[t] + (uint64_t)nb;
+    }
+    const uint64_t nrows = out.row_at[nt];
+    if (nrows != info.num_blocks) return refuse(err, GRK_AMD_ERR_INVALID, "info.num_blocks");
+    out.rows.assign(nrows, grk_amd_coded_block{0, 0, 0});
+    std::vector<BlockState> st(nrows);
+    std::vector<std::vector<Precinct>> left(nt);
+    if (nt >= threads || threads == 1) {
+        std::mutex mu;
+        rc = parallel_for(nt, threads, [&](size_t t) -> int {
+            std::string e;
+            const int r = read_tile(b, info, (uint32_t)t, parts[t], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, left[t], e);
+            if (r) { std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; }
+            return r;
+        });
+    } else {
+        for (uint32_t t = 0; t < nt && !rc; ++t)
+            rc = read_tile(b, info, t, parts[t], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, left[t], err);
+    }
+    if (rc) { if (err.empty()) (void)refuse(err, rc, "the packets cannot be read (%d)", rc); return rc; }
+    // Segment lists and the appendix, in an order that does not depend on the threads: rows in order, a row's records in the order
+    // its precinct met them
+    out.first_segment.assign(nrows + 1, 0);
+    for (uint32_t t = 0; t < nt; ++t)
+        for (const Precinct& P : left[t]) for (const SegRec& s : P.segs) ++out.first_segment[out.row_at[t] + s.row + 1];
+    for (uint64_t i = 0; i < nrows; ++i) {
+        if ((uint64_t)out.first_segment[i] + out.first_segment[i + 1] > 0xFFFFFFFFull) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than 2^32 codeword segments");
+        out.first_segment[i + 1] += out.first_segment[i];
+    }
+    out.segments.resize(out.first_segment[nrows]);
+    std::vector<uint64_t> cursor(nrows);
+    for (uint64_t i = 0; i < nrows; ++i) cursor[i] = out.first_segment[i];
+    for (uint32_t t = 0; t < nt; ++t)
+        for (const Precinct& P : left[t]) for (const SegRec& s : P.segs) out.segments[cursor[out.row_at[t] + s.row]++] = grk_amd_segment{s.len, s.passes};
+    uint64_t app = 0;
+    for (uint64_t i = 0; i < nrows; ++i)
+        if (st[i].pieces > 1) { out.rows[i].offset = len + app; cursor[i] = app; app += st[i].total; }
+    out.appendix_bytes = app;
+    for (uint32_t t = 0; app && t < nt; ++t)
+        for (const Precinct& P : left[t])
+            for (const Piece& q : P.pieces) {
+                const uint64_t i = out.row_at[t] + q.row;
+                if (st[i].pieces > 1) { out.moves.push_back(grk_amd_tp_segment{cursor[i], q.src, q.len, 1u}); cursor[i] += q.len; }
+            }
+    return GRK_AMD_OK;
+}
+
+extern "C" const char* grk_amd_reader_last_error(void) { return g_reader_error.c_str(); }
+
+extern "C" int grk_amd_read_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info* info)
+{
+    if (!info) { g_reader_error = "no info"; return GRK_AMD_ERR_INVALID; }
+    return read_stream_header(cs, len, *info, g_reader_error);
+}
+
+extern "C" int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                        grk_amd_coded_block* rows, uint64_t row_cap,
+                                        uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                        grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+{
+    if (!info) { g_reader_error = "no info"; return GRK_AMD_ERR_INVALID; }
+    StreamTable s;
+    const int rc = read_stream_packets(cs, len, *info, threads, s, g_reader_error);
+    if (rc) return rc;
+    if (num_segments) *num_segments = s.segments.size();
+    if (num_moves) *num_moves = s.moves.size();
+    if (appendix_bytes) *appendix_bytes = s.appendix_bytes;
+    if (!rows) return (int64_t)s.rows.size();
+    if (s.rows.size() > row_cap || (segments && s.segments.size() > seg_cap) || (moves && s.moves.size() > move_cap) || (!moves && !s.moves.empty()))
+        return refuse(g_reader_error, GRK_AMD_ERR_OVERFLOW, "%llu rows, %llu segments, %llu moves do not fit the caller's arrays",
+                      (unsigned long long)s.rows.size(), (unsigned long long)s.segments.size(), (unsigned long long)s.moves.size());
+    if (!s.rows.empty()) std::memcpy(rows, s.rows.data(), s.rows.size() * sizeof rows[0]);
+    if (first_segment) std::memcpy(first_segment, s.first_segment.data(), s.first_segment.size() * sizeof first_segment[0]);
+    if (segments && !s.segments.empty()) std::memcpy(segments, s.segments.data(), s.segments.size() * sizeof segments[0]);
+    if (moves && !s.moves.empty()) std::memcpy(moves, s.moves.data(), s.moves.size() * sizeof moves[0]);
+    return (int64_t)s.rows.size();
+}

@@ -1,0 +1,25 @@
+// grok_amd/csrc/t2_reader.h -- the codestream reader as the library's own callers use it (private; t2_reader.cpp): the results in
+// vectors, the reason of a refusal in `err`.  grk_amd_read_header / grk_amd_read_packets (include/grok_amd.h) wrap these.
+#pragma once
+#include "../../include/grok_amd.h"
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace grk_amd {
+
+struct StreamTable {
+    std::vector<grk_amd_coded_block> rows;          // the whole image's, tile after tile
+    std::vector<uint64_t> row_at;                   // [tile]: its first row; [num_tiles]: their number
+    std::vector<uint32_t> first_segment;            // [rows + 1]
+    std::vector<grk_amd_segment> segments;
+    std::vector<grk_amd_tp_segment> moves;          // dst counted from the start of the appendix
+    uint64_t appendix_bytes = 0;
+};
+
+int read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info& info, std::string& err);
+int read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err);
+
+} // namespace grk_amd
+#pragma GCC visibility pop

@@ -13,6 +13,7 @@
 // It is O(#code-blocks) host work plus one memcpy of the coded bytes.
 #include "../../include/grok_amd.h"
 #include "geometry.h"
+#include "t2_order.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -248,9 +249,10 @@ grk_amd_image_layout plain_layout(const grk_amd_tile_params& p, uint32_t img_w, 
 //   CPRL        component -> precinct position -> resolution
 // where a precinct's position is its top-left corner on the REFERENCE grid (component coordinates times the component's
 // sub-sampling factors), clipped to the tile -- the (y, x) at which the standard's position loops meet it; positions are walked
-// in raster order, several resolutions / components can share one.
-struct Pk { uint32_t c, r, pi; uint64_t x, y; };
-std::vector<Pk> packet_order(const std::vector<const TileGeom*>& cg, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0,
+// in raster order, several resolutions / components can share one.  (Pk and the declaration: t2_order.h -- the codestream reader
+// walks the same sequence, once per layer.)
+} // namespace
+std::vector<Pk> grk_amd::packet_order(const std::vector<const TileGeom*>& cg, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0,
                              uint32_t order)
 {
     const uint32_t ncomp = (uint32_t)cg.size();
@@ -283,6 +285,7 @@ std::vector<Pk> packet_order(const std::vector<const TileGeom*>& cg, const uint8
             return a.c != b.c ? a.c < b.c : a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.r < b.r; });
     return prec;
 }
+namespace {
 
 // a packet's length as the PLT marker segment carries it: a big-endian base-128 number (continuation bit 0x80)
 void plt_length(std::vector<uint8_t>& body, uint64_t v)

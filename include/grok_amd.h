@@ -494,6 +494,77 @@ int64_t grk_amd_write_tile_part(const grk_amd_tile_params* p, uint32_t tile_inde
 int64_t grk_amd_locate_tile_parts(const uint8_t* cs, uint64_t len, uint64_t* offsets, uint32_t* lengths,
                                   uint16_t* tile_index, uint64_t cap, int* used_tlm);
 
+/* ---- reading a codestream (host only; t2_reader.cpp) and decoding a whole image (decode_image.hip) ----------------------
+ * The reader's side of the writers above (CodeStreamDecompress main header + T2Decompress::decompressPacket, t2/T2Decompress.cpp;
+ * written from ITU-T T.800 Annex A / Annex B and T.814): what SIZ, COD and QCD say, then every packet header of every tile,
+ * which yields the block table grk_amd_decode_tiles takes.  It reads what this library's writers and grk_compress produce:
+ *   main header   SOC SIZ CAP COD QCD (Sqcd styles 0 and 2) COM TLM CRG
+ *   tile-parts    one per tile, in any tile order; PLT and COM in the tile-part header
+ *   packets       the five progression orders, any precinct sizes, 1..N layers, SOP / EPH, empty packets, blocks that are not
+ *                 included, tag trees in their general form, Part-1 codeword segments (TERMALL, LAZY) carried on across
+ *                 layers, HT blocks with one pass
+ * GRK_AMD_ERR_UNSUPPORTED (and the reason in grk_amd_reader_last_error): COC, QCC, RGN, POC, PPM, PPT, PLM, Sqcd style 1, more
+ * than one tile-part per tile, components of differing precision or sign, more than 4 components, more than GRK_AMD_MAX_LEVELS
+ * levels, HT blocks with more than one pass, a custom MCT.  GRK_AMD_ERR_INVALID: anything malformed -- the input is untrusted:
+ * no byte outside [cs, cs + len) is read, a packet never runs past its tile-part, a length never wraps. */
+typedef struct grk_amd_stream_info {
+    grk_amd_image_layout layout;          /* SIZ: image area and tile grid                                                  */
+    grk_amd_tile_params  base;            /* SIZ / COD: comps, prec, sgnd, irreversible, mct, levels, code-block exponents, precinct_exp[]
+                                             (a resolution with PPx = PPy = 15 reads as 0 = not set); reserved[0] = 1 and reserved[1]
+                                             = the style bits for Part-1 blocks; tile_w / tile_h / tile_x0 / tile_y0 = tile 0's   */
+    uint32_t flags;                       /* GRK_AMD_CS_TLM / PLT (first tile-part) / SOP / EPH / PROG(order) as found       */
+    uint16_t num_layers;
+    uint8_t  guard_bits, qstyle;          /* Sqcd >> 5, Sqcd & 31                                                            */
+    uint16_t qcd_words[3 * GRK_AMD_MAX_LEVELS + 1];   /* SPqcd: expn << 3 (style 0) or expn << 11 | mant (style 2), as              */
+    uint32_t num_qcd;                                 /* grk_amd_tile_layout gives and grk_amd_set_decode_qcd takes them             */
+    uint8_t  comp_dx[4], comp_dy[4];      /* XRsiz / YRsiz                                                                   */
+    uint32_t num_tiles;
+    uint64_t num_blocks;                  /* rows of the whole image: sum over tiles of grk_amd_tile_num_blocks             */
+} grk_amd_stream_info;
+int grk_amd_read_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info* info);
+/* The block table of the whole image.  rows: tile after tile in tile-index order, tile t with the rows of ITS parameters
+ * (grk_amd_layout_tile) in grk_amd_tile_layout order: the table grk_amd_write_codestream_layout takes and grk_amd_decode_tiles takes
+ * per tile.  missing_msbs as grk_amd_decode_tiles wants it: HT = zero bit-planes; Part-1 = numbps | numpasses << 8 with numbps =
+ * band exponent + guard bits - 1 - zero bit-planes; a block without data has length 0.
+ * Where a block's bytes lie in one piece in the file, rows[i].offset is their position in `cs`: nothing is copied, the
+ * codestream is the coded buffer.  A block whose bytes come in several pieces (several layers) gets an offset at or behind `len`,
+ * in an APPENDIX; `moves` (src in cs, dst in the appendix counted from 0, len; kind 1) say how to fill it.  The coded buffer of a
+ * decode is then cs followed by *appendix_bytes bytes.  A single-layer stream has neither.
+ * first_segment [num_blocks + 1] / segments: every block's codeword segments as grk_amd_set_decode_segments takes them.
+ * `info` is what grk_amd_read_header gave for the same bytes.  threads: host threads to parse on (0 = 1, at most 16): with PLT the
+ * precincts of a tile are independent, without it the tiles are.  Every parsed packet is checked against its PLT entry.
+ * Returns the number of rows; with rows == NULL only the sizes (*num_segments, *num_moves, *appendix_bytes);
+ * GRK_AMD_ERR_OVERFLOW when a capacity is too small. */
+int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                             grk_amd_coded_block* rows, uint64_t row_cap,
+                             uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                             grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
+/* why the calling thread's latest grk_amd_read_header / grk_amd_read_packets refused ("" after a success) */
+const char* grk_amd_reader_last_error(void);
+/* Codestream -> pixels (Route C, decode; CodeStreamDecompress::decompress, codestream/CodeStreamDecompress.cpp:450-519).
+ * cs: the codestream, host memory.  pixels: the image area, component-major planar, tight, ceil(prec / 8) bytes per sample -- the
+ * layout grk_amd_encode_image takes; cap: its size in bytes.  pixels_on_device != 0: a device pointer, and the call is asynchronous
+ * behind the reader (grk_amd_decode_status joins and reports).
+ * The bytes are uploaded once while the host reads the packet headers; blocks of several pieces are gathered on the device; the
+ * tiles are grouped by geometry, every group is one grk_amd_decode_tiles batch, and a placement kernel puts a group's tiles at
+ * their rectangles (a one-tile image is decoded straight into `pixels`).  The QCD words and segment lists the call sets on the
+ * context are put back before it returns.  GRK_AMD_ERR_UNSUPPORTED: what the reader refuses, sub-sampled components, a context
+ * with grk_amd_set_decode_reduce != 0, and an HT stream whose QCD exponents differ from the ones this library derives for the
+ * geometry (HT blocks are decoded against those).  The int16-plane rule (GRK_AMD_ERR_RANGE, grk_amd_set_decode_planes16) holds
+ * per group: with host pixels such a group is decoded again with int32 planes by the call itself, with device pixels
+ * grk_amd_decode_status reports it. */
+int grk_amd_decode_image(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device);
+/* launches of the gather (which = 0) and placement (which = 1) kernels by this context's grk_amd_decode_image calls so far */
+uint64_t grk_amd_decode_image_launches(grk_amd_ctx* ctx, int which);
+/* The two kernels alone (device pointers; queued on the context's stream):
+ * gather: moves[i] = `len` bytes from src_base + src to dst_base + dst (moves in host memory, checked against the two sizes);
+ * placement: ntiles tiles of w x h samples, ncomp components, bps bytes per sample, back to back at `tiles`, tile i to
+ * (rects[2 i], rects[2 i + 1]) = (x, y) of planes of img_w x img_h samples at `image` (rects in host memory). */
+int grk_amd_gather_device(grk_amd_ctx* ctx, const grk_amd_tp_segment* moves, uint64_t num_moves, const void* src_base, uint64_t src_bytes,
+                          void* dst_base, uint64_t dst_bytes);
+int grk_amd_place_tiles_device(grk_amd_ctx* ctx, const void* tiles, uint32_t ntiles, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                               const uint32_t* rects, void* image, uint32_t img_w, uint32_t img_h);
+
 /* ---- one image over the GPUs of a node (node.cpp) -------------------------------------------------------
  * Replaces the reference's tile-level task pool (codestream/CodeStreamCompress.cpp:535-603: tiles are independent tasks whose
  * tile-parts are written in index order) with one grk_amd_ctx + one host thread per device: tile t is coded on device

@@ -123,8 +123,10 @@ def lib():
         L.grk_amd_stage_ingest_mct.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_dwt_fwd.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_encode.argtypes = [vp, PP, u32, vp]
+        L.grk_amd_stage_ht_encode16.argtypes = [vp, PP, u32, vp, u32]
         L.grk_amd_stage_dwt_inv.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_decode.argtypes = [vp, PP, u32, vp, vp, u64, vp]
+        L.grk_amd_stage_ht_decode16.argtypes = [vp, PP, u32, vp, vp, u64, vp]
         L.grk_amd_decode_tiles.argtypes = [vp, PP, u32, vp, vp, u64, i32, vp, i32]
         L.grk_amd_decode_status.argtypes = [vp]
         L.grk_amd_set_decode_qcd.argtypes = [vp, vp, u32]
@@ -226,6 +228,7 @@ def reduced_tile_rect(params, reduce):
 
 
 CS_TLM, CS_PLT, CS_SOP, CS_EPH = 1, 2, 4, 8
+STAGE_HT_ROOM = 1            # grk_amd_stage_ht_encode16 flags
 
 
 def CS_PROG(order):
@@ -533,11 +536,22 @@ class Context:
     def stage_ht_encode(self, params, ntiles, d_mallat):
         self._check(self._L.grk_amd_stage_ht_encode(self._h, C.byref(params), ntiles, d_mallat), "stage_ht_encode")
 
+    def stage_ht_encode16(self, params, ntiles, d_mallat16, flags=0):
+        """K3 from int16 Mallat planes (grk_amd_stage_ht_encode16); flags: STAGE_HT_ROOM."""
+        self._check(self._L.grk_amd_stage_ht_encode16(self._h, C.byref(params), ntiles, d_mallat16, flags), "stage_ht_encode16")
+
     def stage_ht_decode(self, params, ntiles, table, d_coded, coded_bytes, d_mallat):
         t = np.ascontiguousarray(table)
         self._check(self._L.grk_amd_stage_ht_decode(self._h, C.byref(params), ntiles, t.ctypes.data, d_coded, coded_bytes,
                                                     d_mallat),
                     "stage_ht_decode")
+
+    def stage_ht_decode16(self, params, ntiles, table, d_coded, coded_bytes, d_mallat16):
+        """K5 into int16 Mallat planes, with their range check (grk_amd_stage_ht_decode16)."""
+        t = np.ascontiguousarray(table)
+        self._check(self._L.grk_amd_stage_ht_decode16(self._h, C.byref(params), ntiles, t.ctypes.data, d_coded, coded_bytes,
+                                                      d_mallat16),
+                    "stage_ht_decode16")
 
     def decode_host(self, params, table, coded, ntiles=1):
         """table: CODED_DTYPE rows, coded: bytes-like (host). Returns pixels (ntiles, C, H, W)."""

@@ -435,6 +435,22 @@ int grk_amd_stage_ht_decode(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32
     return check_decode_status(c);
 }
 
+// K5b's int16 stores and their range flag as a decode of an 8-bit reversible HT tile runs them (decode_impl's h16 conditions)
+int grk_amd_stage_ht_decode16(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles,
+                              const grk_amd_coded_block* table, const void* d_coded, uint64_t coded_bytes, void* d_mallat16)
+{
+    if (c) { const int jr = join_side(c); if (jr) return jr; }
+    if (!c || !p || !table || !d_coded || !d_mallat16 || ntiles == 0) return GRK_AMD_ERR_INVALID;
+    if (p->irreversible || p->prec > 8 || p->reserved[0] || !c->dec_seg_first.empty())
+        return fail(c, GRK_AMD_ERR_INVALID, "int16 planes are for reversible HT tiles of at most 8 bits without refinement passes");
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = ensure_geom(c, p); if (rc) return rc;
+    grk_amd_ctx::DecUpload* up = nullptr;
+    rc = stage_table(c, table, (uint64_t)c->geom.blocks_per_comp * c->geom.p.num_comps * ntiles, &up); if (rc) return rc;
+    rc = run_ht_decode(c, ntiles, up, d_coded, coded_bytes, d_mallat16, true, false); if (rc) return rc;
+    return check_decode_status(c);
+}
+
 static int decode_impl(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles,
                        const grk_amd_coded_block* table, const void* coded, uint64_t coded_bytes, int coded_on_device,
                        void* pixels, int pixels_on_device, const Rect* win, bool force32 = false)

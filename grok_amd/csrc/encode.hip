@@ -245,6 +245,17 @@ int grk_amd_stage_ht_encode(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32
     return run_ht(c, ntiles, d_mallat);
 }
 
+// the instances an encode of 8-bit reversible pixels launches (H16; flags bit 0: ROOM), on planes the caller chose
+int grk_amd_stage_ht_encode16(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat16, uint32_t flags)
+{
+    if (c) { const int jr = join_side(c); if (jr) return jr; }
+    if (!c || !p || !d_mallat16 || (flags & ~GRK_AMD_STAGE_HT_ROOM)) return GRK_AMD_ERR_INVALID;
+    if (!planes16_ok(*p)) return fail(c, GRK_AMD_ERR_INVALID, "no encode keeps int16 planes for these parameters");
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = ensure_geom(c, p); if (rc) return rc;
+    return run_ht(c, ntiles, d_mallat16, false, true, (flags & GRK_AMD_STAGE_HT_ROOM) != 0);
+}
+
 int grk_amd_fetch_table(grk_amd_ctx* c, grk_amd_coded_block* table, uint64_t* total)
 {
     if (!c || !c->last_nblocks) return GRK_AMD_ERR_INVALID;

@@ -182,7 +182,8 @@ int grk_amd_fetch_coded_async(grk_amd_ctx* ctx, uint8_t* dst, uint64_t nbytes);
 void* grk_amd_coded_device_ptr(grk_amd_ctx* ctx);
 void* grk_amd_plane_device_ptr(grk_amd_ctx* ctx, int which /*0: ingest planes, 1: Mallat planes*/);
 /* (after grk_amd_encode_tiles of 8-bit reversible content the Mallat planes hold int16 coefficients -- same strides
- *  and pitches in elements -- unless the environment says GRK_AMD_PLANES16=0; the stage entry points are int32) */
+ *  and pitches in elements -- unless the environment says GRK_AMD_PLANES16=0; grk_amd_stage_ht_encode16 takes such planes,
+ *  every other stage entry point int32 ones) */
 /* the block table of the last encode where it was produced, for exchanges that never touch the host:
  * which 0: uint64 offsets[nblocks], 1: uint32 lengths[nblocks], 2: uint64 bytes used in the arena,
  * 3: uint64[24] diagnostics -- per block class, how many blocks outgrew the capped LDS buffers of the HT encoder and
@@ -198,7 +199,8 @@ int  grk_amd_fetch_coefficients(grk_amd_ctx* ctx, uint32_t comp, int32_t* dst, u
 
 /* ---- stage entry points (parity tests and per-kernel benchmarks call these) ------------------
  * All pointers are DEVICE pointers; planes are int32 (or float32 bit patterns for 9/7) with
- * row stride grk_amd_plane_stride() and plane pitch grk_amd_plane_elems(). */
+ * row stride grk_amd_plane_stride() and plane pitch grk_amd_plane_elems() -- int16 with the same stride and pitch in elements
+ * for grk_amd_stage_ht_encode16 / grk_amd_stage_ht_decode16. */
 int grk_amd_stage_ingest_mct(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
                              const void* d_pixels, void* d_planes);
 /* forward DWT of num_planes planes: d_in (ingest planes) -> d_out (Mallat layout); d_in is
@@ -208,6 +210,14 @@ int grk_amd_stage_dwt_fwd(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32
 /* HT cleanup-encode every block of num_tiles tiles from Mallat planes into the context arena. */
 int grk_amd_stage_ht_encode(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
                             const void* d_mallat);
+/* The same from int16 Mallat planes (same stride and pitch in ELEMENTS): the kernel instances grk_amd_encode_tiles launches for
+ * 8-bit reversible content -- two quads per lane for the aligned 64 x 64 blocks, int16 loads at the edges, their fallback launch;
+ * the context's GRK_AMD_LDS_CAP setting applies as in an encode.  flags: GRK_AMD_STAGE_HT_ROOM = the instance a pipelined encode
+ * launches beside the next frame's DWT.  GRK_AMD_ERR_INVALID for parameters an encode would not keep int16 planes for
+ * (irreversible, more than 8 bits, no DWT level). */
+#define GRK_AMD_STAGE_HT_ROOM 1u
+int grk_amd_stage_ht_encode16(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
+                              const void* d_mallat16, uint32_t flags);
 
 /* ---- decode: the inverse hot path --------------------------------
  * TileProcessor::decompress T1 + post-T1 for HT blocks: T1HT::decompress (t1/t1_ht/T1HT.cpp:129-179,
@@ -324,6 +334,13 @@ int grk_amd_set_decode_segments(grk_amd_ctx* ctx, const uint32_t* first_segment,
 int grk_amd_stage_ht_decode(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
                             const grk_amd_coded_block* table, const void* d_coded, uint64_t coded_bytes,
                             void* d_mallat);
+/* The same into int16 Mallat planes (same stride and pitch in ELEMENTS), as grk_amd_decode_tiles keeps them for 8-bit reversible
+ * HT tiles, with its range check: a value outside [-bias, bias) -- bias 2048 while the context's inverse transform runs on packed
+ * pairs (the default), 32768 with GRK_AMD_DWT_PK=0 -- returns GRK_AMD_ERR_RANGE.  GRK_AMD_ERR_INVALID for irreversible, more
+ * than 8 bits, Part-1 blocks, and while a segment list is set (the refinement passes work on int32 planes). */
+int grk_amd_stage_ht_decode16(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
+                              const grk_amd_coded_block* table, const void* d_coded, uint64_t coded_bytes,
+                              void* d_mallat16);
 
 /* ---- decode-side stages ------------------------------------------
  * inverse DWT of num_planes Mallat planes -> image-domain planes

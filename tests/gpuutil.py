@@ -46,6 +46,29 @@ def upload_planes(planes, params):
     return to_dev(buf.reshape(-1))
 
 
+def dev_planes16(params, nplanes):
+    """int16 planes: the int32 planes' stride and pitch in elements"""
+    n = G.lib().grk_amd_plane_elems(params) * nplanes
+    return _settled(torch.zeros(int(n), dtype=torch.int16, device="cuda"))
+
+
+def planes16_to_numpy(t, params, nplanes):
+    stride = G.lib().grk_amd_plane_stride(params)
+    a = t.cpu().numpy().reshape(nplanes, params.tile_h, stride)
+    return a[:, :, :params.tile_w]
+
+
+def upload_planes16(planes, params):
+    """planes: (n, H, W) integers that fit int16 -> device tensor of int16 in the padded plane layout."""
+    planes = np.asarray(planes)
+    assert planes.min(initial=0) >= -32768 and planes.max(initial=0) <= 32767
+    stride = G.lib().grk_amd_plane_stride(params)
+    n, H, W = planes.shape
+    buf = np.zeros((n, H, stride), np.int16)
+    buf[:, :, :W] = planes
+    return to_dev(buf.reshape(-1))
+
+
 def split_blocks(table, coded):
     return [bytes(coded[int(o):int(o) + int(l)]) for o, l in zip(table["offset"], table["length"])]
 

@@ -257,6 +257,26 @@ def test_ht_encoder_vs_reference_deep_kmax(kmax):
             assert O.ht_encode_sm(sm, kmax) == R.ht_encode_block(sm, kmax), (w, h, kmax, m)
 
 
+@needs_ref
+@pytest.mark.ref
+@pytest.mark.parametrize("kmax", range(8, 13))
+def test_ht_encoder_vs_reference_up_to_kmax_plus_one_bits(kmax):
+    """The Kmax of 8-bit reversible tiles (8 .. 12), magnitudes below 2^Kmax and below 2^(Kmax + 1) -- the whole range K3's contract
+    names, one bit above what the tests above draw --, every content mode of the int16 GPU tests (tests/ht_content.py): the oracle's
+    HT block encoder == ojph_encode_codeblock.  What test_gpu_ht_planes16.py compares the int16 kernel instances with."""
+    import ht_content as HC
+    rng = np.random.default_rng(100 + kmax)
+    for (w, h) in ((64, 64), (33, 17), (64, 3), (5, 9)):
+        for top in (kmax, kmax + 1):
+            cases = [(m, HC.magnitudes(rng, h, w, top, m)) for m in HC.MODES]
+            cases += [("S%d" % k, HC.single_sample(h, w, k, mag)) for k in range(16) for mag in (1, (1 << top) - 1)]
+            cases += [(q, HC.quad_pattern(rng, h, w, top, q)) for q in HC.Q_KINDS]
+            for name, mag in cases:
+                assert mag.max() < (1 << top)
+                sm = O.signmag(HC.signed(rng, mag), kmax)
+                assert O.ht_encode_sm(sm, kmax) == R.ht_encode_block(sm, kmax), (w, h, kmax, top, name)
+
+
 # ---- every bit depth: the oracle chain + the product's Tier-2 writer == grk_compress, 1 .. 16 bits (unsigned) and 2 .. 16 (signed) --
 import chain
 import grok_amd as G

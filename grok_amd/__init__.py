@@ -5,12 +5,12 @@ host geometry / Tier-2) and the plugin shim grok_amd/lib/libgrokj2k_plugin.so.  
 package is only the ctypes binding used by bench.py and the tests; it never computes anything
 itself and raises loudly when the native library is missing.
 """
-from .capi import (TileParams, Block, CodedBlock, Context, lib, lib_path, NativeLibraryMissing,
+from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Context, lib, lib_path, NativeLibraryMissing,
                    tile_layout, reduced_tile_rect, write_codestream, write_tile_part, write_main_header, locate_tile_parts,
                    CS_TLM, CS_PLT, CS_SOP, CS_EPH, CS_PROG, ImageLayout, layout_tiles, same_tile_geometry, write_codestream_layout, Node, NODE_GATHER,
                    StreamInfo, ReaderError, read_header, read_packets)
 
-__all__ = ["TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
+__all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
            "tile_layout", "reduced_tile_rect", "write_codestream", "write_tile_part", "write_main_header", "locate_tile_parts", "CS_TLM", "CS_PLT", "CS_SOP", "CS_EPH", "CS_PROG",
            "ImageLayout", "layout_tiles", "same_tile_geometry", "write_codestream_layout", "Node", "NODE_GATHER",
            "StreamInfo", "ReaderError", "read_header", "read_packets"]

@@ -53,6 +53,17 @@ class ImageLayout(C.Structure):
                    tile_w or offset[0] + w - tile_origin[0], tile_h or offset[1] + h - tile_origin[1])
 
 
+class PixelLayout(C.Structure):
+    """grk_amd_pixel_layout: how the pixels an encode reads / a decode writes lie in memory (all zero: tiles back to back, component
+    planes, tight)."""
+    _fields_ = [("interleaved", C.c_uint8), ("channels", C.c_uint8), ("fill", C.c_uint16), ("reserved", C.c_uint32),
+                ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64), ("tile_pitch", C.c_uint64)]
+
+    @classmethod
+    def make(cls, interleaved=False, channels=0, row_pitch=0, plane_pitch=0, tile_pitch=0, fill=0):
+        return cls(int(bool(interleaved)), int(channels), int(fill), 0, int(row_pitch), int(plane_pitch), int(tile_pitch))
+
+
 class Block(C.Structure):
     _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32),
                 ("px", C.c_uint32), ("py", C.c_uint32), ("comp", C.c_uint16), ("res", C.c_uint8),
@@ -111,6 +122,11 @@ def lib():
         L.grk_amd_plane_elems.restype = u64
         L.grk_amd_plane_elems.argtypes = [PP]
         L.grk_amd_encode_tiles.argtypes = [vp, PP, u32, vp, i32, vp, C.POINTER(u64)]
+        if hasattr(L, "grk_amd_set_pixel_layout"):            # (absent from older builds loaded through GRK_AMD_LIB for A/B timing)
+            L.grk_amd_set_pixel_layout.argtypes = [vp, C.POINTER(PixelLayout)]
+            L.grk_amd_set_decode_pixel_layout.argtypes = [vp, C.POINTER(PixelLayout)]
+            L.grk_amd_pixel_bytes.restype = u64
+            L.grk_amd_pixel_bytes.argtypes = [PP, C.POINTER(PixelLayout), u32, u32, u32]
         L.grk_amd_fetch_table.argtypes = [vp, vp, C.POINTER(u64)]
         L.grk_amd_fetch_coded.argtypes = [vp, vp, u64]
         L.grk_amd_coded_device_ptr.restype = vp
@@ -216,6 +232,12 @@ def tile_layout(params):
     if rc < 0:
         raise ValueError("grk_amd_tile_layout failed: %d" % rc)
     return list(blocks), list(qcd)[:3 * params.num_levels + 1]
+
+
+def pixel_bytes(params, layout=None, w=0, h=0, ntiles=1):
+    """Bytes `ntiles` tiles of w x h (0: the tile's size) span in `layout` (None: the default); 0 for a layout that is invalid for
+    these parameters (grk_amd_pixel_bytes)."""
+    return int(lib().grk_amd_pixel_bytes(C.byref(params), C.byref(layout) if layout is not None else None, int(w), int(h), int(ntiles)))
 
 
 def reduced_tile_rect(params, reduce):
@@ -388,6 +410,8 @@ class Context:
             raise RuntimeError("grk_amd_create(device=%d) failed: %d (no usable HIP device?)" % (device, rc))
         self._h = h
         self._reduce = 0
+        self._layout = None
+        self._dec_layout = None
 
     def close(self):
         if self._h:
@@ -410,6 +434,35 @@ class Context:
     def synchronize(self):
         self._check(self._L.grk_amd_synchronize(self._h), "synchronize")
 
+    def set_pixel_layout(self, layout):
+        """The layout of the pixels every later encode reads (grk_amd_set_pixel_layout); None: the default."""
+        self._check(self._L.grk_amd_set_pixel_layout(self._h, C.byref(layout) if layout is not None else None), "set_pixel_layout")
+        self._layout = layout
+
+    def set_decode_pixel_layout(self, layout):
+        """The layout of the pixels every later decode writes (grk_amd_set_decode_pixel_layout); None: the default."""
+        self._check(self._L.grk_amd_set_decode_pixel_layout(self._h, C.byref(layout) if layout is not None else None), "set_decode_pixel_layout")
+        self._dec_layout = layout
+
+    def _out_in_layout(self, params, layout, w, h, ntiles, out):
+        """the destination of a host decode in `layout`: the caller's uint8 array (gaps are left as they are) or zeros of the extent"""
+        n = pixel_bytes(params, layout, w, h, ntiles)
+        if n == 0:
+            raise ValueError("the layout is invalid for these parameters")
+        if out is None:
+            out = np.zeros(n, np.uint8)
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < n:
+            raise ValueError("out: a contiguous uint8 array of at least %d bytes" % n)
+        return out
+
+    def _with_decode_layout(self, layout, call):
+        keep = self._dec_layout
+        self.set_decode_pixel_layout(layout)
+        try:
+            return call()
+        finally:
+            self.set_decode_pixel_layout(keep)
+
     def encode_tiles(self, params, ntiles, pixels_ptr, on_device, fetch=True):
         """Runs the hot path. Returns (table ndarray, total_bytes) when fetch else None."""
         if fetch:
@@ -423,10 +476,21 @@ class Context:
                                                  None, None), "encode_tiles")
         return None
 
-    def encode_host(self, params, pixels, ntiles=1):
-        """pixels: numpy array holding the tiles back to back (host memory)."""
+    def encode_host(self, params, pixels, ntiles=1, layout=None):
+        """pixels: numpy array holding the tiles back to back (host memory) -- in `layout` (for this call) if one is given, else in
+        the context's."""
         px = np.ascontiguousarray(pixels)
-        table, tot = self.encode_tiles(params, ntiles, px.ctypes.data, False)
+        if layout is None:
+            table, tot = self.encode_tiles(params, ntiles, px.ctypes.data, False)
+        else:
+            if px.nbytes < pixel_bytes(params, layout, 0, 0, ntiles):
+                raise ValueError("the array is smaller than %d tiles in this layout" % ntiles)
+            keep = self._layout
+            self.set_pixel_layout(layout)
+            try:
+                table, tot = self.encode_tiles(params, ntiles, px.ctypes.data, False)
+            finally:
+                self.set_pixel_layout(keep)
         coded = np.empty(tot, np.uint8)
         if tot:
             self._check(self._L.grk_amd_fetch_coded(self._h, coded.ctypes.data, tot), "fetch_coded")
@@ -446,7 +510,8 @@ class Context:
         return arr
 
     def encode_image(self, layout, base, pixels, flags=0):
-        """Whole image (C, H, W) of any tile layout -> codestream bytes (grk_amd_encode_image)."""
+        """Whole image of any tile layout -> codestream bytes (grk_amd_encode_image): (C, H, W), or the image as the context's pixel
+        layout says (set_pixel_layout: (H, W, C) with row_pitch the image's)."""
         px = np.ascontiguousarray(pixels)
         cap = px.size * 4 + (1 << 20)
         out = np.empty(cap, np.uint8)
@@ -553,12 +618,18 @@ class Context:
                                                       d_mallat16),
                     "stage_ht_decode16")
 
-    def decode_host(self, params, table, coded, ntiles=1):
-        """table: CODED_DTYPE rows, coded: bytes-like (host). Returns pixels (ntiles, C, H, W)."""
+    def decode_host(self, params, table, coded, ntiles=1, layout=None, out=None):
+        """table: CODED_DTYPE rows, coded: bytes-like (host). Returns pixels (ntiles, C, H, W) -- or, with a `layout` (for this call),
+        the uint8 buffer `out` (or a new one) holding them in that layout."""
         t = np.ascontiguousarray(table)
         cb = np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else np.ascontiguousarray(coded)
         dt = np.uint8 if params.prec <= 8 else np.uint16
         _, _, w, h = self.decode_size(params)
+        if layout is not None:
+            out = self._out_in_layout(params, layout, w, h, ntiles, out)
+            self._with_decode_layout(layout, lambda: self._check(self._L.grk_amd_decode_tiles(
+                self._h, C.byref(params), ntiles, t.ctypes.data, cb.ctypes.data, cb.size, 0, out.ctypes.data, 0), "decode_tiles"))
+            return out
         out = np.zeros((ntiles, params.num_comps, h, w), dt)
         self._check(self._L.grk_amd_decode_tiles(self._h, C.byref(params), ntiles, t.ctypes.data, cb.ctypes.data, cb.size, 0,
                                                  out.ctypes.data, 0), "decode_tiles")
@@ -577,12 +648,17 @@ class Context:
             return reduced_tile_rect(params, self._reduce)
         return params.tile_x0, params.tile_y0, params.tile_w, params.tile_h
 
-    def decode_region_host(self, params, table, coded, x0, y0, x1, y1):
+    def decode_region_host(self, params, table, coded, x0, y0, x1, y1, layout=None, out=None):
         """Windowed decode of one tile -> pixels (C, y1 - y0, x1 - x0); the window is in the coordinates of the tile decode_size
-        describes (the reduced tile under set_decode_reduce)."""
+        describes (the reduced tile under set_decode_reduce).  With a `layout` (its pitches the window's): the uint8 buffer."""
         t = np.ascontiguousarray(table)
         cb = np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else np.ascontiguousarray(coded)
         dt = np.uint8 if params.prec <= 8 else np.uint16
+        if layout is not None:
+            out = self._out_in_layout(params, layout, x1 - x0, y1 - y0, 1, out)
+            self._with_decode_layout(layout, lambda: self._check(self._L.grk_amd_decode_region(
+                self._h, C.byref(params), t.ctypes.data, cb.ctypes.data, cb.size, 0, x0, y0, x1, y1, out.ctypes.data, 0), "decode_region"))
+            return out
         out = np.zeros((params.num_comps, y1 - y0, x1 - x0), dt)
         self._check(self._L.grk_amd_decode_region(self._h, C.byref(params), t.ctypes.data, cb.ctypes.data, cb.size, 0,
                                                   x0, y0, x1, y1, out.ctypes.data, 0), "decode_region")
@@ -598,10 +674,16 @@ class Context:
         self._check(self._L.grk_amd_decode_tiles(self._h, C.byref(params), ntiles, t.ctypes.data, d_coded, coded_bytes, 1,
                                                  d_pixels, 1), "decode_tiles")
 
-    def decode_image(self, cs):
-        """Codestream (bytes-like, host) -> pixels (C, H, W) of the image area (grk_amd_decode_image, host pixels)."""
+    def decode_image(self, cs, layout=None, out=None):
+        """Codestream (bytes-like, host) -> pixels (C, H, W) of the image area (grk_amd_decode_image, host pixels) -- or, with a
+        `layout` (row_pitch the image's), the uint8 buffer holding the image in it."""
         buf = _cs_array(cs)
         info = read_header(buf)
+        if layout is not None:
+            out = self._out_in_layout(info.base, layout, info.layout.x1 - info.layout.x0, info.layout.y1 - info.layout.y0, 1, out)
+            self._with_decode_layout(layout, lambda: self._check(self._L.grk_amd_decode_image(
+                self._h, buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "decode_image"))
+            return out
         out = np.zeros((info.base.num_comps, info.layout.y1 - info.layout.y0, info.layout.x1 - info.layout.x0),
                        np.uint8 if info.base.prec <= 8 else np.uint16)
         self._check(self._L.grk_amd_decode_image(self._h, buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "decode_image")

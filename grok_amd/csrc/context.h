@@ -102,6 +102,8 @@ struct grk_amd_ctx {
     std::vector<float> dec_steps;                           // decode: band step sizes as the host holds them (optional), [comp][band]
     std::vector<uint32_t> dec_seg_first;                    // Part-1 decode: codeword segments (optional), [nblocks + 1]
     std::vector<grk_amd_segment> dec_segs;
+    grk_amd_pixel_layout enc_layout{};                      // the pixels an encode reads (grk_amd_set_pixel_layout; all zero: the default)
+    grk_amd_pixel_layout dec_layout{};                      // the pixels a decode writes (grk_amd_set_decode_pixel_layout)
     uint32_t dec_reduce = 0;                                // decode at 1 / 2^dec_reduce of the size (grk_amd_set_decode_reduce)
     std::vector<uint32_t> red_seg_first;                    // ... the segment list of the blocks that decode keeps (decode_impl)
     std::vector<grk_amd_segment> red_segs;
@@ -243,6 +245,11 @@ int probe_streams(grk_amd_ctx* c);                                              
 int vetted_stream(grk_amd_ctx* c, hipStream_t* cur, const std::vector<hipStream_t>& against, int* replaced);     // streams.hip
 int join_side(grk_amd_ctx* c);                                                                                   // streams.hip
 int sequence_streams(grk_amd_ctx* k, bool part1);                                                                // streams.hip
+// A pixel layout resolved for tiles of w x h samples per component (context.hip): every pitch in bytes, `lay` as DwtLevelArgs::px_lay
+// (0: what the default layout amounts to), `bytes` the extent of ntiles tiles
+struct PixelLayout { uint32_t lay, channels, xstep, fill; uint64_t row, kstep, tile, bytes; };
+bool resolve_pixel_layout(const grk_amd_tile_params& p, const grk_amd_pixel_layout* l, uint32_t w, uint32_t h, uint32_t ntiles,
+                          PixelLayout& out, const char** why);
 bool planes16_ok(const grk_amd_tile_params& p);                                                                  // encode.hip
 bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l);                                                    // encode.hip
 #pragma GCC visibility pop

@@ -40,7 +40,7 @@ RegionPlan plan_region(const TileGeom& g, Rect win)
 // d_pixels != nullptr: the last level writes the pixels itself (K7 fused, out_bytes 1 or 2) and d_out is not touched;
 // plan != nullptr: only what the window needs is synthesised, and d_pixels is the window (K7 fused required)
 int run_idwt(grk_amd_ctx* c, uint32_t nplanes, const void* d_mallat, void* d_out, void* d_pixels = nullptr,
-             uint32_t ntiles = 0, uint32_t out_bytes = 0, const RegionPlan* plan = nullptr, bool h16 = false)
+             uint32_t ntiles = 0, uint32_t out_bytes = 0, const RegionPlan* plan = nullptr, bool h16 = false, const PixelLayout* px = nullptr)
 {
     const TileGeom& g = c->geom;
     const uint32_t L = g.p.num_levels;
@@ -72,6 +72,10 @@ int run_idwt(grk_amd_ctx* c, uint32_t nplanes, const void* d_mallat, void* d_out
         a.xcd = c->dwt_xcd;
         a.h16 = h16 ? 1 : 0; a.status = (unsigned int*)c->flag.p;
         a.pk = h16 && c->dwt_pk && !plan;            // (the block decoder flagged every coefficient outside the packed range)
+        if (l == 0 && d_pixels && px && px->lay) {
+            a.px_lay = px->lay; a.px_chan = px->channels; a.px_xstep = px->xstep; a.px_fill = px->fill;
+            a.px_row = px->row; a.px_kstep = px->kstep; a.px_tile = px->tile;
+        }
         const uint32_t sh = (a.ch + a.py + 1) >> 1;
         uint32_t seg = 64;
         const uint64_t strips = (((a.cw + a.px + 1) >> 1) + idwt_level_strip_pairs(a) - 1) / idwt_level_strip_pairs(a);
@@ -392,10 +396,20 @@ int check_decode_status(grk_amd_ctx* c)
     return GRK_AMD_OK;
 }
 
-int run_egress(grk_amd_ctx* c, uint32_t ntiles, const void* d_planes, void* d_pixels, uint32_t out_bytes)
+// the context's decode layout for `ntiles` outputs of w x h (0: the tile of the current geometry), or GRK_AMD_ERR_INVALID and the reason
+int decode_layout(grk_amd_ctx* c, uint32_t w, uint32_t h, uint32_t ntiles, PixelLayout& px)
+{
+    const char* why = "";
+    if (!resolve_pixel_layout(c->geom.p, &c->dec_layout, w, h, ntiles, px, &why)) return fail(c, GRK_AMD_ERR_INVALID, why);
+    if (px.lay && (c->geom.p.prec + 7u) / 8u > 2) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "pixel layout: samples of more than 16 bits leave in the default layout only");
+    return GRK_AMD_OK;
+}
+
+int run_egress(grk_amd_ctx* c, uint32_t ntiles, const void* d_planes, void* d_pixels, uint32_t out_bytes, const PixelLayout& px)
 {
     const TileGeom& g = c->geom;
     EgressArgs a{};
+    a.px_lay = px.lay; a.px_chan = px.channels; a.px_xstep = px.xstep; a.px_fill = px.fill; a.px_row = px.row; a.px_kstep = px.kstep; a.px_tile = px.tile;
     a.planes = (const int32_t*)d_planes; a.pixels = d_pixels;
     a.w = g.p.tile_w; a.h = g.p.tile_h; a.stride = g.stride; a.pitch = g.plane_elems;
     a.ncomp = g.p.num_comps; a.ntiles = ntiles;
@@ -517,18 +531,22 @@ static int decode_impl(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nt
                 ++i;
             }
     }
+    // the pixels' layout (grk_amd_set_decode_pixel_layout) for what this call writes: the window, the reduced tile, the tile
+    PixelLayout px;
+    rc = decode_layout(c, win ? win->x1 - win->x0 : 0, win ? win->y1 - win->y0 : 0, ntiles, px); if (rc) return rc;
     const void* d_coded = coded;
     if (!coded_on_device) {
         HIP_TRY(c, c->dec_coded.ensure(coded_bytes + 64), "alloc coded staging");
         rc = copy_h2d(c, c->dec_coded.p, coded, coded_bytes); if (rc) return rc;
         d_coded = c->dec_coded.p;
     }
-    const size_t px_bytes = win ? (size_t)g.p.num_comps * (win->x1 - win->x0) * (win->y1 - win->y0) * bps
-                                : (size_t)nplanes * g.p.tile_w * g.p.tile_h * bps;
+    const size_t px_bytes = px.bytes;     // (the default layout: the tight window / tiles)
     void* d_px = pixels;
     if (!pixels_on_device) {
         HIP_TRY(c, c->dec_pixels.ensure(px_bytes), "alloc pixel staging");
         d_px = c->dec_pixels.p;
+        // the extent comes back as one copy, gaps included -- and what the caller has in the gaps is to stay: it goes up first
+        if (px.lay) { rc = copy_h2d(c, d_px, pixels, px_bytes); if (rc) return rc; }
     }
     if (!fuse_out) HIP_TRY(c, c->p0.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc planes");
     HIP_TRY(c, c->p1.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc Mallat planes");
@@ -546,10 +564,10 @@ static int decode_impl(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nt
         // with at least one DWT level and 8-/16-bit pixels the last level writes the pixels itself (K7 fused): the
         // int32 image planes (4 bytes per sample written and read back) never exist
         if (fuse_out) {
-            rc = run_idwt(c, nplanes, c->p1.p, nullptr, d_px, ntiles, bps, win ? &plan : nullptr, h16); if (rc) return rc;
+            rc = run_idwt(c, nplanes, c->p1.p, nullptr, d_px, ntiles, bps, win ? &plan : nullptr, h16, &px); if (rc) return rc;
         } else {
             rc = run_idwt(c, nplanes, c->p1.p, c->p0.p); if (rc) return rc;
-            rc = run_egress(c, ntiles, c->p0.p, d_px, bps); if (rc) return rc;
+            rc = run_egress(c, ntiles, c->p0.p, d_px, bps, px); if (rc) return rc;
         }
     }
     if (!pixels_on_device) {
@@ -574,7 +592,7 @@ int grk_amd_decode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             // what the caller set on the context applies to the frame wherever it is decoded
             if (k->dec_qcd != c->dec_qcd || k->dec_steps != c->dec_steps) { k->dec_qcd = c->dec_qcd; k->dec_steps = c->dec_steps; k->have_geom = false; }
             if (k->dec_seg_first != c->dec_seg_first) k->dec_seg_first = c->dec_seg_first;
-            k->dec_reduce = c->dec_reduce;
+            k->dec_reduce = c->dec_reduce; k->dec_layout = c->dec_layout;
             if (k->dec_segs.size() != c->dec_segs.size() ||
                 (!c->dec_segs.empty() && std::memcmp(k->dec_segs.data(), c->dec_segs.data(), c->dec_segs.size() * sizeof(c->dec_segs[0])) != 0))
                 k->dec_segs = c->dec_segs;
@@ -720,7 +738,10 @@ int grk_amd_stage_egress(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
     if (!c || !p || !d_planes || !d_pixels) return GRK_AMD_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     int rc = ensure_geom(c, p); if (rc) return rc;
-    return run_egress(c, ntiles, d_planes, d_pixels, (p->prec + 7u) / 8u);
+    if (!ntiles) return GRK_AMD_ERR_INVALID;
+    PixelLayout px;
+    rc = decode_layout(c, 0, 0, ntiles, px); if (rc) return rc;
+    return run_egress(c, ntiles, d_planes, d_pixels, (p->prec + 7u) / 8u, px);
 }
 
 int grk_amd_set_decode_planes16(grk_amd_ctx* c, int on)

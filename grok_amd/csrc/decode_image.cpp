@@ -90,7 +90,14 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
     const uint32_t nc = info.base.num_comps, bps = (info.base.prec + 7u) / 8u, nt = info.num_tiles;
     for (uint32_t k = 0; k < nc; ++k)
         if (info.comp_dx[k] != 1 || info.comp_dy[k] != 1) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "sub-sampled components");
-    const uint64_t W = info.layout.x1 - info.layout.x0, H = info.layout.y1 - info.layout.y0, total = W * H * nc * bps;
+    const uint64_t W = info.layout.x1 - info.layout.x0, H = info.layout.y1 - info.layout.y0;
+    // the image in the context's decode layout (grk_amd_set_decode_pixel_layout: row_pitch the image's; the default: tight planes)
+    PixelLayout ipx;
+    {
+        const char* lwhy = "";
+        if (W >> 32 || H >> 32 || !resolve_pixel_layout(info.base, &c->dec_layout, (uint32_t)W, (uint32_t)H, 1, ipx, &lwhy)) return fail(c, GRK_AMD_ERR_INVALID, lwhy);
+    }
+    const uint64_t total = ipx.bytes;
     if (total > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "the image does not fit `cap`");
     // the tiles, grouped by geometry
     std::vector<grk_amd_tile_params> tp(nt);
@@ -164,9 +171,21 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
         return rc;
     }
     void* d_img = pixels;
-    if (!pixels_on_device) { HIP_TRY(c, c->img_pixels.ensure(total), "alloc the image"); d_img = c->img_pixels.p; }
+    if (!pixels_on_device) {
+        HIP_TRY(c, c->img_pixels.ensure(total), "alloc the image"); d_img = c->img_pixels.p;
+        // (the extent comes back as one copy: what the caller has in a layout's gaps goes up first)
+        if (ipx.lay) { rc = copy_h2d(c, d_img, pixels, total); if (rc) return rc; }
+    }
+    // the tile decoder writes tight tiles in the same kind of layout; KP places them by rows of whole pixels
+    const uint32_t unit_ch = ipx.lay == 2 ? ipx.channels : nc;
+    struct TileLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~TileLayout() { c->dec_layout = keep; } } tile_layout{c, c->dec_layout};
+    {
+        grk_amd_pixel_layout tl{};
+        if (ipx.lay == 2) { tl.interleaved = 1; tl.channels = (uint8_t)ipx.channels; tl.fill = c->dec_layout.fill; }
+        c->dec_layout = tl;
+    }
     uint64_t group_bytes = 0;
-    for (const auto& G : g.members) group_bytes = std::max<uint64_t>(group_bytes, (uint64_t)tp[G[0]].tile_w * tp[G[0]].tile_h * nc * bps * G.size());
+    for (const auto& G : g.members) group_bytes = std::max<uint64_t>(group_bytes, (uint64_t)tp[G[0]].tile_w * tp[G[0]].tile_h * unit_ch * bps * G.size());
     HIP_TRY(c, c->img_tiles.ensure(group_bytes), "alloc a group's tiles");
     HIP_TRY(c, c->img_status.ensure(64), "alloc status");
     HIP_TRY(c, c->img_rects.ensure((size_t)nt * 8), "alloc places");
@@ -194,8 +213,8 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
             if (rc) return rc;
         }
         HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->img_status.p, (const unsigned int*)c->flag.p, false, c->stream), "keep status");
-        const PlaceArgs a{(const uint8_t*)c->img_tiles.p, (uint32_t)G.size(), p.tile_w, p.tile_h, nc, bps, (const uint32_t*)c->img_rects.p + 2 * rect_at,
-                          (uint8_t*)d_img, (uint32_t)W, (uint32_t)H};
+        const PlaceArgs a{(const uint8_t*)c->img_tiles.p, (uint32_t)G.size(), p.tile_w, p.tile_h, ipx.lay == 2 ? 1u : nc, ipx.lay == 2 ? unit_ch * bps : bps,
+                          (const uint32_t*)c->img_rects.p + 2 * rect_at, (uint8_t*)d_img, (uint32_t)W, (uint32_t)H, ipx.lay ? ipx.row : 0, ipx.lay == 1 ? ipx.kstep : 0};
         HIP_TRY(c, launch_t2dec_place(a, c->stream), "launch placement");
         ++c->img_launches[1];
         rect_at += G.size();

@@ -2,10 +2,19 @@
 #include "context.h"
 
 namespace {
-int run_ingest(grk_amd_ctx* c, uint32_t ntiles, const void* d_pixels, void* d_planes)
+// the context's encode layout for `ntiles` tiles of the current geometry, or GRK_AMD_ERR_INVALID and the reason
+int encode_layout(grk_amd_ctx* c, uint32_t ntiles, PixelLayout& px)
+{
+    const char* why = "";
+    if (!resolve_pixel_layout(c->geom.p, &c->enc_layout, 0, 0, ntiles, px, &why)) return fail(c, GRK_AMD_ERR_INVALID, why);
+    return GRK_AMD_OK;
+}
+
+int run_ingest(grk_amd_ctx* c, uint32_t ntiles, const void* d_pixels, void* d_planes, const PixelLayout& px)
 {
     const TileGeom& g = c->geom;
     IngestArgs a{};
+    a.px_lay = px.lay; a.px_xstep = px.xstep; a.px_row = px.row; a.px_kstep = px.kstep; a.px_tile = px.tile;
     a.pixels = d_pixels; a.planes = (int32_t*)d_planes;
     a.w = g.p.tile_w; a.h = g.p.tile_h; a.stride = g.stride; a.pitch = g.plane_elems;
     a.ncomp = g.p.num_comps; a.ntiles = ntiles;
@@ -72,7 +81,7 @@ HtArgs make_ht_args(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, int* 
 
 // d_pixels != nullptr: level 0 reads the caller's pixels directly (K1 fused into K2), d_in is unused
 int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const void* d_pixels = nullptr, uint32_t ntiles = 0,
-            bool overlap_ht = false, bool h16 = false)
+            bool overlap_ht = false, bool h16 = false, const PixelLayout* px = nullptr)
 {
     const TileGeom& g = c->geom;
     const uint32_t L = g.p.num_levels;
@@ -104,6 +113,9 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
         a.h16 = h16 ? 1 : 0;
         a.pk = h16 && c->dwt_pk && pk16_level_ok(g.p, l);
         a.xcd = c->dwt_xcd;
+        if (l == 0 && d_pixels && px && px->lay) {     // (before the strips are counted: the layout decides between the level-0 kernels)
+            a.px_lay = px->lay; a.px_chan = px->channels; a.px_xstep = px->xstep; a.px_row = px->row; a.px_kstep = px->kstep; a.px_tile = px->tile;
+        }
         // enough workgroups to cover the chip several times, few enough to amortise warm-up rows (profiles/r06_dwt_reads.txt: at 4096
         // the 8K level 0 ran 16-row segments and read 1.55 x its pixels; 2048 -> 32-row segments, 1.35 x, the DWT 1 % faster)
         const uint32_t sh = (a.ch + a.py + 1) >> 1;           // row pairs on the coordinate grid
@@ -224,7 +236,10 @@ int grk_amd_stage_ingest_mct(grk_amd_ctx* c, const grk_amd_tile_params* p, uint3
     if (!c || !p || !d_pixels || !d_planes) return GRK_AMD_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     int rc = ensure_geom(c, p); if (rc) return rc;
-    return run_ingest(c, ntiles, d_pixels, d_planes);
+    if (!ntiles) return GRK_AMD_ERR_INVALID;
+    PixelLayout px;
+    rc = encode_layout(c, ntiles, px); if (rc) return rc;
+    return run_ingest(c, ntiles, d_pixels, d_planes, px);
 }
 
 int grk_amd_stage_dwt_fwd(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nplanes, void* d_in, void* d_out)
@@ -393,11 +408,12 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     int rc = ensure_geom(c, p); if (rc) return rc;
     const TileGeom& g = c->geom;
-    const size_t tile_bytes = (size_t)g.p.num_comps * g.p.tile_w * g.p.tile_h * ((g.p.prec + 7) / 8);
+    PixelLayout px;                      // (the default layout: px.lay = 0, px.bytes = the tight tiles)
+    rc = encode_layout(c, ntiles, px); if (rc) return rc;
     const void* d_px = pixels;
     if (!on_device) {
-        HIP_TRY(c, c->pixels.ensure(tile_bytes * ntiles), "alloc pixel staging");
-        rc = copy_h2d(c, c->pixels.p, pixels, tile_bytes * ntiles); if (rc) return rc;
+        HIP_TRY(c, c->pixels.ensure(px.bytes), "alloc pixel staging");
+        rc = copy_h2d(c, c->pixels.p, pixels, px.bytes); if (rc) return rc;
         d_px = c->pixels.p;
     }
     const uint32_t nplanes = ntiles * g.p.num_comps;
@@ -458,7 +474,7 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             if (!c->ev_px) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_px, hipEventDisableTiming), "create event");
             ScopedTimer tf(c, 3);              // (the call's timer on the stream that carries the call)
             c->want_px_event = true;
-            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, false, h16);
+            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, false, h16, &px);
             c->want_px_event = false;
             if (rc) return rc;
             // the pixel-lifetime contract of every other path: work queued on the context's stream after this call comes after the read
@@ -482,9 +498,9 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             else HIP_TRY(c, launch_ht_alloc_init(h, c->stream), "reset arena allocator");
         }
         if (fused) {
-            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, ov, h16); if (rc) return rc;
+            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, ov, h16, &px); if (rc) return rc;
         } else {
-            rc = run_ingest(c, ntiles, d_px, c->p0.p); if (rc) return rc;
+            rc = run_ingest(c, ntiles, d_px, c->p0.p, px); if (rc) return rc;
             rc = run_dwt(c, nplanes, c->p0.p, c->p1.p, nullptr, ntiles, ov); if (rc) return rc;
         }
         rc = run_ht(c, ntiles, c->p1.p, ov, h16); if (rc) return rc;

@@ -9,6 +9,7 @@
 // Here the tiles are grouped by geometry, each group goes through grk_amd_encode_tiles as one batch, and the
 // tile-parts are written in tile order (codestream/CodeStreamCompress.cpp:535-603); those steps (image.h) serve node.cpp too.
 #include "image.h"
+#include "context.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -43,7 +44,7 @@ int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p)
 }
 
 int grk_amd::plain_image(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,
-                         std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g)
+                         std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g, const grk_amd_pixel_layout* lay)
 {
     const int64_t nt = grk_amd_layout_num_tiles(im);
     if (nt < 0) return (int)nt;
@@ -51,7 +52,12 @@ int grk_amd::plain_image(const grk_amd_image_layout* im, const grk_amd_tile_para
     if ((flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
     const uint64_t W = im->x1 - im->x0, H = im->y1 - im->y0;
     src = SourcePlanes{(const uint8_t*)pixels, (base->prec + 7u) / 8u, {}};
-    for (uint32_t c = 0; c < nc; ++c) src.comp.push_back({c * W * H * src.bps, W, im->x0, im->y0});
+    PixelLayout px;
+    const char* why = "";
+    if (W >> 32 || H >> 32 || !resolve_pixel_layout(*base, lay, (uint32_t)W, (uint32_t)H, 1, px, &why)) return GRK_AMD_ERR_INVALID;
+    src.row_pitch = px.row;
+    src.channels = px.lay == 2 ? px.channels : 0;
+    for (uint32_t c = 0; c < nc; ++c) src.comp.push_back({c * px.kstep, W, im->x0, im->y0});
     units.assign(ntiles, Unit{{}, 0});
     for (uint32_t t = 0; t < ntiles; ++t) {
         int rc = grk_amd_layout_tile(im, base, t, &units[t].p);
@@ -63,16 +69,18 @@ int grk_amd::plain_image(const grk_amd_image_layout* im, const grk_amd_tile_para
 
 void grk_amd::stage_units(const SourcePlanes& src, const std::vector<Unit>& units, const std::vector<uint32_t>& idx, uint8_t* dst, uint32_t threads)
 {
-    const size_t bytes = idx.empty() ? 0 : unit_bytes(units[idx[0]], src.bps), bps = src.bps;
+    const size_t bytes = idx.empty() ? 0 : staged_bytes(src, units[idx[0]]), bps = src.bps;
+    const size_t xstep = src.channels ? src.channels * bps : bps;
     (void)parallel_for(threads, threads, [&](size_t j) -> int {
         for (size_t i = 0; i < idx.size(); ++i) {
             const grk_amd_tile_params& q = units[idx[i]].p;
-            const size_t y0 = (size_t)q.tile_h * j / threads, y1 = (size_t)q.tile_h * (j + 1) / threads, row = (size_t)q.tile_w * bps;
-            for (uint32_t k = 0; k < q.num_comps; ++k) {
+            const size_t y0 = (size_t)q.tile_h * j / threads, y1 = (size_t)q.tile_h * (j + 1) / threads, row = (size_t)q.tile_w * xstep;
+            for (uint32_t k = 0; k < (src.channels ? 1u : q.num_comps); ++k) {
                 const SourcePlanes::Plane& c = src.comp[units[idx[i]].c0 + k];
-                const uint8_t* from = src.px + c.at + ((q.tile_y0 - c.y0) * c.w + (q.tile_x0 - c.x0)) * bps;
+                const size_t pitch = src.row_pitch ? src.row_pitch : c.w * bps;
+                const uint8_t* from = src.px + c.at + (q.tile_y0 - c.y0) * pitch + (q.tile_x0 - c.x0) * xstep;
                 for (size_t y = y0; y < y1; ++y)
-                    std::memcpy(dst + i * bytes + ((size_t)k * q.tile_h + y) * row, from + y * c.w * bps, row);
+                    std::memcpy(dst + i * bytes + ((size_t)k * q.tile_h + y) * row, from + y * pitch, row);
             }
         }
         return GRK_AMD_OK;
@@ -91,7 +99,7 @@ int grk_amd::encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const
     for (size_t k = 0; k < g.members.size(); ++k) {
         const auto& G = g.members[k];
         const grk_amd_tile_params& p = units[G[0]].p;
-        staging.resize(unit_bytes(units[G[0]], src.bps) * G.size());
+        staging.resize(staged_bytes(src, units[G[0]]) * G.size());
         stage_units(src, units, G, staging.data(), 1);
         const uint64_t bpu = (uint64_t)g.geoms[k].blocks_per_comp * p.num_comps;
         std::vector<grk_amd_coded_block> table(bpu * G.size());
@@ -151,8 +159,13 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
     std::vector<Unit> tiles;
     SourcePlanes src;
     UnitGroups g;
-    int64_t rc = plain_image(im, base, pixels, flags, tiles, src, g);
+    // `pixels` is the whole image in the context's encode layout; the tiles are staged tight in the same kind of layout, and the
+    // batches below read them as that
+    const grk_amd_pixel_layout whole = ctx->enc_layout;
+    int64_t rc = plain_image(im, base, pixels, flags, tiles, src, g, &whole);
     if (rc) return rc;
+    struct StagedLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~StagedLayout() { c->enc_layout = keep; } } staged{ctx, whole};
+    ctx->enc_layout = staged_layout(src);
     const uint32_t ntiles = (uint32_t)tiles.size();
     // Tier-2 on the device (grk_amd_assemble_device; GRK_AMD_IMAGE_T2=host: the host writer below, which is also where a layout beyond
     // the device writer's tables goes): every group's finished tile-parts appended in the context's output buffer, then -- their sizes
@@ -166,7 +179,7 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
         for (size_t k = 0; k < g.members.size() && rc >= 0; ++k) {
             const auto& G = g.members[k];
             const grk_amd_tile_params& p = tiles[G[0]].p;
-            staging.resize(unit_bytes(tiles[G[0]], src.bps) * G.size());
+            staging.resize(staged_bytes(src, tiles[G[0]]) * G.size());
             stage_units(src, tiles, G, staging.data(), 1);
             rc = grk_amd_encode_tiles(ctx, &p, (uint32_t)G.size(), staging.data(), 0, nullptr, nullptr);
             if (rc < 0) return rc;
@@ -207,6 +220,10 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
                                                    uint8_t* out, uint64_t cap)
 {
     if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
+    {   // (components of different sizes have no interleaved form, and the runs are staged as planes)
+        const grk_amd_pixel_layout& l = ctx->enc_layout;
+        if (l.interleaved || l.channels || l.row_pitch || l.plane_pitch || l.tile_pitch) return GRK_AMD_ERR_UNSUPPORTED;
+    }
     const int64_t nt = grk_amd_layout_num_tiles(im);
     if (nt < 0) return nt;
     const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps;

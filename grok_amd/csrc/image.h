@@ -14,13 +14,16 @@ namespace grk_amd {
 // component in the caller's image
 struct Unit { grk_amd_tile_params p; uint32_t c0; };
 
-// The caller's planar image: component c's samples start comp[c].at bytes into `px`, in rows of comp[c].w samples, the first of
-// them at (comp[c].x0, comp[c].y0) on the component's grid
+// The caller's image: component c's samples start comp[c].at bytes into `px`, in rows of comp[c].w samples, the first of
+// them at (comp[c].x0, comp[c].y0) on the component's grid.  Under a pixel layout (grk_amd_set_pixel_layout; plain_image) rows lie
+// row_pitch bytes apart (0: tight) and, with channels != 0, the components are interleaved: channels samples per pixel in memory
 struct SourcePlanes {
     const uint8_t* px;
     uint32_t bps;                                  // bytes per sample
     struct Plane { uint64_t at, w, x0, y0; };
     std::vector<Plane> comp;
+    uint64_t row_pitch = 0;
+    uint32_t channels = 0;
 };
 
 struct UnitGroups {
@@ -35,12 +38,26 @@ int add_unit(UnitGroups& g, const grk_amd_tile_params& p);
 
 // A plain image (component-major planar, tight, W x H per component): one unit per tile with all components, grouped.
 // A file with TLM holds at most 255 tiles (one-byte Ttlm): GRK_AMD_ERR_UNSUPPORTED before any work.
+// `lay` (or null: that default): the layout of `pixels`, row_pitch the image's; GRK_AMD_ERR_INVALID when it does not fit the image.
 int plain_image(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,
-                std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g);
+                std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g, const grk_amd_pixel_layout* lay = nullptr);
 
 inline size_t unit_bytes(const Unit& u, uint32_t bps) { return (size_t)u.p.tile_w * u.p.tile_h * u.p.num_comps * bps; }
+// ... as stage_units lays the unit out: an interleaved source keeps its samples per pixel
+inline size_t staged_bytes(const SourcePlanes& src, const Unit& u)
+{
+    return src.channels ? (size_t)u.p.tile_w * u.p.tile_h * src.channels * src.bps : unit_bytes(u, src.bps);
+}
+// the layout grk_amd_encode_tiles reads what stage_units wrote in
+inline grk_amd_pixel_layout staged_layout(const SourcePlanes& src)
+{
+    grk_amd_pixel_layout l{};
+    if (src.channels) { l.interleaved = 1; l.channels = (uint8_t)src.channels; }
+    return l;
+}
 
-// units[idx[i]]'s rows out of the source into `dst`, tight, component-major, unit i at i x unit_bytes (a group's units are of one
+// units[idx[i]]'s rows out of the source into `dst`, tight, component-major (an interleaved source: tight rows of whole pixels, one
+// memcpy per row), unit i at i x staged_bytes (a group's units are of one
 // size); each of `threads` threads copies its share of the rows of every unit component
 void stage_units(const SourcePlanes& src, const std::vector<Unit>& units, const std::vector<uint32_t>& idx, uint8_t* dst, uint32_t threads);
 

@@ -8,7 +8,7 @@ namespace grk_amd {
 
 // ---- K1: ingest + DC shift + forward colour transform (kernels_ingest.hip) -------------------
 struct IngestArgs {
-    const void* pixels;      // tiles back to back, component-major planar, tight
+    const void* pixels;      // tiles back to back, component-major planar, tight -- or as px_lay .. px_tile say
     int32_t*    planes;      // [tile][comp] planes, `stride` elements per row, `pitch` per plane
     uint32_t w, h, stride;
     uint64_t pitch;
@@ -18,6 +18,10 @@ struct IngestArgs {
     int32_t  sext;               // signed samples: 1 << (8*bytes_per_sample - 1) (stored as int8/int16), else 0
     int      mct;                // apply RCT/ICT to components 0..2
     int      irreversible;
+    // a layout other than the default (grk_amd_set_pixel_layout): sample (x, y) of component k of tile t lies at
+    // pixels + t * px_tile + y * px_row + k * px_kstep + x * px_xstep (bytes); px_lay = 0: the default, the four are not read
+    uint32_t px_lay, px_xstep;
+    uint64_t px_row, px_kstep, px_tile;
 };
 hipError_t launch_ingest(const IngestArgs& a, hipStream_t s);
 
@@ -32,7 +36,7 @@ struct DwtLevelArgs {
     uint32_t seg_pairs;   // row pairs per workgroup
     int      irreversible;
     // level 0 fused with K1 (launch_dwt_level0_fused): rows come from the caller's pixel planes
-    const void* pixels;   // tiles back to back, component-major planar, tight (as IngestArgs::pixels)
+    const void* pixels;   // as IngestArgs::pixels
     uint32_t px_bytes;    // 1 or 2 bytes per sample
     int32_t  dc;          // 2^(prec-1) or 0
     int32_t  sext;        // signed samples: sign bit of the stored word (see IngestArgs), else 0
@@ -44,6 +48,10 @@ struct DwtLevelArgs {
     int      h16;         // reversible, 8-bit pixels: every plane (in, ll, mallat) holds int16 instead of int32
     int      xcd;         // XCD-aware workgroup order (kernels_dwt.hip)
     int      pk;          // h16 and every intermediate of this level within 16 bits: arithmetic on packed int16 pairs
+    // level 0 fused with K1 under a pixel layout other than the default (as IngestArgs): px_lay = 0 the default (tight planar, the
+    // fields below are not read), 1 planar with pitches, 2 pixel-interleaved with px_chan samples per pixel in memory
+    uint32_t px_lay, px_chan, px_xstep;
+    uint64_t px_row, px_kstep, px_tile;
 };
 hipError_t launch_dwt_level(const DwtLevelArgs& a, hipStream_t s);
 hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s);
@@ -200,7 +208,7 @@ struct IdwtLevelArgs {
     uint32_t seg_pairs;
     int      irreversible;
     // last level fused with K7 (launch_idwt_level0_fused): the rows leave as the caller's pixels
-    void*    pixels;      // tiles back to back, component-major planar, tight (as EgressArgs::pixels)
+    void*    pixels;      // as EgressArgs::pixels
     uint32_t px_bytes;    // 1 or 2 bytes per sample
     int32_t  dc, lo, hi;  // DC shift and clamp range (EgressArgs)
     int      mct;
@@ -213,6 +221,11 @@ struct IdwtLevelArgs {
     int      h16;         // reversible: ll / mallat / out hold int16; a synthesised value that does not fit sets bit 3 of *status
     int      pk;          // h16 and every coefficient within +-kPkDecodeBound (pk16.h): arithmetic on packed int16 pairs
     unsigned int* status;
+    // the last level fused with K7 under a pixel layout other than the default (grk_amd_set_decode_pixel_layout; as DwtLevelArgs):
+    // sample (x, y) of component k of tile t of the window goes to pixels + t * px_tile + y * px_row + k * px_kstep + x * px_xstep
+    // (bytes); interleaved pixels with more samples in memory than components: the others receive px_fill
+    uint32_t px_lay, px_chan, px_xstep, px_fill;
+    uint64_t px_row, px_kstep, px_tile;
 };
 hipError_t launch_idwt_level(const IdwtLevelArgs& a, hipStream_t s);
 hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, uint32_t ntiles, uint32_t ncomp, hipStream_t s);
@@ -221,13 +234,15 @@ uint32_t   idwt_level_strip_pairs(const IdwtLevelArgs& a);   // coefficient pair
 // ---- K7: inverse colour transform + DC shift + clamp + store as pixels (kernels_idwt.hip) --------
 struct EgressArgs {
     const int32_t* planes;   // [tile][comp] planes (float bit patterns when irreversible)
-    void*    pixels;         // tiles back to back, component-major planar, tight
+    void*    pixels;         // tiles back to back, component-major planar, tight -- or as px_lay .. px_tile say
     uint32_t w, h, stride;
     uint64_t pitch;
     uint32_t ncomp, ntiles;
     uint32_t bytes_per_sample;   // 1, 2 or 4 (int32 out)
     int32_t  dc, lo, hi;
     int      mct, irreversible;
+    uint32_t px_lay, px_chan, px_xstep, px_fill;       // a layout other than the default (as IdwtLevelArgs)
+    uint64_t px_row, px_kstep, px_tile;
 };
 hipError_t launch_egress(const EgressArgs& a, hipStream_t s);
 
@@ -281,6 +296,8 @@ struct PlaceArgs {
     uint32_t ntiles, w, h, ncomp, bps;
     const uint32_t* rects;                           // [tile]: x, y of the tile in the image's planes (checked by the host)
     uint8_t* image; uint32_t img_w, img_h;           // ncomp planes of img_h x img_w samples
+    uint64_t img_row, img_plane;                     // bytes between the image's rows / planes (0: tight).  Interleaved pixels are
+                                                     // placed as ONE component of samples as wide as a pixel
 };
 hipError_t launch_t2dec_place(const PlaceArgs& a, hipStream_t s);
 // *into |= *from (assign: = ) on the stream: a group's decode status into the image's

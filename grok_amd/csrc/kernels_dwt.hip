@@ -132,9 +132,13 @@ __device__ __forceinline__ void h97(const float* w, float& s, float& d, float in
 //   every strip takes a FAST path -- without the general path in the kernel the three-component 9/7 level 0 needs 83 registers
 //   instead of 124 (the 5/3 one 84 instead of 99): five waves per SIMD, and room on a SIMD whose other waves are the block
 //   coder's ROOM instance (kernels_ht.hip) -- the pairing that cfg3's pipeline lacked.
-template <bool F97, int NC, int PX, bool H16 = false, bool GEN = true>
+// STR (PX != 0): the caller's pixels in a layout other than the default (DwtLevelArgs::px_lay: pitched planar, pixel-interleaved) --
+//   every sample is fetched from its own address and a FAST lane packs its pair itself, so that everything behind the load is the
+//   default layout's instruction sequence; the default layout's instances are the ones without it.
+template <bool F97, int NC, int PX, bool H16 = false, bool GEN = true, bool STR = false>
 __global__ __launch_bounds__(kThreads) void dwt_level_kernel(DwtLevelArgs a)
 {
+    static_assert(!STR || PX != 0, "a pixel layout belongs to the level that reads pixels");
     static_assert(!(F97 && H16), "16-bit planes are for the reversible transform");
     // The DWT chain is the critical path of pipelined encodes (its launches run beside K3 of this and of the previous
     // frame, whose waves have slack): its waves take the issue arbiter's top priority.  Measured 0.622 -> 0.603 ms/frame.
@@ -186,6 +190,8 @@ __global__ __launch_bounds__(kThreads) void dwt_level_kernel(DwtLevelArgs a)
     const size_t comp_px = (size_t)cw * ch;
     const PIX* pix = reinterpret_cast<const PIX*>(a.pixels) + (size_t)plane0 * comp_px;
     const bool pvec = vec && (cw & 1u) == 0;          // tightly packed rows: pairs aligned only for even widths
+    const uint8_t* spix = nullptr;                    // STR: component 0 of this workgroup, row 0, column 0
+    if constexpr (STR) spix = reinterpret_cast<const uint8_t*>(a.pixels) + (size_t)(bz / a.zdiv) * a.px_tile + (size_t)(a.comp0 + bz % a.zdiv) * a.px_kstep;
 
     const int32_t J0 = (int32_t)(by * a.seg_pairs);
     const int32_t J1 = min((int32_t)vpairs, J0 + (int32_t)a.seg_pairs);
@@ -221,6 +227,13 @@ __global__ __launch_bounds__(kThreads) void dwt_level_kernel(DwtLevelArgs a)
             } else {
     #pragma unroll
                 for (int k = 0; k < NC; ++k) {
+                    if constexpr (STR) {
+                        const uint8_t* srow = spix + (size_t)k * a.px_kstep + (size_t)rr * a.px_row;
+                        auto at = [&](uint32_t x) { return (int32_t)*reinterpret_cast<const PIX*>(srow + (size_t)x * a.px_xstep); };
+                        if (FAST) q.a[k] = at(lane_col) | (int32_t)((uint32_t)at(lane_col + 1u) << (PX == 1 ? 8 : 16));
+                        else { q.a[k] = at(mA); q.b[k] = at(mB); }
+                        continue;
+                    }
                     const PIX* row = pix + (size_t)k * comp_px + (size_t)rr * cw;
                     if (FAST) {       // the pair stays packed in one register until convert(): a load whose result is
                                       // unpacked at once is waited for at once, and the prefetch buys nothing
@@ -455,10 +468,15 @@ __host__ __device__ inline uint32_t pk_strip_cols(uint32_t cw, uint32_t nt)
     return min(most, ((cw + n - 1) / n + 63u) & ~63u);
 }
 
-template <int NC, int PX, int NT>
+// CH (PX = 1): 0 = the default pixel layout, component planes; 1, 3, 4 = pixel-interleaved with CH samples per pixel in memory
+//   (DwtLevelArgs::px_lay = 2).  A lane's four columns are then 4 CH contiguous bytes: ONE load of CH dwords per row for all NC
+//   components, where the planar form issues NC loads of one dword, and v_perm selectors that pick a component's bytes out of them
+//   (mirrored groups: one more v_perm per pair, which swaps and reverses the two pairs).  Rows lie px_row bytes apart, tiles px_tile.
+template <int NC, int PX, int NT, int CH = 0>
 __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
 {
     static_assert(PX == 0 || PX == 1, "int16 planes or 8-bit pixels");
+    static_assert(CH == 0 || (PX == 1 && (CH == 1 || CH == 3 || CH == 4) && NC <= CH), "interleaved 8-bit pixels of 1, 3 or 4 channels");
     static_assert(PX != 0 || NC == 1, "plane input is one component per workgroup");
     __builtin_amdgcn_s_setprio(3);                         // (as dwt_level_kernel: the DWT chain is the critical path)
     constexpr int kPkCols = NT * kPkLaneCols;                // columns staged per line
@@ -498,16 +516,23 @@ __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
     const bool rev = c0 < 0 || c0 >= (int32_t)cw;
     int32_t lo = c0 < 0 ? -c0 - 3 : (c0 >= (int32_t)cw ? 2 * ((int32_t)cw - 1) - c0 - 3 : c0);
     lo = max(0, min(lo, (int32_t)cw - kPkLaneCols));
-    const uint32_t lane_off = (uint32_t)lo * (PX == 0 ? 2u : 1u);          // bytes into a row
+    const uint32_t lane_off = (uint32_t)lo * (PX == 0 ? 2u : (CH ? (uint32_t)CH : 1u));          // bytes into a row
     // v_perm selectors that unpack a load into the pairs (A: columns 0, 1; B: columns 2, 3), reversed for mirrored groups
     const uint32_t selA = PX == 1 ? (rev ? 0x0c020c03u : 0x0c010c00u) : (rev ? 0x05040706u : 0x03020100u);
     const uint32_t selB = PX == 1 ? (rev ? 0x0c000c01u : 0x0c030c02u) : (rev ? 0x01000302u : 0x07060504u);
     const pk16 dc2 = as_pk((uint32_t)a.dc * 0x10001u);       // (unsigned pixels: the launcher sends signed ones elsewhere)
+    // CH = 3 / 4: sample c of column j is byte CH j + c of the load.  Pair A (columns 0, 1) lies in dwords 0 and 1, pair B (columns 2, 3)
+    // in the last two, whichever component: one selector each over (w1 : w0) and (w[CH-1] : w[CH-2]), plus 0x00010001 per component;
+    // then, for a mirrored group, A = B with its halves swapped and B = A likewise
+    const uint32_t csel = (CH > 1 ? (a.comp0 + bz % a.zdiv) : 0u) * 0x00010001u;
+    const uint32_t ilA = (CH == 3 ? 0x0c030c00u : 0x0c040c00u) + csel, ilB = (CH == 3 ? 0x0c050c02u : 0x0c040c00u) + csel;
+    const uint32_t rotA = rev ? 0x01000302u : 0x07060504u, rotB = rev ? 0x05040706u : 0x03020100u;
 
     __amdgpu_buffer_rsrc_t r_in[NC], r_ll[NC], r_mp[NC];
     #pragma unroll
     for (int k = 0; k < NC; ++k) {
-        r_in[k] = PX == 0 ? buffer_from(in) : buffer_from(pix + (size_t)k * comp_px);
+        if constexpr (CH != 0) r_in[k] = buffer_from(reinterpret_cast<const uint8_t*>(a.pixels) + (size_t)(bz / a.zdiv) * a.px_tile);
+        else r_in[k] = PX == 0 ? buffer_from(in) : buffer_from(pix + (size_t)k * comp_px);
         r_ll[k] = buffer_from(ll + (size_t)k * a.ll_pitch);
         r_mp[k] = buffer_from(mp + (size_t)k * a.m_pitch);
 
@@ -517,10 +542,18 @@ __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
     const int32_t J0 = (int32_t)(by * a.seg_pairs);
     const int32_t J1 = min((int32_t)sh, J0 + (int32_t)a.seg_pairs);
 
-    struct Raw { uint32_t v[NC]; uint2 w[NC]; };
+    struct Raw { uint32_t v[CH > NC ? CH : NC]; uint2 w[NC]; };
     auto fetch_row = [&](int32_t r, Raw& q) {                // raw row fetch: no arithmetic, so that the rows stay in flight
         const uint32_t rr = mirror_row<true>(r, ch);
-        if constexpr (PX == 0) {
+        if constexpr (CH == 1) {
+            q.v[0] = __builtin_amdgcn_raw_buffer_load_b32(r_in[0], lane_off, rr * (uint32_t)a.px_row, kPkLoadAux);
+        } else if constexpr (CH == 3) {
+            const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(r_in[0], lane_off, rr * (uint32_t)a.px_row, kPkLoadAux);
+            q.v[0] = v.x; q.v[1] = v.y; q.v[2] = v.z;
+        } else if constexpr (CH == 4) {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r_in[0], lane_off, rr * (uint32_t)a.px_row, kPkLoadAux);
+            q.v[0] = v.x; q.v[1] = v.y; q.v[2] = v.z; q.v[3] = v.w;
+        } else if constexpr (PX == 0) {
             const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r_in[0], lane_off, rr * a.in_stride * 2u, kPkLoadAux);
             q.w[0].x = v.x; q.w[0].y = v.y;
         } else {
@@ -536,8 +569,15 @@ __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
             pk16 xa[NC], xb[NC];
     #pragma unroll
             for (int k = 0; k < NC; ++k) {
-                xa[k] = as_pk(__builtin_amdgcn_perm(0u, q.v[k], selA));
-                xb[k] = as_pk(__builtin_amdgcn_perm(0u, q.v[k], selB));
+                if constexpr (CH > 1) {
+                    const uint32_t fa = __builtin_amdgcn_perm(q.v[1], q.v[0], ilA + (uint32_t)k * 0x00010001u);
+                    const uint32_t fb = __builtin_amdgcn_perm(q.v[CH - 1], q.v[CH - 2], ilB + (uint32_t)k * 0x00010001u);
+                    xa[k] = as_pk(__builtin_amdgcn_perm(fa, fb, rotA));
+                    xb[k] = as_pk(__builtin_amdgcn_perm(fa, fb, rotB));
+                } else {
+                    xa[k] = as_pk(__builtin_amdgcn_perm(0u, q.v[k], selA));
+                    xb[k] = as_pk(__builtin_amdgcn_perm(0u, q.v[k], selB));
+                }
             }
             if constexpr (NC == 3) {   // RCT (mct.cpp:94-104) after the DC shift: Cb = B - G and Cr = R - G lose the shift,
                                        // Y = (R + 2G + B) >> 2 = G + ((Cb + Cr) >> 2) exactly, minus the shift
@@ -657,8 +697,11 @@ static bool dwt_level_is_pk(const DwtLevelArgs& a)
 {
     // (row offsets are 32-bit byte offsets from a plane's first sample: planes of 2^31 samples and more keep the flat addressing)
     const bool near = (uint64_t)a.m_stride * a.ch < (1ull << 31) && (uint64_t)a.cw * a.ch < (1ull << 31) && (uint64_t)a.in_stride * a.ch < (1ull << 31);
+    // the caller's pixels: planes of the default layout, or interleaved with 1, 3 or 4 samples per pixel (rows at their real pitch);
+    // planar pitches and two-channel pixels go through dwt_level_kernel's strided front end
+    const bool lay = a.px_lay == 0 || (a.px_lay == 2 && (a.px_chan == 1 || a.px_chan == 3 || a.px_chan == 4) && a.px_row * a.ch < (1ull << 31));
     return a.h16 && a.pk && !a.irreversible && (a.px | a.py) == 0 && (a.cw & 3u) == 0 && a.cw >= 256u &&
-           a.ch >= 16 && (a.ch & 1u) == 0 && near;
+           a.ch >= 16 && (a.ch & 1u) == 0 && near && lay;
 }
 // 256 lanes for wide levels (8K level 0: 127 us against 138 with 128 lanes), 128 for narrow ones, whose strips would leave half of
 // 256 lanes idle (64 tiles of 1024^2: levels 0-2 238 -> 203 us)
@@ -702,6 +745,31 @@ hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint
 #define GRK_L0(F97, NC, PX) do { if (all_fast) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, false, false>), grid, block, 0, s, a); \
                                  else hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX>), grid, block, 0, s, a); } while (0)
         const int px = a.px_bytes == 1 ? 1 : 2;
+        if (a.px_lay != 0) {               // a layout of the caller's: the interleaved packed instances, else the strided front end
+            if (!a.irreversible && px == 1 && dwt_level_is_pk(a)) {
+                const uint32_t sc = pk_strip_cols(a.cw, pk_nt(a));
+                grid.x = (a.cw + sc - 1) / sc;
+#define GRK_PKI(NC, CH) do { if (pk_nt(a) == 128) hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 128, CH>), grid, dim3(128), 0, s, a); \
+                             else hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 256, CH>), grid, block, 0, s, a); } while (0)
+                if (a.px_chan == 1) GRK_PKI(1, 1);
+                else if (a.px_chan == 3) { if (nc == 3) GRK_PKI(3, 3); else GRK_PKI(1, 3); }
+                else                     { if (nc == 3) GRK_PKI(3, 4); else GRK_PKI(1, 4); }
+#undef GRK_PKI
+                return;
+            }
+#define GRK_L0S(F97, NC, PX, H16) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, H16, true, true>), grid, block, 0, s, a)
+            if (a.irreversible) {
+                if (nc == 3) { if (px == 1) GRK_L0S(true, 3, 1, false); else GRK_L0S(true, 3, 2, false); }
+                else         { if (px == 1) GRK_L0S(true, 1, 1, false); else GRK_L0S(true, 1, 2, false); }
+            } else if (a.h16 && px == 1) {
+                if (nc == 3) GRK_L0S(false, 3, 1, true); else GRK_L0S(false, 1, 1, true);
+            } else {
+                if (nc == 3) { if (px == 1) GRK_L0S(false, 3, 1, false); else GRK_L0S(false, 3, 2, false); }
+                else         { if (px == 1) GRK_L0S(false, 1, 1, false); else GRK_L0S(false, 1, 2, false); }
+            }
+#undef GRK_L0S
+            return;
+        }
         if (a.irreversible) {
             if (nc == 3) { if (px == 1) GRK_L0(true, 3, 1); else GRK_L0(true, 3, 2); }
             else         { if (px == 1) GRK_L0(true, 1, 1); else GRK_L0(true, 1, 2); }

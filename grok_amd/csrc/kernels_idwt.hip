@@ -138,9 +138,14 @@ __device__ __forceinline__ void egress_px(int32_t (&c)[NC], bool irrev, bool mct
 //   as out of range instead of returning other pixels.  "Fit" is the packed kernels' input range when the chain runs its
 //   larger levels packed (a.pk, set for the whole chain: a level too small or too odd for idwt53_pk_kernel comes here and
 //   may feed a packed one -- ADVICE r2).
-template <bool F97, int NC, int PXO, bool H16 = false>
+// STR (PXO != 0): the pixels leave in a layout other than the default (IdwtLevelArgs::px_lay: pitched planar, pixel-interleaved):
+//   every sample to its own address -- or, for the 8-bit MCT triple into four-channel pixels on 4-byte alignment, one dword per
+//   pixel (R, G, B, fill); the workgroup of a tile's first component also writes the fill of the channels no component owns.
+//   The default layout's instances are the ones without it.
+template <bool F97, int NC, int PXO, bool H16 = false, bool STR = false>
 __global__ __launch_bounds__(kThreads) void idwt_level_kernel(IdwtLevelArgs a)
 {
+    static_assert(!STR || PXO != 0, "a pixel layout belongs to the level that writes pixels");
     static_assert(!(F97 && H16), "16-bit planes are for the reversible transform");
     using T  = typename std::conditional<F97, float, int32_t>::type;
     using PT = typename std::conditional<H16, int16_t, T>::type;             // element type of the planes in memory
@@ -179,6 +184,16 @@ __global__ __launch_bounds__(kThreads) void idwt_level_kernel(IdwtLevelArgs a)
     const uint32_t win_w = a.wx1 - a.wx0;
     const size_t comp_px = (size_t)win_w * (a.wy1 - a.wy0);
     PIX* pix = reinterpret_cast<PIX*>(a.pixels) + (size_t)plane0 * comp_px;
+    uint8_t* spix = nullptr;                          // STR: component 0 of this workgroup, row 0, column 0 of the window
+    uint32_t fill0 = 0, fill1 = 0;                    // STR: the channels [fill0, fill1) are this workgroup's to fill
+    bool quad = false;                                // STR: whole four-channel pixels as dwords
+    if constexpr (STR) {
+        const uint32_t comp = a.comp0 + bz % a.zdiv;
+        uint8_t* tile = reinterpret_cast<uint8_t*>(a.pixels) + (size_t)(bz / a.zdiv) * a.px_tile;
+        spix = tile + (size_t)comp * a.px_kstep;
+        if (a.px_lay == 2 && comp == 0) { fill0 = a.ncomp; fill1 = a.px_chan; }
+        quad = NC == 3 && PXO == 1 && a.px_lay == 2 && a.px_chan == 4 && (((uintptr_t)tile | a.px_row) & 3u) == 0;
+    }
 
     // The pair this lane loads and (lanes [0, kOutPairs)) synthesises: the strip's own pairs in lane order, so that a
     // wave's loads and stores start on cache-line boundaries; the next 2 * kHaloPairs lanes fetch the halo pairs left
@@ -249,6 +264,31 @@ __global__ __launch_bounds__(kThreads) void idwt_level_kernel(IdwtLevelArgs a)
             }
             egress_px<NC>(cA, F97, a.mct != 0, a.dc, a.lo, a.hi);
             egress_px<NC>(cB, F97, a.mct != 0, a.dc, a.lo, a.hi);
+            if constexpr (STR) {
+                if (!FAST && ((uint32_t)r < a.wy0 || (uint32_t)r >= a.wy1)) return;
+                uint8_t* row = spix + (size_t)(FAST ? (uint32_t)r : (uint32_t)r - a.wy0) * a.px_row
+                                    + (ptrdiff_t)(FAST ? cE : cE - (int32_t)a.wx0) * (ptrdiff_t)a.px_xstep;
+                const bool we = st_e && in_e, wo = st_o && in_o;
+                if (quad) {
+                    constexpr int K1 = NC >= 3 ? 1 : 0, K2 = NC >= 3 ? 2 : 0;
+                    const uint32_t f = a.px_fill << 24;
+                    if (we) *reinterpret_cast<uint32_t*>(row) = ((uint32_t)cA[0] & 255u) | (((uint32_t)cA[K1] & 255u) << 8) | (((uint32_t)cA[K2] & 255u) << 16) | f;
+                    if (wo) *reinterpret_cast<uint32_t*>(row + 4) = ((uint32_t)cB[0] & 255u) | (((uint32_t)cB[K1] & 255u) << 8) | (((uint32_t)cB[K2] & 255u) << 16) | f;
+                    return;
+                }
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    PIX* p = reinterpret_cast<PIX*>(row + (size_t)k * a.px_kstep);
+                    if (we) p[0] = (PIX)cA[k];
+                    if (wo) *reinterpret_cast<PIX*>(reinterpret_cast<uint8_t*>(p) + a.px_xstep) = (PIX)cB[k];
+                }
+                for (uint32_t k = fill0; k < fill1; ++k) {
+                    PIX* p = reinterpret_cast<PIX*>(row + (size_t)k * sizeof(PIX));      // (interleaved, spix at channel 0)
+                    if (we) p[0] = (PIX)a.px_fill;
+                    if (wo) *reinterpret_cast<PIX*>(reinterpret_cast<uint8_t*>(p) + a.px_xstep) = (PIX)a.px_fill;
+                }
+                return;
+            }
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
                 if (!FAST && ((uint32_t)r < a.wy0 || (uint32_t)r >= a.wy1)) continue;
@@ -373,10 +413,15 @@ __host__ __device__ inline uint32_t ipk_strip_cols(uint32_t cw)
 }
 
 #define IPK_FENCE __builtin_amdgcn_sched_barrier(0)
-template <int NC, int PXO>
+// CH (PXO = 1): 0 = the default pixel layout, component planes; 1 = one-channel pixels at the caller's pitches; 3, 4 = the MCT triple
+//   into interleaved pixels of CH samples (IdwtLevelArgs::px_lay = 2): a lane's four columns leave as ONE store of CH dwords, put
+//   together with v_perm -- four-channel pixels with px_fill in the fourth sample (a fourth component's own launch, which
+//   follows, overwrites it).  The launcher vouches for 4-byte alignment of tiles and rows.
+template <int NC, int PXO, int CH = 0>
 __global__ __launch_bounds__(kThreads) void idwt53_pk_kernel(IdwtLevelArgs a)
 {
     static_assert(PXO == 0 || PXO == 1, "int16 planes or 8-bit pixels");
+    static_assert(CH == 0 || (PXO == 1 && ((CH == 1 && NC == 1) || ((CH == 3 || CH == 4) && NC == 3))), "interleaved 8-bit pixels: mono, or the triple");
     static_assert(PXO != 0 || NC == 1, "plane output is one component per workgroup");
     // [parity][comp][pair][S, D]: S = LL | LH << 16, D = HL | HH << 16
     __shared__ __attribute__((aligned(16))) uint32_t line[2][NC][kPkPairs * 2];
@@ -424,7 +469,8 @@ __global__ __launch_bounds__(kThreads) void idwt53_pk_kernel(IdwtLevelArgs a)
     for (int k = 0; k < NC; ++k) {
         r_ll[k] = buffer_from(ll + (size_t)k * a.ll_pitch);
         r_mp[k] = buffer_from(mp + (size_t)k * a.m_pitch);
-        r_out[k] = PXO == 0 ? buffer_from(out) : buffer_from(pix + (size_t)k * comp_px);
+        if constexpr (CH != 0) r_out[k] = buffer_from(reinterpret_cast<uint8_t*>(a.pixels) + (size_t)(bz / a.zdiv) * a.px_tile);
+        else r_out[k] = PXO == 0 ? buffer_from(out) : buffer_from(pix + (size_t)k * comp_px);
     }
     __amdgpu_buffer_rsrc_t r_none = buffer_from(a.mallat, true);
 
@@ -451,7 +497,7 @@ __global__ __launch_bounds__(kThreads) void idwt53_pk_kernel(IdwtLevelArgs a)
     const uint32_t nv = min(slanes, (cw - bx * scols + 3u) >> 2);
     const uint32_t tp = min(t, nv - 1u);
     const uint32_t hp = (tp + 1u) * kPkLanePairs;            // its first pair in the staged line
-    const uint32_t oc = (bx * scols + tp * 4u) * (PXO == 0 ? 2u : 1u);      // byte offset of its four samples in an output row
+    const uint32_t oc = (bx * scols + tp * 4u) * (PXO == 0 ? 2u : (CH ? (uint32_t)CH : 1u));      // byte offset of its four samples in an output row
 
     IV53pk colA[NC], colB[NC];
     #pragma unroll
@@ -510,18 +556,39 @@ __global__ __launch_bounds__(kThreads) void idwt53_pk_kernel(IdwtLevelArgs a)
                 cB[0] = vB[2] + gB; cB[1] = gB; cB[2] = vB[1] + gB;
             } else { cA[0] = vA[0]; cB[0] = vB[0]; }
             const pk16 dc2 = as_pk((uint32_t)a.dc * 0x10001u);
+            uint32_t four[NC];                               // a component's four columns, a byte each
     #pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                const uint32_t four = __builtin_amdgcn_perm(sat_pk_u8(cB[k] + dc2), sat_pk_u8(cA[k] + dc2), kSelLoLo);
-                __builtin_amdgcn_raw_buffer_store_b32(four, r_out[k], voff, ru * cw, 0);
+            for (int k = 0; k < NC; ++k) four[k] = __builtin_amdgcn_perm(sat_pk_u8(cB[k] + dc2), sat_pk_u8(cA[k] + dc2), kSelLoLo);
+            if constexpr (CH == 3) {                         // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3 (selectors over G : R, then B : that)
+                constexpr int K1 = NC >= 3 ? 1 : 0, K2 = NC >= 3 ? 2 : 0;
+                u32x3 w;
+                w.x = __builtin_amdgcn_perm(four[K2], __builtin_amdgcn_perm(four[K1], four[0], 0x01000400u), 0x03040100u);
+                w.y = __builtin_amdgcn_perm(four[K2], __builtin_amdgcn_perm(four[K1], four[0], 0x06020005u), 0x03020500u);
+                w.z = __builtin_amdgcn_perm(four[K2], __builtin_amdgcn_perm(four[K1], four[0], 0x00070300u), 0x07020106u);
+                __builtin_amdgcn_raw_buffer_store_b96(w, r_out[0], voff, ru * (uint32_t)a.px_row, 0);
+            } else if constexpr (CH == 4) {                  // R G B F per pixel: (R, G) and (B, F) of two pixels side by side first
+                constexpr int K1 = NC >= 3 ? 1 : 0, K2 = NC >= 3 ? 2 : 0;
+                const uint32_t rg01 = __builtin_amdgcn_perm(four[K1], four[0], 0x05010400u), rg23 = __builtin_amdgcn_perm(four[K1], four[0], 0x07030602u);
+                const uint32_t bf01 = __builtin_amdgcn_perm(a.px_fill, four[K2], 0x04010400u), bf23 = __builtin_amdgcn_perm(a.px_fill, four[K2], 0x04030402u);
+                u32x4 w;
+                w.x = __builtin_amdgcn_perm(bf01, rg01, kSelLoLo); w.y = __builtin_amdgcn_perm(bf01, rg01, kSelHiHi);
+                w.z = __builtin_amdgcn_perm(bf23, rg23, kSelLoLo); w.w = __builtin_amdgcn_perm(bf23, rg23, kSelHiHi);
+                __builtin_amdgcn_raw_buffer_store_b128(w, r_out[0], voff, ru * (uint32_t)a.px_row, 0);
+            } else if constexpr (CH == 1) {
+                __builtin_amdgcn_raw_buffer_store_b32(four[0], r_out[0], voff, ru * (uint32_t)a.px_row, 0);
+            } else {
+    #pragma unroll
+                for (int k = 0; k < NC; ++k) __builtin_amdgcn_raw_buffer_store_b32(four[k], r_out[k], voff, ru * cw, 0);
             }
         }
     };
-    constexpr int kStores = PXO == 0 ? 2 : 2 * NC;           // memory stores per step
+    constexpr int kStores = (PXO == 0 || CH != 0) ? 2 : 2 * NC;           // memory stores per step
     auto no_stores = [&]() {
     #pragma unroll
         for (int k = 0; k < kStores; ++k) {
-            if constexpr (PXO == 0) __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, r_none, oc + 64 * k, 0, 0);
+            if constexpr (CH == 3) __builtin_amdgcn_raw_buffer_store_b96(u32x3{0u, 0u, 0u}, r_none, oc + 64 * k, 0, 0);
+            else if constexpr (CH == 4) __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, r_none, oc + 64 * k, 0, 0);
+            else if constexpr (PXO == 0) __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, r_none, oc + 64 * k, 0, 0);
             else __builtin_amdgcn_raw_buffer_store_b32(0u, r_none, oc + 64 * k, 0, 0);          // (apart, or they merge into wider ones)
         }
     };
@@ -575,7 +642,8 @@ __global__ __launch_bounds__(kThreads) void idwt53_pk_kernel(IdwtLevelArgs a)
 }
 
 // ---- K7 egress, stand-alone (stage entry point; pixel sizes the fused last level does not cover) ----------
-template <typename PIX, int NC>
+// STR: the pixels leave in a layout other than the default (EgressArgs::px_lay), every sample to its own address
+template <typename PIX, int NC, bool STR = false>
 __global__ __launch_bounds__(256) void egress_kernel(EgressArgs a)
 {
     const uint32_t x = (blockIdx.x * 256u + threadIdx.x) * 4u;
@@ -617,6 +685,16 @@ __global__ __launch_bounds__(256) void egress_kernel(EgressArgs a)
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k) c[k][i] = min(max(c[k][i] + a.dc, a.lo), a.hi);
+    }
+    if constexpr (STR) {
+        uint8_t* row = reinterpret_cast<uint8_t*>(a.pixels) + (size_t)tile * a.px_tile + (size_t)y * a.px_row + (size_t)x * a.px_xstep;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            for (uint32_t i = 0; i < n; ++i) *reinterpret_cast<PIX*>(row + (size_t)k * a.px_kstep + (size_t)i * a.px_xstep) = (PIX)c[k][i];
+        if (a.px_lay == 2)
+            for (uint32_t k = a.ncomp; k < a.px_chan; ++k)
+                for (uint32_t i = 0; i < n; ++i) *reinterpret_cast<PIX*>(row + (size_t)k * sizeof(PIX) + (size_t)i * a.px_xstep) = (PIX)a.px_fill;
+        return;
     }
     const bool vec = (n == 4) && ((a.w & 3u) == 0);
 #pragma unroll
@@ -678,9 +756,36 @@ hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, uint32_t ntiles, ui
         dim3 grid(a.nstrips ? a.nstrips : (sw + kOutPairs - 1) / kOutPairs, a.nsegs ? a.nsegs : (sh + a.seg_pairs - 1) / a.seg_pairs, ntiles * zdiv);
 #define GRK_I0(F97, NC, PX) hipLaunchKernelGGL((idwt_level_kernel<F97, NC, PX>), grid, block, 0, s, a)
         const int px = a.px_bytes == 1 ? 1 : 2;
-        if (a.irreversible) {
+        if (a.irreversible && a.px_lay != 0) {
+            if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<true, 3, 1, false, true>), grid, block, 0, s, a);
+                           else         hipLaunchKernelGGL((idwt_level_kernel<true, 3, 2, false, true>), grid, block, 0, s, a); }
+            else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<true, 1, 1, false, true>), grid, block, 0, s, a);
+                           else         hipLaunchKernelGGL((idwt_level_kernel<true, 1, 2, false, true>), grid, block, 0, s, a); }
+        } else if (a.irreversible) {
             if (nc == 3) { if (px == 1) GRK_I0(true, 3, 1); else GRK_I0(true, 3, 2); }
             else         { if (px == 1) GRK_I0(true, 1, 1); else GRK_I0(true, 1, 2); }
+        } else if (a.px_lay != 0) {
+            // a layout of the caller's.  The packed instances: one-channel pixels, or the MCT triple into three- / four-channel ones,
+            // tiles and rows on 4-byte alignment (whole dwords are stored), row offsets within 32 bits; the strided back end otherwise
+            const bool whole = a.wx0 == 0 && a.wy0 == 0 && a.wx1 == a.cw && a.wy1 == a.ch;
+            const bool al = (((uintptr_t)a.pixels | a.px_row | a.px_tile) & 3u) == 0 && a.px_row * a.ch < (1ull << 31);
+            const bool shape = a.px_lay == 2 && ((a.px_chan == 1 && nc == 1) || ((a.px_chan == 3 || a.px_chan == 4) && nc == 3 && a.mct));
+            if (px == 1 && idwt_level_is_pk(a) && a.lo == 0 && a.hi == 255 && whole && al && shape) {
+                grid.x = (a.cw + ipk_strip_cols(a.cw) - 1) / ipk_strip_cols(a.cw);
+                if (a.px_chan == 1)      hipLaunchKernelGGL((idwt53_pk_kernel<1, 1, 1>), grid, block, 0, s, a);
+                else if (a.px_chan == 3) hipLaunchKernelGGL((idwt53_pk_kernel<3, 1, 3>), grid, block, 0, s, a);
+                else                     hipLaunchKernelGGL((idwt53_pk_kernel<3, 1, 4>), grid, block, 0, s, a);
+            } else if (a.h16) {
+                if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 3, 1, true, true>), grid, block, 0, s, a);
+                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 3, 2, true, true>), grid, block, 0, s, a); }
+                else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 1, 1, true, true>), grid, block, 0, s, a);
+                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 1, 2, true, true>), grid, block, 0, s, a); }
+            } else {
+                if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 3, 1, false, true>), grid, block, 0, s, a);
+                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 3, 2, false, true>), grid, block, 0, s, a); }
+                else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 1, 1, false, true>), grid, block, 0, s, a);
+                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 1, 2, false, true>), grid, block, 0, s, a); }
+            }
         } else if (px == 1 && idwt_level_is_pk(a) && a.lo == 0 && a.hi == 255 && a.wx0 == 0 && a.wy0 == 0 && a.wx1 == a.cw && a.wy1 == a.ch &&
                    (nc == 1 || a.mct)) {
             grid.x = (a.cw + ipk_strip_cols(a.cw) - 1) / ipk_strip_cols(a.cw);
@@ -709,16 +814,18 @@ hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, uint32_t ntiles, ui
 hipError_t launch_egress(const EgressArgs& a, hipStream_t s)
 {
     dim3 grid((a.w + 1023) / 1024, a.h, a.ntiles), block(256);
-#define GRK_EGRESS(PIX)                                                                          \
+#define GRK_EGRESS(PIX, STR)                                                                     \
     switch (a.ncomp) {                                                                          \
-    case 1: hipLaunchKernelGGL((egress_kernel<PIX, 1>), grid, block, 0, s, a); break;           \
-    case 2: hipLaunchKernelGGL((egress_kernel<PIX, 2>), grid, block, 0, s, a); break;           \
-    case 3: hipLaunchKernelGGL((egress_kernel<PIX, 3>), grid, block, 0, s, a); break;           \
-    default: hipLaunchKernelGGL((egress_kernel<PIX, 4>), grid, block, 0, s, a); break;          \
+    case 1: hipLaunchKernelGGL((egress_kernel<PIX, 1, STR>), grid, block, 0, s, a); break;      \
+    case 2: hipLaunchKernelGGL((egress_kernel<PIX, 2, STR>), grid, block, 0, s, a); break;      \
+    case 3: hipLaunchKernelGGL((egress_kernel<PIX, 3, STR>), grid, block, 0, s, a); break;      \
+    default: hipLaunchKernelGGL((egress_kernel<PIX, 4, STR>), grid, block, 0, s, a); break;     \
     }
-    if (a.bytes_per_sample == 1) { GRK_EGRESS(uint8_t) }
-    else if (a.bytes_per_sample == 2) { GRK_EGRESS(uint16_t) }
-    else { GRK_EGRESS(int32_t) }
+    if (a.px_lay && a.bytes_per_sample == 1) { GRK_EGRESS(uint8_t, true) }
+    else if (a.px_lay && a.bytes_per_sample == 2) { GRK_EGRESS(uint16_t, true) }
+    else if (a.bytes_per_sample == 1) { GRK_EGRESS(uint8_t, false) }
+    else if (a.bytes_per_sample == 2) { GRK_EGRESS(uint16_t, false) }
+    else { GRK_EGRESS(int32_t, false) }
 #undef GRK_EGRESS
     return hipGetLastError();
 }

@@ -27,7 +27,9 @@ __device__ __forceinline__ void load4(const PIX* p, bool vec, uint32_t n, int32_
     }
 }
 
-template <typename PIX, int NC>
+// STR: the caller's pixels in a layout other than the default (IngestArgs::px_lay: pitched planar, pixel-interleaved) -- every sample
+// at its own address; the default layout's instances are the ones without it
+template <typename PIX, int NC, bool STR = false>
 __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a)
 {
     const uint32_t x = (blockIdx.x * 256u + threadIdx.x) * 4u;
@@ -46,7 +48,10 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a)
     int32_t c[NC][4];
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
-        load4<PIX>(src + (size_t)k * comp_px, vec, n, c[k]);
+        if constexpr (STR) {
+            const uint8_t* row = reinterpret_cast<const uint8_t*>(a.pixels) + (size_t)tile * a.px_tile + (size_t)y * a.px_row + (size_t)k * a.px_kstep;
+            for (uint32_t i = 0; i < 4; ++i) c[k][i] = i < n ? (int32_t)*reinterpret_cast<const PIX*>(row + (size_t)(x + i) * a.px_xstep) : 0;
+        } else load4<PIX>(src + (size_t)k * comp_px, vec, n, c[k]);
         for (int i = 0; i < 4; ++i) c[k][i] = ((c[k][i] ^ a.sext) - a.sext) - a.dc;     // sign-extend int8/int16, DC shift
     }
     if (NC >= 3 && a.mct) {
@@ -73,14 +78,15 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a)
 hipError_t launch_ingest(const IngestArgs& a, hipStream_t s)
 {
     dim3 grid((a.w + 1023) / 1024, a.h, a.ntiles), block(256);
-#define GRK_INGEST(PIX)                                                                          \
+#define GRK_INGEST(PIX, STR)                                                                     \
     switch (a.ncomp) {                                                                          \
-    case 1: hipLaunchKernelGGL((ingest_kernel<PIX, 1>), grid, block, 0, s, a); break;           \
-    case 2: hipLaunchKernelGGL((ingest_kernel<PIX, 2>), grid, block, 0, s, a); break;           \
-    case 3: hipLaunchKernelGGL((ingest_kernel<PIX, 3>), grid, block, 0, s, a); break;           \
-    default: hipLaunchKernelGGL((ingest_kernel<PIX, 4>), grid, block, 0, s, a); break;          \
+    case 1: hipLaunchKernelGGL((ingest_kernel<PIX, 1, STR>), grid, block, 0, s, a); break;      \
+    case 2: hipLaunchKernelGGL((ingest_kernel<PIX, 2, STR>), grid, block, 0, s, a); break;      \
+    case 3: hipLaunchKernelGGL((ingest_kernel<PIX, 3, STR>), grid, block, 0, s, a); break;      \
+    default: hipLaunchKernelGGL((ingest_kernel<PIX, 4, STR>), grid, block, 0, s, a); break;     \
     }
-    if (a.bytes_per_sample == 1) { GRK_INGEST(uint8_t) } else { GRK_INGEST(uint16_t) }
+    if (a.px_lay) { if (a.bytes_per_sample == 1) { GRK_INGEST(uint8_t, true) } else { GRK_INGEST(uint16_t, true) } }
+    else if (a.bytes_per_sample == 1) { GRK_INGEST(uint8_t, false) } else { GRK_INGEST(uint16_t, false) }
 #undef GRK_INGEST
     return hipGetLastError();
 }

@@ -23,9 +23,10 @@ constexpr uint32_t kPlaceRows = 16;         // rows of a tile-component per work
 __global__ __launch_bounds__(256) void t2dec_place_kernel(PlaceArgs a)
 {
     const uint32_t tile = blockIdx.z, comp = blockIdx.y, lane = threadIdx.x & 63u;
-    const uint64_t row_bytes = (uint64_t)a.w * a.bps, img_row = (uint64_t)a.img_w * a.bps;
+    const uint64_t row_bytes = (uint64_t)a.w * a.bps, img_row = a.img_row ? a.img_row : (uint64_t)a.img_w * a.bps;
+    const uint64_t img_plane = a.img_plane ? a.img_plane : (uint64_t)a.img_h * img_row;
     const uint8_t* const s = a.tiles + ((uint64_t)tile * a.ncomp + comp) * a.h * row_bytes;
-    uint8_t* const d = a.image + (uint64_t)comp * a.img_h * img_row + (uint64_t)a.rects[2 * tile + 1] * img_row + (uint64_t)a.rects[2 * tile] * a.bps;
+    uint8_t* const d = a.image + (uint64_t)comp * img_plane + (uint64_t)a.rects[2 * tile + 1] * img_row + (uint64_t)a.rects[2 * tile] * a.bps;
     const uint32_t y1 = min(a.h, (blockIdx.x + 1) * kPlaceRows);
     for (uint32_t y = blockIdx.x * kPlaceRows + (threadIdx.x >> 6); y < y1; y += 4)
         wave_copy(d + y * img_row, s + y * row_bytes, row_bytes, lane);

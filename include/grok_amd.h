@@ -131,7 +131,7 @@ uint64_t grk_amd_plane_elems(const grk_amd_tile_params* p);
 
 /* ---- whole hot path -------------------------------------------------------------------------
  * Encode `num_tiles` tiles of one geometry (grk_amd_same_tile_geometry; the batch is coded with *p) in one batch.  `pixels` holds the tiles back to back,
- * each tile component-major planar, row-major, tightly packed, ceil(prec/8) bytes per sample,
+ * each tile component-major planar, row-major, tightly packed (the default; grk_amd_set_pixel_layout below: interleaved, pitched), ceil(prec/8) bytes per sample,
  * host endian -- the layout grk_compress_tile() takes (TileProcessor.cpp:1177-1213).
  * pixels_on_device != 0: `pixels` is a device pointer (HBM-resident input, what bench.py times).  Lifetime of device pixels: they
  * are read in the order of the context's stream (grk_amd_set_stream) -- whatever the caller queues on that stream behind the call (the
@@ -144,6 +144,47 @@ uint64_t grk_amd_plane_elems(const grk_amd_tile_params* p);
 int grk_amd_encode_tiles(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
                          const void* pixels, int pixels_on_device,
                          grk_amd_coded_block* table, uint64_t* total_bytes);
+/* The layout of the pixels an encode reads (default: the one above).  Frames on a GPU are rarely component planes: a camera, a video
+ * decoder, an image loader and a channels-last tensor hold H x W x C interleaved samples, rows often carry a pitch and display paths a
+ * fourth, unused channel.  Level 0 of the forward transform reads the caller's pixels itself, so a layout is a property of its loads,
+ * not a pass of its own: no transposed copy of the frame is made.
+ *   interleaved  0: component-major planar (default).  1: pixel-interleaved, sample c of pixel x of a row at x * channels + c
+ *   channels     interleaved only: samples per pixel IN MEMORY, num_comps .. 4; 0 = num_comps.  Samples beyond num_comps are skipped
+ *                (RGBX, or RGB out of RGBA)
+ *   fill         decode, interleaved, channels > num_comps: the value the extra samples receive (opaque alpha); an encode does not read it
+ *   row_pitch    bytes between rows, 0 = tight; a multiple of the sample size, at least one tight row
+ *   plane_pitch  planar only: bytes between the component planes of a tile, 0 = tight (h * row pitch)
+ *   tile_pitch   bytes between the tiles of a batch, 0 = tight
+ * A layout does not change which values the pixels have: the coded blocks are those of the same samples in the default layout, bit
+ * for bit, and bytes in gaps and skipped channels are never interpreted.  The layout is context state (NULL = default); it cannot
+ * be checked before the tile parameters are known, so the calls that use it do that, with grk_amd_pixel_bytes: GRK_AMD_ERR_INVALID and
+ * the reason in grk_amd_last_error.  Honoured by grk_amd_encode_tiles (host pixels: the extent grk_amd_pixel_bytes gives goes up as one
+ * copy, gaps included; device pixels; pipelined or not), grk_amd_stage_ingest_mct and grk_amd_encode_image (`pixels` = the whole image
+ * in this layout, row_pitch the image's, tile_pitch unused).  grk_amd_encode_image_subsampled returns GRK_AMD_ERR_UNSUPPORTED while a
+ * layout other than the default is set.  The node API has contexts of its own and the Grok plugin is handed planar int32 by Grok:
+ * neither sees this setting.
+ * grk_amd_set_decode_pixel_layout: the same for the pixels a decode WRITES -- the last inverse level stores them itself, whole pixels
+ * at a time where the alignment allows.  Honoured by grk_amd_decode_tiles (also under grk_amd_set_decode_reduce and in a decode
+ * sequence, whose internal contexts inherit it), grk_amd_decode_region (pitches are the window's), grk_amd_stage_egress and
+ * grk_amd_decode_image (`pixels` = the whole image in this layout).  Bytes in a row gap, a plane gap or a tile gap are never
+ * written -- with host pixels the extent travels both ways for that; the extra samples of interleaved pixels are written with `fill`.
+ * Samples of more than 16 bits leave in the default layout only (GRK_AMD_ERR_UNSUPPORTED).
+ * Device pixels of 8-bit samples off 4-byte alignment take the separate ingest pass, as in the default layout. */
+typedef struct grk_amd_pixel_layout {
+    uint8_t  interleaved;
+    uint8_t  channels;
+    uint16_t fill;
+    uint32_t reserved;
+    uint64_t row_pitch;
+    uint64_t plane_pitch;
+    uint64_t tile_pitch;
+} grk_amd_pixel_layout;
+int grk_amd_set_pixel_layout(grk_amd_ctx* ctx, const grk_amd_pixel_layout* layout);
+int grk_amd_set_decode_pixel_layout(grk_amd_ctx* ctx, const grk_amd_pixel_layout* layout);
+/* Bytes a buffer of `num_tiles` tiles of w x h samples per component (0 = p->tile_w, p->tile_h) spans in `layout` (NULL = default), from
+ * its first sample to the end of its last (interleaved: of its last pixel, skipped channels included); host only.  0 for a layout that is invalid for these parameters: channels below num_comps
+ * or above 4, a pitch smaller than what it spans or no multiple of the sample size, plane_pitch together with interleaved. */
+uint64_t grk_amd_pixel_bytes(const grk_amd_tile_params* p, const grk_amd_pixel_layout* layout, uint32_t w, uint32_t h, uint32_t num_tiles);
 /* Pixel lifetime, relaxed (default off).  Pipelined encodes of small frames run a frame's whole chain on a stream of the context's own
  * (GRK_AMD_FRAME_STREAMS), so keeping the rule above costs a wait of the context's stream per call -- consecutive 512 x 512 frames:
  * 0.057 instead of 0.038 ms per call.  on != 0: the caller PROMISES not to touch a call's device pixels before a stream of its own has
@@ -227,7 +268,7 @@ int grk_amd_stage_ht_encode16(grk_amd_ctx* ctx, const grk_amd_tile_params* p, ui
  * `table` (host) has one row per code-block in the encoder's enumeration order with the block's
  * byte range inside `coded` and its missing_msbs -- exactly what the host's Tier-2 parser knows
  * after decompress_synch_plugin_with_host (plugin/plugin_bridge.cpp:63-76); length 0 = no data.
- * `pixels` receives the tiles back to back, component-major planar, tight, ceil(prec/8) bytes per
+ * `pixels` receives the tiles back to back, component-major planar, tight (or as grk_amd_set_decode_pixel_layout says), ceil(prec/8) bytes per
  * sample.  With pixels_on_device != 0 the call is asynchronous: query grk_amd_decode_status().
  * Returns GRK_AMD_ERR_INVALID for a block the reference decoder would reject. */
 int grk_amd_decode_tiles(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
@@ -272,7 +313,7 @@ int grk_amd_set_decode_planes16(grk_amd_ctx* ctx, int on);
 int grk_amd_plane_sample_bytes(grk_amd_ctx* ctx, const grk_amd_tile_params* p, int decode, uint32_t* packed_levels);
 /* Region (windowed) decode of ONE tile -- what grk_decompress_set_window() + grk_decompress() do on the host
  * (grok.h; partial synthesis: transform/WaveletReverse.cpp:1466-2213, tile/SparseBuffer.h): the pixels of the window
- * [x0, x1) x [y0, y1) of the tile, component-major planar, tight, (x1 - x0) * (y1 - y0) samples per component --
+ * [x0, x1) x [y0, y1) of the tile, component-major planar, tight (or as grk_amd_set_decode_pixel_layout says, pitches the window's), (x1 - x0) * (y1 - y0) samples per component --
  * bit-identical to the same crop of grk_amd_decode_tiles' output.  Only the code-blocks a sample of the window depends
  * on are entropy-decoded and only the strips / row segments of each DWT level that lead to it are synthesised, so
  * the cost follows the window, not the image.  table / coded describe the whole tile, as for grk_amd_decode_tiles.
@@ -454,7 +495,7 @@ int64_t grk_amd_write_codestream_layout(const grk_amd_image_layout* im, const gr
                                         uint8_t* out, uint64_t cap);
 int64_t grk_amd_write_main_header_layout(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
                                          const uint32_t* tile_part_bytes, uint8_t* out, uint64_t cap);
-/* Whole image -> codestream: `pixels` (host) is the image area, component-major planar, row-major, tight, ceil(prec/8)
+/* Whole image -> codestream: `pixels` (host) is the image area, component-major planar, row-major, tight (or as grk_amd_set_pixel_layout says), ceil(prec/8)
  * bytes per sample.  Tiles are grouped by geometry and every group is coded as one grk_amd_encode_tiles batch (one group
  * for an image at the origin whose tile size is a multiple of 2^levels x the code-block size); returns the length. */
 int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
@@ -559,7 +600,7 @@ int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stre
 /* why the calling thread's latest grk_amd_read_header / grk_amd_read_packets refused ("" after a success) */
 const char* grk_amd_reader_last_error(void);
 /* Codestream -> pixels (Route C, decode; CodeStreamDecompress::decompress, codestream/CodeStreamDecompress.cpp:450-519).
- * cs: the codestream, host memory.  pixels: the image area, component-major planar, tight, ceil(prec / 8) bytes per sample -- the
+ * cs: the codestream, host memory.  pixels: the image area, component-major planar, tight (or as grk_amd_set_decode_pixel_layout says; cap >= grk_amd_pixel_bytes of the image), ceil(prec / 8) bytes per sample -- the
  * layout grk_amd_encode_image takes; cap: its size in bytes.  pixels_on_device != 0: a device pointer, and the call is asynchronous
  * behind the reader (grk_amd_decode_status joins and reports).
  * The bytes are uploaded once while the host reads the packet headers; blocks of several pieces are gathered on the device; the

@@ -105,7 +105,7 @@ struct grk_amd_ctx {
     grk_amd_pixel_layout enc_layout{};                      // the pixels an encode reads (grk_amd_set_pixel_layout; all zero: the default)
     grk_amd_pixel_layout dec_layout{};                      // the pixels a decode writes (grk_amd_set_decode_pixel_layout)
     uint32_t dec_reduce = 0;                                // decode at 1 / 2^dec_reduce of the size (grk_amd_set_decode_reduce)
-    std::vector<uint32_t> red_seg_first;                    // ... the segment list of the blocks that decode keeps (decode_impl)
+    std::vector<uint32_t> red_seg_first;                    // ... the segment list of the blocks that decode keeps (decode_impl, decode.hip)
     std::vector<grk_amd_segment> red_segs;
     DevBuf dec_seg_dev;
     HtClass ht_classes[kHtMaxClasses]; uint32_t ht_num_classes = 0;   // block classes of K3: {top resolution, rest} x {LDS small, large}
@@ -158,9 +158,6 @@ struct grk_amd_ctx {
     bool last_h16 = false;           // the latest encode left int16 coefficients in the Mallat planes
     HostStage stage;                 // pinned chunks for pageable host buffers (copy_h2d)
     void* d2h_pin = nullptr; size_t d2h_cap = 0; std::vector<hipEvent_t> d2h_ev;   // copy_d2h: a staging area of the transfer's size, an event per piece
-    // A decode call's tables -- the code-block rows (a window's skipped blocks marked), behind them K5's scratch index and the list
-    // of blocks with data -- are put together in pinned memory the context owns and fetched by a kernel of the call's stream
-    // (launch_dec_upload); two sets in turn: the kernel of one call may still be queued when the next call fills its tables
     // Full decode with overlap on: K5b of the top resolution's blocks (3/4 of them) runs on the side stream beside K5b of the
     // other blocks and the inverse levels that need only those; the last inverse level waits for it
     hipEvent_t ev_dec_front = nullptr, ev_dec_top = nullptr;
@@ -187,10 +184,8 @@ struct grk_amd_ctx {
     hipStream_t probed_before[4] = {};   // main streams probed earlier: a host that alternates between a few streams is not probed at every switch
     int probe_replaced = 0;           // side streams replaced by the probe so far (grk_amd_stream_probe_result)
     bool probe_warm = false;          // the probe's kernels have been launched once (their first launch loads their code: not to be measured)
-    bool seq_vetted = false;          // (a sequence's internal context) its streams have been vetted against its neighbours' (vet_sequence_streams)
+    bool seq_vetted = false;          // (a sequence's internal context) its streams have been vetted against its neighbours' (vet_sequence_streams, decode_sequence.hip)
     unsigned long long* pend_alloc = nullptr; uint32_t pend_alloc_units = 0;   // K3's allocator reset handed to the fused level 0 (run_dwt)
-    // Part-1 decode: blocks of the default style go 64 to a wave (K8L, kernels_t1lanes.hip) unless much longer than the rest
-    // (GRK_AMD_T1_LANES=0: every block its own wave, K8 as in r01-r03; 2: lanes wherever they can be used; see run_t1_decode)
     // Decode of a SEQUENCE of frames (grk_amd_set_decode_pipelining): consecutive grk_amd_decode_tiles calls with device buffers
     // go in turn to this context and to `dec_kids` -- contexts of their own on the same device: own streams, tables, planes --,
     // each behind an event on the caller's stream.  A frame's serial block-decoding chains (K5a / K8) leave most of the machine
@@ -199,8 +194,14 @@ struct grk_amd_ctx {
     uint32_t dec_seq = 0;
     hipEvent_t ev_seq = nullptr;
     hipEvent_t ev_frame_done = nullptr;   // (an internal context of a sequence) behind the last frame it was given: grk_amd_decode_stream_wait_slot
-    int t1_lanes = 1;                    // 0: never, 1: where the cost model below says they are faster, 2: wherever they can (tests)
+    // Part-1 decode: blocks of the default style go 64 to a wave (K8L, kernels_t1lanes.hip) unless much longer than the rest
+    // (GRK_AMD_T1_LANES=0: every block its own wave, K8 as in r01-r03; 2: lanes wherever they can be used; see plan_t1_lists,
+    // decode_plan.cpp)
+    int t1_lanes = 1;                    // 0: never, 1: where the cost model there says they are faster, 2: wherever they can (tests)
     bool t1_pass_sync = true;            // K8L's waves hold blocks of equal bit-plane / pass counts and run pass by pass (GRK_AMD_T1_SYNC=0: free-running lanes)
+    // A decode call's tables -- the code-block rows (a window's skipped blocks marked), behind them the launch lists of the block
+    // decoders (decode_blocks.hip) -- are put together in pinned memory the context owns and fetched by a kernel of the call's stream
+    // (launch_dec_upload); two sets in turn: the kernel of one call may still be queued when the next call fills its tables
     struct DecUpload { char* p = nullptr; char* dp = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } dec_up[2];
     uint32_t dec_turn = 0;
     // grk_amd_decode_image: the uploaded codestream + appendix, a group's decoded tiles, the image (host pixels), the gather's
@@ -252,4 +253,76 @@ bool resolve_pixel_layout(const grk_amd_tile_params& p, const grk_amd_pixel_layo
                           PixelLayout& out, const char** why);
 bool planes16_ok(const grk_amd_tile_params& p);                                                                  // encode.hip
 bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l);                                                    // encode.hip
+
+// ---- steps the encode and decode units share ----
+// The first steps of a grk_amd_stage_* entry point: the side streams joined (where the stage reads what they write), the null
+// checks (args_ok: the stage's other arguments), a refusal the stage has for these parameters (refuse != nullptr), the device,
+// the geometry
+int stage_enter(grk_amd_ctx* c, const grk_amd_tile_params* p, bool args_ok, bool join, const char* refuse = nullptr);   // context.hip
+
+// an event made when it is first needed
+inline hipError_t ensure_event(hipEvent_t* ev) { return *ev ? hipSuccess : hipEventCreateWithFlags(ev, hipEventDisableTiming); }
+// what `later` gets from here on comes after what `earlier` holds now
+inline int order_behind(grk_amd_ctx* c, hipStream_t later, hipEvent_t ev, hipStream_t earlier, const char* what_record, const char* what_wait)
+{
+    HIP_TRY(c, hipEventRecord(ev, earlier), what_record);
+    HIP_TRY(c, hipStreamWaitEvent(later, ev, 0), what_wait);
+    return GRK_AMD_OK;
+}
+
+// DC shift, clamp range, the sign bit of a stored sample (signed samples, else 0) and the bytes a sample takes in the pixels
+struct SampleRange { int32_t dc, lo, hi, sext; uint32_t bytes; };
+inline SampleRange sample_range(const grk_amd_tile_params& p)
+{
+    SampleRange r;
+    r.bytes = (p.prec + 7u) / 8u;
+    r.dc = p.sgnd ? 0 : (1 << (p.prec - 1));
+    r.lo = p.sgnd ? -(1 << (p.prec - 1)) : 0;
+    r.hi = p.sgnd ? (1 << (p.prec - 1)) - 1 : (1 << p.prec) - 1;
+    r.sext = p.sgnd ? (1 << (8 * r.bytes - 1)) : 0;
+    return r;
+}
+
+// a resolved layout into a launcher's px_* fields: what a kernel that READS pixels takes (IngestArgs; DwtLevelArgs adds px_chan) ...
+template <class Args> inline void set_px_in(Args& a, const PixelLayout& px)
+{
+    a.px_lay = px.lay; a.px_xstep = px.xstep; a.px_row = px.row; a.px_kstep = px.kstep; a.px_tile = px.tile;
+}
+// ... and one that WRITES them (IdwtLevelArgs, EgressArgs)
+template <class Args> inline void set_px_out(Args& a, const PixelLayout& px)
+{
+    set_px_in(a, px); a.px_chan = px.channels; a.px_fill = px.fill;
+}
+
+// The LL ping-pong of a transform chain over the context's geometry, forward or inverse: LL_0 is the plane handed in or out,
+// LL_L lives in the Mallat plane, and between them llA holds LL1, LL3, ..., llB holds LL2, LL4, ...
+struct LLPlane { void* p; uint32_t stride; uint64_t pitch; };
+inline LLPlane ll_pingpong(const grk_amd_ctx* c, bool odd)
+{
+    const uint32_t w = c->geom.p.tile_w, hA = (c->geom.p.tile_h + 1) >> 1;
+    if (odd) return {c->llA.p, ll_stride_for(w), (uint64_t)ll_stride_for(w) * hA};
+    return {c->llB.p, ll_stride_for((w + 1) >> 1), (uint64_t)ll_stride_for((w + 1) >> 1) * ((hA + 1) >> 1)};
+}
+inline LLPlane ll_plane(const grk_amd_ctx* c, uint32_t l, void* plane0, void* mallat)
+{
+    const TileGeom& g = c->geom;
+    if (l == 0) return {plane0, g.stride, g.plane_elems};
+    if (l == g.p.num_levels) return {mallat, g.stride, g.plane_elems};
+    return ll_pingpong(c, (l & 1u) != 0);
+}
+// ... both buffers large enough for nplanes planes (before the first ll_plane: growing a buffer moves it)
+inline int ensure_ll(grk_amd_ctx* c, uint32_t nplanes)
+{
+    HIP_TRY(c, c->llA.ensure((size_t)nplanes * ll_pingpong(c, true).pitch * 4 + 256), "alloc LL ping");
+    HIP_TRY(c, c->llB.ensure((size_t)nplanes * ll_pingpong(c, false).pitch * 4 + 256), "alloc LL pong");
+    return GRK_AMD_OK;
+}
+
+// row pairs per workgroup of a DWT level: halved from 64 (to 8 at the least) while strips x row segments x z slots stay below min_wgs
+inline uint32_t row_segment_pairs(uint64_t strips, uint32_t row_pairs, uint32_t zslots, uint32_t min_wgs)
+{
+    uint32_t seg = 64;
+    while (seg > 8 && strips * ((row_pairs + seg - 1) / seg) * zslots < min_wgs) seg >>= 1;
+    return seg;
+}
 #pragma GCC visibility pop

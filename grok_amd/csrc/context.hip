@@ -300,6 +300,15 @@ int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t reduce)
     return GRK_AMD_OK;
 }
 
+int stage_enter(grk_amd_ctx* c, const grk_amd_tile_params* p, bool args_ok, bool join, const char* refuse)
+{
+    if (c && join) { const int jr = join_side(c); if (jr) return jr; }
+    if (!c || !p || !args_ok) return GRK_AMD_ERR_INVALID;
+    if (refuse) return fail(c, GRK_AMD_ERR_INVALID, refuse);
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    return ensure_geom(c, p);
+}
+
 // decode_only: one of a decode sequence's internal contexts (grk_amd_set_decode_pipelining) -- the call's stream and ONE side
 // stream, nothing else: the HIP runtime deals its (default 4) hardware queues to streams in the order they are made, and two
 // frames in flight then sit on four queues of their own whatever else the process has made before (a third stream per context

@@ -13,14 +13,14 @@ int encode_layout(grk_amd_ctx* c, uint32_t ntiles, PixelLayout& px)
 int run_ingest(grk_amd_ctx* c, uint32_t ntiles, const void* d_pixels, void* d_planes, const PixelLayout& px)
 {
     const TileGeom& g = c->geom;
+    const SampleRange r = sample_range(g.p);
     IngestArgs a{};
-    a.px_lay = px.lay; a.px_xstep = px.xstep; a.px_row = px.row; a.px_kstep = px.kstep; a.px_tile = px.tile;
+    set_px_in(a, px);
     a.pixels = d_pixels; a.planes = (int32_t*)d_planes;
     a.w = g.p.tile_w; a.h = g.p.tile_h; a.stride = g.stride; a.pitch = g.plane_elems;
     a.ncomp = g.p.num_comps; a.ntiles = ntiles;
-    a.bytes_per_sample = (g.p.prec + 7) / 8;
-    a.dc = g.p.sgnd ? 0 : (1 << (g.p.prec - 1));
-    a.sext = g.p.sgnd ? (1 << (8 * a.bytes_per_sample - 1)) : 0;
+    a.bytes_per_sample = r.bytes;
+    a.dc = r.dc; a.sext = r.sext;
     a.mct = g.p.mct; a.irreversible = g.p.irreversible;
     ScopedTimer t(c, 0);
     HIP_TRY(c, launch_ingest(a, c->stream), "launch ingest");
@@ -85,57 +85,45 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
 {
     const TileGeom& g = c->geom;
     const uint32_t L = g.p.num_levels;
-    const uint32_t W = g.p.tile_w, H = g.p.tile_h;
     if (L == 0) {
         HIP_TRY(c, hipMemcpyAsync(d_out, d_in, (size_t)nplanes * g.plane_elems * 4, hipMemcpyDeviceToDevice, c->stream), "copy planes");
         return GRK_AMD_OK;
     }
-    // LL ping-pong storage: A holds LL1, LL3, ...; B holds LL2, LL4, ...
-    const uint32_t sA = ll_stride_for(W), hA = (H + 1) >> 1;
-    const uint32_t sB = ll_stride_for((W + 1) >> 1), hB = (hA + 1) >> 1;
-    const uint64_t pitchA = (uint64_t)sA * hA, pitchB = (uint64_t)sB * hB;
-    HIP_TRY(c, c->llA.ensure((size_t)nplanes * pitchA * 4 + 256), "alloc LL ping");
-    HIP_TRY(c, c->llB.ensure((size_t)nplanes * pitchB * 4 + 256), "alloc LL pong");
+    { const int rc = ensure_ll(c, nplanes); if (rc) return rc; }     // (LL ping-pong storage, context.h: ll_plane)
     ScopedTimer t(c, 1);
     for (uint32_t l = 0; l < L; ++l) {
         DwtLevelArgs a{};
         a.cw = level_geom(g, l).w; a.ch = level_geom(g, l).h;
         a.px = level_geom(g, l).x0 & 1u; a.py = level_geom(g, l).y0 & 1u;
-        if (l == 0) { a.in = (const int32_t*)d_in; a.in_stride = g.stride; a.in_pitch = g.plane_elems; }
-        else if (l & 1) { a.in = (const int32_t*)c->llA.p; a.in_stride = sA; a.in_pitch = pitchA; }
-        else { a.in = (const int32_t*)c->llB.p; a.in_stride = sB; a.in_pitch = pitchB; }
+        const LLPlane from = ll_plane(c, l, d_in, d_out), to = ll_plane(c, l + 1, d_in, d_out);
+        a.in = (const int32_t*)from.p; a.in_stride = from.stride; a.in_pitch = from.pitch;
         a.mallat = (int32_t*)d_out; a.m_stride = g.stride; a.m_pitch = g.plane_elems;
-        if (l + 1 == L) { a.ll = (int32_t*)d_out; a.ll_stride = g.stride; a.ll_pitch = g.plane_elems; }
-        else if ((l + 1) & 1) { a.ll = (int32_t*)c->llA.p; a.ll_stride = sA; a.ll_pitch = pitchA; }
-        else { a.ll = (int32_t*)c->llB.p; a.ll_stride = sB; a.ll_pitch = pitchB; }
+        a.ll = (int32_t*)to.p; a.ll_stride = to.stride; a.ll_pitch = to.pitch;
         a.nplanes = nplanes;
         a.irreversible = g.p.irreversible;
         a.h16 = h16 ? 1 : 0;
         a.pk = h16 && c->dwt_pk && pk16_level_ok(g.p, l);
         a.xcd = c->dwt_xcd;
         if (l == 0 && d_pixels && px && px->lay) {     // (before the strips are counted: the layout decides between the level-0 kernels)
-            a.px_lay = px->lay; a.px_chan = px->channels; a.px_xstep = px->xstep; a.px_row = px->row; a.px_kstep = px->kstep; a.px_tile = px->tile;
+            set_px_in(a, *px); a.px_chan = px->channels;
         }
         // enough workgroups to cover the chip several times, few enough to amortise warm-up rows (profiles/r06_dwt_reads.txt: at 4096
         // the 8K level 0 ran 16-row segments and read 1.55 x its pixels; 2048 -> 32-row segments, 1.35 x, the DWT 1 % faster)
         const uint32_t sh = (a.ch + a.py + 1) >> 1;           // row pairs on the coordinate grid
-        uint32_t seg = 64;
         const uint64_t strips = (a.cw + a.px + dwt_level_strip_cols(a) - 1) / dwt_level_strip_cols(a);
         // workgroups along z: planes, or for the fused level 0 tiles (x components when there is no MCT triple)
         const uint32_t zslots = (l == 0 && d_pixels) ? ntiles * ((g.p.mct && g.p.num_comps >= 3) ? 1u : g.p.num_comps) : nplanes;
         // (... for the packed 5/3 kernel; the 32-bit kernels -- 448-column strips, twice the workgroups per row -- are better off with
         //  the finer cut: cfg3's 9/7 family 0.361 ms at 4096, 0.394 at 2048)
-        const uint32_t kMinWgs = a.pk ? 2048u : 4096u;
-        while (seg > 8 && strips * ((sh + seg - 1) / seg) * zslots < kMinWgs) seg >>= 1;
-        a.seg_pairs = seg;
+        a.seg_pairs = row_segment_pairs(strips, sh, zslots, a.pk ? 2048u : 4096u);
         if (a.cw == 0 || a.ch == 0) {
             // a level without samples (a narrow tile off the origin: [ceil(x0 / 2^l), ceil((x0 + w) / 2^l)) can be empty):
             // nothing to transform, and nothing deeper either
         } else if (l == 0 && d_pixels) {
-            a.pixels = d_pixels; a.px_bytes = (g.p.prec + 7) / 8;
+            const SampleRange r = sample_range(g.p);
+            a.pixels = d_pixels; a.px_bytes = r.bytes;
             a.alloc_reset = c->pend_alloc; a.alloc_chunk_units = c->pend_alloc_units; c->pend_alloc = nullptr;
-            a.dc = g.p.sgnd ? 0 : (1 << (g.p.prec - 1));
-            a.sext = g.p.sgnd ? (1 << (8 * a.px_bytes - 1)) : 0;
+            a.dc = r.dc; a.sext = r.sext;
             HIP_TRY(c, launch_dwt_level0_fused(a, ntiles, g.p.num_comps, g.p.mct, c->stream), "launch fused dwt level 0");
             if (c->want_px_event) HIP_TRY(c, hipEventRecord(c->ev_px, c->stream), "record the pixels' last read");
         } else {
@@ -233,9 +221,7 @@ bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l)
 extern "C" {
 int grk_amd_stage_ingest_mct(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_pixels, void* d_planes)
 {
-    if (!c || !p || !d_pixels || !d_planes) return GRK_AMD_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device), "set device");
-    int rc = ensure_geom(c, p); if (rc) return rc;
+    int rc = stage_enter(c, p, d_pixels && d_planes, false); if (rc) return rc;
     if (!ntiles) return GRK_AMD_ERR_INVALID;
     PixelLayout px;
     rc = encode_layout(c, ntiles, px); if (rc) return rc;
@@ -244,30 +230,22 @@ int grk_amd_stage_ingest_mct(grk_amd_ctx* c, const grk_amd_tile_params* p, uint3
 
 int grk_amd_stage_dwt_fwd(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nplanes, void* d_in, void* d_out)
 {
-    if (c) { const int jr = join_side(c); if (jr) return jr; }
-    if (!c || !p || !d_in || !d_out) return GRK_AMD_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device), "set device");
-    int rc = ensure_geom(c, p); if (rc) return rc;
+    const int rc = stage_enter(c, p, d_in && d_out, true); if (rc) return rc;
     return run_dwt(c, nplanes, d_in, d_out);
 }
 
 int grk_amd_stage_ht_encode(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat)
 {
-    if (c) { const int jr = join_side(c); if (jr) return jr; }
-    if (!c || !p || !d_mallat) return GRK_AMD_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device), "set device");
-    int rc = ensure_geom(c, p); if (rc) return rc;
+    const int rc = stage_enter(c, p, d_mallat != nullptr, true); if (rc) return rc;
     return run_ht(c, ntiles, d_mallat);
 }
 
 // the instances an encode of 8-bit reversible pixels launches (H16; flags bit 0: ROOM), on planes the caller chose
 int grk_amd_stage_ht_encode16(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat16, uint32_t flags)
 {
-    if (c) { const int jr = join_side(c); if (jr) return jr; }
-    if (!c || !p || !d_mallat16 || (flags & ~GRK_AMD_STAGE_HT_ROOM)) return GRK_AMD_ERR_INVALID;
-    if (!planes16_ok(*p)) return fail(c, GRK_AMD_ERR_INVALID, "no encode keeps int16 planes for these parameters");
-    HIP_TRY(c, hipSetDevice(c->device), "set device");
-    int rc = ensure_geom(c, p); if (rc) return rc;
+    const int rc = stage_enter(c, p, d_mallat16 && !(flags & ~GRK_AMD_STAGE_HT_ROOM), true,
+                               p && !planes16_ok(*p) ? "no encode keeps int16 planes for these parameters" : nullptr);
+    if (rc) return rc;
     return run_ht(c, ntiles, d_mallat16, false, true, (flags & GRK_AMD_STAGE_HT_ROOM) != 0);
 }
 
@@ -452,9 +430,8 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             c->side_pending = false;
             if (fs) {
                 fs_st = c->fs_parity ? c->side2 : c->side; c->fs_parity ^= 1;
-                if (!c->ev_main) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming), "create event");
-                HIP_TRY(c, hipEventRecord(c->ev_main, c->stream), "record the caller's stream");
-                HIP_TRY(c, hipStreamWaitEvent(fs_st, c->ev_main, 0), "the frame's stream waits for the pixels");
+                HIP_TRY(c, ensure_event(&c->ev_main), "create event");
+                rc = order_behind(c, fs_st, c->ev_main, c->stream, "record the caller's stream", "the frame's stream waits for the pixels"); if (rc) return rc;
             }
             HIP_TRY(c, hipStreamWaitEvent(fs ? fs_st : c->stream, c->ev_side, 0), "wait for the buffer set");
             HIP_TRY(c, hipStreamWaitEvent(fs ? fs_st : c->stream, c->ev_side2, 0), "wait for the buffer set");
@@ -471,7 +448,7 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             // the whole frame on its stream, as the non-overlapped path lays it out (one K3 launch of every block, the ROOM instance)
             struct StreamSwap { grk_amd_ctx* c; hipStream_t keep; StreamSwap(grk_amd_ctx* c_, hipStream_t s) : c(c_), keep(c_->stream) { c->stream = s; }
                                 ~StreamSwap() { c->stream = keep; } } on_frame_stream(c, fs_st);
-            if (!c->ev_px) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_px, hipEventDisableTiming), "create event");
+            HIP_TRY(c, ensure_event(&c->ev_px), "create event");
             ScopedTimer tf(c, 3);              // (the call's timer on the stream that carries the call)
             c->want_px_event = true;
             rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, false, h16, &px);
@@ -513,9 +490,8 @@ int grk_amd_stream_wait_results(grk_amd_ctx* c, void* hip_stream)
 {
     if (!c || !hip_stream) return GRK_AMD_ERR_INVALID;
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!c->ev_main) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming), "create event");
-    HIP_TRY(c, hipEventRecord(c->ev_main, c->stream), "record main stream");
-    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_main, 0), "wait for the main stream");
+    HIP_TRY(c, ensure_event(&c->ev_main), "create event");
+    { const int rc = order_behind(c, s, c->ev_main, c->stream, "record main stream", "wait for the main stream"); if (rc) return rc; }
     if (c->side_pending) {
         HIP_TRY(c, hipStreamWaitEvent(s, c->ev_side, 0), "wait for the side stream");
         HIP_TRY(c, hipStreamWaitEvent(s, c->ev_side2, 0), "wait for the side stream 2");
@@ -536,10 +512,8 @@ int grk_amd_stream_wait_pixels(grk_amd_ctx* c, void* hip_stream)
     hipStream_t s = (hipStream_t)hip_stream;
     if (c->px_event_valid) { HIP_TRY(c, hipStreamWaitEvent(s, c->ev_px, 0), "wait for the pixels' last read"); return GRK_AMD_OK; }
     if (s == c->stream) return GRK_AMD_OK;        // (stream order)
-    if (!c->ev_main) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming), "create event");
-    HIP_TRY(c, hipEventRecord(c->ev_main, c->stream), "record main stream");
-    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_main, 0), "wait for the main stream");
-    return GRK_AMD_OK;
+    HIP_TRY(c, ensure_event(&c->ev_main), "create event");
+    return order_behind(c, s, c->ev_main, c->stream, "record main stream", "wait for the main stream");
 }
 
 int grk_amd_get_pipelining(grk_amd_ctx* c)

@@ -3,6 +3,7 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 #include "geometry.h"
+#include "decode_constants.h"
 
 namespace grk_amd {
 
@@ -126,7 +127,6 @@ uint32_t   dwt_level_strip_cols(const DwtLevelArgs& a);   // ... for this level 
 uint32_t   idwt_strip_pairs();    // coefficient pairs a K6 workgroup owns
 
 // ---- K5: HT cleanup decoder + dequantisation (kernels_htdec.hip) --------------------------------
-constexpr uint32_t kSkipBlock = 0xFFFFFFFFu;   // missing_msbs of a zero-length row: the block lies outside the decoded region
 struct HtDecBlock {          // one per code-block, same layout as grk_amd_coded_block
     uint64_t offset;         // first byte of the block's cleanup pass inside `coded`
     uint32_t length;         // Lcup (0: block has no data -> all samples zero)
@@ -178,9 +178,6 @@ struct T1DecArgs {
 hipError_t launch_t1_decode(const T1DecArgs& a, hipStream_t s);
 
 // ---- K8L: the same decoder with one code-block per LANE + reconstruction from bit-plane bitmaps (kernels_t1lanes.hip) ----
-constexpr uint32_t kT1WorkBytes = 16384;       // a block's share of the Part-1 workspace (K8: 64 x 64 values; K8L: t1_lanes.h)
-constexpr uint32_t kT1LaneMaxPlanes = 14;      // bit-planes whose bitmaps fit behind a block's state there
-constexpr uint32_t kT1LaneMinRows = 9;         // a lane block has at least three stripes (t1_lanes.h: stripe hand-over)
 struct T1LaneArgs {
     const HtDecBlock* table;                   // as T1DecArgs
     const HtBlockDesc* blocks;
@@ -192,7 +189,6 @@ struct T1LaneArgs {
     int irreversible;
     int pass_sync;                             // the waves hold blocks of equal bit-plane / pass counts and run them pass by pass
 };
-constexpr uint32_t kT1NoBlock = 0xFFFFFFFFu;   // list entry of a lane without a block
 hipError_t launch_t1_lanes(const T1LaneArgs& a, hipStream_t s);       // t1_lanes_kernel, then t1_recon_kernel
 // both decoders in ONE launch (the blocks of d.list first, then the lane waves), then t1_recon_kernel: a frame's block decoding on one stream
 hipError_t launch_t1_fused(const T1DecArgs& d, const T1LaneArgs& a, hipStream_t s);

@@ -5,6 +5,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 n=$1; shift
 mkdir -p $R/build/abl/$n
 cd $R/grok_amd/csrc
+# (the library's sources: the one list of them, __graft_entry__.SOURCES)
+srcs=$(cd $R && python3 -c "import __graft_entry__ as e; print(' '.join(e.SOURCES))")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-variable "$@" -shared -o $R/build/abl/$n/libgrok_amd.so \
-  context.hip streams.hip encode.hip decode.hip assemble.hip kernels_ingest.hip kernels_dwt.hip kernels_ht.hip kernels_htdec.hip kernels_t1dec.hip kernels_t1lanes.hip kernels_t2.hip kernels_idwt.hip ../../build/source_stamp.cpp node.cpp geometry.cpp t2_writer.cpp image.cpp
+  -x hip $srcs ../../build/source_stamp.cpp
 echo built $R/build/abl/$n/libgrok_amd.so

@@ -108,8 +108,7 @@ struct grk_amd_ctx {
     std::vector<uint32_t> red_seg_first;                    // ... the segment list of the blocks that decode keeps (decode_impl, decode.hip)
     std::vector<grk_amd_segment> red_segs;
     DevBuf dec_seg_dev;
-    HtClass ht_classes[kHtMaxClasses]; uint32_t ht_num_classes = 0;   // block classes of K3: {top resolution, rest} x {LDS small, large}
-    uint8_t ht_class_top[kHtMaxClasses] = {}, ht_class_big[kHtMaxClasses] = {};
+    std::vector<HtClassPlan> ht_classes;      // block classes of K3 (plan_ht_classes, encode_plan.h); their lists lie in ht_sel
     int seq_index = -1;               // >= 0: one of a decode sequence's internal contexts (grk_amd_set_decode_pipelining)
     int seq_flavour = 0;              // ... whose two streams are made for 0: HT frames, 1: Part-1 frames (sequence_streams)
     hipStream_t side2 = nullptr; hipEvent_t ev_side2 = nullptr;      // the large-LDS classes run beside the small-LDS ones
@@ -162,12 +161,8 @@ struct grk_amd_ctx {
     // other blocks and the inverse levels that need only those; the last inverse level waits for it
     hipEvent_t ev_dec_front = nullptr, ev_dec_top = nullptr;
     bool dec_top_pending = false;
-    // Pipelined encodes of SMALL frames (up to kFrameStreamSamples samples per call): a frame's whole chain on ONE of the two side streams,
-    // taken in turn -- no event inside a frame (12 instead of 18 runtime calls), consecutive frames overlap through the streams.  A call
-    // is bound by the host's launches below ~2048^2 x 3: 512^2 x 3 0.058 -> 0.045 ms, 2048^2 x 3 0.073 -> 0.058; at 4096^2 it makes no
-    // difference, at 8192^2 it loses 19 % (no top-resolution K3 beside the remaining levels, no stream priorities).
-    // GRK_AMD_FRAME_STREAMS = 0: never, 1 (default): by size, 2: always
-    static constexpr uint64_t kFrameStreamSamples = 16ull << 20;
+    // Pipelined encodes of small frames run a frame's whole chain on ONE of the two side streams, taken in turn (encode_constants.h:
+    // kFrameStreamSamples; GRK_AMD_FRAME_STREAMS = 0: never, 1 (default): by size, 2: always)
     int frame_streams = 1; int fs_parity = 0;
     // ... the caller's pixels are then read on the frame's stream, not on the context's: level 0 -- their only reader -- is followed by
     // this event, and the context's stream waits for it, so that whatever the caller queues behind the call in stream order (the
@@ -251,8 +246,6 @@ int sequence_streams(grk_amd_ctx* k, bool part1);                               
 struct PixelLayout { uint32_t lay, channels, xstep, fill; uint64_t row, kstep, tile, bytes; };
 bool resolve_pixel_layout(const grk_amd_tile_params& p, const grk_amd_pixel_layout* l, uint32_t w, uint32_t h, uint32_t ntiles,
                           PixelLayout& out, const char** why);
-bool planes16_ok(const grk_amd_tile_params& p);                                                                  // encode.hip
-bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l);                                                    // encode.hip
 
 // ---- steps the encode and decode units share ----
 // The first steps of a grk_amd_stage_* entry point: the side streams joined (where the stage reads what they write), the null
@@ -318,11 +311,4 @@ inline int ensure_ll(grk_amd_ctx* c, uint32_t nplanes)
     return GRK_AMD_OK;
 }
 
-// row pairs per workgroup of a DWT level: halved from 64 (to 8 at the least) while strips x row segments x z slots stay below min_wgs
-inline uint32_t row_segment_pairs(uint64_t strips, uint32_t row_pairs, uint32_t zslots, uint32_t min_wgs)
-{
-    uint32_t seg = 64;
-    while (seg > 8 && strips * ((row_pairs + seg - 1) / seg) * zslots < min_wgs) seg >>= 1;
-    return seg;
-}
 #pragma GCC visibility pop

@@ -212,10 +212,8 @@ int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t reduce)
     c->gp = *p;
     const TileGeom& g = c->geom;
     c->h_desc.clear();
-    std::vector<uint8_t> h_res;                 // resolution of each block (0 = coarsest)
     for (uint32_t k = 0; k < p->num_comps; ++k)
         for (const auto& b : g.blocks_comp0) {
-            h_res.push_back(b.res);
             HtBlockDesc d;
             d.px = b.px; d.py = b.py;
             d.w = (uint16_t)(b.x1 - b.x0); d.h = (uint16_t)(b.y1 - b.y0);
@@ -223,50 +221,13 @@ int ensure_geom(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t reduce)
             d.inv_step = 1.0f / b.stepsize;
             c->h_desc.push_back(d);
         }
-    // K3 block classes, each its own launch: the top resolution's sub-bands (3/4 of all blocks) are final after DWT
-    // level 0, so they are coded beside the remaining levels (run_dwt, overlap), the rest after the last level; a third
-    // class holds ALL blocks, for when nothing overlaps (one launch, one tail).  The LDS buffers of a launch are sized
-    // for what the class's typical block needs (capped, kernels_ht.hip) -- the LDS per wave is what fixes the occupancy
-    // -- and the blocks that outgrow them, e.g. the few high-Kmax blocks of the low resolutions, go through the fallback
-    // launch.  Only with GRK_AMD_LDS_CAP=0 (worst-case buffers, no fallback) are the large-LDS blocks classes of their
-    // own, so that they do not cost every block a wave per SIMD.  Few classes on purpose: a launch ends with a tail of
-    // long-running waves, and launches on one stream do not overlap (measured: one class per resolution costs 0.15 ms at 8K).
+    // K3's block classes (encode_plan.h): the lists of all classes on the device, one behind the other
     {
-        constexpr size_t kLdsFor16Waves = 10240;
-        std::vector<uint32_t> sel;
-        std::vector<HtClass> cls;
-        std::vector<size_t> first;
-        std::vector<uint8_t> ctop, cbig;
-        auto add_class = [&](int top, int big) {       // top: 1 top resolution, 0 the rest, 2 every block;  big: -1 any, 0 / 1 by LDS need
-            HtClass cl{nullptr, 0, 0, 0, 0, 0, 0};
-            const size_t at = sel.size();
-            uint32_t hist[64] = {0};
-            for (uint32_t i = 0; i < c->h_desc.size(); ++i) {
-                if (top != 2 && (int)(h_res[i] == g.p.num_levels && g.p.num_levels >= 1) != top) continue;
-                const HtBlockDesc& d = c->h_desc[i];
-                const uint32_t samples = (uint32_t)d.w * d.h, quads = ((d.w + 1u) / 2u) * ((d.h + 1u) / 2u);
-                if (big >= 0 && (int)(ht_lds_bytes(samples, quads, d.kmax) > kLdsFor16Waves) != big) continue;
-                cl.count++;
-                cl.max_kmax = std::max<uint32_t>(cl.max_kmax, d.kmax);
-                cl.max_samples = std::max<uint32_t>(cl.max_samples, samples);
-                cl.max_quads = std::max<uint32_t>(cl.max_quads, quads);
-                hist[d.kmax & 63u] += samples;
-                sel.push_back(i);
-            }
-            for (uint32_t k = 0; k < 64; ++k) if (hist[k] > hist[cl.cap_kmax]) cl.cap_kmax = k;     // where most of the samples are
-            if (cl.count) { cls.push_back(cl); first.push_back(at); ctop.push_back((uint8_t)top); cbig.push_back((uint8_t)(big > 0)); }
-        };
-        if (c->lds_cap) { add_class(1, -1); add_class(0, -1); add_class(2, -1); }
-        else { add_class(1, 0); add_class(1, 1); add_class(0, 0); add_class(0, 1); }
-        HIP_TRY(c, c->ht_sel.ensure(sel.size() * 4 + 16), "alloc class index");
-        HIP_TRY(c, hipMemcpyAsync(c->ht_sel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, c->stream), "upload class index");
+        HtClasses plan = plan_ht_classes(g, p->num_comps, c->lds_cap);
+        HIP_TRY(c, c->ht_sel.ensure(plan.sel.size() * 4 + 16), "alloc class index");
+        HIP_TRY(c, hipMemcpyAsync(c->ht_sel.p, plan.sel.data(), plan.sel.size() * 4, hipMemcpyHostToDevice, c->stream), "upload class index");
         HIP_TRY(c, hipStreamSynchronize(c->stream), "sync class index");
-        for (size_t k = 0; k < cls.size(); ++k) {
-            cls[k].sel = (const uint32_t*)c->ht_sel.p + first[k];
-            c->ht_classes[k] = cls[k];
-            c->ht_class_top[k] = ctop[k]; c->ht_class_big[k] = cbig[k];
-        }
-        c->ht_num_classes = (uint32_t)cls.size();
+        c->ht_classes = std::move(plan.classes);
     }
     // decode-side descriptors: inv_step carries the dequantisation scale of the band
     // (codestream/Quantizer.cpp:41-63 with compress = false: log2_gain 0, then / 2^(31 - numbps))

@@ -27,61 +27,60 @@ int run_ingest(grk_amd_ctx* c, uint32_t ntiles, const void* d_pixels, void* d_pl
     return GRK_AMD_OK;
 }
 
-HtArgs make_ht_args(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, int* rc, bool h16)
+// K3's arguments for `ntiles` tiles of the current geometry -- its buffers at their sizes, the arena and allocator plan, the classes
+// with their lists --, built ONCE per call: every launch of the call, on whichever stream, takes a copy
+int make_ht_args(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool h16, HtArgs& a)
 {
-    HtArgs a{};
-    *rc = GRK_AMD_OK;
-    auto try_ = [&](hipError_t e, const char* what) { if (e != hipSuccess && *rc == GRK_AMD_OK) *rc = fail(c, GRK_AMD_ERR_NO_DEVICE, what, e); };
+    a = HtArgs{};
     const TileGeom& g = c->geom;
     const uint32_t bpt = g.blocks_per_comp * g.p.num_comps;
     const uint64_t nblocks = (uint64_t)bpt * ntiles;
-    try_(c->lengths.ensure(nblocks * 4), "alloc lengths");
-    try_(c->offsets.ensure((nblocks + 1) * 8), "alloc offsets");
-    try_(c->flag.ensure(kHtAllocBytes), "alloc allocator state");
-    // arena: worst case of the HT cleanup pass is ~ (kmax+1)/8 * 8/7 bytes per sample + VLC/MEL;
-    // twice the raw input size plus per-block slack covers every lossless case we accept
     const uint64_t raw = (uint64_t)ntiles * g.p.num_comps * g.p.tile_w * g.p.tile_h * ((g.p.prec + 7) / 8);
-    // Allocation regions: every block reserves its bytes with an atomic on its region's word, and the blocks of a launch that fits
-    // the machine in one round (up to ~6 000) all arrive there within microseconds of each other -- atomics on ONE address are
-    // served one after the other, and a chunk refill makes the region's other waves wait.  At least one region per 64 blocks (r04:
-    // with one per 256, K3 of a 2048^2 frame took 0.151 ms, with this 0.048; 1024^2 0.079 -> 0.038, 3072^2 0.177 -> 0.069; from
-    // 4096^2 on all 64 regions were in use before: tools/k3_sizes.py); small jobs take smaller chunks, so that the slack of the
-    // regions' half-used chunks stays small against their coded bytes.
-    constexpr uint32_t kBlocksPerRegion = 64;
-    uint32_t regions = 1;
-    while (regions < kHtAllocRegions && nblocks / (regions * 2) >= kBlocksPerRegion) regions *= 2;
-    // (a chunk holds at least two of the largest blocks the geometry can produce: worst case (Kmax + 2) bits per sample and 15 VLC
-    //  bits per quad, stuffing 1 bit in 15, 256 MEL bytes -- ~20 KiB for a 64 x 64 block at Kmax 31)
-    size_t worst_block = 0;
-    for (uint32_t k = 0; k < c->ht_num_classes; ++k) {
-        const HtClass& hc = c->ht_classes[k];
-        worst_block = std::max(worst_block, ((size_t)hc.max_samples * (hc.max_kmax + 2u) + (size_t)hc.max_quads * 15u) * 16u / 15u / 8u + 280u);
-    }
-    const uint32_t chunk = (nblocks < 16384 && 2 * worst_block <= kHtAllocChunkSmall) ? kHtAllocChunkSmall : kHtAllocChunk;
-    try_(c->arena.ensure(raw * 2 + nblocks * 64 + (size_t)(regions + 1) * kHtAllocChunk + (1u << 20)), "alloc coded arena");
+    const HtArenaPlan plan = plan_ht_arena(nblocks, raw, ntiles, c->ht_classes);
+    HIP_TRY(c, c->lengths.ensure(nblocks * 4), "alloc lengths");
+    HIP_TRY(c, c->offsets.ensure((nblocks + 1) * 8), "alloc offsets");
+    HIP_TRY(c, c->flag.ensure(kHtAllocBytes), "alloc allocator state");
+    HIP_TRY(c, c->arena.ensure(plan.arena_bytes), "alloc coded arena");
+    HIP_TRY(c, c->ovf.ensure(plan.ovf_entries * 4 + 16), "alloc fallback list");
     a.mallat = (const int32_t*)d_mallat; a.stride = g.stride; a.pitch = g.plane_elems; a.h16 = h16 ? 1 : 0;
     a.blocks = (const HtBlockDesc*)c->blockdesc.p; a.blocks_per_tile = bpt; a.ncomp = g.p.num_comps; a.ntiles = ntiles;
     a.arena = (uint8_t*)c->arena.p; a.arena_bytes = c->arena.cap;
     a.alloc = (unsigned long long*)c->flag.p;        // [0] status flags, [1] bytes used (launch_ht_alloc_init resets them)
     a.lengths = (uint32_t*)c->lengths.p; a.offsets = (unsigned long long*)c->offsets.p;
-    try_(c->ovf.ensure(2 * nblocks * 4 + 16), "alloc fallback list");      // (every block is in two classes)
     a.ovf_list = c->lds_cap ? (uint32_t*)c->ovf.p : nullptr;
-    a.region_mask = regions - 1;
-    a.chunk_units = chunk / 16u;
+    a.region_mask = plan.regions - 1;
+    a.chunk_units = plan.chunk / 16u;
     a.irreversible = g.p.irreversible;
-    a.num_classes = c->ht_num_classes;
-    uint32_t ovf_base = 0;
-    for (uint32_t k = 0; k < c->ht_num_classes; ++k) {
-        a.classes[k] = c->ht_classes[k];
-        a.classes[k].ovf_base = ovf_base;
-        ovf_base += c->ht_classes[k].count * ntiles;
+    a.num_classes = (uint32_t)c->ht_classes.size();
+    for (uint32_t k = 0; k < a.num_classes; ++k) {
+        const HtClassPlan& hc = c->ht_classes[k];
+        a.classes[k] = HtClass{(const uint32_t*)c->ht_sel.p + hc.first, hc.count, hc.max_kmax, hc.max_samples, hc.max_quads, plan.ovf_base[k], hc.cap_kmax};
     }
-    return a;
+    return GRK_AMD_OK;
+}
+
+// the classes the schedule (ht_class_stream, encode_plan.h) places at this point of the call, each on its stream
+int launch_ht_at(grk_amd_ctx* c, const HtArgs& h, bool overlapped, HtPoint at, bool one_level)
+{
+    for (uint32_t k = 0; k < h.num_classes; ++k) {
+        const HtStream to = ht_class_stream(c->ht_classes[k].role, overlapped, c->pipelining, at, one_level);
+        if (to == HtStream::NotHere) continue;
+        if (to == HtStream::Main) { HIP_TRY(c, launch_ht_classes(h, k, k + 1, c->stream), "launch ht encode"); continue; }
+        hipStream_t st = to == HtStream::Side ? c->side : c->side2;
+        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_level0, 0), "side stream waits for the level");
+        ScopedTimer tt(c, st == c->side ? 4 : 8, st);
+        // (consecutive encodes pipelined: the top class is still running when the next encode's level 0 arrives)
+        HtArgs hs = h;
+        hs.room = c->pipelining ? 1 : 0;
+        HIP_TRY(c, launch_ht_classes(hs, k, k + 1, st), "launch ht encode (side stream)");
+    }
+    return GRK_AMD_OK;
 }
 
 // d_pixels != nullptr: level 0 reads the caller's pixels directly (K1 fused into K2), d_in is unused
+// overlap_ht != nullptr: K3 of the classes whose sub-bands are final is queued on the side streams behind level 0 and the last level
 int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const void* d_pixels = nullptr, uint32_t ntiles = 0,
-            bool overlap_ht = false, bool h16 = false, const PixelLayout* px = nullptr)
+            const HtArgs* overlap_ht = nullptr, bool h16 = false, const PixelLayout* px = nullptr)
 {
     const TileGeom& g = c->geom;
     const uint32_t L = g.p.num_levels;
@@ -104,18 +103,15 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
         a.h16 = h16 ? 1 : 0;
         a.pk = h16 && c->dwt_pk && pk16_level_ok(g.p, l);
         a.xcd = c->dwt_xcd;
-        if (l == 0 && d_pixels && px && px->lay) {     // (before the strips are counted: the layout decides between the level-0 kernels)
+        if (l == 0 && d_pixels && px && px->lay) {     // (before the level is shaped: the layout decides between the level-0 kernels)
             set_px_in(a, *px); a.px_chan = px->channels;
         }
-        // enough workgroups to cover the chip several times, few enough to amortise warm-up rows (profiles/r06_dwt_reads.txt: at 4096
-        // the 8K level 0 ran 16-row segments and read 1.55 x its pixels; 2048 -> 32-row segments, 1.35 x, the DWT 1 % faster)
-        const uint32_t sh = (a.ch + a.py + 1) >> 1;           // row pairs on the coordinate grid
-        const uint64_t strips = (a.cw + a.px + dwt_level_strip_cols(a) - 1) / dwt_level_strip_cols(a);
-        // workgroups along z: planes, or for the fused level 0 tiles (x components when there is no MCT triple)
+        // the level's kernel, strips and row segments (plan_dwt_level, encode_plan.h).  Workgroups along z: planes, or for the fused
+        // level 0 tiles (x components when there is no MCT triple)
         const uint32_t zslots = (l == 0 && d_pixels) ? ntiles * ((g.p.mct && g.p.num_comps >= 3) ? 1u : g.p.num_comps) : nplanes;
-        // (... for the packed 5/3 kernel; the 32-bit kernels -- 448-column strips, twice the workgroups per row -- are better off with
-        //  the finer cut: cfg3's 9/7 family 0.361 ms at 4096, 0.394 at 2048)
-        a.seg_pairs = row_segment_pairs(strips, sh, zslots, a.pk ? 2048u : 4096u);
+        const DwtLevelShape shape = plan_dwt_level(DwtLevelDesc{a.cw, a.ch, a.px, a.py, a.in_stride, a.m_stride, a.h16 != 0, a.pk != 0,
+                                                                a.irreversible != 0, a.px_lay, a.px_chan, a.px_row, zslots});
+        a.seg_pairs = shape.seg_pairs;
         if (a.cw == 0 || a.ch == 0) {
             // a level without samples (a narrow tile off the origin: [ceil(x0 / 2^l), ceil((x0 + w) / 2^l)) can be empty):
             // nothing to transform, and nothing deeper either
@@ -124,38 +120,15 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
             a.pixels = d_pixels; a.px_bytes = r.bytes;
             a.alloc_reset = c->pend_alloc; a.alloc_chunk_units = c->pend_alloc_units; c->pend_alloc = nullptr;
             a.dc = r.dc; a.sext = r.sext;
-            HIP_TRY(c, launch_dwt_level0_fused(a, ntiles, g.p.num_comps, g.p.mct, c->stream), "launch fused dwt level 0");
+            HIP_TRY(c, launch_dwt_level0_fused(a, shape, ntiles, g.p.num_comps, g.p.mct, c->stream), "launch fused dwt level 0");
             if (c->want_px_event) HIP_TRY(c, hipEventRecord(c->ev_px, c->stream), "record the pixels' last read");
         } else {
-            HIP_TRY(c, launch_dwt_level(a, c->stream), "launch dwt level");
+            HIP_TRY(c, launch_dwt_level(a, shape, c->stream), "launch dwt level");
         }
         if (overlap_ht && (l == 0 || l + 1 == L)) {
-            // After level 0 the top resolution's sub-bands are final: its code-blocks (3/4 of all) are coded on
-            // low-priority side streams while the remaining levels -- short, latency-bound launches that are the
-            // critical path -- run here.  After the last level the rest follows: small-LDS class on this stream (run_ht),
-            // large-LDS class on the second side stream, so that the launches' tails overlap.
-            int rc = GRK_AMD_OK;
-            const HtArgs h = make_ht_args(c, ntiles, d_out, &rc, h16);
-            if (rc) return rc;
             HIP_TRY(c, hipEventRecord(c->ev_level0, c->stream), "record level");
-            for (uint32_t k = 0; k < h.num_classes; ++k) {
-                if (c->ht_class_top[k] == 2) continue;               // (the all-blocks class is for the non-overlapped path)
-                const bool top = c->ht_class_top[k] != 0, big = c->ht_class_big[k] != 0;
-                hipStream_t st = nullptr;
-                if (l == 0 && top) st = big ? c->side2 : c->side;
-                if (l + 1 == L && !top && big) st = c->side2;
-                // the rest: on the main stream (run_ht) beside the tail of the top resolution -- unless consecutive encodes
-                // are pipelined: then the main stream carries nothing but the DWT chain, so that the next encode's level 0
-                // starts as early as possible, and every K3 launch queues on a side stream
-                if (l + 1 == L && !top && !big && c->pipelining) st = c->side2;    // (its tail then overlaps the top class's)
-                if (!st) continue;
-                HIP_TRY(c, hipStreamWaitEvent(st, c->ev_level0, 0), "side stream waits for the level");
-                ScopedTimer tt(c, st == c->side ? 4 : 8, st);
-                // (consecutive encodes pipelined: the top class is still running when the next encode's level 0 arrives)
-                HtArgs hs = h;
-                hs.room = c->pipelining ? 1 : 0;
-                HIP_TRY(c, launch_ht_classes(hs, k, k + 1, st), "launch ht encode (side stream)");
-            }
+            const int rc = launch_ht_at(c, *overlap_ht, true, l == 0 ? HtPoint::AfterLevel0 : HtPoint::AfterLastLevel, L == 1);
+            if (rc) return rc;
             if (l + 1 == L) {
                 HIP_TRY(c, hipEventRecord(c->ev_side, c->side), "record side stream");
                 HIP_TRY(c, hipEventRecord(c->ev_side2, c->side2), "record side stream 2");
@@ -166,57 +139,24 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
 }
 
 // overlapped: the top resolution and the large-LDS classes are already running on the side streams (run_dwt)
-int run_ht(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool overlapped = false, bool h16 = false, bool room = false)
+int run_ht(grk_amd_ctx* c, HtArgs a, bool overlapped = false, bool room = false)
 {
-    int rc = GRK_AMD_OK;
-    HtArgs a = make_ht_args(c, ntiles, d_mallat, &rc, h16);
-    if (rc) return rc;
     a.room = room ? 1 : 0;
     {
         ScopedTimer t(c, 2);
-        if (!overlapped) {         // one launch of every block where there is such a class, else class by class
-            HIP_TRY(c, launch_ht_alloc_init(a, c->stream), "reset arena allocator");
-            bool all = false;
-            for (uint32_t k = 0; k < a.num_classes; ++k) all = all || c->ht_class_top[k] == 2;
-            for (uint32_t k = 0; k < a.num_classes; ++k)
-                if ((c->ht_class_top[k] == 2) == all) HIP_TRY(c, launch_ht_classes(a, k, k + 1, c->stream), "launch ht encode");
-        } else {
-            for (uint32_t k = 0; k < a.num_classes && !c->pipelining; ++k)
-                if (!c->ht_class_top[k] && !c->ht_class_big[k]) HIP_TRY(c, launch_ht_classes(a, k, k + 1, c->stream), "launch ht encode");
-        }
+        if (!overlapped) HIP_TRY(c, launch_ht_alloc_init(a, c->stream), "reset arena allocator");
+        const int rc = launch_ht_at(c, a, overlapped, HtPoint::RunHt, false);
+        if (rc) return rc;
     }
     if (overlapped) {
         c->side_pending = true;
         if (!c->pipelining) { const int jr = join_side(c); if (jr) return jr; }    // pipelining: the next consumer joins
     }
-    c->last_ntiles = ntiles;
-    c->last_nblocks = (uint64_t)c->geom.blocks_per_comp * c->geom.p.num_comps * ntiles;
+    c->last_ntiles = a.ntiles;
+    c->last_nblocks = (uint64_t)a.blocks_per_tile * a.ntiles;
     return GRK_AMD_OK;
 }
 } // namespace
-
-// 16-bit planes are safe when no coefficient of any level can leave int16.  Bound (5/3, L1 norms of the analysis
-// filters: low-pass 1.5, high-pass 2 per dimension; RCT chroma is one bit wider than the pixels): the LL of level l is
-// below M * 2.25^l, a detail band of level l below 4 * M * 2.25^(l-1), with M = 2^prec the largest input magnitude.
-bool planes16_ok(const grk_amd_tile_params& p)
-{
-    if (p.irreversible || p.prec > 8 || p.num_levels == 0) return false;
-    double bound = (double)(1u << p.prec) * 4.0;
-    for (uint32_t l = 1; l < p.num_levels; ++l) bound *= 2.25;
-    return bound + 8.0 * p.num_levels < 32767.0;
-}
-
-// Level l of such a tile on PACKED int16 pairs (kernels_dwt.hip, strip_pk): every intermediate of the 2-D lifting step has to
-// stay inside 16 bits as well.  With M the largest magnitude entering the level (2^prec after DC shift and RCT, times the
-// low-pass gain 1.5 x 1.5 per level before, plus rounding), the largest is the horizontal update's sum of two high-pass
-// values of a vertically high-pass row: 2 x 2 x 2M each, 8M + 2 in all.
-bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l)
-{
-    if (p.sgnd) return false;                        // (the packed unpacking is written for unsigned pixels)
-    double m = (double)(1u << p.prec);
-    for (uint32_t i = 0; i < l; ++i) m = m * 2.25 + 4.0;
-    return 8.0 * m + 16.0 < 32767.0;
-}
 
 extern "C" {
 int grk_amd_stage_ingest_mct(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_pixels, void* d_planes)
@@ -236,17 +176,21 @@ int grk_amd_stage_dwt_fwd(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t
 
 int grk_amd_stage_ht_encode(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat)
 {
-    const int rc = stage_enter(c, p, d_mallat != nullptr, true); if (rc) return rc;
-    return run_ht(c, ntiles, d_mallat);
+    int rc = stage_enter(c, p, d_mallat != nullptr, true); if (rc) return rc;
+    HtArgs h;
+    rc = make_ht_args(c, ntiles, d_mallat, false, h); if (rc) return rc;
+    return run_ht(c, h);
 }
 
 // the instances an encode of 8-bit reversible pixels launches (H16; flags bit 0: ROOM), on planes the caller chose
 int grk_amd_stage_ht_encode16(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat16, uint32_t flags)
 {
-    const int rc = stage_enter(c, p, d_mallat16 && !(flags & ~GRK_AMD_STAGE_HT_ROOM), true,
+    int rc = stage_enter(c, p, d_mallat16 && !(flags & ~GRK_AMD_STAGE_HT_ROOM), true,
                                p && !planes16_ok(*p) ? "no encode keeps int16 planes for these parameters" : nullptr);
     if (rc) return rc;
-    return run_ht(c, ntiles, d_mallat16, false, true, (flags & GRK_AMD_STAGE_HT_ROOM) != 0);
+    HtArgs h;
+    rc = make_ht_args(c, ntiles, d_mallat16, true, h); if (rc) return rc;
+    return run_ht(c, h, false, (flags & GRK_AMD_STAGE_HT_ROOM) != 0);
 }
 
 int grk_amd_fetch_table(grk_amd_ctx* c, grk_amd_coded_block* table, uint64_t* total)
@@ -395,22 +339,18 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
         d_px = c->pixels.p;
     }
     const uint32_t nplanes = ntiles * g.p.num_comps;
-    // with at least one DWT level, level 0 consumes the pixels itself and the int32 ingest planes
-    // (4 bytes per sample written and read back) never exist
-    const bool fused = g.p.num_levels >= 1 && ((uintptr_t)d_px & 3u) == 0;
+    // the call's route (plan_route, encode_plan.h)
+    const Route route = plan_route(g.p, RouteIn{c->overlap, c->pipelining, c->frame_streams, c->planes16, c->side != nullptr, c->side2 != nullptr,
+                                                on_device != 0, (uint32_t)((uintptr_t)d_px & 3u), (uint64_t)nplanes * g.plane_elems});
+    const bool fused = route.fused, ov = route.overlap, fs = route.frame_stream, h16 = route.h16;
     if (!fused) HIP_TRY(c, c->p0.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc planes");
     HIP_TRY(c, c->p1.ensure((size_t)nplanes * g.plane_elems * 4 + 256), "alloc Mallat planes");
     {
         ScopedTimer t(c, 3);
-        const bool ov = c->overlap && g.p.num_levels >= 1 && c->side != nullptr;
         if (ov && c->pipelining && c->seq_index < 0 && probe_streams(c) != GRK_AMD_OK) {
             // (the probe is a convenience: when it cannot run, the streams stay as they are and it is not tried again)
             c->stream_probe = 0; (void)hipGetLastError();
         }
-        // (device-resident pixels only: the staging buffer of host pixels is filled on the main stream, which must then carry level 0)
-        // (... and the fused level 0: the stand-alone ingest writes planes that are not part of a buffer set)
-        const bool fs = ov && c->pipelining && c->side2 != nullptr && on_device && fused &&
-                        (c->frame_streams == 2 || (c->frame_streams == 1 && (uint64_t)nplanes * g.plane_elems <= grk_amd_ctx::kFrameStreamSamples));
         hipStream_t fs_st = nullptr;
         if (ov && c->pipelining) {
             // take the other buffer set: the blocks of the previous encode may still be being coded from the set used
@@ -439,10 +379,10 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
         } else {
             rc = join_side(c); if (rc) return rc;
         }
-        // 8-bit reversible content: int16 LL / Mallat planes between K2 and K3 (half the bytes written and read back);
-        // needs the fused level 0 (the stand-alone ingest kernel writes int32 planes)
-        const bool h16 = c->planes16 && fused && planes16_ok(g.p);
         c->last_h16 = h16;
+        // K3's arguments, once for the call (after the buffer set was taken: they point into it)
+        HtArgs h;
+        rc = make_ht_args(c, ntiles, c->p1.p, h16, h); if (rc) return rc;
         if (fs) {
             t.cancel();
             // the whole frame on its stream, as the non-overlapped path lays it out (one K3 launch of every block, the ROOM instance)
@@ -451,14 +391,14 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             HIP_TRY(c, ensure_event(&c->ev_px), "create event");
             ScopedTimer tf(c, 3);              // (the call's timer on the stream that carries the call)
             c->want_px_event = true;
-            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, false, h16, &px);
+            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, nullptr, h16, &px);
             c->want_px_event = false;
             if (rc) return rc;
             // the pixel-lifetime contract of every other path: work queued on the context's stream after this call comes after the read
             c->px_event_valid = true;
             if (!c->px_hold)
                 HIP_TRY(c, hipStreamWaitEvent(on_frame_stream.keep, c->ev_px, 0), "the context's stream waits for the pixels' last read");
-            rc = run_ht(c, ntiles, c->p1.p, false, h16, true); if (rc) return rc;
+            rc = run_ht(c, h, false, true); if (rc) return rc;
             HIP_TRY(c, hipEventRecord(c->ev_side, fs_st), "record the frame's stream");
             HIP_TRY(c, hipEventRecord(c->ev_side2, fs_st), "record the frame's stream");
             c->side_pending = true;
@@ -467,20 +407,17 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
         }
         c->px_event_valid = false;          // (the pixels are read on the context's stream itself from here on)
         if (ov) {       // the allocator must be reset before the first K3 launch of either stream
-            int rc2 = GRK_AMD_OK;
-            const HtArgs h = make_ht_args(c, ntiles, c->p1.p, &rc2, h16);
-            if (rc2) return rc2;
             // (with the fused level 0 its first workgroup does it: one launch less on the main stream's chain)
             if (fused) { c->pend_alloc = h.alloc; c->pend_alloc_units = h.chunk_units; }
             else HIP_TRY(c, launch_ht_alloc_init(h, c->stream), "reset arena allocator");
         }
         if (fused) {
-            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, ov, h16, &px); if (rc) return rc;
+            rc = run_dwt(c, nplanes, nullptr, c->p1.p, d_px, ntiles, ov ? &h : nullptr, h16, &px); if (rc) return rc;
         } else {
             rc = run_ingest(c, ntiles, d_px, c->p0.p, px); if (rc) return rc;
-            rc = run_dwt(c, nplanes, c->p0.p, c->p1.p, nullptr, ntiles, ov); if (rc) return rc;
+            rc = run_dwt(c, nplanes, c->p0.p, c->p1.p, nullptr, ntiles, ov ? &h : nullptr); if (rc) return rc;
         }
-        rc = run_ht(c, ntiles, c->p1.p, ov, h16); if (rc) return rc;
+        rc = run_ht(c, h, ov); if (rc) return rc;
     }
     if (table || total) return grk_amd_fetch_table(c, table, total);
     return GRK_AMD_OK;

@@ -1,0 +1,150 @@
+// grok_amd/csrc/encode_plan.cpp -- the host's planning for an encode call (encode_plan.h): block classes, LDS buffers, arena,
+// class schedule, route, DWT level shapes.
+#include "encode_plan.h"
+#include <algorithm>
+
+namespace grk_amd {
+
+// ---- K3 block classes ------------------------------------------------------------------------------------------------------------
+HtClasses plan_ht_classes(const TileGeom& g, uint32_t ncomp, bool lds_cap)
+{
+    HtClasses out;
+    const uint32_t bpc = (uint32_t)g.blocks_comp0.size();
+    auto add_class = [&](HtRole role, int top, int big) {      // top: 1 top resolution, 0 the rest, -1 every block;  big: -1 any, 0 / 1 by LDS need
+        HtClassPlan cl{0, 0, 0, 0, 0, (uint32_t)out.sel.size(), role};
+        uint32_t hist[64] = {0};
+        for (uint32_t i = 0; i < ncomp * bpc; ++i) {
+            const grk_amd_block& b = g.blocks_comp0[i % bpc];
+            if (top >= 0 && (int)(b.res == g.p.num_levels && g.p.num_levels >= 1) != top) continue;
+            const uint32_t w = b.x1 - b.x0, h = b.y1 - b.y0;
+            const uint32_t samples = w * h, quads = ((w + 1u) / 2u) * ((h + 1u) / 2u);
+            if (big >= 0 && (int)(ht_lds_bytes(samples, quads, b.kmax) > kLdsFor16Waves) != big) continue;
+            cl.count++;
+            cl.max_kmax = std::max<uint32_t>(cl.max_kmax, b.kmax);
+            cl.max_samples = std::max(cl.max_samples, samples);
+            cl.max_quads = std::max(cl.max_quads, quads);
+            hist[b.kmax & 63u] += samples;
+            out.sel.push_back(i);
+        }
+        for (uint32_t k = 0; k < 64; ++k) if (hist[k] > hist[cl.cap_kmax]) cl.cap_kmax = k;     // where most of the samples are
+        if (cl.count) out.classes.push_back(cl);
+    };
+    if (lds_cap) { add_class(HtRole::Top, 1, -1); add_class(HtRole::Rest, 0, -1); add_class(HtRole::All, -1, -1); }
+    else { add_class(HtRole::TopSmall, 1, 0); add_class(HtRole::TopBig, 1, 1); add_class(HtRole::RestSmall, 0, 0); add_class(HtRole::RestBig, 0, 1); }
+    return out;
+}
+
+// ---- the LDS buffers of a class ---------------------------------------------------------------------------------------------------
+HtLdsPlan ht_lds_layout(uint32_t samples, uint32_t quads, uint32_t kmax, bool capped, bool irrev)
+{
+    HtLdsPlan L{};
+    const uint32_t per_sample = !capped ? kmax + 2u : irrev ? std::min(kmax + 2u, 8u) : std::min(kmax + 2u, kmax <= 11u ? 8u : kmax - 3u);
+    const uint32_t ms_bits = samples * per_sample;
+    const uint32_t vlc_bits = quads * (capped ? 10u : 15u) + 4u;
+    L.ms_cap_bits = ms_bits;
+    L.vlc_cap_bits = vlc_bits;
+    L.ms_words = ((ms_bits + 31u) / 32u + 4u + 3u) & ~3u;           // slack: or_bits64 / window reads touch two words beyond;
+    L.vlc_words = ((vlc_bits + 31u) / 32u + 4u + 3u) & ~3u;         // multiples of 4 words: cleared as uint4
+    // behind the raw streams: the UVLC table (64 x 8 bytes) while phase A runs, then the staged VLC bytes (phase B1: the stuffed
+    // bytes of the stream's capacity) in the same place; then 256 MEL bytes.  (A raw stream's windows read up to 65 words past its
+    // end: the two areas are at least 192 words.)
+    L.stage_bytes = std::max<uint32_t>(((vlc_bits / 7u + 16u) + 15u) & ~15u, 512u);
+    L.bytes = (size_t)(L.ms_words + L.vlc_words) * 4u + L.stage_bytes + 256u;
+    return L;
+}
+
+size_t ht_waves_per_cu(size_t lds_bytes) { return std::min(kMaxWavesPerCu, kLdsPerCu / std::max<size_t>(lds_bytes, 1)); }
+
+HtClassLds plan_ht_lds(uint32_t max_samples, uint32_t max_quads, uint32_t max_kmax, uint32_t cap_kmax, bool irrev, bool have_fallback)
+{
+    HtClassLds r;
+    r.full = ht_lds_layout(max_samples, max_quads, max_kmax, false, false);
+    r.cap = ht_lds_layout(max_samples, max_quads, cap_kmax, true, irrev);
+    r.use_cap = have_fallback && ht_waves_per_cu(r.cap.bytes) > ht_waves_per_cu(r.full.bytes);
+    return r;
+}
+
+// ---- the arena and its allocator ---------------------------------------------------------------------------------------------------
+HtArenaPlan plan_ht_arena(uint64_t nblocks, uint64_t raw_bytes, uint32_t ntiles, const std::vector<HtClassPlan>& classes)
+{
+    HtArenaPlan a{};
+    a.regions = 1;
+    while (a.regions < kHtAllocRegions && nblocks / (a.regions * 2) >= kHtBlocksPerRegion) a.regions *= 2;
+    // (a chunk holds at least two of the largest blocks the geometry can produce: worst case (Kmax + 2) bits per sample and 15 VLC
+    //  bits per quad, stuffing 1 bit in 15, 256 MEL bytes -- ~20 KiB for a 64 x 64 block at Kmax 31)
+    uint32_t ovf_base = 0;
+    for (size_t k = 0; k < classes.size() && k < kHtMaxClasses; ++k) {
+        const HtClassPlan& hc = classes[k];
+        a.worst_block = std::max(a.worst_block, ((size_t)hc.max_samples * (hc.max_kmax + 2u) + (size_t)hc.max_quads * 15u) * 16u / 15u / 8u + 280u);
+        a.ovf_base[k] = ovf_base;
+        ovf_base += hc.count * ntiles;
+    }
+    a.chunk = (nblocks < kHtSmallJobBlocks && 2 * a.worst_block <= kHtAllocChunkSmall) ? kHtAllocChunkSmall : kHtAllocChunk;
+    // arena: worst case of the HT cleanup pass is ~ (kmax+1)/8 * 8/7 bytes per sample + VLC/MEL;
+    // twice the raw input size plus per-block slack covers every lossless case we accept
+    a.arena_bytes = raw_bytes * 2 + nblocks * 64 + (uint64_t)(a.regions + 1) * kHtAllocChunk + (1u << 20);
+    a.ovf_entries = 2 * nblocks;
+    return a;
+}
+
+// ---- which class goes to which stream, and when ------------------------------------------------------------------------------------
+HtStream ht_class_stream(HtRole role, bool overlapped, bool pipelined, HtPoint at, bool one_level)
+{
+    for (const HtScheduleRow& r : kHtSchedule) {
+        if (r.role != role || r.overlapped != overlapped || (r.pipelined >= 0 && (r.pipelined != 0) != pipelined)) continue;
+        if (r.at == at || (one_level && at == HtPoint::AfterLevel0 && r.at == HtPoint::AfterLastLevel)) return r.to;
+    }
+    return HtStream::NotHere;
+}
+
+// ---- the call's route ----------------------------------------------------------------------------------------------------------------
+bool planes16_ok(const grk_amd_tile_params& p)
+{
+    if (p.irreversible || p.prec > 8 || p.num_levels == 0) return false;
+    double bound = (double)(1u << p.prec) * 4.0;
+    for (uint32_t l = 1; l < p.num_levels; ++l) bound *= 2.25;
+    return bound + 8.0 * p.num_levels < 32767.0;
+}
+
+bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l)
+{
+    if (p.sgnd) return false;                        // (the packed unpacking is written for unsigned pixels)
+    double m = (double)(1u << p.prec);
+    for (uint32_t i = 0; i < l; ++i) m = m * 2.25 + 4.0;
+    return 8.0 * m + 16.0 < 32767.0;
+}
+
+Route plan_route(const grk_amd_tile_params& p, const RouteIn& in)
+{
+    Route r;
+    r.fused = p.num_levels >= 1 && in.px_align == 0;
+    r.overlap = in.overlap && p.num_levels >= 1 && in.have_side;
+    r.frame_stream = r.overlap && in.pipelining && in.have_side2 && in.on_device && r.fused &&
+                     (in.frame_streams == 2 || (in.frame_streams == 1 && in.samples <= kFrameStreamSamples));
+    r.h16 = in.planes16 && r.fused && planes16_ok(p);
+    return r;
+}
+
+// ---- the shape of a forward DWT level --------------------------------------------------------------------------------------------
+DwtLevelShape plan_dwt_level(const DwtLevelDesc& d)
+{
+    DwtLevelShape s;
+    // (row offsets are 32-bit byte offsets from a plane's first sample: planes of 2^31 samples and more keep the flat addressing)
+    const bool near = (uint64_t)d.m_stride * d.ch < (1ull << 31) && (uint64_t)d.cw * d.ch < (1ull << 31) && (uint64_t)d.in_stride * d.ch < (1ull << 31);
+    // the caller's pixels: planes of the default layout, or interleaved with 1, 3 or 4 samples per pixel (rows at their real pitch);
+    // planar pitches and two-channel pixels go through dwt_level_kernel's strided front end
+    const bool lay = d.px_lay == 0 || (d.px_lay == 2 && (d.px_chan == 1 || d.px_chan == 3 || d.px_chan == 4) && d.px_row * d.ch < (1ull << 31));
+    s.packed = d.h16 && d.pk && !d.irreversible && (d.px | d.py) == 0 && (d.cw & 3u) == 0 && d.cw >= 256u &&
+               d.ch >= 16 && (d.ch & 1u) == 0 && near && lay;
+    s.lanes = s.packed && d.cw <= kPkNarrowCols ? 128u : 256u;
+    s.strip_cols = s.packed ? pk_strip_cols(d.cw, s.lanes) : kDwtStripCols;
+    s.all_fast = (d.px | d.py) == 0 && (d.cw & 1u) == 0 && d.cw >= 4 && d.ch >= 16 && (d.ch & 1u) == 0;
+    const uint32_t row_pairs = (d.ch + d.py + 1) >> 1;        // row pairs on the coordinate grid
+    // (the packed kernel takes levels on the even grid only: d.px is 0 there)
+    s.grid_x = (uint32_t)(((uint64_t)d.cw + d.px + s.strip_cols - 1) / s.strip_cols);
+    s.seg_pairs = row_segment_pairs(s.grid_x, row_pairs, d.zslots, d.pk ? kDwtMinWgsPacked : kDwtMinWgs);
+    s.grid_y = (row_pairs + s.seg_pairs - 1) / s.seg_pairs;
+    return s;
+}
+
+} // namespace grk_amd

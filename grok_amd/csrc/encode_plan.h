@@ -1,0 +1,149 @@
+// grok_amd/csrc/encode_plan.h -- what an encode call works out on the host before it launches anything: K3's block classes, their
+// LDS buffers, the arena and its allocator, which class goes to which stream and when, the call's route, the shape of each forward
+// DWT level.  Plain integer code over a TileGeom: no HIP, no grk_amd_ctx, so that a plain C++ compiler builds it and
+// tests/c/encode_plan_units.cpp steps through it without a GPU.  These numbers set K3's occupancy, the allocator's contention and
+// the streams' overlap.
+#pragma once
+#include "encode_constants.h"
+#include "geometry.h"
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#pragma GCC visibility push(hidden)       // private to the library, like everything in context.h
+namespace grk_amd {
+
+// ---- K3 block classes ------------------------------------------------------------------------------------------------------------
+// K3 block classes, each its own launch: the top resolution's sub-bands (3/4 of all blocks) are final after DWT
+// level 0, so they are coded beside the remaining levels (run_dwt, overlap), the rest after the last level; a third
+// class holds ALL blocks, for when nothing overlaps (one launch, one tail).  The LDS buffers of a launch are sized
+// for what the class's typical block needs (capped, plan_ht_lds) -- the LDS per wave is what fixes the occupancy
+// -- and the blocks that outgrow them, e.g. the few high-Kmax blocks of the low resolutions, go through the fallback
+// launch.  Only with GRK_AMD_LDS_CAP=0 (worst-case buffers, no fallback) are the large-LDS blocks classes of their
+// own, so that they do not cost every block a wave per SIMD.  Few classes on purpose: a launch ends with a tail of
+// long-running waves, and launches on one stream do not overlap (measured: one class per resolution costs 0.15 ms at 8K).
+enum class HtRole : uint8_t { Top, Rest, All, TopSmall, TopBig, RestSmall, RestBig };
+struct HtClassPlan {
+    uint32_t count;                               // blocks of a tile in the class (never 0: an empty class is not listed)
+    uint32_t max_kmax, max_samples, max_quads;    // extents that size the class's worst-case LDS buffers
+    uint32_t cap_kmax;                            // the exponent most of the class's samples have (a tie: the lower one)
+    uint32_t first;                               // the class's first entry in HtClasses::sel
+    HtRole role;
+};
+struct HtClasses {
+    std::vector<uint32_t> sel;                    // per class, the rows of a tile's block table ([comp][block]) it holds, in table order
+    std::vector<HtClassPlan> classes;             // lds_cap: Top, Rest, All; else TopSmall, TopBig, RestSmall, RestBig
+};
+HtClasses plan_ht_classes(const TileGeom& g, uint32_t ncomp, bool lds_cap);
+
+// ---- the LDS buffers of a class ---------------------------------------------------------------------------------------------------
+struct HtLdsPlan { uint32_t ms_words, vlc_words, ms_cap_bits, vlc_cap_bits, stage_bytes; size_t bytes; };   // (the kernels' HtLds + the launch's dynamic LDS)
+// LDS words of a launch whose largest block has `samples` samples in `quads` quads and exponent kmax
+// capped = false: the worst case (m_n <= U_q <= Kmax + 2 inside the contract; cwd <= 7, UVLC prefix <= 3, suffix <= 5
+// bits per quad).  capped = true: what real content needs with room to spare -- reversible: 8 bits per sample on
+// average for 8-bit content (Kmax <= 11), Kmax - 3 beyond; quantised (irreversible) coefficients: 8 bits whatever the
+// exponent (the default step sizes leave ~3 bits per sample of a 16-bit image); 10 VLC bits per quad.
+HtLdsPlan ht_lds_layout(uint32_t samples, uint32_t quads, uint32_t kmax, bool capped, bool irrev);
+inline size_t ht_lds_bytes(uint32_t samples, uint32_t quads, uint32_t kmax) { return ht_lds_layout(samples, quads, kmax, false, false).bytes; }
+size_t ht_waves_per_cu(size_t lds_bytes);          // waves of K3 a CU holds with that much LDS each
+// capped LDS when that buys occupancy (there is a fallback list and more waves fit a CU), else worst-case buffers
+struct HtClassLds { HtLdsPlan full, cap; bool use_cap; };
+HtClassLds plan_ht_lds(uint32_t max_samples, uint32_t max_quads, uint32_t max_kmax, uint32_t cap_kmax, bool irrev, bool have_fallback);
+
+// ---- the arena and its allocator ---------------------------------------------------------------------------------------------------
+struct HtArenaPlan {
+    uint32_t regions;                  // allocation regions in use (a power of two <= kHtAllocRegions): block i allocates from region i & (regions - 1)
+    uint32_t chunk;                    // bytes a region takes from the shared cursor at a time
+    size_t   worst_block;              // the largest block the classes can produce
+    uint64_t arena_bytes;
+    uint64_t ovf_entries;              // entries of the fallback list (every block is in two classes)
+    uint32_t ovf_base[kHtMaxClasses];  // each class's first entry there
+};
+HtArenaPlan plan_ht_arena(uint64_t nblocks, uint64_t raw_bytes, uint32_t ntiles, const std::vector<HtClassPlan>& classes);
+
+// ---- which class goes to which stream, and when ------------------------------------------------------------------------------------
+// The points of a call at which K3 launches are queued: run_dwt after level 0 and after the last level, then run_ht
+enum class HtPoint : uint8_t { AfterLevel0, AfterLastLevel, RunHt };
+enum class HtStream : uint8_t { NotHere, Main, Side, Side2 };
+struct HtScheduleRow { HtRole role; bool overlapped; int8_t pipelined /* -1: either */; HtPoint at; HtStream to; };
+// Not overlapped: one launch of every block where there is such a class (the roles Top and Rest exist only beside All), else class
+// by class.  Overlapped: after level 0 the top resolution's sub-bands are final: its code-blocks (3/4 of all) are coded on
+// low-priority side streams while the remaining levels -- short, latency-bound launches that are the critical path -- run on the
+// main stream.  After the last level the rest follows: small-LDS class on the main stream (run_ht) beside the tail of the top
+// resolution, large-LDS class on the second side stream, so that the launches' tails overlap -- unless consecutive encodes are
+// pipelined: then the main stream carries nothing but the DWT chain, so that the next encode's level 0 starts as early as possible,
+// and every K3 launch queues on a side stream (the rest's tail then overlaps the top class's).
+inline constexpr HtScheduleRow kHtSchedule[] = {
+    {HtRole::All,       false, -1, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::TopSmall,  false, -1, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::TopBig,    false, -1, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::RestSmall, false, -1, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::RestBig,   false, -1, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::Top,       true,  -1, HtPoint::AfterLevel0,    HtStream::Side},
+    {HtRole::TopSmall,  true,  -1, HtPoint::AfterLevel0,    HtStream::Side},
+    {HtRole::TopBig,    true,  -1, HtPoint::AfterLevel0,    HtStream::Side2},
+    {HtRole::RestBig,   true,  -1, HtPoint::AfterLastLevel, HtStream::Side2},
+    {HtRole::Rest,      true,   0, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::RestSmall, true,   0, HtPoint::RunHt,          HtStream::Main},
+    {HtRole::Rest,      true,   1, HtPoint::AfterLastLevel, HtStream::Side2},
+    {HtRole::RestSmall, true,   1, HtPoint::AfterLastLevel, HtStream::Side2},
+};
+// one_level: L == 1, level 0 is the last level as well -- AfterLevel0 then answers for both points and AfterLastLevel is not asked
+HtStream ht_class_stream(HtRole role, bool overlapped, bool pipelined, HtPoint at, bool one_level);
+
+// ---- the call's route ----------------------------------------------------------------------------------------------------------------
+// 16-bit planes are safe when no coefficient of any level can leave int16.  Bound (5/3, L1 norms of the analysis
+// filters: low-pass 1.5, high-pass 2 per dimension; RCT chroma is one bit wider than the pixels): the LL of level l is
+// below M * 2.25^l, a detail band of level l below 4 * M * 2.25^(l-1), with M = 2^prec the largest input magnitude.
+bool planes16_ok(const grk_amd_tile_params& p);
+// Level l of such a tile on PACKED int16 pairs (kernels_dwt.hip, strip_pk): every intermediate of the 2-D lifting step has to
+// stay inside 16 bits as well.  With M the largest magnitude entering the level (2^prec after DC shift and RCT, times the
+// low-pass gain 1.5 x 1.5 per level before, plus rounding), the largest is the horizontal update's sum of two high-pass
+// values of a vertically high-pass row: 2 x 2 x 2M each, 8M + 2 in all.
+bool pk16_level_ok(const grk_amd_tile_params& p, uint32_t l);
+struct RouteIn {
+    bool overlap, pipelining; int frame_streams; bool planes16;    // the context's settings (grk_amd_ctx)
+    bool have_side, have_side2;                                    // ... and whether it has its side streams
+    bool on_device;                                                // the caller's pixels are device memory
+    uint32_t px_align;                                             // the low two bits of the (device) pixel pointer
+    uint64_t samples;                                              // nplanes * plane_elems
+};
+struct Route {
+    bool fused;          // with at least one DWT level, level 0 consumes the pixels itself and the int32 ingest planes (4 bytes per
+                         // sample written and read back) never exist
+    bool overlap;        // K3 of the top resolution beside the remaining levels
+    bool frame_stream;   // the whole frame on one side stream.  Device-resident pixels only: the staging buffer of host pixels is
+                         // filled on the main stream, which must then carry level 0; and the fused level 0: the stand-alone ingest
+                         // writes planes that are not part of a buffer set
+    bool h16;            // 8-bit reversible content: int16 LL / Mallat planes between K2 and K3 (half the bytes written and read
+                         // back); needs the fused level 0 (the stand-alone ingest kernel writes int32 planes)
+};
+Route plan_route(const grk_amd_tile_params& p, const RouteIn& in);
+
+// ---- the shape of a forward DWT level --------------------------------------------------------------------------------------------
+struct DwtLevelDesc {                  // (the fields of DwtLevelArgs the shape depends on)
+    uint32_t cw, ch, px, py;
+    uint32_t in_stride, m_stride;
+    bool h16, pk, irreversible;
+    uint32_t px_lay, px_chan; uint64_t px_row;
+    uint32_t zslots;                   // workgroups along z: planes, or for the fused level 0 tiles (x components when there is no MCT triple)
+};
+struct DwtLevelShape {
+    bool packed;                       // the level shape dwt53_pk_kernel takes
+    uint32_t lanes;                    // threads of a workgroup: 128 or 256
+    uint32_t strip_cols;               // output columns a workgroup owns
+    bool all_fast;                     // (what dwt_level_kernel calls `even`: every strip of the level takes a FAST path)
+    uint32_t seg_pairs;                // row pairs per workgroup
+    uint32_t grid_x, grid_y;           // strips, row segments
+};
+DwtLevelShape plan_dwt_level(const DwtLevelDesc& d);
+// row pairs per workgroup of a DWT level: halved from 64 (to 8 at the least) while strips x row segments x z slots stay below min_wgs
+inline uint32_t row_segment_pairs(uint64_t strips, uint32_t row_pairs, uint32_t zslots, uint32_t min_wgs)
+{
+    uint32_t seg = 64;
+    while (seg > 8 && strips * ((row_pairs + seg - 1) / seg) * zslots < min_wgs) seg >>= 1;
+    return seg;
+}
+
+} // namespace grk_amd
+#pragma GCC visibility pop

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include "geometry.h"
 #include "decode_constants.h"
+#include "encode_constants.h"
+#include "encode_plan.h"
 
 namespace grk_amd {
 
@@ -54,8 +56,9 @@ struct DwtLevelArgs {
     uint32_t px_lay, px_chan, px_xstep;
     uint64_t px_row, px_kstep, px_tile;
 };
-hipError_t launch_dwt_level(const DwtLevelArgs& a, hipStream_t s);
-hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s);
+// sh: the level's shape (plan_dwt_level, encode_plan.h) -- which kernel, its strips and row segments; a.seg_pairs = sh.seg_pairs
+hipError_t launch_dwt_level(const DwtLevelArgs& a, const DwtLevelShape& sh, hipStream_t s);
+hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, const DwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s);
 
 // ---- K3: HT cleanup encoder, one wavefront per code-block (kernels_ht.hip) -------------------
 struct HtBlockDesc {        // one per code-block of a tile-component set (all comps of one tile)
@@ -66,7 +69,6 @@ struct HtBlockDesc {        // one per code-block of a tile-component set (all c
     uint8_t  pad;
     float    inv_step;      // 1/stepsize (irreversible)
 };
-constexpr uint32_t kHtMaxClasses = 24;      // (resolution, LDS need): up to 10 levels + 1, two each
 struct HtClass {
     const uint32_t* sel;      // device: indices (within a tile) of the blocks of this class; nullptr = all blocks in order
     uint32_t count;
@@ -94,19 +96,6 @@ struct HtArgs {
     const uint32_t* vlc_tab;      // the CxtVLC encode table on the device (set by launch_ht_classes)
     int irreversible;
 };
-size_t ht_lds_bytes(uint32_t samples, uint32_t quads, uint32_t kmax);
-// r03: 64 region words and 64 KiB chunks (r01 / r02: 16 and 256 KiB -- the same 4 MiB of slack at most).  An atomic on a region word
-// executes at the memory side, one after the other per word, and a block coder waits for its answer: with 16 words the round trip
-// was 10.8 % of K3's time (counters of a build that stops behind it), with 64 the 8K frame's K3 takes 0.30 instead of 0.315 ms and
-// the pipelined step 0.422 instead of 0.437 (128 / 256 words: the same; two words: 0.77 ms)
-#ifndef GRK_HT_ALLOC_REGIONS
-#define GRK_HT_ALLOC_REGIONS 64
-#endif
-constexpr uint32_t kHtAllocRegions = GRK_HT_ALLOC_REGIONS;           // region words available; a launch uses region_mask + 1 of them
-constexpr uint32_t kHtAllocChunk = 64u << 10;      // bytes a region takes from the shared cursor at a time (> twice the largest block)
-constexpr uint32_t kHtAllocChunkSmall = 32u << 10; // ... in a job of few blocks (the slack of half-used chunks counts there)
-constexpr size_t   kHtAllocBytes = 256u * (1u + kHtAllocRegions);   // 32 status / cursor / class words, then one 256-byte line per region word
-
 // the allocator's initial state, written by `nthreads` lanes of one workgroup (ht_alloc_init_kernel; the fused level 0 of a pipelined
 // encode): [0] status flags, [1] cursor (bytes), [2 + class] blocks handed to the fallback launch = 0; every region word "chunk full"
 // so that the first allocation refills -- the start field holds a value no real chunk has, otherwise waves waiting for the refill
@@ -122,8 +111,6 @@ hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hip
 // sum of q^2 over each block of the planes an encode left (kernels_ingest.hip: the rate-control hook)
 hipError_t launch_block_energy(const void* mallat, int h16, int irreversible, uint32_t stride, uint64_t pitch, const HtBlockDesc* blocks,
                                uint32_t blocks_per_tile, uint32_t ncomp, uint64_t nblocks, unsigned long long* out, hipStream_t s);
-uint32_t   dwt_strip_cols();      // output columns a K2 workgroup owns
-uint32_t   dwt_level_strip_cols(const DwtLevelArgs& a);   // ... for this level (the packed 5/3 kernel's strips are wider)
 uint32_t   idwt_strip_pairs();    // coefficient pairs a K6 workgroup owns
 
 // ---- K5: HT cleanup decoder + dequantisation (kernels_htdec.hip) --------------------------------

@@ -46,7 +46,7 @@ constexpr int   kCols     = 2 * kThreads;      // columns staged per line
 constexpr int   kHalo     = 4;                 // columns each side
 // Output columns per strip.  At most kCols - 2 * kHalo = 504; 448 makes a strip 224 output pairs = 7 x 128 bytes of
 // every sub-band row, so each wave's stores cover whole, aligned cache lines.
-constexpr int   kOutCols  = 448;
+constexpr int   kOutCols  = (int)kDwtStripCols;      // (448)
 constexpr int   kOutPairs = kOutCols / 2;
 static_assert(kOutCols <= kCols - 2 * kHalo && kOutCols % 2 == 0, "strip does not fit the staged line");
 
@@ -79,7 +79,7 @@ struct V97 {
 };
 
 // ---- the same on PAIRS of int16 in one register (pk16.h); the host vouches for the range level by level
-//      (encode.hip: pk16_level_ok) ------------------------------------------------------------------------------------
+//      (encode_plan.cpp: pk16_level_ok) ------------------------------------------------------------------------------------
 struct V53pk {
     pk16 xe, dp;
     __device__ __forceinline__ void init(pk16 x_even) { xe = x_even; dp = (pk16)(0); }
@@ -127,7 +127,7 @@ __device__ __forceinline__ void h97(const float* w, float& s, float& d, float in
 //   through the transform side by side, so the int32 ingest planes are never written or read
 //   (saves 8 of the 8 + b_in + 4 bytes per sample that K1 + level 0 move separately).
 // H16 (reversible only): the planes this level reads (PX = 0) and writes hold int16 coefficients -- half the bytes
-//   of the int32 working type; the caller guarantees the range (encode.hip: planes16_ok).
+//   of the int32 working type; the caller guarantees the range (encode_plan.cpp: planes16_ok).
 // GEN = false: the instance for levels the launcher knows to be even (on the origin, even width >= 4, even height >= 16), whose
 //   every strip takes a FAST path -- without the general path in the kernel the three-component 9/7 level 0 needs 83 registers
 //   instead of 124 (the 5/3 one 84 instead of 99): five waves per SIMD, and room on a SIMD whose other waves are the block
@@ -451,22 +451,15 @@ __global__ __launch_bounds__(kThreads) void dwt_level_kernel(DwtLevelArgs a)
 //  * addresses.  Buffer descriptors per plane + scalar row offset + a constant 32-bit lane offset: no vector
 //    instruction goes into an address;
 //  * latency.  Rows are fetched two steps ahead.
-constexpr int kPkLaneCols = 4;
+// (kPkLaneCols = 4 columns per lane: encode_constants.h)
 // the rows are read once: non-temporal loads (cache policy bit 1 on gfx950) keep them from pushing the block coder's tables and
 // streams out of the caches it shares with this kernel in the pipelined encode (measured r03: period 0.49 -> 0.47 ms, alone unchanged;
 // non-temporal STORES made this kernel 10 % slower)
 constexpr int kPkLoadAux = 2;
 // NT lanes per workgroup: 256 (strips of up to 960 columns), or 128 -- half the footprint (two waves, 12 KiB of LDS with three
-// components): the better fit for narrow levels (pk_nt below)
+// components): the better fit for narrow levels (kPkNarrowCols, encode_constants.h)
 constexpr int kPkHalo     = kPkLaneCols;                   // one lane's worth each side (the stencil needs 2 left, 1 right)
-// The strips of a level share its width evenly, in multiples of 64 columns (64 bytes of every sub-band row); at most nt - 2
-// lanes of four columns (one halo lane each side): 960 columns for 256 lanes, 448 for 128
-__host__ __device__ inline uint32_t pk_strip_cols(uint32_t cw, uint32_t nt)
-{
-    const uint32_t most = ((nt - 2u) * kPkLaneCols) & ~63u;
-    const uint32_t n = (cw + most - 1) / most;
-    return min(most, ((cw + n - 1) / n + 63u) & ~63u);
-}
+// (the strips of a level: pk_strip_cols, encode_constants.h)
 
 // CH (PX = 1): 0 = the default pixel layout, component planes; 1, 3, 4 = pixel-interleaved with CH samples per pixel in memory
 //   (DwtLevelArgs::px_lay = 2).  A lane's four columns are then 4 CH contiguous bytes: ONE load of CH dwords per row for all NC
@@ -690,33 +683,12 @@ __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
 
 } // namespace
 
-uint32_t dwt_strip_cols() { return kOutCols; }
-
-// the level shape dwt53_pk_kernel takes
-static bool dwt_level_is_pk(const DwtLevelArgs& a)
+hipError_t launch_dwt_level(const DwtLevelArgs& a, const DwtLevelShape& sh, hipStream_t s)
 {
-    // (row offsets are 32-bit byte offsets from a plane's first sample: planes of 2^31 samples and more keep the flat addressing)
-    const bool near = (uint64_t)a.m_stride * a.ch < (1ull << 31) && (uint64_t)a.cw * a.ch < (1ull << 31) && (uint64_t)a.in_stride * a.ch < (1ull << 31);
-    // the caller's pixels: planes of the default layout, or interleaved with 1, 3 or 4 samples per pixel (rows at their real pitch);
-    // planar pitches and two-channel pixels go through dwt_level_kernel's strided front end
-    const bool lay = a.px_lay == 0 || (a.px_lay == 2 && (a.px_chan == 1 || a.px_chan == 3 || a.px_chan == 4) && a.px_row * a.ch < (1ull << 31));
-    return a.h16 && a.pk && !a.irreversible && (a.px | a.py) == 0 && (a.cw & 3u) == 0 && a.cw >= 256u &&
-           a.ch >= 16 && (a.ch & 1u) == 0 && near && lay;
-}
-// 256 lanes for wide levels (8K level 0: 127 us against 138 with 128 lanes), 128 for narrow ones, whose strips would leave half of
-// 256 lanes idle (64 tiles of 1024^2: levels 0-2 238 -> 203 us)
-static uint32_t pk_nt(const DwtLevelArgs& a) { return a.cw <= 2048u ? 128u : 256u; }
-uint32_t dwt_level_strip_cols(const DwtLevelArgs& a) { return dwt_level_is_pk(a) ? pk_strip_cols(a.cw, pk_nt(a)) : (uint32_t)kOutCols; }
-
-hipError_t launch_dwt_level(const DwtLevelArgs& a, hipStream_t s)
-{
-    const uint32_t sh = (a.ch + a.py + 1) >> 1;
-    dim3 grid((a.cw + a.px + kOutCols - 1) / kOutCols, (sh + a.seg_pairs - 1) / a.seg_pairs, a.nplanes);
+    dim3 grid(sh.grid_x, sh.grid_y, a.nplanes);
     dim3 block(kThreads);
-    if (dwt_level_is_pk(a)) {
-        const uint32_t sc = pk_strip_cols(a.cw, pk_nt(a));
-        grid.x = (a.cw + sc - 1) / sc;
-        if (pk_nt(a) == 128) hipLaunchKernelGGL((dwt53_pk_kernel<1, 0, 128>), grid, dim3(128), 0, s, a);
+    if (sh.packed) {
+        if (sh.lanes == 128) hipLaunchKernelGGL((dwt53_pk_kernel<1, 0, 128>), grid, dim3(128), 0, s, a);
         else                 hipLaunchKernelGGL((dwt53_pk_kernel<1, 0, 256>), grid, block, 0, s, a);
         return hipGetLastError();
     }
@@ -731,25 +703,20 @@ hipError_t launch_dwt_level(const DwtLevelArgs& a, hipStream_t s)
 
 // Level 0 straight from the pixels. `a` describes level 0 (cw x ch = tile size, in/in_stride unused);
 // a.nplanes is ignored: the grid covers ntiles x (MCT triple | every component on its own).
-hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s)
+hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, const DwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s)
 {
-    const uint32_t sh = (a0.ch + a0.py + 1) >> 1;
     dim3 block(kThreads);
     auto go = [&](uint32_t comp0, uint32_t zdiv, int nc) {
         DwtLevelArgs a = a0;
         a.comp0 = comp0; a.zdiv = zdiv; a.ncomp = ncomp;
         if (comp0 != 0) a.alloc_reset = nullptr;             // (the first launch resets the allocator)
-        dim3 grid((a.cw + a.px + kOutCols - 1) / kOutCols, (sh + a.seg_pairs - 1) / a.seg_pairs, ntiles * zdiv);
-        // (what the kernel calls `even`: every strip of the level takes a FAST path)
-        const bool all_fast = (a.px | a.py) == 0 && (a.cw & 1u) == 0 && a.cw >= 4 && a.ch >= 16 && (a.ch & 1u) == 0;
-#define GRK_L0(F97, NC, PX) do { if (all_fast) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, false, false>), grid, block, 0, s, a); \
+        dim3 grid(sh.grid_x, sh.grid_y, ntiles * zdiv);
+#define GRK_L0(F97, NC, PX) do { if (sh.all_fast) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, false, false>), grid, block, 0, s, a); \
                                  else hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX>), grid, block, 0, s, a); } while (0)
         const int px = a.px_bytes == 1 ? 1 : 2;
         if (a.px_lay != 0) {               // a layout of the caller's: the interleaved packed instances, else the strided front end
-            if (!a.irreversible && px == 1 && dwt_level_is_pk(a)) {
-                const uint32_t sc = pk_strip_cols(a.cw, pk_nt(a));
-                grid.x = (a.cw + sc - 1) / sc;
-#define GRK_PKI(NC, CH) do { if (pk_nt(a) == 128) hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 128, CH>), grid, dim3(128), 0, s, a); \
+            if (!a.irreversible && px == 1 && sh.packed) {
+#define GRK_PKI(NC, CH) do { if (sh.lanes == 128) hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 128, CH>), grid, dim3(128), 0, s, a); \
                              else hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 256, CH>), grid, block, 0, s, a); } while (0)
                 if (a.px_chan == 1) GRK_PKI(1, 1);
                 else if (a.px_chan == 3) { if (nc == 3) GRK_PKI(3, 3); else GRK_PKI(1, 3); }
@@ -773,17 +740,15 @@ hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, uint32_t ntiles, uint
         if (a.irreversible) {
             if (nc == 3) { if (px == 1) GRK_L0(true, 3, 1); else GRK_L0(true, 3, 2); }
             else         { if (px == 1) GRK_L0(true, 1, 1); else GRK_L0(true, 1, 2); }
-        } else if (px == 1 && dwt_level_is_pk(a)) {
-            const uint32_t sc = pk_strip_cols(a.cw, pk_nt(a));
-            grid.x = (a.cw + sc - 1) / sc;
-            if (pk_nt(a) == 128) {
+        } else if (px == 1 && sh.packed) {
+            if (sh.lanes == 128) {
                 if (nc == 3) hipLaunchKernelGGL((dwt53_pk_kernel<3, 1, 128>), grid, dim3(128), 0, s, a);
                 else         hipLaunchKernelGGL((dwt53_pk_kernel<1, 1, 128>), grid, dim3(128), 0, s, a);
             } else {
                 if (nc == 3) hipLaunchKernelGGL((dwt53_pk_kernel<3, 1, 256>), grid, block, 0, s, a);
                 else         hipLaunchKernelGGL((dwt53_pk_kernel<1, 1, 256>), grid, block, 0, s, a);
             }
-        } else if (a.h16 && px == 1) {       // 16-bit planes exist for 8-bit pixels only (encode.hip: planes16_ok)
+        } else if (a.h16 && px == 1) {       // 16-bit planes exist for 8-bit pixels only (encode_plan.cpp: planes16_ok)
             if (nc == 3) hipLaunchKernelGGL((dwt_level_kernel<false, 3, 1, true>), grid, block, 0, s, a);
             else         hipLaunchKernelGGL((dwt_level_kernel<false, 1, 1, true>), grid, block, 0, s, a);
         } else {

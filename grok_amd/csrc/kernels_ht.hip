@@ -417,7 +417,7 @@ __device__ __forceinline__ unsigned long long arena_alloc(unsigned long long* fl
 {
     unsigned long long* word = flagbuf + 32 * (1 + region);
     const unsigned long long n = (bytes + 15u) >> 4;
-    // (a request that does not fit a chunk -- the host sizes chunks at twice the largest block, encode.hip make_ht_args: only a
+    // (a request that does not fit a chunk -- the host sizes chunks at twice the largest block, encode_plan.cpp plan_ht_arena: only a
     //  geometry it did not foresee gets here -- takes its bytes from the shared cursor itself and leaves the region's chunk alone;
     //  handed a fresh chunk it would run past the chunk's end into the next region's)
     if (n > kChunkUnits) return __hip_atomic_fetch_add(flagbuf + 1, n << 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1418,34 +1418,6 @@ static hipError_t upload_tables()
     return hipMemcpyToSymbol(HIP_SYMBOL(g_uvlc), uv, sizeof(uv), 0, hipMemcpyHostToDevice);
 }
 
-// LDS words of a launch whose largest block has `samples` samples in `quads` quads and exponent kmax
-// capped = false: the worst case (m_n <= U_q <= Kmax + 2 inside the contract; cwd <= 7, UVLC prefix <= 3, suffix <= 5
-// bits per quad).  capped = true: what real content needs with room to spare -- reversible: 8 bits per sample on
-// average for 8-bit content (Kmax <= 11), Kmax - 3 beyond; quantised (irreversible) coefficients: 8 bits whatever the
-// exponent (the default step sizes leave ~3 bits per sample of a 16-bit image); 10 VLC bits per quad.
-static void ht_lds_layout(uint32_t samples, uint32_t quads, uint32_t kmax, bool capped, bool irrev, HtLds& L, size_t& bytes)
-{
-    const uint32_t per_sample = !capped ? kmax + 2u : irrev ? std::min(kmax + 2u, 8u) : std::min(kmax + 2u, kmax <= 11u ? 8u : kmax - 3u);
-    const uint32_t ms_bits = samples * per_sample;
-    const uint32_t vlc_bits = quads * (capped ? 10u : 15u) + 4u;
-    L.ms_cap_bits = ms_bits;
-    L.vlc_cap_bits = vlc_bits;
-    L.ms_words = ((ms_bits + 31u) / 32u + 4u + 3u) & ~3u;           // slack: or_bits64 / window reads touch two words beyond;
-    L.vlc_words = ((vlc_bits + 31u) / 32u + 4u + 3u) & ~3u;         // multiples of 4 words: cleared as uint4
-    // behind the raw streams: the UVLC table (64 x 8 bytes) while phase A runs, then the staged VLC bytes (phase B1: the stuffed
-    // bytes of the stream's capacity) in the same place; then 256 MEL bytes.  (A raw stream's windows read up to 65 words past its
-    // end: the two areas are at least 192 words.)
-    L.stage_bytes = std::max<uint32_t>(((vlc_bits / 7u + 16u) + 15u) & ~15u, 512u);
-    bytes = (size_t)(L.ms_words + L.vlc_words) * 4u + L.stage_bytes + 256u;
-}
-
-size_t ht_lds_bytes(uint32_t samples, uint32_t quads, uint32_t kmax)
-{
-    HtLds L{}; size_t n;
-    ht_lds_layout(samples, quads, kmax, false, false, L, n);
-    return n;
-}
-
 static hipError_t ensure_tables(const uint32_t** tab = nullptr)
 {
     int dev = 0;
@@ -1486,15 +1458,12 @@ hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hip
     for (uint32_t k = first; k < last && k < a.num_classes; ++k) {
         const HtClass& c = a.classes[k];
         if (c.count == 0) continue;
-        // capped LDS when that buys occupancy (waves per CU = 160 KiB / LDS per wave, at most 32), else worst-case buffers
-        HtLds full{}, cap{};
-        size_t shmem_full, shmem_cap;
-        ht_lds_layout(c.max_samples, c.max_quads, c.max_kmax, false, false, full, shmem_full);
-        ht_lds_layout(c.max_samples, c.max_quads, c.cap_kmax, true, a.irreversible != 0, cap, shmem_cap);
-        auto waves = [](size_t lds) { return std::min<size_t>(32, (160u << 10) / std::max<size_t>(lds, 1)); };
-        const bool use_cap = a.ovf_list && waves(shmem_cap) > waves(shmem_full);
-        const HtLds& L = use_cap ? cap : full;
-        const size_t shmem = use_cap ? shmem_cap : shmem_full;
+        // capped LDS when that buys occupancy, else worst-case buffers (plan_ht_lds, encode_plan.h)
+        const HtClassLds lds = plan_ht_lds(c.max_samples, c.max_quads, c.max_kmax, c.cap_kmax, a.irreversible != 0, a.ovf_list != nullptr);
+        auto kernel_arg = [](const HtLdsPlan& p) { return HtLds{p.ms_words, p.vlc_words, p.ms_cap_bits, p.vlc_cap_bits, p.stage_bytes}; };
+        const bool use_cap = lds.use_cap;
+        const HtLds full = kernel_arg(lds.full), L = kernel_arg(use_cap ? lds.cap : lds.full);
+        const size_t shmem_full = lds.full.bytes, shmem = use_cap ? lds.cap.bytes : lds.full.bytes;
         HtArgs b = a;
         b.sel = c.sel; b.sel_count = c.count;
         b.ovf_base = c.ovf_base;

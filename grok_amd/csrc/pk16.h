@@ -1,6 +1,6 @@
 // grok_amd/csrc/pk16.h -- two int16 in one register (v_pk_add / sub / ashr: one instruction, two samples), gfx950.
 // The 5/3 lifting steps are sums, differences and floor shifts, so while nothing leaves 16 bits the halves are exactly what the
-// 32-bit form computes.  Who vouches for the range: the host for the forward transform (encode.hip pk16_level_ok: 8-bit
+// 32-bit form computes.  Who vouches for the range: the host for the forward transform (encode_plan.cpp pk16_level_ok: 8-bit
 // pixels bound every level), the producers' range flags for the inverse (kernels_htdec.hip / kernels_idwt.hip: every
 // coefficient and every intermediate LL inside +-2047, or status bit 3 and the decode is done again in 32 bits).
 #pragma once

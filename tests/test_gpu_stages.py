@@ -293,7 +293,7 @@ def test_int16_planes_equal_int32_planes(C, H, W, L, sgnd, mct, monkeypatch):
 @pytest.mark.parametrize("cell", [1, 2, 4, 8, 0])
 def test_packed_int16_dwt_at_the_extremes(cell, monkeypatch):
     """Levels whose every intermediate stays inside 16 bits run on packed int16 pairs (kernels_dwt.hip strip_pk;
-    encode.hip pk16_level_ok gives the levels).  Content made to drive the lifting sums as far as 8-bit pixels can --
+    encode_plan.cpp pk16_level_ok gives the levels).  Content made to drive the lifting sums as far as 8-bit pixels can --
     0 / 255 checkerboards with cells of 1, 2, 4, 8 pixels (each resonates with one level), and binary noise (cell 0) -- through
     5 levels, with different phases per component so that the RCT's chroma reaches +-255: blocks identical to the 32-bit
     arithmetic (GRK_AMD_DWT_PK=0) and to the oracle chain."""

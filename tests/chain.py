@@ -20,12 +20,12 @@ def band_index(b):
     return 0 if b.res == 0 else 3 * b.res - 2 + (b.band - 1)
 
 
-def encode_tile_oracle(px, prec, levels, irrev=False, mct=None, sgnd=False):
+def encode_tile_oracle(px, prec, levels, irrev=False, mct=None, sgnd=False, cblk=(6, 6)):
     """px: (C,H,W) pixels (int8/int16 when sgnd). Returns (params, blocks, qcd, table, coded bytes)."""
     Cn, H, W = px.shape
     if mct is None:
         mct = Cn >= 3
-    p = G.TileParams.make(W, H, Cn, prec, levels, irreversible=irrev, mct=mct, sgnd=sgnd)
+    p = G.TileParams.make(W, H, Cn, prec, levels, irreversible=irrev, mct=mct, sgnd=sgnd, cblk=cblk)
     blocks, qcd = G.tile_layout(p)
     planes = [px[c].astype(np.int32) - (0 if sgnd else 1 << (prec - 1)) for c in range(Cn)]
     if irrev:

@@ -86,11 +86,11 @@ def test_egress(C, H, W, prec, irrev):
 
 
 # ---- K5: HT cleanup decoder + dequantisation ------------------------------------------------------
-def _ht_dec_case(W, H, L, C, prec, mode, seed, irrev=False):
+def _ht_dec_case(W, H, L, C, prec, mode, seed, irrev=False, cblk=(6, 6)):
     """Random in-range Mallat planes -> oracle block encoder -> HIP decoder == the planes (rev) /
     == oracle decode (irrev)."""
     rng = np.random.default_rng(seed)
-    p = G.TileParams.make(W, H, C, prec, L, irreversible=irrev)
+    p = G.TileParams.make(W, H, C, prec, L, irreversible=irrev, cblk=cblk)
     blocks, qcd = G.tile_layout(p)
     planes = np.zeros((C, H, W), np.int32)
     table = np.zeros(len(blocks), G.capi.CODED_DTYPE)
@@ -415,7 +415,7 @@ def _gpu_decode_reference_stream(cs, part1):
     p = G.TileParams.make(info["W"], info["H"], info["C"], info["prec"], info["levels"],
                           irreversible=bool(info["irreversible"]), mct=bool(info["mct"]), part1=part1,
                           cblksty=info["cblk_sty"] & 0x3F if part1 else 0, origin=(info["x0"], info["y0"]),
-                          precincts=info["prc"] if info["scod"] & 1 else None)
+                          precincts=info["prc"] if info["scod"] & 1 else None, cblk=(info["cbw"], info["cbh"]))
     blocks, _ = G.tile_layout(p)
     rows, data = J.decode_table(info, blocks, part1)
     table = np.array(rows, dtype=G.capi.CODED_DTYPE)

@@ -14,10 +14,10 @@ from test_oracle_ht_refine import make_block, code_block
 pytestmark = pytest.mark.gpu
 
 
-def _case(W, H, L, C, prec, irrev, seed, passes_of, cap=14):
+def _case(W, H, L, C, prec, irrev, seed, passes_of, cap=14, cblk=(6, 6)):
     """cap: the largest Kmax the cleanup magnitudes are drawn for (None: each block's own)"""
     rng = np.random.default_rng(seed)
-    p = G.TileParams.make(W, H, C, prec, L, irreversible=irrev)
+    p = G.TileParams.make(W, H, C, prec, L, irreversible=irrev, cblk=cblk)
     blocks, qcd = G.tile_layout(p)
     table = np.zeros(len(blocks), G.capi.CODED_DTYPE)
     chunks, segs, want, off = [], [], [], 0

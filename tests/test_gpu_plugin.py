@@ -397,12 +397,12 @@ def test_batch_decompress_through_grok_loader(tmp_path):
 
 @needs_ref
 def test_decode_protocol_declines_outside_the_hot_path():
-    """HT + 9/7 streams (D1), multi-segment code-block styles and multi-tile images are answered with non-zero:
+    """HT + 9/7 streams (D1), multi-segment code-block styles, multi-tile images and code-blocks wider than 64 are answered with non-zero:
     the host keeps its CPU decoder (grk_decompress.cpp:953-955)."""
     assert R.plugin_load() == 1
     assert R.plugin_init(0) == 1
     px = synth.g2(3, 128, 128, 8)
-    for kw in (dict(irrev=1, ht=1), dict(ht=0, cblksty=0x04), dict(TW=64, TH=64)):
+    for kw in (dict(irrev=1, ht=1), dict(ht=0, cblksty=0x04), dict(TW=64, TH=64), dict(cblk=(128, 32))):
         cs, _ = R.encode(px, 8, numres=3, mode=1, **kw)
         got, stages = R.plugin_decompress(cs, 3, 128, 128)
         assert isinstance(got, int) and got != 0

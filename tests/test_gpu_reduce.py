@@ -31,7 +31,7 @@ def _reference_stream(cs, part1):
     p = G.TileParams.make(info["W"], info["H"], info["C"], info["prec"], info["levels"],
                           irreversible=bool(info["irreversible"]), mct=bool(info["mct"]), part1=part1,
                           cblksty=info["cblk_sty"] & 0x3F if part1 else 0, origin=(info["x0"], info["y0"]),
-                          precincts=info["prc"] if info["scod"] & 1 else None)
+                          precincts=info["prc"] if info["scod"] & 1 else None, cblk=(info["cbw"], info["cbh"]))
     blocks, _ = G.tile_layout(p)
     rows, data = J.decode_table(info, blocks, part1)
     qcd = [(e << 11) | m for e, m in info["qcd"]] if info["irreversible"] else []

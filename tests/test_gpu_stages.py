@@ -78,10 +78,10 @@ def test_dwt97_bit_exact(W, H, L):
         assert np.array_equal(got[k], want), "plane %d: max ulp %d" % (k, np.abs(got[k].astype(np.int64) - want).max())
 
 
-def _ht_case(W, H, L, C, prec, mode, seed):
+def _ht_case(W, H, L, C, prec, mode, seed, cblk=(6, 6)):
     """Random Mallat planes -> HIP block bytes vs oracle block bytes."""
     rng = np.random.default_rng(seed)
-    p = G.TileParams.make(W, H, C, prec, L)
+    p = G.TileParams.make(W, H, C, prec, L, cblk=cblk)
     blocks, _ = G.tile_layout(p)
     planes = np.zeros((C, H, W), np.int32)
     for b in blocks:
@@ -249,7 +249,7 @@ def test_encode_irreversible_blocks_vs_oracle(C, H, W, prec, L):
     assert not bad, "blocks differing from the oracle: %s" % bad[:10]
 
 
-@pytest.mark.parametrize("cblk", [(5, 5), (6, 5), (4, 4), (5, 6), (2, 2)])
+@pytest.mark.parametrize("cblk", [(5, 5), (6, 5), (4, 4), (5, 6), (2, 2), (6, 2), (2, 6), (6, 3), (3, 5), (3, 3)])
 def test_gpu_codestream_other_block_sizes_vs_grok(cblk):
     """Code-block sizes other than 64x64 (COD SPcod): the GPU file equals Grok's CPU encode byte for byte."""
     import refharness as R

@@ -31,8 +31,8 @@ def _ctx_with(env):
                 os.environ[k] = v
 
 
-def _tile(rng, W, H, L, bits, prec, keep_fewer=0, irrev=False):
-    p = G.TileParams.make(W, H, 1, prec, L, part1=True, irreversible=irrev, mct=False)
+def _tile(rng, W, H, L, bits, prec, keep_fewer=0, irrev=False, cblk=(6, 6)):
+    p = G.TileParams.make(W, H, 1, prec, L, part1=True, irreversible=irrev, mct=False, cblk=cblk)
     blocks, _ = G.tile_layout(p)
     table = np.zeros(len(blocks), G.capi.CODED_DTYPE)
     chunks, off, want = [], 3, np.zeros((H, W), np.int32)          # (the buffer starts off a dword boundary)

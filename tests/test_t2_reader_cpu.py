@@ -104,6 +104,42 @@ def test_fresh_reference_streams_read_as_j2kparse_reads_them(monkeypatch, ht, ir
         assert (info.layout.x0, info.layout.y0) == offset
 
 
+CBLK_SIZES = [(6, 2), (2, 6), (6, 3), (3, 5), (5, 5), (4, 4), (6, 4), (4, 6), (2, 2), (3, 3)]      # exponents (w, h) of the nominal size
+
+
+@needs_ref
+@pytest.mark.parametrize("ht,sty", [(1, 0), (0, 0), (0, 0x05)])
+@pytest.mark.parametrize("cblk", CBLK_SIZES, ids=lambda c: "%dx%d" % (1 << c[0], 1 << c[1]))
+def test_fresh_reference_streams_of_small_code_blocks_read_as_j2kparse_reads_them(monkeypatch, cblk, ht, sty):
+    """`grk_compress -b w,h`: nominal code-block sizes from 64 x 4 to 4 x 4 -- many blocks per band, tag trees several levels deep,
+    precinct-clipped sizes at the low resolutions"""
+    for prec, Cn, H, W in ((8, 3, 100, 77), (12, 3, 130, 200)):
+        cs = ref_stream(monkeypatch, synth.g2(Cn, H, W, prec), prec, numres=4, ht=ht, cblksty=sty, cblk=(1 << cblk[0], 1 << cblk[1]))
+        info = check_against_j2kparse(cs)
+        assert (info.base.cblk_w_exp, info.base.cblk_h_exp) == cblk
+        blocks, _ = G.tile_layout(G.layout_tiles(info.layout, info.base)[0])
+        # (the largest band is (W + 1) // 2 x (H + 1) // 2)
+        assert max(b.x1 - b.x0 for b in blocks) == min(1 << cblk[0], (W + 1) // 2) and max(b.y1 - b.y0 for b in blocks) == min(1 << cblk[1], (H + 1) // 2)
+
+
+@needs_ref
+@pytest.mark.parametrize("cblk", [(128, 32), (32, 128), (1024, 4)])
+def test_code_blocks_wider_or_taller_than_64_are_refused(monkeypatch, cblk):
+    cs = ref_stream(monkeypatch, synth.g2(3, 100, 77, 8), 8, numres=4, cblk=cblk)
+    assert j2kparse.parse(cs)["cbw"] == cblk[0].bit_length() - 1 and j2kparse.parse(cs)["cbh"] == cblk[1].bit_length() - 1
+    with pytest.raises(G.ReaderError) as e:
+        G.read_header(cs)
+    assert e.value.code == ERR_UNSUPPORTED and "at most 2^6" in e.value.reason
+
+
+@pytest.mark.parametrize("cblk", [(1, 6), (7, 6), (6, 7), (6, 1)])
+def test_tile_layout_refuses_code_block_exponents_outside_2_to_6(cblk):
+    p = G.TileParams.make(100, 77, 3, 8, 3, cblk=cblk)
+    assert G.lib().grk_amd_tile_num_blocks(p) == ERR_UNSUPPORTED
+    with pytest.raises(ValueError, match=str(ERR_UNSUPPORTED)):
+        G.tile_layout(p)
+
+
 # ---- 2. against the writers ------------------------------------------------------------------------------------------------------
 def oracle_tables(px, prec, L, layout, precincts=None):
     Cn = px.shape[0]

@@ -216,6 +216,10 @@ def lib():
             L.grk_amd_decode_image_launches.argtypes = [vp, i32]
             L.grk_amd_gather_device.argtypes = [vp, vp, u64, vp, u64, vp, u64]
             L.grk_amd_place_tiles_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, u32, u32]
+        if hasattr(L, "grk_amd_set_decode_upsample"):
+            L.grk_amd_set_decode_upsample.argtypes = [vp, i32]
+            L.grk_amd_stream_comp_size.argtypes = [C.POINTER(StreamInfo), u32, C.POINTER(u32), C.POINTER(u32)]
+            L.grk_amd_place_upsampled_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, u32, u32, vp, u32, u32, u32, u32]
         _lib = L
     return _lib
 
@@ -368,6 +372,19 @@ def read_header(cs):
     if rc:
         raise ReaderError("read_header", rc, L.grk_amd_reader_last_error().decode())
     return info
+
+
+def stream_comp_sizes(info):
+    """[(w, h)] of every component of the image in its own samples (grk_amd_stream_comp_size)"""
+    L = lib()
+    out = []
+    for k in range(info.base.num_comps):
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        rc = L.grk_amd_stream_comp_size(C.byref(info), k, C.byref(w), C.byref(h))
+        if rc:
+            raise ValueError("grk_amd_stream_comp_size failed: %d" % rc)
+        out.append((w.value, h.value))
+    return out
 
 
 def read_packets(cs, info=None, threads=1):
@@ -689,6 +706,22 @@ class Context:
         self._check(self._L.grk_amd_decode_image(self._h, buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "decode_image")
         return out
 
+    def set_decode_upsample(self, on):
+        """decode_image delivers sub-sampled components on the reference grid, W x H each (grk_amd_set_decode_upsample)"""
+        self._check(self._L.grk_amd_set_decode_upsample(self._h, int(bool(on))), "set_decode_upsample")
+
+    def decode_image_planes(self, cs):
+        """Codestream -> one 2-D array per component, each of the component's own size (stream_comp_sizes): what decode_image
+        writes for a stream with sub-sampled components while upsampling is off."""
+        buf = _cs_array(cs)
+        info = read_header(buf)
+        dt = np.uint8 if info.base.prec <= 8 else np.uint16
+        sizes = stream_comp_sizes(info)
+        out = np.zeros(sum(w * h for w, h in sizes), dt)
+        self._check(self._L.grk_amd_decode_image(self._h, buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "decode_image")
+        at = np.concatenate([[0], np.cumsum([w * h for w, h in sizes])])
+        return [out[at[k]:at[k + 1]].reshape(h, w) for k, (w, h) in enumerate(sizes)]
+
     def decode_image_device(self, cs, d_pixels, cap):
         """The same into device memory (asynchronous behind the reader: decode_status joins and reports)."""
         buf = _cs_array(cs)
@@ -702,6 +735,12 @@ class Context:
         m = np.ascontiguousarray(moves, MOVE_DTYPE)
         self._check(self._L.grk_amd_gather_device(self._h, m.ctypes.data if m.size else None, m.size, d_src, int(src_bytes), d_dst,
                                                   int(dst_bytes)), "gather_device")
+
+    def place_upsampled_device(self, d_tiles, nunits, w, h, ncomp, bps, origins, dx, dy, d_image, img_x0, img_y0, img_w, img_h):
+        """origins: [(x, y)] of every unit's first sample in its component; the image area starts at (img_x0, img_y0) of the reference grid"""
+        r = np.ascontiguousarray(origins, np.uint32).reshape(-1)
+        self._check(self._L.grk_amd_place_upsampled_device(self._h, d_tiles, nunits, w, h, ncomp, bps, r.ctypes.data, dx, dy, d_image,
+                                                           img_x0, img_y0, img_w, img_h), "place_upsampled_device")
 
     def place_tiles_device(self, d_tiles, ntiles, w, h, ncomp, bps, rects, d_image, img_w, img_h):
         """rects: [(x, y)] of every tile in the image's planes"""

@@ -104,6 +104,7 @@ struct grk_amd_ctx {
     std::vector<grk_amd_segment> dec_segs;
     grk_amd_pixel_layout enc_layout{};                      // the pixels an encode reads (grk_amd_set_pixel_layout; all zero: the default)
     grk_amd_pixel_layout dec_layout{};                      // the pixels a decode writes (grk_amd_set_decode_pixel_layout)
+    bool dec_upsample = false;                              // grk_amd_decode_image delivers sub-sampled components at W x H (grk_amd_set_decode_upsample)
     uint32_t dec_reduce = 0;                                // decode at 1 / 2^dec_reduce of the size (grk_amd_set_decode_reduce)
     std::vector<uint32_t> red_seg_first;                    // ... the segment list of the blocks that decode keeps (decode_impl, decode.hip)
     std::vector<grk_amd_segment> red_segs;

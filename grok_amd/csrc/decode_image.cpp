@@ -3,7 +3,9 @@
 // travel to the device; the uploaded codestream is then the coded buffer itself -- a block's table row points into it --, with
 // an appendix behind it for the blocks whose bytes come in several pieces (KG gathers those).  The tiles are grouped by geometry
 // as the encoder groups them (image.h: add_unit), every group is one grk_amd_decode_tiles batch into a buffer of its own, and KP
-// puts the group's tiles at their rectangles in the image.
+// puts the group's tiles at their rectangles in the image.  With sub-sampled components the unit is a tile's run of components of
+// one size (image.h: comp_runs), the destination one plane per component of its own size -- or, with grk_amd_set_decode_upsample,
+// the image on the reference grid, where KU takes KP's place.
 #include "context.h"
 #include "image.h"
 #include "t2_reader.h"
@@ -11,7 +13,8 @@
 
 namespace {
 
-// what the call sets on the context, put back when it ends
+// what the call sets on the context, put back when it ends (the caller's own switches -- the int16 planes, the pixel layout,
+// grk_amd_set_decode_upsample -- are not among it: they are left as they are)
 struct SavedSettings {
     grk_amd_ctx* c;
     std::vector<uint16_t> qcd; std::vector<float> steps; std::vector<uint32_t> seg_first; std::vector<grk_amd_segment> segs;
@@ -61,6 +64,38 @@ extern "C" int grk_amd_gather_device(grk_amd_ctx* c, const grk_amd_tp_segment* m
     return run_gather(c, moves, num_moves, src_base, dst_base);
 }
 
+extern "C" int grk_amd_set_decode_upsample(grk_amd_ctx* c, int on)
+{
+    if (!c) return GRK_AMD_ERR_INVALID;
+    c->dec_upsample = on != 0;
+    return GRK_AMD_OK;
+}
+
+extern "C" int grk_amd_place_upsampled_device(grk_amd_ctx* c, const void* tiles, uint32_t nunits, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                                              const uint32_t* origins, uint32_t dx, uint32_t dy, void* image, uint32_t img_x0, uint32_t img_y0,
+                                              uint32_t img_w, uint32_t img_h)
+{
+    if (!c || !tiles || !origins || !image || !nunits || !w || !h || !ncomp || ncomp > 65535 || nunits > 65535 || !bps || bps > 4 || !dx || !dy ||
+        dx > 255 || dy > 255 || !img_w || !img_h || (uint64_t)img_x0 + img_w > 0xFFFFFFFFull || (uint64_t)img_y0 + img_h > 0xFFFFFFFFull)
+        return GRK_AMD_ERR_INVALID;
+    // every sample's footprint starts inside the image area (it may end beyond it: clipped)
+    for (uint32_t u = 0; u < nunits; ++u) {
+        const uint64_t fx0 = (uint64_t)origins[2 * u] * dx, fx1 = ((uint64_t)origins[2 * u] + w - 1) * dx;
+        const uint64_t fy0 = (uint64_t)origins[2 * u + 1] * dy, fy1 = ((uint64_t)origins[2 * u + 1] + h - 1) * dy;
+        if (fx0 < img_x0 || fx1 >= (uint64_t)img_x0 + img_w || fy0 < img_y0 || fy1 >= (uint64_t)img_y0 + img_h)
+            return fail(c, GRK_AMD_ERR_INVALID, "a footprint outside the image");
+    }
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    HIP_TRY(c, c->img_rects.ensure((size_t)nunits * 8), "alloc places");
+    HIP_TRY(c, hipMemcpy(c->img_rects.p, origins, (size_t)nunits * 8, hipMemcpyHostToDevice), "upload places");
+    const UpsampleArgs a{(const uint8_t*)tiles, nunits, w, h, ncomp, bps, (const uint32_t*)c->img_rects.p, dx, dy, (uint8_t*)image, img_x0, img_y0, img_w, img_h,
+                         bps, (uint64_t)img_w * bps, (uint64_t)img_w * img_h * bps};
+    HIP_TRY(c, launch_t2dec_upsample(a, c->stream), "launch upsampling placement");
+    ++c->img_launches[1];
+    return GRK_AMD_OK;
+}
+
 extern "C" int grk_amd_place_tiles_device(grk_amd_ctx* c, const void* tiles, uint32_t ntiles, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
                                           const uint32_t* rects, void* image, uint32_t img_w, uint32_t img_h)
 {
@@ -88,25 +123,53 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
     int rc = read_stream_header(cs, len, info, why);
     if (rc) return fail(c, rc, why.c_str());
     const uint32_t nc = info.base.num_comps, bps = (info.base.prec + 7u) / 8u, nt = info.num_tiles;
-    for (uint32_t k = 0; k < nc; ++k)
-        if (info.comp_dx[k] != 1 || info.comp_dy[k] != 1) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "sub-sampled components");
+    bool sub = false;
+    for (uint32_t k = 0; k < nc; ++k) sub = sub || info.comp_dx[k] != 1 || info.comp_dy[k] != 1;
+    const bool up = sub && c->dec_upsample;
+    if (sub && !up) {       // (components of different sizes have no interleaved form, and each plane is tight: as grk_amd_encode_image_subsampled)
+        const grk_amd_pixel_layout& l = c->dec_layout;
+        if (l.interleaved || l.channels || l.row_pitch || l.plane_pitch || l.tile_pitch)
+            return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a decode pixel layout for sub-sampled components without upsampling (grk_amd_set_decode_upsample)");
+    }
+    // the units of decoding: a tile's runs of components of one size (without sub-sampling: the tile)
+    const std::vector<CompRun> runs = comp_runs(nc, info.base.mct != 0, info.comp_dx, info.comp_dy);
+    if (info.base.mct && !runs[0].mct) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "the colour transform across components of different size");
     const uint64_t W = info.layout.x1 - info.layout.x0, H = info.layout.y1 - info.layout.y0;
-    // the image in the context's decode layout (grk_amd_set_decode_pixel_layout: row_pitch the image's; the default: tight planes)
+    // the image in the context's decode layout (grk_amd_set_decode_pixel_layout: row_pitch the image's; the default: tight planes) ...
     PixelLayout ipx;
     {
         const char* lwhy = "";
         if (W >> 32 || H >> 32 || !resolve_pixel_layout(info.base, &c->dec_layout, (uint32_t)W, (uint32_t)H, 1, ipx, &lwhy)) return fail(c, GRK_AMD_ERR_INVALID, lwhy);
     }
-    const uint64_t total = ipx.bytes;
-    if (total > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "the image does not fit `cap`");
-    // the tiles, grouped by geometry
-    std::vector<grk_amd_tile_params> tp(nt);
-    UnitGroups g;
-    for (uint32_t t = 0; t < nt; ++t) {
-        rc = grk_amd_layout_tile(&info.layout, &info.base, t, &tp[t]);
-        if (!rc) rc = add_unit(g, tp[t]);
-        if (rc) return fail(c, rc, "a tile's geometry");
+    // ... or, sub-sampled components as they are: component k's plane of its own size, tight, the planes back to back
+    struct Plane { uint64_t at, w, h, x0, y0; };
+    std::vector<Plane> plane(nc);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < nc; ++k) {
+        const uint64_t dx = info.comp_dx[k], dy = info.comp_dy[k];
+        const uint64_t x0 = (info.layout.x0 + dx - 1) / dx, y0 = (info.layout.y0 + dy - 1) / dy;
+        plane[k] = Plane{total, ((uint64_t)info.layout.x1 + dx - 1) / dx - x0, ((uint64_t)info.layout.y1 + dy - 1) / dy - y0, x0, y0};
+        total += plane[k].w * plane[k].h * bps;
     }
+    if (!sub || up) total = ipx.bytes;
+    if (total > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "the image does not fit `cap`");
+    // the units, grouped by geometry
+    const uint32_t nr = (uint32_t)runs.size(), nu = nt * nr;
+    std::vector<grk_amd_tile_params> tp(nu);                  // [tile][run]
+    UnitGroups g;
+    for (uint32_t t = 0; t < nt; ++t)
+        for (uint32_t r = 0; r < nr; ++r) {
+            grk_amd_tile_params& p = tp[t * nr + r];
+            if (!sub) rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
+            else {
+                rc = grk_amd_layout_tile_comp(&info.layout, &info.base, info.comp_dx[runs[r].first], info.comp_dy[runs[r].first], t, &p);
+                p.num_comps = (uint16_t)runs[r].count; p.mct = runs[r].mct ? 1 : 0;
+            }
+            if (!rc) rc = add_unit(g, p);
+            if (rc) return fail(c, rc, "a tile's geometry");
+        }
+    // (runs of one geometry -- luma and alpha -- share a group and its batch; they go to different planes: a group's units run by run)
+    for (auto& G : g.members) std::stable_sort(G.begin(), G.end(), [nr](uint32_t a, uint32_t b) { return a % nr < b % nr; });
     const bool ht = !info.base.reserved[0];
     if (ht) {
         // HT blocks are decoded against the band's Kmax of the library's own geometry (ensure_geom), not against the stream's QCD
@@ -137,6 +200,13 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
     const uint64_t coded_bytes = len + tab.appendix_bytes;
     if (coded_bytes > coded_cap) return fail(c, GRK_AMD_ERR_INVALID, "an appendix larger than the codestream");
     rc = check_moves(c, tab.moves.data(), tab.moves.size(), len, tab.appendix_bytes); if (rc) return rc;
+    // a unit's rows in the reader's table: tile after tile, within a tile component after component
+    std::vector<uint64_t> unit_row(nu + 1, 0);
+    for (uint32_t u = 0; u < nu; ++u) {
+        if (u % nr == 0 && unit_row[u] != tab.row_at[u / nr]) return fail(c, GRK_AMD_ERR_INVALID, "the reader's table does not fit the tiles");
+        unit_row[u + 1] = unit_row[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * tp[u].num_comps;
+    }
+    if (unit_row[nu] != tab.rows.size()) return fail(c, GRK_AMD_ERR_INVALID, "the reader's table does not fit the tiles");
     // (from here on the call only queues work; the small tables below are uploaded with blocking copies into buffers that an
     //  earlier call's kernels may still read)
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
@@ -151,9 +221,9 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
         table.clear();
         std::vector<uint32_t> first;
         std::vector<grk_amd_segment> segs;
-        for (uint32_t t : G) {
-            table.insert(table.end(), tab.rows.begin() + tab.row_at[t], tab.rows.begin() + tab.row_at[t + 1]);
-            for (uint64_t i = tab.row_at[t]; want_segs && i < tab.row_at[t + 1]; ++i) {
+        for (uint32_t u : G) {
+            table.insert(table.end(), tab.rows.begin() + unit_row[u], tab.rows.begin() + unit_row[u + 1]);
+            for (uint64_t i = unit_row[u]; want_segs && i < unit_row[u + 1]; ++i) {
                 first.push_back((uint32_t)segs.size());
                 segs.insert(segs.end(), tab.segments.begin() + tab.first_segment[i], tab.segments.begin() + tab.first_segment[i + 1]);
             }
@@ -163,38 +233,83 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
         return grk_amd_set_decode_segments(c, first.data(), segs.data(), (uint32_t)table.size());
     };
     std::vector<grk_amd_coded_block> table;
-    if (nt == 1) {
+    if (nu == 1 && !up) {
         // one tile: decoded straight into the destination (host pixels: grk_amd_decode_tiles repeats a group that leaves the int16
         // planes by itself)
         rc = group_tables(g.members[0], table);
         if (!rc) rc = grk_amd_decode_tiles(c, &tp[0], 1, table.data(), c->img_coded.p, coded_bytes, 1, pixels, pixels_on_device);
         return rc;
     }
+    HIP_TRY(c, c->img_status.ensure(64), "alloc status");
+    if (nt == 1 && !up) {
+        // one tile of several runs: run by run straight into the run's planes; a decode into device pixels leaves its status to
+        // the next one's, so it is kept as for the groups below
+        if (pixels_on_device) HIP_TRY(c, hipMemsetAsync(c->img_status.p, 0, 4, c->stream), "clear status");
+        for (uint32_t r = 0; r < nr; ++r) {
+            rc = group_tables(std::vector<uint32_t>{r}, table); if (rc) return rc;
+            uint8_t* const dst = (uint8_t*)pixels + plane[runs[r].first].at;
+            // (a plane behind planes of odd size may start off the 4-byte alignment the decoder's pixel stores are written for: such a
+            //  run in device memory is decoded beside it and copied)
+            const bool beside = pixels_on_device && ((uintptr_t)dst & 3u);
+            const size_t run_bytes = (size_t)tp[r].tile_w * tp[r].tile_h * tp[r].num_comps * bps;
+            if (beside) HIP_TRY(c, c->img_tiles.ensure(run_bytes), "alloc a run's planes");
+            rc = grk_amd_decode_tiles(c, &tp[r], 1, table.data(), c->img_coded.p, coded_bytes, 1, beside ? c->img_tiles.p : dst, pixels_on_device);
+            if (rc) return rc;
+            if (beside) HIP_TRY(c, hipMemcpyAsync(dst, c->img_tiles.p, run_bytes, hipMemcpyDeviceToDevice, c->stream), "copy a run's planes");
+            if (pixels_on_device)
+                HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->img_status.p, (const unsigned int*)c->flag.p, false, c->stream), "keep status");
+        }
+        if (pixels_on_device)
+            HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->flag.p, (const unsigned int*)c->img_status.p, true, c->stream), "hand over status");
+        return GRK_AMD_OK;
+    }
     void* d_img = pixels;
     if (!pixels_on_device) {
         HIP_TRY(c, c->img_pixels.ensure(total), "alloc the image"); d_img = c->img_pixels.p;
         // (the extent comes back as one copy: what the caller has in a layout's gaps goes up first)
-        if (ipx.lay) { rc = copy_h2d(c, d_img, pixels, total); if (rc) return rc; }
+        if ((!sub || up) && ipx.lay) { rc = copy_h2d(c, d_img, pixels, total); if (rc) return rc; }
     }
-    // the tile decoder writes tight tiles in the same kind of layout; KP places them by rows of whole pixels
-    const uint32_t unit_ch = ipx.lay == 2 ? ipx.channels : nc;
+    // the tile decoder writes tight tiles in the same kind of layout; KP places them by rows of whole pixels.  Runs of sub-sampled
+    // components are decoded as tight planes: KP places them in the components' planes, KU on the reference grid
+    const bool whole_pixels = !sub && ipx.lay == 2;
+    const uint32_t unit_ch = whole_pixels ? ipx.channels : 0;
     struct TileLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~TileLayout() { c->dec_layout = keep; } } tile_layout{c, c->dec_layout};
     {
         grk_amd_pixel_layout tl{};
-        if (ipx.lay == 2) { tl.interleaved = 1; tl.channels = (uint8_t)ipx.channels; tl.fill = c->dec_layout.fill; }
+        if (whole_pixels) { tl.interleaved = 1; tl.channels = (uint8_t)ipx.channels; tl.fill = c->dec_layout.fill; }
         c->dec_layout = tl;
     }
     uint64_t group_bytes = 0;
-    for (const auto& G : g.members) group_bytes = std::max<uint64_t>(group_bytes, (uint64_t)tp[G[0]].tile_w * tp[G[0]].tile_h * unit_ch * bps * G.size());
+    for (const auto& G : g.members)
+        group_bytes = std::max<uint64_t>(group_bytes, (uint64_t)tp[G[0]].tile_w * tp[G[0]].tile_h * (unit_ch ? unit_ch : tp[G[0]].num_comps) * bps * G.size());
     HIP_TRY(c, c->img_tiles.ensure(group_bytes), "alloc a group's tiles");
-    HIP_TRY(c, c->img_status.ensure(64), "alloc status");
-    HIP_TRY(c, c->img_rects.ensure((size_t)nt * 8), "alloc places");
+    HIP_TRY(c, c->img_rects.ensure((size_t)nu * 8), "alloc places");
     {
-        std::vector<uint32_t> rects;                          // group after group
-        for (const auto& G : g.members) for (uint32_t t : G) { rects.push_back(tp[t].tile_x0 - info.layout.x0); rects.push_back(tp[t].tile_y0 - info.layout.y0); }
+        // group after group: where a unit goes in its components' planes -- or, for KU, its first sample in the component
+        std::vector<uint32_t> rects;
+        for (const auto& G : g.members)
+            for (uint32_t u : G) {
+                const Plane& pl = plane[runs[u % nr].first];
+                rects.push_back(tp[u].tile_x0 - (up ? 0u : sub ? (uint32_t)pl.x0 : info.layout.x0));
+                rects.push_back(tp[u].tile_y0 - (up ? 0u : sub ? (uint32_t)pl.y0 : info.layout.y0));
+            }
         HIP_TRY(c, hipMemcpy(c->img_rects.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice), "upload places");
     }
     HIP_TRY(c, hipMemsetAsync(c->img_status.p, 0, 4, c->stream), "clear status");
+    if (up) {
+        // what no footprint covers: the strip left of and above a component's first sample (image origins that are no multiple of
+        // the factor) is 0, the samples beyond num_comps of interleaved pixels are `fill`
+        const uint64_t kstep = ipx.lay == 2 ? bps : ipx.kstep;
+        for (uint32_t k = 0; k < nc; ++k) {
+            const uint32_t zx = (uint32_t)std::min<uint64_t>(W, plane[k].x0 * info.comp_dx[k] - info.layout.x0);
+            const uint32_t zy = (uint32_t)std::min<uint64_t>(H, plane[k].y0 * info.comp_dy[k] - info.layout.y0);
+            uint8_t* const at = (uint8_t*)d_img + k * kstep;
+            HIP_TRY(c, launch_t2dec_fill(FillArgs{at, 0, 0, zx, (uint32_t)H, bps, 0, ipx.xstep, ipx.row}, c->stream), "launch fill");
+            HIP_TRY(c, launch_t2dec_fill(FillArgs{at, zx, 0, (uint32_t)W - zx, zy, bps, 0, ipx.xstep, ipx.row}, c->stream), "launch fill");
+        }
+        for (uint32_t k = nc; ipx.lay == 2 && k < ipx.channels; ++k)
+            HIP_TRY(c, launch_t2dec_fill(FillArgs{(uint8_t*)d_img + k * kstep, 0, 0, (uint32_t)W, (uint32_t)H, bps, ipx.fill, ipx.xstep, ipx.row}, c->stream), "launch fill");
+    }
     size_t rect_at = 0;
     for (const auto& G : g.members) {
         const grk_amd_tile_params& p = tp[G[0]];
@@ -213,10 +328,31 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
             if (rc) return rc;
         }
         HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->img_status.p, (const unsigned int*)c->flag.p, false, c->stream), "keep status");
-        const PlaceArgs a{(const uint8_t*)c->img_tiles.p, (uint32_t)G.size(), p.tile_w, p.tile_h, ipx.lay == 2 ? 1u : nc, ipx.lay == 2 ? unit_ch * bps : bps,
-                          (const uint32_t*)c->img_rects.p + 2 * rect_at, (uint8_t*)d_img, (uint32_t)W, (uint32_t)H, ipx.lay ? ipx.row : 0, ipx.lay == 1 ? ipx.kstep : 0};
-        HIP_TRY(c, launch_t2dec_place(a, c->stream), "launch placement");
-        ++c->img_launches[1];
+        const size_t unit_size = (size_t)p.tile_w * p.tile_h * (unit_ch ? unit_ch : p.num_comps) * bps;
+        for (size_t i0 = 0, i1; i0 < G.size(); i0 = i1) {          // the group's units of one run: one launch into that run's planes
+            for (i1 = i0 + 1; i1 < G.size() && G[i1] % nr == G[i0] % nr;) ++i1;
+            const CompRun& run = runs[G[i0] % nr];
+            const uint8_t* const staged = (const uint8_t*)c->img_tiles.p + i0 * unit_size;
+            const uint32_t* const rects = (const uint32_t*)c->img_rects.p + 2 * (rect_at + i0);
+            const uint32_t count = (uint32_t)(i1 - i0);
+            if (up) {
+                const uint64_t kstep = ipx.lay == 2 ? bps : ipx.kstep;
+                const UpsampleArgs a{staged, count, p.tile_w, p.tile_h, run.count, bps, rects, info.comp_dx[run.first],
+                                     info.comp_dy[run.first], (uint8_t*)d_img + run.first * kstep, info.layout.x0, info.layout.y0, (uint32_t)W, (uint32_t)H,
+                                     ipx.xstep, ipx.row, kstep};
+                HIP_TRY(c, launch_t2dec_upsample(a, c->stream), "launch upsampling placement");
+            } else if (sub) {
+                const Plane& pl = plane[run.first];
+                const PlaceArgs a{staged, count, p.tile_w, p.tile_h, run.count, bps, rects, (uint8_t*)d_img + pl.at,
+                                  (uint32_t)pl.w, (uint32_t)pl.h, 0, 0};
+                HIP_TRY(c, launch_t2dec_place(a, c->stream), "launch placement");
+            } else {
+                const PlaceArgs a{staged, count, p.tile_w, p.tile_h, ipx.lay == 2 ? 1u : nc, ipx.lay == 2 ? unit_ch * bps : bps,
+                                  rects, (uint8_t*)d_img, (uint32_t)W, (uint32_t)H, ipx.lay ? ipx.row : 0, ipx.lay == 1 ? ipx.kstep : 0};
+                HIP_TRY(c, launch_t2dec_place(a, c->stream), "launch placement");
+            }
+            ++c->img_launches[1];
+        }
         rect_at += G.size();
     }
     HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->flag.p, (const unsigned int*)c->img_status.p, true, c->stream), "hand over status");

@@ -229,14 +229,8 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
     const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps;
     const uint32_t bps = (base->prec + 7u) / 8u;
     for (uint32_t c = 0; c < nc; ++c) if (!comp_dx[c] || !comp_dy[c]) return GRK_AMD_ERR_INVALID;
-    struct Run { uint32_t c0, n; };
-    std::vector<Run> runs;
-    for (uint32_t c = 0; c < nc; ++c) {
-        if (!runs.empty() && comp_dx[c] == comp_dx[runs.back().c0] && comp_dy[c] == comp_dy[runs.back().c0]) runs.back().n++;
-        else runs.push_back(Run{c, 1});
-    }
     // (MCT over components of different size: switched off, as the reference does with a warning, CodeStreamCompress.cpp:434-447)
-    const bool mct = base->mct && nc >= 3 && runs[0].n >= 3;
+    const std::vector<CompRun> runs = comp_runs(nc, base->mct != 0, comp_dx, comp_dy);
     // the image's components in `pixels`: component c is ceil(x1 / dx) - ceil(x0 / dx) columns wide, planes back to back
     auto cdiv = [](uint64_t a, uint64_t b) { return (a + b - 1) / b; };
     SourcePlanes src{(const uint8_t*)pixels, bps, {}};
@@ -249,11 +243,11 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
     UnitGroups g;
     for (uint32_t t = 0; t < ntiles; ++t)
         for (uint32_t k = 0; k < runs.size(); ++k) {
-            Unit u{{}, runs[k].c0};
-            int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].c0], comp_dy[runs[k].c0], t, &u.p);
+            Unit u{{}, runs[k].first};
+            int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].first], comp_dy[runs[k].first], t, &u.p);
             if (rc) return rc;
-            u.p.num_comps = (uint16_t)runs[k].n;
-            u.p.mct = (mct && k == 0) ? 1 : 0;
+            u.p.num_comps = (uint16_t)runs[k].count;
+            u.p.mct = runs[k].mct ? 1 : 0;
             units.push_back(u);
             rc = add_unit(g, u.p);
             if (rc) return rc;

@@ -14,6 +14,22 @@ namespace grk_amd {
 // component in the caller's image
 struct Unit { grk_amd_tile_params p; uint32_t c0; };
 
+// The run rule of images with sub-sampled components (SIZ XRsiz / YRsiz), for the encoders, the plugin's tile trees and
+// grk_amd_decode_image alike: consecutive components with equal factors form a run, which is coded and decoded as one unit of
+// `count` components.  mct: the run that starts at component 0 and holds at least three components of an image that signals
+// the colour transform -- the only place where the transform can apply.
+struct CompRun { uint32_t first, count; bool mct; };
+inline std::vector<CompRun> comp_runs(uint32_t num_comps, bool mct, const uint8_t* comp_dx, const uint8_t* comp_dy)
+{
+    std::vector<CompRun> runs;
+    for (uint32_t c0 = 0, n; c0 < num_comps; c0 += n) {
+        n = 1;
+        while (c0 + n < num_comps && comp_dx[c0 + n] == comp_dx[c0] && comp_dy[c0 + n] == comp_dy[c0]) ++n;
+        runs.push_back(CompRun{c0, n, mct && c0 == 0 && n >= 3});
+    }
+    return runs;
+}
+
 // The caller's image: component c's samples start comp[c].at bytes into `px`, in rows of comp[c].w samples, the first of
 // them at (comp[c].x0, comp[c].y0) on the component's grid.  Under a pixel layout (grk_amd_set_pixel_layout; plain_image) rows lie
 // row_pitch bytes apart (0: tight) and, with channels != 0, the components are interleaved: channels samples per pixel in memory

@@ -283,6 +283,25 @@ struct PlaceArgs {
                                                      // placed as ONE component of samples as wide as a pixel
 };
 hipError_t launch_t2dec_place(const PlaceArgs& a, hipStream_t s);
+// KU: placement of sub-sampled components with upsampling to the reference grid.  nunits tile-components groups ("units") of
+// ncomp x h x w samples lie back to back, tight, as for KP; unit u's first sample is sample (origins[2 u], origins[2 u + 1]) of
+// its component.  Sample (i, j) of a component fills its FOOTPRINT [i dx, (i + 1) dx) x [j dy, (j + 1) dy) of the reference grid,
+// clipped to the image area [x0, x0 + img_w) x [y0, y0 + img_h): the footprints, not the tile rectangles, partition the image.
+// The host checked that every footprint starts inside the image area.
+struct UpsampleArgs {
+    const uint8_t* tiles;
+    uint32_t nunits, w, h, ncomp, bps;
+    const uint32_t* origins;
+    uint32_t dx, dy;
+    uint8_t* image;                                  // the first of the unit's components, at the image area's top-left sample
+    uint32_t x0, y0, img_w, img_h;
+    uint64_t xstep, img_row, img_plane;              // bytes between a row's samples, rows, the unit's components in the image
+};
+hipError_t launch_t2dec_upsample(const UpsampleArgs& a, hipStream_t s);
+// `value` into the samples of w x h at (x, y) of one component of such an image: the strip no sample's footprint covers when the
+// image origin is no multiple of a factor, and the samples beyond num_comps of interleaved pixels
+struct FillArgs { uint8_t* image; uint32_t x, y, w, h, bps, value; uint64_t xstep, img_row; };
+hipError_t launch_t2dec_fill(const FillArgs& a, hipStream_t s);
 // *into |= *from (assign: = ) on the stream: a group's decode status into the image's
 hipError_t launch_t2dec_or_status(unsigned int* into, const unsigned int* from, bool assign, hipStream_t s);
 

@@ -4,6 +4,7 @@
 #ifndef GRK_AMD_PLUGIN_INTERNAL_H
 #define GRK_AMD_PLUGIN_INTERNAL_H
 #include "../../include/grk_plugin_abi.h"
+#include "image.h"
 #include <cstring>
 #include <initializer_list>
 #include <memory>
@@ -56,10 +57,9 @@ void drop_tile_cache();
 // the tile p as an image of one tile, and the rectangle of a component sub-sampled by dx, dy in it (num_comps = 1, no MCT)
 grk_amd_image_layout tile_as_image(const grk_amd_tile_params& p);
 int comp_tile_params(const grk_amd_tile_params& p, uint32_t dx, uint32_t dy, grk_amd_tile_params& out);
-// runs of consecutive components with equal sub-sampling factors; mct: the run that starts at component 0 and holds at least
-// three components of a tile that signals the colour transform
-struct CompRun { uint32_t first, count; bool mct; };
-std::vector<CompRun> comp_runs(const grk_amd_tile_params& p, const uint8_t* comp_dx, const uint8_t* comp_dy);
+// runs of consecutive components with equal sub-sampling factors: the library's one rule (image.h)
+using grk_amd::CompRun;
+using grk_amd::comp_runs;
 // the tree's components [comp0, comp0 + p->num_comps), which all have p's geometry (the whole tree: comp0 = 0), and the tree of an
 // image whose components are sub-sampled each in its own way -- decoded at 1 / 2^reduce of their size (0: full size)
 int decode_tree_comps(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const gra_plugin_tile* tile, uint32_t comp0,

@@ -56,17 +56,6 @@ int comp_tile_params(const grk_amd_tile_params& p, uint32_t dx, uint32_t dy, grk
     return rc;
 }
 
-std::vector<CompRun> comp_runs(const grk_amd_tile_params& p, const uint8_t* comp_dx, const uint8_t* comp_dy)
-{
-    std::vector<CompRun> runs;
-    for (uint32_t c0 = 0, n; c0 < p.num_comps; c0 += n) {
-        n = 1;
-        while (c0 + n < p.num_comps && comp_dx[c0 + n] == comp_dx[c0] && comp_dy[c0 + n] == comp_dy[c0]) ++n;
-        runs.push_back(CompRun{c0, n, p.mct && c0 == 0 && n >= 3});
-    }
-    return runs;
-}
-
 bool tree_layout(const grk_amd_tile_params& p, const std::vector<grk_amd_tile_params>* comp_params, TreeLayout& t)
 {
     if (comp_params && comp_params->size() != p.num_comps) return false;
@@ -242,7 +231,7 @@ int decode_tree_subsampled(grk_amd_ctx* ctx, const grk_amd_tile_params* p, const
     if (!ctx || !p || !comp_dx || !comp_dy || !tile || !planes || tile->numComponents != p->num_comps) return GRK_AMD_ERR_INVALID;
     const uint32_t bps = (p->prec + 7u) / 8u;
     size_t at = 0;
-    for (const CompRun& run : comp_runs(*p, comp_dx, comp_dy)) {
+    for (const CompRun& run : comp_runs(p->num_comps, p->mct != 0, comp_dx, comp_dy)) {
         grk_amd_tile_params pr;
         int rc = comp_tile_params(*p, comp_dx[run.first], comp_dy[run.first], pr);
         if (rc) return rc;
@@ -357,7 +346,7 @@ GRA_EXPORT gra_plugin_tile* grk_amd_plugin_tile_create_subsampled(grk_amd_ctx* c
     bool ok = true;
     size_t row = 0;
     uint64_t used = 0;
-    for (const CompRun& run : comp_runs(*p, comp_dx, comp_dy)) {
+    for (const CompRun& run : comp_runs(p->num_comps, p->mct != 0, comp_dx, comp_dy)) {
         grk_amd_tile_params pr = cps[run.first];
         pr.num_comps = (uint16_t)run.count; pr.mct = run.mct ? 1 : 0;
         const int64_t nbl = grk_amd_tile_num_blocks(&pr);

@@ -225,7 +225,9 @@ struct Precinct {
 struct TileCtx {
     Bytes b;
     const grk_amd_stream_info* info;
-    TileGeom g;
+    std::vector<TileGeom> geoms;    // the tile-components' geometries: one, or one per kind of sub-sampling factors
+    std::vector<const TileGeom*> cg;    // [component]: its geometry ...
+    std::vector<uint64_t> row0;         // ... and the first of its rows among the tile's
     uint32_t tile;
     bool ht, sop, eph;
     uint32_t sty;
@@ -248,7 +250,7 @@ inline uint32_t floor_log2(uint32_t v) { uint32_t r = 0; while (v >>= 1) ++r; re
 int read_packet(TileCtx& T, uint32_t i, uint32_t layer, uint32_t number, uint64_t& pos, uint64_t end, std::string& err)
 {
     const Pk& q = T.seq[i];
-    const ResGeom& R = T.g.res[q.r];
+    const ResGeom& R = T.cg[q.c]->res[q.r];
     Precinct& P = T.prec[i];
     if (!P.ready) {
         uint32_t n = 0;
@@ -272,7 +274,7 @@ int read_packet(TileCtx& T, uint32_t i, uint32_t layer, uint32_t number, uint64_
     todo.clear();
     Bits br{T.b.d, pos, end};
     if (br.bit()) {
-        const uint32_t row0 = q.c * T.g.blocks_per_comp;
+        const uint32_t row0 = (uint32_t)T.row0[q.c];
         for (uint32_t bi = 0; bi < R.num_bands; ++bi) {
             const BandGeom::Prec& G = R.band[bi].prec[q.pi];
             if (!G.gw || !G.gh) continue;
@@ -351,6 +353,35 @@ int read_packet(TileCtx& T, uint32_t i, uint32_t layer, uint32_t number, uint64_
 
 struct TilePart { uint64_t at = 0; uint32_t len = 0; bool seen = false; };
 
+inline bool subsampled(const grk_amd_stream_info& info)
+{
+    for (uint32_t c = 0; c < info.base.num_comps && c < 4; ++c) if (info.comp_dx[c] != 1 || info.comp_dy[c] != 1) return true;
+    return false;
+}
+// component c of tile t as a tile of one component: its rectangle in the component's own samples (grk_amd_layout_tile_comp)
+int tile_comp_params(const grk_amd_stream_info& info, uint32_t t, uint32_t c, grk_amd_tile_params& p)
+{
+    const int rc = grk_amd_layout_tile_comp(&info.layout, &info.base, info.comp_dx[c], info.comp_dy[c], t, &p);
+    p.num_comps = 1; p.mct = 0;
+    return rc;
+}
+// the rows of tile t (< 0: no geometry): its own grk_amd_tile_num_blocks, or -- sub-sampled components -- every component's
+int64_t tile_rows(const grk_amd_stream_info& info, uint32_t t, grk_amd_tile_params& p)
+{
+    if (!subsampled(info)) {
+        const int rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
+        return rc ? rc : grk_amd_tile_num_blocks(&p);
+    }
+    int64_t n = 0;
+    for (uint32_t c = 0; c < info.base.num_comps; ++c) {
+        const int rc = tile_comp_params(info, t, c, p);
+        const int64_t nb = rc ? rc : grk_amd_tile_num_blocks(&p);
+        if (nb < 0) return nb;
+        n += nb;
+    }
+    return n;
+}
+
 // One tile: its tile-part header (PLT), then its packets -- in file order, or, when PLT gives every packet's place, precinct by
 // precinct on `threads` threads (a precinct's packets depend on each other through its tag trees and Lblock, on nothing else).
 int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const TilePart& tp, BlockState* st, grk_amd_coded_block* rows,
@@ -362,13 +393,29 @@ int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const
     T.sop = (info.flags & GRK_AMD_CS_SOP) != 0; T.eph = (info.flags & GRK_AMD_CS_EPH) != 0;
     grk_amd_tile_params p;
     int rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
-    if (!rc) rc = build_tile_geom(p, T.g);
     if (rc) return refuse(err, rc, "tile %u: no geometry (%d)", t, rc);
-    const uint32_t order = (info.flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, L = info.num_layers;
-    {
-        std::vector<const TileGeom*> cg(p.num_comps, &T.g);
-        T.seq = packet_order(cg, nullptr, nullptr, p.tile_x0, p.tile_y0, order);
+    const uint32_t nc = p.num_comps;
+    const bool sub = subsampled(info);
+    // every component's tile-component: the tile's own, or -- sub-sampled components -- its rectangle in the component's samples;
+    // components of one size share a geometry
+    T.geoms.reserve(nc);
+    T.cg.resize(nc); T.row0.resize(nc);
+    uint64_t nrows = 0;
+    for (uint32_t c = 0; c < nc; ++c) {
+        uint32_t like = c;
+        for (uint32_t k = 0; k < c; ++k) if (!sub || (info.comp_dx[k] == info.comp_dx[c] && info.comp_dy[k] == info.comp_dy[c])) { like = k; break; }
+        if (like == c) {
+            grk_amd_tile_params pc = p;
+            if (sub) rc = tile_comp_params(info, t, c, pc);
+            T.geoms.emplace_back();
+            if (!rc) rc = build_tile_geom(pc, T.geoms.back());
+            if (rc) return refuse(err, rc, "tile %u component %u: no geometry (%d)", t, c, rc);
+            T.cg[c] = &T.geoms.back();
+        } else T.cg[c] = T.cg[like];
+        T.row0[c] = nrows; nrows += T.cg[c]->blocks_per_comp;
     }
+    const uint32_t order = (info.flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, L = info.num_layers;
+    T.seq = packet_order(T.cg, sub ? info.comp_dx : nullptr, sub ? info.comp_dy : nullptr, p.tile_x0, p.tile_y0, order);
     const uint64_t np = T.seq.size(), npk = np * L;
     // the tile-part header
     const uint64_t end = tp.at + tp.len;
@@ -465,20 +512,19 @@ int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const
         if (pos != end) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: %llu bytes behind the last packet", t, (unsigned long long)(end - pos));
     }
     // the tile's rows (a block of several pieces gets its place in the appendix later)
-    const uint32_t bpc = T.g.blocks_per_comp;
-    for (uint32_t c = 0; c < p.num_comps; ++c)
-        for (uint32_t i = 0; i < bpc; ++i) {
-            const BlockState& s = st[(size_t)c * bpc + i];
-            grk_amd_coded_block& row = rows[(size_t)c * bpc + i];
+    for (uint32_t c = 0; c < nc; ++c)
+        for (uint32_t i = 0; i < T.cg[c]->blocks_per_comp; ++i) {
+            const BlockState& s = st[T.row0[c] + i];
+            grk_amd_coded_block& row = rows[T.row0[c] + i];
             row.offset = s.pieces ? s.src0 : 0; row.length = s.total; row.missing_msbs = 0;
             if (T.ht) row.missing_msbs = s.zbp;
             else if (s.total) {
-                const grk_amd_block& gb = T.g.blocks_comp0[i];
+                const grk_amd_block& gb = T.cg[c]->blocks_comp0[i];
                 const uint32_t bi = gb.res == 0 ? 0u : 3u * gb.res - 2u + (gb.band - 1u);
                 const int expn = info.qstyle ? info.qcd_words[bi] >> 11 : info.qcd_words[bi] >> 3;
                 const int numbps = expn + (int)info.guard_bits - 1 - (int)s.zbp;
                 if (numbps < 1 || (int)s.passes > 3 * numbps - 2)
-                    return refuse(err, GRK_AMD_ERR_INVALID, "tile %u block %u: %u passes over %d bit-planes", t, c * bpc + i, s.passes, numbps);
+                    return refuse(err, GRK_AMD_ERR_INVALID, "tile %u block %u: %u passes over %d bit-planes", t, (uint32_t)T.row0[c] + i, s.passes, numbps);
                 row.missing_msbs = (uint32_t)numbps | (uint32_t)s.passes << 8;
             }
         }
@@ -514,8 +560,7 @@ int grk_amd::read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_
     }
     grk_amd_tile_params p;
     for (uint32_t t = 0; t < info.num_tiles; ++t) {
-        rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
-        const int64_t nb = rc ? rc : grk_amd_tile_num_blocks(&p);
+        const int64_t nb = tile_rows(info, t, p);
         if (nb < 0) return refuse(err, (int)nb, "tile %u (%u x %u at %u, %u): no geometry (%d)", t, p.tile_w, p.tile_h, p.tile_x0, p.tile_y0, (int)nb);
         info.num_blocks += (uint64_t)nb;
         if (info.num_blocks > 4 * kMaxBlocksGuess) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than %llu code-blocks", (unsigned long long)(4 * kMaxBlocksGuess));
@@ -562,8 +607,7 @@ int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_
     out.row_at.assign(nt + 1, 0);
     grk_amd_tile_params p;
     for (uint32_t t = 0; t < nt; ++t) {
-        (void)grk_amd_layout_tile(&info.layout, &info.base, t, &p);
-        const int64_t nb = grk_amd_tile_num_blocks(&p);
+        const int64_t nb = tile_rows(info, t, p);
         if (nb < 0) return refuse(err, (int)nb, "tile %u: no geometry", t);
         out.row_at[t + 1] = out.row_at[t] + (uint64_t)nb;
     }
@@ -618,6 +662,15 @@ extern "C" int grk_amd_read_header(const uint8_t* cs, uint64_t len, grk_amd_stre
 {
     if (!info) { g_reader_error = "no info"; return GRK_AMD_ERR_INVALID; }
     return read_stream_header(cs, len, *info, g_reader_error);
+}
+
+extern "C" int grk_amd_stream_comp_size(const grk_amd_stream_info* info, uint32_t comp, uint32_t* w, uint32_t* h)
+{
+    if (!info || !w || !h || comp >= info->base.num_comps || comp >= 4 || !info->comp_dx[comp] || !info->comp_dy[comp]) return GRK_AMD_ERR_INVALID;
+    const uint64_t dx = info->comp_dx[comp], dy = info->comp_dy[comp];
+    *w = (uint32_t)((info->layout.x1 + dx - 1) / dx - (info->layout.x0 + dx - 1) / dx);
+    *h = (uint32_t)((info->layout.y1 + dy - 1) / dy - (info->layout.y0 + dy - 1) / dy);
+    return GRK_AMD_OK;
 }
 
 extern "C" int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,

@@ -561,6 +561,9 @@ int64_t grk_amd_locate_tile_parts(const uint8_t* cs, uint64_t len, uint64_t* off
  *   packets       the five progression orders, any precinct sizes, 1..N layers, SOP / EPH, empty packets, blocks that are not
  *                 included, tag trees in their general form, Part-1 codeword segments (TERMALL, LAZY) carried on across
  *                 layers, HT blocks with one pass
+ *   components    sub-sampled each in its own way (SIZ XRsiz / YRsiz: 4:2:2, 4:2:0, ...): every component of a tile has its own
+ *                 rectangle (grk_amd_layout_tile_comp), precinct grid and tag trees, and the position-dependent orders (RPCL,
+ *                 PCRL, CPRL) meet its precincts where the factors put them on the reference grid
  * GRK_AMD_ERR_UNSUPPORTED (and the reason in grk_amd_reader_last_error): COC, QCC, RGN, POC, PPM, PPT, PLM, Sqcd style 1, more
  * than one tile-part per tile, components of differing precision or sign, more than 4 components, more than GRK_AMD_MAX_LEVELS
  * levels, HT blocks with more than one pass, a custom MCT.  GRK_AMD_ERR_INVALID: anything malformed -- the input is untrusted:
@@ -577,12 +580,19 @@ typedef struct grk_amd_stream_info {
     uint32_t num_qcd;                                 /* grk_amd_tile_layout gives and grk_amd_set_decode_qcd takes them             */
     uint8_t  comp_dx[4], comp_dy[4];      /* XRsiz / YRsiz                                                                   */
     uint32_t num_tiles;
-    uint64_t num_blocks;                  /* rows of the whole image: sum over tiles of grk_amd_tile_num_blocks             */
+    uint64_t num_blocks;                  /* rows of the whole image: sum over tiles of grk_amd_tile_num_blocks (with a factor
+                                             other than 1: over tiles and components, of the component's rectangle as one component) */
 } grk_amd_stream_info;
 int grk_amd_read_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info* info);
+/* Component `comp` of the image in its own samples: *w = ceil(x1 / dx) - ceil(x0 / dx) columns, *h = ceil(y1 / dy) - ceil(y0 / dy)
+ * rows (W x H for factors of 1); host only.  What sizes the planes grk_amd_decode_image writes for a sub-sampled stream. */
+int grk_amd_stream_comp_size(const grk_amd_stream_info* info, uint32_t comp, uint32_t* w, uint32_t* h);
 /* The block table of the whole image.  rows: tile after tile in tile-index order, tile t with the rows of ITS parameters
  * (grk_amd_layout_tile) in grk_amd_tile_layout order: the table grk_amd_write_codestream_layout takes and grk_amd_decode_tiles takes
- * per tile.  missing_msbs as grk_amd_decode_tiles wants it: HT = zero bit-planes; Part-1 = numbps | numpasses << 8 with numbps =
+ * per tile.  A stream with a sub-sampling factor other than 1: within a tile component after component, component c with the rows
+ * of its rectangle (grk_amd_layout_tile_comp, num_comps = 1) -- the table grk_amd_write_codestream_subsampled takes; the rows of a
+ * run of components with equal factors are the table of one grk_amd_decode_tiles call with num_comps = the run's length.
+ * missing_msbs as grk_amd_decode_tiles wants it: HT = zero bit-planes; Part-1 = numbps | numpasses << 8 with numbps =
  * band exponent + guard bits - 1 - zero bit-planes; a block without data has length 0.
  * Where a block's bytes lie in one piece in the file, rows[i].offset is their position in `cs`: nothing is copied, the
  * codestream is the coded buffer.  A block whose bytes come in several pieces (several layers) gets an offset at or behind `len`,
@@ -606,13 +616,27 @@ const char* grk_amd_reader_last_error(void);
  * The bytes are uploaded once while the host reads the packet headers; blocks of several pieces are gathered on the device; the
  * tiles are grouped by geometry, every group is one grk_amd_decode_tiles batch, and a placement kernel puts a group's tiles at
  * their rectangles (a one-tile image is decoded straight into `pixels`).  The QCD words and segment lists the call sets on the
- * context are put back before it returns.  GRK_AMD_ERR_UNSUPPORTED: what the reader refuses, sub-sampled components, a context
- * with grk_amd_set_decode_reduce != 0, and an HT stream whose QCD exponents differ from the ones this library derives for the
- * geometry (HT blocks are decoded against those).  The int16-plane rule (GRK_AMD_ERR_RANGE, grk_amd_set_decode_planes16) holds
+ * context are put back before it returns.
+ * Sub-sampled components (a factor other than 1 in SIZ): the unit of decoding is a tile's run of consecutive components with equal
+ * factors; the units are grouped by geometry and batched like tiles.  `pixels` then holds one plane per component, back to back:
+ * component c of grk_amd_stream_comp_size columns by rows, tight -- the layout grk_amd_encode_image_subsampled takes; a one-tile image
+ * is decoded run by run straight into its planes.  The colour transform applies where components 0..2 form one run.
+ * grk_amd_set_decode_upsample(ctx, on != 0) (context state, default off): every component of such a stream is delivered on the
+ * reference grid instead, W x H, so that `pixels` is the ordinary image and grk_amd_set_decode_pixel_layout applies to it in full.  No
+ * interpolation: the image sample at reference-grid position (gx, gy) is the component's sample (floor(gx / dx), floor(gy / dy)) --
+ * each sample repeated over its dx x dy cell -- and 0 where that sample does not exist, i.e. left of dx * ceil(X0 / dx) or above
+ * dy * ceil(Y0 / dy): a strip that exists only when the image origin (X0, Y0) is no multiple of the factors (grk_decompress
+ * --upsample does the same).  The units are then placed by a kernel that writes every sample's cell, a one-tile image included.  A
+ * stream without sub-sampling decodes the same with the switch on and off.
+ * GRK_AMD_ERR_UNSUPPORTED: what the reader refuses, a context with grk_amd_set_decode_reduce != 0, an HT stream whose QCD exponents
+ * differ from the ones this library derives for a unit's geometry (HT blocks are decoded against those), a COD that asks for the
+ * colour transform across components of different size, and a decode pixel layout other than the default for a sub-sampled stream
+ * while upsampling is off.  The int16-plane rule (GRK_AMD_ERR_RANGE, grk_amd_set_decode_planes16) holds
  * per group: with host pixels such a group is decoded again with int32 planes by the call itself, with device pixels
  * grk_amd_decode_status reports it. */
 int grk_amd_decode_image(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device);
-/* launches of the gather (which = 0) and placement (which = 1) kernels by this context's grk_amd_decode_image calls so far */
+int grk_amd_set_decode_upsample(grk_amd_ctx* ctx, int on);
+/* launches of the gather (which = 0) and placement (which = 1: plain and upsampling) kernels by this context's grk_amd_decode_image calls so far */
 uint64_t grk_amd_decode_image_launches(grk_amd_ctx* ctx, int which);
 /* The two kernels alone (device pointers; queued on the context's stream):
  * gather: moves[i] = `len` bytes from src_base + src to dst_base + dst (moves in host memory, checked against the two sizes);
@@ -622,6 +646,14 @@ int grk_amd_gather_device(grk_amd_ctx* ctx, const grk_amd_tp_segment* moves, uin
                           void* dst_base, uint64_t dst_bytes);
 int grk_amd_place_tiles_device(grk_amd_ctx* ctx, const void* tiles, uint32_t ntiles, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
                                const uint32_t* rects, void* image, uint32_t img_w, uint32_t img_h);
+/* upsampling placement: the same units, of a component sub-sampled by (dx, dy); unit i's first sample is sample (origins[2 i],
+ * origins[2 i + 1]) of the component.  Sample (x, y) of the component goes to every sample of [x dx, (x + 1) dx) x [y dy, (y + 1) dy)
+ * of the reference grid that lies in the image area [img_x0, img_x0 + img_w) x [img_y0, img_y0 + img_h); `image`: ncomp tight planes
+ * of that area.  GRK_AMD_ERR_INVALID ("... outside the image") when a sample's cell starts outside the area.  The strip no cell
+ * covers (see grk_amd_decode_image) is not written by this call. */
+int grk_amd_place_upsampled_device(grk_amd_ctx* ctx, const void* tiles, uint32_t nunits, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                                   const uint32_t* origins, uint32_t dx, uint32_t dy, void* image, uint32_t img_x0, uint32_t img_y0,
+                                   uint32_t img_w, uint32_t img_h);
 
 /* ---- one image over the GPUs of a node (node.cpp) -------------------------------------------------------
  * Replaces the reference's tile-level task pool (codestream/CodeStreamCompress.cpp:535-603: tiles are independent tasks whose

@@ -83,6 +83,21 @@ class StreamInfo(C.Structure):
                 ("num_blocks", C.c_uint64)]
 
 
+class ImageView(C.Structure):
+    """grk_amd_image_view: reduce (the N finest resolutions dropped) and a window [x0, x1) x [y0, y1) of the (reduced) image, all
+    four 0 = the whole image"""
+    _fields_ = [("reduce", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32)]
+
+    @classmethod
+    def make(cls, reduce=0, window=None):
+        x0, y0, x1, y1 = window if window is not None else (0, 0, 0, 0)
+        return cls(int(reduce), int(x0), int(y0), int(x1), int(y1))
+
+
+VIEW_UNIT_DTYPE = np.dtype([("tile", np.uint32), ("first_comp", np.uint32), ("num_comps", np.uint32), ("w", np.uint32), ("h", np.uint32),
+                            ("x", np.int32), ("y", np.int32), ("whole", np.uint32)])
+
+
 class ReaderError(RuntimeError):
     """read_header / read_packets refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ...) and the reader's reason."""
 
@@ -220,6 +235,15 @@ def lib():
             L.grk_amd_set_decode_upsample.argtypes = [vp, i32]
             L.grk_amd_stream_comp_size.argtypes = [C.POINTER(StreamInfo), u32, C.POINTER(u32), C.POINTER(u32)]
             L.grk_amd_place_upsampled_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, u32, u32, vp, u32, u32, u32, u32]
+        if hasattr(L, "grk_amd_decode_image_view"):
+            PV = C.POINTER(ImageView)
+            L.grk_amd_image_view_size.argtypes = [C.POINTER(StreamInfo), PV, u32, C.POINTER(u32), C.POINTER(u32)]
+            L.grk_amd_plan_image_view.restype = C.c_int64
+            L.grk_amd_plan_image_view.argtypes = [C.POINTER(StreamInfo), PV, vp, u64, C.POINTER(u64), vp, u64]
+            L.grk_amd_decode_image_view.argtypes = [vp, vp, u64, PV, vp, u64, i32]
+            L.grk_amd_decode_image_counters.restype = u64
+            L.grk_amd_decode_image_counters.argtypes = [vp, i32]
+            L.grk_amd_place_tiles_clipped_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, u32, u32]
         _lib = L
     return _lib
 
@@ -385,6 +409,43 @@ def stream_comp_sizes(info):
             raise ValueError("grk_amd_stream_comp_size failed: %d" % rc)
         out.append((w.value, h.value))
     return out
+
+
+def _view_error(what, rc):
+    kind = {ERR_UNSUPPORTED: "unsupported", ERR_INVALID: "invalid", ERR_OVERFLOW: "overflow"}.get(rc, "error")
+    return ValueError("%s refused the view: %s (%d)" % (what, kind, rc))
+
+
+def image_view_size(info, reduce=0, window=None):
+    """[(w, h)] of every component of the view (grk_amd_image_view_size): the planes decode_image_view writes.  ValueError, naming
+    the code (unsupported / invalid), for a view the call refuses."""
+    L = lib()
+    view = ImageView.make(reduce, window)
+    out = []
+    for k in range(info.base.num_comps):
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        rc = L.grk_amd_image_view_size(C.byref(info), C.byref(view), k, C.byref(w), C.byref(h))
+        if rc:
+            raise _view_error("image_view_size", rc)
+        out.append((w.value, h.value))
+    return out
+
+
+def plan_image_view(info, reduce=0, window=None):
+    """grk_amd_plan_image_view -> dict(tiles: the touched tiles in index order (uint32), units: VIEW_UNIT_DTYPE rows, per touched tile
+    and run of components its (reduced) size w x h, its signed position x, y in the view and whether the view holds it wholly)"""
+    L = lib()
+    view = ImageView.make(reduce, window)
+    nt = C.c_uint64(0)
+    n = L.grk_amd_plan_image_view(C.byref(info), C.byref(view), None, 0, C.byref(nt), None, 0)
+    if n < 0:
+        raise _view_error("plan_image_view", int(n))
+    tiles = np.zeros(nt.value, np.uint32)
+    units = np.zeros(n, VIEW_UNIT_DTYPE)
+    n = L.grk_amd_plan_image_view(C.byref(info), C.byref(view), tiles.ctypes.data, tiles.size, C.byref(nt), units.ctypes.data, units.size)
+    if n < 0:
+        raise _view_error("plan_image_view", int(n))
+    return dict(tiles=tiles, units=units)
 
 
 def read_packets(cs, info=None, threads=1):
@@ -705,6 +766,60 @@ class Context:
                        np.uint8 if info.base.prec <= 8 else np.uint16)
         self._check(self._L.grk_amd_decode_image(self._h, buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "decode_image")
         return out
+
+    def decode_image_view(self, cs, reduce=0, window=None, layout=None, out=None):
+        """A view of the codestream's image (grk_amd_decode_image_view, host pixels): at 1 / 2^reduce of its size and / or the window
+        (x0, y0, x1, y1) of that (reduced) image -> pixels (C, h, w) of the view -- or, with a `layout` (row_pitch the view's), the
+        uint8 buffer holding the view in it."""
+        buf = _cs_array(cs)
+        info = read_header(buf)
+        view = ImageView.make(reduce, window)
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        rc = self._L.grk_amd_image_view_size(C.byref(info), C.byref(view), 0, C.byref(w), C.byref(h))
+        if rc:                                   # (the call itself says why)
+            out = np.zeros(16, np.uint8)
+            self._check(self._L.grk_amd_decode_image_view(self._h, buf.ctypes.data, buf.size, C.byref(view), out.ctypes.data, 0, 0), "decode_image_view")
+            raise _view_error("decode_image_view", rc)
+        if layout is not None:
+            out = self._out_in_layout(info.base, layout, w.value, h.value, 1, out)
+            self._with_decode_layout(layout, lambda: self._check(self._L.grk_amd_decode_image_view(
+                self._h, buf.ctypes.data, buf.size, C.byref(view), out.ctypes.data, out.nbytes, 0), "decode_image_view"))
+            return out
+        out = np.zeros((info.base.num_comps, h.value, w.value), np.uint8 if info.base.prec <= 8 else np.uint16)
+        self._check(self._L.grk_amd_decode_image_view(self._h, buf.ctypes.data, buf.size, C.byref(view), out.ctypes.data, out.nbytes, 0),
+                    "decode_image_view")
+        return out
+
+    def decode_image_view_planes(self, cs, reduce):
+        """The same for a stream with sub-sampled components (upsampling off): one 2-D array per component, each of the component's
+        own size at that reduce (image_view_size)."""
+        buf = _cs_array(cs)
+        info = read_header(buf)
+        view = ImageView.make(reduce)
+        dt = np.uint8 if info.base.prec <= 8 else np.uint16
+        sizes = image_view_size(info, reduce)
+        out = np.zeros(sum(w * h for w, h in sizes), dt)
+        self._check(self._L.grk_amd_decode_image_view(self._h, buf.ctypes.data, buf.size, C.byref(view), out.ctypes.data, out.nbytes, 0),
+                    "decode_image_view")
+        at = np.concatenate([[0], np.cumsum([w * h for w, h in sizes])])
+        return [out[at[k]:at[k + 1]].reshape(h, w) for k, (w, h) in enumerate(sizes)]
+
+    def decode_image_view_device(self, cs, d_pixels, cap, reduce=0, window=None):
+        """The same into device memory (asynchronous behind the reader: decode_status joins and reports)."""
+        buf = _cs_array(cs)
+        view = ImageView.make(reduce, window)
+        self._check(self._L.grk_amd_decode_image_view(self._h, buf.ctypes.data, buf.size, C.byref(view), d_pixels, int(cap), 1), "decode_image_view")
+
+    def decode_image_counters(self):
+        """(tiles whose packets were read, codestream bytes uploaded) by this context's decode_image / decode_image_view calls so far"""
+        return int(self._L.grk_amd_decode_image_counters(self._h, 0)), int(self._L.grk_amd_decode_image_counters(self._h, 1))
+
+    def place_tiles_clipped_device(self, d_tiles, ntiles, w, h, ncomp, bps, pos, d_image, img_w, img_h, channels=0):
+        """pos: [(x, y)] of every unit in the destination's planes, signed; what falls outside img_w x img_h is not written.
+        channels != 0: units and destination hold interleaved pixels of that many samples"""
+        r = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        self._check(self._L.grk_amd_place_tiles_clipped_device(self._h, d_tiles, ntiles, w, h, ncomp, bps, channels, r.ctypes.data, d_image,
+                                                               img_w, img_h), "place_tiles_clipped_device")
 
     def set_decode_upsample(self, on):
         """decode_image delivers sub-sampled components on the reference grid, W x H each (grk_amd_set_decode_upsample)"""

@@ -204,6 +204,7 @@ struct grk_amd_ctx {
     // moves, the tiles' places, the status of all groups; launches of the gather / placement kernels so far
     DevBuf img_coded, img_tiles, img_pixels, img_moves, img_rects, img_status;
     uint64_t img_launches[2] = {0, 0};
+    uint64_t img_counters[2] = {0, 0};                      // tiles read, codestream bytes uploaded (grk_amd_decode_image_counters)
     // timing
     bool timing = false;
     Timer timers[10];

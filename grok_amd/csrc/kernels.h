@@ -277,8 +277,9 @@ hipError_t launch_t2dec_gather(const grk_amd_tp_segment* d_moves, uint64_t nmove
 struct PlaceArgs {
     const uint8_t* tiles;                            // ntiles tiles of ncomp x h x w samples of bps bytes, back to back
     uint32_t ntiles, w, h, ncomp, bps;
-    const uint32_t* rects;                           // [tile]: x, y of the tile in the image's planes (checked by the host)
-    uint8_t* image; uint32_t img_w, img_h;           // ncomp planes of img_h x img_w samples
+    const int32_t* rects;                            // [tile]: x, y of the tile in the image's planes; signed: a tile may start left of /
+                                                     // above them, and what lies outside img_w x img_h is not written (clipped)
+    uint8_t* image; uint32_t img_w, img_h;           // ncomp planes of img_h x img_w samples (< 2^31 each)
     uint64_t img_row, img_plane;                     // bytes between the image's rows / planes (0: tight).  Interleaved pixels are
                                                      // placed as ONE component of samples as wide as a pixel
 };

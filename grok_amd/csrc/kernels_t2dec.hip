@@ -3,7 +3,9 @@
 //   KG  gather     a code-block whose bytes come in several pieces (several layers) gets them end to end in the appendix behind
 //                  the uploaded codestream: one wave per piece
 //   KP  placement  a geometry group's decoded tiles (back to back, component-major, tight) into the image's planes at each
-//                  tile's rectangle: a workgroup per (row band, component, tile), a wave per row
+//                  tile's rectangle: a workgroup per (row band, component, tile), a wave per row.  The rectangle's position is
+//                  signed and the tile is clipped to the destination (a view's window, grk_amd_decode_image_view): rows above or
+//                  below it are skipped, a row's surviving run of whole samples (pixels) is what the wave copies
 //   KU  upsampling placement: the same for sub-sampled components delivered on the reference grid -- every source sample is
 //                  written to its footprint of dx x dy image samples (clipped to the image area), a wave per source row as in KP.
 //                  dx = 1 planar rows are copies; dx = 2 rows of one-byte samples into a planar destination are doubled in
@@ -31,11 +33,17 @@ __global__ __launch_bounds__(256) void t2dec_place_kernel(PlaceArgs a)
     const uint32_t tile = blockIdx.z, comp = blockIdx.y, lane = threadIdx.x & 63u;
     const uint64_t row_bytes = (uint64_t)a.w * a.bps, img_row = a.img_row ? a.img_row : (uint64_t)a.img_w * a.bps;
     const uint64_t img_plane = a.img_plane ? a.img_plane : (uint64_t)a.img_h * img_row;
-    const uint8_t* const s = a.tiles + ((uint64_t)tile * a.ncomp + comp) * a.h * row_bytes;
-    uint8_t* const d = a.image + (uint64_t)comp * img_plane + (uint64_t)a.rects[2 * tile + 1] * img_row + (uint64_t)a.rects[2 * tile] * a.bps;
-    const uint32_t y1 = min(a.h, (blockIdx.x + 1) * kPlaceRows);
+    // the tile's columns [cx0, cx1) and rows [cy0, cy1) that fall into the destination's img_w x img_h (all of them for a tile inside it)
+    const int64_t px = a.rects[2 * tile], py = a.rects[2 * tile + 1];
+    const int64_t cx0 = max((int64_t)0, -px), cx1 = min((int64_t)a.w, (int64_t)a.img_w - px);
+    const int64_t cy0 = max((int64_t)0, -py), cy1 = min((int64_t)a.h, (int64_t)a.img_h - py);
+    if (cx0 >= cx1 || cy0 >= cy1) return;
+    const uint8_t* const s = a.tiles + ((uint64_t)tile * a.ncomp + comp) * a.h * row_bytes + (uint64_t)cx0 * a.bps;
+    uint8_t* const d = a.image + (uint64_t)comp * img_plane + (uint64_t)(px + cx0) * a.bps;
+    const uint64_t run = (uint64_t)(cx1 - cx0) * a.bps;
+    const uint32_t y1 = min((uint32_t)cy1, (blockIdx.x + 1) * kPlaceRows);
     for (uint32_t y = blockIdx.x * kPlaceRows + (threadIdx.x >> 6); y < y1; y += 4)
-        wave_copy(d + y * img_row, s + y * row_bytes, row_bytes, lane);
+        if (y >= (uint32_t)cy0) wave_copy(d + (uint64_t)(py + y) * img_row, s + y * row_bytes, run, lane);
 }
 
 // a | b << 8  ->  a | a << 8 | b << 16 | b << 24
@@ -134,6 +142,7 @@ hipError_t launch_t2dec_gather(const grk_amd_tp_segment* d_moves, uint64_t nmove
 hipError_t launch_t2dec_place(const PlaceArgs& a, hipStream_t s)
 {
     if (!a.ntiles || !a.w || !a.h) return hipSuccess;
+    if (a.img_w > 0x7FFFFFFFu || a.img_h > 0x7FFFFFFFu) return hipErrorInvalidValue;          // (positions are signed 32-bit)
     hipLaunchKernelGGL(t2dec_place_kernel, dim3((a.h + kPlaceRows - 1) / kPlaceRows, a.ncomp, a.ntiles), dim3(256), 0, s, a);
     return hipGetLastError();
 }

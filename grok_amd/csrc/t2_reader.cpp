@@ -209,6 +209,7 @@ struct BlockState {
     uint32_t last_seg = 0;          // the open codeword segment's record in its precinct's list
     uint16_t passes = 0, seg_idx = 0;
     uint8_t  lblock = 3, included = 0, zbp = 0, seg_fill = 0;
+    uint8_t  dropped = 0;           // of a resolution the caller's reduced decode drops
 };
 struct SegRec { uint32_t row, len, passes; };
 struct Piece { uint64_t src; uint32_t row, len; };
@@ -351,7 +352,7 @@ int read_packet(TileCtx& T, uint32_t i, uint32_t layer, uint32_t number, uint64_
     return GRK_AMD_OK;
 }
 
-struct TilePart { uint64_t at = 0; uint32_t len = 0; bool seen = false; };
+using TilePart = StreamPart;
 
 inline bool subsampled(const grk_amd_stream_info& info)
 {
@@ -385,7 +386,7 @@ int64_t tile_rows(const grk_amd_stream_info& info, uint32_t t, grk_amd_tile_para
 // One tile: its tile-part header (PLT), then its packets -- in file order, or, when PLT gives every packet's place, precinct by
 // precinct on `threads` threads (a precinct's packets depend on each other through its tag trees and Lblock, on nothing else).
 int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const TilePart& tp, BlockState* st, grk_amd_coded_block* rows,
-              uint32_t threads, std::vector<Precinct>& keep, std::string& err)
+              uint32_t threads, uint32_t drop_res, std::vector<Precinct>& keep, std::string& err)
 {
     TileCtx T;
     T.b = b; T.info = &info; T.tile = t; T.st = st;
@@ -514,8 +515,9 @@ int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const
     // the tile's rows (a block of several pieces gets its place in the appendix later)
     for (uint32_t c = 0; c < nc; ++c)
         for (uint32_t i = 0; i < T.cg[c]->blocks_per_comp; ++i) {
-            const BlockState& s = st[T.row0[c] + i];
+            BlockState& s = st[T.row0[c] + i];
             grk_amd_coded_block& row = rows[T.row0[c] + i];
+            s.dropped = T.cg[c]->blocks_comp0[i].res + drop_res > info.base.num_levels;
             row.offset = s.pieces ? s.src0 : 0; row.length = s.total; row.missing_msbs = 0;
             if (T.ht) row.missing_msbs = s.zbp;
             else if (s.total) {
@@ -581,38 +583,58 @@ int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_
     int rc = read_stream_header(cs, len, own, err);
     if (rc) return rc;
     if (std::memcmp(&own, &info, sizeof own) != 0) return refuse(err, GRK_AMD_ERR_INVALID, "info is not what grk_amd_read_header gives for this codestream");
-    threads = std::max<uint32_t>(1, std::min<uint32_t>(threads, 16));
+    std::vector<StreamPart> parts;
+    rc = locate_stream_parts(cs, len, info, parts, err);
+    if (rc) return rc;
+    return read_stream_packets_of(cs, len, info, parts, nullptr, 0, threads, out, err);
+}
+
+int grk_amd::locate_stream_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, std::vector<StreamPart>& parts, std::string& err)
+{
     const Bytes b{cs, len};
     const uint32_t nt = info.num_tiles;
     // the tile-parts: one per tile
-    std::vector<TilePart> parts(nt);
-    {
-        std::vector<uint64_t> off(nt); std::vector<uint32_t> ln(nt); std::vector<uint16_t> idx(nt);
-        int used = 0;
-        const int64_t n = grk_amd_locate_tile_parts(cs, len, off.data(), ln.data(), idx.data(), nt, &used);
-        if (n < 0) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts cannot be located");
-        for (int64_t i = 0; i < std::min<int64_t>(n, nt); ++i) {
-            if (ln[i] < 14 || !b.has(off[i], ln[i]) || b.u16(off[i]) != 0xFF90 || b.u16(off[i] + 2) != 10)
-                return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: no SOT marker segment where it should start", (long long)i);
-            const uint32_t isot = b.u16(off[i] + 4), psot = b.u32(off[i] + 6), tps = b.u8(off[i] + 10), tn = b.u8(off[i] + 11);
-            if (isot >= nt || (used && isot != idx[i])) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: tile index %u", (long long)i, isot);
-            if (tps != 0 || tn > 1 || parts[isot].seen) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (tile %u)", isot);
-            if (psot && psot != ln[i]) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: Psot %u, TLM %u", (long long)i, psot, ln[i]);
-            parts[isot] = TilePart{off[i], ln[i], true};
-        }
-        if (n > nt) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (%lld tile-parts, %u tiles)", (long long)n, nt);
-        for (uint32_t t = 0; t < nt; ++t) if (!parts[t].seen) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u has no tile-part", t);
+    parts.assign(nt, StreamPart{});
+    std::vector<uint64_t> off(nt); std::vector<uint32_t> ln(nt); std::vector<uint16_t> idx(nt);
+    int used = 0;
+    const int64_t n = grk_amd_locate_tile_parts(cs, len, off.data(), ln.data(), idx.data(), nt, &used);
+    if (n < 0) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts cannot be located");
+    for (int64_t i = 0; i < std::min<int64_t>(n, nt); ++i) {
+        if (ln[i] < 14 || !b.has(off[i], ln[i]) || b.u16(off[i]) != 0xFF90 || b.u16(off[i] + 2) != 10)
+            return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: no SOT marker segment where it should start", (long long)i);
+        const uint32_t isot = b.u16(off[i] + 4), psot = b.u32(off[i] + 6), tps = b.u8(off[i] + 10), tn = b.u8(off[i] + 11);
+        if (isot >= nt || (used && isot != idx[i])) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: tile index %u", (long long)i, isot);
+        if (tps != 0 || tn > 1 || parts[isot].seen) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (tile %u)", isot);
+        if (psot && psot != ln[i]) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: Psot %u, TLM %u", (long long)i, psot, ln[i]);
+        parts[isot] = TilePart{off[i], ln[i], true};
     }
+    if (n > nt) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (%lld tile-parts, %u tiles)", (long long)n, nt);
+    for (uint32_t t = 0; t < nt; ++t) if (!parts[t].seen) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u has no tile-part", t);
+    return GRK_AMD_OK;
+}
+
+int grk_amd::read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, const std::vector<StreamPart>& parts,
+                                    const std::vector<uint32_t>* tiles, uint32_t drop_res, uint32_t threads, StreamTable& out, std::string& err)
+{
+    threads = std::max<uint32_t>(1, std::min<uint32_t>(threads, 16));
+    const Bytes b{cs, len};
+    if (parts.size() != info.num_tiles) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts are not this stream's");
+    // the tiles to read: tile_of(i), i < nt
+    const uint32_t nt = tiles ? (uint32_t)tiles->size() : info.num_tiles;
+    auto tile_of = [tiles](size_t i) { return tiles ? (*tiles)[i] : (uint32_t)i; };
+    for (uint32_t i = 0; i < nt; ++i)
+        if (tile_of(i) >= info.num_tiles || (i && tile_of(i) <= tile_of(i - 1))) return refuse(err, GRK_AMD_ERR_INVALID, "the tile list");
+    int rc = GRK_AMD_OK;
     out = StreamTable{};
     out.row_at.assign(nt + 1, 0);
     grk_amd_tile_params p;
     for (uint32_t t = 0; t < nt; ++t) {
-        const int64_t nb = tile_rows(info, t, p);
-        if (nb < 0) return refuse(err, (int)nb, "tile %u: no geometry", t);
+        const int64_t nb = tile_rows(info, tile_of(t), p);
+        if (nb < 0) return refuse(err, (int)nb, "tile %u: no geometry", tile_of(t));
         out.row_at[t + 1] = out.row_at[t] + (uint64_t)nb;
     }
     const uint64_t nrows = out.row_at[nt];
-    if (nrows != info.num_blocks) return refuse(err, GRK_AMD_ERR_INVALID, "info.num_blocks");
+    if (!tiles && nrows != info.num_blocks) return refuse(err, GRK_AMD_ERR_INVALID, "info.num_blocks");
     out.rows.assign(nrows, grk_amd_coded_block{0, 0, 0});
     std::vector<BlockState> st(nrows);
     std::vector<std::vector<Precinct>> left(nt);
@@ -620,13 +642,13 @@ int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_
         std::mutex mu;
         rc = parallel_for(nt, threads, [&](size_t t) -> int {
             std::string e;
-            const int r = read_tile(b, info, (uint32_t)t, parts[t], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, left[t], e);
+            const int r = read_tile(b, info, tile_of(t), parts[tile_of(t)], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, drop_res, left[t], e);
             if (r) { std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; }
             return r;
         });
     } else {
         for (uint32_t t = 0; t < nt && !rc; ++t)
-            rc = read_tile(b, info, t, parts[t], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, left[t], err);
+            rc = read_tile(b, info, tile_of(t), parts[tile_of(t)], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, drop_res, left[t], err);
     }
     if (rc) { if (err.empty()) (void)refuse(err, rc, "the packets cannot be read (%d)", rc); return rc; }
     // Segment lists and the appendix, in an order that does not depend on the threads: rows in order, a row's records in the order
@@ -645,14 +667,18 @@ int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_
         for (const Precinct& P : left[t]) for (const SegRec& s : P.segs) out.segments[cursor[out.row_at[t] + s.row]++] = grk_amd_segment{s.len, s.passes};
     uint64_t app = 0;
     for (uint64_t i = 0; i < nrows; ++i)
-        if (st[i].pieces > 1) { out.rows[i].offset = len + app; cursor[i] = app; app += st[i].total; }
+        if (st[i].pieces > 1 && !st[i].dropped) { out.rows[i].offset = len + app; cursor[i] = app; app += st[i].total; }
     out.appendix_bytes = app;
-    for (uint32_t t = 0; app && t < nt; ++t)
+    out.move_at.assign(nt + 1, 0);
+    for (uint32_t t = 0; t < nt; ++t) {
         for (const Precinct& P : left[t])
             for (const Piece& q : P.pieces) {
+                if (!app) break;
                 const uint64_t i = out.row_at[t] + q.row;
-                if (st[i].pieces > 1) { out.moves.push_back(grk_amd_tp_segment{cursor[i], q.src, q.len, 1u}); cursor[i] += q.len; }
+                if (st[i].pieces > 1 && !st[i].dropped) { out.moves.push_back(grk_amd_tp_segment{cursor[i], q.src, q.len, 1u}); cursor[i] += q.len; }
             }
+        out.move_at[t + 1] = out.moves.size();
+    }
     return GRK_AMD_OK;
 }
 

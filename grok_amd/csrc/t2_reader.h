@@ -10,8 +10,9 @@
 namespace grk_amd {
 
 struct StreamTable {
-    std::vector<grk_amd_coded_block> rows;          // the whole image's, tile after tile
-    std::vector<uint64_t> row_at;                   // [tile]: its first row; [num_tiles]: their number
+    std::vector<grk_amd_coded_block> rows;          // the whole image's, tile after tile (of a tile list: those tiles')
+    std::vector<uint64_t> row_at;                   // [tile]: its first row; [num_tiles]: their number (of a tile list: by place in it)
+    std::vector<uint64_t> move_at;                  // the same for the tile's moves
     std::vector<uint32_t> first_segment;            // [rows + 1]
     std::vector<grk_amd_segment> segments;
     std::vector<grk_amd_tp_segment> moves;          // dst counted from the start of the appendix
@@ -20,6 +21,16 @@ struct StreamTable {
 
 int read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info& info, std::string& err);
 int read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err);
+
+// The two halves of read_stream_packets, for a caller that reads some of the tiles (grk_amd_decode_image_view):
+// where every tile's one tile-part lies (TLM, else the Psot chain: no packet is read) ...
+struct StreamPart { uint64_t at = 0; uint32_t len = 0; bool seen = false; };
+int locate_stream_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, std::vector<StreamPart>& parts, std::string& err);
+// ... and the packets of `tiles` (rising tile indices; nullptr: every tile).  Offsets stay positions in `cs` (the appendix behind
+// `len`).  drop_res: blocks of the `drop_res` finest resolutions get no place in the appendix and no moves -- a decode at that
+// reduce never reads their rows
+int read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, const std::vector<StreamPart>& parts,
+                           const std::vector<uint32_t>* tiles, uint32_t drop_res, uint32_t threads, StreamTable& out, std::string& err);
 
 } // namespace grk_amd
 #pragma GCC visibility pop

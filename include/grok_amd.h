@@ -638,6 +638,61 @@ int grk_amd_decode_image(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len, void
 int grk_amd_set_decode_upsample(grk_amd_ctx* ctx, int on);
 /* launches of the gather (which = 0) and placement (which = 1: plain and upsampling) kernels by this context's grk_amd_decode_image calls so far */
 uint64_t grk_amd_decode_image_launches(grk_amd_ctx* ctx, int which);
+/* A VIEW of the image: at reduced resolution (grk_decompress -r N, grk_dparameters::cp_reduce) and / or a window of it
+ * (grk_decompress_set_window) -- proxies and thumbnails of a master, a viewport of a very large image.
+ *   reduce r   component k of the image becomes [ceil(ceil(X0 / dx) / 2^r), ceil(ceil(X1 / dx) / 2^r)) x the same in y; tile t delivers
+ *              the rectangle grk_amd_reduced_tile_rect gives, and those rectangles partition the image.  Bit-identical to the
+ *              reference's reduced image -- with an origin off the 2^r grid, to its top-left w x h samples: the reference sizes
+ *              the image from its width (one row / column more that the resolutions do not hold; see grk_amd_reduced_tile_rect).
+ *              r > the stream's levels: GRK_AMD_ERR_INVALID; r = levels is legal (the LL band).
+ *   window     [x0, x1) x [y0, y1) in samples of the (reduced) image, counted from ITS top-left sample (not the canvas: what
+ *              grk_decompress_set_window does); bit-identical to that crop of the whole view.  GRK_AMD_ERR_INVALID: x1 <= x0 or
+ *              y1 <= y0 (other than all four 0 = no window), a window outside the view's image.
+ * GRK_AMD_ERR_UNSUPPORTED: a window of a stream with sub-sampled components (upsampling on or off), a reduce other than 0 of such a
+ * stream while grk_amd_set_decode_upsample is on.  view == NULL or all-zero: exactly grk_amd_decode_image.
+ * `pixels` is the view's image -- component k of grk_amd_image_view_size -- and everything grk_amd_decode_image says about it holds
+ * with the view's sizes and pitches: host or device pixels, grk_amd_set_decode_pixel_layout, tight planes back to back for
+ * sub-sampled components, the int16-plane rule and grk_amd_decode_status, the context's settings put back on return.
+ * Only the touched tiles -- those whose rectangle meets the window -- are read, uploaded and decoded: their tile-parts are found
+ * through TLM or the Psot chain, the packet reader runs over them alone, and their bytes travel as a compact buffer (a view that
+ * touches every tile uploads the codestream as grk_amd_decode_image does).  Under reduce the blocks of the dropped resolutions are
+ * neither gathered nor decoded.  A window of a ONE-tile stream is decoded with grk_amd_decode_region, so that the cost follows the
+ * window (where that call's conditions hold: a DWT level left, samples of at most 16 bits; else as below).  In a multi-tile
+ * stream the touched tiles are decoded whole and the placement kernel clips them to the view: partial tiles of multi-tile streams
+ * are decoded whole, the cost follows the touched tiles.
+ * The reduce is a parameter of the call, not the context's: like grk_amd_decode_image this call refuses (GRK_AMD_ERR_UNSUPPORTED) a
+ * context whose grk_amd_set_decode_reduce is not 0 or that has a decode sequence. */
+typedef struct grk_amd_image_view {
+    uint32_t reduce;            /* 0 = full size; the N finest resolutions dropped, as grk_decompress -r N */
+    uint32_t x0, y0, x1, y1;    /* window [x0, x1) x [y0, y1) in samples of the (reduced) image, relative to its top-left sample;
+                                   all four 0 = the whole image */
+} grk_amd_image_view;
+/* host only: component `comp` of the view: *w x *h samples (the size of its plane in `pixels`) */
+int grk_amd_image_view_size(const grk_amd_stream_info* info, const grk_amd_image_view* view, uint32_t comp, uint32_t* w, uint32_t* h);
+/* host only, no context: the plan of the call.  tiles [tile_cap]: the touched tiles in index order, *num_tiles of them; units [cap]:
+ * per touched tile and run of components of one size (one run without sub-sampling) what its decode delivers -- w x h samples, 0
+ * where nothing of the unit is left at this reduce -- and where that rectangle starts in the view's plane of those components:
+ * (x, y), signed -- it may start left of / above the view; whole = 1 when the view holds all of it.  Returns the number of units
+ * (tiles, units may be NULL: only the counts); GRK_AMD_ERR_OVERFLOW when a capacity is too small, else the refusals above. */
+typedef struct grk_amd_view_unit {
+    uint32_t tile, first_comp, num_comps;
+    uint32_t w, h;
+    int32_t  x, y;
+    uint32_t whole;
+} grk_amd_view_unit;
+int64_t grk_amd_plan_image_view(const grk_amd_stream_info* info, const grk_amd_image_view* view, uint32_t* tiles, uint64_t tile_cap,
+                                uint64_t* num_tiles, grk_amd_view_unit* units, uint64_t cap);
+int grk_amd_decode_image_view(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view,
+                              void* pixels, uint64_t cap, int pixels_on_device);
+/* cumulative per context: which = 0 tiles whose packets a grk_amd_decode_image / grk_amd_decode_image_view call read, 1 codestream
+ * bytes those calls uploaded */
+uint64_t grk_amd_decode_image_counters(grk_amd_ctx* ctx, int which);
+/* The placement kernel with clipping (device pointers; queued on the context's stream): as grk_amd_place_tiles_device, but unit i
+ * goes to the SIGNED position (pos[2 i], pos[2 i + 1]) of the destination's planes and only what falls inside img_w x img_h is
+ * written (a unit wholly outside: nothing).  channels = 0: ncomp planes; channels != 0: the units and the destination hold
+ * interleaved pixels of `channels` samples (ncomp is not used), cut by whole pixels. */
+int grk_amd_place_tiles_clipped_device(grk_amd_ctx* ctx, const void* tiles, uint32_t ntiles, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                                       uint32_t channels, const int32_t* pos, void* image, uint32_t img_w, uint32_t img_h);
 /* The two kernels alone (device pointers; queued on the context's stream):
  * gather: moves[i] = `len` bytes from src_base + src to dst_base + dst (moves in host memory, checked against the two sizes);
  * placement: ntiles tiles of w x h samples, ncomp components, bps bytes per sample, back to back at `tiles`, tile i to

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """What reading a whole codestream costs (grk_amd_decode_image): the Tier-2 reader alone, the whole call beside
 grk_amd_decode_tiles with a table prepared beforehand (what the call adds: reader + plumbing) and beside grk_decompress, and the
-two kernels beside a plain device-to-device copy of the same bytes.  Medians of --repeats (7) on one box, the settings of a group
+two kernels beside a plain device-to-device copy of the same bytes; and views of the 256-tile file (grk_amd_decode_image_view: a 1024^2
+interior window, the whole image at reduce 2) beside the full decode -- with GRK_AMD_LIB naming a library built from an earlier commit,
+--view-only gives that commit's full decode on the same box for the comparison.  Medians of --repeats (7) on one box, the settings of a group
 alternated within each repeat (not one setting's repeats after the other's); host wall clock around a synchronised call.
 
     python tools/decode_image_time.py [--repeats 7] [--ref-repeats 3] [--small] > profiles/decode_image.txt
@@ -50,11 +52,43 @@ def image(S):
     return np.ascontiguousarray(np.tile(base, (1, S // base.shape[1], S // base.shape[2])))
 
 
+def views(c, file, repeats):
+    """the 256-tile file: the full decode, a T x T window across an interior 4-tile corner, the whole image at reduce 2; device pixels,
+    the codestream in pinned memory"""
+    S, T, cs, info = file
+    pinned = c.host_array(cs.size)
+    pinned[:] = cs
+    d_out = torch.zeros(3 * S * S, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    settings, uploaded = {}, {}
+
+    def full():
+        c.decode_image_device(pinned, d_out.data_ptr(), d_out.numel())
+        c.decode_status()
+    settings["decode_image, the whole image (%d tile-parts)" % info.num_tiles] = full
+    if hasattr(c._L, "grk_amd_decode_image_view"):
+        win = (S // 2 - T // 2, S // 2 - T // 2, S // 2 + T // 2, S // 2 + T // 2)
+        for name, kw in (("decode_image_view, %d^2 window across a 4-tile corner" % T, dict(window=win)), ("decode_image_view, reduce 2 (%d^2)" % (S // 4), dict(reduce=2))):
+            def view(kw=kw):
+                c.decode_image_view_device(pinned, d_out.data_ptr(), d_out.numel(), **kw)
+                c.decode_status()
+            b0 = c.decode_image_counters()
+            view()
+            b1 = c.decode_image_counters()
+            uploaded[name] = (b1[0] - b0[0], b1[1] - b0[1])
+            settings[name] = view
+    show("views of the 256-tile file, device pixels, codestream in pinned memory (%s)" % os.path.basename(os.path.dirname(G.lib_path())), alternated(settings, repeats))
+    for name, (tiles, nbytes) in uploaded.items():
+        print("    %-58s %d tiles read, %d of %d bytes uploaded" % (name, tiles, nbytes, cs.size))
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--ref-repeats", type=int, default=3)
     ap.add_argument("--small", action="store_true", help="2048 / 4096 instead of 8192 / 16384 (a quick look)")
+    ap.add_argument("--view-only", action="store_true", help="only the views of the 256-tile file beside its full decode")
     a = ap.parse_args()
     c = G.Context(0)
     S1, S2 = (2048, 4096) if a.small else (8192, 16384)
@@ -63,12 +97,17 @@ def main():
     files = {}
     for name, S, T, flags in (("one tile %d^2 x 3, PLT" % S1, S1, S1, G.CS_PLT), ("one tile %d^2 x 3, no PLT" % S1, S1, S1, 0),
                               ("256 tiles, %d^2 x 3, PLT" % S2, S2, S2 // 16, G.CS_PLT)):
+        if a.view_only and S != S2:
+            continue
         px = image(S)
         cs = np.frombuffer(c.encode_image(G.ImageLayout.make(S, S, T, T), G.TileParams.make(T, T, 3, 8, 5), px, flags), np.uint8)
         info = G.read_header(cs)
         files[name] = (S, T, cs, info)
         print("# %s: %d bytes, %d tiles, %d code-blocks" % (name, cs.size, info.num_tiles, info.num_blocks))
         del px
+    views(c, files["256 tiles, %d^2 x 3, PLT" % S2], a.repeats)
+    if a.view_only:
+        return
     # ---- the reader alone
     for name, (S, T, cs, info) in files.items():
         show("reader alone (header + packets), %s" % name,

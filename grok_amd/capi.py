@@ -94,6 +94,101 @@ class ImageView(C.Structure):
         return cls(int(reduce), int(x0), int(y0), int(x1), int(y1))
 
 
+class SurfaceComp(C.Structure):
+    """grk_amd_surface_comp: where one component lies on a surface (bytes; step in samples, 0 reads as 1)"""
+    _fields_ = [("offset", C.c_uint64), ("row_pitch", C.c_uint64), ("step", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SURFACE_FORMATS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3, "NV16": 4, "I422": 5, "I444": 6}
+
+
+class SurfaceError(RuntimeError):
+    """a surface call refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ERR_OVERFLOW -5) and the reason"""
+
+    def __init__(self, what, code, reason):
+        RuntimeError.__init__(self, "%s failed: %d (%s)" % (what, code, reason))
+        self.code, self.reason = int(code), reason
+
+
+class Surface(C.Structure):
+    """grk_amd_surface: a video surface component by component -- sample (x, y) of component c at
+    base + comp[c].offset + y * comp[c].row_pitch + x * comp[c].step * bps"""
+    _fields_ = [("comp", SurfaceComp * 4)]
+
+    @classmethod
+    def of(cls, comps):
+        """comps: [(offset, row_pitch, step)] per component"""
+        s = cls()
+        for k, (offset, row_pitch, step) in enumerate(comps):
+            s.comp[k] = SurfaceComp(int(offset), int(row_pitch), int(step), 0)
+        return s
+
+    @classmethod
+    def make(cls, fmt, layout, prec=8, pitch=0):
+        """A named format ("NV12", "NV21", "I420", "YV12", "NV16", "I422", "I444" or its number) for the image area of `layout`
+        (grk_amd_surface_format) -> (surface, [(dx, dy)] per component, bytes)"""
+        s = cls()
+        dx, dy = (C.c_uint8 * 4)(), (C.c_uint8 * 4)()
+        nc, nbytes = C.c_uint32(0), C.c_uint64(0)
+        rc = lib().grk_amd_surface_format(SURFACE_FORMATS.get(fmt, fmt), C.byref(layout), int(prec), int(pitch), C.byref(s), dx, dy,
+                                          C.byref(nc), C.byref(nbytes))
+        if rc:
+            raise SurfaceError("surface_format", rc, "format %r, pitch %d, %d bits" % (fmt, pitch, prec))
+        return s, [(dx[k], dy[k]) for k in range(nc.value)], int(nbytes.value)
+
+    def gather(self, buf, sizes, bps):
+        """component k's samples out of the uint8 array `buf` holding the surface: [2-D array] (sizes: [(w, h)], pitches resolved)"""
+        out = []
+        for k, (w, h) in enumerate(sizes):
+            c = self.comp[k]
+            step = c.step or 1
+            pitch = c.row_pitch or ((w - 1) * step + 1) * bps
+            rows = np.lib.stride_tricks.as_strided(buf[c.offset:], (h, w, bps), (pitch, step * bps, 1))
+            out.append(np.ascontiguousarray(rows).view(np.uint8 if bps == 1 else np.uint16).reshape(h, w))
+        return out
+
+    def scatter(self, buf, planes, bps):
+        """the reverse: plane k's samples onto the surface in `buf` (nothing else is written)"""
+        for k, pl in enumerate(planes):
+            h, w = pl.shape
+            c = self.comp[k]
+            step = c.step or 1
+            pitch = c.row_pitch or ((w - 1) * step + 1) * bps
+            rows = np.lib.stride_tricks.as_strided(buf[c.offset:], (h, w, bps), (pitch, step * bps, 1))
+            rows[...] = np.ascontiguousarray(pl, np.uint8 if bps == 1 else np.uint16).view(np.uint8).reshape(h, w, bps)
+
+
+def _sampling(sampling):
+    return (C.c_uint8 * 4)(*[int(a) for a, _ in sampling]), (C.c_uint8 * 4)(*[int(b) for _, b in sampling])
+
+
+def surface_bytes(layout, base, sampling, surface):
+    """Bytes from the base to the end of the last sample of any component (grk_amd_surface_bytes); SurfaceError with the reason for
+    an invalid surface"""
+    dx, dy = _sampling(sampling)
+    why = C.c_char_p()
+    n = lib().grk_amd_surface_bytes(C.byref(layout), C.byref(base), dx, dy, C.byref(surface), C.byref(why))
+    if n == 0:
+        reason = (why.value or b"").decode()
+        raise SurfaceError("surface_bytes", -2 if "16 bits" in reason else -3, reason)
+    return int(n)
+
+
+def surface_plan(layout, base, sampling, surface, cap, base_align=0, decode=False, allow_direct=True):
+    """The plan of encode_surface / decode_surface (grk_amd_surface_plan): per run of components (in_place, PixelLayout, offset of
+    its first sample); SurfaceError with the refusal"""
+    dx, dy = _sampling(sampling)
+    why = C.c_char_p()
+    flags = (C.c_uint8 * 4)()
+    lays = (PixelLayout * 4)()
+    at = (C.c_uint64 * 4)()
+    n = lib().grk_amd_surface_plan(C.byref(layout), C.byref(base), dx, dy, C.byref(surface), int(cap), int(base_align), int(bool(decode)),
+                                   int(bool(allow_direct)), flags, lays, at, 4, C.byref(why))
+    if n < 0:
+        raise SurfaceError("surface_plan", n, (why.value or b"").decode())
+    return [(bool(flags[r]), lays[r], int(at[r])) for r in range(n)]
+
+
 VIEW_UNIT_DTYPE = np.dtype([("tile", np.uint32), ("first_comp", np.uint32), ("num_comps", np.uint32), ("w", np.uint32), ("h", np.uint32),
                             ("x", np.int32), ("y", np.int32), ("whole", np.uint32)])
 
@@ -244,6 +339,20 @@ def lib():
             L.grk_amd_decode_image_counters.restype = u64
             L.grk_amd_decode_image_counters.argtypes = [vp, i32]
             L.grk_amd_place_tiles_clipped_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, u32, u32]
+        if hasattr(L, "grk_amd_encode_surface"):
+            PS, pu8 = C.POINTER(Surface), C.POINTER(C.c_uint8)
+            L.grk_amd_surface_bytes.restype = u64
+            L.grk_amd_surface_bytes.argtypes = [PL, PP, pu8, pu8, PS, C.POINTER(C.c_char_p)]
+            L.grk_amd_surface_format.argtypes = [i32, PL, u32, u64, PS, pu8, pu8, C.POINTER(u32), C.POINTER(u64)]
+            L.grk_amd_surface_plan.argtypes = [PL, PP, pu8, pu8, PS, u64, u32, i32, i32, pu8, C.POINTER(PixelLayout), C.POINTER(u64), u32,
+                                               C.POINTER(C.c_char_p)]
+            L.grk_amd_encode_surface.restype = C.c_int64
+            L.grk_amd_encode_surface.argtypes = [vp, PL, PP, pu8, pu8, PS, vp, u64, i32, u32, vp, u64]
+            L.grk_amd_decode_surface.argtypes = [vp, vp, u64, PS, vp, u64, i32]
+            L.grk_amd_surface_counters.restype = u64
+            L.grk_amd_surface_counters.argtypes = [vp, i32]
+            L.grk_amd_surface_cut_device.argtypes = [vp, vp, u64, C.POINTER(SurfaceComp), u32, u32, u32, u32, u32, vp, vp]
+            L.grk_amd_surface_place_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, C.POINTER(SurfaceComp), vp, u64]
         _lib = L
     return _lib
 
@@ -614,6 +723,63 @@ class Context:
         if n < 0:
             raise RuntimeError("encode_image_subsampled failed: %d (%s)" % (n, self._L.grk_amd_last_error(self._h).decode()))
         return out[:n].tobytes()
+
+    def _surface_fail(self, what, rc):
+        raise SurfaceError(what, rc, self._L.grk_amd_last_error(self._h).decode())
+
+    def encode_surface(self, layout, base, sampling, surface, pixels, flags=0, cap=None):
+        """A video surface -> codestream bytes (grk_amd_encode_surface).  pixels: a uint8 numpy array holding the surface (host), or a
+        device pointer (int) together with `cap`, the bytes behind it."""
+        dx, dy = _sampling(sampling)
+        on_device = not isinstance(pixels, np.ndarray)
+        if on_device:
+            ptr, nbytes = int(pixels), int(cap)
+        else:
+            if pixels.dtype != np.uint8 or not pixels.flags.c_contiguous:
+                raise ValueError("pixels: a contiguous uint8 array")
+            ptr, nbytes = pixels.ctypes.data, pixels.nbytes if cap is None else int(cap)
+        out_cap = nbytes * 4 + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        n = self._L.grk_amd_encode_surface(self._h, C.byref(layout), C.byref(base), dx, dy, C.byref(surface), ptr, nbytes, int(on_device),
+                                           flags, out.ctypes.data, out_cap)
+        if n < 0:
+            self._surface_fail("encode_surface", n)
+        return out[:n].tobytes()
+
+    def decode_surface(self, cs, surface, pixels, cap=None):
+        """Codestream -> the components' samples on a surface (grk_amd_decode_surface); every other byte keeps its value.  pixels: a
+        uint8 numpy array (host: written in place) or a device pointer (int) with `cap` (asynchronous: decode_status joins)."""
+        buf = _cs_array(cs)
+        on_device = not isinstance(pixels, np.ndarray)
+        if on_device:
+            ptr, nbytes = int(pixels), int(cap)
+        else:
+            if pixels.dtype != np.uint8 or not pixels.flags.c_contiguous:
+                raise ValueError("pixels: a contiguous uint8 array")
+            ptr, nbytes = pixels.ctypes.data, pixels.nbytes if cap is None else int(cap)
+        rc = self._L.grk_amd_decode_surface(self._h, buf.ctypes.data, buf.size, C.byref(surface), ptr, nbytes, int(on_device))
+        if rc:
+            self._surface_fail("decode_surface", rc)
+
+    def surface_counters(self):
+        """(units handled in place, units staged, launches of the two surface kernels) by this context's surface calls so far"""
+        return tuple(int(self._L.grk_amd_surface_counters(self._h, k)) for k in range(3))
+
+    def surface_cut_device(self, d_surface, surface_bytes, comps, bps, nunits, w, h, origins, d_tiles):
+        """KS alone: comps [(offset, row_pitch, step)], origins [(x, y)] of every unit's first sample in the components"""
+        cs = (SurfaceComp * len(comps))(*[SurfaceComp(int(o), int(p), int(s), 0) for o, p, s in comps])
+        r = np.ascontiguousarray(origins, np.uint32).reshape(-1)
+        rc = self._L.grk_amd_surface_cut_device(self._h, d_surface, int(surface_bytes), cs, len(comps), bps, nunits, w, h, r.ctypes.data, d_tiles)
+        if rc:
+            self._surface_fail("surface_cut_device", rc)
+
+    def surface_place_device(self, d_tiles, nunits, w, h, bps, origins, comps, d_surface, surface_bytes):
+        """KD alone (the reverse)"""
+        cs = (SurfaceComp * len(comps))(*[SurfaceComp(int(o), int(p), int(s), 0) for o, p, s in comps])
+        r = np.ascontiguousarray(origins, np.uint32).reshape(-1)
+        rc = self._L.grk_amd_surface_place_device(self._h, d_tiles, nunits, w, h, len(comps), bps, r.ctypes.data, cs, d_surface, int(surface_bytes))
+        if rc:
+            self._surface_fail("surface_place_device", rc)
 
     def fetch_table(self, nblocks):
         table = np.zeros(nblocks, CODED_DTYPE)

@@ -205,6 +205,9 @@ struct grk_amd_ctx {
     DevBuf img_coded, img_tiles, img_pixels, img_moves, img_rects, img_status;
     uint64_t img_launches[2] = {0, 0};
     uint64_t img_counters[2] = {0, 0};                      // tiles read, codestream bytes uploaded (grk_amd_decode_image_counters)
+    // grk_amd_encode_surface / grk_amd_decode_surface share those buffers: img_pixels a host surface's copy, img_tiles a group's staged
+    // units, img_rects the units' origins; units handled in place, units staged, launches of KS + KD (grk_amd_surface_counters)
+    uint64_t surf_counters[3] = {0, 0, 0};
     // timing
     bool timing = false;
     Timer timers[10];
@@ -248,6 +251,13 @@ int sequence_streams(grk_amd_ctx* k, bool part1);                               
 struct PixelLayout { uint32_t lay, channels, xstep, fill; uint64_t row, kstep, tile, bytes; };
 bool resolve_pixel_layout(const grk_amd_tile_params& p, const grk_amd_pixel_layout* l, uint32_t w, uint32_t h, uint32_t ntiles,
                           PixelLayout& out, const char** why);
+
+// KS (place = false) or KD for `count` units of w x h samples of one run, tight at d_tiles, their origins (device memory) at
+// d_origins; the surface's first byte at d_surface (surface.cpp).  The caller checked the surface against its buffer
+namespace grk_amd { struct ResolvedSurface; struct CompRun; }
+int queue_surface_kernel(grk_amd_ctx* c, bool place, const grk_amd::ResolvedSurface& rs, const grk_amd::CompRun& run, void* d_surface,
+                         void* d_tiles, uint32_t count, uint32_t w, uint32_t h, const uint32_t* d_origins);                  // surface.cpp
+bool surface_direct_allowed();            // GRK_AMD_SURFACE_DIRECT != 0, read per call (surface.cpp)
 
 // ---- steps the encode and decode units share ----
 // The first steps of a grk_amd_stage_* entry point: the side streams joined (where the stage reads what they write), the null

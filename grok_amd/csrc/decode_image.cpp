@@ -9,9 +9,12 @@
 // grk_amd_decode_image_view is the same path for a view of the image (reduced resolution, a window): image_view_plan.cpp says which
 // tiles it touches and where every unit goes; only those tiles' packets are read and only their tile-parts uploaded, as one compact
 // coded buffer; the tile decoder runs at the view's reduce, and KP clips the tiles that the window holds in part.
+// grk_amd_decode_surface is the same path again with a video surface as the destination (surface_plan.h): a one-tile image's runs that
+// are a pixel layout are decoded straight onto it, every other unit into tight planes that KD (kernels_surface.hip) places.
 #include "context.h"
 #include "image.h"
 #include "image_view_plan.h"
+#include "surface_plan.h"
 #include "t2_reader.h"
 #include <thread>
 
@@ -140,7 +143,10 @@ extern "C" int grk_amd_place_tiles_clipped_device(grk_amd_ctx* c, const void* ti
     return GRK_AMD_OK;
 }
 
-static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap, int pixels_on_device)
+// surf != nullptr (grk_amd_decode_surface): the destination is the caller's surface as *surf describes it -- every component at its own
+// size wherever it lies there, sub-sampled or not; the surface is resolved against the stream's header here
+static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap, int pixels_on_device,
+                       const grk_amd_surface* surf = nullptr)
 {
     grk_amd_stream_info info;
     std::string why;
@@ -153,10 +159,10 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         rc = plan_image_view(info, view, plan, &pwhy);
         if (rc) return fail(c, rc, pwhy);
     }
-    const bool sub = plan.sub, up = sub && c->dec_upsample;
+    const bool sub = plan.sub || surf, up = sub && !surf && c->dec_upsample;
     const uint32_t red = plan.reduce;
     if (red && up) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a reduced resolution of sub-sampled components together with upsampling (grk_amd_set_decode_upsample)");
-    if (sub && !up) {       // (components of different sizes have no interleaved form, and each plane is tight: as grk_amd_encode_image_subsampled)
+    if (sub && !up && !surf) {       // (components of different sizes have no interleaved form, and each plane is tight: as grk_amd_encode_image_subsampled)
         const grk_amd_pixel_layout& l = c->dec_layout;
         if (l.interleaved || l.channels || l.row_pitch || l.plane_pitch || l.tile_pitch)
             return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a decode pixel layout for sub-sampled components without upsampling (grk_amd_set_decode_upsample)");
@@ -170,7 +176,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     PixelLayout ipx;
     {
         const char* lwhy = "";
-        if (W >> 32 || H >> 32 || !resolve_pixel_layout(info.base, &c->dec_layout, (uint32_t)W, (uint32_t)H, 1, ipx, &lwhy)) return fail(c, GRK_AMD_ERR_INVALID, lwhy);
+        if (W >> 32 || H >> 32 || !resolve_pixel_layout(info.base, surf ? nullptr : &c->dec_layout, (uint32_t)W, (uint32_t)H, 1, ipx, &lwhy)) return fail(c, GRK_AMD_ERR_INVALID, lwhy);
     }
     // ... or, sub-sampled components as they are: component k's plane of its own size, tight, the planes back to back
     struct Plane { uint64_t at, w, h, x0, y0; };          // (x0, y0: the component's first sample at full size, for KU)
@@ -182,6 +188,15 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         total += plane[k].w * plane[k].h * bps;
     }
     if (!sub || up) total = ipx.bytes;
+    // ... or wherever the surface puts them: no two of them on one byte, all of it inside `cap`
+    ResolvedSurface rs;
+    if (surf) {
+        const char* swhy = "";
+        rc = resolve_surface(&info.layout, &info.base, info.comp_dx, info.comp_dy, surf, rs, &swhy);
+        if (!rc) rc = check_surface_disjoint(rs, &swhy);
+        if (rc) return fail(c, rc, swhy);
+        total = rs.bytes;
+    }
     if (total > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "the image does not fit `cap`");
     // the units, grouped by geometry (units of one group are of one size at every reduce: same_geometry compares every resolution)
     const uint32_t nr = (uint32_t)runs.size(), ntt = (uint32_t)plan.tiles.size(), nu = ntt * nr;
@@ -304,7 +319,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     std::vector<grk_amd_coded_block> table;
     // the region decoder's own conditions (grk_amd_decode_region): a DWT level left, samples of at most 16 bits
     const bool region_ok = info.base.num_levels > red && bps <= 2;
-    if (nt == 1 && nr == 1 && !up && (plan.units[0].whole || region_ok)) {
+    if (!surf && nt == 1 && nr == 1 && !up && (plan.units[0].whole || region_ok)) {
         // one tile: decoded straight into the destination (host pixels: grk_amd_decode_tiles repeats a group that leaves the int16
         // planes by itself) -- a window of it by the region decoder, whose cost follows the window
         const ViewUnit& u = plan.units[0];
@@ -315,7 +330,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
                                      (uint32_t)(-u.y + (int64_t)H), pixels, pixels_on_device);
     }
     HIP_TRY(c, c->img_status.ensure(64), "alloc status");
-    if (nt == 1 && nr > 1 && !up) {
+    if (!surf && nt == 1 && nr > 1 && !up) {
         // one tile of several runs: run by run straight into the run's planes; a decode into device pixels leaves its status to
         // the next one's, so it is kept as for the groups below
         if (pixels_on_device) HIP_TRY(c, hipMemsetAsync(c->img_status.p, 0, 4, c->stream), "clear status");
@@ -336,6 +351,86 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         if (pixels_on_device)
             HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->flag.p, (const unsigned int*)c->img_status.p, true, c->stream), "hand over status");
         return GRK_AMD_OK;
+    }
+    // a group's batch (`table`: its rows) into device memory at dst, its status kept in the image's
+    auto decode_group = [&](const grk_amd_tile_params& p, uint32_t n, void* dst) -> int {
+        int drc = grk_amd_decode_tiles(c, &p, n, table.data(), c->img_coded.p, coded_bytes, 1, dst, 1); if (drc) return drc;
+        // The int16-plane rule (include/grok_amd.h, grk_amd_set_decode_planes16).  A decode into a device buffer does not repeat
+        // itself: with host pixels this call joins behind a group that may use those planes, reads its status and repeats it
+        // with int32 planes; with device pixels the status goes to grk_amd_decode_status like any other
+        if (!pixels_on_device && c->dec_planes16 && ht && !p.irreversible && p.prec <= 8) {
+            drc = grk_amd_decode_status(c);
+            if (drc == GRK_AMD_ERR_RANGE) {
+                c->dec_planes16 = false;
+                drc = grk_amd_decode_tiles(c, &p, n, table.data(), c->img_coded.p, coded_bytes, 1, dst, 1);
+                c->dec_planes16 = true;
+            }
+            if (drc) return drc;
+        }
+        HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->img_status.p, (const unsigned int*)c->flag.p, false, c->stream), "keep status");
+        return GRK_AMD_OK;
+    };
+    if (surf) {
+        // Onto a surface.  The image's copy of a host surface travels both ways (what is no sample stays); a run of a one-tile image
+        // that the plan (surface_plan.h) finds expressible as a pixel layout is decoded straight onto the surface through it, every
+        // other unit into tight planes that KD places
+        uint8_t* d_surf = (uint8_t*)pixels;
+        if (!pixels_on_device) {
+            HIP_TRY(c, c->img_pixels.ensure(total), "alloc the surface"); d_surf = (uint8_t*)c->img_pixels.p;
+            rc = copy_h2d(c, d_surf, pixels, total); if (rc) return rc;
+        }
+        const bool direct = surface_direct_allowed();
+        std::vector<SurfaceRoute> route(nr);
+        for (uint32_t r = 0; r < nr; ++r)
+            route[r] = plan_surface_run(rs, runs[r], nt == 1, true, direct, pixels_on_device ? cap : total, (uint32_t)((uintptr_t)d_surf & 3u));
+        std::vector<std::vector<uint32_t>> staged(g.members.size());
+        std::vector<uint32_t> origins;
+        uint64_t group_bytes = 0;
+        for (size_t k = 0; k < g.members.size(); ++k) {
+            for (uint32_t u : g.members[k]) if (!route[u % nr].in_place) staged[k].push_back(u);      // (sorted run by run above)
+            for (uint32_t u : staged[k]) {
+                const SurfacePlane& sp = rs.comp[runs[u % nr].first];
+                origins.push_back((uint32_t)(tp[u].tile_x0 - sp.x0));
+                origins.push_back((uint32_t)(tp[u].tile_y0 - sp.y0));
+            }
+            if (!staged[k].empty())
+                group_bytes = std::max<uint64_t>(group_bytes, (uint64_t)tp[staged[k][0]].tile_w * tp[staged[k][0]].tile_h * tp[staged[k][0]].num_comps * bps * staged[k].size());
+        }
+        HIP_TRY(c, c->img_tiles.ensure(group_bytes), "alloc a group's units");
+        HIP_TRY(c, c->img_rects.ensure(origins.size() * 4 + 8), "alloc origins");
+        if (!origins.empty()) HIP_TRY(c, hipMemcpy(c->img_rects.p, origins.data(), origins.size() * 4, hipMemcpyHostToDevice), "upload origins");
+        HIP_TRY(c, hipMemsetAsync(c->img_status.p, 0, 4, c->stream), "clear status");
+        struct KeepLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~KeepLayout() { c->dec_layout = keep; } } keep{c, c->dec_layout};
+        size_t origin_at = 0;
+        for (size_t k = 0; k < g.members.size(); ++k) {
+            for (uint32_t u : g.members[k]) {
+                const SurfaceRoute& r = route[u % nr];
+                if (!r.in_place) continue;
+                c->dec_layout = r.layout;
+                rc = group_tables(std::vector<uint32_t>{u}, table); if (rc) return rc;
+                rc = decode_group(tp[u], 1, d_surf + r.at); if (rc) return rc;
+                ++c->surf_counters[0];
+            }
+            const std::vector<uint32_t>& S = staged[k];
+            if (S.empty()) continue;
+            const grk_amd_tile_params& p = tp[S[0]];
+            c->dec_layout = grk_amd_pixel_layout{};
+            rc = group_tables(S, table); if (rc) return rc;
+            rc = decode_group(p, (uint32_t)S.size(), c->img_tiles.p); if (rc) return rc;
+            const size_t unit_size = (size_t)p.tile_w * p.tile_h * p.num_comps * bps;
+            for (size_t i0 = 0, i1; i0 < S.size(); i0 = i1) {          // the group's units of one run: one launch
+                for (i1 = i0 + 1; i1 < S.size() && S[i1] % nr == S[i0] % nr;) ++i1;
+                rc = queue_surface_kernel(c, true, rs, runs[S[i0] % nr], d_surf, (uint8_t*)c->img_tiles.p + i0 * unit_size, (uint32_t)(i1 - i0), p.tile_w, p.tile_h,
+                                          (const uint32_t*)c->img_rects.p + 2 * (origin_at + i0));
+                if (rc) return rc;
+            }
+            c->surf_counters[1] += S.size();
+            origin_at += S.size();
+        }
+        HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->flag.p, (const unsigned int*)c->img_status.p, true, c->stream), "hand over status");
+        if (pixels_on_device) return GRK_AMD_OK;
+        rc = copy_d2h(c, pixels, d_surf, total); if (rc) return rc;
+        return grk_amd_decode_status(c);
     }
     void* d_img = pixels;
     if (!pixels_on_device) {
@@ -390,20 +485,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         const uint32_t uw = plan.units[G[0]].w, uh = plan.units[G[0]].h;        // (the group's units at the view's reduce)
         if (!uw || !uh) { rect_at += G.size(); continue; }                     // nothing of them is left at this reduce
         rc = group_tables(G, table); if (rc) return rc;
-        rc = grk_amd_decode_tiles(c, &p, (uint32_t)G.size(), table.data(), c->img_coded.p, coded_bytes, 1, c->img_tiles.p, 1); if (rc) return rc;
-        // The int16-plane rule (include/grok_amd.h, grk_amd_set_decode_planes16).  A decode into a device buffer does not repeat
-        // itself: with host pixels this call joins behind a group that may use those planes, reads its status and repeats it
-        // with int32 planes; with device pixels the status goes to grk_amd_decode_status like any other
-        if (!pixels_on_device && c->dec_planes16 && ht && !p.irreversible && p.prec <= 8) {
-            rc = grk_amd_decode_status(c);
-            if (rc == GRK_AMD_ERR_RANGE) {
-                c->dec_planes16 = false;
-                rc = grk_amd_decode_tiles(c, &p, (uint32_t)G.size(), table.data(), c->img_coded.p, coded_bytes, 1, c->img_tiles.p, 1);
-                c->dec_planes16 = true;
-            }
-            if (rc) return rc;
-        }
-        HIP_TRY(c, launch_t2dec_or_status((unsigned int*)c->img_status.p, (const unsigned int*)c->flag.p, false, c->stream), "keep status");
+        rc = decode_group(p, (uint32_t)G.size(), c->img_tiles.p); if (rc) return rc;
         const size_t unit_size = (size_t)uw * uh * (unit_ch ? unit_ch : p.num_comps) * bps;
         for (size_t i0 = 0, i1; i0 < G.size(); i0 = i1) {          // the group's units of one run: one launch into that run's planes
             for (i1 = i0 + 1; i1 < G.size() && G[i1] % nr == G[i0] % nr;) ++i1;
@@ -443,6 +525,15 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
     if (c->dec_reduce) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_decode_image at reduced resolution");
     if (!c->dec_kids.empty()) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_decode_image on a context with a decode sequence (grk_amd_set_decode_pipelining)");
     return decode_view(c, cs, len, nullptr, pixels, cap, pixels_on_device);
+}
+
+extern "C" int grk_amd_decode_surface(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels, uint64_t cap,
+                                      int pixels_on_device)
+{
+    if (!c || !cs || !pixels || !surface) return GRK_AMD_ERR_INVALID;
+    if (c->dec_reduce) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_decode_surface at reduced resolution");
+    if (!c->dec_kids.empty()) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_decode_surface on a context with a decode sequence (grk_amd_set_decode_pipelining)");
+    return decode_view(c, cs, len, nullptr, pixels, cap, pixels_on_device, surface);
 }
 
 extern "C" int grk_amd_decode_image_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap,

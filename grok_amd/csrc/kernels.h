@@ -306,4 +306,22 @@ hipError_t launch_t2dec_fill(const FillArgs& a, hipStream_t s);
 // *into |= *from (assign: = ) on the stream: a group's decode status into the image's
 hipError_t launch_t2dec_or_status(unsigned int* into, const unsigned int* from, bool assign, hipStream_t s);
 
+// ---- KS / KD: units between a video surface and tight unit planes (kernels_surface.hip) ----------------------------------------
+// nunits units of ncomp x h x w samples of bps (1 or 2) bytes lie back to back, tight, component-major at `tiles`; unit u's first
+// sample is sample (origins[2 u], origins[2 u + 1]) of each component, and sample (x, y) of component k lies at
+// surface + comp[k].offset + y * comp[k].row_pitch + x * comp[k].step * bps.  The host checked every sample against the surface's size.
+// KS (cut) reads the surface and writes the tiles; KD (place) the reverse, writing no byte of the surface that is no sample.
+// pair (KD, set by the launcher): ncomp = 2 one-byte components of step 2 and one pitch, one byte apart -- both rows leave merged,
+// in 16-byte stores
+struct SurfaceKernelComp { uint64_t offset, row_pitch; uint32_t step, pad; };
+struct SurfaceArgs {
+    uint8_t* surface; uint8_t* tiles;
+    uint32_t nunits, w, h, ncomp, bps;
+    const uint32_t* origins;
+    SurfaceKernelComp comp[4];
+    uint32_t pair;
+};
+hipError_t launch_surface_cut(const SurfaceArgs& a, hipStream_t s);
+hipError_t launch_surface_place(const SurfaceArgs& a, hipStream_t s);
+
 } // namespace grk_amd

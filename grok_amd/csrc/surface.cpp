@@ -1,0 +1,192 @@
+// grok_amd/csrc/surface.cpp -- a video surface (NV12, I420, NV16 ...; include/grok_amd.h: grk_amd_surface) into a codestream
+// (grk_amd_encode_surface), the two surface kernels as calls of their own, and what the decode side (decode_image.cpp:
+// grk_amd_decode_surface) shares with it.  The units and groups are grk_amd_encode_image_subsampled's (image.h): a unit is a tile's
+// run of components of one size, the units are grouped by geometry, a group is one grk_amd_encode_tiles batch.  Where a unit's pixels
+// come from is the plan's word (surface_plan.h): the surface itself through a pixel layout, or tight planes that KS cut out of it.
+#include "context.h"
+#include "image.h"
+#include "surface_plan.h"
+
+using namespace grk_amd;
+
+int queue_surface_kernel(grk_amd_ctx* c, bool place, const ResolvedSurface& rs, const CompRun& run, void* d_surface, void* d_tiles,
+                         uint32_t count, uint32_t w, uint32_t h, const uint32_t* d_origins)
+{
+    SurfaceArgs a{};
+    a.surface = (uint8_t*)d_surface; a.tiles = (uint8_t*)d_tiles;
+    a.nunits = count; a.w = w; a.h = h; a.ncomp = run.count; a.bps = rs.bps;
+    a.origins = d_origins;
+    for (uint32_t k = 0; k < run.count && k < 4; ++k) {
+        const SurfacePlane& p = rs.comp[run.first + k];
+        a.comp[k] = SurfaceKernelComp{p.offset, p.row_pitch, p.step, 0};
+    }
+    HIP_TRY(c, place ? launch_surface_place(a, c->stream) : launch_surface_cut(a, c->stream), place ? "launch surface placement" : "launch surface cut");
+    ++c->surf_counters[2];
+    return GRK_AMD_OK;
+}
+
+extern "C" uint64_t grk_amd_surface_counters(grk_amd_ctx* c, int which)
+{
+    return c && which >= 0 && which < 3 ? c->surf_counters[which] : 0;
+}
+
+// ---- the kernels alone ---------------------------------------------------------------------------------------------------------
+static int surface_kernel_device(grk_amd_ctx* c, bool place, void* surface, uint64_t surface_bytes, const grk_amd_surface_comp* comps, uint32_t ncomp,
+                                 uint32_t bps, uint32_t nunits, uint32_t w, uint32_t h, const uint32_t* origins, void* tiles)
+{
+    if (!c || !surface || !comps || !origins || !tiles || !ncomp || ncomp > 4 || (bps != 1 && bps != 2) || !nunits || nunits > 65535 || !w || !h)
+        return GRK_AMD_ERR_INVALID;
+    ResolvedSurface rs;
+    rs.bps = bps;
+    uint64_t ox = 0, oy = 0;                         // the farthest origin: every unit is of one size
+    for (uint32_t u = 0; u < nunits; ++u) { ox = std::max<uint64_t>(ox, origins[2 * u]); oy = std::max<uint64_t>(oy, origins[2 * u + 1]); }
+    for (uint32_t k = 0; k < ncomp; ++k) {
+        const grk_amd_surface_comp& sc = comps[k];
+        const uint32_t step = sc.step ? sc.step : 1u;
+        if (step > 4 || sc.offset % bps || sc.row_pitch % bps || (sc.offset | sc.row_pitch) >> 48) return fail(c, GRK_AMD_ERR_INVALID, "surface: a component's step, offset or pitch");
+        // the component as far as the units reach: rows that do not run into the next, the last sample inside the surface
+        const uint64_t cols = ox + w, rows = oy + h, row_span = ((cols - 1) * step + 1) * bps;
+        if (rows > 1 && sc.row_pitch < row_span) return fail(c, GRK_AMD_ERR_INVALID, "surface: a row pitch is smaller than a row");
+        if (sc.offset + (rows - 1) * sc.row_pitch + row_span > surface_bytes) return fail(c, GRK_AMD_ERR_INVALID, "surface: a unit outside the surface");
+        rs.comp.push_back(SurfacePlane{sc.offset, sc.row_pitch, cols, rows, 0, 0, step});
+    }
+    if (place) {
+        const char* why = "";
+        // (of what the units cover: rectangles of the components' top-left cols x rows)
+        if (check_surface_disjoint(rs, &why)) return fail(c, GRK_AMD_ERR_INVALID, why);
+    }
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the origins' device copy may still be read by an earlier call)
+    HIP_TRY(c, c->img_rects.ensure((size_t)nunits * 8), "alloc origins");
+    HIP_TRY(c, hipMemcpy(c->img_rects.p, origins, (size_t)nunits * 8, hipMemcpyHostToDevice), "upload origins");
+    return queue_surface_kernel(c, place, rs, CompRun{0, ncomp, false}, surface, tiles, nunits, w, h, (const uint32_t*)c->img_rects.p);
+}
+
+extern "C" int grk_amd_surface_cut_device(grk_amd_ctx* c, const void* surface, uint64_t surface_bytes, const grk_amd_surface_comp* comps, uint32_t ncomp,
+                                          uint32_t bps, uint32_t nunits, uint32_t w, uint32_t h, const uint32_t* origins, void* tiles)
+{
+    return surface_kernel_device(c, false, const_cast<void*>(surface), surface_bytes, comps, ncomp, bps, nunits, w, h, origins, tiles);
+}
+
+extern "C" int grk_amd_surface_place_device(grk_amd_ctx* c, const void* tiles, uint32_t nunits, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                                            const uint32_t* origins, const grk_amd_surface_comp* comps, void* surface, uint64_t surface_bytes)
+{
+    return surface_kernel_device(c, true, surface, surface_bytes, comps, ncomp, bps, nunits, w, h, origins, const_cast<void*>(tiles));
+}
+
+// ---- surface -> codestream -----------------------------------------------------------------------------------------------------
+bool surface_direct_allowed()
+{
+    const char* const e = std::getenv("GRK_AMD_SURFACE_DIRECT");
+    return !(e && std::strcmp(e, "0") == 0);
+}
+
+extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                          const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                          const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out) return GRK_AMD_ERR_INVALID;
+    ResolvedSurface rs;
+    {
+        const char* why = "";
+        const int rc = resolve_surface(im, base, comp_dx, comp_dy, surface, rs, &why);
+        if (rc) return fail(c, rc, why);
+    }
+    if (rs.bytes > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "surface: it does not fit `cap`");
+    const int64_t nt = grk_amd_layout_num_tiles(im);
+    if (nt < 0) return nt;
+    const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps, bps = rs.bps;
+    const std::vector<CompRun> runs = comp_runs(nc, base->mct != 0, comp_dx, comp_dy);
+    const uint32_t nr = (uint32_t)runs.size();
+    std::vector<Unit> units;                                 // [tile][run]
+    UnitGroups g;
+    for (uint32_t t = 0; t < ntiles; ++t)
+        for (uint32_t k = 0; k < nr; ++k) {
+            Unit u{{}, runs[k].first};
+            int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].first], comp_dy[runs[k].first], t, &u.p);
+            if (rc) return rc;
+            u.p.num_comps = (uint16_t)runs[k].count;
+            u.p.mct = runs[k].mct ? 1 : 0;
+            units.push_back(u);
+            rc = add_unit(g, u.p);
+            if (rc) return rc;
+        }
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    // the surface on the device: the caller's, or a copy of a host surface's extent
+    uint8_t* d_surf = (uint8_t*)const_cast<void*>(pixels);
+    if (!pixels_on_device) {
+        HIP_TRY(c, c->img_pixels.ensure(rs.bytes + 16), "alloc the surface");
+        d_surf = (uint8_t*)c->img_pixels.p;
+        const int rc = copy_h2d(c, d_surf, pixels, rs.bytes); if (rc) return rc;
+    }
+    // each run's route; the staged units group after group, within a group run by run, and their origins in that order
+    const bool direct = surface_direct_allowed();
+    std::vector<SurfaceRoute> route(nr);
+    for (uint32_t k = 0; k < nr; ++k)
+        route[k] = plan_surface_run(rs, runs[k], ntiles == 1, false, direct, cap, (uint32_t)((uintptr_t)d_surf & 3u));
+    std::vector<std::vector<uint32_t>> staged(g.members.size());
+    std::vector<uint32_t> origins;
+    size_t group_bytes = 0;
+    for (size_t k = 0; k < g.members.size(); ++k) {
+        for (uint32_t u : g.members[k]) if (!route[u % nr].in_place) staged[k].push_back(u);
+        std::stable_sort(staged[k].begin(), staged[k].end(), [nr](uint32_t a, uint32_t b) { return a % nr < b % nr; });
+        for (uint32_t u : staged[k]) {
+            const SurfacePlane& p = rs.comp[runs[u % nr].first];
+            origins.push_back((uint32_t)(units[u].p.tile_x0 - p.x0));
+            origins.push_back((uint32_t)(units[u].p.tile_y0 - p.y0));
+        }
+        if (!staged[k].empty()) group_bytes = std::max(group_bytes, unit_bytes(units[staged[k][0]], bps) * staged[k].size());
+    }
+    if (!origins.empty()) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");      // (the buffers below may still be read by an earlier call's kernels)
+        HIP_TRY(c, c->img_tiles.ensure(group_bytes), "alloc a group's units");
+        HIP_TRY(c, c->img_rects.ensure(origins.size() * 4), "alloc origins");
+        HIP_TRY(c, hipMemcpy(c->img_rects.p, origins.data(), origins.size() * 4, hipMemcpyHostToDevice), "upload origins");
+    }
+    // the batches read the surface through a run's layout, or staged planes in the default one: never the caller's setting
+    struct KeepLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~KeepLayout() { c->enc_layout = keep; } } keep{c, c->enc_layout};
+    std::vector<uint64_t> row_at(units.size() + 1, 0);       // unit u's rows start at row_at[u]
+    for (size_t u = 0; u < units.size(); ++u) row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].p.num_comps;
+    std::vector<grk_amd_coded_block> rows(row_at[units.size()]), table;
+    std::vector<uint8_t> coded;
+    // one batch: `batch` units of parameters p from d_px, their rows and bytes to the host
+    auto encode_batch = [&](const grk_amd_tile_params& p, const std::vector<uint32_t>& batch, const void* d_px) -> int {
+        const uint64_t bpu = (uint64_t)g.geoms[g.of[batch[0]]].blocks_per_comp * p.num_comps;
+        table.resize(bpu * batch.size());
+        uint64_t total = 0;
+        int rc = grk_amd_encode_tiles(c, &p, (uint32_t)batch.size(), d_px, 1, table.data(), &total);
+        if (rc) return rc;
+        const size_t at = coded.size();
+        coded.resize(at + total);
+        rc = grk_amd_fetch_coded(c, coded.data() + at, total);
+        if (rc) return rc;
+        for (size_t i = 0; i < batch.size(); ++i)
+            for (uint64_t b = 0; b < bpu; ++b) { rows[row_at[batch[i]] + b] = table[i * bpu + b]; rows[row_at[batch[i]] + b].offset += at; }
+        return GRK_AMD_OK;
+    };
+    size_t origin_at = 0;
+    for (size_t k = 0; k < g.members.size(); ++k) {
+        for (uint32_t u : g.members[k]) {
+            const SurfaceRoute& r = route[u % nr];
+            if (!r.in_place) continue;
+            c->enc_layout = r.layout;
+            const int rc = encode_batch(units[u].p, std::vector<uint32_t>{u}, d_surf + r.at); if (rc) return rc;
+            ++c->surf_counters[0];
+        }
+        const std::vector<uint32_t>& S = staged[k];
+        if (S.empty()) continue;
+        const grk_amd_tile_params& p = units[S[0]].p;
+        const size_t unit_size = unit_bytes(units[S[0]], bps);
+        for (size_t i0 = 0, i1; i0 < S.size(); i0 = i1) {           // the group's units of one run: one launch
+            for (i1 = i0 + 1; i1 < S.size() && S[i1] % nr == S[i0] % nr;) ++i1;
+            const int rc = queue_surface_kernel(c, false, rs, runs[S[i0] % nr], d_surf, (uint8_t*)c->img_tiles.p + i0 * unit_size, (uint32_t)(i1 - i0),
+                                                p.tile_w, p.tile_h, (const uint32_t*)c->img_rects.p + 2 * (origin_at + i0));
+            if (rc) return rc;
+        }
+        c->enc_layout = grk_amd_pixel_layout{};
+        const int rc = encode_batch(p, S, c->img_tiles.p); if (rc) return rc;
+        c->surf_counters[1] += S.size();
+        origin_at += S.size();
+    }
+    return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, out_cap);
+}

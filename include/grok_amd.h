@@ -710,6 +710,92 @@ int grk_amd_place_upsampled_device(grk_amd_ctx* ctx, const void* tiles, uint32_t
                                    const uint32_t* origins, uint32_t dx, uint32_t dy, void* image, uint32_t img_x0, uint32_t img_y0,
                                    uint32_t img_w, uint32_t img_h);
 
+/* ---- video surfaces: NV12, I420, NV16 ... (surface_plan.cpp, surface.cpp, kernels_surface.hip) --------------------------------
+ * What sub-sampled content is held in on a GPU: a video decoder or encoder, a capture card and hardware frames of a media
+ * framework hold a Y plane with a row pitch and then one plane of interleaved Cb / Cr pairs (NV12, NV21, NV16) or two pitched chroma
+ * planes (I420, YV12), with 16-bit samples for 10- and 12-bit video.  A SURFACE describes such a buffer component by component:
+ * sample (x, y) of component c lies at base + comp[c].offset + y * comp[c].row_pitch + x * comp[c].step * bps, bps = ceil(prec / 8),
+ * host endian, LSB-aligned; sample (0, 0) is the component's first sample of the image area and the component is
+ * grk_amd_stream_comp_size columns by rows (the ceil(x / dx) formulas of grk_amd_encode_image_subsampled above).
+ * Rules (GRK_AMD_ERR_INVALID): offset and row_pitch are multiples of bps, a non-zero pitch covers at least one row
+ * (((w_c - 1) * step + 1) * bps), step <= 4, at most 4 components; prec > 16: GRK_AMD_ERR_UNSUPPORTED.
+ * Two components of a DESTINATION (decode) may not share a byte.  Accepted placements of two components: disjoint extents;
+ * interleaved partners (equal pitch and step, offsets k * bps apart, 0 < k < step); side by side (equal pitch, the byte ranges of
+ * their rows inside a pitch disjoint and not wrapping).  Any other overlap: GRK_AMD_ERR_INVALID.  An encode only reads: any overlap. */
+typedef struct grk_amd_surface_comp {
+    uint64_t offset;     /* bytes from the surface's base to the component's first sample */
+    uint64_t row_pitch;  /* bytes between rows; 0 = tight: ((w_c - 1) * step + 1) * bps */
+    uint32_t step;       /* samples from one sample of a row to the next: 1 = a plane of its own, 2 = every other sample (chroma of
+                            NV12) ... 4; 0 reads as 1 */
+    uint32_t reserved;
+} grk_amd_surface_comp;
+typedef struct grk_amd_surface { grk_amd_surface_comp comp[4]; } grk_amd_surface;
+/* host only: bytes from the base to the end of the last sample of any component; 0 for an invalid surface, *why (may be NULL) then
+ * points to the reason (a string of the library's). */
+uint64_t grk_amd_surface_bytes(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                               const grk_amd_surface* surface, const char** why);
+/* host only: the surface and the factors of a named format for the image area of `im` with samples of `prec` bits.  pitch: the luma
+ * row pitch in bytes, 0 = the smallest valid one; interleaved chroma rows take `pitch`, planar chroma rows of the 4:2:x forms
+ * pitch / 2 rounded up to a multiple of bps, I444's planes `pitch`.  Planes follow each other at rows x pitch.  NV21 / YV12: Cr (V) lies
+ * first in memory -- component order stays Y, Cb, Cr.  *num_comps = 3, *bytes = grk_amd_surface_bytes.  GRK_AMD_ERR_INVALID: an unknown
+ * format, a pitch below a row or no multiple of bps; GRK_AMD_ERR_UNSUPPORTED: prec > 16. */
+#define GRK_AMD_SURFACE_NV12 0
+#define GRK_AMD_SURFACE_NV21 1
+#define GRK_AMD_SURFACE_I420 2
+#define GRK_AMD_SURFACE_YV12 3
+#define GRK_AMD_SURFACE_NV16 4
+#define GRK_AMD_SURFACE_I422 5
+#define GRK_AMD_SURFACE_I444 6
+int grk_amd_surface_format(int format, const grk_amd_image_layout* im, uint32_t prec, uint64_t pitch, grk_amd_surface* surface,
+                           uint8_t* comp_dx, uint8_t* comp_dy, uint32_t* num_comps, uint64_t* bytes);
+/* host only, no context: the plan of grk_amd_encode_surface (decode = 0) / grk_amd_decode_surface (decode != 0) for a surface of
+ * `cap` bytes whose base address is `base_align` modulo 4.  A unit -- a tile's run of consecutive components with equal factors --
+ * of a ONE-tile image goes to the tile coder IN PLACE, on the surface's own pointer, where the run is a grk_amd_pixel_layout:
+ *   planar       step 1, one pitch, a single component or offsets rising by one plane pitch of at least a plane's span;
+ *   interleaved  one step in 2..4 and one pitch of at least w * step * bps, offsets bps apart in component order; an encode takes
+ *                step >= the run's components (the others are skipped) where the pixels' extent lies inside `cap`, a decode needs
+ *                step == components (it would write `fill` into the others);
+ *   alignment    a decode's first sample on a 4-byte address (the inverse transform's pixel stores of the default layout are pairs
+ *                and dwords; pitched and interleaved stores fall back to single samples for odd pitches by themselves); an
+ *                encode's on a multiple of bps (8-bit device pixels off 4-byte alignment take the separate ingest pass).
+ * Every other unit -- multi-tile images, reversed component order (NV21, YV12), a lone component of interleaved pixels on decode,
+ * destinations off alignment -- is STAGED: cut out of / placed onto the surface by a kernel, through tight planes.  allow_direct = 0:
+ * all staged (what GRK_AMD_SURFACE_DIRECT=0 does).  in_place[r] (cap_runs entries, may be NULL): 1 / 0 per run, layouts[r] the layout
+ * of an in-place run, at[r] its first sample's offset.  Returns the number of runs, GRK_AMD_ERR_OVERFLOW when grk_amd_surface_bytes
+ * exceeds `cap` (or cap_runs is too small), else the surface's refusal; *why as above. */
+int grk_amd_surface_plan(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                         const grk_amd_surface* surface, uint64_t cap, uint32_t base_align, int decode, int allow_direct,
+                         uint8_t* in_place, grk_amd_pixel_layout* layouts, uint64_t* at, uint32_t cap_runs, const char** why);
+/* Surface -> codestream.  `pixels`: the surface's base, host memory or (pixels_on_device != 0) device memory, `cap` bytes.  The file is
+ * byte-identical to grk_amd_encode_image_subsampled's for the same samples as tight planes (all factors 1: to grk_amd_encode_image's in
+ * the default layout, colour transform included): same flags, any tile layout, image offsets, precincts, the five orders.  Units
+ * are coded in place or staged as grk_amd_surface_plan says (GRK_AMD_SURFACE_DIRECT=0, read per call: all staged); a host surface goes
+ * up as one copy of its extent.  Tier-2 is the host writer over the fetched rows.  The context's pixel layouts are neither consulted
+ * nor changed.  GRK_AMD_ERR_OVERFLOW before any work when the surface does not fit `cap`. */
+int64_t grk_amd_encode_surface(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                               const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                               const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap);
+/* Codestream -> surface: component c's samples on the surface are plane c of grk_amd_decode_image, every component at its own size
+ * (no view, no upsampling: the context's pixel layouts and grk_amd_set_decode_upsample are neither consulted nor changed), and every
+ * byte of [pixels, pixels + cap) that is no sample of a component keeps its value (a host surface travels both ways for that).  A
+ * device surface is asynchronous behind the reader: grk_amd_decode_status joins and reports, the int16-plane rule included; with a
+ * host surface the call repeats such a group with int32 planes by itself.  GRK_AMD_ERR_UNSUPPORTED as grk_amd_decode_image (a context
+ * with a decode reduce or a decode sequence among it); GRK_AMD_ERR_OVERFLOW, before anything is written, when the surface does not
+ * fit `cap`; GRK_AMD_ERR_INVALID for components that share bytes.  QCD words and segments are put back on return. */
+int grk_amd_decode_surface(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface,
+                           void* pixels, uint64_t cap, int pixels_on_device);
+/* cumulative per context: which = 0 units handled in place, 1 units staged, 2 launches of the two surface kernels */
+uint64_t grk_amd_surface_counters(grk_amd_ctx* ctx, int which);
+/* The two kernels alone (device pointers; queued on the context's stream).  nunits units of ncomp x h x w samples of bps (1 or 2)
+ * bytes lie back to back, tight, component-major at `tiles`; unit i's first sample is sample (origins[2 i], origins[2 i + 1]) of
+ * each component; comps[k] (ncomp <= 4 of them) places component k on the surface (row_pitch here is taken as it is: not 0).
+ * cut: surface -> tiles; place: tiles -> surface, writing no byte that is no sample (two 8-bit partners of step 2 in one call are
+ * merged into 16-byte stores).  Every sample is checked against surface_bytes on the host: GRK_AMD_ERR_INVALID outside it. */
+int grk_amd_surface_cut_device(grk_amd_ctx* ctx, const void* surface, uint64_t surface_bytes, const grk_amd_surface_comp* comps, uint32_t ncomp,
+                               uint32_t bps, uint32_t nunits, uint32_t w, uint32_t h, const uint32_t* origins, void* tiles);
+int grk_amd_surface_place_device(grk_amd_ctx* ctx, const void* tiles, uint32_t nunits, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
+                                 const uint32_t* origins, const grk_amd_surface_comp* comps, void* surface, uint64_t surface_bytes);
+
 /* ---- one image over the GPUs of a node (node.cpp) -------------------------------------------------------
  * Replaces the reference's tile-level task pool (codestream/CodeStreamCompress.cpp:535-603: tiles are independent tasks whose
  * tile-parts are written in index order) with one grk_amd_ctx + one host thread per device: tile t is coded on device

@@ -6,6 +6,7 @@
 #include "../../include/grok_amd.h"
 #include "geometry.h"
 #include "kernels.h"
+#include "pixel_layout.h"
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -246,11 +247,6 @@ int probe_streams(grk_amd_ctx* c);                                              
 int vetted_stream(grk_amd_ctx* c, hipStream_t* cur, const std::vector<hipStream_t>& against, int* replaced);     // streams.hip
 int join_side(grk_amd_ctx* c);                                                                                   // streams.hip
 int sequence_streams(grk_amd_ctx* k, bool part1);                                                                // streams.hip
-// A pixel layout resolved for tiles of w x h samples per component (context.hip): every pitch in bytes, `lay` as DwtLevelArgs::px_lay
-// (0: what the default layout amounts to), `bytes` the extent of ntiles tiles
-struct PixelLayout { uint32_t lay, channels, xstep, fill; uint64_t row, kstep, tile, bytes; };
-bool resolve_pixel_layout(const grk_amd_tile_params& p, const grk_amd_pixel_layout* l, uint32_t w, uint32_t h, uint32_t ntiles,
-                          PixelLayout& out, const char** why);
 
 // KS (place = false) or KD for `count` units of w x h samples of one run, tight at d_tiles, their origins (device memory) at
 // d_origins; the surface's first byte at d_surface (surface.cpp).  The caller checked the surface against its buffer
@@ -258,6 +254,9 @@ namespace grk_amd { struct ResolvedSurface; struct CompRun; }
 int queue_surface_kernel(grk_amd_ctx* c, bool place, const grk_amd::ResolvedSurface& rs, const grk_amd::CompRun& run, void* d_surface,
                          void* d_tiles, uint32_t count, uint32_t w, uint32_t h, const uint32_t* d_origins);                  // surface.cpp
 bool surface_direct_allowed();            // GRK_AMD_SURFACE_DIRECT != 0, read per call (surface.cpp)
+
+// a pixel layout of the context that a call sets for its own batches, put back when the call ends (KeepLayout keep{slot, slot};)
+struct KeepLayout { grk_amd_pixel_layout& slot; grk_amd_pixel_layout keep; ~KeepLayout() { slot = keep; } };
 
 // ---- steps the encode and decode units share ----
 // The first steps of a grk_amd_stage_* entry point: the side streams joined (where the stage reads what they write), the null

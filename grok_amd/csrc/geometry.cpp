@@ -1,5 +1,6 @@
 // grok_amd/csrc/geometry.cpp -- see geometry.h for the reference citations.
 #include "geometry.h"
+#include "image.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -254,3 +255,27 @@ bool same_geometry(const TileGeom& a, const TileGeom& b)
 
 
 } // namespace grk_amd
+
+// the next unit of a whole-image call into its geometry group (image.h)
+int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p)
+{
+    TileGeom geom;
+    const int rc = build_tile_geom(p, geom);
+    if (rc) return rc;
+    size_t k = 0;
+    for (; k < g.geoms.size(); ++k)
+        if (g.geoms[k].p.num_comps == p.num_comps && g.geoms[k].p.mct == p.mct && same_geometry(g.geoms[k], geom)) break;
+    if (k == g.geoms.size()) { g.geoms.push_back(std::move(geom)); g.members.emplace_back(); }
+    g.members[k].push_back((uint32_t)g.of.size());
+    g.of.push_back((uint32_t)k);
+    return GRK_AMD_OK;
+}
+
+extern "C" int64_t grk_amd_tile_num_blocks(const grk_amd_tile_params* p)
+{
+    if (!p) return GRK_AMD_ERR_INVALID;
+    grk_amd::TileGeom g;
+    int rc = grk_amd::build_tile_geom(*p, g);
+    if (rc != GRK_AMD_OK) return rc;
+    return (int64_t)g.blocks_per_comp * p->num_comps;
+}

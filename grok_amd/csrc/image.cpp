@@ -29,20 +29,6 @@ extern "C" int grk_amd_same_tile_geometry(const grk_amd_tile_params* a, const gr
 }
 
 // ---- the steps of the whole-image encoders (image.h) -------------------------------------------------------------------------
-int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p)
-{
-    TileGeom geom;
-    const int rc = build_tile_geom(p, geom);
-    if (rc) return rc;
-    size_t k = 0;
-    for (; k < g.geoms.size(); ++k)
-        if (g.geoms[k].p.num_comps == p.num_comps && g.geoms[k].p.mct == p.mct && same_geometry(g.geoms[k], geom)) break;
-    if (k == g.geoms.size()) { g.geoms.push_back(std::move(geom)); g.members.emplace_back(); }
-    g.members[k].push_back((uint32_t)g.of.size());
-    g.of.push_back((uint32_t)k);
-    return GRK_AMD_OK;
-}
-
 int grk_amd::plain_image(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,
                          std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g, const grk_amd_pixel_layout* lay)
 {
@@ -132,26 +118,6 @@ int64_t grk_amd::frame_file(const grk_amd_image_layout* im, const grk_amd_tile_p
     return (int64_t)end;
 }
 
-int grk_amd::parallel_for(size_t n, uint32_t threads, const std::function<int(size_t)>& fn)
-{
-    threads = (uint32_t)std::max<size_t>(1, std::min<size_t>(threads, n));
-    std::atomic<size_t> next{0};
-    std::atomic<int> rc{GRK_AMD_OK};
-    auto work = [&]() {
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= n || rc.load() != GRK_AMD_OK) return;
-            const int r = fn(i);
-            if (r != GRK_AMD_OK) { int ok = GRK_AMD_OK; (void)rc.compare_exchange_strong(ok, r); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (uint32_t i = 1; i < threads; ++i) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-    return rc.load();
-}
-
 extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                         const void* pixels, uint32_t flags, uint8_t* out, uint64_t cap)
 {
@@ -164,7 +130,7 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
     const grk_amd_pixel_layout whole = ctx->enc_layout;
     int64_t rc = plain_image(im, base, pixels, flags, tiles, src, g, &whole);
     if (rc) return rc;
-    struct StagedLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~StagedLayout() { c->enc_layout = keep; } } staged{ctx, whole};
+    KeepLayout staged{ctx->enc_layout, whole};
     ctx->enc_layout = staged_layout(src);
     const uint32_t ntiles = (uint32_t)tiles.size();
     // Tier-2 on the device (grk_amd_assemble_device; GRK_AMD_IMAGE_T2=host: the host writer below, which is also where a layout beyond

@@ -1,6 +1,8 @@
 // grok_amd/csrc/image.h -- the steps every whole-image encoder takes (grk_amd_encode_image, grk_amd_encode_image_subsampled,
 // grk_amd_node_encode_image; private to the library, defined in image.cpp): cut the image into units, group them by geometry, stage
-// each group's pixels, code each group as one grk_amd_encode_tiles batch, frame the file.
+// each group's pixels, code each group as one grk_amd_encode_tiles batch, frame the file.  The header itself is HIP-free, and so are
+// the homes of what the host planners (decode_image_plan.cpp, surface_plan.cpp, t2_reader.cpp) take from it: add_unit lives in
+// geometry.cpp, parallel_for in host_common.cpp; the whole-image decode's planning is decode_image_plan.h.
 #pragma once
 #include "../../include/grok_amd.h"
 #include "geometry.h"

@@ -2,7 +2,9 @@
 // (grk_amd_encode_surface), the two surface kernels as calls of their own, and what the decode side (decode_image.cpp:
 // grk_amd_decode_surface) shares with it.  The units and groups are grk_amd_encode_image_subsampled's (image.h): a unit is a tile's
 // run of components of one size, the units are grouped by geometry, a group is one grk_amd_encode_tiles batch.  Where a unit's pixels
-// come from is the plan's word (surface_plan.h): the surface itself through a pixel layout, or tight planes that KS cut out of it.
+// come from is the plan's word (surface_plan.h): the surface itself through a pixel layout, or tight planes that KS cut out of it --
+// which units are staged, their origins and the launches are plan_surface_staging's, the one plan that the decode side
+// (decode_image_plan.cpp) uses too.
 #include "context.h"
 #include "image.h"
 #include "surface_plan.h"
@@ -98,17 +100,17 @@ extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_la
     const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps, bps = rs.bps;
     const std::vector<CompRun> runs = comp_runs(nc, base->mct != 0, comp_dx, comp_dy);
     const uint32_t nr = (uint32_t)runs.size();
-    std::vector<Unit> units;                                 // [tile][run]
+    std::vector<grk_amd_tile_params> units;                  // [tile][run]
     UnitGroups g;
     for (uint32_t t = 0; t < ntiles; ++t)
         for (uint32_t k = 0; k < nr; ++k) {
-            Unit u{{}, runs[k].first};
-            int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].first], comp_dy[runs[k].first], t, &u.p);
+            grk_amd_tile_params p{};
+            int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].first], comp_dy[runs[k].first], t, &p);
             if (rc) return rc;
-            u.p.num_comps = (uint16_t)runs[k].count;
-            u.p.mct = runs[k].mct ? 1 : 0;
-            units.push_back(u);
-            rc = add_unit(g, u.p);
+            p.num_comps = (uint16_t)runs[k].count;
+            p.mct = runs[k].mct ? 1 : 0;
+            units.push_back(p);
+            rc = add_unit(g, p);
             if (rc) return rc;
         }
     HIP_TRY(c, hipSetDevice(c->device), "set device");
@@ -119,34 +121,22 @@ extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_la
         d_surf = (uint8_t*)c->img_pixels.p;
         const int rc = copy_h2d(c, d_surf, pixels, rs.bytes); if (rc) return rc;
     }
-    // each run's route; the staged units group after group, within a group run by run, and their origins in that order
+    // each run's route; what is staged (surface_plan.h): the units group after group, within a group run by run, their origins in that order
     const bool direct = surface_direct_allowed();
     std::vector<SurfaceRoute> route(nr);
     for (uint32_t k = 0; k < nr; ++k)
         route[k] = plan_surface_run(rs, runs[k], ntiles == 1, false, direct, cap, (uint32_t)((uintptr_t)d_surf & 3u));
-    std::vector<std::vector<uint32_t>> staged(g.members.size());
-    std::vector<uint32_t> origins;
-    size_t group_bytes = 0;
-    for (size_t k = 0; k < g.members.size(); ++k) {
-        for (uint32_t u : g.members[k]) if (!route[u % nr].in_place) staged[k].push_back(u);
-        std::stable_sort(staged[k].begin(), staged[k].end(), [nr](uint32_t a, uint32_t b) { return a % nr < b % nr; });
-        for (uint32_t u : staged[k]) {
-            const SurfacePlane& p = rs.comp[runs[u % nr].first];
-            origins.push_back((uint32_t)(units[u].p.tile_x0 - p.x0));
-            origins.push_back((uint32_t)(units[u].p.tile_y0 - p.y0));
-        }
-        if (!staged[k].empty()) group_bytes = std::max(group_bytes, unit_bytes(units[staged[k][0]], bps) * staged[k].size());
-    }
-    if (!origins.empty()) {
+    const SurfaceStaging st = plan_surface_staging(g.members, route, rs, runs, units);
+    if (!st.origins.empty()) {
         HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");      // (the buffers below may still be read by an earlier call's kernels)
-        HIP_TRY(c, c->img_tiles.ensure(group_bytes), "alloc a group's units");
-        HIP_TRY(c, c->img_rects.ensure(origins.size() * 4), "alloc origins");
-        HIP_TRY(c, hipMemcpy(c->img_rects.p, origins.data(), origins.size() * 4, hipMemcpyHostToDevice), "upload origins");
+        HIP_TRY(c, c->img_tiles.ensure(st.group_bytes), "alloc a group's units");
+        HIP_TRY(c, c->img_rects.ensure(st.origins.size() * 4), "alloc origins");
+        HIP_TRY(c, hipMemcpy(c->img_rects.p, st.origins.data(), st.origins.size() * 4, hipMemcpyHostToDevice), "upload origins");
     }
     // the batches read the surface through a run's layout, or staged planes in the default one: never the caller's setting
-    struct KeepLayout { grk_amd_ctx* c; grk_amd_pixel_layout keep; ~KeepLayout() { c->enc_layout = keep; } } keep{c, c->enc_layout};
+    KeepLayout keep{c->enc_layout, c->enc_layout};
     std::vector<uint64_t> row_at(units.size() + 1, 0);       // unit u's rows start at row_at[u]
-    for (size_t u = 0; u < units.size(); ++u) row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].p.num_comps;
+    for (size_t u = 0; u < units.size(); ++u) row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].num_comps;
     std::vector<grk_amd_coded_block> rows(row_at[units.size()]), table;
     std::vector<uint8_t> coded;
     // one batch: `batch` units of parameters p from d_px, their rows and bytes to the host
@@ -170,17 +160,16 @@ extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_la
             const SurfaceRoute& r = route[u % nr];
             if (!r.in_place) continue;
             c->enc_layout = r.layout;
-            const int rc = encode_batch(units[u].p, std::vector<uint32_t>{u}, d_surf + r.at); if (rc) return rc;
+            const int rc = encode_batch(units[u], std::vector<uint32_t>{u}, d_surf + r.at); if (rc) return rc;
             ++c->surf_counters[0];
         }
-        const std::vector<uint32_t>& S = staged[k];
+        const std::vector<uint32_t>& S = st.staged[k];
         if (S.empty()) continue;
-        const grk_amd_tile_params& p = units[S[0]].p;
-        const size_t unit_size = unit_bytes(units[S[0]], bps);
-        for (size_t i0 = 0, i1; i0 < S.size(); i0 = i1) {           // the group's units of one run: one launch
-            for (i1 = i0 + 1; i1 < S.size() && S[i1] % nr == S[i0] % nr;) ++i1;
-            const int rc = queue_surface_kernel(c, false, rs, runs[S[i0] % nr], d_surf, (uint8_t*)c->img_tiles.p + i0 * unit_size, (uint32_t)(i1 - i0),
-                                                p.tile_w, p.tile_h, (const uint32_t*)c->img_rects.p + 2 * (origin_at + i0));
+        const grk_amd_tile_params& p = units[S[0]];
+        const size_t unit_size = (size_t)p.tile_w * p.tile_h * p.num_comps * bps;
+        for (const RunSegment& s : st.segments[k]) {
+            const int rc = queue_surface_kernel(c, false, rs, runs[s.run], d_surf, (uint8_t*)c->img_tiles.p + s.first * unit_size, s.count,
+                                                p.tile_w, p.tile_h, (const uint32_t*)c->img_rects.p + 2 * (origin_at + s.first));
             if (rc) return rc;
         }
         c->enc_layout = grk_amd_pixel_layout{};

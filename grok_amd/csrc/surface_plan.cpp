@@ -108,6 +108,38 @@ SurfaceRoute plan_surface_run(const ResolvedSurface& rs, const CompRun& run, boo
     return r;
 }
 
+std::vector<RunSegment> run_segments(const std::vector<uint32_t>& units, uint32_t nr)
+{
+    std::vector<RunSegment> out;
+    for (size_t i0 = 0, i1; i0 < units.size(); i0 = i1) {
+        for (i1 = i0 + 1; i1 < units.size() && units[i1] % nr == units[i0] % nr;) ++i1;
+        out.push_back(RunSegment{(uint32_t)i0, (uint32_t)(i1 - i0), units[i0] % nr});
+    }
+    return out;
+}
+
+SurfaceStaging plan_surface_staging(const std::vector<std::vector<uint32_t>>& members, const std::vector<SurfaceRoute>& route, const ResolvedSurface& rs,
+                                    const std::vector<CompRun>& runs, const std::vector<grk_amd_tile_params>& tp)
+{
+    const uint32_t nr = (uint32_t)runs.size();
+    SurfaceStaging s;
+    s.staged.resize(members.size());
+    s.segments.resize(members.size());
+    for (size_t k = 0; k < members.size(); ++k) {
+        std::vector<uint32_t>& S = s.staged[k];
+        for (uint32_t u : members[k]) if (!route[u % nr].in_place) S.push_back(u);
+        std::stable_sort(S.begin(), S.end(), [nr](uint32_t a, uint32_t b) { return a % nr < b % nr; });
+        for (uint32_t u : S) {
+            const SurfacePlane& p = rs.comp[runs[u % nr].first];
+            s.origins.push_back((uint32_t)(tp[u].tile_x0 - p.x0));
+            s.origins.push_back((uint32_t)(tp[u].tile_y0 - p.y0));
+        }
+        if (!S.empty()) s.group_bytes = std::max<uint64_t>(s.group_bytes, (uint64_t)tp[S[0]].tile_w * tp[S[0]].tile_h * tp[S[0]].num_comps * rs.bps * S.size());
+        s.segments[k] = run_segments(S, nr);
+    }
+    return s;
+}
+
 } // namespace grk_amd
 
 using namespace grk_amd;

@@ -1,7 +1,8 @@
 // grok_amd/csrc/surface_plan.h -- the host planning of grk_amd_encode_surface / grk_amd_decode_surface (HIP-free; private to the
 // library, defined in surface_plan.cpp and tested on the CPU): a surface resolved against the image's components, the rule that two
 // components of a destination share no byte, and per run of components the route -- in place through a grk_amd_pixel_layout, or
-// staged through tight planes and the two kernels of kernels_surface.hip.
+// staged through tight planes and the two kernels of kernels_surface.hip --, and the staging plan of a whole call, which
+// grk_amd_encode_surface (surface.cpp) and the surface route of the decode (decode_image_plan.cpp) share.
 #pragma once
 #include "../../include/grok_amd.h"
 #include "image.h"
@@ -28,6 +29,24 @@ struct SurfaceRoute { bool in_place; grk_amd_pixel_layout layout; uint64_t at; }
 // one_tile: the image is one tile (the run is the unit); cap: the bytes behind the base; base_align: the base address modulo 4
 SurfaceRoute plan_surface_run(const ResolvedSurface& rs, const CompRun& run, bool one_tile, bool decode, bool allow_direct, uint64_t cap,
                               uint32_t base_align);
+
+// `count` units of a batch from its `first`, all of run `run`: one launch of a placement (or cut) kernel
+struct RunSegment { uint32_t first, count, run; };
+// a batch's units, sorted run by run (unit u is of run u % nr), as its launches: the units of one run, one launch
+std::vector<RunSegment> run_segments(const std::vector<uint32_t>& units, uint32_t nr);
+
+// What a surface call stages: per geometry group (members[k]: its units) the units whose run is not handled in place, run by run;
+// their origins on the surface's planes (x, y per unit) in that order, group after group -- the one array that is uploaded --; the
+// bytes of the largest group's tight planes; and each group's launches of KS / KD
+struct SurfaceStaging {
+    std::vector<std::vector<uint32_t>> staged;          // [group]
+    std::vector<std::vector<RunSegment>> segments;      // [group]
+    std::vector<uint32_t> origins;
+    uint64_t group_bytes = 0;
+};
+// route, runs: [run]; tp: [unit], the units' parameters
+SurfaceStaging plan_surface_staging(const std::vector<std::vector<uint32_t>>& members, const std::vector<SurfaceRoute>& route, const ResolvedSurface& rs,
+                                    const std::vector<CompRun>& runs, const std::vector<grk_amd_tile_params>& tp);
 
 } // namespace grk_amd
 #pragma GCC visibility pop

@@ -16,7 +16,9 @@ int run_idwt(grk_amd_ctx* c, uint32_t nplanes, const void* d_mallat, void* d_out
     }
     { const int rc = ensure_ll(c, nplanes); if (rc) return rc; }     // (the same ping-pong storage as the forward transform)
     ScopedTimer t(c, 6);
+    const SampleRange r = sample_range(g.p);
     for (int32_t l = (int32_t)L - 1; l >= 0; --l) {
+        // describe the level ...
         IdwtLevelArgs a{};
         a.cw = level_geom(g, (uint32_t)l).w; a.ch = level_geom(g, (uint32_t)l).h;
         a.px = level_geom(g, (uint32_t)l).x0 & 1u; a.py = level_geom(g, (uint32_t)l).y0 & 1u;
@@ -29,34 +31,31 @@ int run_idwt(grk_amd_ctx* c, uint32_t nplanes, const void* d_mallat, void* d_out
         a.xcd = c->dwt_xcd;
         a.h16 = h16 ? 1 : 0; a.status = (unsigned int*)c->flag.p;
         a.pk = h16 && c->dwt_pk && !plan;            // (the block decoder flagged every coefficient outside the packed range)
-        if (l == 0 && d_pixels && px && px->lay) set_px_out(a, *px);
-        const uint32_t sh = (a.ch + a.py + 1) >> 1;
-        const uint64_t strips = (((a.cw + a.px + 1) >> 1) + idwt_level_strip_pairs(a) - 1) / idwt_level_strip_pairs(a);
-        const uint32_t zslots = (l == 0 && d_pixels) ? ntiles * ((g.p.mct && g.p.num_comps >= 3) ? 1u : g.p.num_comps) : nplanes;
-        a.seg_pairs = row_segment_pairs(strips, sh, zslots, 4096);
-        a.wx0 = 0; a.wy0 = 0; a.wx1 = a.cw; a.wy1 = a.ch;
-        if (plan) {       // the strips and row segments that produce need[l]
-            const Rect n = plan->need[(uint32_t)l];
-            const uint32_t op = idwt_strip_pairs(), seg = 16;
-            a.seg_pairs = seg;
-            a.strip0 = ((n.x0 + a.px) / 2) / op; a.nstrips = ((n.x1 - 1 + a.px) / 2) / op - a.strip0 + 1;
-            a.seg0 = ((n.y0 + a.py) / 2) / seg; a.nsegs = ((n.y1 - 1 + a.py) / 2) / seg - a.seg0 + 1;
-            if (l == 0) { a.wx0 = n.x0; a.wy0 = n.y0; a.wx1 = n.x1; a.wy1 = n.y1; }
+        const bool fused = l == 0 && d_pixels;
+        if (fused) {
+            if (px && px->lay) set_px_out(a, *px);
+            a.pixels = d_pixels; a.px_bytes = out_bytes;
+            a.dc = r.dc; a.lo = r.lo; a.hi = r.hi;
+            a.mct = g.p.mct;
         }
+        // ... plan its kernel instance, strips, row segments and, for a region, the sub-grid that produces need[l] (decode_plan.h) ...
+        const uint32_t zslots = fused ? ntiles * level_part_zslots(g.p.mct != 0, g.p.num_comps) : nplanes;
+        const IdwtLevelShape shape = plan_idwt_level(IdwtLevelDesc{
+            a.cw, a.ch, a.px, a.py, a.ll_stride, a.m_stride, a.out_stride, a.h16 != 0, a.pk != 0, a.irreversible != 0, zslots,
+            plan != nullptr, plan ? plan->need[(uint32_t)l] : Rect{}, fused, a.px_bytes, a.lo, a.hi, a.mct != 0,
+            a.px_lay, a.px_chan, a.px_row, a.px_tile, (uint32_t)((uintptr_t)a.pixels & 3u)});
+        // ... fill what the kernel reads of it ...
+        a.seg_pairs = shape.seg_pairs;
+        a.strip0 = shape.strip0; a.nstrips = shape.nstrips; a.seg0 = shape.seg0; a.nsegs = shape.nsegs;
+        a.wx0 = shape.wx0; a.wy0 = shape.wy0; a.wx1 = shape.wx1; a.wy1 = shape.wy1;
         if (a.cw == 0 || a.ch == 0) continue;       // (a level without samples, see run_dwt)
+        // ... and launch
         if (l == 0 && c->dec_top_pending) {           // the top resolution's blocks are decoded on the side stream
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_dec_top, 0), "wait for the top resolution's blocks");
             c->dec_top_pending = false;
         }
-        if (l == 0 && d_pixels) {
-            const SampleRange r = sample_range(g.p);
-            a.pixels = d_pixels; a.px_bytes = out_bytes;
-            a.dc = r.dc; a.lo = r.lo; a.hi = r.hi;
-            a.mct = g.p.mct;
-            HIP_TRY(c, launch_idwt_level0_fused(a, ntiles, g.p.num_comps, c->stream), "launch fused idwt level 0");
-        } else {
-            HIP_TRY(c, launch_idwt_level(a, c->stream), "launch idwt level");
-        }
+        if (fused) HIP_TRY(c, launch_idwt_level0_fused(a, shape, ntiles, g.p.num_comps, c->stream), "launch fused idwt level 0");
+        else       HIP_TRY(c, launch_idwt_level(a, shape, c->stream), "launch idwt level");
     }
     return GRK_AMD_OK;
 }
@@ -83,7 +82,7 @@ int run_egress(grk_amd_ctx* c, uint32_t ntiles, const void* d_planes, void* d_pi
     a.dc = r.dc; a.lo = r.lo; a.hi = r.hi;
     a.mct = g.p.mct; a.irreversible = g.p.irreversible;
     ScopedTimer t(c, 7);
-    HIP_TRY(c, launch_egress(a, c->stream), "launch egress");
+    HIP_TRY(c, launch_egress(a, egress_key(a.px_lay, a.bytes_per_sample, a.ncomp), c->stream), "launch egress");
     return GRK_AMD_OK;
 }
 } // namespace

@@ -222,4 +222,69 @@ int plan_t1_lists(const T1PlanIn& in, uint32_t* h_lane, uint32_t* h_tail, T1List
     return GRK_AMD_OK;
 }
 
+// ---- the shape of an inverse DWT level -------------------------------------------------------------------------------------------
+// the instance of a part of nc components (1, or 3: the MCT triple) of a level of shape s, and its strips (strips32: the 32-bit kernels')
+static IdwtInstance idwt_instance(const IdwtLevelDesc& d, const IdwtLevelShape& s, uint8_t nc, uint32_t strips32)
+{
+    IdwtInstance in{};
+    const uint8_t pxo = !d.fused ? 0 : d.px_bytes == 1 ? 1 : 2;
+    in.packed = s.packed;
+    in.pk = IdwtPkKey{nc, pxo, 0};
+    if (d.fused) {
+        // 8-bit pixels clamped to 0..255 (the packed store saturates to that), the whole tile
+        const bool whole = s.wx0 == 0 && s.wy0 == 0 && s.wx1 == d.cw && s.wy1 == d.ch;
+        in.packed = s.packed && pxo == 1 && d.lo == 0 && d.hi == 255 && whole;
+        if (d.px_lay != 0) {
+            // a layout of the caller's: one-channel pixels, or the MCT triple into three- / four-channel ones, tiles and rows on
+            // 4-byte alignment (whole dwords are stored), row offsets within 32 bits; the strided back end otherwise
+            const bool al = ((d.px_align | d.px_row | d.px_tile) & 3u) == 0 && d.px_row * d.ch < (1ull << 31);
+            const bool lay = d.px_lay == 2 && ((d.px_chan == 1 && nc == 1) || ((d.px_chan == 3 || d.px_chan == 4) && nc == 3 && d.mct));
+            in.packed = in.packed && al && lay;
+            in.pk = IdwtPkKey{nc, 1, (uint8_t)d.px_chan};
+        } else {
+            in.packed = in.packed && (nc == 1 || d.mct);
+        }
+    }
+    in.k = IdwtKey{d.irreversible, nc, pxo, d.h16 && !d.irreversible, d.fused && d.px_lay != 0};
+    in.grid_x = in.packed ? (d.cw + ipk_strip_cols(d.cw) - 1) / ipk_strip_cols(d.cw) : strips32;
+    return in;
+}
+
+IdwtLevelShape plan_idwt_level(const IdwtLevelDesc& d)
+{
+    IdwtLevelShape s{};
+    const uint32_t col_pairs = (d.cw + d.px + 1) >> 1, row_pairs = (d.ch + d.py + 1) >> 1;      // pairs on the coordinate grid
+    // (row offsets are 32-bit byte offsets from a plane's first sample: planes of 2^31 samples and more keep the flat addressing)
+    const bool near = (uint64_t)d.m_stride * d.ch < (1ull << 31) && (uint64_t)d.out_stride * d.ch < (1ull << 31);
+    // d.pk: the caller's word that the inputs are inside the packed range
+    s.packed = d.h16 && d.pk && !d.irreversible && (d.px | d.py) == 0 && (d.cw & 3u) == 0 && d.cw >= 256u && d.ch >= 16 &&
+               (d.ch & 1u) == 0 && !d.region && near;
+    s.strip_pairs = s.packed ? ipk_strip_cols(d.cw) / 2 : kIdwtStripPairs;
+    // The row segments are sized from s.packed's strips, although the fused level can still take the 32-bit kernel and its narrower
+    // strips (idwt_instance: signed or fewer than 8 bits, a window, a layout the packed kernel does not write, a misaligned pointer):
+    // its grid then has more workgroups than the segments were sized for.  Kept as it was -- it decides grids, so speed.
+    s.seg_pairs = row_segment_pairs((col_pairs + s.strip_pairs - 1) / s.strip_pairs, row_pairs, d.zslots, kIdwtMinWgs);
+    s.wx0 = 0; s.wy0 = 0; s.wx1 = d.cw; s.wy1 = d.ch;
+    if (d.region) {       // the strips and row segments that produce `need`
+        const Rect n = d.need;
+        s.seg_pairs = kIdwtRegionSegPairs;
+        s.strip0 = ((n.x0 + d.px) / 2) / kIdwtStripPairs; s.nstrips = ((n.x1 - 1 + d.px) / 2) / kIdwtStripPairs - s.strip0 + 1;
+        s.seg0 = ((n.y0 + d.py) / 2) / s.seg_pairs; s.nsegs = ((n.y1 - 1 + d.py) / 2) / s.seg_pairs - s.seg0 + 1;
+        if (d.fused) { s.wx0 = n.x0; s.wy0 = n.y0; s.wx1 = n.x1; s.wy1 = n.y1; }
+    }
+    // strips x row segments: all of them, or the region's sub-grid
+    const uint32_t strips32 = s.nstrips ? s.nstrips : (col_pairs + kIdwtStripPairs - 1) / kIdwtStripPairs;
+    s.grid_y = s.nsegs ? s.nsegs : (row_pairs + s.seg_pairs - 1) / s.seg_pairs;
+    s.inst[0] = idwt_instance(d, s, 1, strips32);
+    if (d.fused) s.inst[1] = idwt_instance(d, s, 3, strips32);
+    s.grid_x = s.inst[0].grid_x;
+    return s;
+}
+
+EgressKey egress_key(uint32_t px_lay, uint32_t bytes_per_sample, uint32_t ncomp)
+{
+    const uint8_t bytes = bytes_per_sample == 1 ? 1 : bytes_per_sample == 2 ? 2 : 4;      // (4: int32 out)
+    return EgressKey{bytes, (uint8_t)(ncomp <= 4 ? ncomp : 0), px_lay != 0 && bytes != 4};
+}
+
 } // namespace grk_amd

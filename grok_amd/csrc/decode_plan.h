@@ -1,9 +1,10 @@
 // grok_amd/csrc/decode_plan.h -- what a decode call works out on the host before it launches anything: which blocks a window
 // needs, which rows of the caller's table are sound, which block goes to which decoder.  Plain integer code over a block table
-// and a TileGeom: no HIP, no grk_amd_ctx, so that a plain C++ compiler builds it and tests/c/decode_plan_units.cpp steps through
+// and a TileGeom, and the shape of each inverse DWT level: no HIP, no grk_amd_ctx, so that a plain C++ compiler builds it and tests/c/decode_plan_units.cpp steps through
 // it without a GPU.  A planner that can refuse returns a GRK_AMD_* code and leaves the reason in *why; the caller reports it.
 #pragma once
 #include "decode_constants.h"
+#include "dwt_instances.h"
 #include "geometry.h"
 #include <cstddef>
 #include <cstdint>
@@ -64,6 +65,32 @@ struct T1Lists {
 };
 // lane: room for 2 nblocks entries (padding), tail: for nblocks.  GRK_AMD_ERR_NOMEM when the host has no memory for the sort
 int plan_t1_lists(const T1PlanIn& in, uint32_t* lane, uint32_t* tail, T1Lists* out, const char** why);
+
+// ---- the shape of an inverse DWT level -------------------------------------------------------------------------------------------
+struct IdwtLevelDesc {                 // (the fields of IdwtLevelArgs the shape depends on)
+    uint32_t cw, ch, px, py;
+    uint32_t ll_stride, m_stride, out_stride;
+    bool h16, pk, irreversible;
+    uint32_t zslots;                   // workgroups along z: planes, or for the fused last level tiles (x level_part_zslots)
+    bool region; Rect need;            // a region decode: the part of the level that has to be right (RegionPlan::need[l])
+    // the last level fused with K7: the rows leave as the caller's pixels
+    bool fused; uint32_t px_bytes; int32_t lo, hi; bool mct;
+    uint32_t px_lay, px_chan; uint64_t px_row, px_tile;
+    uint32_t px_align;                 // the low two bits of the (device) pixel pointer
+};
+struct IdwtLevelShape {
+    bool packed;                       // the level shape idwt53_pk_kernel takes
+    uint32_t strip_pairs;              // coefficient pairs a workgroup of that kernel owns
+    uint32_t seg_pairs;                // row pairs per workgroup
+    uint32_t grid_x, grid_y;           // strips (of inst[0]: the fused level's parts can differ), row segments
+    uint32_t strip0, nstrips, seg0, nsegs;     // region decode: the sub-grid that produces `need` (0 = all)
+    uint32_t wx0, wy0, wx1, wy1;       // the window of the level the pixels are for
+    IdwtInstance inst[2];              // the kernel instance (dwt_instances.h) and its strips: of a part of one component [0] and, for
+                                       // the fused level, of the MCT triple [1] (every other level: not used, in no list)
+};
+IdwtLevelShape plan_idwt_level(const IdwtLevelDesc& d);
+// the stand-alone K7's instance
+EgressKey egress_key(uint32_t px_lay, uint32_t bytes_per_sample, uint32_t ncomp);
 
 } // namespace grk_amd
 #pragma GCC visibility pop

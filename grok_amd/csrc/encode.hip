@@ -90,6 +90,7 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
     }
     { const int rc = ensure_ll(c, nplanes); if (rc) return rc; }     // (LL ping-pong storage, context.h: ll_plane)
     ScopedTimer t(c, 1);
+    const SampleRange r = sample_range(g.p);
     for (uint32_t l = 0; l < L; ++l) {
         DwtLevelArgs a{};
         a.cw = level_geom(g, l).w; a.ch = level_geom(g, l).h;
@@ -106,17 +107,17 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
         if (l == 0 && d_pixels && px && px->lay) {     // (before the level is shaped: the layout decides between the level-0 kernels)
             set_px_in(a, *px); a.px_chan = px->channels;
         }
-        // the level's kernel, strips and row segments (plan_dwt_level, encode_plan.h).  Workgroups along z: planes, or for the fused
-        // level 0 tiles (x components when there is no MCT triple)
-        const uint32_t zslots = (l == 0 && d_pixels) ? ntiles * ((g.p.mct && g.p.num_comps >= 3) ? 1u : g.p.num_comps) : nplanes;
+        // the level's kernel instance, strips and row segments (plan_dwt_level, encode_plan.h).  Workgroups along z: planes, or for the
+        // fused level 0 tiles (x components when there is no MCT triple)
+        const bool fused = l == 0 && d_pixels;
+        const uint32_t zslots = fused ? ntiles * level_part_zslots(g.p.mct != 0, g.p.num_comps) : nplanes;
         const DwtLevelShape shape = plan_dwt_level(DwtLevelDesc{a.cw, a.ch, a.px, a.py, a.in_stride, a.m_stride, a.h16 != 0, a.pk != 0,
-                                                                a.irreversible != 0, a.px_lay, a.px_chan, a.px_row, zslots});
+                                                                a.irreversible != 0, a.px_lay, a.px_chan, a.px_row, zslots, fused, r.bytes});
         a.seg_pairs = shape.seg_pairs;
         if (a.cw == 0 || a.ch == 0) {
             // a level without samples (a narrow tile off the origin: [ceil(x0 / 2^l), ceil((x0 + w) / 2^l)) can be empty):
             // nothing to transform, and nothing deeper either
-        } else if (l == 0 && d_pixels) {
-            const SampleRange r = sample_range(g.p);
+        } else if (fused) {
             a.pixels = d_pixels; a.px_bytes = r.bytes;
             a.alloc_reset = c->pend_alloc; a.alloc_chunk_units = c->pend_alloc_units; c->pend_alloc = nullptr;
             a.dc = r.dc; a.sext = r.sext;

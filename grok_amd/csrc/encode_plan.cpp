@@ -126,9 +126,34 @@ Route plan_route(const grk_amd_tile_params& p, const RouteIn& in)
 }
 
 // ---- the shape of a forward DWT level --------------------------------------------------------------------------------------------
+// the instance of a part of nc components (1, or 3: the MCT triple) of a level of shape s
+static DwtInstance dwt_instance(const DwtLevelDesc& d, const DwtLevelShape& s, uint8_t nc)
+{
+    DwtInstance in{};
+    const uint8_t px = d.px_bytes == 1 ? 1 : 2;
+    const bool h16 = d.h16 && !d.irreversible;
+    if (!d.fused) {
+        in.packed = s.packed;
+        in.pk = DwtPkKey{1, 0, (uint16_t)s.lanes, 0};
+        in.k = DwtKey{d.irreversible, 1, 0, h16, true, false};
+    } else if (d.px_lay != 0) {        // a layout of the caller's: the interleaved packed instances, else the strided front end
+        in.packed = !d.irreversible && px == 1 && s.packed;
+        const uint8_t ch = d.px_chan == 1 ? 1 : d.px_chan == 3 ? 3 : 4;
+        in.pk = DwtPkKey{ch == 1 ? (uint8_t)1 : nc, 1, (uint16_t)s.lanes, ch};
+        in.k = DwtKey{d.irreversible, nc, px, h16 && px == 1, true, true};
+    } else {
+        in.packed = !d.irreversible && px == 1 && s.packed;
+        in.pk = DwtPkKey{nc, 1, (uint16_t)s.lanes, 0};
+        // 16-bit planes exist for 8-bit pixels only (planes16_ok), and only in the general form
+        if (h16 && px == 1) in.k = DwtKey{false, nc, 1, true, true, false};
+        else                in.k = DwtKey{d.irreversible, nc, px, false, !s.all_fast, false};
+    }
+    return in;
+}
+
 DwtLevelShape plan_dwt_level(const DwtLevelDesc& d)
 {
-    DwtLevelShape s;
+    DwtLevelShape s{};
     // (row offsets are 32-bit byte offsets from a plane's first sample: planes of 2^31 samples and more keep the flat addressing)
     const bool near = (uint64_t)d.m_stride * d.ch < (1ull << 31) && (uint64_t)d.cw * d.ch < (1ull << 31) && (uint64_t)d.in_stride * d.ch < (1ull << 31);
     // the caller's pixels: planes of the default layout, or interleaved with 1, 3 or 4 samples per pixel (rows at their real pitch);
@@ -144,6 +169,8 @@ DwtLevelShape plan_dwt_level(const DwtLevelDesc& d)
     s.grid_x = (uint32_t)(((uint64_t)d.cw + d.px + s.strip_cols - 1) / s.strip_cols);
     s.seg_pairs = row_segment_pairs(s.grid_x, row_pairs, d.zslots, d.pk ? kDwtMinWgsPacked : kDwtMinWgs);
     s.grid_y = (row_pairs + s.seg_pairs - 1) / s.seg_pairs;
+    s.inst[0] = dwt_instance(d, s, 1);
+    if (d.fused) s.inst[1] = dwt_instance(d, s, 3);
     return s;
 }
 

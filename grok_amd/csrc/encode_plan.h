@@ -4,6 +4,7 @@
 // tests/c/encode_plan_units.cpp steps through it without a GPU.  These numbers set K3's occupancy, the allocator's contention and
 // the streams' overlap.
 #pragma once
+#include "dwt_instances.h"
 #include "encode_constants.h"
 #include "geometry.h"
 #include <cstddef>
@@ -126,7 +127,8 @@ struct DwtLevelDesc {                  // (the fields of DwtLevelArgs the shape 
     uint32_t in_stride, m_stride;
     bool h16, pk, irreversible;
     uint32_t px_lay, px_chan; uint64_t px_row;
-    uint32_t zslots;                   // workgroups along z: planes, or for the fused level 0 tiles (x components when there is no MCT triple)
+    uint32_t zslots;                   // workgroups along z: planes, or for the fused level 0 tiles (x level_part_zslots)
+    bool fused; uint32_t px_bytes;     // level 0 reads the caller's pixels of px_bytes (1 or 2) each
 };
 struct DwtLevelShape {
     bool packed;                       // the level shape dwt53_pk_kernel takes
@@ -135,15 +137,10 @@ struct DwtLevelShape {
     bool all_fast;                     // (what dwt_level_kernel calls `even`: every strip of the level takes a FAST path)
     uint32_t seg_pairs;                // row pairs per workgroup
     uint32_t grid_x, grid_y;           // strips, row segments
+    DwtInstance inst[2];               // the kernel instance (dwt_instances.h) of a part of one component [0] and, for the fused
+                                       // level, of the MCT triple [1] (every other level: not used, in no list)
 };
 DwtLevelShape plan_dwt_level(const DwtLevelDesc& d);
-// row pairs per workgroup of a DWT level: halved from 64 (to 8 at the least) while strips x row segments x z slots stay below min_wgs
-inline uint32_t row_segment_pairs(uint64_t strips, uint32_t row_pairs, uint32_t zslots, uint32_t min_wgs)
-{
-    uint32_t seg = 64;
-    while (seg > 8 && strips * ((row_pairs + seg - 1) / seg) * zslots < min_wgs) seg >>= 1;
-    return seg;
-}
 
 } // namespace grk_amd
 #pragma GCC visibility pop

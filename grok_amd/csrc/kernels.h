@@ -6,6 +6,7 @@
 #include "decode_constants.h"
 #include "encode_constants.h"
 #include "encode_plan.h"
+#include "decode_plan.h"
 
 namespace grk_amd {
 
@@ -56,7 +57,7 @@ struct DwtLevelArgs {
     uint32_t px_lay, px_chan, px_xstep;
     uint64_t px_row, px_kstep, px_tile;
 };
-// sh: the level's shape (plan_dwt_level, encode_plan.h) -- which kernel, its strips and row segments; a.seg_pairs = sh.seg_pairs
+// sh: the level's shape (plan_dwt_level, encode_plan.h) -- which kernel instance, its strips and row segments; a.seg_pairs = sh.seg_pairs
 hipError_t launch_dwt_level(const DwtLevelArgs& a, const DwtLevelShape& sh, hipStream_t s);
 hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, const DwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s);
 
@@ -111,7 +112,6 @@ hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hip
 // sum of q^2 over each block of the planes an encode left (kernels_ingest.hip: the rate-control hook)
 hipError_t launch_block_energy(const void* mallat, int h16, int irreversible, uint32_t stride, uint64_t pitch, const HtBlockDesc* blocks,
                                uint32_t blocks_per_tile, uint32_t ncomp, uint64_t nblocks, unsigned long long* out, hipStream_t s);
-uint32_t   idwt_strip_pairs();    // coefficient pairs a K6 workgroup owns
 
 // ---- K5: HT cleanup decoder + dequantisation (kernels_htdec.hip) --------------------------------
 struct HtDecBlock {          // one per code-block, same layout as grk_amd_coded_block
@@ -210,9 +210,10 @@ struct IdwtLevelArgs {
     uint32_t px_lay, px_chan, px_xstep, px_fill;
     uint64_t px_row, px_kstep, px_tile;
 };
-hipError_t launch_idwt_level(const IdwtLevelArgs& a, hipStream_t s);
-hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, uint32_t ntiles, uint32_t ncomp, hipStream_t s);
-uint32_t   idwt_level_strip_pairs(const IdwtLevelArgs& a);   // coefficient pairs a K6 workgroup owns at this level
+// sh: the level's shape (plan_idwt_level, decode_plan.h) -- which kernel instance, its strips and row segments; a.seg_pairs, the
+// sub-grid and the window = sh's
+hipError_t launch_idwt_level(const IdwtLevelArgs& a, const IdwtLevelShape& sh, hipStream_t s);
+hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, const IdwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, hipStream_t s);
 
 // ---- K7: inverse colour transform + DC shift + clamp + store as pixels (kernels_idwt.hip) --------
 struct EgressArgs {
@@ -227,7 +228,7 @@ struct EgressArgs {
     uint32_t px_lay, px_chan, px_xstep, px_fill;       // a layout other than the default (as IdwtLevelArgs)
     uint64_t px_row, px_kstep, px_tile;
 };
-hipError_t launch_egress(const EgressArgs& a, hipStream_t s);
+hipError_t launch_egress(const EgressArgs& a, const EgressKey& key, hipStream_t s);     // key: egress_key (decode_plan.h)
 
 // ---- KT1 / KT2: Tier-2 on the device (kernels_t2.hip) -------------------------------------------------------------------------
 struct T2HeaderArgs {

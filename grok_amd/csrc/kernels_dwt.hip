@@ -683,85 +683,45 @@ __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
 
 } // namespace
 
+// one launch of the instance the planner chose (plan_dwt_level, encode_plan.h): a row of the template's list (dwt_instances.h), or
+// hipErrorInvalidValue -- never another instance in its place
+static hipError_t launch_dwt_instance(const DwtInstance& in, dim3 grid, const DwtLevelArgs& a, hipStream_t s)
+{
+    if (in.packed) {
+        switch (in.pk.code()) {
+#define GRK_X(NC, PX, NT, CH) case DwtPkKey{NC, PX, NT, CH}.code(): hipLaunchKernelGGL((dwt53_pk_kernel<NC, PX, NT, CH>), grid, dim3(NT), 0, s, a); break;
+        GRK_DWT_PK_INSTANCES(GRK_X)
+#undef GRK_X
+        default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (in.k.code()) {
+#define GRK_X(F97, NC, PX, H16, GEN, STR) case DwtKey{F97, NC, PX, H16, GEN, STR}.code(): hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, H16, GEN, STR>), grid, dim3(kThreads), 0, s, a); break;
+        GRK_DWT_INSTANCES(GRK_X)
+#undef GRK_X
+        default: return hipErrorInvalidValue;
+        }
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_dwt_level(const DwtLevelArgs& a, const DwtLevelShape& sh, hipStream_t s)
 {
-    dim3 grid(sh.grid_x, sh.grid_y, a.nplanes);
-    dim3 block(kThreads);
-    if (sh.packed) {
-        if (sh.lanes == 128) hipLaunchKernelGGL((dwt53_pk_kernel<1, 0, 128>), grid, dim3(128), 0, s, a);
-        else                 hipLaunchKernelGGL((dwt53_pk_kernel<1, 0, 256>), grid, block, 0, s, a);
-        return hipGetLastError();
-    }
-    if (a.irreversible)
-        hipLaunchKernelGGL((dwt_level_kernel<true, 1, 0>), grid, block, 0, s, a);
-    else if (a.h16)
-        hipLaunchKernelGGL((dwt_level_kernel<false, 1, 0, true>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((dwt_level_kernel<false, 1, 0>), grid, block, 0, s, a);
-    return hipGetLastError();
+    const hipError_t e = launch_dwt_instance(sh.inst[0], dim3(sh.grid_x, sh.grid_y, a.nplanes), a, s);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // Level 0 straight from the pixels. `a` describes level 0 (cw x ch = tile size, in/in_stride unused);
 // a.nplanes is ignored: the grid covers ntiles x (MCT triple | every component on its own).
 hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, const DwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s)
 {
-    dim3 block(kThreads);
-    auto go = [&](uint32_t comp0, uint32_t zdiv, int nc) {
+    for (uint32_t i = 0; i < level_part_count(mct != 0, ncomp); ++i) {
+        const LevelPart part = level_part(mct != 0, ncomp, i);
         DwtLevelArgs a = a0;
-        a.comp0 = comp0; a.zdiv = zdiv; a.ncomp = ncomp;
-        if (comp0 != 0) a.alloc_reset = nullptr;             // (the first launch resets the allocator)
-        dim3 grid(sh.grid_x, sh.grid_y, ntiles * zdiv);
-#define GRK_L0(F97, NC, PX) do { if (sh.all_fast) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, false, false>), grid, block, 0, s, a); \
-                                 else hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX>), grid, block, 0, s, a); } while (0)
-        const int px = a.px_bytes == 1 ? 1 : 2;
-        if (a.px_lay != 0) {               // a layout of the caller's: the interleaved packed instances, else the strided front end
-            if (!a.irreversible && px == 1 && sh.packed) {
-#define GRK_PKI(NC, CH) do { if (sh.lanes == 128) hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 128, CH>), grid, dim3(128), 0, s, a); \
-                             else hipLaunchKernelGGL((dwt53_pk_kernel<NC, 1, 256, CH>), grid, block, 0, s, a); } while (0)
-                if (a.px_chan == 1) GRK_PKI(1, 1);
-                else if (a.px_chan == 3) { if (nc == 3) GRK_PKI(3, 3); else GRK_PKI(1, 3); }
-                else                     { if (nc == 3) GRK_PKI(3, 4); else GRK_PKI(1, 4); }
-#undef GRK_PKI
-                return;
-            }
-#define GRK_L0S(F97, NC, PX, H16) hipLaunchKernelGGL((dwt_level_kernel<F97, NC, PX, H16, true, true>), grid, block, 0, s, a)
-            if (a.irreversible) {
-                if (nc == 3) { if (px == 1) GRK_L0S(true, 3, 1, false); else GRK_L0S(true, 3, 2, false); }
-                else         { if (px == 1) GRK_L0S(true, 1, 1, false); else GRK_L0S(true, 1, 2, false); }
-            } else if (a.h16 && px == 1) {
-                if (nc == 3) GRK_L0S(false, 3, 1, true); else GRK_L0S(false, 1, 1, true);
-            } else {
-                if (nc == 3) { if (px == 1) GRK_L0S(false, 3, 1, false); else GRK_L0S(false, 3, 2, false); }
-                else         { if (px == 1) GRK_L0S(false, 1, 1, false); else GRK_L0S(false, 1, 2, false); }
-            }
-#undef GRK_L0S
-            return;
-        }
-        if (a.irreversible) {
-            if (nc == 3) { if (px == 1) GRK_L0(true, 3, 1); else GRK_L0(true, 3, 2); }
-            else         { if (px == 1) GRK_L0(true, 1, 1); else GRK_L0(true, 1, 2); }
-        } else if (px == 1 && sh.packed) {
-            if (sh.lanes == 128) {
-                if (nc == 3) hipLaunchKernelGGL((dwt53_pk_kernel<3, 1, 128>), grid, dim3(128), 0, s, a);
-                else         hipLaunchKernelGGL((dwt53_pk_kernel<1, 1, 128>), grid, dim3(128), 0, s, a);
-            } else {
-                if (nc == 3) hipLaunchKernelGGL((dwt53_pk_kernel<3, 1, 256>), grid, block, 0, s, a);
-                else         hipLaunchKernelGGL((dwt53_pk_kernel<1, 1, 256>), grid, block, 0, s, a);
-            }
-        } else if (a.h16 && px == 1) {       // 16-bit planes exist for 8-bit pixels only (encode_plan.cpp: planes16_ok)
-            if (nc == 3) hipLaunchKernelGGL((dwt_level_kernel<false, 3, 1, true>), grid, block, 0, s, a);
-            else         hipLaunchKernelGGL((dwt_level_kernel<false, 1, 1, true>), grid, block, 0, s, a);
-        } else {
-            if (nc == 3) { if (px == 1) GRK_L0(false, 3, 1); else GRK_L0(false, 3, 2); }
-            else         { if (px == 1) GRK_L0(false, 1, 1); else GRK_L0(false, 1, 2); }
-        }
-#undef GRK_L0
-    };
-    if (mct && ncomp >= 3) {
-        go(0, 1, 3);
-        for (uint32_t k = 3; k < ncomp; ++k) go(k, 1, 1);
-    } else {
-        go(0, ncomp, 1);
+        a.comp0 = part.comp0; a.zdiv = part.zdiv; a.ncomp = ncomp;
+        if (part.comp0 != 0) a.alloc_reset = nullptr;        // (the first launch resets the allocator)
+        const hipError_t e = launch_dwt_instance(sh.inst[part.nc == 3], dim3(sh.grid_x, sh.grid_y, ntiles * part.zdiv), a, s);
+        if (e != hipSuccess) return e;
     }
     return hipGetLastError();
 }

@@ -35,10 +35,10 @@ namespace grk_amd {
 namespace {
 
 constexpr int kThreads   = 256;
-constexpr int kHaloPairs = 2;
+constexpr int kHaloPairs = (int)kIdwtHaloPairs;      // (2)
 // Coefficient pairs per strip.  At most kThreads - 2 * kHaloPairs = 252; 224 pairs = 7 cache lines of each sub-band row
 // and 14 of each output row, so loads and stores cover whole, aligned lines.
-constexpr int kOutPairs  = 224;
+constexpr int kOutPairs  = (int)kIdwtStripPairs;     // (224)
 static_assert(kOutPairs <= kThreads - 2 * kHaloPairs, "strip does not fit the staged line");
 
 constexpr float kIDelta = -kDelta, kIGamma = -kGamma, kIBeta = -kBeta, kIAlpha = -kAlpha;     // (dwt_common.h)
@@ -403,14 +403,9 @@ __device__ __forceinline__ uint32_t sat_pk_u8(pk16 v)      // two int16 -> two b
 
 constexpr int kPkLanePairs = 2;
 constexpr int kPkPairs     = kThreads * kPkLanePairs;      // pairs staged per line: 512
-constexpr int kPkOutCols   = 960;                          // output columns per strip at most (240 lanes; one halo lane each side)
+constexpr int kPkOutCols   = (int)kIpkStripCols;           // (960) output columns per strip at most (240 lanes; one halo lane each side)
 static_assert(kPkOutCols / 4 + 2 <= kThreads, "strip does not fit the staged line");
-// the strips of a level share its width evenly, in multiples of 64 output columns
-__host__ __device__ inline uint32_t ipk_strip_cols(uint32_t cw)
-{
-    const uint32_t n = (cw + kPkOutCols - 1) / kPkOutCols;
-    return min((uint32_t)kPkOutCols, ((cw + n - 1) / n + 63u) & ~63u);
-}
+// (the strips of a level: ipk_strip_cols, decode_constants.h)
 
 #define IPK_FENCE __builtin_amdgcn_sched_barrier(0)
 // CH (PXO = 1): 0 = the default pixel layout, component planes; 1 = one-channel pixels at the caller's pitches; 3, 4 = the MCT triple
@@ -712,121 +707,61 @@ __global__ __launch_bounds__(256) void egress_kernel(EgressArgs a)
 
 } // namespace
 
-uint32_t idwt_strip_pairs() { return kOutPairs; }
-
-// the level shape idwt53_pk_kernel takes (a.pk: the launcher's word that the inputs are inside the packed range)
-static bool idwt_level_is_pk(const IdwtLevelArgs& a)
+// one launch of the instance the planner chose (plan_idwt_level, decode_plan.h): a row of the template's list (dwt_instances.h), or
+// hipErrorInvalidValue -- never another instance in its place
+static hipError_t launch_idwt_instance(const IdwtInstance& in, dim3 grid, const IdwtLevelArgs& a, hipStream_t s)
 {
-    // (row offsets are 32-bit byte offsets from a plane's first sample: planes of 2^31 samples and more keep the flat addressing)
-    const bool near = (uint64_t)a.m_stride * a.ch < (1ull << 31) && (uint64_t)a.out_stride * a.ch < (1ull << 31);
-    return a.h16 && a.pk && !a.irreversible && (a.px | a.py) == 0 && (a.cw & 3u) == 0 && a.cw >= 256u && a.ch >= 16 && (a.ch & 1u) == 0 &&
-           a.nstrips == 0 && a.nsegs == 0 && near;
-}
-uint32_t idwt_level_strip_pairs(const IdwtLevelArgs& a) { return idwt_level_is_pk(a) ? ipk_strip_cols(a.cw) / 2 : (uint32_t)kOutPairs; }
-
-hipError_t launch_idwt_level(const IdwtLevelArgs& a, hipStream_t s)
-{
-    const uint32_t sw = (a.cw + a.px + 1) >> 1, sh = (a.ch + a.py + 1) >> 1;      // pairs on the coordinate grid
-    // strips x row segments: all of them, or the caller's sub-grid (region decode)
-    dim3 grid(a.nstrips ? a.nstrips : (sw + kOutPairs - 1) / kOutPairs, a.nsegs ? a.nsegs : (sh + a.seg_pairs - 1) / a.seg_pairs, a.nplanes);
-    dim3 block(kThreads);
-    if (idwt_level_is_pk(a)) {
-        grid.x = (a.cw + ipk_strip_cols(a.cw) - 1) / ipk_strip_cols(a.cw);
-        hipLaunchKernelGGL((idwt53_pk_kernel<1, 0>), grid, block, 0, s, a);
-        return hipGetLastError();
+    const dim3 block(kThreads);
+    grid.x = in.grid_x;
+    if (in.packed) {
+        switch (in.pk.code()) {
+#define GRK_X(NC, PXO, CH) case IdwtPkKey{NC, PXO, CH}.code(): hipLaunchKernelGGL((idwt53_pk_kernel<NC, PXO, CH>), grid, block, 0, s, a); break;
+        GRK_IDWT_PK_INSTANCES(GRK_X)
+#undef GRK_X
+        default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (in.k.code()) {
+#define GRK_X(F97, NC, PXO, H16, STR) case IdwtKey{F97, NC, PXO, H16, STR}.code(): hipLaunchKernelGGL((idwt_level_kernel<F97, NC, PXO, H16, STR>), grid, block, 0, s, a); break;
+        GRK_IDWT_INSTANCES(GRK_X)
+#undef GRK_X
+        default: return hipErrorInvalidValue;
+        }
     }
-    if (a.irreversible)
-        hipLaunchKernelGGL((idwt_level_kernel<true, 1, 0>), grid, block, 0, s, a);
-    else if (a.h16)
-        hipLaunchKernelGGL((idwt_level_kernel<false, 1, 0, true>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((idwt_level_kernel<false, 1, 0>), grid, block, 0, s, a);
-    return hipGetLastError();
+    return hipSuccess;
+}
+
+hipError_t launch_idwt_level(const IdwtLevelArgs& a, const IdwtLevelShape& sh, hipStream_t s)
+{
+    const hipError_t e = launch_idwt_instance(sh.inst[0], dim3(1, sh.grid_y, a.nplanes), a, s);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // The last level (cw x ch = tile size) straight to pixels (a0.pixels, px_bytes 1 or 2, dc/lo/hi, mct set by the caller);
 // a0.nplanes is ignored: the grid covers ntiles x (MCT triple | every component on its own).
-hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, uint32_t ntiles, uint32_t ncomp, hipStream_t s)
+hipError_t launch_idwt_level0_fused(const IdwtLevelArgs& a0, const IdwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, hipStream_t s)
 {
-    const uint32_t sw = (a0.cw + a0.px + 1) >> 1, sh = (a0.ch + a0.py + 1) >> 1;
-    dim3 block(kThreads);
-    auto go = [&](uint32_t comp0, uint32_t zdiv, int nc) {
+    for (uint32_t i = 0; i < level_part_count(a0.mct != 0, ncomp); ++i) {
+        const LevelPart part = level_part(a0.mct != 0, ncomp, i);      // (components beyond the triple: no colour transform, NC = 1)
         IdwtLevelArgs a = a0;
-        a.comp0 = comp0; a.zdiv = zdiv; a.ncomp = ncomp;
-        dim3 grid(a.nstrips ? a.nstrips : (sw + kOutPairs - 1) / kOutPairs, a.nsegs ? a.nsegs : (sh + a.seg_pairs - 1) / a.seg_pairs, ntiles * zdiv);
-#define GRK_I0(F97, NC, PX) hipLaunchKernelGGL((idwt_level_kernel<F97, NC, PX>), grid, block, 0, s, a)
-        const int px = a.px_bytes == 1 ? 1 : 2;
-        if (a.irreversible && a.px_lay != 0) {
-            if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<true, 3, 1, false, true>), grid, block, 0, s, a);
-                           else         hipLaunchKernelGGL((idwt_level_kernel<true, 3, 2, false, true>), grid, block, 0, s, a); }
-            else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<true, 1, 1, false, true>), grid, block, 0, s, a);
-                           else         hipLaunchKernelGGL((idwt_level_kernel<true, 1, 2, false, true>), grid, block, 0, s, a); }
-        } else if (a.irreversible) {
-            if (nc == 3) { if (px == 1) GRK_I0(true, 3, 1); else GRK_I0(true, 3, 2); }
-            else         { if (px == 1) GRK_I0(true, 1, 1); else GRK_I0(true, 1, 2); }
-        } else if (a.px_lay != 0) {
-            // a layout of the caller's.  The packed instances: one-channel pixels, or the MCT triple into three- / four-channel ones,
-            // tiles and rows on 4-byte alignment (whole dwords are stored), row offsets within 32 bits; the strided back end otherwise
-            const bool whole = a.wx0 == 0 && a.wy0 == 0 && a.wx1 == a.cw && a.wy1 == a.ch;
-            const bool al = (((uintptr_t)a.pixels | a.px_row | a.px_tile) & 3u) == 0 && a.px_row * a.ch < (1ull << 31);
-            const bool shape = a.px_lay == 2 && ((a.px_chan == 1 && nc == 1) || ((a.px_chan == 3 || a.px_chan == 4) && nc == 3 && a.mct));
-            if (px == 1 && idwt_level_is_pk(a) && a.lo == 0 && a.hi == 255 && whole && al && shape) {
-                grid.x = (a.cw + ipk_strip_cols(a.cw) - 1) / ipk_strip_cols(a.cw);
-                if (a.px_chan == 1)      hipLaunchKernelGGL((idwt53_pk_kernel<1, 1, 1>), grid, block, 0, s, a);
-                else if (a.px_chan == 3) hipLaunchKernelGGL((idwt53_pk_kernel<3, 1, 3>), grid, block, 0, s, a);
-                else                     hipLaunchKernelGGL((idwt53_pk_kernel<3, 1, 4>), grid, block, 0, s, a);
-            } else if (a.h16) {
-                if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 3, 1, true, true>), grid, block, 0, s, a);
-                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 3, 2, true, true>), grid, block, 0, s, a); }
-                else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 1, 1, true, true>), grid, block, 0, s, a);
-                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 1, 2, true, true>), grid, block, 0, s, a); }
-            } else {
-                if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 3, 1, false, true>), grid, block, 0, s, a);
-                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 3, 2, false, true>), grid, block, 0, s, a); }
-                else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 1, 1, false, true>), grid, block, 0, s, a);
-                               else         hipLaunchKernelGGL((idwt_level_kernel<false, 1, 2, false, true>), grid, block, 0, s, a); }
-            }
-        } else if (px == 1 && idwt_level_is_pk(a) && a.lo == 0 && a.hi == 255 && a.wx0 == 0 && a.wy0 == 0 && a.wx1 == a.cw && a.wy1 == a.ch &&
-                   (nc == 1 || a.mct)) {
-            grid.x = (a.cw + ipk_strip_cols(a.cw) - 1) / ipk_strip_cols(a.cw);
-            if (nc == 3) hipLaunchKernelGGL((idwt53_pk_kernel<3, 1>), grid, block, 0, s, a);
-            else         hipLaunchKernelGGL((idwt53_pk_kernel<1, 1>), grid, block, 0, s, a);
-        } else if (a.h16) {
-            if (nc == 3) { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 3, 1, true>), grid, block, 0, s, a);
-                           else         hipLaunchKernelGGL((idwt_level_kernel<false, 3, 2, true>), grid, block, 0, s, a); }
-            else         { if (px == 1) hipLaunchKernelGGL((idwt_level_kernel<false, 1, 1, true>), grid, block, 0, s, a);
-                           else         hipLaunchKernelGGL((idwt_level_kernel<false, 1, 2, true>), grid, block, 0, s, a); }
-        } else {
-            if (nc == 3) { if (px == 1) GRK_I0(false, 3, 1); else GRK_I0(false, 3, 2); }
-            else         { if (px == 1) GRK_I0(false, 1, 1); else GRK_I0(false, 1, 2); }
-        }
-#undef GRK_I0
-    };
-    if (a0.mct && ncomp >= 3) {
-        go(0, 1, 3);
-        for (uint32_t k = 3; k < ncomp; ++k) go(k, 1, 1);    // components beyond the triple: no colour transform (NC = 1)
-    } else {
-        go(0, ncomp, 1);
+        a.comp0 = part.comp0; a.zdiv = part.zdiv; a.ncomp = ncomp;
+        const hipError_t e = launch_idwt_instance(sh.inst[part.nc == 3], dim3(1, sh.grid_y, ntiles * part.zdiv), a, s);
+        if (e != hipSuccess) return e;
     }
     return hipGetLastError();
 }
 
-hipError_t launch_egress(const EgressArgs& a, hipStream_t s)
+template <int BYTES> struct EgressPix { using type = typename std::conditional<BYTES == 1, uint8_t, typename std::conditional<BYTES == 2, uint16_t, int32_t>::type>::type; };
+
+hipError_t launch_egress(const EgressArgs& a, const EgressKey& key, hipStream_t s)
 {
     dim3 grid((a.w + 1023) / 1024, a.h, a.ntiles), block(256);
-#define GRK_EGRESS(PIX, STR)                                                                     \
-    switch (a.ncomp) {                                                                          \
-    case 1: hipLaunchKernelGGL((egress_kernel<PIX, 1, STR>), grid, block, 0, s, a); break;      \
-    case 2: hipLaunchKernelGGL((egress_kernel<PIX, 2, STR>), grid, block, 0, s, a); break;      \
-    case 3: hipLaunchKernelGGL((egress_kernel<PIX, 3, STR>), grid, block, 0, s, a); break;      \
-    default: hipLaunchKernelGGL((egress_kernel<PIX, 4, STR>), grid, block, 0, s, a); break;     \
+    switch (key.code()) {
+#define GRK_X(BYTES, NC, STR) case EgressKey{BYTES, NC, STR}.code(): hipLaunchKernelGGL((egress_kernel<EgressPix<BYTES>::type, NC, STR>), grid, block, 0, s, a); break;
+    GRK_EGRESS_INSTANCES(GRK_X)
+#undef GRK_X
+    default: return hipErrorInvalidValue;
     }
-    if (a.px_lay && a.bytes_per_sample == 1) { GRK_EGRESS(uint8_t, true) }
-    else if (a.px_lay && a.bytes_per_sample == 2) { GRK_EGRESS(uint16_t, true) }
-    else if (a.bytes_per_sample == 1) { GRK_EGRESS(uint8_t, false) }
-    else if (a.bytes_per_sample == 2) { GRK_EGRESS(uint16_t, false) }
-    else { GRK_EGRESS(int32_t, false) }
-#undef GRK_EGRESS
     return hipGetLastError();
 }
 

@@ -114,4 +114,61 @@ int64_t dp_region(const grk_amd_tile_params* p, const uint32_t* win, uint32_t* l
     for (uint64_t i = 0; i < nrows; ++i) res[i] = g.blocks_comp0[i % g.blocks_per_comp].res;
     return (int64_t)nrows;
 }
+
+// kIdwtStripPairs, kIdwtHaloPairs, kIpkStripCols, kIdwtMinWgs, kIdwtRegionSegPairs
+void dp_idwt_constants(uint32_t* out)
+{
+    out[0] = kIdwtStripPairs; out[1] = kIdwtHaloPairs; out[2] = kIpkStripCols; out[3] = kIdwtMinWgs; out[4] = kIdwtRegionSegPairs;
+}
+uint32_t dp_ipk_strip_cols(uint32_t cw) { return ipk_strip_cols(cw); }
+
+// in = {cw, ch, px, py, ll_stride, m_stride, out_stride, h16, pk, irreversible, zslots, region, need x0, y0, x1, y1, fused, px_bytes, lo, hi,
+//       mct, px_lay, px_chan, px_row, px_tile, px_align}
+// out = {packed, strip_pairs, seg_pairs, grid_x, grid_y, strip0, nstrips, seg0, nsegs, wx0, wy0, wx1, wy1}, then for the part of one
+//       component and for the MCT triple {packed, grid_x, 32-bit key: f97, nc, pxo, h16, str, packed key: nc, pxo, ch}
+void dp_idwt_level(const int64_t* in, uint32_t* out)
+{
+    IdwtLevelDesc d{};
+    d.cw = (uint32_t)in[0]; d.ch = (uint32_t)in[1]; d.px = (uint32_t)in[2]; d.py = (uint32_t)in[3];
+    d.ll_stride = (uint32_t)in[4]; d.m_stride = (uint32_t)in[5]; d.out_stride = (uint32_t)in[6];
+    d.h16 = in[7] != 0; d.pk = in[8] != 0; d.irreversible = in[9] != 0; d.zslots = (uint32_t)in[10];
+    d.region = in[11] != 0; d.need = Rect{(uint32_t)in[12], (uint32_t)in[13], (uint32_t)in[14], (uint32_t)in[15]};
+    d.fused = in[16] != 0; d.px_bytes = (uint32_t)in[17]; d.lo = (int32_t)in[18]; d.hi = (int32_t)in[19]; d.mct = in[20] != 0;
+    d.px_lay = (uint32_t)in[21]; d.px_chan = (uint32_t)in[22]; d.px_row = (uint64_t)in[23]; d.px_tile = (uint64_t)in[24];
+    d.px_align = (uint32_t)in[25];
+    const IdwtLevelShape s = plan_idwt_level(d);
+    const uint32_t head[13] = {s.packed, s.strip_pairs, s.seg_pairs, s.grid_x, s.grid_y, s.strip0, s.nstrips, s.seg0, s.nsegs, s.wx0, s.wy0, s.wx1, s.wy1};
+    std::copy(head, head + 13, out);
+    for (int i = 0; i < 2; ++i) {
+        const IdwtInstance& n = s.inst[i];
+        const uint32_t row[10] = {n.packed, n.grid_x, n.k.f97, n.k.nc, n.k.pxo, n.k.h16, n.k.str, n.pk.nc, n.pk.pxo, n.pk.ch};
+        std::copy(row, row + 10, out + 13 + 10 * i);
+    }
+}
+// out = {bytes, nc, str}
+void dp_egress_key(uint32_t px_lay, uint32_t bytes_per_sample, uint32_t ncomp, uint32_t* out)
+{
+    const EgressKey k = egress_key(px_lay, bytes_per_sample, ncomp);
+    out[0] = k.bytes; out[1] = k.nc; out[2] = k.str;
+}
+// the inverse kernels' instance lists (dwt_instances.h): rows of {f97, nc, pxo, h16, str} / {nc, pxo, ch} / {bytes, nc, str}; each returns
+// the number of rows
+uint32_t dp_idwt_instances(uint32_t* out)
+{
+    uint32_t n = 0;
+    for (const IdwtKey& k : kIdwtInstances) { const uint32_t row[5] = {k.f97, k.nc, k.pxo, k.h16, k.str}; std::copy(row, row + 5, out + 5 * n++); }
+    return n;
+}
+uint32_t dp_idwt_pk_instances(uint32_t* out)
+{
+    uint32_t n = 0;
+    for (const IdwtPkKey& k : kIdwtPkInstances) { const uint32_t row[3] = {k.nc, k.pxo, k.ch}; std::copy(row, row + 3, out + 3 * n++); }
+    return n;
+}
+uint32_t dp_egress_instances(uint32_t* out)
+{
+    uint32_t n = 0;
+    for (const EgressKey& k : kEgressInstances) { const uint32_t row[3] = {k.bytes, k.nc, k.str}; std::copy(row, row + 3, out + 3 * n++); }
+    return n;
+}
 } // extern "C"

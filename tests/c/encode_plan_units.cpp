@@ -93,14 +93,41 @@ void ep_route(const grk_amd_tile_params* p, const uint64_t* in, int* out)
     out[0] = r.fused; out[1] = r.overlap; out[2] = r.frame_stream; out[3] = r.h16;
 }
 
-// in = {cw, ch, px, py, in_stride, m_stride, h16, pk, irreversible, px_lay, px_chan, px_row, zslots}
-// out = {packed, lanes, strip_cols, all_fast, seg_pairs, grid_x, grid_y}
+// in = {cw, ch, px, py, in_stride, m_stride, h16, pk, irreversible, px_lay, px_chan, px_row, zslots, fused, px_bytes}
+// out = {packed, lanes, strip_cols, all_fast, seg_pairs, grid_x, grid_y}, then for the part of one component and for the MCT triple
+//       {packed, 32-bit key: f97, nc, px, h16, gen, str, packed key: nc, px, nt, ch}
 void ep_level(const uint64_t* in, uint32_t* out)
 {
     const DwtLevelShape s = plan_dwt_level(DwtLevelDesc{(uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], (uint32_t)in[4],
                                                         (uint32_t)in[5], in[6] != 0, in[7] != 0, in[8] != 0, (uint32_t)in[9], (uint32_t)in[10],
-                                                        in[11], (uint32_t)in[12]});
+                                                        in[11], (uint32_t)in[12], in[13] != 0, (uint32_t)in[14]});
     out[0] = s.packed; out[1] = s.lanes; out[2] = s.strip_cols; out[3] = s.all_fast; out[4] = s.seg_pairs; out[5] = s.grid_x; out[6] = s.grid_y;
+    for (int i = 0; i < 2; ++i) {
+        const DwtInstance& n = s.inst[i];
+        const uint32_t row[11] = {n.packed, n.k.f97, n.k.nc, n.k.px, n.k.h16, n.k.gen, n.k.str, n.pk.nc, n.pk.px, n.pk.nt, n.pk.ch};
+        std::copy(row, row + 11, out + 7 + 11 * i);
+    }
+}
+// the forward kernels' instance lists (dwt_instances.h): rows of {f97, nc, px, h16, gen, str} / {nc, px, nt, ch}; returns the number of rows
+uint32_t ep_dwt_instances(uint32_t* out)
+{
+    uint32_t n = 0;
+    for (const DwtKey& k : kDwtInstances) { const uint32_t row[6] = {k.f97, k.nc, k.px, k.h16, k.gen, k.str}; std::copy(row, row + 6, out + 6 * n++); }
+    return n;
+}
+uint32_t ep_dwt_pk_instances(uint32_t* out)
+{
+    uint32_t n = 0;
+    for (const DwtPkKey& k : kDwtPkInstances) { const uint32_t row[4] = {k.nc, k.px, k.nt, k.ch}; std::copy(row, row + 4, out + 4 * n++); }
+    return n;
+}
+// the parts of a level fused with the pixels: rows of {comp0, zdiv, nc}; out[0] = z slots per tile; returns the number of parts
+uint32_t ep_level_parts(int mct, uint32_t ncomp, uint32_t* out)
+{
+    const uint32_t n = level_part_count(mct != 0, ncomp);
+    out[0] = level_part_zslots(mct != 0, ncomp);
+    for (uint32_t i = 0; i < n; ++i) { const LevelPart p = level_part(mct != 0, ncomp, i); out[1 + 3 * i] = p.comp0; out[2 + 3 * i] = p.zdiv; out[3 + 3 * i] = p.nc; }
+    return n;
 }
 uint32_t ep_pk_strip_cols(uint32_t cw, uint32_t nt) { return pk_strip_cols(cw, nt); }
 } // extern "C"

@@ -369,12 +369,23 @@ def test_route():
 
 # ---- level shape -----------------------------------------------------------------------------------------------------------------
 
-def level(cw, ch, px=0, py=0, in_stride=None, m_stride=None, h16=True, pk=True, irreversible=False, px_lay=0, px_chan=0, px_row=0, zslots=1):
-    out = np.zeros(7, np.uint32)
+def _level(cw, ch, px=0, py=0, in_stride=None, m_stride=None, h16=True, pk=True, irreversible=False, px_lay=0, px_chan=0, px_row=0, zslots=1,
+           fused=False, px_bytes=1):
+    out = np.zeros(29, np.uint32)
     stride = (cw + 31) & ~31
     lib().ep_level(ptr(np.array([cw, ch, px, py, stride if in_stride is None else in_stride, stride if m_stride is None else m_stride,
-                                 h16, pk, irreversible, px_lay, px_chan, px_row, zslots], np.uint64)), ptr(out))
-    return dict(zip(("packed", "lanes", "strip_cols", "all_fast", "seg_pairs", "grid_x", "grid_y"), (int(v) for v in out)))
+                                 h16, pk, irreversible, px_lay, px_chan, px_row, zslots, fused, px_bytes], np.uint64)), ptr(out))
+    return [int(v) for v in out]
+
+
+def level(*args, **kw):
+    return dict(zip(("packed", "lanes", "strip_cols", "all_fast", "seg_pairs", "grid_x", "grid_y"), _level(*args, **kw)[:7]))
+
+
+def level_inst(nc, *args, **kw):
+    """the instance of the part of nc components (1, or 3: the MCT triple): ("pk", NC, PX, NT, CH) or ("k", F97, NC, PX, H16, GEN, STR)"""
+    row = _level(*args, **kw)[7 + 11 * (nc == 3):][:11]
+    return ("pk",) + tuple(row[7:11]) if row[0] else ("k",) + tuple(row[1:7])
 
 
 def test_level_packed_or_not():
@@ -440,3 +451,91 @@ def test_level_headline_8k():
     assert 2 * got["seg_pairs"] == 32
     # (the 32-bit kernels' 19 strips of 448 columns at their floor of 4096: 19 x 128 = 2432, 19 x 256 = 4864 -> 16 as well)
     assert level(8192, 8192, zslots=1, pk=False) == dict(packed=0, lanes=256, strip_cols=448, all_fast=1, seg_pairs=16, grid_x=19, grid_y=256)
+
+
+# ---- kernel instances ------------------------------------------------------------------------------------------------------------
+
+def instance_tables():
+    out = np.zeros(6 * 64, np.uint32)
+    n = lib().ep_dwt_instances(ptr(out))
+    k = [("k",) + tuple(int(v) for v in out[6 * i:6 * i + 6]) for i in range(n)]
+    n = lib().ep_dwt_pk_instances(ptr(out))
+    return k, [("pk",) + tuple(int(v) for v in out[4 * i:4 * i + 4]) for i in range(n)]
+
+
+def old_forward_ladder(fused, nc, packed, lanes, all_fast, irreversible, h16, px_bytes, px_lay, px_chan):
+    """the nested ifs of launch_dwt_level / launch_dwt_level0_fused as they stood before the lists (dwt_instances.h), rung by rung;
+    sh.packed, sh.lanes, sh.all_fast came from plan_dwt_level then as now"""
+    def k(f97, nc, px, h16=0, gen=1, str_=0):
+        return ("k", f97, nc, px, h16, gen, str_)
+
+    def l0(f97, nc, px):                       # GRK_L0: the all-fast form where every strip is fast
+        return k(f97, nc, px, 0, 0 if all_fast else 1)
+    if not fused:
+        if packed:
+            return ("pk", 1, 0, lanes, 0)
+        if irreversible:
+            return k(1, 1, 0)
+        return k(0, 1, 0, 1) if h16 else k(0, 1, 0)
+    px = 1 if px_bytes == 1 else 2
+    if px_lay != 0:
+        if not irreversible and px == 1 and packed:
+            if px_chan == 1:
+                return ("pk", 1, 1, lanes, 1)
+            if px_chan == 3:
+                return ("pk", 3 if nc == 3 else 1, 1, lanes, 3)
+            return ("pk", 3 if nc == 3 else 1, 1, lanes, 4)
+        if irreversible:
+            return k(1, nc, px, 0, 1, 1)
+        if h16 and px == 1:
+            return k(0, nc, 1, 1, 1, 1)
+        return k(0, nc, px, 0, 1, 1)
+    if irreversible:
+        return l0(1, nc, px)
+    if px == 1 and packed:
+        return ("pk", nc, 1, lanes, 0)
+    if h16 and px == 1:
+        return k(0, nc, 1, 1)
+    return l0(0, nc, px)
+
+
+def test_level_parts():
+    """the MCT triple, then each further component on its own; or every component on its own, as z slots of one launch"""
+    def parts(mct, ncomp):
+        out = np.zeros(16, np.uint32)
+        n = lib().ep_level_parts(mct, ncomp, ptr(out))
+        return int(out[0]), [tuple(int(v) for v in out[1 + 3 * i:4 + 3 * i]) for i in range(n)]
+    assert parts(1, 3) == (1, [(0, 1, 3)])
+    assert parts(1, 4) == (1, [(0, 1, 3), (3, 1, 1)])
+    assert parts(1, 6) == (1, [(0, 1, 3), (3, 1, 1), (4, 1, 1), (5, 1, 1)])
+    for ncomp in (1, 2, 3, 4):
+        assert parts(0, ncomp) == (ncomp, [(0, ncomp, 1)])
+    assert parts(1, 2) == (2, [(0, 2, 1)]) and parts(1, 1) == (1, [(0, 1, 1)])       # (no triple to transform)
+
+
+def test_instance_tables_against_the_old_ladder():
+    """Over the descriptor's discrete fields (shapes: packed with 128 and with 256 lanes, all-fast, general): the planner's key is what
+    the old ladder picked, it is in its kernel's list, and every row of both lists is picked at least once."""
+    k_rows, pk_rows = instance_tables()
+    assert len(k_rows) == len(set(k_rows)) == 31 and len(pk_rows) == len(set(pk_rows)) == 16
+    seen = set()
+    for (cw, ch), fused, irreversible, h16, pk, px_bytes, px_lay, px_chan in itertools.product(
+            ((1024, 64), (4096, 64), (34, 18), (33, 17)), (False, True), (False, True), (False, True), (False, True), (1, 2), (0, 1, 2),
+            (1, 2, 3, 4)):
+        kw = dict(h16=h16, pk=pk, irreversible=irreversible, px_lay=px_lay if fused else 0, px_chan=px_chan if fused else 0,
+                  px_row=cw * px_chan * px_bytes if fused else 0, fused=fused, px_bytes=px_bytes)
+        sh = level(cw, ch, **kw)
+        for nc in (1, 3) if fused else (1,):
+            got = level_inst(nc, cw, ch, **kw)
+            want = old_forward_ladder(fused, nc, sh["packed"], sh["lanes"], sh["all_fast"], irreversible, h16, px_bytes, kw["px_lay"], kw["px_chan"])
+            assert got == want, (cw, ch, nc, kw)
+            assert got in (pk_rows if got[0] == "pk" else k_rows), (cw, ch, nc, kw)
+            seen.add(got)
+    assert seen == set(k_rows) | set(pk_rows), "rows no descriptor selects: %s" % sorted((set(k_rows) | set(pk_rows)) - seen)
+
+
+def test_unfused_level_names_no_triple_instance():
+    """a level between planes has one part; the triple's slot holds a key that is in no list (the launcher refuses it)"""
+    k_rows, pk_rows = instance_tables()
+    row = _level(1024, 64)[18:]
+    assert ("k",) + tuple(row[1:7]) not in k_rows and ("pk",) + tuple(row[7:11]) not in pk_rows

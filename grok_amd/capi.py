@@ -83,6 +83,26 @@ class StreamInfo(C.Structure):
                 ("num_blocks", C.c_uint64)]
 
 
+class Rate(C.Structure):
+    """grk_amd_rate: target_bytes (the blocks' bytes for encode_tiles_rate, the whole file for encode_image_rate), max_drop (Dmax;
+    0 = 6, at most 12), allow_skip"""
+    _fields_ = [("target_bytes", C.c_uint64), ("max_drop", C.c_uint8), ("allow_skip", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+class RateResult(C.Structure):
+    """grk_amd_rate_result"""
+    _fields_ = [("block_bytes", C.c_uint64), ("lagrange_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("distortion", C.c_double),
+                ("lambda_", C.c_double), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RateError(RuntimeError):
+    """a rate-targeted call refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ERR_OVERFLOW -5) and the context's reason"""
+
+    def __init__(self, what, code, reason):
+        RuntimeError.__init__(self, "%s failed: %d (%s)" % (what, code, reason))
+        self.code, self.reason = int(code), reason
+
+
 class ImageView(C.Structure):
     """grk_amd_image_view: reduce (the N finest resolutions dropped) and a window [x0, x1) x [y0, y1) of the (reduced) image, all
     four 0 = the whole image"""
@@ -250,6 +270,12 @@ def lib():
         L.grk_amd_stage_dwt_fwd.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_encode.argtypes = [vp, PP, u32, vp]
         L.grk_amd_stage_ht_encode16.argtypes = [vp, PP, u32, vp, u32]
+        if hasattr(L, "grk_amd_encode_tiles_rate"):       # (absent from older builds loaded through GRK_AMD_LIB for A/B timing)
+            L.grk_amd_stage_ht_encode_drops.argtypes = [vp, PP, u32, vp, i32, vp]
+            L.grk_amd_encode_tiles_rate.argtypes = [vp, PP, u32, vp, i32, C.POINTER(Rate), vp, C.POINTER(u64), C.POINTER(RateResult)]
+            L.grk_amd_encode_image_rate.restype = C.c_int64
+            L.grk_amd_encode_image_rate.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, u32, C.POINTER(Rate), vp, u64, C.POINTER(RateResult)]
+            L.grk_amd_rate_tables.argtypes = [vp, i32, vp, u64]
         L.grk_amd_stage_dwt_inv.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_decode.argtypes = [vp, PP, u32, vp, vp, u64, vp]
         L.grk_amd_stage_ht_decode16.argtypes = [vp, PP, u32, vp, vp, u64, vp]
@@ -387,6 +413,8 @@ def reduced_tile_rect(params, reduce):
 
 
 CS_TLM, CS_PLT, CS_SOP, CS_EPH = 1, 2, 4, 8
+CS_BLOCK_MSBS = 16           # the zero-bit-plane tag trees from the rows' own missing_msbs (the host writers only)
+DROP_SKIP = 0xFF             # a block's drop byte: not coded (grk_amd_stage_ht_encode_drops, rate_tables(3))
 STAGE_HT_ROOM = 1            # grk_amd_stage_ht_encode16 flags
 
 
@@ -614,6 +642,10 @@ class Context:
     def _check(self, rc, what):
         if rc != 0:
             raise RuntimeError("%s failed: %d (%s)" % (what, rc, self._L.grk_amd_last_error(self._h).decode()))
+
+    def last_error(self):
+        """grk_amd_last_error: why the latest failing call failed -- or the note a successful rate-targeted call left"""
+        return self._L.grk_amd_last_error(self._h).decode()
 
     def set_stream(self, stream_ptr):
         self._check(self._L.grk_amd_set_stream(self._h, stream_ptr), "set_stream")
@@ -848,6 +880,46 @@ class Context:
     def stage_ht_encode16(self, params, ntiles, d_mallat16, flags=0):
         """K3 from int16 Mallat planes (grk_amd_stage_ht_encode16); flags: STAGE_HT_ROOM."""
         self._check(self._L.grk_amd_stage_ht_encode16(self._h, C.byref(params), ntiles, d_mallat16, flags), "stage_ht_encode16")
+
+    def stage_ht_encode_drops(self, params, ntiles, d_mallat, planes16, d_drops):
+        """K3 through the instances that take a per-block drop (grk_amd_stage_ht_encode_drops): d_drops = ntiles * blocks_per_tile
+        bytes on the device, 0 .. 254 bit-planes left out or DROP_SKIP; keep them until the table has been fetched."""
+        self._check(self._L.grk_amd_stage_ht_encode_drops(self._h, C.byref(params), ntiles, d_mallat, int(bool(planes16)), d_drops),
+                    "stage_ht_encode_drops")
+
+    def encode_tiles_rate(self, params, ntiles, pixels_ptr, on_device, target_bytes, max_drop=0, allow_skip=False):
+        """grk_amd_encode_tiles_rate: the batch's blocks in at most target_bytes -> (table, total arena bytes, RateResult)"""
+        n = self._L.grk_amd_tile_num_blocks(C.byref(params)) * ntiles
+        table = np.zeros(n, CODED_DTYPE)
+        tot = C.c_uint64(0)
+        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip))), RateResult()
+        rc = self._L.grk_amd_encode_tiles_rate(self._h, C.byref(params), ntiles, pixels_ptr, int(on_device), C.byref(rate), table.ctypes.data,
+                                               C.byref(tot), C.byref(res))
+        if rc:
+            raise RateError("encode_tiles_rate", rc, self._L.grk_amd_last_error(self._h).decode())
+        return table, tot.value, res
+
+    def encode_image_rate(self, layout, base, pixels, target_bytes, flags=0, max_drop=0, allow_skip=False):
+        """grk_amd_encode_image_rate: the image as a file of at most target_bytes -> (codestream bytes, RateResult)"""
+        px = np.ascontiguousarray(pixels)
+        cap = px.size * 4 + (1 << 20)
+        out = np.empty(cap, np.uint8)
+        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip))), RateResult()
+        n = self._L.grk_amd_encode_image_rate(self._h, C.byref(layout), C.byref(base), px.ctypes.data, flags, C.byref(rate), out.ctypes.data,
+                                              cap, C.byref(res))
+        if n < 0:
+            raise RateError("encode_image_rate", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def rate_tables(self, nblocks, max_drop=0):
+        """The tables of the latest rate-targeted call (grk_amd_rate_tables) -> (L uint32 [Dmax + 2, nblocks], E uint64 [Dmax + 2,
+        nblocks] (last row: SKIP), W float64 [nblocks], drop uint8 [nblocks])"""
+        rows = (int(max_drop) or 6) + 2
+        out = (np.zeros((rows, nblocks), np.uint32), np.zeros((rows, nblocks), np.uint64), np.zeros(nblocks, np.float64),
+               np.zeros(nblocks, np.uint8))
+        for which, a in enumerate(out):
+            self._check(self._L.grk_amd_rate_tables(self._h, which, a.ctypes.data, a.nbytes), "rate_tables")
+        return out
 
     def stage_ht_decode(self, params, ntiles, table, d_coded, coded_bytes, d_mallat):
         t = np.ascontiguousarray(table)

@@ -13,6 +13,7 @@ int assemble_enqueue(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntil
 {
     const TileGeom& g = c->geom;
     const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
     auto& T = c->t2;
     if (!T.valid || !same_params(T.p, *p) || T.order != order) {
         T.valid = false;

@@ -157,6 +157,12 @@ struct grk_amd_ctx {
     uint32_t last_ntiles = 0;
     uint64_t last_nblocks = 0;
     bool last_h16 = false;           // the latest encode left int16 coefficients in the Mallat planes
+    const uint8_t* last_drops = nullptr;   // the latest K3 launch took per-block drops: the context's copy of them (drops_keep, [last_nblocks]),
+    DevBuf drops_keep;                     // from which grk_amd_fetch_table makes the rows' zero bit-planes
+    // A rate-targeted encode (rate.hip): the tables over the latest front end's blocks -- L, E candidate-major (RatePlan), W, the
+    // chosen drop bytes, the allocator's result -- and what they were made for
+    DevBuf rate_L, rate_E, rate_W, rate_drop, rate_res;
+    struct RateState { bool valid = false; RatePlan plan{}; uint64_t nblocks = 0; uint32_t ntiles = 0; } rate;
     HostStage stage;                 // pinned chunks for pageable host buffers (copy_h2d)
     void* d2h_pin = nullptr; size_t d2h_cap = 0; std::vector<hipEvent_t> d2h_ev;   // copy_d2h: a staging area of the transfer's size, an event per piece
     // Full decode with overlap on: K5b of the top resolution's blocks (3/4 of them) runs on the side stream beside K5b of the
@@ -257,6 +263,13 @@ bool surface_direct_allowed();            // GRK_AMD_SURFACE_DIRECT != 0, read p
 
 // a pixel layout of the context that a call sets for its own batches, put back when the call ends (KeepLayout keep{slot, slot};)
 struct KeepLayout { grk_amd_pixel_layout& slot; grk_amd_pixel_layout keep; ~KeepLayout() { slot = keep; } };
+
+// ---- what a rate-targeted encode takes from encode.hip ----
+// K3 of `ntiles` tiles of the current geometry from the planes at d_mallat (int16 when h16) through the instances that take a
+// per-block drop (d_drops: device, tile-major in table order, read in stream order; the context keeps a copy for the table)
+int ht_encode_drops(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool h16, const uint8_t* d_drops);               // encode.hip
+// w_mct * w_band * stepsize of row `row` of a tile's block table (T1::getwmsedec; grk_amd_block_distortion)
+double block_weight(const TileGeom& g, uint32_t row);                                                                       // encode.hip
 
 // ---- steps the encode and decode units share ----
 // The first steps of a grk_amd_stage_* entry point: the side streams joined (where the stage reads what they write), the null

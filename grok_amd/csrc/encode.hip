@@ -155,9 +155,35 @@ int run_ht(grk_amd_ctx* c, HtArgs a, bool overlapped = false, bool room = false)
     }
     c->last_ntiles = a.ntiles;
     c->last_nblocks = (uint64_t)a.blocks_per_tile * a.ntiles;
+    c->last_drops = nullptr;
     return GRK_AMD_OK;
 }
 } // namespace
+
+// every block of the call on the main stream, class by class as a non-overlapped encode lays them out, through the drop instances
+int ht_encode_drops(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool h16, const uint8_t* d_drops)
+{
+    HtArgs a;
+    const int rc = make_ht_args(c, ntiles, d_mallat, h16, a); if (rc) return rc;
+    const HtDropPlan dp = plan_ht_drop_instance(a.irreversible != 0, a.h16 != 0);
+    if (!dp.ok) return fail(c, GRK_AMD_ERR_INVALID, "no encode keeps irreversible int16 planes");
+    // (the table's zero bit-planes are made from the drops when it is fetched, which may be long after the caller's buffer is gone)
+    const uint64_t nblocks = (uint64_t)a.blocks_per_tile * a.ntiles;
+    HIP_TRY(c, c->drops_keep.ensure(nblocks), "alloc drops copy");
+    HIP_TRY(c, hipMemcpyAsync(c->drops_keep.p, d_drops, nblocks, hipMemcpyDeviceToDevice, c->stream), "keep the drops");
+    {
+        ScopedTimer t(c, 2);
+        HIP_TRY(c, launch_ht_alloc_init(a, c->stream), "reset arena allocator");
+        for (uint32_t k = 0; k < a.num_classes; ++k) {
+            if (ht_class_stream(c->ht_classes[k].role, false, false, HtPoint::RunHt, false) != HtStream::Main) continue;
+            HIP_TRY(c, launch_ht_classes_drops(a, k, k + 1, d_drops, dp.inst, c->stream), "launch ht encode (drops)");
+        }
+    }
+    c->last_ntiles = a.ntiles;
+    c->last_nblocks = (uint64_t)a.blocks_per_tile * a.ntiles;
+    c->last_drops = (const uint8_t*)c->drops_keep.p;
+    return GRK_AMD_OK;
+}
 
 extern "C" {
 int grk_amd_stage_ingest_mct(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_pixels, void* d_planes)
@@ -194,6 +220,16 @@ int grk_amd_stage_ht_encode16(grk_amd_ctx* c, const grk_amd_tile_params* p, uint
     return run_ht(c, h, false, (flags & GRK_AMD_STAGE_HT_ROOM) != 0);
 }
 
+// the instances that take a per-block drop (kernels_ht.hip DROP), on planes and drops the caller chose
+int grk_amd_stage_ht_encode_drops(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* d_mallat, int planes16,
+                                  const uint8_t* d_drops)
+{
+    const int rc = stage_enter(c, p, d_mallat && d_drops && ntiles, true,
+                               planes16 && p && !planes16_ok(*p) ? "no encode keeps int16 planes for these parameters" : nullptr);
+    if (rc) return rc;
+    return ht_encode_drops(c, ntiles, d_mallat, planes16 != 0, d_drops);
+}
+
 int grk_amd_fetch_table(grk_amd_ctx* c, grk_amd_coded_block* table, uint64_t* total)
 {
     if (!c || !c->last_nblocks) return GRK_AMD_ERR_INVALID;
@@ -201,11 +237,16 @@ int grk_amd_fetch_table(grk_amd_ctx* c, grk_amd_coded_block* table, uint64_t* to
     { const int jr = join_side(c); if (jr) return jr; }
     const uint64_t n = c->last_nblocks;
     uint64_t flagwords[2] = {0, 0};       // [0] low 32 bits: overflow flag, [1]: arena cursor
+    std::vector<uint8_t> h_drops;         // the drop bytes of a launch that took them
     HIP_TRY(c, hipMemcpyAsync(flagwords, c->flag.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch flag");
     if (table) {
         c->h_off.resize(n); c->h_len.resize(n);
         HIP_TRY(c, hipMemcpyAsync(c->h_off.data(), c->offsets.p, n * 8, hipMemcpyDeviceToHost, c->stream), "fetch offsets");
         HIP_TRY(c, hipMemcpyAsync(c->h_len.data(), c->lengths.p, n * 4, hipMemcpyDeviceToHost, c->stream), "fetch lengths");
+        if (c->last_drops) {
+            h_drops.resize(n);
+            HIP_TRY(c, hipMemcpyAsync(h_drops.data(), c->last_drops, n, hipMemcpyDeviceToHost, c->stream), "fetch drops");
+        }
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
     if (flagwords[0] & 1u) return fail(c, GRK_AMD_ERR_OVERFLOW, "coded arena overflow");
@@ -215,6 +256,7 @@ int grk_amd_fetch_table(grk_amd_ctx* c, grk_amd_coded_block* table, uint64_t* to
         for (uint64_t i = 0; i < n; ++i) {
             table[i].offset = c->h_off[i]; table[i].length = c->h_len[i];
             table[i].missing_msbs = c->h_desc[i % bpt].kmax - 1u;      // numbps = 1 is signalled (T1HT.cpp:123)
+            if (!h_drops.empty()) table[i].missing_msbs = drop_missing_msbs(c->h_desc[i % bpt].kmax, h_drops[i]);   // ... d planes further down
         }
     }
     if (total) *total = flagwords[1];
@@ -267,6 +309,8 @@ int grk_amd_fetch_coefficients(grk_amd_ctx* c, uint32_t comp, int32_t* dst, uint
     return GRK_AMD_OK;
 }
 
+} // extern "C"
+
 // Weights of T1::getwmsedec (t1/t1_part1/T1.cpp:394-414): L2 norms of the synthesis basis functions by orientation and decomposition
 // level (dwt_norms / dwt_norms_real, T1.cpp:224-235; T1::getnorm clamps the level, :258-267) and of the inverse colour transform's
 // columns (mct_norms_rev / _irrev, point_transform/mct.cpp:30-35)
@@ -285,6 +329,17 @@ static double band_norm(uint32_t orient, uint32_t level, bool reversible)
     return reversible ? n53[orient & 3u][level] : n97[orient & 3u][level];
 }
 
+double block_weight(const TileGeom& g, uint32_t row)
+{
+    static const double mct_rev[3] = {1.732, .8292, .8292}, mct_irrev[3] = {1.732, 1.805, 1.573};
+    const grk_amd_block& b = g.blocks_comp0[row % g.blocks_per_comp];
+    const uint32_t comp = row / g.blocks_per_comp;
+    const double w1 = (g.p.mct && g.p.num_comps >= 3 && comp < 3) ? (g.p.irreversible ? mct_irrev[comp] : mct_rev[comp]) : 1.0;
+    const double w2 = band_norm(b.band, g.p.num_levels - b.res, !g.p.irreversible);
+    return w1 * w2 * (double)b.stepsize;
+}
+
+extern "C" {
 int grk_amd_block_distortion(grk_amd_ctx* c, double* out, uint64_t cap)
 {
     if (!c || !out || !c->have_geom || c->geom.reduce || !c->last_nblocks || cap < c->last_nblocks) return GRK_AMD_ERR_INVALID;
@@ -299,13 +354,8 @@ int grk_amd_block_distortion(grk_amd_ctx* c, double* out, uint64_t cap)
     std::vector<unsigned long long> e(n);
     HIP_TRY(c, hipMemcpyAsync(e.data(), c->energy.p, n * 8, hipMemcpyDeviceToHost, c->stream), "fetch block energies");
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-    static const double mct_rev[3] = {1.732, .8292, .8292}, mct_irrev[3] = {1.732, 1.805, 1.573};
     for (uint64_t i = 0; i < n; ++i) {
-        const grk_amd_block& b = g.blocks_comp0[(i % bpt) % g.blocks_per_comp];
-        const uint32_t comp = (uint32_t)((i % bpt) / g.blocks_per_comp);
-        const double w1 = (g.p.mct && g.p.num_comps >= 3 && comp < 3) ? (g.p.irreversible ? mct_irrev[comp] : mct_rev[comp]) : 1.0;
-        const double w2 = band_norm(b.band, g.p.num_levels - b.res, !g.p.irreversible);
-        const double w = w1 * w2 * (double)b.stepsize;
+        const double w = block_weight(g, (uint32_t)(i % bpt));
         out[i] = w * w * (double)e[i];
     }
     return GRK_AMD_OK;

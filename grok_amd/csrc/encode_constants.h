@@ -39,6 +39,15 @@ constexpr size_t   kLdsPerCu = 160u << 10;
 constexpr size_t   kMaxWavesPerCu = 32;
 constexpr size_t   kLdsFor16Waves = 10240;
 
+// ---- rate-targeted encodes: dropped bit-planes per block (kernels_ht.hip DROP, kernels_rate.hip) -------------------------------------
+constexpr uint32_t kHtDropSkip = 0xFFu;     // a block's drop byte: the block is not coded (length 0, zero bit-planes Kmax - 1)
+constexpr uint32_t kRateDefaultDrop = 6;    // grk_amd_rate::max_drop = 0
+constexpr uint32_t kRateMaxDrop = 12;       // the largest Dmax a caller may ask for
+constexpr uint32_t kRateMaxCand = kRateMaxDrop + 2;   // candidates of a block at most: d = 0 .. Dmax, SKIP
+constexpr uint32_t kRateAllocThreads = 1024;          // the allocator's one workgroup
+constexpr uint32_t kRateBisectSteps = 40;             // bisection steps of lambda once it is bracketed within a factor of two
+constexpr uint32_t kRateMaxRounds = 4;                // allocate + write rounds of grk_amd_encode_image_rate
+
 // ---- the call's route (encode.hip) -------------------------------------------------------------------------------------------------
 // Pipelined encodes of SMALL frames (up to kFrameStreamSamples samples per call): a frame's whole chain on ONE of the two side streams,
 // taken in turn -- no event inside a frame (12 instead of 18 runtime calls), consecutive frames overlap through the streams.  A call

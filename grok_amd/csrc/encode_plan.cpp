@@ -64,6 +64,29 @@ HtClassLds plan_ht_lds(uint32_t max_samples, uint32_t max_quads, uint32_t max_km
     return r;
 }
 
+// ---- the instances that take a per-block drop, and a rate-targeted call's tables ----------------------------------------------------
+HtDropPlan plan_ht_drop_instance(bool irreversible, bool h16)
+{
+    if (irreversible && h16) return HtDropPlan{false, {false, false}};
+    return HtDropPlan{true, {irreversible, h16}};
+}
+
+RatePlan plan_rate(uint32_t max_drop, bool allow_skip, uint64_t nblocks)
+{
+    RatePlan r{};
+    r.ok = max_drop <= kRateMaxDrop;
+    if (!r.ok) return r;
+    r.dmax = max_drop ? max_drop : kRateDefaultDrop;
+    r.rows = r.dmax + 2u;
+    r.ncand = r.dmax + 1u + (allow_skip ? 1u : 0u);
+    r.trials = r.dmax + 1u;
+    r.l_bytes = (uint64_t)r.rows * nblocks * 4u;
+    r.e_bytes = (uint64_t)r.rows * nblocks * 8u;
+    r.w_bytes = nblocks * 8u;
+    r.drop_bytes = nblocks;
+    return r;
+}
+
 // ---- the arena and its allocator ---------------------------------------------------------------------------------------------------
 HtArenaPlan plan_ht_arena(uint64_t nblocks, uint64_t raw_bytes, uint32_t ntiles, const std::vector<HtClassPlan>& classes)
 {

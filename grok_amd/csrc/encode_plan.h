@@ -51,6 +51,30 @@ size_t ht_waves_per_cu(size_t lds_bytes);          // waves of K3 a CU holds wit
 struct HtClassLds { HtLdsPlan full, cap; bool use_cap; };
 HtClassLds plan_ht_lds(uint32_t max_samples, uint32_t max_quads, uint32_t max_kmax, uint32_t cap_kmax, bool irrev, bool have_fallback);
 
+// ---- the instances that take a per-block drop, and a rate-targeted call's tables ----------------------------------------------------
+// Which ht_encode_drop_kernel instance a launch takes, from the plane form a non-pipelined encode holds: int32 reversible, int32
+// irreversible (float bit patterns), int16 for 8-bit reversible content (read through the general, non-packed fetch).
+struct HtDropInstance { bool irrev, h16; };
+struct HtDropPlan { bool ok; HtDropInstance inst; };           // ok = false: no such plane form (irreversible int16 planes do not exist)
+HtDropPlan plan_ht_drop_instance(bool irreversible, bool h16);
+// The candidates of a block and the tables over them.  Candidate c of 0 .. dmax: c bit-planes dropped; candidate dmax + 1: SKIP (its
+// row exists in L (all 0) and E whether or not the allocator may choose it).  Tables are candidate-major: row c holds nblocks entries
+// in table order.  trials: launches of the drop instances that fill L's rows 0 .. dmax.
+struct RatePlan {
+    bool ok;                           // max_drop within kRateMaxDrop
+    uint32_t dmax, rows, ncand;        // rows = dmax + 2 (of L and E); ncand = what the allocator chooses from: dmax + 1 (+ 1 with SKIP)
+    uint32_t trials;
+    uint64_t l_bytes, e_bytes, w_bytes, drop_bytes;
+};
+RatePlan plan_rate(uint32_t max_drop, bool allow_skip, uint64_t nblocks);
+// the drop byte of candidate c, and the row's zero bit-planes for a drop byte (d clamped to Kmax - 1; SKIP: Kmax - 1)
+inline uint8_t rate_drop_byte(uint32_t c, uint32_t dmax) { return c <= dmax ? (uint8_t)c : (uint8_t)kHtDropSkip; }
+inline uint32_t drop_missing_msbs(uint32_t kmax, uint32_t drop)
+{
+    const uint32_t top = kmax ? kmax - 1u : 0u;
+    return drop == kHtDropSkip ? top : top - (drop < top ? drop : top);
+}
+
 // ---- the arena and its allocator ---------------------------------------------------------------------------------------------------
 struct HtArenaPlan {
     uint32_t regions;                  // allocation regions in use (a power of two <= kHtAllocRegions): block i allocates from region i & (regions - 1)

@@ -186,6 +186,7 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
                                                    uint8_t* out, uint64_t cap)
 {
     if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (as the writer below would, before any work)
     {   // (components of different sizes have no interleaved form, and the runs are staged as planes)
         const grk_amd_pixel_layout& l = ctx->enc_layout;
         if (l.interleaved || l.channels || l.row_pitch || l.plane_pitch || l.tile_pitch) return GRK_AMD_ERR_UNSUPPORTED;

@@ -109,9 +109,36 @@ __device__ __forceinline__ void ht_alloc_reset(unsigned long long* flagbuf, uint
 hipError_t launch_ht_encode(const HtArgs& a, hipStream_t s);          // allocator reset + every class
 hipError_t launch_ht_alloc_init(const HtArgs& a, hipStream_t s);
 hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hipStream_t s);   // classes [first, last)
+// the same through the instances that take a per-block drop: drops[ntiles * blocks_per_tile] (device), tile-major in table order, each
+// 0 .. 254 bit-planes left out (clamped to Kmax - 1) or kHtDropSkip; inst: plan_ht_drop_instance (encode_plan.h) of a's plane form
+hipError_t launch_ht_classes_drops(const HtArgs& a, uint32_t first, uint32_t last, const uint8_t* drops, const HtDropInstance& inst, hipStream_t s);
 // sum of q^2 over each block of the planes an encode left (kernels_ingest.hip: the rate-control hook)
 hipError_t launch_block_energy(const void* mallat, int h16, int irreversible, uint32_t stride, uint64_t pitch, const HtBlockDesc* blocks,
                                uint32_t blocks_per_tile, uint32_t ncomp, uint64_t nblocks, unsigned long long* out, hipStream_t s);
+
+// ---- KR1 / KR2: a rate-targeted encode's statistics and allocator (kernels_rate.hip) -----------------------------------------------
+// Tables are candidate-major over the call's nblocks blocks in table order (RatePlan, encode_plan.h): rows 0 .. dmax = that many
+// bit-planes dropped, row dmax + 1 = SKIP.
+struct RateStatsArgs {
+    const void* mallat; int h16, irreversible; uint32_t stride; uint64_t pitch;      // the planes K3 codes from, as HtArgs
+    const HtBlockDesc* blocks; uint32_t blocks_per_tile, ncomp; uint64_t nblocks;
+    uint32_t dmax;
+    unsigned long long* E;             // [dmax + 2][nblocks]: sum of (2 q - 2 r_c(q))^2 over the block
+};
+hipError_t launch_rate_stats(const RateStatsArgs& a, hipStream_t s);
+struct RateAllocResult {
+    unsigned long long block_bytes, lagrange_bytes, least_bytes;      // the choice's bytes; the Lagrange solution's; the fewest any choice takes
+    double distortion, lambda;                                        // sum of W E of the choice; the multiplier
+    uint32_t feasible, steps;                                         // least_bytes <= budget; evaluations of the multiplier search
+};
+struct RateAllocArgs {
+    const uint32_t* L; const unsigned long long* E; const double* W;   // [rows][nblocks], [rows][nblocks], [nblocks]
+    uint64_t nblocks; uint32_t dmax, ncand;                            // ncand = dmax + 1, or dmax + 2 when SKIP may be chosen
+    uint64_t budget;
+    uint8_t* drop;                     // [nblocks]: the drop bytes for launch_ht_classes_drops
+    RateAllocResult* res;
+};
+hipError_t launch_rate_alloc(const RateAllocArgs& a, hipStream_t s);
 
 // ---- K5: HT cleanup decoder + dequantisation (kernels_htdec.hip) --------------------------------
 struct HtDecBlock {          // one per code-block, same layout as grk_amd_coded_block

@@ -442,8 +442,13 @@ struct HtLds { uint32_t ms_words, vlc_words, ms_cap_bits, vlc_cap_bits, stage_by
 
 // One code-block, by one wavefront.  li = index of the block in the launch's class list, tile = tile index.
 // H16: the Mallat planes hold int16 coefficients (reversible, 8-bit pixels; kernels_dwt.hip H16)
-template <bool IRREV, bool H16>
-__device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, uint32_t tile, const HtLds& L, uint32_t class_id)
+// DROP (the instances of ht_encode_drop_kernel, below): drops[gid] = d least significant bit-planes of the block left out -- the
+// magnitudes are coded as mu >> d under the exponent bound Kmax - d (the row's zero bit-planes are then Kmax - 1 - d; d is clamped to
+// Kmax - 1) --, or kHtDropSkip: the block is not coded at all (length 0).  A block with d > 0 whose shifted samples are all zero has
+// length 0 as well.  int16 planes are read sample by sample (the general fetch) in these instances.
+template <bool IRREV, bool H16, bool DROP = false>
+__device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, uint32_t tile, const HtLds& L, uint32_t class_id,
+                                                const uint8_t* drops = nullptr)
 {
     const uint32_t ms_words = L.ms_words, vlc_words = L.vlc_words;
     // LDS (sized by the launch, HtLds: for real content rather than the worst case, so that 24 waves fit a CU): raw MagSgn bits | raw VLC bits |
@@ -470,7 +475,17 @@ __device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, ui
                       (((size_t)tile * a.ncomp + bd.comp) * a.pitch + (size_t)bd.py * a.stride + bd.px) * EB;
     const bool full = w == 64 && h == 64 && ((bd.px | a.stride) & 1u) == 0;   // aligned row-pair loads, no edges
     const uint32_t kmax = bd.kmax;
-    const bool narrow = kmax + 2 <= 16;           // a quad's four MagSgn values fit 64 bits
+    uint32_t dshift = 0;
+    if constexpr (DROP) {
+        const uint32_t dr = (uint32_t)__builtin_amdgcn_readfirstlane((int)drops[gid]);
+        if (dr == kHtDropSkip) {
+            if (threadIdx.x == 0) { a.lengths[gid] = 0; a.offsets[gid] = 0; }
+            return;
+        }
+        dshift = min(dr, kmax ? kmax - 1u : 0u);
+    }
+    const uint32_t kcode = DROP ? kmax - dshift : kmax;       // the exponent bound the block is coded under
+    const bool narrow = kcode + 2 <= 16;          // a quad's four MagSgn values fit 64 bits
 
     uvlc_l[lane] = g_uvlc[lane];
     {   // clear the raw streams 16 bytes per lane and instruction (ms_words + vlc_words is a multiple of 4)
@@ -511,6 +526,7 @@ __device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, ui
     auto phase_a = [&](auto full_c) {
     constexpr bool FULL = decltype(full_c)::value;
     constexpr bool PK = FULL && H16;         // samples stay packed: word 0 = (x0, y0) | (x0+1, y0) << 16, word 1 = the row below
+    static_assert(!(PK && DROP), "the drop instances read int16 planes through the general fetch");
 
     // ---- sample fetch: r[0]=(x0,y0) [1]=(x0,y0+1) [2]=(x0+1,y0) [3]=(x0+1,y0+1) -------------------
     auto fetch = [&](uint32_t it, int32_t (&r)[4]) {
@@ -599,6 +615,7 @@ __device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, ui
                 } else {
                     mag = (uint32_t)max(r[i], -r[i]);
                 }
+                if constexpr (DROP) mag >>= dshift;
                 ovf |= mag;
                 t[i] = (mag << 1) - 1u;                                // val - 1  (val = 2*mag); -1: insignificant
                 o.vv[i] = t[i] - 1u + ((uint32_t)r[i] >> 31);          // val - 2 + sign
@@ -1094,7 +1111,9 @@ __device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, ui
     // The pair form for packed (8-bit reversible) content only: with four 32-bit samples per quad it needs 110 - 141 registers, four or
     // three waves per SIMD, and codes cfg3 13 % SLOWER than the one-quad form (same box: 0.537 against 0.476 ms).
     // (8-byte row loads: block origin and stride multiples of four samples -- every 64 x 64 block of a Mallat plane)
-    if constexpr (H16) {
+    if constexpr (H16 && DROP) {
+        phase_a(std::false_type{});
+    } else if constexpr (H16) {
         if (full && ((bd.px | a.stride) & 3u) == 0) phase_a2(); else phase_a(std::false_type{});
     } else {
         if (full) phase_a(std::true_type{}); else phase_a(std::false_type{});
@@ -1106,9 +1125,15 @@ __device__ __forceinline__ void ht_encode_block(const HtArgs& a, uint32_t li, ui
         }
         return;
     }
+    if constexpr (DROP) {                 // nothing left of the block behind the shift: no bytes
+        if (dshift != 0 && !__ballot(ovf != 0)) {
+            if (lane == 0) { a.lengths[gid] = 0; a.offsets[gid] = 0; }
+            return;
+        }
+    }
     // magnitudes beyond Kmax+1 bits: outside the contract (see header) -> flag, host reports it
     if constexpr (H16) ovf = (ovf & 0xFFFFu) | (ovf >> 16);          // FULL blocks accumulate two magnitudes per word
-    if (!IRREV && __ballot((ovf >> (kmax + 1)) != 0)) {
+    if (!IRREV && __ballot((ovf >> (kcode + 1)) != 0)) {
         if (lane == 0) atomicOr(reinterpret_cast<unsigned int*>(a.alloc), 2u);
     }
     __syncthreads();
@@ -1382,6 +1407,24 @@ __global__ __launch_bounds__(64) void ht_encode_fallback_kernel(HtArgs a, HtLds 
     }
 }
 
+// The instances that take a per-block drop (HtArgs as above + drops[ntiles * blocks_per_tile], tile-major in table order), and their
+// fallback launch.  Behind every other kernel of this file: the places of those in the code object do not move.
+template <bool IRREV, bool H16>
+__global__ __launch_bounds__(64) void ht_encode_drop_kernel(HtArgs a, HtLds L, uint32_t class_id, const uint8_t* drops)
+{
+    ht_encode_block<IRREV, H16, true>(a, blockIdx.x % a.sel_count, blockIdx.x / a.sel_count, L, class_id, drops);
+}
+template <bool IRREV, bool H16>
+__global__ __launch_bounds__(64) void ht_encode_drop_fallback_kernel(HtArgs a, HtLds L, uint32_t class_id, const uint8_t* drops)
+{
+    const uint32_t count = (uint32_t)a.alloc[2 + class_id];
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        const uint32_t id = a.ovf_list[a.ovf_base + i];
+        ht_encode_block<IRREV, H16, true>(a, id % a.sel_count, id / a.sel_count, L, class_id, drops);
+        __syncthreads();
+    }
+}
+
 } // namespace
 
 static std::atomic<bool> g_tables_ready[16];                 // (zero-initialised: false)
@@ -1486,6 +1529,39 @@ hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hip
         // images at the top resolution -- its workgroups leave at once)
         if (use_cap) GRK_HT(ht_encode_fallback_kernel, std::min<uint32_t>(grid, 1024u), shmem_full, full);
 #undef GRK_HT
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ht_classes_drops(const HtArgs& a, uint32_t first, uint32_t last, const uint8_t* drops, const HtDropInstance& inst, hipStream_t s)
+{
+    const uint32_t* vlc_tab = nullptr;
+    hipError_t e = ensure_tables(&vlc_tab);
+    if (e != hipSuccess) return e;
+    if (!drops || (inst.irrev && inst.h16) || (inst.irrev != (a.irreversible != 0)) || (inst.h16 != (a.h16 != 0))) return hipErrorInvalidValue;
+    for (uint32_t k = first; k < last && k < a.num_classes; ++k) {
+        const HtClass& c = a.classes[k];
+        if (c.count == 0) continue;
+        // the LDS plan of the class as for d = 0 (plan_ht_lds): dropped planes only shorten the raw streams
+        const HtClassLds lds = plan_ht_lds(c.max_samples, c.max_quads, c.max_kmax, c.cap_kmax, a.irreversible != 0, a.ovf_list != nullptr);
+        auto kernel_arg = [](const HtLdsPlan& p) { return HtLds{p.ms_words, p.vlc_words, p.ms_cap_bits, p.vlc_cap_bits, p.stage_bytes}; };
+        const bool use_cap = lds.use_cap;
+        const HtLds full = kernel_arg(lds.full), L = kernel_arg(use_cap ? lds.cap : lds.full);
+        const size_t shmem_full = lds.full.bytes, shmem = use_cap ? lds.cap.bytes : lds.full.bytes;
+        HtArgs b = a;
+        b.sel = c.sel; b.sel_count = c.count;
+        b.ovf_base = c.ovf_base;
+        b.vlc_tab = vlc_tab;
+        const uint32_t grid = c.count * a.ntiles;
+#define GRK_HT_DROP(KERNEL, G, SH, LL)                                                                                              \
+        do {                                                                                                                        \
+            if (inst.h16)        hipLaunchKernelGGL((KERNEL<false, true>), dim3(G), dim3(64), SH, s, b, LL, k, drops);              \
+            else if (inst.irrev) hipLaunchKernelGGL((KERNEL<true, false>), dim3(G), dim3(64), SH, s, b, LL, k, drops);              \
+            else                 hipLaunchKernelGGL((KERNEL<false, false>), dim3(G), dim3(64), SH, s, b, LL, k, drops);             \
+        } while (0)
+        GRK_HT_DROP(ht_encode_drop_kernel, grid, shmem, L);
+        if (use_cap) GRK_HT_DROP(ht_encode_drop_fallback_kernel, std::min<uint32_t>(grid, 1024u), shmem_full, full);
+#undef GRK_HT_DROP
     }
     return hipGetLastError();
 }

@@ -16,6 +16,7 @@
 #include "t2_order.h"
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace {
@@ -115,6 +116,50 @@ inline int new_nodes(uint32_t x, uint32_t y, int height)
 
 int floor_log2(uint32_t v) { int r = 0; while (v >>= 1) ++r; return r; }
 
+// The zero-bit-plane tag tree in its general form (GRK_AMD_CS_BLOCK_MSBS: the rows' own missing_msbs, which differ block by block
+// once an encode drops bit-planes): level 0 holds the leaves (gw x gh, raster), every level above the minimum of its up to four
+// children, up to one root.  A leaf is coded when its block is first included -- in this writer's single layer all of them, in
+// raster order -- against a threshold above its value: from the root down every node's lower bound is raised from what its parent
+// left to its value with one '0' per step, then a '1' the first time the value is reached (B.10.2; t1/TagTree.cpp:170-218).  With
+// every leaf at v this emits v '0's at the root and one '1' per new node: the constant form above, bit for bit.
+struct ZbpTree {
+    struct Level { uint32_t w, h; size_t at; };
+    std::vector<Level> lv;
+    std::vector<uint32_t> value, low;
+    std::vector<uint8_t> known;
+    ZbpTree(const grk_amd_coded_block* cb, uint32_t gw, uint32_t gh)
+    {
+        size_t n = 0;
+        for (uint32_t w = gw, h = gh;; w = (w + 1) >> 1, h = (h + 1) >> 1) {
+            lv.push_back(Level{w, h, n});
+            n += (size_t)w * h;
+            if ((uint64_t)w * h <= 1) break;
+        }
+        value.assign(n, 0xFFFFFFFFu); low.assign(n, 0); known.assign(n, 0);
+        for (size_t i = 0; i < (size_t)gw * gh; ++i) value[i] = cb[i].missing_msbs;
+        for (size_t l = 0; l + 1 < lv.size(); ++l)
+            for (uint32_t y = 0; y < lv[l].h; ++y)
+                for (uint32_t x = 0; x < lv[l].w; ++x) {
+                    uint32_t& up = value[lv[l + 1].at + (size_t)(y >> 1) * lv[l + 1].w + (x >> 1)];
+                    up = std::min(up, value[lv[l].at + (size_t)y * lv[l].w + x]);
+                }
+    }
+    template <class Bits> void code(Bits& hb, uint32_t x, uint32_t y)
+    {
+        const uint32_t threshold = value[(size_t)y * lv[0].w + x] + 1u;
+        uint32_t lo = 0;
+        for (size_t l = lv.size(); l-- > 0;) {
+            const size_t i = lv[l].at + (size_t)(y >> l) * lv[l].w + (x >> l);
+            lo = std::max(lo, low[i]);
+            while (lo < threshold) {
+                if (lo >= value[i]) { if (!known[i]) { hb.bit(1); known[i] = 1; } break; }
+                hb.bit(0); ++lo;
+            }
+            low[i] = lo;
+        }
+    }
+};
+
 // tlm_at: where the Ptlm fields of the TLM marker segment start (0: none written)
 void write_main_header(Out& o, const TileGeom& g, const grk_amd_image_layout& im, uint32_t flags, uint32_t ntiles, uint64_t* tlm_at,
                        const uint8_t* comp_dx = nullptr, const uint8_t* comp_dy = nullptr)
@@ -174,7 +219,7 @@ void write_main_header(Out& o, const TileGeom& g, const grk_amd_image_layout& im
 // sop: the packet's number in the tile (SOP marker segment in front, T2Compress.cpp:149-164) or < 0; eph: EPH after the header
 // the packet of precinct `pi` of resolution r
 void write_packet(Out& o, const TileGeom& g, uint32_t r, uint32_t pi, const grk_amd_coded_block* comp_table, const uint8_t* coded,
-                  int32_t sop = -1, bool eph = false)
+                  int32_t sop = -1, bool eph = false, bool block_msbs = false)
 {
     const ResGeom& R = g.res[r];
     if (sop >= 0) { o.u16(0xFF91); o.u16(4); o.u16((uint32_t)sop & 0xFFFFu); }
@@ -186,12 +231,16 @@ void write_packet(Out& o, const TileGeom& g, uint32_t r, uint32_t pi, const grk_
         if (!P.gw || !P.gh) continue;
         const int height = tag_tree_height(P.gw, P.gh);
         const grk_amd_coded_block* cb = comp_table + P.first_block;
+        const std::unique_ptr<ZbpTree> zbp(block_msbs ? new ZbpTree(cb, P.gw, P.gh) : nullptr);
         for (uint32_t y = 0; y < P.gh; ++y)
             for (uint32_t x = 0; x < P.gw; ++x, ++cb) {
                 const int nn = new_nodes(x, y, height);
                 hb.ones(nn);                                          // inclusion: the path's new nodes
-                if (!(x | y)) hb.zeros((int)B.kmax - 1);              // zero bit-planes: the root's value ...
-                hb.ones(nn);                                          // ... and the path's new nodes
+                if (zbp) zbp->code(hb, x, y);                         // zero bit-planes: the rows' own, the general tree
+                else {
+                    if (!(x | y)) hb.zeros((int)B.kmax - 1);          // zero bit-planes: the root's value ...
+                    hb.ones(nn);                                      // ... and the path's new nodes
+                }
                 const uint32_t len = cb->length;
                 int inc = floor_log2(len) + 1 - 3;
                 if (inc < 0) inc = 0;
@@ -328,13 +377,13 @@ uint64_t write_tile_part(Out& o, const std::vector<const TileGeom*>& cg, const s
 {
     const uint64_t sot = o.n, sot_lit = o.lit ? o.lit->size() : 0;
     const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
-    const bool sop = (flags & GRK_AMD_CS_SOP) != 0, eph = (flags & GRK_AMD_CS_EPH) != 0;
+    const bool sop = (flags & GRK_AMD_CS_SOP) != 0, eph = (flags & GRK_AMD_CS_EPH) != 0, msbs = (flags & GRK_AMD_CS_BLOCK_MSBS) != 0;
     const std::vector<Pk> seq = packet_order(cg, comp_dx, comp_dy, gx0, gy0, order);
     auto packets = [&](Out& dst, std::vector<uint8_t>* plt) {
         int32_t n = 0;
         for (const Pk& q : seq) {
             const uint64_t at = dst.n;
-            write_packet(dst, *cg[q.c], q.r, q.pi, tt + row0[q.c], coded, sop ? n : -1, eph);
+            write_packet(dst, *cg[q.c], q.r, q.pi, tt + row0[q.c], coded, sop ? n : -1, eph, msbs);
             ++n;
             if (plt) plt_length(*plt, dst.n - at);
         }
@@ -443,6 +492,7 @@ extern "C" int64_t grk_amd_write_codestream_subsampled(const grk_amd_image_layou
                                                        uint8_t* out, uint64_t cap)
 {
     if (!base || !table || !coded || !out || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (no encode of sub-sampled components drops bit-planes)
     Layout l;
     int rc = check_layout(im, l);
     if (rc != GRK_AMD_OK) return rc;
@@ -554,6 +604,7 @@ namespace grk_amd {
 int64_t plan_tile_part(const grk_amd_tile_params& p, uint32_t tile_index, uint32_t flags, const grk_amd_coded_block* tile_table,
                        std::vector<uint8_t>& lit, std::vector<grk_amd_tp_segment>& segs)
 {
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (per-block zero bit-planes: the host writers only)
     TileGeom g;
     const int rc = build_tile_geom(p, g);
     if (rc != GRK_AMD_OK) return rc;
@@ -572,6 +623,7 @@ namespace grk_amd {
 int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out)
 {
     const grk_amd_tile_params& p = g.p;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (the header kernel writes the constant tree)
     std::vector<const TileGeom*> cg(p.num_comps, &g);
     const std::vector<Pk> seq = packet_order(cg, nullptr, nullptr, p.tile_x0, p.tile_y0, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
     out.packets.clear();
@@ -615,6 +667,7 @@ extern "C" int64_t grk_amd_plan_tile_part(const grk_amd_tile_params* p, uint32_t
                                           grk_amd_tp_segment* segments, uint64_t segment_cap, uint64_t* num_segments)
 {
     if (!p || !tile_table || !literal_len || !num_segments) return GRK_AMD_ERR_INVALID;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (per-block zero bit-planes: the host writers only)
     std::vector<uint8_t> lit;
     std::vector<grk_amd_tp_segment> segs;
     const int64_t total = grk_amd::plan_tile_part(*p, tile_index, flags, tile_table, lit, segs);

@@ -260,6 +260,16 @@ int grk_amd_stage_ht_encode(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint
 int grk_amd_stage_ht_encode16(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
                               const void* d_mallat16, uint32_t flags);
 
+/* The instances of the block coder that take a per-block drop, on planes and drops the caller chose (device pointers).  d_drops:
+ * num_tiles * blocks_per_tile bytes, tile-major in table order.  0 .. 254: that many least significant bit-planes of the block are left
+ * out -- the magnitudes are coded as mu >> d under the exponent bound Kmax - d, the row's missing_msbs is Kmax - 1 - d, d is clamped to
+ * Kmax - 1 --; a block with d > 0 of which nothing is left behind the shift has length 0.  0xFF: the block is not coded: length 0,
+ * missing_msbs Kmax - 1.  d = 0 codes the block as grk_amd_stage_ht_encode does.  planes16 != 0: int16 planes (the conditions of
+ * grk_amd_stage_ht_encode16).  The context's GRK_AMD_LDS_CAP setting applies.  d_drops is read in the order of the context's stream
+ * (the context keeps a copy of its own for the table's missing_msbs).  A codestream of such rows needs GRK_AMD_CS_BLOCK_MSBS. */
+int grk_amd_stage_ht_encode_drops(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
+                                  const void* d_mallat, int planes16, const uint8_t* d_drops);
+
 /* ---- decode: the inverse hot path --------------------------------
  * TileProcessor::decompress T1 + post-T1 for HT blocks: T1HT::decompress (t1/t1_ht/T1HT.cpp:129-179,
  * ojph_decode_codeblock t1/t1_ht/coding/ojph_block_decoder.cpp:989), dequantisation
@@ -397,7 +407,8 @@ int grk_amd_stage_egress(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_
  * measured with HIP events on the context's stream when timing is enabled.
  * which: 0 ingest+mct, 1 dwt (all levels), 2 ht encode kernel (launches on the context's stream), 3 whole
  *        encode_tiles call, 4 ht encode kernel, top resolution (side stream, beside DWT levels >= 1),
- *        5 ht decode, 6 inverse dwt (all levels), 7 egress, 8 ht encode kernel, large-LDS classes (second side stream).
+ *        5 ht decode, 6 inverse dwt (all levels), 7 egress, 8 ht encode kernel, large-LDS classes (second side stream),
+ *        9 the allocator of a rate-targeted encode (whose trial and final block-coder launches count under 2).
  * One encode runs the ht encode kernel up to three times (2, 4, 8): its time per step is their sum.
  * Pipelined encodes of small frames (a frame's whole chain on one of the side streams, GRK_AMD_FRAME_STREAMS): families 1, 2 and 3
  * are then measured on that stream -- the stream that carries the call -- and 4 / 8 stay empty. */
@@ -501,6 +512,62 @@ int64_t grk_amd_write_main_header_layout(const grk_amd_image_layout* im, const g
 int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                              const void* pixels, uint32_t flags, uint8_t* out, uint64_t cap);
 
+/* ---- rate-targeted encodes: at most N bytes ---------------------------------------------------------------------------------
+ * HTJ2K codes a block in one cleanup pass and this encoder writes one layer, so bytes are saved per BLOCK: block b is coded with its
+ * d_b least significant bit-planes left out (mu >> d_b under Kmax - 1 - d_b zero bit-planes: a decoder that positions the block by
+ * the band's Kmax reconstructs the centre of the coarser bin; QCD, step sizes and guard bits are untouched), or not at all (SKIP).
+ * WHICH DECODERS DO: for the 9/7 transform Grok and grk_amd_decode_image scale the block decoder's words by the band's step and return
+ * the centres.  For the REVERSIBLE transform both shift those words by the BLOCK's own zero bit-planes (Grok: ShiftHTFilter; this
+ * library's HT decoder mirrors it), which cancels the position: a 5/3 block with d planes dropped comes back as mu >> d, and
+ * `distortion` below is then not what either of them delivers.  Use these calls with the 9/7 transform unless the decoder is known to
+ * position reversible blocks by the band; a successful call on a reversible base that dropped anything leaves a note saying so in
+ * grk_amd_last_error ("" otherwise).  The candidates of a block are
+ * d = 0 .. Dmax and, with allow_skip, SKIP.  On the device, for every block and candidate c: L[c][b], the exact length from a trial
+ * launch of the block coder with d = c everywhere (Dmax + 1 extra launches); E[c][b], the exact sum over the block of
+ * (2 q - 2 r_c(q))^2 with q the magnitude a plain encode codes and r_c(q) what a decoder reconstructs (q; 0 where q >> c == 0 and
+ * for SKIP; else ((q >> c) << c) + 2^(c - 1); c taken as min(c, Kmax - 1), the drop the coder clamps to, so that a row describes
+ * the block as coded); W_b = (w_mct * w_band * stepsize)^2 / 4, the weights of grk_amd_block_distortion.
+ * The allocator (one kernel, no per-block data on the host) bisects lambda so that c_b = argmin_c W_b E[c][b] + lambda L[c][b] has
+ * the largest total within the budget (lagrange_bytes), then walks the blocks once in table order and moves a block to the next finer
+ * candidate while that lowers W_b E and fits what is left.  Runs are reproducible: integer sums and fixed-order double sums only.
+ *   grk_amd_encode_tiles_rate   one budget (target_bytes: the code-blocks' bytes) over a batch of same-geometry tiles; the rows
+ *                               carry missing_msbs = Kmax - 1 - d_b and belong in a codestream with GRK_AMD_CS_BLOCK_MSBS.  Synchronous.
+ *   grk_amd_encode_image_rate   a whole image in a file of at most target_bytes, always: through the host writer with
+ *                               GRK_AMD_CS_BLOCK_MSBS; the blocks' budget is the target less what the file spends beside its blocks,
+ *                               lowered by the overshoot and tried again (at most 4 rounds) when the written file is still too
+ *                               long.  A target at or above the plain file's size gives d = 0 everywhere and the bytes of
+ *                               grk_amd_encode_image under GRK_AMD_IMAGE_T2=host, whatever the tiling.  Tiles of several geometries:
+ *                               each group of tiles gets its share of the budget by sample count, capped at its plain bytes (what
+ *                               it cannot use goes to the other groups); a limitation: no common slope across groups yet.
+ *   grk_amd_rate_tables         the tables of the latest of those calls (of its last geometry group), to host memory: which 0 L
+ *                               uint32 [Dmax + 2][nblocks], 1 E uint64 [Dmax + 2][nblocks] (row Dmax + 1: SKIP), 2 W double
+ *                               [nblocks], 3 the chosen drop bytes uint8 [nblocks] (0xFF: SKIP); GRK_AMD_ERR_OVERFLOW: cap_bytes too small
+ * GRK_AMD_ERR_OVERFLOW (the reason in grk_amd_last_error): the target is below what SKIP everywhere -- without allow_skip: Dmax
+ * everywhere -- takes, or the four rounds ran out with the file still too long (the message says which).  GRK_AMD_ERR_UNSUPPORTED: while pipelining is on.  Not offered: sub-sampled images and surfaces, the node, the
+ * plugin, Tier-2 on the device, pipelined sequences, several layers. */
+typedef struct grk_amd_rate {
+    uint64_t target_bytes;   /* the blocks' bytes for grk_amd_encode_tiles_rate; the whole file for grk_amd_encode_image_rate */
+    uint8_t  max_drop;       /* Dmax, 0 = default 6, at most 12 */
+    uint8_t  allow_skip;
+    uint8_t  reserved[6];
+} grk_amd_rate;
+typedef struct grk_amd_rate_result {
+    uint64_t block_bytes;    /* the chosen blocks' bytes, final */
+    uint64_t lagrange_bytes; /* ... of the Lagrange solution, before the fill */
+    uint64_t file_bytes;     /* grk_amd_encode_image_rate: the file's length */
+    double   distortion;     /* sum of W_b E over the chosen candidates, final: the bin-centre model's (see above for 5/3) */
+    double   lambda;
+    uint32_t passes;         /* allocate + encode rounds taken */
+    uint32_t reserved;
+} grk_amd_rate_result;
+int grk_amd_encode_tiles_rate(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const void* pixels,
+                              int pixels_on_device, const grk_amd_rate* rate, grk_amd_coded_block* table, uint64_t* total_bytes,
+                              grk_amd_rate_result* result);
+int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                  const void* pixels, uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t cap,
+                                  grk_amd_rate_result* result);
+int grk_amd_rate_tables(grk_amd_ctx* ctx, int which, void* dst, uint64_t cap_bytes);
+
 /* ---- sub-sampled components (4:2:2, 4:2:0 ...; SIZ XRsiz / YRsiz, grok.h grk_image_comp::dx / dy) ------------------------------------
  * Component c of a tile [x0, x1) x [y0, y1) of the reference grid covers [ceil(x0 / dx_c), ceil(x1 / dx_c)) x [ceil(y0 / dy_c),
  * ceil(y1 / dy_c)) of its own samples (tile/TileProcessor.cpp:605-612): grk_amd_layout_tile_comp gives *base with that rectangle.
@@ -531,6 +598,12 @@ int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_amd_image_la
 #define GRK_AMD_CS_SOP 4u
 #define GRK_AMD_CS_EPH 8u
 /* progression order (grk_cparameters::prog_order, GRK_PROG_ORDER: 0 LRCP, 1 RLCP, 2 RPCL, 3 PCRL, 4 CPRL) << 8 */
+/* The zero-bit-plane tag trees coded from the rows' own missing_msbs (T.800 B.10.2 in its general form) instead of the constant
+ * Kmax - 1 every block of a plain encode has: what a table from grk_amd_encode_tiles_rate / grk_amd_stage_ht_encode_drops needs.
+ * Without the flag every byte is as before; with it and every row at Kmax - 1 as well.  Taken by the host writers
+ * (grk_amd_write_codestream_ex / _layout, grk_amd_write_tile_part; grk_amd_write_main_header accepts it, the header does not
+ * change); grk_amd_plan_tile_part and grk_amd_assemble_device(_async) return GRK_AMD_ERR_UNSUPPORTED. */
+#define GRK_AMD_CS_BLOCK_MSBS 16u
 #define GRK_AMD_CS_PROG_SHIFT 8
 #define GRK_AMD_CS_PROG(order) ((uint32_t)(order) << GRK_AMD_CS_PROG_SHIFT)
 int64_t grk_amd_write_codestream_ex(const grk_amd_tile_params* p, uint32_t img_w, uint32_t img_h,

@@ -10,7 +10,7 @@ from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Cont
                    CS_TLM, CS_PLT, CS_SOP, CS_EPH, CS_PROG, ImageLayout, layout_tiles, same_tile_geometry, write_codestream_layout, Node, NODE_GATHER,
                    StreamInfo, ReaderError, read_header, read_packets, stream_comp_sizes,
                    ImageView, image_view_size, plan_image_view,
-                   Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, surface_bytes, surface_plan,
+                   Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, SURFACE_FORMATS_MSB, surface_bytes, surface_plan,
                    CS_BLOCK_MSBS, DROP_SKIP, Rate, RateResult, RateError)
 
 __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
@@ -18,5 +18,5 @@ __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "C
            "ImageLayout", "layout_tiles", "same_tile_geometry", "write_codestream_layout", "Node", "NODE_GATHER",
            "StreamInfo", "ReaderError", "read_header", "read_packets", "stream_comp_sizes",
            "ImageView", "image_view_size", "plan_image_view",
-           "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "surface_bytes", "surface_plan",
+           "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "SURFACE_FORMATS_MSB", "surface_bytes", "surface_plan",
            "CS_BLOCK_MSBS", "DROP_SKIP", "Rate", "RateResult", "RateError"]

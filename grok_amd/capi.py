@@ -115,11 +115,15 @@ class ImageView(C.Structure):
 
 
 class SurfaceComp(C.Structure):
-    """grk_amd_surface_comp: where one component lies on a surface (bytes; step in samples, 0 reads as 1)"""
-    _fields_ = [("offset", C.c_uint64), ("row_pitch", C.c_uint64), ("step", C.c_uint32), ("reserved", C.c_uint32)]
+    """grk_amd_surface_comp: where one component lies on a surface (bytes; step in samples, 0 reads as 1; shift: the zero bits below
+    a sample in its container, 0 = LSB-aligned)"""
+    _fields_ = [("offset", C.c_uint64), ("row_pitch", C.c_uint64), ("step", C.c_uint32), ("shift", C.c_uint32)]
 
 
 SURFACE_FORMATS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3, "NV16": 4, "I422": 5, "I444": 6}
+# the MSB-aligned two-byte forms of NV12 (GRK_AMD_SURFACE_P016 = 7) and NV16 (GRK_AMD_SURFACE_P216 = 8): name -> (id, the precision
+# the name implies); shift = 16 - prec on every component
+SURFACE_FORMATS_MSB = {"P010": (7, 10), "P012": (7, 12), "P016": (7, 16), "P210": (8, 10), "P212": (8, 12), "P216": (8, 16)}
 
 
 class SurfaceError(RuntimeError):
@@ -137,16 +141,24 @@ class Surface(C.Structure):
 
     @classmethod
     def of(cls, comps):
-        """comps: [(offset, row_pitch, step)] per component"""
+        """comps: [(offset, row_pitch, step)] or [(offset, row_pitch, step, shift)] per component"""
         s = cls()
-        for k, (offset, row_pitch, step) in enumerate(comps):
-            s.comp[k] = SurfaceComp(int(offset), int(row_pitch), int(step), 0)
+        for k, comp in enumerate(comps):
+            s.comp[k] = _surface_comp(comp)
         return s
 
     @classmethod
-    def make(cls, fmt, layout, prec=8, pitch=0):
-        """A named format ("NV12", "NV21", "I420", "YV12", "NV16", "I422", "I444" or its number) for the image area of `layout`
-        (grk_amd_surface_format) -> (surface, [(dx, dy)] per component, bytes)"""
+    def make(cls, fmt, layout, prec=None, pitch=0):
+        """A named format ("NV12", "NV21", "I420", "YV12", "NV16", "I422", "I444", "P010", "P012", "P016", "P210", "P212", "P216" or a
+        format's number) for the image area of `layout` (grk_amd_surface_format) -> (surface, [(dx, dy)] per component, bytes).
+        prec: 8 where neither given nor implied by the name; a P0xx / P2xx name implies its own and a different one is an error"""
+        if fmt in SURFACE_FORMATS_MSB:
+            number, implied = SURFACE_FORMATS_MSB[fmt]
+            if prec is not None and int(prec) != implied:
+                raise ValueError("%s holds %d-bit samples, not %d" % (fmt, implied, prec))
+            fmt, prec = number, implied
+        elif prec is None:
+            prec = 8
         s = cls()
         dx, dy = (C.c_uint8 * 4)(), (C.c_uint8 * 4)()
         nc, nbytes = C.c_uint32(0), C.c_uint64(0)
@@ -164,18 +176,24 @@ class Surface(C.Structure):
             step = c.step or 1
             pitch = c.row_pitch or ((w - 1) * step + 1) * bps
             rows = np.lib.stride_tricks.as_strided(buf[c.offset:], (h, w, bps), (pitch, step * bps, 1))
-            out.append(np.ascontiguousarray(rows).view(np.uint8 if bps == 1 else np.uint16).reshape(h, w))
+            out.append(np.ascontiguousarray(rows).view(np.uint8 if bps == 1 else np.uint16).reshape(h, w) >> c.shift)
         return out
 
     def scatter(self, buf, planes, bps):
-        """the reverse: plane k's samples onto the surface in `buf` (nothing else is written)"""
+        """the reverse: plane k's samples, << shift, onto the surface in `buf` (nothing else is written)"""
         for k, pl in enumerate(planes):
             h, w = pl.shape
             c = self.comp[k]
             step = c.step or 1
             pitch = c.row_pitch or ((w - 1) * step + 1) * bps
             rows = np.lib.stride_tricks.as_strided(buf[c.offset:], (h, w, bps), (pitch, step * bps, 1))
-            rows[...] = np.ascontiguousarray(pl, np.uint8 if bps == 1 else np.uint16).view(np.uint8).reshape(h, w, bps)
+            rows[...] = (np.ascontiguousarray(pl, np.uint8 if bps == 1 else np.uint16) << c.shift).view(np.uint8).reshape(h, w, bps)
+
+
+def _surface_comp(comp):
+    """(offset, row_pitch, step[, shift]) -> SurfaceComp"""
+    offset, row_pitch, step = comp[:3]
+    return SurfaceComp(int(offset), int(row_pitch), int(step), int(comp[3]) if len(comp) > 3 else 0)
 
 
 def _sampling(sampling):
@@ -798,8 +816,8 @@ class Context:
         return tuple(int(self._L.grk_amd_surface_counters(self._h, k)) for k in range(3))
 
     def surface_cut_device(self, d_surface, surface_bytes, comps, bps, nunits, w, h, origins, d_tiles):
-        """KS alone: comps [(offset, row_pitch, step)], origins [(x, y)] of every unit's first sample in the components"""
-        cs = (SurfaceComp * len(comps))(*[SurfaceComp(int(o), int(p), int(s), 0) for o, p, s in comps])
+        """KS alone: comps [(offset, row_pitch, step[, shift])], origins [(x, y)] of every unit's first sample in the components"""
+        cs = (SurfaceComp * len(comps))(*[_surface_comp(cp) for cp in comps])
         r = np.ascontiguousarray(origins, np.uint32).reshape(-1)
         rc = self._L.grk_amd_surface_cut_device(self._h, d_surface, int(surface_bytes), cs, len(comps), bps, nunits, w, h, r.ctypes.data, d_tiles)
         if rc:
@@ -807,7 +825,7 @@ class Context:
 
     def surface_place_device(self, d_tiles, nunits, w, h, bps, origins, comps, d_surface, surface_bytes):
         """KD alone (the reverse)"""
-        cs = (SurfaceComp * len(comps))(*[SurfaceComp(int(o), int(p), int(s), 0) for o, p, s in comps])
+        cs = (SurfaceComp * len(comps))(*[_surface_comp(cp) for cp in comps])
         r = np.ascontiguousarray(origins, np.uint32).reshape(-1)
         rc = self._L.grk_amd_surface_place_device(self._h, d_tiles, nunits, w, h, len(comps), bps, r.ctypes.data, cs, d_surface, int(surface_bytes))
         if rc:

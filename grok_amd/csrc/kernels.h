@@ -339,9 +339,10 @@ hipError_t launch_t2dec_or_status(unsigned int* into, const unsigned int* from, 
 // sample is sample (origins[2 u], origins[2 u + 1]) of each component, and sample (x, y) of component k lies at
 // surface + comp[k].offset + y * comp[k].row_pitch + x * comp[k].step * bps.  The host checked every sample against the surface's size.
 // KS (cut) reads the surface and writes the tiles; KD (place) the reverse, writing no byte of the surface that is no sample.
-// pair (KD, set by the launcher): ncomp = 2 one-byte components of step 2 and one pitch, one byte apart -- both rows leave merged,
-// in 16-byte stores
-struct SurfaceKernelComp { uint64_t offset, row_pitch; uint32_t step, pad; };
+// comp[k].shift (< 8 bps): the zero bits below a sample in its container -- KS reads word >> shift, KD writes v << shift.
+// pair (KD, set by the launcher): ncomp = 2 components of step 2 and one pitch, one sample apart (one-byte samples: no shift;
+// two-byte samples: every address even) -- both rows leave merged, in 16-byte stores
+struct SurfaceKernelComp { uint64_t offset, row_pitch; uint32_t step, shift; };
 struct SurfaceArgs {
     uint8_t* surface; uint8_t* tiles;
     uint32_t nunits, w, h, ncomp, bps;

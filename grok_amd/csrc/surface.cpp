@@ -20,7 +20,7 @@ int queue_surface_kernel(grk_amd_ctx* c, bool place, const ResolvedSurface& rs, 
     a.origins = d_origins;
     for (uint32_t k = 0; k < run.count && k < 4; ++k) {
         const SurfacePlane& p = rs.comp[run.first + k];
-        a.comp[k] = SurfaceKernelComp{p.offset, p.row_pitch, p.step, 0};
+        a.comp[k] = SurfaceKernelComp{p.offset, p.row_pitch, p.step, p.shift};
     }
     HIP_TRY(c, place ? launch_surface_place(a, c->stream) : launch_surface_cut(a, c->stream), place ? "launch surface placement" : "launch surface cut");
     ++c->surf_counters[2];
@@ -46,11 +46,12 @@ static int surface_kernel_device(grk_amd_ctx* c, bool place, void* surface, uint
         const grk_amd_surface_comp& sc = comps[k];
         const uint32_t step = sc.step ? sc.step : 1u;
         if (step > 4 || sc.offset % bps || sc.row_pitch % bps || (sc.offset | sc.row_pitch) >> 48) return fail(c, GRK_AMD_ERR_INVALID, "surface: a component's step, offset or pitch");
+        if (sc.shift >= 8 * bps) return fail(c, GRK_AMD_ERR_INVALID, "surface: a shift of the whole container");
         // the component as far as the units reach: rows that do not run into the next, the last sample inside the surface
         const uint64_t cols = ox + w, rows = oy + h, row_span = ((cols - 1) * step + 1) * bps;
         if (rows > 1 && sc.row_pitch < row_span) return fail(c, GRK_AMD_ERR_INVALID, "surface: a row pitch is smaller than a row");
         if (sc.offset + (rows - 1) * sc.row_pitch + row_span > surface_bytes) return fail(c, GRK_AMD_ERR_INVALID, "surface: a unit outside the surface");
-        rs.comp.push_back(SurfacePlane{sc.offset, sc.row_pitch, cols, rows, 0, 0, step});
+        rs.comp.push_back(SurfacePlane{sc.offset, sc.row_pitch, cols, rows, 0, 0, step, sc.shift});
     }
     if (place) {
         const char* why = "";

@@ -41,6 +41,8 @@ int resolve_surface(const grk_amd_image_layout* im, const grk_amd_tile_params* b
         p.offset = sc.offset;
         p.row_pitch = sc.row_pitch ? sc.row_pitch : row_span(p, out.bps);
         if (p.row_pitch < row_span(p, out.bps)) return refuse(why, GRK_AMD_ERR_INVALID, "surface: a row pitch is smaller than a row");
+        if ((uint64_t)base->prec + sc.shift > 8u * out.bps) return refuse(why, GRK_AMD_ERR_INVALID, "surface: precision plus shift exceed the sample's container");
+        p.shift = sc.shift;
         out.bytes = std::max(out.bytes, p.offset + plane_span(p, out.bps));
         out.comp.push_back(p);
     }
@@ -76,6 +78,8 @@ SurfaceRoute plan_surface_run(const ResolvedSurface& rs, const CompRun& run, boo
     if (!one_tile || !allow_direct || !run.count) return r;
     const uint32_t bps = rs.bps;
     const SurfacePlane& f = rs.comp[run.first];
+    // (a shift is applied by KS / KD only)
+    for (uint32_t k = 0; k < run.count; ++k) if (rs.comp[run.first + k].shift) return r;
     for (uint32_t k = 1; k < run.count; ++k) {
         const SurfacePlane& p = rs.comp[run.first + k];
         if (p.step != f.step || p.row_pitch != f.row_pitch) return r;
@@ -155,8 +159,15 @@ extern "C" int grk_amd_surface_format(int format, const grk_amd_image_layout* im
                                       uint8_t* comp_dx, uint8_t* comp_dy, uint32_t* num_comps, uint64_t* bytes)
 {
     if (!im || !surface || !comp_dx || !comp_dy || !prec || im->x1 <= im->x0 || im->y1 <= im->y0) return GRK_AMD_ERR_INVALID;
-    if (format < GRK_AMD_SURFACE_NV12 || format > GRK_AMD_SURFACE_I444) return GRK_AMD_ERR_INVALID;
+    if (format < GRK_AMD_SURFACE_NV12 || format > GRK_AMD_SURFACE_P216) return GRK_AMD_ERR_INVALID;
     if (prec > 16) return GRK_AMD_ERR_UNSUPPORTED;
+    // P016 / P216: NV12 / NV16 with two-byte samples in the containers' high bits
+    uint32_t shift = 0;
+    if (format == GRK_AMD_SURFACE_P016 || format == GRK_AMD_SURFACE_P216) {
+        if (prec <= 8) return GRK_AMD_ERR_INVALID;
+        shift = 16 - prec;
+        format = format == GRK_AMD_SURFACE_P016 ? GRK_AMD_SURFACE_NV12 : GRK_AMD_SURFACE_NV16;
+    }
     const uint64_t bps = (prec + 7u) / 8u, W = im->x1 - im->x0, H = im->y1 - im->y0;
     const bool pairs = format == GRK_AMD_SURFACE_NV12 || format == GRK_AMD_SURFACE_NV21 || format == GRK_AMD_SURFACE_NV16;
     const bool v_first = format == GRK_AMD_SURFACE_NV21 || format == GRK_AMD_SURFACE_YV12;
@@ -172,15 +183,15 @@ extern "C" int grk_amd_surface_format(int format, const grk_amd_image_layout* im
     const uint64_t cpitch = pairs || dx == 1 ? pitch : cdiv(cdiv(pitch, 2), bps) * bps;
     if (cpitch < wc * bps) return GRK_AMD_ERR_INVALID;
     *surface = grk_amd_surface{};
-    surface->comp[0] = grk_amd_surface_comp{0, pitch, 1, 0};
+    surface->comp[0] = grk_amd_surface_comp{0, pitch, 1, shift};
     const uint64_t chroma = H * pitch;
     const uint32_t u = v_first ? 2 : 1, v = v_first ? 1 : 2;                  // which component lies first in memory
     if (pairs) {
-        surface->comp[u] = grk_amd_surface_comp{chroma, cpitch, 2, 0};
-        surface->comp[v] = grk_amd_surface_comp{chroma + bps, cpitch, 2, 0};
+        surface->comp[u] = grk_amd_surface_comp{chroma, cpitch, 2, shift};
+        surface->comp[v] = grk_amd_surface_comp{chroma + bps, cpitch, 2, shift};
     } else {
-        surface->comp[u] = grk_amd_surface_comp{chroma, cpitch, 1, 0};
-        surface->comp[v] = grk_amd_surface_comp{chroma + hc * cpitch, cpitch, 1, 0};
+        surface->comp[u] = grk_amd_surface_comp{chroma, cpitch, 1, shift};
+        surface->comp[v] = grk_amd_surface_comp{chroma + hc * cpitch, cpitch, 1, shift};
     }
     if (num_comps) *num_comps = 3;
     if (bytes) {

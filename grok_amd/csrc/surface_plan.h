@@ -11,8 +11,9 @@
 #pragma GCC visibility push(hidden)       // nothing declared below is part of the library's interface
 namespace grk_amd {
 
-// component c of the image on the surface: its size, its first sample at (x0, y0) of the component's grid, every pitch in bytes
-struct SurfacePlane { uint64_t offset, row_pitch, w, h, x0, y0; uint32_t step; };
+// component c of the image on the surface: its size, its first sample at (x0, y0) of the component's grid, every pitch in bytes;
+// shift: the zero bits below a sample in its container (P010: 6)
+struct SurfacePlane { uint64_t offset, row_pitch, w, h, x0, y0; uint32_t step, shift; };
 struct ResolvedSurface {
     uint32_t bps = 0;
     std::vector<SurfacePlane> comp;
@@ -24,7 +25,8 @@ int resolve_surface(const grk_amd_image_layout* im, const grk_amd_tile_params* b
 // a destination's components pairwise: disjoint, interleaved partners, or side by side -- else GRK_AMD_ERR_INVALID and *why
 int check_surface_disjoint(const ResolvedSurface& rs, const char** why);
 
-// a run's route: in place (the tile coder on base + at in `layout`) or staged
+// a run's route: in place (the tile coder on base + at in `layout`) or staged; a run with a shifted component is always staged (the
+// shift is KS's and KD's: the tile coders and grk_amd_pixel_layout know none)
 struct SurfaceRoute { bool in_place; grk_amd_pixel_layout layout; uint64_t at; };
 // one_tile: the image is one tile (the run is the unit); cap: the bytes behind the base; base_align: the base address modulo 4
 SurfaceRoute plan_surface_run(const ResolvedSurface& rs, const CompRun& run, bool one_tile, bool decode, bool allow_direct, uint64_t cap,

@@ -783,15 +783,19 @@ int grk_amd_place_upsampled_device(grk_amd_ctx* ctx, const void* tiles, uint32_t
                                    const uint32_t* origins, uint32_t dx, uint32_t dy, void* image, uint32_t img_x0, uint32_t img_y0,
                                    uint32_t img_w, uint32_t img_h);
 
-/* ---- video surfaces: NV12, I420, NV16 ... (surface_plan.cpp, surface.cpp, kernels_surface.hip) --------------------------------
+/* ---- video surfaces: NV12, I420, NV16, P010 ... (surface_plan.cpp, surface.cpp, kernels_surface.hip) --------------------------------
  * What sub-sampled content is held in on a GPU: a video decoder or encoder, a capture card and hardware frames of a media
  * framework hold a Y plane with a row pitch and then one plane of interleaved Cb / Cr pairs (NV12, NV21, NV16) or two pitched chroma
  * planes (I420, YV12), with 16-bit samples for 10- and 12-bit video.  A SURFACE describes such a buffer component by component:
  * sample (x, y) of component c lies at base + comp[c].offset + y * comp[c].row_pitch + x * comp[c].step * bps, bps = ceil(prec / 8),
- * host endian, LSB-aligned; sample (0, 0) is the component's first sample of the image area and the component is
+ * host endian; sample (0, 0) is the component's first sample of the image area and the component is
  * grk_amd_stream_comp_size columns by rows (the ceil(x / dx) formulas of grk_amd_encode_image_subsampled above).
+ * A sample v of component c is stored as v << comp[c].shift: shift = 0 is LSB-aligned (planar I010), shift = 8 * bps - prec is
+ * MSB-aligned (the P010 / P012 / P016 family of hardware video: 10 bits << 6).  An encode reads word >> shift -- what lies in the low
+ * `shift` bits of the caller's memory is discarded, not checked --, a decode writes v << shift with the low bits zero.  The shift is
+ * per component and moves no byte: sizes, placements and the rules below do not depend on it.
  * Rules (GRK_AMD_ERR_INVALID): offset and row_pitch are multiples of bps, a non-zero pitch covers at least one row
- * (((w_c - 1) * step + 1) * bps), step <= 4, at most 4 components; prec > 16: GRK_AMD_ERR_UNSUPPORTED.
+ * (((w_c - 1) * step + 1) * bps), step <= 4, prec + shift <= 8 * bps, at most 4 components; prec > 16: GRK_AMD_ERR_UNSUPPORTED.
  * Two components of a DESTINATION (decode) may not share a byte.  Accepted placements of two components: disjoint extents;
  * interleaved partners (equal pitch and step, offsets k * bps apart, 0 < k < step); side by side (equal pitch, the byte ranges of
  * their rows inside a pitch disjoint and not wrapping).  Any other overlap: GRK_AMD_ERR_INVALID.  An encode only reads: any overlap. */
@@ -800,7 +804,7 @@ typedef struct grk_amd_surface_comp {
     uint64_t row_pitch;  /* bytes between rows; 0 = tight: ((w_c - 1) * step + 1) * bps */
     uint32_t step;       /* samples from one sample of a row to the next: 1 = a plane of its own, 2 = every other sample (chroma of
                             NV12) ... 4; 0 reads as 1 */
-    uint32_t reserved;
+    uint32_t shift;      /* zero bits below the sample in its container: 0 = LSB-aligned, 16 - prec = P010-style */
 } grk_amd_surface_comp;
 typedef struct grk_amd_surface { grk_amd_surface_comp comp[4]; } grk_amd_surface;
 /* host only: bytes from the base to the end of the last sample of any component; 0 for an invalid surface, *why (may be NULL) then
@@ -810,8 +814,10 @@ uint64_t grk_amd_surface_bytes(const grk_amd_image_layout* im, const grk_amd_til
 /* host only: the surface and the factors of a named format for the image area of `im` with samples of `prec` bits.  pitch: the luma
  * row pitch in bytes, 0 = the smallest valid one; interleaved chroma rows take `pitch`, planar chroma rows of the 4:2:x forms
  * pitch / 2 rounded up to a multiple of bps, I444's planes `pitch`.  Planes follow each other at rows x pitch.  NV21 / YV12: Cr (V) lies
- * first in memory -- component order stays Y, Cb, Cr.  *num_comps = 3, *bytes = grk_amd_surface_bytes.  GRK_AMD_ERR_INVALID: an unknown
- * format, a pitch below a row or no multiple of bps; GRK_AMD_ERR_UNSUPPORTED: prec > 16. */
+ * first in memory -- component order stays Y, Cb, Cr.  P016 / P216: the layout of NV12 / NV16 with two bytes per sample and
+ * shift = 16 - prec on all three components -- prec 10: P010 / P210, 12: P012 / P212, 16: P016 / P216 (= NV12 / NV16 at 16 bits).
+ * *num_comps = 3, *bytes = grk_amd_surface_bytes.  GRK_AMD_ERR_INVALID: an unknown format, a pitch below a row or no multiple of
+ * bps, P016 / P216 with prec <= 8; GRK_AMD_ERR_UNSUPPORTED: prec > 16. */
 #define GRK_AMD_SURFACE_NV12 0
 #define GRK_AMD_SURFACE_NV21 1
 #define GRK_AMD_SURFACE_I420 2
@@ -819,6 +825,8 @@ uint64_t grk_amd_surface_bytes(const grk_amd_image_layout* im, const grk_amd_til
 #define GRK_AMD_SURFACE_NV16 4
 #define GRK_AMD_SURFACE_I422 5
 #define GRK_AMD_SURFACE_I444 6
+#define GRK_AMD_SURFACE_P016 7
+#define GRK_AMD_SURFACE_P216 8
 int grk_amd_surface_format(int format, const grk_amd_image_layout* im, uint32_t prec, uint64_t pitch, grk_amd_surface* surface,
                            uint8_t* comp_dx, uint8_t* comp_dy, uint32_t* num_comps, uint64_t* bytes);
 /* host only, no context: the plan of grk_amd_encode_surface (decode = 0) / grk_amd_decode_surface (decode != 0) for a surface of
@@ -832,7 +840,8 @@ int grk_amd_surface_format(int format, const grk_amd_image_layout* im, uint32_t 
  *                and dwords; pitched and interleaved stores fall back to single samples for odd pitches by themselves); an
  *                encode's on a multiple of bps (8-bit device pixels off 4-byte alignment take the separate ingest pass).
  * Every other unit -- multi-tile images, reversed component order (NV21, YV12), a lone component of interleaved pixels on decode,
- * destinations off alignment -- is STAGED: cut out of / placed onto the surface by a kernel, through tight planes.  allow_direct = 0:
+ * destinations off alignment, and every run with a component of shift != 0 (the two kernels apply the shift; the tile coders and
+ * grk_amd_pixel_layout know none) -- is STAGED: cut out of / placed onto the surface by a kernel, through tight planes.  allow_direct = 0:
  * all staged (what GRK_AMD_SURFACE_DIRECT=0 does).  in_place[r] (cap_runs entries, may be NULL): 1 / 0 per run, layouts[r] the layout
  * of an in-place run, at[r] its first sample's offset.  Returns the number of runs, GRK_AMD_ERR_OVERFLOW when grk_amd_surface_bytes
  * exceeds `cap` (or cap_runs is too small), else the surface's refusal; *why as above. */
@@ -862,8 +871,9 @@ uint64_t grk_amd_surface_counters(grk_amd_ctx* ctx, int which);
 /* The two kernels alone (device pointers; queued on the context's stream).  nunits units of ncomp x h x w samples of bps (1 or 2)
  * bytes lie back to back, tight, component-major at `tiles`; unit i's first sample is sample (origins[2 i], origins[2 i + 1]) of
  * each component; comps[k] (ncomp <= 4 of them) places component k on the surface (row_pitch here is taken as it is: not 0).
- * cut: surface -> tiles; place: tiles -> surface, writing no byte that is no sample (two 8-bit partners of step 2 in one call are
- * merged into 16-byte stores).  Every sample is checked against surface_bytes on the host: GRK_AMD_ERR_INVALID outside it. */
+ * cut: surface -> tiles, word >> comps[k].shift; place: tiles -> surface, v << comps[k].shift cut to the container, writing no byte
+ * that is no sample (two partners of step 2 in one call are merged into 16-byte stores); shift < 8 * bps.  Every sample is checked
+ * against surface_bytes on the host: GRK_AMD_ERR_INVALID outside it. */
 int grk_amd_surface_cut_device(grk_amd_ctx* ctx, const void* surface, uint64_t surface_bytes, const grk_amd_surface_comp* comps, uint32_t ncomp,
                                uint32_t bps, uint32_t nunits, uint32_t w, uint32_t h, const uint32_t* origins, void* tiles);
 int grk_amd_surface_place_device(grk_amd_ctx* ctx, const void* tiles, uint32_t nunits, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,

@@ -4,9 +4,14 @@ NV12 8-bit frame resident in device memory, one tile, reversible HT, 5 levels --
 a caller had to do before these calls existed (encode: de-interleave the chroma on the device with torch, copy the three planes to
 the host, grk_amd_encode_image_subsampled; decode: grk_amd_decode_image to tight device planes, then a torch interleave) -- those entry
 points are unchanged, so one library times all three.  And the two kernels alone beside a plain device-to-device copy of the same
-bytes.  Medians of --repeats (7) on one box, the variants alternated within each repeat; host wall clock around a synchronised call.
+bytes.  Then the same frame with 10-bit samples as P010 (two-byte containers, the sample in the high bits): grk_amd_encode_surface /
+grk_amd_decode_surface on the P010 surface (always staged: KS / KD shift on the way) beside what a caller had to do without the
+shift -- a torch shift pass over the frame and the LSB-aligned call -- and beside the staged LSB-aligned 16-bit NV12 calls, whose
+chroma takes the 16-byte two-byte forms of step 2.  --sixteen-only runs just those staged 16-bit NV12 rows, with min and max: they
+work on a library without the shift as well (GRK_AMD_LIB, tools/build_variant.sh), which is how this tree and its parent commit are
+compared.  Medians of --repeats (7) on one box, the variants alternated within each repeat; host wall clock around a synchronised call.
 
-    python tools/surface_time.py [--repeats 7] [--small] > profiles/surface.txt
+    python tools/surface_time.py [--repeats 7] [--small] [--sixteen-only] > profiles/surface.txt
 """
 import argparse
 import os
@@ -44,8 +49,21 @@ def show(title, res, bytes_moved=None):
     sys.stdout.flush()
 
 
-def plane(w, h, seed):
-    base = synth.g2(1, min(h, 2048), min(w, 2048), 8, seed=seed)[0]
+def alternated_spread(settings, repeats):
+    """as alternated: {name: (min, median, max) ms}"""
+    ms = {k: [] for k in settings}
+    for fn in settings.values():
+        fn()
+    for _ in range(repeats):
+        for k, fn in settings.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: (float(np.min(v)), float(np.median(v)), float(np.max(v))) for k, v in ms.items()}
+
+
+def plane(w, h, seed, prec=8):
+    base = synth.g2(1, min(h, 2048), min(w, 2048), prec, seed=seed)[0]
     return np.ascontiguousarray(np.tile(base, ((h + base.shape[0] - 1) // base.shape[0], (w + base.shape[1] - 1) // base.shape[1]))[:h, :w])
 
 
@@ -53,11 +71,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--small", action="store_true", help="1920 x 1080 instead of 7680 x 4320 (a quick look)")
+    ap.add_argument("--sixteen-only", action="store_true", help="only the staged 16-bit NV12 rows, min / median / max (any library)")
+    ap.add_argument("--label", default="tree", help="what --sixteen-only's lines are called")
     a = ap.parse_args()
     W, H = (1920, 1080) if a.small else (7680, 4320)
     c = G.Context(0)
-    print("# tools/surface_time.py: medians of %d repeats, variants alternated within a repeat; %s" % (a.repeats, torch.cuda.get_device_name(0)))
     layout = G.ImageLayout.make(W, H)
+    if a.sixteen_only:
+        sixteen_bit(c, a, layout, W, H)
+        return
+    print("# tools/surface_time.py: medians of %d repeats, variants alternated within a repeat; %s" % (a.repeats, torch.cuda.get_device_name(0)))
     surface, sampling, nbytes = G.Surface.make("NV12", layout, 8, 0)
     base = G.TileParams.make(1, 1, 3, 8, 5, mct=False)
     planes = [plane(W, H, 1), plane(W // 2, H // 2, 2), plane(W // 2, H // 2, 3)]
@@ -156,6 +179,104 @@ def main():
     show("the kernels alone, the interleaved chroma plane only",
          alternated({"KS cut, Cb/Cr (de-interleave)": cut_uv, "KD place, Cb/Cr (merged stores)": place_uv,
                      "plain device-to-device copy of the same bytes": plain(nbytes - W * H)}, a.repeats), nbytes - W * H)
+    sixteen_bit(c, a, layout, W, H)
+
+
+def sixteen_bit(c, a, layout, W, H):
+    """the 10-bit frame: P010 beside a torch shift pass + the LSB-aligned call, and the staged LSB-aligned 16-bit NV12 calls"""
+    prec, shift = 10, 6
+    nv12, sampling, nbytes = G.Surface.make("NV12", layout, prec, 0)
+    base = G.TileParams.make(1, 1, 3, prec, 5, mct=False)
+    planes = [plane(W, H, 1, prec), plane(W // 2, H // 2, 2, prec), plane(W // 2, H // 2, 3, prec)]
+    lsb = np.zeros(nbytes, np.uint8)
+    nv12.scatter(lsb, planes, 2)
+    d_lsb = torch.from_numpy(lsb).cuda()
+    d_out = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    files = {}
+
+    def staged(fn):
+        def run():
+            os.environ["GRK_AMD_SURFACE_DIRECT"] = "0"
+            try:
+                fn()
+            finally:
+                os.environ.pop("GRK_AMD_SURFACE_DIRECT", None)
+        return run
+
+    def enc16():
+        files["nv12"] = c.encode_surface(layout, base, sampling, nv12, d_lsb.data_ptr(), cap=nbytes)
+
+    enc16()
+    pinned = c.host_array(len(files["nv12"]))
+    pinned[:] = np.frombuffer(files["nv12"], np.uint8)
+
+    def dec16():
+        c.decode_surface(pinned, nv12, d_out.data_ptr(), cap=nbytes)
+        c.decode_status()
+
+    if a.sixteen_only:
+        res = alternated_spread({"encode_surface 8K NV12 16-bit containers, staged": staged(enc16),
+                                 "decode_surface 8K NV12 16-bit containers, staged": staged(dec16)}, a.repeats)
+        assert np.array_equal(d_out.cpu().numpy(), lsb)
+        for k, (lo, med, hi) in res.items():
+            print("    %s | %-58s min %9.3f  median %9.3f  max %9.3f ms" % (a.label, k, lo, med, hi))
+        return
+    p010, _, n010 = G.Surface.make("P010", layout, pitch=0)
+    assert n010 == nbytes
+    msb = np.zeros(nbytes, np.uint8)
+    p010.scatter(msb, planes, 2)
+    d_msb = torch.from_numpy(msb).cuda()
+    d_tmp = torch.zeros(nbytes // 2, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    print("# P010 %d x %d, 10 bits: %d bytes; one tile, reversible HT, 5 levels" % (W, H, nbytes))
+
+    def enc_p010():
+        files["p010"] = c.encode_surface(layout, base, sampling, p010, d_msb.data_ptr(), cap=nbytes)
+
+    def enc_shift_pass(fn):
+        def run():
+            # (int16 views: torch has no shifts of uint16; the arithmetic shift's sign bits are masked off)
+            torch.bitwise_and(torch.bitwise_right_shift(d_msb.view(torch.int16), shift), (1 << prec) - 1, out=d_tmp)
+            torch.cuda.synchronize()
+            files["shifted"] = c.encode_surface(layout, base, sampling, nv12, d_tmp.data_ptr(), cap=nbytes)
+        return fn(run) if fn else run
+
+    res = alternated({"encode_surface, P010 (staged, KS shifts)": enc_p010,
+                      "before: torch shift pass + encode_surface NV12 16-bit, in place": enc_shift_pass(None),
+                      "before: torch shift pass + encode_surface NV12 16-bit, staged": enc_shift_pass(staged),
+                      "encode_surface, NV12 16-bit LSB-aligned, in place": enc16,
+                      "encode_surface, NV12 16-bit LSB-aligned, staged": staged(enc16)}, a.repeats)
+    assert files["p010"] == files["shifted"] == files["nv12"]
+    show("encode, device-resident 10-bit frame -> file of %d bytes in host memory" % len(files["p010"]), res)
+    d_p010 = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    d_shifted = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def dec_p010():
+        c.decode_surface(pinned, p010, d_p010.data_ptr(), cap=nbytes)
+        c.decode_status()
+
+    def dec_shift_pass(fn):
+        def decode():
+            c.decode_surface(pinned, nv12, d_shifted.data_ptr(), cap=nbytes)
+            c.decode_status()
+        decode = fn(decode) if fn else decode
+
+        def run():
+            decode()
+            v = d_shifted.view(torch.int16)
+            torch.bitwise_left_shift(v, shift, out=v)
+            torch.cuda.synchronize()
+        return run
+
+    res = alternated({"decode_surface, P010 (staged, KD shifts)": dec_p010,
+                      "before: decode_surface NV12 16-bit, in place + torch shift pass": dec_shift_pass(None),
+                      "before: decode_surface NV12 16-bit, staged + torch shift pass": dec_shift_pass(staged),
+                      "decode_surface, NV12 16-bit LSB-aligned, in place": dec16,
+                      "decode_surface, NV12 16-bit LSB-aligned, staged": staged(dec16)}, a.repeats)
+    assert np.array_equal(d_p010.cpu().numpy(), msb) and np.array_equal(d_shifted.cpu().numpy(), msb) and np.array_equal(d_out.cpu().numpy(), lsb)
+    show("decode, file in pinned host memory -> device-resident 10-bit frame", res)
 
 
 if __name__ == "__main__":

@@ -85,8 +85,9 @@ class StreamInfo(C.Structure):
 
 class Rate(C.Structure):
     """grk_amd_rate: target_bytes (the blocks' bytes for encode_tiles_rate, the whole file for encode_image_rate), max_drop (Dmax;
-    0 = 6, at most 12), allow_skip"""
-    _fields_ = [("target_bytes", C.c_uint64), ("max_drop", C.c_uint8), ("allow_skip", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+    0 = 6, at most 12), allow_skip, joint (encode_image_rate: one set of tables and one multiplier over all geometry groups)"""
+    _fields_ = [("target_bytes", C.c_uint64), ("max_drop", C.c_uint8), ("allow_skip", C.c_uint8), ("joint", C.c_uint8),
+                ("reserved", C.c_uint8 * 5)]
 
 
 class RateResult(C.Structure):
@@ -294,6 +295,18 @@ def lib():
             L.grk_amd_encode_image_rate.restype = C.c_int64
             L.grk_amd_encode_image_rate.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, u32, C.POINTER(Rate), vp, u64, C.POINTER(RateResult)]
             L.grk_amd_rate_tables.argtypes = [vp, i32, vp, u64]
+        if hasattr(L, "grk_amd_encode_surface_rate"):
+            L.grk_amd_encode_image_subsampled_rate.restype = C.c_int64
+            L.grk_amd_encode_image_subsampled_rate.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, vp, vp, u32, C.POINTER(Rate), vp, u64,
+                                                               C.POINTER(RateResult)]
+            L.grk_amd_encode_surface_rate.restype = C.c_int64
+            L.grk_amd_encode_surface_rate.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, vp, vp, vp, u64, i32, u32, C.POINTER(Rate), vp, u64,
+                                                      C.POINTER(RateResult)]
+            L.grk_amd_rate_num_blocks.restype = u64
+            L.grk_amd_rate_num_blocks.argtypes = [vp]
+            L.grk_amd_rate_unit_rows.argtypes = [vp, vp, u32]
+            L.grk_amd_rate_last_budget.restype = u64
+            L.grk_amd_rate_last_budget.argtypes = [vp]
         L.grk_amd_stage_dwt_inv.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_decode.argtypes = [vp, PP, u32, vp, vp, u64, vp]
         L.grk_amd_stage_ht_decode16.argtypes = [vp, PP, u32, vp, vp, u64, vp]
@@ -917,17 +930,71 @@ class Context:
             raise RateError("encode_tiles_rate", rc, self._L.grk_amd_last_error(self._h).decode())
         return table, tot.value, res
 
-    def encode_image_rate(self, layout, base, pixels, target_bytes, flags=0, max_drop=0, allow_skip=False):
-        """grk_amd_encode_image_rate: the image as a file of at most target_bytes -> (codestream bytes, RateResult)"""
+    def encode_image_rate(self, layout, base, pixels, target_bytes, flags=0, max_drop=0, allow_skip=False, joint=False):
+        """grk_amd_encode_image_rate: the image as a file of at most target_bytes -> (codestream bytes, RateResult).  joint: one set of
+        tables and one multiplier over all geometry groups instead of a share of the budget for each"""
         px = np.ascontiguousarray(pixels)
         cap = px.size * 4 + (1 << 20)
         out = np.empty(cap, np.uint8)
-        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip))), RateResult()
+        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), int(bool(joint))), RateResult()
         n = self._L.grk_amd_encode_image_rate(self._h, C.byref(layout), C.byref(base), px.ctypes.data, flags, C.byref(rate), out.ctypes.data,
                                               cap, C.byref(res))
         if n < 0:
             raise RateError("encode_image_rate", n, self._L.grk_amd_last_error(self._h).decode())
         return out[:n].tobytes(), res
+
+    def encode_image_subsampled_rate(self, layout, base, sampling, planes, target_bytes, flags=0, max_drop=0, allow_skip=False):
+        """grk_amd_encode_image_subsampled_rate: encode_image_subsampled in a file of at most target_bytes -> (codestream bytes,
+        RateResult); one set of tables and one multiplier over every component"""
+        dx = (C.c_uint8 * len(sampling))(*[int(a) for a, _ in sampling])
+        dy = (C.c_uint8 * len(sampling))(*[int(b) for _, b in sampling])
+        px = np.concatenate([np.ascontiguousarray(pl).reshape(-1) for pl in planes])
+        cap = px.size * px.itemsize * 4 + (1 << 20)
+        out = np.empty(cap, np.uint8)
+        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), 1), RateResult()
+        n = self._L.grk_amd_encode_image_subsampled_rate(self._h, C.byref(layout), C.byref(base), C.addressof(dx), C.addressof(dy),
+                                                         px.ctypes.data, flags, C.byref(rate), out.ctypes.data, cap, C.byref(res))
+        if n < 0:
+            raise RateError("encode_image_subsampled_rate", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def encode_surface_rate(self, layout, base, sampling, surface, pixels, target_bytes, flags=0, cap=None, max_drop=0, allow_skip=False):
+        """grk_amd_encode_surface_rate: encode_surface in a file of at most target_bytes -> (codestream bytes, RateResult).  pixels: a
+        uint8 numpy array holding the surface (host), or a device pointer (int) together with `cap`"""
+        dx, dy = _sampling(sampling)
+        on_device = not isinstance(pixels, np.ndarray)
+        if on_device:
+            ptr, nbytes = int(pixels), int(cap)
+        else:
+            if pixels.dtype != np.uint8 or not pixels.flags.c_contiguous:
+                raise ValueError("pixels: a contiguous uint8 array")
+            ptr, nbytes = pixels.ctypes.data, pixels.nbytes if cap is None else int(cap)
+        out_cap = nbytes * 4 + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), 1), RateResult()
+        n = self._L.grk_amd_encode_surface_rate(self._h, C.byref(layout), C.byref(base), C.cast(dx, C.c_void_p), C.cast(dy, C.c_void_p),
+                                                C.byref(surface), ptr, nbytes, int(on_device), flags, C.byref(rate), out.ctypes.data, out_cap,
+                                                C.byref(res))
+        if n < 0:
+            raise RateError("encode_surface_rate", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def rate_num_blocks(self):
+        """grk_amd_rate_num_blocks: the blocks the latest rate-targeted call's tables are over (a joint call: the whole image's)"""
+        return int(self._L.grk_amd_rate_num_blocks(self._h))
+
+    def rate_last_budget(self):
+        """grk_amd_rate_last_budget: the blocks' budget of the latest allocator run (a whole-image call: its last round's)"""
+        return int(self._L.grk_amd_rate_last_budget(self._h))
+
+    def rate_unit_rows(self):
+        """grk_amd_rate_unit_rows: the first row of every unit of those tables, in unit order (uint64 array)"""
+        n = self._L.grk_amd_rate_unit_rows(self._h, None, 0)
+        if n < 0:
+            self._check(n, "rate_unit_rows")
+        out = np.zeros(n, np.uint64)
+        self._check(min(self._L.grk_amd_rate_unit_rows(self._h, out.ctypes.data, n), 0), "rate_unit_rows")
+        return out
 
     def rate_tables(self, nblocks, max_drop=0):
         """The tables of the latest rate-targeted call (grk_amd_rate_tables) -> (L uint32 [Dmax + 2, nblocks], E uint64 [Dmax + 2,

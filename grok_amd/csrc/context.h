@@ -161,8 +161,11 @@ struct grk_amd_ctx {
     DevBuf drops_keep;                     // from which grk_amd_fetch_table makes the rows' zero bit-planes
     // A rate-targeted encode (rate.hip): the tables over the latest front end's blocks -- L, E candidate-major (RatePlan), W, the
     // chosen drop bytes, the allocator's result -- and what they were made for
-    DevBuf rate_L, rate_E, rate_W, rate_drop, rate_res;
-    struct RateState { bool valid = false; RatePlan plan{}; uint64_t nblocks = 0; uint32_t ntiles = 0; } rate;
+    // A whole-image call with joint tables (rate_joint): the tables are over every unit's blocks in joint row order, rate_map holds the
+    // batches' maps (RateJointPlan) and rate_bdrop the drop bytes of the batch being coded; unit_rows: each unit's first row
+    DevBuf rate_L, rate_E, rate_W, rate_drop, rate_res, rate_map, rate_bdrop;
+    struct RateState { bool valid = false; RatePlan plan{}; uint64_t nblocks = 0; uint32_t ntiles = 0; std::vector<uint64_t> unit_rows;
+                       uint64_t budget = 0; /* of the latest allocator run */ } rate;
     HostStage stage;                 // pinned chunks for pageable host buffers (copy_h2d)
     void* d2h_pin = nullptr; size_t d2h_cap = 0; std::vector<hipEvent_t> d2h_ev;   // copy_d2h: a staging area of the transfer's size, an event per piece
     // Full decode with overlap on: K5b of the top resolution's blocks (3/4 of them) runs on the side stream beside K5b of the

@@ -288,7 +288,7 @@ void grk_amd_destroy(grk_amd_ctx* c)
     for (DevBuf* b : {&c->pixels, &c->p0, &c->p1, &c->llA, &c->llB, &c->blockdesc, &c->lengths,
                       &c->offsets, &c->arena, &c->flag, &c->dec_desc, &c->dec_table, &c->dec_quads, &c->dec_mslen,
                       &c->dec_coded, &c->dec_pixels, &c->dec_work, &c->ht_sel, &c->energy, &c->rate_L, &c->rate_E, &c->rate_W,
-                      &c->rate_drop, &c->rate_res, &c->drops_keep})
+                      &c->rate_drop, &c->rate_res, &c->rate_map, &c->rate_bdrop, &c->drops_keep})
         b->release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }

@@ -46,6 +46,7 @@ constexpr uint32_t kRateMaxDrop = 12;       // the largest Dmax a caller may ask
 constexpr uint32_t kRateMaxCand = kRateMaxDrop + 2;   // candidates of a block at most: d = 0 .. Dmax, SKIP
 constexpr uint32_t kRateAllocThreads = 1024;          // the allocator's one workgroup
 constexpr uint32_t kRateBisectSteps = 40;             // bisection steps of lambda once it is bracketed within a factor of two
+constexpr uint64_t kRateMaxBlocks = 0x7FFFFFFFull;    // blocks of a call's tables at most: what KR1, KR2 and the map kernels index
 constexpr uint32_t kRateMaxRounds = 4;                // allocate + write rounds of grk_amd_encode_image_rate
 
 // ---- the call's route (encode.hip) -------------------------------------------------------------------------------------------------

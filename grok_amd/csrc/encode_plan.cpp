@@ -87,6 +87,39 @@ RatePlan plan_rate(uint32_t max_drop, bool allow_skip, uint64_t nblocks)
     return r;
 }
 
+RateJointPlan plan_rate_joint(uint32_t max_drop, bool allow_skip, const std::vector<uint64_t>& unit_blocks,
+                              const std::vector<std::vector<uint32_t>>& batches)
+{
+    const RateJointPlan refused{};
+    if (max_drop > kRateMaxDrop || unit_blocks.empty() || batches.empty()) return refused;
+    RateJointPlan r{};
+    r.first_row.resize(unit_blocks.size());
+    for (size_t u = 0; u < unit_blocks.size(); ++u) {
+        if (!unit_blocks[u] || unit_blocks[u] > kRateMaxBlocks) return refused;
+        r.first_row[u] = r.n;
+        r.n += unit_blocks[u];
+        if (r.n > kRateMaxBlocks) return refused;
+    }
+    std::vector<bool> taken(unit_blocks.size(), false);
+    size_t members = 0;
+    for (const std::vector<uint32_t>& b : batches) {
+        if (b.empty()) return refused;
+        std::vector<uint64_t> m;
+        for (uint32_t u : b) {
+            if (u >= unit_blocks.size() || taken[u] || unit_blocks[u] != unit_blocks[b[0]]) return refused;
+            taken[u] = true;
+            m.push_back(r.first_row[u]);
+        }
+        members += b.size();
+        r.map.push_back(m);
+        r.per_unit.push_back((uint32_t)unit_blocks[b[0]]);
+    }
+    if (members != unit_blocks.size()) return refused;
+    r.tables = plan_rate(max_drop, allow_skip, r.n);
+    r.ok = r.tables.ok;
+    return r;
+}
+
 // ---- the arena and its allocator ---------------------------------------------------------------------------------------------------
 HtArenaPlan plan_ht_arena(uint64_t nblocks, uint64_t raw_bytes, uint32_t ntiles, const std::vector<HtClassPlan>& classes)
 {

@@ -67,6 +67,23 @@ struct RatePlan {
     uint64_t l_bytes, e_bytes, w_bytes, drop_bytes;
 };
 RatePlan plan_rate(uint32_t max_drop, bool allow_skip, uint64_t nblocks);
+// One set of tables over a whole image's units (a tile; a run of a tile's components of one size).  The joint row order is the order
+// in which the file's writer takes the table: unit after unit in unit order, unit u's unit_blocks[u] rows at first_row[u] -- whatever
+// the batches are.  A batch (one grk_amd_encode_tiles call: units of one geometry, in any order) writes its columns through
+// map[batch][i] = the first joint row of its i-th member; every member has per_unit[batch] blocks, so entry e of the batch is joint
+// row map[batch][e / per_unit] + e % per_unit < n.
+// ok = false (nothing else filled in): max_drop above kRateMaxDrop; more than kRateMaxBlocks rows; no unit, an empty unit or an empty
+// batch; a member that is no unit; a unit in no batch or in two; a batch whose members differ in their block counts.
+struct RateJointPlan {
+    bool ok;
+    uint64_t n;                                  // rows of a joint table
+    std::vector<uint64_t> first_row;             // [unit]
+    std::vector<std::vector<uint64_t>> map;      // [batch][member]
+    std::vector<uint32_t> per_unit;              // [batch]
+    RatePlan tables;                             // plan_rate over n
+};
+RateJointPlan plan_rate_joint(uint32_t max_drop, bool allow_skip, const std::vector<uint64_t>& unit_blocks,
+                              const std::vector<std::vector<uint32_t>>& batches);
 // the drop byte of candidate c, and the row's zero bit-planes for a drop byte (d clamped to Kmax - 1; SKIP: Kmax - 1)
 inline uint8_t rate_drop_byte(uint32_t c, uint32_t dmax) { return c <= dmax ? (uint8_t)c : (uint8_t)kHtDropSkip; }
 inline uint32_t drop_missing_msbs(uint32_t kmax, uint32_t drop)

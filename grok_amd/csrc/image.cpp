@@ -181,18 +181,15 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
 // is coded as one unit -- the tile's rectangle in their coordinates, `n` components, the multiple component transform only for a
 // run that holds components 0..2 --, the units of all tiles are grouped by geometry, every group is one grk_amd_encode_tiles batch,
 // and the codestream writer takes each component with its own geometry (grk_amd_write_codestream_subsampled).
-extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
-                                                   const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
-                                                   uint8_t* out, uint64_t cap)
+int grk_amd::subsampled_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                              const uint8_t* comp_dy, const void* pixels, std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g)
 {
-    if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
-    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (as the writer below would, before any work)
     {   // (components of different sizes have no interleaved form, and the runs are staged as planes)
         const grk_amd_pixel_layout& l = ctx->enc_layout;
         if (l.interleaved || l.channels || l.row_pitch || l.plane_pitch || l.tile_pitch) return GRK_AMD_ERR_UNSUPPORTED;
     }
     const int64_t nt = grk_amd_layout_num_tiles(im);
-    if (nt < 0) return nt;
+    if (nt < 0) return (int)nt;
     const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps;
     const uint32_t bps = (base->prec + 7u) / 8u;
     for (uint32_t c = 0; c < nc; ++c) if (!comp_dx[c] || !comp_dy[c]) return GRK_AMD_ERR_INVALID;
@@ -200,14 +197,12 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
     const std::vector<CompRun> runs = comp_runs(nc, base->mct != 0, comp_dx, comp_dy);
     // the image's components in `pixels`: component c is ceil(x1 / dx) - ceil(x0 / dx) columns wide, planes back to back
     auto cdiv = [](uint64_t a, uint64_t b) { return (a + b - 1) / b; };
-    SourcePlanes src{(const uint8_t*)pixels, bps, {}};
+    src = SourcePlanes{(const uint8_t*)pixels, bps, {}};
     for (uint64_t c = 0, at = 0; c < nc; ++c) {
         const uint64_t x0 = cdiv(im->x0, comp_dx[c]), y0 = cdiv(im->y0, comp_dy[c]), w = cdiv(im->x1, comp_dx[c]) - x0;
         src.comp.push_back({at, w, x0, y0});
         at += w * (cdiv(im->y1, comp_dy[c]) - y0) * bps;
     }
-    std::vector<Unit> units;
-    UnitGroups g;
     for (uint32_t t = 0; t < ntiles; ++t)
         for (uint32_t k = 0; k < runs.size(); ++k) {
             Unit u{{}, runs[k].first};
@@ -219,9 +214,24 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
             rc = add_unit(g, u.p);
             if (rc) return rc;
         }
+    return GRK_AMD_OK;
+}
+
+extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                   const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
+                                                   uint8_t* out, uint64_t cap)
+{
+    if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
+    // (a plain encode drops nothing: per-block zero bit-planes are grk_amd_encode_image_subsampled_rate's, refused here before any work)
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;
+    std::vector<Unit> units;
+    SourcePlanes src;
+    UnitGroups g;
+    int rc = subsampled_image(ctx, im, base, comp_dx, comp_dy, pixels, units, src, g);
+    if (rc) return rc;
     std::vector<grk_amd_coded_block> rows;                   // tile-major, within a tile component-major (the runs in order)
     std::vector<uint8_t> coded;
-    const int rc = encode_groups_host(ctx, src, units, g, rows, coded);
+    rc = encode_groups_host(ctx, src, units, g, rows, coded);
     if (rc) return rc;
     return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, cap);
 }

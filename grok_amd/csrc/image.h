@@ -91,6 +91,33 @@ int encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const std::vec
 int64_t frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags, const std::vector<uint32_t>& part_len,
                    uint8_t* out, uint64_t cap, const std::function<int(const std::vector<uint64_t>& at)>& body);
 
+// An image of sub-sampled components (grk_amd_encode_image_subsampled's `pixels`: the components back to back, tight) cut into units
+// -- tile by tile, within a tile run by run (comp_runs) -- and grouped.  GRK_AMD_ERR_UNSUPPORTED under a pixel layout of the caller's
+// (components of different sizes have no interleaved form), GRK_AMD_ERR_INVALID for a factor of 0, else the layout's errors.
+int subsampled_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                     const uint8_t* comp_dy, const void* pixels, std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g);
+
+// ---- a whole image in a file of at most N bytes over JOINT tables (rate.hip) -----------------------------------------------------
+// The caller names the image's units (unit_blocks[u]: unit u's rows, in the order the file's writer takes the table) and its
+// batches -- each one grk_amd_encode_tiles call over units of one geometry -- and lends two steps:
+//   front(k, table, total)        batch k's pixels staged where they have to be and coded plainly: grk_amd_encode_tiles with these
+//                                 `table` (host rows or null) and `total`; called once for the tables and again before a round's
+//                                 final launch whenever another batch's planes have taken the context since
+//   write(rows, coded, out, cap)  the file of these rows (joint order; offsets into `coded`), or with out == nullptr its length
+// encode_rate_joint makes the tables L, E, W over all units once (every batch's KR1 and trial launches write their columns through
+// the batch's map: plan_rate_joint), runs KR2 once per round over them -- one multiplier for every block of the image -- and codes
+// each batch with its slice of the chosen drops; the rounds are rate_rounds' (rate.hip), shared with the split route.  Returns the
+// file's length or an error; rate_refusal: what every rate-targeted call refuses before any work (pipelining, max_drop).
+struct RateBatch { grk_amd_tile_params p; std::vector<uint32_t> units; };
+struct RateJointCall {
+    const grk_amd_tile_params* base; const grk_amd_rate* rate;
+    std::vector<uint64_t> unit_blocks; std::vector<RateBatch> batches;
+    std::function<int(size_t k, grk_amd_coded_block* table, uint64_t* total)> front;
+    std::function<int64_t(const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* out, uint64_t cap)> write;
+};
+int rate_refusal(grk_amd_ctx* ctx, const grk_amd_rate* rate);
+int64_t encode_rate_joint(grk_amd_ctx* ctx, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result);
+
 // fn(i) for i in [0, n) on up to `threads` host threads, the caller's among them; items are handed out by a counter and the
 // first error wins (no item starts after it)
 int parallel_for(size_t n, uint32_t threads, const std::function<int(size_t)>& fn);

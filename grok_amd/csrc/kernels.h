@@ -124,8 +124,16 @@ struct RateStatsArgs {
     const HtBlockDesc* blocks; uint32_t blocks_per_tile, ncomp; uint64_t nblocks;
     uint32_t dmax;
     unsigned long long* E;             // [dmax + 2][nblocks]: sum of (2 q - 2 r_c(q))^2 over the block
+    // a batch's columns of a call's joint tables: tile t's blocks at map[t] .. (device, [nblocks / blocks_per_tile]) of rows of n entries;
+    // nullptr: the identity, rows of nblocks entries
+    const unsigned long long* map = nullptr; uint64_t n = 0;
 };
 hipError_t launch_rate_stats(const RateStatsArgs& a, hipStream_t s);
+// A batch's column and a joint row: entry i of `batch` is entry map[i / per_unit] + i % per_unit of `joint` (plan_rate_joint's map:
+// every such index is inside the joint row).  gather = 0: batch -> joint, elements of 4 bytes (a trial's length column into a row of
+// L); gather = 1: joint -> batch, elements of 1 byte (the chosen drop bytes for the batch's final launch)
+struct RateMapArgs { void* batch; void* joint; const unsigned long long* map; uint32_t per_unit; uint64_t count; uint32_t elem; int gather; };
+hipError_t launch_rate_map(const RateMapArgs& a, hipStream_t s);
 struct RateAllocResult {
     unsigned long long block_bytes, lagrange_bytes, least_bytes;      // the choice's bytes; the Lagrange solution's; the fewest any choice takes
     double distortion, lambda;                                        // sum of W E of the choice; the multiplier

@@ -22,10 +22,12 @@ namespace {
 // to Kmax - 1 as the coder clamps it, so that a row describes the block as coded (it differs from the unclamped row only in bands
 // with Kmax <= Dmax).
 // E[c][block] = sum over the block of (2 q - 2 r_c(q))^2, modulo 2^64 (q < 2^30: a 64 x 64 block stays below 2^64 up to q < 2^25).
+// The block's column: its own index in rows of nblocks entries (map == nullptr), or -- a batch writing into a call's joint tables --
+// map[tile] + its index in the tile, in rows of n entries (the host planned the map: plan_rate_joint).
 template <class PLANE, bool IRREV>
 __global__ __launch_bounds__(64) void rate_stats_kernel(const PLANE* mallat, uint32_t stride, uint64_t pitch, const HtBlockDesc* blocks,
                                                         uint32_t blocks_per_tile, uint32_t ncomp, uint64_t nblocks, uint32_t dmax,
-                                                        unsigned long long* E)
+                                                        unsigned long long* E, const unsigned long long* map, uint64_t n)
 {
     const uint64_t i = blockIdx.x;
     if (i >= nblocks) return;
@@ -62,11 +64,25 @@ __global__ __launch_bounds__(64) void rate_stats_kernel(const PLANE* mallat, uin
     for (uint32_t c = 0; c <= kRateMaxDrop; ++c)
         for (int off = 32; off > 0; off >>= 1) acc[c] += __shfl_down(acc[c], off, 64);
     if (lane == 0) {
-        E[i] = 0;                                                   // row 0: nothing dropped
+        const uint64_t col = map ? map[tile] + i % blocks_per_tile : i;
+        E[col] = 0;                                                 // row 0: nothing dropped
 #pragma unroll
-        for (uint32_t c = 1; c <= kRateMaxDrop; ++c) if (c <= dmax) E[(uint64_t)c * nblocks + i] = acc[c];
-        E[(uint64_t)(dmax + 1u) * nblocks + i] = acc[0];            // row dmax + 1: SKIP
+        for (uint32_t c = 1; c <= kRateMaxDrop; ++c) if (c <= dmax) E[(uint64_t)c * n + col] = acc[c];
+        E[(uint64_t)(dmax + 1u) * n + col] = acc[0];                // row dmax + 1: SKIP
     }
+}
+
+// ---- a batch's column of a joint table ------------------------------------------------------------------------------------------------
+// Entry i of a batch (unit i / per_unit, tile-major as K3 writes its length column and reads its drops) is entry map[unit] + i %
+// per_unit of a joint row.  GATHER = false: batch -> joint (a trial's lengths into row d of L); true: joint -> batch (the chosen drop
+// bytes for the batch's final launch).  Every index is inside both arrays: the host planned the map.
+template <class T, bool GATHER>
+__global__ __launch_bounds__(256) void rate_map_kernel(T* batch, T* joint, const unsigned long long* map, uint32_t per_unit, uint64_t count)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t j = map[i / per_unit] + i % per_unit;
+    if constexpr (GATHER) batch[i] = joint[j]; else joint[j] = batch[i];
 }
 
 // ---- KR2 ------------------------------------------------------------------------------------------------------------------------------
@@ -217,17 +233,31 @@ __global__ __launch_bounds__(kRateAllocThreads) void rate_alloc_kernel(RateAlloc
 hipError_t launch_rate_stats(const RateStatsArgs& a, hipStream_t s)
 {
     if (!a.nblocks) return hipSuccess;
-    if (a.dmax == 0 || a.dmax > kRateMaxDrop || a.nblocks > 0x7FFFFFFFull || (a.h16 && a.irreversible)) return hipErrorInvalidValue;
+    const uint64_t n = a.map ? a.n : a.nblocks;
+    if (a.dmax == 0 || a.dmax > kRateMaxDrop || a.nblocks > kRateMaxBlocks || n > kRateMaxBlocks || n < a.nblocks || (a.h16 && a.irreversible))
+        return hipErrorInvalidValue;
     const dim3 grid((uint32_t)a.nblocks), block(64);
-    if (a.h16) hipLaunchKernelGGL((rate_stats_kernel<int16_t, false>), grid, block, 0, s, (const int16_t*)a.mallat, a.stride, a.pitch, a.blocks, a.blocks_per_tile, a.ncomp, a.nblocks, a.dmax, a.E);
-    else if (a.irreversible) hipLaunchKernelGGL((rate_stats_kernel<int32_t, true>), grid, block, 0, s, (const int32_t*)a.mallat, a.stride, a.pitch, a.blocks, a.blocks_per_tile, a.ncomp, a.nblocks, a.dmax, a.E);
-    else hipLaunchKernelGGL((rate_stats_kernel<int32_t, false>), grid, block, 0, s, (const int32_t*)a.mallat, a.stride, a.pitch, a.blocks, a.blocks_per_tile, a.ncomp, a.nblocks, a.dmax, a.E);
+    if (a.h16) hipLaunchKernelGGL((rate_stats_kernel<int16_t, false>), grid, block, 0, s, (const int16_t*)a.mallat, a.stride, a.pitch, a.blocks, a.blocks_per_tile, a.ncomp, a.nblocks, a.dmax, a.E, a.map, n);
+    else if (a.irreversible) hipLaunchKernelGGL((rate_stats_kernel<int32_t, true>), grid, block, 0, s, (const int32_t*)a.mallat, a.stride, a.pitch, a.blocks, a.blocks_per_tile, a.ncomp, a.nblocks, a.dmax, a.E, a.map, n);
+    else hipLaunchKernelGGL((rate_stats_kernel<int32_t, false>), grid, block, 0, s, (const int32_t*)a.mallat, a.stride, a.pitch, a.blocks, a.blocks_per_tile, a.ncomp, a.nblocks, a.dmax, a.E, a.map, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_rate_map(const RateMapArgs& a, hipStream_t s)
+{
+    if (!a.count) return hipSuccess;
+    if (!a.batch || !a.joint || !a.map || !a.per_unit || a.count > kRateMaxBlocks || (a.elem != 1 && a.elem != 4) || (a.gather && a.elem != 1) ||
+        (!a.gather && a.elem != 4))
+        return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((a.count + 255u) / 256u)), block(256);
+    if (a.gather) hipLaunchKernelGGL((rate_map_kernel<uint8_t, true>), grid, block, 0, s, (uint8_t*)a.batch, (uint8_t*)a.joint, a.map, a.per_unit, a.count);
+    else hipLaunchKernelGGL((rate_map_kernel<uint32_t, false>), grid, block, 0, s, (uint32_t*)a.batch, (uint32_t*)a.joint, a.map, a.per_unit, a.count);
     return hipGetLastError();
 }
 
 hipError_t launch_rate_alloc(const RateAllocArgs& a, hipStream_t s)
 {
-    if (!a.nblocks || a.nblocks > 0x7FFFFFFFull || a.dmax == 0 || a.dmax > kRateMaxDrop || a.ncand < a.dmax + 1u || a.ncand > a.dmax + 2u)
+    if (!a.nblocks || a.nblocks > kRateMaxBlocks || a.dmax == 0 || a.dmax > kRateMaxDrop || a.ncand < a.dmax + 1u || a.ncand > a.dmax + 2u)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(rate_alloc_kernel, dim3(1), dim3(kRateAllocThreads), 0, s, a);
     return hipGetLastError();

@@ -6,10 +6,39 @@
 // d = 0 .. Dmax, the arena rewound in between, only the length column kept) give every candidate's exact length, KR2 chooses each
 // block's drop for the budget, and a last launch codes the blocks with those drops.  No per-block data comes to the host before the
 // final table does.
+//
+// A whole image whose units fall into several batches (tiles of several geometries; luma and chroma of a sub-sampled image or of a
+// video surface) has ONE set of tables over all its blocks in the order the file's writer takes them (encode_rate_joint; the row
+// order, the batches' maps and the bounds are plan_rate_joint's, encode_plan.h): each batch's KR1 and trial launches write their
+// columns through the batch's map, KR2 runs once per round over the joint tables -- one multiplier for every block of every
+// component --, and a batch is coded with its slice of the chosen drops.  The tables are made once per call.
 #include "context.h"
 #include "image.h"
 
 namespace {
+
+// KR1 and the Dmax + 1 trial launches over the planes the latest front end left (`ntiles` units of the context's geometry): the
+// batch's columns of E and L, in rows of N entries -- through `map` (device: the units' first rows, plan_rate_joint), or with
+// map == nullptr at the batch's own indices (N: its blocks).  drops: device scratch of one byte per block of the batch
+int batch_tables(grk_amd_ctx* c, const RatePlan& rp, uint32_t ntiles, const unsigned long long* map, uint64_t N, void* drops)
+{
+    const TileGeom& g = c->geom;
+    const uint64_t n = c->last_nblocks;
+    const uint32_t bpt = (uint32_t)(n / ntiles);
+    RateStatsArgs sa{};
+    sa.mallat = c->p1.p; sa.h16 = c->last_h16 ? 1 : 0; sa.irreversible = g.p.irreversible; sa.stride = g.stride; sa.pitch = g.plane_elems;
+    sa.blocks = (const HtBlockDesc*)c->blockdesc.p; sa.blocks_per_tile = bpt; sa.ncomp = g.p.num_comps; sa.nblocks = n;
+    sa.dmax = rp.dmax; sa.E = (unsigned long long*)c->rate_E.p; sa.map = map; sa.n = N;
+    HIP_TRY(c, launch_rate_stats(sa, c->stream), "launch rate statistics");
+    for (uint32_t d = 0; d < rp.trials; ++d) {
+        HIP_TRY(c, hipMemsetAsync(drops, (int)d, n, c->stream), "uniform drops");
+        const int rc = ht_encode_drops(c, ntiles, c->p1.p, c->last_h16, (const uint8_t*)drops); if (rc) return rc;
+        uint32_t* const row = (uint32_t*)c->rate_L.p + (uint64_t)d * N;
+        if (map) HIP_TRY(c, launch_rate_map(RateMapArgs{c->lengths.p, row, map, bpt, n, 4u, 0}, c->stream), "keep the lengths");
+        else HIP_TRY(c, hipMemcpyAsync(row, c->lengths.p, n * 4, hipMemcpyDeviceToDevice, c->stream), "keep the lengths");
+    }
+    return GRK_AMD_OK;
+}
 
 // front end + plain K3 + the tables L, E, W for `ntiles` tiles of *p.  plain_table (optional, host): the rows of the plain encode
 int rate_prepare(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* pixels, int on_device, const grk_amd_rate* rate,
@@ -37,23 +66,16 @@ int rate_prepare(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, 
     for (uint64_t i = bpt; i < n; ++i) w[i] = w[i - bpt];
     HIP_TRY(c, hipMemcpyAsync(c->rate_W.p, w.data(), n * 8, hipMemcpyHostToDevice, c->stream), "upload rate weights");
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-    RateStatsArgs sa{};
-    sa.mallat = c->p1.p; sa.h16 = c->last_h16 ? 1 : 0; sa.irreversible = g.p.irreversible; sa.stride = g.stride; sa.pitch = g.plane_elems;
-    sa.blocks = (const HtBlockDesc*)c->blockdesc.p; sa.blocks_per_tile = bpt; sa.ncomp = g.p.num_comps; sa.nblocks = n;
-    sa.dmax = rp.dmax; sa.E = (unsigned long long*)c->rate_E.p;
-    HIP_TRY(c, launch_rate_stats(sa, c->stream), "launch rate statistics");
     HIP_TRY(c, hipMemsetAsync(c->rate_L.p, 0, rp.l_bytes, c->stream), "clear rate lengths");          // (the SKIP row stays 0)
-    for (uint32_t d = 0; d < rp.trials; ++d) {
-        HIP_TRY(c, hipMemsetAsync(c->rate_drop.p, (int)d, n, c->stream), "uniform drops");
-        rc = ht_encode_drops(c, ntiles, c->p1.p, c->last_h16, (const uint8_t*)c->rate_drop.p); if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync((uint32_t*)c->rate_L.p + (uint64_t)d * n, c->lengths.p, n * 4, hipMemcpyDeviceToDevice, c->stream), "keep the lengths");
-    }
+    rc = batch_tables(c, rp, ntiles, nullptr, n, c->rate_drop.p); if (rc) return rc;
     c->rate.valid = true; c->rate.plan = rp; c->rate.nblocks = n; c->rate.ntiles = ntiles;
+    c->rate.unit_rows.resize(ntiles);
+    for (uint32_t t = 0; t < ntiles; ++t) c->rate.unit_rows[t] = (uint64_t)t * bpt;
     return GRK_AMD_OK;
 }
 
-// KR2 for `budget` bytes of code-blocks over the prepared tables, then the blocks coded with the chosen drops
-int rate_allocate(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
+// KR2 for `budget` bytes of code-blocks over the prepared tables: the chosen drop bytes in rate_drop
+int rate_choose(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
 {
     if (!c->rate.valid) return GRK_AMD_ERR_INVALID;
     const RatePlan& rp = c->rate.plan;
@@ -61,6 +83,7 @@ int rate_allocate(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
     a.L = (const uint32_t*)c->rate_L.p; a.E = (const unsigned long long*)c->rate_E.p; a.W = (const double*)c->rate_W.p;
     a.nblocks = c->rate.nblocks; a.dmax = rp.dmax; a.ncand = rp.ncand; a.budget = budget;
     a.drop = (uint8_t*)c->rate_drop.p; a.res = (RateAllocResult*)c->rate_res.p;
+    c->rate.budget = budget;
     {
         ScopedTimer t(c, 9);
         HIP_TRY(c, launch_rate_alloc(a, c->stream), "launch rate allocator");
@@ -73,6 +96,13 @@ int rate_allocate(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
                       res.least_bytes, rp.ncand == rp.dmax + 2u ? "SKIP" : "the largest drop");
         return fail(c, GRK_AMD_ERR_OVERFLOW, msg);
     }
+    return GRK_AMD_OK;
+}
+
+// ... then the blocks of the one batch the tables are over coded with the chosen drops
+int rate_allocate(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
+{
+    const int rc = rate_choose(c, budget, res); if (rc) return rc;
     return ht_encode_drops(c, c->rate.ntiles, c->p1.p, c->last_h16, (const uint8_t*)c->rate_drop.p);
 }
 
@@ -124,7 +154,7 @@ void note_reversible(grk_amd_ctx* c, const grk_amd_tile_params& p, bool dropped)
 }
 
 // the file's length for a table (sizes only: nothing is written)
-int64_t sized_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags, const std::vector<grk_amd_coded_block>& rows)
+int64_t sized_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags, const grk_amd_coded_block* rows)
 {
     const int64_t nt = grk_amd_layout_num_tiles(im);
     if (nt < 0) return nt;
@@ -133,7 +163,7 @@ int64_t sized_file(const grk_amd_image_layout* im, const grk_amd_tile_params* ba
     for (uint32_t t = 0; t < (uint32_t)nt; ++t) {
         grk_amd_tile_params p;
         const int rc = grk_amd_layout_tile(im, base, t, &p); if (rc) return rc;
-        const int64_t len = grk_amd_write_tile_part(&p, t, flags, rows.data() + row, nullptr, nullptr, 0);
+        const int64_t len = grk_amd_write_tile_part(&p, t, flags, rows + row, nullptr, nullptr, 0);
         if (len < 0) return len;
         const int64_t nb = grk_amd_tile_num_blocks(&p);
         if (nb < 0) return nb;
@@ -179,8 +209,155 @@ int grk_amd_rate_tables(grk_amd_ctx* c, int which, void* dst, uint64_t cap_bytes
     return GRK_AMD_OK;
 }
 
-// Headers and packet headers depend on the allocation: the blocks' budget is the target less what the file of the round before spent
-// beside its blocks (first: the plain file), and a file that still overshoots lowers the budget by its overshoot.
+} // extern "C"
+
+namespace {
+
+// The rounds of every whole-image call. Headers and packet headers depend on the allocation: the blocks' budget is the target less
+// what the file of the round before spent beside its blocks (first: the plain file), and a file that still overshoots lowers the
+// budget by its overshoot.  `rows` hold the plain encode's rows on entry; round(budget, sum): KR2 and the final launches -- `rows` and
+// `coded` as the file's writer takes them; file(out, cap): the file of `rows` and `coded`, or with out == nullptr its length.
+int64_t rate_rounds(grk_amd_ctx* ctx, const grk_amd_tile_params& base, uint64_t target, const std::vector<grk_amd_coded_block>& rows,
+                    std::vector<uint8_t>& coded, const std::function<int(uint64_t budget, RateAllocResult& sum)>& round,
+                    const std::function<int64_t(uint8_t* out, uint64_t cap)>& file, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
+    uint64_t plain_blocks = 0;
+    for (const grk_amd_coded_block& r : rows) plain_blocks += r.length;
+    const int64_t plain = file(nullptr, 0);
+    if (plain < 0) return plain;
+    uint64_t overhead = (uint64_t)plain - plain_blocks;
+    uint64_t budget = target >= (uint64_t)plain ? plain_blocks : target > overhead ? target - overhead : 0;
+    for (uint32_t pass = 1; pass <= kRateMaxRounds; ++pass) {
+        RateAllocResult sum{};
+        const int rc = round(budget, sum); if (rc) return rc;
+        const int64_t len = file(nullptr, 0);
+        if (len < 0) return len;
+        if ((uint64_t)len <= target) {
+            coded.push_back(0);                     // (the writer wants a buffer even when every block was skipped)
+            const int64_t wrote = file(out, cap);
+            if (wrote >= 0) { fill_result(result, sum, (uint64_t)wrote, pass); note_reversible(ctx, base, sum.block_bytes < plain_blocks); }
+            return wrote;
+        }
+        const uint64_t over = (uint64_t)len - target;
+        if (budget == 0 || sum.block_bytes == 0)          // nothing left to take from the blocks: the headers alone are too long
+            return fail(ctx, GRK_AMD_ERR_OVERFLOW, "the target is below what the file takes with no byte of any block in it");
+        budget = std::min<uint64_t>(budget, sum.block_bytes);
+        budget = budget > over ? budget - over : 0;
+    }
+    return fail(ctx, GRK_AMD_ERR_OVERFLOW, "the file was still above the target after 4 allocate + write rounds (the target may be feasible: the rounds ran out)");
+}
+
+} // namespace
+
+// ---- joint tables --------------------------------------------------------------------------------------------------------------
+int grk_amd::rate_refusal(grk_amd_ctx* ctx, const grk_amd_rate* rate)
+{
+    if (ctx->pipelining) return fail(ctx, GRK_AMD_ERR_UNSUPPORTED, "rate-targeted encodes are not pipelined (grk_amd_set_pipelining(ctx, 0))");
+    if (!plan_rate(rate->max_drop, rate->allow_skip != 0, 0).ok) return fail(ctx, GRK_AMD_ERR_INVALID, "grk_amd_rate::max_drop above 12");
+    return GRK_AMD_OK;
+}
+
+int64_t grk_amd::encode_rate_joint(grk_amd_ctx* c, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
+    c->rate.valid = false;
+    { const int rc = rate_refusal(c, call.rate); if (rc) return rc; }
+    const size_t nbatches = call.batches.size();
+    std::vector<std::vector<uint32_t>> members;
+    for (const RateBatch& b : call.batches) members.push_back(b.units);
+    const RateJointPlan jp = plan_rate_joint(call.rate->max_drop, call.rate->allow_skip != 0, call.unit_blocks, members);
+    if (!jp.ok) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "rate tables: more blocks than the allocator indexes");
+    const RatePlan& rp = jp.tables;
+    const uint64_t N = jp.n;
+    // the batches' maps one behind the other on the device, the largest batch's drop bytes, the tables
+    std::vector<unsigned long long> maps;
+    std::vector<size_t> map_at(nbatches);
+    uint64_t largest = 0;
+    for (size_t k = 0; k < nbatches; ++k) {
+        map_at[k] = maps.size();
+        maps.insert(maps.end(), jp.map[k].begin(), jp.map[k].end());
+        largest = std::max<uint64_t>(largest, (uint64_t)jp.per_unit[k] * jp.map[k].size());
+    }
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the buffers below may still be read by an earlier call)
+    HIP_TRY(c, c->rate_L.ensure(rp.l_bytes), "alloc rate lengths");
+    HIP_TRY(c, c->rate_E.ensure(rp.e_bytes), "alloc rate errors");
+    HIP_TRY(c, c->rate_W.ensure(rp.w_bytes), "alloc rate weights");
+    HIP_TRY(c, c->rate_drop.ensure(rp.drop_bytes), "alloc drops");
+    HIP_TRY(c, c->rate_res.ensure(sizeof(RateAllocResult)), "alloc rate result");
+    HIP_TRY(c, c->rate_map.ensure(maps.size() * 8), "alloc rate maps");
+    HIP_TRY(c, c->rate_bdrop.ensure(largest), "alloc a batch's drops");
+    HIP_TRY(c, hipMemcpy(c->rate_map.p, maps.data(), maps.size() * 8, hipMemcpyHostToDevice), "upload rate maps");
+    HIP_TRY(c, hipMemsetAsync(c->rate_L.p, 0, rp.l_bytes, c->stream), "clear rate lengths");          // (the SKIP row stays 0)
+    std::vector<grk_amd_coded_block> rows(N), table;
+    std::vector<uint8_t> coded;
+    std::vector<double> w(N);
+    size_t resident = nbatches;                      // the batch whose planes and geometry the context holds
+    auto map_of = [&](size_t k) { return (const unsigned long long*)c->rate_map.p + map_at[k]; };
+    auto keep_rows = [&](size_t k, size_t at) {
+        const uint64_t bpu = jp.per_unit[k];
+        for (size_t i = 0; i < jp.map[k].size(); ++i)
+            for (uint64_t b = 0; b < bpu; ++b) { rows[jp.map[k][i] + b] = table[i * bpu + b]; rows[jp.map[k][i] + b].offset += at; }
+    };
+    // ---- the tables, batch by batch: the plain rows, the weights, KR1 and the trial launches through the batch's map
+    for (size_t k = 0; k < nbatches; ++k) {
+        const uint32_t bpu = jp.per_unit[k], nunits = (uint32_t)jp.map[k].size();
+        const uint64_t n = (uint64_t)bpu * nunits;
+        table.resize(n);
+        uint64_t total = 0;
+        // (synchronous, with the arena / range flags checked: the trial launches below code from the planes this leaves)
+        int rc = call.front(k, table.data(), &total); if (rc) return rc;
+        resident = k;
+        const TileGeom& g = c->geom;
+        if (c->last_nblocks != n) return fail(c, GRK_AMD_ERR_INVALID, "rate tables: a batch's blocks are not its units'");
+        keep_rows(k, 0);
+        // W_b = (w_mct * w_band * stepsize)^2 / 4 of the unit's own geometry: E counts half steps
+        for (uint32_t i = 0; i < bpu; ++i) {
+            const double v = block_weight(g, i);
+            for (uint64_t at : jp.map[k]) w[at + i] = v * v * 0.25;
+        }
+        rc = batch_tables(c, rp, nunits, map_of(k), N, c->rate_bdrop.p); if (rc) return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->rate_W.p, w.data(), N * 8, hipMemcpyHostToDevice, c->stream), "upload rate weights");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    c->rate.valid = true; c->rate.plan = rp; c->rate.nblocks = N; c->rate.ntiles = 0; c->rate.unit_rows = jp.first_row;
+    // ---- a round: KR2 over the joint tables, then every batch -- its front end again where another batch has taken the context
+    //      since -- coded with its slice of the drops
+    auto round = [&](uint64_t budget, RateAllocResult& sum) -> int {
+        int rc = rate_choose(c, budget, sum); if (rc) return rc;
+        coded.clear();
+        for (size_t k = 0; k < nbatches; ++k) {
+            const uint32_t bpu = jp.per_unit[k], nunits = (uint32_t)jp.map[k].size();
+            const uint64_t n = (uint64_t)bpu * nunits;
+            uint64_t total = 0;
+            if (resident != k) { rc = call.front(k, nullptr, &total); if (rc) return rc; resident = k; }
+            const RateMapArgs ma{c->rate_bdrop.p, c->rate_drop.p, map_of(k), bpu, n, 1u, 1};
+            HIP_TRY(c, launch_rate_map(ma, c->stream), "gather the batch's drops");
+            rc = ht_encode_drops(c, nunits, c->p1.p, c->last_h16, (const uint8_t*)c->rate_bdrop.p); if (rc) return rc;
+            table.resize(n);
+            rc = grk_amd_fetch_table(c, table.data(), &total); if (rc) return rc;
+            const size_t at = coded.size();
+            coded.resize(at + total);
+            if (total) { rc = grk_amd_fetch_coded(c, coded.data() + at, total); if (rc) return rc; }
+            keep_rows(k, at);
+        }
+        return GRK_AMD_OK;
+    };
+    return rate_rounds(c, *call.base, call.rate->target_bytes, rows, coded, round,
+                       [&](uint8_t* o, uint64_t ocap) { return call.write(rows.data(), coded.data(), o, ocap); }, out, cap, result);
+}
+
+extern "C" {
+
+uint64_t grk_amd_rate_num_blocks(grk_amd_ctx* c) { return c && c->rate.valid ? c->rate.nblocks : 0; }
+uint64_t grk_amd_rate_last_budget(grk_amd_ctx* c) { return c && c->rate.valid ? c->rate.budget : 0; }
+
+int grk_amd_rate_unit_rows(grk_amd_ctx* c, uint64_t* first_row, uint32_t cap)
+{
+    if (!c || !c->rate.valid) return GRK_AMD_ERR_INVALID;
+    for (size_t u = 0; u < c->rate.unit_rows.size() && u < cap && first_row; ++u) first_row[u] = c->rate.unit_rows[u];
+    return (int)c->rate.unit_rows.size();
+}
+
 int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels,
                                   uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
 {
@@ -196,19 +373,40 @@ int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* 
     KeepLayout staged{ctx->enc_layout, whole};
     ctx->enc_layout = staged_layout(src);
     const size_t ngroups = g.members.size();
+    std::vector<uint8_t> staging;
+    // a group's tiles staged and coded plainly
+    auto stage_group = [&](size_t k) {
+        const auto& G = g.members[k];
+        staging.resize(staged_bytes(src, tiles[G[0]]) * G.size());
+        stage_units(src, tiles, G, staging.data(), 1);
+    };
+    if (rate->joint) {
+        RateJointCall call{base, rate, {}, {}, {}, {}};
+        for (size_t u = 0; u < tiles.size(); ++u) call.unit_blocks.push_back((uint64_t)g.geoms[g.of[u]].blocks_per_comp * tiles[u].p.num_comps);
+        for (size_t k = 0; k < ngroups; ++k) call.batches.push_back(RateBatch{tiles[g.members[k][0]].p, g.members[k]});
+        call.front = [&](size_t k, grk_amd_coded_block* table, uint64_t* total) -> int {
+            stage_group(k);
+            return grk_amd_encode_tiles(ctx, &call.batches[k].p, (uint32_t)g.members[k].size(), staging.data(), 0, table, total);
+        };
+        call.write = [&](const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* o, uint64_t ocap) -> int64_t {
+            if (!o) return sized_file(im, base, flags, rows);
+            return grk_amd_write_codestream_layout(im, base, rows, coded, flags, o, ocap);
+        };
+        return encode_rate_joint(ctx, call, out, cap, result);
+    }
+    // the split route: every group alone on its own tables, its share of the budget by sample count
     std::vector<uint64_t> row_at(tiles.size() + 1, 0), samples(ngroups, 0), plain_of(ngroups, 0);
     for (size_t u = 0; u < tiles.size(); ++u) {
         row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * tiles[u].p.num_comps;
         samples[g.of[u]] += (uint64_t)tiles[u].p.tile_w * tiles[u].p.tile_h * tiles[u].p.num_comps;
     }
     std::vector<grk_amd_coded_block> rows(row_at.back());
-    std::vector<uint8_t> coded, staging;
-    // a group's tiles staged, coded plainly, its tables made (one group: once for all rounds)
+    std::vector<uint8_t> coded;
+    // ... its tables made (one group: once for all rounds)
     auto prepare = [&](size_t k, bool keep_plain) -> int {
         const auto& G = g.members[k];
         const grk_amd_tile_params& p = tiles[G[0]].p;
-        staging.resize(staged_bytes(src, tiles[G[0]]) * G.size());
-        stage_units(src, tiles, G, staging.data(), 1);
+        stage_group(k);
         const uint64_t bpu = (uint64_t)g.geoms[k].blocks_per_comp * p.num_comps;
         std::vector<grk_amd_coded_block> table(keep_plain ? bpu * G.size() : 0);
         const int pr = rate_prepare(ctx, &p, (uint32_t)G.size(), staging.data(), 0, rate, keep_plain ? table.data() : nullptr);
@@ -217,52 +415,63 @@ int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* 
             for (uint64_t b = 0; b < bpu; ++b) rows[row_at[G[i]] + b] = table[i * bpu + b];
         return GRK_AMD_OK;
     };
-    // the plain file's size and what it spends beside its blocks
-    uint64_t plain_blocks = 0;
     for (size_t k = 0; k < ngroups; ++k) { rc = prepare(k, true); if (rc) return rc; }
     for (size_t u = 0; u < tiles.size(); ++u)
-        for (uint64_t b = row_at[u]; b < row_at[u + 1]; ++b) { plain_of[g.of[u]] += rows[b].length; plain_blocks += rows[b].length; }
-    const int64_t plain = sized_file(im, base, flags, rows);
-    if (plain < 0) return plain;
-    const uint64_t target = rate->target_bytes;
-    uint64_t overhead = (uint64_t)plain - plain_blocks;
-    uint64_t budget = target >= (uint64_t)plain ? plain_blocks : target > overhead ? target - overhead : 0;
-    RateAllocResult sum{};
-    for (uint32_t round = 1; round <= kRateMaxRounds; ++round) {
+        for (uint64_t b = row_at[u]; b < row_at[u + 1]; ++b) plain_of[g.of[u]] += rows[b].length;
+    auto round = [&](uint64_t budget, RateAllocResult& sum) -> int {
         coded.clear();
-        sum = RateAllocResult{};
         const std::vector<uint64_t> share = group_shares(budget, samples, plain_of);
         for (size_t k = 0; k < ngroups; ++k) {
-            if (ngroups > 1) { rc = prepare(k, false); if (rc) return rc; }
+            int rr;
+            if (ngroups > 1) { rr = prepare(k, false); if (rr) return rr; }
             RateAllocResult r{};
-            rc = rate_allocate(ctx, share[k], r); if (rc) return rc;
+            rr = rate_allocate(ctx, share[k], r); if (rr) return rr;
             sum.block_bytes += r.block_bytes; sum.lagrange_bytes += r.lagrange_bytes; sum.distortion += r.distortion; sum.lambda = r.lambda;
             const auto& G = g.members[k];
             const uint64_t bpu = (uint64_t)g.geoms[k].blocks_per_comp * tiles[G[0]].p.num_comps;
             std::vector<grk_amd_coded_block> table(bpu * G.size());
             uint64_t total = 0;
-            rc = grk_amd_fetch_table(ctx, table.data(), &total); if (rc) return rc;
+            rr = grk_amd_fetch_table(ctx, table.data(), &total); if (rr) return rr;
             const size_t at = coded.size();
             coded.resize(at + total);
-            if (total) { rc = grk_amd_fetch_coded(ctx, coded.data() + at, total); if (rc) return rc; }
+            if (total) { rr = grk_amd_fetch_coded(ctx, coded.data() + at, total); if (rr) return rr; }
             for (size_t i = 0; i < G.size(); ++i)
                 for (uint64_t b = 0; b < bpu; ++b) { rows[row_at[G[i]] + b] = table[i * bpu + b]; rows[row_at[G[i]] + b].offset += at; }
         }
-        const int64_t len = sized_file(im, base, flags, rows);
-        if (len < 0) return len;
-        if ((uint64_t)len <= target) {
-            coded.push_back(0);                     // (the writer wants a buffer even when every block was skipped)
-            const int64_t wrote = grk_amd_write_codestream_layout(im, base, rows.data(), coded.data(), flags, out, cap);
-            if (wrote >= 0) { fill_result(result, sum, (uint64_t)wrote, round); note_reversible(ctx, *base, sum.block_bytes < plain_blocks); }
-            return wrote;
-        }
-        const uint64_t over = (uint64_t)len - target;
-        if (budget == 0 || sum.block_bytes == 0)          // nothing left to take from the blocks: the headers alone are too long
-            return fail(ctx, GRK_AMD_ERR_OVERFLOW, "the target is below what the file takes with no byte of any block in it");
-        budget = std::min<uint64_t>(budget, sum.block_bytes);
-        budget = budget > over ? budget - over : 0;
-    }
-    return fail(ctx, GRK_AMD_ERR_OVERFLOW, "the file was still above the target after 4 allocate + write rounds (the target may be feasible: the rounds ran out)");
+        return GRK_AMD_OK;
+    };
+    return rate_rounds(ctx, *base, rate->target_bytes, rows, coded, round, [&](uint8_t* o, uint64_t ocap) -> int64_t {
+        if (!o) return sized_file(im, base, flags, rows.data());
+        return grk_amd_write_codestream_layout(im, base, rows.data(), coded.data(), flags, o, ocap);
+    }, out, cap, result);
+}
+
+int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                             const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
+                                             const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
+    if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy || !rate) return GRK_AMD_ERR_INVALID;
+    { const int rr = rate_refusal(ctx, rate); if (rr) return rr; }
+    flags |= GRK_AMD_CS_BLOCK_MSBS;
+    std::vector<Unit> units;
+    SourcePlanes src;
+    UnitGroups g;
+    const int rc = subsampled_image(ctx, im, base, comp_dx, comp_dy, pixels, units, src, g);
+    if (rc) return rc;
+    std::vector<uint8_t> staging;
+    RateJointCall call{base, rate, {}, {}, {}, {}};
+    for (size_t u = 0; u < units.size(); ++u) call.unit_blocks.push_back((uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].p.num_comps);
+    for (size_t k = 0; k < g.members.size(); ++k) call.batches.push_back(RateBatch{units[g.members[k][0]].p, g.members[k]});
+    call.front = [&](size_t k, grk_amd_coded_block* table, uint64_t* total) -> int {
+        const auto& G = g.members[k];
+        staging.resize(staged_bytes(src, units[G[0]]) * G.size());
+        stage_units(src, units, G, staging.data(), 1);
+        return grk_amd_encode_tiles(ctx, &call.batches[k].p, (uint32_t)G.size(), staging.data(), 0, table, total);
+    };
+    call.write = [&](const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* o, uint64_t ocap) -> int64_t {
+        return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows, coded, flags, o, ocap);
+    };
+    return encode_rate_joint(ctx, call, out, cap, result);
 }
 
 } // extern "C"

@@ -84,99 +84,162 @@ bool surface_direct_allowed()
     return !(e && std::strcmp(e, "0") == 0);
 }
 
+namespace {
+
+// One grk_amd_encode_tiles call of a surface: a unit read in place through its run's layout, or a group's staged units
+struct SurfaceBatch { grk_amd_tile_params p; std::vector<uint32_t> units; bool in_place; size_t group, origin_at; bool counted; };
+
+// A surface resolved, routed and staged for encoding -- what grk_amd_encode_surface and grk_amd_encode_surface_rate share: the
+// units [tile][run] and their groups, each run's route, the staging plan (surface_plan.h), the surface on the device, and the
+// batches in the order they are coded: group after group, a group's in-place units first, then its staged units as one batch.
+struct SurfaceJob {
+    grk_amd_ctx* c;
+    ResolvedSurface rs;
+    std::vector<CompRun> runs;
+    std::vector<grk_amd_tile_params> units;
+    UnitGroups g;
+    std::vector<SurfaceRoute> route;
+    SurfaceStaging st;
+    uint8_t* d_surf = nullptr;
+    std::vector<SurfaceBatch> batches;
+    std::vector<uint64_t> row_at;                            // unit u's rows start at row_at[u]
+
+    int open(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+             const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device)
+    {
+        {
+            const char* why = "";
+            const int rc = resolve_surface(im, base, comp_dx, comp_dy, surface, rs, &why);
+            if (rc) return fail(c, rc, why);
+        }
+        if (rs.bytes > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "surface: it does not fit `cap`");
+        const int64_t nt = grk_amd_layout_num_tiles(im);
+        if (nt < 0) return (int)nt;
+        const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps;
+        runs = comp_runs(nc, base->mct != 0, comp_dx, comp_dy);
+        const uint32_t nr = (uint32_t)runs.size();
+        for (uint32_t t = 0; t < ntiles; ++t)
+            for (uint32_t k = 0; k < nr; ++k) {
+                grk_amd_tile_params p{};
+                int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].first], comp_dy[runs[k].first], t, &p);
+                if (rc) return rc;
+                p.num_comps = (uint16_t)runs[k].count;
+                p.mct = runs[k].mct ? 1 : 0;
+                units.push_back(p);
+                rc = add_unit(g, p);
+                if (rc) return rc;
+            }
+        HIP_TRY(c, hipSetDevice(c->device), "set device");
+        // the surface on the device: the caller's, or a copy of a host surface's extent
+        d_surf = (uint8_t*)const_cast<void*>(pixels);
+        if (!pixels_on_device) {
+            HIP_TRY(c, c->img_pixels.ensure(rs.bytes + 16), "alloc the surface");
+            d_surf = (uint8_t*)c->img_pixels.p;
+            const int rc = copy_h2d(c, d_surf, pixels, rs.bytes); if (rc) return rc;
+        }
+        // each run's route; what is staged (surface_plan.h): the units group after group, within a group run by run, their origins in that order
+        const bool direct = surface_direct_allowed();
+        route.resize(nr);
+        for (uint32_t k = 0; k < nr; ++k)
+            route[k] = plan_surface_run(rs, runs[k], ntiles == 1, false, direct, cap, (uint32_t)((uintptr_t)d_surf & 3u));
+        st = plan_surface_staging(g.members, route, rs, runs, units);
+        if (!st.origins.empty()) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");      // (the buffers below may still be read by an earlier call's kernels)
+            HIP_TRY(c, c->img_tiles.ensure(st.group_bytes), "alloc a group's units");
+            HIP_TRY(c, c->img_rects.ensure(st.origins.size() * 4), "alloc origins");
+            HIP_TRY(c, hipMemcpy(c->img_rects.p, st.origins.data(), st.origins.size() * 4, hipMemcpyHostToDevice), "upload origins");
+        }
+        row_at.assign(units.size() + 1, 0);
+        for (size_t u = 0; u < units.size(); ++u) row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].num_comps;
+        size_t origin_at = 0;
+        for (size_t k = 0; k < g.members.size(); ++k) {
+            for (uint32_t u : g.members[k])
+                if (route[u % nr].in_place) batches.push_back(SurfaceBatch{units[u], {u}, true, k, 0, false});
+            const std::vector<uint32_t>& S = st.staged[k];
+            if (S.empty()) continue;
+            batches.push_back(SurfaceBatch{units[S[0]], S, false, k, origin_at, false});
+            origin_at += S.size();
+        }
+        return GRK_AMD_OK;
+    }
+
+    // batch b through grk_amd_encode_tiles: the surface itself through the run's layout, or staged planes (cut out of the surface
+    // here, every time: the groups share the staging buffer) in the default one -- never the caller's setting, which the public
+    // call puts back (KeepLayout)
+    int front(size_t b, grk_amd_coded_block* table, uint64_t* total)
+    {
+        SurfaceBatch& B = batches[b];
+        const void* d_px;
+        if (B.in_place) {
+            const SurfaceRoute& r = route[B.units[0] % runs.size()];
+            c->enc_layout = r.layout;
+            d_px = d_surf + r.at;
+        } else {
+            const size_t unit_size = (size_t)B.p.tile_w * B.p.tile_h * B.p.num_comps * rs.bps;
+            for (const RunSegment& s : st.segments[B.group]) {
+                const int rc = queue_surface_kernel(c, false, rs, runs[s.run], d_surf, (uint8_t*)c->img_tiles.p + s.first * unit_size, s.count,
+                                                    B.p.tile_w, B.p.tile_h, (const uint32_t*)c->img_rects.p + 2 * (B.origin_at + s.first));
+                if (rc) return rc;
+            }
+            c->enc_layout = grk_amd_pixel_layout{};
+            d_px = c->img_tiles.p;
+        }
+        const int rc = grk_amd_encode_tiles(c, &B.p, (uint32_t)B.units.size(), d_px, 1, table, total);
+        if (rc) return rc;
+        if (!B.counted) { c->surf_counters[B.in_place ? 0 : 1] += B.units.size(); B.counted = true; }
+        return GRK_AMD_OK;
+    }
+};
+
+} // namespace
+
 extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                           const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
                                           const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap)
 {
     if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out) return GRK_AMD_ERR_INVALID;
-    ResolvedSurface rs;
-    {
-        const char* why = "";
-        const int rc = resolve_surface(im, base, comp_dx, comp_dy, surface, rs, &why);
-        if (rc) return fail(c, rc, why);
-    }
-    if (rs.bytes > cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "surface: it does not fit `cap`");
-    const int64_t nt = grk_amd_layout_num_tiles(im);
-    if (nt < 0) return nt;
-    const uint32_t ntiles = (uint32_t)nt, nc = base->num_comps, bps = rs.bps;
-    const std::vector<CompRun> runs = comp_runs(nc, base->mct != 0, comp_dx, comp_dy);
-    const uint32_t nr = (uint32_t)runs.size();
-    std::vector<grk_amd_tile_params> units;                  // [tile][run]
-    UnitGroups g;
-    for (uint32_t t = 0; t < ntiles; ++t)
-        for (uint32_t k = 0; k < nr; ++k) {
-            grk_amd_tile_params p{};
-            int rc = grk_amd_layout_tile_comp(im, base, comp_dx[runs[k].first], comp_dy[runs[k].first], t, &p);
-            if (rc) return rc;
-            p.num_comps = (uint16_t)runs[k].count;
-            p.mct = runs[k].mct ? 1 : 0;
-            units.push_back(p);
-            rc = add_unit(g, p);
-            if (rc) return rc;
-        }
-    HIP_TRY(c, hipSetDevice(c->device), "set device");
-    // the surface on the device: the caller's, or a copy of a host surface's extent
-    uint8_t* d_surf = (uint8_t*)const_cast<void*>(pixels);
-    if (!pixels_on_device) {
-        HIP_TRY(c, c->img_pixels.ensure(rs.bytes + 16), "alloc the surface");
-        d_surf = (uint8_t*)c->img_pixels.p;
-        const int rc = copy_h2d(c, d_surf, pixels, rs.bytes); if (rc) return rc;
-    }
-    // each run's route; what is staged (surface_plan.h): the units group after group, within a group run by run, their origins in that order
-    const bool direct = surface_direct_allowed();
-    std::vector<SurfaceRoute> route(nr);
-    for (uint32_t k = 0; k < nr; ++k)
-        route[k] = plan_surface_run(rs, runs[k], ntiles == 1, false, direct, cap, (uint32_t)((uintptr_t)d_surf & 3u));
-    const SurfaceStaging st = plan_surface_staging(g.members, route, rs, runs, units);
-    if (!st.origins.empty()) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");      // (the buffers below may still be read by an earlier call's kernels)
-        HIP_TRY(c, c->img_tiles.ensure(st.group_bytes), "alloc a group's units");
-        HIP_TRY(c, c->img_rects.ensure(st.origins.size() * 4), "alloc origins");
-        HIP_TRY(c, hipMemcpy(c->img_rects.p, st.origins.data(), st.origins.size() * 4, hipMemcpyHostToDevice), "upload origins");
-    }
-    // the batches read the surface through a run's layout, or staged planes in the default one: never the caller's setting
+    SurfaceJob job{c};
+    int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);
+    if (rc) return rc;
     KeepLayout keep{c->enc_layout, c->enc_layout};
-    std::vector<uint64_t> row_at(units.size() + 1, 0);       // unit u's rows start at row_at[u]
-    for (size_t u = 0; u < units.size(); ++u) row_at[u + 1] = row_at[u] + (uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].num_comps;
-    std::vector<grk_amd_coded_block> rows(row_at[units.size()]), table;
+    std::vector<grk_amd_coded_block> rows(job.row_at.back()), table;
     std::vector<uint8_t> coded;
-    // one batch: `batch` units of parameters p from d_px, their rows and bytes to the host
-    auto encode_batch = [&](const grk_amd_tile_params& p, const std::vector<uint32_t>& batch, const void* d_px) -> int {
-        const uint64_t bpu = (uint64_t)g.geoms[g.of[batch[0]]].blocks_per_comp * p.num_comps;
+    // every batch's rows and bytes to the host
+    for (size_t b = 0; b < job.batches.size(); ++b) {
+        const std::vector<uint32_t>& batch = job.batches[b].units;
+        const uint64_t bpu = job.row_at[batch[0] + 1] - job.row_at[batch[0]];
         table.resize(bpu * batch.size());
         uint64_t total = 0;
-        int rc = grk_amd_encode_tiles(c, &p, (uint32_t)batch.size(), d_px, 1, table.data(), &total);
+        rc = job.front(b, table.data(), &total);
         if (rc) return rc;
         const size_t at = coded.size();
         coded.resize(at + total);
         rc = grk_amd_fetch_coded(c, coded.data() + at, total);
         if (rc) return rc;
         for (size_t i = 0; i < batch.size(); ++i)
-            for (uint64_t b = 0; b < bpu; ++b) { rows[row_at[batch[i]] + b] = table[i * bpu + b]; rows[row_at[batch[i]] + b].offset += at; }
-        return GRK_AMD_OK;
-    };
-    size_t origin_at = 0;
-    for (size_t k = 0; k < g.members.size(); ++k) {
-        for (uint32_t u : g.members[k]) {
-            const SurfaceRoute& r = route[u % nr];
-            if (!r.in_place) continue;
-            c->enc_layout = r.layout;
-            const int rc = encode_batch(units[u], std::vector<uint32_t>{u}, d_surf + r.at); if (rc) return rc;
-            ++c->surf_counters[0];
-        }
-        const std::vector<uint32_t>& S = st.staged[k];
-        if (S.empty()) continue;
-        const grk_amd_tile_params& p = units[S[0]];
-        const size_t unit_size = (size_t)p.tile_w * p.tile_h * p.num_comps * bps;
-        for (const RunSegment& s : st.segments[k]) {
-            const int rc = queue_surface_kernel(c, false, rs, runs[s.run], d_surf, (uint8_t*)c->img_tiles.p + s.first * unit_size, s.count,
-                                                p.tile_w, p.tile_h, (const uint32_t*)c->img_rects.p + 2 * (origin_at + s.first));
-            if (rc) return rc;
-        }
-        c->enc_layout = grk_amd_pixel_layout{};
-        const int rc = encode_batch(p, S, c->img_tiles.p); if (rc) return rc;
-        c->surf_counters[1] += S.size();
-        origin_at += S.size();
+            for (uint64_t k = 0; k < bpu; ++k) { rows[job.row_at[batch[i]] + k] = table[i * bpu + k]; rows[job.row_at[batch[i]] + k].offset += at; }
     }
     return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, out_cap);
+}
+
+extern "C" int64_t grk_amd_encode_surface_rate(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                               const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                               const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                               const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out || !rate) return GRK_AMD_ERR_INVALID;
+    { const int rr = rate_refusal(c, rate); if (rr) return rr; }
+    flags |= GRK_AMD_CS_BLOCK_MSBS;
+    SurfaceJob job{c};
+    const int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);
+    if (rc) return rc;
+    KeepLayout keep{c->enc_layout, c->enc_layout};
+    RateJointCall call{base, rate, {}, {}, {}, {}};
+    for (size_t u = 0; u < job.units.size(); ++u) call.unit_blocks.push_back(job.row_at[u + 1] - job.row_at[u]);
+    for (const SurfaceBatch& B : job.batches) call.batches.push_back(RateBatch{B.p, B.units});
+    call.front = [&](size_t b, grk_amd_coded_block* table, uint64_t* total) { return job.front(b, table, total); };
+    call.write = [&](const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* o, uint64_t ocap) -> int64_t {
+        return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows, coded, flags, o, ocap);
+    };
+    return encode_rate_joint(c, call, out, out_cap, result);
 }

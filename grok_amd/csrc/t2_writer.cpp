@@ -491,8 +491,9 @@ extern "C" int64_t grk_amd_write_codestream_subsampled(const grk_amd_image_layou
                                                        const grk_amd_coded_block* table, const uint8_t* coded, uint32_t flags,
                                                        uint8_t* out, uint64_t cap)
 {
-    if (!base || !table || !coded || !out || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
-    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (no encode of sub-sampled components drops bit-planes)
+    // (out == NULL: the file's length alone, nothing written and `coded` not read; GRK_AMD_CS_BLOCK_MSBS goes to write_packet with
+    //  the other flags)
+    if (!base || !table || (out && !coded) || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
     Layout l;
     int rc = check_layout(im, l);
     if (rc != GRK_AMD_OK) return rc;

@@ -536,20 +536,43 @@ int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, c
  *                               GRK_AMD_CS_BLOCK_MSBS; the blocks' budget is the target less what the file spends beside its blocks,
  *                               lowered by the overshoot and tried again (at most 4 rounds) when the written file is still too
  *                               long.  A target at or above the plain file's size gives d = 0 everywhere and the bytes of
- *                               grk_amd_encode_image under GRK_AMD_IMAGE_T2=host, whatever the tiling.  Tiles of several geometries:
- *                               each group of tiles gets its share of the budget by sample count, capped at its plain bytes (what
- *                               it cannot use goes to the other groups); a limitation: no common slope across groups yet.
- *   grk_amd_rate_tables         the tables of the latest of those calls (of its last geometry group), to host memory: which 0 L
+ *                               grk_amd_encode_image under GRK_AMD_IMAGE_T2=host, whatever the tiling.  Tiles of several geometries,
+ *                               grk_amd_rate::joint = 0: each group of tiles gets its share of the budget by sample count, capped at
+ *                               its plain bytes (what it cannot use goes to the other groups), and runs the allocator alone on its
+ *                               own tables, made again in every round.  joint = 1: the joint tables below.
+ *   grk_amd_encode_image_subsampled_rate, grk_amd_encode_surface_rate
+ *                               the same for an image with sub-sampled components (pixels as for grk_amd_encode_image_subsampled)
+ *                               and for a video surface (resolved, routed and staged exactly as grk_amd_encode_surface does,
+ *                               GRK_AMD_SURFACE_DIRECT included): the file, written by grk_amd_write_codestream_subsampled with
+ *                               GRK_AMD_CS_BLOCK_MSBS, is at most target_bytes; a target at or above the plain file's size gives the
+ *                               bytes of grk_amd_encode_image_subsampled / grk_amd_encode_surface.  Always over joint tables.
+ *   JOINT TABLES                one L, E, W over every block of the image, in the order in which the file's writer takes the table:
+ *                               tile by tile (sub-sampled: within a tile run by run, within a run component by component).  The
+ *                               order depends neither on how the units are grouped into batches nor on whether a surface unit is
+ *                               coded in place or staged, and neither do the file's bytes.  Every batch's statistics and trial
+ *                               launches write their columns into these tables, once per call; the allocator then runs once per
+ *                               round over all of them: ONE multiplier lambda for every block of every component, the fill in
+ *                               joint order.  W_b is the weight of the unit's own geometry, and the distortion the sum over every
+ *                               component's own samples (the reference's convention): a sub-sampled component's samples carry NO
+ *                               factor dx * dy for the area they stand for.
+ *   grk_amd_rate_tables         the tables of the latest of those calls (joint: of the whole image; else of its last geometry
+ *                               group), to host memory: which 0 L
  *                               uint32 [Dmax + 2][nblocks], 1 E uint64 [Dmax + 2][nblocks] (row Dmax + 1: SKIP), 2 W double
  *                               [nblocks], 3 the chosen drop bytes uint8 [nblocks] (0xFF: SKIP); GRK_AMD_ERR_OVERFLOW: cap_bytes too small
+ *   grk_amd_rate_num_blocks     nblocks of those tables (0: there are none)
+ *   grk_amd_rate_last_budget    the blocks' budget the allocator last ran with (a whole-image call: the last round's -- the target
+ *                               less what the round before spent beside its blocks)
+ *   grk_amd_rate_unit_rows      the units the tables are over (joint: the image's units; else the batch's tiles): returns their
+ *                               number, first_row[u] (up to cap entries) = unit u's first row
  * GRK_AMD_ERR_OVERFLOW (the reason in grk_amd_last_error): the target is below what SKIP everywhere -- without allow_skip: Dmax
- * everywhere -- takes, or the four rounds ran out with the file still too long (the message says which).  GRK_AMD_ERR_UNSUPPORTED: while pipelining is on.  Not offered: sub-sampled images and surfaces, the node, the
- * plugin, Tier-2 on the device, pipelined sequences, several layers. */
+ * everywhere -- takes, or the four rounds ran out with the file still too long (the message says which).  GRK_AMD_ERR_UNSUPPORTED: while pipelining is on.  Not offered: per-component visual
+ * weights, the node, the plugin, Tier-2 on the device, pipelined sequences, several layers. */
 typedef struct grk_amd_rate {
     uint64_t target_bytes;   /* the blocks' bytes for grk_amd_encode_tiles_rate; the whole file for grk_amd_encode_image_rate */
     uint8_t  max_drop;       /* Dmax, 0 = default 6, at most 12 */
     uint8_t  allow_skip;
-    uint8_t  reserved[6];
+    uint8_t  joint;          /* grk_amd_encode_image_rate: 1 = joint tables; the sub-sampled and surface calls are always joint */
+    uint8_t  reserved[5];
 } grk_amd_rate;
 typedef struct grk_amd_rate_result {
     uint64_t block_bytes;    /* the chosen blocks' bytes, final */
@@ -567,6 +590,9 @@ int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* 
                                   const void* pixels, uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t cap,
                                   grk_amd_rate_result* result);
 int grk_amd_rate_tables(grk_amd_ctx* ctx, int which, void* dst, uint64_t cap_bytes);
+uint64_t grk_amd_rate_num_blocks(grk_amd_ctx* ctx);
+uint64_t grk_amd_rate_last_budget(grk_amd_ctx* ctx);
+int grk_amd_rate_unit_rows(grk_amd_ctx* ctx, uint64_t* first_row, uint32_t cap);
 
 /* ---- sub-sampled components (4:2:2, 4:2:0 ...; SIZ XRsiz / YRsiz, grok.h grk_image_comp::dx / dy) ------------------------------------
  * Component c of a tile [x0, x1) x [y0, y1) of the reference grid covers [ceil(x0 / dx_c), ceil(x1 / dx_c)) x [ceil(y0 / dy_c),
@@ -577,7 +603,7 @@ int grk_amd_rate_tables(grk_amd_ctx* ctx, int which, void* dst, uint64_t cap_byt
  * other factors base->mct is switched off, as the reference does: CodeStreamCompress.cpp:434-447); the codestream == grk_compress's for the same image (one precinct per resolution or
  * any precinct sizes, the five progression orders, SOP / EPH / TLM / PLT as for any image).
  * grk_amd_write_codestream_subsampled: the table's rows tile by tile, within a tile component by component, each component with the
- * grk_amd_tile_num_blocks() rows of ITS rectangle (num_comps = 1). */
+ * grk_amd_tile_num_blocks() rows of ITS rectangle (num_comps = 1); out == NULL: only the file's length is returned (`coded` is not read). */
 int grk_amd_layout_tile_comp(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t dx, uint32_t dy,
                              uint32_t tile_index, grk_amd_tile_params* out);
 int64_t grk_amd_write_codestream_subsampled(const grk_amd_image_layout* im, const grk_amd_tile_params* base,
@@ -587,6 +613,10 @@ int64_t grk_amd_write_codestream_subsampled(const grk_amd_image_layout* im, cons
 int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                         const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
                                         uint8_t* out, uint64_t cap);
+/* ... in a file of at most rate->target_bytes (rate-targeted encodes, above) */
+int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                             const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
+                                             const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result);
 
 /* The same with the optional pointer marker segments of the reference's encoder (grk_compress -L / -X, grok.h
  * grk_cparameters::writePLT / writeTLM; codestream/markers/LengthMarkers.cpp): TLM in the main header (one-byte tile index +
@@ -601,7 +631,7 @@ int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_amd_image_la
 /* The zero-bit-plane tag trees coded from the rows' own missing_msbs (T.800 B.10.2 in its general form) instead of the constant
  * Kmax - 1 every block of a plain encode has: what a table from grk_amd_encode_tiles_rate / grk_amd_stage_ht_encode_drops needs.
  * Without the flag every byte is as before; with it and every row at Kmax - 1 as well.  Taken by the host writers
- * (grk_amd_write_codestream_ex / _layout, grk_amd_write_tile_part; grk_amd_write_main_header accepts it, the header does not
+ * (grk_amd_write_codestream_ex / _layout / _subsampled, grk_amd_write_tile_part; grk_amd_write_main_header accepts it, the header does not
  * change); grk_amd_plan_tile_part and grk_amd_assemble_device(_async) return GRK_AMD_ERR_UNSUPPORTED. */
 #define GRK_AMD_CS_BLOCK_MSBS 16u
 #define GRK_AMD_CS_PROG_SHIFT 8
@@ -857,6 +887,14 @@ int grk_amd_surface_plan(const grk_amd_image_layout* im, const grk_amd_tile_para
 int64_t grk_amd_encode_surface(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
                                const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap);
+/* ... in a file of at most rate->target_bytes (rate-targeted encodes, above: always over joint tables).  The same resolution, routes
+ * and staging; a unit's pixels are cut out again for a round's final launch when another batch has used the context since; the
+ * counters count a unit once per call.  The file equals grk_amd_encode_image_subsampled_rate's for the same samples as tight planes
+ * and the same target, in place or staged. */
+int64_t grk_amd_encode_surface_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                    const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                    const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_rate* rate,
+                                    uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);
 /* Codestream -> surface: component c's samples on the surface are plane c of grk_amd_decode_image, every component at its own size
  * (no view, no upsampling: the context's pixel layouts and grk_amd_set_decode_upsample are neither consulted nor changed), and every
  * byte of [pixels, pixels + cap) that is no sample of a component keeps its value (a host surface travels both ways for that).  A

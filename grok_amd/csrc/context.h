@@ -132,6 +132,9 @@ struct grk_amd_ctx {
     bool dec_planes16 = true;                               // 16-bit planes between K5b and K6 for 8-bit reversible HT tiles
                                                             // (GRK_AMD_DEC_PLANES16=0 / grk_amd_set_decode_planes16: int32)
     int dwt_pk = 1;                                         // packed int16 pairs in K2 / K6 where the range allows (GRK_AMD_DWT_PK=0: 32-bit)
+    bool k3_alternate = true;                               // pipelined encodes: K3's classes on the two side streams in turn (GRK_AMD_K3_ALT=0: fixed)
+    uint32_t num_cus = 0;                                   // compute units of the device (0: not known)
+    uint32_t k3_parity = 0;                                 // ... which way round this frame; flips per pipelined encode, grk_amd_set_pipelining resets it
     int dwt_xcd = 1;                                        // XCD-aware workgroup order in K2 / K6 (GRK_AMD_DWT_XCD=0: plain)
     bool fuse_egress = true;                                // K7 inside the last inverse DWT level (GRK_AMD_FUSE_EGRESS=0: separate)
     bool planes16 = true;                                   // int16 planes between K2 and K3 where the range allows (GRK_AMD_PLANES16=0: never)

@@ -239,6 +239,7 @@ int create_context(int device_id, int verbose, bool decode_only, grk_amd_ctx** o
     if (hipSetDevice(device_id) != hipSuccess) return GRK_AMD_ERR_NO_DEVICE;
     auto* c = new grk_amd_ctx();
     c->device = device_id; c->verbose = verbose;
+    { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->num_cus = (uint32_t)cus; }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return GRK_AMD_ERR_NO_DEVICE; }
     c->own_stream = true;
     {   // side stream for K3 of the top resolution (lowest priority: the DWT chain on the main stream is the critical path)
@@ -248,6 +249,7 @@ int create_context(int device_id, int verbose, bool decode_only, grk_amd_ctx** o
         if (const char* ef = getenv("GRK_AMD_FUSE_EGRESS")) c->fuse_egress = atoi(ef) != 0;
         if (const char* ex = getenv("GRK_AMD_DWT_XCD")) c->dwt_xcd = atoi(ex) != 0;
         if (const char* ex = getenv("GRK_AMD_DWT_PK")) c->dwt_pk = atoi(ex) != 0;
+        if (const char* ek = getenv("GRK_AMD_K3_ALT")) c->k3_alternate = atoi(ek) != 0;
         if (const char* ed = getenv("GRK_AMD_DEC_PLANES16")) c->dec_planes16 = atoi(ed) != 0;
         if (const char* el = getenv("GRK_AMD_LDS_CAP")) c->lds_cap = atoi(el) != 0;
         if (const char* ef2 = getenv("GRK_AMD_FRAME_STREAMS")) c->frame_streams = atoi(ef2);

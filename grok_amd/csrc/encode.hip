@@ -63,16 +63,23 @@ int make_ht_args(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool h16
 int launch_ht_at(grk_amd_ctx* c, const HtArgs& h, bool overlapped, HtPoint at, bool one_level)
 {
     for (uint32_t k = 0; k < h.num_classes; ++k) {
-        const HtStream to = ht_class_stream(c->ht_classes[k].role, overlapped, c->pipelining, at, one_level);
+        const HtStream to = ht_class_stream(c->ht_classes[k].role, overlapped, c->pipelining, at, one_level, c->k3_parity);
         if (to == HtStream::NotHere) continue;
         if (to == HtStream::Main) { HIP_TRY(c, launch_ht_classes(h, k, k + 1, c->stream), "launch ht encode"); continue; }
         hipStream_t st = to == HtStream::Side ? c->side : c->side2;
         HIP_TRY(c, hipStreamWaitEvent(st, c->ev_level0, 0), "side stream waits for the level");
         ScopedTimer tt(c, st == c->side ? 4 : 8, st);
-        // (consecutive encodes pipelined: the top class is still running when the next encode's level 0 arrives)
+        // (consecutive encodes pipelined: the top class is still running when the next encode's level 0 arrives; the frames take
+        //  the two side streams in turn, c->k3_parity.  Whichever way round, every launch of the frame on a side stream is queued
+        //  by the end of run_dwt's last level, which then records ev_side on `side` AND ev_side2 on `side2`: the pair of events of
+        //  the frame's buffer set covers its last launch on each stream, and grk_amd_encode_tiles waits for both before level 0
+        //  reuses the set)
         HtArgs hs = h;
         hs.room = c->pipelining ? 1 : 0;
-        HIP_TRY(c, launch_ht_classes(hs, k, k + 1, st), "launch ht encode (side stream)");
+        // pipelined frames in turn: a fallback launch sits between a class and the next frame's launch on its stream, and an empty one
+        // of up to 1024 workgroups of worst-case LDS costs 10-14 us of stream time beside K3 -- one workgroup per CU walks the list
+        const uint32_t fb = c->pipelining && c->k3_alternate && c->num_cus ? c->num_cus : kHtFallbackGrid;
+        HIP_TRY(c, launch_ht_classes(hs, k, k + 1, st, fb), "launch ht encode (side stream)");
     }
     return GRK_AMD_OK;
 }
@@ -469,6 +476,7 @@ int grk_amd_encode_tiles(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t 
             rc = run_dwt(c, nplanes, c->p0.p, c->p1.p, nullptr, ntiles, ov ? &h : nullptr); if (rc) return rc;
         }
         rc = run_ht(c, h, ov); if (rc) return rc;
+        if (ov && c->pipelining && c->k3_alternate) c->k3_parity ^= 1u;      // the next pipelined frame: the side streams the other way round
     }
     if (table || total) return grk_amd_fetch_table(c, table, total);
     return GRK_AMD_OK;
@@ -516,6 +524,7 @@ int grk_amd_set_pipelining(grk_amd_ctx* c, int on)
     c->pipelining = on != 0 && c->side != nullptr && c->side2 != nullptr;
     c->pipe_depth = std::min(std::max(on, 1) + 1, grk_amd_ctx::kMaxAltSets + 1);
     c->alt_head = 0;
+    c->k3_parity = 0;
     return rc;
 }
 } // extern "C"

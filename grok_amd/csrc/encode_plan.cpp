@@ -144,11 +144,13 @@ HtArenaPlan plan_ht_arena(uint64_t nblocks, uint64_t raw_bytes, uint32_t ntiles,
 }
 
 // ---- which class goes to which stream, and when ------------------------------------------------------------------------------------
-HtStream ht_class_stream(HtRole role, bool overlapped, bool pipelined, HtPoint at, bool one_level)
+HtStream ht_class_stream(HtRole role, bool overlapped, bool pipelined, HtPoint at, bool one_level, uint32_t parity)
 {
+    const bool swap = overlapped && pipelined && (parity & 1u);
     for (const HtScheduleRow& r : kHtSchedule) {
         if (r.role != role || r.overlapped != overlapped || (r.pipelined >= 0 && (r.pipelined != 0) != pipelined)) continue;
-        if (r.at == at || (one_level && at == HtPoint::AfterLevel0 && r.at == HtPoint::AfterLastLevel)) return r.to;
+        if (r.at == at || (one_level && at == HtPoint::AfterLevel0 && r.at == HtPoint::AfterLastLevel))
+            return !swap ? r.to : r.to == HtStream::Side ? HtStream::Side2 : r.to == HtStream::Side2 ? HtStream::Side : r.to;
     }
     return HtStream::NotHere;
 }

@@ -131,7 +131,12 @@ inline constexpr HtScheduleRow kHtSchedule[] = {
     {HtRole::RestSmall, true,   1, HtPoint::AfterLastLevel, HtStream::Side2},
 };
 // one_level: L == 1, level 0 is the last level as well -- AfterLevel0 then answers for both points and AfterLastLevel is not asked
-HtStream ht_class_stream(HtRole role, bool overlapped, bool pipelined, HtPoint at, bool one_level);
+// parity (pipelined overlapped encodes only; else ignored): consecutive frames take the two side streams in turn -- parity 0 is the
+// table above, parity 1 the table with Side and Side2 exchanged.  Launches on one stream do not overlap, so with a fixed table
+// top(n + 1) queues behind the last wave of top(n) and its fallback launch: K3's wave supply has a hole at every frame boundary.
+// In turn, top(n + 1) queues behind rest(n), which ended long before, and rest(n + 1) behind top(n), where it has slack.  Within
+// a frame Top and Rest (and the Small / Big pairs as the table has them) stay on different streams in either parity.
+HtStream ht_class_stream(HtRole role, bool overlapped, bool pipelined, HtPoint at, bool one_level, uint32_t parity = 0);
 
 // ---- the call's route ----------------------------------------------------------------------------------------------------------------
 // 16-bit planes are safe when no coefficient of any level can leave int16.  Bound (5/3, L1 norms of the analysis

@@ -108,7 +108,9 @@ __device__ __forceinline__ void ht_alloc_reset(unsigned long long* flagbuf, uint
 }
 hipError_t launch_ht_encode(const HtArgs& a, hipStream_t s);          // allocator reset + every class
 hipError_t launch_ht_alloc_init(const HtArgs& a, hipStream_t s);
-hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hipStream_t s);   // classes [first, last)
+// fallback_grid: workgroups of a class's fallback launch at most (they walk the class's list)
+constexpr uint32_t kHtFallbackGrid = 1024;
+hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hipStream_t s, uint32_t fallback_grid = kHtFallbackGrid);   // classes [first, last)
 // the same through the instances that take a per-block drop: drops[ntiles * blocks_per_tile] (device), tile-major in table order, each
 // 0 .. 254 bit-planes left out (clamped to Kmax - 1) or kHtDropSkip; inst: plan_ht_drop_instance (encode_plan.h) of a's plane form
 hipError_t launch_ht_classes_drops(const HtArgs& a, uint32_t first, uint32_t last, const uint8_t* drops, const HtDropInstance& inst, hipStream_t s);

@@ -1491,7 +1491,7 @@ hipError_t launch_ht_alloc_init(const HtArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hipStream_t s)
+hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hipStream_t s, uint32_t fallback_grid)
 {
     const uint32_t* vlc_tab = nullptr;
     hipError_t e = ensure_tables(&vlc_tab);
@@ -1527,7 +1527,7 @@ hipError_t launch_ht_classes(const HtArgs& a, uint32_t first, uint32_t last, hip
         else                                    hipLaunchKernelGGL((ht_encode_kernel<false, false, false>), dim3(grid), dim3(64), shmem, s, b, L, k);
         // the blocks that outgrew the capped buffers: a small fixed grid walks the list (with nothing on it -- natural
         // images at the top resolution -- its workgroups leave at once)
-        if (use_cap) GRK_HT(ht_encode_fallback_kernel, std::min<uint32_t>(grid, 1024u), shmem_full, full);
+        if (use_cap) GRK_HT(ht_encode_fallback_kernel, std::min<uint32_t>(grid, std::max(fallback_grid, 1u)), shmem_full, full);
 #undef GRK_HT
     }
     return hipGetLastError();

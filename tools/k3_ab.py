@@ -2,11 +2,16 @@
     python tools/k3_ab.py [--rounds R] variant ...     variant = head | a name under build/abl/<name>/libgrok_amd.so
 Per build and round: K3 alone (HIP events, grk_amd_set_overlap(0), 60 launches), the DWT family alone, the pipelined 8K step as
 bench.py times it (three frames in rotation, 5 regions of 20 steps behind 40 pre-warm frames: median / min / max), cfg3's K3 alone,
-and the md5 of the 8K codestream (must stay 7e5275ef...).  The pixels are generated once and shared through /tmp."""
+and the md5 of the 8K codestream (must stay 7e5275ef...).  The pixels are generated once and shared through /tmp.
+A variant may carry environment switches, build@ENV=VAL,ENV=VAL; `fixed` is the head build with GRK_AMD_K3_ALT=0 (K3's classes of
+pipelined frames on fixed side streams and fallback launches of up to 1024 workgroups: the schedule before the frames took the
+streams in turn), so one call alternates the two schedules and a parent build on one box --
+    python tools/k3_ab.py --rounds 4 parent fixed head"""
 import hashlib, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 PIX = "/tmp/k3_ab_pixels_%s.npy"
+SWITCHES = {"fixed": "head@GRK_AMD_K3_ALT=0"}
 
 
 def pixels():
@@ -99,13 +104,15 @@ if __name__ == "__main__":
     res = {}
     for r in range(rounds):
         for v in args or ["head"]:
-            name, _, envs = v.partition("@")                 # build@ENV=VAL,ENV=VAL
+            name, _, envs = SWITCHES.get(v, v).partition("@")                 # build@ENV=VAL,ENV=VAL
             env = dict(os.environ)
             env.update(dict(kv.split("=", 1) for kv in envs.split(",") if kv))
             lib = os.path.join(ROOT, "grok_amd", "lib", "libgrok_amd.so") if name == "head" else os.path.join(ROOT, "build", "abl", name, "libgrok_amd.so")
             q = subprocess.run([sys.executable, __file__, "--one", lib, "1" if r == 0 else "0"], capture_output=True, text=True, env=env)
             line = (q.stdout.strip().splitlines() or ["FAILED " + q.stderr[-600:]])[-1]
             print("round %d %-28s %s" % (r, v, line), flush=True)
+            if q.returncode < 0 or q.returncode in (124, 134, 137, 139):       # a signal (abort, fault, time limit): nothing more on this GPU
+                sys.exit("round %d %s ended with %d: stopping" % (r, v, q.returncode))
             try:
                 res.setdefault(v, []).append(json.loads(line))
             except Exception:

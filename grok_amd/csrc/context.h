@@ -132,6 +132,7 @@ struct grk_amd_ctx {
     bool dec_planes16 = true;                               // 16-bit planes between K5b and K6 for 8-bit reversible HT tiles
                                                             // (GRK_AMD_DEC_PLANES16=0 / grk_amd_set_decode_planes16: int32)
     int dwt_pk = 1;                                         // packed int16 pairs in K2 / K6 where the range allows (GRK_AMD_DWT_PK=0: 32-bit)
+    int dwt_pair = 1;                                       // levels 0 and 1 of the packed 5/3 encoder in one launch where plan_dwt_pair has one (GRK_AMD_DWT_PAIR=0: level by level)
     bool k3_alternate = true;                               // pipelined encodes: K3's classes on the two side streams in turn (GRK_AMD_K3_ALT=0: fixed)
     uint32_t num_cus = 0;                                   // compute units of the device (0: not known)
     uint32_t k3_parity = 0;                                 // ... which way round this frame; flips per pipelined encode, grk_amd_set_pipelining resets it

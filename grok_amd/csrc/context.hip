@@ -249,6 +249,7 @@ int create_context(int device_id, int verbose, bool decode_only, grk_amd_ctx** o
         if (const char* ef = getenv("GRK_AMD_FUSE_EGRESS")) c->fuse_egress = atoi(ef) != 0;
         if (const char* ex = getenv("GRK_AMD_DWT_XCD")) c->dwt_xcd = atoi(ex) != 0;
         if (const char* ex = getenv("GRK_AMD_DWT_PK")) c->dwt_pk = atoi(ex) != 0;
+        if (const char* ex = getenv("GRK_AMD_DWT_PAIR")) c->dwt_pair = atoi(ex) != 0;
         if (const char* ek = getenv("GRK_AMD_K3_ALT")) c->k3_alternate = atoi(ek) != 0;
         if (const char* ed = getenv("GRK_AMD_DEC_PLANES16")) c->dec_planes16 = atoi(ed) != 0;
         if (const char* el = getenv("GRK_AMD_LDS_CAP")) c->lds_cap = atoi(el) != 0;

@@ -40,6 +40,10 @@ struct DwtPkKey {        // dwt53_pk_kernel<NC, PX, NT, CH>
     uint8_t nc, px; uint16_t nt; uint8_t ch;
     constexpr uint32_t code() const { return nc | px << 3 | ch << 5 | (uint32_t)nt << 8; }
 };
+struct DwtPairKey {      // pair::dwt53_pk_kernel<NC, PX, NT>
+    uint8_t nc, px; uint16_t nt;
+    constexpr uint32_t code() const { return nc | px << 3 | (uint32_t)nt << 8; }
+};
 struct IdwtKey {         // idwt_level_kernel<F97, NC, PXO, H16, STR>
     bool f97; uint8_t nc, pxo; bool h16, str;
     constexpr uint32_t code() const { return (uint32_t)f97 | nc << 1 | pxo << 4 | (uint32_t)h16 << 6 | (uint32_t)str << 7; }
@@ -76,6 +80,9 @@ struct IdwtInstance { bool packed; IdwtKey k; IdwtPkKey pk; uint32_t grid_x; }; 
     X(1, 1, 128, 1) X(1, 1, 256, 1) X(3, 1, 128, 3) X(3, 1, 256, 3) X(1, 1, 128, 3) X(1, 1, 256, 3)                               \
     X(3, 1, 128, 4) X(3, 1, 256, 4) X(1, 1, 128, 4) X(1, 1, 256, 4)                                                               \
     X(3, 1, 128, 0) X(1, 1, 128, 0) X(3, 1, 256, 0) X(1, 1, 256, 0)
+// K2, two packed 5/3 levels in one launch (pair::dwt53_pk_kernel): the triple from 8-bit pixels in the default layout
+#define GRK_DWT_PAIR_INSTANCES(X) /* NC, PX, NT */                                                                                \
+    X(3, 1, 128) X(3, 1, 256)
 // K6, 32-bit: every level but the fused one (NC 1, PXO 0); the last level to 8- / 16-bit pixels (PXO 1 / 2) in the default layout
 // or a layout of the caller's (STR)
 #define GRK_IDWT_INSTANCES(X) /* F97, NC, PXO, H16, STR */                                                                        \
@@ -99,6 +106,7 @@ struct IdwtInstance { bool packed; IdwtKey k; IdwtPkKey pk; uint32_t grid_x; }; 
 #define GRK_INSTANCE_ROW(...) {__VA_ARGS__},
 inline constexpr DwtKey    kDwtInstances[]    = {GRK_DWT_INSTANCES(GRK_INSTANCE_ROW)};
 inline constexpr DwtPkKey  kDwtPkInstances[]  = {GRK_DWT_PK_INSTANCES(GRK_INSTANCE_ROW)};
+inline constexpr DwtPairKey kDwtPairInstances[] = {GRK_DWT_PAIR_INSTANCES(GRK_INSTANCE_ROW)};
 inline constexpr IdwtKey   kIdwtInstances[]   = {GRK_IDWT_INSTANCES(GRK_INSTANCE_ROW)};
 inline constexpr IdwtPkKey kIdwtPkInstances[] = {GRK_IDWT_PK_INSTANCES(GRK_INSTANCE_ROW)};
 inline constexpr EgressKey kEgressInstances[] = {GRK_EGRESS_INSTANCES(GRK_INSTANCE_ROW)};

@@ -121,9 +121,22 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
         const DwtLevelShape shape = plan_dwt_level(DwtLevelDesc{a.cw, a.ch, a.px, a.py, a.in_stride, a.m_stride, a.h16 != 0, a.pk != 0,
                                                                 a.irreversible != 0, a.px_lay, a.px_chan, a.px_row, zslots, fused, r.bytes});
         a.seg_pairs = shape.seg_pairs;
+        // levels l and l + 1 in one launch where the planner has a pair for them (plan_dwt_pair, encode_plan.h; GRK_AMD_DWT_PAIR=0: never)
+        uint32_t last = l;                             // the last level this turn's launch covers
+        const DwtPairShape pair = plan_dwt_pair_at(g, l, DwtPairAsk{c->dwt_pair != 0, c->dwt_pk != 0, fused, h16, a.px_lay, a.px_chan, a.px_row,
+                                                                    r.bytes, to.stride, ntiles});
         if (a.cw == 0 || a.ch == 0) {
             // a level without samples (a narrow tile off the origin: [ceil(x0 / 2^l), ceil((x0 + w) / 2^l)) can be empty):
             // nothing to transform, and nothing deeper either
+        } else if (pair.ok) {
+            const LLPlane to2 = ll_plane(c, l + 2, d_in, d_out);      // (the LL ping-pong goes on as if both levels had run)
+            a.ll2 = (int32_t*)to2.p; a.ll2_stride = to2.stride; a.ll2_pitch = to2.pitch;
+            a.pixels = d_pixels; a.px_bytes = r.bytes;
+            a.alloc_reset = c->pend_alloc; a.alloc_chunk_units = c->pend_alloc_units; c->pend_alloc = nullptr;
+            a.dc = r.dc; a.sext = r.sext;
+            HIP_TRY(c, launch_dwt_pair(a, pair, ntiles, c->stream), "launch fused dwt levels 0 and 1");
+            if (c->want_px_event) HIP_TRY(c, hipEventRecord(c->ev_px, c->stream), "record the pixels' last read");
+            last = l + 1;
         } else if (fused) {
             a.pixels = d_pixels; a.px_bytes = r.bytes;
             a.alloc_reset = c->pend_alloc; a.alloc_chunk_units = c->pend_alloc_units; c->pend_alloc = nullptr;
@@ -133,15 +146,17 @@ int run_dwt(grk_amd_ctx* c, uint32_t nplanes, void* d_in, void* d_out, const voi
         } else {
             HIP_TRY(c, launch_dwt_level(a, shape, c->stream), "launch dwt level");
         }
-        if (overlap_ht && (l == 0 || l + 1 == L)) {
+        if (overlap_ht && (l == 0 || last + 1 == L)) {
+            // (a launch that covers level 0 AND the last level -- L == 1, or a pair with L == 2 -- answers for both points)
             HIP_TRY(c, hipEventRecord(c->ev_level0, c->stream), "record level");
-            const int rc = launch_ht_at(c, *overlap_ht, true, l == 0 ? HtPoint::AfterLevel0 : HtPoint::AfterLastLevel, L == 1);
+            const int rc = launch_ht_at(c, *overlap_ht, true, l == 0 ? HtPoint::AfterLevel0 : HtPoint::AfterLastLevel, l == 0 && last + 1 == L);
             if (rc) return rc;
-            if (l + 1 == L) {
+            if (last + 1 == L) {
                 HIP_TRY(c, hipEventRecord(c->ev_side, c->side), "record side stream");
                 HIP_TRY(c, hipEventRecord(c->ev_side2, c->side2), "record side stream 2");
             }
         }
+        l = last;
     }
     return GRK_AMD_OK;
 }

@@ -78,5 +78,24 @@ constexpr uint32_t kDwtMinWgsPacked = 2048;
 // (... for the packed 5/3 kernel; the 32-bit kernels -- 448-column strips, twice the workgroups per row -- are better off with
 //  the finer cut: cfg3's 9/7 family 0.361 ms at 4096, 0.394 at 2048)
 constexpr uint32_t kDwtMinWgs = 4096;
+// Two packed levels in one launch (kernels_dwt.hip pair::dwt53_pk_kernel).  Segment `seg` of a level of ch rows (a multiple of 4), cut
+// every seg_pairs (even) row pairs: it STORES the upper level's pairs [store0, store1) and the lower level's pairs [low0, low1), and
+// to feed those it COMPUTES the upper level's pairs first .. last inclusive: the lower level's recurrence starts at LL row
+// 2 low0 - 2 (its own warm-up pair) and its last pair reads LL row 2 low1 -- except at the bottom of the image, where that row is
+// the mirror of one it has; pair `last` is computed all the same, from mirrored rows, and not used.  Pairs below 0 are made from
+// mirrored rows and equal pairs 2 and 1.
+struct DwtPairRows { int32_t store0, store1, first, last, low0, low1; };
+GRK_ENC_FN DwtPairRows dwt_pair_rows(uint32_t seg, uint32_t seg_pairs, uint32_t ch)
+{
+    const int32_t sh = (int32_t)(ch >> 1), j0 = (int32_t)(seg * seg_pairs);
+    const int32_t j1 = j0 + (int32_t)seg_pairs < sh ? j0 + (int32_t)seg_pairs : sh;
+    return DwtPairRows{j0, j1, j0 - 2, j1, j0 >> 1, j1 >> 1};
+}
+// The pair's own floor of workgroups, and the most row pairs of a segment.  Every segment computes three pairs more than it stores, so
+// the pair wants longer segments than a level alone: at 1024 the 8K frame runs 32-pair segments (1152 workgroups), 0.3200 ms per
+// pipelined frame against 0.3230 with 16-pair ones (floor 2048); beyond 32 pairs it loses again -- 64 tiles of 1024^2 0.3395 ms with
+// 64-pair segments, 0.3335 with 32 (profiles/dwt_pair.txt)
+constexpr uint32_t kDwtPairMinWgs = 1024;
+constexpr uint32_t kDwtPairMaxSeg = 32;
 
 } // namespace grk_amd

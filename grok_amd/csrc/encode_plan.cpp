@@ -232,4 +232,40 @@ DwtLevelShape plan_dwt_level(const DwtLevelDesc& d)
     return s;
 }
 
+// ---- two forward DWT levels in one launch -------------------------------------------------------------------------------------------
+DwtPairShape plan_dwt_pair(const DwtPairDesc& d)
+{
+    DwtPairShape s{};
+    const DwtLevelDesc& u = d.upper;
+    const DwtLevelShape up = plan_dwt_level(u), low = plan_dwt_level(d.lower);
+    const bool levels = up.packed && low.packed && up.inst[1].packed && low.inst[0].packed;
+    const bool pixels = u.fused && u.px_lay == 0 && u.px_bytes == 1 && d.mct && d.ncomp == 3 && u.h16 && !u.irreversible;
+    const bool shape = (u.cw & 7u) == 0 && u.cw >= 512 && (u.ch & 3u) == 0 && u.ch >= 32 && (u.px | u.py | d.lower.px | d.lower.py) == 0 &&
+                       d.lower.cw == u.cw >> 1 && d.lower.ch == u.ch >> 1;
+    const bool near = (uint64_t)u.m_stride * u.ch * 2u < (1ull << 31);       // bytes of a Mallat plane of int16
+    if (!(levels && pixels && shape && near && d.ntiles > 0)) return s;
+    s.ok = true;
+    s.lanes = up.lanes;
+    s.strip_cols = up.strip_cols;                                            // (leaves two halo lanes a side: kernels_dwt.hip)
+    s.grid_x = up.grid_x;
+    s.seg_pairs = std::min(kDwtPairMaxSeg, row_segment_pairs(s.grid_x, u.ch >> 1, d.ntiles, kDwtPairMinWgs));
+    s.grid_y = ((u.ch >> 1) + s.seg_pairs - 1) / s.seg_pairs;
+    s.inst = DwtPairKey{3, 1, (uint16_t)s.lanes};
+    return s;
+}
+
+DwtPairShape plan_dwt_pair_at(const TileGeom& g, uint32_t l, const DwtPairAsk& q)
+{
+    if (!q.pair || !q.fused || l != 0 || l + 1 >= g.p.num_levels) return DwtPairShape{};     // (the instances there are read pixels)
+    const ResGeom& g0 = level_geom(g, l);
+    const ResGeom& g1 = level_geom(g, l + 1);
+    const bool irrev = g.p.irreversible != 0;
+    const uint32_t zslots = q.ntiles * level_part_zslots(g.p.mct != 0, g.p.num_comps);
+    const DwtLevelDesc upper{g0.w, g0.h, g0.x0 & 1u, g0.y0 & 1u, g.stride, g.stride, q.h16, q.h16 && q.dwt_pk && pk16_level_ok(g.p, l), irrev,
+                             q.px_lay, q.px_chan, q.px_row, zslots, true, q.px_bytes};
+    const DwtLevelDesc lower{g1.w, g1.h, g1.x0 & 1u, g1.y0 & 1u, q.mid_stride, g.stride, q.h16, q.h16 && q.dwt_pk && pk16_level_ok(g.p, l + 1), irrev,
+                             0, 0, 0, q.ntiles * g.p.num_comps, false, q.px_bytes};
+    return plan_dwt_pair(DwtPairDesc{upper, lower, g.p.mct != 0, g.p.num_comps, q.ntiles});
+}
+
 } // namespace grk_amd

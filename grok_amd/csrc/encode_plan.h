@@ -188,5 +188,28 @@ struct DwtLevelShape {
 };
 DwtLevelShape plan_dwt_level(const DwtLevelDesc& d);
 
+// ---- two forward DWT levels in one launch -------------------------------------------------------------------------------------------
+// Levels l and l + 1 of the packed 5/3 kernel as one launch (kernels_dwt.hip pair::dwt53_pk_kernel): the lower level is fed from the
+// upper one's registers and the LL plane between them is neither written nor read.  `upper` and `lower` are the two levels as
+// plan_dwt_level would be asked about them (the lower one: fused = false, zslots = planes).  A pair is planned when both are packed
+// levels on even origins, the upper one reads planar 8-bit pixels of an MCT triple (exactly three components), its width is a
+// multiple of 8 (at least 512, so that the lower level is wide enough to be a packed level: four LL columns per lane there) and its
+// height a multiple of 4 (at least 32), and the Mallat plane stays below 2^31 bytes (lanes that must not store are given a column
+// offset beyond the plane).  Otherwise ok = false and the levels are launched one by one.
+struct DwtPairDesc { DwtLevelDesc upper, lower; bool mct; uint32_t ncomp, ntiles; };
+struct DwtPairShape {
+    bool ok;
+    uint32_t lanes, strip_cols;        // as the upper level's DwtLevelShape
+    uint32_t seg_pairs;                // row pairs of the UPPER level a workgroup stores (even; segments start on even pairs)
+    uint32_t grid_x, grid_y;
+    DwtPairKey inst;                   // a row of GRK_DWT_PAIR_INSTANCES
+};
+DwtPairShape plan_dwt_pair(const DwtPairDesc& d);
+// ... for levels l and l + 1 of a tile geometry, as run_dwt asks: the context's switches (pair: GRK_AMD_DWT_PAIR, dwt_pk: GRK_AMD_DWT_PK),
+// the call's route (fused: level l reads the caller's pixels; h16: int16 planes), the pixels' layout, the stride of the LL plane
+// between the two levels, and the tiles of the call.  No pair without the switch, off the fused route, or when l + 1 is no level.
+struct DwtPairAsk { bool pair, dwt_pk, fused, h16; uint32_t px_lay, px_chan; uint64_t px_row; uint32_t px_bytes, mid_stride, ntiles; };
+DwtPairShape plan_dwt_pair_at(const TileGeom& g, uint32_t l, const DwtPairAsk& q);
+
 } // namespace grk_amd
 #pragma GCC visibility pop

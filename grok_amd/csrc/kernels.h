@@ -56,10 +56,14 @@ struct DwtLevelArgs {
     // fields below are not read), 1 planar with pitches, 2 pixel-interleaved with px_chan samples per pixel in memory
     uint32_t px_lay, px_chan, px_xstep;
     uint64_t px_row, px_kstep, px_tile;
+    // two levels in one launch (launch_dwt_pair): the LL of the level below this one (cw / 4 x ch / 4); `ll` is not written
+    int32_t* ll2;       uint32_t ll2_stride; uint64_t ll2_pitch;
 };
 // sh: the level's shape (plan_dwt_level, encode_plan.h) -- which kernel instance, its strips and row segments; a.seg_pairs = sh.seg_pairs
 hipError_t launch_dwt_level(const DwtLevelArgs& a, const DwtLevelShape& sh, hipStream_t s);
 hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, const DwtLevelShape& sh, uint32_t ntiles, uint32_t ncomp, int mct, hipStream_t s);
+// levels 0 and 1 of the MCT triple straight from the pixels, in one launch (plan_dwt_pair, encode_plan.h); a0 describes level 0
+hipError_t launch_dwt_pair(const DwtLevelArgs& a0, const DwtPairShape& sh, uint32_t ntiles, hipStream_t s);
 
 // ---- K3: HT cleanup encoder, one wavefront per code-block (kernels_ht.hip) -------------------
 struct HtBlockDesc {        // one per code-block of a tile-component set (all comps of one tile)

@@ -681,6 +681,243 @@ __global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
     store_out(jp, o);
 }
 
+// ---- two packed levels in one launch: level l + 1 fed from level l's registers -------------------------------------------------------
+// For a pair of levels that are both packed levels (plan_dwt_pair, encode_plan.h: planar 8-bit MCT pixels, a width that is a multiple
+// of 8, a height that is a multiple of 4).  Level l runs as in dwt53_pk_kernel and stores its three high-pass bands; its LL row -- two
+// columns per lane, o[k][0] behind the horizontal phase -- is never stored.  Two consecutive steps of level l give one row pair of level
+// l + 1: a second V53pk recurrence per component takes them, its result goes through a second exchange line of half the width, and
+// lane u of the first nv / 2 lanes runs the same stencil on LL columns 4u .. 4u + 3: the level-(l + 1) bands to their Mallat slots
+// and its LL to the ping-pong plane that level l + 1 writes, all in dwords.  The LL plane between the two levels (a quarter of level
+// l's writes, and what level l + 1 read back) is not touched.
+//  * columns: the lower level's low-pass needs LL columns 2i - 2 .. 2i + 2 = six more input columns either side, so the staged line
+//    has TWO halo groups per side (groups 0 .. slanes + 3; lane t < slanes carries group t + 2, the four lanes after them the halo)
+//    and the horizontal phase of level l also runs on groups 1 and slanes + 2, on the two lanes after the strip's own.  Those two
+//    store nothing: their column offset lies beyond the descriptors, which have the planes' real sizes here;
+//  * rows: level-(l + 1) pairs [j, j + n) need LL rows 2j - 2 .. 2(j + n), so a segment runs level-l pairs 2j - 2 .. 2(j + n) -- three
+//    more than it stores -- behind level l's own warm-up step; what a segment computes of its neighbours' pairs goes through the
+//    descriptor of zero length;
+//  * mirroring is done in the domain of the level being transformed.  Top and left: LL made from mirrored samples IS the mirrored LL
+//    (the low-pass is symmetric about an even origin).  Bottom and right it is not -- mirrored samples give s[M] = s[M - 1] where
+//    level l + 1 takes s[M] := s[M - 2] -- so the last pair's recurrence takes x2 = xe, and the lane that owns LL column sw - 2 writes
+//    it to slot sw of the exchange line as well (the right halo lane of the image's last strip writes to a spare slot);
+//  * one barrier per step as before: the second line is written at the end of the step that completes a pair and read behind the
+//    next step's barrier; two barriers lie between a read and the next write, so one buffer is enough.
+namespace pair {
+
+constexpr uint32_t kDropOff = 0x80000000u;         // a column offset beyond every plane (plan_dwt_pair: planes below 2^31 bytes)
+
+template <int NC, int PX, int NT>
+__global__ __launch_bounds__(NT) void dwt53_pk_kernel(DwtLevelArgs a)
+{
+    static_assert(PX == 1, "8-bit pixels in component planes");
+    static_assert((((NT - 4) * kPkLaneCols) & ~63) == (((NT - 2) * kPkLaneCols) & ~63), "pk_strip_cols leaves room for two halo lanes a side");
+    __builtin_amdgcn_s_setprio(3);
+    constexpr int kPkCols = NT * kPkLaneCols;
+    __shared__ __attribute__((aligned(16))) uint32_t line[2][NC][kPkCols];    // [parity][comp][column] = low row | high row << 16
+    __shared__ __attribute__((aligned(16))) uint32_t line1[NC][2 * NT];       // the lower level's: LL column c in slot c + 4
+
+    const uint32_t t = threadIdx.x;
+    uint32_t bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    if (a.alloc_reset && (bx | by | bz) == 0) ht_alloc_reset(a.alloc_reset, a.alloc_chunk_units, threadIdx.x, blockDim.x);
+    if (a.xcd) {                                           // (as dwt53_pk_kernel)
+        const uint32_t gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+        const uint32_t id = bx + gx * (by + gy * bz);
+        const uint32_t q = total >> 3, r = total & 7u, k = id & 7u;
+        const uint32_t lid = k * q + min(k, r) + (id >> 3);
+        bx = lid % gx; by = (lid / gx) % gy; bz = lid / (gx * gy);
+    }
+    const uint32_t cw = a.cw, ch = a.ch;
+    const uint32_t sw = cw >> 1, sh = ch >> 1, sw1 = cw >> 2, sh1 = ch >> 2;
+    const uint32_t scols = pk_strip_cols(cw, NT), slanes = scols / kPkLaneCols;
+
+    const uint32_t plane0 = (bz / a.zdiv) * a.ncomp + a.comp0 + (bz % a.zdiv);
+    int16_t* l2 = reinterpret_cast<int16_t*>(a.ll2) + (size_t)plane0 * a.ll2_pitch;
+    int16_t* mp = reinterpret_cast<int16_t*>(a.mallat) + (size_t)plane0 * a.m_pitch;
+    const size_t comp_px = (size_t)cw * ch;
+    const uint8_t* pix = reinterpret_cast<const uint8_t*>(a.pixels) + (size_t)plane0 * comp_px;
+
+    const uint32_t grp = t < slanes ? t + 2u : (t < slanes + 2u ? t - slanes : (t < slanes + 4u ? t : 2u));
+    const int32_t c0 = (int32_t)(bx * scols) - 2 * kPkHalo + (int32_t)(grp * kPkLaneCols);     // first of its four columns
+    const bool rev = c0 < 0 || c0 >= (int32_t)cw;                                               // (mirrored groups: as dwt53_pk_kernel)
+    int32_t lo = c0 < 0 ? -c0 - 3 : (c0 >= (int32_t)cw ? 2 * ((int32_t)cw - 1) - c0 - 3 : c0);
+    lo = max(0, min(lo, (int32_t)cw - kPkLaneCols));
+    const uint32_t lane_off = (uint32_t)lo;
+    const uint32_t selA = rev ? 0x0c020c03u : 0x0c010c00u, selB = rev ? 0x0c000c01u : 0x0c030c02u;
+    const pk16 dc2 = as_pk((uint32_t)a.dc * 0x10001u);
+
+    __amdgpu_buffer_rsrc_t r_in[NC], r_l2[NC], r_mp[NC];
+    const uint32_t m_bytes = (uint32_t)min((unsigned long long)a.m_pitch * 2u, 0x7fffffffull);
+    const uint32_t l2_bytes = (uint32_t)min((unsigned long long)a.ll2_pitch * 2u, 0x7fffffffull);
+    #pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        r_in[k] = buffer_from(pix + (size_t)k * comp_px);
+        r_l2[k] = buffer_of(l2 + (size_t)k * a.ll2_pitch, l2_bytes);
+        r_mp[k] = buffer_of(mp + (size_t)k * a.m_pitch, m_bytes);
+    }
+    __amdgpu_buffer_rsrc_t r_none = buffer_from(a.mallat, true);
+
+    const DwtPairRows rows = dwt_pair_rows(by, a.seg_pairs, ch);
+    const int32_t J0 = rows.store0;                                        // the upper level's pairs it stores: [J0, J1), both even
+    const int32_t Q0 = rows.first;                                         // ... and the first it computes (the last: J1)
+    const int32_t n1 = rows.low1 - rows.low0;                              // the lower level's pairs: J0 / 2 .. J0 / 2 + n1 - 1
+
+    struct Raw { uint32_t v[NC]; };
+    auto fetch_row = [&](int32_t r, Raw& q) {
+        const uint32_t rr = mirror_row<true>(r, ch);
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) q.v[k] = __builtin_amdgcn_raw_buffer_load_b32(r_in[k], lane_off, rr * cw, kPkLoadAux);
+    };
+    auto convert = [&](const Raw& q, pk16 (&va)[NC], pk16 (&vb)[NC]) {
+        pk16 xa[NC], xb[NC];
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            xa[k] = as_pk(__builtin_amdgcn_perm(0u, q.v[k], selA));
+            xb[k] = as_pk(__builtin_amdgcn_perm(0u, q.v[k], selB));
+        }
+        if constexpr (NC == 3) {   // RCT, as dwt53_pk_kernel
+            const pk16 cba = xa[2] - xa[1], cra = xa[0] - xa[1], cbb = xb[2] - xb[1], crb = xb[0] - xb[1];
+            va[0] = xa[1] + ((cba + cra) >> 2) - dc2; va[1] = cba; va[2] = cra;
+            vb[0] = xb[1] + ((cbb + crb) >> 2) - dc2; vb[1] = cbb; vb[2] = crb;
+        } else { va[0] = xa[0] - dc2; vb[0] = xb[0] - dc2; }
+    };
+
+    V53pk colA[NC], colB[NC], col1[NC];
+    {
+        Raw q; pk16 xa[NC], xb[NC];
+        fetch_row(2 * (Q0 - 1), q);
+        convert(q, xa, xb);
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) { colA[k].init(xa[k]); colB[k].init(xb[k]); }
+    }
+    Raw ra1, ra2, rb1, rb2;
+    fetch_row(2 * Q0 - 1, ra1); fetch_row(2 * Q0, ra2);
+    fetch_row(2 * Q0 + 1, rb1); fetch_row(2 * Q0 + 2, rb2);
+
+    // horizontal phase of the upper level: lane t < slanes produces group min(t, nv - 1) + 2 (past the image: the last one again),
+    // lanes slanes and slanes + 1 the halo groups 1 and nv + 2, which only the lower level reads
+    const uint32_t nv = min(slanes, (sw - bx * (scols / 2) + 1u) >> 1);
+    const bool last_strip = (bx + 1u) * scols >= cw;
+    const uint32_t hg = t < slanes ? min(t, nv - 1u) + 2u : (t == slanes ? 1u : (t == slanes + 1u ? nv + 2u : 2u));
+    const uint32_t hc = hg * kPkLaneCols;
+    const uint32_t oc = t < slanes ? (bx * (scols / 2) + (hg - 2u) * 2u) * 2u : kDropOff;
+    // its two LL columns 2 (hg - 2), + 1 in the second line; slot sw of the image's last strip from the lane that owns sw - 2
+    const uint32_t w1 = 2u * hg + ((last_strip && t == slanes + 1u) ? 2u : 0u);
+    const uint32_t x1slot = (last_strip && t < slanes && hg == nv + 1u) ? 2u * hg + 2u : w1;       // (everyone else: its own slot again)
+    // horizontal phase of the lower level: lane t < nv / 2 on LL columns 4t .. 4t + 3
+    const uint32_t nv1 = nv >> 1;
+    const uint32_t hc1 = 4u * min(t, nv1 - 1u) + 4u;
+    const uint32_t oc1 = t < nv1 ? (bx * (scols / 4) + t * 2u) * 2u : kDropOff;
+
+    pk16 sA[NC], dA[NC], sB[NC], dB[NC];
+    auto vstep = [&](int32_t ii, Raw& r1, Raw& r2) {
+        pk16 x1a[NC], x1b[NC], x2a[NC], x2b[NC];
+        convert(r1, x1a, x1b); convert(r2, x2a, x2b);
+        fetch_row(2 * ii + 5, r1); fetch_row(2 * ii + 6, r2);
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) { colA[k].step(x1a[k], x2a[k], sA[k], dA[k]); colB[k].step(x1b[k], x2b[k], sB[k], dB[k]); }
+    };
+    // the stencil on seven slots of an exchange line, w at the first of its four columns: (LL | LH | HL | HH), two columns each
+    auto stencil = [&](const uint32_t* w, uint32_t (&o)[4]) {
+        const uint2 m = *reinterpret_cast<const uint2*>(w - 2);
+        const uint4 c = *reinterpret_cast<const uint4*>(w);
+        const pk16 m2 = as_pk(m.x), m1 = as_pk(m.y), c0 = as_pk(c.x), c1 = as_pk(c.y), c2 = as_pk(c.z), c3 = as_pk(c.w),
+                   p4 = as_pk(w[4]);
+        const pk16 dm = m1 - ((m2 + c0) >> 1);
+        const pk16 d0 = c1 - ((c0 + c2) >> 1);
+        const pk16 d1 = c3 - ((c2 + p4) >> 1);
+        const pk16 s0 = c0 + ((dm + d0 + (pk16)(2)) >> 2);
+        const pk16 s1 = c2 + ((d0 + d1 + (pk16)(2)) >> 2);
+        o[0] = __builtin_amdgcn_perm(as_u32(s1), as_u32(s0), kSelLoLo);
+        o[1] = __builtin_amdgcn_perm(as_u32(s1), as_u32(s0), kSelHiHi);
+        o[2] = __builtin_amdgcn_perm(as_u32(d1), as_u32(d0), kSelLoLo);
+        o[3] = __builtin_amdgcn_perm(as_u32(d1), as_u32(d0), kSelHiHi);
+    };
+    // the lower level's pair j1 from the second line (written one step earlier), stored at once
+    auto lower_out = [&](int32_t j1, bool valid) {
+        const uint32_t ju = (uint32_t)j1;
+        const uint32_t lrow = __builtin_amdgcn_readfirstlane(ju * a.ll2_stride * 2u),
+                       mlo = __builtin_amdgcn_readfirstlane(ju * a.m_stride * 2u),
+                       mhi = __builtin_amdgcn_readfirstlane((sh1 + ju) * a.m_stride * 2u);
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            uint32_t o1[4];
+            stencil(&line1[k][hc1], o1);
+            const __amdgpu_buffer_rsrc_t rl = valid ? r_l2[k] : r_none, rm = valid ? r_mp[k] : r_none;
+            __builtin_amdgcn_raw_buffer_store_b32(o1[0], rl, oc1, lrow, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(o1[1], rm, oc1, mhi, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(o1[2], rm, oc1 + 2u * sw1, mlo, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(o1[3], rm, oc1 + 2u * sw1, mhi, 0);
+        }
+    };
+    auto hphase = [&](int par, uint32_t (&o)[NC][4]) {       // (the caller reads the second line between the barrier and the stencil)
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            uint4 w;
+            w.x = __builtin_amdgcn_perm(as_u32(dA[k]), as_u32(sA[k]), kSelLoLo);
+            w.y = __builtin_amdgcn_perm(as_u32(dA[k]), as_u32(sA[k]), kSelHiHi);
+            w.z = __builtin_amdgcn_perm(as_u32(dB[k]), as_u32(sB[k]), kSelLoLo);
+            w.w = __builtin_amdgcn_perm(as_u32(dB[k]), as_u32(sB[k]), kSelHiHi);
+            *reinterpret_cast<uint4*>(&line[par][k][grp * kPkLaneCols]) = w;
+        }
+        __syncthreads();
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) stencil(&line[par][k][hc], o[k]);
+    };
+    auto store_out = [&](int32_t j, const uint32_t (&o)[NC][4], bool valid) {
+        const uint32_t ju = (uint32_t)j;
+        const uint32_t mlo = __builtin_amdgcn_readfirstlane(ju * a.m_stride * 2u),
+                       mhi = __builtin_amdgcn_readfirstlane((sh + ju) * a.m_stride * 2u);
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const __amdgpu_buffer_rsrc_t rm = valid ? r_mp[k] : r_none;
+            __builtin_amdgcn_raw_buffer_store_b32(o[k][1], rm, oc, mhi, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(o[k][2], rm, oc + 2u * sw, mlo, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(o[k][3], rm, oc + 2u * sw, mhi, 0);
+        }
+    };
+    // the second recurrence: LL rows x1 (held from the step before) and the one just made; the image's last pair takes x2 = xe
+    pk16 x1[NC];
+    auto lower_vstep = [&](const uint32_t (&o)[NC][4], bool last) {
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const pk16 x2 = last ? col1[k].xe : as_pk(o[k][0]);
+            pk16 s, d;
+            col1[k].step(x1[k], x2, s, d);
+            uint2 w;
+            w.x = __builtin_amdgcn_perm(as_u32(d), as_u32(s), kSelLoLo);
+            w.y = __builtin_amdgcn_perm(as_u32(d), as_u32(s), kSelHiHi);
+            *reinterpret_cast<uint2*>(&line1[k][w1]) = w;
+            line1[k][x1slot] = w.x;
+        }
+    };
+    auto no_stores = [&](int n) {                            // (as dwt53_pk_kernel: the steps before the loop issue what a loop step issues)
+    #pragma unroll
+        for (int k = 0; k < n; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, r_none, 64 * k, 0, 0);
+    };
+    uint32_t o[NC][4];
+    vstep(Q0 - 1, ra1, ra2); no_stores(7 * NC);              // the upper level's warm-up step: no output
+    __builtin_amdgcn_sched_barrier(0);
+    vstep(Q0, rb1, rb2); no_stores(3 * NC); hphase(0, o);
+    #pragma unroll
+    for (int k = 0; k < NC; ++k) col1[k].init(as_pk(o[k][0]));
+    __builtin_amdgcn_sched_barrier(0);
+    // turn `it`: the upper level's pairs A = J0 - 1 + 2 it and B = A + 1, then the lower level's pair J0 / 2 - 1 + it (turn 0: its warm-up),
+    // whose stencil and stores follow in turn it + 1
+    for (int32_t it = 0; it <= n1; ++it) {
+        const int32_t A = Q0 + 1 + 2 * it, B = A + 1;
+        vstep(A, ra1, ra2); store_out(B - 2, o, it >= 1); hphase(1, o); lower_out((J0 >> 1) + it - 2, it >= 2);
+    #pragma unroll
+        for (int k = 0; k < NC; ++k) x1[k] = as_pk(o[k][0]);
+        __builtin_amdgcn_sched_barrier(0);
+        vstep(B, rb1, rb2); store_out(A, o, it >= 1); hphase(0, o); lower_vstep(o, B == (int32_t)sh);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+    lower_out((J0 >> 1) + n1 - 1, true);
+}
+
+} // namespace pair
+
 } // namespace
 
 // one launch of the instance the planner chose (plan_dwt_level, encode_plan.h): a row of the template's list (dwt_instances.h), or
@@ -722,6 +959,21 @@ hipError_t launch_dwt_level0_fused(const DwtLevelArgs& a0, const DwtLevelShape& 
         if (part.comp0 != 0) a.alloc_reset = nullptr;        // (the first launch resets the allocator)
         const hipError_t e = launch_dwt_instance(sh.inst[part.nc == 3], dim3(sh.grid_x, sh.grid_y, ntiles * part.zdiv), a, s);
         if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_dwt_pair(const DwtLevelArgs& a0, const DwtPairShape& sh, uint32_t ntiles, hipStream_t s)
+{
+    if (!sh.ok) return hipErrorInvalidValue;
+    DwtLevelArgs a = a0;
+    a.comp0 = 0; a.zdiv = 1; a.ncomp = 3; a.seg_pairs = sh.seg_pairs;
+    const dim3 grid(sh.grid_x, sh.grid_y, ntiles);
+    switch (sh.inst.code()) {
+#define GRK_X(NC, PX, NT) case DwtPairKey{NC, PX, NT}.code(): hipLaunchKernelGGL((pair::dwt53_pk_kernel<NC, PX, NT>), grid, dim3(NT), 0, s, a); break;
+    GRK_DWT_PAIR_INSTANCES(GRK_X)
+#undef GRK_X
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -26,6 +26,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_from(const void* p, boo
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, none ? 0 : -1, 0x00020000);
 }
+// ... and one of `bytes` bytes: a lane whose offset lies beyond them stores nothing
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_of(const void* p, uint32_t bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
 
 // largest magnitude the packed inverse transform takes in (coefficients and intermediate LL): with it no sum of the
 // horizontal + vertical synthesis, of the inverse RCT and of the DC shift leaves 16 bits (7.5 M + 4, 15.6 M + 128 < 32768)

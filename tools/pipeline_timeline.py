@@ -16,6 +16,8 @@ def family(k):
         return "fallback"
     if "ht_encode_kernel" in k:
         return "k3"
+    if "pair::dwt53_pk_kernel<3" in k:          # levels 0 and 1 in one launch: it cuts the frames as level 0 does
+        return "pair0+1"
     if "dwt53_pk_kernel<3" in k or "dwt_level_kernel<false, 3" in k:
         return "level0"
     if "dwt53_pk" in k or "dwt_level" in k:
@@ -45,7 +47,7 @@ def main():
             r[2] = "top" if r[3] == k3_grids[-1] and len(k3_grids) > 1 else "rest"
         if r[2] == "fallback":
             r[2] = "fb_top" if r[3] == max(g for _, _, f, g in rows if f == "fallback") and len({g for _, _, f, g in rows if f == "fallback"}) > 1 else "fb"
-    starts = [s for s, _, f, _ in rows if f == "level0"]
+    starts = [s for s, _, f, _ in rows if f in ("level0", "pair0+1")]
     print("== %s: %d kernels, %d frames" % (label, len(rows), len(starts)))
     if len(starts) < 6:
         print("too few frames")
@@ -54,7 +56,7 @@ def main():
     for i in range(3, len(starts) - 1):
         t0, t1 = starts[i], starts[i + 1]
         # a frame's kernels: its DWT chain starts inside [t0, t1); its K3 launches are the first of each kind that start at or after t0
-        chain = [(s - t0, e - t0, f) for s, e, f, _ in rows if f in ("level0", "level", "tail") and t0 <= s < t1]
+        chain = [(s - t0, e - t0, f) for s, e, f, _ in rows if f in ("level0", "pair0+1", "level", "tail") and t0 <= s < t1]
         k3 = []
         for kind in ("top", "rest"):
             cand = [(s - t0, e - t0, f) for s, e, f, _ in rows if f == kind and s >= t0]
@@ -66,7 +68,7 @@ def main():
     print("period (level 0 to level 0): mean %.1f us, min %.1f, max %.1f over %d frames" % (mean([f["period"] for f in frames]), min(f["period"] for f in frames), max(f["period"] for f in frames), n))
     ex = frames[n // 2]
     print("one frame (us from its level 0):")
-    lv = 0
+    lv = 1 if any(f == "pair0+1" for _, _, f in ex["chain"]) else 0
     for s, e, f in ex["chain"] + ex["k3"]:
         name = f
         if f == "level":

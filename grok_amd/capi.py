@@ -366,6 +366,7 @@ def lib():
         L.grk_amd_layout_num_tiles.argtypes = [PL]
         L.grk_amd_layout_tile.argtypes = [PL, PP, u32, PP]
         L.grk_amd_same_tile_geometry.argtypes = [PP, PP]
+        L.grk_amd_same_tile_packets.argtypes = [PP, PP, u32]
         L.grk_amd_write_codestream_layout.restype = C.c_int64
         L.grk_amd_write_codestream_layout.argtypes = [PL, PP, vp, vp, u32, vp, u64]
         L.grk_amd_write_main_header_layout.restype = C.c_int64
@@ -487,6 +488,15 @@ def same_tile_geometry(a, b):
     rc = lib().grk_amd_same_tile_geometry(C.byref(a), C.byref(b))
     if rc < 0:
         raise ValueError("grk_amd_same_tile_geometry failed: %d" % rc)
+    return bool(rc)
+
+
+def same_tile_packets(a, b, flags=0):
+    """May tiles a and b share one assemble_device call under the progression order of `flags` (CS_PROG)?  Same component count, same
+    geometry and the same packet sequence (grk_amd_same_tile_packets)."""
+    rc = lib().grk_amd_same_tile_packets(C.byref(a), C.byref(b), int(flags))
+    if rc < 0:
+        raise ValueError("grk_amd_same_tile_packets failed: %d" % rc)
     return bool(rc)
 
 

@@ -107,6 +107,8 @@ int assemble_check(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles
     if (!c || !p || !ntiles || !tile_index) return GRK_AMD_ERR_INVALID;
     if (!c->have_geom || !same_params(c->gp, *p) || c->geom.reduce || ntiles != c->last_ntiles || !c->last_nblocks)
         return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_assemble_device assembles the grk_amd_encode_tiles call before it: same tiles, same parameters");
+    for (uint32_t i = 0; i < ntiles; ++i)
+        if (tile_index[i] > 65535u) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_assemble_device: a tile index beyond 65 535 (Isot is 16 bits)");
     return GRK_AMD_OK;
 }
 } // namespace
@@ -165,7 +167,7 @@ void* grk_amd_assembled_table_ptr(grk_amd_ctx* c, int which)
 // context's pinned chunks on several copy threads (copy_d2h); complete on return
 int grk_amd_fetch_assembled(grk_amd_ctx* c, uint64_t offset, uint64_t nbytes, uint8_t* dst)
 {
-    if (!c || !dst || offset + nbytes > c->t2_out_used) return GRK_AMD_ERR_INVALID;
+    if (!c || !dst || offset > c->t2_out_used || nbytes > c->t2_out_used - offset) return GRK_AMD_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     if (!nbytes) return GRK_AMD_OK;
     { const int rc = copy_d2h(c, dst, (const uint8_t*)c->t2_outs[c->t2_cur].out.p + offset, nbytes); if (rc) return rc; }
@@ -176,7 +178,7 @@ int grk_amd_fetch_assembled(grk_amd_ctx* c, uint64_t offset, uint64_t nbytes, ui
 // the same queued on the context's stream, for pinned memory only; complete after grk_amd_synchronize
 int grk_amd_fetch_assembled_async(grk_amd_ctx* c, uint64_t offset, uint64_t nbytes, uint8_t* dst)
 {
-    if (!c || !dst || offset + nbytes > c->t2_out_used) return GRK_AMD_ERR_INVALID;
+    if (!c || !dst || offset > c->t2_out_used || nbytes > c->t2_out_used - offset) return GRK_AMD_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     if (!host_is_pinned(dst)) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_fetch_assembled_async needs pinned memory (grk_amd_host_alloc)");
     if (nbytes) HIP_TRY(c, hipMemcpyAsync(dst, (const uint8_t*)c->t2_outs[c->t2_cur].out.p + offset, nbytes, hipMemcpyDeviceToHost, c->stream), "download");

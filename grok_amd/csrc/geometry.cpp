@@ -1,6 +1,7 @@
 // grok_amd/csrc/geometry.cpp -- see geometry.h for the reference citations.
 #include "geometry.h"
 #include "image.h"
+#include "t2_order.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -253,18 +254,70 @@ bool same_geometry(const TileGeom& a, const TileGeom& b)
     return true;
 }
 
+// Two tiles of one geometry whose packets come in the same (component, resolution, precinct) sequence.  For LRCP and RLCP the
+// sequence is resolution, component, raster -- the geometry's alone.  The position-major orders walk the precincts by their
+// corners on the reference grid clipped to the tile: where the corners of different resolutions coincide depends on where the
+// tile lies, and same_geometry does not look at that.
+bool same_packets(const TileGeom& a, const TileGeom& b, uint32_t order)
+{
+    if (order <= 1) return true;
+    if (a.p.num_comps != b.p.num_comps) return false;
+    const std::vector<const TileGeom*> ca(a.p.num_comps, &a), cb(b.p.num_comps, &b);
+    const std::vector<Pk> sa = packet_order(ca, nullptr, nullptr, a.p.tile_x0, a.p.tile_y0, order);
+    const std::vector<Pk> sb = packet_order(cb, nullptr, nullptr, b.p.tile_x0, b.p.tile_y0, order);
+    if (sa.size() != sb.size()) return false;
+    for (size_t i = 0; i < sa.size(); ++i)
+        if (sa[i].c != sb[i].c || sa[i].r != sb[i].r || sa[i].pi != sb[i].pi) return false;
+    return true;
+}
 
 } // namespace grk_amd
 
+// One layer's packets of a tile in progression order (t2_order.h; what the five orders are: t2_writer.cpp, with the tile-part writer)
+std::vector<grk_amd::Pk> grk_amd::packet_order(const std::vector<const TileGeom*>& cg, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0,
+                             uint32_t order)
+{
+    const uint32_t ncomp = (uint32_t)cg.size();
+    const grk_amd_tile_params& p = cg[0]->p;
+    std::vector<Pk> prec;                                   // every precinct of the tile: component-major, resolution-major, raster
+    for (uint32_t c = 0; c < ncomp; ++c) {
+        const TileGeom& g = *cg[c];
+        const uint64_t dx = comp_dx && comp_dx[c] ? comp_dx[c] : 1, dy = comp_dy && comp_dy[c] ? comp_dy[c] : 1;
+        for (uint32_t r = 0; r <= p.num_levels; ++r) {
+            const ResGeom& R = g.res[r];
+            const uint32_t sh = p.num_levels - r;
+            for (uint32_t pj = 0; pj < R.nph; ++pj)
+                for (uint32_t pi = 0; pi < R.npw; ++pi) {
+                    const uint64_t cx = (((uint64_t)((R.x0 >> R.ppx) + pi) << R.ppx) << sh) * dx, cy = (((uint64_t)((R.y0 >> R.ppy) + pj) << R.ppy) << sh) * dy;
+                    prec.push_back(Pk{c, r, pj * R.npw + pi, std::max<uint64_t>(cx, gx0), std::max<uint64_t>(cy, gy0)});
+                }
+        }
+    }
+    // (stable sorts of the component-major, resolution-major, raster list: the keys named, everything else in that order)
+    if (order <= 1)                // resolution, component, precinct
+        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) { return a.r != b.r ? a.r < b.r : a.c < b.c; });
+    else if (order == 2)           // resolution, position, component
+        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) {
+            return a.r != b.r ? a.r < b.r : a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.c < b.c; });
+    else if (order == 3)           // position, component, resolution
+        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) {
+            return a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.c != b.c ? a.c < b.c : a.r < b.r; });
+    else                           // component, position, resolution
+        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) {
+            return a.c != b.c ? a.c < b.c : a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.r < b.r; });
+    return prec;
+}
+
 // the next unit of a whole-image call into its geometry group (image.h)
-int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p)
+int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p, uint32_t order)
 {
     TileGeom geom;
     const int rc = build_tile_geom(p, geom);
     if (rc) return rc;
     size_t k = 0;
     for (; k < g.geoms.size(); ++k)
-        if (g.geoms[k].p.num_comps == p.num_comps && g.geoms[k].p.mct == p.mct && same_geometry(g.geoms[k], geom)) break;
+        if (g.geoms[k].p.num_comps == p.num_comps && g.geoms[k].p.mct == p.mct && same_geometry(g.geoms[k], geom) &&
+            same_packets(g.geoms[k], geom, order)) break;
     if (k == g.geoms.size()) { g.geoms.push_back(std::move(geom)); g.members.emplace_back(); }
     g.members[k].push_back((uint32_t)g.of.size());
     g.of.push_back((uint32_t)k);
@@ -278,4 +331,14 @@ extern "C" int64_t grk_amd_tile_num_blocks(const grk_amd_tile_params* p)
     int rc = grk_amd::build_tile_geom(*p, g);
     if (rc != GRK_AMD_OK) return rc;
     return (int64_t)g.blocks_per_comp * p->num_comps;
+}
+
+extern "C" int grk_amd_same_tile_packets(const grk_amd_tile_params* a, const grk_amd_tile_params* b, uint32_t flags)
+{
+    if (!a || !b) return GRK_AMD_ERR_INVALID;
+    grk_amd::TileGeom ga, gb;
+    int rc = grk_amd::build_tile_geom(*a, ga); if (rc) return rc;
+    rc = grk_amd::build_tile_geom(*b, gb); if (rc) return rc;
+    return a->num_comps == b->num_comps && grk_amd::same_geometry(ga, gb) &&
+           grk_amd::same_packets(ga, gb, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u) ? 1 : 0;
 }

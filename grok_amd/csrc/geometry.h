@@ -65,6 +65,10 @@ int reduced_tile_rect(const grk_amd_tile_params& p, uint32_t reduce, uint32_t* x
 
 // the same sub-band partition, block partition and lifting variants: what one batch of grk_amd_encode_tiles needs
 bool same_geometry(const TileGeom& a, const TileGeom& b);
+// ... and, of two such tiles, the same packet sequence in progression order `order` (t2_order.h: packet_order): what one
+// grk_amd_assemble_device call needs on top -- its one plan (t2_device_plan) frames every tile of the batch.  Orders 0 and 1: true
+// without a look; from RPCL on the tiles' sequences are compared, since they depend on where a tile lies on the reference grid.
+bool same_packets(const TileGeom& a, const TileGeom& b, uint32_t order);
 
 // decomposition level l (0 = the tile itself) is resolution L - l
 inline const ResGeom& level_geom(const TileGeom& g, uint32_t l) { return g.res[g.p.num_levels - l]; }

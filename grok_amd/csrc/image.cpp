@@ -47,7 +47,7 @@ int grk_amd::plain_image(const grk_amd_image_layout* im, const grk_amd_tile_para
     units.assign(ntiles, Unit{{}, 0});
     for (uint32_t t = 0; t < ntiles; ++t) {
         int rc = grk_amd_layout_tile(im, base, t, &units[t].p);
-        if (!rc) rc = add_unit(g, units[t].p);
+        if (!rc) rc = add_unit(g, units[t].p, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
         if (rc) return rc;
     }
     return GRK_AMD_OK;

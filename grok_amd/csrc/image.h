@@ -52,9 +52,13 @@ struct UnitGroups {
 
 // the next unit, of parameters `p`, into its group: the first whose num_comps, mct and geometry (same_geometry) it shares -- one
 // batch of grk_amd_encode_tiles --, or a new one.  GRK_AMD_OK or build_tile_geom's error.
-int add_unit(UnitGroups& g, const grk_amd_tile_params& p);
+// `order`: the progression order of a caller whose groups are also framed as one batch each (grk_amd_assemble_device: one packet
+// sequence, the first unit's, for the whole batch) -- from RPCL on a group's units share their packet sequence too (same_packets).
+// 0 for everybody whose Tier-2 is per tile: the decoders, the rate and surface paths.
+int add_unit(UnitGroups& g, const grk_amd_tile_params& p, uint32_t order = 0);
 
-// A plain image (component-major planar, tight, W x H per component): one unit per tile with all components, grouped.
+// A plain image (component-major planar, tight, W x H per component): one unit per tile with all components, grouped by geometry
+// and by the packet sequence of the progression order in `flags` (add_unit).
 // A file with TLM holds at most 255 tiles (one-byte Ttlm): GRK_AMD_ERR_UNSUPPORTED before any work.
 // `lay` (or null: that default): the layout of `pixels`, row_pitch the image's; GRK_AMD_ERR_INVALID when it does not fit the image.
 int plain_image(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,

@@ -368,7 +368,9 @@ int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* 
     SourcePlanes src;
     UnitGroups g;
     const grk_amd_pixel_layout whole = ctx->enc_layout;
-    int64_t rc = plain_image(im, base, pixels, flags, tiles, src, g, &whole);
+    // (grouped without the progression order, by geometry alone: the file is the host writer's, tile by tile, and the split route's
+    //  budgets go by group)
+    int64_t rc = plain_image(im, base, pixels, flags & ~(7u << GRK_AMD_CS_PROG_SHIFT), tiles, src, g, &whole);
     if (rc) return rc;
     KeepLayout staged{ctx->enc_layout, whole};
     ctx->enc_layout = staged_layout(src);

@@ -1,5 +1,6 @@
-// grok_amd/csrc/t2_order.h -- the packet sequence of a tile (private to the library; defined in t2_writer.cpp).  The codestream
-// writers emit the packets of a tile in this order, the codestream reader (t2_reader.cpp) meets them in it.
+// grok_amd/csrc/t2_order.h -- the packet sequence of a tile (private to the library; defined in geometry.cpp).  The codestream
+// writers emit the packets of a tile in this order, the codestream reader (t2_reader.cpp) meets them in it, and the whole-image
+// encoders put only tiles that share it into one device-assembled batch (geometry.h: same_packets).
 #pragma once
 #include "geometry.h"
 #include <cstdint>

@@ -298,43 +298,8 @@ grk_amd_image_layout plain_layout(const grk_amd_tile_params& p, uint32_t img_w, 
 //   CPRL        component -> precinct position -> resolution
 // where a precinct's position is its top-left corner on the REFERENCE grid (component coordinates times the component's
 // sub-sampling factors), clipped to the tile -- the (y, x) at which the standard's position loops meet it; positions are walked
-// in raster order, several resolutions / components can share one.  (Pk and the declaration: t2_order.h -- the codestream reader
-// walks the same sequence, once per layer.)
-} // namespace
-std::vector<Pk> grk_amd::packet_order(const std::vector<const TileGeom*>& cg, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0,
-                             uint32_t order)
-{
-    const uint32_t ncomp = (uint32_t)cg.size();
-    const grk_amd_tile_params& p = cg[0]->p;
-    std::vector<Pk> prec;                                   // every precinct of the tile: component-major, resolution-major, raster
-    for (uint32_t c = 0; c < ncomp; ++c) {
-        const TileGeom& g = *cg[c];
-        const uint64_t dx = comp_dx && comp_dx[c] ? comp_dx[c] : 1, dy = comp_dy && comp_dy[c] ? comp_dy[c] : 1;
-        for (uint32_t r = 0; r <= p.num_levels; ++r) {
-            const ResGeom& R = g.res[r];
-            const uint32_t sh = p.num_levels - r;
-            for (uint32_t pj = 0; pj < R.nph; ++pj)
-                for (uint32_t pi = 0; pi < R.npw; ++pi) {
-                    const uint64_t cx = (((uint64_t)((R.x0 >> R.ppx) + pi) << R.ppx) << sh) * dx, cy = (((uint64_t)((R.y0 >> R.ppy) + pj) << R.ppy) << sh) * dy;
-                    prec.push_back(Pk{c, r, pj * R.npw + pi, std::max<uint64_t>(cx, gx0), std::max<uint64_t>(cy, gy0)});
-                }
-        }
-    }
-    // (stable sorts of the component-major, resolution-major, raster list: the keys named, everything else in that order)
-    if (order <= 1)                // resolution, component, precinct
-        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) { return a.r != b.r ? a.r < b.r : a.c < b.c; });
-    else if (order == 2)           // resolution, position, component
-        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) {
-            return a.r != b.r ? a.r < b.r : a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.c < b.c; });
-    else if (order == 3)           // position, component, resolution
-        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) {
-            return a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.c != b.c ? a.c < b.c : a.r < b.r; });
-    else                           // component, position, resolution
-        std::stable_sort(prec.begin(), prec.end(), [](const Pk& a, const Pk& b) {
-            return a.c != b.c ? a.c < b.c : a.y != b.y ? a.y < b.y : a.x != b.x ? a.x < b.x : a.r < b.r; });
-    return prec;
-}
-namespace {
+// in raster order, several resolutions / components can share one.  (The sequence is packet_order's: t2_order.h, defined in
+// geometry.cpp, where the grouping of tiles compares it too -- the codestream reader walks the same sequence, once per layer.)
 
 // a packet's length as the PLT marker segment carries it: a big-endian base-128 number (continuation bit 0x80)
 void plt_length(std::vector<uint8_t>& body, uint64_t v)

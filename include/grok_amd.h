@@ -465,7 +465,12 @@ int64_t grk_amd_plan_tile_part(const grk_amd_tile_params* p, uint32_t tile_index
  * SOP / EPH / PROG as grk_amd_write_tile_part, whose bytes these are.  part_bytes[i] (optional) = tile-part i's length (what TLM and
  * the caller's placement need).  Returns the bytes assembled by this call, or < 0.  Three kernels (packet headers; the tile-parts' frames
  * and everybody's place; the gather) and one wait for the sizes; the ~100 MB of an 8K frame's code-blocks are moved once, on the device,
- * to where the file has them. */
+ * to where the file has them.
+ * Precondition: ONE packet sequence frames the whole call -- that of a tile at *p's origin (tile_x0, tile_y0) in the progression order
+ * of `flags`.  Tiles of one geometry (grk_amd_same_tile_geometry) share it for LRCP and RLCP; from RPCL on the sequence also depends on
+ * where a tile lies on the reference grid, and only tiles for which grk_amd_same_tile_packets(p, tile, flags) is 1 may share the call:
+ * any other tile's packets would be written in *p's order, which nothing here can detect (the call never sees the tiles' own origins).
+ * tile_index[i] <= 65 535 (Isot is 16 bits), else GRK_AMD_ERR_INVALID. */
 int64_t grk_amd_assemble_device(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
                                 uint32_t flags, uint64_t dst_offset, uint32_t* part_bytes);
 void* grk_amd_assembled_device_ptr(grk_amd_ctx* ctx);
@@ -473,7 +478,8 @@ void* grk_amd_assembled_device_ptr(grk_amd_ctx* ctx);
  * nothing is waited for, nothing comes to the host.  The tile-parts (grk_amd_assembled_device_ptr), their places and lengths and the total
  * (grk_amd_assembled_table_ptr -- 0: uint64[tiles] offsets, 1: uint32[tiles] lengths, 2: uint64[2] {bytes assembled, end}) stay where they are
  * for as many further calls as the encoder rotates buffer sets (grk_amd_set_pipelining): what an exchange needs to send FINISHED tile-parts
- * from device memory ("gather of coded tile-parts over xGMI").  Every asynchronous call of a context uses the same stream. */
+ * from device memory ("gather of coded tile-parts over xGMI").  Every asynchronous call of a context uses the same stream.
+ * The same precondition: every tile of the call is framed with the packet order of a tile at *p's origin (grk_amd_same_tile_packets). */
 int grk_amd_assemble_device_async(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
                                   uint32_t flags, void* hip_stream);
 void* grk_amd_assembled_table_ptr(grk_amd_ctx* ctx, int which);
@@ -498,6 +504,13 @@ int grk_amd_layout_tile(const grk_amd_image_layout* im, const grk_amd_tile_param
 /* 1 when two tiles can share one grk_amd_encode_tiles / grk_amd_decode_tiles batch: same sub-band and code-block partition,
  * same lifting variant at every level (0: they cannot, < 0: error) */
 int grk_amd_same_tile_geometry(const grk_amd_tile_params* a, const grk_amd_tile_params* b);
+/* 1 when the two tiles can ALSO share one grk_amd_assemble_device(_async) call under the progression order of `flags`
+ * (GRK_AMD_CS_PROG): the same number of components, the same geometry and the same sequence of packets (component, resolution,
+ * precinct).  That call frames every tile with the packet order of a tile at its p's origin; for PCRL and CPRL (and, as far as the
+ * comparison goes, RPCL) the order depends on where the precinct corners of the resolutions coincide once clipped to the tile, which
+ * grk_amd_same_tile_geometry does not compare.  For LRCP and RLCP this is grk_amd_same_tile_geometry plus the component count.
+ * (0: they cannot, < 0: error).  Host only. */
+int grk_amd_same_tile_packets(const grk_amd_tile_params* a, const grk_amd_tile_params* b, uint32_t flags);
 /* The codestream of such an image: table = the tiles' rows one tile after the other, tile t having the
  * grk_amd_tile_num_blocks() rows of ITS parameters (grk_amd_layout_tile).  grk_amd_write_codestream(_ex) is this with the
  * layout {origin of p, img_w x img_h, tiles of p->tile_w x p->tile_h}. */

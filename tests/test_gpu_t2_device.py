@@ -112,6 +112,23 @@ def test_refuses_what_it_cannot_assemble():
     n, _ = c.assemble_device(p, [0])
     with pytest.raises(RuntimeError):
         c.assemble_device(p, [0], dst_offset=n + 1)     # a hole in the output
+    # Isot is 16 bits: 65 535 is the last tile index a tile-part can carry
+    with pytest.raises(RuntimeError, match=r"failed: -3 .*Isot"):
+        c.assemble_device(p, [65536])
+    with pytest.raises(RuntimeError, match=r"failed: -3 .*Isot"):
+        c.assemble_device(p, [0xFFFFFFFF])
+    n, lens = c.assemble_device(p, [65535])
+    part = bytes(c.fetch_assembled(0, n))
+    assert int(lens[0]) == n and part[:4] == b"\xff\x90\x00\x0a" and part[4:6] == b"\xff\xff"
+    # a fetch past the end of what was assembled is refused and copies nothing -- also where offset + nbytes wraps around 2^64
+    import ctypes as C
+    for fetch in (c._L.grk_amd_fetch_assembled, c._L.grk_amd_fetch_assembled_async):
+        fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        for offset, nbytes in (((1 << 64) - 8, 16), (n, 1), (n - 8, 9), (n + 1, 0), (0, (1 << 64) - 1)):
+            dst = np.full(64, 0xA5, np.uint8)
+            assert fetch(c._h, offset, nbytes, dst.ctypes.data) == G.capi.ERR_INVALID, (offset, nbytes)
+            assert (dst == 0xA5).all(), (offset, nbytes)
+    assert bytes(c.fetch_assembled(n - 8, 8)) == part[-8:]
 
 
 def test_plt_of_many_packets_splits_into_marker_segments_on_the_device():

@@ -11,6 +11,7 @@ from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Cont
                    StreamInfo, ReaderError, read_header, read_packets, stream_comp_sizes,
                    ImageView, image_view_size, plan_image_view,
                    Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, SURFACE_FORMATS_MSB, surface_bytes, surface_plan,
+                   PACKED_FORMATS, packed_bytes,
                    CS_BLOCK_MSBS, DROP_SKIP, Rate, RateResult, RateError)
 
 __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
@@ -19,4 +20,5 @@ __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "C
            "StreamInfo", "ReaderError", "read_header", "read_packets", "stream_comp_sizes",
            "ImageView", "image_view_size", "plan_image_view",
            "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "SURFACE_FORMATS_MSB", "surface_bytes", "surface_plan",
+           "PACKED_FORMATS", "packed_bytes",
            "CS_BLOCK_MSBS", "DROP_SKIP", "Rate", "RateResult", "RateError"]

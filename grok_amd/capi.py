@@ -228,6 +228,21 @@ def surface_plan(layout, base, sampling, surface, cap, base_align=0, decode=Fals
     return [(bool(flags[r]), lays[r], int(at[r])) for r in range(n)]
 
 
+PACKED_FORMATS = {"YUY2": 0, "UYVY": 1, "YVYU": 2, "Y216": 3, "V210": 4}
+
+
+def packed_bytes(fmt, layout, prec, pitch=0):
+    """A packed 4:2:2 frame (a name of PACKED_FORMATS or the format's number) for the image area of `layout` at `prec` bits
+    (grk_amd_packed_bytes) -> (bytes from the base to the end of the last row's last container, the pitch: `pitch`, or the format's
+    default for 0); SurfaceError with the refusal's code and reason"""
+    p, why = C.c_uint64(int(pitch)), C.c_char_p()
+    n = lib().grk_amd_packed_bytes(PACKED_FORMATS.get(fmt, fmt), C.byref(layout), int(prec), C.byref(p), C.byref(why))
+    if n == 0:
+        reason = (why.value or b"").decode()
+        raise SurfaceError("packed_bytes", -2 if "odd x0" in reason else -3, reason)
+    return int(n), int(p.value)
+
+
 VIEW_UNIT_DTYPE = np.dtype([("tile", np.uint32), ("first_comp", np.uint32), ("num_comps", np.uint32), ("w", np.uint32), ("h", np.uint32),
                             ("x", np.int32), ("y", np.int32), ("whole", np.uint32)])
 
@@ -411,6 +426,18 @@ def lib():
             L.grk_amd_surface_counters.argtypes = [vp, i32]
             L.grk_amd_surface_cut_device.argtypes = [vp, vp, u64, C.POINTER(SurfaceComp), u32, u32, u32, u32, u32, vp, vp]
             L.grk_amd_surface_place_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, C.POINTER(SurfaceComp), vp, u64]
+        if hasattr(L, "grk_amd_encode_packed"):
+            L.grk_amd_packed_bytes.restype = u64
+            L.grk_amd_packed_bytes.argtypes = [i32, PL, u32, C.POINTER(u64), C.POINTER(C.c_char_p)]
+            L.grk_amd_encode_packed.restype = C.c_int64
+            L.grk_amd_encode_packed.argtypes = [vp, PL, PP, i32, u64, vp, u64, i32, u32, vp, u64]
+            L.grk_amd_encode_packed_rate.restype = C.c_int64
+            L.grk_amd_encode_packed_rate.argtypes = [vp, PL, PP, i32, u64, vp, u64, i32, u32, C.POINTER(Rate), vp, u64, C.POINTER(RateResult)]
+            L.grk_amd_decode_packed.argtypes = [vp, vp, u64, i32, u64, vp, u64, i32]
+            L.grk_amd_packed_unpack_device.argtypes = [vp, i32, u32, u32, u32, vp, u64, u64, vp, u64]
+            L.grk_amd_packed_pack_device.argtypes = [vp, i32, u32, u32, u32, vp, u64, vp, u64, u64]
+            L.grk_amd_packed_counters.restype = u64
+            L.grk_amd_packed_counters.argtypes = [vp, i32]
         _lib = L
     return _lib
 
@@ -853,6 +880,66 @@ class Context:
         rc = self._L.grk_amd_surface_place_device(self._h, d_tiles, nunits, w, h, len(comps), bps, r.ctypes.data, cs, d_surface, int(surface_bytes))
         if rc:
             self._surface_fail("surface_place_device", rc)
+
+    @staticmethod
+    def _frame_arg(pixels, cap):
+        """a frame or surface argument: a contiguous uint8 numpy array (host) or a device pointer (int) with `cap` -> (ptr, bytes, on_device)"""
+        if not isinstance(pixels, np.ndarray):
+            return int(pixels), int(cap), 1
+        if pixels.dtype != np.uint8 or not pixels.flags.c_contiguous:
+            raise ValueError("pixels: a contiguous uint8 array")
+        return pixels.ctypes.data, pixels.nbytes if cap is None else int(cap), 0
+
+    def encode_packed(self, layout, base, fmt, pixels, pitch=0, flags=0, cap=None):
+        """A packed 4:2:2 frame (a name of PACKED_FORMATS or the format's number; pitch 0 = the format's default) -> codestream bytes
+        (grk_amd_encode_packed).  pixels: a uint8 numpy array holding the frame (host), or a device pointer (int) together with `cap`"""
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        out_cap = nbytes * 4 + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        n = self._L.grk_amd_encode_packed(self._h, C.byref(layout), C.byref(base), PACKED_FORMATS.get(fmt, fmt), int(pitch), ptr, nbytes, on_device,
+                                          flags, out.ctypes.data, out_cap)
+        if n < 0:
+            self._surface_fail("encode_packed", n)
+        return out[:n].tobytes()
+
+    def encode_packed_rate(self, layout, base, fmt, pixels, target_bytes, pitch=0, flags=0, cap=None, max_drop=0, allow_skip=False):
+        """grk_amd_encode_packed_rate: encode_packed in a file of at most target_bytes -> (codestream bytes, RateResult)"""
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        out_cap = nbytes * 4 + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), 1), RateResult()
+        n = self._L.grk_amd_encode_packed_rate(self._h, C.byref(layout), C.byref(base), PACKED_FORMATS.get(fmt, fmt), int(pitch), ptr, nbytes,
+                                               on_device, flags, C.byref(rate), out.ctypes.data, out_cap, C.byref(res))
+        if n < 0:
+            raise RateError("encode_packed_rate", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def decode_packed(self, cs, fmt, pixels, pitch=0, cap=None):
+        """Codestream -> a packed 4:2:2 frame (grk_amd_decode_packed); what is no sample keeps its value.  pixels: a uint8 numpy array
+        (host: written in place) or a device pointer (int) with `cap` (asynchronous: decode_status joins)."""
+        buf = _cs_array(cs)
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        rc = self._L.grk_amd_decode_packed(self._h, buf.ctypes.data, buf.size, PACKED_FORMATS.get(fmt, fmt), int(pitch), ptr, nbytes, on_device)
+        if rc:
+            self._surface_fail("decode_packed", rc)
+
+    def packed_unpack_device(self, fmt, prec, w, h, d_packed, pitch, packed_bytes, d_planes, planes_bytes):
+        """KU alone: the frame at d_packed -> tight planes Y, Cb, Cr back to back at d_planes (device pointers; queued on the stream)"""
+        rc = self._L.grk_amd_packed_unpack_device(self._h, PACKED_FORMATS.get(fmt, fmt), int(prec), int(w), int(h), d_packed, int(pitch),
+                                                  int(packed_bytes), d_planes, int(planes_bytes))
+        if rc:
+            self._surface_fail("packed_unpack_device", rc)
+
+    def packed_pack_device(self, fmt, prec, w, h, d_planes, planes_bytes, d_packed, pitch, packed_bytes):
+        """KK alone (the reverse)"""
+        rc = self._L.grk_amd_packed_pack_device(self._h, PACKED_FORMATS.get(fmt, fmt), int(prec), int(w), int(h), d_planes, int(planes_bytes),
+                                                d_packed, int(pitch), int(packed_bytes))
+        if rc:
+            self._surface_fail("packed_pack_device", rc)
+
+    def packed_counters(self):
+        """(launches of the unpack kernel, launches of the pack kernel) by this context so far"""
+        return tuple(int(self._L.grk_amd_packed_counters(self._h, k)) for k in range(2))
 
     def fetch_table(self, nblocks):
         table = np.zeros(nblocks, CODED_DTYPE)

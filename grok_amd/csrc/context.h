@@ -222,6 +222,10 @@ struct grk_amd_ctx {
     // grk_amd_encode_surface / grk_amd_decode_surface share those buffers: img_pixels a host surface's copy, img_tiles a group's staged
     // units, img_rects the units' origins; units handled in place, units staged, launches of KS + KD (grk_amd_surface_counters)
     uint64_t surf_counters[3] = {0, 0, 0};
+    // grk_amd_encode_packed / grk_amd_decode_packed (packed.cpp): the frame's three tight planes, each from a 256-byte boundary -- the
+    // device surface that the surface calls above then work on; a host frame's copy lies in img_pixels; launches of KU, of KK
+    DevBuf img_planes;
+    uint64_t packed_counters[2] = {0, 0};
     // timing
     bool timing = false;
     Timer timers[10];
@@ -267,6 +271,19 @@ namespace grk_amd { struct ResolvedSurface; struct CompRun; }
 int queue_surface_kernel(grk_amd_ctx* c, bool place, const grk_amd::ResolvedSurface& rs, const grk_amd::CompRun& run, void* d_surface,
                          void* d_tiles, uint32_t count, uint32_t w, uint32_t h, const uint32_t* d_origins);                  // surface.cpp
 bool surface_direct_allowed();            // GRK_AMD_SURFACE_DIRECT != 0, read per call (surface.cpp)
+// grk_amd_encode_surface / grk_amd_encode_surface_rate behind their null checks: what the packed calls (packed.cpp) enter too
+int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                           const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
+                           uint32_t flags, uint8_t* out, uint64_t out_cap);                                                  // surface.cpp
+int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                                const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
+                                uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);   // surface.cpp
+// grk_amd_decode_surface behind its null checks (`name`: the entry point, for a refusal's text); host_rules: a device surface under
+// the rules of a host destination -- a group that leaves the int16 planes is repeated by the call itself
+int decode_onto_surface(grk_amd_ctx* c, const char* name, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels,
+                        uint64_t cap, int pixels_on_device, bool host_rules);                                                 // decode_image.cpp
+// what the whole-image decodes refuse on the context: a decode reduce (`reduced`: the text behind the entry point's name), a decode sequence
+int refuse_context(grk_amd_ctx* c, const char* name, const char* reduced);                                                    // decode_image.cpp
 
 // a pixel layout of the context that a call sets for its own batches, put back when the call ends (KeepLayout keep{slot, slot};)
 struct KeepLayout { grk_amd_pixel_layout& slot; grk_amd_pixel_layout keep; ~KeepLayout() { slot = keep; } };

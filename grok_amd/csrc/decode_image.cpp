@@ -134,10 +134,14 @@ extern "C" int grk_amd_place_tiles_clipped_device(grk_amd_ctx* c, const void* ti
 }
 
 // surf != nullptr (grk_amd_decode_surface): the destination is the caller's surface as *surf describes it -- every component at its own
-// size wherever it lies there, sub-sampled or not; the surface is resolved against the stream's header by the plan
+// size wherever it lies there, sub-sampled or not; the surface is resolved against the stream's header by the plan.
+// host_rules: the call behaves as one with a host destination does -- it joins behind a group that may leave the int16 planes and
+// repeats it with int32 planes by itself.  That is every call with host pixels, and the packed decode of a host frame (packed.cpp),
+// whose planes lie in device memory all the same.
 static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap, int pixels_on_device,
-                       const grk_amd_surface* surf = nullptr)
+                       const grk_amd_surface* surf = nullptr, bool host_rules = false)
 {
+    host_rules = host_rules || !pixels_on_device;
     // header -> view plan -> destination plan: every refusal that needs no byte of a packet
     grk_amd_stream_info info;
     std::string why;
@@ -238,7 +242,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         // The int16-plane rule (include/grok_amd.h, grk_amd_set_decode_planes16).  A decode into a device buffer does not repeat
         // itself: with host pixels this call joins behind a group that may use those planes, reads its status and repeats it
         // with int32 planes; with device pixels the status goes to grk_amd_decode_status like any other
-        if (!pixels_on_device && c->dec_planes16 && d.ht && !p.irreversible && p.prec <= 8) {
+        if (host_rules && c->dec_planes16 && d.ht && !p.irreversible && p.prec <= 8) {
             drc = grk_amd_decode_status(c);
             if (drc == GRK_AMD_ERR_RANGE) {
                 c->dec_planes16 = false;
@@ -304,7 +308,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
 }
 
 // what the three whole-image entry points refuse on the context (`reduced`: the text behind the entry point's name)
-static int refuse_context(grk_amd_ctx* c, const char* name, const char* reduced)
+int refuse_context(grk_amd_ctx* c, const char* name, const char* reduced)
 {
     if (c->dec_reduce) return fail(c, GRK_AMD_ERR_UNSUPPORTED, (std::string(name) + reduced).c_str());
     if (!c->dec_kids.empty()) return fail(c, GRK_AMD_ERR_UNSUPPORTED, (std::string(name) + " on a context with a decode sequence (grk_amd_set_decode_pipelining)").c_str());
@@ -318,12 +322,20 @@ extern "C" int grk_amd_decode_image(grk_amd_ctx* c, const uint8_t* cs, uint64_t 
     return decode_view(c, cs, len, nullptr, pixels, cap, pixels_on_device);
 }
 
+// grk_amd_decode_surface behind its null checks, and the way in of grk_amd_decode_packed (packed.cpp: `name`), whose surface is the
+// context's own three planes: in device memory, under a host destination's rules where the caller's frame lies on the host
+int decode_onto_surface(grk_amd_ctx* c, const char* name, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels, uint64_t cap,
+                        int pixels_on_device, bool host_rules)
+{
+    const int rc = refuse_context(c, name, " at reduced resolution"); if (rc) return rc;
+    return decode_view(c, cs, len, nullptr, pixels, cap, pixels_on_device, surface, host_rules);
+}
+
 extern "C" int grk_amd_decode_surface(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels, uint64_t cap,
                                       int pixels_on_device)
 {
     if (!c || !cs || !pixels || !surface) return GRK_AMD_ERR_INVALID;
-    const int rc = refuse_context(c, "grk_amd_decode_surface", " at reduced resolution"); if (rc) return rc;
-    return decode_view(c, cs, len, nullptr, pixels, cap, pixels_on_device, surface);
+    return decode_onto_surface(c, "grk_amd_decode_surface", cs, len, surface, pixels, cap, pixels_on_device, false);
 }
 
 extern "C" int grk_amd_decode_image_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap,

@@ -367,4 +367,15 @@ struct SurfaceArgs {
 hipError_t launch_surface_cut(const SurfaceArgs& a, hipStream_t s);
 hipError_t launch_surface_place(const SurfaceArgs& a, hipStream_t s);
 
+// ---- KU / KK: a packed 4:2:2 frame (packed_format.h) and its three tight planes (kernels_packed.hip) ---------------------------
+// Row r of the frame starts at packed + r * pitch; y is w x h, cb and cr ceil(w / 2) x h, tight, LSB-aligned samples of one byte
+// (prec <= 8) or two, at any address.  The host checked format, precision, the frame's alignment and every size (packed.cpp).
+struct PackedArgs {
+    uint8_t* packed; uint64_t pitch;
+    uint8_t *y, *cb, *cr;
+    uint32_t w, h, format, prec;
+};
+hipError_t launch_packed_unpack(const PackedArgs& a, hipStream_t s);
+hipError_t launch_packed_pack(const PackedArgs& a, hipStream_t s);
+
 } // namespace grk_amd

@@ -193,11 +193,12 @@ struct SurfaceJob {
 
 } // namespace
 
-extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
-                                          const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
-                                          const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap)
+// grk_amd_encode_surface behind its null checks -- and grk_amd_encode_packed's way in (packed.cpp), whose surface is the context's
+// own three planes in device memory
+int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                           const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
+                           uint32_t flags, uint8_t* out, uint64_t out_cap)
 {
-    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out) return GRK_AMD_ERR_INVALID;
     SurfaceJob job{c};
     int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);
     if (rc) return rc;
@@ -222,12 +223,19 @@ extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_la
     return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, out_cap);
 }
 
-extern "C" int64_t grk_amd_encode_surface_rate(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
-                                               const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
-                                               const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
-                                               const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result)
+extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                          const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                          const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap)
 {
-    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out || !rate) return GRK_AMD_ERR_INVALID;
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out) return GRK_AMD_ERR_INVALID;
+    return encode_surface_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, out, out_cap);
+}
+
+// the same for grk_amd_encode_surface_rate and grk_amd_encode_packed_rate
+int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                                const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
+                                uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result)
+{
     { const int rr = rate_refusal(c, rate); if (rr) return rr; }
     flags |= GRK_AMD_CS_BLOCK_MSBS;
     SurfaceJob job{c};
@@ -242,4 +250,13 @@ extern "C" int64_t grk_amd_encode_surface_rate(grk_amd_ctx* c, const grk_amd_ima
         return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows, coded, flags, o, ocap);
     };
     return encode_rate_joint(c, call, out, out_cap, result);
+}
+
+extern "C" int64_t grk_amd_encode_surface_rate(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                               const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                               const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                               const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out || !rate) return GRK_AMD_ERR_INVALID;
+    return encode_surface_rate_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, rate, out, out_cap, result);
 }

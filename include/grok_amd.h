@@ -930,6 +930,62 @@ int grk_amd_surface_cut_device(grk_amd_ctx* ctx, const void* surface, uint64_t s
 int grk_amd_surface_place_device(grk_amd_ctx* ctx, const void* tiles, uint32_t nunits, uint32_t w, uint32_t h, uint32_t ncomp, uint32_t bps,
                                  const uint32_t* origins, const grk_amd_surface_comp* comps, void* surface, uint64_t surface_bytes);
 
+/* ---- packed 4:2:2 video frames: YUY2, UYVY, YVYU, Y210 / Y212 / Y216, v210 (packed_format.h, packed.cpp, kernels_packed.hip) ------
+ * What a capture card (UYVY, v210) and Direct3D / VA-API (YUY2, Y210, Y216) hand out: ONE pitched frame whose components differ in
+ * step -- no grk_amd_surface.  Always three components Y, Cb, Cr with factors (1, 1), (2, 1), (2, 1), no colour transform; sample
+ * (0, 0) of the frame is the image area's first luma sample, whose x0 must be even.  For an area of w x h the luma plane is w x h,
+ * each chroma plane cw x h with cw = ceil(w / 2); macropixel m of a row holds Y[2m], Y[2m + 1], Cb[m], Cr[m]:
+ *   YUY2 / UYVY / YVYU  4 bytes: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 / Y0 Cr Y1 Cb; prec 1..8; any base, pitch 0 = 4 cw
+ *   Y216                4 little-endian 16-bit words Y0 Cb Y1 Cr, each v << (16 - prec); prec 9..16 (10: Y210, 12: Y212); base and
+ *                       pitch even, pitch 0 = 8 cw
+ *   V210                a 16-byte block of four little-endian dwords with 10-bit fields at bits 0-9, 10-19, 20-29 (30-31 zero) holds
+ *                       three macropixels -- block b of a row: w0 = Cb[3b] | Y[6b] << 10 | Cr[3b] << 20, w1 = Y[6b+1] | Cb[3b+1] << 10 |
+ *                       Y[6b+2] << 20, w2 = Cr[3b+1] | Y[6b+3] << 10 | Cb[3b+2] << 20, w3 = Y[6b+4] | Cr[3b+2] << 10 | Y[6b+5] << 20;
+ *                       prec exactly 10; a row is ceil(w / 6) blocks; base and pitch multiples of 16, pitch 0 = ceil(w / 48) * 128
+ * An encode ignores the low 16 - prec bits of a Y216 word, bits 30-31 of a v210 dword and every field past the width (Y1 of an odd
+ * width's last macropixel, the unused fields of the last v210 block).  A decode writes exactly the bytes of samples (an odd width's
+ * last Y1 and everything between a row's end and the pitch keep their values); v210: every block that holds a sample is written
+ * whole, fields past the width and bits 30-31 as zero, the bytes behind a row's last block keep their values.
+ * One kernel pair moves the frame to and from three tight planes that the context owns (each from a 256-byte boundary, so that a
+ * one-tile image's planes take the in-place routes of grk_amd_surface_plan); between them the calls are the surface calls above on
+ * that device surface.  The context's pixel layouts, upsample switch and QCD words are neither consulted nor left changed.
+ * Refusals, before any GPU work (the reason: *why, or grk_amd_last_error) -- GRK_AMD_ERR_INVALID: an unknown format, a precision
+ * outside the format's range, a pitch below a row, a pitch or a device base off the format's alignment, num_comps != 3, mct != 0;
+ * GRK_AMD_ERR_UNSUPPORTED: an odd x0, and on decode a stream whose SIZ is not 3 components with factors (1, 1), (2, 1), (2, 1) and a
+ * precision of the format; GRK_AMD_ERR_OVERFLOW: grk_amd_packed_bytes > cap.  What the surface and rate calls refuse is passed on. */
+#define GRK_AMD_PACKED_YUY2 0
+#define GRK_AMD_PACKED_UYVY 1
+#define GRK_AMD_PACKED_YVYU 2
+#define GRK_AMD_PACKED_Y216 3
+#define GRK_AMD_PACKED_V210 4
+/* host only: *pitch (0 on entry = the format's default) checked and filled in; returns the bytes from the base to the end of the
+ * last row's last container, 0 + *why (may be NULL; a string of the library's) on a refusal */
+uint64_t grk_amd_packed_bytes(int format, const grk_amd_image_layout* im, uint32_t prec, uint64_t* pitch, const char** why);
+/* Packed frame -> codestream: byte-identical to grk_amd_encode_image_subsampled for the same samples as tight planes with factors
+ * (1, 1), (2, 1), (2, 1) and the same flags (any tile layout, precincts, the five orders); base: num_comps 3, mct 0, prec as the
+ * format allows.  pixels: host or (pixels_on_device != 0) device memory, `cap` bytes; a host frame goes up as one copy. */
+int64_t grk_amd_encode_packed(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
+                              const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap);
+/* ... in a file of at most rate->target_bytes: exactly grk_amd_encode_image_subsampled_rate's file for the same target */
+int64_t grk_amd_encode_packed_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
+                                   const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_rate* rate,
+                                   uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);
+/* Codestream -> packed frame: component c of the frame is plane c of grk_amd_decode_image, written by the rules above.  A host
+ * frame is uploaded, packed into and downloaded (what is no sample stays); the call is synchronous and repeats a group that leaves
+ * the int16 planes by itself, as grk_amd_decode_surface does.  A device frame: the pack kernel is queued on the context's stream
+ * behind the decode; grk_amd_decode_status joins and reports, GRK_AMD_ERR_RANGE included. */
+int grk_amd_decode_packed(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len, int format, uint64_t pitch, void* pixels, uint64_t cap,
+                          int pixels_on_device);
+/* The two kernels alone (device pointers; queued on the context's stream).  planes: Y (w x h), Cb, Cr (cw x h each), tight, back
+ * to back, samples of bps = prec <= 8 ? 1 : 2 bytes, LSB-aligned, at any address; pitch 0 = the format's default.  The frame's
+ * rules are those above (GRK_AMD_ERR_INVALID); GRK_AMD_ERR_OVERFLOW for a planes_bytes or packed_bytes that is too small. */
+int grk_amd_packed_unpack_device(grk_amd_ctx* ctx, int format, uint32_t prec, uint32_t w, uint32_t h, const void* packed, uint64_t pitch,
+                                 uint64_t packed_bytes, void* planes, uint64_t planes_bytes);
+int grk_amd_packed_pack_device(grk_amd_ctx* ctx, int format, uint32_t prec, uint32_t w, uint32_t h, const void* planes, uint64_t planes_bytes,
+                               void* packed, uint64_t pitch, uint64_t packed_bytes);
+/* cumulative per context: which = 0 launches of the unpack kernel, 1 of the pack kernel */
+uint64_t grk_amd_packed_counters(grk_amd_ctx* ctx, int which);
+
 /* ---- one image over the GPUs of a node (node.cpp) -------------------------------------------------------
  * Replaces the reference's tile-level task pool (codestream/CodeStreamCompress.cpp:535-603: tiles are independent tasks whose
  * tile-parts are written in index order) with one grk_amd_ctx + one host thread per device: tile t is coded on device

@@ -438,6 +438,13 @@ def lib():
             L.grk_amd_packed_pack_device.argtypes = [vp, i32, u32, u32, u32, vp, u64, vp, u64, u64]
             L.grk_amd_packed_counters.restype = u64
             L.grk_amd_packed_counters.argtypes = [vp, i32]
+        if hasattr(L, "grk_amd_encode_route_counters"):
+            L.grk_amd_encode_surface_device.restype = C.c_int64
+            L.grk_amd_encode_surface_device.argtypes = [vp, PL, PP, pu8, pu8, PS, vp, u64, i32, u32, C.POINTER(vp)]
+            L.grk_amd_encode_packed_device.restype = C.c_int64
+            L.grk_amd_encode_packed_device.argtypes = [vp, PL, PP, i32, u64, vp, u64, i32, u32, C.POINTER(vp)]
+            L.grk_amd_encode_route_counters.restype = u64
+            L.grk_amd_encode_route_counters.argtypes = [vp, i32]
         _lib = L
     return _lib
 
@@ -845,6 +852,33 @@ class Context:
         if n < 0:
             self._surface_fail("encode_surface", n)
         return out[:n].tobytes()
+
+    def encode_surface_device(self, layout, base, sampling, surface, pixels, flags=0, cap=None):
+        """grk_amd_encode_surface_device: the file left in device memory -> (device pointer, length); the bytes belong to the context
+        and stay valid until its next encode call.  pixels as encode_surface takes them."""
+        dx, dy = _sampling(sampling)
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        d_file = C.c_void_p(0)
+        n = self._L.grk_amd_encode_surface_device(self._h, C.byref(layout), C.byref(base), dx, dy, C.byref(surface), ptr, nbytes, on_device,
+                                                  flags, C.byref(d_file))
+        if n < 0:
+            self._surface_fail("encode_surface_device", n)
+        return int(d_file.value), int(n)
+
+    def encode_packed_device(self, layout, base, fmt, pixels, pitch=0, flags=0, cap=None):
+        """grk_amd_encode_packed_device: encode_packed with the file left in device memory -> (device pointer, length)"""
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        d_file = C.c_void_p(0)
+        n = self._L.grk_amd_encode_packed_device(self._h, C.byref(layout), C.byref(base), PACKED_FORMATS.get(fmt, fmt), int(pitch), ptr, nbytes,
+                                                 on_device, flags, C.byref(d_file))
+        if n < 0:
+            self._surface_fail("encode_packed_device", n)
+        return int(d_file.value), int(n)
+
+    def encode_route_counters(self):
+        """(files whose tile-parts were assembled on the device, files written by the host writer) by this context's encode_image_subsampled,
+        encode_surface, encode_packed and _device calls so far"""
+        return tuple(int(self._L.grk_amd_encode_route_counters(self._h, k)) for k in range(2))
 
     def decode_surface(self, cs, surface, pixels, cap=None):
         """Codestream -> the components' samples on a surface (grk_amd_decode_surface); every other byte keeps its value.  pixels: a

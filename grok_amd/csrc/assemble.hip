@@ -1,43 +1,39 @@
 // grok_amd/csrc/assemble.hip -- Tier-2 on the device.
 #include "context.h"
+#include "image.h"
+#include "t2_order.h"
 
-extern "C" {
-// The finished tile-parts of the LATEST grk_amd_encode_tiles call, made where the coded bytes are (kernels_t2.hip): KT1 writes every
-// packet's header, KT1b frames the tile-parts (SOT, PLT, SOD) and says where every packet goes, KT2 gathers headers, code-block bytes
-// and frames into the output.  Nothing has to come to the host in between.
+// The finished tile-parts of coded blocks that lie on the device, made where they are (kernels_t2.hip): KT1 writes every packet's
+// header, KT1b frames the tile-parts (SOT, PLT, SOD) and says where every packet goes, KT2 gathers headers, code-block bytes and frames
+// into the output.  Nothing has to come to the host in between.  grk_amd_assemble_device serves the LATEST grk_amd_encode_tiles call
+// from the context's own table and arena; encode_joint_device (image.h) an image whose units several calls coded, from image-wide
+// tables that KK (kernels_t2keep.hip) filled behind each of them.
 namespace {
-// the kernels queued on `st`, which must already be ordered behind the encode's results; `o` takes the tile-parts from dst_offset on
-// (what lies below is kept when the buffer has to grow).  The scratch is the context's: one stream at a time.
-int assemble_enqueue(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
-                     uint64_t dst_offset, hipStream_t st, grk_amd_ctx::T2Out& o)
+// What one call of the writer frames: `ntiles` tiles of ONE plan (on the host and on the device), whose rows lie tile after tile, bpt
+// per tile, in `lengths` / `offsets` (into `arena`, which holds at most arena_bytes bytes of theirs); the status word the kernels
+// raise their bits in
+struct T2Source {
+    const T2Plan* plan; uint32_t max_blocks; const void* d_packets; const void* d_pob;
+    uint32_t bpt;
+    const uint32_t* lengths; const uint64_t* offsets; const uint8_t* arena; uint64_t arena_bytes;
+    unsigned int* status;
+};
+
+// the kernels queued on `st`, which must already be ordered behind the source's tables and bytes; `o` takes the tile-parts from
+// dst_offset on (what lies below is kept when the buffer has to grow; 16 bytes stay free behind them).  The scratch is the
+// context's: one stream at a time.
+int assemble_enqueue(grk_amd_ctx* c, const T2Source& src, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags, uint64_t dst_offset,
+                     hipStream_t st, grk_amd_ctx::T2Out& o)
 {
-    const TileGeom& g = c->geom;
-    const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
-    if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
-    auto& T = c->t2;
-    if (!T.valid || !same_params(T.p, *p) || T.order != order) {
-        T.valid = false;
-        const int rc = t2_device_plan(g, flags, T.plan);
-        if (rc) return fail(c, rc, "tile layout beyond the device writer's tables");
-        T.max_blocks = 0;
-        for (const T2Packet& k : T.plan.packets) T.max_blocks = std::max(T.max_blocks, k.nblocks);
-        // (the tables of the plan before may still be read by a gather that is queued: drained first)
-        HIP_TRY(c, hipStreamSynchronize(st), "sync");
-        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-        HIP_TRY(c, T.packets.ensure(T.plan.packets.size() * sizeof(T2Packet)), "alloc packet table");
-        HIP_TRY(c, T.pob.ensure(T.plan.packet_of_block.size() * 4), "alloc packet-of-block table");
-        HIP_TRY(c, hipMemcpyAsync(T.packets.p, T.plan.packets.data(), T.plan.packets.size() * sizeof(T2Packet), hipMemcpyHostToDevice, st), "upload");
-        HIP_TRY(c, hipMemcpyAsync(T.pob.p, T.plan.packet_of_block.data(), T.plan.packet_of_block.size() * 4, hipMemcpyHostToDevice, st), "upload");
-        HIP_TRY(c, hipStreamSynchronize(st), "sync");
-        T.p = *p; T.order = order; T.valid = true;
-    }
-    const size_t npk = T.plan.packets.size();
-    const uint32_t bpt = (uint32_t)(c->last_nblocks / ntiles);
+    const T2Plan& plan = *src.plan;
+    const size_t npk = plan.packets.size();
+    const uint32_t bpt = src.bpt;
+    const uint64_t nblocks = (uint64_t)bpt * ntiles;
     const size_t nq = npk * ntiles;
     // a frame: SOT 12, SOD 2, PLT: at most 6 bytes per packet and 5 per marker segment of 65 532
     const uint32_t lit_stride = (uint32_t)((14 + 6 * npk + 5 * (6 * npk / 65000 + 2) + 15) & ~(size_t)15);
     // what the call can write at most: every byte of the arena, every header, every frame
-    const uint64_t bound = (uint64_t)c->arena.cap + (uint64_t)ntiles * (T.plan.h_bytes + lit_stride + 8ull * npk);
+    const uint64_t bound = src.arena_bytes + (uint64_t)ntiles * (plan.h_bytes + lit_stride + 8ull * npk) + 16;
     auto need = [&](DevBuf& b, size_t n, const char* what) -> int {
         if (n <= b.cap) return GRK_AMD_OK;
         // (a scratch buffer about to be replaced may be in use by kernels queued earlier on the stream)
@@ -46,9 +42,9 @@ int assemble_enqueue(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntil
         return GRK_AMD_OK;
     };
     int rc;
-    if ((rc = need(c->t2_u, (size_t)T.plan.u_words * 4 * ntiles + 16, "alloc header bits"))) return rc;
-    if ((rc = need(c->t2_h, (size_t)T.plan.h_bytes * ntiles + 16, "alloc headers"))) return rc;
-    if ((rc = need(c->t2_rel, c->last_nblocks * 4, "alloc block places"))) return rc;
+    if ((rc = need(c->t2_u, (size_t)plan.u_words * 4 * ntiles + 16, "alloc header bits"))) return rc;
+    if ((rc = need(c->t2_h, (size_t)plan.h_bytes * ntiles + 16, "alloc headers"))) return rc;
+    if ((rc = need(c->t2_rel, nblocks * 4, "alloc block places"))) return rc;
     if ((rc = need(c->t2_pkhdr, nq * 4, "alloc packet lengths"))) return rc;
     if ((rc = need(c->t2_pkbody, nq * 8, "alloc packet lengths"))) return rc;
     if ((rc = need(c->t2_pkdst, nq * 8, "alloc packet places"))) return rc;
@@ -62,22 +58,24 @@ int assemble_enqueue(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntil
         DevBuf bigger;
         HIP_TRY(c, hipStreamSynchronize(st), "sync");
         HIP_TRY(c, bigger.ensure(dst_offset + bound), "alloc tile-parts");
-        if (dst_offset) HIP_TRY(c, hipMemcpyAsync(bigger.p, o.out.p, dst_offset, hipMemcpyDeviceToDevice, st), "keep tile-parts");
+        // (a file assembled in place starts behind room for its header: there may be nothing below dst_offset yet)
+        const size_t keep = (size_t)std::min<uint64_t>(dst_offset, o.out.cap);
+        if (keep) HIP_TRY(c, hipMemcpyAsync(bigger.p, o.out.p, keep, hipMemcpyDeviceToDevice, st), "keep tile-parts");
         HIP_TRY(c, hipStreamSynchronize(st), "sync");
         o.out.release();
         o.out = bigger;
     }
-    HIP_TRY(c, hipMemsetAsync(c->t2_u.p, 0, (size_t)T.plan.u_words * 4 * ntiles, st), "clear header bits");
+    HIP_TRY(c, hipMemsetAsync(c->t2_u.p, 0, (size_t)plan.u_words * 4 * ntiles, st), "clear header bits");
     // (the tile numbers: pageable memory of the caller's -- the runtime has staged them when the call returns)
     HIP_TRY(c, hipMemcpyAsync(c->t2_index.p, tile_index, (size_t)ntiles * 4, hipMemcpyHostToDevice, st), "upload");
     T2HeaderArgs ha{};
-    ha.packets = (const T2Packet*)T.packets.p; ha.npackets = (uint32_t)npk;
-    ha.lengths = (const uint32_t*)c->lengths.p; ha.bpt = bpt; ha.ntiles = ntiles;
-    ha.ubits = (uint32_t*)c->t2_u.p; ha.u_words = T.plan.u_words;
-    ha.hdr = (uint8_t*)c->t2_h.p; ha.h_bytes = T.plan.h_bytes;
+    ha.packets = (const T2Packet*)src.d_packets; ha.npackets = (uint32_t)npk;
+    ha.lengths = src.lengths; ha.bpt = bpt; ha.ntiles = ntiles;
+    ha.ubits = (uint32_t*)c->t2_u.p; ha.u_words = plan.u_words;
+    ha.hdr = (uint8_t*)c->t2_h.p; ha.h_bytes = plan.h_bytes;
     ha.rel = (uint32_t*)c->t2_rel.p; ha.pk_hdr = (uint32_t*)c->t2_pkhdr.p; ha.pk_body = (uint64_t*)c->t2_pkbody.p;
-    ha.status = (unsigned int*)c->flag.p;
-    HIP_TRY(c, launch_t2_header(ha, T.max_blocks, st), "launch Tier-2 headers");
+    ha.status = src.status;
+    HIP_TRY(c, launch_t2_header(ha, src.max_blocks, st), "launch Tier-2 headers");
     const uint32_t sop = (flags & GRK_AMD_CS_SOP) ? 6u : 0u, eph = (flags & GRK_AMD_CS_EPH) ? 2u : 0u;
     T2FrameArgs fa{};
     fa.npackets = (uint32_t)npk; fa.ntiles = ntiles; fa.pk_hdr = ha.pk_hdr; fa.pk_body = ha.pk_body;
@@ -86,19 +84,60 @@ int assemble_enqueue(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntil
     fa.lit = (uint8_t*)c->t2_lit.p; fa.lit_stride = lit_stride; fa.lit_len = (uint32_t*)c->t2_litlen.p;
     fa.pk_dst = (uint64_t*)c->t2_pkdst.p;
     fa.part_len = (uint32_t*)o.part_len.p; fa.tile_dst = (unsigned long long*)o.tile_dst.p; fa.total = (unsigned long long*)o.total.p;
-    fa.status = (unsigned int*)c->flag.p;
+    fa.status = src.status;
     HIP_TRY(c, launch_t2_frame(fa, st), "launch Tier-2 frames");
     T2GatherArgs ga{};
-    ga.packets = (const T2Packet*)T.packets.p; ga.npackets = (uint32_t)npk; ga.packet_of_block = (const uint32_t*)T.pob.p;
-    ga.lengths = (const uint32_t*)c->lengths.p; ga.offsets = (const uint64_t*)c->offsets.p; ga.arena = (const uint8_t*)c->arena.p;
+    ga.packets = (const T2Packet*)src.d_packets; ga.npackets = (uint32_t)npk; ga.packet_of_block = (const uint32_t*)src.d_pob;
+    ga.lengths = src.lengths; ga.offsets = src.offsets; ga.arena = src.arena;
     ga.bpt = bpt; ga.ntiles = ntiles;
-    ga.hdr = (const uint8_t*)c->t2_h.p; ga.h_bytes = T.plan.h_bytes;
+    ga.hdr = (const uint8_t*)c->t2_h.p; ga.h_bytes = plan.h_bytes;
     ga.rel = (const uint32_t*)c->t2_rel.p; ga.pk_hdr = (const uint32_t*)c->t2_pkhdr.p; ga.pk_dst = (const uint64_t*)c->t2_pkdst.p;
     ga.lit = (const uint8_t*)c->t2_lit.p; ga.lit_stride = lit_stride; ga.lit_len = (const uint32_t*)c->t2_litlen.p;
     ga.tile_dst = (const unsigned long long*)o.tile_dst.p;
     ga.out = (uint8_t*)o.out.p;
     ga.sop = sop; ga.eph = eph;
     HIP_TRY(c, launch_t2_gather(ga, st), "launch Tier-2 gather");
+    return GRK_AMD_OK;
+}
+
+// a plan's tables on the device, complete on return (what read the buffers' earlier contents is drained first)
+int upload_plan(grk_amd_ctx* c, const T2Plan& plan, DevBuf& packets, DevBuf& pob, hipStream_t st)
+{
+    HIP_TRY(c, hipStreamSynchronize(st), "sync");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    HIP_TRY(c, packets.ensure(plan.packets.size() * sizeof(T2Packet) + 16), "alloc packet table");
+    HIP_TRY(c, pob.ensure(plan.packet_of_block.size() * 4 + 16), "alloc packet-of-block table");
+    HIP_TRY(c, hipMemcpyAsync(packets.p, plan.packets.data(), plan.packets.size() * sizeof(T2Packet), hipMemcpyHostToDevice, st), "upload");
+    HIP_TRY(c, hipMemcpyAsync(pob.p, plan.packet_of_block.data(), plan.packet_of_block.size() * 4, hipMemcpyHostToDevice, st), "upload");
+    HIP_TRY(c, hipStreamSynchronize(st), "sync");
+    return GRK_AMD_OK;
+}
+
+uint32_t plan_max_blocks(const T2Plan& plan)
+{
+    uint32_t m = 0;
+    for (const T2Packet& k : plan.packets) m = std::max(m, k.nblocks);
+    return m;
+}
+
+// the latest grk_amd_encode_tiles call as a source: the context's own table and arena, the plan of its geometry in the order of
+// `flags` -- cached in c->t2 on the call's parameters and the order
+int latest_call_source(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, uint32_t flags, hipStream_t st, T2Source& src)
+{
+    const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
+    auto& T = c->t2;
+    if (!T.valid || !same_params(T.p, *p) || T.order != order) {
+        T.valid = false;
+        int rc = t2_device_plan(c->geom, flags, T.plan);
+        if (rc) return fail(c, rc, "tile layout beyond the device writer's tables");
+        T.max_blocks = plan_max_blocks(T.plan);
+        // (the tables of the plan before may still be read by a gather that is queued: drained first)
+        if ((rc = upload_plan(c, T.plan, T.packets, T.pob, st))) return rc;
+        T.p = *p; T.order = order; T.valid = true;
+    }
+    src = T2Source{&T.plan, T.max_blocks, T.packets.p, T.pob.p, (uint32_t)(c->last_nblocks / ntiles), (const uint32_t*)c->lengths.p,
+                   (const uint64_t*)c->offsets.p, (const uint8_t*)c->arena.p, (uint64_t)c->arena.cap, (unsigned int*)c->flag.p};
     return GRK_AMD_OK;
 }
 
@@ -111,7 +150,241 @@ int assemble_check(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles
         if (tile_index[i] > 65535u) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_assemble_device: a tile index beyond 65 535 (Isot is 16 bits)");
     return GRK_AMD_OK;
 }
+
+// the status word's bits as an error (bits 0-1: K3's, 2: KT1's, 3: KT1b's)
+int status_error(grk_amd_ctx* c, uint64_t word)
+{
+    if (word & 1u) return fail(c, GRK_AMD_ERR_OVERFLOW, "coded arena overflow");
+    if (word & 2u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "coefficient magnitude exceeds Kmax+1 bits");
+    if (word & 4u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a code-block longer than the device writer takes");
+    if (word & 8u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "tile-part beyond 4 GB or packet lengths beyond what PLT can carry");
+    return GRK_AMD_OK;
+}
+
+// ---- the joint route ---------------------------------------------------------------------------------------------------------------
+// The plans of the image's tile classes in c->t2j: made when the image (layout, parameters, factors, order) is not the one they were
+// made for.  A class is framed by ONE assemble_enqueue call, which wants its tiles' rows one tile after the other: the image's tables
+// therefore hold the classes one behind the other, within a class the tiles in order, within a tile the runs in order -- for an
+// image of one class (any single-tile image, any image on its grid) the order of the host writers' tables.
+int joint_plans(grk_amd_ctx* c, const JointT2Call& call)
+{
+    auto& J = c->t2j;
+    const uint32_t flags = call.flags, order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, nr = call.nruns, nc = call.base->num_comps;
+    const UnitGroups& g = *call.g;
+    if (J.valid && std::memcmp(&J.im, call.im, sizeof J.im) == 0 && same_params(J.base, *call.base) && J.order == order && J.dx.size() == nc &&
+        std::memcmp(J.dx.data(), call.comp_dx, nc) == 0 && std::memcmp(J.dy.data(), call.comp_dy, nc) == 0 && J.unit_row.size() == g.of.size())
+        return GRK_AMD_OK;
+    J.valid = false;
+    const uint32_t ntiles = (uint32_t)(g.of.size() / nr);
+    const std::vector<CompRun> runs = comp_runs(nc, call.base->mct != 0, call.comp_dx, call.comp_dy);
+    if (runs.size() != nr || (size_t)ntiles * nr != g.of.size()) return GRK_AMD_ERR_INVALID;
+    // a tile's components as the tile-part writer takes them: cg[c] the geometry of the tile's OWN unit (a group's geometry stands
+    // for its first unit's place on the grid only), row0[c]
+    struct TileComps { std::vector<TileGeom> geoms; std::vector<const TileGeom*> cg; std::vector<uint64_t> row0; grk_amd_tile_params tile; };
+    auto comps_of = [&](uint32_t t, TileComps& tc) -> int {
+        int rc = grk_amd_layout_tile(call.im, call.base, t, &tc.tile);
+        if (rc) return rc;
+        tc.geoms.assign(nr, TileGeom{}); tc.cg.assign(nc, nullptr); tc.row0.assign(nc, 0);
+        uint64_t rows = 0;
+        for (uint32_t k = 0; k < nr; ++k) {
+            grk_amd_tile_params p{};
+            if ((rc = grk_amd_layout_tile_comp(call.im, call.base, call.comp_dx[runs[k].first], call.comp_dy[runs[k].first], t, &p))) return rc;
+            p.num_comps = (uint16_t)runs[k].count; p.mct = runs[k].mct ? 1 : 0;
+            if ((rc = build_tile_geom(p, tc.geoms[k]))) return rc;
+            for (uint32_t i = 0; i < runs[k].count; ++i) { tc.cg[runs[k].first + i] = &tc.geoms[k]; tc.row0[runs[k].first + i] = rows; rows += tc.geoms[k].blocks_per_comp; }
+        }
+        return GRK_AMD_OK;
+    };
+    std::vector<std::vector<Pk>> seq(order >= 2 ? ntiles : 0);
+    TileComps tc;
+    for (uint32_t t = 0; t < (uint32_t)seq.size(); ++t) {
+        const int rc = comps_of(t, tc);
+        if (rc) return rc;
+        seq[t] = packet_order(tc.cg, call.comp_dx, call.comp_dy, tc.tile.tile_x0, tc.tile.tile_y0, order);
+    }
+    std::vector<uint32_t> class_of;
+    const uint32_t nclasses = joint_tile_classes(g.of, nr, order, seq, class_of);
+    // (the tables of the classes before may still be read by a gather that is queued)
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    for (size_t k = nclasses; k < J.classes.size(); ++k) { J.classes[k].packets.release(); J.classes[k].pob.release(); }
+    J.classes.resize(nclasses);
+    for (auto& K : J.classes) K.tiles.clear();
+    for (uint32_t t = 0; t < ntiles; ++t) J.classes[class_of[t]].tiles.push_back(t);
+    J.unit_row.assign(g.of.size(), 0);
+    uint64_t row = 0;
+    for (auto& K : J.classes) {
+        int rc = comps_of(K.tiles[0], tc);
+        if (rc) return rc;
+        if ((rc = t2_device_plan_joint(tc.cg, tc.row0, call.comp_dx, call.comp_dy, tc.tile.tile_x0, tc.tile.tile_y0, flags, K.plan))) return rc;
+        K.max_blocks = plan_max_blocks(K.plan);
+        K.bpt = (uint32_t)K.plan.packet_of_block.size();
+        K.row_begin = row;
+        for (uint32_t t : K.tiles)
+            for (uint32_t k = 0; k < nr; ++k) {
+                const TileGeom& G = g.geoms[g.of[(size_t)t * nr + k]];
+                J.unit_row[(size_t)t * nr + k] = row;
+                row += (uint64_t)G.blocks_per_comp * G.p.num_comps;
+            }
+        if (row - K.row_begin != (uint64_t)K.bpt * K.tiles.size()) return GRK_AMD_ERR_INVALID;
+        if ((rc = upload_plan(c, K.plan, K.packets, K.pob, c->stream))) return rc;
+    }
+    J.rows = row;
+    J.im = *call.im; J.base = *call.base; J.order = order;
+    J.dx.assign(call.comp_dx, call.comp_dx + nc); J.dy.assign(call.comp_dy, call.comp_dy + nc);
+    J.valid = true;
+    return GRK_AMD_OK;
+}
+
+// `b` at least n bytes, its first `keep` bytes kept (the stream drained around the move)
+int grow_keeping(grk_amd_ctx* c, DevBuf& b, size_t n, size_t keep, const char* what)
+{
+    if (n <= b.cap) return GRK_AMD_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    DevBuf bigger;
+    HIP_TRY(c, bigger.ensure(n), what);
+    if (keep) HIP_TRY(c, hipMemcpy(bigger.p, b.p, keep, hipMemcpyDeviceToDevice), what);
+    b.release();
+    b = bigger;
+    return GRK_AMD_OK;
+}
 } // namespace
+
+bool grk_amd::image_t2_host()
+{
+    const char* const e = std::getenv("GRK_AMD_IMAGE_T2");
+    return e && std::strcmp(e, "host") == 0;
+}
+
+int64_t grk_amd::encode_joint_device(grk_amd_ctx* c, const JointT2Call& call, uint8_t* out, uint64_t cap, void** d_file)
+{
+    const uint32_t flags = call.flags, nr = call.nruns;
+    const UnitGroups& g = *call.g;
+    if (!nr || g.of.empty() || g.of.size() % nr || (!out && !d_file)) return GRK_AMD_ERR_INVALID;
+    const uint32_t ntiles = (uint32_t)(g.of.size() / nr);
+    // what the device writer does not reach is said before any batch is coded
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;
+    if ((flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    { const int rc = joint_plans(c, call); if (rc) return rc; }
+    auto& J = c->t2j;
+    // the file's main header does not depend on the lengths it will carry (fixed-width TLM fields): its size now
+    std::vector<uint32_t> part_len(ntiles, 0);
+    const int64_t hdr_bytes = main_header_subsampled(call.im, call.base, call.comp_dx, call.comp_dy, flags, part_len.data(), nullptr, 0);
+    if (hdr_bytes < 0) return hdr_bytes;
+
+    // ---- every batch coded and kept (no host step between them but what grk_amd_encode_tiles has itself) ----
+    const size_t nb = call.batches.size();
+    std::vector<uint64_t> rowlist, batch_at(nb + 1, 0);
+    for (size_t b = 0; b < nb; ++b) {
+        for (uint32_t u : call.batches[b]) { if (u >= J.unit_row.size()) return GRK_AMD_ERR_INVALID; rowlist.push_back(J.unit_row[u]); }
+        batch_at[b + 1] = rowlist.size();
+    }
+    if (rowlist.size() != g.of.size()) return GRK_AMD_ERR_INVALID;           // (every unit in exactly one batch: the sizes at least)
+    // (every call of this route ends synchronised: none of these buffers is in use)
+    HIP_TRY(c, c->jt_len.ensure(J.rows * 4 + 16), "alloc the image's lengths");
+    HIP_TRY(c, c->jt_off.ensure(J.rows * 8 + 16), "alloc the image's offsets");
+    HIP_TRY(c, c->jt_state.ensure((nb + 1) * 8 + 16), "alloc the image's cursors");
+    HIP_TRY(c, c->jt_rowat.ensure(rowlist.size() * 8 + 16), "alloc the units' rows");
+    HIP_TRY(c, hipMemsetAsync(c->jt_state.p, 0, (nb + 1) * 8 + 16, c->stream), "clear the image's cursors");
+    HIP_TRY(c, hipMemcpyAsync(c->jt_rowat.p, rowlist.data(), rowlist.size() * 8, hipMemcpyHostToDevice, c->stream), "upload the units' rows");
+    unsigned long long* const cursors = (unsigned long long*)c->jt_state.p;
+    unsigned int* const status = (unsigned int*)(cursors + nb + 1);
+    uint64_t bound_at = 0;                                   // the batches' arena bounds so far: where the next one's bytes end at most
+    for (size_t b = 0; b < nb; ++b) {
+        const std::vector<uint32_t>& B = call.batches[b];
+        if (B.empty()) return GRK_AMD_ERR_INVALID;
+        const TileGeom& G = g.geoms[g.of[B[0]]];
+        const uint64_t bpu = (uint64_t)G.blocks_per_comp * G.p.num_comps;
+        int rc = call.front(b);
+        if (rc) return rc;
+        if ((rc = join_side(c))) return rc;
+        if (c->last_nblocks != bpu * B.size() || bpu >> 32) return fail(c, GRK_AMD_ERR_INVALID, "a batch's table is not its units'");
+        // the image's arena: sized from the arena K3's plan asked for -- known before the launch, never read back
+        const uint64_t ab = std::min<uint64_t>((c->last_arena_bound + 15u) & ~15ull, (uint64_t)c->arena.cap & ~15ull);
+        if ((rc = grow_keeping(c, c->jt_arena, bound_at + ab + 16, bound_at, "alloc the image's arena"))) return rc;
+        T2KeepArgs ka{};
+        ka.lengths = (const uint32_t*)c->lengths.p; ka.offsets = (const unsigned long long*)c->offsets.p;
+        ka.arena = (const uint8_t*)c->arena.p; ka.arena_bound = ab;
+        ka.batch_state = (const unsigned long long*)c->flag.p;
+        ka.nunits = (uint32_t)B.size(); ka.bpu = (uint32_t)bpu;
+        ka.row_at = (const unsigned long long*)c->jt_rowat.p + batch_at[b];
+        ka.j_lengths = (uint32_t*)c->jt_len.p; ka.j_offsets = (unsigned long long*)c->jt_off.p;
+        ka.j_arena = (uint8_t*)c->jt_arena.p; ka.j_cap = bound_at + ab;
+        ka.cursors = cursors + b; ka.status = status;
+        HIP_TRY(c, launch_t2_keep(ka, c->stream), "launch keep");
+        bound_at += ab;
+    }
+
+    // ---- the tile-parts, class by class, each behind the one before ----
+    // a file in device memory is assembled in place behind its header when the classes' tile-parts come in the file's order
+    bool in_order = true;
+    { uint32_t next = 0; for (const auto& K : J.classes) for (uint32_t t : K.tiles) in_order = in_order && t == next++; }
+    const bool in_place = d_file && in_order;
+    auto& o = c->t2_outs[c->t2_cur];
+    std::vector<uint64_t> dev_at(ntiles, 0);
+    const uint64_t first = in_place ? (uint64_t)hdr_bytes : 0;
+    uint64_t used = first;
+    uint32_t status_word = 0;
+    for (const auto& K : J.classes) {
+        const T2Source src{&K.plan, K.max_blocks, K.packets.p, K.pob.p, K.bpt, (const uint32_t*)c->jt_len.p + K.row_begin,
+                           (const uint64_t*)c->jt_off.p + K.row_begin, (const uint8_t*)c->jt_arena.p, bound_at, status};
+        const int rc = assemble_enqueue(c, src, (uint32_t)K.tiles.size(), K.tiles.data(), flags, used, c->stream, o);
+        if (rc) return rc;
+        // only the tile-parts' lengths (and the status word) come to the host
+        std::vector<uint32_t> lens(K.tiles.size());
+        HIP_TRY(c, hipMemcpyAsync(lens.data(), o.part_len.p, lens.size() * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
+        HIP_TRY(c, hipMemcpyAsync(&status_word, status, 4, hipMemcpyDeviceToHost, c->stream), "fetch status");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+        { const int se = status_error(c, status_word); if (se) return se; }
+        for (size_t i = 0; i < lens.size(); ++i) { part_len[K.tiles[i]] = lens[i]; dev_at[K.tiles[i]] = used; used += lens[i]; }
+    }
+    c->t2_out_used = used;
+
+    if (!d_file) {
+        const int64_t n = frame_file(call.im, call.base, flags, part_len, out, cap, [&](const std::vector<uint64_t>& at) -> int {
+            for (uint32_t t = 0; t < ntiles; ++t) {
+                // (tile-parts that lie one behind the other on the device as in the file go in one piece)
+                uint32_t t1 = t;
+                uint64_t n1 = part_len[t];
+                while (t1 + 1 < ntiles && dev_at[t1 + 1] == dev_at[t] + n1) { n1 += part_len[t1 + 1]; ++t1; }
+                const int fr = grk_amd_fetch_assembled(c, dev_at[t], n1, out + at[t]);
+                if (fr) return fr;
+                t = t1;
+            }
+            return GRK_AMD_OK;
+        }, call.comp_dx, call.comp_dy);
+        if (n >= 0) ++c->route_counters[0];
+        return n;
+    }
+    // the file on the device: the header -- written now that the lengths are known -- and EOC around the tile-parts
+    std::vector<uint8_t> hdr((size_t)hdr_bytes + 2);
+    const int64_t hn = main_header_subsampled(call.im, call.base, call.comp_dx, call.comp_dy, flags, part_len.data(), hdr.data(), (uint64_t)hdr_bytes);
+    if (hn != hdr_bytes) return hn < 0 ? hn : GRK_AMD_ERR_INVALID;
+    const uint64_t body = used - first, total = (uint64_t)hdr_bytes + body + 2;
+    uint8_t* file = (uint8_t*)o.out.p;                     // (assemble_enqueue left 16 bytes free behind the tile-parts)
+    if (!in_place) {
+        HIP_TRY(c, c->jt_file.ensure(total + 16), "alloc the file");
+        file = (uint8_t*)c->jt_file.p;
+        uint64_t at = (uint64_t)hdr_bytes;
+        for (uint32_t t = 0; t < ntiles; ++t) {
+            HIP_TRY(c, hipMemcpyAsync(file + at, (const uint8_t*)o.out.p + dev_at[t], part_len[t], hipMemcpyDeviceToDevice, c->stream), "place a tile-part");
+            at += part_len[t];
+        }
+    }
+    const uint8_t eoc[2] = {0xFF, 0xD9};
+    HIP_TRY(c, hipMemcpyAsync(file, hdr.data(), (size_t)hdr_bytes, hipMemcpyHostToDevice, c->stream), "upload the main header");
+    HIP_TRY(c, hipMemcpyAsync(file + hdr_bytes + body, eoc, 2, hipMemcpyHostToDevice, c->stream), "upload EOC");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    *d_file = file;
+    ++c->route_counters[0];
+    return (int64_t)total;
+}
+
+extern "C" {
+uint64_t grk_amd_encode_route_counters(grk_amd_ctx* c, int which)
+{
+    return c && which >= 0 && which < 2 ? c->route_counters[which] : 0;
+}
 
 int64_t grk_amd_assemble_device(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
                                 uint64_t dst_offset, uint32_t* part_bytes)
@@ -121,16 +394,15 @@ int64_t grk_amd_assemble_device(grk_amd_ctx* c, const grk_amd_tile_params* p, ui
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     { const int jr = join_side(c); if (jr) return jr; }
     auto& o = c->t2_outs[c->t2_cur];
-    { const int rc = assemble_enqueue(c, p, ntiles, tile_index, flags, dst_offset, c->stream, o); if (rc) return rc; }
+    T2Source src;
+    { const int rc = latest_call_source(c, p, ntiles, flags, c->stream, src); if (rc) return rc; }
+    { const int rc = assemble_enqueue(c, src, ntiles, tile_index, flags, dst_offset, c->stream, o); if (rc) return rc; }
     uint64_t flagwords[2] = {0, 0}, total[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(flagwords, c->flag.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch flag");
     HIP_TRY(c, hipMemcpyAsync(total, o.total.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch total");
     if (part_bytes) HIP_TRY(c, hipMemcpyAsync(part_bytes, o.part_len.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-    if (flagwords[0] & 1u) return fail(c, GRK_AMD_ERR_OVERFLOW, "coded arena overflow");
-    if (flagwords[0] & 2u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "coefficient magnitude exceeds Kmax+1 bits");
-    if (flagwords[0] & 4u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a code-block longer than the device writer takes");
-    if (flagwords[0] & 8u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "tile-part beyond 4 GB or packet lengths beyond what PLT can carry");
+    { const int se = status_error(c, flagwords[0]); if (se) return se; }
     c->t2_out_used = total[1];
     return (int64_t)total[0];
 }
@@ -150,7 +422,9 @@ int grk_amd_assemble_device_async(grk_amd_ctx* c, const grk_amd_tile_params* p, 
     const int nsets = c->pipelining ? std::max(1, std::min(c->pipe_depth, grk_amd_ctx::kMaxAltSets + 1)) : 1;
     c->t2_cur = (c->t2_cur + 1) % nsets;
     c->t2_out_used = 0;
-    return assemble_enqueue(c, p, ntiles, tile_index, flags, 0, (hipStream_t)hip_stream, c->t2_outs[c->t2_cur]);
+    T2Source src;
+    { const int rc = latest_call_source(c, p, ntiles, flags, (hipStream_t)hip_stream, src); if (rc) return rc; }
+    return assemble_enqueue(c, src, ntiles, tile_index, flags, 0, (hipStream_t)hip_stream, c->t2_outs[c->t2_cur]);
 }
 
 void* grk_amd_assembled_device_ptr(grk_amd_ctx* c) { return c ? c->t2_outs[c->t2_cur].out.p : nullptr; }

@@ -156,6 +156,21 @@ struct grk_amd_ctx {
     T2Out t2_outs[kMaxAltSets + 1];
     int t2_cur = 0;
     uint64_t t2_out_used = 0;        // (the synchronous form) bytes of t2_outs[t2_cur].out that hold tile-parts
+    // Tier-2 on the device over JOINT tables (assemble.hip: encode_joint_device -- sub-sampled images, surfaces, packed frames): the
+    // plans of the image's tile classes, cached apart from `t2` (keyed on the image, not on a plain call's parameters: neither
+    // serves the other), the image-wide tables and arena that KK (kernels_t2keep.hip) fills batch after batch, the running cursors
+    // (uint64[batches + 1]) with the image's status word behind them, the units' first rows batch by batch, and the file of a
+    // grk_amd_encode_*_device call whose tile classes do not lie in tile order
+    struct T2Joint {
+        bool valid = false; grk_amd_image_layout im{}; grk_amd_tile_params base{}; std::vector<uint8_t> dx, dy; uint32_t order = 0;
+        struct Class { T2Plan plan; uint32_t max_blocks = 0, bpt = 0; uint64_t row_begin = 0; std::vector<uint32_t> tiles; DevBuf packets, pob; };
+        std::vector<Class> classes;
+        std::vector<uint64_t> unit_row;                      // [unit]: its first row in the image's tables (class-major, see assemble.hip)
+        uint64_t rows = 0;
+    } t2j;
+    DevBuf jt_len, jt_off, jt_arena, jt_state, jt_rowat, jt_file;
+    uint64_t route_counters[2] = {0, 0};                     // images assembled on the device / written by the host writer (grk_amd_encode_route_counters)
+    uint64_t last_arena_bound = 0;                           // the arena K3's plan asked for in the latest call (plan_ht_arena), <= arena.cap
     std::vector<uint64_t> h_off;
     std::vector<uint32_t> h_len;
     uint32_t last_ntiles = 0;
@@ -272,9 +287,10 @@ int queue_surface_kernel(grk_amd_ctx* c, bool place, const grk_amd::ResolvedSurf
                          void* d_tiles, uint32_t count, uint32_t w, uint32_t h, const uint32_t* d_origins);                  // surface.cpp
 bool surface_direct_allowed();            // GRK_AMD_SURFACE_DIRECT != 0, read per call (surface.cpp)
 // grk_amd_encode_surface / grk_amd_encode_surface_rate behind their null checks: what the packed calls (packed.cpp) enter too
+// (d_file != nullptr: grk_amd_encode_surface_device -- the file stays in device memory, `out` / `out_cap` are not used)
 int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                            const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
-                           uint32_t flags, uint8_t* out, uint64_t out_cap);                                                  // surface.cpp
+                           uint32_t flags, uint8_t* out, uint64_t out_cap, void** d_file = nullptr);                        // surface.cpp
 int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                                 const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
                                 uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);   // surface.cpp

@@ -41,6 +41,7 @@ int make_ht_args(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool h16
     HIP_TRY(c, c->offsets.ensure((nblocks + 1) * 8), "alloc offsets");
     HIP_TRY(c, c->flag.ensure(kHtAllocBytes), "alloc allocator state");
     HIP_TRY(c, c->arena.ensure(plan.arena_bytes), "alloc coded arena");
+    c->last_arena_bound = plan.arena_bytes;
     HIP_TRY(c, c->ovf.ensure(plan.ovf_entries * 4 + 16), "alloc fallback list");
     a.mallat = (const int32_t*)d_mallat; a.stride = g.stride; a.pitch = g.plane_elems; a.h16 = h16 ? 1 : 0;
     a.blocks = (const HtBlockDesc*)c->blockdesc.p; a.blocks_per_tile = bpt; a.ncomp = g.p.num_comps; a.ntiles = ntiles;

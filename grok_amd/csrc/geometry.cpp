@@ -308,6 +308,30 @@ std::vector<grk_amd::Pk> grk_amd::packet_order(const std::vector<const TileGeom*
     return prec;
 }
 
+// the tiles of a sub-sampled image in classes of one joint plan each (t2_order.h)
+uint32_t grk_amd::joint_tile_classes(const std::vector<uint32_t>& of, uint32_t nruns, uint32_t order, const std::vector<std::vector<Pk>>& seq,
+                                     std::vector<uint32_t>& class_of)
+{
+    const uint32_t ntiles = nruns ? (uint32_t)(of.size() / nruns) : 0u;
+    class_of.assign(ntiles, 0);
+    std::vector<uint32_t> lead;                              // [class]: its first tile
+    auto same = [&](uint32_t a, uint32_t b) {
+        for (uint32_t k = 0; k < nruns; ++k) if (of[(size_t)a * nruns + k] != of[(size_t)b * nruns + k]) return false;
+        if (order <= 1) return true;
+        if (seq[a].size() != seq[b].size()) return false;
+        for (size_t i = 0; i < seq[a].size(); ++i)
+            if (seq[a][i].c != seq[b][i].c || seq[a][i].r != seq[b][i].r || seq[a][i].pi != seq[b][i].pi) return false;
+        return true;
+    };
+    for (uint32_t t = 0; t < ntiles; ++t) {
+        uint32_t k = 0;
+        while (k < lead.size() && !same(lead[k], t)) ++k;
+        if (k == lead.size()) lead.push_back(t);
+        class_of[t] = k;
+    }
+    return (uint32_t)lead.size();
+}
+
 // the next unit of a whole-image call into its geometry group (image.h)
 int grk_amd::add_unit(UnitGroups& g, const grk_amd_tile_params& p, uint32_t order)
 {

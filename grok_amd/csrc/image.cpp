@@ -104,9 +104,10 @@ int grk_amd::encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const
 
 int64_t grk_amd::frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
                             const std::vector<uint32_t>& part_len, uint8_t* out, uint64_t cap,
-                            const std::function<int(const std::vector<uint64_t>& at)>& body)
+                            const std::function<int(const std::vector<uint64_t>& at)>& body, const uint8_t* comp_dx, const uint8_t* comp_dy)
 {
-    const int64_t hdr = grk_amd_write_main_header_layout(im, base, flags, part_len.data(), out, cap);
+    const int64_t hdr = comp_dx && comp_dy ? main_header_subsampled(im, base, comp_dx, comp_dy, flags, part_len.data(), out, cap)
+                                           : grk_amd_write_main_header_layout(im, base, flags, part_len.data(), out, cap);
     if (hdr < 0) return hdr;
     std::vector<uint64_t> at(part_len.size() + 1, (uint64_t)hdr);
     for (size_t t = 0; t < part_len.size(); ++t) at[t + 1] = at[t] + part_len[t];
@@ -229,9 +230,27 @@ extern "C" int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_a
     UnitGroups g;
     int rc = subsampled_image(ctx, im, base, comp_dx, comp_dy, pixels, units, src, g);
     if (rc) return rc;
+    // Tier-2 on the device (encode_joint_device; GRK_AMD_IMAGE_T2=host: the host writer below, which is also where an image beyond
+    // the device writer's tables goes): every group coded without a table, its rows and bytes kept on the device
+    if (!image_t2_host()) {
+        const uint32_t nruns = (uint32_t)comp_runs(base->num_comps, base->mct != 0, comp_dx, comp_dy).size();
+        JointT2Call call{im, base, comp_dx, comp_dy, flags, nruns, &g, g.members, {}};
+        std::vector<std::vector<uint8_t>> staged(g.members.size());     // (nothing waits between the batches: each keeps its own pixels)
+        call.front = [&](size_t k) -> int {
+            const auto& G = g.members[k];
+            std::vector<uint8_t>& staging = staged[k];
+            staging.resize(staged_bytes(src, units[G[0]]) * G.size());
+            stage_units(src, units, G, staging.data(), 1);
+            return grk_amd_encode_tiles(ctx, &units[G[0]].p, (uint32_t)G.size(), staging.data(), 0, nullptr, nullptr);
+        };
+        const int64_t n = encode_joint_device(ctx, call, out, cap, nullptr);
+        if (n != GRK_AMD_ERR_UNSUPPORTED) return n;
+    }
     std::vector<grk_amd_coded_block> rows;                   // tile-major, within a tile component-major (the runs in order)
     std::vector<uint8_t> coded;
     rc = encode_groups_host(ctx, src, units, g, rows, coded);
     if (rc) return rc;
-    return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, cap);
+    const int64_t n = grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, cap);
+    if (n >= 0) ++ctx->route_counters[1];
+    return n;
 }

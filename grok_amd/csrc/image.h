@@ -92,8 +92,32 @@ int encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const std::vec
 // The file around tile-parts of known sizes: main header (TLM from `part_len`), `body(at)` puts tile-part t at out + at[t]
 // (at[ntiles]: their end), EOC.  The file's length, or the header writer's error (TLM over 255 tiles: GRK_AMD_ERR_UNSUPPORTED),
 // GRK_AMD_ERR_OVERFLOW when `cap` cannot hold it, or the body's error.
+// comp_dx / comp_dy (both or neither): the file of an image of sub-sampled components -- SIZ carries the factors, COD no colour
+// transform unless components 0..2 share theirs (main_header_subsampled, t2_writer.cpp: the header grk_amd_write_codestream_subsampled writes)
 int64_t frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags, const std::vector<uint32_t>& part_len,
-                   uint8_t* out, uint64_t cap, const std::function<int(const std::vector<uint64_t>& at)>& body);
+                   uint8_t* out, uint64_t cap, const std::function<int(const std::vector<uint64_t>& at)>& body,
+                   const uint8_t* comp_dx = nullptr, const uint8_t* comp_dy = nullptr);
+int64_t main_header_subsampled(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                               uint32_t flags, const uint32_t* tile_part_bytes, uint8_t* out, uint64_t cap);
+
+// ---- Tier-2 on the device for an image whose units are coded by several batches (assemble.hip) -------------------------------------
+// The caller names the image's units -- unit t * nruns + k is run k (comp_runs) of tile t, `g` their geometry groups -- and its batches,
+// each one grk_amd_encode_tiles call over units of one group, and lends front(b): batch b's pixels where they have to be and the
+// call made, without a table (nothing comes to the host).  encode_joint_device keeps every batch's rows and bytes on the device
+// (KK, kernels_t2keep.hip), frames the tiles class by class (t2_order.h: joint_tile_classes, t2_device_plan_joint) with the kernels
+// of grk_amd_assemble_device, and delivers the file: to `out` (main header and EOC written by the host, the tile-parts fetched), or
+// with d_file != nullptr SOC .. EOC contiguous in device memory of the context's, valid until its next encode call (`out`, `cap`
+// unused).  The file's length, GRK_AMD_ERR_UNSUPPORTED where the device writer does not reach (GRK_AMD_CS_BLOCK_MSBS, tables beyond
+// its fields, TLM over 255 tiles) -- before any batch is coded --, or an error.
+struct JointT2Call {
+    const grk_amd_image_layout* im; const grk_amd_tile_params* base; const uint8_t* comp_dx; const uint8_t* comp_dy; uint32_t flags;
+    uint32_t nruns; const UnitGroups* g;
+    std::vector<std::vector<uint32_t>> batches;
+    std::function<int(size_t b)> front;
+};
+int64_t encode_joint_device(grk_amd_ctx* ctx, const JointT2Call& call, uint8_t* out, uint64_t cap, void** d_file);
+// GRK_AMD_IMAGE_T2=host, read per call: the whole-image encoders write their files with the host writer
+bool image_t2_host();
 
 // An image of sub-sampled components (grk_amd_encode_image_subsampled's `pixels`: the components back to back, tight) cut into units
 // -- tile by tile, within a tile run by run (comp_runs) -- and grouped.  GRK_AMD_ERR_UNSUPPORTED under a pixel layout of the caller's

@@ -313,6 +313,23 @@ struct T2GatherArgs {
 };
 hipError_t launch_t2_gather(const T2GatherArgs& a, hipStream_t s);
 
+// ---- KK: a batch's table and coded bytes into image-wide tables and an image-wide arena (kernels_t2keep.hip) -----------------------
+struct T2KeepArgs {
+    const uint32_t* lengths; const unsigned long long* offsets;   // the batch's table: [unit][row], nunits x bpu entries
+    const uint8_t* arena;                            // the batch's coded bytes, from a 16-byte boundary
+    uint64_t arena_bound;                            // what the image's arena was sized for: at most this many bytes of the batch, a
+                                                     // multiple of 16 inside the batch's arena (more in use: bit 0 of *status)
+    const unsigned long long* batch_state;           // K3's allocator state: [0] status bits, [1] bytes of the arena in use
+    uint32_t nunits, bpu;                            // the batch's units, rows per unit
+    const unsigned long long* row_at;                // [unit]: its first row in the image's tables
+    uint32_t* j_lengths; unsigned long long* j_offsets;   // the image's tables
+    uint8_t* j_arena; uint64_t j_cap;                // the image's arena (16-byte aligned) and its size
+    unsigned long long* cursors;                     // [0] where this batch's bytes go (a multiple of 16), [1] written: where the next one's go
+    unsigned int* status;                            // the image's status word: the batches' OR-ed
+    uint32_t grid;                                   // set by the launcher: workgroups
+};
+hipError_t launch_t2_keep(const T2KeepArgs& a, hipStream_t s);
+
 // ---- KG / KP: the device's share of reading a whole codestream (kernels_t2dec.hip) ----------------------------------------------
 // KG: moves[i] = len bytes from src + moves[i].src to dst + moves[i].dst (the host checked them against both buffers)
 hipError_t launch_t2dec_gather(const grk_amd_tp_segment* d_moves, uint64_t nmoves, const uint8_t* src, uint8_t* dst, hipStream_t s);

@@ -137,6 +137,20 @@ extern "C" int64_t grk_amd_encode_packed(grk_amd_ctx* c, const grk_amd_image_lay
     return encode_surface_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, out, out_cap);
 }
 
+extern "C" int64_t grk_amd_encode_packed_device(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                                uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, void** d_file)
+{
+    if (!c || !im || !base || !pixels || !d_file) return GRK_AMD_ERR_INVALID;
+    *d_file = nullptr;
+    PackedFrame f;
+    int rc = open_encode(c, im, base, format, pitch, pixels, cap, pixels_on_device, f);
+    if (rc) return rc;
+    const PlaneSet ps(f);
+    rc = unpack_frame(c, f, ps, pixels, pixels_on_device);
+    if (rc) return rc;
+    return encode_surface_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, nullptr, 0, d_file);
+}
+
 extern "C" int64_t grk_amd_encode_packed_rate(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
                                               uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
                                               const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result)

@@ -197,12 +197,27 @@ struct SurfaceJob {
 // own three planes in device memory
 int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                            const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
-                           uint32_t flags, uint8_t* out, uint64_t out_cap)
+                           uint32_t flags, uint8_t* out, uint64_t out_cap, void** d_file)
 {
+    // (a plain encode drops nothing: per-block zero bit-planes are the rate-targeted call's; the device file has no host writer to go to)
+    if (d_file && (flags & GRK_AMD_CS_BLOCK_MSBS)) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
     SurfaceJob job{c};
     int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);
     if (rc) return rc;
     KeepLayout keep{c->enc_layout, c->enc_layout};
+    // Tier-2 on the device (encode_joint_device, image.h; GRK_AMD_IMAGE_T2=host: the host writer below, where a surface beyond the
+    // device writer's tables goes as well -- a file in device memory has no such way out): every batch coded without a table
+    if (d_file || !image_t2_host()) {
+        JointT2Call call{im, base, comp_dx, comp_dy, flags, (uint32_t)job.runs.size(), &job.g, {}, {}};
+        for (const SurfaceBatch& B : job.batches) call.batches.push_back(B.units);
+        call.front = [&](size_t b) -> int {
+            const int fr = job.front(b, nullptr, nullptr);
+            // (the next batch's cut writes the staging buffer this one's level 0 reads: in stream order whichever stream read it)
+            return fr ? fr : grk_amd_stream_wait_pixels(c, c->stream);
+        };
+        const int64_t n = encode_joint_device(c, call, out, out_cap, d_file);
+        if (d_file || n != GRK_AMD_ERR_UNSUPPORTED) return n;
+    }
     std::vector<grk_amd_coded_block> rows(job.row_at.back()), table;
     std::vector<uint8_t> coded;
     // every batch's rows and bytes to the host
@@ -220,7 +235,18 @@ int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const
         for (size_t i = 0; i < batch.size(); ++i)
             for (uint64_t k = 0; k < bpu; ++k) { rows[job.row_at[batch[i]] + k] = table[i * bpu + k]; rows[job.row_at[batch[i]] + k].offset += at; }
     }
-    return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, out_cap);
+    const int64_t n = grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows.data(), coded.data(), flags, out, out_cap);
+    if (n >= 0) ++c->route_counters[1];
+    return n;
+}
+
+extern "C" int64_t grk_amd_encode_surface_device(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                 const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                                 const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, void** d_file)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !d_file) return GRK_AMD_ERR_INVALID;
+    *d_file = nullptr;
+    return encode_surface_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, nullptr, 0, d_file);
 }
 
 extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,

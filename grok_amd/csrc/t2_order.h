@@ -18,5 +18,20 @@ struct Pk { uint32_t c, r, pi; uint64_t x, y; };
 std::vector<Pk> packet_order(const std::vector<const TileGeom*>& cg, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0,
                              uint32_t order);
 
+// The device writer's plan (geometry.h: T2Plan) of a tile whose components have geometries of their own -- a sub-sampled image: cg[c]
+// and row0[c] (component c's first row in the tile's table) as write_tile_part takes them, the packets in packet_order's sequence.
+// packet_of_block covers the tile's rows [0, max row0 + blocks).  GRK_AMD_ERR_UNSUPPORTED for GRK_AMD_CS_BLOCK_MSBS and for tables
+// beyond the kernels' 32-bit fields, GRK_AMD_ERR_INVALID for rows that no packet or two packets hold.  t2_device_plan(g, ...) is this
+// with every component at g.  (t2_writer.cpp)
+int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                         uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out);
+
+// The tiles of an image of `nruns` units per tile (image.h: unit t * nruns + k is run k of tile t, of[] its geometry group) in CLASSES
+// that one joint plan frames: the same group for every run, and the same packet sequence under `order` -- seq[t] is tile t's
+// packet_order, compared as same_packets compares (component, resolution, precinct); orders 0 and 1 follow from the groups alone and
+// `seq` may be empty.  class_of[t]; returns the number of classes, numbered by their first tile.  (geometry.cpp)
+uint32_t joint_tile_classes(const std::vector<uint32_t>& of, uint32_t nruns, uint32_t order, const std::vector<std::vector<Pk>>& seq,
+                            std::vector<uint32_t>& class_of);
+
 } // namespace grk_amd
 #pragma GCC visibility pop

@@ -13,6 +13,7 @@
 // It is O(#code-blocks) host work plus one memcpy of the coded bytes.
 #include "../../include/grok_amd.h"
 #include "geometry.h"
+#include "image.h"
 #include "t2_order.h"
 #include <algorithm>
 #include <cstring>
@@ -545,6 +546,30 @@ extern "C" int64_t grk_amd_write_main_header_layout(const grk_amd_image_layout* 
     return (int64_t)o.n;
 }
 
+// the main header grk_amd_write_codestream_subsampled writes, with the tile-parts' lengths in its TLM (image.h)
+int64_t grk_amd::main_header_subsampled(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                                        const uint8_t* comp_dy, uint32_t flags, const uint32_t* tile_part_bytes, uint8_t* out, uint64_t cap)
+{
+    if (!base || !comp_dx || !comp_dy) return GRK_AMD_ERR_INVALID;
+    Layout l;
+    int rc = check_layout(im, l);
+    if (rc != GRK_AMD_OK) return rc;
+    const uint32_t ntiles = l.tcols * l.trows, nc = base->num_comps;
+    if (flags & GRK_AMD_CS_TLM) { if (ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED; if (!tile_part_bytes) return GRK_AMD_ERR_INVALID; }
+    grk_amd_tile_params based = *base, p;
+    if (based.mct && nc >= 3 && !(comp_dx[0] == comp_dx[1] && comp_dx[1] == comp_dx[2] && comp_dy[0] == comp_dy[1] && comp_dy[1] == comp_dy[2]))
+        based.mct = 0;
+    TileGeom g;
+    if ((rc = tile_comp_of(l, based, comp_dx[0], comp_dy[0], 0, p)) != GRK_AMD_OK) return rc;
+    if ((rc = build_tile_geom(p, g)) != GRK_AMD_OK) return rc;
+    Out o{out, cap};
+    uint64_t tlm_at = 0;
+    write_main_header(o, g, l.im, flags, ntiles, &tlm_at, comp_dx, comp_dy);
+    for (uint32_t t = 0; tlm_at && t < ntiles; ++t) o.patch32(tlm_at + 5ull * t + 1, tile_part_bytes[t]);
+    if (o.ovf) return GRK_AMD_ERR_OVERFLOW;
+    return (int64_t)o.n;
+}
+
 extern "C" int64_t grk_amd_write_main_header(const grk_amd_tile_params* p, uint32_t img_w, uint32_t img_h, uint32_t flags,
                                              const uint32_t* tile_part_bytes, uint8_t* out, uint64_t cap)
 {
@@ -585,20 +610,25 @@ int64_t plan_tile_part(const grk_amd_tile_params& p, uint32_t tile_index, uint32
 } // namespace grk_amd
 
 namespace grk_amd {
-// What the header kernel needs to know about a tile's packets (no sub-sampling: every component has the tile's geometry).
-int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out)
+// What the header kernel needs to know about a tile's packets: component c's tile-component has the geometry cg[c] and its rows start
+// at row0[c] of the tile's table -- the arguments of write_tile_part, and its packet sequence (t2_order.h).
+int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                         uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out)
 {
-    const grk_amd_tile_params& p = g.p;
     if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (the header kernel writes the constant tree)
-    std::vector<const TileGeom*> cg(p.num_comps, &g);
-    const std::vector<Pk> seq = packet_order(cg, nullptr, nullptr, p.tile_x0, p.tile_y0, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
+    if (cg.empty() || row0.size() != cg.size()) return GRK_AMD_ERR_INVALID;
+    uint64_t rows = 0;
+    for (size_t c = 0; c < cg.size(); ++c) rows = std::max(rows, row0[c] + cg[c]->blocks_per_comp);
+    if (rows > 0xFFFFFFFFull) return GRK_AMD_ERR_UNSUPPORTED;               // (T2Packet::row0 and the kernels' rows per tile are 32 bits)
+    const std::vector<Pk> seq = packet_order(cg, comp_dx, comp_dy, gx0, gy0, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
     out.packets.clear();
-    out.packet_of_block.assign((size_t)g.blocks_per_comp * p.num_comps, 0xFFFFFFFFu);
+    out.packet_of_block.assign((size_t)rows, 0xFFFFFFFFu);
     uint64_t u = 0, h = 0;
     for (const Pk& q : seq) {
+        const TileGeom& g = *cg[q.c];
         const ResGeom& R = g.res[q.r];
         T2Packet k{};
-        k.row0 = q.c * g.blocks_per_comp;
+        k.row0 = (uint32_t)row0[q.c];
         uint64_t bits = 1;
         for (uint32_t bi = 0; bi < R.num_bands; ++bi) {
             const BandGeom& B = R.band[bi];
@@ -608,7 +638,11 @@ int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out)
             k.first_block[b] = P.first_block; k.gw[b] = P.gw; k.gh[b] = P.gh; k.kmax[b] = B.kmax;
             k.height[b] = (uint32_t)tag_tree_height(P.gw, P.gh);
             const uint64_t n = (uint64_t)P.gw * P.gh;
-            for (uint64_t i = 0; i < n; ++i) out.packet_of_block[k.row0 + P.first_block + i] = (uint32_t)out.packets.size();
+            for (uint64_t i = 0; i < n; ++i) {
+                uint32_t& of = out.packet_of_block[k.row0 + P.first_block + i];
+                if (of != 0xFFFFFFFFu) return GRK_AMD_ERR_INVALID;          // (components whose rows overlap)
+                of = (uint32_t)out.packets.size();
+            }
             k.nblocks += (uint32_t)n;
             // per block: two paths of at most `height` nodes, the pass bit, Lblock's comma code and the length
             bits += n * (2ull * k.height[b] + 1 + (kT2MaxLenBits - 3 + 1) + kT2MaxLenBits) + B.kmax;
@@ -624,6 +658,16 @@ int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out)
     for (uint32_t v : out.packet_of_block) if (v == 0xFFFFFFFFu) return GRK_AMD_ERR_INVALID;     // (every block lies in one precinct)
     out.u_words = (uint32_t)u; out.h_bytes = (uint32_t)h;
     return GRK_AMD_OK;
+}
+
+// ... of a tile without sub-sampling: every component has the tile's geometry, component c's rows start at c x blocks_per_comp
+int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out)
+{
+    const grk_amd_tile_params& p = g.p;
+    std::vector<const TileGeom*> cg(p.num_comps, &g);
+    std::vector<uint64_t> row0(p.num_comps);
+    for (uint32_t c = 0; c < p.num_comps; ++c) row0[c] = (uint64_t)c * g.blocks_per_comp;
+    return t2_device_plan_joint(cg, row0, nullptr, nullptr, p.tile_x0, p.tile_y0, flags, out);
 }
 
 } // namespace grk_amd

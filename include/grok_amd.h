@@ -614,7 +614,9 @@ int grk_amd_rate_unit_rows(grk_amd_ctx* ctx, uint64_t* first_row, uint32_t cap);
  * columns x ceil(y1 / dy_c) - ceil(y0 / dy_c) rows, tight (the planar layout of a .yuv / raw file).  Runs of consecutive components
  * with equal factors are coded together (the colour transform applies only where components 0..2 are such a run; with
  * other factors base->mct is switched off, as the reference does: CodeStreamCompress.cpp:434-447); the codestream == grk_compress's for the same image (one precinct per resolution or
- * any precinct sizes, the five progression orders, SOP / EPH / TLM / PLT as for any image).
+ * any precinct sizes, the five progression orders, SOP / EPH / TLM / PLT as for any image).  Tier-2 runs on the device under
+ * grk_amd_encode_image's rule -- GRK_AMD_IMAGE_T2=host, read per call, selects the host writer; the same file either way (see
+ * grk_amd_encode_surface, grk_amd_encode_route_counters).
  * grk_amd_write_codestream_subsampled: the table's rows tile by tile, within a tile component by component, each component with the
  * grk_amd_tile_num_blocks() rows of ITS rectangle (num_comps = 1); out == NULL: only the file's length is returned (`coded` is not read). */
 int grk_amd_layout_tile_comp(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t dx, uint32_t dy,
@@ -895,11 +897,26 @@ int grk_amd_surface_plan(const grk_amd_image_layout* im, const grk_amd_tile_para
  * byte-identical to grk_amd_encode_image_subsampled's for the same samples as tight planes (all factors 1: to grk_amd_encode_image's in
  * the default layout, colour transform included): same flags, any tile layout, image offsets, precincts, the five orders.  Units
  * are coded in place or staged as grk_amd_surface_plan says (GRK_AMD_SURFACE_DIRECT=0, read per call: all staged); a host surface goes
- * up as one copy of its extent.  Tier-2 is the host writer over the fetched rows.  The context's pixel layouts are neither consulted
- * nor changed.  GRK_AMD_ERR_OVERFLOW before any work when the surface does not fit `cap`. */
+ * up as one copy of its extent.  Tier-2 runs on the device, as for grk_amd_encode_image: every batch's rows and coded bytes stay in
+ * device memory, the tile-parts are assembled there and fetched, the main header is written by the host from their lengths
+ * (GRK_AMD_IMAGE_T2=host, read per call: the host writer over the fetched rows, which is also where a layout beyond the device
+ * writer's tables and GRK_AMD_CS_BLOCK_MSBS go, silently; the file is the same byte for byte -- grk_amd_encode_route_counters
+ * tells which ran).  grk_amd_encode_image_subsampled and grk_amd_encode_packed follow the same rule.  The context's pixel layouts
+ * are neither consulted nor changed.  GRK_AMD_ERR_OVERFLOW before any work when the surface does not fit `cap`. */
 int64_t grk_amd_encode_surface(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
                                const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap);
+/* The same file left in DEVICE memory: *d_file points at SOC .. EOC, contiguous, in a buffer the context owns, valid until the next
+ * encode call of that context; returns its length.  Only the tile-parts' lengths come to the host (the main header's size does not
+ * depend on them: the tile-parts are assembled behind room for it, then the header and EOC are uploaded).  There is no host writer
+ * behind this call: GRK_AMD_ERR_UNSUPPORTED where the device writer does not reach (GRK_AMD_CS_BLOCK_MSBS, TLM over 255 tiles, tables
+ * beyond its fields), GRK_AMD_IMAGE_T2 is not consulted.  Synchronous: complete on return. */
+int64_t grk_amd_encode_surface_device(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                      const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                      const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, void** d_file);
+/* cumulative per context, over grk_amd_encode_image_subsampled, grk_amd_encode_surface, grk_amd_encode_packed and the two _device
+ * calls: which = 0 files whose tile-parts were assembled on the device, 1 files written by the host writer */
+uint64_t grk_amd_encode_route_counters(grk_amd_ctx* ctx, int which);
 /* ... in a file of at most rate->target_bytes (rate-targeted encodes, above: always over joint tables).  The same resolution, routes
  * and staging; a unit's pixels are cut out again for a round's final launch when another batch has used the context since; the
  * counters count a unit once per call.  The file equals grk_amd_encode_image_subsampled_rate's for the same samples as tight planes
@@ -966,6 +983,9 @@ uint64_t grk_amd_packed_bytes(int format, const grk_amd_image_layout* im, uint32
  * format allows.  pixels: host or (pixels_on_device != 0) device memory, `cap` bytes; a host frame goes up as one copy. */
 int64_t grk_amd_encode_packed(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
                               const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, uint8_t* out, uint64_t out_cap);
+/* ... left in device memory, as grk_amd_encode_surface_device leaves it (same rules, same lifetime) */
+int64_t grk_amd_encode_packed_device(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                     uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, void** d_file);
 /* ... in a file of at most rate->target_bytes: exactly grk_amd_encode_image_subsampled_rate's file for the same target */
 int64_t grk_amd_encode_packed_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
                                    const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_rate* rate,

@@ -9,9 +9,14 @@ grk_amd_decode_surface on the P010 surface (always staged: KS / KD shift on the 
 shift -- a torch shift pass over the frame and the LSB-aligned call -- and beside the staged LSB-aligned 16-bit NV12 calls, whose
 chroma takes the 16-byte two-byte forms of step 2.  --sixteen-only runs just those staged 16-bit NV12 rows, with min and max: they
 work on a library without the shift as well (GRK_AMD_LIB, tools/build_variant.sh), which is how this tree and its parent commit are
-compared.  Medians of --repeats (7) on one box, the variants alternated within each repeat; host wall clock around a synchronised call.
+compared.  --t2 runs the rows of profiles/surface_t2.txt alone, with min / median / max: the 8K NV12 8-bit frame and the 8K P010
+frame, device-resident, encoded by the default route (Tier-2 on the device) and under GRK_AMD_IMAGE_T2=host (the host writer), with
+grk_amd_encode_surface_device (the file stays in device memory) and a plain device-to-device copy of the file's bytes beside them;
+on a library without these (the parent commit's: GRK_AMD_LIB) the first two rows are the same host route and the third is left out.
+Medians of --repeats (7) on one box, the variants alternated within each repeat; host wall clock around a synchronised call.
 
     python tools/surface_time.py [--repeats 7] [--small] [--sixteen-only] > profiles/surface.txt
+    python tools/surface_time.py --t2 [--label tree] >> profiles/surface_t2.txt
 """
 import argparse
 import os
@@ -72,13 +77,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--small", action="store_true", help="1920 x 1080 instead of 7680 x 4320 (a quick look)")
     ap.add_argument("--sixteen-only", action="store_true", help="only the staged 16-bit NV12 rows, min / median / max (any library)")
-    ap.add_argument("--label", default="tree", help="what --sixteen-only's lines are called")
+    ap.add_argument("--t2", action="store_true", help="only the Tier-2 route rows (profiles/surface_t2.txt), min / median / max (any library)")
+    ap.add_argument("--label", default="tree", help="what --sixteen-only's and --t2's lines are called")
     a = ap.parse_args()
     W, H = (1920, 1080) if a.small else (7680, 4320)
     c = G.Context(0)
     layout = G.ImageLayout.make(W, H)
     if a.sixteen_only:
         sixteen_bit(c, a, layout, W, H)
+        return
+    if a.t2:
+        tier2_routes(c, a, layout, W, H)
         return
     print("# tools/surface_time.py: medians of %d repeats, variants alternated within a repeat; %s" % (a.repeats, torch.cuda.get_device_name(0)))
     surface, sampling, nbytes = G.Surface.make("NV12", layout, 8, 0)
@@ -180,6 +189,59 @@ def main():
          alternated({"KS cut, Cb/Cr (de-interleave)": cut_uv, "KD place, Cb/Cr (merged stores)": place_uv,
                      "plain device-to-device copy of the same bytes": plain(nbytes - W * H)}, a.repeats), nbytes - W * H)
     sixteen_bit(c, a, layout, W, H)
+
+
+def tier2_routes(c, a, layout, W, H):
+    """the encode's Tier-2 routes: device-resident NV12 8-bit and P010 frames, the default route, GRK_AMD_IMAGE_T2=host, the _device call"""
+    have_device = hasattr(c._L, "grk_amd_encode_route_counters")
+    for fmt, prec in (("NV12", 8), ("P010", 10)):
+        surface, sampling, nbytes = G.Surface.make(fmt, layout, None if fmt == "P010" else prec, 0)
+        bps = (prec + 7) // 8
+        base = G.TileParams.make(1, 1, 3, prec, 5, mct=False)
+        planes = [plane(W, H, 1, prec), plane(W // 2, H // 2, 2, prec), plane(W // 2, H // 2, 3, prec)]
+        frame = np.zeros(nbytes, np.uint8)
+        surface.scatter(frame, planes, bps)
+        d_frame = torch.from_numpy(frame).cuda()
+        torch.cuda.synchronize()
+        files, counters = {}, {}
+
+        def enc(host):
+            def run():
+                if host:
+                    os.environ["GRK_AMD_IMAGE_T2"] = "host"
+                before = c.encode_route_counters() if have_device else (0, 0)
+                try:
+                    files[host] = c.encode_surface(layout, base, sampling, surface, d_frame.data_ptr(), cap=nbytes)
+                finally:
+                    os.environ.pop("GRK_AMD_IMAGE_T2", None)
+                after = c.encode_route_counters() if have_device else (0, 0)
+                counters[host] = (after[0] - before[0], after[1] - before[1])
+            return run
+
+        def enc_device():
+            files["device"] = c.encode_surface_device(layout, base, sampling, surface, d_frame.data_ptr(), cap=nbytes)
+
+        settings = {"encode_surface 8K %s, default route" % fmt: enc(False), "encode_surface 8K %s, GRK_AMD_IMAGE_T2=host" % fmt: enc(True)}
+        if have_device:
+            settings["encode_surface_device 8K %s (file stays in device memory)" % fmt] = enc_device
+        enc(False)()
+        d_copy = torch.zeros(len(files[False]), dtype=torch.uint8, device="cuda")
+        d_src = torch.zeros(len(files[False]), dtype=torch.uint8, device="cuda")
+
+        def plain_copy():
+            d_copy.copy_(d_src)
+            torch.cuda.synchronize()
+
+        settings["plain device-to-device copy of the file's %d bytes" % len(files[False])] = plain_copy
+        res = alternated_spread(settings, a.repeats)
+        assert files[False] == files[True]
+        if have_device:
+            assert counters[False] == (1, 0) and counters[True] == (0, 1), counters
+            import gpuutil
+            assert gpuutil.from_dev_ptr(*files["device"]).tobytes() == files[False]
+        for k, (lo, med, hi) in res.items():
+            print("    %s | %-66s min %9.3f  median %9.3f  max %9.3f ms" % (a.label, k, lo, med, hi))
+        sys.stdout.flush()
 
 
 def sixteen_bit(c, a, layout, W, H):

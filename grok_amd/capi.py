@@ -255,6 +255,14 @@ class ReaderError(RuntimeError):
         self.code, self.reason = int(code), reason
 
 
+class StageError(RuntimeError):
+    """Context.stage_assemble refused or failed: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ...) and the context's reason."""
+
+    def __init__(self, what, code, reason):
+        RuntimeError.__init__(self, "%s failed: %d (%s)" % (what, code, reason))
+        self.code, self.reason = int(code), reason
+
+
 _lib = None
 
 
@@ -545,6 +553,14 @@ def write_codestream_layout(layout, base, table, coded, flags=0):
     if n < 0:
         raise RuntimeError("grk_amd_write_codestream_layout failed: %d" % n)
     return out[:n].tobytes()
+
+
+def t2_max_block_bytes():
+    """grk_amd_t2_max_block_bytes: the longest code-block Tier-2 on the device takes"""
+    L = lib()
+    L.grk_amd_t2_max_block_bytes.restype = C.c_uint32
+    L.grk_amd_t2_max_block_bytes.argtypes = []
+    return int(L.grk_amd_t2_max_block_bytes())
 
 
 def write_tile_part(params, tile_index, tile_table, coded, flags=0, size_only=False):
@@ -996,6 +1012,23 @@ class Context:
         n = self._L.grk_amd_assemble_device(self._h, C.addressof(params), idx.size, idx.ctypes.data, flags, dst_offset, lens.ctypes.data)
         if n < 0:
             raise RuntimeError("assemble_device failed: %d (%s)" % (n, self._L.grk_amd_last_error(self._h).decode()))
+        return int(n), lens
+
+    def stage_assemble(self, params, tile_index, table, coded, flags=0):
+        """Tier-2 on the device for a table of the caller's (grk_amd_stage_assemble): `table` CODED_DTYPE, len(tile_index) x (blocks of a
+        tile) rows whose offsets point into `coded` (uint8; rows may share bytes) -> (bytes assembled, [tile-part lengths]); the bytes
+        are fetch_assembled's.  StageError with the code and the context's reason when the call refuses."""
+        idx = np.ascontiguousarray(np.asarray(tile_index, np.uint32))
+        t = np.ascontiguousarray(table, CODED_DTYPE)
+        cbuf = np.ascontiguousarray(np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else coded)
+        lens = np.zeros(idx.size, np.uint32)
+        self._L.grk_amd_stage_assemble.restype = C.c_int64
+        self._L.grk_amd_stage_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   C.c_void_p]
+        n = self._L.grk_amd_stage_assemble(self._h, C.addressof(params), idx.size, idx.ctypes.data, flags, t.ctypes.data,
+                                           cbuf.ctypes.data if cbuf.size else None, cbuf.size, lens.ctypes.data)
+        if n < 0:
+            raise StageError("stage_assemble", n, self._L.grk_amd_last_error(self._h).decode())
         return int(n), lens
 
     def assemble_device_async(self, params, tile_index, flags, stream_ptr):

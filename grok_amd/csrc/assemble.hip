@@ -10,7 +10,7 @@
 // tables that KK (kernels_t2keep.hip) filled behind each of them.
 namespace {
 // What one call of the writer frames: `ntiles` tiles of ONE plan (on the host and on the device), whose rows lie tile after tile, bpt
-// per tile, in `lengths` / `offsets` (into `arena`, which holds at most arena_bytes bytes of theirs); the status word the kernels
+// per tile, in `lengths` / `offsets` (into `arena`; the rows' lengths sum to at most arena_bytes); the status word the kernels
 // raise their bits in
 struct T2Source {
     const T2Plan* plan; uint32_t max_blocks; const void* d_packets; const void* d_pob;
@@ -120,9 +120,8 @@ uint32_t plan_max_blocks(const T2Plan& plan)
     return m;
 }
 
-// the latest grk_amd_encode_tiles call as a source: the context's own table and arena, the plan of its geometry in the order of
-// `flags` -- cached in c->t2 on the call's parameters and the order
-int latest_call_source(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, uint32_t flags, hipStream_t st, T2Source& src)
+// the plan of the context's geometry in the order of `flags` -- cached in c->t2 on the parameters and the order
+int call_plan(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t flags, hipStream_t st)
 {
     const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
     if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
@@ -136,6 +135,14 @@ int latest_call_source(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t nt
         if ((rc = upload_plan(c, T.plan, T.packets, T.pob, st))) return rc;
         T.p = *p; T.order = order; T.valid = true;
     }
+    return GRK_AMD_OK;
+}
+
+// the latest grk_amd_encode_tiles call as a source: the context's own table and arena under the plan of its geometry
+int latest_call_source(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, uint32_t flags, hipStream_t st, T2Source& src)
+{
+    { const int rc = call_plan(c, p, flags, st); if (rc) return rc; }
+    auto& T = c->t2;
     src = T2Source{&T.plan, T.max_blocks, T.packets.p, T.pob.p, (uint32_t)(c->last_nblocks / ntiles), (const uint32_t*)c->lengths.p,
                    (const uint64_t*)c->offsets.p, (const uint8_t*)c->arena.p, (uint64_t)c->arena.cap, (unsigned int*)c->flag.p};
     return GRK_AMD_OK;
@@ -406,6 +413,68 @@ int64_t grk_amd_assemble_device(grk_amd_ctx* c, const grk_amd_tile_params* p, ui
     c->t2_out_used = total[1];
     return (int64_t)total[0];
 }
+
+// Tier-2 on the device for a table of the caller's choosing (the stage call of KT1 / KT1b / KT2, as grk_amd_stage_ht_encode16 is
+// K3's): `table` holds num_tiles x (blocks of a tile) rows in the order of grk_amd_fetch_table, whose offsets point into the `coded`
+// bytes -- rows may share bytes.  Everything is checked on the host before anything is launched; the tile-parts are read with
+// grk_amd_fetch_assembled.  The rows and bytes go to buffers of their own: the latest grk_amd_encode_tiles call stays assemblable.
+int64_t grk_amd_stage_assemble(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
+                               const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes, uint32_t* part_bytes)
+{
+    if (!c || !p || !ntiles || !tile_index || !table || (!coded && coded_bytes)) return GRK_AMD_ERR_INVALID;
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_stage_assemble: per-block zero bit-planes: the host writers only");
+    for (uint32_t i = 0; i < ntiles; ++i)
+        if (tile_index[i] > 65535u) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_assemble: a tile index beyond 65 535 (Isot is 16 bits)");
+    { const int rc = stage_enter(c, p, true, true); if (rc) return rc; }
+    const uint64_t bpt = (uint64_t)c->geom.blocks_per_comp * p->num_comps, rows = bpt * ntiles;
+    if (bpt >> 32) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_stage_assemble: tile layout beyond the device writer's tables");
+    std::vector<uint32_t> h_len(rows);
+    std::vector<uint64_t> h_off(rows);
+    uint64_t sum = 0;
+    char msg[160];
+    for (uint64_t i = 0; i < rows; ++i) {
+        const grk_amd_coded_block& r = table[i];
+        if (!t2_len_ok(r.length)) {
+            std::snprintf(msg, sizeof msg, "grk_amd_stage_assemble: row %llu: a length of %u bytes, the device writer takes less than %u",
+                          (unsigned long long)i, r.length, 1u << kT2MaxLenBits);
+            return fail(c, GRK_AMD_ERR_UNSUPPORTED, msg);
+        }
+        if (r.offset > coded_bytes || r.length > coded_bytes - r.offset) {
+            std::snprintf(msg, sizeof msg, "grk_amd_stage_assemble: row %llu: offset %llu + length %u lies beyond the %llu coded bytes",
+                          (unsigned long long)i, (unsigned long long)r.offset, r.length, (unsigned long long)coded_bytes);
+            return fail(c, GRK_AMD_ERR_INVALID, msg);
+        }
+        h_len[i] = r.length; h_off[i] = r.offset; sum += r.length;
+    }
+    { const int rc = call_plan(c, p, flags, c->stream); if (rc) return rc; }
+    // (no call of this entry leaves work behind: the buffers are free)
+    HIP_TRY(c, c->st_len.ensure(rows * 4 + 16), "alloc the stage's lengths");
+    HIP_TRY(c, c->st_off.ensure(rows * 8 + 16), "alloc the stage's offsets");
+    HIP_TRY(c, c->st_arena.ensure(coded_bytes + 16), "alloc the stage's coded bytes");
+    HIP_TRY(c, c->st_status.ensure(16), "alloc the stage's status word");
+    HIP_TRY(c, hipMemcpyAsync(c->st_len.p, h_len.data(), rows * 4, hipMemcpyHostToDevice, c->stream), "upload lengths");
+    HIP_TRY(c, hipMemcpyAsync(c->st_off.p, h_off.data(), rows * 8, hipMemcpyHostToDevice, c->stream), "upload offsets");
+    if (coded_bytes) { const int rc = copy_h2d(c, c->st_arena.p, coded, coded_bytes); if (rc) return rc; }
+    HIP_TRY(c, hipMemsetAsync(c->st_status.p, 0, 16, c->stream), "clear status");
+    auto& T = c->t2;
+    // (rows may share bytes: what the call writes is bounded by the sum of the lengths, not by the bytes they point into)
+    const T2Source src{&T.plan, T.max_blocks, T.packets.p, T.pob.p, (uint32_t)bpt, (const uint32_t*)c->st_len.p, (const uint64_t*)c->st_off.p,
+                       (const uint8_t*)c->st_arena.p, sum, (unsigned int*)c->st_status.p};
+    auto& o = c->t2_outs[c->t2_cur];
+    c->t2_out_used = 0;
+    { const int rc = assemble_enqueue(c, src, ntiles, tile_index, flags, 0, c->stream, o); if (rc) return rc; }
+    uint32_t status_word = 0;
+    uint64_t total[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(&status_word, c->st_status.p, 4, hipMemcpyDeviceToHost, c->stream), "fetch status");
+    HIP_TRY(c, hipMemcpyAsync(total, o.total.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch total");
+    if (part_bytes) HIP_TRY(c, hipMemcpyAsync(part_bytes, o.part_len.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    { const int se = status_error(c, status_word); if (se) return se; }
+    c->t2_out_used = total[1];
+    return (int64_t)total[0];
+}
+
+uint32_t grk_amd_t2_max_block_bytes(void) { return (1u << kT2MaxLenBits) - 1u; }
 
 // The same without the host: queued on `hip_stream` (made to wait for the encode's results first, as grk_amd_stream_wait_results does),
 // nothing is waited for.  Pipelined encodes rotate as many outputs as buffer sets: a frame's tile-parts, their places / lengths and the

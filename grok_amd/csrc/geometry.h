@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 #include "../../include/grok_amd.h"
+#include "t2_bits.h"
 
 namespace grk_amd {
 
@@ -85,7 +86,7 @@ int64_t plan_tile_part(const grk_amd_tile_params& p, uint32_t tile_index, uint32
 // ---- Tier-2 on the device (kernels_t2.hip; the host's share in t2_writer.cpp) -----------------------------------------------------
 // One packet of a tile in progression order, as the header kernel meets it: up to three bands' code-block grids (rows of the
 // tile's table, raster order within a band), each with the height of its tag trees and its Kmax, and where the packet's raw header
-// bits and stuffed header bytes go in the tile's scratch areas (bounds that hold for any block lengths below 2^29).
+// bits and stuffed header bytes go in the tile's scratch areas (bounds that hold for any block lengths below 2^kT2MaxLenBits).
 struct T2Packet {
     uint32_t row0;                    // first row of the packet's component in the tile's table
     uint32_t nbands, nblocks;
@@ -98,7 +99,7 @@ struct T2Plan {
     std::vector<uint32_t> packet_of_block;        // [rows of a tile]
     uint32_t u_words = 0, h_bytes = 0;            // scratch per tile
 };
-constexpr uint32_t kT2MaxLenBits = 29;            // block lengths the device writer takes (a coded block is a few KB)
+// (kT2MaxLenBits, the block lengths the device writer takes, and kT2MaxHeight: t2_bits.h)
 int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out);
 inline uint32_t ceil_div_pow2(uint32_t v, uint32_t n) { return (uint32_t)(((uint64_t)v + (1ull << n) - 1) >> n); }
 

@@ -8,7 +8,7 @@
 //
 // KT1 t2_header_kernel: one workgroup per (packet, tile).
 //   1. Every code-block's share of the header is a bit string that depends on its place in the band's grid and on its length
-//      alone (t2_writer.cpp, "tag trees as this writer meets them": both trees are uniform): `nn` ones, (root: Kmax - 1 zeros,) `nn`
+//      alone (t2_bits.h; t2_writer.cpp, "tag trees as this writer meets them": both trees are uniform): `nn` ones, (root: Kmax - 1 zeros,) `nn`
 //      ones, the pass bit 0, Lblock's comma code, the length.  A workgroup-wide prefix sum over (bits, bytes) gives every block its
 //      bit position in the RAW header and its byte offset in the packet's body; the bits are OR-ed into zeroed scratch words.
 //   2. Stuffing -- a byte that follows 0xFF carries seven bits -- makes every byte's position depend on the bytes before it:
@@ -107,22 +107,19 @@ __global__ __launch_bounds__(1024) void t2_header_kernel(T2HeaderArgs a)
     for (uint32_t base = 0; base < P.nblocks; base += nthr) {
         const uint32_t j = base + tid;
         const bool valid = j < P.nblocks;
-        uint32_t b = 0, k = 0, len = 0, nn = 0, inc = 0, nbits = 0, zeros = 0;
+        uint32_t b = 0, k = 0, len = 0;
+        T2BlockBits bb{};                                         // the block's bit string (t2_bits.h)
         size_t row = 0;
         if (valid) {
             b = (j >= n0) + (j >= n0 + n1);
             k = j - (b == 0 ? 0u : b == 1 ? n0 : n0 + n1);
             const uint32_t gw = b == 0 ? gw0 : b == 1 ? gw1 : gw2, height = b == 0 ? ht0 : b == 1 ? ht1 : ht2;
-            const uint32_t x = k % gw, y = k / gw, m = x | y;
             row = row_base + (b == 0 ? fb0 : b == 1 ? fb1 : fb2) + k;
             len = a.lengths[row];
-            if (len >> kT2MaxLenBits) { bad = true; len = 0; }
-            nn = m ? min((uint32_t)__builtin_ctz(m) + 1u, height) : height;
-            const int fl = len ? 31 - __builtin_clz(len) : 0;
-            inc = fl + 1 > 3 ? (uint32_t)(fl + 1 - 3) : 0u;
-            zeros = k == 0 ? (b == 0 ? km0 : b == 1 ? km1 : km2) - 1u : 0u;      // the zero-bit-plane tree's root: Kmax - 1
-            nbits = 2 * nn + zeros + 1 + (inc + 1) + (3 + inc);
+            if (!t2_len_ok(len)) { bad = true; len = 0; }         // (KT2 copies nothing of such a block either)
+            bb = t2_block_bits(k % gw, k / gw, height, b == 0 ? km0 : b == 1 ? km1 : km2, len);
         }
+        const uint32_t nbits = bb.nbits;
         const uint64_t v = ((uint64_t)nbits << 40) | len;
         uint64_t incl = v;
 #pragma unroll
@@ -139,11 +136,11 @@ __global__ __launch_bounds__(1024) void t2_header_kernel(T2HeaderArgs a)
             const uint64_t excl = before + incl - v;
             uint32_t pos = (uint32_t)(excl >> 40);
             a.rel[row] = (uint32_t)(excl & kByteMask);
-            put_bits(u, pos, (1ull << nn) - 1ull, nn);
-            pos += nn + zeros;
-            // `nn` ones and the pass bit 0 | Lblock: `inc` ones and a zero | the length in 3 + inc bits
-            const uint64_t tail = ((((((1ull << nn) - 1ull) << 1) << (inc + 1)) | (((1ull << inc) - 1ull) << 1)) << (3 + inc)) | len;
-            put_bits(u, pos, tail, nn + 1 + inc + 1 + 3 + inc);
+            put_bits(u, pos, (1ull << bb.nn) - 1ull, bb.nn);
+            pos += bb.nn + bb.zeros;
+            // `nn` ones and the pass bit 0 | Lblock: `inc` ones and a zero | the length in 3 + inc bits -- in one piece where 64 bits hold it
+            put_bits(u, pos, bb.tail[0], bb.tail_n[0]);
+            if (bb.tail_n[1]) put_bits(u, pos + bb.tail_n[0], bb.tail[1], bb.tail_n[1]);
         }
         carry += total;
     }
@@ -320,7 +317,9 @@ __global__ __launch_bounds__(256) void t2_gather_kernel(T2GatherArgs a)
         const uint64_t tile = item / a.bpt;
         const uint32_t row = (uint32_t)(item - tile * a.bpt);
         const uint64_t q = tile * a.npackets + a.packet_of_block[row];
-        wave_copy(a.out + a.pk_dst[q] + a.sop + a.pk_hdr[q] + a.eph + a.rel[item], a.arena + a.offsets[item], a.lengths[item], lane);
+        const uint32_t len = a.lengths[item];
+        // (a length KT1 refused -- status bit 2 -- counted as 0 there: nothing of that block has a place in the output)
+        if (t2_len_ok(len)) wave_copy(a.out + a.pk_dst[q] + a.sop + a.pk_hdr[q] + a.eph + a.rel[item], a.arena + a.offsets[item], len, lane);
     } else if (item < nblk + npk) {
         const uint64_t q = item - nblk;
         const uint64_t tile = q / a.npackets;

@@ -1,0 +1,54 @@
+// grok_amd/csrc/t2_bits.h -- a code-block's share of a packet header as the device writer composes it (KT1, kernels_t2.hip): the
+// arithmetic alone, for the kernel and for a host program (tests/c/t2_bits_units.cpp) alike.  No HIP in here.
+//
+// In the single layer of this encoder every block is included and both tag trees of a band's precinct are uniform (t2_writer.cpp,
+// "tag trees as this writer meets them"), so block (x, y) of a grid whose trees have `height` levels contributes
+//     nn ones | (the band's first block: Kmax - 1 zeros) | nn ones | the pass bit 0 | Lblock: inc ones, a zero | the length, 3 + inc bits
+// with nn = min(ctz(x | y) + 1, height) (all of the path for the first block) and inc = what Lblock has to grow from 3 for the length.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+#define GRK_T2_FN __host__ __device__ inline
+#else
+#define GRK_T2_FN inline
+#endif
+
+namespace grk_amd {
+
+// Block lengths the device writer takes: below 2^20.  An HT block of 64x64 16-bit coefficients is a few KB, a Part-1 block stays
+// under 64 KB: nothing comes near 1 MB, and the plan's scratch bound (t2_device_plan_joint) is sized by this number.
+constexpr uint32_t kT2MaxLenBits = 20;
+// Tag-tree heights the plan admits (a grid of up to 2^31 x 2^31 blocks): nn ones and the pass bit are one piece of at most 33 bits.
+constexpr uint32_t kT2MaxHeight = 32;
+
+GRK_T2_FN bool t2_len_ok(uint32_t len) { return (len >> kT2MaxLenBits) == 0; }
+
+struct T2BlockBits {
+    uint32_t nn, zeros, inc;
+    uint32_t nbits;                   // all of the block's bits: nn + zeros + the tail's
+    // what follows the first nn ones and the zeros, MSB first, in pieces of at most 64 bits: one piece where it fits (every length
+    // below the limit under a tree of up to 25 levels), else the ones with the pass bit | Lblock with the length
+    uint64_t tail[2]; uint32_t tail_n[2];
+};
+
+// height <= kT2MaxHeight, t2_len_ok(len); the band's first block (x = y = 0) carries the zero-bit-plane tree's root: Kmax - 1 zeros
+GRK_T2_FN T2BlockBits t2_block_bits(uint32_t x, uint32_t y, uint32_t height, uint32_t kmax, uint32_t len)
+{
+    T2BlockBits r;
+    const uint32_t m = x | y;
+    const uint32_t z = m ? (uint32_t)__builtin_ctz(m) + 1u : height;
+    r.nn = z < height ? z : height;
+    const uint32_t fl = len ? 31u - (uint32_t)__builtin_clz(len) : 0u;
+    r.inc = fl + 1u > 3u ? fl + 1u - 3u : 0u;
+    r.zeros = m ? 0u : kmax - 1u;
+    const uint32_t n0 = r.nn + 1u, n1 = (r.inc + 1u) + (3u + r.inc);
+    const uint64_t ones = ((1ull << r.nn) - 1ull) << 1;                               // nn ones, the pass bit 0
+    const uint64_t lblock = ((((1ull << r.inc) - 1ull) << 1) << (3u + r.inc)) | len;  // inc ones, a zero, the length
+    if (n0 + n1 <= 64u) { r.tail[0] = (ones << n1) | lblock; r.tail_n[0] = n0 + n1; r.tail[1] = 0; r.tail_n[1] = 0; }
+    else { r.tail[0] = ones; r.tail_n[0] = n0; r.tail[1] = lblock; r.tail_n[1] = n1; }
+    r.nbits = r.nn + r.zeros + n0 + n1;
+    return r;
+}
+
+} // namespace grk_amd

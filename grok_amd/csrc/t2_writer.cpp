@@ -637,6 +637,7 @@ int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vect
             const uint32_t b = k.nbands++;
             k.first_block[b] = P.first_block; k.gw[b] = P.gw; k.gh[b] = P.gh; k.kmax[b] = B.kmax;
             k.height[b] = (uint32_t)tag_tree_height(P.gw, P.gh);
+            if (k.height[b] > kT2MaxHeight) return GRK_AMD_ERR_UNSUPPORTED;  // (t2_bits.h: a path's ones and the pass bit in 64 bits)
             const uint64_t n = (uint64_t)P.gw * P.gh;
             for (uint64_t i = 0; i < n; ++i) {
                 uint32_t& of = out.packet_of_block[k.row0 + P.first_block + i];

@@ -270,6 +270,21 @@ int grk_amd_stage_ht_encode16(grk_amd_ctx* ctx, const grk_amd_tile_params* p, ui
 int grk_amd_stage_ht_encode_drops(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles,
                                   const void* d_mallat, int planes16, const uint8_t* d_drops);
 
+/* Tier-2 on the device (the kernels behind grk_amd_assemble_device) over a table of the caller's choosing.  HOST pointers: `table` holds
+ * num_tiles x (code-blocks of a tile) rows in the order of grk_amd_fetch_table, whose offsets point into the coded_bytes bytes at
+ * `coded`; rows may share bytes; missing_msbs is ignored (GRK_AMD_CS_BLOCK_MSBS: GRK_AMD_ERR_UNSUPPORTED).  flags: GRK_AMD_CS_*.
+ * The geometry, the plan and its cache are grk_amd_assemble_device's.  Everything is checked on the host before anything is launched:
+ * GRK_AMD_ERR_INVALID for a tile index above 65 535 or a row whose offset + length lies beyond coded_bytes, GRK_AMD_ERR_UNSUPPORTED for
+ * a length above grk_amd_t2_max_block_bytes().  Synchronous.  Returns the bytes assembled -- the tile-parts one behind the other from
+ * offset 0, read with grk_amd_fetch_assembled -- and their lengths in part_bytes[num_tiles] (optional).  The latest
+ * grk_amd_encode_tiles call can still be assembled afterwards. */
+int64_t grk_amd_stage_assemble(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
+                               uint32_t flags, const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes,
+                               uint32_t* part_bytes);
+/* the longest code-block the device writer takes, in bytes; a longer one makes grk_amd_assemble_device and the whole-image encoders'
+ * device route return GRK_AMD_ERR_UNSUPPORTED (the image encoders then take the host writer) */
+uint32_t grk_amd_t2_max_block_bytes(void);
+
 /* ---- decode: the inverse hot path --------------------------------
  * TileProcessor::decompress T1 + post-T1 for HT blocks: T1HT::decompress (t1/t1_ht/T1HT.cpp:129-179,
  * ojph_decode_codeblock t1/t1_ht/coding/ojph_block_decoder.cpp:989), dequantisation

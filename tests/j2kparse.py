@@ -281,3 +281,25 @@ def parse_cod_layers(cs):
             break
         i += 2 + n
     raise ValueError("no COD marker segment in the main header")
+
+
+def plt_segments(part):
+    """The PLT marker segments of one tile-part (bytes from SOT on) -> [(Lplt, Zplt, [packet lengths])], in the order they are written."""
+    part = bytes(part)
+    assert part[:4] == b"\xff\x90\x00\x0a"
+    pos, out = 12, []
+    while part[pos:pos + 2] != b"\xff\x93":
+        marker, ln = struct.unpack(">HH", part[pos:pos + 4])
+        if marker == 0xFF58:
+            body = np.frombuffer(part[pos + 5:pos + 2 + ln], np.uint8)
+            last = np.nonzero((body & 0x80) == 0)[0]          # a number's last byte has no continuation bit
+            assert body.size == 0 or last[-1] == body.size - 1, "a packet length split over two marker segments"
+            vals, start = [], 0
+            for e in last.tolist():
+                v = 0
+                for b in body[start:e + 1].tolist():
+                    v = (v << 7) | (b & 0x7F)
+                vals.append(v); start = e + 1
+            out.append((ln, part[pos + 4], vals))
+        pos += 2 + ln
+    return out

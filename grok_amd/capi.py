@@ -96,6 +96,12 @@ class RateResult(C.Structure):
                 ("lambda_", C.c_double), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RateAllocResult(C.Structure):
+    """grk_amd_rate_alloc_result: everything the allocator kernel reports (Context.stage_rate_alloc)"""
+    _fields_ = [("block_bytes", C.c_uint64), ("lagrange_bytes", C.c_uint64), ("least_bytes", C.c_uint64), ("distortion", C.c_double),
+                ("lambda_", C.c_double), ("feasible", C.c_uint32), ("steps", C.c_uint32)]
+
+
 class RateError(RuntimeError):
     """a rate-targeted call refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ERR_OVERFLOW -5) and the context's reason"""
 
@@ -1081,6 +1087,48 @@ class Context:
         bytes on the device, 0 .. 254 bit-planes left out or DROP_SKIP; keep them until the table has been fetched."""
         self._check(self._L.grk_amd_stage_ht_encode_drops(self._h, C.byref(params), ntiles, d_mallat, int(bool(planes16)), d_drops),
                     "stage_ht_encode_drops")
+
+    def stage_rate_stats(self, params, ntiles, d_mallat, planes16, max_drop, first_rows=None, n=0, E=None):
+        """The statistics kernel on planes of the caller's (grk_amd_stage_rate_stats) -> E uint64 [max_drop + 2, n].  first_rows: the
+        map of a joint table (one first row per tile, rows of n entries), with E the table's contents beforehand; without one n is
+        the call's blocks.  StageError with the code and the context's reason when the call refuses."""
+        self._L.grk_amd_stage_rate_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p]
+        rows = None
+        if first_rows is None:
+            n = self._L.grk_amd_tile_num_blocks(C.byref(params)) * ntiles
+            out = np.zeros((int(max_drop) + 2, max(int(n), 0)), np.uint64)
+        else:
+            rows = np.ascontiguousarray(np.asarray(first_rows, np.uint64))
+            out = np.array(E, np.uint64, order="C").reshape(int(max_drop) + 2, int(n))
+        rc = self._L.grk_amd_stage_rate_stats(self._h, C.addressof(params), ntiles, d_mallat, int(bool(planes16)), int(max_drop),
+                                              rows.ctypes.data if rows is not None else None, int(n), out.ctypes.data)
+        if rc:
+            raise StageError("stage_rate_stats", rc, self._L.grk_amd_last_error(self._h).decode())
+        return out
+
+    def stage_rate_alloc(self, L, E, W, max_drop, allow_skip, budget):
+        """The allocator kernel on tables of the caller's (grk_amd_stage_rate_alloc): L uint32 and E uint64 [max_drop + 2, n], W
+        float64 [n] -> (drop bytes uint8 [n], RateAllocResult).  None for a table passes a null pointer.  StageError when the call
+        refuses."""
+        self._L.grk_amd_stage_rate_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64,
+                                                     C.c_void_p, C.c_void_p]
+        Lc = None if L is None else np.ascontiguousarray(L, np.uint32)
+        Ec = None if E is None else np.ascontiguousarray(E, np.uint64)
+        Wc = None if W is None else np.ascontiguousarray(W, np.float64)
+        n = next((a.shape[-1] for a in (Wc, Lc, Ec) if a is not None), 0)
+        rows = int(max_drop) + 2
+        for a in (Lc, Ec):
+            if a is not None and a.size != rows * n:
+                raise ValueError("stage_rate_alloc: a table of %d entries, not (max_drop + 2) x %d" % (a.size, n))
+        if Wc is not None and Wc.size != n:
+            raise ValueError("stage_rate_alloc: %d weights for %d blocks" % (Wc.size, n))
+        drops, res = np.zeros(max(n, 1), np.uint8), RateAllocResult()
+        rc = self._L.grk_amd_stage_rate_alloc(self._h, *(a.ctypes.data if a is not None else None for a in (Lc, Ec, Wc)), n,
+                                              int(max_drop), int(bool(allow_skip)), int(budget), drops.ctypes.data, C.addressof(res))
+        if rc:
+            raise StageError("stage_rate_alloc", rc, self._L.grk_amd_last_error(self._h).decode())
+        return drops[:n], res
 
     def encode_tiles_rate(self, params, ntiles, pixels_ptr, on_device, target_bytes, max_drop=0, allow_skip=False):
         """grk_amd_encode_tiles_rate: the batch's blocks in at most target_bytes -> (table, total arena bytes, RateResult)"""

@@ -170,7 +170,8 @@ struct grk_amd_ctx {
     } t2j;
     DevBuf jt_len, jt_off, jt_arena, jt_state, jt_rowat, jt_file;
     DevBuf st_len, st_off, st_arena, st_status;              // grk_amd_stage_assemble: the caller's rows and coded bytes, the call's status word
-    uint64_t route_counters[2] = {0, 0};                     // images assembled on the device / written by the host writer (grk_amd_encode_route_counters)
+    DevBuf st_rL, st_rE, st_rW, st_rdrop, st_rres, st_rmap;  // grk_amd_stage_rate_stats / _alloc: the caller's tables, apart from rate_*
+    uint64_t route_counters[2] = {0, 0};                   // images assembled on the device / written by the host writer (grk_amd_encode_route_counters)
     uint64_t last_arena_bound = 0;                           // the arena K3's plan asked for in the latest call (plan_ht_arena), <= arena.cap
     std::vector<uint64_t> h_off;
     std::vector<uint32_t> h_len;

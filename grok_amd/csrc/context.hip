@@ -313,6 +313,7 @@ void grk_amd_destroy(grk_amd_ctx* c)
     for (auto& k : c->t2j.classes) { k.packets.release(); k.pob.release(); }
     for (DevBuf* b : {&c->jt_len, &c->jt_off, &c->jt_arena, &c->jt_state, &c->jt_rowat, &c->jt_file}) b->release();
     for (DevBuf* b : {&c->st_len, &c->st_off, &c->st_arena, &c->st_status}) b->release();
+    for (DevBuf* b : {&c->st_rL, &c->st_rE, &c->st_rW, &c->st_rdrop, &c->st_rres, &c->st_rmap}) b->release();
     if (c->ev_level0) (void)hipEventDestroy(c->ev_level0);
     if (c->ev_side) (void)hipEventDestroy(c->ev_side);
     for (DevBuf* b : {&c->dec_seg_dev, &c->img_coded, &c->img_tiles, &c->img_pixels, &c->img_moves, &c->img_rects, &c->img_status, &c->img_planes}) b->release();

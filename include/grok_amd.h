@@ -285,6 +285,39 @@ int64_t grk_amd_stage_assemble(grk_amd_ctx* ctx, const grk_amd_tile_params* p, u
  * device route return GRK_AMD_ERR_UNSUPPORTED (the image encoders then take the host writer) */
 uint32_t grk_amd_t2_max_block_bytes(void);
 
+/* The statistics kernel of the rate-targeted encodes (KR1, see grk_amd_encode_tiles_rate below) on planes of the caller's choosing.
+ * d_mallat: DEVICE planes of num_tiles tiles, int32 (float32 bit patterns for 9/7), or with planes16 != 0 int16 under the conditions of
+ * grk_amd_stage_ht_encode16.  The kernel runs over the context's block descriptors for *p, as a rate-targeted call runs it, and E
+ * (HOST, uint64 [max_drop + 2][n], row max_drop + 1: SKIP) receives what it wrote.  first_rows == NULL: n is ignored and taken as
+ * num_tiles * (code-blocks of a tile), block i of the call is column i.  first_rows (HOST, [num_tiles]) != NULL: the map of a joint
+ * table -- block j of tile t is column first_rows[t] + j of rows of n entries; the caller's contents of E are uploaded first, so that
+ * every entry the kernel did not write comes back as it went in.  Everything is checked on the host before anything is launched:
+ * GRK_AMD_ERR_INVALID for max_drop 0 or above 12, for a first row whose tile would end beyond n, for int16 planes where no encode
+ * keeps them (9/7 among them).  Synchronous.  The tables of the latest rate-targeted call stay as they are. */
+int grk_amd_stage_rate_stats(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const void* d_mallat, int planes16,
+                             uint32_t max_drop, const uint64_t* first_rows, uint64_t n, uint64_t* E);
+
+/* The allocator of the rate-targeted encodes (KR2) on tables of the caller's choosing.  HOST pointers: L uint32 [rows][n] (every entry
+ * below 2^31), E uint64 [rows][n], W double [n] (positive), rows = max_drop + 2 whether or not SKIP may be chosen (allow_skip == 0: the
+ * last row is not read).  One launch of the kernel for `budget` bytes; drops[n] receives the drop bytes (0 .. max_drop, 0xFF: SKIP)
+ * and *result everything the kernel reports: the bytes of the final choice, of the Lagrange solution before the fill and of the
+ * shortest choice there is, the final choice's sum of W E, the multiplier, whether the budget is feasible (least_bytes <= budget) and
+ * the evaluations the multiplier search made.  A budget below least_bytes is no error of this call: feasible = 0 and the drops are
+ * those of the shortest choice.  GRK_AMD_ERR_INVALID, before anything is launched: max_drop 0 or above 12, n 0, a null pointer, an
+ * entry of L of 2^31 or more.  Synchronous.  The tables go to buffers of their own: the tables, the budget and the drops of the
+ * latest rate-targeted call (grk_amd_rate_tables, grk_amd_rate_last_budget) stay valid. */
+typedef struct grk_amd_rate_alloc_result {
+    uint64_t block_bytes;    /* the final choice's bytes */
+    uint64_t lagrange_bytes; /* ... the Lagrange solution's, before the fill (the shortest choice's where no multiplier was used) */
+    uint64_t least_bytes;    /* the fewest bytes any choice takes */
+    double   distortion;     /* sum of W_b E over the final choice */
+    double   lambda;         /* the multiplier; 0: the finest candidates fit, or the budget is not feasible */
+    uint32_t feasible;       /* least_bytes <= budget */
+    uint32_t steps;          /* evaluations of the multiplier search: bracketing (at most 200) + 40 bisections; 0: no search */
+} grk_amd_rate_alloc_result;
+int grk_amd_stage_rate_alloc(grk_amd_ctx* ctx, const uint32_t* L, const uint64_t* E, const double* W, uint64_t n, uint32_t max_drop,
+                             int allow_skip, uint64_t budget, uint8_t* drops, grk_amd_rate_alloc_result* result);
+
 /* ---- decode: the inverse hot path --------------------------------
  * TileProcessor::decompress T1 + post-T1 for HT blocks: T1HT::decompress (t1/t1_ht/T1HT.cpp:129-179,
  * ojph_decode_codeblock t1/t1_ht/coding/ojph_block_decoder.cpp:989), dequantisation

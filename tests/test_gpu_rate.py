@@ -2,19 +2,19 @@
 oracle's block coder at the reduced exponent bound; the statistics kernel against a numpy restatement; the trial lengths; the
 allocator's result against its own tables (grk_amd_rate_tables); whole files of at most N bytes (grk_amd_encode_image_rate) read back
 by grk_amd_decode_image and by the reference; the refusals."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import grok_amd as G
 import gpuutil as U
-import ht_content as HC
 import oracle as O
+import ratemodel as RM
+import rateplanes as RP
 import refharness as R
 import synth
 from grok_amd.capi import ERR_OVERFLOW, ERR_UNSUPPORTED
+from rateplanes import FORMS, GEOMS
 
 pytestmark = pytest.mark.gpu
 SKIP = G.DROP_SKIP
@@ -22,46 +22,10 @@ DMAX = 6
 
 
 # ---- 1. the block coder with drops == the oracle at the exponent bound kmax - d ------------------------------------------------
-FORMS = {"int32 reversible": (12, False, False), "int32 irreversible": (12, True, False), "int16": (8, False, True)}     # prec, 9/7, int16 planes
-GEOMS = {"cblk 64": (128, 128, (6, 6)), "cblk 32": (128, 128, (5, 5)), "cblk 4": (128, 128, (2, 2)), "ragged 77x53": (77, 53, (5, 5))}
-
-
 def planes_case(form, geom, seed, mode_of=None):
-    """one component, 2 levels: -> (params, blocks, the device planes, planes16, [sign-magnitude words of every block as the d = 0
+    """rateplanes.planes_case: -> (params, blocks, the device planes, planes16, [sign-magnitude words of every block as the d = 0
     coder sees them])"""
-    prec, irrev, h16 = FORMS[form]
-    W, H, cblk = GEOMS[geom]
-    p = G.TileParams.make(W, H, 1, prec, 2, irreversible=irrev, mct=False, cblk=cblk)
-    blocks, _ = G.tile_layout(p)
-    rng = np.random.default_rng(seed)
-    modes = [0, 1, 2, 5, "P", 4]
-    mags = np.zeros((H, W), np.int64)
-    for i, b in enumerate(blocks):
-        bw, bh = b.x1 - b.x0, b.y1 - b.y0
-        mode = mode_of(i) if mode_of else modes[i % len(modes)]
-        m = HC.magnitudes(rng, bh, bw, b.kmax, mode) if not isinstance(mode, tuple) else rng.integers(0, mode[1], (bh, bw))
-        mags[b.py:b.py + bh, b.px:b.px + bw] = m
-    sgn = np.where(rng.random((H, W)) < 0.5, -1, 1)
-    sms = []
-    if irrev:
-        planes = np.zeros((1, H, W), np.float32)
-        for b in blocks:
-            bw, bh = b.x1 - b.x0, b.y1 - b.y0
-            sl = (slice(b.py, b.py + bh), slice(b.px, b.px + bw))
-            planes[0][sl] = (sgn[sl] * (mags[sl] + np.where(mags[sl] > 0, 0.37, 0.0)) * float(b.stepsize)).astype(np.float32)
-            sub = np.ascontiguousarray(planes[0][sl])
-            sm = np.zeros((bh, bw), np.uint32)
-            O.lib().orc_ht_signmag_irrev(sub.ctypes.data, bw, bw, bh, b.kmax, C.c_float(np.float32(1.0) / np.float32(b.stepsize)), sm.ctypes.data)
-            assert np.array_equal((sm & 0x7FFFFFFF) >> (30 - b.kmax), mags[sl])
-            sms.append(sm)
-        dev = U.upload_planes(planes.view(np.int32), p)
-    else:
-        planes = (sgn * mags)[None]
-        for b in blocks:
-            bw, bh = b.x1 - b.x0, b.y1 - b.y0
-            sms.append(O.signmag(planes[0, b.py:b.py + bh, b.px:b.px + bw], b.kmax))
-        dev = U.upload_planes16(planes, p) if h16 else U.upload_planes(planes.astype(np.int32), p)
-    return p, blocks, dev, h16, sms
+    return RP.planes_case(form, geom, seed, mode_of)[:5]
 
 
 def expected_block(sm, kmax, drop):
@@ -182,24 +146,16 @@ def rate_run(irrev, budget_div, skip=True, dmax=DMAX):
 
 
 def quantised(r, b):
-    """the magnitudes the d = 0 coder codes for block b: |x|, or trunc(|c| * (1 / step)) in float32, clamped to 2^kmax - 1"""
+    """the magnitudes the d = 0 coder codes for block b (ratemodel.quantised)"""
     sub = r["planes"][b.comp, b.py:b.py + b.y1 - b.y0, b.px:b.px + b.x1 - b.x0]
-    if not r["p"].irreversible:
-        return np.abs(sub.astype(np.int64))
-    q = (np.abs(sub).astype(np.float32) * (np.float32(1.0) / np.float32(b.stepsize))).astype(np.float32)
-    return np.minimum(np.trunc(q).astype(np.int64), (1 << b.kmax) - 1)
+    return RM.quantised(sub, b.kmax, b.stepsize, bool(r["p"].irreversible))
 
 
 def restated_errors(r, dmax):
-    """E as include/grok_amd.h defines it: c taken as min(c, kmax - 1), the drop the coder clamps to"""
+    """E as include/grok_amd.h defines it (ratemodel.errors): c taken as min(c, kmax - 1), the drop the coder clamps to"""
     want = np.zeros_like(r["E"])
     for i, b in enumerate(r["blocks"]):
-        q = quantised(r, b)
-        for c in range(1, dmax + 1):
-            ce = min(c, b.kmax - 1)
-            rc = np.where(q >> ce == 0, 0, ((q >> ce) << ce) + ((1 << ce) >> 1))
-            want[c, i] = int(((2 * q - 2 * rc) ** 2).sum())
-        want[dmax + 1, i] = int(((2 * q) ** 2).sum())
+        want[:, i] = RM.errors(quantised(r, b), b.kmax, dmax)
     return want
 
 

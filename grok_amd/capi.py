@@ -102,6 +102,25 @@ class RateAllocResult(C.Structure):
                 ("lambda_", C.c_double), ("feasible", C.c_uint32), ("steps", C.c_uint32)]
 
 
+class Quality(C.Structure):
+    """grk_amd_quality: target_psnr (dB over all samples of all components; > 0: used, inf: D = 0), target_distortion (used when
+    target_psnr == 0: D in the units of RateResult.distortion), max_drop (Dmax; 0 = 6, at most 12), allow_skip"""
+    _fields_ = [("target_psnr", C.c_double), ("target_distortion", C.c_double), ("max_drop", C.c_uint8), ("allow_skip", C.c_uint8),
+                ("reserved", C.c_uint8 * 6)]
+
+
+class QualityResult(C.Structure):
+    """grk_amd_quality_result"""
+    _fields_ = [("block_bytes", C.c_uint64), ("lagrange_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("distortion", C.c_double),
+                ("budget", C.c_double), ("psnr", C.c_double), ("lambda_", C.c_double), ("steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class QualityAllocResult(C.Structure):
+    """grk_amd_quality_alloc_result: everything the quality allocator kernel reports (Context.stage_quality_alloc)"""
+    _fields_ = [("block_bytes", C.c_uint64), ("lagrange_bytes", C.c_uint64), ("shortest_bytes", C.c_uint64), ("distortion", C.c_double),
+                ("floor", C.c_double), ("lambda_", C.c_double), ("feasible", C.c_uint32), ("steps", C.c_uint32)]
+
+
 class RateError(RuntimeError):
     """a rate-targeted call refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, ERR_OVERFLOW -5) and the context's reason"""
 
@@ -336,6 +355,20 @@ def lib():
             L.grk_amd_rate_unit_rows.argtypes = [vp, vp, u32]
             L.grk_amd_rate_last_budget.restype = u64
             L.grk_amd_rate_last_budget.argtypes = [vp]
+        if hasattr(L, "grk_amd_encode_tiles_quality"):
+            PQ, PQR, f64 = C.POINTER(Quality), C.POINTER(QualityResult), C.c_double
+            L.grk_amd_encode_tiles_quality.argtypes = [vp, PP, u32, vp, i32, PQ, vp, C.POINTER(u64), PQR]
+            L.grk_amd_encode_image_quality.restype = C.c_int64
+            L.grk_amd_encode_image_quality.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, u32, PQ, vp, u64, PQR]
+            L.grk_amd_encode_image_subsampled_quality.restype = C.c_int64
+            L.grk_amd_encode_image_subsampled_quality.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, vp, vp, u32, PQ, vp, u64, PQR]
+            L.grk_amd_encode_surface_quality.restype = C.c_int64
+            L.grk_amd_encode_surface_quality.argtypes = [vp, C.POINTER(ImageLayout), PP, vp, vp, vp, vp, u64, i32, u32, PQ, vp, u64, PQR]
+            L.grk_amd_encode_packed_quality.restype = C.c_int64
+            L.grk_amd_encode_packed_quality.argtypes = [vp, C.POINTER(ImageLayout), PP, i32, u64, vp, u64, i32, u32, PQ, vp, u64, PQR]
+            L.grk_amd_quality_last_budget.restype = f64
+            L.grk_amd_quality_last_budget.argtypes = [vp]
+            L.grk_amd_stage_quality_alloc.argtypes = [vp, vp, vp, vp, u64, u32, i32, f64, vp, vp]
         L.grk_amd_stage_dwt_inv.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_decode.argtypes = [vp, PP, u32, vp, vp, u64, vp]
         L.grk_amd_stage_ht_decode16.argtypes = [vp, PP, u32, vp, vp, u64, vp]
@@ -1190,6 +1223,103 @@ class Context:
         if n < 0:
             raise RateError("encode_surface_rate", n, self._L.grk_amd_last_error(self._h).decode())
         return out[:n].tobytes(), res
+
+    # ---- quality-targeted encodes: the rate calls' twins, for a PSNR (or, with psnr = 0, a distortion budget) ----
+    @staticmethod
+    def _quality(psnr, distortion, max_drop, allow_skip):
+        return Quality(float(psnr), float(distortion), int(max_drop), int(bool(allow_skip))), QualityResult()
+
+    def stage_quality_alloc(self, L, E, W, max_drop, allow_skip, budget):
+        """The quality allocator kernel on tables of the caller's (grk_amd_stage_quality_alloc): L uint32 and E uint64 [max_drop + 2, n],
+        W float64 [n], budget: the distortion D -> (drop bytes uint8 [n], QualityAllocResult).  None for a table passes a null
+        pointer.  StageError when the call refuses."""
+        Lc = None if L is None else np.ascontiguousarray(L, np.uint32)
+        Ec = None if E is None else np.ascontiguousarray(E, np.uint64)
+        Wc = None if W is None else np.ascontiguousarray(W, np.float64)
+        n = next((a.shape[-1] for a in (Wc, Lc, Ec) if a is not None), 0)
+        rows = int(max_drop) + 2
+        for a in (Lc, Ec):
+            if a is not None and a.size != rows * n:
+                raise ValueError("stage_quality_alloc: a table of %d entries, not (max_drop + 2) x %d" % (a.size, n))
+        if Wc is not None and Wc.size != n:
+            raise ValueError("stage_quality_alloc: %d weights for %d blocks" % (Wc.size, n))
+        drops, res = np.zeros(max(n, 1), np.uint8), QualityAllocResult()
+        rc = self._L.grk_amd_stage_quality_alloc(self._h, *(a.ctypes.data if a is not None else None for a in (Lc, Ec, Wc)), n,
+                                                 int(max_drop), int(bool(allow_skip)), float(budget), drops.ctypes.data, C.addressof(res))
+        if rc:
+            raise StageError("stage_quality_alloc", rc, self._L.grk_amd_last_error(self._h).decode())
+        return drops[:n], res
+
+    def encode_tiles_quality(self, params, ntiles, pixels_ptr, on_device, psnr, distortion=0.0, max_drop=0, allow_skip=False):
+        """grk_amd_encode_tiles_quality: the batch's blocks in the fewest bytes for the target -> (table, total arena bytes, QualityResult)"""
+        n = self._L.grk_amd_tile_num_blocks(C.byref(params)) * ntiles
+        table = np.zeros(n, CODED_DTYPE)
+        tot = C.c_uint64(0)
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        rc = self._L.grk_amd_encode_tiles_quality(self._h, C.byref(params), ntiles, pixels_ptr, int(on_device), C.byref(q), table.ctypes.data,
+                                                  C.byref(tot), C.byref(res))
+        if rc:
+            raise RateError("encode_tiles_quality", rc, self._L.grk_amd_last_error(self._h).decode())
+        return table, tot.value, res
+
+    def encode_image_quality(self, layout, base, pixels, psnr, distortion=0.0, flags=0, max_drop=0, allow_skip=False):
+        """grk_amd_encode_image_quality: the image as the shortest file the allocator finds for the target, over joint tables ->
+        (codestream bytes, QualityResult)"""
+        px = np.ascontiguousarray(pixels)
+        cap = px.size * 4 + (1 << 20)
+        out = np.empty(cap, np.uint8)
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        n = self._L.grk_amd_encode_image_quality(self._h, C.byref(layout), C.byref(base), px.ctypes.data, flags, C.byref(q), out.ctypes.data,
+                                                 cap, C.byref(res))
+        if n < 0:
+            raise RateError("encode_image_quality", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def encode_image_subsampled_quality(self, layout, base, sampling, planes, psnr, distortion=0.0, flags=0, max_drop=0, allow_skip=False):
+        """grk_amd_encode_image_subsampled_quality -> (codestream bytes, QualityResult)"""
+        dx = (C.c_uint8 * len(sampling))(*[int(a) for a, _ in sampling])
+        dy = (C.c_uint8 * len(sampling))(*[int(b) for _, b in sampling])
+        px = np.concatenate([np.ascontiguousarray(pl).reshape(-1) for pl in planes])
+        cap = px.size * px.itemsize * 4 + (1 << 20)
+        out = np.empty(cap, np.uint8)
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        n = self._L.grk_amd_encode_image_subsampled_quality(self._h, C.byref(layout), C.byref(base), C.addressof(dx), C.addressof(dy),
+                                                            px.ctypes.data, flags, C.byref(q), out.ctypes.data, cap, C.byref(res))
+        if n < 0:
+            raise RateError("encode_image_subsampled_quality", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def encode_surface_quality(self, layout, base, sampling, surface, pixels, psnr, distortion=0.0, flags=0, cap=None, max_drop=0,
+                               allow_skip=False):
+        """grk_amd_encode_surface_quality -> (codestream bytes, QualityResult).  pixels: a uint8 numpy array holding the surface (host),
+        or a device pointer (int) together with `cap`"""
+        dx, dy = _sampling(sampling)
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        out_cap = nbytes * 4 + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        n = self._L.grk_amd_encode_surface_quality(self._h, C.byref(layout), C.byref(base), C.cast(dx, C.c_void_p), C.cast(dy, C.c_void_p),
+                                                   C.byref(surface), ptr, nbytes, on_device, flags, C.byref(q), out.ctypes.data, out_cap,
+                                                   C.byref(res))
+        if n < 0:
+            raise RateError("encode_surface_quality", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def encode_packed_quality(self, layout, base, fmt, pixels, psnr, distortion=0.0, pitch=0, flags=0, cap=None, max_drop=0, allow_skip=False):
+        """grk_amd_encode_packed_quality -> (codestream bytes, QualityResult)"""
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        out_cap = nbytes * 4 + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        n = self._L.grk_amd_encode_packed_quality(self._h, C.byref(layout), C.byref(base), PACKED_FORMATS.get(fmt, fmt), int(pitch), ptr, nbytes,
+                                                  on_device, flags, C.byref(q), out.ctypes.data, out_cap, C.byref(res))
+        if n < 0:
+            raise RateError("encode_packed_quality", n, self._L.grk_amd_last_error(self._h).decode())
+        return out[:n].tobytes(), res
+
+    def quality_last_budget(self):
+        """grk_amd_quality_last_budget: the distortion budget the quality allocator last ran with (0.0 after a rate-targeted call)"""
+        return float(self._L.grk_amd_quality_last_budget(self._h))
 
     def rate_num_blocks(self):
         """grk_amd_rate_num_blocks: the blocks the latest rate-targeted call's tables are over (a joint call: the whole image's)"""

@@ -186,7 +186,8 @@ struct grk_amd_ctx {
     // batches' maps (RateJointPlan) and rate_bdrop the drop bytes of the batch being coded; unit_rows: each unit's first row
     DevBuf rate_L, rate_E, rate_W, rate_drop, rate_res, rate_map, rate_bdrop;
     struct RateState { bool valid = false; RatePlan plan{}; uint64_t nblocks = 0; uint32_t ntiles = 0; std::vector<uint64_t> unit_rows;
-                       uint64_t budget = 0; /* of the latest allocator run */ } rate;
+                       uint64_t budget = 0; /* of the latest allocator run (0: that was KQ) */
+                       double qbudget = 0; /* the distortion budget of the latest run of KQ (0: that was KR2) */ } rate;
     HostStage stage;                 // pinned chunks for pageable host buffers (copy_h2d)
     void* d2h_pin = nullptr; size_t d2h_cap = 0; std::vector<hipEvent_t> d2h_ev;   // copy_d2h: a staging area of the transfer's size, an event per piece
     // Full decode with overlap on: K5b of the top resolution's blocks (3/4 of them) runs on the side stream beside K5b of the
@@ -284,7 +285,7 @@ int sequence_streams(grk_amd_ctx* k, bool part1);                               
 
 // KS (place = false) or KD for `count` units of w x h samples of one run, tight at d_tiles, their origins (device memory) at
 // d_origins; the surface's first byte at d_surface (surface.cpp).  The caller checked the surface against its buffer
-namespace grk_amd { struct ResolvedSurface; struct CompRun; }
+namespace grk_amd { struct ResolvedSurface; struct CompRun; struct QualityGoal; }
 int queue_surface_kernel(grk_amd_ctx* c, bool place, const grk_amd::ResolvedSurface& rs, const grk_amd::CompRun& run, void* d_surface,
                          void* d_tiles, uint32_t count, uint32_t w, uint32_t h, const uint32_t* d_origins);                  // surface.cpp
 bool surface_direct_allowed();            // GRK_AMD_SURFACE_DIRECT != 0, read per call (surface.cpp)
@@ -295,7 +296,8 @@ int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const
                            uint32_t flags, uint8_t* out, uint64_t out_cap, void** d_file = nullptr);                        // surface.cpp
 int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                                 const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
-                                uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);   // surface.cpp
+                                uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result,
+                                const grk_amd::QualityGoal* quality = nullptr);   // surface.cpp (quality: image.h, RateJointCall)
 // grk_amd_decode_surface behind its null checks (`name`: the entry point, for a refusal's text); host_rules: a device surface under
 // the rules of a host destination -- a group that leaves the int16 planes is repeated by the call itself
 int decode_onto_surface(grk_amd_ctx* c, const char* name, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels,

@@ -120,6 +120,32 @@ RateJointPlan plan_rate_joint(uint32_t max_drop, bool allow_skip, const std::vec
     return r;
 }
 
+QualityPlan plan_quality(double target_psnr, double target_distortion, uint32_t prec, uint64_t samples)
+{
+    const QualityPlan refused{};
+    if (!(target_psnr >= 0.0) || prec == 0 || prec > 16 || !samples) return refused;
+    QualityPlan r{};
+    const double peak = (double)((1u << prec) - 1u);
+    r.signal = (double)samples * peak * peak;
+    if (target_psnr > 0.0) r.budget = std::isinf(target_psnr) ? 0.0 : r.signal * std::pow(10.0, -target_psnr / 10.0);
+    else if (target_distortion >= 0.0) r.budget = target_distortion;
+    else return refused;
+    r.ok = true;
+    return r;
+}
+
+uint64_t quality_samples(const grk_amd_image_layout& im, uint32_t num_comps, const uint8_t* comp_dx, const uint8_t* comp_dy)
+{
+    if (im.x1 <= im.x0 || im.y1 <= im.y0) return 0;
+    uint64_t s = 0;
+    for (uint32_t c = 0; c < num_comps; ++c) {
+        const uint64_t dx = comp_dx ? comp_dx[c] : 1u, dy = comp_dy ? comp_dy[c] : 1u;
+        if (!dx || !dy) return 0;
+        s += ((im.x1 + dx - 1) / dx - (im.x0 + dx - 1) / dx) * ((im.y1 + dy - 1) / dy - (im.y0 + dy - 1) / dy);
+    }
+    return s;
+}
+
 // ---- the arena and its allocator ---------------------------------------------------------------------------------------------------
 HtArenaPlan plan_ht_arena(uint64_t nblocks, uint64_t raw_bytes, uint32_t ntiles, const std::vector<HtClassPlan>& classes)
 {

@@ -7,6 +7,7 @@
 #include "dwt_instances.h"
 #include "encode_constants.h"
 #include "geometry.h"
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -84,6 +85,21 @@ struct RateJointPlan {
 };
 RateJointPlan plan_rate_joint(uint32_t max_drop, bool allow_skip, const std::vector<uint64_t>& unit_blocks,
                               const std::vector<std::vector<uint32_t>>& batches);
+// A quality target as the distortion budget the quality allocator (KQ) takes: D = S * peak^2 * 10^(-psnr / 10) with peak = 2^prec - 1
+// and S the samples the PSNR is over -- the sum over the components of the component's OWN samples in the image area
+// (quality_samples): a sub-sampled component counts its own samples, with no area factor, the convention W and `distortion` follow.
+// target_psnr > 0: used (+infinity: D = 0); target_psnr == 0: D = target_distortion, which must be >= 0.
+// ok = false: a negative or NaN target_psnr, a negative or NaN target_distortion where it is used, prec 0 or above 16, no sample.
+struct QualityPlan {
+    bool ok;
+    double budget;                     // D
+    double signal;                     // S * peak^2: the model's PSNR of a distortion d is 10 log10(signal / d)
+};
+QualityPlan plan_quality(double target_psnr, double target_distortion, uint32_t prec, uint64_t samples);
+inline double quality_psnr(double signal, double distortion) { return distortion > 0 ? 10.0 * std::log10(signal / distortion) : INFINITY; }
+// S of an image area for components with factors comp_dx / comp_dy (nullptr: all 1): component c holds ceil(x1 / dx) - ceil(x0 / dx)
+// columns and ceil(y1 / dy) - ceil(y0 / dy) rows, however the area is tiled.  0: an empty area or a factor of 0.
+uint64_t quality_samples(const grk_amd_image_layout& im, uint32_t num_comps, const uint8_t* comp_dx, const uint8_t* comp_dy);
 // the drop byte of candidate c, and the row's zero bit-planes for a drop byte (d clamped to Kmax - 1; SKIP: Kmax - 1)
 inline uint8_t rate_drop_byte(uint32_t c, uint32_t dmax) { return c <= dmax ? (uint8_t)c : (uint8_t)kHtDropSkip; }
 inline uint32_t drop_missing_msbs(uint32_t kmax, uint32_t drop)

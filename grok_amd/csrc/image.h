@@ -136,13 +136,26 @@ int subsampled_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk
 // the batch's map: plan_rate_joint), runs KR2 once per round over them -- one multiplier for every block of the image -- and codes
 // each batch with its slice of the chosen drops; the rounds are rate_rounds' (rate.hip), shared with the split route.  Returns the
 // file's length or an error; rate_refusal: what every rate-targeted call refuses before any work (pipelining, max_drop).
+// The call's goal is bytes (rate->target_bytes, the rounds above), or -- quality != nullptr -- a distortion budget: the same tables,
+// then KQ once over them, every batch coded with its slice of the drops and the file written once; no rounds (headers do not enter a
+// distortion budget).  rate then carries max_drop and allow_skip only (QualityTarget makes both from a grk_amd_quality), and the
+// result goes to quality->result.
 struct RateBatch { grk_amd_tile_params p; std::vector<uint32_t> units; };
+struct QualityGoal { double budget, signal; grk_amd_quality_result* result; };       // plan_quality's D and S peak^2 (encode_plan.h)
 struct RateJointCall {
     const grk_amd_tile_params* base; const grk_amd_rate* rate;
     std::vector<uint64_t> unit_blocks; std::vector<RateBatch> batches;
     std::function<int(size_t k, grk_amd_coded_block* table, uint64_t* total)> front;
     std::function<int64_t(const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* out, uint64_t cap)> write;
+    const QualityGoal* quality = nullptr;
 };
+// A grk_amd_quality checked and turned into what the joint call takes: GRK_AMD_OK, or what every quality-targeted call refuses before
+// any work -- pipelining (GRK_AMD_ERR_UNSUPPORTED), max_drop above 12, a target plan_quality refuses (GRK_AMD_ERR_INVALID).  The
+// tables of an earlier call are invalid from here on, refused or not.
+// samples: S of the call (quality_samples, encode_plan.h)
+struct QualityTarget { grk_amd_rate rate; QualityGoal goal; };
+int quality_target(grk_amd_ctx* ctx, const grk_amd_quality* quality, uint32_t prec, uint64_t samples, grk_amd_quality_result* result,
+                   QualityTarget& out);
 int rate_refusal(grk_amd_ctx* ctx, const grk_amd_rate* rate);
 int64_t encode_rate_joint(grk_amd_ctx* ctx, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result);
 

@@ -153,6 +153,39 @@ struct RateAllocArgs {
     RateAllocResult* res;
 };
 hipError_t launch_rate_alloc(const RateAllocArgs& a, hipStream_t s);
+// KQ, the quality allocator: one workgroup of kRateAllocThreads like KR2, over the same L, E, W (> 0) and ncand, for a distortion
+// budget D (a double, >= 0) instead of a byte budget: the fewest bytes it finds whose sum of W E is <= D.  Fixed-order sums only.
+// choose(b, lambda) is KR2's: the smallest W E + lambda L, the finer candidate on a tie.
+//   floor = sum over b of W_b * min_c E[c][b]; feasible = floor <= D.
+//   Not feasible: every block goes to its least-E candidate, the finer of equal ones; there is no search and no trim; feasible = 0
+//   (no error of the stage call).
+//   dist_at(lambda) = sum of W_b * (double)E[choose(b, lambda)][b]; in exact arithmetic it does not fall as lambda rises.
+//   The shortest choice is KR2's fallback: the smallest L, the finer of equally short ones.  If its distortion is <= D it is the
+//   answer; lambda is then reported as +infinity and steps as 0.
+//   Otherwise the search mirrors KR2's, with the same limits: it starts from 1; it doubles while the doubled multiplier still fits
+//   (dist_at <= D), or halves until one fits; bracketing takes at most 200 steps; kRateBisectSteps bisections follow, which keep the
+//   LOWER end fitting; lambda = lo.  Halving that never fits ends at lo = 0, which fits when feasible.
+//   The Lagrange choice at lambda gives lagrange_bytes and its distortion.
+//   The trim is the fill's mirror image, in table order, kFillChunk / 2 blocks at a time (a table of doubles with kFillSteps columns:
+//   at kFillChunk it would not fit a workgroup's 64 KB beside the reduction buffers) in the fill's three phases -- a thread per chain,
+//   one walker, a thread per write-back.  A block moves to the next coarser candidate (c + 1 < ncand) while L strictly falls and
+//   delta = W_b * (double)((int64)E[c + 1][b] - (int64)E[c][b]) is <= left; then left -= delta.  left starts as D - the Lagrange
+//   choice's distortion.  A block that does not fit is passed over and the walk goes on.
+//   The drops are written as KR2 writes them (0 .. dmax, 0xFF for SKIP).
+struct RateQualityResult {
+    unsigned long long block_bytes, lagrange_bytes, shortest_bytes;   // the final choice's bytes; the Lagrange choice's; the shortest choice's
+    double distortion, floor, lambda;                                 // sum of W E summed afresh over the final choice; see above
+    uint32_t feasible, steps;                                         // floor <= D; evaluations of the multiplier search
+};
+struct RateQualityArgs {
+    const uint32_t* L; const unsigned long long* E; const double* W;   // as RateAllocArgs
+    uint64_t nblocks; uint32_t dmax, ncand;
+    double budget;                                                     // D
+    uint8_t* drop;
+    RateQualityResult* res;
+};
+// refuses what launch_rate_alloc refuses, and a D that is negative or NaN
+hipError_t launch_rate_quality(const RateQualityArgs& a, hipStream_t s);
 
 // ---- K5: HT cleanup decoder + dequantisation (kernels_htdec.hip) --------------------------------
 struct HtDecBlock {          // one per code-block, same layout as grk_amd_coded_block

@@ -9,6 +9,9 @@
 //                          decoder reconstructs, in units of (half a quantisation step)^2
 //   KR2 rate_alloc_kernel  one workgroup: bisects the Lagrange multiplier over the tables (lengths from trial launches of the DROP
 //                          instances, the errors of KR1, the blocks' weights), then spends what the budget has left in table order
+// and, for a quality target, one more over the same tables:
+//   KQ  rate_quality_kernel  one workgroup: the largest multiplier whose choice keeps the sum of W E within a distortion budget, then
+//                          a trim in table order that gives up whatever bytes the slack still pays for
 // Everything is integer or a fixed-order double sum: two runs give the same bytes.
 #include "kernels.h"
 
@@ -104,6 +107,27 @@ __device__ __forceinline__ T block_sum(T v, T* red)
     return red[0];
 }
 
+// candidate of block b under multiplier lambda: the smallest W E + lambda L, the finer one of a tie (KR2 and KQ)
+__device__ __forceinline__ uint32_t rate_choose(const uint32_t* L, const unsigned long long* E, const double* W, uint64_t n, uint32_t ncand,
+                                                uint64_t b, double lambda)
+{
+    const double w = W[b];
+    double best = 0; uint32_t bc = 0;
+    for (uint32_t c = 0; c < ncand; ++c) {
+        const double cost = w * (double)E[(uint64_t)c * n + b] + lambda * (double)L[(uint64_t)c * n + b];
+        if (c == 0 || cost < best) { best = cost; bc = c; }
+    }
+    return bc;
+}
+
+// the shortest candidate of block b, the finer one of equally short ones: the choice no multiplier undercuts
+__device__ __forceinline__ uint32_t rate_shortest(const uint32_t* L, uint64_t n, uint32_t ncand, uint64_t b)
+{
+    uint32_t c = 0;
+    for (uint32_t k = 1; k < ncand; ++k) if (L[(uint64_t)k * n + b] < L[(uint64_t)c * n + b]) c = k;
+    return c;
+}
+
 __global__ __launch_bounds__(kRateAllocThreads) void rate_alloc_kernel(RateAllocArgs a)
 {
     __shared__ unsigned long long red_u[kRateAllocThreads];
@@ -114,16 +138,7 @@ __global__ __launch_bounds__(kRateAllocThreads) void rate_alloc_kernel(RateAlloc
     const uint64_t n = a.nblocks;
     const uint32_t ncand = a.ncand;
 
-    // candidate of block b under multiplier lambda: the smallest W E + lambda L, the finer one of a tie
-    auto choose = [&](uint64_t b, double lambda) -> uint32_t {
-        const double w = a.W[b];
-        double best = 0; uint32_t bc = 0;
-        for (uint32_t c = 0; c < ncand; ++c) {
-            const double cost = w * (double)a.E[(uint64_t)c * n + b] + lambda * (double)a.L[(uint64_t)c * n + b];
-            if (c == 0 || cost < best) { best = cost; bc = c; }
-        }
-        return bc;
-    };
+    auto choose = [&](uint64_t b, double lambda) -> uint32_t { return rate_choose(a.L, a.E, a.W, n, ncand, b, lambda); };
     auto total_at = [&](double lambda) -> unsigned long long {
         unsigned long long s = 0;
         for (uint64_t b = t; b < n; b += kRateAllocThreads) s += a.L[(uint64_t)choose(b, lambda) * n + b];
@@ -173,7 +188,7 @@ __global__ __launch_bounds__(kRateAllocThreads) void rate_alloc_kernel(RateAlloc
         for (uint64_t b = t; b < n; b += kRateAllocThreads) {
             uint32_t c;
             if (!shortest) c = choose(b, lambda);
-            else { c = 0; for (uint32_t k = 1; k < ncand; ++k) if (a.L[(uint64_t)k * n + b] < a.L[(uint64_t)c * n + b]) c = k; }
+            else c = rate_shortest(a.L, n, ncand, b);
             a.drop[b] = (uint8_t)c;
             s += a.L[(uint64_t)c * n + b];
         }
@@ -228,6 +243,139 @@ __global__ __launch_bounds__(kRateAllocThreads) void rate_alloc_kernel(RateAlloc
     }
 }
 
+// ---- KQ -------------------------------------------------------------------------------------------------------------------------------
+// The dual of KR2: the fewest bytes whose distortion sum of W E stays within the budget D (kernels.h has the wording).  The trim's
+// table of doubles would not fit the 64 KB of a workgroup beside the two reduction buffers at KR2's chunk: KQ takes half of it.
+constexpr uint32_t kTrimChunk = kFillChunk / 2;
+static_assert(kTrimChunk * kFillSteps * sizeof(double) + kRateAllocThreads * 16u + kTrimChunk * 2u <= 65536u, "KQ's LDS");
+
+__global__ __launch_bounds__(kRateAllocThreads) void rate_quality_kernel(RateQualityArgs a)
+{
+    __shared__ unsigned long long red_u[kRateAllocThreads];
+    __shared__ double red_d[kRateAllocThreads];
+    __shared__ double trim_delta[kTrimChunk][kFillSteps];
+    __shared__ uint8_t trim_len[kTrimChunk], trim_taken[kTrimChunk];
+    const uint32_t t = threadIdx.x;
+    const uint64_t n = a.nblocks;
+    const uint32_t ncand = a.ncand;
+    const double D = a.budget;
+
+    auto dist_of = [&](uint64_t b, uint32_t c) -> double { return a.W[b] * (double)a.E[(uint64_t)c * n + b]; };
+    auto dist_at = [&](double lambda) -> double {
+        double s = 0;
+        for (uint64_t b = t; b < n; b += kRateAllocThreads) s += dist_of(b, rate_choose(a.L, a.E, a.W, n, ncand, b, lambda));
+        return block_sum(s, red_d);
+    };
+
+    // the least distortion any choice has: below that nothing helps.  The shortest choice: the fewest bytes there are.
+    double floor_d, short_d;
+    unsigned long long short_l;
+    {
+        double f = 0, sd = 0;
+        unsigned long long sl = 0;
+        for (uint64_t b = t; b < n; b += kRateAllocThreads) {
+            unsigned long long m = a.E[b];
+            for (uint32_t c = 1; c < ncand; ++c) m = min(m, a.E[(uint64_t)c * n + b]);
+            f += a.W[b] * (double)m;
+            const uint32_t c = rate_shortest(a.L, n, ncand, b);
+            sd += dist_of(b, c);
+            sl += a.L[(uint64_t)c * n + b];
+        }
+        floor_d = block_sum(f, red_d);
+        short_d = block_sum(sd, red_d);
+        short_l = block_sum(sl, red_u);
+    }
+    const bool feasible = floor_d <= D;
+    const bool all_short = feasible && short_d <= D;          // the shortest choice is good enough: no multiplier is finite
+    double lambda = 0;
+    uint32_t steps = 0;
+    if (feasible && !all_short) {
+        // bracket within a factor of two, from 1: up while the doubled multiplier still fits, else down until one fits (200 halvings
+        // without one: 0, which fits -- its choice has the floor's distortion), then bisect.  lo always fits.
+        double lo = 1.0, hi;
+        if (dist_at(lo) <= D) {
+            while (steps < 200u && dist_at(lo * 2.0) <= D) { lo *= 2.0; ++steps; }
+            hi = lo * 2.0;
+        } else {
+            double at_lo;
+            do { lo *= 0.5; ++steps; at_lo = dist_at(lo); } while (steps < 200u && at_lo > D);
+            hi = lo * 2.0;
+            if (at_lo > D) lo = 0.0;
+        }
+        for (uint32_t k = 0; k < kRateBisectSteps; ++k, ++steps) {
+            const double mid = 0.5 * (lo + hi);
+            if (dist_at(mid) <= D) lo = mid; else hi = mid;
+        }
+        lambda = lo;
+    }
+    // the choice the trim starts from: the Lagrange choice at lambda; the shortest one; not feasible: every block at its least E
+    unsigned long long lagrange;
+    double lagrange_d;
+    {
+        unsigned long long s = 0;
+        double d = 0;
+        for (uint64_t b = t; b < n; b += kRateAllocThreads) {
+            uint32_t c;
+            if (all_short) c = rate_shortest(a.L, n, ncand, b);
+            else if (feasible) c = rate_choose(a.L, a.E, a.W, n, ncand, b, lambda);
+            else { c = 0; for (uint32_t k = 1; k < ncand; ++k) if (a.E[(uint64_t)k * n + b] < a.E[(uint64_t)c * n + b]) c = k; }
+            a.drop[b] = (uint8_t)c;
+            s += a.L[(uint64_t)c * n + b];
+            d += dist_of(b, c);
+        }
+        lagrange = block_sum(s, red_u);
+        lagrange_d = block_sum(d, red_d);
+    }
+    // the trim, in table order: a block moves to the next coarser candidate while that strictly shortens it and the distortion it
+    // adds -- which may be negative -- fits what is left; a block that does not fit is passed over and the walk goes on.  kTrimChunk
+    // blocks at a time, in the fill's three phases.
+    double left = D - lagrange_d;                                      // (thread 0's is the one that counts)
+    for (uint64_t base = 0; feasible && base < n; base += kTrimChunk) {
+        const uint64_t b = base + t;
+        uint32_t c = 0;
+        if (t < kTrimChunk && b < n) {
+            c = a.drop[b];
+            const double w = a.W[b];
+            uint32_t len = 0;
+            for (uint32_t s = 0; c + s + 1u < ncand && s < kFillSteps; ++s) {
+                const uint64_t fine = (uint64_t)(c + s) * n + b, coarse = (uint64_t)(c + s + 1u) * n + b;
+                if (!(a.L[coarse] < a.L[fine])) break;
+                trim_delta[t][s] = w * (double)((long long)a.E[coarse] - (long long)a.E[fine]);
+                ++len;
+            }
+            trim_len[t] = (uint8_t)len;
+        }
+        __syncthreads();
+        if (t == 0) {
+            const uint32_t cnt = (uint32_t)min((uint64_t)kTrimChunk, n - base);
+            for (uint32_t i = 0; i < cnt; ++i) {
+                uint32_t k = 0;
+                while (k < trim_len[i] && trim_delta[i][k] <= left) { left -= trim_delta[i][k]; ++k; }
+                trim_taken[i] = (uint8_t)k;
+            }
+        }
+        __syncthreads();
+        if (t < kTrimChunk && b < n) a.drop[b] = (uint8_t)(c + trim_taken[t]);
+        __syncthreads();
+    }
+    // the result, summed afresh over the final choice, and the candidates as the drop bytes the block coder takes
+    unsigned long long bytes = 0;
+    double dist = 0;
+    for (uint64_t b = t; b < n; b += kRateAllocThreads) {
+        const uint32_t c = a.drop[b];
+        bytes += a.L[(uint64_t)c * n + b];
+        dist += dist_of(b, c);
+        a.drop[b] = c <= a.dmax ? (uint8_t)c : (uint8_t)kHtDropSkip;
+    }
+    bytes = block_sum(bytes, red_u);
+    dist = block_sum(dist, red_d);
+    if (t == 0) {
+        a.res->block_bytes = bytes; a.res->lagrange_bytes = lagrange; a.res->shortest_bytes = short_l;
+        a.res->distortion = dist; a.res->floor = floor_d; a.res->lambda = all_short ? (double)INFINITY : lambda;
+        a.res->feasible = feasible ? 1u : 0u; a.res->steps = steps;
+    }
+}
+
 } // namespace
 
 hipError_t launch_rate_stats(const RateStatsArgs& a, hipStream_t s)
@@ -260,6 +408,15 @@ hipError_t launch_rate_alloc(const RateAllocArgs& a, hipStream_t s)
     if (!a.nblocks || a.nblocks > kRateMaxBlocks || a.dmax == 0 || a.dmax > kRateMaxDrop || a.ncand < a.dmax + 1u || a.ncand > a.dmax + 2u)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(rate_alloc_kernel, dim3(1), dim3(kRateAllocThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_rate_quality(const RateQualityArgs& a, hipStream_t s)
+{
+    if (!a.nblocks || a.nblocks > kRateMaxBlocks || a.dmax == 0 || a.dmax > kRateMaxDrop || a.ncand < a.dmax + 1u || a.ncand > a.dmax + 2u ||
+        !(a.budget >= 0.0))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rate_quality_kernel, dim3(1), dim3(kRateAllocThreads), 0, s, a);
     return hipGetLastError();
 }
 

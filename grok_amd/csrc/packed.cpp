@@ -166,6 +166,23 @@ extern "C" int64_t grk_amd_encode_packed_rate(grk_amd_ctx* c, const grk_amd_imag
     return encode_surface_rate_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, rate, out, out_cap, result);
 }
 
+extern "C" int64_t grk_amd_encode_packed_quality(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                                 uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                                 const grk_amd_quality* quality, uint8_t* out, uint64_t out_cap, grk_amd_quality_result* result)
+{
+    if (!c || !im || !base || !pixels || !out || !quality) return GRK_AMD_ERR_INVALID;
+    PackedFrame f;
+    int rc = open_encode(c, im, base, format, pitch, pixels, cap, pixels_on_device, f);
+    if (rc) return rc;
+    QualityTarget qt;          // (before any GPU work, as the surface call has it)
+    rc = quality_target(c, quality, base->prec, quality_samples(*im, base->num_comps, kDx, kDy), result, qt);
+    if (rc) return rc;
+    const PlaneSet ps(f);
+    rc = unpack_frame(c, f, ps, pixels, pixels_on_device);
+    if (rc) return rc;
+    return encode_surface_rate_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, &qt.rate, out, out_cap, nullptr, &qt.goal);
+}
+
 extern "C" int grk_amd_decode_packed(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, int format, uint64_t pitch, void* pixels, uint64_t cap,
                                      int pixels_on_device)
 {

@@ -12,6 +12,9 @@
 // order, the batches' maps and the bounds are plan_rate_joint's, encode_plan.h): each batch's KR1 and trial launches write their
 // columns through the batch's map, KR2 runs once per round over the joint tables -- one multiplier for every block of every
 // component --, and a batch is coded with its slice of the chosen drops.  The tables are made once per call.
+//
+// Quality-targeted encodes (grk_amd_encode_*_quality) take the same tables and, instead of KR2 and its rounds, run KQ once for a
+// distortion budget (plan_quality, encode_plan.h), code the batches and write the file once.
 #include "context.h"
 #include "image.h"
 
@@ -83,7 +86,7 @@ int rate_choose(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
     a.L = (const uint32_t*)c->rate_L.p; a.E = (const unsigned long long*)c->rate_E.p; a.W = (const double*)c->rate_W.p;
     a.nblocks = c->rate.nblocks; a.dmax = rp.dmax; a.ncand = rp.ncand; a.budget = budget;
     a.drop = (uint8_t*)c->rate_drop.p; a.res = (RateAllocResult*)c->rate_res.p;
-    c->rate.budget = budget;
+    c->rate.budget = budget; c->rate.qbudget = 0;
     {
         ScopedTimer t(c, 9);
         HIP_TRY(c, launch_rate_alloc(a, c->stream), "launch rate allocator");
@@ -97,6 +100,51 @@ int rate_choose(grk_amd_ctx* c, uint64_t budget, RateAllocResult& res)
         return fail(c, GRK_AMD_ERR_OVERFLOW, msg);
     }
     return GRK_AMD_OK;
+}
+
+// KQ for a distortion budget over the prepared tables: the chosen drop bytes in rate_drop.  plain_blocks: the bytes of row 0 of L.
+// A budget of 0 is answered without the allocator: nothing may be lost, so every block keeps d = 0 and the file is the plain one.
+// (KQ alone would still take a coarser candidate of EQUAL error in fewer bytes -- in the model a lone odd magnitude survives one
+// dropped plane -- which the 5/3 decoders at hand, positioning a block by its own zero bit-planes, do not return exactly.)
+// The call around it is not shortened for that budget: it still makes all Dmax + 1 trial tables, which grk_amd_rate_tables serves
+// afterwards as after any call, and codes every batch once more with drops of 0 to get the plain rows back -- work a caller who
+// wants the plain file saves by asking for it (grk_amd_encode_image and its kin).
+int quality_choose(grk_amd_ctx* c, double budget, uint64_t plain_blocks, RateQualityResult& res)
+{
+    if (!c->rate.valid) return GRK_AMD_ERR_INVALID;
+    const RatePlan& rp = c->rate.plan;
+    if (budget == 0.0) {
+        HIP_TRY(c, hipMemsetAsync(c->rate_drop.p, 0, rp.drop_bytes, c->stream), "no drops");
+        c->rate.budget = 0; c->rate.qbudget = 0;
+        res = RateQualityResult{};
+        res.block_bytes = res.lagrange_bytes = plain_blocks; res.feasible = 1;
+        return GRK_AMD_OK;
+    }
+    HIP_TRY(c, c->rate_res.ensure(sizeof(RateQualityResult)), "alloc quality result");
+    RateQualityArgs a{};
+    a.L = (const uint32_t*)c->rate_L.p; a.E = (const unsigned long long*)c->rate_E.p; a.W = (const double*)c->rate_W.p;
+    a.nblocks = c->rate.nblocks; a.dmax = rp.dmax; a.ncand = rp.ncand; a.budget = budget;
+    a.drop = (uint8_t*)c->rate_drop.p; a.res = (RateQualityResult*)c->rate_res.p;
+    c->rate.budget = 0; c->rate.qbudget = budget;
+    {
+        ScopedTimer t(c, 9);
+        HIP_TRY(c, launch_rate_quality(a, c->stream), "launch quality allocator");
+    }
+    HIP_TRY(c, hipMemcpyAsync(&res, c->rate_res.p, sizeof(res), hipMemcpyDeviceToHost, c->stream), "fetch quality result");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    // (E[0] = 0 everywhere in the tables of an encode: the floor is 0 and every D >= 0 feasible)
+    if (!res.feasible) return fail(c, GRK_AMD_ERR_OVERFLOW, "the distortion budget is below what the finest candidates leave");
+    return GRK_AMD_OK;
+}
+
+void fill_quality_result(const QualityGoal& goal, const RateQualityResult& r, uint64_t file_bytes)
+{
+    grk_amd_quality_result* out = goal.result;
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->block_bytes = r.block_bytes; out->lagrange_bytes = r.lagrange_bytes; out->file_bytes = file_bytes;
+    out->distortion = r.distortion; out->budget = goal.budget; out->psnr = quality_psnr(goal.signal, r.distortion);
+    out->lambda = r.lambda; out->steps = r.steps;
 }
 
 // ... then the blocks of the one batch the tables are over coded with the chosen drops
@@ -190,6 +238,28 @@ int grk_amd_encode_tiles_rate(grk_amd_ctx* c, const grk_amd_tile_params* p, uint
     return GRK_AMD_OK;
 }
 
+int grk_amd_encode_tiles_quality(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* pixels, int on_device,
+                                 const grk_amd_quality* quality, grk_amd_coded_block* table, uint64_t* total, grk_amd_quality_result* result)
+{
+    if (!c || !p || !pixels || !ntiles || !quality) return GRK_AMD_ERR_INVALID;
+    c->rate.valid = false;
+    QualityTarget qt;
+    int rc = quality_target(c, quality, p->prec, (uint64_t)ntiles * p->tile_w * p->tile_h * p->num_comps, result, qt); if (rc) return rc;
+    const int64_t bpt = grk_amd_tile_num_blocks(p);
+    if (bpt < 0) return (int)bpt;
+    std::vector<grk_amd_coded_block> plain((size_t)bpt * ntiles);
+    rc = rate_prepare(c, p, ntiles, pixels, on_device, &qt.rate, plain.data()); if (rc) return rc;
+    uint64_t plain_blocks = 0;
+    for (const grk_amd_coded_block& r : plain) plain_blocks += r.length;
+    RateQualityResult r{};
+    rc = quality_choose(c, qt.goal.budget, plain_blocks, r); if (rc) return rc;
+    rc = ht_encode_drops(c, ntiles, c->p1.p, c->last_h16, (const uint8_t*)c->rate_drop.p); if (rc) return rc;
+    fill_quality_result(qt.goal, r, 0);
+    if (table || total) { rc = grk_amd_fetch_table(c, table, total); if (rc) return rc; }
+    note_reversible(c, *p, r.block_bytes < plain_blocks);
+    return GRK_AMD_OK;
+}
+
 int grk_amd_rate_tables(grk_amd_ctx* c, int which, void* dst, uint64_t cap_bytes)
 {
     if (!c || !dst || !c->rate.valid) return GRK_AMD_ERR_INVALID;
@@ -257,78 +327,110 @@ int grk_amd::rate_refusal(grk_amd_ctx* ctx, const grk_amd_rate* rate)
     return GRK_AMD_OK;
 }
 
-int64_t grk_amd::encode_rate_joint(grk_amd_ctx* c, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+int grk_amd::quality_target(grk_amd_ctx* ctx, const grk_amd_quality* quality, uint32_t prec, uint64_t samples, grk_amd_quality_result* result,
+                            QualityTarget& out)
 {
-    c->rate.valid = false;
-    { const int rc = rate_refusal(c, call.rate); if (rc) return rc; }
-    const size_t nbatches = call.batches.size();
-    std::vector<std::vector<uint32_t>> members;
-    for (const RateBatch& b : call.batches) members.push_back(b.units);
-    const RateJointPlan jp = plan_rate_joint(call.rate->max_drop, call.rate->allow_skip != 0, call.unit_blocks, members);
-    if (!jp.ok) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "rate tables: more blocks than the allocator indexes");
-    const RatePlan& rp = jp.tables;
-    const uint64_t N = jp.n;
-    // the batches' maps one behind the other on the device, the largest batch's drop bytes, the tables
-    std::vector<unsigned long long> maps;
-    std::vector<size_t> map_at(nbatches);
-    uint64_t largest = 0;
-    for (size_t k = 0; k < nbatches; ++k) {
-        map_at[k] = maps.size();
-        maps.insert(maps.end(), jp.map[k].begin(), jp.map[k].end());
-        largest = std::max<uint64_t>(largest, (uint64_t)jp.per_unit[k] * jp.map[k].size());
-    }
-    HIP_TRY(c, hipSetDevice(c->device), "set device");
-    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the buffers below may still be read by an earlier call)
-    HIP_TRY(c, c->rate_L.ensure(rp.l_bytes), "alloc rate lengths");
-    HIP_TRY(c, c->rate_E.ensure(rp.e_bytes), "alloc rate errors");
-    HIP_TRY(c, c->rate_W.ensure(rp.w_bytes), "alloc rate weights");
-    HIP_TRY(c, c->rate_drop.ensure(rp.drop_bytes), "alloc drops");
-    HIP_TRY(c, c->rate_res.ensure(sizeof(RateAllocResult)), "alloc rate result");
-    HIP_TRY(c, c->rate_map.ensure(maps.size() * 8), "alloc rate maps");
-    HIP_TRY(c, c->rate_bdrop.ensure(largest), "alloc a batch's drops");
-    HIP_TRY(c, hipMemcpy(c->rate_map.p, maps.data(), maps.size() * 8, hipMemcpyHostToDevice), "upload rate maps");
-    HIP_TRY(c, hipMemsetAsync(c->rate_L.p, 0, rp.l_bytes, c->stream), "clear rate lengths");          // (the SKIP row stays 0)
-    std::vector<grk_amd_coded_block> rows(N), table;
+    ctx->rate.valid = false;          // (a refused call leaves no tables behind, as a refused rate-targeted call leaves none)
+    if (ctx->pipelining) return fail(ctx, GRK_AMD_ERR_UNSUPPORTED, "quality-targeted encodes are not pipelined (grk_amd_set_pipelining(ctx, 0))");
+    if (!plan_rate(quality->max_drop, quality->allow_skip != 0, 0).ok) return fail(ctx, GRK_AMD_ERR_INVALID, "grk_amd_quality::max_drop above 12");
+    const QualityPlan qp = plan_quality(quality->target_psnr, quality->target_distortion, prec, samples);
+    if (!qp.ok) return fail(ctx, GRK_AMD_ERR_INVALID, "grk_amd_quality: a target that is negative or not a number");
+    out.rate = grk_amd_rate{};
+    out.rate.max_drop = quality->max_drop; out.rate.allow_skip = quality->allow_skip; out.rate.joint = 1;
+    out.goal = QualityGoal{qp.budget, qp.signal, result};
+    return GRK_AMD_OK;
+}
+
+namespace {
+
+// A joint call's tables and the coding of its batches -- what a byte goal's rounds and a distortion goal's one pass share
+struct JointRun {
+    grk_amd_ctx* c;
+    const RateJointCall& call;
+    RateJointPlan jp;
+    std::vector<size_t> map_at;
+    std::vector<grk_amd_coded_block> rows, table;       // the file's rows in joint order (first: the plain encode's); a batch's
     std::vector<uint8_t> coded;
-    std::vector<double> w(N);
-    size_t resident = nbatches;                      // the batch whose planes and geometry the context holds
-    auto map_of = [&](size_t k) { return (const unsigned long long*)c->rate_map.p + map_at[k]; };
-    auto keep_rows = [&](size_t k, size_t at) {
+    size_t resident = 0;                                // the batch whose planes and geometry the context holds
+
+    const unsigned long long* map_of(size_t k) const { return (const unsigned long long*)c->rate_map.p + map_at[k]; }
+    void keep_rows(size_t k, size_t at)
+    {
         const uint64_t bpu = jp.per_unit[k];
         for (size_t i = 0; i < jp.map[k].size(); ++i)
             for (uint64_t b = 0; b < bpu; ++b) { rows[jp.map[k][i] + b] = table[i * bpu + b]; rows[jp.map[k][i] + b].offset += at; }
-    };
-    // ---- the tables, batch by batch: the plain rows, the weights, KR1 and the trial launches through the batch's map
-    for (size_t k = 0; k < nbatches; ++k) {
-        const uint32_t bpu = jp.per_unit[k], nunits = (uint32_t)jp.map[k].size();
-        const uint64_t n = (uint64_t)bpu * nunits;
-        table.resize(n);
-        uint64_t total = 0;
-        // (synchronous, with the arena / range flags checked: the trial launches below code from the planes this leaves)
-        int rc = call.front(k, table.data(), &total); if (rc) return rc;
-        resident = k;
-        const TileGeom& g = c->geom;
-        if (c->last_nblocks != n) return fail(c, GRK_AMD_ERR_INVALID, "rate tables: a batch's blocks are not its units'");
-        keep_rows(k, 0);
-        // W_b = (w_mct * w_band * stepsize)^2 / 4 of the unit's own geometry: E counts half steps
-        for (uint32_t i = 0; i < bpu; ++i) {
-            const double v = block_weight(g, i);
-            for (uint64_t at : jp.map[k]) w[at + i] = v * v * 0.25;
-        }
-        rc = batch_tables(c, rp, nunits, map_of(k), N, c->rate_bdrop.p); if (rc) return rc;
     }
-    HIP_TRY(c, hipMemcpyAsync(c->rate_W.p, w.data(), N * 8, hipMemcpyHostToDevice, c->stream), "upload rate weights");
-    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-    c->rate.valid = true; c->rate.plan = rp; c->rate.nblocks = N; c->rate.ntiles = 0; c->rate.unit_rows = jp.first_row;
-    // ---- a round: KR2 over the joint tables, then every batch -- its front end again where another batch has taken the context
-    //      since -- coded with its slice of the drops
-    auto round = [&](uint64_t budget, RateAllocResult& sum) -> int {
-        int rc = rate_choose(c, budget, sum); if (rc) return rc;
-        coded.clear();
+
+    // the tables L, E, W over all units, made once: batch by batch the plain rows, the weights, KR1 and the trial launches through
+    // the batch's map
+    int tables()
+    {
+        c->rate.valid = false;
+        { const int rc = rate_refusal(c, call.rate); if (rc) return rc; }
+        const size_t nbatches = call.batches.size();
+        std::vector<std::vector<uint32_t>> members;
+        for (const RateBatch& b : call.batches) members.push_back(b.units);
+        jp = plan_rate_joint(call.rate->max_drop, call.rate->allow_skip != 0, call.unit_blocks, members);
+        if (!jp.ok) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "rate tables: more blocks than the allocator indexes");
+        const RatePlan& rp = jp.tables;
+        const uint64_t N = jp.n;
+        // the batches' maps one behind the other on the device, the largest batch's drop bytes, the tables
+        std::vector<unsigned long long> maps;
+        map_at.resize(nbatches);
+        uint64_t largest = 0;
+        for (size_t k = 0; k < nbatches; ++k) {
+            map_at[k] = maps.size();
+            maps.insert(maps.end(), jp.map[k].begin(), jp.map[k].end());
+            largest = std::max<uint64_t>(largest, (uint64_t)jp.per_unit[k] * jp.map[k].size());
+        }
+        HIP_TRY(c, hipSetDevice(c->device), "set device");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the buffers below may still be read by an earlier call)
+        HIP_TRY(c, c->rate_L.ensure(rp.l_bytes), "alloc rate lengths");
+        HIP_TRY(c, c->rate_E.ensure(rp.e_bytes), "alloc rate errors");
+        HIP_TRY(c, c->rate_W.ensure(rp.w_bytes), "alloc rate weights");
+        HIP_TRY(c, c->rate_drop.ensure(rp.drop_bytes), "alloc drops");
+        HIP_TRY(c, c->rate_res.ensure(sizeof(RateAllocResult)), "alloc rate result");
+        HIP_TRY(c, c->rate_map.ensure(maps.size() * 8), "alloc rate maps");
+        HIP_TRY(c, c->rate_bdrop.ensure(largest), "alloc a batch's drops");
+        HIP_TRY(c, hipMemcpy(c->rate_map.p, maps.data(), maps.size() * 8, hipMemcpyHostToDevice), "upload rate maps");
+        HIP_TRY(c, hipMemsetAsync(c->rate_L.p, 0, rp.l_bytes, c->stream), "clear rate lengths");          // (the SKIP row stays 0)
+        rows.resize(N);
+        std::vector<double> w(N);
+        resident = nbatches;
         for (size_t k = 0; k < nbatches; ++k) {
             const uint32_t bpu = jp.per_unit[k], nunits = (uint32_t)jp.map[k].size();
             const uint64_t n = (uint64_t)bpu * nunits;
+            table.resize(n);
             uint64_t total = 0;
+            // (synchronous, with the arena / range flags checked: the trial launches below code from the planes this leaves)
+            int rc = call.front(k, table.data(), &total); if (rc) return rc;
+            resident = k;
+            const TileGeom& g = c->geom;
+            if (c->last_nblocks != n) return fail(c, GRK_AMD_ERR_INVALID, "rate tables: a batch's blocks are not its units'");
+            keep_rows(k, 0);
+            // W_b = (w_mct * w_band * stepsize)^2 / 4 of the unit's own geometry: E counts half steps
+            for (uint32_t i = 0; i < bpu; ++i) {
+                const double v = block_weight(g, i);
+                for (uint64_t at : jp.map[k]) w[at + i] = v * v * 0.25;
+            }
+            rc = batch_tables(c, rp, nunits, map_of(k), N, c->rate_bdrop.p); if (rc) return rc;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->rate_W.p, w.data(), N * 8, hipMemcpyHostToDevice, c->stream), "upload rate weights");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+        c->rate.valid = true; c->rate.plan = rp; c->rate.nblocks = N; c->rate.ntiles = 0; c->rate.unit_rows = jp.first_row;
+        return GRK_AMD_OK;
+    }
+
+    // every batch -- its front end again where another batch has taken the context since -- coded with its slice of the chosen
+    // drops: `rows` and `coded` as the file's writer takes them
+    int code()
+    {
+        coded.clear();
+        for (size_t k = 0; k < call.batches.size(); ++k) {
+            const uint32_t bpu = jp.per_unit[k], nunits = (uint32_t)jp.map[k].size();
+            const uint64_t n = (uint64_t)bpu * nunits;
+            uint64_t total = 0;
+            int rc;
             if (resident != k) { rc = call.front(k, nullptr, &total); if (rc) return rc; resident = k; }
             const RateMapArgs ma{c->rate_bdrop.p, c->rate_drop.p, map_of(k), bpu, n, 1u, 1};
             HIP_TRY(c, launch_rate_map(ma, c->stream), "gather the batch's drops");
@@ -341,15 +443,41 @@ int64_t grk_amd::encode_rate_joint(grk_amd_ctx* c, const RateJointCall& call, ui
             keep_rows(k, at);
         }
         return GRK_AMD_OK;
+    }
+};
+
+} // namespace
+
+int64_t grk_amd::encode_rate_joint(grk_amd_ctx* c, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
+    JointRun run{c, call};
+    { const int rc = run.tables(); if (rc) return rc; }
+    if (call.quality) {
+        // a distortion budget: KQ once, the batches coded, the file written once
+        uint64_t plain_blocks = 0;
+        for (const grk_amd_coded_block& r : run.rows) plain_blocks += r.length;
+        RateQualityResult r{};
+        int rc = quality_choose(c, call.quality->budget, plain_blocks, r); if (rc) return rc;
+        rc = run.code(); if (rc) return rc;
+        run.coded.push_back(0);                     // (the writer wants a buffer even when every block was skipped)
+        const int64_t wrote = call.write(run.rows.data(), run.coded.data(), out, cap);
+        if (wrote >= 0) { fill_quality_result(*call.quality, r, (uint64_t)wrote); note_reversible(c, *call.base, r.block_bytes < plain_blocks); }
+        return wrote;
+    }
+    // ---- a round: KR2 over the joint tables, then every batch coded with its slice of the drops
+    auto round = [&](uint64_t budget, RateAllocResult& sum) -> int {
+        const int rc = rate_choose(c, budget, sum); if (rc) return rc;
+        return run.code();
     };
-    return rate_rounds(c, *call.base, call.rate->target_bytes, rows, coded, round,
-                       [&](uint8_t* o, uint64_t ocap) { return call.write(rows.data(), coded.data(), o, ocap); }, out, cap, result);
+    return rate_rounds(c, *call.base, call.rate->target_bytes, run.rows, run.coded, round,
+                       [&](uint8_t* o, uint64_t ocap) { return call.write(run.rows.data(), run.coded.data(), o, ocap); }, out, cap, result);
 }
 
 extern "C" {
 
 uint64_t grk_amd_rate_num_blocks(grk_amd_ctx* c) { return c && c->rate.valid ? c->rate.nblocks : 0; }
 uint64_t grk_amd_rate_last_budget(grk_amd_ctx* c) { return c && c->rate.valid ? c->rate.budget : 0; }
+double grk_amd_quality_last_budget(grk_amd_ctx* c) { return c && c->rate.valid ? c->rate.qbudget : 0.0; }
 
 int grk_amd_rate_unit_rows(grk_amd_ctx* c, uint64_t* first_row, uint32_t cap)
 {
@@ -431,10 +559,10 @@ int grk_amd_stage_rate_alloc(grk_amd_ctx* c, const uint32_t* L, const uint64_t* 
     return GRK_AMD_OK;
 }
 
-int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels,
-                                  uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+// grk_amd_encode_image_rate, and -- quality != nullptr: always over joint tables -- grk_amd_encode_image_quality
+static int64_t image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels, uint32_t flags,
+                          const grk_amd_rate* rate, const QualityGoal* quality, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
 {
-    if (!ctx || !im || !base || !pixels || !out || !rate) return GRK_AMD_ERR_INVALID;
     if (ctx->pipelining) return fail(ctx, GRK_AMD_ERR_UNSUPPORTED, "rate-targeted encodes are not pipelined (grk_amd_set_pipelining(ctx, 0))");
     flags |= GRK_AMD_CS_BLOCK_MSBS;
     std::vector<Unit> tiles;
@@ -455,8 +583,8 @@ int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* 
         staging.resize(staged_bytes(src, tiles[G[0]]) * G.size());
         stage_units(src, tiles, G, staging.data(), 1);
     };
-    if (rate->joint) {
-        RateJointCall call{base, rate, {}, {}, {}, {}};
+    if (rate->joint || quality) {
+        RateJointCall call{base, rate, {}, {}, {}, {}, quality};
         for (size_t u = 0; u < tiles.size(); ++u) call.unit_blocks.push_back((uint64_t)g.geoms[g.of[u]].blocks_per_comp * tiles[u].p.num_comps);
         for (size_t k = 0; k < ngroups; ++k) call.batches.push_back(RateBatch{tiles[g.members[k][0]].p, g.members[k]});
         call.front = [&](size_t k, grk_amd_coded_block* table, uint64_t* total) -> int {
@@ -521,11 +649,63 @@ int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* 
     }, out, cap, result);
 }
 
-int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
-                                             const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
-                                             const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+// KQ on tables of the caller's choosing: grk_amd_stage_rate_alloc's rules and buffers
+int grk_amd_stage_quality_alloc(grk_amd_ctx* c, const uint32_t* L, const uint64_t* E, const double* W, uint64_t n, uint32_t max_drop, int allow_skip,
+                                double D, uint8_t* drops, grk_amd_quality_alloc_result* result)
 {
-    if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy || !rate) return GRK_AMD_ERR_INVALID;
+    static_assert(sizeof(grk_amd_quality_alloc_result) == sizeof(RateQualityResult) && offsetof(grk_amd_quality_alloc_result, steps) == offsetof(RateQualityResult, steps) &&
+                  offsetof(grk_amd_quality_alloc_result, floor) == offsetof(RateQualityResult, floor), "grk_amd_quality_alloc_result is RateQualityResult");
+    if (!c) return GRK_AMD_ERR_INVALID;
+    if (!L || !E || !W || !drops || !result) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_quality_alloc: a null pointer");
+    if (max_drop == 0 || max_drop > kRateMaxDrop) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_quality_alloc: max_drop is 1 .. 12");
+    if (!n || n > kRateMaxBlocks) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_quality_alloc: no block, or more than the allocator indexes");
+    if (!(D >= 0.0)) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_quality_alloc: a distortion budget that is negative or not a number");
+    const uint64_t rows = max_drop + 2u;
+    for (uint64_t i = 0; i < rows * n; ++i)
+        if (L[i] >> 31) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_quality_alloc: a length of 2^31 bytes or more");
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    HIP_TRY(c, c->st_rL.ensure(rows * n * 4u), "alloc the stage's lengths");
+    HIP_TRY(c, c->st_rE.ensure(rows * n * 8u), "alloc the stage's errors");
+    HIP_TRY(c, c->st_rW.ensure(n * 8u), "alloc the stage's weights");
+    HIP_TRY(c, c->st_rdrop.ensure(n), "alloc the stage's drops");
+    HIP_TRY(c, c->st_rres.ensure(sizeof(RateQualityResult)), "alloc the stage's result");
+    HIP_TRY(c, hipMemcpyAsync(c->st_rL.p, L, rows * n * 4u, hipMemcpyHostToDevice, c->stream), "upload lengths");
+    HIP_TRY(c, hipMemcpyAsync(c->st_rE.p, E, rows * n * 8u, hipMemcpyHostToDevice, c->stream), "upload errors");
+    HIP_TRY(c, hipMemcpyAsync(c->st_rW.p, W, n * 8u, hipMemcpyHostToDevice, c->stream), "upload weights");
+    HIP_TRY(c, hipMemsetAsync(c->st_rres.p, 0, sizeof(RateQualityResult), c->stream), "clear the result");
+    RateQualityArgs a{};
+    a.L = (const uint32_t*)c->st_rL.p; a.E = (const unsigned long long*)c->st_rE.p; a.W = (const double*)c->st_rW.p;
+    a.nblocks = n; a.dmax = max_drop; a.ncand = max_drop + 1u + (allow_skip ? 1u : 0u); a.budget = D;
+    a.drop = (uint8_t*)c->st_rdrop.p; a.res = (RateQualityResult*)c->st_rres.p;
+    HIP_TRY(c, launch_rate_quality(a, c->stream), "launch quality allocator");
+    HIP_TRY(c, hipMemcpyAsync(result, c->st_rres.p, sizeof(RateQualityResult), hipMemcpyDeviceToHost, c->stream), "fetch quality result");
+    HIP_TRY(c, hipMemcpyAsync(drops, c->st_rdrop.p, n, hipMemcpyDeviceToHost, c->stream), "fetch drops");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    return GRK_AMD_OK;
+}
+
+int64_t grk_amd_encode_image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels,
+                                  uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
+    if (!ctx || !im || !base || !pixels || !out || !rate) return GRK_AMD_ERR_INVALID;
+    return image_rate(ctx, im, base, pixels, flags, rate, nullptr, out, cap, result);
+}
+
+int64_t grk_amd_encode_image_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const void* pixels,
+                                     uint32_t flags, const grk_amd_quality* quality, uint8_t* out, uint64_t cap, grk_amd_quality_result* result)
+{
+    if (!ctx || !im || !base || !pixels || !out || !quality) return GRK_AMD_ERR_INVALID;
+    QualityTarget qt;
+    const int rc = quality_target(ctx, quality, base->prec, quality_samples(*im, base->num_comps, nullptr, nullptr), result, qt);
+    if (rc) return rc;
+    return image_rate(ctx, im, base, pixels, flags, &qt.rate, &qt.goal, out, cap, nullptr);
+}
+
+// grk_amd_encode_image_subsampled_rate and, with quality != nullptr, grk_amd_encode_image_subsampled_quality
+static int64_t subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
+                               const uint8_t* comp_dy, const void* pixels, uint32_t flags, const grk_amd_rate* rate, const QualityGoal* quality,
+                               uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
     { const int rr = rate_refusal(ctx, rate); if (rr) return rr; }
     flags |= GRK_AMD_CS_BLOCK_MSBS;
     std::vector<Unit> units;
@@ -534,7 +714,7 @@ int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_ima
     const int rc = subsampled_image(ctx, im, base, comp_dx, comp_dy, pixels, units, src, g);
     if (rc) return rc;
     std::vector<uint8_t> staging;
-    RateJointCall call{base, rate, {}, {}, {}, {}};
+    RateJointCall call{base, rate, {}, {}, {}, {}, quality};
     for (size_t u = 0; u < units.size(); ++u) call.unit_blocks.push_back((uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].p.num_comps);
     for (size_t k = 0; k < g.members.size(); ++k) call.batches.push_back(RateBatch{units[g.members[k][0]].p, g.members[k]});
     call.front = [&](size_t k, grk_amd_coded_block* table, uint64_t* total) -> int {
@@ -547,6 +727,25 @@ int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_ima
         return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows, coded, flags, o, ocap);
     };
     return encode_rate_joint(ctx, call, out, cap, result);
+}
+
+int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                             const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
+                                             const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
+{
+    if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy || !rate) return GRK_AMD_ERR_INVALID;
+    return subsampled_rate(ctx, im, base, comp_dx, comp_dy, pixels, flags, rate, nullptr, out, cap, result);
+}
+
+int64_t grk_amd_encode_image_subsampled_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
+                                                const grk_amd_quality* quality, uint8_t* out, uint64_t cap, grk_amd_quality_result* result)
+{
+    if (!ctx || !im || !base || !pixels || !out || !comp_dx || !comp_dy || !quality) return GRK_AMD_ERR_INVALID;
+    QualityTarget qt;
+    const int rc = quality_target(ctx, quality, base->prec, quality_samples(*im, base->num_comps, comp_dx, comp_dy), result, qt);
+    if (rc) return rc;
+    return subsampled_rate(ctx, im, base, comp_dx, comp_dy, pixels, flags, &qt.rate, &qt.goal, out, cap, nullptr);
 }
 
 } // extern "C"

@@ -257,10 +257,11 @@ extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_la
     return encode_surface_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, out, out_cap);
 }
 
-// the same for grk_amd_encode_surface_rate and grk_amd_encode_packed_rate
+// the same for grk_amd_encode_surface_rate and grk_amd_encode_packed_rate -- and, with a quality goal (image.h), their _quality twins
 int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                                 const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
-                                uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result)
+                                uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result,
+                                const QualityGoal* quality)
 {
     { const int rr = rate_refusal(c, rate); if (rr) return rr; }
     flags |= GRK_AMD_CS_BLOCK_MSBS;
@@ -268,7 +269,7 @@ int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, 
     const int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);
     if (rc) return rc;
     KeepLayout keep{c->enc_layout, c->enc_layout};
-    RateJointCall call{base, rate, {}, {}, {}, {}};
+    RateJointCall call{base, rate, {}, {}, {}, {}, quality};
     for (size_t u = 0; u < job.units.size(); ++u) call.unit_blocks.push_back(job.row_at[u + 1] - job.row_at[u]);
     for (const SurfaceBatch& B : job.batches) call.batches.push_back(RateBatch{B.p, B.units});
     call.front = [&](size_t b, grk_amd_coded_block* table, uint64_t* total) { return job.front(b, table, total); };
@@ -285,4 +286,16 @@ extern "C" int64_t grk_amd_encode_surface_rate(grk_amd_ctx* c, const grk_amd_ima
 {
     if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out || !rate) return GRK_AMD_ERR_INVALID;
     return encode_surface_rate_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, rate, out, out_cap, result);
+}
+
+extern "C" int64_t grk_amd_encode_surface_quality(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                  const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                                  const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                                  const grk_amd_quality* quality, uint8_t* out, uint64_t out_cap, grk_amd_quality_result* result)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !out || !quality) return GRK_AMD_ERR_INVALID;
+    QualityTarget qt;
+    const int rc = quality_target(c, quality, base->prec, quality_samples(*im, base->num_comps, comp_dx, comp_dy), result, qt);
+    if (rc) return rc;
+    return encode_surface_rate_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, &qt.rate, out, out_cap, nullptr, &qt.goal);
 }

@@ -456,7 +456,7 @@ int grk_amd_stage_egress(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_
  * which: 0 ingest+mct, 1 dwt (all levels), 2 ht encode kernel (launches on the context's stream), 3 whole
  *        encode_tiles call, 4 ht encode kernel, top resolution (side stream, beside DWT levels >= 1),
  *        5 ht decode, 6 inverse dwt (all levels), 7 egress, 8 ht encode kernel, large-LDS classes (second side stream),
- *        9 the allocator of a rate-targeted encode (whose trial and final block-coder launches count under 2).
+ *        9 the allocator of a rate- or quality-targeted encode (whose trial and final block-coder launches count under 2).
  * One encode runs the ht encode kernel up to three times (2, 4, 8): its time per step is their sum.
  * Pipelined encodes of small frames (a frame's whole chain on one of the side streams, GRK_AMD_FRAME_STREAMS): families 1, 2 and 3
  * are then measured on that stream -- the stream that carries the call -- and 4 / 8 stay empty. */
@@ -655,6 +655,89 @@ uint64_t grk_amd_rate_num_blocks(grk_amd_ctx* ctx);
 uint64_t grk_amd_rate_last_budget(grk_amd_ctx* ctx);
 int grk_amd_rate_unit_rows(grk_amd_ctx* ctx, uint64_t* first_row, uint32_t cap);
 
+/* ---- quality-targeted encodes: the fewest bytes for a PSNR ---------------------------------------------------------------------
+ * The other half of rate control: the smallest frame that is at least this good (grk_compress -q).  The tables L, E, W, their joint
+ * order, the block coder's drop instances, the host writer with GRK_AMD_CS_BLOCK_MSBS and the readers are those of the rate-targeted
+ * encodes above; the allocator is KQ, their allocator's dual, and it runs ONCE per call: headers do not enter a distortion budget, so
+ * there are no rounds, and the file is written once.
+ * THE BUDGET: D = S * peak^2 * 10^(-target_psnr / 10), peak = 2^prec - 1, S the sum over the components of the component's OWN
+ * samples in the image area (a sub-sampled component counts its own samples, with no area factor: the convention W and `distortion`
+ * follow; grk_amd_encode_tiles_quality: num_tiles * tile_w * tile_h * num_comps).  target_psnr = +infinity: D = 0.  target_psnr == 0:
+ * D = target_distortion, in the units of grk_amd_rate_result::distortion.
+ * THE ALLOCATOR (one workgroup, fixed-order sums: runs are reproducible), over candidates c = 0 .. Dmax and, with allow_skip, SKIP:
+ *   floor = sum over b of W_b * min_c E[c][b]; feasible = floor <= D.  Not feasible: every block goes to its least-E candidate, the
+ *   finer of equal ones, with no search and no trim (the tables of an encode have E[0] = 0 everywhere: floor = 0, always feasible).
+ *   dist_at(lambda) = sum of W_b * E[choose(b, lambda)][b] with choose(b, lambda) = argmin_c W_b E[c][b] + lambda L[c][b], the finer
+ *   candidate on a tie; in exact arithmetic it does not fall as lambda rises.
+ *   The shortest choice -- the smallest L per block, the finer of equally short ones --, if its distortion is <= D, is the answer;
+ *   lambda is then reported as +infinity and steps as 0.
+ *   Otherwise the search mirrors the rate allocator's, with the same limits: from 1, doubling while the doubled multiplier still fits
+ *   (dist_at <= D) or halving until one fits, at most 200 steps; then 40 bisections that keep the LOWER end fitting; lambda = lo.
+ *   Halving that never fits ends at lo = 0, which fits when feasible.  The Lagrange choice at lambda gives lagrange_bytes.
+ *   The trim, the fill's mirror image, in table order: a block moves to the next coarser candidate (c + 1 within the candidates) while
+ *   L strictly falls and delta = W_b * (E[c + 1][b] - E[c][b]) is <= left; then left -= delta.  left starts as D - the Lagrange
+ *   choice's distortion.  A block that does not fit is passed over and the walk goes on.
+ *   `distortion` is summed afresh over the final choice.
+ * D = 0 gives d = 0 everywhere, whatever the tiling: the file is byte for byte that of grk_amd_encode_image (_subsampled, _surface,
+ * _packed) under GRK_AMD_IMAGE_T2=host.  The encode calls answer it without the allocator (lambda and steps are reported as 0):
+ * nothing may be lost.  The allocator alone -- grk_amd_stage_quality_alloc, and every D > 0 -- does take a coarser candidate of EQUAL
+ * error in fewer bytes where a table has one (a block of a few samples: in the model a lone odd magnitude survives one dropped plane).
+ * WHAT THE MODEL IS: E measures the planes dropped from the magnitudes a plain encode codes, at the bin centres a decoder that
+ * positions a block by the band's Kmax returns.  NOT in `distortion`, `budget` or `psnr`: the 9/7 base quantiser's own error; the
+ * transform's departure from orthogonality (W_b weighs a band's error by its synthesis gain as if the bands' errors did not
+ * interact, and the clamp of the decoded samples to their range is not modelled); for 5/3, what a block-positioning dequantiser
+ * returns (mu >> d, see WHICH DECODERS DO above: a successful 5/3 call that dropped anything leaves the same note in
+ * grk_amd_last_error).  The PSNR of decoded pixels therefore differs from `psnr`, and not by little: measured on an MI355X
+ * (profiles/quality.txt; 9/7, 8-bit synthetic content, Dmax 6 + SKIP) the decoded pixels were 0.8 to 6.5 dB BETTER than targets of 30
+ * to 45 dB -- the call is conservative there: it spends more bytes than the decoded PSNR would need -- and 1.3 to 2.3 dB WORSE than
+ * a target of 50 dB, where the plain 9/7 file itself decodes at 50.1 dB: a target near or above the plain file's own PSNR cannot be
+ * delivered.  Nothing here promises the gap.
+ *   grk_amd_encode_tiles_quality               one budget over a batch of same-geometry tiles; rows as grk_amd_encode_tiles_rate's
+ *   grk_amd_encode_image_quality               a whole image, always over joint tables, through the host writer with
+ *                                              GRK_AMD_CS_BLOCK_MSBS
+ *   grk_amd_encode_image_subsampled_quality, grk_amd_encode_surface_quality, grk_amd_encode_packed_quality
+ *                                              the same for the inputs of their rate-targeted twins; the packed call's file is the
+ *                                              surface call's for the same samples
+ *   grk_amd_rate_tables, grk_amd_rate_num_blocks, grk_amd_rate_unit_rows
+ *                                              serve the latest call of either kind; grk_amd_rate_last_budget is 0 after a quality
+ *                                              call, grk_amd_quality_last_budget the D the quality allocator last ran with (0 after
+ *                                              a rate-targeted call)
+ * GRK_AMD_ERR_INVALID: a negative or NaN target_psnr, a negative or NaN target_distortion where it is used, max_drop above 12.
+ * GRK_AMD_ERR_UNSUPPORTED: while pipelining is on.  Not offered: what the rate-targeted encodes do not offer. */
+typedef struct grk_amd_quality {
+    double  target_psnr;        /* dB over all samples of all components; > 0: used; +inf: D = 0 */
+    double  target_distortion;  /* used when target_psnr == 0: D in the units of grk_amd_rate_result::distortion, >= 0 */
+    uint8_t max_drop, allow_skip, reserved[6];    /* max_drop: Dmax, 0 = default 6, at most 12 */
+} grk_amd_quality;
+typedef struct grk_amd_quality_result {
+    uint64_t block_bytes, lagrange_bytes, file_bytes;     /* the final choice's bytes; the Lagrange choice's, before the trim; the file's (0: tiles) */
+    double   distortion, budget, psnr /* model: 10 log10(S peak^2 / distortion), +inf for 0 */, lambda;
+    uint32_t steps, reserved;
+} grk_amd_quality_result;
+int grk_amd_encode_tiles_quality(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const void* pixels,
+                                 int pixels_on_device, const grk_amd_quality* quality, grk_amd_coded_block* table, uint64_t* total_bytes,
+                                 grk_amd_quality_result* result);
+int64_t grk_amd_encode_image_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                     const void* pixels, uint32_t flags, const grk_amd_quality* quality, uint8_t* out, uint64_t cap,
+                                     grk_amd_quality_result* result);
+double grk_amd_quality_last_budget(grk_amd_ctx* ctx);
+/* KQ on tables of the caller's choosing, under grk_amd_stage_rate_alloc's rules: HOST pointers, rows = max_drop + 2, everything checked
+ * before a launch (GRK_AMD_ERR_INVALID: max_drop 0 or above 12, n 0, a null pointer, an entry of L of 2^31 or more, a D that is
+ * negative or NaN), buffers of its own, synchronous; the tables of the latest rate- or quality-targeted call stay valid.  A D below
+ * `floor` is no error: feasible = 0 and the drops are those of the least-E choice. */
+typedef struct grk_amd_quality_alloc_result {
+    uint64_t block_bytes;    /* the final choice's bytes */
+    uint64_t lagrange_bytes; /* ... the Lagrange choice's, before the trim (the shortest or the least-E choice's where no multiplier was used) */
+    uint64_t shortest_bytes; /* the fewest bytes any choice takes */
+    double   distortion;     /* sum of W_b E over the final choice, summed afresh */
+    double   floor;          /* sum of W_b min_c E: the least distortion any choice has */
+    double   lambda;         /* the multiplier; +infinity: the shortest choice fits; 0: only the least-E choice fits, or not feasible */
+    uint32_t feasible;       /* floor <= D */
+    uint32_t steps;          /* evaluations of the multiplier search: bracketing (at most 200) + 40 bisections; 0: no search */
+} grk_amd_quality_alloc_result;
+int grk_amd_stage_quality_alloc(grk_amd_ctx* ctx, const uint32_t* L, const uint64_t* E, const double* W, uint64_t n, uint32_t max_drop,
+                                int allow_skip, double D, uint8_t* drops, grk_amd_quality_alloc_result* result);
+
 /* ---- sub-sampled components (4:2:2, 4:2:0 ...; SIZ XRsiz / YRsiz, grok.h grk_image_comp::dx / dy) ------------------------------------
  * Component c of a tile [x0, x1) x [y0, y1) of the reference grid covers [ceil(x0 / dx_c), ceil(x1 / dx_c)) x [ceil(y0 / dy_c),
  * ceil(y1 / dy_c)) of its own samples (tile/TileProcessor.cpp:605-612): grk_amd_layout_tile_comp gives *base with that rectangle.
@@ -680,6 +763,10 @@ int64_t grk_amd_encode_image_subsampled(grk_amd_ctx* ctx, const grk_amd_image_la
 int64_t grk_amd_encode_image_subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
                                              const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
                                              const grk_amd_rate* rate, uint8_t* out, uint64_t cap, grk_amd_rate_result* result);
+/* ... in the fewest bytes the quality allocator finds for quality->target_psnr (quality-targeted encodes, above) */
+int64_t grk_amd_encode_image_subsampled_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                const uint8_t* comp_dx, const uint8_t* comp_dy, const void* pixels, uint32_t flags,
+                                                const grk_amd_quality* quality, uint8_t* out, uint64_t cap, grk_amd_quality_result* result);
 
 /* The same with the optional pointer marker segments of the reference's encoder (grk_compress -L / -X, grok.h
  * grk_cparameters::writePLT / writeTLM; codestream/markers/LengthMarkers.cpp): TLM in the main header (one-byte tile index +
@@ -973,6 +1060,12 @@ int64_t grk_amd_encode_surface_rate(grk_amd_ctx* ctx, const grk_amd_image_layout
                                     const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
                                     const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_rate* rate,
                                     uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);
+/* ... for quality->target_psnr (quality-targeted encodes, above): the file equals grk_amd_encode_image_subsampled_quality's for the
+ * same samples as tight planes */
+int64_t grk_amd_encode_surface_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                       const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                       const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_quality* quality,
+                                       uint8_t* out, uint64_t out_cap, grk_amd_quality_result* result);
 /* Codestream -> surface: component c's samples on the surface are plane c of grk_amd_decode_image, every component at its own size
  * (no view, no upsampling: the context's pixel layouts and grk_amd_set_decode_upsample are neither consulted nor changed), and every
  * byte of [pixels, pixels + cap) that is no sample of a component keeps its value (a host surface travels both ways for that).  A
@@ -1038,6 +1131,10 @@ int64_t grk_amd_encode_packed_device(grk_amd_ctx* ctx, const grk_amd_image_layou
 int64_t grk_amd_encode_packed_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
                                    const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_rate* rate,
                                    uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result);
+/* ... for quality->target_psnr: exactly grk_amd_encode_surface_quality's file for the same samples */
+int64_t grk_amd_encode_packed_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
+                                      const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_quality* quality,
+                                      uint8_t* out, uint64_t out_cap, grk_amd_quality_result* result);
 /* Codestream -> packed frame: component c of the frame is plane c of grk_amd_decode_image, written by the rules above.  A host
  * frame is uploaded, packed into and downloaded (what is no sample stays); the call is synchronous and repeats a group that leaves
  * the int16 planes by itself, as grk_amd_decode_surface does.  A device frame: the pack kernel is queued on the context's stream

@@ -1140,12 +1140,8 @@ class Context:
             raise StageError("stage_rate_stats", rc, self._L.grk_amd_last_error(self._h).decode())
         return out
 
-    def stage_rate_alloc(self, L, E, W, max_drop, allow_skip, budget):
-        """The allocator kernel on tables of the caller's (grk_amd_stage_rate_alloc): L uint32 and E uint64 [max_drop + 2, n], W
-        float64 [n] -> (drop bytes uint8 [n], RateAllocResult).  None for a table passes a null pointer.  StageError when the call
-        refuses."""
-        self._L.grk_amd_stage_rate_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64,
-                                                     C.c_void_p, C.c_void_p]
+    def _stage_alloc(self, name, L, E, W, max_drop, allow_skip, budget, res):
+        """stage_rate_alloc and stage_quality_alloc: grk_amd_<name> with `budget` as the call takes it -> (drop bytes, res filled in)"""
         Lc = None if L is None else np.ascontiguousarray(L, np.uint32)
         Ec = None if E is None else np.ascontiguousarray(E, np.uint64)
         Wc = None if W is None else np.ascontiguousarray(W, np.float64)
@@ -1153,15 +1149,23 @@ class Context:
         rows = int(max_drop) + 2
         for a in (Lc, Ec):
             if a is not None and a.size != rows * n:
-                raise ValueError("stage_rate_alloc: a table of %d entries, not (max_drop + 2) x %d" % (a.size, n))
+                raise ValueError("%s: a table of %d entries, not (max_drop + 2) x %d" % (name, a.size, n))
         if Wc is not None and Wc.size != n:
-            raise ValueError("stage_rate_alloc: %d weights for %d blocks" % (Wc.size, n))
-        drops, res = np.zeros(max(n, 1), np.uint8), RateAllocResult()
-        rc = self._L.grk_amd_stage_rate_alloc(self._h, *(a.ctypes.data if a is not None else None for a in (Lc, Ec, Wc)), n,
-                                              int(max_drop), int(bool(allow_skip)), int(budget), drops.ctypes.data, C.addressof(res))
+            raise ValueError("%s: %d weights for %d blocks" % (name, Wc.size, n))
+        drops = np.zeros(max(n, 1), np.uint8)
+        rc = getattr(self._L, "grk_amd_" + name)(self._h, *(a.ctypes.data if a is not None else None for a in (Lc, Ec, Wc)), n,
+                                                 int(max_drop), int(bool(allow_skip)), budget, drops.ctypes.data, C.addressof(res))
         if rc:
-            raise StageError("stage_rate_alloc", rc, self._L.grk_amd_last_error(self._h).decode())
+            raise StageError(name, rc, self._L.grk_amd_last_error(self._h).decode())
         return drops[:n], res
+
+    def stage_rate_alloc(self, L, E, W, max_drop, allow_skip, budget):
+        """The allocator kernel on tables of the caller's (grk_amd_stage_rate_alloc): L uint32 and E uint64 [max_drop + 2, n], W
+        float64 [n] -> (drop bytes uint8 [n], RateAllocResult).  None for a table passes a null pointer.  StageError when the call
+        refuses."""
+        self._L.grk_amd_stage_rate_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64,
+                                                     C.c_void_p, C.c_void_p]
+        return self._stage_alloc("stage_rate_alloc", L, E, W, max_drop, allow_skip, int(budget), RateAllocResult())
 
     def encode_tiles_rate(self, params, ntiles, pixels_ptr, on_device, target_bytes, max_drop=0, allow_skip=False):
         """grk_amd_encode_tiles_rate: the batch's blocks in at most target_bytes -> (table, total arena bytes, RateResult)"""
@@ -1207,18 +1211,12 @@ class Context:
         """grk_amd_encode_surface_rate: encode_surface in a file of at most target_bytes -> (codestream bytes, RateResult).  pixels: a
         uint8 numpy array holding the surface (host), or a device pointer (int) together with `cap`"""
         dx, dy = _sampling(sampling)
-        on_device = not isinstance(pixels, np.ndarray)
-        if on_device:
-            ptr, nbytes = int(pixels), int(cap)
-        else:
-            if pixels.dtype != np.uint8 or not pixels.flags.c_contiguous:
-                raise ValueError("pixels: a contiguous uint8 array")
-            ptr, nbytes = pixels.ctypes.data, pixels.nbytes if cap is None else int(cap)
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
         out_cap = nbytes * 4 + (1 << 20)
         out = np.empty(out_cap, np.uint8)
         rate, res = Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), 1), RateResult()
         n = self._L.grk_amd_encode_surface_rate(self._h, C.byref(layout), C.byref(base), C.cast(dx, C.c_void_p), C.cast(dy, C.c_void_p),
-                                                C.byref(surface), ptr, nbytes, int(on_device), flags, C.byref(rate), out.ctypes.data, out_cap,
+                                                C.byref(surface), ptr, nbytes, on_device, flags, C.byref(rate), out.ctypes.data, out_cap,
                                                 C.byref(res))
         if n < 0:
             raise RateError("encode_surface_rate", n, self._L.grk_amd_last_error(self._h).decode())
@@ -1233,22 +1231,7 @@ class Context:
         """The quality allocator kernel on tables of the caller's (grk_amd_stage_quality_alloc): L uint32 and E uint64 [max_drop + 2, n],
         W float64 [n], budget: the distortion D -> (drop bytes uint8 [n], QualityAllocResult).  None for a table passes a null
         pointer.  StageError when the call refuses."""
-        Lc = None if L is None else np.ascontiguousarray(L, np.uint32)
-        Ec = None if E is None else np.ascontiguousarray(E, np.uint64)
-        Wc = None if W is None else np.ascontiguousarray(W, np.float64)
-        n = next((a.shape[-1] for a in (Wc, Lc, Ec) if a is not None), 0)
-        rows = int(max_drop) + 2
-        for a in (Lc, Ec):
-            if a is not None and a.size != rows * n:
-                raise ValueError("stage_quality_alloc: a table of %d entries, not (max_drop + 2) x %d" % (a.size, n))
-        if Wc is not None and Wc.size != n:
-            raise ValueError("stage_quality_alloc: %d weights for %d blocks" % (Wc.size, n))
-        drops, res = np.zeros(max(n, 1), np.uint8), QualityAllocResult()
-        rc = self._L.grk_amd_stage_quality_alloc(self._h, *(a.ctypes.data if a is not None else None for a in (Lc, Ec, Wc)), n,
-                                                 int(max_drop), int(bool(allow_skip)), float(budget), drops.ctypes.data, C.addressof(res))
-        if rc:
-            raise StageError("stage_quality_alloc", rc, self._L.grk_amd_last_error(self._h).decode())
-        return drops[:n], res
+        return self._stage_alloc("stage_quality_alloc", L, E, W, max_drop, allow_skip, float(budget), QualityAllocResult())
 
     def encode_tiles_quality(self, params, ntiles, pixels_ptr, on_device, psnr, distortion=0.0, max_drop=0, allow_skip=False):
         """grk_amd_encode_tiles_quality: the batch's blocks in the fewest bytes for the target -> (table, total arena bytes, QualityResult)"""

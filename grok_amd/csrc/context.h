@@ -180,12 +180,12 @@ struct grk_amd_ctx {
     bool last_h16 = false;           // the latest encode left int16 coefficients in the Mallat planes
     const uint8_t* last_drops = nullptr;   // the latest K3 launch took per-block drops: the context's copy of them (drops_keep, [last_nblocks]),
     DevBuf drops_keep;                     // from which grk_amd_fetch_table makes the rows' zero bit-planes
-    // A rate-targeted encode (rate.hip): the tables over the latest front end's blocks -- L, E candidate-major (RatePlan), W, the
-    // chosen drop bytes, the allocator's result -- and what they were made for
-    // A whole-image call with joint tables (rate_joint): the tables are over every unit's blocks in joint row order, rate_map holds the
-    // batches' maps (RateJointPlan) and rate_bdrop the drop bytes of the batch being coded; unit_rows: each unit's first row
+    // A rate- or quality-targeted encode (rate.hip, RateRun): the tables over the blocks of the run's units in the run's row order --
+    // L, E candidate-major (RatePlan), W, the chosen drop bytes, the allocator's result -- and what they were made for; unit_rows:
+    // each unit's first row.  A run over several batches also holds the batches' maps in rate_map (RateJointPlan) and the drop
+    // bytes of the batch being coded in rate_bdrop; an identity run (one batch in row order) uses neither.
     DevBuf rate_L, rate_E, rate_W, rate_drop, rate_res, rate_map, rate_bdrop;
-    struct RateState { bool valid = false; RatePlan plan{}; uint64_t nblocks = 0; uint32_t ntiles = 0; std::vector<uint64_t> unit_rows;
+    struct RateState { bool valid = false; RatePlan plan{}; uint64_t nblocks = 0; std::vector<uint64_t> unit_rows;
                        uint64_t budget = 0; /* of the latest allocator run (0: that was KQ) */
                        double qbudget = 0; /* the distortion budget of the latest run of KQ (0: that was KR2) */ } rate;
     HostStage stage;                 // pinned chunks for pageable host buffers (copy_h2d)
@@ -314,6 +314,16 @@ struct KeepLayout { grk_amd_pixel_layout& slot; grk_amd_pixel_layout keep; ~Keep
 int ht_encode_drops(grk_amd_ctx* c, uint32_t ntiles, const void* d_mallat, bool h16, const uint8_t* d_drops);               // encode.hip
 // w_mct * w_band * stepsize of row `row` of a tile's block table (T1::getwmsedec; grk_amd_block_distortion)
 double block_weight(const TileGeom& g, uint32_t row);                                                                       // encode.hip
+// An allocator's arguments over tables on the device (rate_*, a stage call's st_r*): RateAllocArgs (KR2) and RateQualityArgs (KQ)
+template <class Args, class Budget>
+inline Args rate_alloc_args(const DevBuf& L, const DevBuf& E, const DevBuf& W, const DevBuf& drop, const DevBuf& res, uint64_t nblocks, uint32_t dmax, uint32_t ncand, Budget budget)
+{
+    Args a{};
+    a.L = (const uint32_t*)L.p; a.E = (const unsigned long long*)E.p; a.W = (const double*)W.p;
+    a.nblocks = nblocks; a.dmax = dmax; a.ncand = ncand; a.budget = budget;
+    a.drop = (uint8_t*)drop.p; a.res = (decltype(a.res))res.p;
+    return a;
+}
 
 // ---- steps the encode and decode units share ----
 // The first steps of a grk_amd_stage_* entry point: the side streams joined (where the stage reads what they write), the null

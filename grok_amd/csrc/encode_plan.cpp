@@ -120,6 +120,54 @@ RateJointPlan plan_rate_joint(uint32_t max_drop, bool allow_skip, const std::vec
     return r;
 }
 
+uint64_t rate_first_budget(uint64_t target, uint64_t plain_file_bytes, uint64_t plain_block_bytes)
+{
+    const uint64_t overhead = plain_file_bytes - plain_block_bytes;
+    return target >= plain_file_bytes ? plain_block_bytes : target > overhead ? target - overhead : 0;
+}
+
+RateNextBudget rate_next_budget(uint64_t budget, uint64_t block_bytes, uint64_t file_bytes, uint64_t target)
+{
+    if (budget == 0 || block_bytes == 0) return RateNextBudget{false, 0};
+    const uint64_t over = file_bytes - target;
+    budget = std::min(budget, block_bytes);
+    return RateNextBudget{true, budget > over ? budget - over : 0};
+}
+
+// Several geometry groups: each its share of the budget by sample count, but never more than its plain bytes -- what a group cannot
+// use goes to the others, again by sample count (so a budget of all the plain bytes gives every group exactly its own: nothing is
+// dropped anywhere); the last group still open takes the rounding's remainder
+std::vector<uint64_t> group_shares(uint64_t budget, const std::vector<uint64_t>& samples, const std::vector<uint64_t>& plain)
+{
+    const size_t n = samples.size();
+    std::vector<uint64_t> share(n, 0);
+    std::vector<bool> full(n, false);
+    for (;;) {
+        uint64_t open_samples = 0, left = budget;
+        for (size_t k = 0; k < n; ++k) { if (full[k]) left -= share[k]; else open_samples += samples[k]; }
+        if (!open_samples) break;
+        bool again = false;
+        for (size_t k = 0; k < n && !again; ++k) {
+            if (full[k]) continue;
+            if ((uint64_t)((unsigned __int128)left * samples[k] / open_samples) >= plain[k]) { share[k] = plain[k]; full[k] = true; again = true; }
+        }
+        if (again) continue;
+        uint64_t given = 0;
+        size_t last = n;
+        for (size_t k = 0; k < n; ++k) if (!full[k]) last = k;
+        for (size_t k = 0; k < n; ++k) {
+            if (full[k]) continue;
+            share[k] = k == last ? left - given : (uint64_t)((unsigned __int128)left * samples[k] / open_samples);
+            given += share[k];
+        }
+        // (the remainder of up to one byte per other open group can lift the last one above its plain bytes: it takes those, the
+        //  others share the rest anew)
+        if (share[last] > plain[last]) { share[last] = plain[last]; full[last] = true; continue; }
+        break;
+    }
+    return share;
+}
+
 QualityPlan plan_quality(double target_psnr, double target_distortion, uint32_t prec, uint64_t samples)
 {
     const QualityPlan refused{};

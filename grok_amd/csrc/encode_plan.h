@@ -85,6 +85,15 @@ struct RateJointPlan {
 };
 RateJointPlan plan_rate_joint(uint32_t max_drop, bool allow_skip, const std::vector<uint64_t>& unit_blocks,
                               const std::vector<std::vector<uint32_t>>& batches);
+// The blocks' budgets of a whole-image call's rounds (rate_rounds, rate.hip).  The first: all the plain blocks' bytes for a target at
+// or above the plain file, else the target less what the plain file spends beside its blocks (0: the target does not cover that).
+// The next, after a round whose file is still above the target: the smaller of the budget and what the round's blocks took, less the
+// overshoot; left = false: the budget or the blocks' bytes were 0 already -- nothing is left to take.
+uint64_t rate_first_budget(uint64_t target, uint64_t plain_file_bytes, uint64_t plain_block_bytes);
+struct RateNextBudget { bool left; uint64_t budget; };
+RateNextBudget rate_next_budget(uint64_t budget, uint64_t block_bytes, uint64_t file_bytes, uint64_t target);
+// The split route's shares of a round's budget: see group_shares in encode_plan.cpp
+std::vector<uint64_t> group_shares(uint64_t budget, const std::vector<uint64_t>& samples, const std::vector<uint64_t>& plain);
 // A quality target as the distortion budget the quality allocator (KQ) takes: D = S * peak^2 * 10^(-psnr / 10) with peak = 2^prec - 1
 // and S the samples the PSNR is over -- the sum over the components of the component's OWN samples in the image area
 // (quality_samples): a sub-sampled component counts its own samples, with no area factor, the convention W and `distortion` follow.

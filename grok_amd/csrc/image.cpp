@@ -102,6 +102,20 @@ int grk_amd::encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const
     return GRK_AMD_OK;
 }
 
+void grk_amd::planar_rate_call(grk_amd_ctx* ctx, const std::vector<Unit>& units, const SourcePlanes& src, const UnitGroups& g,
+                               std::vector<uint8_t>& staging, RateJointCall& call)
+{
+    for (size_t u = 0; u < units.size(); ++u) call.unit_blocks.push_back((uint64_t)g.geoms[g.of[u]].blocks_per_comp * units[u].p.num_comps);
+    for (const std::vector<uint32_t>& G : g.members) call.batches.push_back(RateBatch{units[G[0]].p, G});
+    const RateJointCall* const self = &call;
+    call.front = [ctx, &units, &src, &staging, self](size_t k, grk_amd_coded_block* table, uint64_t* total) -> int {
+        const std::vector<uint32_t>& G = self->batches[k].units;
+        staging.resize(staged_bytes(src, units[G[0]]) * G.size());
+        stage_units(src, units, G, staging.data(), 1);
+        return grk_amd_encode_tiles(ctx, &self->batches[k].p, (uint32_t)G.size(), staging.data(), 0, table, total);
+    };
+}
+
 int64_t grk_amd::frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
                             const std::vector<uint32_t>& part_len, uint8_t* out, uint64_t cap,
                             const std::function<int(const std::vector<uint64_t>& at)>& body, const uint8_t* comp_dx, const uint8_t* comp_dy)

@@ -125,17 +125,17 @@ bool image_t2_host();
 int subsampled_image(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                      const uint8_t* comp_dy, const void* pixels, std::vector<Unit>& units, SourcePlanes& src, UnitGroups& g);
 
-// ---- a whole image in a file of at most N bytes over JOINT tables (rate.hip) -----------------------------------------------------
+// ---- a whole image in a file of at most N bytes, or in the fewest bytes for a distortion, over joint tables (rate.hip) --------------
 // The caller names the image's units (unit_blocks[u]: unit u's rows, in the order the file's writer takes the table) and its
 // batches -- each one grk_amd_encode_tiles call over units of one geometry -- and lends two steps:
 //   front(k, table, total)        batch k's pixels staged where they have to be and coded plainly: grk_amd_encode_tiles with these
 //                                 `table` (host rows or null) and `total`; called once for the tables and again before a round's
 //                                 final launch whenever another batch's planes have taken the context since
 //   write(rows, coded, out, cap)  the file of these rows (joint order; offsets into `coded`), or with out == nullptr its length
-// encode_rate_joint makes the tables L, E, W over all units once (every batch's KR1 and trial launches write their columns through
-// the batch's map: plan_rate_joint), runs KR2 once per round over them -- one multiplier for every block of the image -- and codes
-// each batch with its slice of the chosen drops; the rounds are rate_rounds' (rate.hip), shared with the split route.  Returns the
-// file's length or an error; rate_refusal: what every rate-targeted call refuses before any work (pipelining, max_drop).
+// encode_rate_joint is a run (RateRun, rate.hip: the one path every rate- and quality-targeted call takes to its tables and its
+// coded blocks) over all units through the batches' maps (plan_rate_joint): the tables L, E, W made once, KR2 once per round over
+// them -- one multiplier for every block of the image --, each batch coded with its slice of the chosen drops and merged into the
+// file's rows; the rounds are rate_rounds' (rate.hip), shared with the split route.  Returns the file's length or an error.
 // The call's goal is bytes (rate->target_bytes, the rounds above), or -- quality != nullptr -- a distortion budget: the same tables,
 // then KQ once over them, every batch coded with its slice of the drops and the file written once; no rounds (headers do not enter a
 // distortion budget).  rate then carries max_drop and allow_skip only (QualityTarget makes both from a grk_amd_quality), and the
@@ -149,14 +149,19 @@ struct RateJointCall {
     std::function<int64_t(const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* out, uint64_t cap)> write;
     const QualityGoal* quality = nullptr;
 };
-// A grk_amd_quality checked and turned into what the joint call takes: GRK_AMD_OK, or what every quality-targeted call refuses before
-// any work -- pipelining (GRK_AMD_ERR_UNSUPPORTED), max_drop above 12, a target plan_quality refuses (GRK_AMD_ERR_INVALID).  The
-// tables of an earlier call are invalid from here on, refused or not.
+// unit_blocks, batches and front of a planar image's call (plain_image's or subsampled_image's units, source and groups: one batch
+// per group, staged into `staging`); the caller adds `write`.  Everything passed is referred to, `call` included
+void planar_rate_call(grk_amd_ctx* ctx, const std::vector<Unit>& units, const SourcePlanes& src, const UnitGroups& g,
+                      std::vector<uint8_t>& staging, RateJointCall& call);
+// What every rate- or quality-targeted call refuses before any work: pipelining (GRK_AMD_ERR_UNSUPPORTED), max_drop above 12
+// (GRK_AMD_ERR_INVALID).  goal: "rate" or "quality", the word the messages name the call and its struct by
+int rate_refusal(grk_amd_ctx* ctx, const grk_amd_rate* rate, const char* goal = "rate");
+// A grk_amd_quality checked and turned into what the joint call takes: GRK_AMD_OK, or rate_refusal's answer, or GRK_AMD_ERR_INVALID
+// for a target plan_quality refuses.  The tables of an earlier call are invalid from here on, refused or not.
 // samples: S of the call (quality_samples, encode_plan.h)
 struct QualityTarget { grk_amd_rate rate; QualityGoal goal; };
 int quality_target(grk_amd_ctx* ctx, const grk_amd_quality* quality, uint32_t prec, uint64_t samples, grk_amd_quality_result* result,
                    QualityTarget& out);
-int rate_refusal(grk_amd_ctx* ctx, const grk_amd_rate* rate);
 int64_t encode_rate_joint(grk_amd_ctx* ctx, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result);
 
 // fn(i) for i in [0, n) on up to `threads` host threads, the caller's among them; items are handed out by a counter and the

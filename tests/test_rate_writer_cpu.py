@@ -271,3 +271,133 @@ def test_drop_bytes_and_zero_bit_planes():
         for d in (0, 1, kmax - 1, kmax, 40, 254):
             assert u.rp_missing_msbs(kmax, d) == kmax - 1 - min(d, kmax - 1)       # clamped to kmax - 1
         assert u.rp_missing_msbs(kmax, 0xFF) == kmax - 1                             # SKIP: the all-zero row
+
+
+# ---- 5. the budgets of a whole-image call's rounds, and the split route's shares of them ----------------------------------------------
+def c_shares(budget, samples, plain):
+    u = units()
+    u.rp_group_shares.argtypes = [C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    s, p, out = np.array(samples, np.uint64), np.array(plain, np.uint64), np.zeros(len(samples), np.uint64)
+    u.rp_group_shares(budget, len(samples), s.ctypes.data, p.ctypes.data, out.ctypes.data)
+    return [int(v) for v in out]
+
+
+def shares_restated(budget, samples, plain):
+    """group_shares in exact integers: every open group's share is floor(left * samples / open samples); a group whose share reaches
+    its plain bytes takes exactly those and closes, and the rest is shared anew; the last open group takes the rounding's remainder --
+    unless that lifts it above its own plain bytes, in which case it closes too"""
+    n = len(samples)
+    share, full = [0] * n, [False] * n
+    while True:
+        left = budget - sum(share[k] for k in range(n) if full[k])
+        opened = [k for k in range(n) if not full[k]]
+        total = sum(samples[k] for k in opened)
+        if not total:
+            return share
+        k = next((k for k in opened if left * samples[k] // total >= plain[k]), None)
+        if k is None:
+            floors = {j: left * samples[j] // total for j in opened[:-1]}
+            k = opened[-1]
+            if left - sum(floors.values()) <= plain[k]:
+                for j, v in floors.items():
+                    share[j] = v
+                share[k] = left - sum(floors.values())
+                return share
+        share[k], full[k] = plain[k], True
+
+
+def check_shares(budget, samples, plain):
+    got = c_shares(budget, samples, plain)
+    assert got == shares_restated(budget, samples, plain), (budget, samples, plain)
+    assert all(g <= p for g, p in zip(got, plain)), (budget, samples, plain, got)
+    assert sum(got) == min(budget, sum(plain)), (budget, samples, plain, got)
+    if budget >= sum(plain):
+        assert got == list(plain)
+    return got
+
+
+def test_group_shares_chosen_cases():
+    samples, plain = [64 * 48 * 3, 36 * 48 * 3, 64 * 28 * 3, 36 * 28 * 3], [5000, 3100, 2900, 1700]
+    for budget in (sum(plain), sum(plain) + 1, 2 ** 40, 2 ** 64 - 1, sum(plain) - 1, sum(plain) // 2, 1, 0):
+        check_shares(budget, samples, plain)
+    assert check_shares(4000, samples, [5000, 0, 2900, 1700])[1] == 0              # a group without plain bytes
+    assert check_shares(700, [5], [777]) == [700] and check_shares(778, [5], [777]) == [777]      # one group
+    assert check_shares(1001, [3, 5, 7], [1000, 1000, 1000]) == [200, 333, 468]    # every floor division inexact
+    assert check_shares(5, [1, 1, 1], [2, 2, 2]) == [1, 2, 2]                      # the remainder does not lift the last group above its own
+    big = [(1 << 40) + 1, (1 << 41) + 3, 7]                                        # products beyond 2^64
+    check_shares((1 << 62) + 12345, big, [1 << 62, 1 << 61, 1 << 60])
+    check_shares(2 ** 64 - 1, big, [1 << 62, 1 << 61, 1 << 60])
+    check_shares((1 << 63) + 1, [2 ** 63 - 1, 2 ** 62 + 1], [1 << 63, 1 << 62])
+
+
+def test_group_shares_random_cases():
+    """3000 cases of 1 .. 6 groups: sample counts and plain bytes of every magnitude (the sums stay below 2^64, as sums of an image's
+    bytes and samples do), budgets around the plain bytes and far from them"""
+    rng = np.random.default_rng(11)
+    for _ in range(3000):
+        n = int(rng.integers(1, 7))
+        bits = int(rng.choice([8, 16, 33, 60]))
+        samples = [int(rng.integers(1, 1 << int(rng.integers(1, bits + 1)))) for _ in range(n)]
+        plain = [int(rng.integers(0, 1 << int(rng.integers(1, bits + 1)))) for _ in range(n)]
+        all_ = sum(plain)
+        budgets = [0, 1, all_ - 1, all_, all_ + 1, all_ // 2, all_ // 3 + 1, int(rng.integers(0, all_ + 2)), 2 * all_]
+        check_shares(max(budgets[int(rng.integers(0, len(budgets)))], 0), samples, plain)
+
+
+def next_budget(budget, blocks, file_bytes, target):
+    u = units()
+    u.rp_next_budget.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
+    out = C.c_uint64(0)
+    left = u.rp_next_budget(budget, blocks, file_bytes, target, C.byref(out))
+    return int(out.value) if left else None
+
+
+def test_round_budgets():
+    """The first budget: the plain blocks' bytes for a target at or above the plain file, else the target less what the plain file
+    spends beside its blocks, 0 where the target does not cover that.  The next: the smaller of the budget and the bytes the round's
+    blocks took, less the file's overshoot, down to 0; nothing is left once the budget or the blocks' bytes are 0.
+    A round is followed by another only when its file overshoots, by one byte at least: so the budgets never rise, fall by one at
+    least per round, and any sequence of overshoots ends in 0 or in "nothing left" after at most the first budget's worth of rounds
+    (the library stops after kRateMaxRounds of them)."""
+    u = units()
+    u.rp_first_budget.restype = C.c_uint64
+    u.rp_first_budget.argtypes = [C.c_uint64] * 3
+    rng = np.random.default_rng(12)
+    for _ in range(3000):
+        blocks = int(rng.integers(0, 1 << int(rng.integers(1, 40))))
+        plain = blocks + int(rng.integers(1, 5000))
+        targets = [0, 1, plain - blocks - 1, plain - blocks, plain - blocks + 1, plain - 1, plain, plain + 1, 2 * plain, int(rng.integers(0, plain + 1))]
+        target = targets[int(rng.integers(0, len(targets)))]
+        want = blocks if target >= plain else max(target - (plain - blocks), 0)
+        assert u.rp_first_budget(target, plain, blocks) == want <= blocks, (target, plain, blocks)
+    assert u.rp_first_budget(2 ** 64 - 1, 2 ** 63, 2 ** 63 - 5) == 2 ** 63 - 5
+    assert next_budget(500, 480, 640, 600) == 440 and next_budget(500, 480, 2000, 600) == 0 and next_budget(480, 500, 601, 600) == 479
+    assert next_budget(0, 0, 640, 600) is None and next_budget(0, 10, 640, 600) is None and next_budget(10, 0, 640, 600) is None
+    for _ in range(300):
+        budget = first = int(rng.integers(0, 400))
+        target = int(rng.integers(50, 1000))
+        rounds = 0
+        while True:
+            blocks = int(rng.integers(0, budget + 1)) if rng.integers(0, 4) == 0 else budget - int(rng.integers(0, budget // 8 + 1))
+            over = int(rng.choice([1, 1, 2, int(rng.integers(1, 60))]))
+            nxt = next_budget(budget, blocks, target + over, target)
+            want = None if budget == 0 or blocks == 0 else max(min(budget, blocks) - over, 0)
+            assert nxt == want, (budget, blocks, over)
+            if nxt is None:
+                break
+            assert nxt < budget
+            budget = nxt
+            rounds += 1
+        assert rounds <= first
+
+
+def test_round_budgets_driver_under_sanitizers():
+    """tests/c/rate_plan_units.cpp as a program of its own (its main walks the chosen cases) under AddressSanitizer and UBSan"""
+    csrc = os.path.join(ROOT, "grok_amd", "csrc")
+    exe = os.path.join(tempfile.mkdtemp(prefix="rate_plan_main_"), "rate_plan_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-D_GLIBCXX_ASSERTIONS", "-DRATE_PLAN_MAIN",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", os.path.join(HERE, "c", "rate_plan_units.cpp"),
+                           os.path.join(csrc, "encode_plan.cpp"), os.path.join(csrc, "geometry.cpp"), "-o", exe, "-lpthread"])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "0 failure(s)" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, \
+        r.stdout + r.stderr

@@ -13,7 +13,7 @@ from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Cont
                    Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, SURFACE_FORMATS_MSB, surface_bytes, surface_plan,
                    PACKED_FORMATS, packed_bytes,
                    CS_BLOCK_MSBS, DROP_SKIP, Rate, RateResult, RateAllocResult, RateError, Quality, QualityResult, QualityAllocResult, StageError, t2_max_block_bytes,
-                   ERR_UNSUPPORTED, ERR_INVALID)
+                   ERR_UNSUPPORTED, ERR_INVALID, READ_DEVICE_FIRST_COPY)
 
 __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
            "tile_layout", "reduced_tile_rect", "write_codestream", "write_tile_part", "write_main_header", "locate_tile_parts", "CS_TLM", "CS_PLT", "CS_SOP", "CS_EPH", "CS_PROG",
@@ -23,4 +23,4 @@ __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "C
            "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "SURFACE_FORMATS_MSB", "surface_bytes", "surface_plan",
            "PACKED_FORMATS", "packed_bytes",
            "CS_BLOCK_MSBS", "DROP_SKIP", "Rate", "RateResult", "RateAllocResult", "RateError", "Quality", "QualityResult", "QualityAllocResult", "StageError", "t2_max_block_bytes",
-           "ERR_UNSUPPORTED", "ERR_INVALID"]
+           "ERR_UNSUPPORTED", "ERR_INVALID", "READ_DEVICE_FIRST_COPY"]

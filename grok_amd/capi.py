@@ -648,6 +648,7 @@ CODED_DTYPE = np.dtype([("offset", np.uint64), ("length", np.uint32), ("missing_
 SEGMENT_DTYPE = np.dtype([("length", np.uint32), ("numpasses", np.uint32)])
 MOVE_DTYPE = np.dtype([("dst", np.uint64), ("src", np.uint64), ("len", np.uint32), ("kind", np.uint32)])
 ERR_UNSUPPORTED, ERR_INVALID, ERR_OVERFLOW, ERR_RANGE = -2, -3, -5, -6
+READ_DEVICE_FIRST_COPY = 4096          # GRK_AMD_READ_DEVICE_FIRST_COPY: the first copy grk_amd_read_header_device makes of a main header
 
 
 def _cs_array(cs):
@@ -1457,6 +1458,55 @@ class Context:
         buf = _cs_array(cs)
         view = ImageView.make(reduce, window)
         self._check(self._L.grk_amd_decode_image_view(self._h, buf.ctypes.data, buf.size, C.byref(view), d_pixels, int(cap), 1), "decode_image_view")
+
+    # ---- a codestream that lies in device memory (grk_amd_read_*_device, grk_amd_decode_image_device) ----
+    def _read_device_fns(self):
+        L = self._L
+        if not getattr(L, "_read_device_bound", False):
+            vp, u64 = C.c_void_p, C.c_uint64
+            L.grk_amd_read_header_device.argtypes = [vp, vp, u64, C.POINTER(StreamInfo)]
+            L.grk_amd_read_packets_device.restype = C.c_int64
+            L.grk_amd_read_packets_device.argtypes = [vp, vp, u64, C.POINTER(StreamInfo), vp, u64]
+            L.grk_amd_decode_image_device.argtypes = [vp, vp, u64, vp, u64, C.c_int]
+            L.grk_amd_read_device_counters.restype = u64
+            L.grk_amd_read_device_counters.argtypes = [vp, C.c_int]
+            L._read_device_bound = True
+        return L
+
+    def read_header_device(self, d_cs, nbytes):
+        """grk_amd_read_header_device: the main header of a codestream at device pointer d_cs -> StreamInfo; ReaderError when refused."""
+        L = self._read_device_fns()
+        info = StreamInfo()
+        rc = L.grk_amd_read_header_device(self._h, int(d_cs), int(nbytes), C.byref(info))
+        if rc:
+            raise ReaderError("read_header_device", rc, self.last_error())
+        return info
+
+    def read_packets_device(self, d_cs, nbytes, info=None):
+        """grk_amd_read_packets_device: every packet header of the codestream at device pointer d_cs, parsed on the device -> rows
+        (CODED_DTYPE, host), what read_packets(...)["rows"] gives for the same bytes; ReaderError with its code when refused."""
+        L = self._read_device_fns()
+        if info is None:
+            info = self.read_header_device(d_cs, nbytes)
+        rows = np.zeros(int(info.num_blocks), CODED_DTYPE)
+        n = L.grk_amd_read_packets_device(self._h, int(d_cs), int(nbytes), C.byref(info), rows.ctypes.data, rows.size)
+        if n < 0:
+            raise ReaderError("read_packets_device", n, self.last_error())
+        return rows[:n]
+
+    def decode_image_resident(self, d_cs, nbytes, pixels, cap, on_device=True):
+        """grk_amd_decode_image_device: the codestream at device pointer d_cs (it is the coded buffer: nothing of it crosses the link)
+        -> pixels at `pixels` (a device pointer, asynchronous behind the reader: decode_status joins; or with on_device False a host
+        address).  ReaderError where the reader refuses the stream."""
+        L = self._read_device_fns()
+        rc = L.grk_amd_decode_image_device(self._h, int(d_cs), int(nbytes), int(pixels), int(cap), int(bool(on_device)))
+        if rc:
+            raise ReaderError("decode_image_resident", rc, self.last_error())
+
+    def read_device_counters(self):
+        """(bytes copied device -> host, bytes copied host -> device, KC launches, chains parsed) by the calls above so far"""
+        L = self._read_device_fns()
+        return tuple(int(L.grk_amd_read_device_counters(self._h, k)) for k in range(4))
 
     def decode_image_counters(self):
         """(tiles whose packets were read, codestream bytes uploaded) by this context's decode_image / decode_image_view calls so far"""

@@ -244,6 +244,9 @@ struct grk_amd_ctx {
     // device surface that the surface calls above then work on; a host frame's copy lies in img_pixels; launches of KU, of KK
     DevBuf img_planes;
     uint64_t packed_counters[2] = {0, 0};
+    // grk_amd_read_packets_device / grk_amd_decode_image_device (read_device.hip): the plan kept for the latest stream header, its
+    // descriptors and scratch on the device, the header's pinned copy, the counters -- made by the first such call
+    struct ReadDevState* rdev = nullptr;
     // timing
     bool timing = false;
     Timer timers[10];
@@ -302,6 +305,12 @@ int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, 
 // the rules of a host destination -- a group that leaves the int16 planes is repeated by the call itself
 int decode_onto_surface(grk_amd_ctx* c, const char* name, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels,
                         uint64_t cap, int pixels_on_device, bool host_rules);                                                 // decode_image.cpp
+// grk_amd_decode_image for a codestream that IS the coded buffer already (d_cs, device memory) and whose header and rows the device
+// reader has made (read_device.hip): decode_view's way in for "coded bytes resident, table given"; `tab` is consumed
+namespace grk_amd { struct StreamTable; }
+int decode_resident(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, grk_amd::StreamTable& tab, void* pixels,
+                    uint64_t cap, int pixels_on_device);                                                                      // decode_image.cpp
+void read_device_release(grk_amd_ctx* c);                                                                                     // read_device.hip
 // what the whole-image decodes refuse on the context: a decode reduce (`reduced`: the text behind the entry point's name), a decode sequence
 int refuse_context(grk_amd_ctx* c, const char* name, const char* reduced);                                                    // decode_image.cpp
 

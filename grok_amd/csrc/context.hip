@@ -317,6 +317,7 @@ void grk_amd_destroy(grk_amd_ctx* c)
     if (c->ev_level0) (void)hipEventDestroy(c->ev_level0);
     if (c->ev_side) (void)hipEventDestroy(c->ev_side);
     for (DevBuf* b : {&c->dec_seg_dev, &c->img_coded, &c->img_tiles, &c->img_pixels, &c->img_moves, &c->img_rects, &c->img_status, &c->img_planes}) b->release();
+    read_device_release(c);
     c->stage.release();
     if (c->d2h_pin) (void)hipHostFree(c->d2h_pin);
     for (hipEvent_t ev : c->d2h_ev) (void)hipEventDestroy(ev);

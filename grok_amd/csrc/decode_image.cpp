@@ -138,15 +138,20 @@ extern "C" int grk_amd_place_tiles_clipped_device(grk_amd_ctx* c, const void* ti
 // host_rules: the call behaves as one with a host destination does -- it joins behind a group that may leave the int16 planes and
 // repeats it with int32 planes by itself.  That is every call with host pixels, and the packed decode of a host frame (packed.cpp),
 // whose planes lie in device memory all the same.
+// res != nullptr (grk_amd_decode_image_device): the codestream lies in device memory and IS the coded buffer -- nothing is uploaded,
+// no packet is read here: the header and the table are the device reader's (read_device.hip); `cs` is not looked at.
+struct ResidentStream { const void* d_cs; const grk_amd_stream_info* info; StreamTable* tab; };
 static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap, int pixels_on_device,
-                       const grk_amd_surface* surf = nullptr, bool host_rules = false)
+                       const grk_amd_surface* surf = nullptr, bool host_rules = false, const ResidentStream* res = nullptr)
 {
     host_rules = host_rules || !pixels_on_device;
     // header -> view plan -> destination plan: every refusal that needs no byte of a packet
     grk_amd_stream_info info;
     std::string why;
     const char* pwhy = "";
-    int rc = read_stream_header(cs, len, info, why);
+    int rc = GRK_AMD_OK;
+    if (res) info = *res->info;
+    else rc = read_stream_header(cs, len, info, why);
     if (rc) return fail(c, rc, why.c_str());
     ViewPlan plan;
     rc = plan_image_view(info, view, plan, &pwhy);
@@ -160,6 +165,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     // the coded buffer.  Where the tile-parts lie: found up front only when the upload depends on it (a view of every tile finds
     // them beside its upload, as the packets are read)
     std::vector<StreamPart> parts;
+    if (res && !d.all) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a view of a codestream in device memory");
     if (!d.all) {
         rc = locate_stream_parts(cs, len, info, parts, why);
         if (rc) return fail(c, rc, why.c_str());
@@ -169,10 +175,12 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     rc = join_side(c); if (rc) return rc;
     // the upload, the packet headers meanwhile
-    HIP_TRY(c, c->img_coded.ensure(coded.coded_cap + 64), "alloc the coded buffer");
+    if (!res) HIP_TRY(c, c->img_coded.ensure(coded.coded_cap + 64), "alloc the coded buffer");
+    void* const coded_buf = res ? const_cast<void*>(res->d_cs) : c->img_coded.p;
     StreamTable tab;
     int rrc = GRK_AMD_OK;
-    {
+    if (res) tab = std::move(*res->tab);
+    else {
         const uint32_t threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
         std::thread reader([&]() {
             if (d.all) rrc = locate_stream_parts(cs, len, info, parts, why);
@@ -184,7 +192,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     }
     if (rc) return rc;
     if (rrc) return fail(c, rrc, why.c_str());
-    c->img_counters[0] += plan.tiles.size(); c->img_counters[1] += coded.up_len;
+    if (!res) { c->img_counters[0] += plan.tiles.size(); c->img_counters[1] += coded.up_len; }
     std::vector<uint64_t> unit_row;
     rc = rebase_table(tab, len, d.all, plan.tiles, parts, coded, d, unit_row, &pwhy);
     if (rc) return fail(c, rc, pwhy);
@@ -192,7 +200,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     // (from here on the call only queues work; the small tables below are uploaded with blocking copies into buffers that an
     //  earlier call's kernels may still read)
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-    rc = run_gather(c, tab.moves.data(), tab.moves.size(), c->img_coded.p, (uint8_t*)c->img_coded.p + coded.up_len); if (rc) return rc;
+    rc = run_gather(c, tab.moves.data(), tab.moves.size(), coded_buf, (uint8_t*)coded_buf + coded.up_len); if (rc) return rc;
 
     SavedSettings saved(c);
     c->dec_steps.clear();
@@ -212,8 +220,8 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         // planes by itself) -- a window of it by the region decoder, whose cost follows the window
         rc = batch_tables(d.g.members[0].data(), d.g.members[0].size());
         if (rc) return rc;
-        if (d.route == ImageRoute::Direct) return grk_amd_decode_tiles(c, &d.tp[0], 1, table.data(), c->img_coded.p, coded_bytes, 1, pixels, pixels_on_device);
-        return grk_amd_decode_region(c, &d.tp[0], table.data(), c->img_coded.p, coded_bytes, 1, d.region[0], d.region[1], d.region[2], d.region[3], pixels,
+        if (d.route == ImageRoute::Direct) return grk_amd_decode_tiles(c, &d.tp[0], 1, table.data(), coded_buf, coded_bytes, 1, pixels, pixels_on_device);
+        return grk_amd_decode_region(c, &d.tp[0], table.data(), coded_buf, coded_bytes, 1, d.region[0], d.region[1], d.region[2], d.region[3], pixels,
                                      pixels_on_device);
     }
     HIP_TRY(c, c->img_status.ensure(64), "alloc status");
@@ -226,7 +234,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
             rc = batch_tables(&r, 1); if (rc) return rc;
             uint8_t* const dst = (uint8_t*)pixels + rd.at;
             if (rd.beside) HIP_TRY(c, c->img_tiles.ensure(rd.bytes), "alloc a run's planes");
-            rc = grk_amd_decode_tiles(c, &d.tp[r], 1, table.data(), c->img_coded.p, coded_bytes, 1, rd.beside ? c->img_tiles.p : dst, pixels_on_device);
+            rc = grk_amd_decode_tiles(c, &d.tp[r], 1, table.data(), coded_buf, coded_bytes, 1, rd.beside ? c->img_tiles.p : dst, pixels_on_device);
             if (rc) return rc;
             if (rd.beside) HIP_TRY(c, hipMemcpyAsync(dst, c->img_tiles.p, rd.bytes, hipMemcpyDeviceToDevice, c->stream), "copy a run's planes");
             if (pixels_on_device)
@@ -238,7 +246,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     }
     // a batch (`table`: its rows) into device memory at dst, its status kept in the image's
     auto decode_group = [&](const grk_amd_tile_params& p, uint32_t n, void* dst) -> int {
-        int drc = grk_amd_decode_tiles(c, &p, n, table.data(), c->img_coded.p, coded_bytes, 1, dst, 1); if (drc) return drc;
+        int drc = grk_amd_decode_tiles(c, &p, n, table.data(), coded_buf, coded_bytes, 1, dst, 1); if (drc) return drc;
         // The int16-plane rule (include/grok_amd.h, grk_amd_set_decode_planes16).  A decode into a device buffer does not repeat
         // itself: with host pixels this call joins behind a group that may use those planes, reads its status and repeats it
         // with int32 planes; with device pixels the status goes to grk_amd_decode_status like any other
@@ -246,7 +254,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
             drc = grk_amd_decode_status(c);
             if (drc == GRK_AMD_ERR_RANGE) {
                 c->dec_planes16 = false;
-                drc = grk_amd_decode_tiles(c, &p, n, table.data(), c->img_coded.p, coded_bytes, 1, dst, 1);
+                drc = grk_amd_decode_tiles(c, &p, n, table.data(), coded_buf, coded_bytes, 1, dst, 1);
                 c->dec_planes16 = true;
             }
             if (drc) return drc;
@@ -305,6 +313,13 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     if (pixels_on_device) return GRK_AMD_OK;
     rc = copy_d2h(c, pixels, d_img, d.total); if (rc) return rc;
     return grk_amd_decode_status(c);
+}
+
+int decode_resident(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, StreamTable& tab, void* pixels, uint64_t cap,
+                    int pixels_on_device)
+{
+    const ResidentStream res{d_cs, &info, &tab};
+    return decode_view(c, nullptr, len, nullptr, pixels, cap, pixels_on_device, nullptr, false, &res);
 }
 
 // what the three whole-image entry points refuse on the context (`reduced`: the text behind the entry point's name)

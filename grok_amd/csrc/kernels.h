@@ -428,4 +428,30 @@ struct PackedArgs {
 hipError_t launch_packed_unpack(const PackedArgs& a, hipStream_t s);
 hipError_t launch_packed_pack(const PackedArgs& a, hipStream_t s);
 
+// ---- KL / KH / KC: Tier-2 READ on the device (kernels_t2read.hip; the parse core: t2_parse.h, the plan: t2_read_plan.h) ----------
+// cs: the codestream in device memory, `len` bytes; no byte outside it is read.  tiles / packets: the plan's, uploaded as they are.
+// KL fills part_at / part_len ([tile]; a length of 0: not located), KH body_at ([tile]: behind SOD, 0: header refused), has_plt and
+// -- with PLT -- plt_len / pk_start ([tile's pkt_base + packet]), KC every row of `rows`.  status: the call's word (t2_parse.h),
+// set to kT2pNoStatus before KL.  KH and KC pass over tiles whose earlier stage left nothing.
+struct T2ReadTile; struct T2ReadPacket;
+struct T2ReadTlmEntry { uint64_t at; uint32_t ln, idx; };
+struct T2ReadArgs {
+    const uint8_t* cs; uint64_t len;
+    uint32_t num_tiles;
+    const T2ReadTile* tiles; const T2ReadPacket* packets;
+    uint32_t ht, sop, eph;
+    // KL: tlm_n entries from TLM (tlm != nullptr; tlm_count: all of TLM's), or the Psot chain from sot_at
+    const T2ReadTlmEntry* tlm; uint32_t tlm_n; uint64_t tlm_count; uint64_t sot_at;
+    uint32_t* first_of;                              // [tile] scratch
+    unsigned long long* part_at; uint32_t* part_len; unsigned long long* body_at; uint32_t* has_plt;
+    uint32_t* plt_len; unsigned long long* pk_start;
+    uint8_t* nodes;
+    grk_amd_coded_block* rows;
+    unsigned long long* status;
+    uint64_t chains;                                 // KC's grid
+};
+hipError_t launch_t2read_locate(const T2ReadArgs& a, hipStream_t s);
+hipError_t launch_t2read_headers(const T2ReadArgs& a, hipStream_t s);
+hipError_t launch_t2read_chains(const T2ReadArgs& a, hipStream_t s);
+
 } // namespace grk_amd

@@ -1,0 +1,224 @@
+// grok_amd/csrc/read_device.hip -- a codestream that lies in DEVICE memory read where it lies (grk_amd_read_header_device,
+// grk_amd_read_packets_device, grk_amd_decode_image_device): the executor of t2_read_plan.h over the kernels of kernels_t2read.hip.
+// What comes to the host is the main header (read_stream_header runs on the copy), the call's status word and the finished rows;
+// what goes up is the plan's descriptors -- once per kind of stream: the plan is kept while the header stays the same -- and TLM's
+// places.  No byte of a tile-part crosses the link.
+#include "context.h"
+#include "t2_read_plan.h"
+#include "t2_reader.h"
+
+struct ReadDevState {
+    bool have_plan = false;
+    grk_amd_stream_info info{};
+    T2ReadPlan plan;
+    DevBuf tiles, packets, parts, plt_len, pk_start, nodes, rows, status, tlm;
+    uint8_t* pin = nullptr; size_t pin_cap = 0;         // the header's copy, the status word behind a 16-byte boundary
+    uint64_t counters[4] = {0, 0, 0, 0};
+};
+
+void read_device_release(grk_amd_ctx* c)
+{
+    ReadDevState* r = c->rdev;
+    if (!r) return;
+    for (DevBuf* b : {&r->tiles, &r->packets, &r->parts, &r->plt_len, &r->pk_start, &r->nodes, &r->rows, &r->status, &r->tlm}) b->release();
+    if (r->pin) (void)hipHostFree(r->pin);
+    delete r;
+    c->rdev = nullptr;
+}
+
+namespace {
+
+ReadDevState* state(grk_amd_ctx* c) { if (!c->rdev) c->rdev = new ReadDevState; return c->rdev; }
+
+int ensure_pin(grk_amd_ctx* c, ReadDevState* r, size_t n)
+{
+    if (n <= r->pin_cap) return GRK_AMD_OK;
+    uint8_t* p = nullptr;
+    const size_t want = n + (n >> 1) + 64;
+    HIP_TRY(c, hipHostMalloc((void**)&p, want, hipHostMallocDefault), "alloc the header's copy");
+    if (r->pin) { std::memcpy(p, r->pin, r->pin_cap); (void)hipHostFree(r->pin); }
+    r->pin = p; r->pin_cap = want;
+    return GRK_AMD_OK;
+}
+
+// What read_stream_header will look at in a stream of `len` bytes of which buf holds the first `have`: the bytes up to where its
+// walks end.  <= have: everything it reads is there
+uint64_t header_need(const uint8_t* b, uint64_t have, uint64_t len)
+{
+    auto u16 = [&](uint64_t i) { return (uint32_t)(b[i] << 8 | b[i + 1]); };
+    if (have < 4) return std::min<uint64_t>(len, 4);
+    uint64_t at = 2;
+    for (;;) {
+        if (at + 4 > len) return have;
+        if (at + 4 > have) return at + 4;
+        const uint32_t m = u16(at);
+        if (m == 0xFF90) break;
+        const uint32_t l = u16(at + 2);
+        if (m < 0xFF30 || l < 2 || at + 2 + l > len) return have;
+        if (at + 2 + l > have) return std::min<uint64_t>(len, at + 2 + (uint64_t)l + 16);
+        at += 2 + (uint64_t)l;
+    }
+    // (the first tile-part's header says whether the file has PLT: up to its first PLT or SOD)
+    for (uint64_t q = at + 12;;) {
+        if (q + 4 > len) return have;
+        if (q + 4 > have) return q + 4;
+        const uint32_t m = u16(q), l = u16(q + 2);
+        if (m == 0xFF93 || m == 0xFF58 || m < 0xFF30 || l < 2) return have;
+        q += 2 + (uint64_t)l;
+    }
+}
+
+// The main header to the host, in the order of the context's stream: GRK_AMD_READ_DEVICE_FIRST_COPY bytes, then -- a long COM, a
+// TLM of thousands of tiles -- what the first copy shows is missing.  *have: bytes of the stream in r->pin
+int fetch_header(grk_amd_ctx* c, ReadDevState* r, const void* d_cs, uint64_t len, uint64_t* have)
+{
+    uint64_t got = 0, want = std::min<uint64_t>(len, GRK_AMD_READ_DEVICE_FIRST_COPY);
+    for (int turn = 0; turn < 64 && want > got; ++turn) {
+        const int rc = ensure_pin(c, r, want + 32); if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(r->pin + got, (const uint8_t*)d_cs + got, want - got, hipMemcpyDeviceToHost, c->stream), "fetch the main header");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+        r->counters[0] += want - got;
+        got = want;
+        const uint64_t need = header_need(r->pin, got, len);
+        if (need > got) want = std::min<uint64_t>(len, need + 2048);
+    }
+    *have = got;
+    return GRK_AMD_OK;
+}
+
+int header_device(grk_amd_ctx* c, const void* d_cs, uint64_t len, grk_amd_stream_info& info, uint64_t* have)
+{
+    ReadDevState* r = state(c);
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    int rc = fetch_header(c, r, d_cs, len, have); if (rc) return rc;
+    std::string why;
+    // (the copy holds every byte read_stream_header looks at: over it the result is what the whole stream gives)
+    rc = read_stream_header(r->pin, *have, info, why);
+    return rc ? fail(c, rc, why.c_str()) : GRK_AMD_OK;
+}
+
+// the rows of the stream whose header (info; its first `have` bytes in the pinned copy) the caller has read: into tab.rows on the
+// host when tab != nullptr, else into rows[row_cap] (nullptr: counted only)
+int64_t packets_device(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, uint64_t have, grk_amd_coded_block* rows,
+                       uint64_t row_cap, StreamTable* tab)
+{
+    ReadDevState* r = state(c);
+    const char* pwhy = "";
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the tables below may still be read by an earlier call's kernels)
+    if (!r->have_plan || std::memcmp(&r->info, &info, sizeof info) != 0) {
+        r->have_plan = false;
+        const int rc = plan_t2_read(info, r->plan, &pwhy);
+        if (rc) return fail(c, rc, pwhy);
+        HIP_TRY(c, r->tiles.ensure(r->plan.bytes_tiles()), "alloc the tiles' descriptors");
+        HIP_TRY(c, r->packets.ensure(r->plan.bytes_packets()), "alloc the packets' descriptors");
+        HIP_TRY(c, hipMemcpy(r->tiles.p, r->plan.tiles.data(), r->plan.bytes_tiles(), hipMemcpyHostToDevice), "upload the tiles' descriptors");
+        HIP_TRY(c, hipMemcpy(r->packets.p, r->plan.packets.data(), r->plan.bytes_packets(), hipMemcpyHostToDevice), "upload the packets' descriptors");
+        r->counters[1] += r->plan.bytes_tiles() + r->plan.bytes_packets();
+        r->info = info; r->have_plan = true;
+    }
+    const T2ReadPlan& P = r->plan;
+    const uint32_t nt = P.num_tiles;
+    // TLM's places, or where the Psot chain starts
+    bool tlm = false;
+    std::vector<uint64_t> at; std::vector<uint32_t> ln, idx;
+    uint64_t count = 0;
+    if (t2_read_tlm(r->pin, have, len, nt, &tlm, at, ln, idx, &count)) return fail(c, GRK_AMD_ERR_INVALID, t2p_text(kT2pNotLocated));
+    uint64_t sot_at = 2;
+    while (sot_at + 4 <= have && !(r->pin[sot_at] == 0xFF && r->pin[sot_at + 1] == 0x90)) sot_at += 2 + ((uint64_t)r->pin[sot_at + 2] << 8 | r->pin[sot_at + 3]);
+    const uint64_t entries = std::max<uint64_t>(P.total_packets, nt);
+    HIP_TRY(c, r->parts.ensure((size_t)nt * 32), "alloc the tile-parts' places");
+    HIP_TRY(c, r->plt_len.ensure(entries * 4), "alloc packet lengths");
+    HIP_TRY(c, r->pk_start.ensure(entries * 8), "alloc packet starts");
+    HIP_TRY(c, r->nodes.ensure(P.node_bytes + 16), "alloc tag-tree nodes");
+    HIP_TRY(c, r->rows.ensure(P.bytes_rows() + 16), "alloc the rows");
+    HIP_TRY(c, r->status.ensure(8), "alloc status");
+    T2ReadArgs a{};
+    a.cs = (const uint8_t*)d_cs; a.len = len; a.num_tiles = nt;
+    a.tiles = (const T2ReadTile*)r->tiles.p; a.packets = (const T2ReadPacket*)r->packets.p;
+    a.ht = P.ht; a.sop = P.sop; a.eph = P.eph;
+    if (tlm) {
+        std::vector<T2ReadTlmEntry> e(at.size());
+        for (size_t i = 0; i < e.size(); ++i) e[i] = T2ReadTlmEntry{at[i], ln[i], idx[i]};
+        HIP_TRY(c, r->tlm.ensure(e.size() * sizeof e[0] + 16), "alloc TLM's places");
+        if (!e.empty()) HIP_TRY(c, hipMemcpy(r->tlm.p, e.data(), e.size() * sizeof e[0], hipMemcpyHostToDevice), "upload TLM's places");
+        r->counters[1] += e.size() * sizeof e[0];
+        a.tlm = (const T2ReadTlmEntry*)r->tlm.p; a.tlm_n = (uint32_t)e.size(); a.tlm_count = count;
+    }
+    a.sot_at = sot_at;
+    uint8_t* const parts = (uint8_t*)r->parts.p;                // per tile 32 bytes: 8 + 8 + 4 + 4 + 4
+    a.part_at = (unsigned long long*)parts; a.body_at = (unsigned long long*)(parts + (size_t)nt * 8);
+    a.part_len = (uint32_t*)(parts + (size_t)nt * 16); a.has_plt = (uint32_t*)(parts + (size_t)nt * 20); a.first_of = (uint32_t*)(parts + (size_t)nt * 24);
+    a.plt_len = (uint32_t*)r->plt_len.p; a.pk_start = (unsigned long long*)r->pk_start.p;
+    a.nodes = (uint8_t*)r->nodes.p; a.rows = (grk_amd_coded_block*)r->rows.p;
+    a.status = (unsigned long long*)r->status.p; a.chains = P.chains;
+    HIP_TRY(c, hipMemsetAsync(r->status.p, 0xFF, 8, c->stream), "clear status");
+    HIP_TRY(c, launch_t2read_locate(a, c->stream), "launch KL");
+    HIP_TRY(c, launch_t2read_headers(a, c->stream), "launch KH");
+    HIP_TRY(c, launch_t2read_chains(a, c->stream), "launch KC");
+    ++r->counters[2]; r->counters[3] += P.chains;
+    int rc = ensure_pin(c, r, have + 32); if (rc) return rc;
+    uint64_t* const h_status = (uint64_t*)(r->pin + ((have + 15) & ~(uint64_t)15));
+    HIP_TRY(c, hipMemcpyAsync(h_status, r->status.p, 8, hipMemcpyDeviceToHost, c->stream), "fetch status");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    r->counters[0] += 8;
+    const uint64_t st = *h_status;
+    if (st != kT2pNoStatus) {
+        char buf[200];
+        const uint32_t why = t2p_status_why(st);
+        if (!t2p_status_is_tile(st)) std::snprintf(buf, sizeof buf, "tile-part %u: %s", t2p_status_number(st), t2p_text(why));
+        else if (t2p_status_stage(st) == 0) std::snprintf(buf, sizeof buf, "tile %u: %s", t2p_status_tile_of(st), t2p_text(why));
+        else std::snprintf(buf, sizeof buf, "tile %u %s %u: %s", t2p_status_tile_of(st), t2p_status_stage(st) == 1 ? "packet" : "block", t2p_status_number(st), t2p_text(why));
+        return fail(c, t2p_code(why), buf);
+    }
+    if (tab) {
+        *tab = StreamTable{};
+        tab->rows.resize(P.rows);
+        tab->row_at.assign(nt + 1, P.rows); tab->move_at.assign(nt + 1, 0);
+        for (uint32_t t = 0; t < nt; ++t) tab->row_at[t] = P.tiles[t].row_base;
+        tab->first_segment.assign(P.rows + 1, 0);
+        rows = tab->rows.data(); row_cap = P.rows;
+    }
+    if (!rows) return (int64_t)P.rows;
+    if (P.rows > row_cap) return fail(c, GRK_AMD_ERR_OVERFLOW, "the rows do not fit the caller's array");
+    if (P.rows) { rc = copy_d2h(c, rows, r->rows.p, P.bytes_rows()); if (rc) return rc; }
+    r->counters[0] += P.bytes_rows();
+    return (int64_t)P.rows;
+}
+
+} // namespace
+
+extern "C" int grk_amd_read_header_device(grk_amd_ctx* c, const void* d_cs, uint64_t len, grk_amd_stream_info* info)
+{
+    if (!c || !d_cs || !info) return GRK_AMD_ERR_INVALID;
+    uint64_t have = 0;
+    return header_device(c, d_cs, len, *info, &have);
+}
+
+extern "C" int64_t grk_amd_read_packets_device(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info* info, grk_amd_coded_block* rows,
+                                               uint64_t row_cap)
+{
+    if (!c || !d_cs || !info) return GRK_AMD_ERR_INVALID;
+    grk_amd_stream_info own;
+    uint64_t have = 0;
+    const int rc = header_device(c, d_cs, len, own, &have); if (rc) return rc;
+    if (std::memcmp(&own, info, sizeof own) != 0) return fail(c, GRK_AMD_ERR_INVALID, "info is not what grk_amd_read_header_device gives for this codestream");
+    return packets_device(c, d_cs, len, own, have, rows, row_cap, nullptr);
+}
+
+extern "C" uint64_t grk_amd_read_device_counters(grk_amd_ctx* c, int which)
+{
+    return c && c->rdev && which >= 0 && which < 4 ? c->rdev->counters[which] : 0;
+}
+
+extern "C" int grk_amd_decode_image_device(grk_amd_ctx* c, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device)
+{
+    if (!c || !d_cs || !pixels) return GRK_AMD_ERR_INVALID;
+    int rc = refuse_context(c, "grk_amd_decode_image_device", " at reduced resolution"); if (rc) return rc;
+    grk_amd_stream_info info;
+    uint64_t have = 0;
+    rc = header_device(c, d_cs, len, info, &have); if (rc) return rc;
+    StreamTable tab;
+    const int64_t n = packets_device(c, d_cs, len, info, have, nullptr, 0, &tab);
+    if (n < 0) return (int)n;
+    return decode_resident(c, d_cs, len, info, tab, pixels, cap, pixels_on_device);
+}

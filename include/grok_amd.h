@@ -940,6 +940,31 @@ int grk_amd_decode_image_view(grk_amd_ctx* ctx, const uint8_t* cs, uint64_t len,
 /* cumulative per context: which = 0 tiles whose packets a grk_amd_decode_image / grk_amd_decode_image_view call read, 1 codestream
  * bytes those calls uploaded */
 uint64_t grk_amd_decode_image_counters(grk_amd_ctx* ctx, int which);
+
+/* ---- a codestream that lies in DEVICE memory, read where it lies ---------------------------------------------------------------
+ * Every grk_amd_encode_*_device call leaves its file (SOC .. EOC) in device memory; so do peer and storage DMA.  These calls read
+ * such a file without bringing its body to the host: the packet headers are parsed by kernels (KL: the tile-parts located, KH: the
+ * tile-part headers with PLT, KC: the packets, one wave per chain -- with PLT a packet, without a tile).  They take files of ONE
+ * quality layer, HT or Part-1 without LAZY / TERMALL; everything else is GRK_AMD_ERR_UNSUPPORTED before any launch.  d_cs is read
+ * in the order of the context's stream; every call here but a grk_amd_decode_image_device into device pixels returns synchronised.
+ *
+ * grk_amd_read_header_device: grk_amd_read_header for such a stream.  Only the main header comes to the host: a first copy of
+ *   GRK_AMD_READ_DEVICE_FIRST_COPY bytes and, where the header is longer (a long COM, a TLM of thousands of tiles), a second copy
+ *   of the rest.  *info is what grk_amd_read_header gives for the same bytes.
+ * grk_amd_read_packets_device: grk_amd_read_packets for such a stream: the rows (HOST memory; NULL: counted only), field for field
+ *   what grk_amd_read_packets gives, or the code it gives with threads = 1; grk_amd_last_error names the tile and the packet.
+ *   One layer: no segment lists, no moves.  Returns the number of rows.
+ * grk_amd_decode_image_device: grk_amd_decode_image for such a stream: the stream is the coded buffer, nothing of its body goes
+ *   either way over the link; the rows come to the host once (grk_amd_decode_tiles takes a host table).  Pixels, layouts,
+ *   up-sampling, the int16-plane rule and the refusals on the context are grk_amd_decode_image's.
+ * grk_amd_read_device_counters: 0 bytes copied device -> host by these calls, 1 bytes copied host -> device by the reader (the
+ *   plan's descriptors, once per kind of stream; TLM's places), 2 launches of KC, 3 chains parsed. */
+#define GRK_AMD_READ_DEVICE_FIRST_COPY 4096
+int grk_amd_read_header_device(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, grk_amd_stream_info* info);
+int64_t grk_amd_read_packets_device(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, const grk_amd_stream_info* info,
+                                    grk_amd_coded_block* rows, uint64_t row_cap);
+int grk_amd_decode_image_device(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device);
+uint64_t grk_amd_read_device_counters(grk_amd_ctx* ctx, int which);
 /* The placement kernel with clipping (device pointers; queued on the context's stream): as grk_amd_place_tiles_device, but unit i
  * goes to the SIGNED position (pos[2 i], pos[2 i + 1]) of the destination's planes and only what falls inside img_w x img_h is
  * written (a unit wholly outside: nothing).  channels = 0: ncomp planes; channels != 0: the units and the destination hold

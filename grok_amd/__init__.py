@@ -12,7 +12,7 @@ from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Cont
                    ImageView, image_view_size, plan_image_view,
                    Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, SURFACE_FORMATS_MSB, surface_bytes, surface_plan,
                    PACKED_FORMATS, packed_bytes,
-                   CS_BLOCK_MSBS, DROP_SKIP, Rate, RateResult, RateAllocResult, RateError, Quality, QualityResult, QualityAllocResult, StageError, t2_max_block_bytes,
+                   CS_BLOCK_MSBS, DROP_SKIP, Rate, RateResult, RateAllocResult, RateError, Quality, QualityResult, QualityAllocResult, StageError, t2_max_block_bytes, t2_max_block_msbs,
                    ERR_UNSUPPORTED, ERR_INVALID, READ_DEVICE_FIRST_COPY)
 
 __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
@@ -22,5 +22,5 @@ __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "C
            "ImageView", "image_view_size", "plan_image_view",
            "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "SURFACE_FORMATS_MSB", "surface_bytes", "surface_plan",
            "PACKED_FORMATS", "packed_bytes",
-           "CS_BLOCK_MSBS", "DROP_SKIP", "Rate", "RateResult", "RateAllocResult", "RateError", "Quality", "QualityResult", "QualityAllocResult", "StageError", "t2_max_block_bytes",
+           "CS_BLOCK_MSBS", "DROP_SKIP", "Rate", "RateResult", "RateAllocResult", "RateError", "Quality", "QualityResult", "QualityAllocResult", "StageError", "t2_max_block_bytes", "t2_max_block_msbs",
            "ERR_UNSUPPORTED", "ERR_INVALID", "READ_DEVICE_FIRST_COPY"]

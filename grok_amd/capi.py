@@ -369,6 +369,19 @@ def lib():
             L.grk_amd_quality_last_budget.restype = f64
             L.grk_amd_quality_last_budget.argtypes = [vp]
             L.grk_amd_stage_quality_alloc.argtypes = [vp, vp, vp, vp, u64, u32, i32, f64, vp, vp]
+        if hasattr(L, "grk_amd_rate_device_counters"):   # (absent from older builds loaded through GRK_AMD_LIB for A/B timing)
+            # the rate- and quality-targeted calls that leave their file in device memory
+            PQ, PQR = C.POINTER(Quality), C.POINTER(QualityResult)
+            PV, PLy = C.POINTER(vp), C.POINTER(ImageLayout)
+            for name, args in (("grk_amd_encode_surface_rate_device", [vp, PLy, PP, vp, vp, vp, vp, u64, i32, u32, C.POINTER(Rate), PV, C.POINTER(RateResult)]),
+                               ("grk_amd_encode_surface_quality_device", [vp, PLy, PP, vp, vp, vp, vp, u64, i32, u32, PQ, PV, PQR]),
+                               ("grk_amd_encode_packed_rate_device", [vp, PLy, PP, i32, u64, vp, u64, i32, u32, C.POINTER(Rate), PV, C.POINTER(RateResult)]),
+                               ("grk_amd_encode_packed_quality_device", [vp, PLy, PP, i32, u64, vp, u64, i32, u32, PQ, PV, PQR]),
+                               ("grk_amd_assemble_rate_device", [vp, PP, u32, vp, u32, u64, vp])):
+                getattr(L, name).restype = C.c_int64
+                getattr(L, name).argtypes = args
+            L.grk_amd_rate_device_counters.restype = u64
+            L.grk_amd_rate_device_counters.argtypes = [vp, i32]
         L.grk_amd_stage_dwt_inv.argtypes = [vp, PP, u32, vp, vp]
         L.grk_amd_stage_ht_decode.argtypes = [vp, PP, u32, vp, vp, u64, vp]
         L.grk_amd_stage_ht_decode16.argtypes = [vp, PP, u32, vp, vp, u64, vp]
@@ -600,6 +613,14 @@ def t2_max_block_bytes():
     L.grk_amd_t2_max_block_bytes.restype = C.c_uint32
     L.grk_amd_t2_max_block_bytes.argtypes = []
     return int(L.grk_amd_t2_max_block_bytes())
+
+
+def t2_max_block_msbs():
+    """grk_amd_t2_max_block_msbs: the most zero bit-planes of a code-block the device writer's general tag tree takes"""
+    L = lib()
+    L.grk_amd_t2_max_block_msbs.restype = C.c_uint32
+    L.grk_amd_t2_max_block_msbs.argtypes = []
+    return int(L.grk_amd_t2_max_block_msbs())
 
 
 def write_tile_part(params, tile_index, tile_table, coded, flags=0, size_only=False):
@@ -1054,7 +1075,7 @@ class Context:
             raise RuntimeError("assemble_device failed: %d (%s)" % (n, self._L.grk_amd_last_error(self._h).decode()))
         return int(n), lens
 
-    def stage_assemble(self, params, tile_index, table, coded, flags=0):
+    def stage_assemble(self, params, tile_index, table, coded, flags=0, _fn="grk_amd_stage_assemble"):
         """Tier-2 on the device for a table of the caller's (grk_amd_stage_assemble): `table` CODED_DTYPE, len(tile_index) x (blocks of a
         tile) rows whose offsets point into `coded` (uint8; rows may share bytes) -> (bytes assembled, [tile-part lengths]); the bytes
         are fetch_assembled's.  StageError with the code and the context's reason when the call refuses."""
@@ -1062,14 +1083,19 @@ class Context:
         t = np.ascontiguousarray(table, CODED_DTYPE)
         cbuf = np.ascontiguousarray(np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else coded)
         lens = np.zeros(idx.size, np.uint32)
-        self._L.grk_amd_stage_assemble.restype = C.c_int64
-        self._L.grk_amd_stage_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
-                                                   C.c_void_p]
-        n = self._L.grk_amd_stage_assemble(self._h, C.addressof(params), idx.size, idx.ctypes.data, flags, t.ctypes.data,
-                                           cbuf.ctypes.data if cbuf.size else None, cbuf.size, lens.ctypes.data)
+        fn = getattr(self._L, _fn)
+        fn.restype = C.c_int64
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        n = fn(self._h, C.addressof(params), idx.size, idx.ctypes.data, flags, t.ctypes.data, cbuf.ctypes.data if cbuf.size else None,
+               cbuf.size, lens.ctypes.data)
         if n < 0:
-            raise StageError("stage_assemble", n, self._L.grk_amd_last_error(self._h).decode())
+            raise StageError(_fn[len("grk_amd_"):], n, self._L.grk_amd_last_error(self._h).decode())
         return int(n), lens
+
+    def stage_assemble_msbs(self, params, tile_index, table, coded, flags=0):
+        """stage_assemble with the rows' missing_msbs written (grk_amd_stage_assemble_msbs): the general zero-bit-plane tag tree, the
+        tile-parts write_tile_part writes under CS_BLOCK_MSBS (accepted in `flags`, and implied)."""
+        return self.stage_assemble(params, tile_index, table, coded, flags, _fn="grk_amd_stage_assemble_msbs")
 
     def assemble_device_async(self, params, tile_index, flags, stream_ptr):
         """grk_amd_assemble_device_async: Tier-2 of the latest encode queued on `stream_ptr`; results stay on the device."""
@@ -1300,6 +1326,65 @@ class Context:
         if n < 0:
             raise RateError("encode_packed_quality", n, self._L.grk_amd_last_error(self._h).decode())
         return out[:n].tobytes(), res
+
+    # ---- the rate- and quality-targeted calls that leave their file in device memory -> (device pointer, length, result) ----
+    def _rate_device(self, what, fn, head, goal, res):
+        d_file = C.c_void_p(0)
+        n = fn(*(head + [C.byref(goal), C.byref(d_file), C.byref(res)]))
+        if n < 0:
+            raise RateError(what, n, self._L.grk_amd_last_error(self._h).decode())
+        return int(d_file.value), int(n), res
+
+    def _surface_head(self, layout, base, sampling, surface, pixels, flags, cap):
+        dx, dy = _sampling(sampling)
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        return [self._h, C.byref(layout), C.byref(base), C.cast(dx, C.c_void_p), C.cast(dy, C.c_void_p), C.byref(surface), ptr, nbytes,
+                on_device, flags]
+
+    def _packed_head(self, layout, base, fmt, pixels, pitch, flags, cap):
+        ptr, nbytes, on_device = self._frame_arg(pixels, cap)
+        return [self._h, C.byref(layout), C.byref(base), PACKED_FORMATS.get(fmt, fmt), int(pitch), ptr, nbytes, on_device, flags]
+
+    def encode_surface_rate_device(self, layout, base, sampling, surface, pixels, target_bytes, flags=0, cap=None, max_drop=0, allow_skip=False):
+        """grk_amd_encode_surface_rate_device: encode_surface_rate with Tier-2 on the device and the file left in device memory ->
+        (device pointer, length, RateResult); the bytes belong to the context and stay valid until its next encode call"""
+        return self._rate_device("encode_surface_rate_device", self._L.grk_amd_encode_surface_rate_device,
+                                 self._surface_head(layout, base, sampling, surface, pixels, flags, cap),
+                                 Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), 1), RateResult())
+
+    def encode_surface_quality_device(self, layout, base, sampling, surface, pixels, psnr, distortion=0.0, flags=0, cap=None, max_drop=0,
+                                      allow_skip=False):
+        """grk_amd_encode_surface_quality_device -> (device pointer, length, QualityResult)"""
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        return self._rate_device("encode_surface_quality_device", self._L.grk_amd_encode_surface_quality_device,
+                                 self._surface_head(layout, base, sampling, surface, pixels, flags, cap), q, res)
+
+    def encode_packed_rate_device(self, layout, base, fmt, pixels, target_bytes, pitch=0, flags=0, cap=None, max_drop=0, allow_skip=False):
+        """grk_amd_encode_packed_rate_device -> (device pointer, length, RateResult)"""
+        return self._rate_device("encode_packed_rate_device", self._L.grk_amd_encode_packed_rate_device,
+                                 self._packed_head(layout, base, fmt, pixels, pitch, flags, cap),
+                                 Rate(int(target_bytes), int(max_drop), int(bool(allow_skip)), 1), RateResult())
+
+    def encode_packed_quality_device(self, layout, base, fmt, pixels, psnr, distortion=0.0, pitch=0, flags=0, cap=None, max_drop=0,
+                                     allow_skip=False):
+        """grk_amd_encode_packed_quality_device -> (device pointer, length, QualityResult)"""
+        q, res = self._quality(psnr, distortion, max_drop, allow_skip)
+        return self._rate_device("encode_packed_quality_device", self._L.grk_amd_encode_packed_quality_device,
+                                 self._packed_head(layout, base, fmt, pixels, pitch, flags, cap), q, res)
+
+    def rate_device_counters(self):
+        """grk_amd_rate_device_counters of the latest such call: (Tier-2 passes on the device, bytes of coded blocks copied to the host)"""
+        return tuple(int(self._L.grk_amd_rate_device_counters(self._h, k)) for k in range(2))
+
+    def assemble_rate_device(self, params, tile_index, flags=0, dst_offset=0):
+        """grk_amd_assemble_rate_device: assemble_device for the encode_tiles_rate / encode_tiles_quality call before it, the rows' zero
+        bit-planes written -> (bytes assembled, [tile-part lengths]); RateError when the latest encode was not such a call"""
+        idx = np.ascontiguousarray(np.asarray(tile_index, np.uint32))
+        lens = np.zeros(idx.size, np.uint32)
+        n = self._L.grk_amd_assemble_rate_device(self._h, C.byref(params), idx.size, idx.ctypes.data, flags, dst_offset, lens.ctypes.data)
+        if n < 0:
+            raise RateError("assemble_rate_device", n, self._L.grk_amd_last_error(self._h).decode())
+        return int(n), lens
 
     def quality_last_budget(self):
         """grk_amd_quality_last_budget: the distortion budget the quality allocator last ran with (0.0 after a rate-targeted call)"""

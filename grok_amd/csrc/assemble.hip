@@ -17,6 +17,7 @@ struct T2Source {
     uint32_t bpt;
     const uint32_t* lengths; const uint64_t* offsets; const uint8_t* arena; uint64_t arena_bytes;
     unsigned int* status;
+    const uint8_t* msbs = nullptr;    // [tile][row]: the rows' missing_msbs for the general zero-bit-plane tree (`plan` made for it); NULL: the constant one
 };
 
 // the kernels queued on `st`, which must already be ordered behind the source's tables and bytes; `o` takes the tile-parts from
@@ -44,6 +45,7 @@ int assemble_enqueue(grk_amd_ctx* c, const T2Source& src, uint32_t ntiles, const
     int rc;
     if ((rc = need(c->t2_u, (size_t)plan.u_words * 4 * ntiles + 16, "alloc header bits"))) return rc;
     if ((rc = need(c->t2_h, (size_t)plan.h_bytes * ntiles + 16, "alloc headers"))) return rc;
+    if (src.msbs && (rc = need(c->t2_nodes, (size_t)plan.v_bytes * ntiles + 16, "alloc tag-tree nodes"))) return rc;
     if ((rc = need(c->t2_rel, nblocks * 4, "alloc block places"))) return rc;
     if ((rc = need(c->t2_pkhdr, nq * 4, "alloc packet lengths"))) return rc;
     if ((rc = need(c->t2_pkbody, nq * 8, "alloc packet lengths"))) return rc;
@@ -75,6 +77,7 @@ int assemble_enqueue(grk_amd_ctx* c, const T2Source& src, uint32_t ntiles, const
     ha.hdr = (uint8_t*)c->t2_h.p; ha.h_bytes = plan.h_bytes;
     ha.rel = (uint32_t*)c->t2_rel.p; ha.pk_hdr = (uint32_t*)c->t2_pkhdr.p; ha.pk_body = (uint64_t*)c->t2_pkbody.p;
     ha.status = src.status;
+    ha.msbs = src.msbs; ha.nodes = src.msbs ? (uint8_t*)c->t2_nodes.p : nullptr; ha.v_bytes = plan.v_bytes;
     HIP_TRY(c, launch_t2_header(ha, src.max_blocks, st), "launch Tier-2 headers");
     const uint32_t sop = (flags & GRK_AMD_CS_SOP) ? 6u : 0u, eph = (flags & GRK_AMD_CS_EPH) ? 2u : 0u;
     T2FrameArgs fa{};
@@ -121,19 +124,20 @@ uint32_t plan_max_blocks(const T2Plan& plan)
 }
 
 // the plan of the context's geometry in the order of `flags` -- cached in c->t2 on the parameters and the order
-int call_plan(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t flags, hipStream_t st)
+// (msbs: the plan of the general zero-bit-plane tree, asked for by the calls that write it -- never through the flag)
+int call_plan(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t flags, hipStream_t st, bool msbs = false)
 {
     const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
-    if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
+    if (!msbs && (flags & GRK_AMD_CS_BLOCK_MSBS)) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
     auto& T = c->t2;
-    if (!T.valid || !same_params(T.p, *p) || T.order != order) {
+    if (!T.valid || !same_params(T.p, *p) || T.order != order || T.msbs != msbs) {
         T.valid = false;
-        int rc = t2_device_plan(c->geom, flags, T.plan);
+        int rc = msbs ? t2_device_plan_msbs(c->geom, flags, T.plan) : t2_device_plan(c->geom, flags, T.plan);
         if (rc) return fail(c, rc, "tile layout beyond the device writer's tables");
         T.max_blocks = plan_max_blocks(T.plan);
         // (the tables of the plan before may still be read by a gather that is queued: drained first)
         if ((rc = upload_plan(c, T.plan, T.packets, T.pob, st))) return rc;
-        T.p = *p; T.order = order; T.valid = true;
+        T.p = *p; T.order = order; T.msbs = msbs; T.valid = true;
     }
     return GRK_AMD_OK;
 }
@@ -158,13 +162,14 @@ int assemble_check(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles
     return GRK_AMD_OK;
 }
 
-// the status word's bits as an error (bits 0-1: K3's, 2: KT1's, 3: KT1b's)
+// the status word's bits as an error (bits 0-1: K3's, 2 and 4: KT1's, 3: KT1b's)
 int status_error(grk_amd_ctx* c, uint64_t word)
 {
     if (word & 1u) return fail(c, GRK_AMD_ERR_OVERFLOW, "coded arena overflow");
     if (word & 2u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "coefficient magnitude exceeds Kmax+1 bits");
     if (word & 4u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a code-block longer than the device writer takes");
     if (word & 8u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "tile-part beyond 4 GB or packet lengths beyond what PLT can carry");
+    if (word & 16u) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "a code-block with more zero bit-planes than the device writer takes");
     return GRK_AMD_OK;
 }
 
@@ -173,12 +178,12 @@ int status_error(grk_amd_ctx* c, uint64_t word)
 // made for.  A class is framed by ONE assemble_enqueue call, which wants its tiles' rows one tile after the other: the image's tables
 // therefore hold the classes one behind the other, within a class the tiles in order, within a tile the runs in order -- for an
 // image of one class (any single-tile image, any image on its grid) the order of the host writers' tables.
-int joint_plans(grk_amd_ctx* c, const JointT2Call& call)
+int joint_plans(grk_amd_ctx* c, const JointT2Call& call, bool msbs)
 {
     auto& J = c->t2j;
     const uint32_t flags = call.flags, order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, nr = call.nruns, nc = call.base->num_comps;
     const UnitGroups& g = *call.g;
-    if (J.valid && std::memcmp(&J.im, call.im, sizeof J.im) == 0 && same_params(J.base, *call.base) && J.order == order && J.dx.size() == nc &&
+    if (J.valid && J.msbs == msbs && std::memcmp(&J.im, call.im, sizeof J.im) == 0 && same_params(J.base, *call.base) && J.order == order && J.dx.size() == nc &&
         std::memcmp(J.dx.data(), call.comp_dx, nc) == 0 && std::memcmp(J.dy.data(), call.comp_dy, nc) == 0 && J.unit_row.size() == g.of.size())
         return GRK_AMD_OK;
     J.valid = false;
@@ -222,7 +227,9 @@ int joint_plans(grk_amd_ctx* c, const JointT2Call& call)
     for (auto& K : J.classes) {
         int rc = comps_of(K.tiles[0], tc);
         if (rc) return rc;
-        if ((rc = t2_device_plan_joint(tc.cg, tc.row0, call.comp_dx, call.comp_dy, tc.tile.tile_x0, tc.tile.tile_y0, flags, K.plan))) return rc;
+        // (the general zero-bit-plane tree is asked for by name, never through the flag)
+        if ((rc = msbs ? t2_device_plan_joint_msbs(tc.cg, tc.row0, call.comp_dx, call.comp_dy, tc.tile.tile_x0, tc.tile.tile_y0, flags, K.plan)
+                       : t2_device_plan_joint(tc.cg, tc.row0, call.comp_dx, call.comp_dy, tc.tile.tile_x0, tc.tile.tile_y0, flags, K.plan))) return rc;
         K.max_blocks = plan_max_blocks(K.plan);
         K.bpt = (uint32_t)K.plan.packet_of_block.size();
         K.row_begin = row;
@@ -236,7 +243,7 @@ int joint_plans(grk_amd_ctx* c, const JointT2Call& call)
         if ((rc = upload_plan(c, K.plan, K.packets, K.pob, c->stream))) return rc;
     }
     J.rows = row;
-    J.im = *call.im; J.base = *call.base; J.order = order;
+    J.im = *call.im; J.base = *call.base; J.order = order; J.msbs = msbs;
     J.dx.assign(call.comp_dx, call.comp_dx + nc); J.dy.assign(call.comp_dy, call.comp_dy + nc);
     J.valid = true;
     return GRK_AMD_OK;
@@ -262,66 +269,97 @@ bool grk_amd::image_t2_host()
     return e && std::strcmp(e, "host") == 0;
 }
 
-int64_t grk_amd::encode_joint_device(grk_amd_ctx* c, const JointT2Call& call, uint8_t* out, uint64_t cap, void** d_file)
+// ---- encode_joint_device in its three parts: plans and buffers | a batch, coded by the caller, kept | the classes framed, the file ----
+int grk_amd::joint_device_open(JointT2Run& r)
 {
-    const uint32_t flags = call.flags, nr = call.nruns;
+    grk_amd_ctx* const c = r.c;
+    const JointT2Call& call = *r.call;
+    const uint32_t nr = call.nruns;
     const UnitGroups& g = *call.g;
-    if (!nr || g.of.empty() || g.of.size() % nr || (!out && !d_file)) return GRK_AMD_ERR_INVALID;
-    const uint32_t ntiles = (uint32_t)(g.of.size() / nr);
-    // what the device writer does not reach is said before any batch is coded
-    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;
-    if ((flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
+    if (!nr || g.of.empty() || g.of.size() % nr) return GRK_AMD_ERR_INVALID;
+    r.ntiles = (uint32_t)(g.of.size() / nr);
+    if ((call.flags & GRK_AMD_CS_TLM) && r.ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
     HIP_TRY(c, hipSetDevice(c->device), "set device");
-    { const int rc = joint_plans(c, call); if (rc) return rc; }
+    { const int rc = joint_plans(c, call, r.msbs); if (rc) return rc; }
     auto& J = c->t2j;
     // the file's main header does not depend on the lengths it will carry (fixed-width TLM fields): its size now
-    std::vector<uint32_t> part_len(ntiles, 0);
-    const int64_t hdr_bytes = main_header_subsampled(call.im, call.base, call.comp_dx, call.comp_dy, flags, part_len.data(), nullptr, 0);
-    if (hdr_bytes < 0) return hdr_bytes;
-
-    // ---- every batch coded and kept (no host step between them but what grk_amd_encode_tiles has itself) ----
-    const size_t nb = call.batches.size();
-    std::vector<uint64_t> rowlist, batch_at(nb + 1, 0);
-    for (size_t b = 0; b < nb; ++b) {
+    r.part_len.assign(r.ntiles, 0);
+    r.hdr_bytes = main_header_subsampled(call.im, call.base, call.comp_dx, call.comp_dy, call.flags, r.part_len.data(), nullptr, 0);
+    if (r.hdr_bytes < 0) return (int)r.hdr_bytes;
+    r.nb = call.batches.size();
+    std::vector<uint64_t>& rowlist = r.rowlist;              // (uploaded in stream order: it lives as long as the run)
+    rowlist.clear();
+    r.batch_at.assign(r.nb + 1, 0);
+    for (size_t b = 0; b < r.nb; ++b) {
         for (uint32_t u : call.batches[b]) { if (u >= J.unit_row.size()) return GRK_AMD_ERR_INVALID; rowlist.push_back(J.unit_row[u]); }
-        batch_at[b + 1] = rowlist.size();
+        r.batch_at[b + 1] = rowlist.size();
     }
     if (rowlist.size() != g.of.size()) return GRK_AMD_ERR_INVALID;           // (every unit in exactly one batch: the sizes at least)
     // (every call of this route ends synchronised: none of these buffers is in use)
     HIP_TRY(c, c->jt_len.ensure(J.rows * 4 + 16), "alloc the image's lengths");
     HIP_TRY(c, c->jt_off.ensure(J.rows * 8 + 16), "alloc the image's offsets");
-    HIP_TRY(c, c->jt_state.ensure((nb + 1) * 8 + 16), "alloc the image's cursors");
+    if (r.msbs) HIP_TRY(c, c->jt_msbs.ensure(J.rows + 16), "alloc the image's zero bit-planes");
+    HIP_TRY(c, c->jt_state.ensure((r.nb + 1) * 8 + 16), "alloc the image's cursors");
     HIP_TRY(c, c->jt_rowat.ensure(rowlist.size() * 8 + 16), "alloc the units' rows");
-    HIP_TRY(c, hipMemsetAsync(c->jt_state.p, 0, (nb + 1) * 8 + 16, c->stream), "clear the image's cursors");
     HIP_TRY(c, hipMemcpyAsync(c->jt_rowat.p, rowlist.data(), rowlist.size() * 8, hipMemcpyHostToDevice, c->stream), "upload the units' rows");
-    unsigned long long* const cursors = (unsigned long long*)c->jt_state.p;
-    unsigned int* const status = (unsigned int*)(cursors + nb + 1);
-    uint64_t bound_at = 0;                                   // the batches' arena bounds so far: where the next one's bytes end at most
-    for (size_t b = 0; b < nb; ++b) {
-        const std::vector<uint32_t>& B = call.batches[b];
-        if (B.empty()) return GRK_AMD_ERR_INVALID;
-        const TileGeom& G = g.geoms[g.of[B[0]]];
-        const uint64_t bpu = (uint64_t)G.blocks_per_comp * G.p.num_comps;
-        int rc = call.front(b);
-        if (rc) return rc;
-        if ((rc = join_side(c))) return rc;
-        if (c->last_nblocks != bpu * B.size() || bpu >> 32) return fail(c, GRK_AMD_ERR_INVALID, "a batch's table is not its units'");
-        // the image's arena: sized from the arena K3's plan asked for -- known before the launch, never read back
-        const uint64_t ab = std::min<uint64_t>((c->last_arena_bound + 15u) & ~15ull, (uint64_t)c->arena.cap & ~15ull);
-        if ((rc = grow_keeping(c, c->jt_arena, bound_at + ab + 16, bound_at, "alloc the image's arena"))) return rc;
-        T2KeepArgs ka{};
-        ka.lengths = (const uint32_t*)c->lengths.p; ka.offsets = (const unsigned long long*)c->offsets.p;
-        ka.arena = (const uint8_t*)c->arena.p; ka.arena_bound = ab;
-        ka.batch_state = (const unsigned long long*)c->flag.p;
-        ka.nunits = (uint32_t)B.size(); ka.bpu = (uint32_t)bpu;
-        ka.row_at = (const unsigned long long*)c->jt_rowat.p + batch_at[b];
-        ka.j_lengths = (uint32_t*)c->jt_len.p; ka.j_offsets = (unsigned long long*)c->jt_off.p;
-        ka.j_arena = (uint8_t*)c->jt_arena.p; ka.j_cap = bound_at + ab;
-        ka.cursors = cursors + b; ka.status = status;
-        HIP_TRY(c, launch_t2_keep(ka, c->stream), "launch keep");
-        bound_at += ab;
-    }
+    return joint_device_reset(r);
+}
 
+// the image's cursors and status word at zero: before the first batch of the image -- or of a round that codes every batch again
+int grk_amd::joint_device_reset(JointT2Run& r)
+{
+    grk_amd_ctx* const c = r.c;
+    HIP_TRY(c, hipMemsetAsync(c->jt_state.p, 0, (r.nb + 1) * 8 + 16, c->stream), "clear the image's cursors");
+    r.bound_at = 0;
+    return GRK_AMD_OK;
+}
+
+// batch b, which the caller has just coded (its table, bytes and -- a launch with drops -- drop bytes are the context's), kept: KK
+int grk_amd::joint_device_keep(JointT2Run& r, size_t b)
+{
+    grk_amd_ctx* const c = r.c;
+    const JointT2Call& call = *r.call;
+    const UnitGroups& g = *call.g;
+    const std::vector<uint32_t>& B = call.batches[b];
+    if (B.empty()) return GRK_AMD_ERR_INVALID;
+    const TileGeom& G = g.geoms[g.of[B[0]]];
+    const uint64_t bpu = (uint64_t)G.blocks_per_comp * G.p.num_comps;
+    unsigned long long* const cursors = (unsigned long long*)c->jt_state.p;
+    int rc;
+    if ((rc = join_side(c))) return rc;
+    if (c->last_nblocks != bpu * B.size() || bpu >> 32) return fail(c, GRK_AMD_ERR_INVALID, "a batch's table is not its units'");
+    // the image's arena: sized from the arena K3's plan asked for -- known before the launch, never read back
+    const uint64_t ab = std::min<uint64_t>((c->last_arena_bound + 15u) & ~15ull, (uint64_t)c->arena.cap & ~15ull);
+    if ((rc = grow_keeping(c, c->jt_arena, r.bound_at + ab + 16, r.bound_at, "alloc the image's arena"))) return rc;
+    T2KeepArgs ka{};
+    ka.lengths = (const uint32_t*)c->lengths.p; ka.offsets = (const unsigned long long*)c->offsets.p;
+    ka.arena = (const uint8_t*)c->arena.p; ka.arena_bound = ab;
+    ka.batch_state = (const unsigned long long*)c->flag.p;
+    ka.nunits = (uint32_t)B.size(); ka.bpu = (uint32_t)bpu;
+    ka.row_at = (const unsigned long long*)c->jt_rowat.p + r.batch_at[b];
+    ka.j_lengths = (uint32_t*)c->jt_len.p; ka.j_offsets = (unsigned long long*)c->jt_off.p;
+    ka.j_arena = (uint8_t*)c->jt_arena.p; ka.j_cap = r.bound_at + ab;
+    ka.cursors = cursors + b; ka.status = (unsigned int*)(cursors + r.nb + 1);
+    if (r.msbs) {
+        // the rows' zero bit-planes from the drops the batch was coded with (a plain launch: none dropped), under the batch's own Kmax
+        ka.drops = c->last_drops; ka.blocks = (const HtBlockDesc*)c->blockdesc.p; ka.j_msbs = (uint8_t*)c->jt_msbs.p;
+    }
+    HIP_TRY(c, launch_t2_keep(ka, c->stream), "launch keep");
+    r.bound_at += ab;
+    return GRK_AMD_OK;
+}
+
+int64_t grk_amd::joint_device_finish(JointT2Run& r, uint8_t* out, uint64_t cap, void** d_file)
+{
+    grk_amd_ctx* const c = r.c;
+    const JointT2Call& call = *r.call;
+    const uint32_t flags = call.flags, ntiles = r.ntiles;
+    const int64_t hdr_bytes = r.hdr_bytes;
+    const uint64_t bound_at = r.bound_at;
+    std::vector<uint32_t>& part_len = r.part_len;
+    auto& J = c->t2j;
+    unsigned int* const status = (unsigned int*)((unsigned long long*)c->jt_state.p + r.nb + 1);
+    if (!out && !d_file) return GRK_AMD_ERR_INVALID;
     // ---- the tile-parts, class by class, each behind the one before ----
     // a file in device memory is assembled in place behind its header when the classes' tile-parts come in the file's order
     bool in_order = true;
@@ -334,7 +372,8 @@ int64_t grk_amd::encode_joint_device(grk_amd_ctx* c, const JointT2Call& call, ui
     uint32_t status_word = 0;
     for (const auto& K : J.classes) {
         const T2Source src{&K.plan, K.max_blocks, K.packets.p, K.pob.p, K.bpt, (const uint32_t*)c->jt_len.p + K.row_begin,
-                           (const uint64_t*)c->jt_off.p + K.row_begin, (const uint8_t*)c->jt_arena.p, bound_at, status};
+                           (const uint64_t*)c->jt_off.p + K.row_begin, (const uint8_t*)c->jt_arena.p, bound_at, status,
+                           r.msbs ? (const uint8_t*)c->jt_msbs.p + K.row_begin : nullptr};
         const int rc = assemble_enqueue(c, src, (uint32_t)K.tiles.size(), K.tiles.data(), flags, used, c->stream, o);
         if (rc) return rc;
         // only the tile-parts' lengths (and the status word) come to the host
@@ -360,7 +399,6 @@ int64_t grk_amd::encode_joint_device(grk_amd_ctx* c, const JointT2Call& call, ui
             }
             return GRK_AMD_OK;
         }, call.comp_dx, call.comp_dy);
-        if (n >= 0) ++c->route_counters[0];
         return n;
     }
     // the file on the device: the header -- written now that the lengths are known -- and EOC around the tile-parts
@@ -383,8 +421,26 @@ int64_t grk_amd::encode_joint_device(grk_amd_ctx* c, const JointT2Call& call, ui
     HIP_TRY(c, hipMemcpyAsync(file + hdr_bytes + body, eoc, 2, hipMemcpyHostToDevice, c->stream), "upload EOC");
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
     *d_file = file;
-    ++c->route_counters[0];
     return (int64_t)total;
+}
+
+int64_t grk_amd::encode_joint_device(grk_amd_ctx* c, const JointT2Call& call, uint8_t* out, uint64_t cap, void** d_file)
+{
+    if (!out && !d_file) return GRK_AMD_ERR_INVALID;
+    // what the device writer does not reach is said before any batch is coded
+    if (call.flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;
+    JointT2Run r{c, &call, false};
+    { const int rc = joint_device_open(r); if (rc) return rc; }
+    // ---- every batch coded and kept (no host step between them but what grk_amd_encode_tiles has itself) ----
+    for (size_t b = 0; b < r.nb; ++b) {
+        if (call.batches[b].empty()) return GRK_AMD_ERR_INVALID;
+        int rc = call.front(b);
+        if (rc) return rc;
+        if ((rc = joint_device_keep(r, b))) return rc;
+    }
+    const int64_t n = joint_device_finish(r, out, cap, d_file);
+    if (n >= 0) ++c->route_counters[0];
+    return n;
 }
 
 extern "C" {
@@ -414,39 +470,84 @@ int64_t grk_amd_assemble_device(grk_amd_ctx* c, const grk_amd_tile_params* p, ui
     return (int64_t)total[0];
 }
 
+// grk_amd_assemble_device for the grk_amd_encode_tiles_rate / _quality call before it (any launch of the block coder's drop instances):
+// the rows' zero bit-planes are written, made on the device from the context's copy of the drop bytes the blocks were coded with --
+// those calls are identity runs, the drops are in table order.  GRK_AMD_ERR_INVALID when the latest encode took no drops.
+int64_t grk_amd_assemble_rate_device(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
+                                     uint64_t dst_offset, uint32_t* part_bytes)
+{
+    { const int rc = assemble_check(c, p, ntiles, tile_index); if (rc) return rc; }
+    if (!c->last_drops) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_assemble_rate_device assembles a rate- or quality-targeted grk_amd_encode_tiles call: the latest encode dropped nothing");
+    if (dst_offset > c->t2_out_used) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_assemble_rate_device: dst_offset lies behind what has been assembled");
+    HIP_TRY(c, hipSetDevice(c->device), "set device");
+    { const int jr = join_side(c); if (jr) return jr; }
+    flags &= ~(uint32_t)GRK_AMD_CS_BLOCK_MSBS;                                // (accepted and implied)
+    { const int rc = call_plan(c, p, flags, c->stream, true); if (rc) return rc; }
+    auto& T = c->t2;
+    const uint32_t bpt = (uint32_t)(c->last_nblocks / ntiles);
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");                      // (st_msbs may still be read by an earlier call)
+    HIP_TRY(c, c->st_msbs.ensure(c->last_nblocks + 16), "alloc zero bit-planes");
+    HIP_TRY(c, launch_t2_drop_msbs(c->last_drops, (const HtBlockDesc*)c->blockdesc.p, bpt, c->last_nblocks, (uint8_t*)c->st_msbs.p, c->stream), "launch zero bit-planes");
+    const T2Source src{&T.plan, T.max_blocks, T.packets.p, T.pob.p, bpt, (const uint32_t*)c->lengths.p, (const uint64_t*)c->offsets.p,
+                       (const uint8_t*)c->arena.p, (uint64_t)c->arena.cap, (unsigned int*)c->flag.p, (const uint8_t*)c->st_msbs.p};
+    auto& o = c->t2_outs[c->t2_cur];
+    { const int rc = assemble_enqueue(c, src, ntiles, tile_index, flags, dst_offset, c->stream, o); if (rc) return rc; }
+    uint64_t flagwords[2] = {0, 0}, total[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(flagwords, c->flag.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch flag");
+    HIP_TRY(c, hipMemcpyAsync(total, o.total.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch total");
+    if (part_bytes) HIP_TRY(c, hipMemcpyAsync(part_bytes, o.part_len.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    { const int se = status_error(c, flagwords[0]); if (se) return se; }
+    c->t2_out_used = total[1];
+    return (int64_t)total[0];
+}
+
 // Tier-2 on the device for a table of the caller's choosing (the stage call of KT1 / KT1b / KT2, as grk_amd_stage_ht_encode16 is
 // K3's): `table` holds num_tiles x (blocks of a tile) rows in the order of grk_amd_fetch_table, whose offsets point into the `coded`
 // bytes -- rows may share bytes.  Everything is checked on the host before anything is launched; the tile-parts are read with
 // grk_amd_fetch_assembled.  The rows and bytes go to buffers of their own: the latest grk_amd_encode_tiles call stays assemblable.
-int64_t grk_amd_stage_assemble(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
-                               const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes, uint32_t* part_bytes)
+// (msbs: grk_amd_stage_assemble_msbs, `who` -- the rows' missing_msbs are written, through the general zero-bit-plane tree)
+static int64_t stage_assemble_any(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
+                                  const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes, uint32_t* part_bytes,
+                                  bool msbs, const char* who)
 {
+    char msg[200];
     if (!c || !p || !ntiles || !tile_index || !table || (!coded && coded_bytes)) return GRK_AMD_ERR_INVALID;
+    if (msbs) flags &= ~(uint32_t)GRK_AMD_CS_BLOCK_MSBS;                      // (accepted and implied)
     if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_stage_assemble: per-block zero bit-planes: the host writers only");
     for (uint32_t i = 0; i < ntiles; ++i)
-        if (tile_index[i] > 65535u) return fail(c, GRK_AMD_ERR_INVALID, "grk_amd_stage_assemble: a tile index beyond 65 535 (Isot is 16 bits)");
+        if (tile_index[i] > 65535u) {
+            std::snprintf(msg, sizeof msg, "%s: a tile index beyond 65 535 (Isot is 16 bits)", who);
+            return fail(c, GRK_AMD_ERR_INVALID, msg);
+        }
     { const int rc = stage_enter(c, p, true, true); if (rc) return rc; }
     const uint64_t bpt = (uint64_t)c->geom.blocks_per_comp * p->num_comps, rows = bpt * ntiles;
-    if (bpt >> 32) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_stage_assemble: tile layout beyond the device writer's tables");
+    if (bpt >> 32) { std::snprintf(msg, sizeof msg, "%s: tile layout beyond the device writer's tables", who); return fail(c, GRK_AMD_ERR_UNSUPPORTED, msg); }
     std::vector<uint32_t> h_len(rows);
     std::vector<uint64_t> h_off(rows);
+    std::vector<uint8_t> h_msbs(msbs ? rows : 0);
     uint64_t sum = 0;
-    char msg[160];
     for (uint64_t i = 0; i < rows; ++i) {
         const grk_amd_coded_block& r = table[i];
         if (!t2_len_ok(r.length)) {
-            std::snprintf(msg, sizeof msg, "grk_amd_stage_assemble: row %llu: a length of %u bytes, the device writer takes less than %u",
-                          (unsigned long long)i, r.length, 1u << kT2MaxLenBits);
+            std::snprintf(msg, sizeof msg, "%s: row %llu: a length of %u bytes, the device writer takes less than %u",
+                          who, (unsigned long long)i, r.length, 1u << kT2MaxLenBits);
             return fail(c, GRK_AMD_ERR_UNSUPPORTED, msg);
         }
         if (r.offset > coded_bytes || r.length > coded_bytes - r.offset) {
-            std::snprintf(msg, sizeof msg, "grk_amd_stage_assemble: row %llu: offset %llu + length %u lies beyond the %llu coded bytes",
-                          (unsigned long long)i, (unsigned long long)r.offset, r.length, (unsigned long long)coded_bytes);
+            std::snprintf(msg, sizeof msg, "%s: row %llu: offset %llu + length %u lies beyond the %llu coded bytes",
+                          who, (unsigned long long)i, (unsigned long long)r.offset, r.length, (unsigned long long)coded_bytes);
             return fail(c, GRK_AMD_ERR_INVALID, msg);
         }
+        if (msbs && r.missing_msbs > kT2MaxMsbs) {
+            std::snprintf(msg, sizeof msg, "%s: row %llu: %u zero bit-planes, the device writer takes at most %u",
+                          who, (unsigned long long)i, r.missing_msbs, kT2MaxMsbs);
+            return fail(c, GRK_AMD_ERR_UNSUPPORTED, msg);
+        }
         h_len[i] = r.length; h_off[i] = r.offset; sum += r.length;
+        if (msbs) h_msbs[i] = (uint8_t)r.missing_msbs;
     }
-    { const int rc = call_plan(c, p, flags, c->stream); if (rc) return rc; }
+    { const int rc = call_plan(c, p, flags, c->stream, msbs); if (rc) return rc; }
     // (no call of this entry leaves work behind: the buffers are free)
     HIP_TRY(c, c->st_len.ensure(rows * 4 + 16), "alloc the stage's lengths");
     HIP_TRY(c, c->st_off.ensure(rows * 8 + 16), "alloc the stage's offsets");
@@ -454,12 +555,16 @@ int64_t grk_amd_stage_assemble(grk_amd_ctx* c, const grk_amd_tile_params* p, uin
     HIP_TRY(c, c->st_status.ensure(16), "alloc the stage's status word");
     HIP_TRY(c, hipMemcpyAsync(c->st_len.p, h_len.data(), rows * 4, hipMemcpyHostToDevice, c->stream), "upload lengths");
     HIP_TRY(c, hipMemcpyAsync(c->st_off.p, h_off.data(), rows * 8, hipMemcpyHostToDevice, c->stream), "upload offsets");
+    if (msbs) {
+        HIP_TRY(c, c->st_msbs.ensure(rows + 16), "alloc the stage's zero bit-planes");
+        HIP_TRY(c, hipMemcpyAsync(c->st_msbs.p, h_msbs.data(), rows, hipMemcpyHostToDevice, c->stream), "upload zero bit-planes");
+    }
     if (coded_bytes) { const int rc = copy_h2d(c, c->st_arena.p, coded, coded_bytes); if (rc) return rc; }
     HIP_TRY(c, hipMemsetAsync(c->st_status.p, 0, 16, c->stream), "clear status");
     auto& T = c->t2;
     // (rows may share bytes: what the call writes is bounded by the sum of the lengths, not by the bytes they point into)
     const T2Source src{&T.plan, T.max_blocks, T.packets.p, T.pob.p, (uint32_t)bpt, (const uint32_t*)c->st_len.p, (const uint64_t*)c->st_off.p,
-                       (const uint8_t*)c->st_arena.p, sum, (unsigned int*)c->st_status.p};
+                       (const uint8_t*)c->st_arena.p, sum, (unsigned int*)c->st_status.p, msbs ? (const uint8_t*)c->st_msbs.p : nullptr};
     auto& o = c->t2_outs[c->t2_cur];
     c->t2_out_used = 0;
     { const int rc = assemble_enqueue(c, src, ntiles, tile_index, flags, 0, c->stream, o); if (rc) return rc; }
@@ -474,6 +579,22 @@ int64_t grk_amd_stage_assemble(grk_amd_ctx* c, const grk_amd_tile_params* p, uin
     return (int64_t)total[0];
 }
 
+int64_t grk_amd_stage_assemble(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
+                               const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes, uint32_t* part_bytes)
+{
+    return stage_assemble_any(c, p, ntiles, tile_index, flags, table, coded, coded_bytes, part_bytes, false, "grk_amd_stage_assemble");
+}
+
+// The same with the rows' missing_msbs written: the zero-bit-plane tag trees in their general form (KT1's instance of it), what
+// grk_amd_write_tile_part writes under GRK_AMD_CS_BLOCK_MSBS -- the flag is accepted here and implied.  The same host checks before
+// any launch, and GRK_AMD_ERR_UNSUPPORTED for a row above grk_amd_t2_max_block_msbs().
+int64_t grk_amd_stage_assemble_msbs(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
+                                    const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes, uint32_t* part_bytes)
+{
+    return stage_assemble_any(c, p, ntiles, tile_index, flags, table, coded, coded_bytes, part_bytes, true, "grk_amd_stage_assemble_msbs");
+}
+
+uint32_t grk_amd_t2_max_block_msbs(void) { return kT2MaxMsbs; }
 uint32_t grk_amd_t2_max_block_bytes(void) { return (1u << kT2MaxLenBits) - 1u; }
 
 // The same without the host: queued on `hip_stream` (made to wait for the encode's results first, as grk_amd_stream_wait_results does),

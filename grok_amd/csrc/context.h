@@ -145,10 +145,12 @@ struct grk_amd_ctx {
     // finished tile-parts
     struct T2State {
         bool valid = false; grk_amd_tile_params p{}; uint32_t order = 0;
+        bool msbs = false;                                   // the plan of the general zero-bit-plane tree (t2_device_plan_msbs)
         T2Plan plan; uint32_t max_blocks = 0;
         DevBuf packets, pob;
     } t2;
     DevBuf t2_u, t2_h, t2_rel, t2_pkhdr, t2_pkbody, t2_pkdst, t2_lit, t2_litlen, t2_index;      // scratch: ONE stream at a time uses it
+    DevBuf t2_nodes;                                         // ... the general zero-bit-plane tree's node values (T2Plan::v_bytes per tile)
     // the finished tile-parts, their places and lengths ([tile]: uint64 / uint32) and {bytes assembled by the call, end of the output};
     // the asynchronous form rotates as many of these as the encoder rotates buffer sets, so that a frame's tile-parts stay where they
     // are while an exchange sends them
@@ -163,14 +165,17 @@ struct grk_amd_ctx {
     // grk_amd_encode_*_device call whose tile classes do not lie in tile order
     struct T2Joint {
         bool valid = false; grk_amd_image_layout im{}; grk_amd_tile_params base{}; std::vector<uint8_t> dx, dy; uint32_t order = 0;
+        bool msbs = false;                                   // the classes' plans are those of the general zero-bit-plane tree
         struct Class { T2Plan plan; uint32_t max_blocks = 0, bpt = 0; uint64_t row_begin = 0; std::vector<uint32_t> tiles; DevBuf packets, pob; };
         std::vector<Class> classes;
         std::vector<uint64_t> unit_row;                      // [unit]: its first row in the image's tables (class-major, see assemble.hip)
         uint64_t rows = 0;
     } t2j;
-    DevBuf jt_len, jt_off, jt_arena, jt_state, jt_rowat, jt_file;
+    DevBuf jt_len, jt_off, jt_arena, jt_state, jt_rowat, jt_file, jt_msbs;
     DevBuf st_len, st_off, st_arena, st_status;              // grk_amd_stage_assemble: the caller's rows and coded bytes, the call's status word
+    DevBuf st_msbs;                                          // grk_amd_stage_assemble_msbs: the rows' missing_msbs, a byte each
     DevBuf st_rL, st_rE, st_rW, st_rdrop, st_rres, st_rmap;  // grk_amd_stage_rate_stats / _alloc: the caller's tables, apart from rate_*
+    uint64_t rate_dev_counters[2] = {0, 0};                // the latest rate- / quality-targeted _device call: Tier-2 passes on the device, coded bytes fetched
     uint64_t route_counters[2] = {0, 0};                   // images assembled on the device / written by the host writer (grk_amd_encode_route_counters)
     uint64_t last_arena_bound = 0;                           // the arena K3's plan asked for in the latest call (plan_ht_arena), <= arena.cap
     std::vector<uint64_t> h_off;
@@ -300,7 +305,8 @@ int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const
 int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                                 const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
                                 uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result,
-                                const grk_amd::QualityGoal* quality = nullptr);   // surface.cpp (quality: image.h, RateJointCall)
+                                const grk_amd::QualityGoal* quality = nullptr, void** d_file = nullptr);   // surface.cpp (quality: image.h,
+                                // RateJointCall; d_file != nullptr: the _device twins -- Tier-2 on the device, `out` / `out_cap` are not used)
 // grk_amd_decode_surface behind its null checks (`name`: the entry point, for a refusal's text); host_rules: a device surface under
 // the rules of a host destination -- a group that leaves the int16 planes is repeated by the call itself
 int decode_onto_surface(grk_amd_ctx* c, const char* name, const uint8_t* cs, uint64_t len, const grk_amd_surface* surface, void* pixels,

@@ -111,7 +111,7 @@ inline double quality_psnr(double signal, double distortion) { return distortion
 uint64_t quality_samples(const grk_amd_image_layout& im, uint32_t num_comps, const uint8_t* comp_dx, const uint8_t* comp_dy);
 // the drop byte of candidate c, and the row's zero bit-planes for a drop byte (d clamped to Kmax - 1; SKIP: Kmax - 1)
 inline uint8_t rate_drop_byte(uint32_t c, uint32_t dmax) { return c <= dmax ? (uint8_t)c : (uint8_t)kHtDropSkip; }
-inline uint32_t drop_missing_msbs(uint32_t kmax, uint32_t drop)
+GRK_T2_FN uint32_t drop_missing_msbs(uint32_t kmax, uint32_t drop)
 {
     const uint32_t top = kmax ? kmax - 1u : 0u;
     return drop == kHtDropSkip ? top : top - (drop < top ? drop : top);

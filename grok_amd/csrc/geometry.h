@@ -93,14 +93,18 @@ struct T2Packet {
     uint32_t first_block[3], gw[3], gh[3], kmax[3], height[3];
     uint32_t u_at, u_words;           // raw header bits: 32-bit words of the tile's scratch
     uint32_t h_at;                    // stuffed header: bytes of the tile's header scratch
+    uint32_t v_at;                    // the general zero-bit-plane tree's node values, band after band: bytes of the tile's node scratch
 };
 struct T2Plan {
     std::vector<T2Packet> packets;
     std::vector<uint32_t> packet_of_block;        // [rows of a tile]
     uint32_t u_words = 0, h_bytes = 0;            // scratch per tile
+    uint32_t v_bytes = 0;                         // ... and, in a plan of the general tree alone, for the node values
 };
 // (kT2MaxLenBits, the block lengths the device writer takes, and kT2MaxHeight: t2_bits.h)
 int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out);
+// the plan of the general zero-bit-plane tree (t2_order.h: t2_device_plan_joint_msbs) of a tile without sub-sampling
+int t2_device_plan_msbs(const TileGeom& g, uint32_t flags, T2Plan& out);
 inline uint32_t ceil_div_pow2(uint32_t v, uint32_t n) { return (uint32_t)(((uint64_t)v + (1ull << n) - 1) >> n); }
 
 } // namespace grk_amd

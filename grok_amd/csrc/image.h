@@ -116,6 +116,25 @@ struct JointT2Call {
     std::function<int(size_t b)> front;
 };
 int64_t encode_joint_device(grk_amd_ctx* ctx, const JointT2Call& call, uint8_t* out, uint64_t cap, void** d_file);
+// encode_joint_device in its three parts, for a caller that codes the batches itself -- the rate- and quality-targeted calls that leave
+// their file in device memory (rate.hip: every round codes every batch again, with the drops the allocator chose):
+//   joint_device_open     the classes' plans and the image's buffers, the cursors at zero
+//   joint_device_reset    the cursors at zero again: before a further round's first batch
+//   joint_device_keep     batch b, just coded by the caller, kept in the image's tables and arena (KK)
+//   joint_device_finish   the classes framed, the file delivered as encode_joint_device delivers it
+// msbs: the rows' zero bit-planes are written -- KK makes them from the drops a batch was coded with, KT1's general instance writes
+// their tag trees (plans of t2_device_plan_joint_msbs); asked for here, never through GRK_AMD_CS_BLOCK_MSBS in call.flags.
+struct JointT2Run {
+    grk_amd_ctx* c; const JointT2Call* call; bool msbs;
+    uint32_t ntiles = 0; size_t nb = 0; int64_t hdr_bytes = 0;
+    std::vector<uint64_t> rowlist{}, batch_at{};
+    uint64_t bound_at = 0;                                   // the kept batches' arena bounds so far
+    std::vector<uint32_t> part_len{};
+};
+int joint_device_open(JointT2Run& r);
+int joint_device_reset(JointT2Run& r);
+int joint_device_keep(JointT2Run& r, size_t b);
+int64_t joint_device_finish(JointT2Run& r, uint8_t* out, uint64_t cap, void** d_file);
 // GRK_AMD_IMAGE_T2=host, read per call: the whole-image encoders write their files with the host writer
 bool image_t2_host();
 
@@ -163,6 +182,13 @@ struct QualityTarget { grk_amd_rate rate; QualityGoal goal; };
 int quality_target(grk_amd_ctx* ctx, const grk_amd_quality* quality, uint32_t prec, uint64_t samples, grk_amd_quality_result* result,
                    QualityTarget& out);
 int64_t encode_rate_joint(grk_amd_ctx* ctx, const RateJointCall& call, uint8_t* out, uint64_t cap, grk_amd_rate_result* result);
+// The same call with Tier-2 on the device and the file left in device memory (*d_file: SOC .. EOC, the context's, valid until its next
+// encode call): the run drives the parts of encode_joint_device (JointT2Run with msbs) in place of code_all / merge -- per round the
+// image's cursors reset, every batch coded with its slice of the drops and kept by KK with its rows' zero bit-planes, the classes framed.
+// A round's file length is the device's total; the plain file is sized on the host from the plain rows (call.write with out == nullptr
+// and no coded bytes).  Budgets and results are encode_rate_joint's.  t2: the image as encode_joint_device takes it, its batches the
+// units of call.batches in the same order (t2.front is not used: the run codes).  No coded byte comes to the host.
+int64_t encode_rate_joint_device(grk_amd_ctx* ctx, const RateJointCall& call, const JointT2Call& t2, void** d_file, grk_amd_rate_result* result);
 
 // fn(i) for i in [0, n) on up to `threads` host threads, the caller's among them; items are handed out by a counter and the
 // first error wins (no item starts after it)

@@ -314,6 +314,9 @@ struct T2HeaderArgs {
     uint32_t* rel;                                   // [tile][row]: the block's offset in its packet's body
     uint32_t* pk_hdr; uint64_t* pk_body;             // [tile][packet]: header / body bytes
     unsigned int* status;                            // bit 2: a block length the writer does not take (>= 2^kT2MaxLenBits)
+    // the general zero-bit-plane tree (NULL: the constant one): the rows' missing_msbs, [tile][row], and the node values' scratch,
+    // per tile (T2Plan::v_bytes of a plan made for it).  Bit 4 of *status: a row above kT2MaxMsbs, written as if it were at it
+    const uint8_t* msbs; uint8_t* nodes; uint32_t v_bytes;
 };
 hipError_t launch_t2_header(const T2HeaderArgs& a, uint32_t max_blocks_per_packet, hipStream_t s);
 struct T2FrameArgs {
@@ -360,8 +363,14 @@ struct T2KeepArgs {
     unsigned long long* cursors;                     // [0] where this batch's bytes go (a multiple of 16), [1] written: where the next one's go
     unsigned int* status;                            // the image's status word: the batches' OR-ed
     uint32_t grid;                                   // set by the launcher: workgroups
+    // j_msbs != NULL: the rows' zero bit-planes as well, a byte each -- drop_missing_msbs (encode_plan.h) of the drop bytes the batch
+    // was coded with (batch order; NULL: a plain launch, nothing dropped) under the Kmax of the batch's block descriptors [bpu]
+    const uint8_t* drops; const HtBlockDesc* blocks; uint8_t* j_msbs;
 };
 hipError_t launch_t2_keep(const T2KeepArgs& a, hipStream_t s);
+// msbs[i] = the zero bit-planes of row i of a table of n rows, bpt per tile, coded with drops[i] (as KK makes them): for a call whose
+// rows stay where the block coder left them (grk_amd_assemble_rate_device)
+hipError_t launch_t2_drop_msbs(const uint8_t* drops, const HtBlockDesc* blocks, uint32_t bpt, uint64_t n, uint8_t* msbs, hipStream_t s);
 
 // ---- KG / KP: the device's share of reading a whole codestream (kernels_t2dec.hip) ----------------------------------------------
 // KG: moves[i] = len bytes from src + moves[i].src to dst + moves[i].dst (the host checked them against both buffers)

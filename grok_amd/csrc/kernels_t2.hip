@@ -75,7 +75,11 @@ struct ChainWalk {
 
 } // namespace
 
-template <uint32_t kWinWords>
+// kMsbs: the instance of the general zero-bit-plane tree (a.msbs: every row's own missing_msbs).  A phase in front of step 1 builds
+// the packet's trees in global scratch (a.nodes; per band level 0 = the rows' values, every level above the minimum of up to 2 x 2
+// children, one byte per node): a one-precinct 8K tile's packet has 49 152 blocks, whose nodes do not fit static LDS beside the
+// windows.  Step 1 then reads a block's path from them (t2_bits.h: t2_block_bits_msbs).
+template <uint32_t kWinWords, bool kMsbs = false>
 __global__ __launch_bounds__(1024) void t2_header_kernel(T2HeaderArgs a)
 {
     constexpr uint32_t kWinBits = kWinWords * 32, kWinChunks = kWinBits / kChunkBits, kWinSups = kWinChunks / kSup;
@@ -100,15 +104,61 @@ __global__ __launch_bounds__(1024) void t2_header_kernel(T2HeaderArgs a)
     const size_t row_base = (size_t)tile * a.bpt + Pp->row0;
     const uint32_t n0 = nbands > 0 ? gw0 * Pp->gh[0] : 0u, n1 = nbands > 1 ? gw1 * Pp->gh[1] : 0u;
 
+    // ---- 0. (general tree) the bands' node values, level by level ------------------------------------------------------------
+    bool bad = false, deep = false;
+    uint8_t* const nodes = kMsbs ? a.nodes + (size_t)tile * a.v_bytes + Pp->v_at : nullptr;
+    // a band's nodes lie behind those of the bands before it
+    const uint32_t gh0 = Pp->gh[0], gh1 = Pp->gh[1], gh2 = Pp->gh[2];
+    const uint32_t nd1 = kMsbs && nbands > 0 ? (uint32_t)t2_tree_nodes(gw0, gh0) : 0u;
+    const uint32_t nd2 = kMsbs && nbands > 1 ? nd1 + (uint32_t)t2_tree_nodes(gw1, gh1) : 0u;
+    if constexpr (kMsbs) {
+        const uint8_t* const mv = a.msbs + row_base;
+        for (uint32_t j = tid; j < P.nblocks; j += nthr) {
+            const uint32_t b = (j >= n0) + (j >= n0 + n1);
+            const uint32_t k = j - (b == 0 ? 0u : b == 1 ? n0 : n0 + n1);
+            uint32_t v = mv[(b == 0 ? fb0 : b == 1 ? fb1 : fb2) + k];
+            if (v > kT2MaxMsbs) { deep = true; v = kT2MaxMsbs; }    // (written as if it were at the limit: nothing is indexed by more)
+            __hip_atomic_store(nodes + (b == 0 ? 0u : b == 1 ? nd1 : nd2) + k, (uint8_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        const uint32_t hmax = max(ht0, max(nbands > 1 ? ht1 : 0u, nbands > 2 ? ht2 : 0u));
+        for (uint32_t l = 1; l < hmax; ++l) {                       // (uniform: the heights are the packet's)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            for (uint32_t b = 0; b < nbands; ++b) {
+                if (l >= (b == 0 ? ht0 : b == 1 ? ht1 : ht2)) continue;
+                // level l - 1: cw x ch at `from`; level l: w x h behind it
+                uint32_t cw = b == 0 ? gw0 : b == 1 ? gw1 : gw2, ch = b == 0 ? gh0 : b == 1 ? gh1 : gh2;
+                uint32_t from = b == 0 ? 0u : b == 1 ? nd1 : nd2;
+                for (uint32_t i = 1; i < l; ++i) { from += cw * ch; cw = (cw + 1u) >> 1; ch = (ch + 1u) >> 1; }
+                const uint32_t w = (cw + 1u) >> 1, h = (ch + 1u) >> 1, to = from + cw * ch;
+                for (uint32_t i = tid; i < w * h; i += nthr) {
+                    const uint32_t x = 2u * (i % w), y = 2u * (i / w);
+                    const uint8_t* const c0 = nodes + from + y * cw + x;
+                    uint32_t v = __hip_atomic_load(c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (x + 1u < cw) v = min(v, (uint32_t)__hip_atomic_load(c0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                    if (y + 1u < ch) {
+                        v = min(v, (uint32_t)__hip_atomic_load(c0 + cw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                        if (x + 1u < cw) v = min(v, (uint32_t)__hip_atomic_load(c0 + cw + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                    }
+                    __hip_atomic_store(nodes + to + i, (uint8_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+
     // ---- 1. the blocks' bit strings at their places in the raw header ------------------------------------------------------
     uint64_t carry = 1ull << 40;                                  // the packet's first bit: "not empty"
     if (tid == 0) __hip_atomic_fetch_or(u, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    bool bad = false;
     for (uint32_t base = 0; base < P.nblocks; base += nthr) {
         const uint32_t j = base + tid;
         const bool valid = j < P.nblocks;
         uint32_t b = 0, k = 0, len = 0;
         T2BlockBits bb{};                                         // the block's bit string (t2_bits.h)
+        T2MsbsBits mb{};                                          // ... under the general tree
         size_t row = 0;
         if (valid) {
             b = (j >= n0) + (j >= n0 + n1);
@@ -117,9 +167,21 @@ __global__ __launch_bounds__(1024) void t2_header_kernel(T2HeaderArgs a)
             row = row_base + (b == 0 ? fb0 : b == 1 ? fb1 : fb2) + k;
             len = a.lengths[row];
             if (!t2_len_ok(len)) { bad = true; len = 0; }         // (KT2 copies nothing of such a block either)
-            bb = t2_block_bits(k % gw, k / gw, height, b == 0 ? km0 : b == 1 ? km1 : km2, len);
+            if constexpr (kMsbs) {
+                const uint32_t x = k % gw, y = k / gw, m = x | y;
+                const uint8_t* const nb = nodes + (b == 0 ? 0u : b == 1 ? nd1 : nd2);
+                const uint32_t nn = min(m ? (uint32_t)__builtin_ctz(m) + 1u : height, height);
+                uint32_t vp = 0;
+                if (nn < height) {                                // the node at level nn: the one above the block's new nodes
+                    uint32_t at = 0, w = gw, h = b == 0 ? gh0 : b == 1 ? gh1 : gh2;
+                    for (uint32_t l = 0; l < nn; ++l) { at += w * h; w = (w + 1u) >> 1; h = (h + 1u) >> 1; }
+                    vp = __hip_atomic_load(nb + at + (y >> nn) * w + (x >> nn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                mb = t2_block_bits_msbs(x, y, height, __hip_atomic_load(nb + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), vp, len);
+            } else
+                bb = t2_block_bits(k % gw, k / gw, height, b == 0 ? km0 : b == 1 ? km1 : km2, len);
         }
-        const uint32_t nbits = bb.nbits;
+        const uint32_t nbits = kMsbs ? mb.nbits : bb.nbits;
         const uint64_t v = ((uint64_t)nbits << 40) | len;
         uint64_t incl = v;
 #pragma unroll
@@ -136,15 +198,33 @@ __global__ __launch_bounds__(1024) void t2_header_kernel(T2HeaderArgs a)
             const uint64_t excl = before + incl - v;
             uint32_t pos = (uint32_t)(excl >> 40);
             a.rel[row] = (uint32_t)(excl & kByteMask);
-            put_bits(u, pos, (1ull << bb.nn) - 1ull, bb.nn);
-            pos += bb.nn + bb.zeros;
-            // `nn` ones and the pass bit 0 | Lblock: `inc` ones and a zero | the length in 3 + inc bits -- in one piece where 64 bits hold it
-            put_bits(u, pos, bb.tail[0], bb.tail_n[0]);
-            if (bb.tail_n[1]) put_bits(u, pos + bb.tail_n[0], bb.tail[1], bb.tail_n[1]);
+            if constexpr (kMsbs) {
+                put_bits(u, pos, (1ull << mb.nn) - 1ull, mb.nn);
+                // the new nodes' ones from the leaf up -- the zeros in front of each are the scratch's --, neighbours in one piece
+                const uint32_t gw = b == 0 ? gw0 : b == 1 ? gw1 : gw2, x = k % gw, y = k / gw;
+                const uint8_t* const nb = nodes + (b == 0 ? 0u : b == 1 ? nd1 : nd2);
+                uint32_t at = 0, w = gw, h = b == 0 ? gh0 : b == 1 ? gh1 : gh2, run_at = 0, run_n = 0;
+                for (uint32_t l = 0; l < mb.nn; ++l) {
+                    const uint32_t vl = __hip_atomic_load(nb + at + (y >> l) * w + (x >> l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    const uint32_t q = t2_msbs_one_at(mb, l, vl);
+                    if (run_n && q + 1u == run_at) { run_at = q; ++run_n; }
+                    else { put_bits(u, pos + run_at, (1ull << run_n) - 1ull, run_n); run_at = q; run_n = 1; }
+                    at += w * h; w = (w + 1u) >> 1; h = (h + 1u) >> 1;
+                }
+                put_bits(u, pos + run_at, (1ull << run_n) - 1ull, run_n);
+                put_bits(u, pos + mb.nbits - mb.tail_n, mb.tail, mb.tail_n);
+            } else {
+                put_bits(u, pos, (1ull << bb.nn) - 1ull, bb.nn);
+                pos += bb.nn + bb.zeros;
+                // `nn` ones and the pass bit 0 | Lblock: `inc` ones and a zero | the length in 3 + inc bits -- in one piece where 64 bits hold it
+                put_bits(u, pos, bb.tail[0], bb.tail_n[0]);
+                if (bb.tail_n[1]) put_bits(u, pos + bb.tail_n[0], bb.tail[1], bb.tail_n[1]);
+            }
         }
         carry += total;
     }
     if (bad) atomicOr(a.status, 4u);
+    if (deep) atomicOr(a.status, 16u);
     const uint32_t nbits_total = (uint32_t)(carry >> 40);
     const uint32_t nwords = (nbits_total + 31u) >> 5;
     // the raw bits are complete before anybody reads them back.  A WORKGROUP-scope fence: an agent-scope one (__threadfence) writes the
@@ -338,12 +418,31 @@ __global__ __launch_bounds__(256) void t2_gather_kernel(T2GatherArgs a)
     }
 }
 
+// the rows' zero bit-planes from the drop bytes the blocks were coded with (drop_missing_msbs, encode_plan.h; KK does the same as it
+// keeps a batch): one lane per row
+__global__ __launch_bounds__(256) void t2_drop_msbs_kernel(const uint8_t* drops, const HtBlockDesc* blocks, uint32_t bpt, uint64_t n, uint8_t* msbs)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) msbs[i] = (uint8_t)drop_missing_msbs(blocks[i % bpt].kmax, drops[i]);
+}
+
+hipError_t launch_t2_drop_msbs(const uint8_t* drops, const HtBlockDesc* blocks, uint32_t bpt, uint64_t n, uint8_t* msbs, hipStream_t s)
+{
+    if (!n || !bpt) return hipSuccess;
+    hipLaunchKernelGGL(t2_drop_msbs_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, s, drops, blocks, bpt, n, msbs);
+    return hipGetLastError();
+}
+
 hipError_t launch_t2_header(const T2HeaderArgs& a, uint32_t max_blocks_per_packet, hipStream_t s)
 {
     if (!a.npackets || !a.ntiles) return hipSuccess;
     // (a packet of a few blocks -- small precincts, low resolutions -- does not need sixteen waves' barriers)
     const uint32_t threads = max_blocks_per_packet > 1024 ? 1024u : max_blocks_per_packet > 128 ? 256u : 64u;
-    if (threads == 1024u) hipLaunchKernelGGL(t2_header_kernel<4096>, dim3(a.npackets, a.ntiles), dim3(threads), 0, s, a);
+    if (a.msbs) {                       // the general zero-bit-plane tree: an instance of its own, the constant one's code stays as it is
+        if (!a.nodes) return hipErrorInvalidValue;
+        if (threads == 1024u) hipLaunchKernelGGL((t2_header_kernel<4096, true>), dim3(a.npackets, a.ntiles), dim3(threads), 0, s, a);
+        else hipLaunchKernelGGL((t2_header_kernel<512, true>), dim3(a.npackets, a.ntiles), dim3(threads), 0, s, a);
+    } else if (threads == 1024u) hipLaunchKernelGGL(t2_header_kernel<4096>, dim3(a.npackets, a.ntiles), dim3(threads), 0, s, a);
     else hipLaunchKernelGGL(t2_header_kernel<512>, dim3(a.npackets, a.ntiles), dim3(threads), 0, s, a);
     return hipGetLastError();
 }

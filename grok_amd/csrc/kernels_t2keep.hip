@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) void t2_keep_kernel(T2KeepArgs a)
         const uint64_t u = i / a.bpu, j = a.row_at[u] + (i - u * a.bpu);
         a.j_lengths[j] = fits ? a.lengths[i] : 0u;
         a.j_offsets[j] = base + (fits ? a.offsets[i] : 0ull);
+        if (a.j_msbs) a.j_msbs[j] = (uint8_t)drop_missing_msbs(a.blocks[i - u * a.bpu].kmax, a.drops ? a.drops[i] : 0u);
     }
     const uint4* const s = reinterpret_cast<const uint4*>(a.arena);
     uint4* const d = reinterpret_cast<uint4*>(a.j_arena + base);

@@ -183,6 +183,41 @@ extern "C" int64_t grk_amd_encode_packed_quality(grk_amd_ctx* c, const grk_amd_i
     return encode_surface_rate_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, &qt.rate, out, out_cap, nullptr, &qt.goal);
 }
 
+// ... and their twins that leave the file in device memory (grk_amd_encode_surface_rate_device / _quality_device behind the unpack)
+extern "C" int64_t grk_amd_encode_packed_rate_device(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                                     uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                                     const grk_amd_rate* rate, void** d_file, grk_amd_rate_result* result)
+{
+    if (!c || !im || !base || !pixels || !d_file || !rate) return GRK_AMD_ERR_INVALID;
+    *d_file = nullptr;
+    PackedFrame f;
+    int rc = open_encode(c, im, base, format, pitch, pixels, cap, pixels_on_device, f);
+    if (rc) return rc;
+    { const int rr = rate_refusal(c, rate); if (rr) return rr; }
+    const PlaneSet ps(f);
+    rc = unpack_frame(c, f, ps, pixels, pixels_on_device);
+    if (rc) return rc;
+    return encode_surface_rate_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, rate, nullptr, 0, result, nullptr, d_file);
+}
+
+extern "C" int64_t grk_amd_encode_packed_quality_device(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                                        uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                                        const grk_amd_quality* quality, void** d_file, grk_amd_quality_result* result)
+{
+    if (!c || !im || !base || !pixels || !d_file || !quality) return GRK_AMD_ERR_INVALID;
+    *d_file = nullptr;
+    PackedFrame f;
+    int rc = open_encode(c, im, base, format, pitch, pixels, cap, pixels_on_device, f);
+    if (rc) return rc;
+    QualityTarget qt;
+    rc = quality_target(c, quality, base->prec, quality_samples(*im, base->num_comps, kDx, kDy), result, qt);
+    if (rc) return rc;
+    const PlaneSet ps(f);
+    rc = unpack_frame(c, f, ps, pixels, pixels_on_device);
+    if (rc) return rc;
+    return encode_surface_rate_job(c, im, base, kDx, kDy, &ps.surface, c->img_planes.p, ps.total, 1, flags, &qt.rate, nullptr, 0, nullptr, &qt.goal, d_file);
+}
+
 extern "C" int grk_amd_decode_packed(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, int format, uint64_t pitch, void* pixels, uint64_t cap,
                                      int pixels_on_device)
 {

@@ -153,6 +153,7 @@ struct RateRun {
         const size_t at = coded.size();
         coded.resize(at + total);
         if (total) { rc = grk_amd_fetch_coded(c, coded.data() + at, total); if (rc) return rc; }
+        c->rate_dev_counters[1] += total;
         keep_rows(k, at);
         return GRK_AMD_OK;
     }
@@ -473,7 +474,65 @@ int64_t grk_amd::encode_rate_joint(grk_amd_ctx* c, const RateJointCall& call, ui
     }, file, out, cap, result);
 }
 
+int64_t grk_amd::encode_rate_joint_device(grk_amd_ctx* c, const RateJointCall& call, const JointT2Call& t2, void** d_file, grk_amd_rate_result* result)
+{
+    c->rate_dev_counters[0] = c->rate_dev_counters[1] = 0;
+    if (!d_file || t2.batches.size() != call.batches.size()) return GRK_AMD_ERR_INVALID;
+    for (size_t k = 0; k < call.batches.size(); ++k) if (t2.batches[k] != call.batches[k].units) return GRK_AMD_ERR_INVALID;
+    std::vector<grk_amd_coded_block> rows;
+    std::vector<uint8_t> coded;                              // (stays empty: the bytes stay on the device)
+    RateRun run{c, call.rate, call.unit_blocks, call.batches, call.front, rows, coded};
+    // what the device writer does not reach is said before any batch is coded
+    JointT2Run jr{c, &t2, true};
+    { const int rc = joint_device_open(jr); if (rc) return rc; }
+    { const int rc = run.tables(true); if (rc) return rc; }
+    // a Tier-2 pass: every batch coded with its slice of the chosen drops and kept, the classes framed -> the file's length
+    const auto pass = [&]() -> int64_t {
+        int rc = joint_device_reset(jr); if (rc) return rc;
+        for (size_t k = 0; k < call.batches.size(); ++k) {
+            rc = run.code(k); if (rc) return rc;
+            rc = joint_device_keep(jr, k); if (rc) return rc;
+        }
+        const int64_t n = joint_device_finish(jr, nullptr, 0, d_file);
+        if (n >= 0) ++c->rate_dev_counters[0];
+        return n;
+    };
+    const uint64_t plain_blocks = length_sum(rows);
+    if (call.quality) {
+        RateQualityResult r{};
+        const int rc = quality_choose(c, call.quality->budget, plain_blocks, r); if (rc) return rc;
+        const int64_t n = pass();
+        if (n >= 0) { fill_quality_result(*call.quality, r, (uint64_t)n); note_reversible(c, *call.base, r.block_bytes < plain_blocks); }
+        return n;
+    }
+    // the rounds of rate_rounds, the file's length the device's
+    const uint64_t target = call.rate->target_bytes;
+    const int64_t plain = call.write(rows.data(), nullptr, nullptr, 0);
+    if (plain < 0) return plain;
+    uint64_t budget = rate_first_budget(target, (uint64_t)plain, plain_blocks);
+    for (uint32_t round = 1; round <= kRateMaxRounds; ++round) {
+        RateAllocResult sum{};
+        const int rc = rate_choose(c, budget, sum); if (rc) return rc;
+        const int64_t len = pass();
+        if (len < 0) return len;
+        if ((uint64_t)len <= target) {
+            fill_result(result, sum, (uint64_t)len, round);
+            note_reversible(c, *call.base, sum.block_bytes < plain_blocks);
+            return len;
+        }
+        const RateNextBudget next = rate_next_budget(budget, sum.block_bytes, (uint64_t)len, target);
+        if (!next.left) return fail(c, GRK_AMD_ERR_OVERFLOW, "the target is below what the file takes with no byte of any block in it");
+        budget = next.budget;
+    }
+    return fail(c, GRK_AMD_ERR_OVERFLOW, "the file was still above the target after 4 allocate + write rounds (the target may be feasible: the rounds ran out)");
+}
+
 extern "C" {
+
+uint64_t grk_amd_rate_device_counters(grk_amd_ctx* c, int which)
+{
+    return c && which >= 0 && which < 2 ? c->rate_dev_counters[which] : 0;
+}
 
 int grk_amd_encode_tiles_rate(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const void* pixels, int on_device,
                               const grk_amd_rate* rate, grk_amd_coded_block* table, uint64_t* total, grk_amd_rate_result* result)

@@ -261,7 +261,7 @@ extern "C" int64_t grk_amd_encode_surface(grk_amd_ctx* c, const grk_amd_image_la
 int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx,
                                 const uint8_t* comp_dy, const grk_amd_surface* surface, const void* pixels, uint64_t cap, int pixels_on_device,
                                 uint32_t flags, const grk_amd_rate* rate, uint8_t* out, uint64_t out_cap, grk_amd_rate_result* result,
-                                const QualityGoal* quality)
+                                const QualityGoal* quality, void** d_file)
 {
     { const int rr = rate_refusal(c, rate); if (rr) return rr; }
     flags |= GRK_AMD_CS_BLOCK_MSBS;
@@ -276,6 +276,15 @@ int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, 
     call.write = [&](const grk_amd_coded_block* rows, const uint8_t* coded, uint8_t* o, uint64_t ocap) -> int64_t {
         return grk_amd_write_codestream_subsampled(im, base, comp_dx, comp_dy, rows, coded, flags, o, ocap);
     };
+    if (d_file) {
+        // Tier-2 on the device, the general zero-bit-plane tree asked for by the call itself (never through the flag); GRK_AMD_IMAGE_T2
+        // is not consulted: a file in device memory has no host writer to go to
+        JointT2Call t2{im, base, comp_dx, comp_dy, flags & ~(uint32_t)GRK_AMD_CS_BLOCK_MSBS, (uint32_t)job.runs.size(), &job.g, {}, {}};
+        for (const SurfaceBatch& B : job.batches) t2.batches.push_back(B.units);
+        const int64_t n = encode_rate_joint_device(c, call, t2, d_file, result);
+        if (n >= 0) ++c->route_counters[0];
+        return n;
+    }
     return encode_rate_joint(c, call, out, out_cap, result);
 }
 
@@ -298,4 +307,30 @@ extern "C" int64_t grk_amd_encode_surface_quality(grk_amd_ctx* c, const grk_amd_
     const int rc = quality_target(c, quality, base->prec, quality_samples(*im, base->num_comps, comp_dx, comp_dy), result, qt);
     if (rc) return rc;
     return encode_surface_rate_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, &qt.rate, out, out_cap, nullptr, &qt.goal);
+}
+
+// The rate- and quality-targeted calls that leave their file in device memory: the arguments, refusals and results of
+// grk_amd_encode_surface_rate / _quality, `d_file` as grk_amd_encode_surface_device has it.  Tier-2 runs on the device in every round
+// (KT1's general zero-bit-plane tree); no coded byte crosses the link (grk_amd_rate_device_counters).
+extern "C" int64_t grk_amd_encode_surface_rate_device(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                      const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                                      const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                                      const grk_amd_rate* rate, void** d_file, grk_amd_rate_result* result)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !d_file || !rate) return GRK_AMD_ERR_INVALID;
+    *d_file = nullptr;
+    return encode_surface_rate_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, rate, nullptr, 0, result, nullptr, d_file);
+}
+
+extern "C" int64_t grk_amd_encode_surface_quality_device(grk_amd_ctx* c, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                                         const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                                         const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                                         const grk_amd_quality* quality, void** d_file, grk_amd_quality_result* result)
+{
+    if (!c || !im || !base || !comp_dx || !comp_dy || !surface || !pixels || !d_file || !quality) return GRK_AMD_ERR_INVALID;
+    *d_file = nullptr;
+    QualityTarget qt;
+    const int rc = quality_target(c, quality, base->prec, quality_samples(*im, base->num_comps, comp_dx, comp_dy), result, qt);
+    if (rc) return rc;
+    return encode_surface_rate_job(c, im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device, flags, &qt.rate, nullptr, 0, nullptr, &qt.goal, d_file);
 }

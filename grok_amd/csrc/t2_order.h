@@ -25,6 +25,11 @@ std::vector<Pk> packet_order(const std::vector<const TileGeom*>& cg, const uint8
 // with every component at g.  (t2_writer.cpp)
 int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx, const uint8_t* comp_dy,
                          uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out);
+// The same for the header kernel's general zero-bit-plane tree (the rows' own missing_msbs, each at most kT2MaxMsbs): the raw-bit
+// scratch holds kT2MaxMsbs more bits per block, and every packet gets a place (T2Packet::v_at, T2Plan::v_bytes) for its bands' node
+// values.  GRK_AMD_CS_BLOCK_MSBS in `flags` is accepted and implied.
+int t2_device_plan_joint_msbs(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx,
+                              const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out);
 
 // The tiles of an image of `nruns` units per tile (image.h: unit t * nruns + k is run k of tile t, of[] its geometry group) in CLASSES
 // that one joint plan frames: the same group for every run, and the same packet sequence under `order` -- seq[t] is tile t's

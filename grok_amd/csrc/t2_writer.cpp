@@ -612,10 +612,10 @@ int64_t plan_tile_part(const grk_amd_tile_params& p, uint32_t tile_index, uint32
 namespace grk_amd {
 // What the header kernel needs to know about a tile's packets: component c's tile-component has the geometry cg[c] and its rows start
 // at row0[c] of the tile's table -- the arguments of write_tile_part, and its packet sequence (t2_order.h).
-int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx, const uint8_t* comp_dy,
-                         uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out)
+// (msbs: the plan of the header kernel's general zero-bit-plane tree)
+static int device_plan(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                       uint32_t gx0, uint32_t gy0, uint32_t flags, bool msbs, T2Plan& out)
 {
-    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (the header kernel writes the constant tree)
     if (cg.empty() || row0.size() != cg.size()) return GRK_AMD_ERR_INVALID;
     uint64_t rows = 0;
     for (size_t c = 0; c < cg.size(); ++c) rows = std::max(rows, row0[c] + cg[c]->blocks_per_comp);
@@ -623,13 +623,13 @@ int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vect
     const std::vector<Pk> seq = packet_order(cg, comp_dx, comp_dy, gx0, gy0, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
     out.packets.clear();
     out.packet_of_block.assign((size_t)rows, 0xFFFFFFFFu);
-    uint64_t u = 0, h = 0;
+    uint64_t u = 0, h = 0, v = 0;
     for (const Pk& q : seq) {
         const TileGeom& g = *cg[q.c];
         const ResGeom& R = g.res[q.r];
         T2Packet k{};
         k.row0 = (uint32_t)row0[q.c];
-        uint64_t bits = 1;
+        uint64_t bits = 1, nodes = 0;
         for (uint32_t bi = 0; bi < R.num_bands; ++bi) {
             const BandGeom& B = R.band[bi];
             const BandGeom::Prec& P = B.prec[q.pi];
@@ -647,18 +647,35 @@ int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vect
             k.nblocks += (uint32_t)n;
             // per block: two paths of at most `height` nodes, the pass bit, Lblock's comma code and the length
             bits += n * (2ull * k.height[b] + 1 + (kT2MaxLenBits - 3 + 1) + kT2MaxLenBits) + B.kmax;
+            // the general tree: a path's zeros end at the block's own value, and every level of the band's tree holds a byte per node
+            if (msbs) { bits += n * kT2MaxMsbs; nodes += t2_tree_nodes(P.gw, P.gh); }
         }
         if (bits > 0x7FFFFFFFull) return GRK_AMD_ERR_UNSUPPORTED;
         k.u_at = (uint32_t)u; k.u_words = (uint32_t)((bits + 31) / 32 + 2);
         k.h_at = (uint32_t)h;
+        k.v_at = (uint32_t)v;
         u += (k.u_words + 31u) & ~31ull;                         // (packets start on 128-byte lines)
         h += ((bits + 6) / 7 + 2 + 15) & ~15ull;                 // a stuffed byte carries at least 7 bits
-        if (u > 0x3FFFFFFFull || h > 0xFFFFFFFFull) return GRK_AMD_ERR_UNSUPPORTED;
+        v += (nodes + 15) & ~15ull;
+        if (u > 0x3FFFFFFFull || h > 0xFFFFFFFFull || v > 0xFFFFFFFFull) return GRK_AMD_ERR_UNSUPPORTED;
         out.packets.push_back(k);
     }
-    for (uint32_t v : out.packet_of_block) if (v == 0xFFFFFFFFu) return GRK_AMD_ERR_INVALID;     // (every block lies in one precinct)
-    out.u_words = (uint32_t)u; out.h_bytes = (uint32_t)h;
+    for (uint32_t of : out.packet_of_block) if (of == 0xFFFFFFFFu) return GRK_AMD_ERR_INVALID;     // (every block lies in one precinct)
+    out.u_words = (uint32_t)u; out.h_bytes = (uint32_t)h; out.v_bytes = (uint32_t)v;
     return GRK_AMD_OK;
+}
+
+int t2_device_plan_joint(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                         uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out)
+{
+    if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (the general tree is asked for by name: below)
+    return device_plan(cg, row0, comp_dx, comp_dy, gx0, gy0, flags, false, out);
+}
+
+int t2_device_plan_joint_msbs(const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx,
+                              const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0, uint32_t flags, T2Plan& out)
+{
+    return device_plan(cg, row0, comp_dx, comp_dy, gx0, gy0, flags & ~(uint32_t)GRK_AMD_CS_BLOCK_MSBS, true, out);
 }
 
 // ... of a tile without sub-sampling: every component has the tile's geometry, component c's rows start at c x blocks_per_comp
@@ -669,6 +686,15 @@ int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out)
     std::vector<uint64_t> row0(p.num_comps);
     for (uint32_t c = 0; c < p.num_comps; ++c) row0[c] = (uint64_t)c * g.blocks_per_comp;
     return t2_device_plan_joint(cg, row0, nullptr, nullptr, p.tile_x0, p.tile_y0, flags, out);
+}
+
+int t2_device_plan_msbs(const TileGeom& g, uint32_t flags, T2Plan& out)
+{
+    const grk_amd_tile_params& p = g.p;
+    std::vector<const TileGeom*> cg(p.num_comps, &g);
+    std::vector<uint64_t> row0(p.num_comps);
+    for (uint32_t c = 0; c < p.num_comps; ++c) row0[c] = (uint64_t)c * g.blocks_per_comp;
+    return t2_device_plan_joint_msbs(cg, row0, nullptr, nullptr, p.tile_x0, p.tile_y0, flags, out);
 }
 
 } // namespace grk_amd

@@ -284,6 +284,15 @@ int64_t grk_amd_stage_assemble(grk_amd_ctx* ctx, const grk_amd_tile_params* p, u
 /* the longest code-block the device writer takes, in bytes; a longer one makes grk_amd_assemble_device and the whole-image encoders'
  * device route return GRK_AMD_ERR_UNSUPPORTED (the image encoders then take the host writer) */
 uint32_t grk_amd_t2_max_block_bytes(void);
+/* grk_amd_stage_assemble with the rows' missing_msbs WRITTEN: the zero-bit-plane tag trees in their general form, every block with
+ * its own value (the rows of a rate- or quality-targeted encode) -- the tile-parts grk_amd_write_tile_part writes under
+ * GRK_AMD_CS_BLOCK_MSBS, which is accepted in `flags` and implied.  The same checks on the host before anything is launched, and
+ * GRK_AMD_ERR_UNSUPPORTED for a row whose missing_msbs lies above grk_amd_t2_max_block_msbs() (63: above any Kmax - 1 of this library's
+ * geometry).  A zero-length row is included like any other, with whatever missing_msbs it carries. */
+int64_t grk_amd_stage_assemble_msbs(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
+                                    uint32_t flags, const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes,
+                                    uint32_t* part_bytes);
+uint32_t grk_amd_t2_max_block_msbs(void);
 
 /* The statistics kernel of the rate-targeted encodes (KR1, see grk_amd_encode_tiles_rate below) on planes of the caller's choosing.
  * d_mallat: DEVICE planes of num_tiles tiles, int32 (float32 bit patterns for 9/7), or with planes16 != 0 int16 under the conditions of
@@ -522,6 +531,11 @@ int64_t grk_amd_plan_tile_part(const grk_amd_tile_params* p, uint32_t tile_index
 int64_t grk_amd_assemble_device(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
                                 uint32_t flags, uint64_t dst_offset, uint32_t* part_bytes);
 void* grk_amd_assembled_device_ptr(grk_amd_ctx* ctx);
+/* grk_amd_assemble_device for the grk_amd_encode_tiles_rate / grk_amd_encode_tiles_quality call before it: the rows' zero bit-planes --
+ * made on the device from the drops the blocks were coded with -- are written (the tile-parts of grk_amd_write_tile_part under
+ * GRK_AMD_CS_BLOCK_MSBS, which is accepted in `flags` and implied).  GRK_AMD_ERR_INVALID when the latest encode was not such a call. */
+int64_t grk_amd_assemble_rate_device(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
+                                     uint32_t flags, uint64_t dst_offset, uint32_t* part_bytes);
 /* The same without the host: queued on `hip_stream`, which is first made to wait for the encode's results (grk_amd_stream_wait_results);
  * nothing is waited for, nothing comes to the host.  The tile-parts (grk_amd_assembled_device_ptr), their places and lengths and the total
  * (grk_amd_assembled_table_ptr -- 0: uint64[tiles] offsets, 1: uint32[tiles] lengths, 2: uint64[2] {bytes assembled, end}) stay where they are
@@ -1160,6 +1174,32 @@ int64_t grk_amd_encode_packed_rate(grk_amd_ctx* ctx, const grk_amd_image_layout*
 int64_t grk_amd_encode_packed_quality(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format, uint64_t pitch,
                                       const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags, const grk_amd_quality* quality,
                                       uint8_t* out, uint64_t out_cap, grk_amd_quality_result* result);
+
+/* ---- Rate- and quality-targeted files left in DEVICE memory ----------------------------------------------------------------------------
+ * The twins of grk_amd_encode_surface_rate / _quality and grk_amd_encode_packed_rate / _quality: the same arguments with `d_file` in place
+ * of `out, out_cap` (*d_file: SOC .. EOC, contiguous, in a buffer the context owns, valid until its next encode call, as
+ * grk_amd_encode_surface_device has it), the same refusals (pipelining, max_drop, a target that is not a number), the same budgets and
+ * rounds -- the file and every field of the result are the host-memory call's.  Tier-2 runs on the device in every round: the block
+ * coder's rows stay where they are, their zero bit-planes are made from the chosen drops on the device and written by the header
+ * kernel's general tag tree; only the plain encode's rows (16 bytes per block) and each round's tile-part lengths come to the host.
+ * GRK_AMD_IMAGE_T2 is not consulted.  The calls end synchronised; a successful one counts in grk_amd_encode_route_counters(ctx, 0).
+ * grk_amd_rate_device_counters(ctx, which) of the latest such call -- 0: its Tier-2 passes on the device (the rounds; 1 for a quality
+ * target), 1: bytes of coded blocks it copied to the host (0). */
+int64_t grk_amd_encode_surface_rate_device(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                           const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                           const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                           const grk_amd_rate* rate, void** d_file, grk_amd_rate_result* result);
+int64_t grk_amd_encode_surface_quality_device(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base,
+                                              const uint8_t* comp_dx, const uint8_t* comp_dy, const grk_amd_surface* surface,
+                                              const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                              const grk_amd_quality* quality, void** d_file, grk_amd_quality_result* result);
+int64_t grk_amd_encode_packed_rate_device(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                          uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                          const grk_amd_rate* rate, void** d_file, grk_amd_rate_result* result);
+int64_t grk_amd_encode_packed_quality_device(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_amd_tile_params* base, int format,
+                                             uint64_t pitch, const void* pixels, uint64_t cap, int pixels_on_device, uint32_t flags,
+                                             const grk_amd_quality* quality, void** d_file, grk_amd_quality_result* result);
+uint64_t grk_amd_rate_device_counters(grk_amd_ctx* ctx, int which);
 /* Codestream -> packed frame: component c of the frame is plane c of grk_amd_decode_image, written by the rules above.  A host
  * frame is uploaded, packed into and downloaded (what is no sample stays); the call is synchronous and repeats a group that leaves
  * the int16 planes by itself, as grk_amd_decode_surface does.  A device frame: the pack kernel is queued on the context's stream

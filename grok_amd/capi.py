@@ -1553,6 +1553,10 @@ class Context:
             L.grk_amd_read_packets_device.restype = C.c_int64
             L.grk_amd_read_packets_device.argtypes = [vp, vp, u64, C.POINTER(StreamInfo), vp, u64]
             L.grk_amd_decode_image_device.argtypes = [vp, vp, u64, vp, u64, C.c_int]
+            L.grk_amd_read_packets_device_ex.restype = C.c_int64
+            L.grk_amd_read_packets_device_ex.argtypes = [vp, vp, u64, C.POINTER(StreamInfo), vp, u64, vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
+                                                         C.POINTER(u64)]
+            L.grk_amd_decode_image_device_ex.argtypes = [vp, vp, u64, vp, u64, C.c_int]
             L.grk_amd_read_device_counters.restype = u64
             L.grk_amd_read_device_counters.argtypes = [vp, C.c_int]
             L._read_device_bound = True
@@ -1588,10 +1592,42 @@ class Context:
         if rc:
             raise ReaderError("decode_image_resident", rc, self.last_error())
 
-    def read_device_counters(self):
-        """(bytes copied device -> host, bytes copied host -> device, KC launches, chains parsed) by the calls above so far"""
+    def read_packets_device_ex(self, d_cs, nbytes, info=None):
+        """grk_amd_read_packets_device_ex: the general reader -- layers, LAZY / TERMALL -- of the codestream at device pointer d_cs
+        -> the dict read_packets gives for the same bytes (the moves in the order of their dst); ReaderError with its code when
+        refused."""
         L = self._read_device_fns()
-        return tuple(int(L.grk_amd_read_device_counters(self._h, k)) for k in range(4))
+        if info is None:
+            info = self.read_header_device(d_cs, nbytes)
+        nseg, nmov, app = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        # the sizes first, then the tables
+        n = L.grk_amd_read_packets_device_ex(self._h, int(d_cs), int(nbytes), C.byref(info), None, 0, None, None, 0, C.byref(nseg), None, 0, C.byref(nmov),
+                                             C.byref(app))
+        if n < 0:
+            raise ReaderError("read_packets_device_ex", n, self.last_error())
+        rows = np.zeros(int(n), CODED_DTYPE)
+        first = np.zeros(int(n) + 1, np.uint32)
+        segs = np.zeros(int(nseg.value), SEGMENT_DTYPE)
+        moves = np.zeros(int(nmov.value), MOVE_DTYPE)
+        n = L.grk_amd_read_packets_device_ex(self._h, int(d_cs), int(nbytes), C.byref(info), rows.ctypes.data, rows.size, first.ctypes.data, segs.ctypes.data,
+                                             segs.size, C.byref(nseg), moves.ctypes.data, moves.size, C.byref(nmov), C.byref(app))
+        if n < 0:
+            raise ReaderError("read_packets_device_ex", n, self.last_error())
+        return dict(rows=rows, first_segment=first, segments=segs, moves=moves, appendix_bytes=int(app.value))
+
+    def decode_image_resident_ex(self, d_cs, nbytes, pixels, cap, on_device=True):
+        """grk_amd_decode_image_device_ex: decode_image_resident on top of the general reader.  Without an appendix the stream is the
+        coded buffer; with one it is staged in front of its appendix in the context's own buffer (read_device_counters()[4])."""
+        L = self._read_device_fns()
+        rc = L.grk_amd_decode_image_device_ex(self._h, int(d_cs), int(nbytes), int(pixels), int(cap), int(bool(on_device)))
+        if rc:
+            raise ReaderError("decode_image_resident_ex", rc, self.last_error())
+
+    def read_device_counters(self):
+        """(bytes copied device -> host, bytes copied host -> device, KC launches, chains parsed, bytes the _ex decode copied device
+        to device, KC-L launches) by the calls above so far"""
+        L = self._read_device_fns()
+        return tuple(int(L.grk_amd_read_device_counters(self._h, k)) for k in range(6))
 
     def decode_image_counters(self):
         """(tiles whose packets were read, codestream bytes uploaded) by this context's decode_image / decode_image_view calls so far"""

@@ -316,6 +316,12 @@ int decode_onto_surface(grk_amd_ctx* c, const char* name, const uint8_t* cs, uin
 namespace grk_amd { struct StreamTable; }
 int decode_resident(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, grk_amd::StreamTable& tab, void* pixels,
                     uint64_t cap, int pixels_on_device);                                                                      // decode_image.cpp
+// ... and for a table with an appendix (tab.appendix_bytes; the general reader's): the moves lie in device memory where the reader's
+// placement kernel left them (tab.moves is empty), the stream is staged in front of its appendix in the context's coded buffer --
+// one device-to-device copy of `len` bytes, added to *staged -- and d_cs is only read
+int decode_resident_moves(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, grk_amd::StreamTable& tab,
+                          const grk_amd_tp_segment* d_moves, uint64_t num_moves, uint64_t* staged, void* pixels, uint64_t cap,
+                          int pixels_on_device);                                                                              // decode_image.cpp
 void read_device_release(grk_amd_ctx* c);                                                                                     // read_device.hip
 // what the whole-image decodes refuse on the context: a decode reduce (`reduced`: the text behind the entry point's name), a decode sequence
 int refuse_context(grk_amd_ctx* c, const char* name, const char* reduced);                                                    // decode_image.cpp

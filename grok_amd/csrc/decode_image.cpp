@@ -140,7 +140,9 @@ extern "C" int grk_amd_place_tiles_clipped_device(grk_amd_ctx* c, const void* ti
 // whose planes lie in device memory all the same.
 // res != nullptr (grk_amd_decode_image_device): the codestream lies in device memory and IS the coded buffer -- nothing is uploaded,
 // no packet is read here: the header and the table are the device reader's (read_device.hip); `cs` is not looked at.
-struct ResidentStream { const void* d_cs; const grk_amd_stream_info* info; StreamTable* tab; };
+// d_moves (num_moves of them, device memory): the table has an appendix -- the stream is staged in front of it in the context's coded
+// buffer (the decoders take one coded base), the gather reads the moves where they lie; *staged: bytes copied so
+struct ResidentStream { const void* d_cs; const grk_amd_stream_info* info; StreamTable* tab; const grk_amd_tp_segment* d_moves; uint64_t num_moves; uint64_t* staged; };
 static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const grk_amd_image_view* view, void* pixels, uint64_t cap, int pixels_on_device,
                        const grk_amd_surface* surf = nullptr, bool host_rules = false, const ResidentStream* res = nullptr)
 {
@@ -176,11 +178,19 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     rc = join_side(c); if (rc) return rc;
     // the upload, the packet headers meanwhile
     if (!res) HIP_TRY(c, c->img_coded.ensure(coded.coded_cap + 64), "alloc the coded buffer");
-    void* const coded_buf = res ? const_cast<void*>(res->d_cs) : c->img_coded.p;
+    void* coded_buf = res ? const_cast<void*>(res->d_cs) : c->img_coded.p;
     StreamTable tab;
     int rrc = GRK_AMD_OK;
-    if (res) tab = std::move(*res->tab);
-    else {
+    if (res) {
+        tab = std::move(*res->tab);
+        if (tab.appendix_bytes) {
+            if (!res->d_moves || !tab.moves.empty()) return fail(c, GRK_AMD_ERR_INVALID, "an appendix without its moves in device memory");
+            HIP_TRY(c, c->img_coded.ensure(coded.coded_cap + 64), "alloc the coded buffer");
+            coded_buf = c->img_coded.p;
+            HIP_TRY(c, hipMemcpyAsync(coded_buf, res->d_cs, len, hipMemcpyDeviceToDevice, c->stream), "stage the codestream");
+            if (res->staged) *res->staged += len;
+        }
+    } else {
         const uint32_t threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
         std::thread reader([&]() {
             if (d.all) rrc = locate_stream_parts(cs, len, info, parts, why);
@@ -200,7 +210,12 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     // (from here on the call only queues work; the small tables below are uploaded with blocking copies into buffers that an
     //  earlier call's kernels may still read)
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
-    rc = run_gather(c, tab.moves.data(), tab.moves.size(), coded_buf, (uint8_t*)coded_buf + coded.up_len); if (rc) return rc;
+    if (res && tab.appendix_bytes) {
+        if (res->num_moves) {
+            HIP_TRY(c, launch_t2dec_gather(res->d_moves, res->num_moves, (const uint8_t*)coded_buf, (uint8_t*)coded_buf + coded.up_len, c->stream), "launch gather");
+            ++c->img_launches[0];
+        }
+    } else { rc = run_gather(c, tab.moves.data(), tab.moves.size(), coded_buf, (uint8_t*)coded_buf + coded.up_len); if (rc) return rc; }
 
     SavedSettings saved(c);
     c->dec_steps.clear();
@@ -318,7 +333,14 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
 int decode_resident(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, StreamTable& tab, void* pixels, uint64_t cap,
                     int pixels_on_device)
 {
-    const ResidentStream res{d_cs, &info, &tab};
+    const ResidentStream res{d_cs, &info, &tab, nullptr, 0, nullptr};
+    return decode_view(c, nullptr, len, nullptr, pixels, cap, pixels_on_device, nullptr, false, &res);
+}
+
+int decode_resident_moves(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, StreamTable& tab, const grk_amd_tp_segment* d_moves,
+                          uint64_t num_moves, uint64_t* staged, void* pixels, uint64_t cap, int pixels_on_device)
+{
+    const ResidentStream res{d_cs, &info, &tab, d_moves, num_moves, staged};
     return decode_view(c, nullptr, len, nullptr, pixels, cap, pixels_on_device, nullptr, false, &res);
 }
 

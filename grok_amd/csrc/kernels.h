@@ -463,4 +463,29 @@ hipError_t launch_t2read_locate(const T2ReadArgs& a, hipStream_t s);
 hipError_t launch_t2read_headers(const T2ReadArgs& a, hipStream_t s);
 hipError_t launch_t2read_chains(const T2ReadArgs& a, hipStream_t s);
 
+// ---- the general reader: several layers, several codeword segments (kernels_t2read_layers.hip) ----------------------------------------
+// KL and KH run on `a` as they are (a.tiles: T2ReadLayersPlan's, whose npackets count every layer's); a.nodes is not used.
+constexpr uint32_t kT2ReadScanRows = 256;            // rows per workgroup of KF
+struct T2ReadLayerPk; struct T2pRowState; struct T2ReadSegRecord; struct T2ReadPieceRecord;
+struct T2ReadLayersArgs {
+    T2ReadArgs a;
+    const T2ReadLayerPk* lpk;
+    uint32_t layers, order, sty, seg_per_row, piece_per_row;
+    uint32_t* nodes32; T2pRowState* state;
+    T2ReadSegRecord* seg_log; T2ReadPieceRecord* piece_log;
+    uint32_t* counts;                                // [chain][2]: records in its share of the two logs
+    // KF, KP
+    uint64_t nrows;
+    uint32_t* first_segment;                         // [rows + 1]
+    unsigned long long* app_at;                      // [rows]: a row of several pieces' place in the appendix
+    uint32_t* move_first;                            // [rows]: its first move
+    unsigned long long* sums;                        // [ceil(rows / kT2ReadScanRows)][3] scratch
+    unsigned long long* totals;                      // [3]: segments, appendix bytes, moves
+    grk_amd_segment* segments; uint64_t seg_cap;
+    grk_amd_tp_segment* moves; uint64_t move_cap;
+};
+hipError_t launch_t2read_chains_layers(const T2ReadLayersArgs& g, hipStream_t s);
+hipError_t launch_t2read_finish(const T2ReadLayersArgs& g, hipStream_t s);
+hipError_t launch_t2read_place(const T2ReadLayersArgs& g, hipStream_t s);
+
 } // namespace grk_amd

@@ -12,7 +12,8 @@
 //                  stream and the nodes is made uniform with readfirstlane: the state lives in scalar registers); the lanes
 //                  fetch the stream a window at a time, clear the chain's tag-tree nodes and store rows 64 at a time.
 // Refusals go to ONE 64-bit word with atomicMin (t2_parse.h: the status word); a wave that fails stops its own chain, nobody
-// waits for anybody.  Plain C++: no inline assembly.
+// waits for anybody.  Plain C++: no inline assembly.  Behind KC: the general reader's kernels (KC-L, KF, KP) for files of several
+// layers or codeword segments (grk_amd_read_packets_device_ex; the parse: t2_parse_layers.h), which reuse KL and KH as they are.
 #define GRK_T2P_UNIFORM(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))
 #include "kernels.h"
 #include "t2_parse.h"
@@ -299,6 +300,245 @@ hipError_t launch_t2read_chains(const T2ReadArgs& a, hipStream_t s)
 {
     if (!a.chains) return hipSuccess;
     hipLaunchKernelGGL(t2read_chains_kernel, dim3((uint32_t)a.chains), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ==== the general reader: several layers, several codeword segments (t2_parse_layers.h) ==========================================
+//   KC-L chains    one wave per chain, as KC: with PLT a precinct with its L packets, each found through its packet start, without
+//                  a tile's packets in file order.  The chain clears its nodes (32-bit) and its rows' state, and logs what every
+//                  contribution adds -- segment records and piece records, 64 at a time -- into its rows' share of the two logs.
+//   KF  finish     over the rows: the row from its state (the bit-plane check: stage 2), and three exclusive scans -- segments,
+//                  appendix bytes and moves of the rows before -- by workgroups of 256 rows, a scan of their sums, and an add.
+//   KP  place      a lane per log record: segments[first_segment[row] + ordinal] += the record's (a row's records come from one
+//                  wave, the sums are 32-bit atomics on zeroed memory), moves[move_first[row] + ordinal] = the piece's.
+namespace {
+
+// records to a chain's share of a log 64 at a time; never beyond the share (a full share: `over`, which no stream can cause)
+template <class Rec> struct LogSink {
+    Rec* log; uint32_t cap; Rec* s_rec; uint32_t count, n; bool over;
+    __device__ void flush()
+    {
+        if (!n) return;
+        __syncthreads();
+        const uint32_t lane = threadIdx.x;
+        if (lane < n && count + lane < cap) log[count + lane] = s_rec[lane];
+        if (count + n > cap) over = true;
+        count = count + n > cap ? cap : count + n;
+        __syncthreads();
+        n = 0;
+    }
+    __device__ void put(const Rec& r)
+    {
+        if (n == 64) flush();
+        if (threadIdx.x == 0) s_rec[n] = r;
+        ++n;
+    }
+};
+
+struct LayerSink {
+    LogSink<T2ReadSegRecord> segs; LogSink<T2ReadPieceRecord> pieces;
+    __device__ void seg(uint32_t row, uint32_t ordinal, uint32_t len, uint32_t passes, bool opens) { segs.put(T2ReadSegRecord{row, ordinal, len, passes | (opens ? 1u << 31 : 0u)}); }
+    __device__ void piece(uint32_t row, uint32_t ordinal, uint64_t rel, uint32_t len, uint32_t before) { pieces.put(T2ReadPieceRecord{rel, row, ordinal, len, before}); }
+};
+
+// the tile of chain / of row: the last whose base is not beyond it
+__device__ uint32_t tile_of_chain(const T2ReadTile* tiles, uint32_t nt, uint32_t chain)
+{
+    uint32_t lo = 0, hi = nt;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (tiles[mid].chain_base <= chain) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ uint32_t tile_of_row(const T2ReadTile* tiles, uint32_t nt, uint64_t row)
+{
+    uint32_t lo = 0, hi = nt;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (tiles[mid].row_base <= row) lo = mid; else hi = mid; }
+    return lo;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(64) void t2read_chains_layers_kernel(T2ReadLayersArgs g)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWin];
+    __shared__ T2ReadSegRecord s_seg[64];
+    __shared__ T2ReadPieceRecord s_piece[64];
+    const T2ReadArgs& a = g.a;
+    const uint32_t chain = blockIdx.x, lane = threadIdx.x;
+    if (lane == 0) { g.counts[2 * chain] = 0; g.counts[2 * chain + 1] = 0; }
+    const uint32_t t = tile_of_chain(a.tiles, a.num_tiles, chain);
+    const T2ReadTile T = a.tiles[t];
+    const uint64_t body = a.body_at[t];
+    if (!body) return;                                          // (not located, or its header refused)
+    const uint64_t end = a.part_at[t] + a.part_len[t];
+    const uint32_t L = g.layers, np = T.npackets / L;
+    const bool plt = a.has_plt[t] != 0, split = plt && T.nchains == np;
+    const uint32_t i0 = chain - T.chain_base;
+    if (!split && i0) return;                                   // one chain parses the tile
+    const T2ReadPacket* const pk = a.packets + T.first_packet;
+    const T2ReadLayerPk* const lp = g.lpk + T.first_packet;
+    uint32_t* const nodes = g.nodes32 + T.node_base;
+    T2pRowState* const state = g.state + T.row_base;
+    // the chain's nodes and its rows' state zeroed by all lanes
+    {
+        const uint32_t from = split ? pk[i0].node_at : 0u, n = split ? pk[i0].node_n : T.node_bytes;
+        for (uint32_t i = lane; i < n; i += 64) nodes[from + i] = 0;
+        uint32_t* const sw = (uint32_t*)state;
+        if (split) {
+            for (uint32_t bi = 0; bi < pk[i0].nbands; ++bi) {
+                const T2ReadBand& B = pk[i0].band[bi];
+                const uint32_t words = B.gw * B.gh * kT2pStateWords;
+                for (uint32_t i = lane; i < words; i += 64) sw[(size_t)B.first_row * kT2pStateWords + i] = 0;
+            }
+        } else for (uint64_t i = lane; i < (uint64_t)T.rows * kT2pStateWords; i += 64) sw[i] = 0;
+        __threadfence_block();
+        __syncthreads();
+    }
+    const uint64_t share = (uint64_t)T.row_base + (split ? lp[i0].blocks_before : 0u);
+    const uint32_t share_rows = split ? pk[i0].nblocks : T.rows;
+    LayerSink sink{{g.seg_log + share * g.seg_per_row, share_rows * g.seg_per_row, s_seg, 0, 0, false},
+                   {g.piece_log + share * g.piece_per_row, share_rows * g.piece_per_row, s_piece, 0, 0, false}};
+    WindowSrc src{a.cs, a.len, s_win, 0, false};
+    uint64_t pos = body;
+    bool failed = false;
+    // one packet: precinct i, layer l, the tile's packet k
+    auto one = [&](uint32_t i, uint32_t l, uint32_t k) -> bool {
+        if (split) pos = a.pk_start[T.pkt_base + k];
+        const uint64_t from = pos;
+        const uint32_t pieces0 = sink.pieces.count + sink.pieces.n;
+        uint64_t body_at = 0;
+        const uint32_t why = t2p_read_packet_layer(src, pk[i], nodes, state, a.ht != 0, g.sty, a.sop != 0, a.eph != 0, l, k, pos, end, sink, &body_at);
+        sink.segs.flush(); sink.pieces.flush();
+        if (why) { if (lane == 0) report(a.status, t2p_status_tile(t, 1, k, why)); failed = true; return false; }
+        // the pieces' sources: relative to the end of the header until now; a row's first piece is its offset
+        __threadfence_block();
+        __syncthreads();
+        for (uint32_t j = pieces0 + lane; j < sink.pieces.count; j += 64) {
+            T2ReadPieceRecord* const r = sink.pieces.log + j;
+            const uint64_t at = body_at + r->src;
+            r->src = at;
+            if (r->ordinal == 0) { state[r->row].src_lo = (uint32_t)at; state[r->row].src_hi = (uint32_t)(at >> 32); }
+        }
+        if (plt && pos - from != a.plt_len[T.pkt_base + k]) { if (lane == 0) report(a.status, t2p_status_tile(t, 1, k, kT2pPltSize)); failed = true; return false; }
+        return true;
+    };
+    if (split) {
+        for (uint32_t l = 0; l < L; ++l)
+            if (!one(i0, l, (uint32_t)t2p_packet_number(g.order, np, L, i0, l, lp[i0].run_first, lp[i0].run_count))) break;
+    } else {
+        t2p_tile_packets(g.order, np, L, [&](uint32_t i, uint32_t* first, uint32_t* count) { *first = lp[i].run_first; *count = lp[i].run_count; }, one);
+        if (!failed && pos != end && lane == 0) report(a.status, t2p_status_tile(t, 1, T.npackets, kT2pTail));
+    }
+    if ((sink.segs.over || sink.pieces.over) && lane == 0) report(a.status, t2p_status_tile(t, 1, T.npackets, kT2pPasses));
+    if (lane == 0) { g.counts[2 * chain] = sink.segs.count; g.counts[2 * chain + 1] = sink.pieces.count; }
+}
+
+// ---- KF --------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void t2read_finish_rows_kernel(T2ReadLayersArgs g)
+{
+    __shared__ uint64_t s_scan[256];
+    const uint64_t r = (uint64_t)blockIdx.x * kT2ReadScanRows + threadIdx.x;
+    uint64_t nseg = 0, app = 0, mv = 0;
+    if (r < g.nrows) {
+        const T2pRowState s = g.state[r];
+        grk_amd_coded_block row;
+        if (!t2p_finish_row(s, g.a.ht != 0, &row)) {
+            const uint32_t t = tile_of_row(g.a.tiles, g.a.num_tiles, r);
+            report(g.a.status, t2p_status_tile(t, 2, (uint32_t)(r - g.a.tiles[t].row_base), kT2pPart1Planes));
+        }
+        g.a.rows[r] = row;
+        nseg = s.nsegs;
+        if (s.pieces > 1) { app = s.total; mv = s.pieces; }
+    }
+    uint64_t total = 0;
+    const uint64_t i0 = scan256(nseg, s_scan, &total);
+    if (threadIdx.x == 0) g.sums[3 * (uint64_t)blockIdx.x] = total;
+    const uint64_t i1 = scan256(app, s_scan, &total);
+    if (threadIdx.x == 0) g.sums[3 * (uint64_t)blockIdx.x + 1] = total;
+    const uint64_t i2 = scan256(mv, s_scan, &total);
+    if (threadIdx.x == 0) g.sums[3 * (uint64_t)blockIdx.x + 2] = total;
+    if (r < g.nrows) { g.first_segment[r] = (uint32_t)(i0 - nseg); g.app_at[r] = i1 - app; g.move_first[r] = (uint32_t)(i2 - mv); }
+}
+// the workgroups' sums to exclusive ones, in place; the totals
+__global__ __launch_bounds__(256) void t2read_finish_scan_kernel(T2ReadLayersArgs g)
+{
+    __shared__ uint64_t s_scan[256];
+    const uint64_t nb = (g.nrows + kT2ReadScanRows - 1) / kT2ReadScanRows;
+    for (uint32_t q = 0; q < 3; ++q) {
+        uint64_t carry = 0;
+        for (uint64_t base = 0; base < nb; base += 256) {
+            const uint64_t b = base + threadIdx.x;
+            const uint64_t v = b < nb ? g.sums[3 * b + q] : 0;
+            uint64_t total = 0;
+            const uint64_t incl = scan256(v, s_scan, &total);
+            if (b < nb) g.sums[3 * b + q] = carry + incl - v;
+            carry += total;
+        }
+        if (threadIdx.x == 0) { g.totals[q] = carry; if (q == 0) g.first_segment[g.nrows] = (uint32_t)carry; }
+    }
+}
+__global__ __launch_bounds__(256) void t2read_finish_add_kernel(T2ReadLayersArgs g)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kT2ReadScanRows + threadIdx.x;
+    if (r >= g.nrows) return;
+    const unsigned long long* const sum = g.sums + 3 * (uint64_t)blockIdx.x;
+    g.first_segment[r] += (uint32_t)sum[0];
+    const uint64_t at = g.app_at[r] + sum[1];
+    g.app_at[r] = at;
+    g.move_first[r] += (uint32_t)sum[2];
+    if (g.state[r].pieces > 1) g.a.rows[r].offset = g.a.len + at;       // (behind the stream: the appendix)
+}
+
+// ---- KP --------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kPlaceSlices = 8;                 // workgroups per chain
+__global__ __launch_bounds__(256) void t2read_place_kernel(T2ReadLayersArgs g)
+{
+    const T2ReadArgs& a = g.a;
+    const uint32_t chain = blockIdx.x;
+    const uint32_t t = tile_of_chain(a.tiles, a.num_tiles, chain);
+    const T2ReadTile T = a.tiles[t];
+    const uint32_t np = T.npackets / g.layers, i0 = chain - T.chain_base;
+    const bool split = T.nchains == np && a.has_plt[t] != 0;
+    const uint64_t share = (uint64_t)T.row_base + (split ? g.lpk[T.first_packet + i0].blocks_before : 0u);
+    const uint32_t nseg = g.counts[2 * chain], npiece = g.counts[2 * chain + 1];
+    const T2ReadSegRecord* const sl = g.seg_log + share * g.seg_per_row;
+    const T2ReadPieceRecord* const pl = g.piece_log + share * g.piece_per_row;
+    const uint32_t step = 256 * kPlaceSlices;
+    for (uint32_t j = blockIdx.y * 256 + threadIdx.x; j < nseg; j += step) {
+        const T2ReadSegRecord r = sl[j];
+        if (r.row >= T.rows) continue;
+        const uint64_t at = (uint64_t)g.first_segment[T.row_base + r.row] + r.ordinal;
+        if (at >= g.seg_cap) continue;
+        atomicAdd(&g.segments[at].length, r.len);
+        atomicAdd(&g.segments[at].numpasses, r.passes_opens & 0x7FFFFFFFu);
+    }
+    for (uint32_t j = blockIdx.y * 256 + threadIdx.x; j < npiece; j += step) {
+        const T2ReadPieceRecord r = pl[j];
+        if (r.row >= T.rows || g.state[T.row_base + r.row].pieces < 2) continue;
+        const uint64_t at = (uint64_t)g.move_first[T.row_base + r.row] + r.ordinal;
+        if (at >= g.move_cap) continue;
+        g.moves[at] = grk_amd_tp_segment{g.app_at[T.row_base + r.row] + r.before, r.src, r.len, 1u};
+    }
+}
+
+hipError_t launch_t2read_chains_layers(const T2ReadLayersArgs& g, hipStream_t s)
+{
+    if (!g.a.chains) return hipSuccess;
+    hipLaunchKernelGGL(t2read_chains_layers_kernel, dim3((uint32_t)g.a.chains), dim3(64), 0, s, g);
+    return hipGetLastError();
+}
+hipError_t launch_t2read_finish(const T2ReadLayersArgs& g, hipStream_t s)
+{
+    if (!g.nrows) return hipSuccess;
+    const uint32_t nb = (uint32_t)((g.nrows + kT2ReadScanRows - 1) / kT2ReadScanRows);
+    hipLaunchKernelGGL(t2read_finish_rows_kernel, dim3(nb), dim3(256), 0, s, g);
+    hipLaunchKernelGGL(t2read_finish_scan_kernel, dim3(1), dim3(256), 0, s, g);
+    hipLaunchKernelGGL(t2read_finish_add_kernel, dim3(nb), dim3(256), 0, s, g);
+    return hipGetLastError();
+}
+hipError_t launch_t2read_place(const T2ReadLayersArgs& g, hipStream_t s)
+{
+    if (!g.a.chains) return hipSuccess;
+    hipLaunchKernelGGL(t2read_place_kernel, dim3((uint32_t)g.a.chains, kPlaceSlices), dim3(256), 0, s, g);
     return hipGetLastError();
 }
 

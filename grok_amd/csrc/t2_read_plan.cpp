@@ -50,17 +50,10 @@ std::vector<uint32_t> tile_key(const grk_amd_stream_info& info, const grk_amd_ti
 
 } // namespace
 
-int grk_amd::plan_t2_read(const grk_amd_stream_info& info, T2ReadPlan& out, const char** why)
+// the plan of a file of L layers (lpk == nullptr: the single-layer reader's, L = 1; else the general reader's, with what its
+// chain kernel needs beside every packet descriptor)
+static int plan_common(const grk_amd_stream_info& info, T2ReadPlan& out, const char** why, std::vector<T2ReadLayerPk>* lpk, uint64_t L)
 {
-    const char* dummy; if (!why) why = &dummy;
-    *why = "";
-    out = T2ReadPlan{};
-    if (info.num_layers != 1) { *why = "the device reader takes files of one quality layer"; return GRK_AMD_ERR_UNSUPPORTED; }
-    out.ht = !info.base.reserved[0];
-    if (!out.ht && (info.base.reserved[1] & 0x05)) {
-        *why = "the device reader takes Part-1 code-blocks of one codeword segment (no LAZY, no TERMALL)";
-        return GRK_AMD_ERR_UNSUPPORTED;
-    }
     out.sop = (info.flags & GRK_AMD_CS_SOP) != 0; out.eph = (info.flags & GRK_AMD_CS_EPH) != 0;
     out.plt = (info.flags & GRK_AMD_CS_PLT) != 0;
     out.num_tiles = info.num_tiles;
@@ -118,6 +111,7 @@ int grk_amd::plan_t2_read(const grk_amd_stream_info& info, T2ReadPlan& out, cons
                     d.nblocks += G.gw * G.gh;
                 }
                 d.node_n = (uint32_t)(node_at - d.node_at);
+                if (lpk) lpk->push_back(T2ReadLayerPk{0, 0, (uint32_t)tile_blocks, 0});
                 tile_blocks += d.nblocks;
                 cl.max_chain_blocks = std::max(cl.max_chain_blocks, d.nblocks);
                 if (node_at > 0x7FFFFFFFull) { *why = "tag trees beyond 2^31 nodes"; return GRK_AMD_ERR_UNSUPPORTED; }
@@ -125,23 +119,67 @@ int grk_amd::plan_t2_read(const grk_amd_stream_info& info, T2ReadPlan& out, cons
             }
             if (tile_blocks != nrows) { *why = "a tile whose packets do not hold its code-blocks once each"; return GRK_AMD_ERR_INVALID; }
             if (!out.plt) cl.max_chain_blocks = (uint32_t)nrows;
+            // RLCP: the layers run inside a resolution -- a precinct's run: the packets of its resolution, which follow each other
+            for (size_t i = 0; lpk && i < seq.size();) {
+                size_t j = i;
+                while (j < seq.size() && seq[j].r == seq[i].r) ++j;
+                for (size_t k = i; k < j; ++k) { (*lpk)[cl.first_packet + k].run_first = (uint32_t)i; (*lpk)[cl.first_packet + k].run_count = (uint32_t)(j - i); }
+                i = j;
+            }
             cl.node_bytes = (uint32_t)((node_at + 15) & ~15ull);
             it = seen.emplace(key, (uint32_t)out.classes.size()).first;
             out.classes.push_back(cl);
         }
         const T2ReadClass& cl = out.classes[it->second];
         T2ReadTile& T = out.tiles[t];
-        T.cls = it->second; T.first_packet = cl.first_packet; T.npackets = cl.npackets;
+        if (cl.npackets * L > 0x7FFFFFFFull) { *why = "tables beyond the device reader's 32-bit fields"; return GRK_AMD_ERR_UNSUPPORTED; }
+        T.cls = it->second; T.first_packet = cl.first_packet; T.npackets = (uint32_t)(cl.npackets * L);
         T.row_base = (uint32_t)rows; T.rows = cl.rows;
         T.chain_base = (uint32_t)chains; T.nchains = out.plt ? cl.npackets : 1u;
         T.pkt_base = (uint32_t)pkts; T.node_base = (uint32_t)nodes; T.node_bytes = cl.node_bytes;
-        rows += cl.rows; chains += T.nchains; pkts += cl.npackets; nodes += cl.node_bytes;
+        rows += cl.rows; chains += T.nchains; pkts += T.npackets; nodes += cl.node_bytes;
         if (rows > 0x7FFFFFFFull || chains > 0x7FFFFFFFull || pkts > 0x7FFFFFFFull || nodes > 0xFFFFFFFFull) {
             *why = "tables beyond the device reader's 32-bit fields"; return GRK_AMD_ERR_UNSUPPORTED;
         }
     }
     if (rows != info.num_blocks) { *why = "info.num_blocks"; return GRK_AMD_ERR_INVALID; }
     out.rows = rows; out.chains = chains; out.total_packets = pkts; out.node_bytes = nodes;
+    return GRK_AMD_OK;
+}
+
+int grk_amd::plan_t2_read(const grk_amd_stream_info& info, T2ReadPlan& out, const char** why)
+{
+    const char* dummy; if (!why) why = &dummy;
+    *why = "";
+    out = T2ReadPlan{};
+    if (info.num_layers != 1) { *why = "the device reader takes files of one quality layer"; return GRK_AMD_ERR_UNSUPPORTED; }
+    out.ht = !info.base.reserved[0];
+    if (!out.ht && (info.base.reserved[1] & 0x05)) {
+        *why = "the device reader takes Part-1 code-blocks of one codeword segment (no LAZY, no TERMALL)";
+        return GRK_AMD_ERR_UNSUPPORTED;
+    }
+    return plan_common(info, out, why, nullptr, 1);
+}
+
+int grk_amd::plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPlan& out, const char** why)
+{
+    const char* dummy; if (!why) why = &dummy;
+    *why = "";
+    out = T2ReadLayersPlan{};
+    if (!info.num_layers) { *why = "a file without layers"; return GRK_AMD_ERR_INVALID; }
+    T2ReadPlan& B = out.base;
+    B.ht = !info.base.reserved[0];
+    out.layers = info.num_layers; out.sty = info.base.reserved[1]; out.order = (info.flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
+    const int rc = plan_common(info, B, why, &out.lpk, info.num_layers);
+    if (rc) return rc;
+    out.segments_per_row = t2p_max_segments(B.ht, out.sty);
+    out.seg_records_per_row = t2p_max_seg_records(B.ht, out.sty, out.layers);
+    out.piece_records_per_row = t2p_max_piece_records(B.ht, out.layers);
+    // (node scratch at four bytes a node; the logs' and tables' entries are counted in 32 bits)
+    if (B.node_bytes > 0x3FFFFFFFull || B.rows * out.seg_records_per_row > 0x7FFFFFFFull || B.rows * out.piece_records_per_row > 0x7FFFFFFFull ||
+        B.rows * out.segments_per_row > 0x7FFFFFFFull) {
+        *why = "tables beyond the device reader's 32-bit fields"; return GRK_AMD_ERR_UNSUPPORTED;
+    }
     return GRK_AMD_OK;
 }
 

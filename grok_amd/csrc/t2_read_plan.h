@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/grok_amd.h"
 #include "t2_parse.h"
+#include "t2_parse_layers.h"
 #include <vector>
 
 #pragma GCC visibility push(hidden)
@@ -45,6 +46,40 @@ struct T2ReadPlan {
 // GRK_AMD_OK, or the refusal's code and in *why its reason: more than one layer, Part-1 with LAZY or TERMALL (several codeword
 // segments), tables beyond the kernels' 32-bit fields -- GRK_AMD_ERR_UNSUPPORTED --, or a tile's geometry error
 int plan_t2_read(const grk_amd_stream_info& info, T2ReadPlan& out, const char** why);
+
+// ---- the general reader: several layers, several codeword segments (t2_parse_layers.h; KC-L, KF, KP) ---------------------------------
+// what KC-L reads beside a packet descriptor (a precinct here: it has one packet per layer)
+struct T2ReadLayerPk {
+    uint32_t run_first, run_count;      // RLCP: the precincts of its resolution among the tile's, which follow each other
+    uint32_t blocks_before;             // code-blocks of the tile's precincts before it: where its share of the logs starts
+    uint32_t pad;
+};
+// one contribution's share of a codeword segment / one non-empty contribution (what the chains log and KP places)
+struct T2ReadSegRecord { uint32_t row, ordinal, len, passes_opens; };           // passes | opens << 31
+struct T2ReadPieceRecord { unsigned long long src; uint32_t row, ordinal, len, before; };
+
+struct T2ReadLayersPlan {
+    // As plan_t2_read gives it, but: a tile's npackets and pkt_base count the packets of ALL layers (KH's PLT scratch), its chains
+    // are its precincts (with PLT: a chain reads the precinct's L packets) or the tile (without), node_base / node_bytes / node_at
+    // count 32-bit nodes, and a class's npackets its precincts
+    T2ReadPlan base;
+    uint32_t layers = 1, order = 0, sty = 0;
+    std::vector<T2ReadLayerPk> lpk;     // beside base.packets
+    // The logs are sized by the worst case: per row what no stream can exceed (a record carries a pass, a row has 164 at most; see
+    // t2_parse_layers.h), so a chain's share -- its rows' -- starts at (the tile's row_base + blocks_before) * records per row
+    uint32_t seg_records_per_row = 1, piece_records_per_row = 1, segments_per_row = 1;
+    uint64_t bytes_nodes() const { return base.node_bytes * 4; }
+    uint64_t bytes_state() const { return base.rows * sizeof(T2pRowState); }
+    uint64_t bytes_seg_log() const { return base.rows * seg_records_per_row * sizeof(T2ReadSegRecord); }
+    uint64_t bytes_piece_log() const { return base.rows * piece_records_per_row * sizeof(T2ReadPieceRecord); }
+    uint64_t bytes_counts() const { return base.chains * 8; }                                  // per chain: records in its two logs
+    uint64_t bytes_segments() const { return base.rows * segments_per_row * sizeof(grk_amd_segment); }
+    uint64_t bytes_moves() const { return base.rows * piece_records_per_row * sizeof(grk_amd_tp_segment); }
+    uint64_t bytes_lpk() const { return (uint64_t)lpk.size() * sizeof(T2ReadLayerPk); }
+};
+// GRK_AMD_OK, or GRK_AMD_ERR_UNSUPPORTED for tables beyond the kernels' 32-bit fields, or a tile's geometry error.  Takes every
+// layer count and code-block style the host reader takes
+int plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPlan& out, const char** why);
 
 // ---- locating the tile-parts from TLM (the host's share of KL) ------------------------------------------------------------------------
 // The main header's bytes [0, n) (all of it, to the first SOT) of a stream of `len` bytes: TLM's entries in marker order as

@@ -958,9 +958,10 @@ uint64_t grk_amd_decode_image_counters(grk_amd_ctx* ctx, int which);
 /* ---- a codestream that lies in DEVICE memory, read where it lies ---------------------------------------------------------------
  * Every grk_amd_encode_*_device call leaves its file (SOC .. EOC) in device memory; so do peer and storage DMA.  These calls read
  * such a file without bringing its body to the host: the packet headers are parsed by kernels (KL: the tile-parts located, KH: the
- * tile-part headers with PLT, KC: the packets, one wave per chain -- with PLT a packet, without a tile).  They take files of ONE
- * quality layer, HT or Part-1 without LAZY / TERMALL; everything else is GRK_AMD_ERR_UNSUPPORTED before any launch.  d_cs is read
- * in the order of the context's stream; every call here but a grk_amd_decode_image_device into device pixels returns synchronised.
+ * tile-part headers with PLT, KC: the packets, one wave per chain -- with PLT a packet, without a tile).  The first three take
+ * files of ONE quality layer, HT or Part-1 without LAZY / TERMALL; everything else is GRK_AMD_ERR_UNSUPPORTED before any launch --
+ * several layers and LAZY / TERMALL are read by the _ex calls below, which are asked for by name.  d_cs is read in the order of the
+ * context's stream; every call here but a decode into device pixels returns synchronised.
  *
  * grk_amd_read_header_device: grk_amd_read_header for such a stream.  Only the main header comes to the host: a first copy of
  *   GRK_AMD_READ_DEVICE_FIRST_COPY bytes and, where the header is longer (a long COM, a TLM of thousands of tiles), a second copy
@@ -979,6 +980,29 @@ int64_t grk_amd_read_packets_device(grk_amd_ctx* ctx, const void* d_cs, uint64_t
                                     grk_amd_coded_block* rows, uint64_t row_cap);
 int grk_amd_decode_image_device(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device);
 uint64_t grk_amd_read_device_counters(grk_amd_ctx* ctx, int which);
+/* The GENERAL reader of a stream in device memory, asked for by name (the three calls above keep what they take and refuse): 1 .. N
+ * quality layers, HT blocks of one pass in all, Part-1 blocks of every style grk_amd_read_packets takes -- LAZY and TERMALL segments
+ * carried on across layers among them --, with or without PLT / TLM / SOP / EPH, every progression order, precinct grid, tile
+ * layout and sub-sampling.  It refuses what grk_amd_read_packets refuses, with its code.  KL and KH as above; KC-L: one wave per
+ * chain -- with PLT a precinct with its packets of every layer, without a tile in file order -- logs what each contribution adds;
+ * KF finishes the rows and scans them (first_segment, the appendix, the moves); KP places the logs' records.
+ *
+ * grk_amd_read_packets_device_ex: grk_amd_read_packets for such a stream, with that call's contract: rows == NULL returns only the
+ *   sizes; GRK_AMD_ERR_OVERFLOW when a capacity is too small (or moves == NULL where there are moves); offsets at or behind `len`
+ *   point into an appendix of *appendix_bytes; moves have kind 1, src in the stream and dst counted from 0 in the appendix.  All
+ *   output arrays are HOST memory; first_segment has rows + 1 entries.  rows, first_segment, segments and *appendix_bytes are
+ *   grk_amd_read_packets' field for field; the moves are its moves as a set, here in the order of their dst.
+ * grk_amd_decode_image_device_ex: grk_amd_decode_image_device on top of it.  Without an appendix -- every single-layer file, LAZY /
+ *   TERMALL included, and layered files whose blocks all have one piece -- the stream is the coded buffer, nothing is copied.  With
+ *   one, the context stages [stream | appendix] in its own coded buffer (one device-to-device copy of `len` bytes: the decoders take
+ *   one coded base) and the gather fills the appendix from moves that never leave the device.  d_cs is only read, and nothing is
+ *   assumed about memory behind d_cs + len.
+ * grk_amd_read_device_counters: 4 bytes the _ex decode copied device to device, 5 launches of KC-L. */
+int64_t grk_amd_read_packets_device_ex(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, const grk_amd_stream_info* info,
+                                       grk_amd_coded_block* rows, uint64_t row_cap,
+                                       uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                       grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
+int grk_amd_decode_image_device_ex(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device);
 /* The placement kernel with clipping (device pointers; queued on the context's stream): as grk_amd_place_tiles_device, but unit i
  * goes to the SIGNED position (pos[2 i], pos[2 i + 1]) of the destination's planes and only what falls inside img_w x img_h is
  * written (a unit wholly outside: nothing).  channels = 0: ncomp planes; channels != 0: the units and the destination hold

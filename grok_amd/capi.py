@@ -453,6 +453,8 @@ def lib():
             L.grk_amd_read_packets.restype = C.c_int64
             L.grk_amd_read_packets.argtypes = [vp, u64, C.POINTER(StreamInfo), u32, vp, u64, vp, vp, u64, C.POINTER(u64), vp, u64,
                                                C.POINTER(u64), C.POINTER(u64)]
+            L.grk_amd_read_packets_parts.restype = C.c_int64
+            L.grk_amd_read_packets_parts.argtypes = L.grk_amd_read_packets.argtypes
             L.grk_amd_reader_last_error.restype = C.c_char_p
             L.grk_amd_decode_image.argtypes = [vp, vp, u64, vp, u64, i32]
             L.grk_amd_decode_image_launches.restype = u64
@@ -737,11 +739,12 @@ def plan_image_view(info, reduce=0, window=None):
     return dict(tiles=tiles, units=units)
 
 
-def read_packets(cs, info=None, threads=1):
+def read_packets(cs, info=None, threads=1, _call="grk_amd_read_packets"):
     """grk_amd_read_packets: every packet header of every tile -> dict(rows CODED_DTYPE, first_segment uint32 [rows + 1],
     segments SEGMENT_DTYPE, moves MOVE_DTYPE, appendix_bytes).  A row's offset points into `cs`, or -- at or behind len(cs) --
     into the appendix that `moves` fill."""
     L = lib()
+    call = getattr(L, _call)
     buf = _cs_array(cs)
     if info is None:
         info = read_header(buf)
@@ -754,16 +757,22 @@ def read_packets(cs, info=None, threads=1):
         first = np.zeros(nrows + 1, np.uint32)
         segs = np.zeros(seg_cap, SEGMENT_DTYPE)
         moves = np.zeros(move_cap, MOVE_DTYPE)
-        n = L.grk_amd_read_packets(buf.ctypes.data, buf.size, C.byref(info), threads, rows.ctypes.data, rows.size, first.ctypes.data,
-                                   segs.ctypes.data, segs.size, C.byref(nseg), moves.ctypes.data, moves.size, C.byref(nmov), C.byref(app))
+        n = call(buf.ctypes.data, buf.size, C.byref(info), threads, rows.ctypes.data, rows.size, first.ctypes.data,
+                 segs.ctypes.data, segs.size, C.byref(nseg), moves.ctypes.data, moves.size, C.byref(nmov), C.byref(app))
         if n == ERR_OVERFLOW and (nseg.value > seg_cap or nmov.value > move_cap):
             seg_cap, move_cap = max(seg_cap, int(nseg.value)), max(move_cap, int(nmov.value))
             continue
         if n < 0:
-            raise ReaderError("read_packets", n, L.grk_amd_reader_last_error().decode())
+            raise ReaderError(_call[len("grk_amd_"):], n, L.grk_amd_reader_last_error().decode())
         break
     segs, moves = segs[:nseg.value], moves[:nmov.value]
     return dict(rows=rows, first_segment=first, segments=segs, moves=moves, appendix_bytes=int(app.value))
+
+
+def read_packets_parts(cs, info=None, threads=1):
+    """grk_amd_read_packets_parts: read_packets for a codestream whose tiles may be divided into tile-parts (1..255 per tile); the
+    same dict, every offset and every move's src a position in `cs`."""
+    return read_packets(cs, info, threads, "grk_amd_read_packets_parts")
 
 
 class Context:
@@ -1557,6 +1566,8 @@ class Context:
             L.grk_amd_read_packets_device_ex.argtypes = [vp, vp, u64, C.POINTER(StreamInfo), vp, u64, vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
                                                          C.POINTER(u64)]
             L.grk_amd_decode_image_device_ex.argtypes = [vp, vp, u64, vp, u64, C.c_int]
+            L.grk_amd_read_packets_device_parts.restype = C.c_int64
+            L.grk_amd_read_packets_device_parts.argtypes = L.grk_amd_read_packets_device_ex.argtypes
             L.grk_amd_read_device_counters.restype = u64
             L.grk_amd_read_device_counters.argtypes = [vp, C.c_int]
             L._read_device_bound = True
@@ -1592,27 +1603,37 @@ class Context:
         if rc:
             raise ReaderError("decode_image_resident", rc, self.last_error())
 
-    def read_packets_device_ex(self, d_cs, nbytes, info=None):
+    def read_packets_device_parts(self, d_cs, nbytes, info=None):
+        """grk_amd_read_packets_device_parts: read_packets_device_ex for a codestream whose tiles may be divided into tile-parts -> the
+        dict read_packets_parts gives for the same bytes (the moves in the order of their dst)."""
+        return self.read_packets_device_ex(d_cs, nbytes, info, "grk_amd_read_packets_device_parts")
+
+    def read_device_parts_launches(self):
+        """launches of KL-P / KH-P by this context's calls so far (grk_amd_read_device_counters, index 6)"""
+        return int(self._read_device_fns().grk_amd_read_device_counters(self._h, 6))
+
+    def read_packets_device_ex(self, d_cs, nbytes, info=None, _call="grk_amd_read_packets_device_ex"):
         """grk_amd_read_packets_device_ex: the general reader -- layers, LAZY / TERMALL -- of the codestream at device pointer d_cs
         -> the dict read_packets gives for the same bytes (the moves in the order of their dst); ReaderError with its code when
         refused."""
         L = self._read_device_fns()
+        call = getattr(L, _call)
         if info is None:
             info = self.read_header_device(d_cs, nbytes)
         nseg, nmov, app = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         # the sizes first, then the tables
-        n = L.grk_amd_read_packets_device_ex(self._h, int(d_cs), int(nbytes), C.byref(info), None, 0, None, None, 0, C.byref(nseg), None, 0, C.byref(nmov),
+        n = call(self._h, int(d_cs), int(nbytes), C.byref(info), None, 0, None, None, 0, C.byref(nseg), None, 0, C.byref(nmov),
                                              C.byref(app))
         if n < 0:
-            raise ReaderError("read_packets_device_ex", n, self.last_error())
+            raise ReaderError(_call[len("grk_amd_"):], n, self.last_error())
         rows = np.zeros(int(n), CODED_DTYPE)
         first = np.zeros(int(n) + 1, np.uint32)
         segs = np.zeros(int(nseg.value), SEGMENT_DTYPE)
         moves = np.zeros(int(nmov.value), MOVE_DTYPE)
-        n = L.grk_amd_read_packets_device_ex(self._h, int(d_cs), int(nbytes), C.byref(info), rows.ctypes.data, rows.size, first.ctypes.data, segs.ctypes.data,
+        n = call(self._h, int(d_cs), int(nbytes), C.byref(info), rows.ctypes.data, rows.size, first.ctypes.data, segs.ctypes.data,
                                              segs.size, C.byref(nseg), moves.ctypes.data, moves.size, C.byref(nmov), C.byref(app))
         if n < 0:
-            raise ReaderError("read_packets_device_ex", n, self.last_error())
+            raise ReaderError(_call[len("grk_amd_"):], n, self.last_error())
         return dict(rows=rows, first_segment=first, segments=segs, moves=moves, appendix_bytes=int(app.value))
 
     def decode_image_resident_ex(self, d_cs, nbytes, pixels, cap, on_device=True):

@@ -194,15 +194,25 @@ void plan_coded(uint64_t len, uint32_t num_layers, bool all, const std::vector<u
     const uint32_t ntt = (uint32_t)tiles.size();
     o = CodedPlan{};
     o.part_to.assign(ntt, 0);
+    o.span_at.assign(ntt + 1, 0);
     o.up_len = len;
     if (all) o.copies.push_back(CodedCopy{0, 0, len});
     else {
+        // tile after tile, a tile's tile-parts in their order (each tile's chain ends within its 255)
         o.up_len = 0;
-        for (uint32_t i = 0; i < ntt; ++i) { o.part_to[i] = o.up_len; o.up_len += parts[tiles[i]].len; }
-        for (uint32_t i = 0, j; i < ntt; i = j) {        // tile-parts that follow each other in the file: one copy
-            uint64_t n = parts[tiles[i]].len;
-            for (j = i + 1; j < ntt && parts[tiles[j]].at == parts[tiles[i]].at + n; ++j) n += parts[tiles[j]].len;
-            o.copies.push_back(CodedCopy{o.part_to[i], parts[tiles[i]].at, n});
+        for (uint32_t i = 0; i < ntt; ++i) {
+            o.part_to[i] = o.up_len;
+            for (uint32_t idx = tiles[i], k = 0; k < 255; idx = parts[idx].next, ++k) {
+                o.spans.push_back(CodedSpan{parts[idx].at, parts[idx].len, o.up_len});
+                o.up_len += parts[idx].len;
+                if (!parts[idx].next || parts[idx].next >= parts.size()) break;
+            }
+            o.span_at[i + 1] = (uint32_t)o.spans.size();
+        }
+        for (size_t i = 0, j; i < o.spans.size(); i = j) {        // tile-parts that follow each other in the file: one copy
+            uint64_t n = o.spans[i].len;
+            for (j = i + 1; j < o.spans.size() && o.spans[j].at == o.spans[i].at + n; ++j) n += o.spans[j].len;
+            o.copies.push_back(CodedCopy{o.spans[i].to, o.spans[i].at, n});
         }
     }
     // (an appendix holds bytes of what is uploaded: never more than that)
@@ -223,21 +233,28 @@ int rebase_table(StreamTable& tab, uint64_t len, bool all, const std::vector<uin
     const uint32_t ntt = (uint32_t)tiles.size(), nr = dest.nr, nu = ntt * nr;
     const uint64_t up_len = coded.up_len;
     if (!all) {
-        // the reader's offsets are positions in the codestream (the appendix behind it): onto the compact buffer
+        // the reader's offsets are positions in the codestream (the appendix behind it): onto the compact buffer, each through the
+        // tile-part of its tile that it lies in (a tile's tile-parts rise in the file)
+        if (coded.span_at.size() != (size_t)ntt + 1) return refuse(why, GRK_AMD_ERR_INVALID, "the coded plan does not fit the tiles");
         for (uint32_t i = 0; i < ntt; ++i) {
-            const StreamPart& sp = parts[tiles[i]];
+            const CodedSpan* const s0 = coded.spans.data() + coded.span_at[i];
+            const CodedSpan* const s1 = coded.spans.data() + coded.span_at[i + 1];
+            auto onto = [&](uint64_t& at) -> bool {
+                const CodedSpan* sp = std::upper_bound(s0, s1, at, [](uint64_t v, const CodedSpan& q) { return v < q.at; });
+                if (sp == s0) return false;
+                --sp;
+                if (at - sp->at > sp->len) return false;
+                at = at - sp->at + sp->to;
+                return true;
+            };
             for (uint64_t k = tab.row_at[i]; k < tab.row_at[i + 1]; ++k) {
                 grk_amd_coded_block& row = tab.rows[k];
                 if (!row.length) continue;
                 if (row.offset >= len) row.offset = row.offset - len + up_len;
-                else if (row.offset < sp.at || row.offset - sp.at > sp.len) return refuse(why, GRK_AMD_ERR_INVALID, "a block outside its tile-part");
-                else row.offset = row.offset - sp.at + coded.part_to[i];
+                else if (!onto(row.offset)) return refuse(why, GRK_AMD_ERR_INVALID, "a block outside its tile-part");
             }
-            for (uint64_t k = tab.move_at[i]; k < tab.move_at[i + 1]; ++k) {
-                grk_amd_tp_segment& m = tab.moves[k];
-                if (m.src < sp.at || m.src - sp.at > sp.len) return refuse(why, GRK_AMD_ERR_INVALID, "a block outside its tile-part");
-                m.src = m.src - sp.at + coded.part_to[i];
-            }
+            for (uint64_t k = tab.move_at[i]; k < tab.move_at[i + 1]; ++k)
+                if (!onto(tab.moves[k].src)) return refuse(why, GRK_AMD_ERR_INVALID, "a block outside its tile-part");
         }
     }
     coded.coded_bytes = up_len + tab.appendix_bytes;

@@ -93,10 +93,14 @@ int plan_image_dest(const grk_amd_stream_info& info, const ViewPlan& plan, const
                     const char** why);
 
 // ---- the coded buffer ----------------------------------------------------------------------------------------------------------
-// the codestream itself, or -- a view that leaves tiles out -- the touched tiles' tile-parts end to end in index order
+// the codestream itself, or -- a view that leaves tiles out -- the touched tiles' tile-parts end to end: the tiles in index order,
+// a tile's tile-parts in theirs
 struct CodedCopy { uint64_t to, from, n; };
+struct CodedSpan { uint64_t at; uint32_t len; uint64_t to; };      // a tile-part: where it lies in the file, its bytes, where in the buffer
 struct CodedPlan {
-    std::vector<uint64_t> part_to;          // [touched tile]: where its tile-part starts in the buffer
+    std::vector<uint64_t> part_to;          // [touched tile]: where its first tile-part starts in the buffer
+    std::vector<uint32_t> span_at;          // [touched tiles + 1]: the tile's tile-parts in `spans`
+    std::vector<CodedSpan> spans;
     uint64_t up_len = 0, coded_cap = 0;     // bytes uploaded; with the room of an appendix (never more than what is uploaded)
     uint64_t coded_bytes = 0;               // (rebase_table) bytes uploaded + the appendix the reader found
     std::vector<CodedCopy> copies;          // host to device, tile-parts that follow each other in the file as one

@@ -488,4 +488,24 @@ hipError_t launch_t2read_chains_layers(const T2ReadLayersArgs& g, hipStream_t s)
 hipError_t launch_t2read_finish(const T2ReadLayersArgs& g, hipStream_t s);
 hipError_t launch_t2read_place(const T2ReadLayersArgs& g, hipStream_t s);
 
+// ---- tiles divided into tile-parts (KL-P, KH-P, KC-L over a tile's part table; KF and KP as above) ------------------------------------
+// g.a.part_at / part_len / first_of and g.a.tlm are not used.  KH-P leaves in g.a.body_at[tile] a non-zero word for a tile whose headers
+// were read, in g.a.has_plt[tile] whether it is a PLT tile (every tile-part that holds packets lists exactly its own).
+struct T2ReadPartsArgs {
+    T2ReadLayersArgs g;
+    uint32_t cap;                                    // tile-parts the arrays below hold
+    uint32_t n_given;                                // TLM: the file's tile-parts, fo_* filled by the host; 0: KL-P hops along Psot
+    // [cap] in file order: where, how long, TLM's tile index (0xFFFFFFFF: TLM names none); KL-P's claim on a table slot
+    unsigned long long* fo_at; uint32_t* fo_len; uint32_t* fo_idx; uint32_t* claim;
+    // [tile]: its tile-parts, its smallest and largest non-zero TNsot; [tiles + 1]: its slice of the part table
+    uint32_t* count; uint32_t* tn_min; uint32_t* tn_max; uint32_t* slice;
+    // the part table, [cap]: a tile's tile-parts at slice[tile] + TPsot
+    unsigned long long* tp_at; uint32_t* tp_len; uint32_t* tp_tile; uint32_t* tp_file;
+    unsigned long long* tp_body; uint32_t* tp_has_plt; uint32_t* tp_npk; uint32_t* tp_first;
+    unsigned long long* located;                     // [1]: the tile-parts found
+};
+hipError_t launch_t2read_locate_parts(const T2ReadPartsArgs& p, hipStream_t s);
+hipError_t launch_t2read_headers_parts(const T2ReadPartsArgs& p, uint32_t nparts, hipStream_t s);
+hipError_t launch_t2read_chains_parts(const T2ReadPartsArgs& p, hipStream_t s);
+
 } // namespace grk_amd

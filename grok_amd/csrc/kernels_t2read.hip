@@ -542,4 +542,365 @@ hipError_t launch_t2read_place(const T2ReadLayersArgs& g, hipStream_t s)
     return hipGetLastError();
 }
 
+// ==== tiles divided into tile-parts (grk_amd_read_packets_device_parts) ==============================================================
+//   KL-P locate    every tile-part of the file.  With TLM the host has the places; without, one lane hops along the Psot chain, at
+//                  most `cap` hops (cap <= len / 14 + 1).  All lanes then check the SOTs (striding: more than 256 tile-parts) and
+//                  count the tile-parts of every tile, a scan over the tiles gives each its slice of the part table, and every
+//                  tile-part goes to slice + TPsot: a slot claimed twice, a TPsot beyond the tile's count, a slot's file place
+//                  before its predecessor's, the TNsot rules and a 256th tile-part are refusals.  One workgroup.
+//   KH-P headers   a workgroup per tile-part walks its marker segments and counts its PLT entries; then a workgroup per tile scans
+//                  its tile-parts' counts into each one's first PLT entry, decides whether the tile is a PLT tile, checks the counts
+//                  against the tile's packets, and assembles the entries (KH's parallel assembly) and, for a PLT tile, the packet starts.
+//   KC-L over the part table: a precinct chain looks up the tile-part its packet starts in for the packet's `end`; a chain that reads
+//                  the tile in file order steps from body to body (t2_parse_layers.h: t2p_part_step).  KF and KP as they are.
+namespace {
+__device__ __forceinline__ uint32_t load_u32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+}
+
+__global__ __launch_bounds__(256) void t2read_locate_parts_kernel(T2ReadPartsArgs p)
+{
+    __shared__ uint64_t s_scan[256];
+    __shared__ unsigned long long s_n;
+    __shared__ uint32_t s_fail;
+    const T2ReadArgs& a = p.g.a;
+    const uint32_t tid = threadIdx.x, nt = a.num_tiles, cap = p.cap;
+    DirectSrc src{a.cs};
+    for (uint32_t t = tid; t < nt; t += 256) { p.count[t] = 0; p.tn_min[t] = 0xFFFFFFFFu; p.tn_max[t] = 0; p.slice[t] = 0; a.body_at[t] = 0; a.has_plt[t] = 0; }
+    if (tid == 0) p.slice[nt] = 0;
+    for (uint32_t j = tid; j < cap; j += 256) {
+        p.claim[j] = 0xFFFFFFFFu; p.tp_at[j] = 0; p.tp_len[j] = 0; p.tp_tile[j] = 0; p.tp_file[j] = 0;
+        p.tp_body[j] = 0; p.tp_has_plt[j] = 0; p.tp_npk[j] = 0; p.tp_first[j] = 0;
+    }
+    if (tid == 0) {
+        s_fail = 0;
+        uint64_t n = p.n_given < cap ? p.n_given : cap;
+        if (!p.n_given) {
+            // the Psot chain: every hop checked against the stream's length and at least 14 bytes long
+            uint64_t at = a.sot_at;
+            n = 0;
+            for (uint32_t hop = 0; hop <= cap; ++hop) {
+                uint64_t l = 0;
+                const int r = t2p_hop(src, a.len, at, &l);
+                if (r == 0) break;
+                if (r == 2) { s_fail = kT2pNotLocated; break; }
+                if (n == cap) { s_fail = kT2pPartsOfFile; break; }
+                p.fo_at[n] = at; p.fo_len[n] = (uint32_t)l; p.fo_idx[n] = 0xFFFFFFFFu;
+                ++n; at += l;
+            }
+            if (n == 0 && !s_fail) s_fail = kT2pNotLocated;
+        }
+        s_n = n;
+        p.located[0] = n;
+    }
+    __threadfence();
+    __syncthreads();
+    if (s_fail) { if (tid == 0) report(a.status, t2p_status_locate((uint32_t)s_n, s_fail)); return; }
+    const uint32_t n = (uint32_t)s_n;
+    // pass 1: every SOT; the tile-parts of every tile counted
+    for (uint32_t i = tid; i < n; i += 256) {
+        uint32_t isot = 0, tps = 0, tn = 0;
+        const uint32_t why = t2p_check_sot_part(src, a.len, p.fo_at[i], p.fo_len[i], nt, p.fo_idx[i], i + 1 == n, &isot, &tps, &tn);
+        if (why) { report(a.status, t2p_status_locate(i, why)); continue; }
+        atomicAdd(&p.count[isot], 1u);
+        if (tn) { atomicMin(&p.tn_min[isot], tn); atomicMax(&p.tn_max[isot], tn); }
+    }
+    __threadfence();
+    __syncthreads();
+    // every tile's slice of the table
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < nt; base += 256) {
+        const uint32_t t = base + tid;
+        const uint64_t v = t < nt ? load_u32(&p.count[t]) : 0;
+        uint64_t total = 0;
+        const uint64_t incl = scan256(v, s_scan, &total);
+        if (t < nt) p.slice[t] = (uint32_t)(carry + incl - v);
+        carry += total;
+    }
+    if (tid == 0) p.slice[nt] = (uint32_t)carry;
+    __threadfence();
+    __syncthreads();
+    // pass 2: the slot slice + TPsot, claimed by the first tile-part in the file that names it
+    for (uint32_t i = tid; i < n; i += 256) {
+        uint32_t isot = 0, tps = 0, tn = 0;
+        if (t2p_check_sot_part(src, a.len, p.fo_at[i], p.fo_len[i], nt, p.fo_idx[i], i + 1 == n, &isot, &tps, &tn)) continue;
+        if (tps < load_u32(&p.count[isot])) { const uint32_t slot = load_u32(&p.slice[isot]) + tps; if (slot < cap) atomicMin(&p.claim[slot], i); }
+    }
+    __threadfence();
+    __syncthreads();
+    for (uint32_t i = tid; i < n; i += 256) {
+        uint32_t isot = 0, tps = 0, tn = 0;
+        if (t2p_check_sot_part(src, a.len, p.fo_at[i], p.fo_len[i], nt, p.fo_idx[i], i + 1 == n, &isot, &tps, &tn)) continue;
+        const uint32_t c = load_u32(&p.count[isot]), mn = load_u32(&p.tn_min[isot]), mx = load_u32(&p.tn_max[isot]);
+        const uint32_t slot = load_u32(&p.slice[isot]) + tps;
+        uint32_t why = kT2pOk;
+        if (c > kT2pMaxPartsOfTile && tps >= kT2pMaxPartsOfTile) why = kT2pPartsOfTile;
+        else if (tps >= c || slot >= cap || load_u32(&p.claim[slot]) != i) why = kT2pTpsot;
+        else if ((tn && mn != mx) || (mx && mx <= tps)) why = kT2pTnsot;
+        if (why) { report(a.status, t2p_status_locate(i, why)); continue; }
+        p.tp_at[slot] = p.fo_at[i]; p.tp_len[slot] = p.fo_len[i]; p.tp_tile[slot] = isot; p.tp_file[slot] = i;
+    }
+    __threadfence();
+    __syncthreads();
+    // pass 3: a tile's tile-parts lie in the file in TPsot order; every tile has one; TNsot is not beyond them
+    for (uint32_t j = tid; j + 1 < n; j += 256) {
+        if (load_u32(&p.claim[j]) == 0xFFFFFFFFu || load_u32(&p.claim[j + 1]) == 0xFFFFFFFFu) continue;
+        if (p.tp_len[j] && p.tp_len[j + 1] && p.tp_tile[j] == p.tp_tile[j + 1] && p.tp_file[j + 1] < p.tp_file[j])
+            report(a.status, t2p_status_locate(p.tp_file[j + 1], kT2pTpsot));
+    }
+    for (uint32_t t = tid; t < nt; t += 256) {
+        const uint32_t c = load_u32(&p.count[t]);
+        if (!c) report(a.status, t2p_status_locate(n + 1 + t, kT2pNoPart));
+        else if (load_u32(&p.tn_max[t]) > c) report(a.status, t2p_status_locate(n + 1 + t, kT2pTnsot));
+    }
+}
+
+// KH-P, first step: the tile-part in slot blockIdx.x -- its marker segments walked, its PLT entries counted and checked
+__global__ __launch_bounds__(256) void t2read_headers_parts_kernel(T2ReadPartsArgs p)
+{
+    __shared__ uint64_t s_scan[256];
+    __shared__ int s_kind;
+    __shared__ unsigned long long s_next, s_lo, s_hi;
+    __shared__ uint32_t s_fail;
+    const T2ReadArgs& a = p.g.a;
+    const uint32_t j = blockIdx.x, tid = threadIdx.x;
+    if (j >= p.cap) return;
+    const uint32_t ln = p.tp_len[j];
+    if (!ln) return;
+    const uint32_t t = p.tp_tile[j];
+    if (t >= a.num_tiles) return;
+    const uint32_t part = j - p.slice[t];
+    const uint64_t npk = a.tiles[t].npackets;
+    const uint64_t at = p.tp_at[j], end = at + ln;
+    DirectSrc src{a.cs};
+    uint64_t pos = at + 12, count = 0;
+    bool have_plt = false;
+    if (tid == 0) s_fail = 0;
+    for (uint32_t hop = 0, hops = ln / 4 + 2; hop < hops; ++hop) {
+        __syncthreads();
+        if (tid == 0) {
+            uint64_t next = 0, lo = 0, hi = 0;
+            s_kind = t2p_header_segment(src, pos, end, &next, &lo, &hi);
+            s_next = next; s_lo = lo; s_hi = hi;
+        }
+        __syncthreads();
+        const int kind = s_kind;
+        if (kind < 0) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, part, (uint32_t)-kind)); return; }
+        pos = s_next;
+        if (kind == 0) break;
+        if (kind != 1) continue;
+        have_plt = true;
+        const uint64_t lo = s_lo, hi = s_hi;
+        for (uint64_t base = lo; base < hi; base += 256) {
+            const uint64_t i = base + tid;
+            const bool term = i < hi && t2p_plt_terminator(src, i);
+            uint64_t total = 0;
+            (void)scan256(term ? 1u : 0u, s_scan, &total);
+            if (term) {
+                uint32_t v = 0;
+                const uint32_t why = t2p_plt_entry(src, lo, i, &v);
+                if (why) atomicMax(&s_fail, why);
+            }
+            count += total;
+            if (count > npk) atomicMax(&s_fail, (uint32_t)kT2pPltMany);
+            __syncthreads();
+            if (s_fail) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, part, s_fail)); return; }
+        }
+        if (hi > lo && !t2p_plt_terminator(src, hi - 1)) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, part, kT2pPltCount)); return; }
+    }
+    if (s_kind != 0) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, part, kT2pNoSod)); return; }
+    if (tid == 0) { p.tp_body[j] = pos; p.tp_has_plt[j] = have_plt ? 1u : 0u; p.tp_npk[j] = (uint32_t)count; }
+}
+
+// KH-P, second step: the tile blockIdx.x over its tile-parts
+__global__ __launch_bounds__(256) void t2read_tile_parts_kernel(T2ReadPartsArgs p)
+{
+    __shared__ uint64_t s_scan[256];
+    __shared__ int s_kind;
+    __shared__ unsigned long long s_next, s_lo, s_hi;
+    __shared__ uint32_t s_fail, s_any, s_missing;
+    const T2ReadArgs& a = p.g.a;
+    const uint32_t t = blockIdx.x, tid = threadIdx.x;
+    const uint32_t j0 = p.slice[t], np = p.slice[t + 1] - j0;
+    if (!np || np > kT2pMaxPartsOfTile || j0 + np > p.cap) return;
+    const T2ReadTile T = a.tiles[t];
+    const uint64_t npk = T.npackets;
+    DirectSrc src{a.cs};
+    if (tid == 0) { s_fail = 0; s_any = 0; s_missing = 0; }
+    __syncthreads();
+    const bool mine = tid < np;
+    const uint64_t body = mine ? p.tp_body[j0 + tid] : 0;
+    const uint64_t bytes = mine && body ? p.tp_at[j0 + tid] + p.tp_len[j0 + tid] - body : 0;
+    const uint32_t cnt = mine ? p.tp_npk[j0 + tid] : 0, has = mine ? p.tp_has_plt[j0 + tid] : 0;
+    if (mine && !body) atomicMax(&s_fail, 1u);                   // (a tile-part whose header was refused: reported there)
+    if (has) atomicMax(&s_any, 1u);
+    if (mine && bytes && !has) atomicMax(&s_missing, 1u);
+    uint64_t all = 0, room = 0;
+    const uint64_t incl = scan256(cnt, s_scan, &all);
+    (void)scan256(bytes, s_scan, &room);
+    __syncthreads();
+    if (s_fail) return;
+    if (all > npk) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, 0, kT2pPltMany)); return; }
+    if (npk > room) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, 0, kT2pPacketsBytes)); return; }
+    const bool plt_tile = np == 1 ? p.tp_has_plt[j0] != 0 : (s_any && !s_missing);
+    if (plt_tile && all != npk) { if (tid == 0) report(a.status, t2p_status_tile(t, 0, 0, kT2pPltCount)); return; }
+    if (mine) p.tp_first[j0 + tid] = T.pkt_base + (uint32_t)(incl - cnt);
+    __threadfence();
+    __syncthreads();
+    // the entries, tile-part after tile-part (all <= npk: they fit the tile's share of plt_len)
+    for (uint32_t q = 0; q < np; ++q) {
+        const uint32_t j = j0 + q;
+        if (!p.tp_has_plt[j]) continue;
+        const uint32_t first = load_u32(&p.tp_first[j]), want = p.tp_npk[j];
+        const uint64_t at = p.tp_at[j], end = at + p.tp_len[j];
+        uint64_t pos = at + 12, count = 0;
+        for (uint32_t hop = 0, hops = p.tp_len[j] / 4 + 2; hop < hops; ++hop) {
+            __syncthreads();
+            if (tid == 0) {
+                uint64_t next = 0, lo = 0, hi = 0;
+                s_kind = t2p_header_segment(src, pos, end, &next, &lo, &hi);
+                s_next = next; s_lo = lo; s_hi = hi;
+            }
+            __syncthreads();
+            const int kind = s_kind;
+            pos = s_next;
+            if (kind <= 0) break;
+            if (kind != 1) continue;
+            const uint64_t lo = s_lo, hi = s_hi;
+            for (uint64_t base = lo; base < hi; base += 256) {
+                const uint64_t i = base + tid;
+                const bool term = i < hi && t2p_plt_terminator(src, i);
+                uint64_t total = 0;
+                const uint64_t rank = scan256(term ? 1u : 0u, s_scan, &total);
+                if (term) {
+                    const uint64_t k = count + rank - 1;
+                    uint32_t v = 0;
+                    if (!t2p_plt_entry(src, lo, i, &v) && k < want) a.plt_len[first + k] = v;
+                }
+                count += total;
+            }
+        }
+        if (!plt_tile) continue;
+        // a PLT tile: the packet starts; the lengths add up to the tile-part
+        __threadfence();
+        __syncthreads();
+        uint64_t run = p.tp_body[j];
+        for (uint64_t base = 0; base < want; base += 256) {
+            const uint64_t k = base + tid;
+            const uint64_t v = k < want ? a.plt_len[first + k] : 0;
+            uint64_t total = 0;
+            const uint64_t inc = scan256(v, s_scan, &total);
+            if (k < want) a.pk_start[first + k] = run + inc - v;
+            run += total;
+        }
+        if (run != end && tid == 0) report(a.status, t2p_status_tile(t, 0, q, kT2pPartPlt));
+    }
+    if (tid == 0) { a.body_at[t] = p.tp_body[j0]; a.has_plt[t] = plt_tile ? 1u : 0u; }
+}
+
+__global__ __launch_bounds__(64) void t2read_chains_parts_kernel(T2ReadPartsArgs p)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWin];
+    __shared__ T2ReadSegRecord s_seg[64];
+    __shared__ T2ReadPieceRecord s_piece[64];
+    const T2ReadLayersArgs& g = p.g;
+    const T2ReadArgs& a = g.a;
+    const uint32_t chain = blockIdx.x, lane = threadIdx.x;
+    if (lane == 0) { g.counts[2 * chain] = 0; g.counts[2 * chain + 1] = 0; }
+    const uint32_t t = tile_of_chain(a.tiles, a.num_tiles, chain);
+    const T2ReadTile T = a.tiles[t];
+    if (!a.body_at[t]) return;                                  // (not located, or a header refused)
+    const uint32_t j0 = p.slice[t], nparts = p.slice[t + 1] - j0;
+    if (!nparts || nparts > kT2pMaxPartsOfTile || j0 + nparts > p.cap) return;
+    const T2pParts PT{p.tp_at + j0, p.tp_len + j0, p.tp_body + j0, p.tp_has_plt + j0, p.tp_npk + j0, p.tp_first + j0, nparts};
+    const uint32_t L = g.layers, np = T.npackets / L;
+    const bool plt = a.has_plt[t] != 0, split = plt && T.nchains == np;
+    const uint32_t i0 = chain - T.chain_base;
+    if (!split && i0) return;                                   // one chain parses the tile
+    const T2ReadPacket* const pk = a.packets + T.first_packet;
+    const T2ReadLayerPk* const lp = g.lpk + T.first_packet;
+    uint32_t* const nodes = g.nodes32 + T.node_base;
+    T2pRowState* const state = g.state + T.row_base;
+    {
+        const uint32_t from = split ? pk[i0].node_at : 0u, n = split ? pk[i0].node_n : T.node_bytes;
+        for (uint32_t i = lane; i < n; i += 64) nodes[from + i] = 0;
+        uint32_t* const sw = (uint32_t*)state;
+        if (split) {
+            for (uint32_t bi = 0; bi < pk[i0].nbands; ++bi) {
+                const T2ReadBand& B = pk[i0].band[bi];
+                const uint32_t words = B.gw * B.gh * kT2pStateWords;
+                for (uint32_t i = lane; i < words; i += 64) sw[(size_t)B.first_row * kT2pStateWords + i] = 0;
+            }
+        } else for (uint64_t i = lane; i < (uint64_t)T.rows * kT2pStateWords; i += 64) sw[i] = 0;
+        __threadfence_block();
+        __syncthreads();
+    }
+    const uint64_t share = (uint64_t)T.row_base + (split ? lp[i0].blocks_before : 0u);
+    const uint32_t share_rows = split ? pk[i0].nblocks : T.rows;
+    LayerSink sink{{g.seg_log + share * g.seg_per_row, share_rows * g.seg_per_row, s_seg, 0, 0, false},
+                   {g.piece_log + share * g.piece_per_row, share_rows * g.piece_per_row, s_piece, 0, 0, false}};
+    WindowSrc src{a.cs, a.len, s_win, 0, false};
+    T2pPartWalk walk{0, 0, 0};
+    uint64_t pos = 0;
+    t2p_part_walk_start(PT, walk, pos);
+    bool failed = false;
+    auto refuse = [&](uint32_t k, uint32_t why) { if (lane == 0) report(a.status, t2p_status_tile(t, 1, k, why)); failed = true; return false; };
+    // one packet: precinct i, layer l, the tile's packet k; its `end` is the end of the tile-part it starts in
+    auto one = [&](uint32_t i, uint32_t l, uint32_t k) -> bool {
+        uint64_t end = 0;
+        if (split) {
+            pos = a.pk_start[T.pkt_base + k];
+            end = t2p_part_end(PT, t2p_part_of(PT, pos));
+        } else {
+            const uint32_t why = t2p_part_step(PT, walk, pos);
+            if (why) return refuse(k, why);
+            end = walk.end;
+        }
+        const uint64_t from = pos;
+        const uint32_t pieces0 = sink.pieces.count + sink.pieces.n;
+        uint64_t body_at = 0;
+        const uint32_t why = t2p_read_packet_layer(src, pk[i], nodes, state, a.ht != 0, g.sty, a.sop != 0, a.eph != 0, l, k, pos, end, sink, &body_at);
+        sink.segs.flush(); sink.pieces.flush();
+        if (why) return refuse(k, why);
+        __threadfence_block();
+        __syncthreads();
+        for (uint32_t j = pieces0 + lane; j < sink.pieces.count; j += 64) {
+            T2ReadPieceRecord* const r = sink.pieces.log + j;
+            const uint64_t at = body_at + r->src;
+            r->src = at;
+            if (r->ordinal == 0) { state[r->row].src_lo = (uint32_t)at; state[r->row].src_hi = (uint32_t)(at >> 32); }
+        }
+        if (split) { if (pos - from != a.plt_len[T.pkt_base + k]) return refuse(k, kT2pPltSize); }
+        else { const uint32_t w2 = t2p_part_packet(PT, walk, a.plt_len, pos - from); if (w2) return refuse(k, w2); }
+        return true;
+    };
+    if (split) {
+        for (uint32_t l = 0; l < L; ++l)
+            if (!one(i0, l, (uint32_t)t2p_packet_number(g.order, np, L, i0, l, lp[i0].run_first, lp[i0].run_count))) break;
+    } else {
+        t2p_tile_packets(g.order, np, L, [&](uint32_t i, uint32_t* first, uint32_t* count) { *first = lp[i].run_first; *count = lp[i].run_count; }, one);
+        if (!failed) { const uint32_t why = t2p_part_finish(PT, walk, pos); if (why) refuse(T.npackets, why); }
+    }
+    if ((sink.segs.over || sink.pieces.over) && lane == 0) report(a.status, t2p_status_tile(t, 1, T.npackets, kT2pPasses));
+    if (lane == 0) { g.counts[2 * chain] = sink.segs.count; g.counts[2 * chain + 1] = sink.pieces.count; }
+}
+
+hipError_t launch_t2read_locate_parts(const T2ReadPartsArgs& p, hipStream_t s)
+{
+    hipLaunchKernelGGL(t2read_locate_parts_kernel, dim3(1), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_t2read_headers_parts(const T2ReadPartsArgs& p, uint32_t nparts, hipStream_t s)
+{
+    if (!nparts || !p.g.a.num_tiles) return hipSuccess;
+    hipLaunchKernelGGL(t2read_headers_parts_kernel, dim3(nparts), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(t2read_tile_parts_kernel, dim3(p.g.a.num_tiles), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_t2read_chains_parts(const T2ReadPartsArgs& p, hipStream_t s)
+{
+    if (!p.g.a.chains) return hipSuccess;
+    hipLaunchKernelGGL(t2read_chains_parts_kernel, dim3((uint32_t)p.g.a.chains), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
 } // namespace grk_amd

@@ -5,6 +5,8 @@
 // places.  No byte of a tile-part crosses the link.  The _ex calls run the general reader (plan_t2_read_layers; KC-L, KF, KP) for
 // files of several layers or codeword segments: segment lists come to the host where a caller or the Part-1 decoder wants them,
 // the moves only to a caller that asks -- a decode's gather reads them where KP left them.
+// grk_amd_read_packets_device_parts is the general reader for tiles divided into tile-parts: KL-P and KH-P build a part table in the
+// place of KL and KH, KC-L reads a tile's bytes through it; the _ex decode turns to it when KL refuses a second tile-part.
 #include "context.h"
 #include "t2_read_plan.h"
 #include "t2_reader.h"
@@ -15,7 +17,8 @@ struct ReadDevState {
     T2ReadPlan plan;
     DevBuf tiles, packets, parts, plt_len, pk_start, nodes, rows, status, tlm;
     uint8_t* pin = nullptr; size_t pin_cap = 0;         // the header's copy, the status word behind a 16-byte boundary
-    uint64_t counters[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t last_why = 0;                              // why the latest status word refused (T2pWhy)
+    uint64_t counters[7] = {0, 0, 0, 0, 0, 0, 0};         // [6]: launches of KL-P / KH-P; the located count comes to the host with the status word behind KL-P
     // the general reader (grk_amd_read_packets_device_ex): its own plan and descriptors, the scratch of KC-L, KF and KP
     bool have_lplan = false;
     grk_amd_stream_info linfo{};
@@ -111,6 +114,7 @@ int refuse_status(grk_amd_ctx* c, uint64_t st)
 {
     char buf[200];
     const uint32_t why = t2p_status_why(st);
+    if (c->rdev) c->rdev->last_why = why;
     if (!t2p_status_is_tile(st)) std::snprintf(buf, sizeof buf, "tile-part %u: %s", t2p_status_number(st), t2p_text(why));
     else if (t2p_status_stage(st) == 0) std::snprintf(buf, sizeof buf, "tile %u: %s", t2p_status_tile_of(st), t2p_text(why));
     else std::snprintf(buf, sizeof buf, "tile %u %s %u: %s", t2p_status_tile_of(st), t2p_status_stage(st) == 1 ? "packet" : "block", t2p_status_number(st), t2p_text(why));
@@ -208,7 +212,8 @@ struct ReadExOut {
     StreamTable* tab; bool tab_segments;
 };
 
-int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, uint64_t have, const ReadExOut& o)
+// parts: tiles divided into tile-parts are read (KL-P, KH-P and KC-L over the part table in the place of KL, KH and KC-L)
+int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, uint64_t have, const ReadExOut& o, bool parts = false)
 {
     ReadDevState* r = state(c);
     const char* pwhy = "";
@@ -233,11 +238,15 @@ int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const 
     bool tlm = false;
     std::vector<uint64_t> at; std::vector<uint32_t> ln, idx;
     uint64_t count = 0;
-    if (t2_read_tlm(r->pin, have, len, nt, &tlm, at, ln, idx, &count)) return fail(c, GRK_AMD_ERR_INVALID, t2p_text(kT2pNotLocated));
+    if (t2_read_tlm(r->pin, have, len, parts ? kT2pMaxPartsOfFile : nt, &tlm, at, ln, idx, &count)) return fail(c, GRK_AMD_ERR_INVALID, t2p_text(kT2pNotLocated));
     uint64_t sot_at = 2;
     while (sot_at + 4 <= have && !(r->pin[sot_at] == 0xFF && r->pin[sot_at + 1] == 0x90)) sot_at += 2 + ((uint64_t)r->pin[sot_at + 2] << 8 | r->pin[sot_at + 3]);
     const uint64_t entries = std::max<uint64_t>(P.total_packets, nt), nblocks = (P.rows + kT2ReadScanRows - 1) / kT2ReadScanRows;
-    HIP_TRY(c, r->parts.ensure((size_t)nt * 32), "alloc the tile-parts' places");
+    // the part table's room: TLM says how many tile-parts the file has; without, the Psot chain cannot have more than len / 14 + 1
+    if (parts && tlm && count > kT2pMaxPartsOfFile) return fail(c, GRK_AMD_ERR_UNSUPPORTED, t2p_text(kT2pPartsOfFile));
+    const uint64_t cap = !parts ? 0 : tlm ? std::max<uint64_t>(count, 1) : std::min<uint64_t>(len / 14 + 1, kT2pMaxPartsOfFile);
+    const size_t tile_words = ((size_t)nt * 4 + 4 + 7) & ~(size_t)7;         // a per-tile array of 32-bit words, 8-byte aligned
+    HIP_TRY(c, r->parts.ensure(parts ? (size_t)nt * 8 + 5 * tile_words + (size_t)cap * 64 + 64 : (size_t)nt * 32), "alloc the tile-parts' places");
     HIP_TRY(c, r->plt_len.ensure(entries * 4), "alloc packet lengths");
     HIP_TRY(c, r->pk_start.ensure(entries * 8), "alloc packet starts");
     HIP_TRY(c, r->nodes32.ensure(Q.bytes_nodes() + 16), "alloc tag-tree nodes");
@@ -251,13 +260,13 @@ int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const 
     HIP_TRY(c, r->move_first.ensure(P.rows * 4 + 16), "alloc the rows' first moves");
     HIP_TRY(c, r->sums.ensure(nblocks * 24 + 16), "alloc the scan's sums");
     HIP_TRY(c, r->totals.ensure(32), "alloc the totals");
-    HIP_TRY(c, r->status.ensure(8), "alloc status");
+    HIP_TRY(c, r->status.ensure(16), "alloc status");
     T2ReadLayersArgs g{};
     T2ReadArgs& a = g.a;
     a.cs = (const uint8_t*)d_cs; a.len = len; a.num_tiles = nt;
     a.tiles = (const T2ReadTile*)r->ltiles.p; a.packets = (const T2ReadPacket*)r->lpackets.p;
     a.ht = P.ht; a.sop = P.sop; a.eph = P.eph;
-    if (tlm) {
+    if (tlm && !parts) {
         std::vector<T2ReadTlmEntry> e(at.size());
         for (size_t i = 0; i < e.size(); ++i) e[i] = T2ReadTlmEntry{at[i], ln[i], idx[i]};
         HIP_TRY(c, r->tlm.ensure(e.size() * sizeof e[0] + 16), "alloc TLM's places");
@@ -266,9 +275,37 @@ int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const 
         a.tlm = (const T2ReadTlmEntry*)r->tlm.p; a.tlm_n = (uint32_t)e.size(); a.tlm_count = count;
     }
     a.sot_at = sot_at;
-    uint8_t* const parts = (uint8_t*)r->parts.p;                // per tile 32 bytes: 8 + 8 + 4 + 4 + 4
-    a.part_at = (unsigned long long*)parts; a.body_at = (unsigned long long*)(parts + (size_t)nt * 8);
-    a.part_len = (uint32_t*)(parts + (size_t)nt * 16); a.has_plt = (uint32_t*)(parts + (size_t)nt * 20); a.first_of = (uint32_t*)(parts + (size_t)nt * 24);
+    uint8_t* const pbuf = (uint8_t*)r->parts.p;                 // per tile 32 bytes: 8 + 8 + 4 + 4 + 4
+    T2ReadPartsArgs pa{};
+    if (!parts) {
+        a.part_at = (unsigned long long*)pbuf; a.body_at = (unsigned long long*)(pbuf + (size_t)nt * 8);
+        a.part_len = (uint32_t*)(pbuf + (size_t)nt * 16); a.has_plt = (uint32_t*)(pbuf + (size_t)nt * 20); a.first_of = (uint32_t*)(pbuf + (size_t)nt * 24);
+    } else {
+        // per tile: body_at (8), then has_plt, count, tn_min, tn_max, slice (4 each, slice one more); per tile-part of `cap`: 64 bytes
+        uint8_t* q = pbuf;
+        a.body_at = (unsigned long long*)q; q += (size_t)nt * 8;
+        a.has_plt = (uint32_t*)q; q += tile_words;
+        pa.count = (uint32_t*)q; q += tile_words;
+        pa.tn_min = (uint32_t*)q; q += tile_words;
+        pa.tn_max = (uint32_t*)q; q += tile_words;
+        pa.slice = (uint32_t*)q; q += tile_words;
+        pa.fo_at = (unsigned long long*)q; q += cap * 8;
+        pa.tp_at = (unsigned long long*)q; q += cap * 8;
+        pa.tp_body = (unsigned long long*)q; q += cap * 8;
+        uint32_t** const words[] = {&pa.fo_len, &pa.fo_idx, &pa.claim, &pa.tp_len, &pa.tp_tile, &pa.tp_file, &pa.tp_has_plt, &pa.tp_npk, &pa.tp_first};
+        for (uint32_t** w : words) { *w = (uint32_t*)q; q += cap * 4; }
+        pa.cap = (uint32_t)cap; pa.n_given = tlm ? (uint32_t)count : 0u;
+        pa.located = (unsigned long long*)r->status.p + 1;
+        if (tlm) {
+            // (TLM's places go up as the file-order arrays; a.tlm stays unused)
+            if (at.size() != count) return fail(c, GRK_AMD_ERR_INVALID, t2p_text(kT2pNotLocated));
+            if (count) {
+                HIP_TRY(c, hipMemcpy(pa.fo_at, at.data(), count * 8, hipMemcpyHostToDevice), "upload TLM's places");
+                HIP_TRY(c, hipMemcpy(pa.fo_len, ln.data(), count * 4, hipMemcpyHostToDevice), "upload TLM's lengths");
+                HIP_TRY(c, hipMemcpy(pa.fo_idx, idx.data(), count * 4, hipMemcpyHostToDevice), "upload TLM's tile indices");
+            }
+        }
+    }
     a.plt_len = (uint32_t*)r->plt_len.p; a.pk_start = (unsigned long long*)r->pk_start.p;
     a.rows = (grk_amd_coded_block*)r->rows.p;
     a.status = (unsigned long long*)r->status.p; a.chains = P.chains;
@@ -288,9 +325,25 @@ int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const 
     };
     HIP_TRY(c, hipMemsetAsync(r->status.p, 0xFF, 8, c->stream), "clear status");
     HIP_TRY(c, hipMemsetAsync(r->totals.p, 0, 32, c->stream), "clear the totals");
-    HIP_TRY(c, launch_t2read_locate(a, c->stream), "launch KL");
-    HIP_TRY(c, launch_t2read_headers(a, c->stream), "launch KH");
-    HIP_TRY(c, launch_t2read_chains_layers(g, c->stream), "launch KC-L");
+    if (!parts) {
+        HIP_TRY(c, launch_t2read_locate(a, c->stream), "launch KL");
+        HIP_TRY(c, launch_t2read_headers(a, c->stream), "launch KH");
+        HIP_TRY(c, launch_t2read_chains_layers(g, c->stream), "launch KC-L");
+    } else {
+        // KL-P, then the status word and the located count (one word) to the host: KH-P's grid is the file's tile-parts
+        pa.g = g;
+        HIP_TRY(c, hipMemsetAsync((uint8_t*)r->status.p + 8, 0, 8, c->stream), "clear the located count");
+        HIP_TRY(c, launch_t2read_locate_parts(pa, c->stream), "launch KL-P");
+        HIP_TRY(c, hipMemcpyAsync(h_words, r->status.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch status and the located count");
+        HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+        r->counters[0] += 16; ++r->counters[6];
+        if (h_words[0] != kT2pNoStatus) return refuse_status(c, h_words[0]);
+        const uint64_t located = h_words[1];
+        if (!located || located > cap) return fail(c, GRK_AMD_ERR_INVALID, t2p_text(kT2pNotLocated));
+        HIP_TRY(c, launch_t2read_headers_parts(pa, (uint32_t)located, c->stream), "launch KH-P");
+        r->counters[6] += 2;
+        HIP_TRY(c, launch_t2read_chains_parts(pa, c->stream), "launch KC-L");
+    }
     ++r->counters[5]; r->counters[3] += P.chains;
     // (a chain that was refused, or never ran, leaves its rows' state as it was: KF and KP run on what every chain has finished)
     rc = fetch_status(); if (rc) return rc;
@@ -354,6 +407,18 @@ extern "C" int64_t grk_amd_read_packets_device_ex(grk_amd_ctx* c, const void* d_
     return packets_device_ex(c, d_cs, len, own, have, ReadExOut{rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes, nullptr, false});
 }
 
+extern "C" int64_t grk_amd_read_packets_device_parts(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info* info, grk_amd_coded_block* rows,
+                                                     uint64_t row_cap, uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                                     grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+{
+    if (!c || !d_cs || !info) return GRK_AMD_ERR_INVALID;
+    grk_amd_stream_info own;
+    uint64_t have = 0;
+    const int rc = header_device(c, d_cs, len, own, &have); if (rc) return rc;
+    if (std::memcmp(&own, info, sizeof own) != 0) return fail(c, GRK_AMD_ERR_INVALID, "info is not what grk_amd_read_header_device gives for this codestream");
+    return packets_device_ex(c, d_cs, len, own, have, ReadExOut{rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes, nullptr, false}, true);
+}
+
 extern "C" int grk_amd_decode_image_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device)
 {
     if (!c || !d_cs || !pixels) return GRK_AMD_ERR_INVALID;
@@ -364,7 +429,12 @@ extern "C" int grk_amd_decode_image_device_ex(grk_amd_ctx* c, const void* d_cs, 
     StreamTable tab;
     uint64_t nmoves = 0;
     const bool want_segs = info.base.reserved[0] && (info.base.reserved[1] & 0x05);          // (Part-1 with LAZY / TERMALL: decode_image_plan's want_segs)
-    const int64_t n = packets_device_ex(c, d_cs, len, info, have, ReadExOut{nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, &nmoves, nullptr, &tab, want_segs});
+    // a file with one tile-part per tile goes the way it always went; one that KL refuses for a second tile-part is read again over
+    // the part table (KL-P, KH-P)
+    const ReadExOut out{nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, &nmoves, nullptr, &tab, want_segs};
+    c->rdev->last_why = 0;
+    int64_t n = packets_device_ex(c, d_cs, len, info, have, out);
+    if (n == GRK_AMD_ERR_UNSUPPORTED && (c->rdev->last_why == kT2pMultiPart || c->rdev->last_why == kT2pManyParts)) n = packets_device_ex(c, d_cs, len, info, have, out, true);
     if (n < 0) return (int)n;
     if (!tab.appendix_bytes) return decode_resident(c, d_cs, len, info, tab, pixels, cap, pixels_on_device);
     return decode_resident_moves(c, d_cs, len, info, tab, (const grk_amd_tp_segment*)c->rdev->moves.p, nmoves, &c->rdev->counters[4], pixels, cap, pixels_on_device);
@@ -390,7 +460,7 @@ extern "C" int64_t grk_amd_read_packets_device(grk_amd_ctx* c, const void* d_cs,
 
 extern "C" uint64_t grk_amd_read_device_counters(grk_amd_ctx* c, int which)
 {
-    return c && c->rdev && which >= 0 && which < 6 ? c->rdev->counters[which] : 0;
+    return c && c->rdev && which >= 0 && which < 7 ? c->rdev->counters[which] : 0;
 }
 
 extern "C" int grk_amd_decode_image_device(grk_amd_ctx* c, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device)

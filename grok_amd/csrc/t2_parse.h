@@ -37,13 +37,14 @@ enum T2pWhy : uint32_t {
     kT2pNoSod, kT2pBrokenSegment, kT2pBrokenPlt, kT2pPltWrap, kT2pPltMany, kT2pMarker, kT2pPacketsBytes, kT2pPltCount,    // KH
     kT2pNoSop, kT2pZeroPlanes, kT2pHtPasses, kT2pPasses, kT2pLblock, kT2pLenBits, kT2pBlockWrap, kT2pHeaderPast,          // KC
     kT2pNoEph, kT2pBodyPast, kT2pPltSize, kT2pTail, kT2pPart1Planes,
+    kT2pTpsot, kT2pTnsot, kT2pPartsOfTile, kT2pPartsOfFile, kT2pPsotZero, kT2pPartPlt, kT2pTileEnds,                       // KL-P, KH-P, the chains' part stepping
     kT2pWhys
 };
 GRK_T2_FN int t2p_code(uint32_t why)
 {
     if (why == kT2pOk) return 0;
-    return why == kT2pMultiPart || why == kT2pManyParts || why == kT2pMarker || why == kT2pHtPasses ? -2 /* GRK_AMD_ERR_UNSUPPORTED */
-                                                                                                    : -3 /* GRK_AMD_ERR_INVALID */;
+    return why == kT2pMultiPart || why == kT2pManyParts || why == kT2pMarker || why == kT2pHtPasses || why == kT2pPartsOfTile || why == kT2pPartsOfFile
+               ? -2 /* GRK_AMD_ERR_UNSUPPORTED */ : -3 /* GRK_AMD_ERR_INVALID */;
 }
 GRK_T2_FN const char* t2p_text(uint32_t why)
 {
@@ -75,6 +76,13 @@ GRK_T2_FN const char* t2p_text(uint32_t why)
     case kT2pPltSize: return "the packet's size is not PLT's";
     case kT2pTail: return "bytes behind the last packet";
     case kT2pPart1Planes: return "more passes than the block's bit-planes hold";
+    case kT2pTpsot: return "a TPsot that is missing, repeated or out of file order";
+    case kT2pTnsot: return "TNsot does not fit the tile's tile-parts";
+    case kT2pPartsOfTile: return "more than 255 tile-parts of one tile";
+    case kT2pPartsOfFile: return "more than 65535 tile-parts";
+    case kT2pPsotZero: return "Psot 0 in a tile-part that is not the file's last";
+    case kT2pPartPlt: return "the PLT lengths do not add up to the tile-part";
+    case kT2pTileEnds: return "the tile's last tile-part ends before its last packet";
     default: return "";
     }
 }
@@ -279,6 +287,22 @@ GRK_T2_FN uint32_t t2p_check_sot(Src& s, uint64_t len, uint64_t at, uint32_t ln,
     if (s.byte(at + 10) != 0 || s.byte(at + 11) > 1) return kT2pMultiPart;
     const uint32_t psot = t2p_u32(s, at + 6);
     if (psot && psot != ln) return kT2pPsotTlm;
+    return kT2pOk;
+}
+// The same for a file whose tiles may be divided into tile-parts (locate_stream_parts): the SOT alone, TPsot and TNsot handed out
+// for the checks across a tile's tile-parts.  last: the tile-part is the file's last (Psot may be 0 there only)
+constexpr uint32_t kT2pMaxPartsOfTile = 255, kT2pMaxPartsOfFile = 65535;
+template <class Src>
+GRK_T2_FN uint32_t t2p_check_sot_part(Src& s, uint64_t len, uint64_t at, uint32_t ln, uint32_t num_tiles, uint32_t want_isot, bool last, uint32_t* isot,
+                                      uint32_t* tpsot, uint32_t* tnsot)
+{
+    if (ln < 14 || at > len || ln > len - at || t2p_u16(s, at) != 0xFF90 || t2p_u16(s, at + 2) != 10) return kT2pNoSot;
+    const uint32_t i = t2p_u16(s, at + 4);
+    if (i >= num_tiles || (want_isot != 0xFFFFFFFFu && i != (want_isot & 0xFFFFu))) return kT2pTileIndex;
+    *isot = i; *tpsot = s.byte(at + 10); *tnsot = s.byte(at + 11);
+    const uint32_t psot = t2p_u32(s, at + 6);
+    if (psot && psot != ln) return kT2pPsotTlm;
+    if (!psot && !last) return kT2pPsotZero;
     return kT2pOk;
 }
 // One hop of the Psot chain from `at` (a file without TLM): 0 no further tile-part, 1 one of *ln bytes, 2 a tile-part that does

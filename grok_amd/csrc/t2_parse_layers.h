@@ -216,4 +216,70 @@ template <class Run, class Fn> GRK_T2_FN void t2p_tile_packets(uint32_t order, u
     }
 }
 
+// ---- a tile divided into tile-parts -----------------------------------------------------------------------------------------------------
+// The tile's packet sequence is its tile-parts' bodies end to end, each body whole packets.  What KL-P and KH-P leave about the
+// tile's n tile-parts in TPsot order (they rise in the file): where each lies, its body, whether it carries PLT, how many packets
+// that lists and where those entries start among the tile's PLT lengths.
+struct T2pParts {
+    const unsigned long long* at; const uint32_t* len; const unsigned long long* body;
+    const uint32_t* has_plt; const uint32_t* npk; const uint32_t* first;
+    uint32_t n;
+};
+GRK_T2_FN uint64_t t2p_load64(const unsigned long long* p)
+{
+    const uint32_t* const w = (const uint32_t*)p;
+    return (uint64_t)GRK_T2P_UNIFORM(w[0]) | (uint64_t)GRK_T2P_UNIFORM(w[1]) << 32;
+}
+GRK_T2_FN uint64_t t2p_part_end(const T2pParts& P, uint32_t p) { return t2p_load64(P.at + p) + GRK_T2P_UNIFORM(P.len[p]); }
+// the tile-part a position lies in: the last that starts at or before it (at most 8 steps for 255 tile-parts)
+GRK_T2_FN uint32_t t2p_part_of(const T2pParts& P, uint64_t pos)
+{
+    uint32_t lo = 0, hi = P.n;
+    for (uint32_t step = 0; step < 9 && hi - lo > 1; ++step) { const uint32_t mid = (lo + hi) >> 1; if (t2p_load64(P.at + mid) <= pos) lo = mid; else hi = mid; }
+    return lo;
+}
+// a chain that reads the tile in file order: the tile-part at hand, packets read in it, its end
+struct T2pPartWalk { uint32_t p, used; uint64_t end; };
+GRK_T2_FN void t2p_part_walk_start(const T2pParts& P, T2pPartWalk& w, uint64_t& pos) { w.p = 0; w.used = 0; w.end = t2p_part_end(P, 0); pos = t2p_load64(P.body); }
+// leaving a tile-part: its PLT, if it has one, listed just the packets read in it
+GRK_T2_FN uint32_t t2p_part_leave(const T2pParts& P, const T2pPartWalk& w)
+{
+    return GRK_T2P_UNIFORM(P.has_plt[w.p]) && w.used != GRK_T2P_UNIFORM(P.npk[w.p]) ? (uint32_t)kT2pPartPlt : (uint32_t)kT2pOk;
+}
+// before a packet: on to the next tile-part that holds a byte when pos has reached the end of the one at hand
+GRK_T2_FN uint32_t t2p_part_step(const T2pParts& P, T2pPartWalk& w, uint64_t& pos)
+{
+    for (uint32_t hop = 0; hop < P.n && pos == w.end; ++hop) {
+        const uint32_t why = t2p_part_leave(P, w);
+        if (why) return why;
+        if (w.p + 1 >= P.n) return kT2pTileEnds;
+        ++w.p; w.used = 0;
+        pos = t2p_load64(P.body + w.p); w.end = t2p_part_end(P, w.p);
+    }
+    return kT2pOk;
+}
+// behind a packet of `size` bytes: the tile-part's PLT entry for it (plt_len: the tile's PLT lengths)
+GRK_T2_FN uint32_t t2p_part_packet(const T2pParts& P, T2pPartWalk& w, const uint32_t* plt_len, uint64_t size)
+{
+    if (GRK_T2P_UNIFORM(P.has_plt[w.p])) {
+        if (w.used >= GRK_T2P_UNIFORM(P.npk[w.p])) return kT2pPartPlt;
+        if (size != GRK_T2P_UNIFORM(plt_len[GRK_T2P_UNIFORM(P.first[w.p]) + w.used])) return kT2pPltSize;
+    }
+    ++w.used;
+    return kT2pOk;
+}
+// behind the tile's last packet: it ends its tile-part, and what follows of the tile holds nothing
+GRK_T2_FN uint32_t t2p_part_finish(const T2pParts& P, T2pPartWalk& w, uint64_t pos)
+{
+    for (uint32_t hop = 0; hop < P.n; ++hop) {
+        if (pos != w.end) return kT2pTail;
+        const uint32_t why = t2p_part_leave(P, w);
+        if (why) return why;
+        if (w.p + 1 >= P.n) return kT2pOk;
+        ++w.p; w.used = 0;
+        pos = t2p_load64(P.body + w.p); w.end = t2p_part_end(P, w.p);
+    }
+    return kT2pOk;
+}
+
 } // namespace grk_amd

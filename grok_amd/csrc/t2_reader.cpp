@@ -5,6 +5,9 @@
 // Written from ITU-T T.800 Annex A (marker segments), Annex B (B.10 packet headers, B.10.2 tag trees, B.10.7 lengths, B.12
 // progression) and T.814 (the HT code-block style bit), as tests/j2kparse.py was.
 //
+// A tile may be divided into tile-parts (read_stream_packets with allow_parts, grk_amd_read_packets_parts): its packet sequence is
+// its tile-parts' bodies end to end, each body whole packets, so only where a tile's bytes lie changes.
+//
 // This is a parser of UNTRUSTED input: every read is checked against the end of its container (the codestream, the marker
 // segment, the tile-part, with PLT the packet), every count against what the bytes present could hold, sums are made in 64 bits.
 #include "t2_reader.h"
@@ -383,9 +386,11 @@ int64_t tile_rows(const grk_amd_stream_info& info, uint32_t t, grk_amd_tile_para
     return n;
 }
 
-// One tile: its tile-part header (PLT), then its packets -- in file order, or, when PLT gives every packet's place, precinct by
-// precinct on `threads` threads (a precinct's packets depend on each other through its tag trees and Lblock, on nothing else).
-int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const TilePart& tp, BlockState* st, grk_amd_coded_block* rows,
+// One tile: its tile-parts' headers (PLT), then its packets -- the tile-parts' bodies end to end are the tile's packet sequence,
+// and every body holds whole packets.  In file order, or, when PLT gives every packet's place (every tile-part that holds packets
+// lists exactly its own), precinct by precinct on `threads` threads (a precinct's packets depend on each other through its tag
+// trees and Lblock, on nothing else).  parts[t] is the tile's first tile-part, .next leads to the following ones.
+int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const std::vector<TilePart>& parts, BlockState* st, grk_amd_coded_block* rows,
               uint32_t threads, uint32_t drop_res, std::vector<Precinct>& keep, std::string& err)
 {
     TileCtx T;
@@ -418,42 +423,67 @@ int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const
     const uint32_t order = (info.flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, L = info.num_layers;
     T.seq = packet_order(T.cg, sub ? info.comp_dx : nullptr, sub ? info.comp_dy : nullptr, p.tile_x0, p.tile_y0, order);
     const uint64_t np = T.seq.size(), npk = np * L;
-    // the tile-part header
-    const uint64_t end = tp.at + tp.len;
-    uint64_t pos = tp.at + 12;
+    // the tile-part headers: where every body lies, and the PLT entries of all of them one list
+    struct Body { uint64_t pos, end; uint64_t plt_at, plt_n; bool have_plt; };
+    std::vector<Body> body;
     std::vector<uint32_t> plt;
-    bool have_plt = false;
-    uint64_t v = 0; bool open = false;
-    for (;;) {
-        if (end - pos < 2) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: no SOD marker", t);
-        const uint32_t m = b.u16(pos);
-        if (m == 0xFF93) { pos += 2; break; }
-        if (end - pos < 4) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: no SOD marker", t);
-        const uint32_t l = b.u16(pos + 2);
-        if (m < 0xFF30 || l < 2 || (uint64_t)l + 2 > end - pos) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: broken marker segment 0x%04X", t, m);
-        if (m == 0xFF58) {
-            if (l < 3) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: broken PLT", t);
-            have_plt = true;
-            for (uint64_t i = pos + 5; i < pos + 2 + l; ++i) {
-                const uint32_t x = b.u8(i);
-                v = v << 7 | (x & 0x7Fu); open = true;
-                if (v > 0xFFFFFFFFull) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: a PLT packet length wraps", t);
-                if (!(x & 0x80u)) {
-                    if (plt.size() >= npk) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: PLT lists more than the tile's %llu packets", t, (unsigned long long)npk);
-                    plt.push_back((uint32_t)v); v = 0; open = false;
+    const bool multi = parts[t].next != 0;
+    char where[48];
+    auto at_part = [&](size_t k) -> const char* {           // "tile 3", of a tile in several tile-parts "tile 3 tile-part 1"
+        if (multi) std::snprintf(where, sizeof where, "tile %u tile-part %u", t, (unsigned)k);
+        else std::snprintf(where, sizeof where, "tile %u", t);
+        return where;
+    };
+    uint64_t body_bytes = 0;
+    for (uint32_t idx = t;; idx = parts[idx].next) {
+        const TilePart& tp = parts[idx];
+        const size_t k = body.size();
+        if (k >= 255 || tp.len < 14 || !b.has(tp.at, tp.len)) return refuse(err, GRK_AMD_ERR_INVALID, "%s: the tile-part list", at_part(k));
+        const uint64_t end = tp.at + tp.len;
+        uint64_t pos = tp.at + 12;
+        Body B{0, end, plt.size(), 0, false};
+        uint64_t v = 0; bool open = false;
+        for (;;) {
+            if (end - pos < 2) return refuse(err, GRK_AMD_ERR_INVALID, "%s: no SOD marker", at_part(k));
+            const uint32_t m = b.u16(pos);
+            if (m == 0xFF93) { pos += 2; break; }
+            if (end - pos < 4) return refuse(err, GRK_AMD_ERR_INVALID, "%s: no SOD marker", at_part(k));
+            const uint32_t l = b.u16(pos + 2);
+            if (m < 0xFF30 || l < 2 || (uint64_t)l + 2 > end - pos) return refuse(err, GRK_AMD_ERR_INVALID, "%s: broken marker segment 0x%04X", at_part(k), m);
+            if (m == 0xFF58) {
+                if (l < 3) return refuse(err, GRK_AMD_ERR_INVALID, "%s: broken PLT", at_part(k));
+                B.have_plt = true;
+                for (uint64_t i = pos + 5; i < pos + 2 + l; ++i) {
+                    const uint32_t x = b.u8(i);
+                    v = v << 7 | (x & 0x7Fu); open = true;
+                    if (v > 0xFFFFFFFFull) return refuse(err, GRK_AMD_ERR_INVALID, "%s: a PLT packet length wraps", at_part(k));
+                    if (!(x & 0x80u)) {
+                        if (plt.size() >= npk) return refuse(err, GRK_AMD_ERR_INVALID, "%s: PLT lists more than the tile's %llu packets", at_part(k), (unsigned long long)npk);
+                        plt.push_back((uint32_t)v); v = 0; open = false;
+                    }
                 }
+            } else if (m == 0xFF64) {
+                // COM
+            } else if (const char* name = marker_name(m)) {
+                return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%s marker segment in a tile-part header", name);
+            } else {
+                return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "marker segment 0x%04X in a tile-part header", m);
             }
-        } else if (m == 0xFF64) {
-            // COM
-        } else if (const char* name = marker_name(m)) {
-            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%s marker segment in a tile-part header", name);
-        } else {
-            return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "marker segment 0x%04X in a tile-part header", m);
+            pos += 2 + (uint64_t)l;
         }
-        pos += 2 + (uint64_t)l;
+        B.pos = pos; B.plt_n = plt.size() - B.plt_at;
+        if (open) return refuse(err, GRK_AMD_ERR_INVALID, "%s: PLT lists %llu packets and a part of one", at_part(k), (unsigned long long)B.plt_n);
+        body_bytes += end - pos;
+        body.push_back(B);
+        if (!tp.next) break;
+        if (tp.next >= parts.size()) return refuse(err, GRK_AMD_ERR_INVALID, "%s: the tile-part list", at_part(k));
     }
-    if (npk > end - pos) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: %llu packets in %llu bytes", t, (unsigned long long)npk, (unsigned long long)(end - pos));
-    if (have_plt && (open || plt.size() != npk))
+    if (npk > body_bytes) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: %llu packets in %llu bytes", t, (unsigned long long)npk, (unsigned long long)body_bytes);
+    // a PLT tile: every tile-part that holds packets lists them
+    bool plt_tile = !plt.empty();
+    for (const Body& B : body) if (B.pos != B.end && !B.have_plt) plt_tile = false;
+    if (!multi) plt_tile = body[0].have_plt;
+    if (plt_tile && plt.size() != npk)
         return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: PLT lists %llu packets of %llu", t, (unsigned long long)plt.size(), (unsigned long long)npk);
     T.prec.resize(np);
     // RLCP: the layers run inside a resolution -- run[i] = {first packet of seq[i]'s resolution, packets of it}
@@ -467,39 +497,73 @@ int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const
             i = j;
         }
     }
-    // the number (place in the tile-part) of precinct i's packet of layer l
+    // the number (place in the tile's packet sequence) of precinct i's packet of layer l
     auto number_of = [&](uint64_t i, uint64_t l) -> uint64_t {
         if (order == 0) return l * np + i;
         if (order == 1) return (uint64_t)run[i].first * L + l * run[i].second + (i - run[i].first);
         return i * L + l;
     };
-    if (have_plt && threads > 1 && np > 1) {
-        std::vector<uint64_t> start(npk + 1, pos);
-        for (uint64_t k = 0; k < npk; ++k) start[k + 1] = start[k] + plt[k];
-        if (start[npk] != end) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: the PLT lengths do not add up to the tile-part", t);
+    // (a packet's refusal names the tile-part it was read in)
+    auto in_part = [&](std::string& e, size_t k) { if (multi) e += " (tile-part " + std::to_string(k) + ")"; };
+    if (plt_tile && threads > 1 && np > 1) {
+        std::vector<uint64_t> start(npk + 1, 0);
+        std::vector<uint8_t> part_of(multi ? npk : 0);
+        uint64_t k = 0;
+        for (size_t q = 0; q < body.size(); ++q) {
+            uint64_t at = body[q].pos;
+            for (uint64_t j = 0; j < body[q].plt_n; ++j, ++k) {
+                start[k] = at; at += plt[k];
+                if (multi) part_of[k] = (uint8_t)q;
+                if (at > body[q].end) break;
+            }
+            if (at != body[q].end) return refuse(err, GRK_AMD_ERR_INVALID, "%s: the PLT lengths do not add up to the tile-part", at_part(q));
+        }
         std::mutex mu;
         rc = parallel_for(np, threads, [&](size_t i) -> int {
             std::string e;
             for (uint32_t l = 0; l < L; ++l) {
                 const uint64_t k = number_of(i, l);
                 uint64_t at = start[k];
-                int r = read_packet(T, (uint32_t)i, l, (uint32_t)k, at, start[k + 1], e);
-                if (!r && at != start[k + 1]) r = refuse(e, GRK_AMD_ERR_INVALID, "tile %u packet %llu: %llu bytes, PLT says %u", t, (unsigned long long)k,
-                                                         (unsigned long long)(at - start[k]), plt[k]);
-                if (r) { std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; return r; }
+                const uint64_t stop = start[k] + plt[k];
+                int r = read_packet(T, (uint32_t)i, l, (uint32_t)k, at, stop, e);
+                if (!r && at != stop) r = refuse(e, GRK_AMD_ERR_INVALID, "tile %u packet %llu: %llu bytes, PLT says %u", t, (unsigned long long)k,
+                                                 (unsigned long long)(at - start[k]), plt[k]);
+                if (r) { in_part(e, multi ? part_of[k] : 0); std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; return r; }
             }
             return GRK_AMD_OK;
         });
         if (rc) return rc;
     } else {
-        uint64_t k = 0;
+        uint64_t k = 0, used = 0;            // packets read in all; in the tile-part at hand
+        size_t cur = 0;
+        uint64_t pos = body[0].pos;
+        // a tile-part is left where its last packet ends: its PLT, if it has one, listed just those
+        auto leave = [&]() -> int {
+            if (body[cur].have_plt && used != body[cur].plt_n)
+                return refuse(err, GRK_AMD_ERR_INVALID, "%s: the PLT lengths do not add up to the tile-part (%llu packets listed, %llu read)", at_part(cur),
+                              (unsigned long long)body[cur].plt_n, (unsigned long long)used);
+            return GRK_AMD_OK;
+        };
         auto one = [&](uint64_t i, uint32_t l) -> int {
+            while (multi && pos == body[cur].end) {          // on to the next tile-part that holds a byte
+                if (int r = leave()) return r;
+                if (cur + 1 == body.size())
+                    return refuse(err, GRK_AMD_ERR_INVALID, "%s: the tile ends at packet %llu of %llu", at_part(cur), (unsigned long long)k, (unsigned long long)npk);
+                ++cur; used = 0; pos = body[cur].pos;
+            }
+            const Body& B = body[cur];
             const uint64_t from = pos;
-            const int r = read_packet(T, (uint32_t)i, l, (uint32_t)k, pos, end, err);
-            if (r) return r;
-            if (have_plt && pos - from != plt[k])
-                return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %llu: %llu bytes, PLT says %u", t, (unsigned long long)k, (unsigned long long)(pos - from), plt[k]);
-            ++k;
+            const int r = read_packet(T, (uint32_t)i, l, (uint32_t)k, pos, B.end, err);
+            if (r) { in_part(err, cur); return r; }
+            if (B.have_plt && (used >= B.plt_n || pos - from != plt[B.plt_at + used])) {
+                if (used >= B.plt_n)
+                    return refuse(err, GRK_AMD_ERR_INVALID, "%s: the PLT lengths do not add up to the tile-part (packet %llu is not listed)", at_part(cur), (unsigned long long)k);
+                refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %llu: %llu bytes, PLT says %u", t, (unsigned long long)k, (unsigned long long)(pos - from),
+                       plt[B.plt_at + used]);
+                in_part(err, cur);
+                return GRK_AMD_ERR_INVALID;
+            }
+            ++k; ++used;
             return GRK_AMD_OK;
         };
         if (order == 0) {
@@ -510,7 +574,13 @@ int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const
         } else {
             for (uint64_t i = 0; i < np; ++i) for (uint32_t l = 0; l < L; ++l) if ((rc = one(i, l))) return rc;
         }
-        if (pos != end) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u: %llu bytes behind the last packet", t, (unsigned long long)(end - pos));
+        // the tile's last packet ends its tile-part; what follows of the tile holds nothing
+        for (;; ++cur, used = 0, pos = body[cur].pos) {
+            if (pos != body[cur].end)
+                return refuse(err, GRK_AMD_ERR_INVALID, "%s: %llu bytes behind the last packet", at_part(cur), (unsigned long long)(body[cur].end - pos));
+            if ((rc = leave())) return rc;
+            if (cur + 1 == body.size()) break;
+        }
     }
     // the tile's rows (a block of several pieces gets its place in the appendix later)
     for (uint32_t c = 0; c < nc; ++c)
@@ -577,19 +647,84 @@ int grk_amd::read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_
     return GRK_AMD_OK;
 }
 
-int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err)
+int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err,
+                                 bool allow_parts)
 {
     grk_amd_stream_info own;
     int rc = read_stream_header(cs, len, own, err);
     if (rc) return rc;
     if (std::memcmp(&own, &info, sizeof own) != 0) return refuse(err, GRK_AMD_ERR_INVALID, "info is not what grk_amd_read_header gives for this codestream");
     std::vector<StreamPart> parts;
-    rc = locate_stream_parts(cs, len, info, parts, err);
+    rc = allow_parts ? locate_stream_parts(cs, len, info, parts, err) : locate_stream_parts_single(cs, len, info, parts, err);
     if (rc) return rc;
     return read_stream_packets_of(cs, len, info, parts, nullptr, 0, threads, out, err);
 }
 
+// Every tile-part of the file, each tile's in TPsot order (T.800 A.4.2; the reference: TileLengthMarkers, CodeStreamDecompress's SOT
+// checks): from TLM, else along the Psot chain.  Only SOT marker segments are read here.
 int grk_amd::locate_stream_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, std::vector<StreamPart>& parts, std::string& err)
+{
+    const Bytes b{cs, len};
+    const uint32_t nt = info.num_tiles;
+    constexpr uint32_t kMaxParts = 65535, kMaxPartsOfTile = 255;
+    std::vector<uint64_t> off; std::vector<uint32_t> ln; std::vector<uint16_t> idx;
+    const bool tlm = (info.flags & GRK_AMD_CS_TLM) != 0;
+    if (tlm) {
+        int used = 0;
+        const int64_t n = grk_amd_locate_tile_parts(cs, len, nullptr, nullptr, nullptr, 0, &used);
+        if (n < 0 || !used) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts cannot be located");
+        if (n > kMaxParts) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "%lld tile-parts (at most %u)", (long long)n, kMaxParts);
+        off.resize(n); ln.resize(n); idx.resize(n);
+        (void)grk_amd_locate_tile_parts(cs, len, off.data(), ln.data(), idx.data(), (uint64_t)n, &used);
+    } else {
+        // SOT to SOT over Psot: every hop is at least 14 bytes, so the walk ends with the stream
+        uint64_t at = 2;
+        while (b.has(at, 4) && b.u16(at) != 0xFF90) at += 2 + (uint64_t)b.u16(at + 2);       // (the main header: parse_main_header has passed it)
+        while (b.has(at, 12) && b.u16(at) == 0xFF90) {
+            const uint32_t isot = b.u16(at + 4), psot = b.u32(at + 6), tps = b.u8(at + 10);
+            const uint64_t l = psot ? psot : len >= at + 2 ? len - 2 - at : 0;               // Psot 0: the last tile-part runs to EOC
+            if (l < 14 || !b.has(at, l))
+                return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: Psot %u leaves the stream (%llu bytes from its SOT)", isot, tps, psot,
+                              (unsigned long long)(len - at));
+            if (off.size() == kMaxParts) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than %u tile-parts", kMaxParts);
+            off.push_back(at); ln.push_back((uint32_t)l); idx.push_back((uint16_t)isot);
+            at += l;
+        }
+    }
+    const size_t n = off.size();
+    parts.assign(nt, StreamPart{});
+    parts.reserve(std::max<size_t>(nt, n));
+    struct Seen { uint32_t count = 0, declared = 0, last = 0; };          // tile-parts so far, its non-zero TNsot, the place of the latest in `parts`
+    std::vector<Seen> seen(nt);
+    for (size_t i = 0; i < n; ++i) {
+        if (ln[i] < 14 || !b.has(off[i], ln[i]) || b.u16(off[i]) != 0xFF90 || b.u16(off[i] + 2) != 10)
+            return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %llu: no SOT marker segment where it should start", (unsigned long long)i);
+        const uint32_t isot = b.u16(off[i] + 4), psot = b.u32(off[i] + 6), tps = b.u8(off[i] + 10), tn = b.u8(off[i] + 11);
+        if (isot >= nt || (tlm && isot != idx[i])) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %llu: tile index %u", (unsigned long long)i, isot);
+        if (psot && psot != ln[i]) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: Psot %u, TLM %u", isot, tps, psot, ln[i]);
+        if (!psot && i + 1 != n) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: Psot 0 in a tile-part that is not the file's last", isot, tps);
+        Seen& s = seen[isot];
+        if (tps >= kMaxPartsOfTile && tps == s.count) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "tile %u tile-part %u: more than %u tile-parts of one tile", isot, tps, kMaxPartsOfTile);
+        if (tps != s.count)
+            return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: the file has %u tile-parts of the tile before it (a TPsot missing, repeated or out of order)",
+                          isot, tps, s.count);
+        if (tn && s.declared && tn != s.declared) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: TNsot %u, an earlier tile-part said %u", isot, tps, tn, s.declared);
+        if (tn) s.declared = tn;
+        if (s.declared && s.declared <= tps) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: TNsot %u", isot, tps, s.declared);
+        if (!s.count) { parts[isot] = StreamPart{off[i], ln[i], true, 0}; s.last = isot; }
+        else { parts[s.last].next = (uint32_t)parts.size(); s.last = (uint32_t)parts.size(); parts.push_back(StreamPart{off[i], ln[i], true, 0}); }
+        ++s.count;
+    }
+    for (uint32_t t = 0; t < nt; ++t) {
+        if (!seen[t].count) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u has no tile-part", t);
+        if (seen[t].declared > seen[t].count)
+            return refuse(err, GRK_AMD_ERR_INVALID, "tile %u tile-part %u: missing (TNsot %u, %u found)", t, seen[t].count, seen[t].declared, seen[t].count);
+    }
+    return GRK_AMD_OK;
+}
+
+// ... of a file with one tile-part per tile; any other is refused (the three older reader calls)
+int grk_amd::locate_stream_parts_single(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, std::vector<StreamPart>& parts, std::string& err)
 {
     const Bytes b{cs, len};
     const uint32_t nt = info.num_tiles;
@@ -606,7 +741,7 @@ int grk_amd::locate_stream_parts(const uint8_t* cs, uint64_t len, const grk_amd_
         if (isot >= nt || (used && isot != idx[i])) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: tile index %u", (long long)i, isot);
         if (tps != 0 || tn > 1 || parts[isot].seen) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (tile %u)", isot);
         if (psot && psot != ln[i]) return refuse(err, GRK_AMD_ERR_INVALID, "tile-part %lld: Psot %u, TLM %u", (long long)i, psot, ln[i]);
-        parts[isot] = TilePart{off[i], ln[i], true};
+        parts[isot] = TilePart{off[i], ln[i], true, 0};
     }
     if (n > nt) return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "more than one tile-part per tile (%lld tile-parts, %u tiles)", (long long)n, nt);
     for (uint32_t t = 0; t < nt; ++t) if (!parts[t].seen) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u has no tile-part", t);
@@ -618,7 +753,7 @@ int grk_amd::read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_a
 {
     threads = std::max<uint32_t>(1, std::min<uint32_t>(threads, 16));
     const Bytes b{cs, len};
-    if (parts.size() != info.num_tiles) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts are not this stream's");
+    if (parts.size() < info.num_tiles) return refuse(err, GRK_AMD_ERR_INVALID, "the tile-parts are not this stream's");
     // the tiles to read: tile_of(i), i < nt
     const uint32_t nt = tiles ? (uint32_t)tiles->size() : info.num_tiles;
     auto tile_of = [tiles](size_t i) { return tiles ? (*tiles)[i] : (uint32_t)i; };
@@ -642,13 +777,13 @@ int grk_amd::read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_a
         std::mutex mu;
         rc = parallel_for(nt, threads, [&](size_t t) -> int {
             std::string e;
-            const int r = read_tile(b, info, tile_of(t), parts[tile_of(t)], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, drop_res, left[t], e);
+            const int r = read_tile(b, info, tile_of(t), parts, st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, drop_res, left[t], e);
             if (r) { std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; }
             return r;
         });
     } else {
         for (uint32_t t = 0; t < nt && !rc; ++t)
-            rc = read_tile(b, info, tile_of(t), parts[tile_of(t)], st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, drop_res, left[t], err);
+            rc = read_tile(b, info, tile_of(t), parts, st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, drop_res, left[t], err);
     }
     if (rc) { if (err.empty()) (void)refuse(err, rc, "the packets cannot be read (%d)", rc); return rc; }
     // Segment lists and the appendix, in an order that does not depend on the threads: rows in order, a row's records in the order
@@ -699,14 +834,14 @@ extern "C" int grk_amd_stream_comp_size(const grk_amd_stream_info* info, uint32_
     return GRK_AMD_OK;
 }
 
-extern "C" int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
-                                        grk_amd_coded_block* rows, uint64_t row_cap,
-                                        uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
-                                        grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+static int64_t read_packets_into(bool allow_parts, const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                 grk_amd_coded_block* rows, uint64_t row_cap,
+                                 uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                 grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
 {
     if (!info) { g_reader_error = "no info"; return GRK_AMD_ERR_INVALID; }
     StreamTable s;
-    const int rc = read_stream_packets(cs, len, *info, threads, s, g_reader_error);
+    const int rc = read_stream_packets(cs, len, *info, threads, s, g_reader_error, allow_parts);
     if (rc) return rc;
     if (num_segments) *num_segments = s.segments.size();
     if (num_moves) *num_moves = s.moves.size();
@@ -720,4 +855,20 @@ extern "C" int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const g
     if (segments && !s.segments.empty()) std::memcpy(segments, s.segments.data(), s.segments.size() * sizeof segments[0]);
     if (moves && !s.moves.empty()) std::memcpy(moves, s.moves.data(), s.moves.size() * sizeof moves[0]);
     return (int64_t)s.rows.size();
+}
+
+extern "C" int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                        grk_amd_coded_block* rows, uint64_t row_cap,
+                                        uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                        grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+{
+    return read_packets_into(false, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
+}
+
+extern "C" int64_t grk_amd_read_packets_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                              grk_amd_coded_block* rows, uint64_t row_cap,
+                                              uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                              grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+{
+    return read_packets_into(true, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
 }

@@ -20,12 +20,18 @@ struct StreamTable {
 };
 
 int read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info& info, std::string& err);
-int read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err);
+// allow_parts: tiles divided into tile-parts are read (grk_amd_read_packets_parts); else a second tile-part of a tile is refused
+int read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err,
+                        bool allow_parts = false);
 
 // The two halves of read_stream_packets, for a caller that reads some of the tiles (grk_amd_decode_image_view):
-// where every tile's one tile-part lies (TLM, else the Psot chain: no packet is read) ...
-struct StreamPart { uint64_t at = 0; uint32_t len = 0; bool seen = false; };
+// where every tile's tile-parts lie (TLM, else the Psot chain: no packet is read) ...
+// parts[t], t < num_tiles: tile t's first tile-part (TPsot 0); .next: the place in `parts` of the tile's following tile-part, behind
+// the first num_tiles entries (0: this is the tile's last).  A tile's parts are at most 255, the file's at most 65535.
+struct StreamPart { uint64_t at = 0; uint32_t len = 0; bool seen = false; uint32_t next = 0; };
 int locate_stream_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, std::vector<StreamPart>& parts, std::string& err);
+// ... of a file with one tile-part per tile: parts has num_tiles entries; a second tile-part of a tile is GRK_AMD_ERR_UNSUPPORTED
+int locate_stream_parts_single(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, std::vector<StreamPart>& parts, std::string& err);
 // ... and the packets of `tiles` (rising tile indices; nullptr: every tile).  Offsets stay positions in `cs` (the appendix behind
 // `len`).  drop_res: blocks of the `drop_res` finest resolutions get no place in the appendix and no moves -- a decode at that
 // reduce never reads their rows

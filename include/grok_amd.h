@@ -824,7 +824,8 @@ int64_t grk_amd_locate_tile_parts(const uint8_t* cs, uint64_t len, uint64_t* off
  * written from ITU-T T.800 Annex A / Annex B and T.814): what SIZ, COD and QCD say, then every packet header of every tile,
  * which yields the block table grk_amd_decode_tiles takes.  It reads what this library's writers and grk_compress produce:
  *   main header   SOC SIZ CAP COD QCD (Sqcd styles 0 and 2) COM TLM CRG
- *   tile-parts    one per tile, in any tile order; PLT and COM in the tile-part header
+ *   tile-parts    one per tile, in any tile order; PLT and COM in the tile-part header.  grk_amd_read_packets_parts (below) and the
+ *                 decode calls that read a file by themselves also take tiles divided into 1..255 tile-parts
  *   packets       the five progression orders, any precinct sizes, 1..N layers, SOP / EPH, empty packets, blocks that are not
  *                 included, tag trees in their general form, Part-1 codeword segments (TERMALL, LAZY) carried on across
  *                 layers, HT blocks with one pass
@@ -874,7 +875,29 @@ int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stre
                              grk_amd_coded_block* rows, uint64_t row_cap,
                              uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                              grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
-/* why the calling thread's latest grk_amd_read_header / grk_amd_read_packets refused ("" after a success) */
+/* grk_amd_read_packets for a codestream whose tiles may be divided into TILE-PARTS (what `grk_compress -u R|L|C`, the cinema and
+ * broadcast profiles and any writer that streams a tile resolution by resolution produce), asked for by name; signature and
+ * contract are grk_amd_read_packets', which keeps refusing a second tile-part of a tile.  A tile's packet sequence is its
+ * tile-parts' bodies end to end, each body a whole number of packets: rows, first_segment, segments, moves and *appendix_bytes are
+ * those of the undivided file, every offset and every move's src the byte's place in THIS file; nothing is copied for a
+ * single-layer file.  Taken on top of everything grk_amd_read_packets takes:
+ *   1..255 tile-parts per tile, at most 65535 in the file; a tile's in TPsot order 0, 1, 2, ... in the file, the tile-parts of
+ *   different tiles interleaved in any way; TNsot 0 ("not said here") or the tile's count in any mixture, 0 in every one included;
+ *   Psot 0 in the file's last tile-part only; tile-parts that hold no packet; TLM with one entry per tile-part in file order (every
+ *   Stlm form grk_amd_locate_tile_parts reads) or none; PLT and COM in every tile-part header, a tile-part's PLT listing its own
+ *   packets.  A tile whose every tile-part that holds packets carries PLT for exactly those is parsed precinct by precinct on
+ *   `threads` threads; any other tile as one chain in file order, the PLT entries that are present held against the packets read.
+ * GRK_AMD_ERR_INVALID, the reason naming tile and tile-part: a TPsot that is missing, repeated or out of file order; two different
+ * non-zero TNsot of one tile; a TNsot not above a TPsot seen, or above the tile-parts found; a packet that runs past the end of its
+ * tile-part; packets left over or missing at the tile's last tile-part; PLT lengths that do not add up to their tile-part; a Psot
+ * that leaves the stream; a tile without a tile-part.  GRK_AMD_ERR_UNSUPPORTED: COD / QCD / COC / QCC / RGN / POC / PPT in a
+ * tile-part header, a 256th tile-part of a tile, more than 65535 in the file.  grk_amd_read_header's flags describe the first
+ * tile-part.  Writing tile-parts is not built: the writers make one per tile. */
+int64_t grk_amd_read_packets_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                   grk_amd_coded_block* rows, uint64_t row_cap,
+                                   uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                   grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
+/* why the calling thread's latest grk_amd_read_header / grk_amd_read_packets / grk_amd_read_packets_parts refused ("" after a success) */
 const char* grk_amd_reader_last_error(void);
 /* Codestream -> pixels (Route C, decode; CodeStreamDecompress::decompress, codestream/CodeStreamDecompress.cpp:450-519).
  * cs: the codestream, host memory.  pixels: the image area, component-major planar, tight (or as grk_amd_set_decode_pixel_layout says; cap >= grk_amd_pixel_bytes of the image), ceil(prec / 8) bytes per sample -- the
@@ -1003,6 +1026,22 @@ int64_t grk_amd_read_packets_device_ex(grk_amd_ctx* ctx, const void* d_cs, uint6
                                        uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                                        grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
 int grk_amd_decode_image_device_ex(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device);
+/* grk_amd_read_packets_device_parts: grk_amd_read_packets_device_ex for a stream whose tiles may be divided into tile-parts, asked for
+ * by name: that call's signature and contract, built on the general reader (KC-L, KF, KP: 1 .. N layers, every style).  Field for
+ * field what grk_amd_read_packets_parts returns -- the moves as a set --, or the code that call gives with threads = 1.  KL-P (one
+ * workgroup) takes every tile-part of the file: TLM's places from the host, or one lane along the Psot chain (at most len / 14 + 1
+ * hops); all lanes check the SOTs and count the tile-parts per tile, a scan gives every tile its slice of a part table, a tile-part
+ * goes to slice + TPsot.  The status word and the located count (one word) come to the host behind it: KH-P's grid is the file's
+ * tile-parts.  KH-P: a workgroup per tile-part walks its header and counts its PLT entries; a workgroup per tile scans the counts,
+ * decides whether the tile is a PLT tile, and assembles entries and packet starts.  KC-L then bounds a packet by the end of the
+ * tile-part it starts in and steps from body to body where it reads a tile in file order.
+ * grk_amd_decode_image_device_ex takes such files without a switch: a file that KL refuses for a second tile-part is read again
+ * this way (a file with one tile-part per tile goes exactly the way it went); grk_amd_decode_image_device keeps its refusal.
+ * grk_amd_read_device_counters: 6 launches of KL-P / KH-P (three per read). */
+int64_t grk_amd_read_packets_device_parts(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, const grk_amd_stream_info* info,
+                                          grk_amd_coded_block* rows, uint64_t row_cap,
+                                          uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                          grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
 /* The placement kernel with clipping (device pointers; queued on the context's stream): as grk_amd_place_tiles_device, but unit i
  * goes to the SIGNED position (pos[2 i], pos[2 i + 1]) of the destination's planes and only what falls inside img_w x img_h is
  * written (a unit wholly outside: nothing).  channels = 0: ncomp planes; channels != 0: the units and the destination hold

@@ -13,7 +13,8 @@ from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Cont
                    Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, SURFACE_FORMATS_MSB, surface_bytes, surface_plan,
                    PACKED_FORMATS, packed_bytes,
                    CS_BLOCK_MSBS, DROP_SKIP, Rate, RateResult, RateAllocResult, RateError, Quality, QualityResult, QualityAllocResult, StageError, t2_max_block_bytes, t2_max_block_msbs,
-                   ERR_UNSUPPORTED, ERR_INVALID, READ_DEVICE_FIRST_COPY)
+                   ERR_UNSUPPORTED, ERR_INVALID, READ_DEVICE_FIRST_COPY,
+                   CS_TP, TP_R, TP_L, TP_C, WriterError, tile_part_starts, write_tile_parts, write_main_header_parts)
 
 __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
            "tile_layout", "reduced_tile_rect", "write_codestream", "write_tile_part", "write_main_header", "locate_tile_parts", "CS_TLM", "CS_PLT", "CS_SOP", "CS_EPH", "CS_PROG",
@@ -23,4 +24,5 @@ __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "C
            "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "SURFACE_FORMATS_MSB", "surface_bytes", "surface_plan",
            "PACKED_FORMATS", "packed_bytes",
            "CS_BLOCK_MSBS", "DROP_SKIP", "Rate", "RateResult", "RateAllocResult", "RateError", "Quality", "QualityResult", "QualityAllocResult", "StageError", "t2_max_block_bytes", "t2_max_block_msbs",
-           "ERR_UNSUPPORTED", "ERR_INVALID", "READ_DEVICE_FIRST_COPY"]
+           "ERR_UNSUPPORTED", "ERR_INVALID", "READ_DEVICE_FIRST_COPY",
+           "CS_TP", "TP_R", "TP_L", "TP_C", "WriterError", "tile_part_starts", "write_tile_parts", "write_main_header_parts"]

@@ -288,6 +288,17 @@ class StageError(RuntimeError):
         self.code, self.reason = int(code), reason
 
 
+class WriterError(RuntimeError):
+    """a host writer call refused: .code (ERR_UNSUPPORTED -2, ERR_INVALID -3, -5 overflow) and grk_amd_writer_last_error's reason."""
+
+    def __init__(self, what, code):
+        L = lib()
+        L.grk_amd_writer_last_error.restype = C.c_char_p
+        L.grk_amd_writer_last_error.argtypes = []
+        self.code, self.reason = int(code), L.grk_amd_writer_last_error().decode()
+        RuntimeError.__init__(self, "%s failed: %d (%s)" % (what, code, self.reason))
+
+
 _lib = None
 
 
@@ -546,6 +557,14 @@ DROP_SKIP = 0xFF             # a block's drop byte: not coded (grk_amd_stage_ht_
 STAGE_HT_ROOM = 1            # grk_amd_stage_ht_encode16 flags
 
 
+TP_R, TP_L, TP_C = 1, 2, 3   # the division letters of CS_TP
+
+
+def CS_TP(letter):
+    """tiles divided into tile-parts at this letter of the progression order (TP_R / TP_L / TP_C, grk_compress -u); 0: not divided"""
+    return int(letter) << 12
+
+
 def CS_PROG(order):
     """progression order for the writer's flags: 0 LRCP, 1 RLCP, 2 RPCL, 3 PCRL, 4 CPRL"""
     return int(order) << 8
@@ -605,7 +624,7 @@ def write_codestream_layout(layout, base, table, coded, flags=0):
     t = np.ascontiguousarray(table)
     n = L.grk_amd_write_codestream_layout(C.byref(layout), C.byref(base), t.ctypes.data, cbuf.ctypes.data, flags, out.ctypes.data, cap)
     if n < 0:
-        raise RuntimeError("grk_amd_write_codestream_layout failed: %d" % n)
+        raise WriterError("grk_amd_write_codestream_layout", n)
     return out[:n].tobytes()
 
 
@@ -651,6 +670,69 @@ def write_main_header(params, img_w, img_h, flags=0, tile_part_bytes=None):
                                     out.ctypes.data, out.size)
     if n < 0:
         raise RuntimeError("grk_amd_write_main_header failed: %d" % n)
+    return out[:n].tobytes()
+
+
+def _u8s(values):
+    return (C.c_uint8 * len(values))(*[int(v) for v in values]) if values is not None else None
+
+
+def tile_part_starts(tile, flags, sampling=None):
+    """grk_amd_tile_part_starts: (the first packet number of every tile-part of `tile` under flags' order and division, the tile's
+    packets).  tile: the tile on the reference grid (layout_tiles); sampling: [(dx, dy)] per component or None.  WriterError."""
+    L = lib()
+    L.grk_amd_tile_part_starts.restype = C.c_int64
+    L.grk_amd_tile_part_starts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    dx = _u8s([a for a, _ in sampling]) if sampling else None
+    dy = _u8s([b for _, b in sampling]) if sampling else None
+    starts = np.zeros(256, np.uint32)
+    npk = C.c_uint32(0)
+    n = L.grk_amd_tile_part_starts(C.addressof(tile), dx, dy, int(flags), starts.ctypes.data, starts.size, C.byref(npk))
+    if n < 0:
+        raise WriterError("grk_amd_tile_part_starts", n)
+    return [int(v) for v in starts[:n]], int(npk.value)
+
+
+def write_tile_parts(params, tile_index, tile_table, coded, flags=0, starts=None, size_only=False, cap=None):
+    """A tile divided into tile-parts (grk_amd_write_tile_parts) at the packets `starts`, or with starts None under the division of
+    `flags` -> (the parts' bytes one behind the other, [their lengths]); size_only: (the length, [lengths]).  WriterError."""
+    L = lib()
+    L.grk_amd_write_tile_parts.restype = C.c_int64
+    L.grk_amd_write_tile_parts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    t = np.ascontiguousarray(tile_table)
+    s = np.ascontiguousarray(starts, np.uint32) if starts is not None else None
+    lens = np.zeros(max(256, 0 if s is None else s.size), np.uint32)
+    args = (C.addressof(params), tile_index, int(flags), t.ctypes.data)
+    div = (s.ctypes.data if s is not None else None, s.size if s is not None else 0)
+    if size_only:
+        n = L.grk_amd_write_tile_parts(*args, None, *div, None, 0, lens.ctypes.data if s is None or s.size <= 255 else None)
+        if n < 0:
+            raise WriterError("grk_amd_write_tile_parts", n)
+        return int(n), lens
+    cbuf = np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else coded
+    if cap is None:
+        cap = int(t["length"].sum()) + len(t) * 8 + 4096 + 32 * 256
+    out = np.empty(cap + 64, np.uint8)
+    out[cap:] = 0xA5                                         # (a guard the call must not touch)
+    n = L.grk_amd_write_tile_parts(*args, cbuf.ctypes.data, *div, out.ctypes.data, cap, lens.ctypes.data if s is None or s.size <= 255 else None)
+    assert (out[cap:] == 0xA5).all(), "grk_amd_write_tile_parts wrote beyond cap"
+    if n < 0:
+        raise WriterError("grk_amd_write_tile_parts", n)
+    k = s.size if s is not None else int(np.count_nonzero(lens))
+    return out[:n].tobytes(), [int(v) for v in lens[:k]]
+
+
+def write_main_header_parts(layout, base, flags, parts_per_tile, part_bytes):
+    """grk_amd_write_main_header_parts: the main header of a file of divided tiles; TLM (CS_TLM) lists part_bytes in file order"""
+    L = lib()
+    L.grk_amd_write_main_header_parts.restype = C.c_int64
+    L.grk_amd_write_main_header_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    ppt = np.ascontiguousarray(parts_per_tile, np.uint32)
+    pb = np.ascontiguousarray(part_bytes, np.uint32)
+    out = np.empty(4096 + 5 * pb.size, np.uint8)
+    n = L.grk_amd_write_main_header_parts(C.addressof(layout), C.addressof(base), int(flags), ppt.ctypes.data, pb.ctypes.data, out.ctypes.data, out.size)
+    if n < 0:
+        raise WriterError("grk_amd_write_main_header_parts", n)
     return out[:n].tobytes()
 
 
@@ -1081,8 +1163,32 @@ class Context:
         self._L.grk_amd_assemble_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
         n = self._L.grk_amd_assemble_device(self._h, C.addressof(params), idx.size, idx.ctypes.data, flags, dst_offset, lens.ctypes.data)
         if n < 0:
-            raise RuntimeError("assemble_device failed: %d (%s)" % (n, self._L.grk_amd_last_error(self._h).decode()))
+            raise StageError("assemble_device", n, self._L.grk_amd_last_error(self._h).decode())
         return int(n), lens
+
+    def assembled_parts(self):
+        """grk_amd_assembled_parts: the tile-parts per tile of the latest assemble call (1: undivided)"""
+        self._L.grk_amd_assembled_parts.restype = C.c_uint32
+        self._L.grk_amd_assembled_parts.argtypes = [C.c_void_p]
+        return int(self._L.grk_amd_assembled_parts(self._h))
+
+    def stage_assemble_parts(self, params, tile_index, table, coded, flags=0, starts=None):
+        """grk_amd_stage_assemble_parts: stage_assemble with every tile divided into tile-parts at the packets `starts` (None: under
+        the division of `flags`) -> (bytes assembled, the parts' lengths [tile][part]).  StageError."""
+        idx = np.ascontiguousarray(np.asarray(tile_index, np.uint32))
+        t = np.ascontiguousarray(table, CODED_DTYPE)
+        cbuf = np.ascontiguousarray(np.frombuffer(coded, np.uint8) if not isinstance(coded, np.ndarray) else coded)
+        s = np.ascontiguousarray(starts, np.uint32) if starts is not None else None
+        lens = np.zeros((idx.size, 256), np.uint32)
+        fn = self._L.grk_amd_stage_assemble_parts
+        fn.restype = C.c_int64
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        n = fn(self._h, C.addressof(params), idx.size, idx.ctypes.data, int(flags), t.ctypes.data, cbuf.ctypes.data if cbuf.size else None,
+               cbuf.size, s.ctypes.data if s is not None else None, s.size if s is not None else 0, lens.ctypes.data)
+        if n < 0:
+            raise StageError("stage_assemble_parts", n, self._L.grk_amd_last_error(self._h).decode())
+        k = self.assembled_parts()
+        return int(n), lens.reshape(-1)[:idx.size * k].reshape(idx.size, k).copy()
 
     def stage_assemble(self, params, tile_index, table, coded, flags=0, _fn="grk_amd_stage_assemble"):
         """Tier-2 on the device for a table of the caller's (grk_amd_stage_assemble): `table` CODED_DTYPE, len(tile_index) x (blocks of a

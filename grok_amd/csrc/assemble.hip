@@ -2,6 +2,7 @@
 #include "context.h"
 #include "image.h"
 #include "t2_order.h"
+#include "t2_parts.h"
 
 // The finished tile-parts of coded blocks that lie on the device, made where they are (kernels_t2.hip): KT1 writes every packet's
 // header, KT1b frames the tile-parts (SOT, PLT, SOD) and says where every packet goes, KT2 gathers headers, code-block bytes and frames
@@ -23,16 +24,39 @@ struct T2Source {
 // the kernels queued on `st`, which must already be ordered behind the source's tables and bytes; `o` takes the tile-parts from
 // dst_offset on (what lies below is kept when the buffer has to grow; 16 bytes stay free behind them).  The scratch is the
 // context's: one stream at a time.
+// Tiles divided into tile-parts (GRK_AMD_CS_TP) take a path of their own: `starts` / `nparts` are the caller's division
+// (grk_amd_stage_assemble_parts), or with starts == NULL the plan's (T2Plan::part_starts, made from the flags); an undivided call
+// -- one part, none named -- runs KT1, KT1b and KT2 as before.  Divided: KT1, KT1p, KT1q, KT1r, KT2p (kernels_t2parts.hip).
 int assemble_enqueue(grk_amd_ctx* c, const T2Source& src, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags, uint64_t dst_offset,
-                     hipStream_t st, grk_amd_ctx::T2Out& o)
+                     hipStream_t st, grk_amd_ctx::T2Out& o, const uint32_t* starts = nullptr, uint32_t nparts = 0)
 {
     const T2Plan& plan = *src.plan;
     const size_t npk = plan.packets.size();
     const uint32_t bpt = src.bpt;
     const uint64_t nblocks = (uint64_t)bpt * ntiles;
     const size_t nq = npk * ntiles;
+    if (!starts && plan.part_starts.size() > 1) { starts = plan.part_starts.data(); nparts = (uint32_t)plan.part_starts.size(); }
+    const bool divided = starts != nullptr;
+    const bool plt = (flags & GRK_AMD_CS_PLT) != 0;
+    // the parts' frames in a tile's frame scratch, each with room for what its packets can need (t2_parts.h), on 16-byte boundaries
+    std::vector<T2Part>& parts = c->t2_parts_host;
+    if (divided) {
+        if (!nparts || nparts > kMaxTileParts || starts[0] != 0) return GRK_AMD_ERR_INVALID;
+        parts.assign(nparts, T2Part{});
+        uint64_t at = 0;
+        for (uint32_t k = 0; k < nparts; ++k) {
+            const uint64_t first = starts[k], last = k + 1 < nparts ? starts[k + 1] : npk;
+            if (first > last || last > npk) return GRK_AMD_ERR_INVALID;
+            parts[k] = T2Part{(uint32_t)first, (uint32_t)(last - first), (uint32_t)at};
+            at += (part_frame_bound(last - first, plt) + 15) & ~15ull;
+        }
+        if (at >> 32) return GRK_AMD_ERR_UNSUPPORTED;
+    }
+    o.nparts = divided ? nparts : 1u;
     // a frame: SOT 12, SOD 2, PLT: at most 6 bytes per packet and 5 per marker segment of 65 532
-    const uint32_t lit_stride = (uint32_t)((14 + 6 * npk + 5 * (6 * npk / 65000 + 2) + 15) & ~(size_t)15);
+    const uint32_t lit_stride = divided ? parts.back().frame_at + (uint32_t)((part_frame_bound(parts.back().count, plt) + 15) & ~15ull)
+                                        : (uint32_t)((14 + 6 * npk + 5 * (6 * npk / 65000 + 2) + 15) & ~(size_t)15);
+    const size_t nframes = (size_t)ntiles * (divided ? nparts : 1u);
     // what the call can write at most: every byte of the arena, every header, every frame
     const uint64_t bound = src.arena_bytes + (uint64_t)ntiles * (plan.h_bytes + lit_stride + 8ull * npk) + 16;
     auto need = [&](DevBuf& b, size_t n, const char* what) -> int {
@@ -51,7 +75,12 @@ int assemble_enqueue(grk_amd_ctx* c, const T2Source& src, uint32_t ntiles, const
     if ((rc = need(c->t2_pkbody, nq * 8, "alloc packet lengths"))) return rc;
     if ((rc = need(c->t2_pkdst, nq * 8, "alloc packet places"))) return rc;
     if ((rc = need(c->t2_lit, (size_t)lit_stride * ntiles, "alloc frames"))) return rc;
-    if ((rc = need(c->t2_litlen, (size_t)ntiles * 4, "alloc frames"))) return rc;
+    if ((rc = need(c->t2_litlen, nframes * 4, "alloc frames"))) return rc;
+    if (divided) {
+        if ((rc = need(c->t2_parts, (size_t)nparts * sizeof(T2Part), "alloc the tile-parts' table"))) return rc;
+        if ((rc = need(o.tp_len, nframes * 4, "alloc the parts' lengths"))) return rc;
+        if ((rc = need(o.tp_dst, nframes * 8, "alloc the parts' places"))) return rc;
+    }
     if ((rc = need(c->t2_index, (size_t)ntiles * 4, "alloc tile numbers"))) return rc;
     if ((rc = need(o.tile_dst, (size_t)ntiles * 8, "alloc tile-part places"))) return rc;
     if ((rc = need(o.part_len, (size_t)ntiles * 4, "alloc tile-part lengths"))) return rc;
@@ -80,6 +109,34 @@ int assemble_enqueue(grk_amd_ctx* c, const T2Source& src, uint32_t ntiles, const
     ha.msbs = src.msbs; ha.nodes = src.msbs ? (uint8_t*)c->t2_nodes.p : nullptr; ha.v_bytes = plan.v_bytes;
     HIP_TRY(c, launch_t2_header(ha, src.max_blocks, st), "launch Tier-2 headers");
     const uint32_t sop = (flags & GRK_AMD_CS_SOP) ? 6u : 0u, eph = (flags & GRK_AMD_CS_EPH) ? 2u : 0u;
+    if (divided) {
+        // (pageable memory of the context's, like the tile numbers above: the runtime has staged the table when hipMemcpyAsync returns,
+        //  so the next call -- of grk_amd_assemble_device_async too, which waits for nothing -- may write c->t2_parts_host anew)
+        HIP_TRY(c, hipMemcpyAsync(c->t2_parts.p, parts.data(), (size_t)nparts * sizeof(T2Part), hipMemcpyHostToDevice, st), "upload");
+        T2PartsArgs pa{};
+        pa.npackets = (uint32_t)npk; pa.ntiles = ntiles; pa.nparts = nparts; pa.parts = (const T2Part*)c->t2_parts.p;
+        pa.pk_hdr = ha.pk_hdr; pa.pk_body = ha.pk_body; pa.tile_index = (const uint32_t*)c->t2_index.p;
+        pa.extra = sop + eph; pa.plt = plt ? 1u : 0u; pa.dst_offset = dst_offset;
+        pa.lit = (uint8_t*)c->t2_lit.p; pa.lit_stride = lit_stride; pa.lit_len = (uint32_t*)c->t2_litlen.p;
+        pa.tp_len = (uint32_t*)o.tp_len.p; pa.tp_dst = (unsigned long long*)o.tp_dst.p; pa.pk_dst = (uint64_t*)c->t2_pkdst.p;
+        pa.part_len = (uint32_t*)o.part_len.p; pa.tile_dst = (unsigned long long*)o.tile_dst.p; pa.total = (unsigned long long*)o.total.p;
+        pa.status = src.status;
+        HIP_TRY(c, launch_t2_part_frames(pa, st), "launch tile-part frames");
+        HIP_TRY(c, launch_t2_part_places(pa, st), "launch tile-part places");
+        HIP_TRY(c, launch_t2_part_packets(pa, st), "launch tile-part packet places");
+        T2GatherArgs ga{};
+        ga.packets = (const T2Packet*)src.d_packets; ga.npackets = (uint32_t)npk; ga.packet_of_block = (const uint32_t*)src.d_pob;
+        ga.lengths = src.lengths; ga.offsets = src.offsets; ga.arena = src.arena;
+        ga.bpt = bpt; ga.ntiles = ntiles;
+        ga.hdr = (const uint8_t*)c->t2_h.p; ga.h_bytes = plan.h_bytes;
+        ga.rel = (const uint32_t*)c->t2_rel.p; ga.pk_hdr = (const uint32_t*)c->t2_pkhdr.p; ga.pk_dst = (const uint64_t*)c->t2_pkdst.p;
+        ga.lit = (const uint8_t*)c->t2_lit.p; ga.lit_stride = lit_stride; ga.lit_len = (const uint32_t*)c->t2_litlen.p;
+        ga.tile_dst = (const unsigned long long*)o.tile_dst.p;
+        ga.out = (uint8_t*)o.out.p;
+        ga.sop = sop; ga.eph = eph;
+        HIP_TRY(c, launch_t2_gather_parts(ga, pa.parts, nparts, pa.tp_dst, st), "launch Tier-2 gather");
+        return GRK_AMD_OK;
+    }
     T2FrameArgs fa{};
     fa.npackets = (uint32_t)npk; fa.ntiles = ntiles; fa.pk_hdr = ha.pk_hdr; fa.pk_body = ha.pk_body;
     fa.tile_index = (const uint32_t*)c->t2_index.p; fa.extra = sop + eph; fa.plt = (flags & GRK_AMD_CS_PLT) ? 1u : 0u;
@@ -129,15 +186,17 @@ int call_plan(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t flags, hipS
 {
     const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
     if (!msbs && (flags & GRK_AMD_CS_BLOCK_MSBS)) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
+    const uint32_t tp = (flags >> GRK_AMD_CS_TP_SHIFT) & 3u;
+    { std::string why; const int np = tile_part_count(flags, p->num_levels, p->num_comps, &why); if (np < 0) return fail(c, np, why.c_str()); }
     auto& T = c->t2;
-    if (!T.valid || !same_params(T.p, *p) || T.order != order || T.msbs != msbs) {
+    if (!T.valid || !same_params(T.p, *p) || T.order != order || T.tp != tp || T.msbs != msbs) {
         T.valid = false;
         int rc = msbs ? t2_device_plan_msbs(c->geom, flags, T.plan) : t2_device_plan(c->geom, flags, T.plan);
         if (rc) return fail(c, rc, "tile layout beyond the device writer's tables");
         T.max_blocks = plan_max_blocks(T.plan);
         // (the tables of the plan before may still be read by a gather that is queued: drained first)
         if ((rc = upload_plan(c, T.plan, T.packets, T.pob, st))) return rc;
-        T.p = *p; T.order = order; T.msbs = msbs; T.valid = true;
+        T.p = *p; T.order = order; T.tp = tp; T.msbs = msbs; T.valid = true;
     }
     return GRK_AMD_OK;
 }
@@ -183,7 +242,8 @@ int joint_plans(grk_amd_ctx* c, const JointT2Call& call, bool msbs)
     auto& J = c->t2j;
     const uint32_t flags = call.flags, order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u, nr = call.nruns, nc = call.base->num_comps;
     const UnitGroups& g = *call.g;
-    if (J.valid && J.msbs == msbs && std::memcmp(&J.im, call.im, sizeof J.im) == 0 && same_params(J.base, *call.base) && J.order == order && J.dx.size() == nc &&
+    const uint32_t tp = (flags >> GRK_AMD_CS_TP_SHIFT) & 3u;
+    if (J.valid && J.msbs == msbs && std::memcmp(&J.im, call.im, sizeof J.im) == 0 && same_params(J.base, *call.base) && J.order == order && J.tp == tp && J.dx.size() == nc &&
         std::memcmp(J.dx.data(), call.comp_dx, nc) == 0 && std::memcmp(J.dy.data(), call.comp_dy, nc) == 0 && J.unit_row.size() == g.of.size())
         return GRK_AMD_OK;
     J.valid = false;
@@ -243,7 +303,7 @@ int joint_plans(grk_amd_ctx* c, const JointT2Call& call, bool msbs)
         if ((rc = upload_plan(c, K.plan, K.packets, K.pob, c->stream))) return rc;
     }
     J.rows = row;
-    J.im = *call.im; J.base = *call.base; J.order = order; J.msbs = msbs;
+    J.im = *call.im; J.base = *call.base; J.order = order; J.tp = tp; J.msbs = msbs;
     J.dx.assign(call.comp_dx, call.comp_dx + nc); J.dy.assign(call.comp_dy, call.comp_dy + nc);
     J.valid = true;
     return GRK_AMD_OK;
@@ -263,6 +323,14 @@ int grow_keeping(grk_amd_ctx* c, DevBuf& b, size_t n, size_t keep, const char* w
 }
 } // namespace
 
+int grk_amd::assembled_part_bytes(grk_amd_ctx* c, uint32_t ntiles, uint32_t* out)
+{
+    auto& o = c->t2_outs[c->t2_cur];
+    HIP_TRY(c, hipMemcpyAsync(out, o.nparts > 1 ? o.tp_len.p : o.part_len.p, (size_t)ntiles * o.nparts * 4, hipMemcpyDeviceToHost, c->stream), "fetch the parts' lengths");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
+    return GRK_AMD_OK;
+}
+
 bool grk_amd::image_t2_host()
 {
     const char* const e = std::getenv("GRK_AMD_IMAGE_T2");
@@ -279,12 +347,19 @@ int grk_amd::joint_device_open(JointT2Run& r)
     if (!nr || g.of.empty() || g.of.size() % nr) return GRK_AMD_ERR_INVALID;
     r.ntiles = (uint32_t)(g.of.size() / nr);
     if ((call.flags & GRK_AMD_CS_TLM) && r.ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
+    {   // tiles divided into tile-parts: the plain encodes alone (a rate's byte budget would have to count the extra frames)
+        if (r.msbs && (call.flags & GRK_AMD_CS_TP(3))) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "GRK_AMD_CS_TP: not taken by the rate- and quality-targeted calls");
+        const int np = image_division(c, call.flags, call.base, r.ntiles);
+        if (np < 0) return np;
+        r.nparts = (uint32_t)np;
+    }
     HIP_TRY(c, hipSetDevice(c->device), "set device");
     { const int rc = joint_plans(c, call, r.msbs); if (rc) return rc; }
     auto& J = c->t2j;
     // the file's main header does not depend on the lengths it will carry (fixed-width TLM fields): its size now
     r.part_len.assign(r.ntiles, 0);
-    r.hdr_bytes = main_header_subsampled(call.im, call.base, call.comp_dx, call.comp_dy, call.flags, r.part_len.data(), nullptr, 0);
+    r.tp_len.assign((size_t)r.ntiles * r.nparts, 0);
+    r.hdr_bytes = main_header_any(call.im, call.base, call.comp_dx, call.comp_dy, call.flags, r.ntiles, r.nparts, r.nparts > 1 ? r.tp_len.data() : r.part_len.data(), nullptr, 0);
     if (r.hdr_bytes < 0) return (int)r.hdr_bytes;
     r.nb = call.batches.size();
     std::vector<uint64_t>& rowlist = r.rowlist;              // (uploaded in stream order: it lives as long as the run)
@@ -377,12 +452,15 @@ int64_t grk_amd::joint_device_finish(JointT2Run& r, uint8_t* out, uint64_t cap, 
         const int rc = assemble_enqueue(c, src, (uint32_t)K.tiles.size(), K.tiles.data(), flags, used, c->stream, o);
         if (rc) return rc;
         // only the tile-parts' lengths (and the status word) come to the host
-        std::vector<uint32_t> lens(K.tiles.size());
+        std::vector<uint32_t> lens(K.tiles.size()), tpl(r.nparts > 1 ? K.tiles.size() * r.nparts : 0);
         HIP_TRY(c, hipMemcpyAsync(lens.data(), o.part_len.p, lens.size() * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
+        // (divided tiles: the parts' lengths for TLM beside the spans)
+        if (!tpl.empty()) HIP_TRY(c, hipMemcpyAsync(tpl.data(), o.tp_len.p, tpl.size() * 4, hipMemcpyDeviceToHost, c->stream), "fetch the parts' lengths");
         HIP_TRY(c, hipMemcpyAsync(&status_word, status, 4, hipMemcpyDeviceToHost, c->stream), "fetch status");
         HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
         { const int se = status_error(c, status_word); if (se) return se; }
         for (size_t i = 0; i < lens.size(); ++i) { part_len[K.tiles[i]] = lens[i]; dev_at[K.tiles[i]] = used; used += lens[i]; }
+        for (size_t i = 0; i < tpl.size(); ++i) r.tp_len[(size_t)K.tiles[i / r.nparts] * r.nparts + i % r.nparts] = tpl[i];
     }
     c->t2_out_used = used;
 
@@ -398,12 +476,12 @@ int64_t grk_amd::joint_device_finish(JointT2Run& r, uint8_t* out, uint64_t cap, 
                 t = t1;
             }
             return GRK_AMD_OK;
-        }, call.comp_dx, call.comp_dy);
+        }, call.comp_dx, call.comp_dy, r.nparts, r.tp_len.data());
         return n;
     }
     // the file on the device: the header -- written now that the lengths are known -- and EOC around the tile-parts
     std::vector<uint8_t> hdr((size_t)hdr_bytes + 2);
-    const int64_t hn = main_header_subsampled(call.im, call.base, call.comp_dx, call.comp_dy, flags, part_len.data(), hdr.data(), (uint64_t)hdr_bytes);
+    const int64_t hn = main_header_any(call.im, call.base, call.comp_dx, call.comp_dy, flags, ntiles, r.nparts, r.nparts > 1 ? r.tp_len.data() : part_len.data(), hdr.data(), (uint64_t)hdr_bytes);
     if (hn != hdr_bytes) return hn < 0 ? hn : GRK_AMD_ERR_INVALID;
     const uint64_t body = used - first, total = (uint64_t)hdr_bytes + body + 2;
     uint8_t* file = (uint8_t*)o.out.p;                     // (assemble_enqueue left 16 bytes free behind the tile-parts)
@@ -507,12 +585,20 @@ int64_t grk_amd_assemble_rate_device(grk_amd_ctx* c, const grk_amd_tile_params* 
 // bytes -- rows may share bytes.  Everything is checked on the host before anything is launched; the tile-parts are read with
 // grk_amd_fetch_assembled.  The rows and bytes go to buffers of their own: the latest grk_amd_encode_tiles call stays assemblable.
 // (msbs: grk_amd_stage_assemble_msbs, `who` -- the rows' missing_msbs are written, through the general zero-bit-plane tree)
+// (starts / nparts: grk_amd_stage_assemble_parts -- the tiles divided at these packets, part_bytes then [tile][part]; NULL: no division
+//  but the flags')
 static int64_t stage_assemble_any(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
                                   const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes, uint32_t* part_bytes,
-                                  bool msbs, const char* who)
+                                  bool msbs, const char* who, const uint32_t* starts = nullptr, uint32_t nparts = 0, bool per_part = false)
 {
     char msg[200];
-    if (!c || !p || !ntiles || !tile_index || !table || (!coded && coded_bytes)) return GRK_AMD_ERR_INVALID;
+    if (!c || !p || !ntiles || !tile_index || !table || (!coded && coded_bytes) || (!starts != !nparts)) return GRK_AMD_ERR_INVALID;
+    if (starts) {
+        flags &= ~(uint32_t)GRK_AMD_CS_TP(3);                                 // (the caller's division, not the flags')
+        bool ok = nparts <= kMaxTileParts && starts[0] == 0;
+        for (uint32_t k = 1; ok && k < nparts; ++k) ok = starts[k - 1] <= starts[k];
+        if (!ok) { std::snprintf(msg, sizeof msg, "%s: 1 .. 255 tile-parts whose first packets do not decrease, the first at 0", who); return fail(c, GRK_AMD_ERR_INVALID, msg); }
+    }
     if (msbs) flags &= ~(uint32_t)GRK_AMD_CS_BLOCK_MSBS;                      // (accepted and implied)
     if (flags & GRK_AMD_CS_BLOCK_MSBS) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "grk_amd_stage_assemble: per-block zero bit-planes: the host writers only");
     for (uint32_t i = 0; i < ntiles; ++i)
@@ -548,6 +634,10 @@ static int64_t stage_assemble_any(grk_amd_ctx* c, const grk_amd_tile_params* p, 
         if (msbs) h_msbs[i] = (uint8_t)r.missing_msbs;
     }
     { const int rc = call_plan(c, p, flags, c->stream, msbs); if (rc) return rc; }
+    if (starts && starts[nparts - 1] > c->t2.plan.packets.size()) {
+        std::snprintf(msg, sizeof msg, "%s: a tile-part from packet %u on, the tile has %zu", who, starts[nparts - 1], c->t2.plan.packets.size());
+        return fail(c, GRK_AMD_ERR_INVALID, msg);
+    }
     // (no call of this entry leaves work behind: the buffers are free)
     HIP_TRY(c, c->st_len.ensure(rows * 4 + 16), "alloc the stage's lengths");
     HIP_TRY(c, c->st_off.ensure(rows * 8 + 16), "alloc the stage's offsets");
@@ -567,12 +657,13 @@ static int64_t stage_assemble_any(grk_amd_ctx* c, const grk_amd_tile_params* p, 
                        (const uint8_t*)c->st_arena.p, sum, (unsigned int*)c->st_status.p, msbs ? (const uint8_t*)c->st_msbs.p : nullptr};
     auto& o = c->t2_outs[c->t2_cur];
     c->t2_out_used = 0;
-    { const int rc = assemble_enqueue(c, src, ntiles, tile_index, flags, 0, c->stream, o); if (rc) return rc; }
+    { const int rc = assemble_enqueue(c, src, ntiles, tile_index, flags, 0, c->stream, o, starts, nparts); if (rc) return rc; }
     uint32_t status_word = 0;
     uint64_t total[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(&status_word, c->st_status.p, 4, hipMemcpyDeviceToHost, c->stream), "fetch status");
     HIP_TRY(c, hipMemcpyAsync(total, o.total.p, 16, hipMemcpyDeviceToHost, c->stream), "fetch total");
-    if (part_bytes) HIP_TRY(c, hipMemcpyAsync(part_bytes, o.part_len.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
+    if (part_bytes && per_part && o.nparts > 1) HIP_TRY(c, hipMemcpyAsync(part_bytes, o.tp_len.p, (size_t)ntiles * o.nparts * 4, hipMemcpyDeviceToHost, c->stream), "fetch the parts' lengths");
+    else if (part_bytes) HIP_TRY(c, hipMemcpyAsync(part_bytes, o.part_len.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, c->stream), "fetch tile-part lengths");
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");
     { const int se = status_error(c, status_word); if (se) return se; }
     c->t2_out_used = total[1];
@@ -593,6 +684,17 @@ int64_t grk_amd_stage_assemble_msbs(grk_amd_ctx* c, const grk_amd_tile_params* p
 {
     return stage_assemble_any(c, p, ntiles, tile_index, flags, table, coded, coded_bytes, part_bytes, true, "grk_amd_stage_assemble_msbs");
 }
+
+// grk_amd_stage_assemble with the tiles divided into tile-parts: at the caller's packets (starts[nparts], as grk_amd_write_tile_parts
+// takes them), or with starts == NULL under the division of `flags`.  part_bytes: [num_tiles][parts], the parts' lengths.
+int64_t grk_amd_stage_assemble_parts(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, const uint32_t* tile_index, uint32_t flags,
+                                     const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes,
+                                     const uint32_t* starts, uint32_t nparts, uint32_t* part_bytes)
+{
+    return stage_assemble_any(c, p, ntiles, tile_index, flags, table, coded, coded_bytes, part_bytes, false, "grk_amd_stage_assemble_parts", starts, nparts, true);
+}
+
+uint32_t grk_amd_assembled_parts(grk_amd_ctx* c) { return c ? c->t2_outs[c->t2_cur].nparts : 0; }
 
 uint32_t grk_amd_t2_max_block_msbs(void) { return kT2MaxMsbs; }
 uint32_t grk_amd_t2_max_block_bytes(void) { return (1u << kT2MaxLenBits) - 1u; }
@@ -624,7 +726,8 @@ void* grk_amd_assembled_table_ptr(grk_amd_ctx* c, int which)
 {
     if (!c) return nullptr;
     auto& o = c->t2_outs[c->t2_cur];
-    return which == 0 ? o.tile_dst.p : which == 1 ? o.part_len.p : which == 2 ? o.total.p : nullptr;
+    // (3: uint32[tiles][grk_amd_assembled_parts] the tile-parts' lengths; tables 0 and 1 are the tiles' -- of a divided tile its span)
+    return which == 0 ? o.tile_dst.p : which == 1 ? o.part_len.p : which == 2 ? o.total.p : which == 3 ? (o.nparts > 1 ? o.tp_len.p : o.part_len.p) : nullptr;
 }
 
 // bytes [offset, offset + nbytes) of the assembled tile-parts to host memory: pinned memory in one DMA, pageable memory through the

@@ -145,16 +145,19 @@ struct grk_amd_ctx {
     // finished tile-parts
     struct T2State {
         bool valid = false; grk_amd_tile_params p{}; uint32_t order = 0;
+        uint32_t tp = 0;                                     // the division into tile-parts the plan's part_starts were made for (GRK_AMD_CS_TP's letter)
         bool msbs = false;                                   // the plan of the general zero-bit-plane tree (t2_device_plan_msbs)
         T2Plan plan; uint32_t max_blocks = 0;
         DevBuf packets, pob;
     } t2;
     DevBuf t2_u, t2_h, t2_rel, t2_pkhdr, t2_pkbody, t2_pkdst, t2_lit, t2_litlen, t2_index;      // scratch: ONE stream at a time uses it
     DevBuf t2_nodes;                                         // ... the general zero-bit-plane tree's node values (T2Plan::v_bytes per tile)
+    DevBuf t2_parts; std::vector<T2Part> t2_parts_host;      // ... a divided call's tile-parts (kernels.h: T2Part), the same for every tile of the call
     // the finished tile-parts, their places and lengths ([tile]: uint64 / uint32) and {bytes assembled by the call, end of the output};
     // the asynchronous form rotates as many of these as the encoder rotates buffer sets, so that a frame's tile-parts stay where they
     // are while an exchange sends them
-    struct T2Out { DevBuf out, tile_dst, part_len, total; };
+    // (a call whose tiles are divided into tile-parts: tile_dst / part_len are the tiles' spans, tp_dst / tp_len [tile][part] the parts')
+    struct T2Out { DevBuf out, tile_dst, part_len, total, tp_len, tp_dst; uint32_t nparts = 1; };
     T2Out t2_outs[kMaxAltSets + 1];
     int t2_cur = 0;
     uint64_t t2_out_used = 0;        // (the synchronous form) bytes of t2_outs[t2_cur].out that hold tile-parts
@@ -164,7 +167,7 @@ struct grk_amd_ctx {
     // (uint64[batches + 1]) with the image's status word behind them, the units' first rows batch by batch, and the file of a
     // grk_amd_encode_*_device call whose tile classes do not lie in tile order
     struct T2Joint {
-        bool valid = false; grk_amd_image_layout im{}; grk_amd_tile_params base{}; std::vector<uint8_t> dx, dy; uint32_t order = 0;
+        bool valid = false; grk_amd_image_layout im{}; grk_amd_tile_params base{}; std::vector<uint8_t> dx, dy; uint32_t order = 0, tp = 0;
         bool msbs = false;                                   // the classes' plans are those of the general zero-bit-plane tree
         struct Class { T2Plan plan; uint32_t max_blocks = 0, bpt = 0; uint64_t row_begin = 0; std::vector<uint32_t> tiles; DevBuf packets, pob; };
         std::vector<Class> classes;

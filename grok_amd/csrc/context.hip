@@ -307,9 +307,9 @@ void grk_amd_destroy(grk_amd_ctx* c)
     }
     c->ovf.release();
     for (DevBuf* b : {&c->t2.packets, &c->t2.pob, &c->t2_u, &c->t2_h, &c->t2_rel, &c->t2_pkhdr, &c->t2_pkbody, &c->t2_pkdst, &c->t2_lit,
-                      &c->t2_litlen, &c->t2_index, &c->t2_nodes})
+                      &c->t2_litlen, &c->t2_index, &c->t2_nodes, &c->t2_parts})
         b->release();
-    for (auto& o : c->t2_outs) for (DevBuf* b : {&o.out, &o.tile_dst, &o.part_len, &o.total}) b->release();
+    for (auto& o : c->t2_outs) for (DevBuf* b : {&o.out, &o.tile_dst, &o.part_len, &o.total, &o.tp_len, &o.tp_dst}) b->release();
     for (auto& k : c->t2j.classes) { k.packets.release(); k.pob.release(); }
     for (DevBuf* b : {&c->jt_len, &c->jt_off, &c->jt_arena, &c->jt_state, &c->jt_rowat, &c->jt_file, &c->jt_msbs}) b->release();
     for (DevBuf* b : {&c->st_len, &c->st_off, &c->st_arena, &c->st_status, &c->st_msbs}) b->release();

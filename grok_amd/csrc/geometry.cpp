@@ -7,6 +7,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 
 namespace grk_amd {
@@ -365,4 +366,98 @@ extern "C" int grk_amd_same_tile_packets(const grk_amd_tile_params* a, const grk
     rc = grk_amd::build_tile_geom(*b, gb); if (rc) return rc;
     return a->num_comps == b->num_comps && grk_amd::same_geometry(ga, gb) &&
            grk_amd::same_packets(ga, gb, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u) ? 1 : 0;
+}
+
+// ---- tiles divided into tile-parts (GRK_AMD_CS_TP; t2_order.h) -----------------------------------------------------------------------
+// The reference's rule (CodeStreamCompress::get_num_tp, pi_enable_tile_part_generation) for this encoder's one layer: with `pos` the
+// place of the division letter in the progression order's name, a packet's key is its coordinates for the letters 0 .. pos, and a new
+// tile-part starts where the key changes.  The parts are the keys, whether or not a key has packets: the product of the letters'
+// extents (L: 1, R: num_levels + 1, C: num_comps).  A P at or before the division letter multiplies by a bound on the precincts in the
+// reference and normally fails its own limit: refused here.
+namespace {
+thread_local std::string g_writer_error;
+const char* const kOrderNames[5] = {"LRCP", "RLCP", "RPCL", "PCRL", "CPRL"};
+}
+
+int grk_amd::writer_refuse(int code, const std::string& why) { g_writer_error = why; return code; }
+extern "C" const char* grk_amd_writer_last_error(void) { return g_writer_error.c_str(); }
+
+int grk_amd::tile_part_count(uint32_t flags, uint32_t num_levels, uint32_t num_comps, std::string* why)
+{
+    const uint32_t d = (flags >> GRK_AMD_CS_TP_SHIFT) & 3u, order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
+    if (!d) return 1;
+    auto refuse = [&](const std::string& s) { if (why) *why = s; return (int)GRK_AMD_ERR_UNSUPPORTED; };
+    if (order > 4) { if (why) *why = "no such progression order"; return GRK_AMD_ERR_INVALID; }
+    const char letter = d == GRK_AMD_TP_R ? 'R' : d == GRK_AMD_TP_L ? 'L' : 'C';
+    const char* const name = kOrderNames[order];
+    uint64_t n = 1;
+    for (uint32_t i = 0;; ++i) {
+        if (name[i] == 'P')
+            return refuse(std::string("tile-parts divided at ") + letter + " under " + name + ": a P at or before the division letter");
+        n *= name[i] == 'R' ? num_levels + 1u : name[i] == 'C' ? num_comps : 1u;
+        if (name[i] == letter) break;
+    }
+    if (n > 255) return refuse(std::to_string(n) + " tile-parts per tile: TPsot takes at most 255");
+    return (int)n;
+}
+
+int grk_amd::tile_part_starts(const std::vector<Pk>& seq, uint32_t flags, uint32_t num_levels, uint32_t num_comps, std::vector<uint32_t>& starts,
+                              std::string* why)
+{
+    const int n = tile_part_count(flags, num_levels, num_comps, why);
+    if (n < 0) return n;
+    starts.assign((size_t)n, 0);
+    if (n == 1) return n;
+    const uint32_t d = (flags >> GRK_AMD_CS_TP_SHIFT) & 3u, order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
+    const char letter = d == GRK_AMD_TP_R ? 'R' : d == GRK_AMD_TP_L ? 'L' : 'C';
+    const char* const name = kOrderNames[order];
+    std::vector<uint32_t> count((size_t)n, 0);
+    for (const Pk& q : seq) {
+        uint32_t key = 0;                                   // the key as a number: the letters' coordinates, the first the most significant
+        for (uint32_t i = 0;; ++i) {
+            if (name[i] == 'R') key = key * (num_levels + 1u) + q.r;
+            else if (name[i] == 'C') key = key * num_comps + q.c;
+            if (name[i] == letter) break;
+        }
+        ++count[key];
+    }
+    for (int k = 1; k < n; ++k) starts[k] = starts[k - 1] + count[k - 1];
+    return n;
+}
+
+extern "C" int64_t grk_amd_tile_part_starts(const grk_amd_tile_params* tile, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t flags,
+                                            uint32_t* starts, uint32_t cap, uint32_t* num_packets)
+{
+    using namespace grk_amd;
+    if (!tile || !tile->num_comps || (!comp_dx != !comp_dy)) return writer_refuse(GRK_AMD_ERR_INVALID, "grk_amd_tile_part_starts: no tile, or one of comp_dx / comp_dy alone");
+    if (((flags >> GRK_AMD_CS_PROG_SHIFT) & 7u) > 4) return writer_refuse(GRK_AMD_ERR_INVALID, "no such progression order");
+    const uint32_t nc = tile->num_comps;
+    // (the rule's refusals need the letters' extents alone: said before the geometry is looked at)
+    { std::string why; const int n = tile_part_count(flags, tile->num_levels, nc, &why); if (n < 0) return writer_refuse(n, why); }
+    // component c's tile-component: the tile's rectangle in its own coordinates (grk_amd_layout_tile_comp)
+    std::vector<TileGeom> geoms(nc);
+    std::vector<const TileGeom*> cg(nc);
+    const uint64_t x0 = tile->tile_x0, y0 = tile->tile_y0, x1 = x0 + tile->tile_w, y1 = y0 + tile->tile_h;
+    for (uint32_t c = 0; c < nc; ++c) {
+        const uint64_t dx = comp_dx && comp_dx[c] ? comp_dx[c] : 1, dy = comp_dy && comp_dy[c] ? comp_dy[c] : 1;
+        grk_amd_tile_params p = *tile;
+        const uint64_t cx0 = (x0 + dx - 1) / dx, cy0 = (y0 + dy - 1) / dy, cx1 = (x1 + dx - 1) / dx, cy1 = (y1 + dy - 1) / dy;
+        if (cx1 <= cx0 || cy1 <= cy0) return writer_refuse(GRK_AMD_ERR_UNSUPPORTED, "a tile without a sample of a component");
+        p.tile_x0 = (uint32_t)cx0; p.tile_y0 = (uint32_t)cy0; p.tile_w = (uint32_t)(cx1 - cx0); p.tile_h = (uint32_t)(cy1 - cy0);
+        if (c && dx == (comp_dx && comp_dx[c - 1] ? comp_dx[c - 1] : 1) && dy == (comp_dy && comp_dy[c - 1] ? comp_dy[c - 1] : 1)) { cg[c] = cg[c - 1]; continue; }
+        const int rc = build_tile_geom(p, geoms[c]);
+        if (rc) return writer_refuse(rc, "grk_amd_tile_part_starts: the tile's parameters are refused");
+        cg[c] = &geoms[c];
+    }
+    const std::vector<Pk> seq = packet_order(cg, comp_dx, comp_dy, tile->tile_x0, tile->tile_y0, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
+    std::vector<uint32_t> s;
+    std::string why;
+    const int n = tile_part_starts(seq, flags, tile->num_levels, nc, s, &why);
+    if (n < 0) return writer_refuse(n, why);
+    if (num_packets) *num_packets = (uint32_t)seq.size();
+    if (starts) {
+        if ((uint32_t)n > cap) return writer_refuse(GRK_AMD_ERR_OVERFLOW, "grk_amd_tile_part_starts: more tile-parts than `cap`");
+        std::copy(s.begin(), s.end(), starts);
+    }
+    return n;
 }

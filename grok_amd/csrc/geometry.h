@@ -100,6 +100,7 @@ struct T2Plan {
     std::vector<uint32_t> packet_of_block;        // [rows of a tile]
     uint32_t u_words = 0, h_bytes = 0;            // scratch per tile
     uint32_t v_bytes = 0;                         // ... and, in a plan of the general tree alone, for the node values
+    std::vector<uint32_t> part_starts;            // the first packet of every tile-part under the flags' division (GRK_AMD_CS_TP; {0}: none)
 };
 // (kT2MaxLenBits, the block lengths the device writer takes, and kT2MaxHeight: t2_bits.h)
 int t2_device_plan(const TileGeom& g, uint32_t flags, T2Plan& out);

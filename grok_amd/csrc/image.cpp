@@ -10,6 +10,8 @@
 // tile-parts are written in tile order (codestream/CodeStreamCompress.cpp:535-603); those steps (image.h) serve node.cpp too.
 #include "image.h"
 #include "context.h"
+#include "t2_order.h"
+#include "t2_parts.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -116,12 +118,34 @@ void grk_amd::planar_rate_call(grk_amd_ctx* ctx, const std::vector<Unit>& units,
     };
 }
 
+int grk_amd::image_division(grk_amd_ctx* c, uint32_t flags, const grk_amd_tile_params* base, uint32_t ntiles)
+{
+    std::string why;
+    const int np = tile_part_count(flags, base->num_levels, base->num_comps, &why);
+    if (np < 0) return fail(c, np, why.c_str());
+    if (np > 1 && (flags & GRK_AMD_CS_TLM) && (uint64_t)np * ntiles > kMaxTlmEntries)
+        return fail(c, GRK_AMD_ERR_UNSUPPORTED, "more tile-parts than one TLM marker segment lists (13 106)");
+    return np;
+}
+
+int64_t grk_amd::main_header_any(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                                 uint32_t flags, uint32_t ntiles, uint32_t nparts, const uint32_t* tp_bytes, uint8_t* out, uint64_t cap)
+{
+    if (nparts > 1) {
+        const std::vector<uint32_t> per_tile(ntiles, nparts);
+        return main_header_parts(im, base, comp_dx, comp_dy, flags, per_tile.data(), tp_bytes, out, cap);
+    }
+    return comp_dx ? main_header_subsampled(im, base, comp_dx, comp_dy, flags, tp_bytes, out, cap)
+                   : grk_amd_write_main_header_layout(im, base, flags, tp_bytes, out, cap);
+}
+
 int64_t grk_amd::frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
                             const std::vector<uint32_t>& part_len, uint8_t* out, uint64_t cap,
-                            const std::function<int(const std::vector<uint64_t>& at)>& body, const uint8_t* comp_dx, const uint8_t* comp_dy)
+                            const std::function<int(const std::vector<uint64_t>& at)>& body, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                            uint32_t nparts, const uint32_t* tp_bytes)
 {
-    const int64_t hdr = comp_dx && comp_dy ? main_header_subsampled(im, base, comp_dx, comp_dy, flags, part_len.data(), out, cap)
-                                           : grk_amd_write_main_header_layout(im, base, flags, part_len.data(), out, cap);
+    const int64_t hdr = main_header_any(im, base, comp_dx && comp_dy ? comp_dx : nullptr, comp_dx && comp_dy ? comp_dy : nullptr, flags,
+                                        (uint32_t)part_len.size(), nparts, nparts > 1 ? tp_bytes : part_len.data(), out, cap);
     if (hdr < 0) return hdr;
     std::vector<uint64_t> at(part_len.size() + 1, (uint64_t)hdr);
     for (size_t t = 0; t < part_len.size(); ++t) at[t + 1] = at[t] + part_len[t];
@@ -151,9 +175,12 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
     // Tier-2 on the device (grk_amd_assemble_device; GRK_AMD_IMAGE_T2=host: the host writer below, which is also where a layout beyond
     // the device writer's tables goes): every group's finished tile-parts appended in the context's output buffer, then -- their sizes
     // known -- the main header and each tile-part fetched to its place
+    // tiles divided into tile-parts (GRK_AMD_CS_TP): what neither route can write is said before any work
+    uint32_t nparts = 1;
+    { const int np = image_division(ctx, flags, base, ntiles); if (np < 0) return np; nparts = (uint32_t)np; }
     const char* const et2 = std::getenv("GRK_AMD_IMAGE_T2");
     if (!(et2 && std::strcmp(et2, "host") == 0)) {
-        std::vector<uint32_t> part_len(ntiles, 0);
+        std::vector<uint32_t> part_len(ntiles, 0), tp_len((size_t)ntiles * nparts, 0), tpl;
         std::vector<uint64_t> dev_at(ntiles, 0);
         std::vector<uint8_t> staging;
         uint64_t used = 0;
@@ -168,9 +195,15 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
             rc = grk_amd_assemble_device(ctx, &p, (uint32_t)G.size(), G.data(), flags, used, lens.data());
             if (rc < 0) break;
             for (size_t i = 0; i < G.size(); ++i) { part_len[G[i]] = lens[i]; dev_at[G[i]] = used; used += lens[i]; }
+            if (nparts > 1) {           // the parts' lengths for TLM beside the spans
+                tpl.resize(G.size() * nparts);
+                const int fr = assembled_part_bytes(ctx, (uint32_t)G.size(), tpl.data());
+                if (fr) return fr;
+                for (size_t i = 0; i < tpl.size(); ++i) tp_len[(size_t)G[i / nparts] * nparts + i % nparts] = tpl[i];
+            }
         }
-        if (rc >= 0)
-            return frame_file(im, base, flags, part_len, out, cap, [&](const std::vector<uint64_t>& at) -> int {
+        if (rc >= 0) {
+            const int64_t n = frame_file(im, base, flags, part_len, out, cap, [&](const std::vector<uint64_t>& at) -> int {
                 for (uint32_t t = 0; t < ntiles; ++t) {
                     // (tile-parts that lie one behind the other on the device as in the file go in one piece)
                     uint32_t t1 = t;
@@ -181,7 +214,9 @@ extern "C" int64_t grk_amd_encode_image(grk_amd_ctx* ctx, const grk_amd_image_la
                     t = t1;
                 }
                 return GRK_AMD_OK;
-            });
+            }, nullptr, nullptr, nparts, tp_len.data());
+            return n;
+        }
         if (rc != GRK_AMD_ERR_UNSUPPORTED) return rc;
     }
     std::vector<grk_amd_coded_block> rows;

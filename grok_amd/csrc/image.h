@@ -94,11 +94,19 @@ int encode_groups_host(grk_amd_ctx* ctx, const SourcePlanes& src, const std::vec
 // GRK_AMD_ERR_OVERFLOW when `cap` cannot hold it, or the body's error.
 // comp_dx / comp_dy (both or neither): the file of an image of sub-sampled components -- SIZ carries the factors, COD no colour
 // transform unless components 0..2 share theirs (main_header_subsampled, t2_writer.cpp: the header grk_amd_write_codestream_subsampled writes)
+// tp_bytes (tiles divided into tile-parts, GRK_AMD_CS_TP: nparts > 1 each): the parts' lengths in file order for TLM, nparts per tile;
+// part_len[t] stays the tile's SPAN -- all its parts, which is what `body` places
 int64_t frame_file(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags, const std::vector<uint32_t>& part_len,
                    uint8_t* out, uint64_t cap, const std::function<int(const std::vector<uint64_t>& at)>& body,
-                   const uint8_t* comp_dx = nullptr, const uint8_t* comp_dy = nullptr);
+                   const uint8_t* comp_dx = nullptr, const uint8_t* comp_dy = nullptr, uint32_t nparts = 1, const uint32_t* tp_bytes = nullptr);
 int64_t main_header_subsampled(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
                                uint32_t flags, const uint32_t* tile_part_bytes, uint8_t* out, uint64_t cap);
+// the main header of a file of divided tiles (grk_amd_write_main_header_parts; comp_dx / comp_dy both or neither: main_header_subsampled's)
+int64_t main_header_parts(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                          uint32_t flags, const uint32_t* parts_per_tile, const uint32_t* part_bytes, uint8_t* out, uint64_t cap);
+// the header of either kind: nparts parts in every tile (1: the undivided file's header, tp_bytes the tiles' lengths)
+int64_t main_header_any(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                        uint32_t flags, uint32_t ntiles, uint32_t nparts, const uint32_t* tp_bytes, uint8_t* out, uint64_t cap);
 
 // ---- Tier-2 on the device for an image whose units are coded by several batches (assemble.hip) -------------------------------------
 // The caller names the image's units -- unit t * nruns + k is run k (comp_runs) of tile t, `g` their geometry groups -- and its batches,
@@ -130,11 +138,18 @@ struct JointT2Run {
     std::vector<uint64_t> rowlist{}, batch_at{};
     uint64_t bound_at = 0;                                   // the kept batches' arena bounds so far
     std::vector<uint32_t> part_len{};
+    uint32_t nparts = 1;                                     // tile-parts per tile (GRK_AMD_CS_TP) ...
+    std::vector<uint32_t> tp_len{};                          // ... and their lengths in file order, for TLM: [tile][part]
 };
 int joint_device_open(JointT2Run& r);
 int joint_device_reset(JointT2Run& r);
 int joint_device_keep(JointT2Run& r, size_t b);
 int64_t joint_device_finish(JointT2Run& r, uint8_t* out, uint64_t cap, void** d_file);
+// GRK_AMD_CS_TP as a whole-image call meets it, before any work: the tile-parts per tile (1: none), or the refusal with its reason in the
+// context -- the rule's (t2_order.h: tile_part_count), or with TLM more parts in the file than one marker segment lists
+int image_division(grk_amd_ctx* c, uint32_t flags, const grk_amd_tile_params* base, uint32_t ntiles);
+// the tile-parts' lengths of the latest grk_amd_assemble_device call (its table 3: [tile][grk_amd_assembled_parts]) to the host
+int assembled_part_bytes(grk_amd_ctx* c, uint32_t ntiles, uint32_t* out);
 // GRK_AMD_IMAGE_T2=host, read per call: the whole-image encoders write their files with the host writer
 bool image_t2_host();
 

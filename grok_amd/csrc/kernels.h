@@ -349,6 +349,31 @@ struct T2GatherArgs {
 };
 hipError_t launch_t2_gather(const T2GatherArgs& a, hipStream_t s);
 
+// ---- KT1p / KT1q / KT1r / KT2p: tiles divided into tile-parts (kernels_t2parts.hip) -------------------------------------------------
+// Part k of every tile of the call holds the tile's packets [first, first + count) and has its frame (SOT with TPsot / TNsot / Psot,
+// the PLT marker segments of its own packets, SOD) at frame_at bytes of the tile's frame scratch, part_frame_bound(count) of room
+struct T2Part { uint32_t first, count, frame_at; };
+struct T2PartsArgs {
+    uint32_t npackets, ntiles, nparts;
+    const T2Part* parts;                             // [part]: the same division for every tile of the call
+    const uint32_t* pk_hdr; const uint64_t* pk_body; // [tile][packet], KT1's
+    const uint32_t* tile_index;                      // [tile]: Isot
+    uint32_t extra, plt;                             // as T2FrameArgs
+    uint64_t dst_offset;
+    uint8_t* lit; uint32_t lit_stride;               // the tiles' frame scratch
+    uint32_t* lit_len;                               // [tile][part]: the frame's bytes
+    uint32_t* tp_len; unsigned long long* tp_dst;    // [tile][part]: the part's length (Psot) and its place in the output
+    uint64_t* pk_dst;                                // [tile][packet]
+    uint32_t* part_len; unsigned long long* tile_dst;   // [tile]: the tile's SPAN -- all its parts, which lie one behind the other
+    unsigned long long* total;
+    unsigned int* status;                            // bit 3: a part or a tile's span beyond 4 GB / PLT beyond 256 marker segments in a part
+};
+hipError_t launch_t2_part_frames(const T2PartsArgs& a, hipStream_t s);     // KT1p
+hipError_t launch_t2_part_places(const T2PartsArgs& a, hipStream_t s);     // KT1q
+hipError_t launch_t2_part_packets(const T2PartsArgs& a, hipStream_t s);    // KT1r
+// KT2p: KT2 with ntiles x nparts frame items (g.lit_len: [tile][part]; g.tile_dst is not read)
+hipError_t launch_t2_gather_parts(const T2GatherArgs& g, const T2Part* parts, uint32_t nparts, const unsigned long long* tp_dst, hipStream_t s);
+
 // ---- KK: a batch's table and coded bytes into image-wide tables and an image-wide arena (kernels_t2keep.hip) -----------------------
 struct T2KeepArgs {
     const uint32_t* lengths; const unsigned long long* offsets;   // the batch's table: [unit][row], nunits x bpu entries

@@ -183,6 +183,10 @@ static int64_t node_encode_locked(grk_amd_node* nd, const grk_amd_image_layout* 
     if (!nd) return GRK_AMD_ERR_INVALID;
     std::lock_guard<std::mutex> lk(nd->mu);
     nd->err.clear();
+    if (flags & GRK_AMD_CS_TP(3)) {
+        nd->err = "GRK_AMD_CS_TP: tiles divided into tile-parts are not written by the node";
+        return GRK_AMD_ERR_UNSUPPORTED;
+    }
     int64_t rc = node_encode_image(nd, im, base, pixels, pixels_device, flags, out, cap, false);
     // (a layout beyond the device writer's tables -- header bits of one packet past 2^31, a code-block of 512 MB: the host writer takes it)
     if (rc == GRK_AMD_ERR_UNSUPPORTED && !(flags & GRK_AMD_NODE_GATHER) && device_t2()) {

@@ -340,6 +340,8 @@ int64_t image_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const grk_a
                    const grk_amd_rate* rate, const QualityGoal* quality, uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
 {
     if (ctx->pipelining) return rate_refusal(ctx, rate);          // (max_drop is looked at behind plain_image's checks, by the run)
+    // (a byte budget would have to count the extra frames)
+    if (flags & GRK_AMD_CS_TP(3)) return fail(ctx, GRK_AMD_ERR_UNSUPPORTED, "GRK_AMD_CS_TP: tiles divided into tile-parts are not written by the rate- and quality-targeted calls");
     flags |= GRK_AMD_CS_BLOCK_MSBS;
     std::vector<Unit> tiles;
     SourcePlanes src;
@@ -405,6 +407,7 @@ int64_t subsampled_rate(grk_amd_ctx* ctx, const grk_amd_image_layout* im, const 
                         uint8_t* out, uint64_t cap, grk_amd_rate_result* result)
 {
     { const int rr = rate_refusal(ctx, rate); if (rr) return rr; }
+    if (flags & GRK_AMD_CS_TP(3)) return fail(ctx, GRK_AMD_ERR_UNSUPPORTED, "GRK_AMD_CS_TP: tiles divided into tile-parts are not written by the rate- and quality-targeted calls");
     flags |= GRK_AMD_CS_BLOCK_MSBS;
     std::vector<Unit> units;
     SourcePlanes src;

@@ -201,6 +201,8 @@ int64_t encode_surface_job(grk_amd_ctx* c, const grk_amd_image_layout* im, const
 {
     // (a plain encode drops nothing: per-block zero bit-planes are the rate-targeted call's; the device file has no host writer to go to)
     if (d_file && (flags & GRK_AMD_CS_BLOCK_MSBS)) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "per-block zero bit-planes: the host writers only");
+    // (a division into tile-parts that neither route writes is refused before any work)
+    { const int64_t nt = grk_amd_layout_num_tiles(im); if (nt < 0) return nt; const int np = image_division(c, flags, base, (uint32_t)nt); if (np < 0) return np; }
     SurfaceJob job{c};
     int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);
     if (rc) return rc;
@@ -264,6 +266,7 @@ int64_t encode_surface_rate_job(grk_amd_ctx* c, const grk_amd_image_layout* im, 
                                 const QualityGoal* quality, void** d_file)
 {
     { const int rr = rate_refusal(c, rate); if (rr) return rr; }
+    if (flags & GRK_AMD_CS_TP(3)) return fail(c, GRK_AMD_ERR_UNSUPPORTED, "GRK_AMD_CS_TP: tiles divided into tile-parts are not written by the rate- and quality-targeted calls");
     flags |= GRK_AMD_CS_BLOCK_MSBS;
     SurfaceJob job{c};
     const int rc = job.open(im, base, comp_dx, comp_dy, surface, pixels, cap, pixels_on_device);

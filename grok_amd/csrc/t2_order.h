@@ -4,6 +4,7 @@
 #pragma once
 #include "geometry.h"
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #pragma GCC visibility push(hidden)
@@ -37,6 +38,18 @@ int t2_device_plan_joint_msbs(const std::vector<const TileGeom*>& cg, const std:
 // `seq` may be empty.  class_of[t]; returns the number of classes, numbered by their first tile.  (geometry.cpp)
 uint32_t joint_tile_classes(const std::vector<uint32_t>& of, uint32_t nruns, uint32_t order, const std::vector<std::vector<Pk>>& seq,
                             std::vector<uint32_t>& class_of);
+
+// ---- tiles divided into tile-parts (GRK_AMD_CS_TP; geometry.cpp) ---------------------------------------------------------------------
+// The tile-parts of a tile under the order and division of `flags`: their number (1 without a division) -- fixed by the letters'
+// extents, whether or not a part has packets -- or GRK_AMD_ERR_UNSUPPORTED with *why: a P at or before the division letter, more than
+// 255 parts.
+int tile_part_count(uint32_t flags, uint32_t num_levels, uint32_t num_comps, std::string* why = nullptr);
+// ... and the first packet of every part in `seq`, the tile's packet_order under the same flags (non-decreasing; equal neighbours: a
+// part without packets).  Returns the number of parts.
+int tile_part_starts(const std::vector<Pk>& seq, uint32_t flags, uint32_t num_levels, uint32_t num_comps, std::vector<uint32_t>& starts,
+                     std::string* why = nullptr);
+// the reason of a host writer call's refusal, for grk_amd_writer_last_error (per thread); returns `code`
+int writer_refuse(int code, const std::string& why);
 
 } // namespace grk_amd
 #pragma GCC visibility pop

@@ -15,6 +15,7 @@
 #include "geometry.h"
 #include "image.h"
 #include "t2_order.h"
+#include "t2_parts.h"
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -162,8 +163,10 @@ struct ZbpTree {
 };
 
 // tlm_at: where the Ptlm fields of the TLM marker segment start (0: none written)
+// parts_per_tile (a file of tiles divided into tile-parts; NULL: one each): TLM lists every tile-part in file order -- a tile's parts
+// together, the tiles in order -- and is the header's LAST marker segment, where the model of such files (tests/tileparts.py) puts it
 void write_main_header(Out& o, const TileGeom& g, const grk_amd_image_layout& im, uint32_t flags, uint32_t ntiles, uint64_t* tlm_at,
-                       const uint8_t* comp_dx = nullptr, const uint8_t* comp_dy = nullptr)
+                       const uint8_t* comp_dx = nullptr, const uint8_t* comp_dy = nullptr, const uint32_t* parts_per_tile = nullptr)
 {
     if (tlm_at) *tlm_at = 0;
     const grk_amd_tile_params& p = g.p;
@@ -205,7 +208,7 @@ void write_main_header(Out& o, const TileGeom& g, const grk_amd_image_layout& im
     }
     // TLM (markers/LengthMarkers.cpp:166-189, written between QCD and COM: CodeStreamCompress.cpp:734): Ztlm 0, Stlm 0x50 =
     // one-byte tile index + four-byte tile-part length per tile-part; the lengths are patched in once they are known
-    if (flags & GRK_AMD_CS_TLM) {
+    if ((flags & GRK_AMD_CS_TLM) && !parts_per_tile) {
         o.u16(0xFF55); o.u16(4 + 5 * ntiles); o.u8(0); o.u8(0x50);
         if (tlm_at) *tlm_at = o.n;
         for (uint32_t t = 0; t < ntiles; ++t) { o.u8(t); o.u32(0); }
@@ -215,6 +218,14 @@ void write_main_header(Out& o, const TileGeom& g, const grk_amd_image_layout& im
     const uint32_t cl = (uint32_t)std::strlen(kCom);
     o.u16(0xFF64); o.u16(4 + cl); o.u16(1);
     o.bytes(reinterpret_cast<const uint8_t*>(kCom), cl);
+    if ((flags & GRK_AMD_CS_TLM) && parts_per_tile) {
+        uint32_t entries = 0;
+        for (uint32_t t = 0; t < ntiles; ++t) entries += parts_per_tile[t];
+        o.u16(0xFF55); o.u16(4 + 5 * entries); o.u8(0); o.u8(0x50);
+        if (tlm_at) *tlm_at = o.n;
+        for (uint32_t t = 0; t < ntiles; ++t)
+            for (uint32_t k = 0; k < parts_per_tile[t]; ++k) { o.u8(t); o.u32(0); }
+    }
 }
 
 // sop: the packet's number in the tile (SOP marker segment in front, T2Compress.cpp:149-164) or < 0; eph: EPH after the header
@@ -337,23 +348,61 @@ void write_plt(Out& o, const std::vector<uint8_t>& body)
     } while (at < body.size());
 }
 
+// A tile divided into tile-parts (GRK_AMD_CS_TP): the first packet of every part -- the caller's (`starts`, `nparts`), or with
+// starts == NULL the division of `flags` (t2_order.h: tile_part_starts).  The writer leaves the parts' lengths in part_bytes and, for
+// starts it cannot take, the error in `error`.
+struct Division { const uint32_t* starts; uint32_t nparts; std::vector<uint32_t> part_bytes; int error = GRK_AMD_OK; };
+
 uint64_t write_tile_part(Out& o, const std::vector<const TileGeom*>& cg, const std::vector<uint64_t>& row0, const uint8_t* comp_dx,
                          const uint8_t* comp_dy, uint32_t gx0, uint32_t gy0, uint32_t t, uint32_t flags, const grk_amd_coded_block* tt,
-                         const uint8_t* coded)
+                         const uint8_t* coded, Division* dv = nullptr)
 {
     const uint64_t sot = o.n, sot_lit = o.lit ? o.lit->size() : 0;
     const uint32_t order = (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
     const bool sop = (flags & GRK_AMD_CS_SOP) != 0, eph = (flags & GRK_AMD_CS_EPH) != 0, msbs = (flags & GRK_AMD_CS_BLOCK_MSBS) != 0;
     const std::vector<Pk> seq = packet_order(cg, comp_dx, comp_dy, gx0, gy0, order);
-    auto packets = [&](Out& dst, std::vector<uint8_t>* plt) {
-        int32_t n = 0;
-        for (const Pk& q : seq) {
+    // packets [first, last) of the tile (Nsop: the packet's number in the TILE)
+    auto packets = [&](Out& dst, std::vector<uint8_t>* plt, size_t first = 0, size_t last = ~(size_t)0) {
+        last = std::min(last, seq.size());
+        for (size_t n = first; n < last; ++n) {
+            const Pk& q = seq[n];
             const uint64_t at = dst.n;
-            write_packet(dst, *cg[q.c], q.r, q.pi, tt + row0[q.c], coded, sop ? n : -1, eph, msbs);
-            ++n;
+            write_packet(dst, *cg[q.c], q.r, q.pi, tt + row0[q.c], coded, sop ? (int32_t)n : -1, eph, msbs);
             if (plt) plt_length(*plt, dst.n - at);
         }
     };
+    if (dv) {
+        // the parts one behind the other: SOT (TPsot, TNsot), the PLT of the part's own packets (none in a part without), SOD, the packets
+        std::vector<uint32_t> from_flags;
+        const uint32_t* starts = dv->starts;
+        uint32_t nparts = dv->nparts;
+        if (!starts) {
+            const int n = tile_part_starts(seq, flags, cg[0]->p.num_levels, (uint32_t)cg.size(), from_flags);
+            if (n < 0) { dv->error = n; return 0; }
+            starts = from_flags.data(); nparts = (uint32_t)n;
+        }
+        bool ok = nparts >= 1 && nparts <= kMaxTileParts && starts[0] == 0;
+        for (uint32_t k = 0; ok && k < nparts; ++k) ok = starts[k] <= seq.size() && (!k || starts[k - 1] <= starts[k]);
+        if (!ok) { dv->error = GRK_AMD_ERR_INVALID; return 0; }
+        dv->part_bytes.assign(nparts, 0);
+        for (uint32_t k = 0; k < nparts; ++k) {
+            const size_t first = starts[k], last = k + 1 < nparts ? starts[k + 1] : seq.size();
+            const uint64_t at = o.n, at_lit = o.lit ? o.lit->size() : 0;
+            o.u16(0xFF90); o.u16(10); o.u16(t); o.u32(0); o.u8(k); o.u8(nparts);
+            if ((flags & GRK_AMD_CS_PLT) && last > first) {
+                std::vector<uint8_t> body;
+                Out cnt{nullptr, 0};
+                packets(cnt, &body, first, last);
+                write_plt(o, body);
+            }
+            o.u16(0xFF93);
+            packets(o, nullptr, first, last);
+            if ((o.n - at) >> 32) o.ovf = true;                 // (Psot is 32 bits)
+            o.patch32(at + 6, (uint32_t)(o.n - at), at_lit, at);
+            dv->part_bytes[k] = (uint32_t)(o.n - at);
+        }
+        return o.n - sot;
+    }
     o.u16(0xFF90); o.u16(10); o.u16(t); o.u32(0); o.u8(0); o.u8(1);
     if (flags & GRK_AMD_CS_PLT) {
         // the packets are sized with a counting pass
@@ -369,12 +418,25 @@ uint64_t write_tile_part(Out& o, const std::vector<const TileGeom*>& cg, const s
 }
 
 // an image without sub-sampling: every component has the tile's own geometry, comp c's rows start at c * blocks_per_comp
-uint64_t write_tile_part(Out& o, const TileGeom& g, uint32_t t, uint32_t flags, const grk_amd_coded_block* tt, const uint8_t* coded)
+uint64_t write_tile_part(Out& o, const TileGeom& g, uint32_t t, uint32_t flags, const grk_amd_coded_block* tt, const uint8_t* coded,
+                         Division* dv = nullptr)
 {
     std::vector<const TileGeom*> cg(g.p.num_comps, &g);
     std::vector<uint64_t> row0(g.p.num_comps);
     for (uint32_t c = 0; c < g.p.num_comps; ++c) row0[c] = (uint64_t)c * g.blocks_per_comp;
-    return write_tile_part(o, cg, row0, nullptr, nullptr, g.p.tile_x0, g.p.tile_y0, t, flags, tt, coded);
+    return write_tile_part(o, cg, row0, nullptr, nullptr, g.p.tile_x0, g.p.tile_y0, t, flags, tt, coded, dv);
+}
+
+// What a file's writer makes of GRK_AMD_CS_TP before any byte: the parts per tile (1: the undivided file, byte for byte), or the
+// refusal -- the rule's, or more tile-parts than one TLM marker segment lists
+int file_division(uint32_t flags, const grk_amd_tile_params& base, uint32_t ntiles)
+{
+    std::string why;
+    const int n = tile_part_count(flags, base.num_levels, base.num_comps, &why);
+    if (n < 0) return writer_refuse(n, why);
+    if (n > 1 && (flags & GRK_AMD_CS_TLM) && (uint64_t)n * ntiles > kMaxTlmEntries)
+        return writer_refuse(GRK_AMD_ERR_UNSUPPORTED, std::to_string((uint64_t)n * ntiles) + " tile-parts: one TLM marker segment lists at most 13 106");
+    return n;
 }
 
 } // namespace
@@ -407,6 +469,10 @@ extern "C" int64_t grk_amd_write_codestream_layout(const grk_amd_image_layout* i
     if (rc != GRK_AMD_OK) return rc;
     const uint32_t ntiles = l.tcols * l.trows;
     if ((flags & GRK_AMD_CS_TLM) && ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;     // (one-byte Ttlm, as the reference writes it)
+    const int nparts = file_division(flags, *base, ntiles);
+    if (nparts < 0) return nparts;
+    const std::vector<uint32_t> per_tile(nparts > 1 ? ntiles : 0, (uint32_t)nparts);
+    Division dv{nullptr, 0};
     TileGeom g;
     grk_amd_tile_params p;
     Out o{out, cap};
@@ -415,10 +481,12 @@ extern "C" int64_t grk_amd_write_codestream_layout(const grk_amd_image_layout* i
         tile_of(l, *base, t, p);
         rc = build_tile_geom(p, g);
         if (rc != GRK_AMD_OK) return rc;
-        if (t == 0) write_main_header(o, g, l.im, flags, ntiles, &tlm_at);
-        const uint64_t len = write_tile_part(o, g, t, flags, table + row, coded);
+        if (t == 0) write_main_header(o, g, l.im, flags, ntiles, &tlm_at, nullptr, nullptr, nparts > 1 ? per_tile.data() : nullptr);
+        const uint64_t len = write_tile_part(o, g, t, flags, table + row, coded, nparts > 1 ? &dv : nullptr);
+        if (dv.error) return dv.error;
         row += (uint64_t)g.blocks_per_comp * p.num_comps;
-        if (tlm_at) o.patch32(tlm_at + 5ull * t + 1, (uint32_t)len);
+        if (tlm_at && nparts > 1) { for (int k = 0; k < nparts; ++k) o.patch32(tlm_at + 5ull * ((uint64_t)t * nparts + k) + 1, dv.part_bytes[k]); }
+        else if (tlm_at) o.patch32(tlm_at + 5ull * t + 1, (uint32_t)len);
     }
     o.u16(0xFFD9);
     if (o.ovf) return GRK_AMD_ERR_OVERFLOW;
@@ -471,6 +539,10 @@ extern "C" int64_t grk_amd_write_codestream_subsampled(const grk_amd_image_layou
     if (based.mct && nc >= 3 && !(comp_dx[0] == comp_dx[1] && comp_dx[1] == comp_dx[2] && comp_dy[0] == comp_dy[1] && comp_dy[1] == comp_dy[2]))
         based.mct = 0;
     base = &based;
+    const int nparts = file_division(flags, *base, ntiles);
+    if (nparts < 0) return nparts;
+    const std::vector<uint32_t> per_tile(nparts > 1 ? ntiles : 0, (uint32_t)nparts);
+    Division dv{nullptr, 0};
     std::vector<TileGeom> geoms(nc);
     std::vector<const TileGeom*> cg(nc);
     std::vector<uint64_t> row0(nc);
@@ -485,10 +557,12 @@ extern "C" int64_t grk_amd_write_codestream_subsampled(const grk_amd_image_layou
             if ((rc = build_tile_geom(p, geoms[c])) != GRK_AMD_OK) return rc;
             cg[c] = &geoms[c]; row0[c] = rows; rows += geoms[c].blocks_per_comp;
         }
-        if (t == 0) write_main_header(o, geoms[0], l.im, flags, ntiles, &tlm_at, comp_dx, comp_dy);
-        const uint64_t len = write_tile_part(o, cg, row0, comp_dx, comp_dy, pt.tile_x0, pt.tile_y0, t, flags, table + row, coded);
+        if (t == 0) write_main_header(o, geoms[0], l.im, flags, ntiles, &tlm_at, comp_dx, comp_dy, nparts > 1 ? per_tile.data() : nullptr);
+        const uint64_t len = write_tile_part(o, cg, row0, comp_dx, comp_dy, pt.tile_x0, pt.tile_y0, t, flags, table + row, coded, nparts > 1 ? &dv : nullptr);
+        if (dv.error) return dv.error;
         row += rows;
-        if (tlm_at) o.patch32(tlm_at + 5ull * t + 1, (uint32_t)len);
+        if (tlm_at && nparts > 1) { for (int k = 0; k < nparts; ++k) o.patch32(tlm_at + 5ull * ((uint64_t)t * nparts + k) + 1, dv.part_bytes[k]); }
+        else if (tlm_at) o.patch32(tlm_at + 5ull * t + 1, (uint32_t)len);
     }
     o.u16(0xFFD9);
     if (o.ovf) return GRK_AMD_ERR_OVERFLOW;
@@ -591,11 +665,70 @@ extern "C" int64_t grk_amd_write_tile_part(const grk_amd_tile_params* p, uint32_
     return (int64_t)o.n;
 }
 
+extern "C" int64_t grk_amd_write_tile_parts(const grk_amd_tile_params* p, uint32_t tile_index, uint32_t flags, const grk_amd_coded_block* tile_table,
+                                            const uint8_t* coded, const uint32_t* starts, uint32_t nparts, uint8_t* out, uint64_t cap, uint32_t* part_bytes)
+{
+    if (!p || !tile_table || (out && !coded) || (!starts != !nparts)) return GRK_AMD_ERR_INVALID;
+    if (starts && (nparts > kMaxTileParts || starts[0] != 0)) return writer_refuse(GRK_AMD_ERR_INVALID, "grk_amd_write_tile_parts: 1 .. 255 tile-parts, the first from packet 0");
+    if (!starts) { const int n = file_division(flags & ~(uint32_t)GRK_AMD_CS_TLM, *p, 1); if (n < 0) return n; }
+    TileGeom g;
+    int rc = build_tile_geom(*p, g);
+    if (rc != GRK_AMD_OK) return rc;
+    Out o{out, cap};
+    Division dv{starts, nparts};
+    write_tile_part(o, g, tile_index, flags, tile_table, coded, &dv);
+    if (dv.error) return writer_refuse(dv.error, "grk_amd_write_tile_parts: starts that decrease or lie beyond the tile's packets");
+    if (o.ovf) return GRK_AMD_ERR_OVERFLOW;
+    if (part_bytes) std::copy(dv.part_bytes.begin(), dv.part_bytes.end(), part_bytes);
+    return (int64_t)o.n;
+}
+
+extern "C" int64_t grk_amd_write_main_header_parts(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
+                                                   const uint32_t* parts_per_tile, const uint32_t* part_bytes, uint8_t* out, uint64_t cap)
+{
+    return grk_amd::main_header_parts(im, base, nullptr, nullptr, flags, parts_per_tile, part_bytes, out, cap);
+}
+
+// the main header of a file of divided tiles, plain (comp_dx == NULL) or sub-sampled (image.h)
+int64_t grk_amd::main_header_parts(const grk_amd_image_layout* im, const grk_amd_tile_params* base, const uint8_t* comp_dx, const uint8_t* comp_dy,
+                                   uint32_t flags, const uint32_t* parts_per_tile, const uint32_t* part_bytes, uint8_t* out, uint64_t cap)
+{
+    if (!base || !parts_per_tile || (!comp_dx != !comp_dy)) return GRK_AMD_ERR_INVALID;
+    Layout l;
+    int rc = check_layout(im, l);
+    if (rc != GRK_AMD_OK) return rc;
+    const uint32_t ntiles = l.tcols * l.trows, nc = base->num_comps;
+    uint64_t entries = 0;
+    for (uint32_t t = 0; t < ntiles; ++t) {
+        if (!parts_per_tile[t] || parts_per_tile[t] > kMaxTileParts) return writer_refuse(GRK_AMD_ERR_INVALID, "1 .. 255 tile-parts per tile");
+        entries += parts_per_tile[t];
+    }
+    if (flags & GRK_AMD_CS_TLM) {
+        if (ntiles > 255) return GRK_AMD_ERR_UNSUPPORTED;
+        if (entries > kMaxTlmEntries) return writer_refuse(GRK_AMD_ERR_UNSUPPORTED, std::to_string(entries) + " tile-parts: one TLM marker segment lists at most 13 106");
+        if (!part_bytes) return GRK_AMD_ERR_INVALID;
+    }
+    grk_amd_tile_params based = *base, p;
+    if (comp_dx && based.mct && nc >= 3 && !(comp_dx[0] == comp_dx[1] && comp_dx[1] == comp_dx[2] && comp_dy[0] == comp_dy[1] && comp_dy[1] == comp_dy[2]))
+        based.mct = 0;
+    TileGeom g;
+    if (comp_dx) { if ((rc = tile_comp_of(l, based, comp_dx[0], comp_dy[0], 0, p)) != GRK_AMD_OK) return rc; }
+    else tile_of(l, based, 0, p);
+    if ((rc = build_tile_geom(p, g)) != GRK_AMD_OK) return rc;
+    Out o{out, cap};
+    uint64_t tlm_at = 0;
+    write_main_header(o, g, l.im, flags, ntiles, &tlm_at, comp_dx, comp_dy, parts_per_tile);
+    for (uint64_t e = 0; tlm_at && e < entries; ++e) o.patch32(tlm_at + 5 * e + 1, part_bytes[e]);
+    if (o.ovf) return GRK_AMD_ERR_OVERFLOW;
+    return (int64_t)o.n;
+}
+
 namespace grk_amd {
 int64_t plan_tile_part(const grk_amd_tile_params& p, uint32_t tile_index, uint32_t flags, const grk_amd_coded_block* tile_table,
                        std::vector<uint8_t>& lit, std::vector<grk_amd_tp_segment>& segs)
 {
     if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (per-block zero bit-planes: the host writers only)
+    if (flags & GRK_AMD_CS_TP(3)) return GRK_AMD_ERR_UNSUPPORTED;           // (one tile-part per tile)
     TileGeom g;
     const int rc = build_tile_geom(p, g);
     if (rc != GRK_AMD_OK) return rc;
@@ -621,6 +754,7 @@ static int device_plan(const std::vector<const TileGeom*>& cg, const std::vector
     for (size_t c = 0; c < cg.size(); ++c) rows = std::max(rows, row0[c] + cg[c]->blocks_per_comp);
     if (rows > 0xFFFFFFFFull) return GRK_AMD_ERR_UNSUPPORTED;               // (T2Packet::row0 and the kernels' rows per tile are 32 bits)
     const std::vector<Pk> seq = packet_order(cg, comp_dx, comp_dy, gx0, gy0, (flags >> GRK_AMD_CS_PROG_SHIFT) & 7u);
+    { const int np = tile_part_starts(seq, flags, cg[0]->p.num_levels, (uint32_t)cg.size(), out.part_starts); if (np < 0) return np; }
     out.packets.clear();
     out.packet_of_block.assign((size_t)rows, 0xFFFFFFFFu);
     uint64_t u = 0, h = 0, v = 0;
@@ -705,6 +839,7 @@ extern "C" int64_t grk_amd_plan_tile_part(const grk_amd_tile_params* p, uint32_t
 {
     if (!p || !tile_table || !literal_len || !num_segments) return GRK_AMD_ERR_INVALID;
     if (flags & GRK_AMD_CS_BLOCK_MSBS) return GRK_AMD_ERR_UNSUPPORTED;      // (per-block zero bit-planes: the host writers only)
+    if (flags & GRK_AMD_CS_TP(3)) return writer_refuse(GRK_AMD_ERR_UNSUPPORTED, "grk_amd_plan_tile_part plans one tile-part per tile: GRK_AMD_CS_TP is not taken");
     std::vector<uint8_t> lit;
     std::vector<grk_amd_tp_segment> segs;
     const int64_t total = grk_amd::plan_tile_part(*p, tile_index, flags, tile_table, lit, segs);

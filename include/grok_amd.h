@@ -281,6 +281,14 @@ int grk_amd_stage_ht_encode_drops(grk_amd_ctx* ctx, const grk_amd_tile_params* p
 int64_t grk_amd_stage_assemble(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
                                uint32_t flags, const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes,
                                uint32_t* part_bytes);
+/* grk_amd_stage_assemble with every tile divided into tile-parts (GRK_AMD_CS_TP, below): at the caller's packets -- starts[nparts] as
+ * grk_amd_write_tile_parts takes them, the same for every tile -- or with starts == NULL / nparts == 0 under the division of `flags`.
+ * All checks run on the host before any launch (GRK_AMD_ERR_INVALID for starts that decrease, do not begin at 0, exceed the tile's
+ * packets or number more than 255).  The tiles' parts lie one behind the other from offset 0; part_bytes[num_tiles][parts] (optional)
+ * are the parts' lengths, grk_amd_assembled_parts() their number per tile.  The bytes are grk_amd_write_tile_parts'. */
+int64_t grk_amd_stage_assemble_parts(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
+                                     uint32_t flags, const grk_amd_coded_block* table, const uint8_t* coded, uint64_t coded_bytes,
+                                     const uint32_t* starts, uint32_t nparts, uint32_t* part_bytes);
 /* the longest code-block the device writer takes, in bytes; a longer one makes grk_amd_assemble_device and the whole-image encoders'
  * device route return GRK_AMD_ERR_UNSUPPORTED (the image encoders then take the host writer) */
 uint32_t grk_amd_t2_max_block_bytes(void);
@@ -545,6 +553,11 @@ int64_t grk_amd_assemble_rate_device(grk_amd_ctx* ctx, const grk_amd_tile_params
 int grk_amd_assemble_device_async(grk_amd_ctx* ctx, const grk_amd_tile_params* p, uint32_t num_tiles, const uint32_t* tile_index,
                                   uint32_t flags, void* hip_stream);
 void* grk_amd_assembled_table_ptr(grk_amd_ctx* ctx, int which);
+/* Under GRK_AMD_CS_TP (which grk_amd_assemble_device, _rate_device and _async honour: the bytes of grk_amd_write_tile_parts) a tile's
+ * parts lie one behind the other; tables 0 and 1 and part_bytes[i] then describe the tile's SPAN -- all its parts --, and
+ *   table 3: uint32[tiles][grk_amd_assembled_parts(ctx)] the tile-parts' own lengths (what TLM lists)
+ * grk_amd_assembled_parts: the tile-parts per tile of the latest assemble call (1: undivided, table 3 is then table 1). */
+uint32_t grk_amd_assembled_parts(grk_amd_ctx* ctx);
 /* bytes [offset, offset + nbytes) of the assembled tile-parts to host memory (pinned: one DMA; pageable: through pinned chunks on
  * several copy threads); complete on return */
 int grk_amd_fetch_assembled(grk_amd_ctx* ctx, uint64_t offset, uint64_t nbytes, uint8_t* dst);
@@ -813,6 +826,49 @@ int64_t grk_amd_write_main_header(const grk_amd_tile_params* p, uint32_t img_w, 
                                   const uint32_t* tile_part_bytes, uint8_t* out, uint64_t cap);
 int64_t grk_amd_write_tile_part(const grk_amd_tile_params* p, uint32_t tile_index, uint32_t flags,
                                 const grk_amd_coded_block* tile_table, const uint8_t* coded, uint8_t* out, uint64_t cap);
+/* ---- tiles divided into tile-parts (grk_compress -u R|L|C; T.800 A.4.2) ----------------------------------------------------
+ * Bits 12-13 of `flags`: the division letter.  0: one tile-part per tile, every byte as before.  The rule is the reference's
+ * (CodeStreamCompress::get_num_tp, pi_enable_tile_part_generation) for this encoder's one layer: with `pos` the place of the letter in
+ * the progression order's name (LRCP, RLCP, RPCL, PCRL, CPRL), a packet's key is its coordinates for the letters 0 .. pos, and a new
+ * tile-part starts wherever the key changes.  A tile has as many parts as there are keys -- the product of the letters' extents
+ * (R: num_levels + 1, C: num_comps, L: 1) --, whether or not a key has packets: a part without packets is 14 bytes.
+ *              R        L                             C
+ *   LRCP       R parts  1 (the undivided file)        R x C
+ *   RLCP       R        R                             R x C
+ *   RPCL       R        refused                       refused
+ *   PCRL       refused  refused                       refused
+ *   CPRL       refused  refused                       C
+ * Refused: GRK_AMD_ERR_UNSUPPORTED -- a P at or before the division letter; more than 255 parts per tile; with GRK_AMD_CS_TLM more than
+ * 13 106 parts in the file (one TLM marker segment).  The reason: grk_amd_writer_last_error for the host-only calls,
+ * grk_amd_last_error for a context's.
+ * A divided tile: its parts one behind the other, the tiles in their order; every part SOT (TPsot = k, TNsot = the tile's parts,
+ * Psot = the part's length), with GRK_AMD_CS_PLT the PLT marker segments of its OWN packets (Zplt from 0; none in a part without
+ * packets), SOD, its packets unchanged -- SOP's Nsop keeps counting through the tile.  (The reference writes one PLT for the whole tile
+ * into the first part; this writer does not copy that.)  With GRK_AMD_CS_TLM the single TLM marker segment lists every tile-part in
+ * file order and is the LAST segment of a divided file's main header.
+ * Taken by grk_amd_write_codestream_ex / _layout / _subsampled, grk_amd_write_tile_parts, grk_amd_assemble_device(_async),
+ * grk_amd_assemble_rate_device and the plain whole-image encoders; GRK_AMD_ERR_UNSUPPORTED from the rate- and quality-targeted calls,
+ * grk_amd_plan_tile_part, grk_amd_node_* and the plugin. */
+#define GRK_AMD_CS_TP_SHIFT 12
+#define GRK_AMD_CS_TP(d)    ((uint32_t)(d) << GRK_AMD_CS_TP_SHIFT)
+#define GRK_AMD_TP_R 1
+#define GRK_AMD_TP_L 2
+#define GRK_AMD_TP_C 3
+/* the first packet number of every tile-part of a tile under flags' order and division (non-decreasing; equal neighbours: a
+ * tile-part without packets); returns the number of tile-parts, *num_packets the tile's packets; comp_dx / comp_dy NULL: 1.
+ * `tile` is the tile on the reference grid (grk_amd_layout_tile).  starts == NULL: the count alone. */
+int64_t grk_amd_tile_part_starts(const grk_amd_tile_params* tile, const uint8_t* comp_dx, const uint8_t* comp_dy, uint32_t flags,
+                                 uint32_t* starts, uint32_t cap, uint32_t* num_packets);
+/* starts / nparts: the division as grk_amd_tile_part_starts gives it, or NULL / 0: taken from flags.  Explicit starts may be any
+ * non-decreasing packet numbers <= the tile's packets, starts[0] == 0, 1 <= nparts <= 255 (GRK_AMD_ERR_INVALID otherwise).
+ * part_bytes[nparts] (optional): the parts' lengths.  out == NULL: sizes only. */
+int64_t grk_amd_write_tile_parts(const grk_amd_tile_params* p, uint32_t tile_index, uint32_t flags, const grk_amd_coded_block* tile_table,
+                                 const uint8_t* coded, const uint32_t* starts, uint32_t nparts, uint8_t* out, uint64_t cap, uint32_t* part_bytes);
+/* main header whose TLM lists tile-parts: parts_per_tile[tiles], part_bytes in file order */
+int64_t grk_amd_write_main_header_parts(const grk_amd_image_layout* im, const grk_amd_tile_params* base, uint32_t flags,
+                                        const uint32_t* parts_per_tile, const uint32_t* part_bytes, uint8_t* out, uint64_t cap);
+/* why the calling thread's latest host writer call (the three above, grk_amd_write_codestream_*) refused a division */
+const char* grk_amd_writer_last_error(void);
 /* Random access (the reader's side of markers/LengthMarkers.cpp:91-164): offset, length and tile index of every tile-part
  * of a codestream -- from its TLM marker segments when present (*used_tlm = 1: no byte of a tile-part is read), else by
  * hopping over Psot.  Returns the number of tile-parts (entries beyond `cap` are counted, not stored) or < 0. */

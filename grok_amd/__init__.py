@@ -8,7 +8,7 @@ itself and raises loudly when the native library is missing.
 from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Context, lib, lib_path, NativeLibraryMissing,
                    tile_layout, reduced_tile_rect, write_codestream, write_tile_part, write_main_header, locate_tile_parts,
                    CS_TLM, CS_PLT, CS_SOP, CS_EPH, CS_PROG, ImageLayout, layout_tiles, same_tile_geometry, same_tile_packets, write_codestream_layout, Node, NODE_GATHER,
-                   StreamInfo, ReaderError, read_header, read_packets, read_packets_parts, stream_comp_sizes,
+                   StreamInfo, ReaderError, read_header, read_packets, read_packets_parts, read_packets_refine, stream_comp_sizes,
                    ImageView, image_view_size, plan_image_view,
                    Surface, SurfaceComp, SurfaceError, SURFACE_FORMATS, SURFACE_FORMATS_MSB, surface_bytes, surface_plan,
                    PACKED_FORMATS, packed_bytes,
@@ -19,7 +19,7 @@ from .capi import (PixelLayout, pixel_bytes, TileParams, Block, CodedBlock, Cont
 __all__ = ["PixelLayout", "pixel_bytes", "TileParams", "Block", "CodedBlock", "Context", "lib", "lib_path", "NativeLibraryMissing",
            "tile_layout", "reduced_tile_rect", "write_codestream", "write_tile_part", "write_main_header", "locate_tile_parts", "CS_TLM", "CS_PLT", "CS_SOP", "CS_EPH", "CS_PROG",
            "ImageLayout", "layout_tiles", "same_tile_geometry", "same_tile_packets", "write_codestream_layout", "Node", "NODE_GATHER",
-           "StreamInfo", "ReaderError", "read_header", "read_packets", "read_packets_parts", "stream_comp_sizes",
+           "StreamInfo", "ReaderError", "read_header", "read_packets", "read_packets_parts", "read_packets_refine", "stream_comp_sizes",
            "ImageView", "image_view_size", "plan_image_view",
            "Surface", "SurfaceComp", "SurfaceError", "SURFACE_FORMATS", "SURFACE_FORMATS_MSB", "surface_bytes", "surface_plan",
            "PACKED_FORMATS", "packed_bytes",

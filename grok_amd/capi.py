@@ -466,6 +466,9 @@ def lib():
                                                C.POINTER(u64), C.POINTER(u64)]
             L.grk_amd_read_packets_parts.restype = C.c_int64
             L.grk_amd_read_packets_parts.argtypes = L.grk_amd_read_packets.argtypes
+            if hasattr(L, "grk_amd_read_packets_refine"):          # (GRK_AMD_LIB may name a build from before it)
+                L.grk_amd_read_packets_refine.restype = C.c_int64
+                L.grk_amd_read_packets_refine.argtypes = L.grk_amd_read_packets.argtypes
             L.grk_amd_reader_last_error.restype = C.c_char_p
             L.grk_amd_decode_image.argtypes = [vp, vp, u64, vp, u64, i32]
             L.grk_amd_decode_image_launches.restype = u64
@@ -855,6 +858,12 @@ def read_packets_parts(cs, info=None, threads=1):
     """grk_amd_read_packets_parts: read_packets for a codestream whose tiles may be divided into tile-parts (1..255 per tile); the
     same dict, every offset and every move's src a position in `cs`."""
     return read_packets(cs, info, threads, "grk_amd_read_packets_parts")
+
+
+def read_packets_refine(cs, info=None, threads=1):
+    """grk_amd_read_packets_refine: read_packets_parts for an HTJ2K codestream whose code-blocks carry SigProp / MagRef passes; the
+    same dict, an HT block's segments {Lcup, 1} alone or {Lcup, 1}, {Lref, 1 | 2}."""
+    return read_packets(cs, info, threads, "grk_amd_read_packets_refine")
 
 
 class Context:
@@ -1674,6 +1683,9 @@ class Context:
             L.grk_amd_decode_image_device_ex.argtypes = [vp, vp, u64, vp, u64, C.c_int]
             L.grk_amd_read_packets_device_parts.restype = C.c_int64
             L.grk_amd_read_packets_device_parts.argtypes = L.grk_amd_read_packets_device_ex.argtypes
+            if hasattr(L, "grk_amd_read_packets_device_refine"):
+                L.grk_amd_read_packets_device_refine.restype = C.c_int64
+                L.grk_amd_read_packets_device_refine.argtypes = L.grk_amd_read_packets_device_ex.argtypes
             L.grk_amd_read_device_counters.restype = u64
             L.grk_amd_read_device_counters.argtypes = [vp, C.c_int]
             L._read_device_bound = True
@@ -1713,6 +1725,11 @@ class Context:
         """grk_amd_read_packets_device_parts: read_packets_device_ex for a codestream whose tiles may be divided into tile-parts -> the
         dict read_packets_parts gives for the same bytes (the moves in the order of their dst)."""
         return self.read_packets_device_ex(d_cs, nbytes, info, "grk_amd_read_packets_device_parts")
+
+    def read_packets_device_refine(self, d_cs, nbytes, info=None):
+        """grk_amd_read_packets_device_refine: read_packets_device_parts for an HTJ2K codestream whose code-blocks carry refinement
+        passes -> the dict read_packets_refine gives for the same bytes (the moves in the order of their dst)."""
+        return self.read_packets_device_ex(d_cs, nbytes, info, "grk_amd_read_packets_device_refine")
 
     def read_device_parts_launches(self):
         """launches of KL-P / KH-P by this context's calls so far (grk_amd_read_device_counters, index 6)"""

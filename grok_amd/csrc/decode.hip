@@ -144,8 +144,7 @@ int decode_impl(grk_amd_ctx* c, const grk_amd_tile_params* p, uint32_t ntiles, c
     // Every coefficient and every synthesised LL sample of a stream that an 8-bit image produced fits (the encoder's
     // planes16_ok bound); a stream whose values do not is reported by decode_status (GRK_AMD_ERR_RANGE), and a synchronous
     // call decodes it again with int32 planes right here -- never other pixels.
-    const bool h16 = c->dec_planes16 && !force32 && fuse_out && !p->reserved[0] && !g.p.irreversible && g.p.prec <= 8 &&
-                     c->dec_seg_first.empty();
+    const bool h16 = decode_takes_planes16(c->dec_planes16, force32, fuse_out, g.p, !c->dec_seg_first.empty());
     {
         ScopedTimer t(c, 3);
         rc = p->reserved[0] ? run_t1_decode(c, ntiles, up, d_coded, coded_bytes, c->p1.p)

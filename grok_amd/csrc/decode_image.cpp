@@ -159,7 +159,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     rc = plan_image_view(info, view, plan, &pwhy);
     if (rc) return fail(c, rc, pwhy);
     // (a host destination's copy on the device is the context's own allocation: aligned far beyond 4 bytes)
-    const ImageDestIn in{c->dec_layout, c->dec_upsample, pixels_on_device != 0, cap, pixels_on_device ? (uint32_t)((uintptr_t)pixels & 3u) : 0u,
+    ImageDestIn in{c->dec_layout, c->dec_upsample, pixels_on_device != 0, cap, pixels_on_device ? (uint32_t)((uintptr_t)pixels & 3u) : 0u,
                          surf && surface_direct_allowed()};
     ImageDest d;
     rc = plan_image_dest(info, plan, in, surf, d, &pwhy);
@@ -181,8 +181,10 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     void* coded_buf = res ? const_cast<void*>(res->d_cs) : c->img_coded.p;
     StreamTable tab;
     int rrc = GRK_AMD_OK;
+    bool refined = false;                  // the table is the refine reader's
     if (res) {
         tab = std::move(*res->tab);
+        refined = !tab.segments.empty();   // (read_device.hip asks for an HT file's segments only behind that reader)
         if (tab.appendix_bytes) {
             if (!res->d_moves || !tab.moves.empty()) return fail(c, GRK_AMD_ERR_INVALID, "an appendix without its moves in device memory");
             HIP_TRY(c, c->img_coded.ensure(coded.coded_cap + 64), "alloc the coded buffer");
@@ -194,7 +196,8 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         const uint32_t threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
         std::thread reader([&]() {
             if (d.all) rrc = locate_stream_parts(cs, len, info, parts, why);
-            if (!rrc) rrc = read_stream_packets_of(cs, len, info, parts, d.all ? nullptr : &plan.tiles, plan.reduce, threads, tab, why);
+            // (an HT file whose blocks have refinement passes is read a second time in here, by the reader that takes them)
+            if (!rrc) rrc = read_decode_packets(cs, len, info, parts, d.all ? nullptr : &plan.tiles, plan.reduce, threads, tab, why, &refined);
         });
         for (size_t i = 0; i < coded.copies.size() && !rc; ++i)
             rc = copy_h2d(c, (uint8_t*)c->img_coded.p + coded.copies[i].to, cs + coded.copies[i].from, coded.copies[i].n);
@@ -202,6 +205,10 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
     }
     if (rc) return rc;
     if (rrc) return fail(c, rrc, why.c_str());
+    // only the packets show that an HT file has refinement segments: the destination's plan again, now with segment lists (int32
+    // planes) and no region decoder
+    rc = replan_for_refinement(info, plan, in, surf, tab, refined, d, &pwhy);
+    if (rc) return fail(c, rc, pwhy);
     if (!res) { c->img_counters[0] += plan.tiles.size(); c->img_counters[1] += coded.up_len; }
     std::vector<uint64_t> unit_row;
     rc = rebase_table(tab, len, d.all, plan.tiles, parts, coded, d, unit_row, &pwhy);
@@ -265,7 +272,7 @@ static int decode_view(grk_amd_ctx* c, const uint8_t* cs, uint64_t len, const gr
         // The int16-plane rule (include/grok_amd.h, grk_amd_set_decode_planes16).  A decode into a device buffer does not repeat
         // itself: with host pixels this call joins behind a group that may use those planes, reads its status and repeats it
         // with int32 planes; with device pixels the status goes to grk_amd_decode_status like any other
-        if (host_rules && c->dec_planes16 && d.ht && !p.irreversible && p.prec <= 8) {
+        if (host_rules && c->dec_planes16 && group_checks_planes16(d, p)) {
             drc = grk_amd_decode_status(c);
             if (drc == GRK_AMD_ERR_RANGE) {
                 c->dec_planes16 = false;

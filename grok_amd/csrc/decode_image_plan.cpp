@@ -161,9 +161,11 @@ int plan_image_dest(const grk_amd_stream_info& info, const ViewPlan& plan, const
                 }
     }
     // Part-1 blocks of several codeword segments need the segment list; one segment per block is what the table row says
-    d.want_segs = !d.ht && (info.base.reserved[1] & 0x05);
-    // the region decoder's own conditions (grk_amd_decode_region): a DWT level left, samples of at most 16 bits
-    const bool region_ok = info.base.num_levels > red && bps <= 2;
+    // -- and so do HT blocks with refinement passes, which only the packets show (in.ht_refine)
+    d.want_segs = d.ht ? in.ht_refine : (info.base.reserved[1] & 0x05) != 0;
+    // the region decoder's own conditions (grk_amd_decode_region): a DWT level left, samples of at most 16 bits -- and no HT
+    // refinement segments, which do not add up to the rows it empties
+    const bool region_ok = info.base.num_levels > red && bps <= 2 && !(d.ht && in.ht_refine);
     if (!surf && nt == 1 && nr == 1 && !up && (plan.units[0].whole || region_ok)) {
         // one tile: decoded straight into the destination -- a window of it by the region decoder, whose cost follows the window
         const ViewUnit& u = plan.units[0];
@@ -270,6 +272,34 @@ int rebase_table(StreamTable& tab, uint64_t len, bool all, const std::vector<uin
     if (unit_row[nu] != tab.rows.size()) return refuse(why, GRK_AMD_ERR_INVALID, "the reader's table does not fit the tiles");
     return GRK_AMD_OK;
 }
+
+int read_decode_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, const std::vector<StreamPart>& parts, const std::vector<uint32_t>* tiles,
+                        uint32_t drop_res, uint32_t threads, StreamTable& tab, std::string& err, bool* refined)
+{
+    *refined = false;
+    int rc = read_stream_packets_of(cs, len, info, parts, tiles, drop_res, threads, tab, err);
+    if (rc && tab.met_ht_second_pass) {
+        *refined = true;
+        rc = read_stream_packets_of(cs, len, info, parts, tiles, drop_res, threads, tab, err, true);
+    }
+    return rc;
+}
+
+int replan_for_refinement(const grk_amd_stream_info& info, const ViewPlan& plan, ImageDestIn& in, const grk_amd_surface* surf, const StreamTable& tab, bool refined,
+                          ImageDest& d, const char** why)
+{
+    if (!refined || !d.ht || !table_has_second_segment(tab)) return GRK_AMD_OK;
+    in.ht_refine = true;
+    return plan_image_dest(info, plan, in, surf, d, why);
+}
+
+bool table_has_second_segment(const StreamTable& tab)
+{
+    for (size_t i = 0; i + 1 < tab.first_segment.size(); ++i) if (tab.first_segment[i + 1] - tab.first_segment[i] > 1) return true;
+    return false;
+}
+
+bool group_checks_planes16(const ImageDest& d, const grk_amd_tile_params& p) { return d.ht && !d.want_segs && !p.irreversible && p.prec <= 8; }
 
 void group_tables(const StreamTable& tab, const std::vector<uint64_t>& unit_row, const uint32_t* units, size_t n, bool want_segs,
                   std::vector<grk_amd_coded_block>& rows, std::vector<uint32_t>& first, std::vector<grk_amd_segment>& segs)

@@ -24,6 +24,7 @@ struct ImageDestIn {
     uint64_t cap = 0;
     uint32_t dst_align = 0;             // the device destination's address modulo 4 (host pixels: the context's own copy, 0)
     bool surface_direct = true;         // a surface's runs may be decoded in place (GRK_AMD_SURFACE_DIRECT)
+    bool ht_refine = false;             // the packets are read and HT blocks among them have refinement passes (table_has_second_segment)
 };
 
 enum class ImageRoute {
@@ -88,7 +89,11 @@ struct ImageDest {
     std::vector<FillRect> fills;            // (up) in launch order
 };
 
-// surf != nullptr: the destination is the caller's surface
+// surf != nullptr: the destination is the caller's surface.
+// An HT file does not announce refinement passes in its header: a decode plans, reads the packets, and -- table_has_second_segment --
+// plans again with in.ht_refine.  The batches then carry their segment lists (want_segs), which keeps them off the int16 planes
+// (group_checks_planes16: K5c refines int32 words), and a window of a one-tile image goes the Staged route: the region decoder
+// empties the rows of the blocks outside the window, whose segment lists would no longer add up to them.
 int plan_image_dest(const grk_amd_stream_info& info, const ViewPlan& plan, const ImageDestIn& in, const grk_amd_surface* surf, ImageDest& out,
                     const char** why);
 
@@ -113,6 +118,21 @@ int check_moves(const grk_amd_tp_segment* moves, uint64_t n, uint64_t src_bytes,
 // unit_row ([units + 1]: a unit's rows in the reader's table) from the units' geometry, checked against the reader's row_at
 int rebase_table(StreamTable& tab, uint64_t len, bool all, const std::vector<uint32_t>& tiles, const std::vector<StreamPart>& parts, CodedPlan& coded,
                  const ImageDest& dest, std::vector<uint64_t>& unit_row, const char** why);
+
+// The packets of the tiles a whole-image decode touches (tiles == nullptr: all), as every such decode reads them: through the reader
+// that every file goes through and -- only where that one met an HT block's second pass (StreamTable::met_ht_second_pass) -- again
+// through the one that takes refinement passes; *refined: the table is the second reading's.  Every other refusal stands as it is
+int read_decode_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, const std::vector<StreamPart>& parts, const std::vector<uint32_t>* tiles,
+                        uint32_t drop_res, uint32_t threads, StreamTable& tab, std::string& err, bool* refined);
+// a row of the reader's table has a second codeword segment (an HT block's: its refinement passes)
+bool table_has_second_segment(const StreamTable& tab);
+// behind the packets: a refined reading (read_decode_packets, or the device reader's) whose table has a second segment plans the
+// destination again with in.ht_refine -- which tiles are touched does not change, a CodedPlan made before stands
+int replan_for_refinement(const grk_amd_stream_info& info, const ViewPlan& plan, ImageDestIn& in, const grk_amd_surface* surf, const StreamTable& tab, bool refined,
+                          ImageDest& d, const char** why);
+// a staged batch of parameters p may have run on the int16 planes: with host pixels its status is read, and it is decoded again on
+// int32 planes when a coefficient left them (include/grok_amd.h, grk_amd_set_decode_planes16)
+bool group_checks_planes16(const ImageDest& d, const grk_amd_tile_params& p);
 
 // the rows of `units` one unit after the other and -- want_segs -- their segment lists, rebased: first has rows + 1 entries
 void group_tables(const StreamTable& tab, const std::vector<uint64_t>& unit_row, const uint32_t* units, size_t n, bool want_segs,

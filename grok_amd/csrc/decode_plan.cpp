@@ -136,6 +136,11 @@ int plan_ht_refinement(const grk_amd_coded_block* table, uint64_t nblocks, const
     return GRK_AMD_OK;
 }
 
+bool decode_takes_planes16(bool setting, bool force32, bool fuse_out, const grk_amd_tile_params& p, bool have_segments)
+{
+    return setting && !force32 && fuse_out && !p.reserved[0] && !p.irreversible && p.prec <= 8 && !have_segments;
+}
+
 // Which decoder takes which block.  A block is one dependent chain of MQ decisions (about ten per coded byte); 64 chains
 // to a wave (K8L) make the throughput, but a chain alone in a wave (K8) advances ~2.5 times faster, and a frame's time
 // is its longest chain's: the blocks longer than a quarter of the longest one -- a handful: the LL band -- and

@@ -51,6 +51,11 @@ int select_segments(bool reduced, const std::vector<uint32_t>& first, const std:
 int plan_ht_refinement(const grk_amd_coded_block* table, uint64_t nblocks, const SegList& sl, grk_amd_segment* ref,
                        uint32_t* max_refine_bytes, const char** why);
 
+// A decode call keeps its Mallat planes in int16: the caller's setting (grk_amd_set_decode_planes16) and not the exact repeat of a
+// call that left them, the fused last level, a reversible HT tile of at most 8 bits -- and no segment list on the context: K5c
+// refines the int32 sign-magnitude words K5b leaves in the plane
+bool decode_takes_planes16(bool setting, bool force32, bool fuse_out, const grk_amd_tile_params& p, bool have_segments);
+
 // ---- the Part-1 launch lists -----------------------------------------------------------------------------------------------------
 struct T1PlanIn {
     const grk_amd_coded_block* table; uint64_t nblocks;

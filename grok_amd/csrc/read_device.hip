@@ -20,7 +20,7 @@ struct ReadDevState {
     uint32_t last_why = 0;                              // why the latest status word refused (T2pWhy)
     uint64_t counters[7] = {0, 0, 0, 0, 0, 0, 0};         // [6]: launches of KL-P / KH-P; the located count comes to the host with the status word behind KL-P
     // the general reader (grk_amd_read_packets_device_ex): its own plan and descriptors, the scratch of KC-L, KF and KP
-    bool have_lplan = false;
+    bool have_lplan = false, lplan_refine = false;
     grk_amd_stream_info linfo{};
     T2ReadLayersPlan lplan;
     DevBuf ltiles, lpackets, lpk, nodes32, rstate, seg_log, piece_log, counts, first_seg, app_at, move_first, sums, totals, segments, moves;
@@ -213,14 +213,16 @@ struct ReadExOut {
 };
 
 // parts: tiles divided into tile-parts are read (KL-P, KH-P and KC-L over the part table in the place of KL, KH and KC-L)
-int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, uint64_t have, const ReadExOut& o, bool parts = false)
+// ht_refine: HT blocks' refinement passes are read -- the plan's sizes and the style word KC-L hands the parse core say so
+int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info& info, uint64_t have, const ReadExOut& o, bool parts = false,
+                          bool ht_refine = false)
 {
     ReadDevState* r = state(c);
     const char* pwhy = "";
     HIP_TRY(c, hipStreamSynchronize(c->stream), "sync");          // (the tables below may still be read by an earlier call's kernels)
-    if (!r->have_lplan || std::memcmp(&r->linfo, &info, sizeof info) != 0) {
+    if (!r->have_lplan || r->lplan_refine != ht_refine || std::memcmp(&r->linfo, &info, sizeof info) != 0) {
         r->have_lplan = false;
-        const int rc = plan_t2_read_layers(info, r->lplan, &pwhy);
+        const int rc = plan_t2_read_layers(info, r->lplan, &pwhy, ht_refine);
         if (rc) return fail(c, rc, pwhy);
         const T2ReadLayersPlan& Q = r->lplan;
         HIP_TRY(c, r->ltiles.ensure(Q.base.bytes_tiles()), "alloc the tiles' descriptors");
@@ -230,7 +232,7 @@ int64_t packets_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, const 
         HIP_TRY(c, hipMemcpy(r->lpackets.p, Q.base.packets.data(), Q.base.bytes_packets(), hipMemcpyHostToDevice), "upload the packets' descriptors");
         HIP_TRY(c, hipMemcpy(r->lpk.p, Q.lpk.data(), Q.bytes_lpk(), hipMemcpyHostToDevice), "upload the precincts' descriptors");
         r->counters[1] += Q.base.bytes_tiles() + Q.base.bytes_packets() + Q.bytes_lpk();
-        r->linfo = info; r->have_lplan = true;
+        r->linfo = info; r->have_lplan = true; r->lplan_refine = ht_refine;
     }
     const T2ReadLayersPlan& Q = r->lplan;
     const T2ReadPlan& P = Q.base;
@@ -419,6 +421,19 @@ extern "C" int64_t grk_amd_read_packets_device_parts(grk_amd_ctx* c, const void*
     return packets_device_ex(c, d_cs, len, own, have, ReadExOut{rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes, nullptr, false}, true);
 }
 
+extern "C" int64_t grk_amd_read_packets_device_refine(grk_amd_ctx* c, const void* d_cs, uint64_t len, const grk_amd_stream_info* info, grk_amd_coded_block* rows,
+                                                      uint64_t row_cap, uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                                      grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+{
+    if (!c || !d_cs || !info) return GRK_AMD_ERR_INVALID;
+    grk_amd_stream_info own;
+    uint64_t have = 0;
+    const int rc = header_device(c, d_cs, len, own, &have); if (rc) return rc;
+    if (std::memcmp(&own, info, sizeof own) != 0) return fail(c, GRK_AMD_ERR_INVALID, "info is not what grk_amd_read_header_device gives for this codestream");
+    return packets_device_ex(c, d_cs, len, own, have, ReadExOut{rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes, nullptr, false},
+                             true, true);
+}
+
 extern "C" int grk_amd_decode_image_device_ex(grk_amd_ctx* c, const void* d_cs, uint64_t len, void* pixels, uint64_t cap, int pixels_on_device)
 {
     if (!c || !d_cs || !pixels) return GRK_AMD_ERR_INVALID;
@@ -435,6 +450,13 @@ extern "C" int grk_amd_decode_image_device_ex(grk_amd_ctx* c, const void* d_cs, 
     c->rdev->last_why = 0;
     int64_t n = packets_device_ex(c, d_cs, len, info, have, out);
     if (n == GRK_AMD_ERR_UNSUPPORTED && (c->rdev->last_why == kT2pMultiPart || c->rdev->last_why == kT2pManyParts)) n = packets_device_ex(c, d_cs, len, info, have, out, true);
+    // ... and one that KC-L refuses for an HT block's second pass with the refinement passes read (over the part table: it reads
+    // either kind of file), its segment lists to the host: the decode finds the refinement segments there
+    if (n == GRK_AMD_ERR_UNSUPPORTED && c->rdev->last_why == kT2pHtPasses) {
+        ReadExOut refine = out;
+        refine.tab_segments = true;
+        n = packets_device_ex(c, d_cs, len, info, have, refine, true, true);
+    }
     if (n < 0) return (int)n;
     if (!tab.appendix_bytes) return decode_resident(c, d_cs, len, info, tab, pixels, cap, pixels_on_device);
     return decode_resident_moves(c, d_cs, len, info, tab, (const grk_amd_tp_segment*)c->rdev->moves.p, nmoves, &c->rdev->counters[4], pixels, cap, pixels_on_device);

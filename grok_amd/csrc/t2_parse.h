@@ -38,12 +38,13 @@ enum T2pWhy : uint32_t {
     kT2pNoSop, kT2pZeroPlanes, kT2pHtPasses, kT2pPasses, kT2pLblock, kT2pLenBits, kT2pBlockWrap, kT2pHeaderPast,          // KC
     kT2pNoEph, kT2pBodyPast, kT2pPltSize, kT2pTail, kT2pPart1Planes,
     kT2pTpsot, kT2pTnsot, kT2pPartsOfTile, kT2pPartsOfFile, kT2pPsotZero, kT2pPartPlt, kT2pTileEnds,                       // KL-P, KH-P, the chains' part stepping
+    kT2pHtSet,                                                                                                             // KC-L reading HT refinement passes
     kT2pWhys
 };
 GRK_T2_FN int t2p_code(uint32_t why)
 {
     if (why == kT2pOk) return 0;
-    return why == kT2pMultiPart || why == kT2pManyParts || why == kT2pMarker || why == kT2pHtPasses || why == kT2pPartsOfTile || why == kT2pPartsOfFile
+    return why == kT2pMultiPart || why == kT2pManyParts || why == kT2pMarker || why == kT2pHtPasses || why == kT2pHtSet || why == kT2pPartsOfTile || why == kT2pPartsOfFile
                ? -2 /* GRK_AMD_ERR_UNSUPPORTED */ : -3 /* GRK_AMD_ERR_INVALID */;
 }
 GRK_T2_FN const char* t2p_text(uint32_t why)
@@ -66,6 +67,7 @@ GRK_T2_FN const char* t2p_text(uint32_t why)
     case kT2pNoSop: return "no SOP marker segment with the packet's number";
     case kT2pZeroPlanes: return "zero bit-planes without end";
     case kT2pHtPasses: return "an HT code-block with more than one pass";
+    case kT2pHtSet: return "an HT code-block with more than one pass of a kind (more than 3 passes: placeholder passes or a second HT set)";
     case kT2pPasses: return "more than 164 coding passes";
     case kT2pLblock: return "Lblock beyond 32";
     case kT2pLenBits: return "a length of more than 32 bits";

@@ -36,6 +36,21 @@ struct T2pRowState {
 };
 static_assert(sizeof(T2pRowState) == 4 * kT2pStateWords, "eight words");
 
+// A bit of the `sty` argument above COD's code-block style bits: the HT blocks' refinement passes are read (T.814 over B.10.7.2).  An HT
+// block's passes are one HT set -- Cleanup, SigProp, MagRef, numbered across the layers --, the cleanup pass a codeword segment of its
+// own, SigProp and MagRef the next one's: LAZY's alternation without its first segment of 10.  More than three passes are placeholder
+// passes or a second HT set, whose lengths no encoder or decoder at hand shows how to read: refused (kT2pHtSet), as every pass
+// beyond the first is without the bit (kT2pHtPasses).
+constexpr uint32_t kT2pStyHtRefine = 0x100u;
+constexpr uint32_t kT2pHtSetPasses = 3;
+GRK_T2_FN uint32_t t2p_ht_seg_capacity(uint32_t sty, uint32_t idx) { return (sty & kT2pStyHtRefine) && (idx & 1u) ? 2u : 1u; }
+// kT2pOk, or why an HT block that has `before` passes does not take np more
+GRK_T2_FN uint32_t t2p_ht_passes_why(uint32_t sty, uint32_t before, uint32_t np)
+{
+    if (sty & kT2pStyHtRefine) return before + np > kT2pHtSetPasses ? (uint32_t)kT2pHtSet : (uint32_t)kT2pOk;
+    return np != 1 || before != 0 ? (uint32_t)kT2pHtPasses : (uint32_t)kT2pOk;
+}
+
 // passes a codeword segment holds (B.10.7.2): TERMALL 1; LAZY 10, then 2 and 1 in turn; else all of them
 GRK_T2_FN uint32_t t2p_seg_capacity(uint32_t sty, uint32_t idx)
 {
@@ -47,15 +62,21 @@ GRK_T2_FN uint32_t t2p_seg_capacity(uint32_t sty, uint32_t idx)
 // and a row has 164 at most; a row opens at most t2p_max_segments() segments and every contribution continues one more at most
 GRK_T2_FN uint32_t t2p_max_segments(bool ht, uint32_t sty)
 {
-    if (ht) return 1;
+    if (ht) return (sty & kT2pStyHtRefine) ? 2u : 1u;
     if (sty & 0x04u) return kT2pMaxPasses;
     if (sty & 0x01u) return 1 + 2 * ((kT2pMaxPasses - 10) / 3) + ((kT2pMaxPasses - 10) % 3 ? 1 : 0);         // 10, then 2 and 1 in turn: 104
     return 1;
 }
 GRK_T2_FN uint32_t t2p_max_piece_records(bool ht, uint32_t layers) { return ht ? 1u : layers < kT2pMaxPasses ? layers : kT2pMaxPasses; }
+// ... with the style word's say: an HT block read with its refinement passes contributes in three layers at most
+GRK_T2_FN uint32_t t2p_max_piece_records_sty(bool ht, uint32_t sty, uint32_t layers)
+{
+    if (ht && (sty & kT2pStyHtRefine)) return layers < kT2pHtSetPasses ? layers : kT2pHtSetPasses;
+    return t2p_max_piece_records(ht, layers);
+}
 GRK_T2_FN uint32_t t2p_max_seg_records(bool ht, uint32_t sty, uint32_t layers)
 {
-    const uint64_t n = (uint64_t)t2p_max_segments(ht, sty) + t2p_max_piece_records(ht, layers) - 1;
+    const uint64_t n = (uint64_t)t2p_max_segments(ht, sty) + t2p_max_piece_records_sty(ht, sty, layers) - 1;
     return n < kT2pMaxPasses ? (uint32_t)n : kT2pMaxPasses;
 }
 
@@ -89,7 +110,7 @@ GRK_T2_FN uint32_t t2p_tree_decode32(uint32_t* nodes, uint32_t gw, uint32_t gh, 
 // ---- one packet header of layer `layer` ---------------------------------------------------------------------------------------------
 // The packet `q` (the tile's packet `number` in file order) from pos (advanced to behind the packet's bodies) and not beyond `end`.
 // nodes: the tile's node scratch in 32-bit nodes (q's node_at counts nodes here); state: the tile's rows' state.  *body_at: the end
-// of the header (and of EPH): a piece's source is *body_at + rel.  sty: the code-block style (Part-1).
+// of the header (and of EPH): a piece's source is *body_at + rel.  sty: the code-block style (Part-1), kT2pStyHtRefine (HT).
 template <class Src, class Sink>
 GRK_T2_FN uint32_t t2p_read_packet_layer(Src& src, const T2ReadPacket& q, uint32_t* nodes, T2pRowState* state, bool ht, uint32_t sty, bool sop, bool eph,
                                          uint32_t layer, uint32_t number, uint64_t& pos, uint64_t end, Sink& sink, uint64_t* body_at)
@@ -130,7 +151,7 @@ GRK_T2_FN uint32_t t2p_read_packet_layer(Src& src, const T2ReadPacket& q, uint32
                         else { t = br.bits(5); np = t < 31 ? 6 + t : 37 + br.bits(7); }
                     }
                     GRK_T2P_COUNT(kT2pLoopPasses, np);
-                    if (ht && (np != 1 || passes)) return kT2pHtPasses;
+                    if (ht) { const uint32_t hw = t2p_ht_passes_why(sty, passes, np); if (hw) return hw; }
                     if (passes + np > kT2pMaxPasses) return kT2pPasses;
                     while (br.bit()) if (++lb > kT2pMaxLblock) return kT2pLblock;
                     GRK_T2P_COUNT(kT2pLoopLblock, lb);
@@ -138,7 +159,7 @@ GRK_T2_FN uint32_t t2p_read_packet_layer(Src& src, const T2ReadPacket& q, uint32
                     uint32_t left = np, turns = 0;
                     // (a turn takes at least one pass)
                     for (; left && turns < kT2pMaxPasses; ++turns) {
-                        const uint32_t cap = ht ? 1u : t2p_seg_capacity(sty, seg_idx);
+                        const uint32_t cap = ht ? t2p_ht_seg_capacity(sty, seg_idx) : t2p_seg_capacity(sty, seg_idx);
                         const uint32_t room = cap - seg_fill, k = left < room ? left : room;
                         const uint32_t nb = lb + t2p_floor_log2(k);
                         if (nb > kT2pMaxLenBits) return kT2pLenBits;

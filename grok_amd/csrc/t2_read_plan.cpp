@@ -161,7 +161,7 @@ int grk_amd::plan_t2_read(const grk_amd_stream_info& info, T2ReadPlan& out, cons
     return plan_common(info, out, why, nullptr, 1);
 }
 
-int grk_amd::plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPlan& out, const char** why)
+int grk_amd::plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPlan& out, const char** why, bool ht_refine)
 {
     const char* dummy; if (!why) why = &dummy;
     *why = "";
@@ -170,11 +170,12 @@ int grk_amd::plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPl
     T2ReadPlan& B = out.base;
     B.ht = !info.base.reserved[0];
     out.layers = info.num_layers; out.sty = info.base.reserved[1]; out.order = (info.flags >> GRK_AMD_CS_PROG_SHIFT) & 7u;
+    if (B.ht && ht_refine) out.sty |= kT2pStyHtRefine;         // (the parse core's option travels in the style word)
     const int rc = plan_common(info, B, why, &out.lpk, info.num_layers);
     if (rc) return rc;
     out.segments_per_row = t2p_max_segments(B.ht, out.sty);
     out.seg_records_per_row = t2p_max_seg_records(B.ht, out.sty, out.layers);
-    out.piece_records_per_row = t2p_max_piece_records(B.ht, out.layers);
+    out.piece_records_per_row = t2p_max_piece_records_sty(B.ht, out.sty, out.layers);
     // (node scratch at four bytes a node; the logs' and tables' entries are counted in 32 bits)
     if (B.node_bytes > 0x3FFFFFFFull || B.rows * out.seg_records_per_row > 0x7FFFFFFFull || B.rows * out.piece_records_per_row > 0x7FFFFFFFull ||
         B.rows * out.segments_per_row > 0x7FFFFFFFull) {

@@ -78,8 +78,9 @@ struct T2ReadLayersPlan {
     uint64_t bytes_lpk() const { return (uint64_t)lpk.size() * sizeof(T2ReadLayerPk); }
 };
 // GRK_AMD_OK, or GRK_AMD_ERR_UNSUPPORTED for tables beyond the kernels' 32-bit fields, or a tile's geometry error.  Takes every
-// layer count and code-block style the host reader takes
-int plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPlan& out, const char** why);
+// layer count and code-block style the host reader takes.  ht_refine: an HT block's refinement passes are read (sty carries
+// kT2pStyHtRefine): two segments, min(layers, 3) piece records and their sum less one segment records per row
+int plan_t2_read_layers(const grk_amd_stream_info& info, T2ReadLayersPlan& out, const char** why, bool ht_refine = false);
 
 // ---- locating the tile-parts from TLM (the host's share of KL) ------------------------------------------------------------------------
 // The main header's bytes [0, n) (all of it, to the first SOT) of a stream of `len` bytes: TLM's entries in marker order as

@@ -234,6 +234,8 @@ struct TileCtx {
     std::vector<uint64_t> row0;         // ... and the first of its rows among the tile's
     uint32_t tile;
     bool ht, sop, eph;
+    bool ht_refine;                 // an HT block's refinement passes are read (grk_amd_read_packets_refine)
+    std::atomic<bool>* met_ht_second_pass;      // told of the refusal below
     uint32_t sty;
     BlockState* st;                 // the tile's rows
     std::vector<Pk> seq;            // one layer's packets in order
@@ -248,6 +250,9 @@ inline uint32_t seg_capacity(uint32_t sty, uint32_t idx)
     if (sty & 0x01) return idx == 0 ? 10u : (idx & 1u) ? 2u : 1u;
     return 0xFFFFu;
 }
+// ... of an HT block read with its refinement passes (T.814): its passes are one HT set -- Cleanup, SigProp, MagRef, numbered across
+// the layers --, the cleanup pass a codeword segment of its own, SigProp and MagRef the next one's
+inline uint32_t ht_seg_capacity(bool refine, uint32_t idx) { return refine && (idx & 1u) ? 2u : 1u; }
 inline uint32_t floor_log2(uint32_t v) { uint32_t r = 0; while (v >>= 1) ++r; return r; }
 
 // One packet: seq[i] in layer `layer`, the tile's packet number `number`, from pos (advanced) and not beyond `end`.
@@ -307,15 +312,21 @@ int read_packet(TileCtx& T, uint32_t i, uint32_t layer, uint32_t number, uint64_
                         if (v < 3) np = 3 + v;
                         else { v = br.bits(5); np = v < 31 ? 6 + v : 37 + br.bits(7); }
                     }
-                    if (T.ht && (np != 1 || s.passes))
+                    if (T.ht && !T.ht_refine && (np != 1 || s.passes)) {
+                        T.met_ht_second_pass->store(true, std::memory_order_relaxed);
                         return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "tile %u packet %u: an HT code-block with more than one pass", T.tile, number);
+                    }
+                    // (a fourth pass is a placeholder pass or a second HT set's: how their lengths are signalled nothing at hand shows)
+                    if (T.ht && T.ht_refine && (uint32_t)s.passes + np > 3)
+                        return refuse(err, GRK_AMD_ERR_UNSUPPORTED, "tile %u packet %u: an HT code-block with more than one pass of a kind (%u passes: placeholder passes or a second HT set)",
+                                      T.tile, number, (uint32_t)s.passes + np);
                     if ((uint32_t)s.passes + np > 164) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: more than 164 coding passes", T.tile, number);
                     uint32_t lb = s.lblock;
                     while (br.bit()) if (++lb > 32) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: Lblock beyond 32", T.tile, number);
                     s.lblock = (uint8_t)lb;
                     uint64_t sum = 0;
                     for (uint32_t left = np; left;) {
-                        const uint32_t cap = T.ht ? 1u : seg_capacity(T.sty, s.seg_idx);
+                        const uint32_t cap = T.ht ? ht_seg_capacity(T.ht_refine, s.seg_idx) : seg_capacity(T.sty, s.seg_idx);
                         const uint32_t k = std::min<uint32_t>(left, cap - s.seg_fill);
                         const uint32_t nb = lb + floor_log2(k);
                         if (nb > 32) return refuse(err, GRK_AMD_ERR_INVALID, "tile %u packet %u: a length of %u bits", T.tile, number, nb);
@@ -391,11 +402,12 @@ int64_t tile_rows(const grk_amd_stream_info& info, uint32_t t, grk_amd_tile_para
 // lists exactly its own), precinct by precinct on `threads` threads (a precinct's packets depend on each other through its tag
 // trees and Lblock, on nothing else).  parts[t] is the tile's first tile-part, .next leads to the following ones.
 int read_tile(const Bytes& b, const grk_amd_stream_info& info, uint32_t t, const std::vector<TilePart>& parts, BlockState* st, grk_amd_coded_block* rows,
-              uint32_t threads, uint32_t drop_res, std::vector<Precinct>& keep, std::string& err)
+              uint32_t threads, uint32_t drop_res, bool ht_refine, std::atomic<bool>& met_ht_second_pass, std::vector<Precinct>& keep, std::string& err)
 {
     TileCtx T;
+    T.met_ht_second_pass = &met_ht_second_pass;
     T.b = b; T.info = &info; T.tile = t; T.st = st;
-    T.ht = !info.base.reserved[0]; T.sty = info.base.reserved[1];
+    T.ht = !info.base.reserved[0]; T.sty = info.base.reserved[1]; T.ht_refine = ht_refine;
     T.sop = (info.flags & GRK_AMD_CS_SOP) != 0; T.eph = (info.flags & GRK_AMD_CS_EPH) != 0;
     grk_amd_tile_params p;
     int rc = grk_amd_layout_tile(&info.layout, &info.base, t, &p);
@@ -609,6 +621,7 @@ thread_local std::string g_reader_error;
 
 } // namespace
 
+
 int grk_amd::read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info& info, std::string& err)
 {
     err.clear();
@@ -648,7 +661,7 @@ int grk_amd::read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_
 }
 
 int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err,
-                                 bool allow_parts)
+                                 bool allow_parts, bool ht_refine)
 {
     grk_amd_stream_info own;
     int rc = read_stream_header(cs, len, own, err);
@@ -657,7 +670,7 @@ int grk_amd::read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_
     std::vector<StreamPart> parts;
     rc = allow_parts ? locate_stream_parts(cs, len, info, parts, err) : locate_stream_parts_single(cs, len, info, parts, err);
     if (rc) return rc;
-    return read_stream_packets_of(cs, len, info, parts, nullptr, 0, threads, out, err);
+    return read_stream_packets_of(cs, len, info, parts, nullptr, 0, threads, out, err, ht_refine);
 }
 
 // Every tile-part of the file, each tile's in TPsot order (T.800 A.4.2; the reference: TileLengthMarkers, CodeStreamDecompress's SOT
@@ -749,7 +762,7 @@ int grk_amd::locate_stream_parts_single(const uint8_t* cs, uint64_t len, const g
 }
 
 int grk_amd::read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, const std::vector<StreamPart>& parts,
-                                    const std::vector<uint32_t>* tiles, uint32_t drop_res, uint32_t threads, StreamTable& out, std::string& err)
+                                    const std::vector<uint32_t>* tiles, uint32_t drop_res, uint32_t threads, StreamTable& out, std::string& err, bool ht_refine)
 {
     threads = std::max<uint32_t>(1, std::min<uint32_t>(threads, 16));
     const Bytes b{cs, len};
@@ -773,19 +786,20 @@ int grk_amd::read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_a
     out.rows.assign(nrows, grk_amd_coded_block{0, 0, 0});
     std::vector<BlockState> st(nrows);
     std::vector<std::vector<Precinct>> left(nt);
+    std::atomic<bool> met{false};
     if (nt >= threads || threads == 1) {
         std::mutex mu;
         rc = parallel_for(nt, threads, [&](size_t t) -> int {
             std::string e;
-            const int r = read_tile(b, info, tile_of(t), parts, st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, drop_res, left[t], e);
+            const int r = read_tile(b, info, tile_of(t), parts, st.data() + out.row_at[t], out.rows.data() + out.row_at[t], 1, drop_res, ht_refine, met, left[t], e);
             if (r) { std::lock_guard<std::mutex> lk(mu); if (err.empty()) err = e; }
             return r;
         });
     } else {
         for (uint32_t t = 0; t < nt && !rc; ++t)
-            rc = read_tile(b, info, tile_of(t), parts, st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, drop_res, left[t], err);
+            rc = read_tile(b, info, tile_of(t), parts, st.data() + out.row_at[t], out.rows.data() + out.row_at[t], threads, drop_res, ht_refine, met, left[t], err);
     }
-    if (rc) { if (err.empty()) (void)refuse(err, rc, "the packets cannot be read (%d)", rc); return rc; }
+    if (rc) { if (err.empty()) (void)refuse(err, rc, "the packets cannot be read (%d)", rc); out.met_ht_second_pass = met.load(); return rc; }
     // Segment lists and the appendix, in an order that does not depend on the threads: rows in order, a row's records in the order
     // its precinct met them
     out.first_segment.assign(nrows + 1, 0);
@@ -834,14 +848,14 @@ extern "C" int grk_amd_stream_comp_size(const grk_amd_stream_info* info, uint32_
     return GRK_AMD_OK;
 }
 
-static int64_t read_packets_into(bool allow_parts, const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+static int64_t read_packets_into(bool allow_parts, bool ht_refine, const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
                                  grk_amd_coded_block* rows, uint64_t row_cap,
                                  uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                                  grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
 {
     if (!info) { g_reader_error = "no info"; return GRK_AMD_ERR_INVALID; }
     StreamTable s;
-    const int rc = read_stream_packets(cs, len, *info, threads, s, g_reader_error, allow_parts);
+    const int rc = read_stream_packets(cs, len, *info, threads, s, g_reader_error, allow_parts, ht_refine);
     if (rc) return rc;
     if (num_segments) *num_segments = s.segments.size();
     if (num_moves) *num_moves = s.moves.size();
@@ -862,7 +876,7 @@ extern "C" int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const g
                                         uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                                         grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
 {
-    return read_packets_into(false, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
+    return read_packets_into(false, false, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
 }
 
 extern "C" int64_t grk_amd_read_packets_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
@@ -870,5 +884,13 @@ extern "C" int64_t grk_amd_read_packets_parts(const uint8_t* cs, uint64_t len, c
                                               uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                                               grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
 {
-    return read_packets_into(true, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
+    return read_packets_into(true, false, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
+}
+
+extern "C" int64_t grk_amd_read_packets_refine(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                               grk_amd_coded_block* rows, uint64_t row_cap,
+                                               uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                               grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes)
+{
+    return read_packets_into(true, true, cs, len, info, threads, rows, row_cap, first_segment, segments, seg_cap, num_segments, moves, move_cap, num_moves, appendix_bytes);
 }

@@ -2,6 +2,7 @@
 // vectors, the reason of a refusal in `err`.  grk_amd_read_header / grk_amd_read_packets (include/grok_amd.h) wrap these.
 #pragma once
 #include "../../include/grok_amd.h"
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -17,12 +18,16 @@ struct StreamTable {
     std::vector<grk_amd_segment> segments;
     std::vector<grk_amd_tp_segment> moves;          // dst counted from the start of the appendix
     uint64_t appendix_bytes = 0;
+    // set by a reading that was refused: a tile of it met an HT block's second pass, which only a reading with ht_refine takes
+    // (with several threads the code and the reason returned may be another tile's: this says it of the whole file)
+    bool met_ht_second_pass = false;
 };
 
 int read_stream_header(const uint8_t* cs, uint64_t len, grk_amd_stream_info& info, std::string& err);
-// allow_parts: tiles divided into tile-parts are read (grk_amd_read_packets_parts); else a second tile-part of a tile is refused
+// allow_parts: tiles divided into tile-parts are read (grk_amd_read_packets_parts); else a second tile-part of a tile is refused.
+// ht_refine: an HT block's SigProp and MagRef passes are read (grk_amd_read_packets_refine); else a second pass of an HT block is refused
 int read_stream_packets(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, uint32_t threads, StreamTable& out, std::string& err,
-                        bool allow_parts = false);
+                        bool allow_parts = false, bool ht_refine = false);
 
 // The two halves of read_stream_packets, for a caller that reads some of the tiles (grk_amd_decode_image_view):
 // where every tile's tile-parts lie (TLM, else the Psot chain: no packet is read) ...
@@ -36,7 +41,7 @@ int locate_stream_parts_single(const uint8_t* cs, uint64_t len, const grk_amd_st
 // `len`).  drop_res: blocks of the `drop_res` finest resolutions get no place in the appendix and no moves -- a decode at that
 // reduce never reads their rows
 int read_stream_packets_of(const uint8_t* cs, uint64_t len, const grk_amd_stream_info& info, const std::vector<StreamPart>& parts,
-                           const std::vector<uint32_t>* tiles, uint32_t drop_res, uint32_t threads, StreamTable& out, std::string& err);
+                           const std::vector<uint32_t>* tiles, uint32_t drop_res, uint32_t threads, StreamTable& out, std::string& err, bool ht_refine = false);
 
 } // namespace grk_amd
 #pragma GCC visibility pop

@@ -884,13 +884,15 @@ int64_t grk_amd_locate_tile_parts(const uint8_t* cs, uint64_t len, uint64_t* off
  *                 decode calls that read a file by themselves also take tiles divided into 1..255 tile-parts
  *   packets       the five progression orders, any precinct sizes, 1..N layers, SOP / EPH, empty packets, blocks that are not
  *                 included, tag trees in their general form, Part-1 codeword segments (TERMALL, LAZY) carried on across
- *                 layers, HT blocks with one pass
+ *                 layers, HT blocks with one pass.  grk_amd_read_packets_refine (below) and the decode calls that read a file by
+ *                 themselves also take HT blocks with SigProp and MagRef passes (one HT set: at most 3 passes over all layers)
  *   components    sub-sampled each in its own way (SIZ XRsiz / YRsiz: 4:2:2, 4:2:0, ...): every component of a tile has its own
  *                 rectangle (grk_amd_layout_tile_comp), precinct grid and tag trees, and the position-dependent orders (RPCL,
  *                 PCRL, CPRL) meet its precincts where the factors put them on the reference grid
  * GRK_AMD_ERR_UNSUPPORTED (and the reason in grk_amd_reader_last_error): COC, QCC, RGN, POC, PPM, PPT, PLM, Sqcd style 1, more
- * than one tile-part per tile, components of differing precision or sign, more than 4 components, more than GRK_AMD_MAX_LEVELS
- * levels, HT blocks with more than one pass, a custom MCT.  GRK_AMD_ERR_INVALID: anything malformed -- the input is untrusted:
+ * than one tile-part per tile (grk_amd_read_packets; not _parts, _refine), components of differing precision or sign, more than 4
+ * components, more than GRK_AMD_MAX_LEVELS levels, HT blocks with more than one pass (grk_amd_read_packets, _parts) or with more
+ * than 3 (_refine: placeholder passes, a second HT set), a custom MCT.  GRK_AMD_ERR_INVALID: anything malformed -- the input is untrusted:
  * no byte outside [cs, cs + len) is read, a packet never runs past its tile-part, a length never wraps. */
 typedef struct grk_amd_stream_info {
     grk_amd_image_layout layout;          /* SIZ: image area and tile grid                                                  */
@@ -947,13 +949,32 @@ int64_t grk_amd_read_packets(const uint8_t* cs, uint64_t len, const grk_amd_stre
  * non-zero TNsot of one tile; a TNsot not above a TPsot seen, or above the tile-parts found; a packet that runs past the end of its
  * tile-part; packets left over or missing at the tile's last tile-part; PLT lengths that do not add up to their tile-part; a Psot
  * that leaves the stream; a tile without a tile-part.  GRK_AMD_ERR_UNSUPPORTED: COD / QCD / COC / QCC / RGN / POC / PPT in a
- * tile-part header, a 256th tile-part of a tile, more than 65535 in the file.  grk_amd_read_header's flags describe the first
- * tile-part.  Writing tile-parts is not built: the writers make one per tile. */
+ * tile-part header, a 256th tile-part of a tile, more than 65535 in the file; HT blocks with more than one pass, as
+ * grk_amd_read_packets.  grk_amd_read_header's flags describe the first tile-part. */
 int64_t grk_amd_read_packets_parts(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
                                    grk_amd_coded_block* rows, uint64_t row_cap,
                                    uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                                    grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
-/* why the calling thread's latest grk_amd_read_header / grk_amd_read_packets / grk_amd_read_packets_parts refused ("" after a success) */
+/* grk_amd_read_packets_parts for an HTJ2K codestream whose code-blocks carry REFINEMENT passes (what an HT encoder writes for a
+ * file with quality layers: later layers add SigProp and MagRef to a block's cleanup pass), asked for by name; signature and
+ * contract are grk_amd_read_packets_parts' -- tile-parts included --, which keeps refusing an HT block's second pass, as does
+ * grk_amd_read_packets.  The signalling is T.814's over T.800 B.10.7: an HT block's passes form one HT set, Cleanup, SigProp,
+ * MagRef, numbered across all layers.  The cleanup pass is a codeword segment of its own, SigProp and MagRef share the next one;
+ * a segment's length field has Lblock + floor(log2 k) bits for the k passes of that segment in the contribution, and a segment
+ * filled by two contributions (SigProp in one layer, MagRef in a later one) accumulates its length.  For an HT block:
+ *   rows[i].missing_msbs   the zero bit-planes, as ever
+ *   segments               {Lcup, 1} alone, or {Lcup, 1}, {Lref, 1 | 2}: what grk_amd_set_decode_segments takes for the HT block
+ *                          decoder (a refinement segment of 0 bytes decodes as the cleanup pass alone)
+ *   moves / the appendix   a block whose bytes arrive in more than one layer, exactly as a Part-1 block's
+ * GRK_AMD_ERR_UNSUPPORTED, the reason "... an HT code-block with more than one pass of a kind (N passes: placeholder passes or a
+ * second HT set)": more than 3 passes in a block's first contribution or over all its layers.  Those are placeholder passes or
+ * a second HT set; no encoder or decoder this library was built against writes or reads them, so how their lengths are signalled
+ * is not guessed here.  A Part-1 file is read as grk_amd_read_packets_parts reads it. */
+int64_t grk_amd_read_packets_refine(const uint8_t* cs, uint64_t len, const grk_amd_stream_info* info, uint32_t threads,
+                                    grk_amd_coded_block* rows, uint64_t row_cap,
+                                    uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                    grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
+/* why the calling thread's latest grk_amd_read_header / grk_amd_read_packets / _parts / _refine refused ("" after a success) */
 const char* grk_amd_reader_last_error(void);
 /* Codestream -> pixels (Route C, decode; CodeStreamDecompress::decompress, codestream/CodeStreamDecompress.cpp:450-519).
  * cs: the codestream, host memory.  pixels: the image area, component-major planar, tight (or as grk_amd_set_decode_pixel_layout says; cap >= grk_amd_pixel_bytes of the image), ceil(prec / 8) bytes per sample -- the
@@ -1098,6 +1119,17 @@ int64_t grk_amd_read_packets_device_parts(grk_amd_ctx* ctx, const void* d_cs, ui
                                           grk_amd_coded_block* rows, uint64_t row_cap,
                                           uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
                                           grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
+/* grk_amd_read_packets_device_refine: grk_amd_read_packets_device_parts for an HTJ2K stream whose code-blocks carry refinement
+ * passes, asked for by name: that call's signature and contract.  Field for field what grk_amd_read_packets_refine returns -- the
+ * moves as a set --, or the code that call gives with threads = 1.  The same kernels: the plan sizes the logs for two segments,
+ * min(layers, 3) pieces and their sum less one segment records per row, and KC-L's parse core fills an HT block's segments 1, 2 by
+ * the style word it is handed.  grk_amd_decode_image_device_ex takes such files without a switch: a file that KC-L refuses for
+ * an HT block's second pass is read again this way, the segment lists come to the host, and blocks with a second segment are
+ * refined by K5c on int32 planes; grk_amd_decode_image_device and the other reader calls keep their refusal. */
+int64_t grk_amd_read_packets_device_refine(grk_amd_ctx* ctx, const void* d_cs, uint64_t len, const grk_amd_stream_info* info,
+                                           grk_amd_coded_block* rows, uint64_t row_cap,
+                                           uint32_t* first_segment, grk_amd_segment* segments, uint64_t seg_cap, uint64_t* num_segments,
+                                           grk_amd_tp_segment* moves, uint64_t move_cap, uint64_t* num_moves, uint64_t* appendix_bytes);
 /* The placement kernel with clipping (device pointers; queued on the context's stream): as grk_amd_place_tiles_device, but unit i
  * goes to the SIGNED position (pos[2 i], pos[2 i + 1]) of the destination's planes and only what falls inside img_w x img_h is
  * written (a unit wholly outside: nothing).  channels = 0: ncomp planes; channels != 0: the units and the destination hold
